@@ -84,7 +84,40 @@ def parse_args():
                    help="batches in flight (lynse_hip_flat_search_submit_* / _wait): step i+1 is enqueued before step i is waited "
                         "for; 1 = the blocking entry points (one host round trip per step); 0 = default: 1 on one GPU (the "
                         "kernel durations of the roofline stay undisturbed; in flight gains < 1 %% there), 3 on a sharded collection")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (ids / distances / counts of the batch) to DIR/<name>.npy "
+                        "(rank 0; float64 / float32): the inputs depend on the arguments only, so two builds can be compared output for output")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, out, B, K):
+    """--dump-outputs: the arrays a caller of the timed path receives for the batch — global row ids (`ids.npy`, float64: exact below
+    2**53, an empty slot is 2**64 - 1), distances (`distances.npy`, float32 as returned) and the number of results per query (`counts.npy`) —
+    written from the host copies of `out` (a ShardOutputs).  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the queries is written, and
+    `query_index.npy` names which."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    ids = out.rows[:B].cpu().numpy().view(np.uint64).astype(np.float64)
+    dists = out.dists[:B].cpu().numpy().astype(np.float32)
+    counts = out.counts[:B].cpu().numpy().view(np.uint32).astype(np.float64)
+    qidx = np.arange(B, dtype=np.float64)
+    per_query = K * (8 + 4) + 8 + 8
+    if B * per_query > DUMP_LIMIT_BYTES:
+        sel = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // per_query, replace=False))
+        ids, dists, counts, qidx = ids[sel], dists[sel], counts[sel], qidx[sel]
+    files = []
+    for name, a in (("counts", counts), ("distances", dists), ("ids", ids), ("query_index", qidx)):
+        np.save(d / ("%s.npy" % name), np.ascontiguousarray(a))
+        files.append("%s.npy" % name)
+    return files
 
 
 def gen_block(block: int, rows_in_block: int, dim: int, seed: int, device) -> torch.Tensor:
@@ -307,11 +340,16 @@ def main():
     sh.index.profile_get(reset=True)
     barrier()
     t_start = time.perf_counter()
-    run_steps(args.steps, args.profile_every if (world == 1 and in_flight > 1) else 0)
+    drain_every = args.profile_every if (world == 1 and in_flight > 1) else 0
+    run_steps(args.steps, drain_every)
     barrier()
     elapsed = time.perf_counter() - t_start
     prof = sh.index.profile_get(reset=True)
     sh.index.profile_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the buffers the LAST timed step wrote (a drained step: `out`; a ticket: its own)
+        last = out if (in_flight == 1 or (drain_every and (args.steps - 1) % drain_every == 0)) else outs_default[(args.steps - 1) % in_flight]
+        dumped = dump_outputs(args.dump_outputs, last, B, K)
     # (outside the timed region) latency of ONE blocking batch: the same step through the blocking entry points
     lat_steps = max(1, min(args.steps, 10))
     barrier()
@@ -448,6 +486,8 @@ def main():
         }
         if verify is not None:
             result["verify"] = verify
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
         if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: the other ranks of a sharded run would sit in the barrier)
             result["cpu_baseline"] = cpu_baseline(args, N, D, K, metric)
         if world == 1 and not args.no_configs and metric == 0:
@@ -576,6 +616,9 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
     run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t_start
+    dumped = None
+    if args.dump_outputs and rank == 0 and not getattr(args, "_c4_second", False):   # (the headline collection's last timed step)
+        dumped = dump_outputs(args.dump_outputs, outs[(args.steps - 1) % in_flight], B, K)
     barrier()
     t_lat = time.perf_counter()
     for _ in range(5):
@@ -657,6 +700,8 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
             "tickets": stats,
             "verify": {"tickets_equal_blocking_search": same, "queries": nv, "recall_at_k_vs_exact_top_k_of_the_collection": recall},
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
         if not args.no_cpu_baseline and world == 1 and not getattr(args, "_c4_second", False):
             try:
                 result["cpu_baseline"] = cpu_baseline_ivf(args, N, D, K, nlist, nprobe, KC)
@@ -778,6 +823,9 @@ def run_c5(args, rank, local_rank, world, dev, dist, result_out):
     elapsed = time.perf_counter() - t_start
     prof = sh.index.profile_get(reset=True)
     sh.index.profile_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, outs[(args.steps - 1) % in_flight], B, K)
     barrier()
     t_lat = time.perf_counter()
     for _ in range(5):
@@ -849,6 +897,8 @@ def run_c5(args, rank, local_rank, world, dev, dist, result_out):
             "blocking_ms_per_batch": round(lat_ms, 4),
             "verify": {"tickets_equal_blocking_search": same, "oracle_bit_exact_on_200k_row_sample": bool(exact)},
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
         if not args.no_cpu_baseline and world == 1:
             try:
                 result["cpu_baseline"] = cpu_baseline(args, N, bits, K, metric)

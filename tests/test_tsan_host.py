@@ -35,12 +35,26 @@ def driver():
     return exe
 
 
+def _without_aslr(cmd):
+    """gcc's libtsan expects the program and its libraries inside fixed address ranges and stops with "unexpected memory mapping" on
+    kernels that randomise mmap over more bits (vm.mmap_rnd_bits > 28).  The driver runs with address-space randomisation switched off
+    for its own process (`setarch -R`: a personality flag of that child), as newer sanitizer runtimes arrange for themselves; where
+    setarch is missing or refused the driver runs as it is."""
+    import platform
+    import shutil
+
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True, timeout=60).returncode == 0:
+        return [setarch, platform.machine(), "-R"] + cmd
+    return cmd
+
+
 @pytest.mark.parametrize("scenario", ["readers", "tickets", "ivf", "comm1", "dead_peer"])
 def test_host_state_machine_under_threadsanitizer(driver, scenario):
     env = dict(os.environ)
     env["LYNSE_HIP_RCCL_PATH"] = str(OUT / "librcclstub.so")
     env["TSAN_OPTIONS"] = "halt_on_error=0 second_deadlock_stack=1"
-    p = subprocess.run([str(driver), scenario], env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run(_without_aslr([str(driver), scenario]), env=env, capture_output=True, text=True, timeout=600)
     assert "ThreadSanitizer" not in p.stderr, p.stderr[-6000:]
     assert "CHECK FAILED" not in p.stderr, p.stderr[-3000:]
     assert p.returncode == 0, p.stderr[-3000:]
