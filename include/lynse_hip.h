@@ -281,6 +281,38 @@ int lynse_hip_ivf_load_binary(const float *rows, uint64_t n, uint32_t dim, const
                               const float *thresholds, int device, lynse_hip_ivf **out);
 /* Fitted BinaryQuantizer state of a binary index: thresholds[dim], already_binary flag. */
 int lynse_hip_ivf_thresholds(const lynse_hip_ivf *h, float *thresholds, int *already_binary);
+/* IVF-{IP,L2,COS}-SQ8 (src/index/mod.rs:361-375; IVFIndex with QuantizerType::Scalar, ivf.rs:132-337; ScalarQuantizer,
+ * quantizer/mod.rs:110-250).  ip / l2 / cosine only.
+ *  - fit: per dimension min from f32::MAX and max from f32::MIN with strict < / > over all rows (NaN never wins),
+ *    scale = (max - min) / 255 in f32, 1.0 where max == min (NOT the FLAT SQ8 scale 255 / range);
+ *  - encode: ((v - min) / scale) clamped to [0, 255], truncated (NaN -> 0, +inf -> 255); decode: fl(fl(code * scale) + min);
+ *  - build: k-means (train_for_metric, routing metric = index metric) on decode(encode(rows)); the slab store holds those
+ *    decoded rows, the original f32 rows are kept beside them in HBM (twice the footprint of IVF-Flat, as the reference
+ *    keeps data + encoded_data);
+ *  - search (lynse_hip_ivf_search_f32 / _search_filtered_f32 / _search_f32_device): the query is encoded and decoded, the
+ *    pool = min(max(10 k, k), |candidates|) best candidates by the distance of DECODED query and rows (the ordinary IVF
+ *    search with k = pool: same probe rule, empty-probe fallback and subset), then rescored with compute_distance_f32 on the
+ *    ORIGINAL query and rows; the best min(k, pool) come back with their exact distances.  Ties at BOTH cuts are pinned by the
+ *    canonical (distance, original row) key — the reference's quickselect / sort_unstable leave them unpinned;
+ *  - insert encodes with the fitted quantizer (no refit: values outside the range clamp) and assigns the decoded rows; delete
+ *    reassigns the decoded rows that are left;
+ *  - refused with LYNSE_ERR_UNSUPPORTED on an SQ8 handle: lynse_hip_ivf_search_metric_f32 (IvfFlatMmap semantics),
+ *    lynse_hip_ivf_search_submit_f32_device (tickets), lynse_hip_ivf_search_sharded_f32_device and lynse_hip_ivf_set_row_map
+ *    with a non-identity map (an SQ8 index is not row-sharded); there is no device-resident (_device) or sharded build /
+ *    load of an SQ8 index.
+ * lynse_hip_ivf_load_sq8 is the twin of lynse_hip_ivf_load_binary: `rows` are the ORIGINAL rows, `mins` / `scales` (dim each)
+ * the quantizer; lynse_hip_ivf_sq8_params returns the fitted one. */
+int lynse_hip_ivf_build_sq8(const float *rows, uint64_t n, uint32_t dim, uint32_t nlist, uint32_t max_iter, int metric,
+                            int device, lynse_hip_ivf **out);
+int lynse_hip_ivf_load_sq8(const float *rows, uint64_t n, uint32_t dim, const float *centroids, uint32_t nlist,
+                           const uint32_t *assignments, const float *mins, const float *scales, int metric, int device,
+                           lynse_hip_ivf **out);
+int lynse_hip_ivf_sq8_params(const lynse_hip_ivf *h, float *mins, float *scales);
+/* No reference counterpart (QueryProfile.rerank_us, src/engine.rs:6906-6919, is what it feeds): with lynse_hip_ivf_profile_enable on,
+ * the SQ8 searches timed so far and their summed stage times in microseconds, from HIP events on the search stream:
+ * out3[0] searches, out3[1] the pool stage (after the query codec -> after the pool stage), out3[2] the rerank (k_ivfsq_rerank, plus
+ * the host selection of a pool beyond 16,384).  reset != 0 clears them. */
+int lynse_hip_ivf_sq8_stage_times(lynse_hip_ivf *h, double *out3, int reset);
 /* IVFIndex::insert (src/index/ivf.rs:392-441): `rows` (n x dim f32; a binary index pushes them through its quantizer) are
  * assigned to the EXISTING centroids with the routing metric (every centroid in ascending order, strictly better wins) and
  * appended behind the rows already indexed (new row ids old_len .. old_len + n - 1); no retraining.

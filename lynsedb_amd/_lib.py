@@ -114,6 +114,10 @@ SIGNATURES = {
     "lynse_hip_ivf_search_sharded_f32_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "lynse_hip_ivf_delete_rows": (C.c_int, [_vp, _vp, C.c_uint64]),
     "lynse_hip_ivf_assign_f32": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "lynse_hip_ivf_build_sq8": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_ivf_load_sq8": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_ivf_sq8_params": (C.c_int, [_vp, _vp, _vp]),
+    "lynse_hip_ivf_sq8_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
     "lynse_hip_comm_load_rccl": (C.c_int, [C.c_char_p]),
     "lynse_hip_comm_unique_id": (C.c_int, [_vp]),
     "lynse_hip_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -72,6 +72,19 @@ def metric_from_index_mode(mode: str) -> int:
     return out.value
 
 
+def ivf_quantizer_of(mode: str) -> Optional[str]:
+    """The quantizer an `IVF-*` index mode names (src/index/mod.rs:361-385): None for IVF-Flat and the binary modes (their
+    quantizer follows from the metric), "sq8" for IVF-{IP,L2,COS,COSINE}-SQ8 (ip / l2 / cosine only); PQ is not built."""
+    parts = str(mode).upper().split("-")
+    if "PQ" in parts:
+        raise NotImplementedError("quantized IVF variants other than SQ8 (PQ) are outside this path")
+    if "SQ8" in parts:
+        if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
+            raise NotImplementedError(f"{mode}: IVF-*-SQ8 is defined for ip / l2 / cosine")
+        return "sq8"
+    return None
+
+
 def _f32(a, ndim: int, what: str) -> np.ndarray:
     a = np.asarray(a)
     if a.dtype != np.float32:
@@ -406,9 +419,10 @@ class IvfFlatIndex:
     """`lynse._core.IvfFlatIndex` (src/python/mod.rs:2056-2156): k-means partitions, rows stored as
     contiguous per-partition slabs in HBM, search scans the nprobe nearest slabs."""
 
-    def __init__(self, handle, dim: int):
+    def __init__(self, handle, dim: int, sq8: bool = False):
         self._h = handle
         self._dim = dim
+        self._sq8 = sq8
 
     def profile_enable(self, on=True) -> None:
         check(lib.lynse_hip_ivf_profile_enable(self._h, int(on)))
@@ -426,17 +440,24 @@ class IvfFlatIndex:
 
     @staticmethod
     def build(path, data, dim: int, n_partitions: int = 256, n_iters: int = 20, metric: str = "ip",
-              device: Optional[int] = None, l2_partitions: bool = True) -> "IvfFlatIndex":
+              device: Optional[int] = None, l2_partitions: bool = True, quantizer: Optional[str] = None) -> "IvfFlatIndex":
+        """`quantizer="sq8"`: the IVF-{IP,L2,COS}-SQ8 IVFIndex (ivf.rs:132-337 with QuantizerType::Scalar) — k-means and the list scans
+        on the decoded rows, an exact rerank of a 10 k pool against the original rows (ip / l2 / cosine)."""
         m = metric if isinstance(metric, int) else metric_from_str(metric)
         a = _f32(data, 2, "data")
         if a.shape[1] != dim:
             raise ValueError(f"data dimension mismatch: expected {dim}, got {a.shape[1]}")
         if n_partitions <= 0:
             raise IOError("IVF partition count must be greater than zero")
-        if a.shape[0] < n_partitions:
+        if quantizer is not None and str(quantizer).lower() != "sq8":
+            raise NotImplementedError(f"IVF quantizer {quantizer!r} is outside this path (sq8 and the binary metrics are built)")
+        if a.shape[0] < n_partitions and quantizer is None:
             raise IOError("IVF requires at least as many vectors as partitions")
         h = C.c_void_p()
         dev = default_device() if device is None else int(device)
+        if quantizer is not None:   # an IVFIndex mode: k-means clamps the list count to the rows (kmeans.rs:74-139)
+            check(lib.lynse_hip_ivf_build_sq8(_ptr(a), a.shape[0], dim, n_partitions, n_iters, m, dev, C.byref(h)))
+            return IvfFlatIndex(h, dim, sq8=True)
         if m >= 3:  # IVF-HAMMING/JACCARD-BINARY (src/index/mod.rs:376-385) is an IVFIndex mode: no IvfFlat L2 cells
             l2_partitions = False
         check(lib.lynse_hip_ivf_build(_ptr(a), a.shape[0], dim, n_partitions, n_iters, m,
@@ -526,6 +547,41 @@ class IvfFlatIndex:
         if ivfflat_routing:
             check(lib.lynse_hip_ivf_set_routing(h, 1))
         return idx
+
+    @staticmethod
+    def load_sq8(data, centroids, assignments, mins, scales, metric: str = "ip", device: Optional[int] = None) -> "IvfFlatIndex":
+        """The twin of `load` for IVF-*-SQ8: `data` are the ORIGINAL rows, (`mins`, `scales`) the ScalarQuantizer state
+        (`sq8_params()` of a built index); the index stores decode(encode(data)) in the lists given by `assignments`."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        a = _f32(data, 2, "data")
+        c = _f32(centroids, 2, "centroids")
+        asg = np.ascontiguousarray(assignments, dtype=np.uint32)
+        mn, sc = _f32(mins, 1, "mins"), _f32(scales, 1, "scales")
+        if mn.size != a.shape[1] or sc.size != a.shape[1]:
+            raise ValueError("quantizer dimension mismatch")
+        h = C.c_void_p()
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_ivf_load_sq8(_ptr(a), a.shape[0], a.shape[1], _ptr(c), c.shape[0], _ptr(asg), _ptr(mn), _ptr(sc), m, dev,
+                                         C.byref(h)))
+        return IvfFlatIndex(h, a.shape[1], sq8=True)
+
+    def sq8_params(self):
+        """SQ8 index: the fitted ScalarQuantizer (min_val f32[dim], scale f32[dim]; scale = range / 255, 1.0 for a constant dimension)."""
+        mn = np.empty(self._dim, np.float32)
+        sc = np.empty(self._dim, np.float32)
+        check(lib.lynse_hip_ivf_sq8_params(self._h, _ptr(mn), _ptr(sc)))
+        return mn, sc
+
+    def sq8_stage_times(self, reset: bool = True) -> dict:
+        """SQ8 index with profiling on (`profile_enable`): searches timed and the summed microseconds of the pool stage and of the
+        rerank, from HIP events on the search stream (`lynse_hip_ivf_sq8_stage_times`)."""
+        out = np.zeros(3, np.float64)
+        check(lib.lynse_hip_ivf_sq8_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "pool_us": float(out[1]), "rerank_us": float(out[2])}
+
+    @property
+    def is_sq8(self) -> bool:
+        return self._sq8
 
     def __len__(self) -> int:
         return int(lib.lynse_hip_ivf_len(self._h))
@@ -831,9 +887,8 @@ class Collection:
                 raise NotImplementedError("PQ / RaBitQ / PolarVec flat modes are outside this path (SURVEY.md §2)")
             self._ivf = None
         elif mode.startswith("IVF"):
-            if any(t in mode.split("-") for t in ("SQ8", "PQ")):
-                raise NotImplementedError("quantized IVF variants are outside this path")
-            self._ivf_params = {"n_clusters": int(params.get("n_clusters", 256))}
+            quantizer = ivf_quantizer_of(mode)
+            self._ivf_params = {"n_clusters": int(params.get("n_clusters", 256)), "quantizer": quantizer}
             self._ivf_nprobe = int(params.get("nprobe", 32))
             self._index_mode, self._metric = mode, metric
             self._build_ivf()
@@ -847,7 +902,8 @@ class Collection:
         nlist = min(self._ivf_params["n_clusters"], max(n, 1))
         # the metric id goes through as it is: binary metrics build the IVF-*-BINARY mode, float metrics an IVFIndex
         # trained with its routing metric (ivf.rs:163-170)
-        self._ivf = IvfFlatIndex.build(None, data, self._dim, nlist, 20, int(self._metric), device=self._device, l2_partitions=False)
+        self._ivf = IvfFlatIndex.build(None, data, self._dim, nlist, 20, int(self._metric), device=self._device, l2_partitions=False,
+                                       quantizer=self._ivf_params.get("quantizer"))
         self._ivf_rows = n
 
     def _use_sq8(self) -> bool:  # Collection::resolve_use_sq8 (engine.rs:4684-4689)
@@ -937,13 +993,18 @@ class Collection:
             filter_matches = int(self._subset_rows(subset).size)
             filter_us = int((time.perf_counter() - t0) * 1e6)
         target = self._ivf if self._ivf is not None else self._flat
+        sq8 = self._ivf is not None and self._ivf.is_sq8
         target.profile_enable(True)
         target.profile_get(reset=True)
+        if sq8:
+            self._ivf.sq8_stage_times(reset=True)
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
         finally:
             dev = target.profile_get(reset=True)
+            # IVF-*-SQ8: the exact rerank of the pool (HIP events on the search stream); 0 for the modes without one
+            rerank_us = int(self._ivf.sq8_stage_times(reset=True)["rerank_us"]) if sq8 else 0
             target.profile_enable(False)
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
@@ -951,7 +1012,7 @@ class Collection:
                    "index_path": "ann_index" if self._ivf is not None else ("flat_mmap_filtered" if subset is not None else "flat_mmap"),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
-                   "filter_us": filter_us, "search_us": search_us, "rerank_us": 0, "total_us": int((time.perf_counter() - started) * 1e6),
+                   "filter_us": filter_us, "search_us": search_us, "rerank_us": rerank_us, "total_us": int((time.perf_counter() - started) * 1e6),
                    "device": {"pipeline_us": float(dev["total_us"]), "scan_us": float(dev["scan_us"]), "scan_launches": int(dev["scan_launches"]),
                               "scan_rows": int(dev["scan_rows"]), "scan_bytes": int(dev["scan_bytes"]), "rescored_candidates": int(dev["pool_entries"]),
                               "fallback_queries": int(dev["fallback_queries"]), "plan": int(dev["last_plan"])}}

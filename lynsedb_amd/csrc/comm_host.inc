@@ -293,6 +293,10 @@ extern "C" int lynse_hip_ivf_search_sharded_f32_device(lynse_hip_ivf* h, lynse_h
     if (!h || !c) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     if (nq == 0) return LYNSE_OK;
     if (!d_queries || !d_out_counts || (k && (!d_out_rows || !d_out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    {
+        IVF_GUARD(h);
+        if (h->sq8) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index is not row-sharded");
+    }
     LY_TRY(comm_check_alive(c));
     std::lock_guard<std::mutex> lk(c->mu);
     LY_HIP(hipSetDevice(c->device));

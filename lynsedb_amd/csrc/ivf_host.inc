@@ -57,6 +57,27 @@ struct lynse_hip_ivf {
     int already_binary = 0;
     std::vector<float> bq_thr;        // dim per-dimension thresholds (0.5 everywhere for {0,1} corpora)
     float* d_bq_thr = nullptr;
+    // IVF-{IP,L2,COS}-SQ8 (ivf.rs:132-337 with QuantizerType::Scalar): `store` holds the DECODED rows (the pool stage is the
+    // ordinary IVF scan over them), d_raw the original f32 rows in ORIGINAL row order for the exact rerank
+    bool sq8 = false;
+    std::vector<float> sq_min, sq_scale;  // fitted ScalarQuantizer: min_val, scale = range / 255
+    float* d_sq = nullptr;            // [min | scale] on the device (2 x dim)
+    float* d_raw = nullptr;           // n x dim original rows
+    struct Sq8Scratch {               // per-search buffers of the SQ8 path (grown on demand; searches hold the guard)
+        float* d_q = nullptr; size_t q_cap = 0;
+        uint64_t* d_prow = nullptr; size_t prow_cap = 0;
+        float* d_pdist = nullptr; size_t pdist_cap = 0;
+        uint32_t* d_pcnt = nullptr; size_t pcnt_cap = 0;
+        uint64_t* d_keys = nullptr; size_t keys_cap = 0;
+        uint64_t* d_orow = nullptr; size_t orow_cap = 0;
+        float* d_odist = nullptr; size_t odist_cap = 0;
+        uint32_t* d_ocnt = nullptr; size_t ocnt_cap = 0;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // profiling: after the query codec / after the pool stage / after the rerank
+    } sq;
+    // profiling (lynse_hip_ivf_sq8_stage_times): searches timed, and the pool stage / the rerank in microseconds (HIP events on the
+    // search stream; the host selection of a pool beyond the LDS counts to the rerank)
+    uint64_t sq_searches = 0;
+    double sq_pool_us = 0.0, sq_rerank_us = 0.0;
     lynse_hip_flat* cstore = nullptr; // the centroid matrix as a FLAT shard: exact routing = its top-nprobe search
     uint32_t* d_smask = nullptr;      // subset filter by slab position
     uint64_t smask_words = 0;
@@ -87,8 +108,12 @@ static void ivf_free(lynse_hip_ivf* h) {
     if (!h) return;
     if (h->store) {
         (void)hipSetDevice(h->store->device);
-        for (void* p : {(void*)h->d_orig, (void*)h->d_offsets, (void*)h->d_centroids, (void*)h->d_rdims, (void*)h->d_bq_thr, (void*)h->d_smask})
+        for (void* p : {(void*)h->d_orig, (void*)h->d_offsets, (void*)h->d_centroids, (void*)h->d_rdims, (void*)h->d_bq_thr, (void*)h->d_smask,
+                        (void*)h->d_sq, (void*)h->d_raw, (void*)h->sq.d_q, (void*)h->sq.d_prow, (void*)h->sq.d_pdist, (void*)h->sq.d_pcnt,
+                        (void*)h->sq.d_keys, (void*)h->sq.d_orow, (void*)h->sq.d_odist, (void*)h->sq.d_ocnt})
             if (p) (void)hipFree(p);
+        for (hipEvent_t e : h->sq.ev)
+            if (e) (void)hipEventDestroy(e);
         for (auto& x : h->scr) x.release();
         if (h->cstore) lynse_hip_flat_destroy(h->cstore);
         lynse_hip_flat_destroy(h->store);
@@ -110,6 +135,7 @@ extern "C" uint32_t lynse_hip_ivf_nlist(const lynse_hip_ivf* h) { return h ? h->
 extern "C" int lynse_hip_ivf_set_row_map(lynse_hip_ivf* h, uint64_t stride, uint64_t offset) {
     if (!h || stride == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "bad row map");
     IVF_GUARD(h);   // (searches read the row map under the guard)
+    if (h->sq8 && (stride != 1 || offset != 0)) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index is not row-sharded");
     h->row_stride = stride;
     h->row_offset = offset;
     return LYNSE_OK;
@@ -702,6 +728,137 @@ extern "C" int lynse_hip_ivf_load_device(const float* d_rows, uint64_t n, uint32
     return ivf_assemble(d_rows, n, dim, centroids, nlist, assignments, metric, 0, device, out, true);
 }
 
+// ---------------------------------------------------------------------------- IVF-*-SQ8 ----
+// IVFIndex with QuantizerType::Scalar (ivf.rs:132-337, ScalarQuantizer quantizer/mod.rs:110-250): the quantizer is fitted on
+// all rows, k-means (train_for_metric, routing metric = index metric) runs on decode(encode(rows)), the slab store holds those
+// decoded rows — the pool stage of a search is the ordinary IVF scan over them with k = pool — and the original f32 rows stay
+// in HBM (d_raw, original row order) for the exact rerank.  Kernels: k_ivfsq_* (kernels.h).
+
+// ScalarQuantizer::fit over n rows in HBM (n > 0): mins, scales
+static int sq_fit_device(const float* d_v, uint64_t n, uint32_t dim, std::vector<float>* mins, std::vector<float>* scales) {
+    const uint32_t strips = (uint32_t)std::min<uint64_t>(n, 1024);
+    float* d_p = nullptr;
+    struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_p};
+    LY_HIP(hipMalloc(&d_p, ((size_t)strips * 2 + 2) * dim * 4));
+    float* d_o = d_p + (size_t)strips * 2 * dim;
+    hipLaunchKernelGGL(k_ivfsq_minmax, dim3((dim + 255) / 256, strips), dim3(256), 0, 0, d_v, dim, n, d_p, d_p + (size_t)strips * dim);
+    hipLaunchKernelGGL(k_ivfsq_fit, dim3((dim + 255) / 256), dim3(256), 0, 0, d_p, d_p + (size_t)strips * dim, dim, strips, d_o, d_o + dim);
+    LY_HIP(hipGetLastError());
+    std::vector<float> o((size_t)dim * 2);
+    LY_HIP(hipMemcpy(o.data(), d_o, (size_t)dim * 8, hipMemcpyDeviceToHost));
+    mins->assign(o.begin(), o.begin() + dim);
+    scales->assign(o.begin() + dim, o.end());
+    return LYNSE_OK;
+}
+
+// encode -> decode of n rows (HBM -> HBM, in place allowed) with the quantizer d_sq = [min | scale]
+static int sq_codec_device(const float* d_in, uint64_t n, uint32_t dim, const float* d_sq, float* d_out, hipStream_t st) {
+    if (n == 0) return LYNSE_OK;
+    const uint64_t total = n * dim;
+    hipLaunchKernelGGL(k_ivfsq_codec, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 8192)), dim3(256), 0, st,
+                       d_in, n, dim, d_sq, d_sq + dim, d_out, (uint8_t*)nullptr);
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
+
+// decode(encode(rows)) of host rows for an SQ8 index (host copy): the routing space of insert / assign
+static int sq_decode_host(const lynse_hip_ivf* h, const float* rows, uint64_t n, std::vector<float>* dec, float** d_keep = nullptr) {
+    dec->resize((size_t)n * h->dim);
+    if (n == 0) return LYNSE_OK;
+    LY_HIP(hipSetDevice(h->store->device));   // (h->d_sq lives on the index's device, whatever the calling thread's current one is)
+    float* d_v = nullptr;
+    struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_v};
+    LY_HIP(hipMalloc(&d_v, (size_t)n * h->dim * 8));
+    LY_TRY(h2d_done(d_v, rows, (size_t)n * h->dim * 4));
+    LY_TRY(sq_codec_device(d_v, n, h->dim, h->d_sq, d_v + (size_t)n * h->dim, 0));
+    LY_HIP(hipMemcpy(dec->data(), d_v + (size_t)n * h->dim, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost));
+    if (d_keep) { *d_keep = d_v; d_v = nullptr; }   // (the caller takes the buffer: originals first, decoded rows behind them)
+    return LYNSE_OK;
+}
+
+// the common part of build_sq8 / load_sq8: original rows uploaded, quantizer on the device, decoded rows beside them
+static int sq_prepare(const float* rows, uint64_t n, uint32_t dim, const float* mins_in, const float* scales_in, int device,
+                      float** d_raw, float** d_dec, float** d_sq, std::vector<float>* mins, std::vector<float>* scales) {
+    LY_HIP(hipSetDevice(device));
+    LY_HIP(hipMalloc(d_raw, std::max<size_t>((size_t)n * dim * 4, 4)));
+    LY_HIP(hipMalloc(d_dec, std::max<size_t>((size_t)n * dim * 4, 4)));
+    LY_HIP(hipMalloc(d_sq, (size_t)dim * 8));
+    if (n) LY_TRY(h2d_done(*d_raw, rows, (size_t)n * dim * 4));
+    if (mins_in) {
+        mins->assign(mins_in, mins_in + dim);
+        scales->assign(scales_in, scales_in + dim);
+    } else {
+        LY_TRY(sq_fit_device(*d_raw, n, dim, mins, scales));
+    }
+    LY_TRY(h2d_done(*d_sq, mins->data(), (size_t)dim * 4));
+    LY_TRY(h2d_done(*d_sq + dim, scales->data(), (size_t)dim * 4));
+    LY_TRY(sq_codec_device(*d_raw, n, dim, *d_sq, *d_dec, 0));
+    LY_HIP(hipStreamSynchronize(nullptr));
+    return LYNSE_OK;
+}
+
+static int ivf_sq8_common(const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t nlist, const uint32_t* assignments,
+                          const float* mins_in, const float* scales_in, uint32_t max_iter, int metric, int device, lynse_hip_ivf** out) {
+    if (metric != M_IP && metric != M_L2 && metric != M_COS)
+        return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF-*-SQ8 is defined for ip / l2 / cosine");
+    if (n == 0) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "no vectors to index");   // ScalarQuantizer::fit: empty training data
+    float *d_raw = nullptr, *d_dec = nullptr, *d_sq = nullptr;
+    struct G { float*& a; float*& b; float*& c; ~G() { for (float* p : {a, b, c}) if (p) (void)hipFree(p); } } g{d_raw, d_dec, d_sq};
+    std::vector<float> mins, scales, cen;
+    std::vector<uint32_t> asg;
+    LY_TRY(sq_prepare(rows, n, dim, mins_in, scales_in, device, &d_raw, &d_dec, &d_sq, &mins, &scales));
+    if (!centroids) {   // train_for_metric on the decoded rows (ivf.rs:163-170)
+        uint32_t k = 0;
+        LY_TRY(ivf_kmeans(d_dec, n, dim, nlist, max_iter, metric, device, &cen, &asg, &k, true));
+        if (k == 0) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "no vectors to index");
+        nlist = k;
+        centroids = cen.data();
+        assignments = asg.data();
+    }
+    LY_TRY(ivf_assemble(d_dec, n, dim, centroids, nlist, assignments, metric, 0, device, out, true));
+    lynse_hip_ivf* h = *out;
+    h->sq8 = true;
+    h->sq_min = std::move(mins);
+    h->sq_scale = std::move(scales);
+    std::swap(h->d_sq, d_sq);
+    std::swap(h->d_raw, d_raw);
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_ivf_build_sq8(const float* rows, uint64_t n, uint32_t dim, uint32_t nlist, uint32_t max_iter, int metric, int device,
+                                       lynse_hip_ivf** out) {
+    LY_TRY(ivf_check_args(rows, n, dim, nlist, metric, out));
+    return ivf_sq8_common(rows, n, dim, nullptr, nlist, nullptr, nullptr, nullptr, max_iter, metric, device, out);
+}
+
+extern "C" int lynse_hip_ivf_load_sq8(const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t nlist,
+                                      const uint32_t* assignments, const float* mins, const float* scales, int metric, int device,
+                                      lynse_hip_ivf** out) {
+    LY_TRY(ivf_check_args(rows, n, dim, nlist, metric, out));
+    if (!centroids || (!assignments && n) || !mins || !scales) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    return ivf_sq8_common(rows, n, dim, centroids, nlist, assignments, mins, scales, 0, metric, device, out);
+}
+
+extern "C" int lynse_hip_ivf_sq8_params(const lynse_hip_ivf* h, float* mins, float* scales) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "not an IVF-*-SQ8 index");
+    IVF_GUARD(h);
+    if (!h->sq8) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "not an IVF-*-SQ8 index");
+    if (mins) memcpy(mins, h->sq_min.data(), h->sq_min.size() * 4);
+    if (scales) memcpy(scales, h->sq_scale.data(), h->sq_scale.size() * 4);
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_ivf_sq8_stage_times(lynse_hip_ivf* h, double* out3, int reset) {
+    if (!h || !out3) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    IVF_GUARD(h);
+    if (!h->sq8) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "not an IVF-*-SQ8 index");
+    out3[0] = (double)h->sq_searches;
+    out3[1] = h->sq_pool_us;
+    out3[2] = h->sq_rerank_us;
+    if (reset) { h->sq_searches = 0; h->sq_pool_us = 0.0; h->sq_rerank_us = 0.0; }
+    return LYNSE_OK;
+}
+
 // ------------------------------------------------------------------- incremental insert / delete ----
 // IVFIndex::insert (ivf.rs:392-441): new vectors go through the quantizer (binary modes), are assigned to the EXISTING
 // centroids with the routing metric — compute_distance_f32 against every centroid in ascending order, strictly-better wins —
@@ -734,9 +891,10 @@ extern "C" int lynse_hip_ivf_assign_f32(lynse_hip_ivf* h, const float* rows, uin
     IVF_GUARD(h);   // (insert / delete replace the centroid store too)
     if (!h->store || !h->cstore) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
     if (n && (!rows || !out_assignments)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!h->binary) return ivf_assign_rows(h, rows, n, out_assignments);
+    if (!h->binary && !h->sq8) return ivf_assign_rows(h, rows, n, out_assignments);
     std::vector<float> enc;
-    ivf_encode_rows(h, rows, n, &enc);
+    if (h->sq8) LY_TRY(sq_decode_host(h, rows, n, &enc));
+    else ivf_encode_rows(h, rows, n, &enc);
     return ivf_assign_rows(h, enc.data(), n, out_assignments);
 }
 
@@ -756,7 +914,9 @@ static int ivf_rows_in_original_order(lynse_hip_ivf* h, std::vector<float>* out)
 }
 
 // replace the device structures of `h` with a fresh assembly over (rows, assignments) under the SAME centroids / settings
-static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint64_t n, const std::vector<uint32_t>& asg, const IvfRowSource* rs = nullptr) {
+// (new_raw: an SQ8 index's original rows for the new assembly, n x dim in original row order; owned by the index on success)
+static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint64_t n, const std::vector<uint32_t>& asg, const IvfRowSource* rs = nullptr,
+                          float* new_raw = nullptr) {
     lynse_hip_ivf* fresh = nullptr;
     const int device = h->store->device;
     LY_TRY(ivf_assemble(rs ? nullptr : rows.data(), n, h->dim, h->centroids.data(), h->nlist, asg.data(), h->metric, h->ivfflat_routing, device, &fresh, false, rs));
@@ -766,6 +926,13 @@ static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint
     if (h->binary) {
         const int rc = ivf_set_thresholds(fresh, h->bq_thr, h->already_binary);
         if (rc != LYNSE_OK) { ivf_free(fresh); return rc; }
+    }
+    if (h->sq8) {   // the quantizer moves over unchanged (insert does not refit, ivf.rs:392-441); the new original rows come with the call
+        fresh->sq8 = true;
+        fresh->sq_min = h->sq_min; fresh->sq_scale = h->sq_scale;
+        std::swap(fresh->d_sq, h->d_sq);
+        fresh->d_raw = new_raw;
+        fresh->sq_searches = h->sq_searches; fresh->sq_pool_us = h->sq_pool_us; fresh->sq_rerank_us = h->sq_rerank_us;
     }
     // (profiling state of the old store carries over: it used to be dropped silently)
     fresh->store->profiling = h->store->profiling.load();
@@ -799,6 +966,18 @@ extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uin
     std::vector<float> enc_new;
     const float* routed = rows;
     if (h->binary) { ivf_encode_rows(h, rows, n, &enc_new); routed = enc_new.data(); }
+    float* new_raw = nullptr;   // SQ8: the original rows of the grown index (old ones + the new ones, original row order)
+    struct FreeRaw { float*& p; ~FreeRaw() { if (p) (void)hipFree(p); } } fraw{new_raw};
+    if (h->sq8) {   // encode with the FITTED quantizer (no refit: values outside its range clamp), route the decoded rows
+        float* d_new = nullptr;
+        struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_new};
+        LY_HIP(hipSetDevice(h->store->device));
+        LY_TRY(sq_decode_host(h, rows, n, &enc_new, &d_new));
+        routed = enc_new.data();
+        LY_HIP(hipMalloc(&new_raw, (size_t)(old_n + n) * h->dim * 4));
+        if (old_n) LY_HIP(hipMemcpy(new_raw, h->d_raw, (size_t)old_n * h->dim * 4, hipMemcpyDeviceToDevice));
+        LY_HIP(hipMemcpy(new_raw + (size_t)old_n * h->dim, d_new, (size_t)n * h->dim * 4, hipMemcpyDeviceToDevice));
+    }
     std::vector<uint32_t> asg(h->assignments);
     asg.resize(old_n + n);
     LY_TRY(ivf_assign_rows(h, routed, n, asg.data() + old_n));
@@ -808,7 +987,9 @@ extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uin
     for (uint64_t p = 0; p < old_n; ++p) old_pos[h->orig[p]] = (uint32_t)p;
     IvfRowSource rs{h->store->rows, h->store->ld, old_pos.data(), routed, old_n, n};
     static const std::vector<float> none;
-    return ivf_reassemble(h, none, old_n + n, asg, &rs);
+    LY_TRY(ivf_reassemble(h, none, old_n + n, asg, &rs, new_raw));
+    new_raw = nullptr;   // (owned by the index now)
+    return LYNSE_OK;
 }
 
 extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_ids, uint64_t n_ids) {
@@ -824,6 +1005,27 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
     std::vector<bool> gone(old_n, false);
     for (uint64_t i = 0; i < n_ids; ++i)
         if (row_ids[i] < old_n) gone[row_ids[i]] = true;   // unknown ids are ignored (a HashSet lookup that never matches)
+    float* new_raw = nullptr;   // SQ8: the original rows that are kept, in order (the decoded ones are reassigned below)
+    struct FreeRaw { float*& p; ~FreeRaw() { if (p) (void)hipFree(p); } } fraw{new_raw};
+    if (h->sq8) {
+        std::vector<uint32_t> keep;
+        keep.reserve(old_n);
+        for (uint64_t r = 0; r < old_n; ++r)
+            if (!gone[r]) keep.push_back((uint32_t)r);
+        LY_HIP(hipSetDevice(h->store->device));
+        uint32_t* d_keep = nullptr;
+        struct G { uint32_t*& p; ~G() { if (p) (void)hipFree(p); } } g{d_keep};
+        LY_HIP(hipMalloc(&new_raw, std::max<size_t>(keep.size() * h->dim * 4, 4)));
+        if (!keep.empty()) {
+            LY_HIP(hipMalloc(&d_keep, keep.size() * 4));
+            LY_TRY(h2d_done(d_keep, keep.data(), keep.size() * 4));
+            const uint64_t pieces = (uint64_t)keep.size() * ((h->dim + 3) / 4);
+            hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0,
+                               h->d_raw, h->dim, d_keep, (uint64_t)keep.size(), new_raw, h->dim, h->dim);
+            LY_HIP(hipGetLastError());
+            LY_HIP(hipStreamSynchronize(nullptr));
+        }
+    }
     if (h->store->ld == h->dim && old_n) {
         // Rows stay in HBM (as in insert): kmeans::assign_metric over everything that is left = the top-1 of a FLAT search over the
         // centroid store with the slab rows themselves as device queries (every old slab position; the deleted ones are dropped
@@ -852,7 +1054,9 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
             }
         IvfRowSource rs{h->store->rows, h->store->ld, old_pos.data(), nullptr, (uint64_t)old_pos.size(), 0};
         static const std::vector<float> none;
-        return ivf_reassemble(h, none, old_pos.size(), asg, &rs);
+        LY_TRY(ivf_reassemble(h, none, old_pos.size(), asg, &rs, new_raw));
+        new_raw = nullptr;
+        return LYNSE_OK;
     }
     std::vector<float> all;
     LY_TRY(ivf_rows_in_original_order(h, &all));
@@ -863,7 +1067,9 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
         if (!gone[r]) { kept.insert(kept.end(), all.begin() + (size_t)r * h->dim, all.begin() + (size_t)(r + 1) * h->dim); ++m; }
     std::vector<uint32_t> asg(m);
     LY_TRY(ivf_assign_rows(h, kept.data(), m, asg.data()));   // kmeans::assign_metric over everything that is left
-    return ivf_reassemble(h, kept, m, asg);
+    LY_TRY(ivf_reassemble(h, kept, m, asg, nullptr, new_raw));
+    new_raw = nullptr;
+    return LYNSE_OK;
 }
 
 // ------------------------------------------------------------------------------------ search ----
@@ -1565,6 +1771,13 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
     return LYNSE_OK;
 }
 
+static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                             uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
+                             const uint64_t* subset, uint64_t n_subset, int metric_override, bool on_device);
+static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                          uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
+                          const uint64_t* subset, uint64_t n_subset, bool on_device);
+
 static int ivf_search_impl(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
                            uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
                            const uint64_t* subset, uint64_t n_subset, int metric_override = -1, bool on_device = false) {
@@ -1575,6 +1788,17 @@ static int ivf_search_impl(lynse_hip_ivf* h, const float* queries, uint64_t nq, 
     const std::shared_ptr<std::mutex> guard = ivf_guard_of(h);
     std::lock_guard<std::mutex> glk(*guard);   // (insert / delete replace h->store: read it under the index guard)
     if (!h->store) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
+    if (h->sq8) {
+        if (metric_override >= 0) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index searches with the metric it was built for");
+        return ivf_search_sq8(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, filtered, subset, n_subset, on_device);
+    }
+    return ivf_search_locked(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, filtered, subset, n_subset, metric_override, on_device);
+}
+
+// the search itself, the index guard held
+static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                             uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
+                             const uint64_t* subset, uint64_t n_subset, int metric_override, bool on_device) {
     lynse_hip_flat* s = h->store;
     std::unique_lock<std::shared_mutex> lk(s->rw);
     struct MetricScope {  // the metric of THIS call (lynse_hip_ivf_search_metric_f32), visible to ivf_search_chunk under the lock
@@ -1666,6 +1890,148 @@ static int ivf_search_impl(lynse_hip_ivf* h, const float* queries, uint64_t nq, 
     return LYNSE_OK;
 }
 
+// IVFIndex::search of an SQ8 index (ivf.rs:181-337), the index guard held.  The query is encoded and decoded; the POOL STAGE is
+// the ordinary IVF search of the decoded query over the decoded slab store with k = pool = min(max(10 k, k), n) — the same centroid
+// ranking, probe rule, all-lists-empty fallback, subset, kernels and plans (certified int8 pass, large-k path) — so each query's
+// pool is the best min(pool, |candidates|) candidates by (decoded distance, original row), left in device memory.  The RERANK
+// (k_ivfsq_rerank) scores them exactly against the original query and rows and keeps the best min(k, pool) by (exact distance,
+// original row); a pool above what one workgroup's LDS sorts (16,384 keys) is scored on the device and selected on the host.
+// The rerank adds its pool entries to the search context's rescored-candidate counter (lynse_hip_ivf_profile_get: pool_entries =
+// the pool stage's exact rescoring + the rerank).
+static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                          uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
+                          const uint64_t* subset, uint64_t n_subset, bool on_device) {
+    lynse_hip_flat* s = h->store;
+    const uint64_t n = s->n;
+    const uint32_t D = h->dim;
+    auto zero_counts = [&]() -> int {
+        if (on_device) return memset_done(out_counts, 0, nq * 4);
+        memset(out_counts, 0, nq * 4);
+        return LYNSE_OK;
+    };
+    if (n == 0 || k == 0) return zero_counts();
+    if (filtered) {   // no subset row in the index: nothing to answer from (ivf.rs:267-269)
+        bool any = false;
+        for (uint64_t i = 0; i < n_subset && !any; ++i) any = subset[i] < n;
+        if (!any) return zero_counts();
+    }
+    const uint32_t pool = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(10ull * k, k), n);
+    const bool asc = metric_ascending(h->metric);
+    uint32_t p2 = 2;
+    while (p2 < pool) p2 <<= 1;
+    const size_t q_lds = ((size_t)D + 3) / 4 * 16;
+    if (q_lds > 160u * 1024u) return set_error(LYNSE_ERR_UNSUPPORTED, "IVF-*-SQ8 rerank: the query does not fit in LDS");
+    const bool select_dev = pool <= 16384 && (size_t)p2 * 8 + q_lds <= 160u * 1024u;
+    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>(QCHUNK, (256ull << 20) / ((uint64_t)pool * 16)));
+    auto& sc = h->sq;
+    LY_HIP(hipSetDevice(s->device));
+    LY_TRY(ivf_grow(&sc.d_q, &sc.q_cap, (size_t)qc * D * 2));
+    LY_TRY(ivf_grow(&sc.d_prow, &sc.prow_cap, (size_t)qc * pool));
+    LY_TRY(ivf_grow(&sc.d_pdist, &sc.pdist_cap, (size_t)qc * pool));
+    LY_TRY(ivf_grow(&sc.d_pcnt, &sc.pcnt_cap, (size_t)qc));
+    if (!select_dev) LY_TRY(ivf_grow(&sc.d_keys, &sc.keys_cap, (size_t)qc * pool));
+    if (select_dev && !on_device) {
+        LY_TRY(ivf_grow(&sc.d_orow, &sc.orow_cap, (size_t)qc * k));
+        LY_TRY(ivf_grow(&sc.d_odist, &sc.odist_cap, (size_t)qc * k));
+        LY_TRY(ivf_grow(&sc.d_ocnt, &sc.ocnt_cap, (size_t)qc));
+    }
+    static std::once_flag lds_once;
+    static int lds_rc = LYNSE_OK;
+    std::call_once(lds_once, []() {
+        lds_rc = set_max_lds(k_ivfsq_rerank<true>, 160 * 1024);
+        if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_ivfsq_rerank<false>, 160 * 1024);
+    });
+    LY_TRY(lds_rc);
+    const bool timed = s->profiling.load();
+    if (timed)
+        for (hipEvent_t& e : sc.ev)
+            if (!e) LY_HIP(hipEventCreate(&e));
+    double pool_us = 0.0, rerank_us = 0.0;
+    float* d_qo = sc.d_q;                       // original queries
+    float* d_qd = sc.d_q + (size_t)qc * D;      // decoded queries
+    std::vector<uint64_t> keys, h_rows;
+    std::vector<uint32_t> pcnt, h_cnt;
+    std::vector<float> h_dists;
+    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
+        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
+        {
+            std::unique_lock<std::shared_mutex> lk(s->rw);
+            LY_TRY(use_device(s));
+            hipStream_t st = cur(s).stream;
+            LY_HIP(hipMemcpyAsync(d_qo, queries + q0 * D, (size_t)nqc * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+            LY_TRY(sq_codec_device(d_qo, nqc, D, h->d_sq, d_qd, st));
+            if (timed) LY_HIP(hipEventRecord(sc.ev[0], st));
+            LY_HIP(hipStreamSynchronize(st));
+        }
+        // pool stage: the decoded queries over the decoded rows, k = pool, results left in device memory
+        LY_TRY(ivf_search_locked(h, d_qd, nqc, pool, nprobe, sc.d_prow, sc.d_pdist, sc.d_pcnt, filtered, subset, n_subset, -1, true));
+        std::unique_lock<std::shared_mutex> lk(s->rw);
+        LY_TRY(use_device(s));
+        hipStream_t st = cur(s).stream;
+        if (timed) LY_HIP(hipEventRecord(sc.ev[1], st));
+        IvfSqRerankArgs a{h->d_raw, n, D, D, d_qo, sc.d_prow, sc.d_pcnt, pool, p2, h->metric, k, k, nullptr, nullptr, nullptr, nullptr,
+                          s->profiling.load() ? cur(s).ws.pool_total : nullptr};
+        if (select_dev) {
+            a.out_rows = on_device ? out_rows + q0 * k : sc.d_orow;
+            a.out_dists = on_device ? out_dists + q0 * k : sc.d_odist;
+            a.out_counts = on_device ? out_counts + q0 : sc.d_ocnt;
+            hipLaunchKernelGGL(k_ivfsq_rerank<true>, dim3(nqc), dim3(256), (size_t)p2 * 8 + q_lds, st, a);
+            LY_HIP(hipGetLastError());
+            if (timed) LY_HIP(hipEventRecord(sc.ev[2], st));
+            if (!on_device) {
+                LY_HIP(hipMemcpyAsync(out_rows + q0 * k, sc.d_orow, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
+                LY_HIP(hipMemcpyAsync(out_dists + q0 * k, sc.d_odist, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
+                LY_HIP(hipMemcpyAsync(out_counts + q0, sc.d_ocnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+            }
+            LY_HIP(hipStreamSynchronize(st));
+        } else {   // k > 1,638: every pool entry scored on the device, the canonical top k on the host (as ivf_search_large_k)
+            a.keys_out = sc.d_keys;
+            hipLaunchKernelGGL(k_ivfsq_rerank<false>, dim3(nqc), dim3(256), q_lds, st, a);
+            LY_HIP(hipGetLastError());
+            if (timed) LY_HIP(hipEventRecord(sc.ev[2], st));
+            keys.resize((size_t)nqc * pool);
+            pcnt.resize(nqc);
+            LY_HIP(hipMemcpyAsync(keys.data(), sc.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(pcnt.data(), sc.d_pcnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipStreamSynchronize(st));
+            const auto t_sel = std::chrono::steady_clock::now();
+            h_rows.resize((size_t)nqc * k);
+            h_dists.resize((size_t)nqc * k);
+            h_cnt.resize(nqc);
+            for (uint32_t q = 0; q < nqc; ++q) {
+                const uint32_t P = std::min<uint32_t>(pcnt[q], pool);
+                auto b = keys.begin() + (size_t)q * pool;
+                const uint32_t cnt = std::min<uint32_t>(k, P);
+                std::partial_sort(b, b + cnt, b + P);   // ascending keys = (distance in metric order, original row)
+                for (uint32_t i = 0; i < k; ++i) {
+                    h_rows[(size_t)q * k + i] = i < cnt ? (uint64_t)key_row(b[i]) : ~0ull;
+                    h_dists[(size_t)q * k + i] = i < cnt ? key_score(b[i], asc) : (asc ? INFINITY : -INFINITY);
+                }
+                h_cnt[q] = cnt;
+            }
+            if (timed) rerank_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sel).count();
+            if (on_device) {
+                LY_TRY(h2d_done(out_rows + q0 * k, h_rows.data(), h_rows.size() * 8));
+                LY_TRY(h2d_done(out_dists + q0 * k, h_dists.data(), h_dists.size() * 4));
+                LY_TRY(h2d_done(out_counts + q0, h_cnt.data(), h_cnt.size() * 4));
+            } else {
+                memcpy(out_rows + q0 * k, h_rows.data(), h_rows.size() * 8);
+                memcpy(out_dists + q0 * k, h_dists.data(), h_dists.size() * 4);
+                memcpy(out_counts + q0, h_cnt.data(), h_cnt.size() * 4);
+            }
+        }
+        if (timed) {   // (the stream was synchronised behind the rerank in both branches)
+            float a_ms = 0.f, b_ms = 0.f;
+            LY_HIP(hipEventElapsedTime(&a_ms, sc.ev[0], sc.ev[1]));
+            LY_HIP(hipEventElapsedTime(&b_ms, sc.ev[1], sc.ev[2]));
+            pool_us += (double)a_ms * 1000.0;
+            rerank_us += (double)b_ms * 1000.0;
+        }
+    }
+    if (timed) { h->sq_searches += 1; h->sq_pool_us += pool_us; h->sq_rerank_us += rerank_us; }
+    return LYNSE_OK;
+}
+
 extern "C" int lynse_hip_ivf_search_f32(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
                                         uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     return ivf_search_impl(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, false, nullptr, 0);
@@ -1678,14 +2044,16 @@ extern "C" int lynse_hip_ivf_search_metric_f32(lynse_hip_ivf* h, const float* qu
                                                int metric, uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
     if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
-    bool is_binary;
+    bool is_binary, is_sq8;
     int index_metric;
     {   // (insert / delete swap the whole index structure under the guard: even its constant fields are read under it)
         IVF_GUARD(h);
         if (!h->store) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
         is_binary = h->binary != 0;
+        is_sq8 = h->sq8;
         index_metric = h->metric;
     }
+    if (is_sq8) return set_error(LYNSE_ERR_UNSUPPORTED, "IvfFlatMmap::search(metric) is not defined for an IVF-*-SQ8 index (IVFIndex searches with its build metric)");
     if (is_binary || metric >= M_HAMMING) {
         if (metric == index_metric || (is_binary && metric >= M_HAMMING && (metric == M_TANIMOTO ? M_JACCARD : metric) == (index_metric == M_TANIMOTO ? M_JACCARD : index_metric)))
             return ivf_search_impl(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, false, nullptr, 0);

@@ -4547,4 +4547,137 @@ __global__ void __launch_bounds__(NT) k_merge(MergeArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// IVF-{IP,L2,COS}-SQ8 (IVFIndex with QuantizerType::Scalar, ivf.rs:132-337; ScalarQuantizer, quantizer/mod.rs:110-250).
+// NOT the FLAT SQ8 above: scale = range / 255 (1.0 for a constant dimension), codes truncate toward zero, and the
+// index keeps decode(encode(row)) = fl(fl(code * scale) + min) as f32 rows the IVF scans read like any other slab.
+//   k_ivfsq_minmax / k_ivfsq_fit   ScalarQuantizer::fit: per-dimension min / max from f32::MAX / f32::MIN with strict
+//                                  `<` / `>` in row order (NaN never wins; of equal values the first row's stays: -0 / +0)
+//   k_ivfsq_codec                  encode -> decode of rows or queries (codes optional)
+//   k_ivfsq_rerank                 the exact rerank of the decoded-distance pool against the ORIGINAL rows
+// ------------------------------------------------------------------------------------------------
+// thread = one dimension (coalesced across a row), blockIdx.y = a strip of rows scanned in row order; partials[strip][d]
+__global__ void __launch_bounds__(256) k_ivfsq_minmax(const float* __restrict__ V, uint32_t D, uint64_t n,
+                                                      float* __restrict__ pmin, float* __restrict__ pmax) {
+    const uint64_t per = (n + gridDim.y - 1) / gridDim.y;
+    const uint64_t r0 = (uint64_t)blockIdx.y * per, r1 = r0 + per < n ? r0 + per : n;
+    const uint32_t d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= D) return;
+    float mn = __FLT_MAX__, mx = -__FLT_MAX__;
+    for (uint64_t r = r0; r < r1; ++r) {
+        const float v = V[r * D + d];
+        if (v < mn) mn = v;
+        if (v > mx) mx = v;
+    }
+    pmin[(size_t)blockIdx.y * D + d] = mn;
+    pmax[(size_t)blockIdx.y * D + d] = mx;
+}
+
+// the strips merged in row order with the same strict comparisons (= one sequential pass), then range = max - min and
+// scale = range / 255 in f32, 1.0 where range == 0
+__global__ void __launch_bounds__(256) k_ivfsq_fit(const float* __restrict__ pmin, const float* __restrict__ pmax, uint32_t D,
+                                                   uint32_t strips, float* __restrict__ mins, float* __restrict__ scales) {
+    const uint32_t d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= D) return;
+    float mn = __FLT_MAX__, mx = -__FLT_MAX__;
+    for (uint32_t s = 0; s < strips; ++s) {
+        const float a = pmin[(size_t)s * D + d], b = pmax[(size_t)s * D + d];
+        if (a < mn) mn = a;
+        if (b > mx) mx = b;
+    }
+    const float range = __fsub_rn(mx, mn);
+    mins[d] = mn;
+    scales[d] = range == 0.0f ? 1.0f : __fdiv_rn(range, 255.0f);
+}
+
+// code = ((v - min) / scale).clamp(0, 255) as u8 (NaN -> 0, +inf -> 255, -inf -> 0); decoded = fl(fl(code * scale) + min).
+// In place is allowed (dec == V).
+__global__ void __launch_bounds__(256) k_ivfsq_codec(const float* V, uint64_t n, uint32_t D, const float* __restrict__ mins,
+                                                     const float* __restrict__ scales, float* dec, uint8_t* __restrict__ codes) {
+    const uint64_t total = n * D;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t d = (uint32_t)(i % D);
+        const float mn = mins[d], sc = scales[d];
+        float t = __fdiv_rn(__fsub_rn(V[i], mn), sc);
+        if (t != t) t = 0.0f;
+        t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);
+        const uint32_t c = (uint32_t)t;   // truncation toward zero
+        if (codes) codes[i] = (uint8_t)c;
+        dec[i] = __fadd_rn(__fmul_rn((float)c, sc), mn);
+    }
+}
+
+// One workgroup per query.  The pool stage (the IVF scan over the decoded slab with k = pool) left the pool's original
+// row ids in pool_rows[q * pool_ld ..] (pool_cnt[q] of them, best-first by decoded distance); the original query is
+// staged in LDS, the original rows (row-major, `ld` floats, original row order) are gathered and scored with the
+// single-row kernels — compute_distance_f32, lo_compute_distance — and, SELECT, the pool is sorted by the canonical
+// (distance, original row) key in LDS (bitonic over p2 >= pool_cnt keys) and the best min(k, pool) written in the layout of
+// lynse_hip_ivf_search_f32 (rows ~0 / worst distance padding, counts).  !SELECT: the keys go to keys_out[q * pool_ld ..]
+// for a host selection (pools beyond the LDS).
+struct IvfSqRerankArgs {
+    const float* V;
+    uint64_t n;              // rows of V
+    uint32_t ld, D;
+    const float* q;          // nq x D original queries
+    const uint64_t* pool_rows;
+    const uint32_t* pool_cnt;
+    uint32_t pool_ld;
+    uint32_t p2;             // SELECT: power of two >= every pool_cnt (keys in LDS)
+    int metric;
+    uint32_t k, out_k;       // best k written, output stride out_k
+    uint64_t* out_rows;
+    float* out_dists;
+    uint32_t* out_counts;
+    uint64_t* keys_out;      // !SELECT
+    unsigned long long* pool_total;   // += the pool entries rescored (the profile's pool_entries), may be NULL
+};
+
+template <bool SELECT>
+__global__ void __launch_bounds__(256) k_ivfsq_rerank(IvfSqRerankArgs a) {
+    extern __shared__ uint64_t sm_rr[];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const int g = tid & 7;
+    const bool asc = metric_ascending(a.metric);
+    uint64_t* keys = sm_rr;                                                          // SELECT: p2 keys
+    float* q_l = reinterpret_cast<float*>(sm_rr + (SELECT ? a.p2 : 0));
+    for (uint32_t i = tid; i < a.D; i += 256) q_l[i] = a.q[(size_t)q * a.D + i];
+    __syncthreads();
+    const uint32_t P = a.pool_cnt[q] < a.pool_ld ? a.pool_cnt[q] : a.pool_ld;
+    const uint64_t* pr = a.pool_rows + (size_t)q * a.pool_ld;
+    if (tid == 0 && a.pool_total) atomicAdd(a.pool_total, (unsigned long long)P);
+    const uint32_t bound = (P + 31u) / 32u * 32u;   // whole waves run the same trip count (exact_score shuffles inside its 8 lanes)
+    for (uint32_t i = tid >> 3; i < bound; i += 32) {
+        if (P == 0) break;
+        const uint64_t r64 = pr[i < P ? i : P - 1];
+        const uint32_t row = r64 < a.n ? (uint32_t)r64 : 0u;   // (a pool entry is an original row id < n)
+        float s = exact_score<32>(a.metric, LYNSE_IPFORM_SINGLE, q_l, a.V + (size_t)row * a.ld, a.D, g);
+        if (r64 >= a.n) s = __builtin_nanf("");                // (never: would rank last, make_key)
+        if (g == 0 && i < P) {
+            if (SELECT) keys[i] = make_key(s, row, asc);
+            else a.keys_out[(size_t)q * a.pool_ld + i] = make_key(s, row, asc);
+        }
+    }
+    if constexpr (SELECT) {
+        for (uint32_t i = P + tid; i < a.p2; i += 256) keys[i] = KEY_SENTINEL;
+        __syncthreads();
+        for (uint32_t size = 2; size <= a.p2; size <<= 1)
+            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                for (uint32_t t = tid; t < a.p2 / 2; t += 256) {
+                    const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                    const bool up = (lo & size) == 0;
+                    const uint64_t x = keys[lo], y = keys[hi];
+                    if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
+                }
+                __syncthreads();
+            }
+        const uint32_t cnt = P < a.k ? P : a.k;
+        for (uint32_t i = tid; i < a.out_k; i += 256) {
+            const bool in = i < cnt;
+            a.out_rows[(size_t)q * a.out_k + i] = in ? (uint64_t)key_row(keys[i]) : ~0ull;
+            a.out_dists[(size_t)q * a.out_k + i] = in ? key_score(keys[i], asc) : (asc ? LY_INF : -LY_INF);
+        }
+        if (tid == 0) a.out_counts[q] = cnt;
+    }
+}
+
 }  // namespace lynse
