@@ -186,6 +186,50 @@ int lynse_hip_flat_search_sq8_f32(lynse_hip_flat *h, const float *queries, uint6
                                   uint32_t *out_counts);
 /* The SQ8 quantiser state (per-dimension minimum and scale = 255 / range, 0 for a constant dimension). */
 int lynse_hip_flat_sq8_params(lynse_hip_flat *h, float *mins, float *scales);
+/* FLAT-{IP,L2,COS,COSINE}-PQ and FLAT-*-PQ<n> (PQIndex, src/storage/pq_mmap.rs; Collection, engine.rs:4559-4600, :5504-5526).
+ * f32 handles and ip / l2 / cosine only.  The rules:
+ *  1. M = the n of "PQ<n>" when n > 0 divides dim, else the first divisor of dim in [16, 8, 32, 4, 12, 24, 6, 2, 1]
+ *     (parse_n_subspaces, pq_mmap.rs:1107-1128; Python: parse_n_subspaces); ss = dim / M; K = min(clamp(n_clusters, 1, 256), n).
+ *  2. Training sample: train_n = min(n, 50,000) rows; when train_n < n, rows 0, s, 2s, ... with s = max(n / train_n, 1).
+ *  3. Per subspace m, k-means (kmeans_subspace, :577-662): 6 iterations when K <= 64, else 15.  Assignment: l2_squared_f32
+ *     against every centroid in order, the first strictly smaller than the best so far (from f32::MAX) wins, so NaN never wins.
+ *     Assignments start at 0; a pass that moves none stops that subspace BEFORE the update (K = 1 keeps the initial
+ *     centroids).  Update: per-cluster f32 sums in ascending row order, then *= fl(1 / count).  An empty cluster becomes
+ *     new[src] * (1 + 0.01 ((d % 2) - 0.5)), src = the LAST most-populated cluster; new[src] is already divided when src < c
+ *     and still the raw sum when src > c.
+ *  4. Initialisation (random_init_centroids, :665-689): SmallRng::seed_from_u64(m) = xoshiro256++ seeded by SplitMix64;
+ *     gen_range(0..train_n) by widening multiply with rejection zone (n << lzcnt(n)) - 1; distinct indices, at most 10 K
+ *     attempts; centroids still missing become prev[d] * (1 + 0.001 d).  lynse_hip_pq_xoshiro_stream / _splitmix_stream /
+ *     _init_indices expose this host code for known-answer tests.
+ *  5. Encode: argmin of l2_squared_f32 over the K codewords, first strictly smaller wins (a NaN sub-vector gets code 0).
+ *  6. Tables: lut[m][c] = inner_product_f32 (IP) or l2_squared_f32 (L2 AND cosine) of the RAW query's sub-vector m and codeword
+ *     c; the ADC score is 0.0f + lut[0][c0] + lut[1][c1] + ..., added in f32 in ascending m.
+ *  7. Search: k' = min(k, n_pq), N = min(k' * oversample, n_pq) (the Collection passes 32, PQ_OVERSAMPLE); the N best ADC
+ *     scores (largest for IP, smallest otherwise), rescored with compute_distance_f32 on the original rows; the best k' come
+ *     back with their exact distances.  Both cuts use the canonical (score, row) key (the reference's heap + sort_unstable
+ *     leave ties unpinned); NaN and +-inf order as in the FLAT searches.  Output layout of lynse_hip_flat_search_f32.
+ *  8. The index covers the first n_pq rows: rows appended after a build or a load stay outside it (n_pq is unchanged).  Build and
+ *     load replace an earlier PQ index; lynse_hip_flat_drop_pq removes it.  The exact searches of the handle are unchanged.
+ *  Refused with LYNSE_ERR_UNSUPPORTED: an F16 shard, a packed-only handle, a row-sharded handle (set_row_map with stride != 1
+ *  or offset != 0: there is no sharded PQ search), and the binary metrics.  There is no ticket (submit / wait) or upsert form.
+ *  The PQ search holds the handle's lock exclusively (its scratch is per handle) and runs on context 0.
+ * lynse_hip_flat_load_pq applies PQIndex::load's checks (M == 0, K outside 1..=256, M * ss != dim, n > u32::MAX: "Invalid PQ index
+ * dimensions"; a code >= K: "PQ index contains an out-of-range code") and needs n <= the handle's rows.  lynse_hip_flat_pq_params
+ * returns mks = {M, K, ss} and n_pq (all 0 without an index) and, when the pointers are not NULL, codebooks[M][K][ss] and
+ * codes[n_pq][M].  lynse_hip_flat_pq_stage_times, with profiling on: out3[0] searches, out3[1] the scan stage (tables, ADC scan and
+ * the pool cut) and out3[2] the rescore (plus the host selection of a pool beyond 16,384), microseconds from HIP events; reset != 0
+ * clears them. */
+int lynse_hip_flat_build_pq(lynse_hip_flat *h, uint32_t n_subspaces, uint32_t n_clusters);
+int lynse_hip_flat_load_pq(lynse_hip_flat *h, uint32_t n_subspaces, uint32_t n_clusters, const float *codebooks,
+                           const uint8_t *codes, uint64_t n);
+int lynse_hip_flat_pq_params(lynse_hip_flat *h, uint32_t *mks, uint64_t *n_pq, float *codebooks, uint8_t *codes);
+int lynse_hip_flat_drop_pq(lynse_hip_flat *h);
+int lynse_hip_flat_search_pq_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric,
+                                 uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
+int lynse_hip_flat_pq_stage_times(lynse_hip_flat *h, double *out3, int reset);
+int lynse_hip_pq_xoshiro_stream(const uint64_t *state4, uint64_t count, uint64_t *out);
+int lynse_hip_pq_splitmix_stream(uint64_t seed, uint64_t count, uint64_t *out);
+int lynse_hip_pq_init_indices(uint64_t seed, uint64_t n, uint32_t k, uint32_t *idx, uint32_t *chosen);
 /* Same with every buffer already resident in this handle's device memory; enqueued on `stream`
  * (a hipStream_t, NULL = the handle's own non-blocking stream) and synchronised before returning.
  * Device inputs of every *_device entry must be COMPLETE when the call is made (synchronise the

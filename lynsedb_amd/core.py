@@ -76,13 +76,49 @@ def ivf_quantizer_of(mode: str) -> Optional[str]:
     """The quantizer an `IVF-*` index mode names (src/index/mod.rs:361-385): None for IVF-Flat and the binary modes (their
     quantizer follows from the metric), "sq8" for IVF-{IP,L2,COS,COSINE}-SQ8 (ip / l2 / cosine only); PQ is not built."""
     parts = str(mode).upper().split("-")
-    if "PQ" in parts:
+    if any(t == "PQ" or (t.startswith("PQ") and t[2:].isdigit()) for t in parts):   # IVF-*-PQ and IVF-*-PQ<n>
         raise NotImplementedError("quantized IVF variants other than SQ8 (PQ) are outside this path")
     if "SQ8" in parts:
         if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
             raise NotImplementedError(f"{mode}: IVF-*-SQ8 is defined for ip / l2 / cosine")
         return "sq8"
     return None
+
+
+PQ_OVERSAMPLE = 32   # engine.rs PQ_OVERSAMPLE / pq_mmap.rs DEFAULT_OVERSAMPLE
+
+
+def parse_n_subspaces(index_type: str, dim: int) -> int:
+    """parse_n_subspaces (src/storage/pq_mmap.rs:1107-1128): the digits after "PQ" when they are > 0 and divide `dim`, else the first
+    divisor of `dim` in [16, 8, 32, 4, 12, 24, 6, 2, 1]."""
+    s = str(index_type).upper()
+    pos = s.find("PQ")
+    if pos >= 0:
+        digits = ""
+        for ch in s[pos + 2:]:
+            if not ch.isdigit():
+                break
+            digits += ch
+        if digits:
+            n = int(digits)
+            if n > 0 and dim % n == 0:
+                return n
+    for c in (16, 8, 32, 4, 12, 24, 6, 2, 1):
+        if dim % c == 0:
+            return c
+    return 1
+
+
+def flat_pq_mode(mode: str) -> bool:
+    """True for FLAT-{IP,L2,COS,COSINE}-PQ[<n>]; binary metrics and the other FLAT quantisers (RaBitQ, PolarVec) are refused."""
+    parts = str(mode).upper().split("-")
+    if not parts or parts[0] != "FLAT":
+        return False
+    if not any(p.startswith("PQ") and p[2:].isdigit() or p == "PQ" for p in parts[1:]):
+        return False
+    if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
+        raise NotImplementedError(f"{mode}: FLAT-*-PQ is defined for ip / l2 / cosine")
+    return True
 
 
 def _f32(a, ndim: int, what: str) -> np.ndarray:
@@ -253,6 +289,55 @@ class FlatIndex:
         mins, scales = np.empty(self._dim, np.float32), np.empty(self._dim, np.float32)
         check(lib.lynse_hip_flat_sq8_params(self._h, _ptr(mins), _ptr(scales)))
         return mins, scales
+
+    # -- FLAT-*-PQ (PQIndex, src/storage/pq_mmap.rs; include/lynse_hip.h states the contract) --------------------------------
+    def build_pq(self, n_subspaces: int, n_clusters: int = 256) -> None:
+        """Train the product quantiser on the rows held now and encode them (rows appended later stay outside the index)."""
+        check(lib.lynse_hip_flat_build_pq(self._h, int(n_subspaces), int(n_clusters)))
+
+    def load_pq(self, codebooks, codes) -> None:
+        """Install a trained quantiser: codebooks f32 [M][K][ss], codes u8 [n][M] for the first n rows."""
+        cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+        cd = np.ascontiguousarray(codes, dtype=np.uint8)
+        if cb.ndim != 3 or cd.ndim != 2 or cd.shape[1] != cb.shape[0]:
+            raise ValueError("codebooks must be [M][K][ss] and codes [n][M]")
+        check(lib.lynse_hip_flat_load_pq(self._h, cb.shape[0], cb.shape[1], _ptr(cb), _ptr(cd), cd.shape[0]))
+
+    def drop_pq(self) -> None:
+        check(lib.lynse_hip_flat_drop_pq(self._h))
+
+    def pq_params(self, arrays: bool = True) -> dict:
+        """{"M", "K", "ss", "n"} and, with `arrays`, "codebooks" f32 [M][K][ss] and "codes" u8 [n][M]; M == 0 without an index."""
+        mks = np.zeros(3, np.uint32)
+        n = C.c_uint64(0)
+        check(lib.lynse_hip_flat_pq_params(self._h, _ptr(mks), C.byref(n), None, None))
+        m, k, ss = (int(x) for x in mks)
+        out = {"M": m, "K": k, "ss": ss, "n": int(n.value)}
+        if arrays and m:
+            cb = np.empty((m, k, ss), np.float32)
+            cd = np.empty((int(n.value), m), np.uint8)
+            check(lib.lynse_hip_flat_pq_params(self._h, _ptr(mks), C.byref(n), _ptr(cb), _ptr(cd)))
+            out["codebooks"], out["codes"] = cb, cd
+        return out
+
+    def search_pq_batch_arrays(self, queries, k: int, metric, oversample: int = PQ_OVERSAMPLE):
+        """ADC scan over the codes, the N = min(k' * oversample, n_pq) best by (ADC score, row), exact rescore of those rows."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_flat_search_pq_f32(self._h, _ptr(q), nq, k, m, int(oversample), _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+    def pq_stage_times(self, reset: bool = True) -> dict:
+        """With profiling on: PQ searches timed and the summed microseconds of the scan stage and of the rescore."""
+        out = np.zeros(3, np.float64)
+        check(lib.lynse_hip_flat_pq_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
 
     def search_filtered_batch_arrays(self, queries, k: int, metric, subset_rows):
         """`FlatMmap::search_filtered` (flat_mmap.rs:491-815) for a batch sharing one subset of row indices."""
@@ -812,6 +897,7 @@ class Collection:
         self._pending_ids: list = []
         self._pending_rows = 0
         self._tombstone: set = set()    # user ids (engine.rs:3182-3194)
+        self._pq = False                # FLAT-*-PQ built over the rows flushed at build time (FlatIndex.build_pq)
 
     def name(self) -> str:
         return self._name
@@ -883,11 +969,19 @@ class Collection:
         params = dict(params or {})
         self._flush_pending()
         if mode.startswith("FLAT"):
-            if any(t in mode.split("-") for t in ("PQ", "RABITQ", "POLARVEC")):
-                raise NotImplementedError("PQ / RaBitQ / PolarVec flat modes are outside this path (SURVEY.md §2)")
+            if any(t in mode.split("-") for t in ("RABITQ", "POLARVEC")):
+                raise NotImplementedError("RaBitQ / PolarVec flat modes are outside this path (SURVEY.md §2)")
+            pq = flat_pq_mode(mode)
             self._ivf = None
+            self._flat.drop_pq()   # building any mode drops an earlier PQ index (engine.rs:4559-4600)
+            self._pq = False
+            if pq and len(self._flat) > 0:   # over 0 rows nothing is built and searches stay exact
+                self._flat.build_pq(parse_n_subspaces(mode, self._dim), int(params.get("n_clusters", 256)))
+                self._pq = True
         elif mode.startswith("IVF"):
             quantizer = ivf_quantizer_of(mode)
+            self._flat.drop_pq()
+            self._pq = False
             self._ivf_params = {"n_clusters": int(params.get("n_clusters", 256)), "quantizer": quantizer}
             self._ivf_nprobe = int(params.get("nprobe", 32))
             self._index_mode, self._metric = mode, metric
@@ -963,6 +1057,8 @@ class Collection:
             if subset_rows.size == 0:
                 return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
             return self._flat.search_filtered_batch_arrays(q, search_k, self._metric, subset_rows)
+        if self._pq:   # search_auxiliary_quantized (engine.rs:5504-5526): rows committed after the build are not in the index
+            return self._flat.search_pq_batch_arrays(q, search_k, self._metric, PQ_OVERSAMPLE)
         if self._use_sq8() and self._metric in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
             return self._flat.search_sq8_batch_arrays(q, search_k, self._metric)
         return self._flat.search_batch_arrays(q, search_k, self._metric)
@@ -994,10 +1090,13 @@ class Collection:
             filter_us = int((time.perf_counter() - t0) * 1e6)
         target = self._ivf if self._ivf is not None else self._flat
         sq8 = self._ivf is not None and self._ivf.is_sq8
+        pq = self._ivf is None and self._pq and subset is None
         target.profile_enable(True)
         target.profile_get(reset=True)
         if sq8:
             self._ivf.sq8_stage_times(reset=True)
+        if pq:
+            self._flat.pq_stage_times(reset=True)
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
@@ -1005,11 +1104,14 @@ class Collection:
             dev = target.profile_get(reset=True)
             # IVF-*-SQ8: the exact rerank of the pool (HIP events on the search stream); 0 for the modes without one
             rerank_us = int(self._ivf.sq8_stage_times(reset=True)["rerank_us"]) if sq8 else 0
+            if pq:   # FLAT-*-PQ: the exact rescore of the ADC pool
+                rerank_us = int(self._flat.pq_stage_times(reset=True)["rescore_us"])
             target.profile_enable(False)
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
-                   "index_path": "ann_index" if self._ivf is not None else ("flat_mmap_filtered" if subset is not None else "flat_mmap"),
+                   "index_path": "ann_index" if self._ivf is not None else ("flat_mmap_filtered" if subset is not None else
+                                                                            ("pq_two_pass" if pq else "flat_mmap")),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
                    "filter_us": filter_us, "search_us": search_us, "rerank_us": rerank_us, "total_us": int((time.perf_counter() - started) * 1e6),

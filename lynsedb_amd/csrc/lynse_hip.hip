@@ -27,6 +27,7 @@
 #include "scan_qs.h"
 #include "scan_qh.h"
 #include "ivf.h"
+#include "pq.h"
 
 using namespace lynse;
 
@@ -229,6 +230,8 @@ struct Workspace {
     }
 };
 
+struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
+
 struct lynse_hip_flat {
     uint32_t dim = 0, ld = 0, words = 0;
     int device = 0;
@@ -339,11 +342,15 @@ struct lynse_hip_flat {
     uint32_t* g_ids32 = nullptr;
     uint64_t g_cap = 0;
 
+    PqState* pq = nullptr;                // FLAT-{IP,L2,COS}-PQ index over the first pq->n rows (pq_host.inc); NULL = none
+
     std::atomic<bool> profiling{false};   // (read by searches without the lock: atomics)
     std::atomic<uint32_t> prof_rate{1};              // every prof_rate-th search records its events (lynse_hip_flat_profile_enable(h, n))
     std::atomic<uint32_t> prof_seq{0};
     lynse_hip_profile prof{};
 };
+
+static void pq_release(lynse_hip_flat* h);
 
 static inline bool is_f16(const lynse_hip_flat* h) { return h->dtype == LYNSE_DTYPE_F16; }
 // the row matrix the exact-scoring kernels read: f32 rows, or the f16 bits of an F16 shard handed in as float* with a pitch
@@ -475,6 +482,7 @@ extern "C" int lynse_hip_flat_create(uint32_t dim, int device, lynse_hip_flat** 
 extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
+    pq_release(h);
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
@@ -3813,3 +3821,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "comm_host.inc"
 #include "async_host.inc"
 #include "ivf_async.inc"
+#include "pq_host.inc"

@@ -1,0 +1,471 @@
+// pq_host.inc — FLAT-{IP,L2,COS}-PQ on a FLAT handle (PQIndex, src/storage/pq_mmap.rs; Collection, src/engine.rs:4559-4600,
+// :5504-5526).  Included at the end of lynse_hip.hip; kernels in pq.h, the exact rescore is k_ivfsq_rerank (kernels.h).
+// DESIGN.md §12.
+
+// The quantiser and the per-handle search scratch.  Codes cover the first n rows of the handle: rows appended after a build or a
+// load stay outside the index (the reference neither re-encodes nor drops them on flush).
+struct PqState {
+    uint32_t M = 0, K = 0, ss = 0;
+    uint64_t n = 0;
+    float* cb = nullptr;          // [M][K][ss] f32 codebooks
+    uint8_t* codes = nullptr;     // [n][M] u8 codes
+    float *d_q = nullptr, *d_lut = nullptr;
+    size_t q_cap = 0, lut_cap = 0;
+    uint32_t *d_S = nullptr, *d_hist = nullptr, *d_pcnt = nullptr, *d_ocnt = nullptr;
+    size_t S_cap = 0, hist_cap = 0, pcnt_cap = 0, ocnt_cap = 0;
+    PqSel* d_sel = nullptr;
+    size_t sel_cap = 0;
+    uint64_t *d_prow = nullptr, *d_keys = nullptr, *d_orow = nullptr;
+    size_t prow_cap = 0, keys_cap = 0, orow_cap = 0;
+    float* d_odist = nullptr;
+    size_t odist_cap = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // profiling: before the tables / after the pool cut / after the rescore
+    double searches = 0.0, scan_us = 0.0, rescore_us = 0.0;
+
+    void free_index() {
+        if (cb) (void)hipFree(cb);
+        if (codes) (void)hipFree(codes);
+        cb = nullptr;
+        codes = nullptr;
+        M = K = ss = 0;
+        n = 0;
+    }
+    ~PqState() {
+        free_index();
+        for (void* p : {(void*)d_q, (void*)d_lut, (void*)d_S, (void*)d_hist, (void*)d_pcnt, (void*)d_ocnt, (void*)d_sel, (void*)d_prow,
+                        (void*)d_keys, (void*)d_orow, (void*)d_odist})
+            if (p) (void)hipFree(p);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+static void pq_release(lynse_hip_flat* h) {
+    delete h->pq;
+    h->pq = nullptr;
+}
+
+// ---- SmallRng (rand 0.8.5 on 64-bit: Xoshiro256PlusPlus) and random_init_centroids' draws --------------------------------
+namespace pqrng {
+static inline uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
+static inline uint64_t splitmix(uint64_t& state) {   // SeedableRng::seed_from_u64's generator (rand_core 0.6)
+    state += 0x9e3779b97f4a7c15ull;
+    uint64_t z = state;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+struct Xoshiro256pp {
+    uint64_t s[4];
+    static Xoshiro256pp seed_from_u64(uint64_t seed) {
+        Xoshiro256pp r;
+        uint64_t st = seed;
+        for (auto& w : r.s) w = splitmix(st);
+        if (!(r.s[0] | r.s[1] | r.s[2] | r.s[3])) return seed_from_u64(0);   // from_seed: an all-zero seed re-seeds from 0
+        return r;
+    }
+    uint64_t next() {
+        const uint64_t result = rotl(s[0] + s[3], 23) + s[0];
+        const uint64_t t = s[1] << 17;
+        s[2] ^= s[0];
+        s[3] ^= s[1];
+        s[1] ^= s[2];
+        s[0] ^= s[3];
+        s[2] ^= t;
+        s[3] = rotl(s[3], 45);
+        return result;
+    }
+    // gen_range(0..n), n >= 1 (UniformInt::sample_single: widening multiply, rejection zone = (n << lzcnt(n)) - 1)
+    uint64_t below(uint64_t n) {
+        const uint64_t zone = (n << __builtin_clzll(n)) - 1;
+        for (;;) {
+            const unsigned __int128 p = (unsigned __int128)next() * n;
+            if ((uint64_t)p <= zone) return (uint64_t)(p >> 64);
+        }
+    }
+};
+// random_init_centroids (pq_mmap.rs:665-689): distinct indices, at most 10 k attempts; returns how many were chosen
+static uint32_t init_indices(uint64_t seed, uint64_t n, uint32_t k, uint32_t* idx) {
+    Xoshiro256pp rng = Xoshiro256pp::seed_from_u64(seed);
+    std::vector<uint64_t> seen;
+    seen.reserve(k);
+    uint32_t c = 0;
+    uint64_t attempts = 0;
+    while (c < k && attempts < (uint64_t)k * 10) {
+        const uint64_t i = rng.below(n);
+        if (std::find(seen.begin(), seen.end(), i) == seen.end()) {
+            seen.push_back(i);
+            idx[c++] = (uint32_t)i;
+        }
+        ++attempts;
+    }
+    return c;
+}
+}  // namespace pqrng
+
+extern "C" int lynse_hip_pq_xoshiro_stream(const uint64_t* state4, uint64_t count, uint64_t* out) {
+    if (!state4 || (count && !out)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    pqrng::Xoshiro256pp r;
+    for (int i = 0; i < 4; ++i) r.s[i] = state4[i];
+    for (uint64_t i = 0; i < count; ++i) out[i] = r.next();
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_pq_splitmix_stream(uint64_t seed, uint64_t count, uint64_t* out) {
+    if (count && !out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t st = seed;
+    for (uint64_t i = 0; i < count; ++i) out[i] = pqrng::splitmix(st);
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_pq_init_indices(uint64_t seed, uint64_t n, uint32_t k, uint32_t* idx, uint32_t* chosen) {
+    if (!chosen || (k && !idx)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n == 0 && k) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
+    *chosen = k ? pqrng::init_indices(seed, n, k, idx) : 0u;
+    return LYNSE_OK;
+}
+
+// ---- build / load ------------------------------------------------------------------------------------------------------------
+static int pq_check_handle(const lynse_hip_flat* h) {
+    if (h->dtype != LYNSE_DTYPE_F32) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ on an F16 shard is not supported");
+    if (h->packed_only) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ is defined for float rows (ip / l2 / cosine)");
+    if (h->row_stride != 1 || h->row_offset != 0) return set_error(LYNSE_ERR_UNSUPPORTED, "a PQ index is not row-sharded");
+    return LYNSE_OK;
+}
+
+// encode (pq_mmap.rs:696-735): codes[i][m] = argmin over the K codewords of l2_squared_f32, first strictly smaller wins
+static int pq_launch_assign(PqAssignArgs a, uint64_t n_rows, hipStream_t st) {
+    const size_t lds = (size_t)a.K * a.ss * 4;
+    a.cb_lds = lds <= 64u * 1024u;
+    const dim3 grid((uint32_t)((n_rows + 255) / 256), a.M);
+    const size_t sh = a.cb_lds ? lds : 0;
+    if (a.ss <= 8) hipLaunchKernelGGL(k_pq_assign<8>, grid, dim3(256), sh, st, a);
+    else if (a.ss <= 16) hipLaunchKernelGGL(k_pq_assign<16>, grid, dim3(256), sh, st, a);
+    else if (a.ss <= 32) hipLaunchKernelGGL(k_pq_assign<32>, grid, dim3(256), sh, st, a);
+    else if (a.ss <= 64) hipLaunchKernelGGL(k_pq_assign<64>, grid, dim3(256), sh, st, a);
+    else if (a.ss <= 128) hipLaunchKernelGGL(k_pq_assign<128>, grid, dim3(256), sh, st, a);
+    else hipLaunchKernelGGL(k_pq_assign<0>, grid, dim3(256), sh, st, a);
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
+
+template <typename T>
+struct PqDevBuf {   // scratch of one build, freed on every exit path
+    T* p = nullptr;
+    int alloc(size_t count) {
+        LY_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+        return LYNSE_OK;
+    }
+    ~PqDevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// PQIndex::build_with_clusters (pq_mmap.rs:73-149) over the handle's rows, the writer lock held
+static int pq_build_locked(lynse_hip_flat* h, uint32_t M, uint32_t n_clusters) {
+    const uint64_t n = h->n;
+    const uint32_t D = h->dim;
+    if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
+    if (M == 0 || D % M != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "dim must be divisible by n_subspaces");
+    const uint32_t ss = D / M;
+    const uint32_t K = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(std::max<uint32_t>(n_clusters, 1), 256), n);
+    const uint64_t train_n = std::min<uint64_t>(n, 50000);
+    const uint64_t stride = train_n < n ? std::max<uint64_t>(n / train_n, 1) : 1;
+    const uint32_t iters = K <= 64 ? 6 : 15;
+    hipStream_t st = cur(h).stream;
+    PqDevBuf<float> T, raw;
+    PqDevBuf<uint32_t> idx, chosen, asg, active, changed, count;
+    LY_TRY(T.alloc((size_t)train_n * D));
+    LY_TRY(raw.alloc((size_t)M * K * ss));
+    LY_TRY(idx.alloc((size_t)M * K));
+    LY_TRY(chosen.alloc(M));
+    LY_TRY(asg.alloc((size_t)M * train_n));
+    LY_TRY(active.alloc(M));
+    LY_TRY(changed.alloc(M));
+    LY_TRY(count.alloc((size_t)M * K));
+    float* cb = nullptr;
+    uint8_t* codes = nullptr;
+    LY_HIP(hipMalloc(&cb, (size_t)M * K * ss * 4));
+    if (hipMalloc(&codes, (size_t)n * M) != hipSuccess) {
+        (void)hipFree(cb);
+        return set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(PQ codes)");
+    }
+    auto fail = [&](int rc) { (void)hipFree(cb); (void)hipFree(codes); return rc; };
+    const uint32_t gather_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((train_n * D + 255) / 256, (uint64_t)h->num_cu * 32));
+    hipLaunchKernelGGL(k_pq_gather, dim3(gather_blocks), dim3(256), 0, st, h->rows, h->ld, D, stride, train_n, T.p);
+    if (hipGetLastError() != hipSuccess) return fail(set_error(LYNSE_ERR_DEVICE, "k_pq_gather launch"));
+    // the K draws of each subspace (seed m) on the host
+    std::vector<uint32_t> h_idx((size_t)M * K, 0u), h_chosen(M), h_active(M, 1u), h_changed(M);
+    for (uint32_t m = 0; m < M; ++m) h_chosen[m] = pqrng::init_indices(m, train_n, K, h_idx.data() + (size_t)m * K);
+    int rc = LYNSE_OK;
+    auto run = [&]() -> int {
+        LY_HIP(hipMemcpyAsync(idx.p, h_idx.data(), h_idx.size() * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(chosen.p, h_chosen.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(active.p, h_active.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(asg.p, 0, (size_t)M * train_n * 4, st));
+        hipLaunchKernelGGL(k_pq_init, dim3(M), dim3(64), 0, st, T.p, D, ss, K, idx.p, chosen.p, cb);
+        LY_HIP(hipGetLastError());
+        for (uint32_t it = 0; it < iters; ++it) {
+            LY_HIP(hipMemsetAsync(changed.p, 0, (size_t)M * 4, st));
+            PqAssignArgs a{T.p, D, train_n, M, ss, K, cb, 0, active.p, asg.p, changed.p, nullptr};
+            LY_TRY(pq_launch_assign(a, train_n, st));
+            LY_HIP(hipMemcpyAsync(h_changed.data(), changed.p, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipStreamSynchronize(st));
+            bool any = false;
+            for (uint32_t m = 0; m < M; ++m) {   // no assignment moved: this subspace stops BEFORE the update
+                h_active[m] = h_active[m] && h_changed[m];
+                any = any || h_active[m];
+            }
+            if (!any) break;
+            LY_HIP(hipMemcpyAsync(active.p, h_active.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_pq_update, dim3(K, M), dim3(64), 0, st, T.p, D, train_n, ss, K, active.p, asg.p, raw.p, cb, count.p);
+            LY_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_pq_empty, dim3(M), dim3(64), 0, st, ss, K, active.p, raw.p, cb, count.p);
+            LY_HIP(hipGetLastError());
+        }
+        PqAssignArgs e{h->rows, h->ld, n, M, ss, K, cb, 0, nullptr, nullptr, nullptr, codes};
+        LY_TRY(pq_launch_assign(e, n, st));
+        LY_HIP(hipStreamSynchronize(st));
+        return LYNSE_OK;
+    };
+    rc = run();
+    if (rc != LYNSE_OK) {
+        (void)hipStreamSynchronize(st);
+        return fail(rc);
+    }
+    if (!h->pq) h->pq = new PqState();
+    PqState& p = *h->pq;
+    p.free_index();
+    p.M = M; p.K = K; p.ss = ss; p.n = n;
+    p.cb = cb;
+    p.codes = codes;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_build_pq(lynse_hip_flat* h, uint32_t n_subspaces, uint32_t n_clusters) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_WRITER(h, lk);
+    LY_TRY(use_device(h));
+    LY_TRY(pq_check_handle(h));
+    return pq_build_locked(h, n_subspaces, n_clusters);
+}
+
+extern "C" int lynse_hip_flat_load_pq(lynse_hip_flat* h, uint32_t M, uint32_t K, const float* codebooks, const uint8_t* codes, uint64_t n) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_WRITER(h, lk);
+    LY_TRY(use_device(h));
+    LY_TRY(pq_check_handle(h));
+    // PQIndex::load's checks (pq_mmap.rs:481-494, :526-531)
+    if (M == 0 || K == 0 || K > 256 || h->dim % M != 0 || n > 0xffffffffull)
+        return set_error(LYNSE_ERR_INVALID_ARGUMENT, "Invalid PQ index dimensions");
+    if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
+    if (n > h->n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the PQ index covers more rows than the handle holds");
+    if (!codebooks || !codes) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint64_t i = 0; i < n * M; ++i)
+        if (codes[i] >= K) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "PQ index contains an out-of-range code");
+    const uint32_t ss = h->dim / M;
+    float* cb = nullptr;
+    uint8_t* cd = nullptr;
+    LY_HIP(hipMalloc(&cb, (size_t)M * K * ss * 4));
+    if (hipMalloc(&cd, (size_t)n * M) != hipSuccess) {
+        (void)hipFree(cb);
+        return set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(PQ codes)");
+    }
+    if (h2d_done(cb, codebooks, (size_t)M * K * ss * 4) != LYNSE_OK || h2d_done(cd, codes, (size_t)n * M) != LYNSE_OK) {
+        (void)hipFree(cb);
+        (void)hipFree(cd);
+        return LYNSE_ERR_DEVICE;
+    }
+    if (!h->pq) h->pq = new PqState();
+    PqState& p = *h->pq;
+    p.free_index();
+    p.M = M; p.K = K; p.ss = ss; p.n = n;
+    p.cb = cb;
+    p.codes = cd;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_pq_params(lynse_hip_flat* h, uint32_t* mks, uint64_t* n_pq, float* codebooks, uint8_t* codes) {
+    if (!h || !mks || !n_pq) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    if (!h->pq || !h->pq->cb) {
+        mks[0] = mks[1] = mks[2] = 0;
+        *n_pq = 0;
+        return LYNSE_OK;
+    }
+    const PqState& p = *h->pq;
+    mks[0] = p.M; mks[1] = p.K; mks[2] = p.ss;
+    *n_pq = p.n;
+    LY_TRY(use_device(h));
+    if (codebooks) LY_HIP(hipMemcpy(codebooks, p.cb, (size_t)p.M * p.K * p.ss * 4, hipMemcpyDeviceToHost));
+    if (codes) LY_HIP(hipMemcpy(codes, p.codes, (size_t)p.n * p.M, hipMemcpyDeviceToHost));
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_drop_pq(lynse_hip_flat* h) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_WRITER(h, lk);
+    LY_TRY(use_device(h));
+    if (h->pq) h->pq->free_index();
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_pq_stage_times(lynse_hip_flat* h, double* out3, int reset) {
+    if (!h || !out3) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    LY_WRITER(h, lk);
+    if (!h->pq) { out3[0] = out3[1] = out3[2] = 0.0; return LYNSE_OK; }
+    out3[0] = h->pq->searches;
+    out3[1] = h->pq->scan_us;
+    out3[2] = h->pq->rescore_us;
+    if (reset) h->pq->searches = h->pq->scan_us = h->pq->rescore_us = 0.0;
+    return LYNSE_OK;
+}
+
+// ---- search --------------------------------------------------------------------------------------------------------------------
+// PQIndex::search_candidates + rescore_exact_candidates (pq_mmap.rs:176-240, vector_store.rs:611-638): k' = min(k, n_pq),
+// N = min(k' * oversample, n_pq) rows by the canonical (ADC score, row) key, rescored with compute_distance_f32 on the original rows,
+// the best k' by (exact distance, row).  Queries go in chunks whose score matrix stays under 512 MiB.
+extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t oversample,
+                                            uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    if (metric_binary(metric)) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ is defined for ip / l2 / cosine");
+    if (nq == 0) return LYNSE_OK;
+    if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    LY_WRITER(h, lk);
+    LY_TRY(use_device(h));
+    LY_TRY(pq_check_handle(h));
+    if (!h->pq || !h->pq->cb) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no PQ index on this handle: build or load one first");
+    PqState& p = *h->pq;
+    const uint64_t n = p.n;
+    const uint32_t D = h->dim;
+    if (k == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n);
+    const uint32_t N = (uint32_t)std::min<uint64_t>((uint64_t)kk * oversample, n);
+    if (N == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
+    const bool asc = metric_ascending(metric);
+    uint32_t p2 = 2;
+    while (p2 < N) p2 <<= 1;
+    const size_t q_lds = ((size_t)D + 3) / 4 * 16;
+    if (q_lds > 160u * 1024u) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ rescore: the query does not fit in LDS");
+    const bool select_dev = N <= 16384 && (size_t)p2 * 8 + q_lds <= 160u * 1024u;
+    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (uint64_t)QCHUNK, (512ull << 20) / (n * 4), (256ull << 20) / ((uint64_t)N * 8)}));
+    LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
+    LY_TRY(ivf_grow(&p.d_lut, &p.lut_cap, (size_t)qc * p.M * p.K));
+    LY_TRY(ivf_grow(&p.d_S, &p.S_cap, (size_t)qc * n));
+    LY_TRY(ivf_grow(&p.d_sel, &p.sel_cap, (size_t)qc));
+    LY_TRY(ivf_grow(&p.d_prow, &p.prow_cap, (size_t)qc * N));
+    LY_TRY(ivf_grow(&p.d_pcnt, &p.pcnt_cap, (size_t)qc));
+    if (p.hist_cap < (size_t)qc * PQ_BINS) {
+        LY_TRY(ivf_grow(&p.d_hist, &p.hist_cap, (size_t)qc * PQ_BINS));
+        LY_TRY(memset_done(p.d_hist, 0, p.hist_cap * 4));   // k_pq_find clears what it read: zero between searches
+    }
+    if (select_dev) {
+        LY_TRY(ivf_grow(&p.d_orow, &p.orow_cap, (size_t)qc * k));
+        LY_TRY(ivf_grow(&p.d_odist, &p.odist_cap, (size_t)qc * k));
+        LY_TRY(ivf_grow(&p.d_ocnt, &p.ocnt_cap, (size_t)qc));
+    } else {
+        LY_TRY(ivf_grow(&p.d_keys, &p.keys_cap, (size_t)qc * N));
+    }
+    static std::once_flag lds_once;
+    static int lds_rc = LYNSE_OK;
+    std::call_once(lds_once, []() {
+        lds_rc = set_max_lds(k_ivfsq_rerank<true>, 160 * 1024);
+        if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_ivfsq_rerank<false>, 160 * 1024);
+    });
+    LY_TRY(lds_rc);
+    const bool timed = h->profiling.load();
+    if (timed)
+        for (hipEvent_t& e : p.ev)
+            if (!e) LY_HIP(hipEventCreate(&e));
+    hipStream_t st = cur(h).stream;
+    double scan_us = 0.0, rescore_us = 0.0;
+    std::vector<PqSel> sel0;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> pcnt;
+    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
+        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
+        LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+        if (timed) LY_HIP(hipEventRecord(p.ev[0], st));
+        const uint64_t lut_threads = (uint64_t)nqc * p.M * p.K;
+        hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, p.d_q, nqc, D, p.M, p.ss, p.K, p.cb,
+                           metric == M_IP ? 1 : 0, p.d_lut);
+        LY_HIP(hipGetLastError());
+        // the ADC scan: QB = 4 queries share a code load when the batch has them; tables in <= 64 KiB of LDS
+        const int qb = nqc >= 4 ? 4 : 1;
+        const uint32_t mc = std::max<uint32_t>(1, std::min<uint32_t>(p.M, 16384u / ((uint32_t)qb * p.K)));
+        PqAdcArgs aa{p.codes, n, p.M, p.K, mc, p.d_lut, nqc, asc ? 1 : 0, p.d_S};
+        const dim3 agrid((uint32_t)((n + PQ_NT * PQ_R - 1) / (PQ_NT * PQ_R)), (nqc + qb - 1) / qb);
+        const size_t alds = (size_t)qb * mc * p.K * 4;
+        if (qb == 4) hipLaunchKernelGGL(k_pq_adc<4>, agrid, dim3(PQ_NT), alds, st, aa);
+        else hipLaunchKernelGGL(k_pq_adc<1>, agrid, dim3(PQ_NT), alds, st, aa);
+        LY_HIP(hipGetLastError());
+        // the N best (score, row) keys -> pool rows
+        if (N < n) {
+            sel0.assign(nqc, PqSel{0ull, 64u, N, 0u, 0u});
+            LY_HIP(hipMemcpyAsync(p.d_sel, sel0.data(), (size_t)nqc * sizeof(PqSel), hipMemcpyHostToDevice, st));
+            const uint32_t rpb = 8192;
+            const dim3 hgrid((uint32_t)((n + rpb - 1) / rpb), nqc);
+            for (uint32_t pass = 0; pass < 6; ++pass) {
+                hipLaunchKernelGGL(k_pq_hist, hgrid, dim3(256), 0, st, p.d_S, n, p.d_sel, p.d_hist, rpb);
+                LY_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_pq_find, dim3(nqc), dim3(256), 0, st, p.d_sel, p.d_hist);
+                LY_HIP(hipGetLastError());
+            }
+            LY_HIP(hipMemsetAsync(p.d_pcnt, 0, (size_t)nqc * 4, st));
+            const uint32_t eblocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 1024));
+            hipLaunchKernelGGL(k_pq_emit, dim3(eblocks, nqc), dim3(256), 0, st, p.d_S, n, p.d_sel, N, p.d_prow, p.d_pcnt);
+            LY_HIP(hipGetLastError());
+        } else {
+            const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)nqc * n + 255) / 256, (uint64_t)h->num_cu * 32));
+            hipLaunchKernelGGL(k_pq_pool_all, dim3(blocks), dim3(256), 0, st, n, nqc, N, p.d_prow, p.d_pcnt);
+            LY_HIP(hipGetLastError());
+        }
+        if (timed) LY_HIP(hipEventRecord(p.ev[1], st));
+        IvfSqRerankArgs a{h->rows, n, h->ld, D, p.d_q, p.d_prow, p.d_pcnt, N, p2, metric, kk, k, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (select_dev) {
+            a.out_rows = p.d_orow;
+            a.out_dists = p.d_odist;
+            a.out_counts = p.d_ocnt;
+            hipLaunchKernelGGL(k_ivfsq_rerank<true>, dim3(nqc), dim3(256), (size_t)p2 * 8 + q_lds, st, a);
+            LY_HIP(hipGetLastError());
+            if (timed) LY_HIP(hipEventRecord(p.ev[2], st));
+            LY_HIP(hipMemcpyAsync(out_rows + q0 * k, p.d_orow, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(out_dists + q0 * k, p.d_odist, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(out_counts + q0, p.d_ocnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+            LY_TRY(stream_wait(st));
+        } else {   // N > 16,384: every pool entry scored on the device, the canonical best k' selected on the host
+            a.keys_out = p.d_keys;
+            hipLaunchKernelGGL(k_ivfsq_rerank<false>, dim3(nqc), dim3(256), q_lds, st, a);
+            LY_HIP(hipGetLastError());
+            if (timed) LY_HIP(hipEventRecord(p.ev[2], st));
+            keys.resize((size_t)nqc * N);
+            pcnt.resize(nqc);
+            LY_HIP(hipMemcpyAsync(keys.data(), p.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(pcnt.data(), p.d_pcnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipStreamSynchronize(st));
+            const auto t_sel = std::chrono::steady_clock::now();
+            for (uint32_t q = 0; q < nqc; ++q) {
+                const uint32_t P = std::min<uint32_t>(pcnt[q], N);
+                auto b = keys.begin() + (size_t)q * N;
+                const uint32_t cnt = std::min<uint32_t>(kk, P);
+                std::partial_sort(b, b + cnt, b + P);   // ascending keys = (distance in metric order, row)
+                for (uint32_t i = 0; i < k; ++i) {
+                    out_rows[(q0 + q) * k + i] = i < cnt ? (uint64_t)key_row(b[i]) : ~0ull;
+                    out_dists[(q0 + q) * k + i] = i < cnt ? key_score(b[i], asc) : (asc ? INFINITY : -INFINITY);
+                }
+                out_counts[q0 + q] = cnt;
+            }
+            if (timed) rescore_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sel).count();
+        }
+        if (timed) {
+            float a_ms = 0.f, b_ms = 0.f;
+            LY_HIP(hipEventElapsedTime(&a_ms, p.ev[0], p.ev[1]));
+            LY_HIP(hipEventElapsedTime(&b_ms, p.ev[1], p.ev[2]));
+            scan_us += (double)a_ms * 1000.0;
+            rescore_us += (double)b_ms * 1000.0;
+        }
+    }
+    if (timed) { p.searches += 1; p.scan_us += scan_us; p.rescore_us += rescore_us; }
+    return LYNSE_OK;
+}

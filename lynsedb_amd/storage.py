@@ -281,3 +281,62 @@ def save_ivf_flat(data_path, index, data: np.ndarray) -> IvfMeta:
     meta = IvfMeta(cen.shape[1], slab.shape[0], cen.shape[0], cen, off, orig)
     save_ivf_meta(ivf_meta_path(data_path), meta)
     return meta
+
+
+# ---- pq_index.bin (PQIndex::save / load, src/storage/pq_mmap.rs:431-541) ------------------------------------------------------
+PQ_MAGIC = 0x5051_4D4D   # "PQMM"
+PQ_VERSION = 1
+
+
+@dataclass
+class PqIndexFile:
+    n_subspaces: int
+    n_clusters: int
+    subspace_size: int
+    dim: int
+    codebooks: np.ndarray   # f32 [M][K][ss]
+    codes: np.ndarray       # u8 [n][M]
+
+    @property
+    def n_vectors(self) -> int:
+        return int(self.codes.shape[0])
+
+
+def save_pq_index(path, pq: PqIndexFile) -> None:
+    """32-byte little-endian header (magic, version, M, K, ss as u32, n as u64, dim as u32), the f32 codebooks, the u8 codes."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    cb = np.ascontiguousarray(pq.codebooks, dtype="<f4").reshape(-1)
+    codes = np.ascontiguousarray(pq.codes, dtype=np.uint8).reshape(-1)
+    header = np.array([PQ_MAGIC, PQ_VERSION, pq.n_subspaces, pq.n_clusters, pq.subspace_size], "<u4").tobytes()
+    header += np.array([pq.n_vectors], "<u8").tobytes() + np.array([pq.dim], "<u4").tobytes()
+    with open(path, "wb") as f:
+        f.write(header)
+        f.write(cb.tobytes())
+        f.write(codes.tobytes())
+
+
+def load_pq_index(path) -> PqIndexFile:
+    """PQIndex::load with the reference's checks and messages (IOError = its io::Error)."""
+    raw = Path(path).read_bytes()
+    if len(raw) < 32:
+        if len(raw) >= 4 and int(np.frombuffer(raw[:4], "<u4")[0]) != PQ_MAGIC:
+            raise IOError("Invalid PQ magic bytes")
+        raise IOError("failed to fill whole buffer")
+    magic, version, m, k, ss = (int(x) for x in np.frombuffer(raw[:20], "<u4"))
+    n = int(np.frombuffer(raw[20:28], "<u8")[0])
+    dim = int(np.frombuffer(raw[28:32], "<u4")[0])
+    if magic != PQ_MAGIC:
+        raise IOError("Invalid PQ magic bytes")
+    if version != PQ_VERSION:
+        raise IOError(f"Unsupported PQ version: {version}")
+    if m == 0 or not (1 <= k <= 256) or ss == 0 or m * ss != dim or n > 0xFFFFFFFF:
+        raise IOError("Invalid PQ index dimensions")
+    cb_len, code_len = m * k * ss, n * m
+    if len(raw) < 32 + 4 * cb_len + code_len:
+        raise IOError("failed to fill whole buffer")
+    cb = np.frombuffer(raw, "<f4", cb_len, 32).astype(np.float32).reshape(m, k, ss)
+    codes = np.frombuffer(raw, np.uint8, code_len, 32 + 4 * cb_len).reshape(n, m).copy()
+    if codes.size and int(codes.max()) >= k:
+        raise IOError("PQ index contains an out-of-range code")
+    return PqIndexFile(m, k, ss, dim, cb, codes)
