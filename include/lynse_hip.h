@@ -354,7 +354,7 @@ int lynse_hip_ivf_load_sq8(const float *rows, uint64_t n, uint32_t dim, const fl
 int lynse_hip_ivf_sq8_params(const lynse_hip_ivf *h, float *mins, float *scales);
 /* No reference counterpart (QueryProfile.rerank_us, src/engine.rs:6906-6919, is what it feeds): with lynse_hip_ivf_profile_enable on,
  * the SQ8 searches timed so far and their summed stage times in microseconds, from HIP events on the search stream:
- * out3[0] searches, out3[1] the pool stage (after the query codec -> after the pool stage), out3[2] the rerank (k_ivfsq_rerank, plus
+ * out3[0] searches, out3[1] the pool stage (after the query codec -> after the pool stage), out3[2] the rerank (k_pool_rerank, plus
  * the host selection of a pool beyond 16,384).  reset != 0 clears them. */
 int lynse_hip_ivf_sq8_stage_times(lynse_hip_ivf *h, double *out3, int reset);
 /* IVFIndex::insert (src/index/ivf.rs:392-441): `rows` (n x dim f32; a binary index pushes them through its quantizer) are

@@ -65,14 +65,8 @@ struct lynse_hip_ivf {
     float* d_raw = nullptr;           // n x dim original rows
     struct Sq8Scratch {               // per-search buffers of the SQ8 path (grown on demand; searches hold the guard)
         float* d_q = nullptr; size_t q_cap = 0;
-        uint64_t* d_prow = nullptr; size_t prow_cap = 0;
         float* d_pdist = nullptr; size_t pdist_cap = 0;
-        uint32_t* d_pcnt = nullptr; size_t pcnt_cap = 0;
-        uint64_t* d_keys = nullptr; size_t keys_cap = 0;
-        uint64_t* d_orow = nullptr; size_t orow_cap = 0;
-        float* d_odist = nullptr; size_t odist_cap = 0;
-        uint32_t* d_ocnt = nullptr; size_t ocnt_cap = 0;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // profiling: after the query codec / after the pool stage / after the rerank
+        PoolRerank rr;                // the pool's rows and counts, the rerank's buffers and timing events
     } sq;
     // profiling (lynse_hip_ivf_sq8_stage_times): searches timed, and the pool stage / the rerank in microseconds (HIP events on the
     // search stream; the host selection of a pool beyond the LDS counts to the rerank)
@@ -109,11 +103,9 @@ static void ivf_free(lynse_hip_ivf* h) {
     if (h->store) {
         (void)hipSetDevice(h->store->device);
         for (void* p : {(void*)h->d_orig, (void*)h->d_offsets, (void*)h->d_centroids, (void*)h->d_rdims, (void*)h->d_bq_thr, (void*)h->d_smask,
-                        (void*)h->d_sq, (void*)h->d_raw, (void*)h->sq.d_q, (void*)h->sq.d_prow, (void*)h->sq.d_pdist, (void*)h->sq.d_pcnt,
-                        (void*)h->sq.d_keys, (void*)h->sq.d_orow, (void*)h->sq.d_odist, (void*)h->sq.d_ocnt})
+                        (void*)h->d_sq, (void*)h->d_raw, (void*)h->sq.d_q, (void*)h->sq.d_pdist})
             if (p) (void)hipFree(p);
-        for (hipEvent_t e : h->sq.ev)
-            if (e) (void)hipEventDestroy(e);
+        h->sq.rr.release();
         for (auto& x : h->scr) x.release();
         if (h->cstore) lynse_hip_flat_destroy(h->cstore);
         lynse_hip_flat_destroy(h->store);
@@ -1731,7 +1723,6 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
                 if (!allowed || (*allowed)[h->orig[p]]) pos.push_back((uint32_t)p);
         }
         const uint32_t P = (uint32_t)pos.size();
-        uint32_t cnt = 0;
         if (P) {
             if (P > cap_pos) {
                 if (d_pos) (void)hipFree(d_pos);
@@ -1753,15 +1744,8 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
             keys.resize(P);
             LY_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)P * 8, hipMemcpyDeviceToHost, st));
             LY_HIP(hipStreamSynchronize(st));
-            cnt = std::min<uint32_t>(kk, P);
-            std::partial_sort(keys.begin(), keys.begin() + cnt, keys.end());   // ascending keys = (distance in metric order, original row)
-            for (uint32_t i = 0; i < cnt; ++i) {
-                res_rows[q * k + i] = (uint64_t)key_row(keys[i]) * h->row_stride + h->row_offset;
-                res_dists[q * k + i] = key_score(keys[i], asc);
-            }
         }
-        for (uint32_t i = cnt; i < k; ++i) { res_rows[q * k + i] = ~0ull; res_dists[q * k + i] = asc ? INFINITY : -INFINITY; }
-        res_counts[q] = cnt;
+        res_counts[q] = select_pool_keys(keys.data(), P, kk, k, asc, res_rows + q * k, res_dists + q * k, h->row_stride, h->row_offset);
     }
     if (on_device) {
         LY_TRY(h2d_done(out_rows, o_rows.data(), o_rows.size() * 8));
@@ -1894,8 +1878,8 @@ static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq
 // the ordinary IVF search of the decoded query over the decoded slab store with k = pool = min(max(10 k, k), n) — the same centroid
 // ranking, probe rule, all-lists-empty fallback, subset, kernels and plans (certified int8 pass, large-k path) — so each query's
 // pool is the best min(pool, |candidates|) candidates by (decoded distance, original row), left in device memory.  The RERANK
-// (k_ivfsq_rerank) scores them exactly against the original query and rows and keeps the best min(k, pool) by (exact distance,
-// original row); a pool above what one workgroup's LDS sorts (16,384 keys) is scored on the device and selected on the host.
+// (PoolRerank, rerank_host.inc) scores them exactly against the original query and rows and keeps the best min(k, pool) by
+// (exact distance, original row); a pool above what one workgroup's LDS sorts (16,384 keys) is selected on the host.
 // The rerank adds its pool entries to the search context's rescored-candidate counter (lynse_hip_ivf_profile_get: pool_entries =
 // the pool stage's exact rescoring + the rerank).
 static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
@@ -1916,42 +1900,15 @@ static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, u
         if (!any) return zero_counts();
     }
     const uint32_t pool = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(10ull * k, k), n);
-    const bool asc = metric_ascending(h->metric);
-    uint32_t p2 = 2;
-    while (p2 < pool) p2 <<= 1;
-    const size_t q_lds = ((size_t)D + 3) / 4 * 16;
-    if (q_lds > 160u * 1024u) return set_error(LYNSE_ERR_UNSUPPORTED, "IVF-*-SQ8 rerank: the query does not fit in LDS");
-    const bool select_dev = pool <= 16384 && (size_t)p2 * 8 + q_lds <= 160u * 1024u;
     const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>(QCHUNK, (256ull << 20) / ((uint64_t)pool * 16)));
     auto& sc = h->sq;
     LY_HIP(hipSetDevice(s->device));
+    PoolRerank::Search rr(sc.rr);
+    LY_TRY(rr.begin(h->d_raw, n, D, D, h->metric, pool, k, k, qc, on_device, s->profiling.load(), "IVF-*-SQ8 rerank"));
     LY_TRY(ivf_grow(&sc.d_q, &sc.q_cap, (size_t)qc * D * 2));
-    LY_TRY(ivf_grow(&sc.d_prow, &sc.prow_cap, (size_t)qc * pool));
     LY_TRY(ivf_grow(&sc.d_pdist, &sc.pdist_cap, (size_t)qc * pool));
-    LY_TRY(ivf_grow(&sc.d_pcnt, &sc.pcnt_cap, (size_t)qc));
-    if (!select_dev) LY_TRY(ivf_grow(&sc.d_keys, &sc.keys_cap, (size_t)qc * pool));
-    if (select_dev && !on_device) {
-        LY_TRY(ivf_grow(&sc.d_orow, &sc.orow_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&sc.d_odist, &sc.odist_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&sc.d_ocnt, &sc.ocnt_cap, (size_t)qc));
-    }
-    static std::once_flag lds_once;
-    static int lds_rc = LYNSE_OK;
-    std::call_once(lds_once, []() {
-        lds_rc = set_max_lds(k_ivfsq_rerank<true>, 160 * 1024);
-        if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_ivfsq_rerank<false>, 160 * 1024);
-    });
-    LY_TRY(lds_rc);
-    const bool timed = s->profiling.load();
-    if (timed)
-        for (hipEvent_t& e : sc.ev)
-            if (!e) LY_HIP(hipEventCreate(&e));
-    double pool_us = 0.0, rerank_us = 0.0;
     float* d_qo = sc.d_q;                       // original queries
     float* d_qd = sc.d_q + (size_t)qc * D;      // decoded queries
-    std::vector<uint64_t> keys, h_rows;
-    std::vector<uint32_t> pcnt, h_cnt;
-    std::vector<float> h_dists;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
         {
@@ -1960,75 +1917,17 @@ static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, u
             hipStream_t st = cur(s).stream;
             LY_HIP(hipMemcpyAsync(d_qo, queries + q0 * D, (size_t)nqc * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
             LY_TRY(sq_codec_device(d_qo, nqc, D, h->d_sq, d_qd, st));
-            if (timed) LY_HIP(hipEventRecord(sc.ev[0], st));
+            LY_TRY(rr.pool_start(st));
             LY_HIP(hipStreamSynchronize(st));
         }
         // pool stage: the decoded queries over the decoded rows, k = pool, results left in device memory
-        LY_TRY(ivf_search_locked(h, d_qd, nqc, pool, nprobe, sc.d_prow, sc.d_pdist, sc.d_pcnt, filtered, subset, n_subset, -1, true));
+        LY_TRY(ivf_search_locked(h, d_qd, nqc, pool, nprobe, sc.rr.d_prow, sc.d_pdist, sc.rr.d_pcnt, filtered, subset, n_subset, -1, true));
         std::unique_lock<std::shared_mutex> lk(s->rw);
         LY_TRY(use_device(s));
-        hipStream_t st = cur(s).stream;
-        if (timed) LY_HIP(hipEventRecord(sc.ev[1], st));
-        IvfSqRerankArgs a{h->d_raw, n, D, D, d_qo, sc.d_prow, sc.d_pcnt, pool, p2, h->metric, k, k, nullptr, nullptr, nullptr, nullptr,
-                          s->profiling.load() ? cur(s).ws.pool_total : nullptr};
-        if (select_dev) {
-            a.out_rows = on_device ? out_rows + q0 * k : sc.d_orow;
-            a.out_dists = on_device ? out_dists + q0 * k : sc.d_odist;
-            a.out_counts = on_device ? out_counts + q0 : sc.d_ocnt;
-            hipLaunchKernelGGL(k_ivfsq_rerank<true>, dim3(nqc), dim3(256), (size_t)p2 * 8 + q_lds, st, a);
-            LY_HIP(hipGetLastError());
-            if (timed) LY_HIP(hipEventRecord(sc.ev[2], st));
-            if (!on_device) {
-                LY_HIP(hipMemcpyAsync(out_rows + q0 * k, sc.d_orow, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
-                LY_HIP(hipMemcpyAsync(out_dists + q0 * k, sc.d_odist, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
-                LY_HIP(hipMemcpyAsync(out_counts + q0, sc.d_ocnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-            }
-            LY_HIP(hipStreamSynchronize(st));
-        } else {   // k > 1,638: every pool entry scored on the device, the canonical top k on the host (as ivf_search_large_k)
-            a.keys_out = sc.d_keys;
-            hipLaunchKernelGGL(k_ivfsq_rerank<false>, dim3(nqc), dim3(256), q_lds, st, a);
-            LY_HIP(hipGetLastError());
-            if (timed) LY_HIP(hipEventRecord(sc.ev[2], st));
-            keys.resize((size_t)nqc * pool);
-            pcnt.resize(nqc);
-            LY_HIP(hipMemcpyAsync(keys.data(), sc.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipMemcpyAsync(pcnt.data(), sc.d_pcnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipStreamSynchronize(st));
-            const auto t_sel = std::chrono::steady_clock::now();
-            h_rows.resize((size_t)nqc * k);
-            h_dists.resize((size_t)nqc * k);
-            h_cnt.resize(nqc);
-            for (uint32_t q = 0; q < nqc; ++q) {
-                const uint32_t P = std::min<uint32_t>(pcnt[q], pool);
-                auto b = keys.begin() + (size_t)q * pool;
-                const uint32_t cnt = std::min<uint32_t>(k, P);
-                std::partial_sort(b, b + cnt, b + P);   // ascending keys = (distance in metric order, original row)
-                for (uint32_t i = 0; i < k; ++i) {
-                    h_rows[(size_t)q * k + i] = i < cnt ? (uint64_t)key_row(b[i]) : ~0ull;
-                    h_dists[(size_t)q * k + i] = i < cnt ? key_score(b[i], asc) : (asc ? INFINITY : -INFINITY);
-                }
-                h_cnt[q] = cnt;
-            }
-            if (timed) rerank_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sel).count();
-            if (on_device) {
-                LY_TRY(h2d_done(out_rows + q0 * k, h_rows.data(), h_rows.size() * 8));
-                LY_TRY(h2d_done(out_dists + q0 * k, h_dists.data(), h_dists.size() * 4));
-                LY_TRY(h2d_done(out_counts + q0, h_cnt.data(), h_cnt.size() * 4));
-            } else {
-                memcpy(out_rows + q0 * k, h_rows.data(), h_rows.size() * 8);
-                memcpy(out_dists + q0 * k, h_dists.data(), h_dists.size() * 4);
-                memcpy(out_counts + q0, h_cnt.data(), h_cnt.size() * 4);
-            }
-        }
-        if (timed) {   // (the stream was synchronised behind the rerank in both branches)
-            float a_ms = 0.f, b_ms = 0.f;
-            LY_HIP(hipEventElapsedTime(&a_ms, sc.ev[0], sc.ev[1]));
-            LY_HIP(hipEventElapsedTime(&b_ms, sc.ev[1], sc.ev[2]));
-            pool_us += (double)a_ms * 1000.0;
-            rerank_us += (double)b_ms * 1000.0;
-        }
+        LY_TRY(rr.run(d_qo, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, s->profiling.load() ? cur(s).ws.pool_total : nullptr,
+                      cur(s).stream));
     }
-    if (timed) { h->sq_searches += 1; h->sq_pool_us += pool_us; h->sq_rerank_us += rerank_us; }
+    if (rr.timed) { h->sq_searches += 1; h->sq_pool_us += rr.pool_us; h->sq_rerank_us += rr.rerank_us; }
     return LYNSE_OK;
 }
 

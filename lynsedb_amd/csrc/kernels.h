@@ -4554,7 +4554,7 @@ __global__ void __launch_bounds__(NT) k_merge(MergeArgs a) {
 //   k_ivfsq_minmax / k_ivfsq_fit   ScalarQuantizer::fit: per-dimension min / max from f32::MAX / f32::MIN with strict
 //                                  `<` / `>` in row order (NaN never wins; of equal values the first row's stays: -0 / +0)
 //   k_ivfsq_codec                  encode -> decode of rows or queries (codes optional)
-//   k_ivfsq_rerank                 the exact rerank of the decoded-distance pool against the ORIGINAL rows
+//   k_pool_rerank                  the exact rerank of a candidate pool against the ORIGINAL rows (also FLAT-PQ's rescore)
 // ------------------------------------------------------------------------------------------------
 // thread = one dimension (coalesced across a row), blockIdx.y = a strip of rows scanned in row order; partials[strip][d]
 __global__ void __launch_bounds__(256) k_ivfsq_minmax(const float* __restrict__ V, uint32_t D, uint64_t n,
@@ -4607,14 +4607,14 @@ __global__ void __launch_bounds__(256) k_ivfsq_codec(const float* V, uint64_t n,
     }
 }
 
-// One workgroup per query.  The pool stage (the IVF scan over the decoded slab with k = pool) left the pool's original
-// row ids in pool_rows[q * pool_ld ..] (pool_cnt[q] of them, best-first by decoded distance); the original query is
-// staged in LDS, the original rows (row-major, `ld` floats, original row order) are gathered and scored with the
+// One workgroup per query.  A pool stage (IVF-SQ8's IVF scan over the decoded slab with k = pool, FLAT-PQ's ADC scan and
+// pool cut) left the pool's original row ids in pool_rows[q * pool_ld ..] (pool_cnt[q] of them, in any order); the original
+// query is staged in LDS, the original rows (row-major, `ld` floats, original row order) are gathered and scored with the
 // single-row kernels — compute_distance_f32, lo_compute_distance — and, SELECT, the pool is sorted by the canonical
 // (distance, original row) key in LDS (bitonic over p2 >= pool_cnt keys) and the best min(k, pool) written in the layout of
 // lynse_hip_ivf_search_f32 (rows ~0 / worst distance padding, counts).  !SELECT: the keys go to keys_out[q * pool_ld ..]
-// for a host selection (pools beyond the LDS).
-struct IvfSqRerankArgs {
+// for a host selection (pools beyond the LDS).  Host side: PoolRerank (rerank_host.inc).
+struct PoolRerankArgs {
     const float* V;
     uint64_t n;              // rows of V
     uint32_t ld, D;
@@ -4633,7 +4633,7 @@ struct IvfSqRerankArgs {
 };
 
 template <bool SELECT>
-__global__ void __launch_bounds__(256) k_ivfsq_rerank(IvfSqRerankArgs a) {
+__global__ void __launch_bounds__(256) k_pool_rerank(PoolRerankArgs a) {
     extern __shared__ uint64_t sm_rr[];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const int g = tid & 7;

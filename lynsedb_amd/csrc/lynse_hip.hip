@@ -3816,6 +3816,7 @@ static int stream_wait_bounded(hipStream_t st, hipEvent_t* ev, uint32_t timeout_
 constexpr uint32_t STATUS_OVERFLOW = 1u, STATUS_EMPTY_LISTS = 2u, STATUS_REDO = STATUS_OVERFLOW | STATUS_EMPTY_LISTS;
 static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u; }
 
+#include "rerank_host.inc"
 #include "ivf_host.inc"
 #include "shard_host.inc"
 #include "comm_host.inc"

@@ -1,6 +1,6 @@
 // pq.h — FLAT-{IP,L2,COS}-PQ (PQIndex, src/storage/pq_mmap.rs): the product quantiser's training, encode, ADC lookup tables,
 // the ADC scan over the u8 codes and the exact selection of the N best ADC scores.  The exact rescore of those N rows is
-// k_ivfsq_rerank (kernels.h).  DESIGN.md §12.
+// k_pool_rerank (kernels.h).  DESIGN.md §12.
 //   k_pq_gather     the training sample (rows 0, s, 2s, ...) as a dense n x dim matrix
 //   k_pq_init       random_init_centroids after the host drew the indices (the SmallRng stream is host code)
 //   k_pq_assign     assignment of rows against one subspace's K codewords (training and encode)

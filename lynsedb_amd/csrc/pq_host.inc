@@ -1,5 +1,5 @@
 // pq_host.inc — FLAT-{IP,L2,COS}-PQ on a FLAT handle (PQIndex, src/storage/pq_mmap.rs; Collection, src/engine.rs:4559-4600,
-// :5504-5526).  Included at the end of lynse_hip.hip; kernels in pq.h, the exact rescore is k_ivfsq_rerank (kernels.h).
+// :5504-5526).  Included at the end of lynse_hip.hip; kernels in pq.h, the exact rescore is k_pool_rerank (kernels.h).
 // DESIGN.md §12.
 
 // The quantiser and the per-handle search scratch.  Codes cover the first n rows of the handle: rows appended after a build or a
@@ -11,15 +11,11 @@ struct PqState {
     uint8_t* codes = nullptr;     // [n][M] u8 codes
     float *d_q = nullptr, *d_lut = nullptr;
     size_t q_cap = 0, lut_cap = 0;
-    uint32_t *d_S = nullptr, *d_hist = nullptr, *d_pcnt = nullptr, *d_ocnt = nullptr;
-    size_t S_cap = 0, hist_cap = 0, pcnt_cap = 0, ocnt_cap = 0;
+    uint32_t *d_S = nullptr, *d_hist = nullptr;
+    size_t S_cap = 0, hist_cap = 0;
     PqSel* d_sel = nullptr;
     size_t sel_cap = 0;
-    uint64_t *d_prow = nullptr, *d_keys = nullptr, *d_orow = nullptr;
-    size_t prow_cap = 0, keys_cap = 0, orow_cap = 0;
-    float* d_odist = nullptr;
-    size_t odist_cap = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // profiling: before the tables / after the pool cut / after the rescore
+    PoolRerank rr;                // the pool's rows and counts, the rescore's buffers and timing events
     double searches = 0.0, scan_us = 0.0, rescore_us = 0.0;
 
     void free_index() {
@@ -32,11 +28,9 @@ struct PqState {
     }
     ~PqState() {
         free_index();
-        for (void* p : {(void*)d_q, (void*)d_lut, (void*)d_S, (void*)d_hist, (void*)d_pcnt, (void*)d_ocnt, (void*)d_sel, (void*)d_prow,
-                        (void*)d_keys, (void*)d_orow, (void*)d_odist})
+        for (void* p : {(void*)d_q, (void*)d_lut, (void*)d_S, (void*)d_hist, (void*)d_sel})
             if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+        rr.release();
     }
 };
 
@@ -344,49 +338,23 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
     const uint32_t N = (uint32_t)std::min<uint64_t>((uint64_t)kk * oversample, n);
     if (N == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
     const bool asc = metric_ascending(metric);
-    uint32_t p2 = 2;
-    while (p2 < N) p2 <<= 1;
-    const size_t q_lds = ((size_t)D + 3) / 4 * 16;
-    if (q_lds > 160u * 1024u) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ rescore: the query does not fit in LDS");
-    const bool select_dev = N <= 16384 && (size_t)p2 * 8 + q_lds <= 160u * 1024u;
     const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (uint64_t)QCHUNK, (512ull << 20) / (n * 4), (256ull << 20) / ((uint64_t)N * 8)}));
+    PoolRerank::Search rr(p.rr);
+    LY_TRY(rr.begin(h->rows, n, h->ld, D, metric, N, kk, k, qc, false, h->profiling.load(), "PQ rescore"));
     LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
     LY_TRY(ivf_grow(&p.d_lut, &p.lut_cap, (size_t)qc * p.M * p.K));
     LY_TRY(ivf_grow(&p.d_S, &p.S_cap, (size_t)qc * n));
     LY_TRY(ivf_grow(&p.d_sel, &p.sel_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&p.d_prow, &p.prow_cap, (size_t)qc * N));
-    LY_TRY(ivf_grow(&p.d_pcnt, &p.pcnt_cap, (size_t)qc));
     if (p.hist_cap < (size_t)qc * PQ_BINS) {
         LY_TRY(ivf_grow(&p.d_hist, &p.hist_cap, (size_t)qc * PQ_BINS));
         LY_TRY(memset_done(p.d_hist, 0, p.hist_cap * 4));   // k_pq_find clears what it read: zero between searches
     }
-    if (select_dev) {
-        LY_TRY(ivf_grow(&p.d_orow, &p.orow_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&p.d_odist, &p.odist_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&p.d_ocnt, &p.ocnt_cap, (size_t)qc));
-    } else {
-        LY_TRY(ivf_grow(&p.d_keys, &p.keys_cap, (size_t)qc * N));
-    }
-    static std::once_flag lds_once;
-    static int lds_rc = LYNSE_OK;
-    std::call_once(lds_once, []() {
-        lds_rc = set_max_lds(k_ivfsq_rerank<true>, 160 * 1024);
-        if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_ivfsq_rerank<false>, 160 * 1024);
-    });
-    LY_TRY(lds_rc);
-    const bool timed = h->profiling.load();
-    if (timed)
-        for (hipEvent_t& e : p.ev)
-            if (!e) LY_HIP(hipEventCreate(&e));
     hipStream_t st = cur(h).stream;
-    double scan_us = 0.0, rescore_us = 0.0;
     std::vector<PqSel> sel0;
-    std::vector<uint64_t> keys;
-    std::vector<uint32_t> pcnt;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
         LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        if (timed) LY_HIP(hipEventRecord(p.ev[0], st));
+        LY_TRY(rr.pool_start(st));
         const uint64_t lut_threads = (uint64_t)nqc * p.M * p.K;
         hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, p.d_q, nqc, D, p.M, p.ss, p.K, p.cb,
                            metric == M_IP ? 1 : 0, p.d_lut);
@@ -412,60 +380,17 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
                 hipLaunchKernelGGL(k_pq_find, dim3(nqc), dim3(256), 0, st, p.d_sel, p.d_hist);
                 LY_HIP(hipGetLastError());
             }
-            LY_HIP(hipMemsetAsync(p.d_pcnt, 0, (size_t)nqc * 4, st));
+            LY_HIP(hipMemsetAsync(p.rr.d_pcnt, 0, (size_t)nqc * 4, st));
             const uint32_t eblocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 1024));
-            hipLaunchKernelGGL(k_pq_emit, dim3(eblocks, nqc), dim3(256), 0, st, p.d_S, n, p.d_sel, N, p.d_prow, p.d_pcnt);
+            hipLaunchKernelGGL(k_pq_emit, dim3(eblocks, nqc), dim3(256), 0, st, p.d_S, n, p.d_sel, N, p.rr.d_prow, p.rr.d_pcnt);
             LY_HIP(hipGetLastError());
         } else {
             const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)nqc * n + 255) / 256, (uint64_t)h->num_cu * 32));
-            hipLaunchKernelGGL(k_pq_pool_all, dim3(blocks), dim3(256), 0, st, n, nqc, N, p.d_prow, p.d_pcnt);
+            hipLaunchKernelGGL(k_pq_pool_all, dim3(blocks), dim3(256), 0, st, n, nqc, N, p.rr.d_prow, p.rr.d_pcnt);
             LY_HIP(hipGetLastError());
         }
-        if (timed) LY_HIP(hipEventRecord(p.ev[1], st));
-        IvfSqRerankArgs a{h->rows, n, h->ld, D, p.d_q, p.d_prow, p.d_pcnt, N, p2, metric, kk, k, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (select_dev) {
-            a.out_rows = p.d_orow;
-            a.out_dists = p.d_odist;
-            a.out_counts = p.d_ocnt;
-            hipLaunchKernelGGL(k_ivfsq_rerank<true>, dim3(nqc), dim3(256), (size_t)p2 * 8 + q_lds, st, a);
-            LY_HIP(hipGetLastError());
-            if (timed) LY_HIP(hipEventRecord(p.ev[2], st));
-            LY_HIP(hipMemcpyAsync(out_rows + q0 * k, p.d_orow, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipMemcpyAsync(out_dists + q0 * k, p.d_odist, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipMemcpyAsync(out_counts + q0, p.d_ocnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-            LY_TRY(stream_wait(st));
-        } else {   // N > 16,384: every pool entry scored on the device, the canonical best k' selected on the host
-            a.keys_out = p.d_keys;
-            hipLaunchKernelGGL(k_ivfsq_rerank<false>, dim3(nqc), dim3(256), q_lds, st, a);
-            LY_HIP(hipGetLastError());
-            if (timed) LY_HIP(hipEventRecord(p.ev[2], st));
-            keys.resize((size_t)nqc * N);
-            pcnt.resize(nqc);
-            LY_HIP(hipMemcpyAsync(keys.data(), p.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipMemcpyAsync(pcnt.data(), p.d_pcnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-            LY_HIP(hipStreamSynchronize(st));
-            const auto t_sel = std::chrono::steady_clock::now();
-            for (uint32_t q = 0; q < nqc; ++q) {
-                const uint32_t P = std::min<uint32_t>(pcnt[q], N);
-                auto b = keys.begin() + (size_t)q * N;
-                const uint32_t cnt = std::min<uint32_t>(kk, P);
-                std::partial_sort(b, b + cnt, b + P);   // ascending keys = (distance in metric order, row)
-                for (uint32_t i = 0; i < k; ++i) {
-                    out_rows[(q0 + q) * k + i] = i < cnt ? (uint64_t)key_row(b[i]) : ~0ull;
-                    out_dists[(q0 + q) * k + i] = i < cnt ? key_score(b[i], asc) : (asc ? INFINITY : -INFINITY);
-                }
-                out_counts[q0 + q] = cnt;
-            }
-            if (timed) rescore_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sel).count();
-        }
-        if (timed) {
-            float a_ms = 0.f, b_ms = 0.f;
-            LY_HIP(hipEventElapsedTime(&a_ms, p.ev[0], p.ev[1]));
-            LY_HIP(hipEventElapsedTime(&b_ms, p.ev[1], p.ev[2]));
-            scan_us += (double)a_ms * 1000.0;
-            rescore_us += (double)b_ms * 1000.0;
-        }
+        LY_TRY(rr.run(p.d_q, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, nullptr, st));
     }
-    if (timed) { p.searches += 1; p.scan_us += scan_us; p.rescore_us += rescore_us; }
+    if (rr.timed) { p.searches += 1; p.scan_us += rr.pool_us; p.rescore_us += rr.rerank_us; }
     return LYNSE_OK;
 }

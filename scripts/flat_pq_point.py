@@ -7,7 +7,7 @@ took on top of the rows, from hipMemGetInfo through torch), then times, per batc
 calls through the Python wrapper, host queries and outputs):
   pq          the whole PQ search (tables + ADC scan + pool cut + exact rescore), profiling off;
   scan_stage  tables + ADC scan + pool cut, HIP events (lynse_hip_flat_pq_stage_times, profiling on; mean per search);
-  rescore     k_ivfsq_rerank over the pool, the same way;
+  rescore     k_pool_rerank over the pool, the same way;
   flat        the exact FLAT search of the same rows.
 recall@k is the overlap of the PQ answer with the exact FLAT answer over 256 queries.  Prints one JSON line.
 """

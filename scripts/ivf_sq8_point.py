@@ -6,7 +6,7 @@ Builds an SQ8 index over a clustered collection (device k-means on the decoded r
 queries (median of --reps blocking C-ABI calls through the Python wrapper, host queries and outputs):
   sq8          the whole SQ8 search (query codec + pool stage + rerank), profiling off;
   pool_stage   the SQ8 pool stage, HIP events on the search stream (lynse_hip_ivf_sq8_stage_times, profiling on; mean per search);
-  rerank       k_ivfsq_rerank, the same way;
+  rerank       k_pool_rerank, the same way;
   ivf_flat_k100  IVF-Flat over the DECODED rows with the same lists at k = pool = 10 k (the pool stage as a search of its own);
   ivf_flat     IVF-Flat over the ORIGINAL rows with the same centroids / lists at k.
 Prints one JSON line.
