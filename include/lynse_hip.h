@@ -357,6 +357,43 @@ int lynse_hip_ivf_sq8_params(const lynse_hip_ivf *h, float *mins, float *scales)
  * out3[0] searches, out3[1] the pool stage (after the query codec -> after the pool stage), out3[2] the rerank (k_pool_rerank, plus
  * the host selection of a pool beyond 16,384).  reset != 0 clears them. */
 int lynse_hip_ivf_sq8_stage_times(lynse_hip_ivf *h, double *out3, int reset);
+/* SPANN-{IP,L2,COS}[-SQ8] (src/index/mod.rs:387-419; SPANNIndex, src/index/spann.rs): an IVF handle whose rows sit in up to
+ * R + 1 posting lists (R = replica_count, at most 63).  rank(c) = distance(row, centroid c) (compute_distance_f32), negated for IP.
+ *  - build (spann.rs:266-324): sq8 != 0 fits the ScalarQuantizer and works on decode(encode(rows)) from here on, as IVF-*-SQ8 does;
+ *    k-means is train_for_metric(rows, n, dim, nlist, max_iter, metric), nlist = min(nlist, n).  R == 0: the lists are the k-means
+ *    assignments; R >= 1: every row is placed by the posting rule against the FINAL centroids.  Lists hold rows in ascending order.
+ *  - posting rule (posting_centroids_for_vector, :130-186): keep = min(R + 1, nlist) slots (+inf, none); for c = 0 .. nlist - 1 in
+ *    order, c is skipped when rank(c) >= rank of the last slot (false for NaN), else inserted behind every slot whose rank is not
+ *    greater.  No centroid in slot 0: list 0 only.  Else [slot 0], and for R >= 1 every later slot with rank <= p + max(|p|, EPS) *
+ *    0.35000002 (p = rank of slot 0, f32, no fused multiply-add) while fewer than R + 1 lists are chosen.  For finite ranks the slots
+ *    are the canonical (rank, centroid) top-keep; a row that can meet a non-finite rank follows the sequential rule literally.
+ *  - search (:326-433; lynse_hip_ivf_search_f32 / _search_filtered_f32): an index of 0 rows is LYNSE_ERR_INDEX_NOT_BUILT; k == 0
+ *    answers nothing; nprobe == 0 -> 1 (the build default nprobe of the reference is the caller's to pass), clamped to nlist.  The
+ *    centroids are ranked as IVF ranks them; the candidates are the DISTINCT rows of the probed lists (intersected with the subset);
+ *    fewer than k of them -> all (subset) rows.  Plain modes: the top k by (distance, row).  SQ8: the query is encoded and decoded,
+ *    the pool = min(max(10 k, k), |candidates|) best candidates by decoded distance is rescored on the original query and rows and
+ *    the best min(k, pool) kept; both cuts pinned by the (distance, row) key.  Short results are padded as everywhere (row ~0, the
+ *    worst distance of the metric).
+ *  - insert (:459-509, lynse_hip_ivf_insert_f32): the new rows are encoded with the fitted quantizer (no refit), placed by the posting
+ *    rule against the unchanged centroids and appended to the end of each of their lists.  delete (:435-457, lynse_hip_ivf_delete_rows):
+ *    the rows go, the rest are renumbered in order and ALL lists are rebuilt with the posting rule (R == 0 included).
+ *  - lynse_hip_ivf_len is the number of rows, lynse_hip_ivf_nlist the number of lists; lynse_hip_ivf_sq8_params /
+ *    _sq8_stage_times / _profile_* work as for IVF-*-SQ8.  Refused with LYNSE_ERR_UNSUPPORTED: lynse_hip_ivf_search_f32_device,
+ *    lynse_hip_ivf_search_submit_f32_device, lynse_hip_ivf_search_sharded_f32_device, lynse_hip_ivf_search_metric_f32,
+ *    lynse_hip_ivf_set_row_map, lynse_hip_ivf_set_routing, lynse_hip_ivf_assign_f32 and lynse_hip_ivf_export (they assume one list
+ *    per row, a row map or another centroid ranking), lynse_hip_ivf_set_fused_search(h, 1) (the fused few-query selection assumes
+ *    unique (distance, row) keys), and a binary metric at build / load.
+ * lynse_hip_spann_load: `rows` are the ORIGINAL rows; the lists as list-major CSR (list_offsets nlist + 1, list_rows the rows of every
+ * list); every row must sit in 1 .. replica_count + 1 distinct lists (else LYNSE_ERR_INVALID_ARGUMENT); mins / scales (dim each)
+ * make it an SQ8 index, NULL a plain one.  lynse_hip_spann_postings returns the lists in the same form
+ * (offsets nlist + 1, rows n_postings; NULL pointers are skipped). */
+int lynse_hip_spann_build(const float *rows, uint64_t n, uint32_t dim, uint32_t nlist, uint32_t max_iter, int metric,
+                          uint32_t replica_count, int sq8, int device, lynse_hip_ivf **out);
+int lynse_hip_spann_load(const float *rows, uint64_t n, uint32_t dim, const float *centroids, uint32_t nlist,
+                         const uint64_t *list_offsets, const uint32_t *list_rows, uint32_t replica_count, int metric,
+                         const float *mins, const float *scales, int device, lynse_hip_ivf **out);
+int lynse_hip_spann_postings(const lynse_hip_ivf *h, uint64_t *offsets, uint32_t *rows, uint64_t *n_postings);
+int lynse_hip_spann_replica_count(const lynse_hip_ivf *h, uint32_t *replica_count);
 /* IVFIndex::insert (src/index/ivf.rs:392-441): `rows` (n x dim f32; a binary index pushes them through its quantizer) are
  * assigned to the EXISTING centroids with the routing metric (every centroid in ascending order, strictly better wins) and
  * appended behind the rows already indexed (new row ids old_len .. old_len + n - 1); no retraining.

@@ -127,6 +127,10 @@ SIGNATURES = {
     "lynse_hip_ivf_load_sq8": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "lynse_hip_ivf_sq8_params": (C.c_int, [_vp, _vp, _vp]),
     "lynse_hip_ivf_sq8_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
+    "lynse_hip_spann_build": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_spann_load": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_spann_postings": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "lynse_hip_spann_replica_count": (C.c_int, [_vp, _vp]),
     "lynse_hip_comm_load_rccl": (C.c_int, [C.c_char_p]),
     "lynse_hip_comm_unique_id": (C.c_int, [_vp]),
     "lynse_hip_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -121,6 +121,76 @@ def flat_pq_mode(mode: str) -> bool:
     return True
 
 
+SPANN_MODES = {"SPANN-IP": (_lib.METRIC_IP, False), "SPANN-L2": (_lib.METRIC_L2, False), "SPANN-COS": (_lib.METRIC_COSINE, False),
+               "SPANN-COSINE": (_lib.METRIC_COSINE, False), "SPANN-IP-SQ8": (_lib.METRIC_IP, True), "SPANN-L2-SQ8": (_lib.METRIC_L2, True),
+               "SPANN-COS-SQ8": (_lib.METRIC_COSINE, True), "SPANN-COSINE-SQ8": (_lib.METRIC_COSINE, True)}
+SPANN_DEFAULT_REPLICAS = 1   # spann::DEFAULT_REPLICA_COUNT
+
+
+def spann_mode_of(mode: str) -> Optional[tuple]:
+    """The SPANN index modes (src/index/mod.rs:387-419): (metric id, sq8) for SPANN-{IP,L2,COS,COSINE}[-SQ8], None for a mode that is
+    not SPANN-*; any other SPANN-* name is refused as the reference refuses an unknown index type (ValueError, InvalidArgument)."""
+    u = str(mode).upper()
+    if not u.startswith("SPANN"):
+        return None
+    if u not in SPANN_MODES:
+        raise ValueError(f"Invalid argument: Unknown index type: {mode}")
+    return SPANN_MODES[u]
+
+
+def spann_build_options(params: Optional[dict]) -> dict:
+    """IndexBuildOptions for a SPANN mode (src/index/mod.rs:502-542, :626-655): n_clusters (alias n_centroids) = 256, nprobe = 32,
+    replica_count = 1; a value of 0 is refused with ValueError("Invalid argument: <name> must be greater than 0")."""
+    p = dict(params or {})
+    if "n_centroids" in p and "n_clusters" not in p:
+        p["n_clusters"] = p.pop("n_centroids")
+    out = {}
+    for name, default in (("n_clusters", 256), ("nprobe", 32), ("replica_count", SPANN_DEFAULT_REPLICAS)):
+        v = p.get(name)
+        if v is not None and int(v) == 0:
+            raise ValueError(f"Invalid argument: {name} must be greater than 0")
+        out[name] = default if v is None else int(v)
+    return out
+
+
+def spann_posting_rule(ranks, replica_count: int) -> list:
+    """posting_centroids_for_vector (src/index/spann.rs:130-186) over one row's centroid ranks (distance, negated for IP; f32): the
+    lists the row sits in, the primary first.  The restatement the device kernels are checked against."""
+    r = np.asarray(ranks, np.float32).reshape(-1)
+    nc = r.size
+    if nc == 0:
+        return []
+    keep = min(replica_count + 1, nc)
+    best = [(np.float32(np.inf), None)] * keep
+    for c in range(nc):
+        rank = r[c]
+        if rank >= best[keep - 1][0]:
+            continue
+        pos = keep - 1
+        while pos > 0 and rank < best[pos - 1][0]:
+            best[pos] = best[pos - 1]
+            pos -= 1
+        best[pos] = (rank, c)
+    if best[0][1] is None:
+        return [0]
+    sel = [best[0][1]]
+    if replica_count == 0:
+        return sel
+    p = np.float32(best[0][0])
+    eps = np.float32(np.finfo(np.float32).eps)
+    with np.errstate(all="ignore"):
+        a = np.float32(abs(p))
+        m = eps if np.isnan(a) else max(a, eps)   # f32::max ignores NaN
+        slack = np.float32(m * (np.float32(1.35) - np.float32(1.0)))   # 0.35000002
+        threshold = np.float32(p + slack)
+    for rank, c in best[1:]:
+        if c is None:
+            continue
+        if len(sel) <= replica_count and rank <= threshold:
+            sel.append(c)
+    return sel
+
+
 def _f32(a, ndim: int, what: str) -> np.ndarray:
     a = np.asarray(a)
     if a.dtype != np.float32:
@@ -763,6 +833,144 @@ class IvfFlatIndex:
         return rows[0, :c].astype(np.uint32), dists[0, :c].copy()
 
 
+class SpannIndex:
+    """`SPANNIndex` (src/index/spann.rs): k-means centroids, every row in up to replica_count + 1 posting lists (boundary replicas),
+    the lists as contiguous slabs in HBM; search scans the nprobe nearest lists and keeps the best k DISTINCT rows.  SQ8: lists of
+    decoded rows, an exact rerank of a 10 k pool against the original rows.  The contract is in include/lynse_hip.h."""
+
+    def __init__(self, handle, dim: int, sq8: bool, nprobe: int = 32):
+        self._h = handle
+        self._dim = dim
+        self._sq8 = sq8
+        self.nprobe = int(nprobe)   # the build default of a search with nprobe == 0
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.lynse_hip_ivf_destroy(h)
+
+    @staticmethod
+    def build(data, dim: int, n_clusters: int = 256, n_iters: int = 20, metric: str = "ip", replica_count: int = SPANN_DEFAULT_REPLICAS,
+              sq8: bool = False, nprobe: int = 32, device: Optional[int] = None) -> "SpannIndex":
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        a = _f32(data, 2, "data")
+        if a.shape[1] != dim:
+            raise ValueError(f"data dimension mismatch: expected {dim}, got {a.shape[1]}")
+        h = C.c_void_p()
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_spann_build(_ptr(a), a.shape[0], dim, int(n_clusters), int(n_iters), m, int(replica_count), 1 if sq8 else 0, dev,
+                                        C.byref(h)))
+        return SpannIndex(h, dim, bool(sq8), nprobe)
+
+    @staticmethod
+    def load(data, centroids, list_offsets, list_rows, replica_count: int, metric: str = "ip", mins=None, scales=None,
+             device: Optional[int] = None, nprobe: int = 32) -> "SpannIndex":
+        """`data`: the ORIGINAL rows; the lists as list-major CSR (`postings()` of a built index); (`mins`, `scales`) make it SQ8."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        a = _f32(data, 2, "data")
+        c = _f32(centroids, 2, "centroids")
+        off = np.ascontiguousarray(np.asarray(list_offsets).reshape(-1), dtype=np.uint64)
+        rows = np.ascontiguousarray(np.asarray(list_rows).reshape(-1), dtype=np.uint32)
+        if off.size != c.shape[0] + 1:
+            raise ValueError("list_offsets needs n_lists + 1 entries")
+        sq8 = mins is not None
+        mn = _f32(mins, 1, "mins") if sq8 else None
+        sc = _f32(scales, 1, "scales") if sq8 else None
+        h = C.c_void_p()
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_spann_load(_ptr(a), a.shape[0], a.shape[1], _ptr(c), c.shape[0], _ptr(off), _ptr(rows) if rows.size else None,
+                                       int(replica_count), m, _ptr(mn) if sq8 else None, _ptr(sc) if sq8 else None, dev, C.byref(h)))
+        return SpannIndex(h, a.shape[1], sq8, nprobe)
+
+    def postings(self):
+        """The posting lists as list-major CSR: (offsets u64[n_lists + 1], rows u32[postings]), rows ascending inside a list."""
+        n = C.c_uint64(0)
+        check(lib.lynse_hip_spann_postings(self._h, None, None, C.byref(n)))
+        off = np.zeros(self.n_partitions + 1, np.uint64)
+        rows = np.zeros(max(n.value, 1), np.uint32)
+        check(lib.lynse_hip_spann_postings(self._h, _ptr(off), _ptr(rows), C.byref(n)))
+        return off, rows[:n.value]
+
+    @property
+    def replica_count(self) -> int:
+        out = C.c_uint32(0)
+        check(lib.lynse_hip_spann_replica_count(self._h, C.byref(out)))
+        return int(out.value)
+
+    @property
+    def is_sq8(self) -> bool:
+        return self._sq8
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    def __len__(self) -> int:
+        return int(lib.lynse_hip_ivf_len(self._h))
+
+    @property
+    def n_partitions(self) -> int:
+        return int(lib.lynse_hip_ivf_nlist(self._h))
+
+    def profile_enable(self, on=True) -> None:
+        check(lib.lynse_hip_ivf_profile_enable(self._h, int(on)))
+
+    def profile_get(self, reset: bool = True) -> dict:
+        p = _lib.Profile()
+        check(lib.lynse_hip_ivf_profile_get(self._h, C.byref(p), 1 if reset else 0))
+        return {f: getattr(p, f) for f, _ in _lib.Profile._fields_}
+
+    def sq8_params(self):
+        mn = np.empty(self._dim, np.float32)
+        sc = np.empty(self._dim, np.float32)
+        check(lib.lynse_hip_ivf_sq8_params(self._h, _ptr(mn), _ptr(sc)))
+        return mn, sc
+
+    def sq8_stage_times(self, reset: bool = True) -> dict:
+        out = np.zeros(3, np.float64)
+        check(lib.lynse_hip_ivf_sq8_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "pool_us": float(out[1]), "rerank_us": float(out[2])}
+
+    def insert(self, data) -> None:
+        """`SPANNIndex::insert` (spann.rs:459-509): posting rule against the unchanged centroids, appended to the end of each list."""
+        a = _f32(data, 2, "data")
+        if a.shape[1] != self._dim:
+            raise ValueError(f"dimension mismatch: expected {self._dim}, got {a.shape[1]}")
+        check(lib.lynse_hip_ivf_insert_f32(self._h, _ptr(a), a.shape[0]))
+
+    def delete(self, rows) -> None:
+        """`SPANNIndex::delete` (spann.rs:435-457): drop the rows, renumber the rest in order, rebuild every list."""
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.uint64)
+        check(lib.lynse_hip_ivf_delete_rows(self._h, _ptr(r) if r.size else None, r.size))
+
+    def _nprobe(self, nprobe) -> int:
+        return self.nprobe if not nprobe else int(nprobe)
+
+    def search_batch_arrays(self, queries, k: int, nprobe: int = 0):
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_ivf_search_f32(self._h, _ptr(q), nq, k, self._nprobe(nprobe), _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+    def search_filtered_batch_arrays(self, queries, k: int, nprobe: int, subset_rows):
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        sub = np.ascontiguousarray(np.asarray(subset_rows).reshape(-1), dtype=np.uint64)
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_ivf_search_filtered_f32(self._h, _ptr(q), nq, k, self._nprobe(nprobe), _ptr(sub) if sub.size else None, sub.size,
+                                                    _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+
 def py_compute_distance(a, b, metric: str) -> float:
     """src/python/mod.rs:2161-2185."""
     m = metric_from_str(metric)
@@ -889,7 +1097,7 @@ class Collection:
         self._id_arrays: list = []     # row -> user id (engine.rs:3071-3073)
         self._index_mode = "FLAT-IP"   # resolve_metric default IP (engine.rs:5529-5534)
         self._metric = _lib.METRIC_IP
-        self._ivf: Optional[IvfFlatIndex] = None
+        self._ivf = None                # IvfFlatIndex, or SpannIndex for the SPANN-* modes
         self._ivf_rows = 0              # rows the IVF index was built over
         self._ivf_params: dict = {}
         self._ivf_nprobe = 32           # IndexBuildOptions default (src/index/mod.rs:498-655)
@@ -978,6 +1186,17 @@ class Collection:
             if pq and len(self._flat) > 0:   # over 0 rows nothing is built and searches stay exact
                 self._flat.build_pq(parse_n_subspaces(mode, self._dim), int(params.get("n_clusters", 256)))
                 self._pq = True
+        elif mode.startswith("SPANN"):
+            metric, sq8 = spann_mode_of(mode)
+            opts = spann_build_options(params)
+            self._flat.drop_pq()
+            self._pq = False
+            if len(self._flat) == 0:   # graph / partition indexes need data (engine.rs:4606-4612)
+                raise ValueError("Empty database")
+            self._ivf_params = {"n_clusters": opts["n_clusters"], "spann": (opts["replica_count"], sq8)}
+            self._ivf_nprobe = opts["nprobe"]
+            self._index_mode, self._metric = mode, metric
+            self._build_ivf()
         elif mode.startswith("IVF"):
             quantizer = ivf_quantizer_of(mode)
             self._flat.drop_pq()
@@ -993,6 +1212,12 @@ class Collection:
     def _build_ivf(self) -> None:
         n = len(self._flat)
         data = self._flat.read_rows(0, n)
+        if "spann" in self._ivf_params:   # SPANNIndex: train_for_metric clamps the list count to the rows
+            replicas, sq8 = self._ivf_params["spann"]
+            self._ivf = SpannIndex.build(data, self._dim, self._ivf_params["n_clusters"], 20, int(self._metric), replicas, sq8,
+                                         self._ivf_nprobe, device=self._device)
+            self._ivf_rows = n
+            return
         nlist = min(self._ivf_params["n_clusters"], max(n, 1))
         # the metric id goes through as it is: binary metrics build the IVF-*-BINARY mode, float metrics an IVFIndex
         # trained with its routing metric (ivf.rs:163-170)
@@ -1102,7 +1327,7 @@ class Collection:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
         finally:
             dev = target.profile_get(reset=True)
-            # IVF-*-SQ8: the exact rerank of the pool (HIP events on the search stream); 0 for the modes without one
+            # IVF-*-SQ8 / SPANN-*-SQ8: the exact rerank of the pool (HIP events on the search stream); 0 for the modes without one
             rerank_us = int(self._ivf.sq8_stage_times(reset=True)["rerank_us"]) if sq8 else 0
             if pq:   # FLAT-*-PQ: the exact rescore of the ADC pool
                 rerank_us = int(self._flat.pq_stage_times(reset=True)["rescore_us"])

@@ -296,6 +296,7 @@ extern "C" int lynse_hip_ivf_search_sharded_f32_device(lynse_hip_ivf* h, lynse_h
     {
         IVF_GUARD(h);
         if (h->sq8) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index is not row-sharded");
+        if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "a SPANN index is not row-sharded");
     }
     LY_TRY(comm_check_alive(c));
     std::lock_guard<std::mutex> lk(c->mu);

@@ -73,6 +73,7 @@ extern "C" int lynse_hip_ivf_search_submit_f32_device(lynse_hip_ivf* h, lynse_hi
     if (!h->store) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
     if (h->binary) return set_error(LYNSE_ERR_UNSUPPORTED, "searches in flight are defined for float IVF indexes");
     if (h->sq8) return set_error(LYNSE_ERR_UNSUPPORTED, "searches in flight are not defined for IVF-*-SQ8 indexes (pool + rerank)");
+    if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "searches in flight are not defined for SPANN indexes");
     lynse_hip_flat* s = h->store;
     if (c && s->device != c->device) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the shard and the communicator live on different devices");
     std::unique_lock<std::shared_mutex> lk(s->rw);

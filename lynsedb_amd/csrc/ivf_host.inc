@@ -72,6 +72,26 @@ struct lynse_hip_ivf {
     // search stream; the host selection of a pool beyond the LDS counts to the rerank)
     uint64_t sq_searches = 0;
     double sq_pool_us = 0.0, sq_rerank_us = 0.0;
+    // SPANN-{IP,L2,COS}[-SQ8] (spann_host.inc): a row sits in up to replicas + 1 lists, so the slab store holds POSTINGS (store->n of
+    // them, `orig` repeats rows) and n_rows rows; `assignments` is empty (no single list per row)
+    bool spann = false;
+    uint32_t replicas = 0;
+    uint64_t n_rows = 0;
+    struct SpannScratch {             // per-search buffers of the SPANN path (grown on demand; searches hold the guard)
+        float* d_q = nullptr; size_t q_cap = 0;
+        uint64_t* d_rows = nullptr; size_t rows_cap = 0;   // the k' keys of the list scan ...
+        float* d_dists = nullptr; size_t dists_cap = 0;
+        uint32_t* d_cnt = nullptr; size_t cnt_cap = 0;
+        uint64_t* d_orow = nullptr; size_t orow_cap = 0;   // ... and the distinct rows (plain modes)
+        float* d_odist = nullptr; size_t odist_cap = 0;
+        uint32_t* d_ocnt = nullptr; size_t ocnt_cap = 0;
+        uint32_t* d_qmap = nullptr; size_t qmap_cap = 0;   // the queries of a fallback rerun
+        void release() {
+            for (void* p : {(void*)d_q, (void*)d_rows, (void*)d_dists, (void*)d_cnt, (void*)d_orow, (void*)d_odist, (void*)d_ocnt, (void*)d_qmap})
+                if (p) (void)hipFree(p);
+            *this = SpannScratch();
+        }
+    } sp;
     lynse_hip_flat* cstore = nullptr; // the centroid matrix as a FLAT shard: exact routing = its top-nprobe search
     uint32_t* d_smask = nullptr;      // subset filter by slab position
     uint64_t smask_words = 0;
@@ -106,6 +126,7 @@ static void ivf_free(lynse_hip_ivf* h) {
                         (void*)h->d_sq, (void*)h->d_raw, (void*)h->sq.d_q, (void*)h->sq.d_pdist})
             if (p) (void)hipFree(p);
         h->sq.rr.release();
+        h->sp.release();
         for (auto& x : h->scr) x.release();
         if (h->cstore) lynse_hip_flat_destroy(h->cstore);
         lynse_hip_flat_destroy(h->store);
@@ -120,6 +141,7 @@ extern "C" int lynse_hip_ivf_destroy(lynse_hip_ivf* h) {
 extern "C" uint64_t lynse_hip_ivf_len(const lynse_hip_ivf* h) {
     if (!h) return 0;
     IVF_GUARD(h);   // (insert / delete replace h->store)
+    if (h->spann) return h->n_rows;   // (the store holds postings)
     return h->store ? h->store->n : 0;
 }
 extern "C" uint32_t lynse_hip_ivf_nlist(const lynse_hip_ivf* h) { return h ? h->nlist : 0; }
@@ -128,6 +150,7 @@ extern "C" int lynse_hip_ivf_set_row_map(lynse_hip_ivf* h, uint64_t stride, uint
     if (!h || stride == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "bad row map");
     IVF_GUARD(h);   // (searches read the row map under the guard)
     if (h->sq8 && (stride != 1 || offset != 0)) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index is not row-sharded");
+    if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "a SPANN index is not row-sharded");
     h->row_stride = stride;
     h->row_offset = offset;
     return LYNSE_OK;
@@ -137,6 +160,7 @@ extern "C" int lynse_hip_ivf_set_fused_search(lynse_hip_ivf* h, int on) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     IVF_GUARD(h);
     if (!h->store) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (h->spann && on) return set_error(LYNSE_ERR_UNSUPPORTED, "a SPANN index searches with the staged pipeline (replicated rows)");
     return lynse_hip_flat_set_fused_search(h->store, on);
 }
 
@@ -146,6 +170,7 @@ extern "C" int lynse_hip_ivf_set_routing(lynse_hip_ivf* h, int ivfflat_routing) 
     IVF_GUARD(h);
     if (!h->store) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     (void)hipSetDevice(h->store->device);
+    if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "a SPANN index ranks every centroid exactly (IVFIndex routing)");
     h->no_fallback = ivfflat_routing == 2 ? 1 : 0;
     if (ivfflat_routing == 2) return LYNSE_OK;  // routing semantics unchanged, only the fallback is switched off
     h->ivfflat_routing = ivfflat_routing ? 1 : 0;
@@ -158,6 +183,7 @@ extern "C" int lynse_hip_ivf_export(const lynse_hip_ivf* h, float* centroids, ui
                                     uint32_t* original_ids) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     IVF_GUARD(h);   // (insert / delete rewrite assignments / offsets / original ids)
+    if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "export assumes one list per row: lynse_hip_spann_postings gives a SPANN index's lists");
     if (centroids) memcpy(centroids, h->centroids.data(), h->centroids.size() * 4);
     if (assignments) memcpy(assignments, h->assignments.data(), h->assignments.size() * 4);
     if (offsets) memcpy(offsets, h->offsets.data(), h->offsets.size() * 8);
@@ -231,13 +257,17 @@ struct IvfRowSource {
     uint64_t first_new, n_new;
 };
 
+// row_off (SPANN, rows on the device only): row i sits in the lists assignments[row_off[i] .. row_off[i + 1]) — the store holds
+// row_off[n] postings, `orig` repeats rows, `assignments` stays empty.
 static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t nlist,
                         const uint32_t* assignments, int metric, int ivfflat_routing, int device, lynse_hip_ivf** out,
-                        bool rows_on_device = false, const IvfRowSource* rs = nullptr) {
+                        bool rows_on_device = false, const IvfRowSource* rs = nullptr, const uint64_t* row_off = nullptr) {
     auto* h = new lynse_hip_ivf();
     h->dim = dim; h->nlist = nlist; h->metric = metric; h->ivfflat_routing = ivfflat_routing;
     int rc = lynse_hip_flat_create(dim, device, &h->store);
     if (rc != LYNSE_OK) { delete h; return rc; }
+    const uint64_t n_rows = n;
+    if (row_off) n = row_off[n_rows];   // (from here on: slab positions)
     h->offsets.assign(nlist + 1, 0);
     for (uint64_t i = 0; i < n; ++i) {
         if (assignments[i] >= nlist) { ivf_free(h); return set_error(LYNSE_ERR_INVALID_ARGUMENT, "assignment out of range"); }
@@ -245,10 +275,15 @@ static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float
     }
     for (uint32_t p = 0; p < nlist; ++p) h->offsets[p + 1] += h->offsets[p];
     h->orig.resize(n);
-    h->assignments.assign(assignments, assignments + n);
+    if (!row_off) h->assignments.assign(assignments, assignments + n);
     {
         std::vector<uint64_t> wp(h->offsets.begin(), h->offsets.end() - 1);
-        for (uint64_t i = 0; i < n; ++i) h->orig[wp[assignments[i]]++] = (uint32_t)i;
+        if (row_off) {
+            for (uint64_t r = 0; r < n_rows; ++r)
+                for (uint64_t j = row_off[r]; j < row_off[r + 1]; ++j) h->orig[wp[assignments[j]]++] = (uint32_t)r;
+        } else {
+            for (uint64_t i = 0; i < n; ++i) h->orig[wp[assignments[i]]++] = (uint32_t)i;
+        }
     }
     auto fail = [&](const char* what) { ivf_free(h); return set_error(LYNSE_ERR_OUT_OF_MEMORY, what); };
     if (hipMalloc(&h->d_orig, std::max<size_t>((size_t)n * 4, 4)) != hipSuccess) return fail("hipMalloc(orig)");
@@ -753,9 +788,9 @@ static int sq_codec_device(const float* d_in, uint64_t n, uint32_t dim, const fl
     return LYNSE_OK;
 }
 
-// decode(encode(rows)) of host rows for an SQ8 index (host copy): the routing space of insert / assign
+// decode(encode(rows)) of host rows for an SQ8 index (host copy unless dec is NULL): the routing space of insert / assign
 static int sq_decode_host(const lynse_hip_ivf* h, const float* rows, uint64_t n, std::vector<float>* dec, float** d_keep = nullptr) {
-    dec->resize((size_t)n * h->dim);
+    if (dec) dec->resize((size_t)n * h->dim);
     if (n == 0) return LYNSE_OK;
     LY_HIP(hipSetDevice(h->store->device));   // (h->d_sq lives on the index's device, whatever the calling thread's current one is)
     float* d_v = nullptr;
@@ -763,7 +798,8 @@ static int sq_decode_host(const lynse_hip_ivf* h, const float* rows, uint64_t n,
     LY_HIP(hipMalloc(&d_v, (size_t)n * h->dim * 8));
     LY_TRY(h2d_done(d_v, rows, (size_t)n * h->dim * 4));
     LY_TRY(sq_codec_device(d_v, n, h->dim, h->d_sq, d_v + (size_t)n * h->dim, 0));
-    LY_HIP(hipMemcpy(dec->data(), d_v + (size_t)n * h->dim, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost));
+    if (dec) LY_HIP(hipMemcpy(dec->data(), d_v + (size_t)n * h->dim, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost));
+    else LY_HIP(hipStreamSynchronize(nullptr));
     if (d_keep) { *d_keep = d_v; d_v = nullptr; }   // (the caller takes the buffer: originals first, decoded rows behind them)
     return LYNSE_OK;
 }
@@ -882,6 +918,7 @@ extern "C" int lynse_hip_ivf_assign_f32(lynse_hip_ivf* h, const float* rows, uin
     if (!h) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
     IVF_GUARD(h);   // (insert / delete replace the centroid store too)
     if (!h->store || !h->cstore) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
+    if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "assign is defined for one list per row, not for a SPANN index");
     if (n && (!rows || !out_assignments)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!h->binary && !h->sq8) return ivf_assign_rows(h, rows, n, out_assignments);
     std::vector<float> enc;
@@ -907,11 +944,9 @@ static int ivf_rows_in_original_order(lynse_hip_ivf* h, std::vector<float>* out)
 
 // replace the device structures of `h` with a fresh assembly over (rows, assignments) under the SAME centroids / settings
 // (new_raw: an SQ8 index's original rows for the new assembly, n x dim in original row order; owned by the index on success)
-static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint64_t n, const std::vector<uint32_t>& asg, const IvfRowSource* rs = nullptr,
-                          float* new_raw = nullptr) {
-    lynse_hip_ivf* fresh = nullptr;
-    const int device = h->store->device;
-    LY_TRY(ivf_assemble(rs ? nullptr : rows.data(), n, h->dim, h->centroids.data(), h->nlist, asg.data(), h->metric, h->ivfflat_routing, device, &fresh, false, rs));
+// hand the settings of `h` to a fresh assembly `fresh` under the same centroids, then swap them: `h` owns the new structures, the old
+// ones are freed (new_raw as in ivf_reassemble)
+static int ivf_adopt(lynse_hip_ivf* h, lynse_hip_ivf* fresh, float* new_raw) {
     fresh->no_fallback = h->no_fallback;
     fresh->row_stride = h->row_stride; fresh->row_offset = h->row_offset;
     fresh->store->no_fused = h->store->no_fused;
@@ -926,6 +961,8 @@ static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint
         fresh->d_raw = new_raw;
         fresh->sq_searches = h->sq_searches; fresh->sq_pool_us = h->sq_pool_us; fresh->sq_rerank_us = h->sq_rerank_us;
     }
+    fresh->spann = h->spann;
+    fresh->replicas = h->replicas;   // (n_rows is the caller's to set)
     // (profiling state of the old store carries over: it used to be dropped silently)
     fresh->store->profiling = h->store->profiling.load();
     fresh->store->prof_rate = h->store->prof_rate.load();
@@ -942,6 +979,17 @@ static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint
     return LYNSE_OK;
 }
 
+static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint64_t n, const std::vector<uint32_t>& asg, const IvfRowSource* rs = nullptr,
+                          float* new_raw = nullptr) {
+    lynse_hip_ivf* fresh = nullptr;
+    const int device = h->store->device;
+    LY_TRY(ivf_assemble(rs ? nullptr : rows.data(), n, h->dim, h->centroids.data(), h->nlist, asg.data(), h->metric, h->ivfflat_routing, device, &fresh, false, rs));
+    return ivf_adopt(h, fresh, new_raw);
+}
+
+static int spann_insert(lynse_hip_ivf* h, const float* rows, uint64_t n);
+static int spann_delete(lynse_hip_ivf* h, const uint64_t* row_ids, uint64_t n_ids);
+
 extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uint64_t n) {
     if (!h) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
     const std::shared_ptr<std::mutex> guard = ivf_guard_of(h);
@@ -953,6 +1001,7 @@ extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uin
     if (h->inflight != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "searches are in flight on this index: wait for the outstanding tickets first");
     if (n == 0) return LYNSE_OK;
     if (!rows) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "rows is NULL");
+    if (h->spann) return spann_insert(h, rows, n);
     const uint64_t old_n = h->store->n;
     if (old_n + n > 0xfffffff0ull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF vector count exceeds the u32 ID capacity");
     std::vector<float> enc_new;
@@ -993,6 +1042,7 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
     if (h->inflight != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "searches are in flight on this index: wait for the outstanding tickets first");
     if (n_ids == 0) return LYNSE_OK;
     if (!row_ids) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row_ids is NULL");
+    if (h->spann) return spann_delete(h, row_ids, n_ids);
     const uint64_t old_n = h->store->n;
     std::vector<bool> gone(old_n, false);
     for (uint64_t i = 0; i < n_ids; ++i)
@@ -1761,6 +1811,8 @@ static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq
 static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
                           uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
                           const uint64_t* subset, uint64_t n_subset, bool on_device);
+static int spann_search(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                        uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered, const uint64_t* subset, uint64_t n_subset);
 
 static int ivf_search_impl(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
                            uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool filtered,
@@ -1772,6 +1824,11 @@ static int ivf_search_impl(lynse_hip_ivf* h, const float* queries, uint64_t nq, 
     const std::shared_ptr<std::mutex> guard = ivf_guard_of(h);
     std::lock_guard<std::mutex> glk(*guard);   // (insert / delete replace h->store: read it under the index guard)
     if (!h->store) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
+    if (h->spann) {
+        if (metric_override >= 0) return set_error(LYNSE_ERR_UNSUPPORTED, "a SPANN index searches with the metric it was built for");
+        if (on_device) return set_error(LYNSE_ERR_UNSUPPORTED, "device-resident search is not defined for a SPANN index");
+        return spann_search(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, filtered, subset, n_subset);
+    }
     if (h->sq8) {
         if (metric_override >= 0) return set_error(LYNSE_ERR_UNSUPPORTED, "an IVF-*-SQ8 index searches with the metric it was built for");
         return ivf_search_sq8(h, queries, nq, k, nprobe, out_rows, out_dists, out_counts, filtered, subset, n_subset, on_device);
@@ -1821,13 +1878,17 @@ static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq
     std::vector<uint64_t> list_matches;
     if (filtered) {  // subset (original row ids) -> matches per list (host) + slab-position bitmask (device)
         list_matches.assign(h->nlist, 0);
-        std::vector<bool> seen(s->n, false);
+        const uint64_t n_rows = h->spann ? h->n_rows : s->n;
+        std::vector<bool> seen(n_rows, false);
         uint64_t valid = 0;
         for (uint64_t i = 0; i < n_subset; ++i) {
             const uint64_t r = subset[i];
-            if (r < s->n && !seen[r]) { seen[r] = true; list_matches[h->assignments[r]] += 1; ++valid; }
+            if (r < n_rows && !seen[r]) { seen[r] = true; if (!h->spann) list_matches[h->assignments[r]] += 1; ++valid; }
         }
         if (valid == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }  // ivf.rs:267-269
+        if (h->spann)   // (a row counts in every list it sits in)
+            for (uint32_t c = 0; c < h->nlist; ++c)
+                for (uint64_t p = h->offsets[c]; p < h->offsets[c + 1]; ++p) list_matches[c] += seen[h->orig[p]] ? 1 : 0;
         const uint64_t words = (s->n + 31) / 32 + 8;
         auto& fc = cur(s);   // (the slab store's context 0: IVF searches hold its exclusive lock)
         if (words > fc.mask_words) {
@@ -1951,6 +2012,7 @@ extern "C" int lynse_hip_ivf_search_metric_f32(lynse_hip_ivf* h, const float* qu
         is_binary = h->binary != 0;
         is_sq8 = h->sq8;
         index_metric = h->metric;
+        if (h->spann) return set_error(LYNSE_ERR_UNSUPPORTED, "IvfFlatMmap::search(metric) is not defined for a SPANN index");
     }
     if (is_sq8) return set_error(LYNSE_ERR_UNSUPPORTED, "IvfFlatMmap::search(metric) is not defined for an IVF-*-SQ8 index (IVFIndex searches with its build metric)");
     if (is_binary || metric >= M_HAMMING) {

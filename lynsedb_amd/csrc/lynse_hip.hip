@@ -28,6 +28,7 @@
 #include "scan_qh.h"
 #include "ivf.h"
 #include "pq.h"
+#include "spann.h"
 
 using namespace lynse;
 
@@ -3818,6 +3819,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 
 #include "rerank_host.inc"
 #include "ivf_host.inc"
+#include "spann_host.inc"
 #include "shard_host.inc"
 #include "comm_host.inc"
 #include "async_host.inc"
