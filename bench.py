@@ -12,6 +12,11 @@ RCCL all-gather and merged on the device: total work is fixed -> "scaling": "str
 Inputs (rows and queries) are resident in HBM before the timed region; the timed region is bracketed
 by barrier + torch.cuda.synchronize() and the MAX over ranks is reported.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line; "roofline" and the
+pipeline figures on it come from HIP events recorded inside the timed steps.  Everything that takes work of its own —
+the latency of one blocking batch, two batches in flight, verification against torch and the oracle, "cpu_baseline",
+the other metrics, distribution and BASELINE configurations (c2), the second data set (c4) — runs only with --full.
+
 Extra objects on the JSON line: "roofline" (dominant kernel k_scan_qs: the bytes it physically streams and its matrix
 ops over the HIP-event duration of its launches on the launch stream inside the timed region, against 8 TB/s and the
 dense MFMA peak; `bound` names the BINDING resource from the committed rocprofv3 --pmc pass of that kernel —
@@ -19,9 +24,9 @@ profiles/rNN_binding.json: the int8 matrix pipe at the power-capped clock for th
 counters, `hbm` / `mfma` both live fractions; the SURVEY 8(d) algorithmic-f32-bytes figure rides along) and
 "cpu_baseline" (the oracle's restatement of the reference's rayon scan on a persistent pinned pool, timed on this host's
 cores over a bounded row sample: ONE protocol — 20 warm-ups + 30 queries — for the thread sweep and the figure, the best
-thread count run three times, median / best / spread / host CPU model and NUMA layout on the line).
-`configs` holds the other BASELINE.json configurations at one GPU's share: `ms` = the blocking C-ABI call through ctypes
-with prebuilt arguments, `ms_python_wrapper` = the same through lynsedb_amd's Python wrapper + a torch synchronise.
+thread count run three times, median / best / spread / host CPU model and NUMA layout on the line; --full).
+`configs` (--full) holds the other BASELINE.json configurations at one GPU's share: `ms` = the blocking C-ABI call through
+ctypes with prebuilt arguments, `ms_python_wrapper` = the same through lynsedb_amd's Python wrapper + a torch synchronise.
 """
 from __future__ import annotations
 
@@ -57,6 +62,10 @@ def parse_args():
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--metric", default="ip")
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure, outside the timed steps: the latency of one blocking batch, two batches "
+                        "in flight, verification against torch / the oracle, the CPU baseline, the other metrics, distribution and BASELINE "
+                        "configurations (c2), the second data set (c4); the --no-* switches below leave parts of it out")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-rows", type=int, default=1_000_000)
     p.add_argument("--cpu-queries", type=int, default=30, help="timed CPU queries (flat_search_bench.py:94-97: 30 trials)")
@@ -350,32 +359,33 @@ def main():
     if args.dump_outputs and rank == 0:   # the buffers the LAST timed step wrote (a drained step: `out`; a ticket: its own)
         last = out if (in_flight == 1 or (drain_every and (args.steps - 1) % drain_every == 0)) else outs_default[(args.steps - 1) % in_flight]
         dumped = dump_outputs(args.dump_outputs, last, B, K)
-    # (outside the timed region) latency of ONE blocking batch: the same step through the blocking entry points
-    lat_steps = max(1, min(args.steps, 10))
-    barrier()
-    t_lat = time.perf_counter()
-    for _ in range(lat_steps):
-        sh.search_device(queries, K, metric, out)
-    barrier()
-    lat_ms = (time.perf_counter() - t_lat) / lat_steps * 1000.0
-    two_ms = None
-    if world == 1 and in_flight == 1 and not args.no_configs:   # (outside the timed region; not in the lean profiling command) the same K steps with two tickets in flight
-        outs2 = [sh.alloc_outputs(B, K) for _ in range(2)]
-        run_steps(4, 0, 2, outs2)
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        run_steps(args.steps, 0, 2, outs2)
-        torch.cuda.synchronize()
-        two_ms = (time.perf_counter() - t2) / args.steps * 1000.0
+    lat_ms = two_ms = None
+    if args.full:
+        # (outside the timed region) latency of ONE blocking batch: the same step through the blocking entry points
+        lat_steps = max(1, min(args.steps, 10))
+        barrier()
+        t_lat = time.perf_counter()
+        for _ in range(lat_steps):
+            sh.search_device(queries, K, metric, out)
+        barrier()
+        lat_ms = (time.perf_counter() - t_lat) / lat_steps * 1000.0
+        if world == 1 and in_flight == 1 and not args.no_configs:   # (outside the timed region; not in the lean profiling command) the same K steps with two tickets in flight
+            outs2 = [sh.alloc_outputs(B, K) for _ in range(2)]
+            run_steps(4, 0, 2, outs2)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            run_steps(args.steps, 0, 2, outs2)
+            torch.cuda.synchronize()
+            two_ms = (time.perf_counter() - t2) / args.steps * 1000.0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
     gc.enable()
-    # ---- verification (outside the timed region): recall@k and score agreement vs torch fp32
+    # ---- verification (--full, outside the timed region): recall@k and score agreement vs torch fp32
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verify = sh.verify_against_torch(queries, K, metric, out, nverify=min(args.verify_queries, B))
         if world == 1 and metric == 0 and rank == 0:
             verify.update(oracle_distance_bits(sh.index, queries, out, B, K))
@@ -478,19 +488,20 @@ def main():
                        "build_s": round(build_s, 1), "derived_build_s": round(prepare_s, 3),
                        "hbm_bytes_per_gpu": int(hbm_bytes), "hbm_bytes_over_f32_rows": round(hbm_bytes / max(n_local * D * 4, 1), 3)},
             "roofline": roofline,
-            "blocking_ms_per_batch": round(lat_ms, 4),
-            "two_in_flight_ms_per_step": (round(two_ms, 4) if two_ms is not None else None),
             "pipeline_us_per_step": round(prof["total_us"] / max(prof["searches"], 1), 1),
             "rescored_per_query": round(prof["pool_entries"] / max(prof["searches"] * B, 1), 1),
             "fallback_queries": int(prof["fallback_queries"]),
         }
+        if args.full:
+            result["blocking_ms_per_batch"] = round(lat_ms, 4)
+            result["two_in_flight_ms_per_step"] = round(two_ms, 4) if two_ms is not None else None
         if verify is not None:
             result["verify"] = verify
         if dumped is not None:
             result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
-        if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: the other ranks of a sharded run would sit in the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: the other ranks of a sharded run would sit in the barrier)
             result["cpu_baseline"] = cpu_baseline(args, N, D, K, metric)
-        if world == 1 and not args.no_configs and metric == 0:
+        if args.full and world == 1 and not args.no_configs and metric == 0:
             # OUTSIDE the headline's timed region: the same workload on a second distribution (the certified int8 margin is
             # data dependent) and the other BASELINE.json configurations at one GPU's share, each with its own time, rate,
             # roofline fraction and an oracle-parity bool.  The headline index is released first.
@@ -604,13 +615,14 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
     torch.cuda.synchronize()
     run_steps(20)                               # clocks
     run_steps(args.warmup)
-    sh.index.profile_enable(True)
-    sh.index.profile_get(reset=True)
-    barrier()
-    for _ in range(3):                          # scan-launch timing on three BLOCKING steps outside the timed region (tickets are not profiled)
-        sh.search_device(queries, K, nprobe, outs[0])
-    prof = sh.index.profile_get(reset=True)
-    sh.index.profile_enable(False)
+    if args.full:
+        sh.index.profile_enable(True)
+        sh.index.profile_get(reset=True)
+        barrier()
+        for _ in range(3):                      # scan-launch timing on three BLOCKING steps outside the timed region (tickets are not profiled)
+            sh.search_device(queries, K, nprobe, outs[0])
+        prof = sh.index.profile_get(reset=True)
+        sh.index.profile_enable(False)
     barrier()
     t_start = time.perf_counter()
     run_steps(args.steps)
@@ -619,59 +631,55 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
     dumped = None
     if args.dump_outputs and rank == 0 and not getattr(args, "_c4_second", False):   # (the headline collection's last timed step)
         dumped = dump_outputs(args.dump_outputs, outs[(args.steps - 1) % in_flight], B, K)
-    barrier()
-    t_lat = time.perf_counter()
-    for _ in range(5):
-        sh.search_device(queries, K, nprobe, outs[0])
-    barrier()
-    lat_ms = (time.perf_counter() - t_lat) / 5 * 1000.0
+    if args.full:
+        barrier()
+        t_lat = time.perf_counter()
+        for _ in range(5):
+            sh.search_device(queries, K, nprobe, outs[0])
+        barrier()
+        lat_ms = (time.perf_counter() - t_lat) / 5 * 1000.0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     gc.enable()
     stats = sh.index.ticket_stats()
-    # ---- verification, outside the timed region: (a) tickets == the blocking sharded search, bit for bit; (b) recall@k against the
-    # exact top-k of the WHOLE collection (torch fp32 matmul over every rank's rows, candidates gathered and merged)
-    o_t, o_b = ShardOutputs(B, K, world, dev), ShardOutputs(B, K, world, dev)
-    sh.search_submit(queries, K, nprobe, o_t).wait()
-    sh.search_device(queries, K, nprobe, o_b)
-    torch.cuda.synchronize()
-    same = bool(torch.equal(o_t.rows, o_b.rows) and torch.equal(o_t.dists, o_b.dists) and torch.equal(o_t.counts, o_b.counts))
-    nv = min(args.verify_queries, B)
-    best_s = torch.full((nv, K), -float("inf"), device=dev)
-    best_r = torch.zeros((nv, K), dtype=torch.int64, device=dev)
-    # (the slab-ordered rows live inside the library: this rank's rows are regenerated block-wise from the same generator state)
-    g.manual_seed(1000 + rank)
-    for b0 in range(0, n_local, 250_000):
-        e = min(n_local, b0 + 250_000)
-        gids, blk = gen_block(b0, e)
-        sc = queries[:nv] @ blk.T
-        cs, ci = torch.cat([best_s, sc], dim=1).topk(K, dim=1)
-        allr = torch.cat([best_r, gids.unsqueeze(0).expand(nv, -1)], dim=1)
-        best_s, best_r = cs, torch.gather(allr, 1, ci)
-        del blk, sc
-    if dist is not None:
-        gs = [torch.empty_like(best_s) for _ in range(world)]
-        gr = [torch.empty_like(best_r) for _ in range(world)]
-        dist.all_gather(gs, best_s)
-        dist.all_gather(gr, best_r)
-        cs, ci = torch.cat(gs, dim=1).topk(K, dim=1)
-        best_r = torch.gather(torch.cat(gr, dim=1), 1, ci)
-    got = o_b.rows[:nv].cpu().numpy()
-    exact = best_r.cpu().numpy()
-    recall = float(np.mean([len(set(got[i].tolist()) & set(exact[i].tolist())) / K for i in range(nv)]))
+    if args.full:
+        # ---- verification, outside the timed region: (a) tickets == the blocking sharded search, bit for bit; (b) recall@k against the
+        # exact top-k of the WHOLE collection (torch fp32 matmul over every rank's rows, candidates gathered and merged)
+        o_t, o_b = ShardOutputs(B, K, world, dev), ShardOutputs(B, K, world, dev)
+        sh.search_submit(queries, K, nprobe, o_t).wait()
+        sh.search_device(queries, K, nprobe, o_b)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(o_t.rows, o_b.rows) and torch.equal(o_t.dists, o_b.dists) and torch.equal(o_t.counts, o_b.counts))
+        nv = min(args.verify_queries, B)
+        best_s = torch.full((nv, K), -float("inf"), device=dev)
+        best_r = torch.zeros((nv, K), dtype=torch.int64, device=dev)
+        # (the slab-ordered rows live inside the library: this rank's rows are regenerated block-wise from the same generator state)
+        g.manual_seed(1000 + rank)
+        for b0 in range(0, n_local, 250_000):
+            e = min(n_local, b0 + 250_000)
+            gids, blk = gen_block(b0, e)
+            sc = queries[:nv] @ blk.T
+            cs, ci = torch.cat([best_s, sc], dim=1).topk(K, dim=1)
+            allr = torch.cat([best_r, gids.unsqueeze(0).expand(nv, -1)], dim=1)
+            best_s, best_r = cs, torch.gather(allr, 1, ci)
+            del blk, sc
+        if dist is not None:
+            gs = [torch.empty_like(best_s) for _ in range(world)]
+            gr = [torch.empty_like(best_r) for _ in range(world)]
+            dist.all_gather(gs, best_s)
+            dist.all_gather(gr, best_r)
+            cs, ci = torch.cat(gs, dim=1).topk(K, dim=1)
+            best_r = torch.gather(torch.cat(gr, dim=1), 1, ci)
+        got = o_b.rows[:nv].cpu().numpy()
+        exact = best_r.cpu().numpy()
+        recall = float(np.mean([len(set(got[i].tolist()) & set(exact[i].tolist())) / K for i in range(nv)]))
+        del o_t, o_b
     result = None
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
         qps = B * args.steps / elapsed
-        plan = int(prof.get("last_plan", 0))
-        i8c = bool(plan & 4)
-        launches = max(int(prof["scan_launches"]), 1)
-        scan_s = prof["scan_us"] * 1e-6
-        elem = 1 if i8c else 2
-        kernel_bytes = float(prof["scan_rows"]) * D * elem            # rows of the probed lists the tiled scans streamed (3 steps)
-        hbm_gbps = kernel_bytes / scan_s / 1e9 if scan_s > 0 else 0.0
         result = {
             "metric": "queries/sec, IVF-Flat IP %dx%d float32, nlist=%d nprobe=%d, batch=%d, k=%d" % (N, D, nlist, nprobe, B, K),
             "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -690,19 +698,27 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
                                    ("torch.distributed" if world > 1 else "none"),
                        "batches_in_flight": in_flight, "generate_s": round(gen_s, 1), "train_s": round(train_s, 1), "load_s": round(load_s, 1),
                        "lists_trained": int(cen.shape[0])},
-            "roofline": {"bound": "hbm", "kernel": "k_scan_h16<..,TILED,%s> over the probed lists" % ("I8C" if i8c else "F16"), "binding": binding_of("c4_share_nq256"),
-                         "achieved": round(hbm_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(hbm_gbps / HBM_PEAK_GBPS, 4),
-                         "traffic": None, "launches": launches, "avg_launch_us": round(prof["scan_us"] / launches, 2),
-                         "rows_scanned_per_step": int(prof["scan_rows"] // max(int(prof["searches"]), 1)),
-                         "note": "rank-0 shard, three blocking steps outside the timed region (HIP events around the tiled scan launches); "
-                                 "bytes = rows of the probed lists x %d B/element" % elem},
-            "blocking_ms_per_batch": round(lat_ms, 4),
             "tickets": stats,
-            "verify": {"tickets_equal_blocking_search": same, "queries": nv, "recall_at_k_vs_exact_top_k_of_the_collection": recall},
         }
+        if args.full:
+            plan = int(prof.get("last_plan", 0))
+            i8c = bool(plan & 4)
+            launches = max(int(prof["scan_launches"]), 1)
+            scan_s = prof["scan_us"] * 1e-6
+            elem = 1 if i8c else 2
+            kernel_bytes = float(prof["scan_rows"]) * D * elem            # rows of the probed lists the tiled scans streamed (3 steps)
+            hbm_gbps = kernel_bytes / scan_s / 1e9 if scan_s > 0 else 0.0
+            result["roofline"] = {"bound": "hbm", "kernel": "k_scan_h16<..,TILED,%s> over the probed lists" % ("I8C" if i8c else "F16"), "binding": binding_of("c4_share_nq256"),
+                                  "achieved": round(hbm_gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(hbm_gbps / HBM_PEAK_GBPS, 4),
+                                  "traffic": None, "launches": launches, "avg_launch_us": round(prof["scan_us"] / launches, 2),
+                                  "rows_scanned_per_step": int(prof["scan_rows"] // max(int(prof["searches"]), 1)),
+                                  "note": "rank-0 shard, three blocking steps outside the timed region (HIP events around the tiled scan launches); "
+                                          "bytes = rows of the probed lists x %d B/element" % elem}
+            result["blocking_ms_per_batch"] = round(lat_ms, 4)
+            result["verify"] = {"tickets_equal_blocking_search": same, "queries": nv, "recall_at_k_vs_exact_top_k_of_the_collection": recall}
         if dumped is not None:
             result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
-        if not args.no_cpu_baseline and world == 1 and not getattr(args, "_c4_second", False):
+        if args.full and not args.no_cpu_baseline and world == 1 and not getattr(args, "_c4_second", False):
             try:
                 result["cpu_baseline"] = cpu_baseline_ivf(args, N, D, K, nlist, nprobe, KC)
             except Exception as e:  # noqa: BLE001
@@ -715,13 +731,13 @@ def run_c4(args, rank, local_rank, world, dev, dist, result_out):
         except Exception:  # noqa: BLE001
             pass
         sh.comm = None
-    del sh, outs, o_t, o_b
+    del sh, outs
     torch.cuda.empty_cache()
     if getattr(args, "_c4_second", False):
         return result if rank == 0 else None
-    # ---- the second collection: 1024 generating centres under the same nlist — lists do NOT coincide with the data's clusters, recall@k
+    # ---- the second collection (--full): 1024 generating centres under the same nlist — lists do NOT coincide with the data's clusters, recall@k
     # against the exact top-k is a measurement (tests/test_gpu_baseline_configs.py::test_c4_* builds the same shape against the oracle)
-    if not args.no_second_dataset and KC == nlist and nlist > 1024 // 4:
+    if args.full and not args.no_second_dataset and KC == nlist and nlist > 1024 // 4:
         args._c4_second, args._c4_centres = True, max(nlist // 4, 1)
         try:
             second = run_c4(args, rank, local_rank, world, dev, dist, result_out)
@@ -826,39 +842,41 @@ def run_c5(args, rank, local_rank, world, dev, dist, result_out):
     dumped = None
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, outs[(args.steps - 1) % in_flight], B, K)
-    barrier()
-    t_lat = time.perf_counter()
-    for _ in range(5):
-        sh.search_packed_device(queries, K, metric, outs[0])
-    barrier()
-    lat_ms = (time.perf_counter() - t_lat) / 5 * 1000.0
+    if args.full:
+        barrier()
+        t_lat = time.perf_counter()
+        for _ in range(5):
+            sh.search_packed_device(queries, K, metric, outs[0])
+        barrier()
+        lat_ms = (time.perf_counter() - t_lat) / 5 * 1000.0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     gc.enable()
-    # ---- verification (outside the timed region): tickets == blocking sharded search; the scan kernels against the oracle on a
-    # 200k-row index of this rank's first rows (same kernels, same batch: bit-exact ids and distances)
-    o_t, o_b = sh.alloc_outputs(B, K), sh.alloc_outputs(B, K)
-    sh.search_submit(queries, K, metric, o_t).wait()
-    sh.search_packed_device(queries, K, metric, o_b)
-    torch.cuda.synchronize()
-    same = bool(torch.equal(o_t.rows, o_b.rows) and torch.equal(o_t.dists, o_b.dists) and torch.equal(o_t.counts, o_b.counts))
-    small = L.FlatIndex(None, bits, local_rank)
-    small.write_packed_device(first_words)
-    small.finalize()
-    sr = torch.zeros((B, K), dtype=torch.int64, device=dev)
-    sd = torch.zeros((B, K), dtype=torch.float32, device=dev)
-    sc = torch.zeros(B, dtype=torch.int32, device=dev)
-    small.search_packed_device(queries, K, metric, sr, sd, sc)
-    torch.cuda.synchronize()
-    host_rows = first_words.cpu().numpy().view(np.uint64)
-    host_q = queries.cpu().numpy().view(np.uint64)
-    orc = O.get()
-    exact = True
-    for qi in (0, B // 2, B - 1):
-        e_ids, e_d = orc.canonical_topk_packed(host_q[qi], host_rows, K, O.HAMMING)
-        exact = exact and np.array_equal(sr[qi].cpu().numpy().astype(np.uint32)[:len(e_ids)], e_ids) and np.array_equal(sd[qi].cpu().numpy()[:len(e_ids)], e_d)
+    if args.full:
+        # ---- verification (outside the timed region): tickets == blocking sharded search; the scan kernels against the oracle on a
+        # 200k-row index of this rank's first rows (same kernels, same batch: bit-exact ids and distances)
+        o_t, o_b = sh.alloc_outputs(B, K), sh.alloc_outputs(B, K)
+        sh.search_submit(queries, K, metric, o_t).wait()
+        sh.search_packed_device(queries, K, metric, o_b)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(o_t.rows, o_b.rows) and torch.equal(o_t.dists, o_b.dists) and torch.equal(o_t.counts, o_b.counts))
+        small = L.FlatIndex(None, bits, local_rank)
+        small.write_packed_device(first_words)
+        small.finalize()
+        sr = torch.zeros((B, K), dtype=torch.int64, device=dev)
+        sd = torch.zeros((B, K), dtype=torch.float32, device=dev)
+        sc = torch.zeros(B, dtype=torch.int32, device=dev)
+        small.search_packed_device(queries, K, metric, sr, sd, sc)
+        torch.cuda.synchronize()
+        host_rows = first_words.cpu().numpy().view(np.uint64)
+        host_q = queries.cpu().numpy().view(np.uint64)
+        orc = O.get()
+        exact = True
+        for qi in (0, B // 2, B - 1):
+            e_ids, e_d = orc.canonical_topk_packed(host_q[qi], host_rows, K, O.HAMMING)
+            exact = exact and np.array_equal(sr[qi].cpu().numpy().astype(np.uint32)[:len(e_ids)], e_ids) and np.array_equal(sd[qi].cpu().numpy()[:len(e_ids)], e_d)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
         qps = B * args.steps / elapsed
@@ -894,12 +912,13 @@ def run_c5(args, rank, local_rank, world, dev, dist, result_out):
                          "launches": launches, "avg_launch_us": round(prof["scan_us"] / launches, 2), "timed_steps": timed_steps,
                          "note": "rank-0 shard; bytes = rows x %d B (%s); HIP events around the scan launches of every %d-th step" % (
                              bits // 2 if mfma else bits // 8, "one FP4 nibble per bit" if mfma else "packed words", (args.profile_every if args.profile_every > 0 else 4))},
-            "blocking_ms_per_batch": round(lat_ms, 4),
-            "verify": {"tickets_equal_blocking_search": same, "oracle_bit_exact_on_200k_row_sample": bool(exact)},
         }
+        if args.full:
+            result["blocking_ms_per_batch"] = round(lat_ms, 4)
+            result["verify"] = {"tickets_equal_blocking_search": same, "oracle_bit_exact_on_200k_row_sample": bool(exact)}
         if dumped is not None:
             result["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 result["cpu_baseline"] = cpu_baseline(args, N, bits, K, metric)
             except Exception as e:  # noqa: BLE001

@@ -3,7 +3,7 @@
 V=$1; A=$2; B=$3; shift 3
 for r in 1 2 3; do
   for x in $A $B; do
-    env $V=$x timeout 300 python bench.py --no-cpu-baseline --no-configs --no-verify --steps 30 --warmup 5 "$@" 2>/dev/null | tail -1 | python -c "
+    env $V=$x timeout 300 python bench.py --full --no-cpu-baseline --no-configs --no-verify --steps 30 --warmup 5 "$@" 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$V=$x', 'ms_per_step', d['ms_per_step'], 'blocking', d['blocking_ms_per_batch'], 'frac', d['roofline']['frac'], 'rescored', d['rescored_per_query'], 'fallback', d['fallback_queries'])"
   done
 done

@@ -7,7 +7,7 @@ cp lynsedb_amd/liblynse_hip.so /tmp/A.so; cp "$B" /tmp/B.so
 for r in $(seq 1 $R); do
   for v in A B; do
     cp /tmp/$v.so lynsedb_amd/liblynse_hip.so
-    timeout 300 python bench.py --no-cpu-baseline --no-configs --no-verify --steps 40 --warmup 5 "$@" 2>/dev/null | tail -1 > /tmp/line.json
+    timeout 300 python bench.py --full --no-cpu-baseline --no-configs --no-verify --steps 40 --warmup 5 "$@" 2>/dev/null | tail -1 > /tmp/line.json
     python - "$v" <<'PY'
 import json,sys
 d=json.load(open('/tmp/line.json'))

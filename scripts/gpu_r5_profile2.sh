@@ -3,7 +3,9 @@
 # headline command and of its L2 / cosine variants, PMC traffic
 set -x
 mkdir -p gpurun_out/r05
-(time timeout 1500 python bench.py) > gpurun_out/r05/bench_full.json 2> gpurun_out/r05/bench_full.err
+export O=${OUT:-build/r05}
+mkdir -p "$O"
+(time timeout 1500 python bench.py --full) > $O/bench_full.json 2> $O/bench_full.err
 rm -rf gpurun_out/r05_c2 gpurun_out/r05_l2 gpurun_out/r05_cosine
 bash scripts/prof.sh r05_c2 python bench.py --no-cpu-baseline --no-configs --no-verify --steps 18 --warmup 3 > gpurun_out/r05/prof_c2.log 2>&1
 python scripts/summarize_pmc.py gpurun_out/r05_c2 gpurun_out/r05/r05_c2_pmc k_scan_qs k_scan_h16 k_select k_select_final k_i8c_prep_queries > gpurun_out/r05/sum2.log 2>&1
@@ -16,10 +18,10 @@ for M in l2 cosine; do
 done
 find gpurun_out -name "*kernel_trace.csv" -size +3M -delete
 find gpurun_out -name "*counter_collection.csv" -size +12M -delete
-tail -3 gpurun_out/r05/bench_full.err
+tail -3 $O/bench_full.err
 python - <<'PY'
-import json
-d=json.loads(open("gpurun_out/r05/bench_full.json").read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.environ["O"] + "/bench_full.json").read().strip().splitlines()[-1])
 print(d["ms_per_step"], d["value"], d["roofline"]["frac"], d["roofline"].get("avg_launch_us"), d["blocking_ms_per_batch"], d["two_in_flight_ms_per_step"], d["config"]["batches_in_flight"])
 print({k: (v.get("ms_per_step") if isinstance(v, dict) else v) for k, v in d.get("same_shard_variants", {}).items()})
 print(d.get("second_distribution"))

@@ -5,7 +5,7 @@
 set -x
 O=gpurun_out/r06
 mkdir -p $O
-(time timeout 1500 python bench.py) > $O/bench_full.json 2> $O/bench_full.err
+(time timeout 1500 python bench.py --full) > $O/bench_full.json 2> $O/bench_full.err
 bash scripts/prof.sh r06_c2 python bench.py --no-cpu-baseline --no-configs --no-verify --steps 18 --warmup 3 > $O/prof_c2.log 2>&1
 python scripts/summarize_pmc.py gpurun_out/r06_c2 $O/r06_c2_pmc k_scan_qs k_scan_h16 k_select k_select_final k_i8c_prep_queries > $O/sum.log 2>&1
 python scripts/pmc_traffic.py gpurun_out/r06_c2 $O/r06_pmc_traffic.json 10000000 768 0 >> $O/sum.log 2>&1
@@ -25,8 +25,8 @@ done
 unset LYNSE_BENCH_NO_INFLIGHT LYNSE_BENCH_C4_ITERS LYNSE_BENCH_C4_NO_SECOND
 find gpurun_out -name "*kernel_trace.csv" -size +3M -delete
 find gpurun_out -name "*counter_collection.csv" -size +12M -delete
-(time timeout 900 python bench.py --config c4 --steps 30 --warmup 3) > $O/bench_c4.json 2> $O/bench_c4.err
-(time timeout 900 python bench.py --config c5 --steps 30 --warmup 3) > $O/bench_c5.json 2> $O/bench_c5.err
+(time timeout 900 python bench.py --config c4 --steps 30 --warmup 3 --full) > $O/bench_c4.json 2> $O/bench_c4.err
+(time timeout 900 python bench.py --config c5 --steps 30 --warmup 3 --full) > $O/bench_c5.json 2> $O/bench_c5.err
 S="timeout 300 python bench.py --no-cpu-baseline --no-configs --no-verify --steps 80 --warmup 5 --rows 1250000"
 LYNSE_BENCH_FORCE_COMM=1 $S --in-flight 3 > $O/shard_1p25m_in_flight_1rank_comm.json 2>/dev/null
 $S --in-flight 3 > $O/shard_1p25m_in_flight.json 2>/dev/null

@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 ROOT=$(pwd)
 mkdir -p gpurun_out/tl
 for fl in 1 3; do
-B="python bench.py --no-cpu-baseline --no-verify --no-configs --steps 40 --warmup 5 --rows 1250000 --in-flight $fl"
+B="python bench.py --full --no-cpu-baseline --no-verify --no-configs --steps 40 --warmup 5 --rows 1250000 --in-flight $fl"
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace -d $ROOT/gpurun_out/tl/f$fl -o u --output-format csv -- bash -c "cd $ROOT && $B" > $ROOT/gpurun_out/tl/f$fl.log 2>&1)
 f=$(find gpurun_out/tl/f$fl -name "*kernel_trace.csv" | head -1)
 echo "== in flight $fl"; python scripts/trace_timeline.py $f 16
