@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from conftest import oracle_for_every_query
 
 pytestmark = pytest.mark.gpu
 IP, L2, COS = O.IP, O.L2, O.COS
@@ -126,10 +127,14 @@ def ref_build(ref, data, M, n_clusters=256, code_rows=None):
 
 
 def _cut(scores, asc, N, rows):
-    """positions of the N best by the canonical (score, row) key: NaN ranks last (as +-inf), -0 == +0"""
+    """positions of the N best by the canonical (score, row) key: NaN ranks last (as +-inf), -0 == +0.  A partition first keeps
+    every key up to the N-th smallest (ties at the cut included), so the lexsort that decides them sees all of them."""
     s = np.where(np.isnan(scores), np.inf if asc else -np.inf, scores).astype(f32) + f32(0.0)
     key = s if asc else -s
-    order = np.lexsort((rows, key))
+    cand = np.arange(key.size)
+    if 0 < N < key.size:
+        cand = np.nonzero(key <= np.partition(key, N - 1)[N - 1])[0]
+    order = cand[np.lexsort((rows[cand], key[cand]))]
     return order[:N], s
 
 
@@ -142,22 +147,25 @@ def ref_search(ref, data, cb, codes, queries, k, metric, oversample=32):
     asc = metric != IP
     kk = min(k, n_pq)
     N = min(kk * oversample, n_pq)
-    out = []
-    for qi in range(queries.shape[0]):
+    by_m = np.ascontiguousarray(codes.T)
+
+    def one(qi):
         acc = np.zeros(n_pq, f32)
         for m in range(M):
-            acc = (acc + lut[qi, m, codes[:, m]]).astype(f32)
+            acc = (acc + lut[qi, m, by_m[m]]).astype(f32)
         pool, _ = _cut(acc, asc, N, np.arange(n_pq))
         pool = np.ascontiguousarray(pool, np.uint64)
         d = np.zeros(pool.size, f32)
         lib.pqr_dists(_p(np.ascontiguousarray(queries[qi])), _p(data), dim, _p(pool), pool.size, metric, fp["lo_compute_distance"], _p(d))
         sel, s = _cut(d, asc, kk, pool)
-        out.append((pool[sel].astype(np.uint64), s[sel]))
-    return out
+        return pool[sel].astype(np.uint64), s[sel]
+
+    return oracle_for_every_query(one, queries.shape[0])
 
 
 def check_search(got, exp):
     rows, dists, counts = got
+    assert counts.shape[0] == len(exp)
     for qi, (e_r, e_d) in enumerate(exp):
         c = int(counts[qi])
         assert c == e_r.size, (qi, c, e_r.size)
@@ -171,9 +179,26 @@ def make_index(L, data):
     return idx
 
 
+def loaded_pq(L, rng, n, dim, M, K):
+    """n random rows with random codebooks [M][K][dim / M] and codes < K installed through load_pq: search cases without a
+    training restatement"""
+    data = rng.standard_normal((n, dim)).astype(f32)
+    cb = rng.standard_normal((M, K, dim // M)).astype(f32)
+    codes = rng.integers(0, K, (n, M), dtype=np.uint8)
+    idx = make_index(L, data)
+    idx.load_pq(cb, codes)
+    return idx, data, cb, codes
+
+
 # ------------------------------------------------------------------------------------------- tests ----
-@pytest.mark.parametrize("n,dim,M,ncl", [(2000, 32, 8, 256), (50, 16, 4, 256), (300, 24, 6, 1), (1000, 36, 12, 64)])
+@pytest.mark.parametrize("n,dim,M,ncl", [(2000, 32, 8, 256), (50, 16, 4, 256), (300, 24, 6, 1), (1000, 36, 12, 64),
+                                         (1000, 384, 16, 256), (1000, 768, 16, 256), (1000, 1536, 16, 256), (1000, 300, 4, 256),
+                                         (1000, 768, 4, 256)])
 def test_codebooks_and_codes_bit_equal(L, ref, n, dim, M, ncl):
+    """The sub-vector width ss = dim / M picks k_pq_assign's instance and the codebook's home (LDS when K ss 4 <= 64 KiB):
+    ss <= 16 below; 24 -> <32> (24 KiB in LDS), 48 -> <64> (48 KiB in LDS), 96 -> <128> (96 KiB: global memory), 75 -> <128>
+    (75 KiB: global memory; nine 8-chunks, the odd one and a tail of 3), 192 -> <0> (sub-vector read from memory).  ss = 75, 96 and
+    192 also take k_pq_update / k_pq_empty past one 64-column pass."""
     rng = np.random.default_rng(n + dim)
     data = rng.standard_normal((n, dim)).astype(f32)
     idx = make_index(L, data)
@@ -221,10 +246,17 @@ def test_stride_sample_120k(L, ref):
 
 
 @pytest.mark.parametrize("metric", [IP, L2, COS])
-@pytest.mark.parametrize("M", [8, 16, 32])
-def test_search_parity(L, ref, metric, M):
-    rng = np.random.default_rng(M * 10 + metric)
-    n, dim = 3000, 32
+@pytest.mark.parametrize("dim,M", [pytest.param(32, 8, id="8"), pytest.param(32, 16, id="16"), pytest.param(32, 32, id="32"),
+                                   pytest.param(384, 16, id="384x16"), pytest.param(768, 16, id="768x16"),
+                                   pytest.param(1536, 16, id="1536x16"), pytest.param(300, 4, id="300x4"),
+                                   pytest.param(768, 4, id="768x4")])
+def test_search_parity(L, ref, metric, dim, M):
+    """Every query of every batch.  The tables' sub-vector width ss = dim / M picks the path through pq_pair in k_pq_lut: 4, 2, 1
+    (one 8-chunk or the tail only), 24 (one 16-wide two-accumulator step and the odd 8-chunk), 48 (three steps), 96 (six),
+    75 (four steps, the odd 8-chunk and a tail of 3) and 192 (twelve steps).  k = 1, 10 cut the pool by the radix selection,
+    k = 100 pools every row."""
+    rng = np.random.default_rng(M * 10 + metric + (0 if dim == 32 else dim))
+    n = 3000 if dim == 32 else 1500
     data = rng.standard_normal((n, dim)).astype(f32)
     idx = make_index(L, data)
     idx.build_pq(M, 256)
@@ -234,11 +266,8 @@ def test_search_parity(L, ref, metric, M):
         queries = rng.standard_normal((nq, dim)).astype(f32)
         queries[0] = data[11]
         for k in (1, 10, 100):
-            if nq == 256 and k == 100:
-                continue
-            exp = ref_search(ref, data, cb, codes, queries[: min(nq, 16)], k, metric)
-            got = idx.search_pq_batch_arrays(queries, k, NAME[metric])
-            check_search(tuple(a[: min(nq, 16)] for a in got), exp)
+            exp = ref_search(ref, data, cb, codes, queries, k, metric)
+            check_search(idx.search_pq_batch_arrays(queries, k, NAME[metric]), exp)
 
 
 def test_search_odd_dim_large_pool_and_k(L, ref):
@@ -253,6 +282,74 @@ def test_search_odd_dim_large_pool_and_k(L, ref):
         for k in (600, 10000):          # N = 19,200 (> 16,384: the host-selected pool) and N = n_pq
             exp = ref_search(ref, data, p["codebooks"], p["codes"], queries, k, metric)
             check_search(idx.search_pq_batch_arrays(queries, k, NAME[metric]), exp)
+    # 300 queries at k = 600: two query chunks (256 + 44), the host selection's buffers reused by the second one
+    many = rng.standard_normal((300, dim)).astype(f32)
+    exp = ref_search(ref, data, p["codebooks"], p["codes"], many, 600, L2)
+    check_search(idx.search_pq_batch_arrays(many, 600, "l2"), exp)
+
+
+@pytest.mark.parametrize("dim,M,K,nqs", [pytest.param(768, 96, 256, (1, 3, 7), id="M96"),
+                                         pytest.param(768, 768, 256, (1, 5), id="PQ768"),
+                                         pytest.param(64, 32, 150, (1, 4, 9), id="K150")])
+def test_adc_table_chunks(L, ref, dim, M, K, nqs):
+    """k_pq_adc when the tables of a query group exceed 64 KiB: mc = min(M, 16384 / (qb K)) subspaces per LDS chunk, qb = 4 from
+    four queries on, else 1.  M = 96: six chunks at qb = 4, two (64 + 32) at qb = 1.  PQ768 (ss = 1): 48 chunks at qb = 4, 12 at
+    qb = 1.  K = 150, M = 32: mc = 27 at qb = 4, so the byte path (mc % 4 != 0) with a ragged last chunk of 5; one chunk of 32 on
+    the word path at qb = 1.  nq = 7, 5, 9 end in a partial group of four."""
+    rng = np.random.default_rng(M + K)
+    idx, data, cb, codes = loaded_pq(L, rng, 4000, dim, M, K)
+    for nq in nqs:
+        queries = rng.standard_normal((nq, dim)).astype(f32)
+        queries[0] = data[7]
+        for metric in (IP, L2, COS):
+            exp = ref_search(ref, data, cb, codes, queries, 10, metric)
+            check_search(idx.search_pq_batch_arrays(queries, 10, NAME[metric]), exp)
+
+
+def test_query_chunks_of_256(L, ref):
+    """nq = 601: query chunks of 256 / 256 / 89 (QCHUNK), the last ending in a partial group of four; every query checked."""
+    rng = np.random.default_rng(601)
+    n, dim = 3000, 32
+    data = rng.standard_normal((n, dim)).astype(f32)
+    idx = make_index(L, data)
+    idx.build_pq(8, 256)
+    p = idx.pq_params()
+    queries = rng.standard_normal((601, dim)).astype(f32)
+    for metric in (IP, L2, COS):
+        exp = ref_search(ref, data, p["codebooks"], p["codes"], queries, 10, metric)
+        check_search(idx.search_pq_batch_arrays(queries, 10, NAME[metric]), exp)
+
+
+def test_query_chunks_of_223_at_600k_rows(L, ref):
+    """n_pq = 600,000: the [chunk][n_pq] score matrix caps a query chunk at floor(512 MiB / 4 n_pq) = 223 queries, which is no
+    multiple of the ADC's groups of four; 230 queries run as 223 + 7.  One metric (IP: the descending key) keeps the restatement's
+    600,000-row ADC sums to a few seconds."""
+    rng = np.random.default_rng(600)
+    n = 600_000
+    assert (512 << 20) // (4 * n) == 223
+    idx, data, cb, codes = loaded_pq(L, rng, n, 16, 4, 256)
+    queries = rng.standard_normal((230, 16)).astype(f32)
+    queries[0] = data[599_999]
+    exp = ref_search(ref, data, cb, codes, queries, 10, IP)
+    check_search(idx.search_pq_batch_arrays(queries, 10, "ip"), exp)
+
+
+def test_rescore_at_768_on_both_sides_of_the_lds_limit(L, ref):
+    """D = 768 (a 3 KiB query in LDS beside the keys).  k = 512: a pool of N = 16,384 keys, sorted in LDS (128 KiB + 3 KiB of
+    160 KiB).  k = 513: N = 16,416 > 16,384, scored on the device and selected on the host.  n = 17,000 keeps N < n, so both pools
+    come from the radix selection."""
+    rng = np.random.default_rng(768)
+    n = 17_000
+    idx, data, cb, codes = loaded_pq(L, rng, n, 768, 16, 256)
+    queries = rng.standard_normal((3, 768)).astype(f32)
+    queries[0] = data[5]
+    for k, N in ((512, 16_384), (513, 16_416)):
+        assert min(k * 32, n) == N
+        for metric in (IP, L2, COS):
+            exp = ref_search(ref, data, cb, codes, queries, k, metric)
+            got = idx.search_pq_batch_arrays(queries, k, NAME[metric])
+            assert (got[2] == k).all()
+            check_search(got, exp)
 
 
 def test_ties_and_nan_query(L, ref):

@@ -97,21 +97,32 @@ def loaded(L, oracle, data, nlist, metric, iters=8):
 
 
 # -------------------------------------------------------------------------------------- quantizer ----
-def test_sq8_params_bit_equal_to_the_restatement(L):
-    rng = np.random.default_rng(1)
-    n, dim = 1500, 24
+def _sq8_params_case(L, seed, dim, const, nan, neg, inf):
+    rng = np.random.default_rng(seed)
+    n = 1500
     data = rng.standard_normal((n, dim)).astype(f32)
-    data[:, 3] = 2.5                                    # constant dimension: scale 1.0
-    data[::7, 5] = np.nan                               # NaN elements among finite ones never win min / max
-    data[:, 9] = -np.abs(data[:, 9]) - 3.0              # negative-only values
-    data[11, 12] = np.inf                               # +inf is a max like any other value
+    data[:, const] = 2.5                                # constant dimension: scale 1.0
+    data[::7, nan] = np.nan                             # NaN elements among finite ones never win min / max
+    data[:, neg] = -np.abs(data[:, neg]) - 3.0          # negative-only values
+    data[11, inf] = np.inf                              # +inf is a max like any other value
     for metric in (IP, L2, COS):
         idx = L.IvfFlatIndex.build(None, data, dim, 8, 5, NAME[metric], quantizer="sq8")
         mn, sc = idx.sq8_params()
         e_mn, e_sc = sq_fit(data)
         assert np.array_equal(mn.view(np.uint32), e_mn.view(np.uint32)), (mn, e_mn)
         assert np.array_equal(sc.view(np.uint32), e_sc.view(np.uint32)), (sc, e_sc)
-        assert sc[3] == 1.0
+        assert sc[const] == 1.0
+
+
+def test_sq8_params_bit_equal_to_the_restatement(L):
+    _sq8_params_case(L, 1, 24, 3, 5, 9, 12)
+
+
+@pytest.mark.parametrize("dim,cols", [(300, (259, 261, 265, 268)), (768, (259, 517, 265, 524))])
+def test_sq8_params_past_the_first_column_block(L, dim, cols):
+    """k_ivfsq_minmax / k_ivfsq_fit cover 256 columns per blockIdx.x: D = 300 and 768 take two and three column blocks, with the
+    constant, NaN-laced, negative-only and +inf columns in the second (and third) one."""
+    _sq8_params_case(L, dim, dim, *cols)
 
 
 def test_sq8_is_refused_for_binary_metrics_and_non_sq8_handles(L):
@@ -124,10 +135,15 @@ def test_sq8_is_refused_for_binary_metrics_and_non_sq8_handles(L):
 
 
 # --------------------------------------------------------------------------------------- training ----
-@pytest.mark.parametrize("metric", [IP, L2, COS])
-def test_sq8_build_trains_on_the_decoded_rows(L, oracle, metric):
-    _, data = clustered(10 + metric, 3000, 24)
-    idx = L.IvfFlatIndex.build(None, data, 24, 16, 20, NAME[metric], quantizer="sq8")
+AT_768 = [pytest.param(IP, 24, id="0"), pytest.param(L2, 24, id="1"), pytest.param(COS, 24, id="2"),
+          pytest.param(IP, 768, id="768-0"), pytest.param(L2, 768, id="768-1"), pytest.param(COS, 768, id="768-2")]
+
+
+@pytest.mark.parametrize("metric,dim", AT_768)
+def test_sq8_build_trains_on_the_decoded_rows(L, oracle, metric, dim):
+    """D = 768: the device quantiser over three column blocks, k-means on the decoded rows at embedding width."""
+    _, data = clustered(10 + metric + (0 if dim == 24 else dim), 3000, dim)
+    idx = L.IvfFlatIndex.build(None, data, dim, 16, 20, NAME[metric], quantizer="sq8")
     mn, sc = idx.sq8_params()
     dec = sq_codec(data, mn, sc)
     e_cen, e_asg = oracle.kmeans_train(dec, 16, 20, metric)
@@ -151,6 +167,10 @@ def test_sq8_search_sweep(L, oracle, metric):
             for nprobe in (1, 8, nlist):
                 check(oracle, idx.search_batch_arrays(queries, k, nprobe), queries, data, dec, cen, asg, nprobe, k, metric, mn, sc,
                       what=(nq, k, nprobe))
+    # nq = 600: query chunks of 256 / 256 / 88, each with its own codec, pool stage and rerank
+    more = (data[rng.integers(0, data.shape[0], 344)] + 0.1 * rng.standard_normal((344, 40))).astype(f32)
+    queries = np.concatenate([allq, more])
+    check(oracle, idx.search_batch_arrays(queries, 10, 8), queries, data, dec, cen, asg, 8, 10, metric, mn, sc, what="nq=600")
 
 
 def test_sq8_pool_stage_plans(L, oracle):
@@ -170,6 +190,40 @@ def test_sq8_pool_stage_plans(L, oracle):
             assert plan & bit, (nq, plan)
         check(oracle, got, queries[:nq], data, dec, cen, asg, nprobe, k, IP, mn, sc, what=("plan", nq))
     idx.profile_enable(False)
+
+
+def test_sq8_pool_stage_int8_plan_at_768(L, oracle):
+    """The certified int8 pass at embedding width: 64 IP queries over 66,000 rows of six whole 128-column slabs (D = 768).  Any
+    lists load: each decoded row goes to its best of 64 sampled decoded rows by a float64 inner product (no k-means restatement
+    at this size)."""
+    rng, data = clustered(33, 66_000, 768, ncent=24)
+    mn, sc = sq_fit(data)
+    dec = sq_codec(data, mn, sc)
+    cen = dec[rng.choice(data.shape[0], 64, replace=False)].copy()
+    asg = np.argmax(dec.astype(np.float64) @ cen.T.astype(np.float64), axis=1).astype(np.uint32)
+    idx = L.IvfFlatIndex.load_sq8(data, cen, asg, mn, sc, "ip")
+    queries = (data[rng.integers(0, data.shape[0], 64)] + 0.05 * rng.standard_normal((64, 768))).astype(f32)
+    idx.profile_enable(True)
+    idx.profile_get(reset=True)
+    got = idx.search_batch_arrays(queries, 10, 8)
+    plan = int(idx.profile_get(reset=True)["last_plan"])
+    idx.profile_enable(False)
+    assert plan & 64, plan
+    check(oracle, got, queries, data, dec, cen, asg, 8, 10, IP, mn, sc, what="int8 plan at 768")
+
+
+@pytest.mark.parametrize("metric", [IP, L2, COS])
+def test_sq8_rerank_lds_boundary_at_768(L, oracle, metric):
+    """D = 768, 16,400 rows, every list probed.  k = 1,638: a pool of 16,380 keys, sorted in LDS beside the 3 KiB query.
+    k = 1,639: a pool of 16,390 > 16,384, scored on the device and selected on the host."""
+    rng, data = clustered(170 + metric, 16_400, 768, ncent=8)
+    idx, mn, sc, dec, cen, asg = loaded(L, oracle, data, 8, metric, iters=2)
+    q = (data[rng.integers(0, data.shape[0], 2)] + 0.05 * rng.standard_normal((2, 768))).astype(f32)
+    for k, pool in ((1638, 16_380), (1639, 16_390)):
+        assert min(10 * k, data.shape[0]) == pool and (pool <= 16_384) == (k == 1638)
+        got = idx.search_batch_arrays(q, k, 8)
+        assert (got[2] == k).all()
+        check(oracle, got, q, data, dec, cen, asg, 8, k, metric, mn, sc, what=("rerank", k))
 
 
 @pytest.mark.parametrize("metric", [IP, L2, COS])
@@ -222,11 +276,11 @@ def test_sq8_filtered(L, oracle, metric):
 
 
 # ------------------------------------------------------------------------------------ insert / delete ----
-@pytest.mark.parametrize("metric", [IP, L2, COS])
-def test_sq8_insert_clamps_and_delete_reassigns(L, oracle, metric):
-    rng, data = clustered(70 + metric, 4000, 24)
+@pytest.mark.parametrize("metric,dim", AT_768)
+def test_sq8_insert_clamps_and_delete_reassigns(L, oracle, metric, dim):
+    rng, data = clustered(70 + metric + (0 if dim == 24 else dim), 4000, dim)
     idx, mn, sc, dec, cen, asg = loaded(L, oracle, data, 16, metric)
-    new = (3.0 * rng.standard_normal((300, 24))).astype(f32)          # partly outside the fitted range: the codes clamp
+    new = (3.0 * rng.standard_normal((300, dim))).astype(f32)         # partly outside the fitted range: the codes clamp
     idx.insert(new)
     mn2, sc2 = idx.sq8_params()
     assert np.array_equal(mn2.view(np.uint32), mn.view(np.uint32)) and np.array_equal(sc2.view(np.uint32), sc.view(np.uint32))
@@ -382,6 +436,14 @@ def test_sq8_device_search_with_host_selected_pool(L, oracle):
     idx.search_device(torch.as_tensor(q, device=dev), k, 16, r, d, c)
     got = (r.cpu().numpy().view(np.uint64), d.cpu().numpy(), c.cpu().numpy().astype(np.uint32))
     check(oracle, got, q, data, dec, cen, asg, 16, k, L2, mn, sc, what="device k=2000")
+    # 600 device-resident queries: query chunks of 256 / 256 / 88 read from and written to each chunk's offset in the device buffers
+    q = (data[rng.integers(0, data.shape[0], 600)] + 0.05 * rng.standard_normal((600, 16))).astype(f32)
+    r = torch.zeros((600, 10), dtype=torch.int64, device=dev)
+    d = torch.zeros((600, 10), dtype=torch.float32, device=dev)
+    c = torch.zeros(600, dtype=torch.int32, device=dev)
+    idx.search_device(torch.as_tensor(q, device=dev), 10, 4, r, d, c)
+    got = (r.cpu().numpy().view(np.uint64), d.cpu().numpy(), c.cpu().numpy().astype(np.uint32))
+    check(oracle, got, q, data, dec, cen, asg, 4, 10, L2, mn, sc, what="device nq=600")
 
 
 def test_sq8_sharded_search_is_refused(L):

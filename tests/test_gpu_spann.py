@@ -150,6 +150,88 @@ def test_insert_postings_of_non_finite_and_extreme_rows(L, oracle, metric, R):
     assert len(idx) == allrows.shape[0]
 
 
+@pytest.mark.parametrize("metric,R", [(L2, 1), (IP, 2)])
+def test_build_over_more_than_65536_rows(L, oracle, metric, R):
+    """70,000 rows: the top-keep FLAT search runs in two batches (65,536 + 4,464, the second with row0 > 0) and k_spann_flag
+    strides its grid (8,192 blocks x 4 rows per pass).  Postings bit-equal to the rule; queries at rows of the second batch."""
+    rng, data = clustered(200 + R, 70_000, 16, ncent=12, noise=0.6)
+    nlist = 16
+    idx = L.SpannIndex.build(data, 16, nlist, 5, NAME[metric], replica_count=R)
+    cen, _ = oracle.kmeans_train(data, nlist, 5, metric)
+    off, rows = csr_of(row_lists(oracle, data, cen, metric, R), cen.shape[0])
+    assert_postings(idx, off, rows, (metric, R))
+    at = 65_536 + rng.integers(0, 70_000 - 65_536, 8)
+    queries = (data[at] + 0.01).astype(f32)
+    got = idx.search_batch_arrays(queries, 10, 4)
+    check_search(oracle, got, queries, data, cen, off, rows, 4, 10, metric, what=(metric, R))
+    assert (got[0][:, :10] >= 65_536).any()
+    if metric == L2:
+        assert np.array_equal(got[0][:, 0], at.astype(np.uint64))
+
+
+def test_insert_of_more_than_65536_rows(L, oracle):
+    """An insert of 66,000 rows: two top-keep batches and a strided k_spann_flag grid over the new rows, whose NaN, +inf and 3e38
+    rows sit before and past 32,768 and 65,536 (k_spann_slow for rows of both batches)."""
+    rng, data = clustered(210, 2000, 12, ncent=6, noise=0.5)
+    nlist, metric, R = 10, COS, 1
+    idx = L.SpannIndex.build(data, 12, nlist, 20, NAME[metric], replica_count=R)
+    cen, _ = oracle.kmeans_train(data, nlist, 20, metric)
+    new = (np.repeat(data, 33, axis=0) + 0.3 * rng.standard_normal((66_000, 12))).astype(f32)
+    for at in (100, 40_000, 65_800):
+        new[at, 3] = np.nan
+        new[at + 1, :] = np.inf
+        new[at + 2, :] = f32(3e38)
+    idx.insert(new)
+    want = row_lists(oracle, data, cen, metric, R) + row_lists(oracle, new, cen, metric, R)
+    assert_postings(idx, *csr_of(want, cen.shape[0]), "insert of 66,000 rows")
+    assert len(idx) == 68_000
+
+
+@pytest.mark.parametrize("metric", [IP, L2, COS])
+def test_slow_rule_over_16384_centroids(L, oracle, metric):
+    """k_spann_slow at nlist = 16,384 (the IVF limit): 64 KiB of ranks plus the keep slots in LDS.  Loaded over lists of the nearest
+    centroid (float64), then an insert of rows with NaN, +-inf and 3e38 elements beside ordinary ones, compared with row_lists."""
+    rng = np.random.default_rng(220 + metric)
+    nlist, dim, R = 16_384, 8, 2
+    cen = rng.standard_normal((nlist, dim)).astype(f32)
+    data = rng.standard_normal((20_000, dim)).astype(f32)
+    c64 = cen.astype(np.float64)
+    near = np.argmin(np.sum(c64 ** 2, 1)[None] - 2 * data.astype(np.float64) @ c64.T, axis=1)
+    old = [[int(c)] for c in near]
+    off, rows = csr_of(old, nlist)
+    idx = L.SpannIndex.load(data, cen, off, rows, R, NAME[metric])
+    new = rng.standard_normal((10, dim)).astype(f32)
+    new[0, 3] = np.nan
+    new[1, :] = np.nan
+    new[2, 5] = np.inf
+    new[3, 5] = -np.inf
+    new[4, :] = np.inf
+    new[5, 0], new[5, 1] = np.inf, -np.inf
+    new[6, :] = f32(3e38)                 # inner products overflow
+    new[7, ::2], new[7, 1::2] = f32(3e38), f32(-3e38)
+    idx.insert(new)
+    want = old + row_lists(oracle, new, cen, metric, R)
+    assert_postings(idx, *csr_of(want, nlist), metric)
+
+
+@pytest.mark.parametrize("metric,sq8", [(IP, False), (L2, False), (COS, False), (L2, True)])
+def test_build_at_768(L, oracle, metric, sq8):
+    """D = 768: the posting rule's top-keep is the FLAT search of the rows against the centroid store at embedding width;
+    postings and a search checked (SQ8: on the decoded rows, with the exact rerank)."""
+    rng, data = clustered(230 + metric + 10 * sq8, 3000, 768, ncent=10, noise=0.6)
+    nlist, R = 16, 2
+    idx = L.SpannIndex.build(data, 768, nlist, 10, NAME[metric], replica_count=R, sq8=sq8)
+    sq = sq_fit(data) if sq8 else None
+    route = sq_codec(data, *sq) if sq8 else data
+    cen, _ = oracle.kmeans_train(route, nlist, 10, metric)
+    off, rows = csr_of(row_lists(oracle, route, cen, metric, R), cen.shape[0])
+    assert_postings(idx, off, rows, (metric, sq8))
+    assert rows.size > data.shape[0]
+    queries = (data[rng.integers(0, data.shape[0], 12)] + 0.05 * rng.standard_normal((12, 768))).astype(f32)
+    got = idx.search_batch_arrays(queries, 10, 4)
+    check_search(oracle, got, queries, data, cen, off, rows, 4, 10, metric, scored=route if sq8 else None, sq=sq, what=(metric, sq8))
+
+
 # ----------------------------------------------------------------------------------------- search ----
 def loaded(L, oracle, data, nlist, metric, R):
     """an index over given lists: k-means of the oracle, lists by the rule (the build path is checked above)"""
@@ -231,7 +313,8 @@ def test_sq8_search_pools(L, oracle, metric):
     assert idx.is_sq8
     g_mn, g_sc = idx.sq8_params()
     assert np.array_equal(g_mn.view(np.uint32), mn.view(np.uint32))
-    for nq, k, nprobe in ((1, 10, 4), (7, 1, 1), (40, 100, 8), (3, 1700, 4), (2, 3000, 24)):   # pools up to 17,000 / all rows: host-selected
+    # pools up to 17,000 / all rows: host-selected; 300 queries: query chunks of 256 + 44
+    for nq, k, nprobe in ((1, 10, 4), (7, 1, 1), (40, 100, 8), (3, 1700, 4), (2, 3000, 24), (300, 10, 4)):
         queries = (data[rng.integers(0, 4000, nq)] + 0.2 * rng.standard_normal((nq, 16))).astype(f32)
         got = idx.search_batch_arrays(queries, k, nprobe)
         check_search(oracle, got, queries, data, cen, off, rows, nprobe, k, metric, scored=dec, sq=(mn, sc), what=(metric, nq, k, nprobe))
