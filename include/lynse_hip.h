@@ -180,7 +180,9 @@ int lynse_hip_flat_search_filtered_bitset_f32(lynse_hip_flat *h, const float *qu
  * pass 2 rescores those exactly with the single-row f32 kernels and returns the best k.  Approximate by design: a true
  * neighbour outside the n_cand best codes is lost, exactly as in the reference.  Ties at the n_cand cut and between equal
  * exact distances are broken by row id (the reference leaves them to heap / unstable-sort order).  Other metrics take the
- * ordinary exact path, as `use_sq8` does. */
+ * ordinary exact path, as `use_sq8` does.  Non-finite values: the fit ignores a NaN element (its code is 0) and a dimension
+ * holding +-inf gets scale 0 (every code 0), so pass 1 stays an integer ranking; pass 2 follows the NON-FINITE VALUES rule of the
+ * FLAT searches above (a NaN distance is the worst value of the metric, ties by ascending row). */
 int lynse_hip_flat_search_sq8_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k,
                                   int metric, uint64_t *out_rows, float *out_dists,
                                   uint32_t *out_counts);

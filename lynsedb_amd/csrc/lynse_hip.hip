@@ -3214,7 +3214,11 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             if (i8c && !i8c_codes_finite(h, metric, nqc, msk)) { i8c_strike_counter(h, metric).store(-1); i8c = false; }
         }
         i8c_attempted = i8c_attempted || i8c;
-        if (!binary && !i8c && !small_path_ok(h, nqc, kk, metric, filtered)) LY_TRY(need_shadow());   // this chunk scans the f16 shadow
+        // this chunk scans the f16 shadow.  (Not on the gathered-rows strategy: the compact copy was gathered from the complete shadow
+        // above and the handle now VIEWS it — n is the subset size, so shadow_ready() would report a stale shadow and
+        // ensure_shadow_locked() would point an F16 shard's aliased rows16 back at the whole shard: the scan then scored rows
+        // 0 .. n_subset - 1 of the shard under the subset's row ids)
+        if (!binary && !i8c && !direct && !small_path_ok(h, nqc, kk, metric, filtered)) LY_TRY(need_shadow());
         if (small_path_ok(h, nqc, kk, metric, filtered)) {
             // fused single-launch search: the last workgroup writes straight into the caller's device buffers, or into
             // pinned host memory (no copy kernels, one synchronisation); it cannot overflow

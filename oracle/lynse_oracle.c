@@ -1072,6 +1072,13 @@ size_t lo_canonical_topk_f16(const float *query, const float *cands_decoded, siz
     return r;
 }
 
+/* The f16 kernels' distance of `query` to every decoded row, NaN / +-inf propagated as the arithmetic gives them: what the
+ * pinned non-finite order of include/lynse_hip.h is applied to on an F16 shard. */
+void lo_all_distances_f16(const float *query, const float *cands_decoded, size_t dim, size_t n, int metric, float *out);
+void lo_all_distances_f16(const float *query, const float *cands_decoded, size_t dim, size_t n, int metric, float *out) {
+    for (size_t i = 0; i < n; ++i) out[i] = lo_distance_f16(query, cands_decoded + i * dim, dim, metric);
+}
+
 /* ------------------------------------------------------------- SQ8 two-pass FLAT (FLAT-*-SQ8) */
 
 /* SQ8Data::from_f32_parallel (flat_mmap.rs:5685-5737): per-dimension min / scale = 255/(max-min) (0 when the range is
@@ -1147,6 +1154,8 @@ size_t lo_sq8_search_canonical(const float *query, const float *cands, const uin
     for (size_t i = 0; i < n_cand; ++i) {
         p[i].id = sc[i].row;
         p[i].d = lo_compute_distance(query, cands + (size_t)sc[i].row * dim, dim, metric);
+        /* the non-finite rule of the FLAT searches (include/lynse_hip.h): a NaN distance is the worst value of the metric, ties by row */
+        if (p[i].d != p[i].d) p[i].d = lo_metric_is_ascending(metric) ? INFINITY : -INFINITY;
     }
     g_cmp_asc = lo_metric_is_ascending(metric);
     qsort(p, n_cand, sizeof(cpair_t), cmp_canonical);

@@ -81,6 +81,7 @@ class Oracle:
         s("lo_distance_f16", C.c_float, _f32p, _f32p, _sz, C.c_int)
         s("lo_round_f16", None, _f32p, _sz, _f32p)
         s("lo_canonical_topk_f16", _sz, _f32p, _f32p, _sz, _sz, _sz, C.c_int, _u32p, _f32p)
+        s("lo_all_distances_f16", None, _f32p, _f32p, _sz, _sz, C.c_int, _f32p)
         s("lo_flat_search_filtered", _sz, _f32p, _f32p, _sz, _sz, _sz, C.c_int, _u64p, _sz, C.c_int, _u32p, _f32p)
         s("lo_packed_search_filtered", _sz, _u64p, _u64p, _sz, _sz, _sz, C.c_int, _u64p, _sz, _u32p, _f32p)
         s("lo_canonical_topk_filtered", _sz, _f32p, _f32p, _u64p, _u64p, _sz, _sz, _sz, _sz, C.c_int, _u64p, _sz, _u32p, _f32p)
@@ -270,6 +271,25 @@ class Oracle:
         c, pc = self._f(cands_decoded)
         n, dim = c.shape
         return self._topk_call(self.lib.lo_canonical_topk_f16, k, pq, pc, dim, n, k, metric)
+
+    def all_distances_f16(self, query, cands_decoded, metric):
+        """The f16 kernels' distance to every decoded row; NaN / +-inf come out as the arithmetic gives them."""
+        q, pq = self._f(query)
+        c, pc = self._f(cands_decoded)
+        n, dim = c.shape
+        out = np.zeros(n, np.float32)
+        self.lib.lo_all_distances_f16(pq, pc, dim, n, metric, out.ctypes.data_as(_f32p))
+        return out
+
+    def sq8_quantize(self, rows, mins, scales):
+        """SQ8 codes u8[n, dim] of `rows` under a fitted (mins, scales); one row = SQ8Data::quantize_query (flat_mmap.rs:5741-5750)."""
+        d, pd = self._f(np.atleast_2d(rows))
+        n, dim = d.shape
+        m, pm = self._f(mins)
+        sc, psc = self._f(scales)
+        codes = np.zeros((n, dim), np.uint8)
+        self.lib.lo_sq8_quantize(pd, n, dim, pm, psc, codes.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return codes
 
     def flat_search_filtered(self, query, cands, k, metric, subset, n_threads=8):
         """FlatMmap::search_filtered on f32 rows, the reference's policy (subset order / chunk order)."""

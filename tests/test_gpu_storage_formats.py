@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from conftest import oracle_for_every_query
 from lynsedb_amd import storage as S
 
 pytestmark = pytest.mark.gpu
@@ -279,3 +280,178 @@ def test_f16_shard_on_the_certified_int8_pass(L, oracle, name, metric):
             e_ids, e_d = oracle.canonical_topk_f16(queries[qi], data, k, metric)
             assert np.array_equal(rows[qi].astype(np.uint32), e_ids), (name, nq, qi, rows[qi], e_ids)
             assert np.array_equal(dists[qi].view(np.uint32), e_d.view(np.uint32)), (name, nq, qi)
+
+
+# ------------------------------------------------------------------ FLAT-*-SQ8 at embedding widths, on every path of the two-pass mode
+SQ8_METRICS = [(O.IP, "ip"), (O.L2, "l2"), (O.COS, "cosine")]
+
+
+def _sq8_expect(oracle, queries, data, mins, scales, codes, k, metric):
+    return oracle_for_every_query(lambda qi: oracle.sq8_search(queries[qi], data, mins, scales, codes, k, metric), queries.shape[0])
+
+
+def _sq8_assert(got, want, tag, first=0):
+    """Every query, every returned slot: count, row ids, the 32 bits of each distance."""
+    rows, dists, counts = got
+    for qi in range(rows.shape[0]):
+        e_ids, e_d = want[first + qi]
+        c = int(counts[qi])
+        assert c == len(e_ids), (tag, qi, c, len(e_ids))
+        g_d = np.ascontiguousarray(dists[qi, :c], f32)
+        assert np.array_equal(g_d.view(np.uint32), e_d.view(np.uint32)), (tag, qi, g_d[:6], e_d[:6], rows[qi, :6], e_ids[:6])
+        assert np.array_equal(rows[qi, :c].astype(np.uint32), e_ids), (tag, qi, rows[qi, :8], e_ids[:8])
+
+
+def _sq8_params_equal(idx, mins, scales):
+    g_mins, g_scales = idx.sq8_params()
+    return np.array_equal(g_mins.view(np.uint32), mins.view(np.uint32)) and np.array_equal(g_scales.view(np.uint32), scales.view(np.uint32))
+
+
+@pytest.mark.parametrize("dim", [384, 768, 1024, 1536])
+def test_sq8_two_pass_parity_at_embedding_widths(L, oracle, dim):
+    """nslab = ceil(D / 128) = 3, 6, 8 and 12 slabs of the int8 MFMA scan over codes at pitch ld8; batches of 64 and 256 (the
+    k_rescore_pool grid of >= 64 queries) and of 300 (two chunks of the 256-query loop)."""
+    n = 12_000_000 // dim
+    rng = np.random.default_rng(400 + dim)
+    data = rng.standard_normal((n, dim)).astype(f32)
+    data[:, 3] = 1.5                    # constant dimension: scale 0, code 0
+    queries = (data[rng.integers(0, n, 300)] + 0.05 * rng.standard_normal((300, dim))).astype(f32)
+    queries[0] *= 3                     # outside the rows' range: codes clamp to 0 / 255
+    idx = L.FlatIndex(None, dim, 0)
+    idx.write(data)
+    mins, scales, codes = oracle.sq8_fit(data)
+    assert _sq8_params_equal(idx, mins, scales)
+    k = 10
+    for metric, name in SQ8_METRICS:
+        want = _sq8_expect(oracle, queries, data, mins, scales, codes, k, metric)
+        for nq in (64, 256, 300):
+            _sq8_assert(idx.search_sq8_batch_arrays(queries[:nq], k, name), want, (dim, name, nq))
+        _sq8_assert(idx.search_sq8_batch_arrays(queries[256:], k, name), want, (dim, name, "tail"), first=256)
+
+
+@pytest.mark.parametrize("dim", [130, 768])
+def test_sq8_pass_1_ranking_alone(L, oracle, dim, monkeypatch):
+    """LYNSE_HIP_SQ8_PASS1=1 (read per call): the search stops after pass 1 and returns the best k rows of the n_cand = 20 k (cosine
+    100 k) it kept, in (code score, row) order, with the integer score of the u8 codes as the distance — u32 dot for ip (descending),
+    u32 squared L2 for l2 and cosine, as f32 like `dist_fn(..) as f32` (sq8_two_pass_search).  Expected: int64 numpy over the
+    restatement's codes and the query coded by the restatement's rule (oracle.sq8_quantize = SQ8Data::quantize_query)."""
+    monkeypatch.setenv("LYNSE_HIP_SQ8_PASS1", "1")
+    n, nq, k = 12_000, 40, 200          # n_cand = 4000 (ip / l2), all 12,000 rows (cosine); n <= the candidate capacity: one pass
+    rng = np.random.default_rng(500 + dim)
+    data = rng.standard_normal((n, dim)).astype(f32)
+    queries = (data[rng.integers(0, n, nq)] + 0.05 * rng.standard_normal((nq, dim))).astype(f32)
+    queries[0] *= 50                    # far outside the fitted ranges: every code clamps to 0 / 255
+    queries[1] = -1e30
+    queries[2] = 1e30
+    idx = L.FlatIndex(None, dim, 0)
+    idx.write(data)
+    mins, scales, codes = oracle.sq8_fit(data)
+    assert _sq8_params_equal(idx, mins, scales)
+    qc = oracle.sq8_quantize(queries, mins, scales).astype(np.int64)
+    assert not qc[1].any() and np.all(qc[2] == 255) and np.isin(qc[0], [0, 255]).mean() > 0.9
+    c64 = codes.astype(np.int64)
+    dot = c64 @ qc.T                                                        # [n, nq], exact
+    l2 = (c64 * c64).sum(1)[:, None] + (qc * qc).sum(1)[None, :] - 2 * dot
+    assert l2.min() >= 0 and max(dot.max(), l2.max()) < 2 ** 32
+    for metric, name in SQ8_METRICS:
+        rows, dists, counts = idx.search_sq8_batch_arrays(queries, k, name)
+        for qi in range(nq):
+            s = (dot if metric == O.IP else l2)[:, qi].astype(f32)           # `as f32` of the u32 score
+            order = np.lexsort((np.arange(n), -s if metric == O.IP else s))[:k]
+            assert int(counts[qi]) == k
+            assert np.array_equal(dists[qi].view(np.uint32), s[order].view(np.uint32)), (name, qi, dists[qi, :6], s[order][:6])
+            assert np.array_equal(rows[qi].astype(np.int64), order), (name, qi, rows[qi, :8], order[:8])
+
+
+@pytest.mark.parametrize("dim", [96, 768])
+def test_sq8_incremental_codes_inside_the_fitted_ranges(L, oracle, dim):
+    """sq8_merge_new_rows: rows appended strictly inside every fitted range leave mins / scales where they are, only the new rows are
+    coded and the old codes are kept — in the two-pass mode those codes decide the answer.  Then one row outside the range: a refit."""
+    n0, n1, nq, k = (20_000, 2000, 40, 10) if dim == 96 else (6000, 1000, 40, 10)
+    rng = np.random.default_rng(600 + dim)
+    data0 = rng.standard_normal((n0, dim)).astype(f32)
+    lo, hi = data0.min(0), data0.max(0)
+    pad = (0.01 * (hi - lo)).astype(f32)
+    extra = np.clip(rng.standard_normal((n1, dim)).astype(f32), lo + pad, hi - pad).astype(f32)
+    assert np.all(extra > lo) and np.all(extra < hi)
+    queries = np.concatenate([extra[rng.integers(0, n1, nq // 2)], data0[rng.integers(0, n0, nq // 2)]])
+    queries = (queries + 0.02 * rng.standard_normal(queries.shape)).astype(f32)       # half of them next to the new rows
+    idx = L.FlatIndex(None, dim, 0)
+    idx.reserve(n0 + n1 + 1)            # no reallocation: the codes of the first build survive the appends
+    idx.write(data0)
+    mins0, scales0, codes0 = oracle.sq8_fit(data0)
+    for metric, name in SQ8_METRICS:
+        _sq8_assert(idx.search_sq8_batch_arrays(queries, k, name), _sq8_expect(oracle, queries, data0, mins0, scales0, codes0, k, metric), ("first", dim, name))
+    assert idx.coarse_state()["sq8_rows"] == n0
+    idx.write(extra)
+    both = np.concatenate([data0, extra])
+    mins, scales, codes = oracle.sq8_fit(both)
+    assert np.array_equal(mins, mins0) and np.array_equal(scales, scales0) and np.array_equal(codes[:n0], codes0)   # the case the incremental build is for
+    one_go = L.FlatIndex(None, dim, 0)
+    one_go.write(both)
+    for metric, name in SQ8_METRICS:
+        got = idx.search_sq8_batch_arrays(queries, k, name)
+        _sq8_assert(got, _sq8_expect(oracle, queries, both, mins, scales, codes, k, metric), ("appended", dim, name))
+        ref = one_go.search_sq8_batch_arrays(queries, k, name)
+        assert all(np.array_equal(a, b) for a, b in zip((got[0], got[1].view(np.uint32), got[2]), (ref[0], ref[1].view(np.uint32), ref[2]))), name
+    assert idx.coarse_state()["sq8_rows"] == n0 + n1 and _sq8_params_equal(idx, mins, scales)
+    outside = (hi * 2 + 1).astype(f32).reshape(1, dim)      # beyond every maximum: every scale moves, every row is coded again
+    idx.write(outside)
+    one_go.write(outside)
+    both = np.concatenate([both, outside])
+    mins, scales, codes = oracle.sq8_fit(both)
+    assert not np.array_equal(scales, scales0)
+    for metric, name in SQ8_METRICS:
+        got = idx.search_sq8_batch_arrays(queries, k, name)
+        _sq8_assert(got, _sq8_expect(oracle, queries, both, mins, scales, codes, k, metric), ("refit", dim, name))
+        ref = one_go.search_sq8_batch_arrays(queries, k, name)
+        assert all(np.array_equal(a, b) for a, b in zip((got[0], got[1].view(np.uint32), got[2]), (ref[0], ref[1].view(np.uint32), ref[2]))), name
+    assert idx.coarse_state()["sq8_rows"] == n0 + n1 + 1 and _sq8_params_equal(idx, mins, scales)
+
+
+@pytest.mark.parametrize("metric,name,k", [(O.IP, "ip", 300), (O.L2, "l2", 250), (O.COS, "cosine", 60)])
+def test_sq8_more_candidates_than_one_pass_holds_at_width(L, oracle, metric, name, k):
+    """search_sq8_large (row ranges, host merge, pass 2 as the subset-filtered exact search) at an embedding width, 40 queries."""
+    rng = np.random.default_rng(777 + metric)
+    n, dim, nq = 20_000, 768, 40
+    data = rng.standard_normal((n, dim)).astype(f32)
+    queries = (data[rng.integers(0, n, nq)] + 0.05 * rng.standard_normal((nq, dim))).astype(f32)
+    idx = L.FlatIndex(None, dim, 0)
+    idx.write(data)
+    mins, scales, codes = oracle.sq8_fit(data)
+    want = _sq8_expect(oracle, queries, data, mins, scales, codes, k, metric)
+    assert all(len(w[0]) == k for w in want)
+    _sq8_assert(idx.search_sq8_batch_arrays(queries, k, name), want, (name, k))
+
+
+@pytest.mark.parametrize("n,dim", [(5000, 32), (3000, 768)])
+def test_sq8_non_finite_rows_and_queries(L, oracle, n, dim):
+    """Non-finite values in the two-pass mode (include/lynse_hip.h, FLAT-SQ8): the fit ignores a NaN element (its code is 0) and a column
+    holding +-inf gets scale 0, so pass 1 is defined; pass 2 follows the non-finite rule of the FLAT searches (NaN = the worst value of
+    the metric, ties by row)."""
+    rng = np.random.default_rng(900 + dim)
+    nq, k = 8, 10
+    data = rng.standard_normal((n, dim)).astype(f32)
+    sp = rng.choice(n, 9, replace=False)
+    data[sp[0:3], 3] = np.nan
+    data[sp[3:5], 5] = np.inf
+    data[sp[5:7], 6] = -np.inf
+    data[sp[7], 1] = np.inf
+    data[sp[7], 2] = -np.inf
+    data[sp[8], 3] = np.nan
+    data[sp[8], 5] = np.inf
+    queries = (data[rng.integers(0, n, nq)] + 0.05 * rng.standard_normal((nq, dim))).astype(f32)
+    queries = np.where(np.isfinite(queries), queries, f32(0.25)).astype(f32)
+    queries[:4] = data[sp[[0, 3, 5, 7]]]                     # next to the special rows (finite where the row is not)
+    queries[:4] = np.where(np.isfinite(queries[:4]), queries[:4], f32(1.0))
+    queries[-1, 7] = np.nan                                  # every exact distance NaN: the pass-1 candidates at the worst value, by row
+    idx = L.FlatIndex(None, dim, 0)
+    idx.write(data)
+    mins, scales, codes = oracle.sq8_fit(data)
+    assert scales[5] == 0 and scales[6] == 0 and np.isfinite(mins[3]) and scales[3] > 0
+    assert _sq8_params_equal(idx, mins, scales)
+    for metric, name in SQ8_METRICS:
+        want = _sq8_expect(oracle, queries, data, mins, scales, codes, k, metric)
+        worst = -np.inf if metric == O.IP else np.inf
+        assert np.all(want[-1][1] == worst)
+        _sq8_assert(idx.search_sq8_batch_arrays(queries, k, name), want, (n, dim, name))
