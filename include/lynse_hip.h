@@ -232,6 +232,47 @@ int lynse_hip_flat_pq_stage_times(lynse_hip_flat *h, double *out3, int reset);
 int lynse_hip_pq_xoshiro_stream(const uint64_t *state4, uint64_t count, uint64_t *out);
 int lynse_hip_pq_splitmix_stream(uint64_t seed, uint64_t count, uint64_t *out);
 int lynse_hip_pq_init_indices(uint64_t seed, uint64_t n, uint32_t k, uint32_t *idx, uint32_t *chosen);
+/* FLAT-{IP,L2,COS,COSINE}-RABITQ (RaBitQIndex, src/storage/rabitq_mmap.rs; Collection, engine.rs:4476, :4552, :5504-5526): 1-bit
+ * codes of a randomised Hadamard rotation, scanned whole, and an exact rescore.  f32 handles and ip / l2 / cosine only; no
+ * training.  The rules:
+ *  1. padded_dim = next_power_of_two(dim), code_bytes = ceil(padded_dim / 8), ceil(padded_dim / 64) sign words.  Sign word w is
+ *     the w-th next_u64() of SmallRng::seed_from_u64(42) (xoshiro256++ seeded by SplitMix64; lynse_hip_rabitq_sign_words exposes
+ *     this host code for known-answer tests).  Bit i % 64 of word i / 64 set = "negate element i".
+ *  2. Encode a row (:101-132): norm = sqrt(sum x * x), summed in f32 in ascending index order from 0, correctly rounded sqrt.
+ *     The row is zero-padded to padded_dim, the signs applied, then the in-place unnormalised FWHT (:359-377): stages
+ *     h = 1, 2, 4, ...; each butterfly (x + y, x - y) with x the lower index.  Bit d % 8 of byte d / 8 is buf[d] >= 0.0
+ *     (-0.0 sets it, NaN does not); bits at d >= padded_dim stay 0.
+ *  3. Query (:202-213): the same pad, signs and FWHT; total_q = the f32 sum of all padded_dim rotated values in ascending order;
+ *     lut[b][v] = the f32 sum, from 0.0f, of q_rot[8 b + bit] over the set bits of v in ascending bit order.
+ *  4. Score (compute_binary_score, :560-585), no FMA contraction anywhere: sum_set = 0.0f + lut[0][c0] + lut[1][c1] + ... in
+ *     ascending byte order; ip_raw = 2 sum_set - total_q; IP maximises ip_raw * norm; L2 and cosine minimise
+ *     norm * norm - ((2 ip_raw) * norm) / (float)padded_dim.
+ *  5. Search: k' = min(k, n_rbq), N = min(k' * oversample, n_rbq) (the Collection passes 200, DEFAULT_OVERSAMPLE); the N best
+ *     scores form the pool, rescored with compute_distance_f32 on the original rows; the best k' come back with their exact
+ *     distances.  Both cuts use the canonical (score, row) key (the reference's per-thread heaps and sort_unstable leave ties
+ *     unpinned, as for PQ); NaN and +-inf order as in the FLAT searches, -0 == +0.  Output layout of lynse_hip_flat_search_f32.
+ *  6. The index covers the first n_rbq rows: rows appended after a build or a load stay outside it (n_rbq is unchanged).  Build
+ *     and load replace an earlier RaBitQ index; lynse_hip_flat_drop_rabitq removes it.  The exact searches are unchanged.
+ *  Refused with LYNSE_ERR_UNSUPPORTED: padded_dim * 4 bytes beyond the 160 KiB of LDS, an F16 shard, a packed-only handle, a
+ *  row-sharded handle and the binary metrics.  There is no ticket (submit / wait) or upsert form.  The search holds the handle's
+ *  lock exclusively (its scratch is per handle) and runs on context 0.
+ * lynse_hip_flat_load_rabitq takes what rabitq_index.bin holds: dim (must be the handle's: "Invalid RaBitQ dimensions"), the
+ * sign words (a word the file lacks negates nothing, as apply_signs has it), codes[n][code_bytes] and norms[n]; n <= the handle's
+ * rows.  lynse_hip_flat_rabitq_params returns dims = {dim, padded_dim, code_bytes} and n_rbq (all 0 without an index) and, for
+ * the pointers that are not NULL, the ceil(padded_dim / 64) sign words, codes[n_rbq][code_bytes] and norms[n_rbq] (the device
+ * keeps the codes in a tiled layout of its own; this is the file's).  lynse_hip_flat_rabitq_stage_times, with profiling on:
+ * out3[0] searches, out3[1] the scan stage (query transform, scan and the pool cut) and out3[2] the rescore (plus the host
+ * selection of a pool beyond 16,384), microseconds from HIP events; reset != 0 clears them. */
+int lynse_hip_flat_build_rabitq(lynse_hip_flat *h);
+int lynse_hip_flat_load_rabitq(lynse_hip_flat *h, uint32_t dim, const uint64_t *sign_words, uint32_t n_sign_words,
+                               const uint8_t *codes, const float *norms, uint64_t n);
+int lynse_hip_flat_rabitq_params(lynse_hip_flat *h, uint32_t *dims, uint64_t *n_rbq, uint64_t *sign_words, uint8_t *codes,
+                                 float *norms);
+int lynse_hip_flat_drop_rabitq(lynse_hip_flat *h);
+int lynse_hip_flat_search_rabitq_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric,
+                                     uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
+int lynse_hip_flat_rabitq_stage_times(lynse_hip_flat *h, double *out3, int reset);
+int lynse_hip_rabitq_sign_words(uint64_t seed, uint64_t count, uint64_t *out);
 /* Same with every buffer already resident in this handle's device memory; enqueued on `stream`
  * (a hipStream_t, NULL = the handle's own non-blocking stream) and synchronised before returning.
  * Device inputs of every *_device entry must be COMPLETE when the call is made (synchronise the

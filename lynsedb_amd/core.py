@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from pathlib import Path
 from typing import Iterable, Optional, Sequence
 
 import numpy as np
@@ -110,7 +111,7 @@ def parse_n_subspaces(index_type: str, dim: int) -> int:
 
 
 def flat_pq_mode(mode: str) -> bool:
-    """True for FLAT-{IP,L2,COS,COSINE}-PQ[<n>]; binary metrics and the other FLAT quantisers (RaBitQ, PolarVec) are refused."""
+    """True for FLAT-{IP,L2,COS,COSINE}-PQ[<n>]; binary metrics are refused (the other FLAT quantisers: flat_rabitq_mode)."""
     parts = str(mode).upper().split("-")
     if not parts or parts[0] != "FLAT":
         return False
@@ -118,6 +119,24 @@ def flat_pq_mode(mode: str) -> bool:
         return False
     if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
         raise NotImplementedError(f"{mode}: FLAT-*-PQ is defined for ip / l2 / cosine")
+    return True
+
+
+RABITQ_OVERSAMPLE = 200   # rabitq_mmap.rs DEFAULT_OVERSAMPLE
+RABITQ_INDEX_FILE = "rabitq_index.bin"
+
+
+def flat_rabitq_mode(mode: str) -> bool:
+    """True for FLAT-{IP,L2,COS,COSINE}-RABITQ; binary metrics are refused, and so is the remaining FLAT quantiser (PolarVec)."""
+    parts = str(mode).upper().split("-")
+    if not parts or parts[0] != "FLAT":
+        return False
+    if "POLARVEC" in parts[1:]:
+        raise NotImplementedError("PolarVec flat modes are outside this path (SURVEY.md §2)")
+    if "RABITQ" not in parts[1:]:
+        return False
+    if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
+        raise NotImplementedError(f"{mode}: FLAT-*-RABITQ is defined for ip / l2 / cosine")
     return True
 
 
@@ -407,6 +426,59 @@ class FlatIndex:
         """With profiling on: PQ searches timed and the summed microseconds of the scan stage and of the rescore."""
         out = np.zeros(3, np.float64)
         check(lib.lynse_hip_flat_pq_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+
+    # -- FLAT-*-RABITQ (RaBitQIndex, src/storage/rabitq_mmap.rs; include/lynse_hip.h states the contract) ----------------------
+    def build_rabitq(self) -> None:
+        """Encode the rows held now into 1-bit codes and norms (no training; rows appended later stay outside the index)."""
+        check(lib.lynse_hip_flat_build_rabitq(self._h))
+
+    def load_rabitq(self, sign_words, codes, norms) -> None:
+        """Install an index as rabitq_index.bin holds it: u64 sign words, codes u8 [n][code_bytes], norms f32 [n] for the first n rows."""
+        sw = np.ascontiguousarray(sign_words, dtype=np.uint64).reshape(-1)
+        cd = np.ascontiguousarray(codes, dtype=np.uint8)
+        nm = np.ascontiguousarray(norms, dtype=np.float32).reshape(-1)
+        padded = 1 << max(self._dim - 1, 0).bit_length()
+        if cd.ndim != 2 or cd.shape[1] != (padded + 7) // 8 or nm.shape[0] != cd.shape[0]:
+            raise ValueError("codes must be [n][ceil(next_pow2(dim) / 8)] and norms [n]")
+        check(lib.lynse_hip_flat_load_rabitq(self._h, self._dim, _ptr(sw), sw.shape[0], _ptr(cd), _ptr(nm), cd.shape[0]))
+
+    def drop_rabitq(self) -> None:
+        check(lib.lynse_hip_flat_drop_rabitq(self._h))
+
+    def rabitq_params(self, arrays: bool = True) -> dict:
+        """{"dim", "padded_dim", "code_bytes", "n"} and, with `arrays`, "sign_words" u64, "codes" u8 [n][code_bytes] and "norms"
+        f32 [n]; padded_dim == 0 without an index."""
+        dims = np.zeros(3, np.uint32)
+        n = C.c_uint64(0)
+        check(lib.lynse_hip_flat_rabitq_params(self._h, _ptr(dims), C.byref(n), None, None, None))
+        dim, padded, cb = (int(x) for x in dims)
+        out = {"dim": dim, "padded_dim": padded, "code_bytes": cb, "n": int(n.value)}
+        if arrays and padded:
+            sw = np.empty((padded + 63) // 64, np.uint64)
+            cd = np.empty((int(n.value), cb), np.uint8)
+            nm = np.empty(int(n.value), np.float32)
+            check(lib.lynse_hip_flat_rabitq_params(self._h, _ptr(dims), C.byref(n), _ptr(sw), _ptr(cd), _ptr(nm)))
+            out["sign_words"], out["codes"], out["norms"] = sw, cd, nm
+        return out
+
+    def search_rabitq_batch_arrays(self, queries, k: int, metric, oversample: int = RABITQ_OVERSAMPLE):
+        """Scan of the 1-bit codes, the N = min(k' * oversample, n_rbq) best by (score, row), exact rescore of those rows."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_flat_search_rabitq_f32(self._h, _ptr(q), nq, k, m, int(oversample), _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+    def rabitq_stage_times(self, reset: bool = True) -> dict:
+        """With profiling on: RaBitQ searches timed and the summed microseconds of the scan stage and of the rescore."""
+        out = np.zeros(3, np.float64)
+        check(lib.lynse_hip_flat_rabitq_stage_times(self._h, _ptr(out), 1 if reset else 0))
         return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
 
     def search_filtered_batch_arrays(self, queries, k: int, metric, subset_rows):
@@ -1090,9 +1162,10 @@ class Collection:
     The reference resolves `where_expr` to a row BitSet through its field store (out of scope); the
     precomputed filter itself is in scope and is passed here as `subset=` (a `BitSet` or an array of row indices)."""
 
-    def __init__(self, name: str, dim: int, device: Optional[int] = None):
+    def __init__(self, name: str, dim: int, device: Optional[int] = None, path=None):
         self._name, self._dim = name, int(dim)
         self._device = device
+        self._path = None if path is None else Path(path)   # where the auxiliary index file (rabitq_index.bin) persists; None = nowhere
         self._flat = FlatIndex(None, dim, device)
         self._id_arrays: list = []     # row -> user id (engine.rs:3071-3073)
         self._index_mode = "FLAT-IP"   # resolve_metric default IP (engine.rs:5529-5534)
@@ -1106,6 +1179,7 @@ class Collection:
         self._pending_rows = 0
         self._tombstone: set = set()    # user ids (engine.rs:3182-3194)
         self._pq = False                # FLAT-*-PQ built over the rows flushed at build time (FlatIndex.build_pq)
+        self._rabitq = False            # FLAT-*-RABITQ, likewise (FlatIndex.build_rabitq); at most one of the two exists
 
     def name(self) -> str:
         return self._name
@@ -1177,20 +1251,21 @@ class Collection:
         params = dict(params or {})
         self._flush_pending()
         if mode.startswith("FLAT"):
-            if any(t in mode.split("-") for t in ("RABITQ", "POLARVEC")):
-                raise NotImplementedError("RaBitQ / PolarVec flat modes are outside this path (SURVEY.md §2)")
+            rabitq = flat_rabitq_mode(mode)   # (refuses PolarVec)
             pq = flat_pq_mode(mode)
             self._ivf = None
-            self._flat.drop_pq()   # building any mode drops an earlier PQ index (engine.rs:4559-4600)
-            self._pq = False
+            self._drop_aux()   # building any mode drops an earlier PQ / RaBitQ index (engine.rs:4476, :4552, :4559-4600)
             if pq and len(self._flat) > 0:   # over 0 rows nothing is built and searches stay exact
                 self._flat.build_pq(parse_n_subspaces(mode, self._dim), int(params.get("n_clusters", 256)))
                 self._pq = True
+            elif rabitq and len(self._flat) > 0:
+                self._flat.build_rabitq()
+                self._rabitq = True
+                self._save_rabitq()
         elif mode.startswith("SPANN"):
             metric, sq8 = spann_mode_of(mode)
             opts = spann_build_options(params)
-            self._flat.drop_pq()
-            self._pq = False
+            self._drop_aux()
             if len(self._flat) == 0:   # graph / partition indexes need data (engine.rs:4606-4612)
                 raise ValueError("Empty database")
             self._ivf_params = {"n_clusters": opts["n_clusters"], "spann": (opts["replica_count"], sq8)}
@@ -1199,8 +1274,7 @@ class Collection:
             self._build_ivf()
         elif mode.startswith("IVF"):
             quantizer = ivf_quantizer_of(mode)
-            self._flat.drop_pq()
-            self._pq = False
+            self._drop_aux()
             self._ivf_params = {"n_clusters": int(params.get("n_clusters", 256)), "quantizer": quantizer}
             self._ivf_nprobe = int(params.get("nprobe", 32))
             self._index_mode, self._metric = mode, metric
@@ -1208,6 +1282,45 @@ class Collection:
         else:
             raise NotImplementedError(f"index type {index_type} is outside the FLAT/IVF hot path")
         self._index_mode, self._metric = mode, metric
+
+    def _drop_aux(self) -> None:
+        """At most one auxiliary quantised index exists: whatever is built next, the earlier one and its file go."""
+        self._flat.drop_pq()
+        self._flat.drop_rabitq()
+        self._pq = self._rabitq = False
+        if self._path is not None:
+            (self._path / RABITQ_INDEX_FILE).unlink(missing_ok=True)
+
+    def _save_rabitq(self) -> None:
+        if self._path is None:
+            return
+        from .storage import RabitqIndexFile, save_rabitq_index
+
+        p = self._flat.rabitq_params()
+        save_rabitq_index(self._path / RABITQ_INDEX_FILE, RabitqIndexFile(p["dim"], p["padded_dim"], p["sign_words"], p["codes"], p["norms"]))
+
+    def try_load_rabitq(self, index_type: str) -> bool:
+        """try_load_pq_rabitq's RaBitQ half for a reopened collection whose rows are back in place: `index_type` is the stored
+        mode; rabitq_index.bin under the collection's path is installed when the mode names RaBitQ, the file is there, its dim is
+        the collection's and it covers no more rows than are flushed.  False (and exact search) otherwise."""
+        from .storage import load_rabitq_index
+
+        mode = str(index_type).upper()
+        if self._path is None or not flat_rabitq_mode(mode):
+            return False
+        f = self._path / RABITQ_INDEX_FILE
+        if not f.exists():
+            return False
+        idx = load_rabitq_index(f)
+        if idx.dim != self._dim or idx.n_vectors == 0 or idx.n_vectors > len(self._flat):
+            return False
+        self._flat.drop_pq()
+        self._pq = False
+        self._flat.load_rabitq(idx.sign_words, idx.codes, idx.norms)
+        self._ivf = None
+        self._rabitq = True
+        self._index_mode, self._metric = mode, metric_from_index_mode(mode)
+        return True
 
     def _build_ivf(self) -> None:
         n = len(self._flat)
@@ -1284,6 +1397,8 @@ class Collection:
             return self._flat.search_filtered_batch_arrays(q, search_k, self._metric, subset_rows)
         if self._pq:   # search_auxiliary_quantized (engine.rs:5504-5526): rows committed after the build are not in the index
             return self._flat.search_pq_batch_arrays(q, search_k, self._metric, PQ_OVERSAMPLE)
+        if self._rabitq:
+            return self._flat.search_rabitq_batch_arrays(q, search_k, self._metric, RABITQ_OVERSAMPLE)
         if self._use_sq8() and self._metric in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
             return self._flat.search_sq8_batch_arrays(q, search_k, self._metric)
         return self._flat.search_batch_arrays(q, search_k, self._metric)
@@ -1316,12 +1431,16 @@ class Collection:
         target = self._ivf if self._ivf is not None else self._flat
         sq8 = self._ivf is not None and self._ivf.is_sq8
         pq = self._ivf is None and self._pq and subset is None
+        rabitq = self._ivf is None and self._rabitq and subset is None
         target.profile_enable(True)
         target.profile_get(reset=True)
         if sq8:
             self._ivf.sq8_stage_times(reset=True)
         if pq:
             self._flat.pq_stage_times(reset=True)
+        if rabitq:
+            self._flat.rabitq_stage_times(reset=True)
+        stage_us = None
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
@@ -1331,18 +1450,23 @@ class Collection:
             rerank_us = int(self._ivf.sq8_stage_times(reset=True)["rerank_us"]) if sq8 else 0
             if pq:   # FLAT-*-PQ: the exact rescore of the ADC pool
                 rerank_us = int(self._flat.pq_stage_times(reset=True)["rescore_us"])
+            if rabitq:   # FLAT-*-RABITQ: both stages of the two-pass search
+                t = self._flat.rabitq_stage_times(reset=True)
+                rerank_us, stage_us = int(t["rescore_us"]), {"scan_us": float(t["scan_us"]), "rescore_us": float(t["rescore_us"])}
             target.profile_enable(False)
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
                    "index_path": "ann_index" if self._ivf is not None else ("flat_mmap_filtered" if subset is not None else
-                                                                            ("pq_two_pass" if pq else "flat_mmap")),
+                                                                            ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else "flat_mmap"))),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
                    "filter_us": filter_us, "search_us": search_us, "rerank_us": rerank_us, "total_us": int((time.perf_counter() - started) * 1e6),
                    "device": {"pipeline_us": float(dev["total_us"]), "scan_us": float(dev["scan_us"]), "scan_launches": int(dev["scan_launches"]),
                               "scan_rows": int(dev["scan_rows"]), "scan_bytes": int(dev["scan_bytes"]), "rescored_candidates": int(dev["pool_entries"]),
                               "fallback_queries": int(dev["fallback_queries"]), "plan": int(dev["last_plan"])}}
+        if stage_us is not None:
+            profile["device"]["rabitq_stages"] = stage_us
         return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
                 "profile": profile}
 

@@ -4632,6 +4632,31 @@ struct PoolRerankArgs {
     unsigned long long* pool_total;   // += the pool entries rescored (the profile's pool_entries), may be NULL
 };
 
+// The selection that ends the rerank of query q: keys[0 .. P) hold the scored pool; they are sorted by the canonical key in LDS
+// (bitonic over p2 >= P keys) and the best min(k, P) written in the layout of lynse_hip_ivf_search_f32.
+template <int NT>
+__device__ __forceinline__ void pool_select_tail(uint64_t* keys, uint32_t P, const PoolRerankArgs& a, uint32_t q, uint32_t tid, bool asc) {
+    for (uint32_t i = P + tid; i < a.p2; i += NT) keys[i] = KEY_SENTINEL;
+    __syncthreads();
+    for (uint32_t size = 2; size <= a.p2; size <<= 1)
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t t = tid; t < a.p2 / 2; t += NT) {
+                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const uint64_t x = keys[lo], y = keys[hi];
+                if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
+            }
+            __syncthreads();
+        }
+    const uint32_t cnt = P < a.k ? P : a.k;
+    for (uint32_t i = tid; i < a.out_k; i += NT) {
+        const bool in = i < cnt;
+        a.out_rows[(size_t)q * a.out_k + i] = in ? (uint64_t)key_row(keys[i]) : ~0ull;
+        a.out_dists[(size_t)q * a.out_k + i] = in ? key_score(keys[i], asc) : (asc ? LY_INF : -LY_INF);
+    }
+    if (tid == 0) a.out_counts[q] = cnt;
+}
+
 template <bool SELECT>
 __global__ void __launch_bounds__(256) k_pool_rerank(PoolRerankArgs a) {
     extern __shared__ uint64_t sm_rr[];
@@ -4644,9 +4669,9 @@ __global__ void __launch_bounds__(256) k_pool_rerank(PoolRerankArgs a) {
     __syncthreads();
     const uint32_t P = a.pool_cnt[q] < a.pool_ld ? a.pool_cnt[q] : a.pool_ld;
     const uint64_t* pr = a.pool_rows + (size_t)q * a.pool_ld;
-    if (tid == 0 && a.pool_total) atomicAdd(a.pool_total, (unsigned long long)P);
+    if (tid == 0 && blockIdx.y == 0 && a.pool_total) atomicAdd(a.pool_total, (unsigned long long)P);
     const uint32_t bound = (P + 31u) / 32u * 32u;   // whole waves run the same trip count (exact_score shuffles inside its 8 lanes)
-    for (uint32_t i = tid >> 3; i < bound; i += 32) {
+    for (uint32_t i = (tid >> 3) + 32 * blockIdx.y; i < bound; i += 32 * gridDim.y) {   // (gridDim.y > 1: !SELECT, split scoring)
         if (P == 0) break;
         const uint64_t r64 = pr[i < P ? i : P - 1];
         const uint32_t row = r64 < a.n ? (uint32_t)r64 : 0u;   // (a pool entry is an original row id < n)
@@ -4657,27 +4682,18 @@ __global__ void __launch_bounds__(256) k_pool_rerank(PoolRerankArgs a) {
             else a.keys_out[(size_t)q * a.pool_ld + i] = make_key(s, row, asc);
         }
     }
-    if constexpr (SELECT) {
-        for (uint32_t i = P + tid; i < a.p2; i += 256) keys[i] = KEY_SENTINEL;
-        __syncthreads();
-        for (uint32_t size = 2; size <= a.p2; size <<= 1)
-            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                for (uint32_t t = tid; t < a.p2 / 2; t += 256) {
-                    const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                    const bool up = (lo & size) == 0;
-                    const uint64_t x = keys[lo], y = keys[hi];
-                    if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
-                }
-                __syncthreads();
-            }
-        const uint32_t cnt = P < a.k ? P : a.k;
-        for (uint32_t i = tid; i < a.out_k; i += 256) {
-            const bool in = i < cnt;
-            a.out_rows[(size_t)q * a.out_k + i] = in ? (uint64_t)key_row(keys[i]) : ~0ull;
-            a.out_dists[(size_t)q * a.out_k + i] = in ? key_score(keys[i], asc) : (asc ? LY_INF : -LY_INF);
-        }
-        if (tid == 0) a.out_counts[q] = cnt;
-    }
+    if constexpr (SELECT) pool_select_tail<256>(keys, P, a, q, tid, asc);
+}
+
+// The selection alone, for a pool that k_pool_rerank<false> scored with several workgroups per query (a few queries, each with a
+// pool of thousands of rows: one workgroup per query would gather them at the latency of one CU): keys_out[q] -> LDS -> the tail.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_pool_select(PoolRerankArgs a) {
+    extern __shared__ uint64_t sm_rr[];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t P = a.pool_cnt[q] < a.pool_ld ? a.pool_cnt[q] : a.pool_ld;
+    for (uint32_t i = tid; i < P; i += NT) sm_rr[i] = a.keys_out[(size_t)q * a.pool_ld + i];
+    pool_select_tail<NT>(sm_rr, P, a, q, tid, metric_ascending(a.metric));
 }
 
 }  // namespace lynse

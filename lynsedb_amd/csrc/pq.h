@@ -339,9 +339,15 @@ __global__ void __launch_bounds__(256) k_pq_hist(const uint32_t* __restrict__ S,
     __syncthreads();
     const uint64_t r0 = (uint64_t)blockIdx.x * rows_per_block, r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
     const uint32_t* Sq = S + (size_t)q * n;
-    for (uint64_t r = r0 + tid; r < r1; r += 256) {
-        const uint64_t key = ((uint64_t)Sq[r] << 32) | r;
-        if (pq_sel_match(key, s)) atomicAdd(&h[(uint32_t)(key >> lo) & ((1u << w) - 1u)], 1u);
+    for (uint64_t rb = r0 + tid; rb < r1; rb += 256 * 8) {   // 8 independent loads in flight per thread, then their updates
+        uint32_t v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = rb + 256 * j < r1 ? Sq[rb + 256 * j] : 0u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint64_t r = rb + 256 * j, key = ((uint64_t)v[j] << 32) | r;
+            if (r < r1 && pq_sel_match(key, s)) atomicAdd(&h[(uint32_t)(key >> lo) & ((1u << w) - 1u)], 1u);
+        }
     }
     __syncthreads();
     for (uint32_t i = tid; i < (1u << w); i += 256)
@@ -349,35 +355,49 @@ __global__ void __launch_bounds__(256) k_pq_hist(const uint32_t* __restrict__ S,
 }
 
 __global__ void __launch_bounds__(256) k_pq_find(PqSel* __restrict__ sel, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t part[256];
+    __shared__ uint32_t part[256], own[2];
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     PqSel s = sel[q];
     if (s.done) return;
     const uint32_t lo = s.hi > PQ_DIGIT ? s.hi - PQ_DIGIT : 0u, w = s.hi - lo, nb = 1u << w;
     uint32_t* hq = hist + (size_t)q * PQ_BINS;
-    const uint32_t per = (nb + 255) / 256;   // bins per thread, contiguous
-    uint32_t t = 0;
-    for (uint32_t b = tid * per; b < (tid + 1) * per && b < nb; ++b) t += hq[b];
+    const uint32_t per = (nb + 255) / 256;   // bins per thread, contiguous (at most PQ_BINS / 256 = 8: read once, kept in registers)
+    uint32_t t = 0, mine[PQ_BINS / 256];
+#pragma unroll
+    for (uint32_t j = 0; j < PQ_BINS / 256; ++j) {
+        const uint32_t b = tid * per + j;
+        mine[j] = (j < per && b < nb) ? hq[b] : 0u;
+        t += mine[j];
+    }
     part[tid] = t;
     __syncthreads();
-    if (tid == 0) {
-        uint32_t cum = 0, owner = 0;
-        for (; owner < 256; ++owner) {
-            if (cum + part[owner] >= s.need) break;
-            cum += part[owner];
-        }
-        part[0] = owner;   // (read back below)
-        part[1] = cum;
+    // inclusive prefix sums of the 256 partial counts (one thread walking them in LDS took longer than the histogram pass);
+    // the owner is the first thread whose bins reach rank `need`: before < need <= before + t, true for exactly one thread
+    for (uint32_t d = 1; d < 256; d <<= 1) {
+        const uint32_t add = tid >= d ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    const uint32_t before = part[tid] - t;
+    if (tid == 0) own[0] = 256u;   // no owner (never: need <= the keys that match)
+    __syncthreads();
+    if (before < s.need && s.need <= before + t) {
+        own[0] = tid;
+        own[1] = before;
     }
     __syncthreads();
-    const uint32_t owner = part[0];
+    const uint32_t owner = own[0];
     if (tid == owner) {
-        uint32_t cum = part[1], b = tid * per;
-        for (; b + 1 < (tid + 1) * per && b + 1 < nb; ++b) {
-            if (cum + hq[b] >= s.need) break;
-            cum += hq[b];
+        uint32_t cum = own[1], b = tid * per, in_b = mine[0];
+#pragma unroll
+        for (uint32_t j = 0; j + 1 < PQ_BINS / 256; ++j) {   // the first bin of mine whose running count reaches `need`, else the last
+            if (b == tid * per + j && b + 1 < (tid + 1) * per && b + 1 < nb && cum + mine[j] < s.need) {
+                cum += mine[j];
+                ++b;
+                in_b = mine[j + 1];
+            }
         }
-        const uint32_t in_b = hq[b];
         s.need -= cum;
         s.prefix = (s.hi >= 64 ? 0ull : (s.prefix << w)) | b;
         s.hi = lo;
@@ -388,18 +408,36 @@ __global__ void __launch_bounds__(256) k_pq_find(PqSel* __restrict__ sel, uint32
     for (uint32_t b = tid; b < nb; b += 256) hq[b] = 0;
 }
 
-// every row whose key is <= the selected one (the first s.hi bits <= prefix) goes to the pool, in no particular order
+// every row whose key is <= the selected one (the first s.hi bits <= prefix) goes to the pool, in no particular order.  A block
+// collects the hits of a tile of PQ_EMIT_TILE rows in LDS and reserves their pool slots with ONE atomic on the query's counter (a
+// pool of thousands of rows, one returning atomic each on the same address, cost more than reading the scores).
+constexpr uint32_t PQ_EMIT_TILE = 2048;   // 256 threads x 8 independent loads
+
 __global__ void __launch_bounds__(256) k_pq_emit(const uint32_t* __restrict__ S, uint64_t n, PqSel* __restrict__ sel, uint32_t pool_ld,
                                                  uint64_t* __restrict__ pool_rows, uint32_t* __restrict__ pool_cnt) {
-    const uint32_t q = blockIdx.y;
+    __shared__ uint32_t hit[PQ_EMIT_TILE];
+    __shared__ uint32_t n_hit, base;
+    const uint32_t q = blockIdx.y, tid = threadIdx.x;
     const PqSel s = sel[q];
     const uint32_t* Sq = S + (size_t)q * n;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (uint64_t)gridDim.x * 256) {
-        const uint64_t key = ((uint64_t)Sq[r] << 32) | r;
-        if ((key >> s.hi) <= s.prefix) {
-            const uint32_t slot = atomicAdd(&pool_cnt[q], 1u);
-            if (slot < pool_ld) pool_rows[(size_t)q * pool_ld + slot] = r;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * PQ_EMIT_TILE; t0 < n; t0 += (uint64_t)gridDim.x * PQ_EMIT_TILE) {
+        if (tid == 0) n_hit = 0;
+        __syncthreads();
+        const uint64_t t1 = t0 + PQ_EMIT_TILE < n ? t0 + PQ_EMIT_TILE : n;
+        uint32_t v[PQ_EMIT_TILE / 256];
+#pragma unroll
+        for (uint32_t j = 0; j < PQ_EMIT_TILE / 256; ++j) v[j] = t0 + 256 * j + tid < t1 ? Sq[t0 + 256 * j + tid] : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < PQ_EMIT_TILE / 256; ++j) {
+            const uint64_t r = t0 + 256 * j + tid, key = ((uint64_t)v[j] << 32) | r;
+            if (r < t1 && (key >> s.hi) <= s.prefix) hit[atomicAdd(&n_hit, 1u)] = (uint32_t)(r - t0);
         }
+        __syncthreads();
+        if (tid == 0 && n_hit) base = atomicAdd(&pool_cnt[q], n_hit);
+        __syncthreads();
+        for (uint32_t i = tid; i < n_hit; i += 256)
+            if (base + i < pool_ld) pool_rows[(size_t)q * pool_ld + base + i] = t0 + hit[i];
+        __syncthreads();
     }
 }
 

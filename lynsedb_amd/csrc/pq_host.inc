@@ -11,10 +11,7 @@ struct PqState {
     uint8_t* codes = nullptr;     // [n][M] u8 codes
     float *d_q = nullptr, *d_lut = nullptr;
     size_t q_cap = 0, lut_cap = 0;
-    uint32_t *d_S = nullptr, *d_hist = nullptr;
-    size_t S_cap = 0, hist_cap = 0;
-    PqSel* d_sel = nullptr;
-    size_t sel_cap = 0;
+    ScoreCut cut;                 // the [chunk][n] score matrix and its radix selection (rerank_host.inc)
     PoolRerank rr;                // the pool's rows and counts, the rescore's buffers and timing events
     double searches = 0.0, scan_us = 0.0, rescore_us = 0.0;
 
@@ -28,8 +25,9 @@ struct PqState {
     }
     ~PqState() {
         free_index();
-        for (void* p : {(void*)d_q, (void*)d_lut, (void*)d_S, (void*)d_hist, (void*)d_sel})
+        for (void* p : {(void*)d_q, (void*)d_lut})
             if (p) (void)hipFree(p);
+        cut.release();
         rr.release();
     }
 };
@@ -338,19 +336,13 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
     const uint32_t N = (uint32_t)std::min<uint64_t>((uint64_t)kk * oversample, n);
     if (N == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
     const bool asc = metric_ascending(metric);
-    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (uint64_t)QCHUNK, (512ull << 20) / (n * 4), (256ull << 20) / ((uint64_t)N * 8)}));
+    const uint64_t qc = ScoreCut::chunk(nq, n, N);
     PoolRerank::Search rr(p.rr);
     LY_TRY(rr.begin(h->rows, n, h->ld, D, metric, N, kk, k, qc, false, h->profiling.load(), "PQ rescore"));
     LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
     LY_TRY(ivf_grow(&p.d_lut, &p.lut_cap, (size_t)qc * p.M * p.K));
-    LY_TRY(ivf_grow(&p.d_S, &p.S_cap, (size_t)qc * n));
-    LY_TRY(ivf_grow(&p.d_sel, &p.sel_cap, (size_t)qc));
-    if (p.hist_cap < (size_t)qc * PQ_BINS) {
-        LY_TRY(ivf_grow(&p.d_hist, &p.hist_cap, (size_t)qc * PQ_BINS));
-        LY_TRY(memset_done(p.d_hist, 0, p.hist_cap * 4));   // k_pq_find clears what it read: zero between searches
-    }
+    LY_TRY(p.cut.grow(qc, n));
     hipStream_t st = cur(h).stream;
-    std::vector<PqSel> sel0;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
         LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
@@ -362,33 +354,14 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
         // the ADC scan: QB = 4 queries share a code load when the batch has them; tables in <= 64 KiB of LDS
         const int qb = nqc >= 4 ? 4 : 1;
         const uint32_t mc = std::max<uint32_t>(1, std::min<uint32_t>(p.M, 16384u / ((uint32_t)qb * p.K)));
-        PqAdcArgs aa{p.codes, n, p.M, p.K, mc, p.d_lut, nqc, asc ? 1 : 0, p.d_S};
+        PqAdcArgs aa{p.codes, n, p.M, p.K, mc, p.d_lut, nqc, asc ? 1 : 0, p.cut.d_S};
         const dim3 agrid((uint32_t)((n + PQ_NT * PQ_R - 1) / (PQ_NT * PQ_R)), (nqc + qb - 1) / qb);
         const size_t alds = (size_t)qb * mc * p.K * 4;
         if (qb == 4) hipLaunchKernelGGL(k_pq_adc<4>, agrid, dim3(PQ_NT), alds, st, aa);
         else hipLaunchKernelGGL(k_pq_adc<1>, agrid, dim3(PQ_NT), alds, st, aa);
         LY_HIP(hipGetLastError());
         // the N best (score, row) keys -> pool rows
-        if (N < n) {
-            sel0.assign(nqc, PqSel{0ull, 64u, N, 0u, 0u});
-            LY_HIP(hipMemcpyAsync(p.d_sel, sel0.data(), (size_t)nqc * sizeof(PqSel), hipMemcpyHostToDevice, st));
-            const uint32_t rpb = 8192;
-            const dim3 hgrid((uint32_t)((n + rpb - 1) / rpb), nqc);
-            for (uint32_t pass = 0; pass < 6; ++pass) {
-                hipLaunchKernelGGL(k_pq_hist, hgrid, dim3(256), 0, st, p.d_S, n, p.d_sel, p.d_hist, rpb);
-                LY_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_pq_find, dim3(nqc), dim3(256), 0, st, p.d_sel, p.d_hist);
-                LY_HIP(hipGetLastError());
-            }
-            LY_HIP(hipMemsetAsync(p.rr.d_pcnt, 0, (size_t)nqc * 4, st));
-            const uint32_t eblocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 1024));
-            hipLaunchKernelGGL(k_pq_emit, dim3(eblocks, nqc), dim3(256), 0, st, p.d_S, n, p.d_sel, N, p.rr.d_prow, p.rr.d_pcnt);
-            LY_HIP(hipGetLastError());
-        } else {
-            const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)nqc * n + 255) / 256, (uint64_t)h->num_cu * 32));
-            hipLaunchKernelGGL(k_pq_pool_all, dim3(blocks), dim3(256), 0, st, n, nqc, N, p.rr.d_prow, p.rr.d_pcnt);
-            LY_HIP(hipGetLastError());
-        }
+        LY_TRY(p.cut.run(nqc, n, N, p.rr, h->num_cu, st));
         LY_TRY(rr.run(p.d_q, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, nullptr, st));
     }
     if (rr.timed) { p.searches += 1; p.scan_us += rr.pool_us; p.rescore_us += rr.rerank_us; }

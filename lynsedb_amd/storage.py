@@ -340,3 +340,82 @@ def load_pq_index(path) -> PqIndexFile:
     if codes.size and int(codes.max()) >= k:
         raise IOError("PQ index contains an out-of-range code")
     return PqIndexFile(m, k, ss, dim, cb, codes)
+
+
+# ---- rabitq_index.bin (RaBitQIndex::save / load, src/storage/rabitq_mmap.rs:236-330) ------------------------------------------
+RABITQ_MAGIC = 0x5242_5451   # "RBTQ"
+RABITQ_VERSION = 2
+
+
+def next_power_of_two(n: int) -> int:
+    return 1 << max(int(n) - 1, 0).bit_length()
+
+
+@dataclass
+class RabitqIndexFile:
+    dim: int
+    padded_dim: int
+    sign_words: np.ndarray   # u64 [n_sign_words]
+    codes: np.ndarray        # u8 [n][ceil(padded_dim / 8)]
+    norms: np.ndarray        # f32 [n]
+
+    @property
+    def n_vectors(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def code_bytes(self) -> int:
+        return (self.padded_dim + 7) // 8
+
+
+def save_rabitq_index(path, idx: RabitqIndexFile) -> None:
+    """Version 2, little endian: u32 magic, version, dim, padded_dim; u64 n; u32 n_sign_words; the u64 sign words; the u8 codes
+    [n][code_bytes]; the f32 norms [n]."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    sw = np.ascontiguousarray(idx.sign_words, dtype="<u8").reshape(-1)
+    codes = np.ascontiguousarray(idx.codes, dtype=np.uint8).reshape(idx.n_vectors, idx.code_bytes)
+    norms = np.ascontiguousarray(idx.norms, dtype="<f4").reshape(-1)
+    if norms.shape[0] != idx.n_vectors:
+        raise ValueError("norms must hold one value per code row")
+    header = np.array([RABITQ_MAGIC, RABITQ_VERSION, idx.dim, idx.padded_dim], "<u4").tobytes()
+    header += np.array([idx.n_vectors], "<u8").tobytes() + np.array([sw.shape[0]], "<u4").tobytes()
+    with open(path, "wb") as f:
+        f.write(header)
+        f.write(sw.tobytes())
+        f.write(codes.tobytes())
+        f.write(norms.tobytes())
+
+
+def load_rabitq_index(path) -> RabitqIndexFile:
+    """RaBitQIndex::load with the reference's checks, in its order, and its messages (IOError = its io::Error).  Versions 1 and 2
+    are read alike: version 1 wrote floor(padded_dim / 8) code bytes, which differs only below 8, where it is refused."""
+    raw = Path(path).read_bytes()
+
+    def take(off, count, fmt):
+        size = count * np.dtype(fmt).itemsize
+        if len(raw) < off + size:
+            raise IOError("failed to fill whole buffer")
+        return np.frombuffer(raw, fmt, count, off), off + size
+
+    v, off = take(0, 1, "<u4")
+    if int(v[0]) != RABITQ_MAGIC:
+        raise IOError("Invalid RaBitQ magic bytes")
+    v, off = take(off, 1, "<u4")
+    version = int(v[0])
+    if not (1 <= version <= RABITQ_VERSION):
+        raise IOError(f"Unsupported RaBitQ version: {version}")
+    v, off = take(off, 2, "<u4")
+    dim, padded = int(v[0]), int(v[1])
+    v, off = take(off, 1, "<u8")
+    n = int(v[0])
+    if dim == 0 or padded != next_power_of_two(dim):
+        raise IOError("Invalid RaBitQ dimensions")
+    if version == 1 and padded < 8:
+        raise IOError("RaBitQ v1 index is invalid for dimensions below 8")
+    cb = (padded + 7) // 8
+    v, off = take(off, 1, "<u4")
+    sw, off = take(off, int(v[0]), "<u8")
+    codes, off = take(off, n * cb, np.uint8)
+    norms, off = take(off, n, "<f4")
+    return RabitqIndexFile(dim, padded, sw.astype(np.uint64), codes.reshape(n, cb).copy(), norms.astype(np.float32))
