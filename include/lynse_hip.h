@@ -273,6 +273,33 @@ int lynse_hip_flat_search_rabitq_f32(lynse_hip_flat *h, const float *queries, ui
                                      uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
 int lynse_hip_flat_rabitq_stage_times(lynse_hip_flat *h, double *out3, int reset);
 int lynse_hip_rabitq_sign_words(uint64_t seed, uint64_t count, uint64_t *out);
+/* Range search (Collection::search_range, src/engine.rs:6410-6483): every row of the handle is scored with the single-row kernel
+ * (compute_distance_f32) and the rows on the passing side of the caller's threshold come back, best first, at most max_results of
+ * them.  One threshold per query.  The rules:
+ *  1. Distances: the single-row form of the metric at every n (for ip the two-accumulator kernel, never the batch-of-8 form, whatever
+ *     lynse_hip_flat_set_ip_form says).  An F16 shard is scored on its exactly decoded rows with the f32 kernels (as_f32_cow), not
+ *     with the f16 sequential sums.  The binary metrics take the packed popcount forms on the rows and the query thresholded at
+ *     0.5 (pack_binary_query), so a packed-only handle works; ip / l2 / cosine on a packed-only handle are refused.
+ *  2. The pass test: d <= threshold, for ip d >= threshold; plain IEEE comparisons.  A NaN distance never passes, a NaN threshold
+ *     passes nothing, +-inf distances and thresholds are ordinary values.
+ *  3. bitset_words (the reference's BitSet layout: bit r of word r / 64, LSB first; NULL = every row) restricts the scan to its
+ *     rows before the cap; rows the words do not cover are out, bits at or beyond len are ignored.
+ *  4. out_passed[q] (may be NULL) = the rows that passed.  When more than max_results passed the best max_results are kept; what is
+ *     kept comes back best first.  Both steps use the canonical (distance in metric order, row ascending) key, -0 == +0 (the
+ *     reference's select_nth_unstable_by / sort_unstable_by leave ties unpinned).  The distances are the computed values.
+ *  5. Layout: out_rows / out_dists hold nq * max_results entries, out_counts[q] = min(passed, max_results) of them valid, the rest
+ *     padded with row ~0 and the worst distance of the metric, like the other searches.  nq == 0 or max_results == 0: LYNSE_OK, only
+ *     the counts are written and no device is touched.  A NULL required pointer: LYNSE_ERR_INVALID_ARGUMENT.
+ *  Refused with LYNSE_ERR_UNSUPPORTED: a row-sharded handle (set_row_map with stride != 1 or offset != 0) and a row too wide for
+ *  a query and a row to share the 160 KiB of LDS (dim beyond ~20,000).  A FLAT-handle entry: IVF and SPANN handles have none, and
+ *  there is no ticket (submit / wait) form.  The search holds the handle's lock EXCLUSIVELY (its scratch — the score matrix, the
+ *  selection state, the keys — is per handle) and runs on context 0, so it is refused while tickets are outstanding.  Queries go
+ *  in chunks that keep the score matrix at or under 512 MiB and the kept keys at or under 256 MiB. */
+int lynse_hip_flat_search_range_f32(lynse_hip_flat *h, const float *queries, uint64_t nq,
+                                    const float *thresholds /* nq */, uint32_t max_results, int metric,
+                                    const uint64_t *bitset_words /* NULL = every row */, uint64_t n_words,
+                                    uint64_t *out_rows /* nq*max_results */, float *out_dists, uint32_t *out_counts /* nq */,
+                                    uint64_t *out_passed /* nq, may be NULL: rows that passed before the cap */);
 /* Same with every buffer already resident in this handle's device memory; enqueued on `stream`
  * (a hipStream_t, NULL = the handle's own non-blocking stream) and synchronised before returning.
  * Device inputs of every *_device entry must be COMPLETE when the call is made (synchronise the

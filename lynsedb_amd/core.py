@@ -481,6 +481,37 @@ class FlatIndex:
         check(lib.lynse_hip_flat_rabitq_stage_times(self._h, _ptr(out), 1 if reset else 0))
         return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
 
+    def search_range_batch_arrays(self, queries, thresholds, max_results: int, metric, bitset_words=None):
+        """Range search (Collection::search_range, engine.rs:6410-6483) for a batch, one threshold per query: the exact scan of every
+        row (of the rows of `bitset_words`, the reference's BitSet words, when given), the rows with d <= threshold (ip: d >= threshold)
+        -> (rows u64[nq, max_results], distances f32[nq, max_results], counts u32[nq], passed u64[nq]): the best
+        counts[q] = min(passed[q], max_results) passers by (distance, row), best first, padded with row ~0 and the worst distance."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, cap = q.shape[0], int(max_results)
+        if cap < 0:
+            raise ValueError("max_results must not be negative")
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        if thr.size != nq:
+            raise ValueError(f"one threshold per query: expected {nq}, got {thr.size}")
+        rows = np.empty((nq, cap), np.uint64)
+        dists = np.empty((nq, cap), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        passed = np.zeros(nq, np.uint64)
+        if cap == 0 or nq == 0:   # search_range's first early return: nothing is scanned
+            return rows, dists, counts, passed
+        words, n_words = None, 0
+        if bitset_words is not None:
+            words = np.ascontiguousarray(np.asarray(bitset_words).reshape(-1), dtype=np.uint64)
+            n_words = int(words.size)
+            if n_words == 0:   # an empty mask is still a mask (NULL would mean every row)
+                words = np.zeros(1, np.uint64)
+        check(lib.lynse_hip_flat_search_range_f32(self._h, _ptr(q), nq, _ptr(thr), cap, m, None if words is None else _ptr(words), n_words,
+                                                  _ptr(rows), _ptr(dists), _ptr(counts), _ptr(passed)))
+        return rows, dists, counts, passed
+
     def search_filtered_batch_arrays(self, queries, k: int, metric, subset_rows):
         """`FlatMmap::search_filtered` (flat_mmap.rs:491-815) for a batch sharing one subset of row indices."""
         m = metric if isinstance(metric, int) else metric_from_str(metric)
@@ -1498,6 +1529,38 @@ class Collection:
             ids, d_i = filter_tombstoned_limit(ids, d_i, tomb, k)                              # engine.rs:4819-4820
             out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), self._index_mode, self._dim, k))
         return out
+
+
+    def search_range(self, vector, threshold: float, max_results: int = 1000, subset=None):
+        """`Collection.search_range` (src/python/mod.rs:1784-1795 over Collection::search_range, src/engine.rs:6410-6483): the exact scan
+        of every flushed, non-deleted row with the collection's metric, whatever index is built; the rows with distance <= threshold
+        (ip: score >= threshold), at most `max_results` of them, best first -> (ids, distances) as a list of ints and a list of floats.
+        Rows still in the pending buffer are not searched (the reference reads the vector store only).  Ties at the cut and in the
+        order go by ascending row.  `subset=` (a BitSet or row indices) is this build's addition, as on `search`."""
+        max_results = int(max_results)
+        if max_results == 0:   # engine.rs:6416-6418, before the dimension check
+            return [], []
+        if max_results < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        q = np.ascontiguousarray(np.asarray(vector, dtype=np.float32).reshape(-1))
+        if q.size != self._dim:   # engine.rs:6421-6426 -> wrapped as RuntimeError, as on search
+            raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {q.size}")
+        n = len(self._flat)
+        if n == 0:
+            return [], []
+        words = None
+        if subset is not None:
+            words = BitSet.from_rows(self._subset_rows(subset), n).words
+        if self._tombstone:   # tombstoned rows leave before the cap (:6439-6441): they are cleared from the row mask
+            ids = self._id_map()[:n]
+            dead = np.nonzero(np.isin(ids, np.fromiter(self._tombstone, dtype=np.int64, count=len(self._tombstone))))[0].astype(np.uint64)
+            if dead.size:
+                if words is None:
+                    words = BitSet.from_rows(np.arange(n, dtype=np.uint64), n).words
+                words = words & ~BitSet.from_rows(dead, n).words
+        rows, dists, counts, _ = self._flat.search_range_batch_arrays(q.reshape(1, -1), [threshold], max_results, self._metric, words)
+        c = int(counts[0])
+        return [int(x) for x in self._id_map()[rows[0, :c].astype(np.int64)]], [float(x) for x in dists[0, :c]]
 
 
 _METRIC_NAMES = {_lib.METRIC_IP: "ip", _lib.METRIC_L2: "l2", _lib.METRIC_COSINE: "cosine", _lib.METRIC_HAMMING: "hamming",

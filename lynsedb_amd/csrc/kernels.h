@@ -2879,6 +2879,14 @@ struct BinArgs {
     const uint32_t* mask;  // filtered search: bit r = row r is in the subset (k_scan_binary_rows only)
 };
 
+// the distance of the popcount scans from their two counts (c0 / c1: xor bits / unused, and-bits / or-bits, and-bits / popcount sum)
+template <int KIND>  // 0 hamming, 1 jaccard/tanimoto, 2 dice
+__device__ __forceinline__ float binary_distance(uint32_t c0, uint32_t c1) {
+    if (KIND == 0) return (float)c0;
+    if (KIND == 1) return c1 == 0 ? 0.0f : __fsub_rn(1.0f, __fdiv_rn((float)c0, (float)c1));
+    return c1 == 0 ? 0.0f : __fsub_rn(1.0f, __fdiv_rn((float)(2u * c0), (float)c1));
+}
+
 constexpr int BIN_MAX_CHUNKS = 4;  // 4 chunks x 8 lanes x 2 words = 64 words = 4096 bits
 
 template <int KIND>  // 0 hamming, 1 jaccard/tanimoto, 2 dice
@@ -2987,10 +2995,7 @@ __global__ void __launch_bounds__(256) k_scan_binary_wide(BinArgs a) {
                 c1 += __shfl_xor(c1, 4, 8);
             }
             if (g == 0 && row < a.row1) {
-                float dist;
-                if (KIND == 0) dist = (float)c0;
-                else if (KIND == 1) dist = c1 == 0 ? 0.0f : __fsub_rn(1.0f, __fdiv_rn((float)c0, (float)c1));
-                else dist = c1 == 0 ? 0.0f : __fsub_rn(1.0f, __fdiv_rn((float)(2u * c0), (float)c1));
+                const float dist = binary_distance<KIND>(c0, c1);
                 if (a.emit_all) {
                     const uint32_t slot = row - a.row0;
                     if (slot < a.cap) a.cand[(size_t)q * a.cap + slot] = valid ? make_key(dist, row, true) : KEY_SENTINEL;

@@ -29,6 +29,7 @@
 #include "ivf.h"
 #include "pq.h"
 #include "rabitq.h"
+#include "range.h"
 #include "spann.h"
 
 using namespace lynse;
@@ -234,6 +235,7 @@ struct Workspace {
 
 struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
 struct RbqState;  // FLAT-*-RABITQ codes + search scratch (rabitq_host.inc)
+struct RangeState;  // range search scratch (range_host.inc)
 
 struct lynse_hip_flat {
     uint32_t dim = 0, ld = 0, words = 0;
@@ -347,6 +349,7 @@ struct lynse_hip_flat {
 
     PqState* pq = nullptr;                // FLAT-{IP,L2,COS}-PQ index over the first pq->n rows (pq_host.inc); NULL = none
     RbqState* rbq = nullptr;              // FLAT-{IP,L2,COS}-RABITQ index over the first rbq->n rows (rabitq_host.inc); NULL = none
+    RangeState* range = nullptr;          // scratch of lynse_hip_flat_search_range_f32 (range_host.inc); NULL until the first one
 
     std::atomic<bool> profiling{false};   // (read by searches without the lock: atomics)
     std::atomic<uint32_t> prof_rate{1};              // every prof_rate-th search records its events (lynse_hip_flat_profile_enable(h, n))
@@ -356,6 +359,7 @@ struct lynse_hip_flat {
 
 static void pq_release(lynse_hip_flat* h);
 static void rbq_release(lynse_hip_flat* h);
+static void range_release(lynse_hip_flat* h);
 
 static inline bool is_f16(const lynse_hip_flat* h) { return h->dtype == LYNSE_DTYPE_F16; }
 // the row matrix the exact-scoring kernels read: f32 rows, or the f16 bits of an F16 shard handed in as float* with a pitch
@@ -489,6 +493,7 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     (void)hipSetDevice(h->device);
     pq_release(h);
     rbq_release(h);
+    range_release(h);
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
@@ -3835,3 +3840,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "ivf_async.inc"
 #include "pq_host.inc"
 #include "rabitq_host.inc"
+#include "range_host.inc"

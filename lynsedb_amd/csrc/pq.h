@@ -413,6 +413,7 @@ __global__ void __launch_bounds__(256) k_pq_find(PqSel* __restrict__ sel, uint32
 // pool of thousands of rows, one returning atomic each on the same address, cost more than reading the scores).
 constexpr uint32_t PQ_EMIT_TILE = 2048;   // 256 threads x 8 independent loads
 
+template <bool KEYS = false>   // KEYS: the whole key (image << 32 | row) goes out instead of the row (range search sorts them as they are)
 __global__ void __launch_bounds__(256) k_pq_emit(const uint32_t* __restrict__ S, uint64_t n, PqSel* __restrict__ sel, uint32_t pool_ld,
                                                  uint64_t* __restrict__ pool_rows, uint32_t* __restrict__ pool_cnt) {
     __shared__ uint32_t hit[PQ_EMIT_TILE];
@@ -436,7 +437,8 @@ __global__ void __launch_bounds__(256) k_pq_emit(const uint32_t* __restrict__ S,
         if (tid == 0 && n_hit) base = atomicAdd(&pool_cnt[q], n_hit);
         __syncthreads();
         for (uint32_t i = tid; i < n_hit; i += 256)
-            if (base + i < pool_ld) pool_rows[(size_t)q * pool_ld + base + i] = t0 + hit[i];
+            if (base + i < pool_ld)
+                pool_rows[(size_t)q * pool_ld + base + i] = KEYS ? (((uint64_t)Sq[t0 + hit[i]] << 32) | (t0 + hit[i])) : t0 + hit[i];
         __syncthreads();
     }
 }

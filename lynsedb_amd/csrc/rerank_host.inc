@@ -205,22 +205,30 @@ struct ScoreCut {
         }
         return LYNSE_OK;
     }
+    // The selection from the states in sel0 (one per query; a state that starts `done` keeps its prefix: every key whose first
+    // bits are <= it is taken), then the emission of the taken keys of each query to out[q * N ..] — the rows, or KEYS: the whole
+    // keys — with their number in d_cnt[q].  `select`: some state is not done yet.
+    template <bool KEYS>
+    int cut(uint32_t nqc, uint64_t n, uint32_t N, bool select, uint64_t* out, uint32_t* d_cnt, hipStream_t st) {
+        LY_HIP(hipMemcpyAsync(d_sel, sel0.data(), (size_t)nqc * sizeof(PqSel), hipMemcpyHostToDevice, st));
+        const uint32_t rpb = 8192;
+        const dim3 hgrid((uint32_t)((n + rpb - 1) / rpb), nqc);
+        for (uint32_t pass = 0; select && pass < 6; ++pass) {
+            hipLaunchKernelGGL(k_pq_hist, hgrid, dim3(256), 0, st, d_S, n, d_sel, d_hist, rpb);
+            LY_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_pq_find, dim3(nqc), dim3(256), 0, st, d_sel, d_hist);
+            LY_HIP(hipGetLastError());
+        }
+        LY_HIP(hipMemsetAsync(d_cnt, 0, (size_t)nqc * 4, st));
+        const uint32_t eblocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + PQ_EMIT_TILE - 1) / PQ_EMIT_TILE, 1024));
+        hipLaunchKernelGGL(k_pq_emit<KEYS>, dim3(eblocks, nqc), dim3(256), 0, st, d_S, n, d_sel, N, out, d_cnt);
+        LY_HIP(hipGetLastError());
+        return LYNSE_OK;
+    }
     int run(uint32_t nqc, uint64_t n, uint32_t N, PoolRerank& rr, uint32_t num_cu, hipStream_t st) {
         if (N < n) {
             sel0.assign(nqc, PqSel{0ull, 64u, N, 0u, 0u});
-            LY_HIP(hipMemcpyAsync(d_sel, sel0.data(), (size_t)nqc * sizeof(PqSel), hipMemcpyHostToDevice, st));
-            const uint32_t rpb = 8192;
-            const dim3 hgrid((uint32_t)((n + rpb - 1) / rpb), nqc);
-            for (uint32_t pass = 0; pass < 6; ++pass) {
-                hipLaunchKernelGGL(k_pq_hist, hgrid, dim3(256), 0, st, d_S, n, d_sel, d_hist, rpb);
-                LY_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_pq_find, dim3(nqc), dim3(256), 0, st, d_sel, d_hist);
-                LY_HIP(hipGetLastError());
-            }
-            LY_HIP(hipMemsetAsync(rr.d_pcnt, 0, (size_t)nqc * 4, st));
-            const uint32_t eblocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + PQ_EMIT_TILE - 1) / PQ_EMIT_TILE, 1024));
-            hipLaunchKernelGGL(k_pq_emit, dim3(eblocks, nqc), dim3(256), 0, st, d_S, n, d_sel, N, rr.d_prow, rr.d_pcnt);
-            LY_HIP(hipGetLastError());
+            LY_TRY(cut<false>(nqc, n, N, true, rr.d_prow, rr.d_pcnt, st));
         } else {
             const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)nqc * n + 255) / 256, (uint64_t)num_cu * 32));
             hipLaunchKernelGGL(k_pq_pool_all, dim3(blocks), dim3(256), 0, st, n, nqc, N, rr.d_prow, rr.d_pcnt);
