@@ -136,6 +136,9 @@ int ticket_enqueue_exchange(lynse_hip_ticket* t, bool comm_locked = false) {
                                   t->out_counts, c->xstream, so, c->h_status + t->slot);
 }
 
+// LYNSE_HIP_DEBUG_FAIL_SUBMIT=1 (tests): the preparation of a sharded submit, FLAT or IVF, fails locally; read per call
+bool debug_fail_submit() { return env_on("LYNSE_HIP_DEBUG_FAIL_SUBMIT", false); }
+
 int submit_impl(lynse_hip_flat* h, lynse_hip_comm* c, const void* d_queries, bool packed, uint64_t nq, uint32_t k, int metric,
                 uint64_t* d_out_rows, float* d_out_dists, uint32_t* d_out_counts, lynse_hip_ticket** out) {
     if (!h || !out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -194,8 +197,7 @@ int submit_impl(lynse_hip_flat* h, lynse_hip_comm* c, const void* d_queries, boo
     std::string pre_msg;
     auto prepare = [&]() -> int {
     if (c && shape_ok) {   // tests: a simulated local failure of a sharded submit (LYNSE_HIP_DEBUG_FAIL_SUBMIT=1; read per call)
-        const char* e = getenv("LYNSE_HIP_DEBUG_FAIL_SUBMIT");
-        if (e && atoi(e) != 0) return set_error(LYNSE_ERR_OUT_OF_MEMORY, "LYNSE_HIP_DEBUG_FAIL_SUBMIT: simulated local failure of a sharded submit");
+        if (debug_fail_submit()) return set_error(LYNSE_ERR_OUT_OF_MEMORY, "LYNSE_HIP_DEBUG_FAIL_SUBMIT: simulated local failure of a sharded submit");
     }
     if (shape_ok && !binary && h->n > 0 && h->n_stats == h->n && h->inflight.load() != 0 && !basic_ready()) {
         rlk.unlock();

@@ -34,7 +34,7 @@ int rccl_load_locked(const char* path) {
     if (g_rccl.lib) return LYNSE_OK;
     std::vector<std::string> candidates;
     if (path && *path) candidates.push_back(path);
-    if (const char* e = getenv("LYNSE_HIP_RCCL_PATH")) candidates.push_back(e);
+    if (const char* e = env_str("LYNSE_HIP_RCCL_PATH")) candidates.push_back(e);
     for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) candidates.push_back(n);
     std::string tried;
     for (const std::string& c : candidates) {
@@ -390,7 +390,7 @@ extern "C" int lynse_hip_ivf_kmeans_sharded(const float* rows_local, uint64_t n_
     // order lo_kmeans_train_sharded specifies, whatever the world size — and ONE integer ncclAllReduce of the member counts + the
     // "changed" word; the reduced sums and words are read back once (the centroid update is host code, as without sharding).
     // LYNSE_HIP_KM_FORCE_COLLECTIVE=1 runs it at world 1 too (tests: the kernels and the one-rank collectives on real hardware).
-    const bool force_collective = []() { const char* e = getenv("LYNSE_HIP_KM_FORCE_COLLECTIVE"); return e && atoi(e) != 0; }();   // (read per call: tests flip it)
+    const bool force_collective = env_on("LYNSE_HIP_KM_FORCE_COLLECTIVE", false);   // (read per call: tests flip it)
     if (c && (world > 1 || force_collective)) {
         sh.reduce_iter = [&](float* d_sums, uint64_t count, const uint64_t* d_off, uint32_t k, uint32_t changed, hipStream_t st, float* h_sums,
                              uint32_t* h_counts) -> int {

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/lynse_hip.h"
 
@@ -44,6 +45,15 @@ __host__ __device__ inline float key_score(uint64_t key, bool asc) {
 __host__ __device__ inline uint32_t key_row(uint64_t key) { return (uint32_t)key; }
 
 constexpr uint64_t KEY_SENTINEL = ~0ull;
+
+// ---- environment knobs ------------------------------------------------------------------------
+// Every LYNSE_HIP_* name is parsed at ONE place in the host code: a named static accessor next to the code it steers, built on these.
+// The accessor also fixes WHEN the name is read — a `static const` inside it: once per process; none: on every call (tests flip those).
+// DESIGN §10 has the table.
+inline const char* env_str(const char* name) { return getenv(name); }   // nullptr = unset
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// dflt = true: "unset or non-zero" (a switch that is on); dflt = false: "set and non-zero" (one that is off)
+inline bool env_on(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
 
 // ---- geometry of the f16 MFMA scan ------------------------------------------------------------
 constexpr int SCAN_BK = 64;         // K elements per slab

@@ -34,7 +34,7 @@ namespace {
 bool ivf_async_shape_ok(lynse_hip_ivf* h, uint32_t nq, uint32_t nprobe) {
     lynse_hip_flat* s = h->store;
     const Workspace& w = cur(s).ws;
-    const int dg_env = []() { const char* e = getenv("LYNSE_HIP_IVF_DEVICE_GROUPING"); return e ? atoi(e) : 1; }();
+    const int dg_env = ivf_device_grouping();
     const uint32_t np_eff = std::min<uint32_t>(nprobe, h->nlist);
     const uint32_t pass_lists = std::max<uint32_t>(1, w.cap / 16);
     const uint64_t win_bound = (uint64_t)nq * (h->worst_rows[np_eff] / (uint32_t)SCAN_BR + 2ull * np_eff) + 16;
@@ -93,8 +93,7 @@ extern "C" int lynse_hip_ivf_search_submit_f32_device(lynse_hip_ivf* h, lynse_hi
     const bool idle = h->inflight == 0;
     auto prepare = [&]() -> int {
         if (c) {   // tests: a simulated local failure of a sharded submit (LYNSE_HIP_DEBUG_FAIL_SUBMIT=1; read per call)
-            const char* e = getenv("LYNSE_HIP_DEBUG_FAIL_SUBMIT");
-            if (e && atoi(e) != 0) return set_error(LYNSE_ERR_OUT_OF_MEMORY, "LYNSE_HIP_DEBUG_FAIL_SUBMIT: simulated local failure of a sharded submit");
+            if (debug_fail_submit()) return set_error(LYNSE_ERR_OUT_OF_MEMORY, "LYNSE_HIP_DEBUG_FAIL_SUBMIT: simulated local failure of a sharded submit");
         }
         if (s->n > 0) {
             if (idle) {

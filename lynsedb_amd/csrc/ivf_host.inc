@@ -610,8 +610,7 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
         // Round 5 (SURVEY 2a K9): the arg-best epilogue — lane-max scan + k_assign_pick (flat_assign_top1_device); only the rows whose two
         // best coarse centroids lie within the certified margin go through the exact top-1 search.  LYNSE_HIP_ASSIGN_FAST=0: every row
         // through the search (A/B; read per build)
-        const char* fe = getenv("LYNSE_HIP_ASSIGN_FAST");
-        bool fast = k <= 16384 && !(fe && atoi(fe) == 0);
+        bool fast = k <= 16384 && env_on("LYNSE_HIP_ASSIGN_FAST", true);
         std::vector<uint32_t> hids(AQ), hredo(AQ);
         uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_r);           // (AQ x 8 bytes: ids in the first half, the redo list in the second)
         uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_r) + AQ;
@@ -646,7 +645,7 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
             LY_HIP(hipMemcpy(hrows.data(), d_r, nr * 8, hipMemcpyDeviceToHost));
             for (uint64_t i = 0; i < nr; ++i) out[r0 + i] = (uint32_t)hrows[i];
         }
-        if (getenv("LYNSE_HIP_ASSIGN_DBG")) fprintf(stderr, "[lynse] assignment pass: %llu rows, fast path %d, %llu rows through the exact search so far\n",
+        if (env_str("LYNSE_HIP_ASSIGN_DBG")) fprintf(stderr, "[lynse] assignment pass: %llu rows, fast path %d, %llu rows through the exact search so far\n",
                                                     (unsigned long long)n, fast ? 1 : 0, (unsigned long long)assign_redo);
         return LYNSE_OK;
     };
@@ -1130,16 +1129,9 @@ static int launch_scan_tiled(const ScanArgs& a, int metric, bool scale, uint32_t
     if (scan_variant() == 3) return launch_scan_h16<1, 4, 1, 1, 3, 3, true>(a, metric, grid, st);
 #ifdef LYNSE_EXPERIMENTS
     const size_t lds = (size_t)4 * (SCAN_BR * GL_BK * 4 + 32 * GL_BK * 2) + 4 * 1024;
-    static std::atomic<bool> attr_done[6] = {false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
-#define LY_GOT(M, S, slot) return go(k_scan_glds<1, 4, 1, 1, M, S, 4, 2, true>, slot)
-    if (scale) { switch (metric) { case M_IP: LY_GOT(M_IP, true, 0); case M_L2: LY_GOT(M_L2, true, 1); default: LY_GOT(M_COS, true, 2); } }
-    switch (metric) { case M_IP: LY_GOT(M_IP, false, 3); case M_L2: LY_GOT(M_L2, false, 4); default: LY_GOT(M_COS, false, 5); }
+#define LY_GOT(M, S) return launch_lds<k_scan_glds<1, 4, 1, 1, M, S, 4, 2, true>>(grid, 256, lds, st, a)
+    if (scale) { switch (metric) { case M_IP: LY_GOT(M_IP, true); case M_L2: LY_GOT(M_L2, true); default: LY_GOT(M_COS, true); } }
+    switch (metric) { case M_IP: LY_GOT(M_IP, false); case M_L2: LY_GOT(M_L2, false); default: LY_GOT(M_COS, false); }
 #undef LY_GOT
 #else
     (void)scale;
@@ -1216,8 +1208,7 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
         ra.Qf = w.Qf; ra.D = D; ra.C = h->d_centroids; ra.ldc = h->ldc; ra.nlist = h->nlist; ra.metric = route_metric;
         ra.nprobe = np_eff; ra.mode = heuristic ? 1 : 0; ra.rdims = h->d_rdims; ra.nrd = (uint32_t)h->rdims.size();
         ra.shortlist = std::min<uint32_t>(std::max<uint32_t>(np_eff * 3, 24), 96);  // ivf_flat_mmap.rs:395
-        static std::atomic<bool> attr = false;
-        if (!attr) { LY_TRY(set_max_lds(k_ivf_route<256>, 16384 * 8)); attr = true; }
+        LY_TRY(ensure_lds<k_ivf_route<256>>(16384 * 8));
         uint32_t np2 = 2;
         while (np2 < h->nlist) np2 <<= 1;
         ra.probes = scr.d_probes;
@@ -1230,6 +1221,9 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
 
     return LYNSE_OK;
 }
+
+// LYNSE_HIP_IVF_DEVICE_GROUPING=0: the probed lists are grouped on the host (A/B; read per call: tests flip it)
+static int ivf_device_grouping() { return env_int("LYNSE_HIP_IVF_DEVICE_GROUPING", 1); }
 
 static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32_t nq, uint32_t k, uint32_t out_k, uint32_t nprobe,
                                    uint64_t* out_rows, float* out_dists, uint32_t* out_counts, bool safe, bool* overflowed,
@@ -1268,8 +1262,7 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
     {
         const uint32_t np_f = std::min<uint32_t>(nprobe, h->nlist);
         const bool heuristic_f = h->ivfflat_routing && metric == M_IP && D >= 64 && h->nlist >= 64 && !h->rdims.empty();
-        static const int fused_env = []() { const char* e = getenv("LYNSE_HIP_FUSED"); return e ? atoi(e) : 1; }();
-        if (fused_env && !s->no_fused && !binary && !smask && !safe && h16 && nq <= (uint32_t)SMALL_MAX_Q && k <= (uint32_t)SMALL_MAX_K &&
+        if (fused_env() && !s->no_fused && !binary && !smask && !safe && h16 && nq <= (uint32_t)SMALL_MAX_Q && k <= (uint32_t)SMALL_MAX_K &&
             np_f < h->nlist && np_f <= (uint32_t)SMALL_MAX_K && !heuristic_f && s->dtype == LYNSE_DTYPE_F32 &&
             // (the probed lists are scored exactly from the f32 slab: at most the np_f largest lists — 1 GB is ~0.3 ms of this kernel;
             // the bound used to be max_list_len x nprobe <= 256 MB, which uneven k-means lists exceed long before the rows do)
@@ -1400,8 +1393,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         p.Q = w.Qf; p.D = D; p.qpad = qpad; p.nslab = nslab; p.mins = aug ? s->sq8a_mins : (cosq ? s->sq8c_mins : s->sq8_mins);
         p.scales = aug ? s->sq8a_scales : (cosq ? s->sq8c_scales : s->sq8_scales);
         p.a1 = aug ? s->sq8a_a1 : (cosq ? s->sq8c_a1 : s->sq8_a1); p.vmax = s->vmax;
-        static const bool cs_env = []() { const char* e = getenv("LYNSE_HIP_I8C_CS"); return !e || atoi(e) != 0; }();   // (0: the Hoelder terms alone, A/B)
-        if (cs_env) { p.a2sq = aug ? s->sq8a_a2sq : (cosq ? s->sq8c_a2sq : s->sq8_a2sq); p.eps2 = aug ? s->sq8a_eps2 : (cosq ? s->sq8c_eps2 : s->sq8_eps2); }   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
+        if (i8c_cs_on()) { p.a2sq = aug ? s->sq8a_a2sq : (cosq ? s->sq8c_a2sq : s->sq8_a2sq); p.eps2 = aug ? s->sq8a_eps2 : (cosq ? s->sq8c_eps2 : s->sq8_eps2); }   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
         p.cosine = cosq ? 1 : 0; p.aug = aug ? (int)s->aug_cols : 0;
         p.img = reinterpret_cast<int8_t*>(w.Q16); p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
@@ -1426,7 +1418,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     // workgroup, the scan launches read their tile counts from device memory — no copy of the probes to the host, no host
     // loop, no uploads.  Float searches of one pass whose pairs fit one workgroup's LDS; the all-lists-empty fallback of
     // IVFIndex is flagged by the kernel and redone on the host path.  (LYNSE_HIP_IVF_DEVICE_GROUPING=0: host path, A/B.)
-    const int dg_env = []() { const char* e = getenv("LYNSE_HIP_IVF_DEVICE_GROUPING"); return e ? atoi(e) : 1; }();   // (read per call: tests flip it)
+    const int dg_env = ivf_device_grouping();
     const uint32_t pass_lists = std::max<uint32_t>(1, w.cap / 16);
     const uint64_t win_bound = (uint64_t)nq * (h->worst_rows[std::min<uint32_t>(np_eff, h->nlist)] / tile_rows + 2ull * np_eff) + 16;
     const bool dev_group = dg_env && !force_host && !binary && !smask && !list_matches && !safe && h16 && np_eff < h->nlist && np_eff <= pass_lists &&
@@ -1477,12 +1469,8 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     fa.row_stride = h->row_stride; fa.row_offset = h->row_offset;
     fa.orig_ids = binary ? nullptr : h->d_orig;  // the packed scan already emits original rows
     fa.out_rows = w.out_rows; fa.out_dists = w.out_dists; fa.out_counts = w.out_counts; fa.pool_total = nullptr;
-    static std::atomic<bool> sel_attr = false;
-    if (!sel_attr) {
-        LY_TRY(set_max_lds(k_select<SEL_NT>, SEL_LDS_MAX));
-        LY_TRY(set_max_lds(k_final<SEL_NT>, SEL_LDS_MAX));
-        sel_attr = true;
-    }
+    LY_TRY(ensure_lds<k_select<SEL_NT>>(SEL_LDS_MAX));
+    LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
     // one position window: the tiled scan of its tile list (count on the host, or in device memory: ntiles_dev) + the select
     // lynse_hip_ivf_profile_get: HIP events around the tiled scan launches of the blocking searches (scan_us / scan_launches), the
     // rows their tiles cover (scan_rows: a list probed by several 32-query groups is streamed once per group)
@@ -1521,11 +1509,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         if (i8c) {
             a.V16 = reinterpret_cast<const _Float16*>(aug ? s->sq8a : (cosq ? s->sq8c : s->sq8)); a.ld16 = aug ? s->ld8a : s->ld8;
             constexpr size_t lds = (size_t)(3 * 128 + 3 * 32) * 128;
-            static std::atomic<bool> attr = false;
-            auto kern = k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, true, false, 0, false, 2>;
-            if (!attr) { LY_TRY(set_max_lds(kern, lds)); attr = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-            LY_HIP(hipGetLastError());
+            LY_TRY((launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, true, false, 0, false, 2>>(grid, 256, lds, st, a)));
         } else
         LY_TRY(launch_scan_tiled(a, metric, s->sv != 1.0f, grid, st));
         }
@@ -1536,7 +1520,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         sa.neg_metric1 = (aug || cosq) ? metric + 1 : 0;
         sa.exact = binary ? 1 : 0; sa.tighten = binary ? 0 : 1; sa.emit_all_n = -1; sa.keep_ties = 1; sa.Qf = w.Qf; sa.V = s->rows; sa.ld = s->ld; sa.D = D;
         sa.lds_bytes = sel_lds_bytes(w.cap, nq);
-        if (getenv("LYNSE_HIP_SEL_STAMPS") && nq <= 256)   // debugging: phase stamps of the select behind window win_no (lynse_hip_debug_ivf_sel_stamps)
+        if (sel_stamps_on() && nq <= 256)   // debugging: phase stamps of the select behind window win_no (lynse_hip_debug_ivf_sel_stamps)
             sa.stamps = reinterpret_cast<unsigned long long*>(w.gsync + 64) + (size_t)(win_no++ & 3) * 256 * 8;
         hipLaunchKernelGGL(k_select<SEL_NT>, dim3(nq), dim3(SEL_NT), sa.lds_bytes, st, sa);
         LY_HIP(hipGetLastError());
@@ -1569,8 +1553,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         ga.a0 = a0; ga.tile_rows = tile_rows; ga.win_cap = (uint32_t)win_bound; ga.flag_empty = (!h->ivfflat_routing && !h->no_fallback) ? 1u : 0u;
         ga.pair_q = scr.d_pair_q; ga.groups = scr.d_groups; ga.tiles = scr.d_tiles; ga.hdr = scr.d_ghdr; ga.tbase = scr.d_tbase; ga.gmax = (uint32_t)gmax; ga.prank = scr.d_prank;
         const size_t glds = ((size_t)h->nlist * 2 + std::max<size_t>(h->nlist, P) + 16 + 256) * 4;
-        static std::atomic<bool> gattr = false;
-        if (!gattr) { LY_TRY(set_max_lds(k_ivf_group<1024>, ((size_t)IVF_GROUP_MAX_LISTS * 2 + IVF_GROUP_MAX_PAIRS + 16 + 256) * 4 + 64)); gattr = true; }
+        LY_TRY(ensure_lds<k_ivf_group<1024>>(((size_t)IVF_GROUP_MAX_LISTS * 2 + IVF_GROUP_MAX_PAIRS + 16 + 256) * 4 + 64));
         hipLaunchKernelGGL(k_ivf_group<1024>, dim3(1), dim3(1024), glds, st, ga);
         hipLaunchKernelGGL(k_ivf_emit_tiles, dim3(64), dim3(256), 0, st, ga);
         hipLaunchKernelGGL(k_ivf_gather_groups, dim3((uint32_t)s->num_cu * 8), dim3(256), 0, st, w.Q16, qpad, scr.d_gimg, scr.d_groups, scr.d_pair_q,

@@ -82,7 +82,7 @@ static int h2d_done(void* dst, const void* src, size_t n) {
 // blocked reader of the same handle, gets the core (eight blocked readers were eight spinning cores) — for up to
 // LYNSE_HIP_SPIN_US in all (default 5 ms: any batch this library answers at the BASELINE sizes), then block as before.
 static int stream_wait(hipStream_t st) {
-    static const int64_t spin_us = []() { const char* e = getenv("LYNSE_HIP_SPIN_US"); return e ? (int64_t)atoll(e) : (int64_t)5000; }();
+    static const int64_t spin_us = []() { const char* e = env_str("LYNSE_HIP_SPIN_US"); return e ? (int64_t)atoll(e) : (int64_t)5000; }();
     if (spin_us > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         bool polite = false;
@@ -459,7 +459,7 @@ extern "C" int lynse_hip_flat_create(uint32_t dim, int device, lynse_hip_flat** 
     // 48..63 and 96..127 columns: the f16 rows are padded (zeros) to a whole 64-element slab — at most a third more shadow bytes, and the
     // float batches of such a shard (deep-96, GloVe-100 ...) run the whole-slab kernels: k_scan_qh (scan_qh.h) and the non-ragged
     // k_scan_h16 variants.  LYNSE_HIP_SHADOW_PAD=0: the 8-element pitch (A/B, tests; read when the handle is created)
-    if (((dim >= 48 && dim < 64) || (dim >= 96 && dim < 128)) && !(getenv("LYNSE_HIP_SHADOW_PAD") && atoi(getenv("LYNSE_HIP_SHADOW_PAD")) == 0))
+    if (((dim >= 48 && dim < 64) || (dim >= 96 && dim < 128)) && env_on("LYNSE_HIP_SHADOW_PAD", true))
         h->ld16 = round_up(dim, 64);
     h->ld8 = round_up(dim, 16);
     h->ld_bpm = round_up(dim, 256) / 2;
@@ -470,7 +470,7 @@ extern "C" int lynse_hip_flat_create(uint32_t dim, int device, lynse_hip_flat** 
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         h->num_cu = prop.multiProcessorCount;
-    if (const char* ce = getenv("LYNSE_HIP_CONTEXTS")) h->n_ctx = std::max(1, std::min((int)lynse_hip_flat::MAX_CTX, atoi(ce)));
+    if (const char* ce = env_str("LYNSE_HIP_CONTEXTS")) h->n_ctx = std::max(1, std::min((int)lynse_hip_flat::MAX_CTX, atoi(ce)));
     hipError_t e = hipStreamCreateWithFlags(&h->ctx[0].stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete h;
@@ -761,7 +761,7 @@ static int finalize_locked(lynse_hip_flat* h) {
     h->vmax = std::sqrt(f[1]);
     h->vmin = (st[2] == 0x7f800000u) ? 0.0f : std::sqrt(f[2]);
     h->cos_degenerate = st[3] ? 1 : 0;
-    h->rows_integer = ((st[4] & 1u) == 0u && getenv("LYNSE_HIP_NO_EXACT_INT") == nullptr) ? 1 : 0;
+    h->rows_integer = ((st[4] & 1u) == 0u && env_str("LYNSE_HIP_NO_EXACT_INT") == nullptr) ? 1 : 0;
     h->rows_nonneg = (st[4] & 2u) == 0u ? 1 : 0;
     int e = (h->amax > 0.0f && std::isfinite(h->amax)) ? std::ilogb(h->amax) : 13;
     e = std::max(-100, std::min(100, e));
@@ -804,7 +804,7 @@ static int ensure_packed_locked(lynse_hip_flat* h) {
 // Batched Hamming on the int8 MFMA (kernels.h, k_bits_to_pm1): batches of at least LYNSE_HIP_BIN_MFMA_MINQ (default 72)
 // queries, unfiltered, Hamming only (Jaccard / Dice need the row popcounts in the score: the popcount kernels keep them).
 static uint32_t bin_mfma_minq() {
-    static const uint32_t v = []() { const char* e = getenv("LYNSE_HIP_BIN_MFMA_MINQ"); return e ? (uint32_t)atoi(e) : 72u; }();
+    static const uint32_t v = (uint32_t)env_int("LYNSE_HIP_BIN_MFMA_MINQ", 72);
     return v;   // (the MFMA pass costs the same for 33 or 256 queries — 1.9 ms at 12.5M x 1024 bits —, the popcount kernel ~27 us per query: they cross near 70)
 }
 static bool bin_mfma_eligible(const lynse_hip_flat* h, int metric, bool filtered, uint64_t nq) {
@@ -976,7 +976,7 @@ constexpr uint32_t SEG_MAX = 2048;    // most segments per query (grid x row-wav
 static void seg_geometry(uint32_t grid, uint32_t wr, uint32_t* nseg, uint32_t* seg) {
     *nseg = grid * wr;
     *seg = 0;
-    static const int off = []() { const char* e = getenv("LYNSE_HIP_NO_SEGMENTS"); return e ? atoi(e) : 0; }();
+    static const int off = env_int("LYNSE_HIP_NO_SEGMENTS", 0);
     if (off || *nseg == 0 || *nseg > SEG_MAX) { *nseg = 0; return; }
     *seg = std::min<uint32_t>(255u, SEG_KEYS / *nseg);
 }
@@ -986,6 +986,32 @@ static size_t scan_lds_bytes(int bq) { return (size_t)2 * (SCAN_BR + bq) * SCAN_
 template <typename K>
 static int set_max_lds(K kernel, size_t bytes) {
     LY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return LYNSE_OK;
+}
+// The opt-in to more than 64 KiB of dynamic LDS, one record per kernel instantiation K: the size already granted, raised when a launch
+// asks for more (every site that launches K shares the record, and a later one may need more than the first).  The record is per
+// process, not per device: the library's model is one process per device.  Two threads racing on the first call both set the attribute;
+// the one whose record update finds that the other got in between sets the larger of the two sizes again, so that once both have
+// returned the attribute and the record agree on the maximum (a plain store could leave the record above the attribute).  That holds
+// only after the racers have returned: while one of them is between its two steps the attribute can be below the record, and a third
+// thread launching K then would skip the opt-in.  No lock is taken for it, since no site can get there: every instantiation is launched
+// with one size or is granted its maximum up front.
+template <auto K>
+static int ensure_lds(size_t bytes) {
+    static std::atomic<size_t> granted{0};
+    size_t seen = granted.load(std::memory_order_acquire);
+    if (bytes <= seen) return LYNSE_OK;
+    for (;;) {
+        LY_TRY(set_max_lds(K, bytes));
+        if (granted.compare_exchange_strong(seen, bytes, std::memory_order_acq_rel, std::memory_order_acquire)) return LYNSE_OK;
+        bytes = std::max(bytes, seen);   // (the record moved under us: our call may have lowered the attribute below it)
+    }
+}
+template <auto K, typename... Args>
+static int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... a) {
+    LY_TRY(ensure_lds<K>(lds));
+    hipLaunchKernelGGL(K, grid, block, lds, st, a...);
+    LY_HIP(hipGetLastError());
     return LYNSE_OK;
 }
 
@@ -1058,13 +1084,13 @@ static std::vector<Stage> make_plan(const lynse_hip_flat* h, uint32_t k, int lev
         return plan;
     }
     if (level == 0 && tile_rows && n > 4ull * h->cap) {
-        static const uint32_t s_env = []() { const char* e = getenv("LYNSE_HIP_SAMPLE_ROWS"); return e ? (uint32_t)atoi(e) : 0u; }();
+        static const uint32_t s_env = (uint32_t)env_int("LYNSE_HIP_SAMPLE_ROWS", 0);
         // emit-all sample: every sample row becomes a key (S <= cap / 2).  Threshold-only sample: 16 keys per tile, and a
         // tile per CU costs the same latency as 32 tiles — a larger sample gives a tighter first threshold for free
         // (its rows are scanned again: keep it <= n / 16).
         uint32_t S = s_env ? std::min<uint32_t>(s_env, h->cap / 2) : h->cap / 2;
         if (threshold_only_sample) {
-            static const uint32_t big_env = []() { const char* e = getenv("LYNSE_HIP_SAMPLE_ROWS_TO"); return e ? (uint32_t)atoi(e) : 0u; }();
+            static const uint32_t big_env = (uint32_t)env_int("LYNSE_HIP_SAMPLE_ROWS_TO", 0);
             const uint64_t want = big_env ? big_env : (uint64_t)h->num_cu * tile_rows;
             S = (uint32_t)std::max<uint64_t>(S, std::min<uint64_t>(std::min<uint64_t>(want, big_env ? n / 4 : n / 16), (uint64_t)h->cap / 16 * tile_rows));
             S = S / tile_rows * tile_rows;
@@ -1076,7 +1102,7 @@ static std::vector<Stage> make_plan(const lynse_hip_flat* h, uint32_t k, int lev
             s0.sample_tiles = nt;
             s0.sample_stride = (uint32_t)stride;
             plan.push_back(s0);
-            static const uint64_t genv = []() { const char* e = getenv("LYNSE_HIP_SAMPLE_GROWTH"); return e ? (uint64_t)atoi(e) : 0ull; }();
+            static const uint64_t genv = (uint64_t)env_int("LYNSE_HIP_SAMPLE_GROWTH", 0);
             const uint64_t gmax = genv ? genv : growth_hint ? growth_hint : (threshold_only_sample ? 32ull : 16ull);  // measured best on 10M and 1.25M rows
             const uint64_t g = std::max<uint64_t>(2, std::min<uint64_t>(gmax, h->cap / (8ull * std::max<uint32_t>(k, 1))));
             uint64_t seen = S, b = 0;
@@ -1110,21 +1136,11 @@ static int launch_scan(lynse_hip_flat* h, const ScanArgs& a, int metric, uint32_
     constexpr int NT = WQ * WR * 64;
     constexpr int BQ = WQ * TQ * 32;
     const size_t lds = scan_lds_bytes(BQ);
-    static std::atomic<bool> attr_done[3] = {false, false, false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) {
-            LY_TRY(set_max_lds(kern, lds));
-            attr_done[slot] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     (void)h;
     switch (metric) {
-    case M_IP: return go(k_scan_f16<WQ, WR, TQ, TR, M_IP, PD>, 0);
-    case M_L2: return go(k_scan_f16<WQ, WR, TQ, TR, M_L2, PD>, 1);
-    default: return go(k_scan_f16<WQ, WR, TQ, TR, M_COS, PD>, 2);
+    case M_IP: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_IP, PD>>(grid, NT, lds, st, a);
+    case M_L2: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_L2, PD>>(grid, NT, lds, st, a);
+    default: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_COS, PD>>(grid, NT, lds, st, a);
     }
 }
 
@@ -1134,28 +1150,18 @@ static int launch_scan_glds(const ScanArgs& a, int metric, bool scale, uint32_t 
     constexpr int BQ = WQ * TQ * 32;
     constexpr int BR = WR * TR * 32;
     const size_t lds = (size_t)NS * (BR * GL_BK * 4 + BQ * GL_BK * 2) + (metric == M_IP ? 0 : (size_t)NS * 1024);  // + per-tile norm ring
-    static std::atomic<bool> attr_done[12] = {false};
-    static const int nt_hint = []() { const char* e = getenv("LYNSE_HIP_SCAN_NT"); return e ? atoi(e) : 1; }();
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) {
-            LY_TRY(set_max_lds(kern, lds));
-            attr_done[slot] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
-#define LY_GO(M, S, H, slot) return go(k_scan_glds<WQ, WR, TQ, TR, M, S, NS, H>, slot)
+    static const int nt_hint = env_int("LYNSE_HIP_SCAN_NT", 1);
+#define LY_GO(M, S, H) return launch_lds<k_scan_glds<WQ, WR, TQ, TR, M, S, NS, H>>(grid, NT, lds, st, a)
     if (nt_hint) {
         if (scale) {
-            switch (metric) { case M_IP: LY_GO(M_IP, true, 2, 0); case M_L2: LY_GO(M_L2, true, 2, 1); default: LY_GO(M_COS, true, 2, 2); }
+            switch (metric) { case M_IP: LY_GO(M_IP, true, 2); case M_L2: LY_GO(M_L2, true, 2); default: LY_GO(M_COS, true, 2); }
         }
-        switch (metric) { case M_IP: LY_GO(M_IP, false, 2, 3); case M_L2: LY_GO(M_L2, false, 2, 4); default: LY_GO(M_COS, false, 2, 5); }
+        switch (metric) { case M_IP: LY_GO(M_IP, false, 2); case M_L2: LY_GO(M_L2, false, 2); default: LY_GO(M_COS, false, 2); }
     }
     if (scale) {
-        switch (metric) { case M_IP: LY_GO(M_IP, true, 0, 6); case M_L2: LY_GO(M_L2, true, 0, 7); default: LY_GO(M_COS, true, 0, 8); }
+        switch (metric) { case M_IP: LY_GO(M_IP, true, 0); case M_L2: LY_GO(M_L2, true, 0); default: LY_GO(M_COS, true, 0); }
     }
-    switch (metric) { case M_IP: LY_GO(M_IP, false, 0, 9); case M_L2: LY_GO(M_L2, false, 0, 10); default: LY_GO(M_COS, false, 0, 11); }
+    switch (metric) { case M_IP: LY_GO(M_IP, false, 0); case M_L2: LY_GO(M_L2, false, 0); default: LY_GO(M_COS, false, 0); }
 #undef LY_GO
 }
 
@@ -1197,7 +1203,7 @@ extern "C" int lynse_hip_debug_phase_cycles(unsigned long long* out, int n) {  /
 // 1 / 2 = register-staged kernel with prefetch depth 1 / 2
 static int scan_variant() {
 #ifdef LYNSE_EXPERIMENTS
-    static const int v = []() { const char* e = getenv("LYNSE_HIP_SCAN_VARIANT"); return e ? atoi(e) : 3; }();
+    static const int v = env_int("LYNSE_HIP_SCAN_VARIANT", 3);
     return v;
 #else
     return 3;  // the superseded variants are only compiled with make EXPERIMENTS=1
@@ -1214,39 +1220,27 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
     constexpr int BQ = WQ * TQ * 32, BR = WR * TR * 32;
     constexpr size_t rings = (size_t)(NSV * BR + NSQ * BQ) * (HK * 2);
     const size_t lds = (rings + (NSV + 1) * 1024 <= 160 * 1024) ? rings + (NSV + 1) * 1024 : rings;
-    static std::atomic<bool> attr_done[64] = {false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid, grid_y), dim3(WQ * WR * 64), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
+    constexpr int NT = WQ * WR * 64;
+    const dim3 g(grid, grid_y);
     const bool filt = a.mask != nullptr || a.row_ids != nullptr;
     const bool ragged = a.ld16 % HK != 0;
 #ifdef LYNSE_EXPERIMENTS
     if constexpr (WQ == 2 && WR == 4 && !TILED) {  // timing experiments (LYNSE_HIP_DEBUG_FLAGS bits 8..11 = DBG << 8)
         if (metric == M_IP && !filt && !ragged && ((a.debug_flags >> 8) & 15)) {
-            auto ex = [&](auto kern) -> int {
-                LY_TRY(set_max_lds(kern, lds));
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(WQ * WR * 64), lds, st, a);
-                return LYNSE_OK;
-            };
             switch ((a.debug_flags >> 8) & 15) {
-            case 1: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 1>)); break;
-            case 2: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 2>)); break;
-            case 3: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 3>)); break;
-            case 7: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 7>)); break;
-            case 11: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 11>)); break;
-            case 12: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 12>)); break;
-            case 15: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 15>)); break;
-            case 14: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 14>)); break;
-            case 13: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 13>)); break;
-            case 4: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 4>)); break;
-            case 8: LY_TRY(ex(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 8>)); break;
+            case 1: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 1>>(grid, NT, lds, st, a);
+            case 2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 2>>(grid, NT, lds, st, a);
+            case 3: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 3>>(grid, NT, lds, st, a);
+            case 7: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 7>>(grid, NT, lds, st, a);
+            case 11: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 11>>(grid, NT, lds, st, a);
+            case 12: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 12>>(grid, NT, lds, st, a);
+            case 15: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 15>>(grid, NT, lds, st, a);
+            case 14: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 14>>(grid, NT, lds, st, a);
+            case 13: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 13>>(grid, NT, lds, st, a);
+            case 4: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 4>>(grid, NT, lds, st, a);
+            case 8: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 8>>(grid, NT, lds, st, a);
             default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
             }
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
         }
     }
 #endif
@@ -1254,22 +1248,16 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
     if constexpr (WQ == 4 && WR == 2 && TR == 4 && !TILED) {  // decomposition of the low-D L2 scan (C3): LYNSE_HIP_DEBUG_FLAGS bits 8..12 = DBG << 8
         const int dbg = (a.debug_flags >> 8) & 31;
         if (metric == M_L2 && !filt && !ragged && dbg && a.emit_all == 0) {
-            auto ex = [&](auto kern) -> int {
-                LY_TRY(set_max_lds(kern, lds));
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(WQ * WR * 64), lds, st, a);
-                LY_HIP(hipGetLastError());
-                return LYNSE_OK;
-            };
             switch (dbg) {
-            case 16: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 16, false, 0, 0, 0, true>);   // no epilogue
-            case 17: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 17, false, 0, 0, 0, true>);   // + no MFMA (DMA + LDS reads)
-            case 19: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 19, false, 0, 0, 0, true>);   // DMA only
-            case 20: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 20, false, 0, 0, 0, true>);   // no epilogue, no query DMA
-            case 24: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 24, false, 0, 0, 0, true>);   // no epilogue, no row DMA
-            case 28: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 28, false, 0, 0, 0, true>);   // MFMA + LDS reads only
-            case 30: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 30, false, 0, 0, 0, true>);   // MFMA only
-            case 12: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 12, false, 0, 0, 0, true>);   // MFMA + LDS reads + epilogue (no DMA)
-            case 4: return ex(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 4, false, 0, 0, 0, true>);     // everything but the query DMA
+            case 16: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 16, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue
+            case 17: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 17, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // + no MFMA (DMA + LDS reads)
+            case 19: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 19, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // DMA only
+            case 20: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 20, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue, no query DMA
+            case 24: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 24, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue, no row DMA
+            case 28: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 28, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA + LDS reads only
+            case 30: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 30, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA only
+            case 12: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 12, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA + LDS reads + epilogue (no DMA)
+            case 4: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 4, false, 0, 0, 0, true>>(grid, NT, lds, st, a);     // everything but the query DMA
             default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
             }
         }
@@ -1277,66 +1265,66 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
 #endif
     if constexpr (WQ * WR == 8 && !TILED) {
         // one kernel per (metric, ragged / filter variant, emission mode)
-        auto by_emit = [&](auto mtag, auto ragtag, auto filtag, int base) -> int {
+        auto by_emit = [&](auto mtag, auto ragtag, auto filtag) -> int {
             constexpr int M = decltype(mtag)::value;
             constexpr bool RG = decltype(ragtag)::value, FL = decltype(filtag)::value;
             if constexpr (WR < 4 && !FL && M != M_IP) {  // many survivors per block expected: one-pass epilogue (kernels.h, DENSE)
-                if (a.emit_all == 0 && a.dense) return go(k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0, 0, true>, base + 27 + (RG ? 1 : 0));
+                if (a.emit_all == 0 && a.dense) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0, 0, true>>(g, NT, lds, st, a);
             }
-            if (a.emit_all == 0) return go(k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0>, base);
+            if (a.emit_all == 0) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0>>(g, NT, lds, st, a);
             if constexpr (!FL) {  // (the lane-max sample stage exists for the unfiltered tilings only)
-                if (a.emit_all == 2) return go(k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 2>, base + 2);
+                if (a.emit_all == 2) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 2>>(g, NT, lds, st, a);
             }
-            return go(k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 1>, base + 1);
+            return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 1>>(g, NT, lds, st, a);
         };
-        auto by_variant = [&](auto mtag, int base) -> int {
+        auto by_variant = [&](auto mtag) -> int {
             if (filt) {  // subset filter compiled in (always the ragged-capable variant)
                 if constexpr (WR >= 4) return set_error(LYNSE_ERR_INTERNAL, "subset-filtered scans run on the <4,2,2,4> tiling");
-                else return by_emit(mtag, std::true_type{}, std::true_type{}, base + 6);
+                else return by_emit(mtag, std::true_type{}, std::true_type{});
             }
-            if (ragged) return by_emit(mtag, std::true_type{}, std::false_type{}, base + 3);
-            return by_emit(mtag, std::false_type{}, std::false_type{}, base);  // no ragged last slab: branch-free DMA issue
+            if (ragged) return by_emit(mtag, std::true_type{}, std::false_type{});
+            return by_emit(mtag, std::false_type{}, std::false_type{});  // no ragged last slab: branch-free DMA issue
         };
         if constexpr (WR >= 4) {  // <2,4,4,2>: unfiltered IP only
 #ifndef LYNSE_EXPERIMENTS
             if (metric != M_IP) return set_error(LYNSE_ERR_INTERNAL, "the <2,4,4,2> tiling is compiled for IP only");
 #else
-            if (metric == M_L2) return by_variant(std::integral_constant<int, M_L2>{}, 9);
-            if (metric == M_COS) return by_variant(std::integral_constant<int, M_COS>{}, 18);
+            if (metric == M_L2) return by_variant(std::integral_constant<int, M_L2>{});
+            if (metric == M_COS) return by_variant(std::integral_constant<int, M_COS>{});
 #endif
-            return by_variant(std::integral_constant<int, M_IP>{}, 0);
+            return by_variant(std::integral_constant<int, M_IP>{});
         } else {
             switch (metric) {
             case M_IP:
 #ifndef LYNSE_EXPERIMENTS
                 if (!filt) return set_error(LYNSE_ERR_INTERNAL, "unfiltered IP scans run on the <2,4,4,2> tiling");
-                return by_emit(std::integral_constant<int, M_IP>{}, std::true_type{}, std::true_type{}, 6);
+                return by_emit(std::integral_constant<int, M_IP>{}, std::true_type{}, std::true_type{});
 #else
-                return by_variant(std::integral_constant<int, M_IP>{}, 0);
+                return by_variant(std::integral_constant<int, M_IP>{});
 #endif
-            case M_L2: return by_variant(std::integral_constant<int, M_L2>{}, 9);
-            default: return by_variant(std::integral_constant<int, M_COS>{}, 18);
+            case M_L2: return by_variant(std::integral_constant<int, M_L2>{});
+            default: return by_variant(std::integral_constant<int, M_COS>{});
             }
         }
     } else {
         if (!ragged && !filt) {
             switch (metric) {
-            case M_IP: return go(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false>, 3);
-            case M_L2: return go(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, false>, 4);
-            default: return go(k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, false>, 5);
+            case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
+            case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
+            default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
             }
         }
         if (filt) {  // subset filter compiled in (always the ragged-capable variant: one instantiation per metric)
             switch (metric) {
-            case M_IP: return go(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true, 0, true>, 6);
-            case M_L2: return go(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true, 0, true>, 7);
-            default: return go(k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true, 0, true>, 8);
+            case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
+            case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
+            default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
             }
         }
         switch (metric) {
-        case M_IP: return go(k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true>, 0);
-        case M_L2: return go(k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true>, 1);
-        default: return go(k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true>, 2);
+        case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
+        case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
+        default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
         }
     }
 }
@@ -1345,62 +1333,51 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
 // rings) over the SQ8 codes — HBM-bound like its f16 twin, at half the bytes; emission mode at run time (EMIT = -1)
 static int launch_scan_i8c_small(const ScanArgs& a, uint32_t grid, hipStream_t st, bool l2n = false, bool filt = false) {
     constexpr size_t lds = (size_t)(3 * 128 + 3 * 32) * 128;
-    static std::atomic<bool> attr_done[4] = {false, false, false, false};
     if (filt) {   // masked scan of a small batch (row bitmask in the epilogue): whole slabs
         if (a.ld16 % 128 != 0 || a.row_ids || l2n) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        auto kern = k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>;
-        if (!attr_done[3]) { LY_TRY(set_max_lds(kern, lds)); attr_done[3] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
+        return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>>(grid, 256, lds, st, a);
     }
-    if (l2n) {   // plain-code L2 (I8Q = 4): + the norm ring
-        constexpr size_t ldsn = lds + 4 * 1024;
-        auto kern = k_scan_h16<1, 4, 1, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>;
-        if (!attr_done[2]) { LY_TRY(set_max_lds(kern, ldsn)); attr_done[2] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), ldsn, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    }
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
-    if (a.ld16 % 128 == 0) return go(k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>, 0);
-    return go(k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>, 1);
+    if (l2n)   // plain-code L2 (I8Q = 4): + the norm ring
+        return launch_lds<k_scan_h16<1, 4, 1, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>>(grid, 256, lds + 4 * 1024, st, a);
+    if (a.ld16 % 128 == 0) return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>>(grid, 256, lds, st, a);
+    return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>>(grid, 256, lds, st, a);
 }
+
+// The query-stationary tiling of the certified int8 pass (scan_qs.h): threshold stages of an unfiltered FLAT batch over whole
+// 768-byte code rows — 8 waves x 32 register-resident queries, 64-row tiles, rows-only LDS ring.  LYNSE_HIP_QS=0: the 256 x 256
+// tile of k_scan_h16 (A/B, tests; read per call).
+// LYNSE_HIP_QS selects the instantiation (A/B; the default is the fastest measured): 1 = 64-row tiles, whole-K stages, 3-stage ring,
+// ping-pong roles; 2 = 32-row tiles, 6-stage ring, fragments prefetched across the barrier; 3 = as 1 without the ping-pong roles.
+static int qs_variant() { return env_int("LYNSE_HIP_QS", 1); }
+static uint32_t qs_rows(int v) { return v == 2 ? 32u : 64u; }   // rows per tile
+// LYNSE_HIP_QS_WIDTHS=0: the query-stationary tiling for 768 columns only (A/B; read per call)
+static bool qs_widths_on() { return env_on("LYNSE_HIP_QS_WIDTHS", true); }
+// LYNSE_HIP_QS_MASKED=0: the masked threshold stages on the DENSE masked epilogue of k_scan_h16 (A/B; read per call)
+static bool qs_masked_on() { return env_on("LYNSE_HIP_QS_MASKED", true); }
+// LYNSE_HIP_AG=1: the threshold stages of the certified int8 pass with one wave per SIMD (kernels.h, AG; A/B, tests; read per call)
+static int ag_env() { return env_int("LYNSE_HIP_AG", 0); }
 
 // Squared L2 on the query-stationary tiling (scan_qs.h, MET = 1): threshold stages of unfiltered batches of 129..256 queries over code
 // rows of 768 bytes (64-row tiles).  Rows per tile, or 0.
 static uint32_t qs_l2_rows(const ScanArgs& a) {
-    const char* e = getenv("LYNSE_HIP_QS");
-    if (e && atoi(e) == 0) return 0;
+    const int v = qs_variant();
+    if (v == 0) return 0;
     if (a.emit_all != 0 || a.qpad != 256 || a.nq > 256 || a.tile_stride != 0 || a.skip_stride != 0 || a.mask || a.row_ids || a.row1 <= a.row0) return 0;
     if (a.ld16 == 768 && a.nslab == 6) return 64;
     // 256 / 384 / 512 / 640 columns (LYNSE_HIP_QS_WIDTHS=0 or an A/B variant of LYNSE_HIP_QS: 768 only)
-    const char* w = getenv("LYNSE_HIP_QS_WIDTHS");
-    if ((w && atoi(w) == 0) || (e && atoi(e) != 1)) return 0;
+    if (!qs_widths_on() || v != 1) return 0;
     // (6M rows, 256 queries: 256 / 384 columns 0.772 / 0.916 ms on the <4,2,2,4> tiling against 0.773 / 0.929 here — the float epilogue weighs more the
     // fewer MFMAs a tile has; 512 / 640 columns 1.125 / 1.347 -> 1.106 / 1.307; 100 queries: 0.65 / 0.80 / 0.94 / 1.11 -> 0.61 / 0.72 / 0.83 / 0.94)
     if (a.nslab >= 2 && a.nslab <= 5 && a.ld16 == a.nslab * 128u && (a.nslab >= 4 || a.nq <= 128)) return 64;
     return 0;
 }
 static int launch_scan_qs_l2(const ScanArgs& a, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[8] = {false};
-    auto go = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     switch (a.nslab) {
-    case 2: return go(k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 1>, 2, (size_t)3 * 2 * 64 * 128 + 4 * 256);
-    case 3: return go(k_scan_qs<3, 2, 3, 3, false, 8, 0, 1, 0, 1>, 3, (size_t)3 * 3 * 64 * 128 + 4 * 256);
-    case 4: return go(k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 1>, 4, (size_t)3 * 4 * 64 * 128 + 4 * 256);
-    case 5: return go(k_scan_qs<5, 2, 5, 3, false, 8, 0, 1, 0, 1>, 5, (size_t)3 * 5 * 64 * 128 + 4 * 256);
-    default: return go(k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 1>, 6, (size_t)3 * 6 * 64 * 128 + 4 * 256);
+    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + 4 * 256, st, a);
+    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128 + 4 * 256, st, a);
+    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128 + 4 * 256, st, a);
+    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128 + 4 * 256, st, a);
+    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128 + 4 * 256, st, a);
     }
 }
 
@@ -1409,72 +1386,39 @@ static int launch_scan_qs_l2(const ScanArgs& a, uint32_t grid, hipStream_t st) {
 static int launch_scan_i8l2(const ScanArgs& a, uint32_t grid, hipStream_t st, bool qs = false) {
     if (qs) return launch_scan_qs_l2(a, grid, st);
     constexpr size_t lds = (size_t)(2 * 256 + 2 * 256) * 128 + 3 * 1024;
-    static std::atomic<bool> attr_done[4] = {false, false, false, false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     if (a.ld16 % 128 != 0) return set_error(LYNSE_ERR_INTERNAL, "the plain-code L2 scan needs whole 128-column slabs");
-    if (a.emit_all == 1) return go(k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 1>, 0);
-    if (a.emit_all == 2) return go(k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 2>, 1);
-    if (a.dense) return go(k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0, 0, true>, 2);
-    return go(k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0>, 3);
+    if (a.emit_all == 1) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 1>>(grid, 512, lds, st, a);
+    if (a.emit_all == 2) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 2>>(grid, 512, lds, st, a);
+    if (a.dense) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0, 0, true>>(grid, 512, lds, st, a);
+    return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0>>(grid, 512, lds, st, a);
 }
 
 // certified int8 coarse pass for batches of 33..64 queries (128 rows x 64 queries, 4 waves, two workgroups per CU, 3 + 3 stages)
 // and of 65..128 queries (256 rows x 128 queries, 8 waves as 2 x 4, 3 + 2 stages): per row byte they do a quarter / half of the
 // MFMA and fragment-read work of the 256-query tiling, which a batch of 40 or 100 queries would otherwise pay in full
 static int launch_scan_i8c_mid(const ScanArgs& a, uint32_t grid, hipStream_t st, bool wide, bool l2n = false, bool filt = false) {
-    static std::atomic<bool> attr_done[8] = {false, false, false, false, false, false, false, false};
     const bool rag = a.ld16 % 128 != 0;
     if (filt) {   // masked scan (row bitmask in the epilogue): whole slabs
         if (rag || a.row_ids || l2n) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        auto gof = [&](auto kern, int slot, size_t lds, uint32_t threads) -> int {
-            if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
-        };
-        if (!wide) return gof(k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>, 6, (size_t)(3 * 128 + 3 * 64) * 128, 256);
-        return gof(k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, true, 2>, 7, (size_t)(3 * 256 + 2 * 128) * 128, 512);
+        if (!wide) return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>>(grid, 256, (size_t)(3 * 128 + 3 * 64) * 128, st, a);
+        return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, true, 2>>(grid, 512, (size_t)(3 * 256 + 2 * 128) * 128, st, a);
     }
     if (l2n) {   // plain-code L2 (I8Q = 4): whole slabs, + the norm ring
-        auto gol = [&](auto kern, int slot, size_t lds, uint32_t threads) -> int {
-            if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
-        };
-        if (!wide) return gol(k_scan_h16<1, 4, 2, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>, 4, (size_t)(3 * 128 + 3 * 64) * 128 + 4 * 1024, 256);
-        return gol(k_scan_h16<2, 4, 2, 2, M_L2, 3, 2, 2, false, false, 0, false, 4>, 5, (size_t)(3 * 256 + 2 * 128) * 128 + 4 * 1024, 512);
+        if (!wide) return launch_lds<k_scan_h16<1, 4, 2, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>>(grid, 256, (size_t)(3 * 128 + 3 * 64) * 128 + 4 * 1024, st, a);
+        return launch_lds<k_scan_h16<2, 4, 2, 2, M_L2, 3, 2, 2, false, false, 0, false, 4>>(grid, 512, (size_t)(3 * 256 + 2 * 128) * 128 + 4 * 1024, st, a);
     }
-    auto go = [&](auto kern, int slot, size_t lds, uint32_t threads) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     if (!wide) {
         constexpr size_t lds = (size_t)(3 * 128 + 3 * 64) * 128;
-        if (!rag) return go(k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>, 0, lds, 256);
-        return go(k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>, 1, lds, 256);
+        if (!rag) return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>>(grid, 256, lds, st, a);
+        return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>>(grid, 256, lds, st, a);
     }
     constexpr size_t lds = (size_t)(3 * 256 + 2 * 128) * 128;
-    if (!rag) return go(k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, false, 2>, 2, lds, 512);
-    return go(k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, true, 0, false, 2>, 3, lds, 512);
+    if (!rag) return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, false, 2>>(grid, 512, lds, st, a);
+    return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, true, 0, false, 2>>(grid, 512, lds, st, a);
 }
 
 // certified int8 coarse pass: the 256 x 256 IP tiling with 3 + 2-stage rings over 128-element slabs, one kernel per
 // (ragged last slab, emission mode)
-// The query-stationary tiling of the certified int8 pass (scan_qs.h): threshold stages of an unfiltered FLAT batch over whole
-// 768-byte code rows — 8 waves x 32 register-resident queries, 64-row tiles, rows-only LDS ring.  LYNSE_HIP_QS=0: the 256 x 256
-// tile of k_scan_h16 (A/B, tests; read per call).
-// LYNSE_HIP_QS selects the instantiation (A/B; the default is the fastest measured): 1 = 64-row tiles, whole-K stages, 3-stage ring,
-// ping-pong roles; 2 = 32-row tiles, 6-stage ring, fragments prefetched across the barrier; 3 = as 1 without the ping-pong roles.
-static int qs_variant() { const char* e = getenv("LYNSE_HIP_QS"); return e ? atoi(e) : 1; }
-static uint32_t qs_rows(int v) { return v == 2 ? 32u : 64u; }   // rows per tile
 // Self-tightening single-launch scan (scan_qs.h, STS; LYNSE_HIP_STS=1 — OFF by default): unfiltered FLAT batches of 129..256 queries on
 // the certified int8 pass (IP, cosine) over whole 768-byte code rows, k <= 32 (one partition maximum per wanted neighbour), shards
 // large enough that every workgroup helper covers a query (8 grid >= nq) — first plan level only, the overflow ladder keeps the
@@ -1490,25 +1434,20 @@ static uint32_t qs_rows(int v) { return v == 2 ? 32u : 64u; }   // rows per tile
 static bool qs_width_ok(uint32_t ld, uint32_t nslab, bool only768 = false) {
     if (ld == 768 && nslab == 6) return true;
     if (only768 || qs_variant() != 1) return false;
-    const char* e = getenv("LYNSE_HIP_QS_WIDTHS");
-    if (e && atoi(e) == 0) return false;
+    if (!qs_widths_on()) return false;
     return ((nslab >= 2 && nslab <= 5) || nslab == 8) && ld == nslab * 128u;   // (8 slabs = 1024 columns: 32-row tiles, B = 128 registers)
 }
-static bool sts_env_on() { const char* e = getenv("LYNSE_HIP_STS"); return e && atoi(e) != 0; }
+static bool sts_env_on() { return env_on("LYNSE_HIP_STS", false); }
 static bool qs_scan_ok(const ScanArgs& a, bool fs, bool filt, bool f4) {
     const int v = qs_variant();
     if (v < 1 || v > 3) return false;
     // filt: the MASKED threshold stages of a subset-filtered search (row bitmask; k_scan_qs<.., MSK>) — LYNSE_HIP_QS_MASKED=0: the DENSE
     // masked epilogue of k_scan_h16 (A/B; read per call)
-    if (filt) {
-        const char* e = getenv("LYNSE_HIP_QS_MASKED");
-        if ((e && atoi(e) == 0) || v == 2 || !a.mask || a.row_ids) return false;
-    }
+    if (filt && (!qs_masked_on() || v == 2 || !a.mask || a.row_ids)) return false;
     // f4: batched Hamming on the FP4 MFMA (k_scan_qs<.., F4>): 1024-bit fingerprints = 512 B of nibbles = 4 slabs; its plans carry an emit-all
     // sample whose tiles the kernel skips (a.skip_stride).  LYNSE_HIP_QS_F4=0: the 256 x 256 tile of k_scan_h16<.., I8Q = 3> (A/B; read per call)
     if (f4) {
-        const char* e = getenv("LYNSE_HIP_QS_F4");
-        return !(e && atoi(e) == 0) && v == 1 && !fs && !filt && a.emit_all == 0 && (a.nslab == 2 || a.nslab == 4 || a.nslab == 8) && a.ld16 == a.nslab * 128u &&   // 512 / 1024 / 2048-bit rows
+        return env_on("LYNSE_HIP_QS_F4", true) && v == 1 && !fs && !filt && a.emit_all == 0 && (a.nslab == 2 || a.nslab == 4 || a.nslab == 8) && a.ld16 == a.nslab * 128u &&   // 512 / 1024 / 2048-bit rows
                a.qpad == 256 && a.nq <= 256 &&
                a.tile_stride == 0 && !a.mask && !a.row_ids && a.row1 > a.row0;
     }
@@ -1520,72 +1459,44 @@ static bool qs_scan_ok(const ScanArgs& a, bool fs, bool filt, bool f4) {
 // batch in flight (query image, sample stage, selects, final rescoring) run beside it instead of between its launches.
 static uint32_t qs_grid(const ScanArgs& a, uint32_t num_cu) {
     const uint32_t rt = a.nslab == 8 ? 32u : qs_rows(qs_variant());   // (1024 columns: 32-row tiles)
-    const char* e = getenv("LYNSE_HIP_SCAN_CUS");
-    const uint32_t cus = e && atoi(e) > 0 ? std::min<uint32_t>((uint32_t)atoi(e), num_cu) : num_cu;
+    const int e = env_int("LYNSE_HIP_SCAN_CUS", 0);
+    const uint32_t cus = e > 0 ? std::min<uint32_t>((uint32_t)e, num_cu) : num_cu;
     return std::min<uint32_t>((a.row1 - a.row0 + rt - 1) / rt, cus);
 }
 static int launch_scan_qs(const ScanArgs& a, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[5] = {false, false, false, false, false};
-    if (a.dyn_thr) {   // self-tightening thresholds: the whole shard in one launch (scan_qs.h, STS)
-        auto kern = k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 1>;
-        constexpr size_t lds = (size_t)3 * 6 * 64 * 128 + QS_STS_LDS;
-        if (!attr_done[4]) { LY_TRY(set_max_lds(kern, lds)); attr_done[4] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    }
-    auto go = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
-    if (a.mask) return go(k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 0, 1>, 0, (size_t)3 * 6 * 64 * 128);   // masked threshold stages (MSK)
-    static std::atomic<bool> attr_w[8] = {false};
-    auto gow = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_w[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_w[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
+    if (a.dyn_thr)   // self-tightening thresholds: the whole shard in one launch (scan_qs.h, STS)
+        return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128 + QS_STS_LDS, st, a);
+    if (a.mask) return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);   // masked threshold stages (MSK)
     switch (a.nslab) {   // the narrower code rows (qs_width_ok)
-    case 2: return gow(k_scan_qs<2, 2, 2, 3, false, 8, 0, 1>, 2, (size_t)3 * 2 * 64 * 128);
-    case 3: return gow(k_scan_qs<3, 2, 3, 3, false, 8, 0, 1>, 3, (size_t)3 * 3 * 64 * 128);
-    case 4: return gow(k_scan_qs<4, 2, 4, 3, false, 8, 0, 1>, 4, (size_t)3 * 4 * 64 * 128);
-    case 5: return gow(k_scan_qs<5, 2, 5, 3, false, 8, 0, 1>, 5, (size_t)3 * 5 * 64 * 128);
-    case 8: return gow(k_scan_qs<8, 1, 8, 4, false, 8, 0, 1>, 7, (size_t)4 * 8 * 32 * 128);
+    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);
+    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128, st, a);
+    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
+    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128, st, a);
+    case 8: return launch_lds<k_scan_qs<8, 1, 8, 4, false, 8, 0, 1>>(grid, 512, (size_t)4 * 8 * 32 * 128, st, a);
     default: break;
     }
     switch (qs_variant()) {
-    case 2: return go(k_scan_qs<6, 1, 6, 6, true, 8, 0, 0>, 2, (size_t)6 * 6 * 32 * 128);
-    case 3: return go(k_scan_qs<6, 2, 6, 3, false, 8, 0, 0>, 3, (size_t)3 * 6 * 64 * 128);
-    default: return go(k_scan_qs<6, 2, 6, 3, false, 8, 0, 1>, 1, (size_t)3 * 6 * 64 * 128);
+    case 2: return launch_lds<k_scan_qs<6, 1, 6, 6, true, 8, 0, 0>>(grid, 512, (size_t)6 * 6 * 32 * 128, st, a);
+    case 3: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
+    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
     }
 }
 
 // The threshold-only SAMPLE stage on the query-stationary tiling (scan_qs.h, SMP = 1): the sample rows as 64-row tiles, four per workgroup
 // on a full chip (one 144-KB workgroup per CU), 4 keys per workgroup and query = 1024 keys per query.  LYNSE_HIP_QS_SAMPLE=0: the 256 x 256 sample tiles of k_scan_h16 (A/B; read per call).
 static bool qs_sample_ok(const ScanArgs& a, bool fs, bool filt, bool f4, uint32_t plan_tile) {
-    const char* e = getenv("LYNSE_HIP_QS_SAMPLE");
     const int v = qs_variant();
-    if ((e && atoi(e) == 0) || (v != 1 && v != 3)) return false;
+    if (!env_on("LYNSE_HIP_QS_SAMPLE", true) || (v != 1 && v != 3)) return false;
     return !fs && !filt && !f4 && a.emit_all == 2 && plan_tile == 256 && a.nslab != 8 && qs_width_ok(a.ld16, a.nslab) && a.qpad == 256 && a.nq <= 256 && a.tile_stride >= 256 &&
            a.skip_stride == 0 && !a.mask && !a.row_ids && a.row1 > a.row0;
 }
 static int launch_scan_qs_sample(const ScanArgs& a, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[8] = {false};
-    auto go = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     switch (a.nslab) {
-    case 2: return go(k_scan_qs<2, 2, 2, 3, false, 8, 0, 0, 0, 0, 1>, 2, (size_t)3 * 2 * 64 * 128);
-    case 3: return go(k_scan_qs<3, 2, 3, 3, false, 8, 0, 0, 0, 0, 1>, 3, (size_t)3 * 3 * 64 * 128);
-    case 4: return go(k_scan_qs<4, 2, 4, 3, false, 8, 0, 0, 0, 0, 1>, 4, (size_t)3 * 4 * 64 * 128);
-    case 5: return go(k_scan_qs<5, 2, 5, 3, false, 8, 0, 0, 0, 0, 1>, 5, (size_t)3 * 5 * 64 * 128);
-    default: return go(k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 0, 0, 1>, 6, (size_t)3 * 6 * 64 * 128);
+    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);
+    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128, st, a);
+    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
+    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128, st, a);
+    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
     }
 }
 
@@ -1595,7 +1506,7 @@ static int launch_scan_qs_sample(const ScanArgs& a, uint32_t grid, hipStream_t s
 // 0.190-0.194 against 0.213-0.219 ms per batch on the same box; DESIGN 4.3 has the phase table and what the first versions lost to
 // (keys stored straight to global memory stalled the ring; a grouped slow path as long as the MFMAs of its step).
 constexpr int QH_DEFAULT = 1;
-static int qh_variant() { const char* e = getenv("LYNSE_HIP_QH"); return e ? atoi(e) : QH_DEFAULT; }   // 0 = k_scan_h16, 1 = k_scan_qh
+static int qh_variant() { return env_int("LYNSE_HIP_QH", QH_DEFAULT); }   // 0 = k_scan_h16, 1 = k_scan_qh
 // the batch SHAPE k_scan_qh takes (shared with i8c_eligible, which sends FLAT-IP batches of this shape to the float pass only because
 // this kernel runs them: ADVICE r5): 33..256 queries — one 256-query chunk —, rows of one or two whole 64-element slabs
 static bool qh_shape(uint32_t ld16, uint64_t nq) { return qh_variant() == 1 && nq > SCAN_BQ_SMALL && nq <= QCHUNK && (ld16 == 64u || ld16 == 128u); }
@@ -1609,34 +1520,26 @@ static uint32_t qh_grid(const ScanArgs& a, uint32_t num_cu, uint32_t* segs_per_w
     return std::min<uint32_t>((a.row1 - a.row0 + 63u) / 64u, 2u * num_cu);
 }
 static int launch_scan_qh(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[16] = {false};
-    auto go = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     // 32 queries per wave, 64-row tiles, two workgroups per CU (<= 80 KB of LDS each)
     constexpr size_t stg1 = 8 * 144 * 24 + 1024, nrm1 = 4 * 256 + stg1;   // (three ring stages: the LDS of the fourth is the staging regions')
     if (a.nslab == 1) {
         switch (metric) {
-        case M_IP: return go(k_scan_qh<1, M_IP, 3, 2, 1>, 6, (size_t)3 * 1 * 64 * 128 + stg1);
-        case M_L2: return go(k_scan_qh<1, M_L2, 3, 2, 1>, 7, (size_t)3 * 1 * 64 * 128 + nrm1);
-        default: return go(k_scan_qh<1, M_COS, 3, 2, 1>, 8, (size_t)3 * 1 * 64 * 128 + nrm1);
+        case M_IP: return launch_lds<k_scan_qh<1, M_IP, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + stg1, st, a);
+        case M_L2: return launch_lds<k_scan_qh<1, M_L2, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
+        default: return launch_lds<k_scan_qh<1, M_COS, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
         }
     }
     switch (metric) {
-    case M_IP: return go(k_scan_qh<2, M_IP, 3, 2, 1>, 9, (size_t)3 * 2 * 64 * 128 + stg1);
-    case M_L2: return go(k_scan_qh<2, M_L2, 3, 2, 1>, 10, (size_t)3 * 2 * 64 * 128 + nrm1);
-    default: return go(k_scan_qh<2, M_COS, 3, 2, 1>, 11, (size_t)3 * 2 * 64 * 128 + nrm1);
+    case M_IP: return launch_lds<k_scan_qh<2, M_IP, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + stg1, st, a);
+    case M_L2: return launch_lds<k_scan_qh<2, M_L2, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
+    default: return launch_lds<k_scan_qh<2, M_COS, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
     }
 }
 
 // The threshold-only SAMPLE stage of the same plans on k_scan_qh<.., SMP> (scan_qh.h): the sample rows as 64-row tiles, two workgroups per CU,
 // 4 keys per workgroup and query.  LYNSE_HIP_QH_SAMPLE=0: the 256 x 256 sample tiles of k_scan_h16<.., EMIT = 2> (A/B; read per call).
 static bool qh_sample_ok(const ScanArgs& a, bool filt, uint32_t qchunks, int level, uint32_t plan_tile) {
-    const char* e = getenv("LYNSE_HIP_QH_SAMPLE");
-    if ((e && atoi(e) == 0) || qh_variant() != 1 || level != 0) return false;
+    if (!env_on("LYNSE_HIP_QH_SAMPLE", true) || qh_variant() != 1 || level != 0) return false;
     return !filt && a.emit_all == 2 && plan_tile == 256 && qchunks == 1 && a.qpad == 256 && a.nq <= 256 && a.tile_stride >= 256 && a.skip_stride == 0 && !a.mask && !a.row_ids &&
            !a.tiles && a.row1 > a.row0 && (a.nslab == 1 || a.nslab == 2) && a.ld16 == a.nslab * 64u;
 }
@@ -1649,25 +1552,18 @@ static uint32_t qh_sample_grid(const ScanArgs& a, uint32_t sample_tiles, bool fi
     return ok ? sgrid : 0u;
 }
 static int launch_scan_qh_sample(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[8] = {false};
-    auto go = [&](auto kern, int slot, size_t lds) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
     constexpr size_t stg1 = 8 * 144 * 24 + 1024, nrm1 = 4 * 256 + stg1;
     if (a.nslab == 1) {
         switch (metric) {
-        case M_IP: return go(k_scan_qh<1, M_IP, 3, 2, 1, 1>, 0, (size_t)3 * 1 * 64 * 128 + stg1);
-        case M_L2: return go(k_scan_qh<1, M_L2, 3, 2, 1, 1>, 1, (size_t)3 * 1 * 64 * 128 + nrm1);
-        default: return go(k_scan_qh<1, M_COS, 3, 2, 1, 1>, 2, (size_t)3 * 1 * 64 * 128 + nrm1);
+        case M_IP: return launch_lds<k_scan_qh<1, M_IP, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + stg1, st, a);
+        case M_L2: return launch_lds<k_scan_qh<1, M_L2, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
+        default: return launch_lds<k_scan_qh<1, M_COS, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
         }
     }
     switch (metric) {
-    case M_IP: return go(k_scan_qh<2, M_IP, 3, 2, 1, 1>, 3, (size_t)3 * 2 * 64 * 128 + stg1);
-    case M_L2: return go(k_scan_qh<2, M_L2, 3, 2, 1, 1>, 4, (size_t)3 * 2 * 64 * 128 + nrm1);
-    default: return go(k_scan_qh<2, M_COS, 3, 2, 1, 1>, 5, (size_t)3 * 2 * 64 * 128 + nrm1);
+    case M_IP: return launch_lds<k_scan_qh<2, M_IP, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + stg1, st, a);
+    case M_L2: return launch_lds<k_scan_qh<2, M_L2, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
+    default: return launch_lds<k_scan_qh<2, M_COS, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
     }
 }
 
@@ -1678,97 +1574,67 @@ static int launch_scan_qh_sample(const ScanArgs& a, int metric, uint32_t grid, h
 static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, bool fs = false, bool filt = false, bool f4 = false, bool qs = false) {
     constexpr size_t lds = (size_t)(3 * 256 + 2 * 256) * 128;
     if (qs && f4) {   // batched Hamming on the query-stationary tiling (scan_qs.h, F4)
-        static std::atomic<bool> attr_f4[3] = {false, false, false};
-        auto gof = [&](auto kern, int slot, size_t qlds) -> int {
-            if (!attr_f4[slot]) { LY_TRY(set_max_lds(kern, qlds)); attr_f4[slot] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), qlds, st, a);
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
-        };
-        if (a.nslab == 2) return gof(k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>, 0, (size_t)3 * 2 * 64 * 128);   // 512-bit rows
-        if (a.nslab == 8) return gof(k_scan_qs<8, 1, 8, 4, false, 8, 0, 1, 0, 0, 0, 0, 1>, 2, (size_t)4 * 8 * 32 * 128);   // 2048-bit rows: 32-row tiles
-        return gof(k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>, 1, (size_t)3 * 4 * 64 * 128);
+        if (a.nslab == 2) return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);   // 512-bit rows
+        if (a.nslab == 8) return launch_lds<k_scan_qs<8, 1, 8, 4, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)4 * 8 * 32 * 128, st, a);   // 2048-bit rows: 32-row tiles
+        return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
     }
     if (qs) return launch_scan_qs(a, grid, st);
-    static std::atomic<bool> attr_done[16] = {false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
 #ifdef LYNSE_EXPERIMENTS
     if (a.ld16 % 128 == 0 && a.emit_all == 0 && ((a.debug_flags >> 8) & 31)) {  // timing experiments: DBG variants of the int8 kernel
-        auto ex = [&](auto kern) -> int {
-            LY_TRY(set_max_lds(kern, lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
-        };
         switch ((a.debug_flags >> 8) & 31) {
-        case 3: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 3, false, 2, 0>);    // DMA only
-        case 4: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 4, false, 2, 0>);    // no query-image DMA
-        case 8: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 8, false, 2, 0>);    // no row DMA
-        case 12: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 12, false, 2, 0>);  // MFMA + LDS reads only
-        case 7: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 7, false, 2, 0>);    // row DMA only
-        case 11: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 11, false, 2, 0>);  // query DMA only
-        case 1: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 1, false, 2, 0>);    // no MFMA (DMA + LDS reads)
-        case 13: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 13, false, 2, 0>);  // LDS reads only
-        case 14: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 14, false, 2, 0>);  // MFMA only
-        case 2: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 2, false, 2, 0>);    // no LDS reads (DMA + MFMA)
-        case 16: return ex(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 16, false, 2, 0>);  // no epilogue
+        case 3: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 3, false, 2, 0>>(grid, 512, lds, st, a);    // DMA only
+        case 4: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 4, false, 2, 0>>(grid, 512, lds, st, a);    // no query-image DMA
+        case 8: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 8, false, 2, 0>>(grid, 512, lds, st, a);    // no row DMA
+        case 12: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 12, false, 2, 0>>(grid, 512, lds, st, a);  // MFMA + LDS reads only
+        case 7: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 7, false, 2, 0>>(grid, 512, lds, st, a);    // row DMA only
+        case 11: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 11, false, 2, 0>>(grid, 512, lds, st, a);  // query DMA only
+        case 1: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 1, false, 2, 0>>(grid, 512, lds, st, a);    // no MFMA (DMA + LDS reads)
+        case 13: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 13, false, 2, 0>>(grid, 512, lds, st, a);  // LDS reads only
+        case 14: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 14, false, 2, 0>>(grid, 512, lds, st, a);  // MFMA only
+        case 2: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 2, false, 2, 0>>(grid, 512, lds, st, a);    // no LDS reads (DMA + MFMA)
+        case 16: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 16, false, 2, 0>>(grid, 512, lds, st, a);  // no epilogue
         default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
         }
     }
 #endif
     if (f4) {   // batched Hamming: FP4 +-1 operands (kernels.h, I8Q = 3); whole 128-B slabs by construction, unfiltered
         if (a.ld16 % 128 != 0 || filt || fs) return set_error(LYNSE_ERR_INTERNAL, "the FP4 Hamming scan runs unfiltered over whole slabs");
-        if (a.emit_all == 1) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 1>, 11);
-        if (a.emit_all == 2) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 2>, 12);
-        if (a.dense) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0, 0, true>, 13);
-        return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0>, 14);
+        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 1>>(grid, 512, lds, st, a);
+        if (a.emit_all == 2) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 2>>(grid, 512, lds, st, a);
+        if (a.dense) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0, 0, true>>(grid, 512, lds, st, a);
+        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0>>(grid, 512, lds, st, a);
     }
     if (filt) {  // masked scan (subset as a row bitmask): emit-all sample with sentinels, DENSE threshold stages (kernels.h, FILT && I8C)
         if (a.ld16 % 128 != 0 || a.row_ids) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        if (a.emit_all == 1) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 1>, 9);
+        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 1>>(grid, 512, lds, st, a);
         if (a.emit_all != 0 || !a.dense) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan runs emit-all and DENSE threshold stages");
-        return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 0, 0, true>, 10);
+        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 0, 0, true>>(grid, 512, lds, st, a);
     }
     // One wave per SIMD: 4 waves x (128 queries x 128 rows), accumulators in fixed AGPR tuples (kernels.h, AG) — the threshold
     // stages over whole 128-column slabs (LYNSE_HIP_AG=1; the sample stages keep the 8-wave kernels)
-    const int ag_env = []() { const char* e = getenv("LYNSE_HIP_AG"); return e ? atoi(e) : 0; }();   // (read per call: A/B, tests)
-    if (ag_env && a.ld16 % 128 == 0 && a.emit_all == 0 && !fs) {
-        static std::atomic<bool> ag_attr[2] = {false, false};
-        auto go4 = [&](auto kern, int slot) -> int {
-            if (!ag_attr[slot]) { LY_TRY(set_max_lds(kern, lds)); ag_attr[slot] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-            LY_HIP(hipGetLastError());
-            return LYNSE_OK;
-        };
-        if (a.dense) return go4(k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>, 0);
-        return go4(k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>, 1);
+    if (ag_env() && a.ld16 % 128 == 0 && a.emit_all == 0 && !fs) {
+        if (a.dense) return launch_lds<k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>>(grid, 256, lds, st, a);
+        return launch_lds<k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>>(grid, 256, lds, st, a);
     }
     if (a.ld16 % 128 == 0) {
-        static const int prio = []() { const char* e = getenv("LYNSE_HIP_PRIO"); return e ? atoi(e) : 0; }();
-        static std::atomic<bool> prattr = false;
-        if (a.emit_all == 0 && prio) { auto k = k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, false, true>; if (!prattr) { LY_TRY(set_max_lds(k, lds)); prattr = true; } hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a); LY_HIP(hipGetLastError()); return LYNSE_OK; }
-        static const int place = []() { const char* e = getenv("LYNSE_HIP_PLACE"); return e ? atoi(e) : 0; }();
-        static std::atomic<bool> pattr[2] = {false, false};
-        if (a.emit_all == 0 && place == 1) { auto k = k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 1>; if (!pattr[0]) { LY_TRY(set_max_lds(k, lds)); pattr[0] = true; } hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a); LY_HIP(hipGetLastError()); return LYNSE_OK; }
-        if (a.emit_all == 0 && place == 2) { auto k = k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 2>; if (!pattr[1]) { LY_TRY(set_max_lds(k, lds)); pattr[1] = true; } hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a); LY_HIP(hipGetLastError()); return LYNSE_OK; }
+        static const int prio = env_int("LYNSE_HIP_PRIO", 0);
+        if (a.emit_all == 0 && prio) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, false, true>>(grid, 512, lds, st, a);
+        static const int place = env_int("LYNSE_HIP_PLACE", 0);
+        if (a.emit_all == 0 && place == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 1>>(grid, 512, lds, st, a);
+        if (a.emit_all == 0 && place == 2) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 2>>(grid, 512, lds, st, a);
         if (fs) {  // fused sample stage: sample tile + in-launch thresholds + the first threshold stage (kernels.h, FS)
             if (a.emit_all != 0) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is a threshold stage");
             if (!a.dense) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is compiled with the DENSE epilogue");  // (the two-level body spills 12 B with it)
-            return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true, false, true, 1>, 7);
+            return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true, false, true, 1>>(grid, 512, lds, st, a);
         }
-        if (a.emit_all == 0 && a.dense) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>, 6);
-        if (a.emit_all == 0) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>, 0);
-        if (a.emit_all == 1) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 1>, 1);
-        return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 2>, 2);
+        if (a.emit_all == 0 && a.dense) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>>(grid, 512, lds, st, a);
+        if (a.emit_all == 0) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>>(grid, 512, lds, st, a);
+        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 1>>(grid, 512, lds, st, a);
+        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 2>>(grid, 512, lds, st, a);
     }
-    if (a.emit_all == 0) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 0>, 3);
-    if (a.emit_all == 1) return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 1>, 4);
-    return go(k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 2>, 5);
+    if (a.emit_all == 0) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 0>>(grid, 512, lds, st, a);
+    if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 1>>(grid, 512, lds, st, a);
+    return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 2>>(grid, 512, lds, st, a);
 }
 
 // f16 shadow rows [n16, n) (all rows again when the scale changed)
@@ -1819,21 +1685,15 @@ static int ensure_shadow_locked(lynse_hip_flat* h) {
 }
 
 static int launch_scan_binary(const BinArgs& a, int metric, uint32_t grid, size_t lds, hipStream_t st) {
-    static std::atomic<bool> attr_done[3] = {false, false, false};
-    auto go = [&](auto kern, int slot) -> int {
-        if (!attr_done[slot]) {
-            LY_TRY(set_max_lds(kern, 160 * 1024 - 64));
-            attr_done[slot] = true;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
+    // (the opt-in is to the most the kernel may be launched with: the launch size depends on the batch)
+    constexpr size_t LDS_MAX = 160 * 1024 - 64;
     switch (metric) {
-    case M_HAMMING: return go(k_scan_binary<0>, 0);
-    case M_DICE: return go(k_scan_binary<2>, 2);
-    default: return go(k_scan_binary<1>, 1);
+    case M_HAMMING: LY_TRY(ensure_lds<k_scan_binary<0>>(LDS_MAX)); hipLaunchKernelGGL(k_scan_binary<0>, dim3(grid), dim3(256), lds, st, a); break;
+    case M_DICE: LY_TRY(ensure_lds<k_scan_binary<2>>(LDS_MAX)); hipLaunchKernelGGL(k_scan_binary<2>, dim3(grid), dim3(256), lds, st, a); break;
+    default: LY_TRY(ensure_lds<k_scan_binary<1>>(LDS_MAX)); hipLaunchKernelGGL(k_scan_binary<1>, dim3(grid), dim3(256), lds, st, a); break;
     }
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
 }
 
 // rows wider than 4096 bits (k_scan_binary_wide): no LDS, no register-resident words
@@ -1850,28 +1710,21 @@ static int launch_scan_binary_wide(const BinArgs& a, int metric, uint32_t grid, 
 // lane-per-row batched kernel: WCAP = the power of two >= words
 template <int KIND>
 static int launch_scan_binary_rows_k(const BinArgs& a, uint32_t grid, hipStream_t st) {
-    static std::atomic<bool> attr_done[12] = {false};
-    auto go = [&](auto kern, int wcap, int slot) -> int {
-        const size_t lds = (size_t)4 * 64 * bin_rows_stride(wcap);
-        if (!attr_done[slot]) { LY_TRY(set_max_lds(kern, lds)); attr_done[slot] = true; }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-        LY_HIP(hipGetLastError());
-        return LYNSE_OK;
-    };
+    auto lds = [](int wcap) { return (size_t)4 * 64 * bin_rows_stride(wcap); };
     if (a.W & 1u) {
-        if (a.W <= 1) return go(k_scan_binary_rows<KIND, 1, true>, 1, 0);
-        if (a.W <= 4) return go(k_scan_binary_rows<KIND, 4, true>, 4, 1);
-        if (a.W <= 8) return go(k_scan_binary_rows<KIND, 8, true>, 8, 2);
-        if (a.W <= 16) return go(k_scan_binary_rows<KIND, 16, true>, 16, 3);
-        if (a.W <= 32) return go(k_scan_binary_rows<KIND, 32, true>, 32, 4);
-        return go(k_scan_binary_rows<KIND, 64, true>, 64, 5);
+        if (a.W <= 1) return launch_lds<k_scan_binary_rows<KIND, 1, true>>(grid, 256, lds(1), st, a);
+        if (a.W <= 4) return launch_lds<k_scan_binary_rows<KIND, 4, true>>(grid, 256, lds(4), st, a);
+        if (a.W <= 8) return launch_lds<k_scan_binary_rows<KIND, 8, true>>(grid, 256, lds(8), st, a);
+        if (a.W <= 16) return launch_lds<k_scan_binary_rows<KIND, 16, true>>(grid, 256, lds(16), st, a);
+        if (a.W <= 32) return launch_lds<k_scan_binary_rows<KIND, 32, true>>(grid, 256, lds(32), st, a);
+        return launch_lds<k_scan_binary_rows<KIND, 64, true>>(grid, 256, lds(64), st, a);
     }
-    if (a.W <= 2) return go(k_scan_binary_rows<KIND, 2, false>, 2, 6);
-    if (a.W <= 4) return go(k_scan_binary_rows<KIND, 4, false>, 4, 7);
-    if (a.W <= 8) return go(k_scan_binary_rows<KIND, 8, false>, 8, 8);
-    if (a.W <= 16) return go(k_scan_binary_rows<KIND, 16, false>, 16, 9);
-    if (a.W <= 32) return go(k_scan_binary_rows<KIND, 32, false>, 32, 10);
-    return go(k_scan_binary_rows<KIND, 64, false>, 64, 11);
+    if (a.W <= 2) return launch_lds<k_scan_binary_rows<KIND, 2, false>>(grid, 256, lds(2), st, a);
+    if (a.W <= 4) return launch_lds<k_scan_binary_rows<KIND, 4, false>>(grid, 256, lds(4), st, a);
+    if (a.W <= 8) return launch_lds<k_scan_binary_rows<KIND, 8, false>>(grid, 256, lds(8), st, a);
+    if (a.W <= 16) return launch_lds<k_scan_binary_rows<KIND, 16, false>>(grid, 256, lds(16), st, a);
+    if (a.W <= 32) return launch_lds<k_scan_binary_rows<KIND, 32, false>>(grid, 256, lds(32), st, a);
+    return launch_lds<k_scan_binary_rows<KIND, 64, false>>(grid, 256, lds(64), st, a);
 }
 static int launch_scan_binary_rows(const BinArgs& a, int metric, uint32_t grid, hipStream_t st) {
     switch (metric) {
@@ -1888,7 +1741,7 @@ static inline uint32_t sel_lds_bytes(uint32_t cap, uint32_t nq = 0) {
     // (a widened pass — thousands of queries per launch, the k-means assignment — is bound by how many of its one-per-query workgroups
     // fit a CU: no scratch there, 4096 key slots stay 32 KB instead of 80 KB)
     if (nq > 512) return cap * 8u;
-    static const size_t extra = []() { const char* e = getenv("LYNSE_HIP_SEL_SCRATCH_KB"); return (size_t)(e ? atoi(e) : 48) * 1024; }();   // (0: the direct loads, A/B)
+    static const size_t extra = (size_t)env_int("LYNSE_HIP_SEL_SCRATCH_KB", 48) * 1024;   // (0: the direct loads, A/B)
     return (uint32_t)std::min<size_t>((size_t)cap * 8 + extra, SEL_LDS_MAX);
 }
 
@@ -1901,6 +1754,30 @@ static int get_event(lynse_hip_flat* h, size_t idx, hipEvent_t* out) {
     *out = cur(h).ev_pool[idx];
     return LYNSE_OK;
 }
+
+// The knobs of run_chunk that more than one place reads.
+// LYNSE_HIP_DENSE: 1 / 0 = the threshold stages always / never on the DENSE epilogue (kernels.h), unset = the rule of each pass.  Read once
+// per process by the scan stages of run_chunk (dense_env()); read per call where the fused sample stage asks whether DENSE is off at
+// all (dense_env_now()) — both as before.
+static int dense_env_now() { return env_int("LYNSE_HIP_DENSE", -1); }
+static int dense_env() { static const int v = dense_env_now(); return v; }
+// LYNSE_HIP_DEBUG_FLAGS: ScanArgs::debug_flags of every scan launch (bit 1: no emit-all, bit 6: phase stamps, bits 8..12: the timing
+// variants of an EXPERIMENTS build); read once per process
+static int debug_flags_env() { static const int v = env_int("LYNSE_HIP_DEBUG_FLAGS", 0); return v; }
+// LYNSE_HIP_NO_LANE_MAX=1: the sample stage emits every score instead of one key per lane (A/B); read once per process
+static int no_lane_max_env() { static const int v = env_int("LYNSE_HIP_NO_LANE_MAX", 0); return v; }
+// LYNSE_HIP_I8C_CS=0: the Hoelder terms of the int8 bound alone, without the Cauchy-Schwarz terms (A/B); read once per process
+static bool i8c_cs_on() { static const bool v = env_on("LYNSE_HIP_I8C_CS", true); return v; }
+// LYNSE_HIP_SEL_STAMPS (set): phase stamps of the selects (lynse_hip_debug_sel_stamps / _ivf_sel_stamps); read per call
+static bool sel_stamps_on() { return env_str("LYNSE_HIP_SEL_STAMPS") != nullptr; }
+// LYNSE_HIP_FUSED=0: no fused single-launch search (k_small_search), FLAT and IVF (A/B); read once per process
+static int fused_env() { static const int v = env_int("LYNSE_HIP_FUSED", 1); return v; }
+#ifdef LYNSE_EXPERIMENTS
+// LYNSE_HIP_SCAN_W16: the wave tiling of the 256 x 256 tile — of the f16 kernel (default -1: by metric) and of the superseded f32 ring
+// kernel (default 2); each read once per process
+template <int DFLT>
+static int scan_w16_env() { static const int v = env_int("LYNSE_HIP_SCAN_W16", DFLT); return v; }
+#endif
 
 static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked = false);   // (defined with the other int8-pass rules)
 // lynse_hip_flat_coarse_scores: one emit-all stage over the whole (small) shard, then stop — the candidate buffer then holds the
@@ -1946,15 +1823,15 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     const uint32_t nslab = bin_mfma ? h->ld_bpm / 128 : i8c ? ((aug ? h->dim + h->aug_cols : h->dim) + 127) / 128 : glds ? (h->dim + GL_BK - 1) / GL_BK : (h->dim + SCAN_BK - 1) / SCAN_BK;  // h16: HK == SCAN_BK == 64
     const bool small = nq <= SCAN_BQ_SMALL;
     // mid-size batches on the int8 codes: 33..64 queries -> the 128 x 64 tiling, 65..128 -> the 256 x 128 tiling (LYNSE_HIP_MID_TILINGS=0: off)
-    const int mid_env = []() { const char* e = getenv("LYNSE_HIP_MID_TILINGS"); return e ? atoi(e) : 1; }();   // (read per call: tests flip it)
+    const int mid_env = env_int("LYNSE_HIP_MID_TILINGS", 1);   // (read per call: tests flip it)
     // ... unless the query-stationary tiling takes the batch (768-column codes of the IP / cosine / plain-L2 forms; a row bitmask only on
     // the IP / cosine form): waves without queries skip their MFMAs there, and it beats both mid tilings from 33 queries on (10M x 768, IP:
     // 40 / 64 / 100 / 128 queries 1.28 / 1.32 / 1.48 / 1.49 -> 1.22 / 1.25 / 1.29 / 1.31 ms; L2 1.39 / 1.43 / 1.81 / 1.89 -> 1.34 / 1.38 / 1.57 /
     // 1.62).  LYNSE_HIP_QS_MID=0: the mid tilings (A/B, tests; read per call)
-    const bool qs_mid = []() { const char* e = getenv("LYNSE_HIP_QS_MID"); return !e || atoi(e) != 0; }() && qs_variant() >= 1 && qs_variant() <= 3 && i8c && !bin_mfma &&
+    const bool qs_mid = env_on("LYNSE_HIP_QS_MID", true) && qs_variant() >= 1 && qs_variant() <= 3 && i8c && !bin_mfma &&
                         !small && !row_ids && h16 && !aug && qs_width_ok(h->ld8, (h->dim + 127) / 128, mask != nullptr) && !(l2n && (h->dim + 127) / 128 == 8) && nq <= 256 &&   // (plain-L2: not on the 32-row tiles of 1024 columns)
                         (h->ld8 == 768 || nq > 64) &&   // (narrower rows: the 128 x 64 tiling keeps 33..64 queries — 6M x 256, 40 queries: 0.34 ms against 0.37)
-                        (!mask || (!l2n && qs_variant() != 2 && []() { const char* e = getenv("LYNSE_HIP_QS_MASKED"); return !e || atoi(e) != 0; }()));
+                        (!mask || (!l2n && qs_variant() != 2 && qs_masked_on()));
     const bool mid_ok = mid_env && !qs_mid && i8c && !bin_mfma && !small && !row_ids && h16 && (!mask || (aug ? h->ld8a : h->ld8) % 128 == 0);
     const bool mid64 = mid_ok && nq <= 64, mid128 = mid_ok && !mid64 && nq <= 128;
     const bool narrow = small || mid64;   // 128-row tiles
@@ -1967,13 +1844,9 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     if (mask || row_ids) ip_form = LYNSE_IPFORM_SINGLE;
     if (h->dtype == LYNSE_DTYPE_F16) ip_form = LYNSE_IPFORM_F16SEQ;  // every f16 path of the reference uses the sequential kernels  // search_filtered scores every row with the single-row kernels (flat_mmap.rs:553-560)
 
-    static std::atomic<bool> sel_attr = false;
-    if (!sel_attr) {
-        LY_TRY(set_max_lds(k_select<SEL_NT>, SEL_LDS_MAX));
-        LY_TRY(set_max_lds(k_final<SEL_NT>, SEL_LDS_MAX));
-        LY_TRY(set_max_lds(k_select_final<SEL_NT>, SEL_LDS_MAX));
-        sel_attr = true;
-    }
+    LY_TRY(ensure_lds<k_select<SEL_NT>>(SEL_LDS_MAX));
+    LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
+    LY_TRY(ensure_lds<k_select_final<SEL_NT>>(SEL_LDS_MAX));
 
     const uint32_t sts_ld8 = cosq ? h->ld8 : h->ld8;
     const bool sts = allow_sts && sts_env_on() && level == 0 && i8c && !bin_mfma && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids && h16 &&
@@ -1999,8 +1872,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         p.Q = Qf; p.D = h->dim; p.qpad = qpad; p.nslab = nslab; p.nq = nq; p.mins = aug ? h->sq8a_mins : (cosq ? h->sq8c_mins : h->sq8_mins);
         p.scales = aug ? h->sq8a_scales : (cosq ? h->sq8c_scales : h->sq8_scales);
         p.a1 = aug ? h->sq8a_a1 : (cosq ? h->sq8c_a1 : h->sq8_a1); p.vmax = h->vmax;
-        static const bool cs_env = []() { const char* e = getenv("LYNSE_HIP_I8C_CS"); return !e || atoi(e) != 0; }();   // (0: the Hoelder terms alone, A/B)
-        if (cs_env) { p.a2sq = aug ? h->sq8a_a2sq : (cosq ? h->sq8c_a2sq : h->sq8_a2sq); p.eps2 = aug ? h->sq8a_eps2 : (cosq ? h->sq8c_eps2 : h->sq8_eps2); } p.cosine = cosq ? 1 : 0; p.img = reinterpret_cast<int8_t*>(w.Q16); p.aug = aug ? (int)h->aug_cols : 0; p.l2n = l2n ? 1 : 0;
+        if (i8c_cs_on()) { p.a2sq = aug ? h->sq8a_a2sq : (cosq ? h->sq8c_a2sq : h->sq8_a2sq); p.eps2 = aug ? h->sq8a_eps2 : (cosq ? h->sq8c_eps2 : h->sq8_eps2); } p.cosine = cosq ? 1 : 0; p.img = reinterpret_cast<int8_t*>(w.Q16); p.aug = aug ? (int)h->aug_cols : 0; p.l2n = l2n ? 1 : 0;
         p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
         if (sts) {   // seed the partition maxima of the self-tightening scan from a few sample rows (valid thresholds from the first tile on)
@@ -2023,23 +1895,22 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
 
     // the sampled plan needs the strided-tile support of k_scan_h16; every other kernel starts at level 1
     const uint32_t plan_tile = (h16 && !binary) ? (narrow ? 128u : 256u) : 0u;
-    static const int no_sample = []() { const char* e = getenv("LYNSE_HIP_NO_SAMPLE_PLAN"); return e ? atoi(e) : 0; }();
+    static const int no_sample = env_int("LYNSE_HIP_NO_SAMPLE_PLAN", 0);
     // wave tiling of the 256 x 256 tile (measured on MI355X, 10M x 768, 256 queries): IP is fastest with <2,4,4,2> and the
     // 3+2-stage split rings, L2 / cosine (norm ring in LDS, more registers in the epilogue) with <4,2,2,4> and 2+2 stages
 #ifdef LYNSE_EXPERIMENTS
-    static const int w16env = []() { const char* e = getenv("LYNSE_HIP_SCAN_W16"); return e ? atoi(e) : -1; }();
+    const int w16env = scan_w16_env<-1>();
 #else
     constexpr int w16env = -1;  // (the product build compiles each tiling only for the metrics it is the default of)
 #endif
     const bool filt = mask != nullptr || row_ids != nullptr;
     // (the subset-filter variants of <2,4,4,2> spill 96 B into the MFMA loop: masked 10M x 768 scan 7.5 ms vs 4.9 ms with <4,2,2,4>)
     const int waves16 = l2n ? 0 : i8c ? 3 : (w16env >= 0 ? w16env : ((metric == M_IP && !filt) ? 3 : 0));
-    static const int no_lane_max0 = []() { const char* e = getenv("LYNSE_HIP_NO_LANE_MAX"); return e ? atoi(e) : 0; }();
     // the subset-filter kernel variants carry no lane-max code (registers)
     // (k <= 16: the best tile alone supplies k keys, so even a shard sorted by score gets a tight threshold from its best
     // sample tile; up to k = 128 the sample as a whole supplies >= 8 k keys — a clustered shard may then overflow the first
     // stage and fall back to the contiguous plan)
-    const bool can_threshold_only = h16 && !binary && !filt && !no_lane_max0 && k <= 128;
+    const bool can_threshold_only = h16 && !binary && !filt && !no_lane_max_env() && k <= 128;
     Stage assign_stage{0u, (uint32_t)h->n};   // (tl_assign) every 256-row tile of the store as a "sample" tile: lane-max keys, no threshold
     assign_stage.sample_tiles = (uint32_t)((h->n + 255) / 256);
     assign_stage.sample_stride = 256;
@@ -2055,9 +1926,8 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     // sampled plan: the sample stage only has to produce a threshold -> one key per lane (its best row) instead of every
     // score, as long as that leaves comfortably more than k keys per query (2 WR keys per tile and query)
     const uint32_t sample_keys_per_tile = (small || mid64 || mid128 || waves16 != 0) ? 16u : 8u;  // 2 WR lanes per query and tile x their best 2 rows (WR = 4: 16, <4,2,2,4>: 8)
-    static const int no_lane_max = []() { const char* e = getenv("LYNSE_HIP_NO_LANE_MAX"); return e ? atoi(e) : 0; }();
     // k <= keys per tile: the best sample tile alone supplies k keys (a shard sorted by score still gets a tight threshold)
-    const bool sample_threshold_only = h16 && !binary && !filt && sample.sample_tiles && !no_lane_max && sample_keys_per_tile &&
+    const bool sample_threshold_only = h16 && !binary && !filt && sample.sample_tiles && !no_lane_max_env() && sample_keys_per_tile &&
                                        (k <= sample_keys_per_tile || (uint64_t)sample.sample_tiles * sample_keys_per_tile >= 8ull * k);
     // Fused sample stage (k_scan_h16<.., FS>, LYNSE_HIP_FUSED_SAMPLE=1; OFF by default): the sample tiles are scored by the
     // workgroups of the FIRST threshold stage (one each) and the grid agrees on the thresholds inside that launch — no
@@ -2066,16 +1936,15 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     // than the two launches it replaces (MI355X, 1.25M x 768 x 256: 366 us against 33 + 26 + 261 us; s_memtime stamps,
     // scripts/dbg_fs_stamps.py: first tile 32 us, hand-over 1 27 us, select 15 us, hand-over 2 17 us, restart): a grid-wide
     // hand-over drains the LDS-DMA ring of every CU and idles the chip twice, which costs more than a kernel boundary.
-    const int fs_env = []() { const char* e = getenv("LYNSE_HIP_FUSED_SAMPLE"); return e ? atoi(e) : 0; }();   // (read per call: tests flip it)
-    static const int dbg_env = []() { const char* e = getenv("LYNSE_HIP_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    const bool fs = fs_env != 0 && !dbg_env && i8c && !aug && !cosq && !l2n && !bin_mfma && !mid64 && !mid128 && h->ld8 % 128 == 0 && sample_threshold_only && plan.size() >= 2 && k <= 32 &&
+    const int fs_env = env_int("LYNSE_HIP_FUSED_SAMPLE", 0);   // (read per call: tests flip it)
+    const bool fs = fs_env != 0 && !debug_flags_env() && i8c && !aug && !cosq && !l2n && !bin_mfma && !mid64 && !mid128 && h->ld8 % 128 == 0 && sample_threshold_only && plan.size() >= 2 && k <= 32 &&
                     sample.sample_tiles == (uint32_t)h->num_cu && (plan[1].r1 - plan[1].r0 + 255) / 256 >= (uint32_t)h->num_cu &&
                     (uint64_t)k * 50000ull > (uint64_t)sample.sample_tiles * plan_tile &&   // (the stage behind the sample runs the DENSE epilogue)
-                    []() { const char* e = getenv("LYNSE_HIP_DENSE"); return !e || atoi(e) != 0; }();
+                    dense_env_now() != 0;
     bool plan_used_segments = false, plan_used_qs = false, plan_qs_sample = false, plan_used_qh = false;
     // the select behind the last stage + exact rescoring + final order in one launch (k_select_final); LYNSE_HIP_FUSED_TAIL=0:
     // the three separate kernels (A/B)
-    const int fused_tail_env = []() { const char* e = getenv("LYNSE_HIP_FUSED_TAIL"); return e ? atoi(e) : 1; }();   // (read per call: tests flip it)
+    const int fused_tail_env = env_int("LYNSE_HIP_FUSED_TAIL", 1);   // (read per call: tests flip it)
     const bool fused_tail = fused_tail_env != 0 && !plan.empty();
     SelectArgs sa_last{};
     for (size_t si = 0; si < plan.size(); ++si) {
@@ -2097,7 +1966,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             b.P = h->packed; b.W = h->words; b.row0 = s.r0; b.row1 = s.r1; b.QW = w.QW; b.nq = nq;
             b.thr = w.thr; b.cand = w.cand; b.count = w.count; b.cap = w.cap; b.emit_all = emit_all ? 1 : 0;
             b.mask = mask;
-            static const int rows_minq = []() { const char* e = getenv("LYNSE_HIP_BIN_ROWS_MINQ"); return e ? atoi(e) : 1; }();
+            static const int rows_minq = env_int("LYNSE_HIP_BIN_ROWS_MINQ", 1);
             if (h->words > 16u * BIN_MAX_CHUNKS) {  // wider than 4096 bits: the generic strided kernel
                 const uint32_t groups = (s.r1 - s.r0 + 31) / 32;
                 const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(groups, (uint32_t)h->num_cu * 8));
@@ -2128,7 +1997,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             a.row_ids = row_ids;
             a.tile_stride = s.sample_stride;  // 0 = contiguous
             if (!s.sample_tiles && sample.sample_tiles && !sample_threshold_only) { a.skip_stride = sample.sample_stride; a.skip_tiles = sample.sample_tiles; }
-            static const int big_rows = []() { const char* e = getenv("LYNSE_HIP_SCAN_BR"); return e ? atoi(e) : 256; }();
+            static const int big_rows = env_int("LYNSE_HIP_SCAN_BR", 256);
             uint32_t tile_rows = (glds && !small && big_rows == 256) ? 256u : (uint32_t)SCAN_BR;
             if (h16) tile_rows = narrow ? 128u : 256u;
             a.V16 = h->rows16; a.ld16 = h->ld16;
@@ -2141,7 +2010,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             // sampled plan: the sample stage only has to produce a threshold -> one key per lane (its best row) instead of
             // every score, as long as that leaves at least k keys per query
             if (sample_threshold_only && s.sample_tiles) a.emit_all = 2;
-            static const int dbg = []() { const char* e = getenv("LYNSE_HIP_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
+            const int dbg = debug_flags_env();
             a.debug_flags = dbg;
             if (dbg & 2) a.emit_all = 0;
             if (dbg & 64) {  // phase timing of the LAST (largest) stage: 256 blocks x 8 waves x 4 counters, printed by the host
@@ -2181,11 +2050,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                 // DENSE epilogue while the threshold is loose (kernels.h): the int8 margin keeps ~5x the rows an exact threshold
                 // would, so a 32-query x 64-row block holds a survivor with probability ~ 2048 * 5 k / rows-seen-before; above
                 // ~0.2 one integer compare per accumulator beats level 1 + (mostly) level 2.  Segments are per wave half then.
-                static const int dense_env = []() { const char* e = getenv("LYNSE_HIP_DENSE"); return e ? atoi(e) : -1; }();
                 const uint64_t seen_before = s.sample_tiles ? 0 : (sample.sample_tiles ? std::max<uint64_t>((uint64_t)sample.sample_tiles * plan_tile, s.r0) : s.r0);
                 a.dense = (!a.emit_all && a.ld16 % 128 == 0 && seen_before &&
-                           (filt || (dense_env >= 0 ? dense_env != 0 : (uint64_t)k * 50000ull > seen_before))) ? 1 : 0;   // (masked: DENSE is the one epilogue compiled with the mask)
-                const bool ag = getenv("LYNSE_HIP_AG") && atoi(getenv("LYNSE_HIP_AG")) && a.ld16 % 128 == 0 && !a.emit_all && !fs_stage && !filt && !bin_mfma;
+                           (filt || (dense_env() >= 0 ? dense_env() != 0 : (uint64_t)k * 50000ull > seen_before))) ? 1 : 0;   // (masked: DENSE is the one epilogue compiled with the mask)
+                const bool ag = ag_env() && a.ld16 % 128 == 0 && !a.emit_all && !fs_stage && !filt && !bin_mfma;
                 if (sts) {
                     a.dyn_thr = w.dyn; a.dyn_marg = w.dyn + w.qcap; a.dyn_slot = w.dyn + 2 * (size_t)w.qcap; a.dyn_ks = k;
                     a.dyn_warm = h->n >= 4000000ull ? 4u : 2u;   // tiles per workgroup that only feed the maxima first (scanned again at the end)
@@ -2218,7 +2086,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                 if (fs_stage) {
                     a.fs_stride = sample.sample_stride; a.fs_rows = (uint32_t)h->n; a.gsync = w.gsync; a.Qf = Qf; a.marg2 = w.marg2;
                     a.thr_out = w.thr; a.k = k; a.ip_form = ip_form; a.metric = metric;
-                    if (getenv("LYNSE_HIP_FS_STAMPS")) a.debug_flags |= 128;
+                    if (env_str("LYNSE_HIP_FS_STAMPS")) a.debug_flags |= 128;
                 }
                 LY_TRY(launch_scan_i8c(a, launch_grid, st, fs_stage, filt, bin_mfma, qs));
                 }
@@ -2243,11 +2111,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                 } else {
                     const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
                     // DENSE epilogue (<4,2,2,4>, L2 / cosine, unfiltered; kernels.h).  Its segments are per wave half.
-                    static const int dense_env = []() { const char* e = getenv("LYNSE_HIP_DENSE"); return e ? atoi(e) : -1; }();
                     const uint64_t seen_before = s.sample_tiles ? 0 : (sample.sample_tiles ? std::max<uint64_t>((uint64_t)sample.sample_tiles * plan_tile, s.r0) : s.r0);
                     // (since the grouped branches + shared, prefetched norm loads of the DENSE epilogue it beats the two-level filter
                     // at every threshold tightness measured: 1M x 128 and 4M x 128 / 768, k = 10 and 100)
-                    a.dense = (!a.emit_all && waves16 == 0 && metric != M_IP && !filt && seen_before && (dense_env >= 0 ? dense_env != 0 : true)) ? 1 : 0;
+                    a.dense = (!a.emit_all && waves16 == 0 && metric != M_IP && !filt && seen_before && (dense_env() >= 0 ? dense_env() != 0 : true)) ? 1 : 0;
                     if (!a.emit_all) seg_geometry(grid, a.dense ? 4 : ((waves16 == 3 || waves16 == 2) ? 4 : 2), &a.nseg, &a.seg);
                     if (qchunks > 1 && !(plan.size() == 1 && (a.emit_all == 1 || (tl_assign && a.emit_all == 2))))
                         return set_error(LYNSE_ERR_INTERNAL, "the widened pipeline runs single-stage emit-all plans only");
@@ -2269,7 +2136,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
                     LY_TRY((launch_scan_glds<4, 2, 2, 3, 4>(a, metric, scale, grid, st)));
                 } else if (tile_rows == 256) {
-                    static const int gw16 = []() { const char* e = getenv("LYNSE_HIP_SCAN_W16"); return e ? atoi(e) : 2; }();
+                    const int gw16 = scan_w16_env<2>();
                     const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
                     if (gw16 == 3) LY_TRY((launch_scan_glds<1, 8, 8, 1, 3>(a, metric, scale, grid, st)));
                     else if (gw16 == 0) LY_TRY((launch_scan_glds<4, 2, 2, 4, 3>(a, metric, scale, grid, st)));
@@ -2310,7 +2177,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         sa.k = k; sa.cap = w.cap; sa.keep_max = w.cap / 2; sa.metric = key_metric; sa.ip_form = ip_form;   // (bin_mfma: best-first +-1 dot products; aug: negated squared L2)
         sa.neg_metric1 = (aug || cosq) ? metric + 1 : 0;
         sa.exact = binary ? 1 : 0;
-        static const int tighten_env = []() { const char* e = getenv("LYNSE_HIP_TIGHTEN"); return e ? atoi(e) : 1; }();
+        static const int tighten_env = env_int("LYNSE_HIP_TIGHTEN", 1);
         // (worth its ~k exact rescorings per query and stage where the margin is wide — the int8 pass — or k is small)
         sa.tighten = (!binary && tighten_env && (i8c || k <= 32)) ? 1 : 0;
         sa.drop_sentinels = (mask && emit_all) ? 1 : 0;
@@ -2323,9 +2190,9 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         sa.Qf = Qf; sa.V = score_rows(h); sa.ld = score_ld(h); sa.D = h->dim;
         sa.candB = w.candB; sa.segcnt = w.segcnt; sa.seg = st_seg; sa.nseg = st_nseg;
         sa.abort_word = fs_stage ? w.gsync + 2 : nullptr;
-        if (getenv("LYNSE_HIP_SEL_STAMPS"))   // debugging: phase stamps of the select behind stage si ([stage][query][8] behind the fs stamps)
+        if (sel_stamps_on())   // debugging: phase stamps of the select behind stage si ([stage][query][8] behind the fs stamps)
             sa.stamps = reinterpret_cast<unsigned long long*>(w.gsync + 64) + (size_t)si * 256 * 8;
-        if (fs_stage && getenv("LYNSE_HIP_DEBUG_FS")) return LYNSE_OK;   // debugging: stop behind the fused stage (lynse_hip_debug_workspace)
+        if (fs_stage && env_str("LYNSE_HIP_DEBUG_FS")) return LYNSE_OK;   // debugging: stop behind the fused stage (lynse_hip_debug_workspace)
         if (fused_tail && si + 1 == plan.size()) { sa_last = sa; continue; }  // the last select runs inside k_select_final
         // (round 5, tried: the survivors of the last select handed to the final rescoring in LDS instead of through cand[q] — a store, its
         // acknowledgement and a load less in the tail's chain: 10M 1.8216 / 1.8213 / 1.8527 against 1.8206 / 1.8455 / 1.8381 ms, shard
@@ -2357,7 +2224,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     if (hdr_direct) { fa.h_hdr = w.h_hdr; fa.hdr_q = w.qcap; }
     if (fused_tail) {
         TailArgs ta{sa_last, fa};
-        ta.s.hand_exact = getenv("LYNSE_HIP_HAND_EXACT") ? atoi(getenv("LYNSE_HIP_HAND_EXACT")) : 1;   // (0: the final rescoring always reads its rows, A/B)
+        ta.s.hand_exact = env_int("LYNSE_HIP_HAND_EXACT", 1);   // (0: the final rescoring always reads its rows, A/B)
         ta.s.lds_bytes = ta.f.lds_bytes = sel_lds_bytes(w.cap, nq);
         hipLaunchKernelGGL(k_select_final<SEL_NT>, dim3(nq), dim3(SEL_NT), ta.s.lds_bytes, st, ta);
         LY_HIP(hipGetLastError());
@@ -2429,9 +2296,8 @@ static int flat_assign_top1_device(lynse_hip_flat* h, const float* d_q, uint64_t
 // The fused single-launch search (k_small_search): a few queries over a shard small enough that the eight dependent
 // launches of the staged pipeline, not the bytes, are the cost.  Exact scores straight from the f32 rows.
 static bool small_path_ok(const lynse_hip_flat* h, uint64_t nq, uint32_t kk, int metric, bool filtered) {
-    static const int env = []() { const char* e = getenv("LYNSE_HIP_FUSED"); return e ? atoi(e) : 1; }();
-    static const uint64_t max_bytes = []() { const char* e = getenv("LYNSE_HIP_FUSED_MAX_MB"); return (uint64_t)(e ? atoi(e) : 64) << 20; }();
-    return env && !h->no_fused && metric <= M_COS && !filtered && h->dtype == LYNSE_DTYPE_F32 && !h->packed_only && nq <= (uint64_t)SMALL_MAX_Q &&
+    static const uint64_t max_bytes = (uint64_t)env_int("LYNSE_HIP_FUSED_MAX_MB", 64) << 20;
+    return fused_env() && !h->no_fused && metric <= M_COS && !filtered && h->dtype == LYNSE_DTYPE_F32 && !h->packed_only && nq <= (uint64_t)SMALL_MAX_Q &&
            kk <= (uint32_t)SMALL_MAX_K && (uint64_t)h->n * h->ld * 4 * nq <= max_bytes &&
            (size_t)((h->dim + 3) / 4 * 4) * 4 + (size_t)128 * 1024 + 64 <= 150u * 1024u;
 }
@@ -2466,11 +2332,10 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         const uint64_t passes = (n_scan + (uint64_t)grid * 128 - 1) / ((uint64_t)grid * 128);
         if (passes > 1) grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, (n_scan + 128 * passes - 1) / (128 * passes)));
     }
-    if (const char* ge = getenv("LYNSE_HIP_SMALL_GRID")) grid = std::max(1u, std::min<uint32_t>(grid, (uint32_t)atoi(ge)));   // development
+    if (const char* ge = env_str("LYNSE_HIP_SMALL_GRID")) grid = std::max(1u, std::min<uint32_t>(grid, (uint32_t)atoi(ge)));   // development
     auto pow2_at_least = [](uint32_t v) { uint32_t p = 2; while (p < v) p <<= 1; return p; };
     const size_t lds = (size_t)((h->dim + 3) / 4 * 4) * 4 + (size_t)SMALL_NT * 8 + (size_t)pow2_at_least(std::min<uint32_t>(k, grid) * k) * 8 + 64;  // the query, the wave lists (later the heads of the merge), the merge's candidate keys
-    static std::atomic<bool> small_attr = false;
-    if (!small_attr) { LY_TRY(set_max_lds(k_small_search, 160 * 1024 - 1024)); small_attr = true; }
+    LY_TRY(ensure_lds<k_small_search>(160 * 1024 - 1024));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timed = tl_prof && ev_used && scan_events;
     if (timed) {
@@ -2478,7 +2343,7 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         LY_TRY(get_event(h, (*ev_used)++, &e1));
         LY_HIP(hipEventRecord(e0, st));
     }
-    static const bool small_dbg = []() { const char* e = getenv("LYNSE_HIP_SMALL_DBG"); return e && atoi(e) != 0; }();
+    static const bool small_dbg = env_on("LYNSE_HIP_SMALL_DBG", false);
     static unsigned long long* d_dbg = nullptr;
     if (small_dbg) {   // development: where the time of the fused search goes (stderr; synchronises)
         if (!d_dbg) LY_HIP(hipMalloc(&d_dbg, (size_t)SMALL_NT * 4 * 8));
@@ -2722,12 +2587,8 @@ static int run_chunk_sq8(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t ou
     const bool ip = metric == M_IP;
     const int m1 = ip ? M_IP : M_L2;  // cosine ranks the codes by squared L2 too (:5887-5890)
     const uint32_t nslab = (h->dim + 127) / 128, qpad = SCAN_BQ_LARGE;
-    static std::atomic<bool> attr = false;
-    if (!attr) {
-        LY_TRY(set_max_lds(k_select<SEL_NT>, SEL_LDS_MAX));
-        LY_TRY(set_max_lds(k_final<SEL_NT>, SEL_LDS_MAX));
-        attr = true;
-    }
+    LY_TRY(ensure_lds<k_select<SEL_NT>>(SEL_LDS_MAX));
+    LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
     LY_HIP(hipMemsetAsync(w.Q16, 0, (size_t)nslab * qpad * 128, st));
     hipLaunchKernelGGL(k_sq8_prep_queries, dim3(nq), dim3(256), 0, st, w.Qf, h->dim, qpad, nslab, h->sq8_mins, h->sq8_scales,
                        reinterpret_cast<int8_t*>(w.Q16), w.qn2, w.thr, w.count, w.overflow, ip ? 1 : 0);
@@ -2745,17 +2606,8 @@ static int run_chunk_sq8(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t ou
         a.candB = w.candB; a.segcnt = w.segcnt;
         if (!a.emit_all) seg_geometry(grid, 2, &a.nseg, &a.seg);
         constexpr size_t lds = (size_t)(2 * 256 + 2 * 256) * 128 + 3 * 1024;
-        static std::atomic<bool> a2[2] = {false, false};
-        if (ip) {
-            auto kern = k_scan_h16<4, 2, 2, 4, M_IP, 2, 2, 2, false, true, 0, false, 1>;
-            if (!a2[0]) { LY_TRY(set_max_lds(kern, lds)); a2[0] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        } else {
-            auto kern = k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, true, 0, false, 1>;
-            if (!a2[1]) { LY_TRY(set_max_lds(kern, lds)); a2[1] = true; }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-        }
-        LY_HIP(hipGetLastError());
+        if (ip) LY_TRY((launch_lds<k_scan_h16<4, 2, 2, 4, M_IP, 2, 2, 2, false, true, 0, false, 1>>(grid, 512, lds, st, a)));
+        else LY_TRY((launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, true, 0, false, 1>>(grid, 512, lds, st, a)));
         SelectArgs sa{};
         sa.cand = w.cand; sa.count = w.count; sa.overflow = w.overflow; sa.thr = w.thr; sa.marg2 = w.marg2;
         sa.k = n_cand; sa.cap = w.cap; sa.keep_max = w.cap / 2; sa.metric = m1; sa.ip_form = LYNSE_IPFORM_SINGLE;
@@ -2772,8 +2624,7 @@ static int run_chunk_sq8(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t ou
     fa.exact = 0; fa.Qf = w.Qf; fa.V = h->rows; fa.ld = h->ld; fa.D = h->dim;
     fa.row_stride = h->row_stride; fa.row_offset = h->row_offset;
     fa.out_rows = w.out_rows; fa.out_dists = w.out_dists; fa.out_counts = w.out_counts; fa.pool_total = nullptr;
-    const char* dbg = getenv("LYNSE_HIP_SQ8_PASS1");  // tests: return the pass-1 ranking (integer scores) instead of rescoring
-    if (pass1_only || (dbg && atoi(dbg))) {
+    if (pass1_only || env_on("LYNSE_HIP_SQ8_PASS1", false)) {   // (tests: return the pass-1 ranking (integer scores) instead of rescoring; read per call)
         fa.metric = m1;
     } else {
         hipLaunchKernelGGL(k_rescore_pool<256>, dim3(nq, nq >= 64 ? 4 : 32), dim3(256), 0, st, fa);
@@ -2834,7 +2685,7 @@ extern "C" int lynse_hip_flat_search_sq8_f32(lynse_hip_flat* h, const float* que
 // certified int8 coarse pass: FLAT-IP batches of 33..256 queries over an f32 shard (auto: shards of >= 64K rows;
 // LYNSE_HIP_COARSE=i8 / f16 forces / disables it); strikes: overflows so far (3 turn it off), -1 = data not finite
 static int coarse_env() {
-    static const int v = []() { const char* e = getenv("LYNSE_HIP_COARSE"); return !e ? 0 : (!strcmp(e, "i8") ? 2 : (!strcmp(e, "f16") ? 1 : 0)); }();
+    static const int v = []() { const char* e = env_str("LYNSE_HIP_COARSE"); return !e ? 0 : (!strcmp(e, "i8") ? 2 : (!strcmp(e, "f16") ? 1 : 0)); }();
     return v;
 }
 // per-metric state of the certified int8 pass: IP reads the SQ8 codes of the rows, squared L2 the codes of the augmented rows
@@ -2846,7 +2697,7 @@ static std::atomic<int>& i8c_strike_counter(lynse_hip_flat* h, int metric) {
 // everything else (ragged widths, masked scans, IVF) on the codes of the AUGMENTED rows through the IP kernels.  nqc = 0: "not a FLAT
 // batch" (IVF): the augmented form.  LYNSE_HIP_L2_PLAIN=0: always the augmented form.
 static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked) {
-    static const int on = []() { const char* e = getenv("LYNSE_HIP_L2_PLAIN"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("LYNSE_HIP_L2_PLAIN", 1);
     // (1M x 128, k = 100: 0.244 ms on the f16 shadow, 0.277 on the codes with the <4,2,2,4> tiling and 0.291 with the query-stationary
     // L2 tiling (k_scan_qs<1,4,1,6,.., MET = 1>, built and measured in round 4: at k = 100 the first threshold lets 0.8 % of all
     // (row, query) pairs through and the scan is bound by the emission of ~8000 keys per query, not by the tiling) — from 256
@@ -2873,7 +2724,7 @@ static bool i8c_eligible(const lynse_hip_flat* h, int metric, bool filtered, uin
     // masked int8 scan (whole 128-column slabs only)
     // view: a row-range view of search_large_k (h->n is the range): the SQ8 codes belong to the whole shard
     const int strikes = (metric == M_L2 ? h->i8c_strikes_l2 : (metric == M_COS ? h->i8c_strikes_cos : h->i8c_strikes)).load();
-    static const int l2_off = []() { const char* e = getenv("LYNSE_HIP_COARSE_L2"); return e && !strcmp(e, "f16") ? 1 : 0; }();
+    static const int l2_off = []() { const char* e = env_str("LYNSE_HIP_COARSE_L2"); return e && !strcmp(e, "f16") ? 1 : 0; }();
     // squared L2 streams round_up(dim + 1, 128) bytes of augmented codes per row against 2 round_up(dim, 8) of the f16 shadow and
     // rescoring pools ~10x wider: it pays from ~256 dimensions on (MI355X: 10M x 768 x 256 3.97 -> 2.81 ms; 1M x 128, k = 100
     // 0.24 -> 0.34 ms: stays on the f16 pass)
@@ -2885,7 +2736,7 @@ static bool i8c_eligible(const lynse_hip_flat* h, int metric, bool filtered, uin
     if (masked && metric != M_L2 && h->ld8 % 128 != 0) return false;
     // batches of <= 32 queries (the 128 x 32 tiling, HBM-bound: half the bytes = half the time) from 256K rows on — below, the scan
     // is a few tens of microseconds either way and the exact few-query kernel often answers alone (LYNSE_HIP_COARSE_SMALLQ=0: off)
-    static const int smallq = []() { const char* e = getenv("LYNSE_HIP_COARSE_SMALLQ"); return e ? atoi(e) : 1; }();
+    static const int smallq = env_int("LYNSE_HIP_COARSE_SMALLQ", 1);
     const bool nq_ok = nqc > SCAN_BQ_SMALL || (smallq && nqc >= 1 && (coarse_env() == 2 || h->n >= 262144));   // (masked small batches too)
     // (F16 shards too: the codes are built from the exactly decoded halves, the exact rescoring uses the f16 kernels' sequential
     // sums — any summation order is inside the bound's rounding term)
@@ -2894,7 +2745,7 @@ static bool i8c_eligible(const lynse_hip_flat* h, int metric, bool filtered, uin
     // rows and its margin ~2.5x tighter (round 5, 1M rows, 256 queries: 64 columns k = 10 / 100 0.222 / 0.318 -> 0.137 / 0.166 ms, 100 columns
     // 0.234 / 0.344 -> 0.169 / 0.188, 128 columns 0.163 / 0.273 -> 0.175 / 0.193; 100 queries 0.157 -> 0.127).  LYNSE_HIP_IP_LOWD=i8: the int8 pass
     // (read per call: tests; ivf: the list scans of an IVF store run the work-list tilings of k_scan_h16 either way — they keep the codes)
-    const char* lowd_env = getenv("LYNSE_HIP_IP_LOWD");
+    const char* lowd_env = env_str("LYNSE_HIP_IP_LOWD");
     const bool lowd_i8 = lowd_env && !strcmp(lowd_env, "i8");
     // (gated on the very shape predicate qh_scan_ok applies — a batch k_scan_qh would not take must not lose the int8 pass to the slower
     // 256 x 256 f16 tile; `view` = the gathered rows of a subset filter, a widened handle never comes here with <= 256 queries)
@@ -3013,8 +2864,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         // at ~3.6 TB/s, measured 10M x 768 x 256 with a 50 % subset: 2.2 ms)
         const bool mask_i8 = i8c_eligible(h, metric, false, std::min<uint64_t>(nq, QCHUNK), caller_holds_exclusive, true);
         const double c_scan = (mask_i8 ? (double)h->n * (double)h->dim / (nq <= SCAN_BQ_SMALL ? 6.5e12 : 3.6e12) : (double)h->n * row_b / rate) * chunks + 80e-6;
-        const char* fe = getenv("LYNSE_HIP_FILTER_STRATEGY");  // tests: 1 = gathered rows, 2 = masked scan (read per call)
-        const int force = fe ? atoi(fe) : 0;
+        const int force = env_int("LYNSE_HIP_FILTER_STRATEGY", 0);  // tests: 1 = gathered rows, 2 = masked scan (read per call)
         return (double)n_subset * row_b <= 8e9 && (force == 1 || (force == 0 && c_direct < c_scan));
     };
     if (!caller_holds_exclusive) {
@@ -3772,11 +3622,7 @@ static int merge_topk_device_impl(const void* d_blocks, uint64_t block_bytes, ui
     if (total > 8192) return set_error(LYNSE_ERR_UNSUPPORTED, "n_lists * k exceeds the merge kernel capacity (8192)");
     uint32_t np2 = 2;
     while (np2 < total) np2 <<= 1;
-    static std::atomic<bool> attr = false;
-    if (!attr) {
-        LY_TRY(set_max_lds(k_merge<256>, 8192 * 12));
-        attr = true;
-    }
+    LY_TRY(ensure_lds<k_merge<256>>(8192 * 12));
     MergeArgs a{};
     a.blocks = (const char*)d_blocks; a.block_bytes = block_bytes; a.rows_off = rows_off; a.dists_off = dists_off;
     a.counts_off = counts_off; a.n_lists = n_lists; a.k = k; a.metric = metric;
@@ -3800,7 +3646,7 @@ extern "C" int lynse_hip_merge_topk_device(const void* d_blocks, uint64_t block_
 // that died or returned early must not strand its peers inside hipStreamSynchronize for good.  The reference's coordinator retries a
 // shard once and errors (src/cluster.rs:243-261).  lynse_hip_set_wait_timeout_ms / LYNSE_HIP_WAIT_TIMEOUT_MS; 0 = 30 s for waits behind a
 // collective, unbounded for one shard alone.
-static std::atomic<uint32_t> g_wait_timeout_ms{[]() { const char* e = getenv("LYNSE_HIP_WAIT_TIMEOUT_MS"); return e ? (uint32_t)atoll(e) : 0u; }()};
+static std::atomic<uint32_t> g_wait_timeout_ms{[]() { const char* e = env_str("LYNSE_HIP_WAIT_TIMEOUT_MS"); return e ? (uint32_t)atoll(e) : 0u; }()};
 extern "C" int lynse_hip_set_wait_timeout_ms(uint32_t ms) { g_wait_timeout_ms.store(ms); return LYNSE_OK; }
 static uint32_t collective_timeout_ms() { const uint32_t to = g_wait_timeout_ms.load(); return to ? to : 30000u; }
 

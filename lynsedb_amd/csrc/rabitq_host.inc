@@ -68,13 +68,8 @@ static int rbq_check_handle(const lynse_hip_flat* h) {
 // the rotation kernels keep rb * P floats in LDS: past 64 KiB the limit is raised once per kernel
 static int rbq_rotation_lds(size_t bytes) {
     if (bytes <= 64u * 1024u) return LYNSE_OK;
-    static std::once_flag once;
-    static int rc = LYNSE_OK;
-    std::call_once(once, []() {
-        rc = set_max_lds(k_rbq_encode, PoolRerank::LDS_MAX);
-        if (rc == LYNSE_OK) rc = set_max_lds(k_rbq_query, PoolRerank::LDS_MAX);
-    });
-    return rc;
+    LY_TRY(ensure_lds<k_rbq_encode>(PoolRerank::LDS_MAX));
+    return ensure_lds<k_rbq_query>(PoolRerank::LDS_MAX);
 }
 
 // a fresh index of n rows in `out` (device buffers allocated, the codes zeroed, the sign words uploaded)

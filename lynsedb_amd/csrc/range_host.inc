@@ -103,20 +103,12 @@ extern "C" int lynse_hip_flat_search_range_f32(lynse_hip_flat* h, const float* q
     size_t lds = 0;
     if (!binary) {
         LY_TRY(range_plan(D, qc, &TQ, &R, &stride, &lds));
-        static std::once_flag once;
-        static int rc = LYNSE_OK;
-        std::call_once(once, []() { rc = set_max_lds(k_range_scan, PoolRerank::LDS_MAX); });
-        LY_TRY(rc);
+        LY_TRY(ensure_lds<k_range_scan>(PoolRerank::LDS_MAX));
     }
     const bool sort_dev = N <= 16384;
     if (sort_dev) {
-        static std::once_flag once;
-        static int rc = LYNSE_OK;
-        std::call_once(once, []() {
-            rc = set_max_lds(k_pool_select<256>, PoolRerank::LDS_MAX);
-            if (rc == LYNSE_OK) rc = set_max_lds(k_pool_select<1024>, PoolRerank::LDS_MAX);
-        });
-        LY_TRY(rc);
+        LY_TRY(ensure_lds<k_pool_select<256>>(PoolRerank::LDS_MAX));
+        LY_TRY(ensure_lds<k_pool_select<1024>>(PoolRerank::LDS_MAX));
     }
     hipStream_t st = cur(h).stream;
     const uint64_t mask_words = bitset_words ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;

@@ -71,15 +71,10 @@ struct PoolRerank {
             if (!select_dev || split > 1) LY_TRY(ivf_grow(&r.d_keys, &r.keys_cap, (size_t)qc * pool));
             if (select_dev && !dev_out) LY_TRY(ivf_grow(&r.d_out, &r.out_cap, ((size_t)qc * out_k * 12 + (size_t)qc * 4 + 7) / 8));
             a = PoolRerankArgs{V, n, ld, D, nullptr, r.d_prow, r.d_pcnt, pool, p2, metric, k_sel, out_k, nullptr, nullptr, nullptr, nullptr, nullptr};
-            static std::once_flag lds_once;
-            static int lds_rc = LYNSE_OK;
-            std::call_once(lds_once, []() {
-                lds_rc = set_max_lds(k_pool_rerank<true>, LDS_MAX);
-                if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_pool_rerank<false>, LDS_MAX);
-                if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_pool_select<256>, LDS_MAX);
-                if (lds_rc == LYNSE_OK) lds_rc = set_max_lds(k_pool_select<1024>, LDS_MAX);
-            });
-            LY_TRY(lds_rc);
+            LY_TRY(ensure_lds<k_pool_rerank<true>>(LDS_MAX));
+            LY_TRY(ensure_lds<k_pool_rerank<false>>(LDS_MAX));
+            LY_TRY(ensure_lds<k_pool_select<256>>(LDS_MAX));
+            LY_TRY(ensure_lds<k_pool_select<1024>>(LDS_MAX));
             if (timed)
                 for (hipEvent_t& e : r.ev)
                     if (!e) LY_HIP(hipEventCreate(&e));

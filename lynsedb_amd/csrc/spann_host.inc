@@ -59,8 +59,7 @@ static int spann_postings(lynse_hip_flat* cs, const float* d_rows, uint64_t n, u
     LY_HIP(hipMemcpy(&n_slow, d_nslow, 4, hipMemcpyDeviceToHost));
     if (n_slow) {   // rows that can meet a NaN / infinite rank: the sequential rule over every centroid
         const size_t lds = (size_t)nlist * 4 + (size_t)keep * 8;
-        static std::atomic<bool> attr = false;
-        if (!attr) { LY_TRY(set_max_lds(k_spann_slow, 16384 * 4 + SPANN_MAX_KEEP * 8)); attr = true; }
+        LY_TRY(ensure_lds<k_spann_slow>(16384 * 4 + SPANN_MAX_KEEP * 8));
         hipLaunchKernelGGL(k_spann_slow, dim3(n_slow), dim3(256), lds, 0, d_rows, dim, cs->rows, cs->ld, dim, nlist, keep, R, metric, d_slow,
                            d_lists, d_cnt);
         LY_HIP(hipGetLastError());

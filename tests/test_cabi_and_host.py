@@ -235,3 +235,21 @@ def test_lynse_hip_devices_env_selects_the_device_of_a_rank(monkeypatch):
         L.default_device()
     monkeypatch.delenv("LYNSE_HIP_DEVICES")
     assert L.default_device() == 4                      # LOCAL_RANK alone: one process per GPU
+
+
+def test_design_knob_table_lists_every_env_name():
+    """DESIGN §10 is the one table of the LYNSE_HIP_* environment knobs: its names are exactly the names the host code
+    (lynsedb_amd/csrc) and the Python mirror (lynsedb_amd/*.py) mention."""
+    name = re.compile(r"LYNSE_HIP_[A-Z0-9_]+")
+    pkg = ROOT / "lynsedb_amd"
+    used = set()
+    for f in [*sorted((pkg / "csrc").iterdir()), *sorted(pkg.glob("*.py"))]:
+        if f.is_file() and (f.suffix in (".hip", ".h", ".inc", ".py") or f.name == "Makefile"):
+            used |= set(name.findall(f.read_text()))
+    used.discard("LYNSE_HIP_ABI_VERSION")  # the ABI version macro of include/lynse_hip.h: no environment variable
+    design = (ROOT / "DESIGN.md").read_text()
+    section = design[design.index("## 10. Environment knobs"):design.index("\n## 11. ")]
+    rows = [ln.split("|")[1] for ln in section.splitlines() if ln.startswith("| `LYNSE_HIP_")]
+    table = [n for cell in rows for n in name.findall(cell)]
+    assert len(table) == len(set(table)), sorted(n for n in set(table) if table.count(n) > 1)
+    assert set(table) == used, (sorted(used - set(table)), sorted(set(table) - used))
