@@ -69,8 +69,36 @@ enum {
     LYNSE_METRIC_HAMMING = 3,
     LYNSE_METRIC_JACCARD = 4,
     LYNSE_METRIC_DICE = 5,
-    LYNSE_METRIC_TANIMOTO = 6
+    LYNSE_METRIC_TANIMOTO = 6,
+    LYNSE_METRIC_L1 = 7,          /* the additive metrics: see the contract below */
+    LYNSE_METRIC_CHEBYSHEV = 8,
+    LYNSE_METRIC_CANBERRA = 9,
+    LYNSE_METRIC_BRAY_CURTIS = 10
 };
+/* THE ADDITIVE METRICS (ids 7-10; the reference's `supports_flat_approx` group, src/distance/mod.rs:177-188, FLAT-L1 / -MANHATTAN /
+ * -CITYBLOCK / -CHEBYSHEV / -CHEBYCHEV / -LINF / -CANBERRA / -BRAY-CURTIS / -BRAYCURTIS, src/index/mod.rs:426-495).  All four are
+ * ascending.  The distance of a query a and a row b of D floats is the reference's AVX2 form bit for bit, all in f32, nothing fused:
+ *   shape  chunks = D / 8; lane g of an 8-lane accumulator takes the elements 8 i + g, i = 0 .. chunks - 1, in order; the lanes are
+ *          then reduced SEQUENTIALLY from lane 0 to lane 7 (not the pairwise tree of ip / l2 / cosine); the D % 8 tail elements
+ *          are folded in one by one after that.
+ *   L1           lane: acc += |a - b|; reduce: 0.0 + l0 + ... + l7; tail: sum += |a - b|.
+ *   Chebyshev    lane: acc = (acc > d) ? acc : d with d = |a - b| (_mm256_max_ps: d whenever either operand is NaN, so a NaN step
+ *                erases what the lane held and the next non-NaN step replaces the NaN); reduce and tail: f32::max from 0.0, which
+ *                returns the non-NaN operand — a NaN left in a lane by its last step is dropped, the result is never NaN.
+ *   Canberra     lane: den = |a| + |b|, q = |a - b| / den (IEEE), acc += (den != 0, ordered) ? q : +0 — a NaN den adds +0 in the
+ *                body; reduce as L1; tail: if (den != 0.0) sum += |a - b| / den — plain !=, so a NaN den DOES add NaN there.
+ *   Bray-Curtis  num += |a - b| and den += |a + b|, both reduced and tailed as L1; den == 0 ? (num == 0 ? 0 : +inf) : num / den.
+ * Searches follow the NON-FINITE VALUES rule and the canonical order above: a NaN distance is reported as +inf, the order is
+ * (distance, row ascending), min(k, live rows) entries come back.
+ * Accepted by lynse_hip_flat_search_f32 / _filtered_f32 / _filtered_bitset_f32 (an exact scan of every row into a score matrix, the
+ * cut and order of the range search; the call holds the handle's lock exclusively, runs on context 0, is refused while tickets are
+ * outstanding and goes in query chunks like the range search), lynse_hip_flat_search_range_f32, lynse_hip_top_k_search,
+ * lynse_hip_compute_distance, and as ascending metrics by lynse_hip_merge_topk / lynse_hip_merge_row_results /
+ * lynse_hip_metric_is_ascending (1) / lynse_hip_metric_is_binary (0).
+ * Refused with LYNSE_ERR_UNSUPPORTED: top-k on an F16 shard (the f16 sequential forms are not built; the range search scores the
+ * decoded rows), a packed-only handle, a row-mapped handle, a row too wide for a query and a row to share the LDS — and every other
+ * entry that takes a metric id (IVF / SPANN, SQ8, PQ, RaBitQ, packed queries, the _device, submit and sharded forms, prepare,
+ * coarse_scores, merge_topk_device).  Ids outside 0-10 stay LYNSE_ERR_UNKNOWN_METRIC. */
 
 /* IP accumulation form of the exact rescoring pass. */
 enum { LYNSE_IPFORM_AUTO = 0, LYNSE_IPFORM_SINGLE = 1, LYNSE_IPFORM_BATCH8 = 2,

@@ -25,6 +25,7 @@ ERR_INVALID_ARGUMENT, ERR_DIMENSION_MISMATCH, ERR_UNKNOWN_METRIC, ERR_NOT_FINALI
 ERR_OUT_OF_MEMORY, ERR_DEVICE, ERR_INTERNAL, ERR_INDEX_NOT_BUILT, ERR_UNSUPPORTED, ERR_TIMEOUT = 5, 6, 7, 8, 9, 10
 
 METRIC_IP, METRIC_L2, METRIC_COSINE, METRIC_HAMMING, METRIC_JACCARD, METRIC_DICE, METRIC_TANIMOTO = range(7)
+METRIC_L1, METRIC_CHEBYSHEV, METRIC_CANBERRA, METRIC_BRAY_CURTIS = 7, 8, 9, 10   # the additive metrics: exact FLAT scans only
 IPFORM_AUTO, IPFORM_SINGLE, IPFORM_BATCH8 = 0, 1, 2
 
 

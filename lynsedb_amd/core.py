@@ -157,6 +157,30 @@ def spann_mode_of(mode: str) -> Optional[tuple]:
     return SPANN_MODES[u]
 
 
+ADDITIVE_METRICS = (_lib.METRIC_L1, _lib.METRIC_CHEBYSHEV, _lib.METRIC_CANBERRA, _lib.METRIC_BRAY_CURTIS)
+# resolve_domain_index_type's flat names of the additive metrics (src/index/mod.rs:426-495)
+ADDITIVE_FLAT_MODES = {"FLAT-L1": _lib.METRIC_L1, "FLAT-MANHATTAN": _lib.METRIC_L1, "FLAT-CITYBLOCK": _lib.METRIC_L1,
+                       "FLAT-CHEBYSHEV": _lib.METRIC_CHEBYSHEV, "FLAT-CHEBYCHEV": _lib.METRIC_CHEBYSHEV, "FLAT-LINF": _lib.METRIC_CHEBYSHEV,
+                       "FLAT-CANBERRA": _lib.METRIC_CANBERRA, "FLAT-BRAY-CURTIS": _lib.METRIC_BRAY_CURTIS,
+                       "FLAT-BRAYCURTIS": _lib.METRIC_BRAY_CURTIS}
+
+
+def additive_mode_of(mode: str) -> Optional[int]:
+    """The metric id of a FLAT-{L1,MANHATTAN,CITYBLOCK,CHEBYSHEV,CHEBYCHEV,LINF,CANBERRA,BRAY-CURTIS,BRAYCURTIS} index mode (any letter
+    case), None for a mode that names none of the four additive metrics; any other mode naming one (FLAT-L1-SQ8, IVF-L1, SPANN-CHEBYSHEV ...)
+    is refused as the reference refuses an unknown index type (ValueError, InvalidArgument)."""
+    u = str(mode).upper()
+    if u in ADDITIVE_FLAT_MODES:
+        return ADDITIVE_FLAT_MODES[u]
+    try:
+        m = metric_from_index_mode(u)
+    except (ValueError, NotImplementedError):
+        return None
+    if m in ADDITIVE_METRICS:
+        raise ValueError(f"Invalid argument: Unknown index type: {mode}")
+    return None
+
+
 def spann_build_options(params: Optional[dict]) -> dict:
     """IndexBuildOptions for a SPANN mode (src/index/mod.rs:502-542, :626-655): n_clusters (alias n_centroids) = 256, nprobe = 32,
     replica_count = 1; a value of 0 is refused with ValueError("Invalid argument: <name> must be greater than 0")."""
@@ -601,7 +625,7 @@ class FlatIndex:
         ticket; `wait()` makes the results final in d_rows / d_dists / d_counts.  Up to LYNSE_HIP_CONTEXTS batches overlap on
         the device.  `comm`: the communicator handle of a row-sharded collection (a collective then)."""
         m = metric if isinstance(metric, int) else metric_from_str(metric)
-        if m >= 3 and d_queries.is_floating_point():
+        if _lib.METRIC_HAMMING <= m <= _lib.METRIC_TANIMOTO and d_queries.is_floating_point():
             # float queries of a binary metric are packed by the blocking entry point (pack_binary_query); batches in flight
             # take packed words: answer this one now (only without a communicator: the sharded entry points are packed-only too)
             if comm is not None:
@@ -610,7 +634,7 @@ class FlatIndex:
             return SearchTicket(None, None)
         _sync_producer(d_queries)
         t = C.c_void_p()
-        fn = lib.lynse_hip_flat_search_submit_packed_u64_device if m >= 3 else lib.lynse_hip_flat_search_submit_f32_device
+        fn = lib.lynse_hip_flat_search_submit_packed_u64_device if _lib.METRIC_HAMMING <= m <= _lib.METRIC_TANIMOTO else lib.lynse_hip_flat_search_submit_f32_device
         check(fn(self._h, comm, C.c_void_p(d_queries.data_ptr()), d_queries.shape[0], int(k), m, C.c_void_p(d_rows.data_ptr()),
                  C.c_void_p(d_dists.data_ptr()), C.c_void_p(d_counts.data_ptr()), C.byref(t)))
         return SearchTicket(t, (d_queries, d_rows, d_dists, d_counts))
@@ -1273,6 +1297,7 @@ class Collection:
         flat_mmap.rs:891-905); IVF-* trains a k-means IVFIndex (engine.rs:4616-4627), `IVF-{HAMMING,JACCARD}-BINARY`
         the binary-quantised one (src/index/mod.rs:376-385)."""
         mode = str(index_type).upper()
+        additive = additive_mode_of(mode)   # (refuses every other mode that names one of the four additive metrics)
         try:
             metric = metric_from_index_mode(mode)
         except NotImplementedError:
@@ -1281,7 +1306,11 @@ class Collection:
             raise RuntimeError(str(e))
         params = dict(params or {})
         self._flush_pending()
-        if mode.startswith("FLAT"):
+        if additive is not None:   # FLAT-L1 ... FLAT-BRAYCURTIS: no index object, no auxiliary index, the exact scan of the metric
+            self._ivf = None
+            self._drop_aux()
+            metric = additive
+        elif mode.startswith("FLAT"):
             rabitq = flat_rabitq_mode(mode)   # (refuses PolarVec)
             pq = flat_pq_mode(mode)
             self._ivf = None
@@ -1564,7 +1593,9 @@ class Collection:
 
 
 _METRIC_NAMES = {_lib.METRIC_IP: "ip", _lib.METRIC_L2: "l2", _lib.METRIC_COSINE: "cosine", _lib.METRIC_HAMMING: "hamming",
-                 _lib.METRIC_JACCARD: "jaccard", _lib.METRIC_DICE: "dice", _lib.METRIC_TANIMOTO: "tanimoto"}
+                 _lib.METRIC_JACCARD: "jaccard", _lib.METRIC_DICE: "dice", _lib.METRIC_TANIMOTO: "tanimoto",
+                 _lib.METRIC_L1: "l1", _lib.METRIC_CHEBYSHEV: "chebyshev", _lib.METRIC_CANBERRA: "canberra",
+                 _lib.METRIC_BRAY_CURTIS: "bray_curtis"}
 
 
 class DatabaseManager:

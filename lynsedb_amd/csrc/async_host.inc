@@ -143,7 +143,7 @@ int submit_impl(lynse_hip_flat* h, lynse_hip_comm* c, const void* d_queries, boo
                 uint64_t* d_out_rows, float* d_out_dists, uint32_t* d_out_counts, lynse_hip_ticket** out) {
     if (!h || !out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     *out = nullptr;
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     if (nq && (!d_queries || !d_out_counts || (k && (!d_out_rows || !d_out_dists)))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (c && h->device != c->device) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the shard and the communicator live on different devices");
     if (c && (uint64_t)c->world * k > 8192) return set_error(LYNSE_ERR_UNSUPPORTED, "world * k exceeds the merge kernel capacity (8192)");

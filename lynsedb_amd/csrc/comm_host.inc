@@ -241,8 +241,9 @@ static int sharded_exchange_blocking(lynse_hip_comm* c, int slot, hipStream_t st
 // every rank of the communicator must call it with the same nq / k / metric.  `packed` = queries are packed u64 words.
 static int sharded_search(lynse_hip_flat* h, lynse_hip_comm* c, const void* d_queries, bool packed, uint64_t nq, uint32_t k, int metric,
                           uint64_t* d_out_rows, float* d_out_dists, uint32_t* d_out_counts) {
+    if (metric_additive(metric)) return metric_check(metric);   // (before the handles: a refusal needs no communicator)
     if (!h || !c) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     if (h->device != c->device) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the shard and the communicator live on different devices");
     if (nq == 0) return LYNSE_OK;
     if (!d_queries || !d_out_counts || (k && (!d_out_rows || !d_out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -350,6 +351,7 @@ extern "C" int lynse_hip_ivf_kmeans_sharded(const float* rows_local, uint64_t n_
                                             uint32_t* out_assignments, uint32_t* out_k) {
     if (!out_centroids || !out_k || (n_local && (!rows_local || !out_assignments))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (world == 0 || rank >= world || dim == 0 || nlist == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "bad shard geometry");
+    if (metric_additive(metric)) return metric_check(metric);
     if (metric < M_IP || metric > M_COS) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "sharded training takes ip / l2 / cosine");
     if (n_local != (n_global > rank ? (n_global - rank + world - 1) / world : 0)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "n_local does not match rows g % world == rank of n_global");
     if (world > 1 && !c && !reduce) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "a communicator or a reduction callback is needed");
@@ -435,6 +437,7 @@ extern "C" int lynse_hip_ivf_build_sharded_device(const float* d_rows_local, uin
                                                   lynse_hip_comm* c, lynse_hip_reduce_fn reduce, void* reduce_ctx, lynse_hip_ivf** out) {
     if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
+    if (metric_additive(metric)) return metric_check(metric);
     if (ivfflat_routing && n_global < nlist) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF requires at least as many vectors as partitions");   // ivf_flat_mmap.rs:69-75
     const uint32_t kmax = (uint32_t)std::min<uint64_t>(nlist, n_global);
     std::vector<float> cen((size_t)kmax * dim);

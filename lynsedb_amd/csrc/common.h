@@ -10,10 +10,13 @@
 namespace lynse {
 
 // Metric classes used by the kernels.
-enum : int { M_IP = 0, M_L2 = 1, M_COS = 2, M_HAMMING = 3, M_JACCARD = 4, M_DICE = 5, M_TANIMOTO = 6 };
+enum : int { M_IP = 0, M_L2 = 1, M_COS = 2, M_HAMMING = 3, M_JACCARD = 4, M_DICE = 5, M_TANIMOTO = 6,
+             M_L1 = 7, M_CHEBYSHEV = 8, M_CANBERRA = 9, M_BRAY_CURTIS = 10 };
 
 __host__ __device__ inline bool metric_ascending(int m) { return m != M_IP; }  // distance/mod.rs:111-116
-__host__ __device__ inline bool metric_binary(int m) { return m >= M_HAMMING; }  // distance/mod.rs:161-166
+__host__ __device__ inline bool metric_binary(int m) { return m >= M_HAMMING && m <= M_TANIMOTO; }  // distance/mod.rs:161-166
+// Manhattan, Chebyshev, Canberra, Bray-Curtis (distance/mod.rs:177-188): exact FLAT scans only (additive.h)
+__host__ __device__ inline bool metric_additive(int m) { return m >= M_L1 && m <= M_BRAY_CURTIS; }
 
 // ---- candidate keys -------------------------------------------------------------------------
 // A candidate is one u64: high word = order-preserving image of the f32 score arranged so that an

@@ -362,6 +362,7 @@ static int ivf_check_args(const float* rows, uint64_t n, uint32_t dim, uint32_t 
     if (nlist == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF partition count must be greater than zero");  // :76-81
     if (!rows && n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "rows is NULL");
     if (n > 0xfffffff0ull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF vector count exceeds the u32 ID capacity");  // :89-94
+    if (metric_additive(metric)) return metric_check(metric);
     if (!metric_valid(metric)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown metric");
     if (nlist > 16384) return set_error(LYNSE_ERR_UNSUPPORTED, "nlist > 16384 is not supported yet");
     return LYNSE_OK;
@@ -1986,7 +1987,7 @@ extern "C" int lynse_hip_ivf_search_f32(lynse_hip_ivf* h, const float* queries, 
 extern "C" int lynse_hip_ivf_search_metric_f32(lynse_hip_ivf* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
                                                int metric, uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "IVF index is not built");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     bool is_binary, is_sq8;
     int index_metric;
     {   // (insert / delete swap the whole index structure under the guard: even its constant fields are read under it)

@@ -30,6 +30,7 @@
 #include "pq.h"
 #include "rabitq.h"
 #include "range.h"
+#include "additive.h"
 #include "spann.h"
 
 using namespace lynse;
@@ -142,17 +143,19 @@ extern "C" int lynse_hip_metric_from_str(const char* name, int* out) {  // dista
         {"hamming", M_HAMMING}, {"jaccard", M_JACCARD},
         {"dice", M_DICE}, {"sorensen", M_DICE}, {"sorensen_dice", M_DICE}, {"sorensen-dice", M_DICE},
         {"tanimoto", M_TANIMOTO},
+        {"l1", M_L1}, {"manhattan", M_L1}, {"cityblock", M_L1},
+        {"chebyshev", M_CHEBYSHEV}, {"chebychev", M_CHEBYSHEV}, {"linf", M_CHEBYSHEV}, {"l_inf", M_CHEBYSHEV}, {"l-infinity", M_CHEBYSHEV},
+        {"canberra", M_CANBERRA},
+        {"bray_curtis", M_BRAY_CURTIS}, {"bray-curtis", M_BRAY_CURTIS}, {"braycurtis", M_BRAY_CURTIS},
     };
     for (auto& t : tab)
         if (s == t.n) { *out = t.m; return LYNSE_OK; }
-    // valid names of the reference's other nine metrics (distance/mod.rs:46-60): recognised, but not part of this path
-    for (const char* o : {"l1", "manhattan", "cityblock", "haversine", "haversine_m", "haversine-m", "geo", "correlation", "pearson",
-                          "hellinger", "wasserstein", "wasserstein1d", "wasserstein_1d", "wasserstein-1d", "emd", "jensen_shannon",
-                          "jensen-shannon", "jensenshannon", "js", "chebyshev", "chebychev", "linf", "l_inf", "l-infinity", "canberra",
-                          "bray_curtis", "bray-curtis", "braycurtis"})
+    // valid names of the reference's other six metrics (distance/mod.rs:46-60): recognised, but not part of this path
+    for (const char* o : {"haversine", "haversine_m", "haversine-m", "geo", "correlation", "pearson", "hellinger", "wasserstein",
+                          "wasserstein1d", "wasserstein_1d", "wasserstein-1d", "emd", "jensen_shannon", "jensen-shannon", "jensenshannon", "js"})
         if (s == o)
             return set_error(LYNSE_ERR_UNSUPPORTED, std::string("metric '") + name + "' is a LynseDB metric outside the GPU FLAT / IVF path "
-                                                    "(supported: ip, l2, cosine, hamming, jaccard, dice, tanimoto)");
+                                                    "(supported: ip, l2, cosine, hamming, jaccard, dice, tanimoto, l1, chebyshev, canberra, bray_curtis)");
     return set_error(LYNSE_ERR_UNKNOWN_METRIC, std::string("Unknown metric: ") + name);
 }
 
@@ -169,21 +172,23 @@ extern "C" int lynse_hip_metric_from_index_mode(const char* mode, int* out) {  /
         p = e + 1;
     }
     auto has = [&](const char* v) { return std::find(tok.begin(), tok.end(), v) != tok.end(); };
-    // metric families outside this path take precedence in the reference's chain
-    if ((has("JENSEN") && has("SHANNON")) || (has("BRAY") && has("CURTIS")))
-        return set_error(LYNSE_ERR_UNSUPPORTED, std::string("index mode names a LynseDB metric outside the GPU FLAT / IVF path: ") + mode);
-    for (const char* o : {"JENSENSHANNON", "JS", "CHEBYSHEV", "CHEBYCHEV", "LINF", "CANBERRA", "BRAYCURTIS"})
-        if (has(o)) return set_error(LYNSE_ERR_UNSUPPORTED, std::string("index mode names a LynseDB metric outside the GPU FLAT / IVF path: ") + mode);
+    // the reference's chain order: Jensen-Shannon (outside this path), the additive metrics but L1, the binary metrics, the
+    // other metrics outside this path, L1, then l2 / cos / ip
+    auto outside = [&]() { return set_error(LYNSE_ERR_UNSUPPORTED, std::string("index mode names a LynseDB metric outside the GPU FLAT / IVF path: ") + mode); };
+    if ((has("JENSEN") && has("SHANNON")) || has("JENSENSHANNON") || has("JS")) return outside();
     int m = -1;
-    if (has("TANIMOTO")) m = M_TANIMOTO;
+    if (has("CHEBYSHEV") || has("CHEBYCHEV") || has("LINF")) m = M_CHEBYSHEV;
+    else if (has("CANBERRA")) m = M_CANBERRA;
+    else if (has("BRAYCURTIS") || (has("BRAY") && has("CURTIS"))) m = M_BRAY_CURTIS;
+    else if (has("TANIMOTO")) m = M_TANIMOTO;
     else if (has("JACCARD")) m = M_JACCARD;
     else if (has("HAMMING")) m = M_HAMMING;
     else if (has("DICE") || has("SORENSEN")) m = M_DICE;
     else {
-        for (const char* o : {"HAVERSINE", "GEO", "CORRELATION", "PEARSON", "HELLINGER", "WASSERSTEIN",
-                              "WASSERSTEIN1D", "EMD", "L1", "MANHATTAN", "CITYBLOCK"})
-            if (has(o)) return set_error(LYNSE_ERR_UNSUPPORTED, std::string("index mode names a LynseDB metric outside the GPU FLAT / IVF path: ") + mode);
-        if (has("L2") || has("L2SQ")) m = M_L2;
+        for (const char* o : {"HAVERSINE", "GEO", "CORRELATION", "PEARSON", "HELLINGER", "WASSERSTEIN", "WASSERSTEIN1D", "EMD"})
+            if (has(o)) return outside();
+        if (has("L1") || has("MANHATTAN") || has("CITYBLOCK")) m = M_L1;
+        else if (has("L2") || has("L2SQ")) m = M_L2;
         else if (has("COS") || has("COSINE")) m = M_COS;
         else if (has("IP")) m = M_IP;
     }
@@ -193,9 +198,17 @@ extern "C" int lynse_hip_metric_from_index_mode(const char* mode, int* out) {  /
 }
 
 extern "C" int lynse_hip_metric_is_ascending(int metric) { return metric_ascending(metric) ? 1 : 0; }
-extern "C" int lynse_hip_metric_is_binary(int metric) { return (metric >= M_HAMMING && metric <= M_TANIMOTO) ? 1 : 0; }
+extern "C" int lynse_hip_metric_is_binary(int metric) { return metric_binary(metric) ? 1 : 0; }
 
-static bool metric_valid(int m) { return m >= M_IP && m <= M_TANIMOTO; }
+static bool metric_valid(int m) { return m >= M_IP && m <= M_BRAY_CURTIS; }   // every id of the header
+// ... for the entries the additive metrics (ids 7-10) are not built for: every one but the exact FLAT searches (additive_host.inc)
+static int metric_check(int m) {
+    if (metric_additive(m))
+        return set_error(LYNSE_ERR_UNSUPPORTED, "l1 / chebyshev / canberra / bray_curtis are served by the exact FLAT searches only "
+                                                "(lynse_hip_flat_search_f32, its filtered forms and the range search)");
+    if (!metric_valid(m)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    return LYNSE_OK;
+}
 
 // ------------------------------------------------------------------------------------ handle ----
 constexpr size_t H_OUT_BYTES = 96 * 1024;  // results up to this size come back through pinned memory (no pageable-copy stalls)
@@ -2643,7 +2656,7 @@ static int search_sq8_large(lynse_hip_flat* h, std::unique_lock<std::shared_mute
 extern "C" int lynse_hip_flat_search_sq8_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric,
                                              uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     // use_sq8 only changes ip / l2 / cosine (flat_mmap.rs:891-896); every other metric takes the ordinary path
     if (metric > M_COS) return lynse_hip_flat_search_f32(h, queries, nq, k, metric, out_rows, out_dists, out_counts);
     if (nq == 0) return LYNSE_OK;
@@ -2810,7 +2823,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
     // filtered: the subset is either a list of row ids (`subset`, n_subset) or BitSet words (`bitset_words`; n_subset =
     // number of set bits below len, counted by the caller)
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     if (nq == 0) return LYNSE_OK;
     if (!q_src || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     LY_TRY(use_device(h));
@@ -3158,6 +3171,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
 extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* queries, uint64_t nq, int metric, int coarse,
                                             float* out_scores, float* out_bound, int* out_form) {
     if (!h || !queries || !out_scores || !out_bound) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (metric_additive(metric)) return metric_check(metric);
     if (metric < M_IP || metric > M_COS) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "float metrics only");
     if (nq == 0 || nq > QCHUNK) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "1..256 queries");
     LY_TRY(use_device(h));
@@ -3226,7 +3240,7 @@ extern "C" uint64_t lynse_hip_flat_bpm_rows(const lynse_hip_flat* h) {
 // this after a bulk load so that the first query does not pay for it under the writer lock.
 extern "C" int lynse_hip_flat_prepare(lynse_hip_flat* h, int metric, uint64_t nq) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     LY_WRITER(h, lk);
     LY_TRY(use_device(h));
     if (h->n == 0) return LYNSE_OK;
@@ -3471,14 +3485,21 @@ static int search_sq8_large(lynse_hip_flat* h, std::unique_lock<std::shared_mute
     return LYNSE_OK;
 }
 
+// ids 7-10 leave before the staged pipeline (additive_host.inc)
+static int additive_search(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, bool filtered,
+                           const uint64_t* subset, uint64_t n_subset, const uint64_t* bitset_words, uint64_t n_words,
+                           uint64_t* out_rows, float* out_dists, uint32_t* out_counts);
+
 extern "C" int lynse_hip_flat_search_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric,
                                          uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
+    if (metric_additive(metric)) return additive_search(h, queries, nq, k, metric, false, nullptr, 0, nullptr, 0, out_rows, out_dists, out_counts);
     return search_impl(h, queries, false, nq, k, metric, out_rows, out_dists, out_counts, false, nullptr);
 }
 
 extern "C" int lynse_hip_flat_search_filtered_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric,
                                                   const uint64_t* subset_rows, uint64_t n_subset, uint64_t* out_rows,
                                                   float* out_dists, uint32_t* out_counts) {
+    if (metric_additive(metric)) return additive_search(h, queries, nq, k, metric, true, subset_rows, n_subset, nullptr, 0, out_rows, out_dists, out_counts);
     return search_impl(h, queries, false, nq, k, metric, out_rows, out_dists, out_counts, false, nullptr, subset_rows, n_subset, true);
 }
 
@@ -3487,6 +3508,10 @@ extern "C" int lynse_hip_flat_search_filtered_bitset_f32(lynse_hip_flat* h, cons
                                                          float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     if (n_words && !bitset_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "bitset is NULL");
+    if (metric_additive(metric)) {   // (an empty BitSet is still a filter: no rows)
+        static const uint64_t none = 0;
+        return additive_search(h, queries, nq, k, metric, true, nullptr, 0, bitset_words ? bitset_words : &none, n_words, out_rows, out_dists, out_counts);
+    }
     const uint64_t n = lynse_hip_flat_len(h);
     uint64_t count = 0;  // BitSet::count() restricted to rows below len
     const uint64_t full = std::min<uint64_t>(n_words, n / 64);
@@ -3610,7 +3635,7 @@ static int merge_topk_device_impl(const void* d_blocks, uint64_t block_bytes, ui
                                   uint64_t dists_off, uint64_t counts_off, uint32_t n_lists, uint64_t nq,
                                   uint32_t k, int metric, uint64_t* d_out_rows, float* d_out_dists,
                                   uint32_t* d_out_counts, void* stream, uint64_t status_off, uint32_t* out_status) {
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     if (nq == 0) return LYNSE_OK;
     if (!d_blocks || !d_out_counts || (k && (!d_out_rows || !d_out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_lists == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "n_lists is zero");
@@ -3687,3 +3712,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "pq_host.inc"
 #include "rabitq_host.inc"
 #include "range_host.inc"
+#include "additive_host.inc"

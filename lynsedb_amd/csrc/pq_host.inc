@@ -320,7 +320,7 @@ extern "C" int lynse_hip_flat_pq_stage_times(lynse_hip_flat* h, double* out3, in
 extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t oversample,
                                             uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (!metric_valid(metric)) return set_error(LYNSE_ERR_UNKNOWN_METRIC, "Unknown metric id");
+    LY_TRY(metric_check(metric));
     if (metric_binary(metric)) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ is defined for ip / l2 / cosine");
     if (nq == 0) return LYNSE_OK;
     if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");

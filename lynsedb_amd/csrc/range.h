@@ -2,7 +2,7 @@
 // kernels (compute_distance_f32), the rows on the passing side of a caller-given threshold kept.  The cut at max_results is the
 // radix selection of pq.h (k_pq_hist / k_pq_find / k_pq_emit), the order the LDS sort of k_pool_select (kernels.h).  DESIGN.md §16.
 //   k_range_scan      f32 / f16 rows: a tile of rows goes through LDS with 16-B loads (an F16 shard is decoded there, exactly), a
-//                     tile of queries sits next to it, exact_score in its single-row form for every (query, row) of the tiles
+//                     tile of queries sits next to it, exact_score in its single-row form (ids 7-10: additive_score) for every (query, row) of the tiles
 //   k_range_scan_bin  packed rows: the popcount distances of k_scan_binary_wide (binary_distance)
 // Both write S[q][row] = the score_ord image of a passing distance, RANGE_FAIL for a row that fails the test, is masked out or
 // scores NaN, and add the passers of a query to count[q]: ballot + popcount in the wave, LDS across the block, one device atomic
@@ -30,6 +30,10 @@ __device__ __forceinline__ bool range_live(const uint64_t* __restrict__ mask, ui
     const uint64_t w = row >> 6;
     return w < mask_words && ((mask[w] >> (row & 63u)) & 1ull);
 }
+
+// ids 7-10 (additive.h, included after this file): one (query, row) pair by the 8 lanes of a group, as exact_score
+template <int UB = 8>
+__device__ __forceinline__ float additive_score(int metric, const float* __restrict__ q, const float* __restrict__ v, uint32_t D, int g);
 
 struct RangeScanArgs {
     const void* V;          // n rows: f32 (pitch ld floats, ld % 4 == 0) or the f16 bits of an F16 shard (pitch ld halves, ld % 8 == 0)
@@ -100,7 +104,8 @@ __global__ void __launch_bounds__(RANGE_NT) k_range_scan(RangeScanArgs a) {
             const float* v = rows_l + (size_t)(in ? rr : 0u) * a.stride;
             const bool live = in && range_live(a.mask, a.mask_words, row);
             for (uint32_t j = 0; j < tq; ++j) {
-                const float d = exact_score<16>(a.metric, LYNSE_IPFORM_SINGLE, q_l + (size_t)j * a.D, v, a.D, g);
+                const float d = metric_additive(a.metric) ? additive_score<16>(a.metric, q_l + (size_t)j * a.D, v, a.D, g)
+                                                          : exact_score<16>(a.metric, LYNSE_IPFORM_SINGLE, q_l + (size_t)j * a.D, v, a.D, g);
                 const bool pass = live && g == 0 && range_pass(d, thr_l[j], asc);
                 if (in && g == 0) a.S[(size_t)(q0 + j) * a.n + row] = pass ? score_ord(d, asc) : RANGE_FAIL;
                 const uint64_t b = __ballot(pass);

@@ -258,7 +258,7 @@ class ShardedFlat:
             def wait(self):
                 return None
 
-        if metric >= _lib.METRIC_HAMMING and d_queries.is_floating_point():
+        if _lib.METRIC_HAMMING <= metric <= _lib.METRIC_TANIMOTO and d_queries.is_floating_point():
             self.search_device(d_queries, k, metric, out)   # float queries of a binary metric: packed inside the blocking call
             return _Done()
         if self.world == 1 or self.comm is not None:  # (a 1-rank communicator still runs the exchange half: status word, merge)
@@ -331,7 +331,7 @@ class ShardedFlat:
     def verify_against_torch(self, d_queries, k: int, metric: int, out: ShardOutputs, nverify: int = 16) -> dict:
         import torch
 
-        if metric >= _lib.METRIC_HAMMING:
+        if _lib.METRIC_HAMMING <= metric <= _lib.METRIC_TANIMOTO:
             return {"skipped": "binary metric"}
         n_local = len(self.index)
         dev = d_queries.device
