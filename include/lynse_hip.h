@@ -680,6 +680,54 @@ int lynse_hip_ivf_ticket_stats(lynse_hip_ivf *h, uint64_t *out);
 int lynse_hip_flat_coarse_scores(lynse_hip_flat *h, const float *queries, uint64_t nq, int metric, int coarse,
                                  float *out_scores, float *out_bound, int *out_form);
 
+/* ---- sparse vectors: SparseVectorStore (src/engine.rs:550-718), index mode SPARSE-FLAT-IP ---- */
+
+/* SPARSE VECTORS (Collection::add_sparse_vectors / search_sparse, src/engine.rs:4250-4279, :4962-5002).  A sparse vector is a list of
+ * (u32 index, f32 value) pairs; the store is a CSR matrix in HBM (indptr u64[n + 1] | indices u32 | values f32, three arrays), rows
+ * 0 .. n - 1.  The rules:
+ *  1. Normalising (normalize_sparse_entries, :6925-6943), input pairs in any order: a non-finite value is the error "sparse vector
+ *     values must be finite"; values == 0.0 are skipped; the rest are merged per index in input order (each index starts at 0.0f and
+ *     takes += value in f32); entries whose merged value is 0.0 are dropped; the output ascends by index.
+ *     lynse_hip_sparse_normalize does this for n vectors in CSR into caller buffers (never longer than the input); host only, no
+ *     handle, no device.
+ *  2. Scoring (sparse_inner_product, :6945-6965): score = 0.0f; for each index present in both vectors, in ascending index order,
+ *     score += q * v — the multiply and the add are separate f32 operations, never fused.
+ *  3. Search (SparseVectorStore::search, :660-695): a row is a result only if score != 0.0 (a plain IEEE comparison: a score that
+ *     cancels to +-0 and a row with no common index are dropped, a NaN score — inf - inf after overflow — is kept); the order is score
+ *     descending, then row ascending; at most k come back.  NaN follows the NON-FINITE VALUES rule: reported as -inf, ranked last,
+ *     ties by row; +-inf are ordinary values.  An empty query or k == 0: an empty result.
+ *  4. lynse_hip_sparse_set_rows replaces the whole store (upsert_many rewrites its whole map too).  Checked before any device work:
+ *     indptr[0] == 0 and non-decreasing, indices strictly ascending within a row, values finite and non-zero, n < 2^32 (a selection
+ *     key carries a 32-bit row) — LYNSE_ERR_INVALID_ARGUMENT otherwise.  Empty rows are legal and never score; n == 0 empties the store.
+ *  5. lynse_hip_sparse_search takes nq NORMALISED queries in CSR, validated like rows (LYNSE_ERR_INVALID_ARGUMENT).  Layout as
+ *     lynse_hip_flat_search_f32: stride k, out_counts[q] entries valid, the rest padded with row ~0 and -inf.  out_passed[q] (may be
+ *     NULL) = the rows with a non-zero score before the cut.  bitset_words are the reference's BitSet words over sparse rows, treated
+ *     as lynse_hip_flat_search_range_f32 treats its words (NULL = every row, rows the words do not cover are out, bits at or beyond n
+ *     are ignored).  The call holds the handle's lock EXCLUSIVELY (the scratch is per handle) and goes in query chunks that keep the
+ *     score matrix at or under 512 MiB.
+ *  6. Limit: a query of more than 4,096 entries is refused with LYNSE_ERR_UNSUPPORTED before any launch — a query tile's lookup table
+ *     (at most half full, a power of two of slots) has to fit the 160 KiB of LDS next to the staged results, and 8,192 slots is the
+ *     largest that does.  Tiles hold up to 16 queries and shrink down to 1 before anything is refused.
+ *  7. Profile: scan_launches, scan_us, scan_rows, scan_bytes = (nnz * 8 + (n + 1) * 8) per query tile (each tile streams the CSR once),
+ *     total_us = first launch to last launch of a chunk.
+ * Without a usable HIP device lynse_hip_sparse_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+typedef struct lynse_hip_sparse lynse_hip_sparse;
+int lynse_hip_sparse_normalize(const uint64_t *indptr /* n+1 */, const uint32_t *indices, const float *values, uint64_t n,
+                               uint64_t *out_indptr /* n+1 */, uint32_t *out_indices, float *out_values);
+int lynse_hip_sparse_create(int device, lynse_hip_sparse **out);
+int lynse_hip_sparse_destroy(lynse_hip_sparse *h);
+int lynse_hip_sparse_set_rows(lynse_hip_sparse *h, const uint64_t *indptr /* n+1 */, const uint32_t *indices,
+                              const float *values, uint64_t n);
+int lynse_hip_sparse_len(lynse_hip_sparse *h, uint64_t *out_rows, uint64_t *out_nnz);
+uint64_t lynse_hip_sparse_hbm_bytes(lynse_hip_sparse *h);
+int lynse_hip_sparse_search(lynse_hip_sparse *h, const uint64_t *q_indptr /* nq+1 */, const uint32_t *q_indices,
+                            const float *q_values, uint64_t nq, uint32_t k,
+                            const uint64_t *bitset_words /* NULL = every row */, uint64_t n_words,
+                            uint64_t *out_rows /* nq*k */, float *out_scores, uint32_t *out_counts /* nq */,
+                            uint64_t *out_passed /* nq, may be NULL */);
+int lynse_hip_sparse_profile_enable(lynse_hip_sparse *h, int on);
+int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, int reset);
+
 /* ---- shard-node glue around a search (host only, no device work) ---- */
 
 /* Collection::filter_tombstoned_limit (src/engine.rs:3286-3308): drop the tombstoned ids, keep the order, at most

@@ -1098,6 +1098,142 @@ class SpannIndex:
         return rows[:, :k], dists[:, :k], counts
 
 
+# ---------------------------------------------------------------------------------------------
+# Sparse vectors (SparseVectorStore, src/engine.rs:550-718; index mode SPARSE-FLAT-IP)
+# ---------------------------------------------------------------------------------------------
+SPARSE_INDEX_MODE = "SPARSE-FLAT-IP"
+SPARSE_VECTORS_FILE = "sparse_vectors.jsonl"
+
+
+def normalize_sparse_vector(vector) -> list:
+    """`_normalize_sparse_vector` (python/lynse/_backend.py:31-43): a dict {index: value} or an iterable of (index, value) pairs ->
+    [(int index, float value)], in input order.  The values are cast to f32 and an index has to fit the core's u32."""
+    items = vector.items() if isinstance(vector, dict) else vector
+    out = []
+    for item in items:
+        if len(item) != 2:
+            raise ValueError("sparse vector entries must be (index, value) pairs")
+        index, value = item
+        index = int(index)
+        if index < 0:
+            raise ValueError("sparse vector indices must be non-negative")
+        if index > 0xFFFFFFFF:
+            raise OverflowError("sparse vector index does not fit in u32")
+        out.append((index, float(np.float32(value))))
+    return out
+
+
+def _sparse_csr(vectors) -> tuple:
+    """[(index, value) lists] -> the raw CSR arrays (indptr u64, indices u32, values f32), entries as given"""
+    lens = np.fromiter((len(v) for v in vectors), dtype=np.uint64, count=len(vectors))
+    indptr = np.zeros(len(vectors) + 1, np.uint64)
+    np.cumsum(lens, out=indptr[1:])
+    flat = [e for v in vectors for e in v]
+    indices = np.fromiter((e[0] for e in flat), dtype=np.uint32, count=len(flat))
+    values = np.fromiter((e[1] for e in flat), dtype=np.float32, count=len(flat))
+    return indptr, indices, values
+
+
+def sparse_normalize_arrays(indptr, indices, values) -> tuple:
+    """`normalize_sparse_entries` (engine.rs:6925-6943) for a batch in CSR, by lynse_hip_sparse_normalize (host code, no device): a
+    non-finite value raises ValueError("sparse vector values must be finite"); zeros skipped, duplicates summed in input order,
+    zero sums dropped, ascending indices -> (indptr, indices, values)."""
+    indptr = np.ascontiguousarray(np.asarray(indptr).reshape(-1), dtype=np.uint64)
+    indices = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.uint32)
+    values = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.float32)
+    if indptr.size == 0 or int(indptr[-1]) != indices.size or indices.size != values.size:
+        raise ValueError("sparse CSR arrays do not match: indptr[-1], len(indices) and len(values) must agree")
+    n = indptr.size - 1
+    o_ptr = np.zeros(n + 1, np.uint64)
+    o_idx = np.zeros(max(indices.size, 1), np.uint32)
+    o_val = np.zeros(max(indices.size, 1), np.float32)
+    check(lib.lynse_hip_sparse_normalize(_ptr(indptr), _ptr(indices), _ptr(values), n, _ptr(o_ptr), _ptr(o_idx), _ptr(o_val)))
+    m = int(o_ptr[-1])
+    return o_ptr, o_idx[:m].copy(), o_val[:m].copy()
+
+
+class SparseIndex:
+    """A CSR matrix of sparse rows in HBM and its exact inner-product scan (include/lynse_hip.h, SPARSE VECTORS): this build's
+    device half of the reference's SparseVectorStore.  Rows and queries are NORMALISED vectors (sparse_normalize_arrays)."""
+
+    def __init__(self, device: Optional[int] = None):
+        self._h = C.c_void_p()
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_sparse_create(dev, C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.lynse_hip_sparse_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @staticmethod
+    def _csr(indptr, indices, values):
+        indptr = np.ascontiguousarray(np.asarray(indptr).reshape(-1), dtype=np.uint64)
+        indices = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.uint32)
+        values = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.float32)
+        if indptr.size == 0:
+            indptr = np.zeros(1, np.uint64)
+        if indices.size != values.size or int(indptr.max()) > indices.size:
+            raise ValueError("sparse CSR arrays do not match: indptr must stay within len(indices) == len(values)")
+        return indptr, indices, values
+
+    def set_rows(self, indptr, indices, values) -> None:
+        """Replaces the whole store with the rows of the CSR arrays (indptr u64[n + 1], indices u32, values f32)."""
+        indptr, indices, values = self._csr(indptr, indices, values)
+        check(lib.lynse_hip_sparse_set_rows(self._h, _ptr(indptr), _ptr(indices), _ptr(values), indptr.size - 1))
+
+    def _len(self) -> tuple:
+        rows, nnz = C.c_uint64(0), C.c_uint64(0)
+        check(lib.lynse_hip_sparse_len(self._h, C.byref(rows), C.byref(nnz)))
+        return int(rows.value), int(nnz.value)
+
+    def __len__(self) -> int:
+        return self._len()[0]
+
+    @property
+    def nnz(self) -> int:
+        return self._len()[1]
+
+    def hbm_bytes(self) -> int:
+        return int(lib.lynse_hip_sparse_hbm_bytes(self._h))
+
+    def search_batch_arrays(self, q_indptr, q_indices, q_values, k: int, words=None):
+        """The rows with a non-zero inner product, best first by (score descending, row ascending) -> (rows u64[nq, k], scores
+        f32[nq, k], counts u32[nq], passed u64[nq]): counts[q] = min(passed[q], k) entries valid, the rest row ~0 and -inf.  `words`
+        are BitSet words over the sparse rows (None = every row)."""
+        q_indptr, q_indices, q_values = self._csr(q_indptr, q_indices, q_values)
+        nq, k = q_indptr.size - 1, int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        rows = np.full((nq, k), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        scores = np.full((nq, k), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        passed = np.zeros(nq, np.uint64)
+        if nq == 0:
+            return rows, scores, counts, passed
+        n_words = 0
+        if words is not None:
+            words = np.ascontiguousarray(np.asarray(words).reshape(-1), dtype=np.uint64)
+            n_words = int(words.size)
+            if n_words == 0:   # an empty mask is still a mask (NULL would mean every row)
+                words = np.zeros(1, np.uint64)
+        check(lib.lynse_hip_sparse_search(self._h, _ptr(q_indptr), _ptr(q_indices), _ptr(q_values), nq, k,
+                                          None if words is None else _ptr(words), n_words, _ptr(rows), _ptr(scores), _ptr(counts), _ptr(passed)))
+        return rows, scores, counts, passed
+
+    def profile_enable(self, on=True) -> None:
+        check(lib.lynse_hip_sparse_profile_enable(self._h, int(bool(on))))
+
+    def profile_get(self, reset: bool = True) -> dict:
+        p = _lib.Profile()
+        check(lib.lynse_hip_sparse_profile_get(self._h, C.byref(p), 1 if reset else 0))
+        return {f: getattr(p, f) for f, _ in _lib.Profile._fields_}
+
+
 def py_compute_distance(a, b, metric: str) -> float:
     """src/python/mod.rs:2161-2185."""
     m = metric_from_str(metric)
@@ -1235,6 +1371,10 @@ class Collection:
         self._tombstone: set = set()    # user ids (engine.rs:3182-3194)
         self._pq = False                # FLAT-*-PQ built over the rows flushed at build time (FlatIndex.build_pq)
         self._rabitq = False            # FLAT-*-RABITQ, likewise (FlatIndex.build_rabitq); at most one of the two exists
+        self._sparse: dict = {}         # user id -> (indices u32, values f32), normalised (SparseVectorStore.vectors)
+        self._sparse_ids = np.zeros(0, np.int64)   # the ids of the uploaded sparse rows, ascending: sparse row -> user id
+        self._sparse_index = None       # SparseIndex, created by the first sparse search
+        self._sparse_dirty = False      # the store changed since the last upload
 
     def name(self) -> str:
         return self._name
@@ -1559,6 +1699,122 @@ class Collection:
             out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), self._index_mode, self._dim, k))
         return out
 
+
+    # -- sparse vectors (engine.rs:4250-4279, :4962-5002) ---------------------------------------
+    def _ids_known(self, ids: np.ndarray) -> np.ndarray:
+        """is_id_exists for a batch: which of `ids` name a flushed or a pending row"""
+        known = np.zeros(ids.size, bool)
+        for a in list(self._id_arrays) + self._pending_ids:
+            known |= np.isin(ids, a)
+        return known
+
+    def add_sparse_vectors(self, vectors, ids: Sequence[int]) -> None:
+        """`Collection.add_sparse_vectors` (src/python/mod.rs:1115-1120 over engine.rs:4252-4279): attaches sparse vectors (dicts or
+        lists of (index, value) pairs) to ids that exist, flushed or pending.  An id seen again is replaced, a vector that normalises
+        to empty removes its id, a failed call leaves the store as it was.  With `path=` the store is rewritten to
+        <path>/sparse_vectors.jsonl.  The device copy is refreshed by the next sparse search."""
+        vecs = [normalize_sparse_vector(v) for v in vectors]
+        ids = [int(i) for i in ids]
+        if len(ids) != len(vecs):
+            raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match sparse vector count ({len(vecs)})")
+        seen, known = set(), self._ids_known(np.asarray(ids, dtype=np.int64))
+        for i, ok in zip(ids, known):
+            if i in seen:
+                raise RuntimeError(f"Invalid argument: duplicate id {i} within sparse vector batch")
+            seen.add(i)
+            if not ok:
+                raise RuntimeError(f"Invalid argument: cannot add sparse vector for unknown id {i}")
+        try:
+            ptr, idx, val = sparse_normalize_arrays(*_sparse_csr(vecs))
+        except ValueError as e:
+            raise RuntimeError(f"Invalid argument: {e}") from None
+        nxt = dict(self._sparse)
+        for r, i in enumerate(ids):
+            a, b = int(ptr[r]), int(ptr[r + 1])
+            if a == b:
+                nxt.pop(i, None)
+            else:
+                nxt[i] = (idx[a:b].copy(), val[a:b].copy())
+        if self._path is not None:
+            from .storage import save_sparse_vectors
+
+            save_sparse_vectors(self._path / SPARSE_VECTORS_FILE, nxt)
+        self._sparse, self._sparse_dirty = nxt, True
+
+    def try_load_sparse(self) -> bool:
+        """SparseVectorStore::load for a reopened collection: <path>/sparse_vectors.jsonl replaces the store.  False without a path
+        or a file."""
+        from .storage import load_sparse_vectors
+
+        if self._path is None or not (self._path / SPARSE_VECTORS_FILE).exists():
+            return False
+        self._sparse, self._sparse_dirty = load_sparse_vectors(self._path / SPARSE_VECTORS_FILE), True
+        return True
+
+    def sparse_len(self) -> int:
+        return len(self._sparse)
+
+    def _sparse_upload(self) -> None:
+        """the CSR of the store in ascending id order, so that (score, row ascending) is the reference's (score, id ascending)"""
+        if self._sparse_index is None:
+            self._sparse_index = SparseIndex(self._device)
+        if not self._sparse_dirty:
+            return
+        ids = np.array(sorted(self._sparse), dtype=np.int64)
+        lens = np.fromiter((self._sparse[int(i)][0].size for i in ids), dtype=np.uint64, count=ids.size)
+        indptr = np.zeros(ids.size + 1, np.uint64)
+        np.cumsum(lens, out=indptr[1:])
+        indices = np.concatenate([self._sparse[int(i)][0] for i in ids]) if ids.size else np.zeros(0, np.uint32)
+        values = np.concatenate([self._sparse[int(i)][1] for i in ids]) if ids.size else np.zeros(0, np.float32)
+        self._sparse_index.set_rows(indptr, indices, values)
+        self._sparse_ids, self._sparse_dirty = ids, False
+
+    def _sparse_words(self, subset) -> Optional[np.ndarray]:
+        """the BitSet words over sparse rows of a dense-row subset minus the tombstoned ids; None = every row"""
+        n = int(self._sparse_ids.size)
+        words = None
+        if subset is not None:
+            rows = self._subset_rows(subset).astype(np.int64)
+            rows = rows[rows < len(self._flat) + self._pending_rows]
+            allowed = self._user_ids(rows)
+            words = BitSet.from_rows(np.nonzero(np.isin(self._sparse_ids, allowed))[0], n).words
+        if self._tombstone:
+            dead = np.nonzero(np.isin(self._sparse_ids, np.fromiter(self._tombstone, dtype=np.int64, count=len(self._tombstone))))[0]
+            if dead.size:
+                if words is None:
+                    words = BitSet.from_rows(np.arange(n, dtype=np.uint64), n).words
+                words = words & ~BitSet.from_rows(dead, n).words
+        return words
+
+    def batch_search_sparse(self, vectors, k: Optional[int] = None, subset=None) -> list:
+        """`search_sparse` for a batch of query vectors sharing one subset, in ONE device call (this build's addition)."""
+        k = 10 if k is None else int(k)
+        if k < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        vecs = [normalize_sparse_vector(v) for v in vectors]
+        try:
+            ptr, idx, val = sparse_normalize_arrays(*_sparse_csr(vecs))
+        except ValueError as e:
+            raise RuntimeError(f"Invalid argument: {e}") from None
+        empty = lambda: SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), SPARSE_INDEX_MODE, 0, k)   # noqa: E731
+        if k == 0 or idx.size == 0 or not self._sparse:   # (engine.rs:4971-4980): the device is not touched
+            return [empty() for _ in vecs]
+        self._sparse_upload()
+        rows, scores, counts, _ = self._sparse_index.search_batch_arrays(ptr, idx, val, k, self._sparse_words(subset))
+        out = []
+        for i in range(len(vecs)):
+            c = int(counts[i])
+            out.append(SearchResult(self._sparse_ids[rows[i, :c].astype(np.int64)], scores[i, :c].copy(), SPARSE_INDEX_MODE, 0, k))
+        return out
+
+    def search_sparse(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, subset=None) -> SearchResult:
+        """`Collection.search_sparse` (src/python/mod.rs:1221-1237 over engine.rs:4964-5002): the ids whose sparse vector has a
+        non-zero inner product with `vector`, by (score descending, id ascending), at most k (default 10); the scores are in
+        `distances()`, the mode is SPARSE-FLAT-IP, the dimension 0.  Tombstoned ids are left out before the cut.  `subset=` (a BitSet
+        or dense row indices) stands in for the resolved `where_expr`, as on `search`."""
+        if where_expr:
+            raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
+        return self.batch_search_sparse([vector], k, subset=subset)[0]
 
     def search_range(self, vector, threshold: float, max_results: int = 1000, subset=None):
         """`Collection.search_range` (src/python/mod.rs:1784-1795 over Collection::search_range, src/engine.rs:6410-6483): the exact scan

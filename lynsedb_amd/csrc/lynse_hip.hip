@@ -31,6 +31,7 @@
 #include "rabitq.h"
 #include "range.h"
 #include "additive.h"
+#include "sparse.h"
 #include "spann.h"
 
 using namespace lynse;
@@ -3713,3 +3714,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "rabitq_host.inc"
 #include "range_host.inc"
 #include "additive_host.inc"
+#include "sparse_host.inc"

@@ -26,6 +26,85 @@ static void range_release(lynse_hip_flat* h) {
     h->range = nullptr;
 }
 
+// What follows a scan that left the score images in cut.d_S and the passer counts in d_cnt (the range search here, the sparse search
+// in sparse_host.inc): the counts read back into out_passed / out_counts, the best min(passed, N) keys of each of the nqc queries by the
+// canonical (score, row) key written best first at stride out_k and padded with rows ~0 and the worst score.  A query with more
+// passers than N goes through the radix selection of its N best keys; any other takes every key below RANGE_FAIL (a state that starts
+// done: the first 32 bits <= RANGE_FAIL - 1); a chunk in which nothing passed launches nothing more.  Sorted in LDS (k_pool_select)
+// up to 16,384 keys, on the host beyond.  The outputs start at the chunk's first query; `launched` runs once the chunk's last launch
+// is enqueued (profiling).
+template <typename F>
+static int range_cut_and_order(ScoreCut& cut, PoolRerank& rr, const uint32_t* d_cnt, std::vector<uint32_t>& cnt, std::vector<uint64_t>& keys,
+                               std::vector<uint64_t>& h_out, uint32_t nqc, uint64_t n, uint32_t N, uint32_t out_k, int metric, hipStream_t st,
+                               uint64_t* out_rows, float* out_dists, uint32_t* out_counts, uint64_t* out_passed, F&& launched) {
+    const bool asc = metric_ascending(metric), sort_dev = N <= 16384;
+    const float worst = asc ? INFINITY : -INFINITY;
+    auto pad = [&](uint32_t q, uint32_t from) {
+        for (uint32_t i = from; i < out_k; ++i) {
+            out_rows[(size_t)q * out_k + i] = ~0ull;
+            out_dists[(size_t)q * out_k + i] = worst;
+        }
+    };
+    cnt.resize(nqc);
+    LY_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+    LY_TRY(stream_wait(st));
+    uint32_t most = 0;
+    bool select = false;
+    cut.sel0.resize(nqc);
+    for (uint32_t i = 0; i < nqc; ++i) {
+        const uint32_t c = cnt[i];
+        if (out_passed) out_passed[i] = c;
+        out_counts[i] = std::min(c, N);
+        most = std::max(most, std::min(c, N));
+        select = select || c > N;
+        cut.sel0[i] = c > N ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u};
+    }
+    if (most == 0) {
+        for (uint32_t i = 0; i < nqc; ++i) pad(i, 0);
+        return launched();
+    }
+    LY_TRY(cut.cut<true>(nqc, n, N, select, rr.d_keys, rr.d_pcnt, st));
+    if (sort_dev) {   // sorted in LDS (k_pool_select), rows | distances | counts of the chunk back in one copy
+        uint32_t p2 = 2;
+        while (p2 < most) p2 <<= 1;
+        const uint32_t ok = most;   // output stride of the chunk on the device: no query emitted more
+        const size_t o_dist = (size_t)nqc * ok * 8, o_cnt = (size_t)nqc * ok * 12, o_all = o_cnt + (size_t)nqc * 4;
+        uint8_t* ob = reinterpret_cast<uint8_t*>(rr.d_out);
+        PoolRerankArgs x{};
+        x.pool_cnt = rr.d_pcnt;
+        x.pool_ld = N;
+        x.p2 = p2;
+        x.metric = metric;
+        x.k = ok;
+        x.out_k = ok;
+        x.out_rows = rr.d_out;
+        x.out_dists = reinterpret_cast<float*>(ob + o_dist);
+        x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
+        x.keys_out = rr.d_keys;
+        if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(nqc), dim3(1024), (size_t)p2 * 8, st, x);
+        else hipLaunchKernelGGL(k_pool_select<256>, dim3(nqc), dim3(256), (size_t)p2 * 8, st, x);
+        LY_HIP(hipGetLastError());
+        LY_TRY(launched());
+        h_out.resize((o_all + 7) / 8);
+        LY_HIP(hipMemcpyAsync(h_out.data(), rr.d_out, o_all, hipMemcpyDeviceToHost, st));
+        LY_TRY(stream_wait(st));
+        const uint8_t* hb = reinterpret_cast<const uint8_t*>(h_out.data());
+        for (uint32_t i = 0; i < nqc; ++i) {   // (k_pool_select padded a shorter result up to `ok`)
+            memcpy(out_rows + (size_t)i * out_k, hb + (size_t)i * ok * 8, (size_t)ok * 8);
+            memcpy(out_dists + (size_t)i * out_k, hb + o_dist + (size_t)i * ok * 4, (size_t)ok * 4);
+            pad(i, ok);
+        }
+    } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host, as select_pool_keys does for large pools
+        LY_TRY(launched());
+        keys.resize((size_t)nqc * N);
+        LY_HIP(hipMemcpyAsync(keys.data(), rr.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
+        LY_TRY(stream_wait(st));
+        for (uint32_t i = 0; i < nqc; ++i)
+            select_pool_keys(keys.data() + (size_t)i * N, out_counts[i], N, out_k, asc, out_rows + (size_t)i * out_k, out_dists + (size_t)i * out_k);
+    }
+    return LYNSE_OK;
+}
+
 // The LDS tiles of k_range_scan for rows of D floats and chunks of up to qc queries: up to 24 KiB of queries, then rows up to 78 KiB
 // in all (two workgroups per CU: one stages its tile while the other scores); a row too wide for that takes the whole LDS.
 static int range_plan(uint32_t D, uint64_t qc, uint32_t* TQ, uint32_t* R, uint32_t* stride, size_t* lds) {
@@ -148,64 +227,8 @@ extern "C" int lynse_hip_flat_search_range_f32(lynse_hip_flat* h, const float* q
             hipLaunchKernelGGL(k_range_scan, grid, dim3(RANGE_NT), lds, st, a);
         }
         LY_HIP(hipGetLastError());
-        p.cnt.resize(nqc);
-        LY_HIP(hipMemcpyAsync(p.cnt.data(), p.d_cnt, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-        LY_TRY(stream_wait(st));
-        // a query with more passers than N goes through the radix selection of its N best keys; any other takes every key below
-        // RANGE_FAIL (a state that starts done: the first 32 bits <= RANGE_FAIL - 1)
-        uint32_t most = 0;
-        bool select = false;
-        p.cut.sel0.resize(nqc);
-        for (uint32_t i = 0; i < nqc; ++i) {
-            const uint32_t c = p.cnt[i];
-            if (out_passed) out_passed[q0 + i] = c;
-            out_counts[q0 + i] = std::min(c, N);
-            most = std::max(most, std::min(c, N));
-            select = select || c > N;
-            p.cut.sel0[i] = c > N ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u};
-        }
-        if (most == 0) {
-            for (uint32_t i = 0; i < nqc; ++i) pad(q0 + i, 0);
-            continue;
-        }
-        LY_TRY(p.cut.cut<true>(nqc, n, N, select, p.rr.d_keys, p.rr.d_pcnt, st));
-        if (sort_dev) {   // sorted in LDS (k_pool_select), rows | distances | counts of the chunk back in one copy
-            uint32_t p2 = 2;
-            while (p2 < most) p2 <<= 1;
-            const uint32_t ok = most;   // output stride of the chunk on the device: no query emitted more
-            const size_t o_dist = (size_t)nqc * ok * 8, o_cnt = (size_t)nqc * ok * 12, o_all = o_cnt + (size_t)nqc * 4;
-            uint8_t* ob = reinterpret_cast<uint8_t*>(p.rr.d_out);
-            PoolRerankArgs x{};
-            x.pool_cnt = p.rr.d_pcnt;
-            x.pool_ld = N;
-            x.p2 = p2;
-            x.metric = metric;
-            x.k = ok;
-            x.out_k = ok;
-            x.out_rows = p.rr.d_out;
-            x.out_dists = reinterpret_cast<float*>(ob + o_dist);
-            x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
-            x.keys_out = p.rr.d_keys;
-            if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(nqc), dim3(1024), (size_t)p2 * 8, st, x);
-            else hipLaunchKernelGGL(k_pool_select<256>, dim3(nqc), dim3(256), (size_t)p2 * 8, st, x);
-            LY_HIP(hipGetLastError());
-            p.h_out.resize((o_all + 7) / 8);
-            LY_HIP(hipMemcpyAsync(p.h_out.data(), p.rr.d_out, o_all, hipMemcpyDeviceToHost, st));
-            LY_TRY(stream_wait(st));
-            const uint8_t* hb = reinterpret_cast<const uint8_t*>(p.h_out.data());
-            for (uint32_t i = 0; i < nqc; ++i) {   // (k_pool_select padded a shorter result up to `ok`)
-                memcpy(out_rows + (q0 + i) * max_results, hb + (size_t)i * ok * 8, (size_t)ok * 8);
-                memcpy(out_dists + (q0 + i) * max_results, hb + o_dist + (size_t)i * ok * 4, (size_t)ok * 4);
-                pad(q0 + i, ok);
-            }
-        } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host, as select_pool_keys does for large pools
-            p.keys.resize((size_t)nqc * N);
-            LY_HIP(hipMemcpyAsync(p.keys.data(), p.rr.d_keys, p.keys.size() * 8, hipMemcpyDeviceToHost, st));
-            LY_TRY(stream_wait(st));
-            for (uint32_t i = 0; i < nqc; ++i)
-                select_pool_keys(p.keys.data() + (size_t)i * N, out_counts[q0 + i], N, max_results, asc, out_rows + (q0 + i) * max_results,
-                                 out_dists + (q0 + i) * max_results);
-        }
+        LY_TRY(range_cut_and_order(p.cut, p.rr, p.d_cnt, p.cnt, p.keys, p.h_out, nqc, n, N, max_results, metric, st, out_rows + q0 * max_results,
+                                   out_dists + q0 * max_results, out_counts + q0, out_passed ? out_passed + q0 : nullptr, []() { return (int)LYNSE_OK; }));
     }
     return LYNSE_OK;
 }

@@ -419,3 +419,80 @@ def load_rabitq_index(path) -> RabitqIndexFile:
     codes, off = take(off, n * cb, np.uint8)
     norms, off = take(off, n, "<f4")
     return RabitqIndexFile(dim, padded, sw.astype(np.uint64), codes.reshape(n, cb).copy(), norms.astype(np.float32))
+
+
+# ---- sparse vectors: sparse_vectors.jsonl (SparseVectorRecord / SparseVectorStore, src/engine.rs:550-718) ----
+
+def _f32_json(x) -> str:
+    """the shortest decimal that reads back as the f32 `x`, laid out as serde_json's writer does (ryu): positional with at least one
+    fraction digit for 1e-5 <= |x| < 1e16, else d.ddde[-]X"""
+    x = np.float32(x)
+    if x == 0:
+        return "-0.0" if np.signbit(x) else "0.0"
+    mant, exp = np.format_float_scientific(x, unique=True, trim="-").split("e")
+    sign = "-" if mant.startswith("-") else ""
+    digits = mant.lstrip("-").replace(".", "")
+    e10 = int(exp)
+    if -5 <= e10 < 16:
+        if e10 < 0:
+            body = "0." + "0" * (-e10 - 1) + digits
+        elif len(digits) <= e10 + 1:
+            body = digits + "0" * (e10 + 1 - len(digits)) + ".0"
+        else:
+            body = digits[:e10 + 1] + "." + digits[e10 + 1:]
+        return sign + body
+    return sign + digits[0] + ("." + digits[1:] if len(digits) > 1 else "") + "e" + str(e10)
+
+
+def save_sparse_vectors(path, vectors: dict) -> None:
+    """SparseVectorStore::write_records (:697-717): one {"id":u64,"indices":[u32],"values":[f32]} record per line in ascending id
+    order, written to a temporary file and renamed into place.  `vectors`: id -> (indices, values), normalised."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    lines = []
+    for i in sorted(vectors):
+        idx, val = vectors[i]
+        lines.append('{"id":%d,"indices":[%s],"values":[%s]}\n' % (int(i), ",".join(str(int(x)) for x in idx), ",".join(_f32_json(v) for v in val)))
+    tmp = path.with_name(path.name + ".tmp")
+    with open(tmp, "w", encoding="utf-8") as f:
+        f.write("".join(lines))
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+
+
+def load_sparse_vectors(path) -> dict:
+    """SparseVectorStore::load (:573-617): blank lines skipped, an indices / values length mismatch refused with the reference's
+    message, every record normalised (normalize_sparse_entries), a record that normalises to empty removes its id, a later line for
+    an id wins -> id -> (indices u32, values f32).  A missing file is an empty store."""
+    from .core import sparse_normalize_arrays
+
+    path = Path(path)
+    out: dict = {}
+    if not path.exists():
+        return out
+    for line_no, line in enumerate(path.read_text(encoding="utf-8").splitlines()):
+        line = line.strip()
+        if not line:
+            continue
+        try:
+            rec = json.loads(line)
+            rid, indices, values = rec["id"], rec["indices"], rec["values"]
+            if not isinstance(rid, int) or isinstance(rid, bool) or rid < 0 or rid > 0xFFFFFFFFFFFFFFFF or any((not isinstance(x, int)) or isinstance(x, bool) or x < 0 or x > 0xFFFFFFFF for x in indices):
+                raise ValueError("id and indices must be unsigned integers")
+            vals = np.array([float(v) for v in values], dtype=np.float64)
+        except (ValueError, KeyError, TypeError) as e:
+            raise StorageError(f"failed to parse sparse vector record at line {line_no + 1}: {e}") from None
+        if len(indices) != len(values):
+            raise StorageError(f"sparse vector record for id {rid} has {len(indices)} indices but {len(values)} values")
+        with np.errstate(over="ignore"):
+            v32 = vals.astype(np.float32)
+        try:
+            _, idx, val = sparse_normalize_arrays(np.array([0, len(indices)], np.uint64), np.array(indices, np.uint32), v32)
+        except ValueError as e:
+            raise StorageError(str(e)) from None
+        if idx.size == 0:
+            out.pop(rid, None)
+        else:
+            out[rid] = (idx, val)
+    return out
