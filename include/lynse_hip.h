@@ -128,8 +128,9 @@ typedef struct lynse_hip_profile {
                                  pass), bit 7 the sample stage ran INSIDE the launch of the first threshold stage (one scan launch less than
                                  stages), bits 8..15 number of scan stages, bits 16..23 wave tiling
                                  (0x24 = <2,4,4,2>, 0x42 = <4,2,2,4>, 0x14 = <1,4,1,1>, 0x81 = the query-stationary k_scan_qs), bit 24 the self-tightening
-                                 single-launch scan, bit 25 the sample stage ran on the query-stationary tiling — lets a test pin the kernel
-                                 instantiation a benchmark configuration runs */
+                                 single-launch scan, bit 25 the sample stage ran on the query-stationary tiling, bit 26 the stages read the
+                                 non-negative 7-bit copy of the codes (SQ7: FLAT-IP, 129..256 queries, LYNSE_HIP_SQ7) — lets a test pin
+                                 the kernel instantiation a benchmark configuration runs */
 } lynse_hip_profile;
 
 /* ---- library ---- */
@@ -679,6 +680,15 @@ int lynse_hip_ivf_ticket_stats(lynse_hip_ivf *h, uint64_t *out);
  * norms), bit 3 unit-row cosine codes.  tests/test_gpu_certificate.py holds the bound against constructed worst cases. */
 int lynse_hip_flat_coarse_scores(lynse_hip_flat *h, const float *queries, uint64_t nq, int metric, int coarse,
                                  float *out_scores, float *out_bound, int *out_form);
+
+/* The same diagnostics for the SQ7 form of the FLAT-IP int8 pass: the scan of batches of 129..256 queries may read a NON-NEGATIVE 7-bit
+ * copy of the codes (scale 127 / range, codes 0..127 stored without an offset) instead of the SQ8 codes — chosen on non-negative shards
+ * of >= 10M rows, LYNSE_HIP_SQ7=1 / 0 forces / disables it; results never change, last_plan bit 26 tells.  129..256 queries;
+ * LYNSE_ERR_UNSUPPORTED where the shape has no SQ7 scan.  *out_form gains bit 4. */
+int lynse_hip_flat_coarse_scores_sq7(lynse_hip_flat *h, const float *queries, uint64_t nq, float *out_scores, float *out_bound, int *out_form);
+/* SQ7 state of a shard: rows the copy covers (0 = not built) and the overflows of its scan so far (each is re-answered on the SQ8 codes;
+ * 3 switch SQ7 off for the handle). */
+int lynse_hip_flat_sq7_state(lynse_hip_flat *h, uint64_t *out_rows, int *out_strikes);
 
 /* ---- sparse vectors: SparseVectorStore (src/engine.rs:550-718), index mode SPARSE-FLAT-IP ---- */
 

@@ -161,6 +161,8 @@ SIGNATURES = {
     "lynse_hip_ivf_build_sharded_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                                     _vp, _vp, _vp, C.POINTER(_vp)]),
     "lynse_hip_flat_coarse_scores": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
+    "lynse_hip_flat_coarse_scores_sq7": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_int)]),
+    "lynse_hip_flat_sq7_state": (C.c_int, [_vp, _u64p, C.POINTER(C.c_int)]),
     "lynse_hip_sparse_normalize": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "lynse_hip_sparse_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "lynse_hip_sparse_destroy": (C.c_int, [_vp]),

@@ -668,6 +668,21 @@ class FlatIndex:
         check(lib.lynse_hip_flat_coarse_scores(self._h, _ptr(q), q.shape[0], m, 1 if coarse in ("i8", "int8", 1, True) else 0, _ptr(scores), _ptr(bound), C.byref(form)))
         return scores, bound, form.value
 
+    def coarse_scores_sq7(self, queries):
+        """`coarse_scores` for the SQ7 form of the FLAT-IP int8 pass (`lynse_hip_flat_coarse_scores_sq7`): 129..256 queries, LYNSE_HIP_SQ7 not 0."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        scores = np.empty((q.shape[0], len(self)), np.float32)
+        bound = np.empty(q.shape[0], np.float32)
+        form = C.c_int(0)
+        check(lib.lynse_hip_flat_coarse_scores_sq7(self._h, _ptr(q), q.shape[0], _ptr(scores), _ptr(bound), C.byref(form)))
+        return scores, bound, form.value
+
+    def sq7_state(self) -> dict:
+        """Rows covered by the non-negative 7-bit copy of the codes (0: not built) and the overflow strikes of its scan (3 = switched off)."""
+        rows, strikes = C.c_uint64(0), C.c_int(0)
+        check(lib.lynse_hip_flat_sq7_state(self._h, C.byref(rows), C.byref(strikes)))
+        return {"sq7_rows": rows.value, "sq7_strikes": strikes.value}
+
     def coarse_state(self) -> dict:
         """State of the coarse-pass selection: overflow strikes of the certified int8 pass (3 = switched off, -1 = off because the
         rows are not finite) and the rows covered by the SQ8 codes built so far."""

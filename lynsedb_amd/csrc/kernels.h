@@ -2408,14 +2408,15 @@ __global__ void __launch_bounds__(256) k_sq8_minmax(const T* __restrict__ V, uin
     atomicMax(&omax[d], f32_to_ord(mx));
 }
 
+// top = the largest code: 255 (SQ8), 127 (the non-negative 7-bit copy, SQ7)
 __global__ void __launch_bounds__(256) k_sq8_scales(const uint32_t* __restrict__ omin, const uint32_t* __restrict__ omax, uint32_t D,
-                                                    float* __restrict__ mins, float* __restrict__ scales) {
+                                                    float* __restrict__ mins, float* __restrict__ scales, float top = 255.0f) {
     const uint32_t d = blockIdx.x * 256 + threadIdx.x;
     if (d >= D) return;
     const float mn = ord_to_f32(omin[d]), mx = ord_to_f32(omax[d]);
     const float range = __fsub_rn(mx, mn);
-    mins[d] = mn;
-    scales[d] = range > 1e-30f ? __fdiv_rn(255.0f, range) : 0.0f;
+    if (mins) mins[d] = mn;
+    scales[d] = range > 1e-30f ? __fdiv_rn(top, range) : 0.0f;
 }
 
 // did merging the new rows' min / max into the per-dimension table move any entry?  (ordered-int images; flag |= 1)
@@ -2438,10 +2439,10 @@ __global__ void __launch_bounds__(256) k_vec_minmax(const float* __restrict__ x,
         for (uint32_t j = 0; j < ncopies; ++j) { atomicMin(omin + j, f32_to_ord(mn)); atomicMax(omax + j, f32_to_ord(mx)); }
 }
 
-__device__ __forceinline__ int sq8_code(float v, float mn, float sc) {
+__device__ __forceinline__ int sq8_code(float v, float mn, float sc, float top = 255.0f) {
     float q = roundf(__fmul_rn(__fsub_rn(v, mn), sc));  // f32::round: half away from zero
     if (!(q == q)) return 0;
-    q = q < 0.0f ? 0.0f : (q > 255.0f ? 255.0f : q);
+    q = q < 0.0f ? 0.0f : (q > top ? top : q);
     return (int)q;
 }
 
@@ -2452,7 +2453,11 @@ __global__ void __launch_bounds__(256) k_sq8_quantize(const T* __restrict__ V, u
                                                       int8_t* __restrict__ out, uint32_t ld8, int* __restrict__ sums,
                                                       int* __restrict__ sums2, uint32_t* __restrict__ stats,
                                                       const float* __restrict__ extra_col = nullptr, uint32_t n_extra = 0,
-                                                      const float* __restrict__ row_scale = nullptr) {
+                                                      const float* __restrict__ row_scale = nullptr, int sq7 = 0) {
+    // sq7 != 0: the NON-NEGATIVE 7-bit copy (SQ7): scales = 127 / range, codes in [0, 127] stored WITHOUT the -128 offset — every product
+    // with a non-negative query image is non-negative (the int8 pipe draws less power on such operands).  stats[0] / stats[2]
+    // are taken over code - 64 (k_i8c_prep_queries moves the mid code's share of the query-residual term into B_q); the residual bound
+    // below holds as it stands (the f32 evaluation error is <= 127 * 2^-22 here).
     // extra_col != nullptr: columns D .. D + n_extra - 1 of the coded row all hold extra_col[row] (mins / scales have D + n_extra
     // entries) — the squared row norm of the L2 form of the certified int8 pass (k_i8c_prep_queries, aug); sums / sums2 may be
     // NULL then
@@ -2476,11 +2481,12 @@ __global__ void __launch_bounds__(256) k_sq8_quantize(const T* __restrict__ V, u
             if (d < D || (extra_col && d < D + n_extra)) {
                 const float v = d < D ? (row_scale ? __fmul_rn((float)V[row * ld + d], row_scale[row]) : (float)V[row * ld + d]) : extra_col[row];
                 if (!(fabsf(v) < LY_INF)) nonfinite += 1;
-                const int code = sq8_code(v, mins[d], scales[d]);
-                c = code - 128;
+                const int code = sq8_code(v, mins[d], scales[d], sq7 ? 127.0f : 255.0f);
+                c = sq7 ? code : code - 128;
+                const int cc = sq7 ? code - 64 : c;   // what the statistics are taken over
                 s1 += c;
-                s2 += c * c;
-                l1 += c < 0 ? -c : c;
+                s2 += cc * cc;
+                l1 += cc < 0 ? -cc : cc;
                 const float e = __fsub_rn(__fmul_rn(__fsub_rn(v, mins[d]), scales[d]), (float)code);   // (the value sq8_code rounded, minus the code)
                 const float ea = fabsf(e);
                 if (ea == ea) { e2 = __fmaf_rn(e, e, e2); e1 += ea; }
@@ -2591,6 +2597,12 @@ struct I8cPrepArgs {
     // Seeding of the self-tightening scan (ScanArgs::dyn_*; dyn_thr == nullptr: off): the integer dot products of this query's
     // image with seed_rows sample rows of the shard (spread over the tiles of every partition) give the first partition
     // maxima; dyn_marg = the margin 2E (+ the float evaluation error of B_q + s_q dot on both sides) in dot units, rounded up.
+    // sq7 = 1: the rows are the non-negative 7-bit codes (k_sq8_quantize, sq7): v_d = min_d + (c_d + eps_d) / scale7_d with c_d in [0, 127]
+    // stored as they are, so  q . v = [sum q_d min_d] + s_q sum u_d c_d + s_q sum eta_d c_d + sum w_d eps_d,  w = q / scale7: B_q loses its
+    // 128 sum w term.  The codes are not centred, and eta is known here exactly: s_q sum eta_d c_d = 64 s_q sum eta_d + s_q sum eta_d (c_d - 64);
+    // the first part goes into B_q, the second is bounded as before with a1 / a2sq taken over c - 64 (k_sq8_quantize) — without the split
+    // the query term carries the codes' mean (2-4x the margin on centred data).  mins / scales / eps2: the SQ7 copy's.
+    int sq7;
     const int8_t* codes;   // the rows the scan streams: [n_rows][ld8] signed SQ8 codes
     uint32_t ld8, n_rows, tile_rows, dyn_ks, seed_rows;
     int *dyn_thr, *dyn_slot, *dyn_marg;
@@ -2663,7 +2675,7 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
     // ---- the int8 image + sum eta_d^2 (eta_d = w_d / s_q - u_d: the residual of the query's own quantisation)
     const double inv = 1.0 / (double)s_sq;
     const uint32_t total = a.nslab * 128;
-    double eta2 = 0.0;
+    double eta2 = 0.0, eta1 = 0.0;
     for (uint32_t i = tid; i < total; i += 256) {
         int u = 0;
         if (i < DA) {
@@ -2674,14 +2686,15 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
             r = r < -127.0 ? -127.0 : (r > 127.0 ? 127.0 : r);
             u = (r == r) ? (int)r : 0;
             const double eta = t - (double)u;
-            if (eta == eta) eta2 += eta * eta;
+            if (eta == eta) { eta2 += eta * eta; eta1 += eta; }
         }
         const uint32_t s = i / 128, k = i % 128, l = k >> 4, e = k & 15, p = l ^ ((q >> 1) & 7);
         a.img[(((size_t)s * a.qpad + q) * 8 + p) * 16 + e] = (int8_t)u;
         if (a.dyn_thr) s_u[i] = (int8_t)u;
     }
-    for (int o = 32; o > 0; o >>= 1) eta2 += __shfl_xor(eta2, o, 64);
-    if (lane == 0) red2[1][wave] = eta2;
+    for (int o = 32; o > 0; o >>= 1) { eta2 += __shfl_xor(eta2, o, 64); eta1 += __shfl_xor(eta1, o, 64); }
+    __shared__ double red3[4];
+    if (lane == 0) { red2[1][wave] = eta2; red3[wave] = eta1; }
     __syncthreads();
     if (tid == 0) {
         wmax = fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]));
@@ -2692,9 +2705,11 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
         sw2 = (red2[0][0] + red2[0][1]) + (red2[0][2] + red2[0][3]);
         eta2 = (red2[1][0] + red2[1][1]) + (red2[1][2] + red2[1][3]);
         const float sq = s_sq;
-        const double bq = sqm + 128.0 * sw - (a.aug ? s2 : 0.0) - (a.cosine ? 1.0 : 0.0);
+        eta1 = (red3[0] + red3[1]) + (red3[2] + red3[3]);
+        const double bq = sqm + (a.sq7 ? 64.0 * (double)sq * eta1 : 128.0 * sw) - (a.aug ? s2 : 0.0) - (a.cosine ? 1.0 : 0.0);
         const float bqf = (float)bq;
         const double a1 = (double)a.a1;
+        const double a1mag = a.sq7 ? a1 + 64.0 * (double)DA : a1;   // |dot| <= 127 a1mag (sq7: sum c <= sum |c - 64| + 64 D)
         const double gam = 10.0 * (double)a.D * 5.9604645e-8;  // reference f32 accumulation order vs the real dot product
         const double ref_term = a.cosine ? 9.0 * ((double)a.D + 8.0) * 5.9604645e-8
                                 : a.aug  ? 8.0 * ((double)a.D + 8.0) * 5.9604645e-8 * (s2 + (double)a.vmax * (double)a.vmax)
@@ -2708,7 +2723,7 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
         double tq = 0.5001 * (double)sq * a1, tr = 0.5001 * swabs;
         if (a.a2sq) { const double c2 = 1.0002 * (double)sq * sqrt(eta2) * sqrt((double)a.a2sq); tq = c2 < tq ? c2 : tq; }
         if (a.eps2 > 0.0f) { const double c2 = 1.0002 * sqrt(sw2) * sqrt((double)a.eps2); tr = c2 < tr ? c2 : tr; }
-        double E = tr + tq + 2.5e-7 * (fabs(bq) + (a.cosine ? 1.0 : fabs(s2)) + 127.0 * (double)sq * a1) + ref_term;
+        double E = tr + tq + 2.5e-7 * (fabs(bq) + (a.cosine ? 1.0 : fabs(s2)) + 127.0 * (double)sq * a1mag) + ref_term;
         float bq_out = bqf;
         if (a.l2n) {
             const double vm2 = (double)a.vmax * (double)a.vmax;

@@ -325,6 +325,17 @@ struct lynse_hip_flat {
     uint32_t sq8_a1 = 0, sq8_a2sq = 0;   // max row L1 / sum of squares of the signed codes
     float sq8_eps2 = 0.0f;                 // bound of the max row sum of squared quantisation residuals (k_sq8_quantize stats[3])
     bool sq8_finite = false;
+    uint64_t sq8_fit = 0;   // counts the fits of the min / max table (a new fit recodes every row: ensure_sq8_locked)
+    // SQ7: the NON-NEGATIVE 7-bit copy of the codes (scale 127 / range, codes [0, 127] stored without the offset; layout, pitch and minima
+    // of `sq8`) the 129..256-query IP scan streams instead of `sq8` when rows — and with them, presumably, queries — are non-negative: every
+    // MAC of the int8 pipe is then non-negative and the power-capped scan holds a higher clock.  Follows the SQ8 life cycle.
+    int8_t* sq7 = nullptr;
+    uint64_t n_sq7 = 0, sq7_cap = 0, sq7_fit = 0;   // sq7_fit: the sq8_fit the copy was coded under
+    float* sq7_scales = nullptr;
+    uint32_t* sq7_stats = nullptr;
+    uint32_t sq7_a1 = 0, sq7_a2sq = 0;   // max row sum / sum of squares of the (uncentred) codes
+    float sq7_eps2 = 0.0f;
+    std::atomic<int> sq7_strikes{0};       // overflows of the SQ7 scan (each re-answered on the SQ8 codes); 3 switch it off for the handle
     // the L2 form of the certified int8 pass: SQ8 codes of the AUGMENTED rows [v, |v|^2] (k_i8c_prep_queries, aug = 1), pitch
     // ld8a = round_up(dim + 1, 128) (whole 128-column slabs: the non-ragged scan kernels), built lazily on the first L2 batch
     // of 33..256 queries
@@ -519,7 +530,8 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     for (void* p : {(void*)h->rows, (void*)h->rows_h, (void*)h->rows16, (void*)h->packed, (void*)h->vn2, (void*)h->vrinv, (void*)h->d_stats,
                     (void*)h->g_rows16, (void*)h->g_vn2, (void*)h->g_vrinv, (void*)h->g_ids32,
                     (void*)h->bpm, (void*)h->sq8c, (void*)h->sq8c_mins, (void*)h->sq8c_scales, (void*)h->sq8c_mm, (void*)h->sq8c_stats, (void*)h->sq8a, (void*)h->sq8a_mins, (void*)h->sq8a_scales, (void*)h->sq8a_mm, (void*)h->sq8a_stats,
-                    (void*)h->sq8, (void*)h->sq8_mins, (void*)h->sq8_scales, (void*)h->sq8_sum, (void*)h->sq8_sum2, (void*)h->sq8_mm, (void*)h->sq8_stats, (void*)h->sq8_mm_prev})
+                    (void*)h->sq8, (void*)h->sq8_mins, (void*)h->sq8_scales, (void*)h->sq8_sum, (void*)h->sq8_sum2, (void*)h->sq8_mm, (void*)h->sq8_stats, (void*)h->sq8_mm_prev,
+                    (void*)h->sq7, (void*)h->sq7_scales, (void*)h->sq7_stats})
         if (p) (void)hipFree(p);
     for (auto& c : h->ctx)
         if (c.stream) (void)hipStreamDestroy(c.stream);
@@ -1797,6 +1809,9 @@ static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked = false)
 // lynse_hip_flat_coarse_scores: one emit-all stage over the whole (small) shard, then stop — the candidate buffer then holds the
 // coarse score of every (row, query) exactly as the scan kernels compute it
 static thread_local bool tl_coarse_dump = false;
+static int fused_sample_env() { return env_int("LYNSE_HIP_FUSED_SAMPLE", 0); }   // (read per call: tests flip it)
+static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked);
+static bool sq7_ready(const lynse_hip_flat* h);
 // flat_assign_top1_device: the lane-max scan of the k-means assignment over EVERY tile of the (small) centroid store, then stop —
 // k_assign_pick reads the keys (kernels.h)
 static thread_local bool tl_assign = false;
@@ -1807,7 +1822,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                      size_t* ev_used, std::vector<std::pair<size_t, uint64_t>>* scan_events, bool* sampled_plan,
                      const uint32_t* mask = nullptr, const uint32_t* row_ids = nullptr, bool i8c = false,
                      uint64_t* r_dst = nullptr, float* d_dst = nullptr, uint32_t* c2_dst = nullptr, uint32_t* any_ovf = nullptr,
-                     const float* qsrc = nullptr, bool hdr_direct = false, bool allow_sts = true, bool* used_sts = nullptr) {
+                     const float* qsrc = nullptr, bool hdr_direct = false, bool allow_sts = true, bool* used_sts = nullptr,
+                     bool allow_sq7 = false, bool* used_sq7 = nullptr) {
+    // allow_sq7 / used_sq7: the chunk may scan the non-negative 7-bit copy of the codes / did (the blocking FLAT search and the certificate
+    // diagnostics pass true; an overflow is re-answered on the SQ8 codes, without a strike against the int8 pass)
     // allow_sts / used_sts: the self-tightening single-launch scan may answer this chunk / did (an overflow of it is retried on the
     // staged plan of the same coarse pass, without a strike)
     // qsrc: the float queries of the chunk when they already live in device memory that stays valid for the whole search (no
@@ -1867,6 +1885,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                      k >= 1 && k <= 32 && qs_variant() >= 1 && qs_variant() <= 3 && sts_ld8 == 768 && nslab == 6 && qpad == 256 && h->n >= 65536 &&
                      h->n < 0xffffff00ull && (metric == M_IP || cosq);
     if (used_sts) *used_sts = sts;
+    // SQ7: same kernels, same plan — only the code rows every stage reads and the prep outputs (B_q, E) differ
+    // (sq7_wanted is the whole predicate of the shape: IP, 129..256 queries — so no small / mid tiling —, no self-tightening or fused-sample plan)
+    const bool sq7 = allow_sq7 && i8c && !bin_mfma && !mask && !row_ids && sq7_wanted(h, metric, nq, false) && sq7_ready(h);
+    if (used_sq7) *used_sq7 = sq7;
     if (bin_mfma) {
         // (the prep kernels write every byte of the image: the lines of their queries, pad columns included, and — blocks nq .. qpad - 1 of the
         // grid — zero lines for the pad queries of the tile; up to round 5 a hipMemsetAsync of the image ran in front: a launch of its own)
@@ -1889,6 +1911,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         if (i8c_cs_on()) { p.a2sq = aug ? h->sq8a_a2sq : (cosq ? h->sq8c_a2sq : h->sq8_a2sq); p.eps2 = aug ? h->sq8a_eps2 : (cosq ? h->sq8c_eps2 : h->sq8_eps2); } p.cosine = cosq ? 1 : 0; p.img = reinterpret_cast<int8_t*>(w.Q16); p.aug = aug ? (int)h->aug_cols : 0; p.l2n = l2n ? 1 : 0;
         p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
+        if (sq7) {
+            p.sq7 = 1; p.scales = h->sq7_scales; p.a1 = h->sq7_a1;
+            if (i8c_cs_on()) { p.a2sq = h->sq7_a2sq; p.eps2 = h->sq7_eps2; }
+        }
         if (sts) {   // seed the partition maxima of the self-tightening scan from a few sample rows (valid thresholds from the first tile on)
             p.codes = cosq ? h->sq8c : h->sq8; p.ld8 = sts_ld8; p.n_rows = (uint32_t)h->n; p.tile_rows = 64; p.dyn_ks = k;
             p.seed_rows = std::min<uint32_t>(1024u, 32u * k);
@@ -1950,7 +1976,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     // than the two launches it replaces (MI355X, 1.25M x 768 x 256: 366 us against 33 + 26 + 261 us; s_memtime stamps,
     // scripts/dbg_fs_stamps.py: first tile 32 us, hand-over 1 27 us, select 15 us, hand-over 2 17 us, restart): a grid-wide
     // hand-over drains the LDS-DMA ring of every CU and idles the chip twice, which costs more than a kernel boundary.
-    const int fs_env = env_int("LYNSE_HIP_FUSED_SAMPLE", 0);   // (read per call: tests flip it)
+    const int fs_env = fused_sample_env();
     const bool fs = fs_env != 0 && !debug_flags_env() && i8c && !aug && !cosq && !l2n && !bin_mfma && !mid64 && !mid128 && h->ld8 % 128 == 0 && sample_threshold_only && plan.size() >= 2 && k <= 32 &&
                     sample.sample_tiles == (uint32_t)h->num_cu && (plan[1].r1 - plan[1].r0 + 255) / 256 >= (uint32_t)h->num_cu &&
                     (uint64_t)k * 50000ull > (uint64_t)sample.sample_tiles * plan_tile &&   // (the stage behind the sample runs the DENSE epilogue)
@@ -2016,6 +2042,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             if (h16) tile_rows = narrow ? 128u : 256u;
             a.V16 = h->rows16; a.ld16 = h->ld16;
             if (i8c) { a.V16 = reinterpret_cast<const _Float16*>(bin_mfma ? (const int8_t*)h->bpm : (aug ? h->sq8a : (cosq ? h->sq8c : h->sq8))); a.ld16 = bin_mfma ? h->ld_bpm : (aug ? h->ld8a : h->ld8); }
+            if (sq7) a.V16 = reinterpret_cast<const _Float16*>(h->sq7);
             if (glds && !small && big_rows == 192 && metric == M_IP) tile_rows = 192u;
             a.qpad = qpad; a.nq = nq; a.nslab = nslab; a.ntiles = (s.r1 - s.r0 + tile_rows - 1) / tile_rows;
             if (s.sample_tiles) a.ntiles = s.sample_tiles;
@@ -2222,7 +2249,8 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         std::lock_guard<std::mutex> plk(h->prof_mu);
         h->prof.last_plan = (sample.sample_tiles ? 1u : 0u) | ((sample.sample_tiles && sample_threshold_only) ? 2u : 0u) | (i8c ? 4u : 0u) |
                             (plan_used_segments ? 8u : 0u) | (small ? 16u : 0u) | (fs ? 128u : 0u) | ((uint64_t)(plan.size() & 0xff) << 8) | (tiling << 16) |
-                            (sts ? (1ull << 24) : 0ull) | (plan_qs_sample ? (1ull << 25) : 0ull);   // bit 24: self-tightening single-launch scan; bit 25: sample stage on the query-stationary tiling
+                            (sts ? (1ull << 24) : 0ull) | (plan_qs_sample ? (1ull << 25) : 0ull) |   // bit 24: self-tightening single-launch scan; bit 25: sample stage on the query-stationary tiling
+                            (sq7 ? (1ull << 26) : 0ull);   // bit 26: the stages read the non-negative 7-bit copy of the codes (SQ7)
     }
     FinalArgs fa{};
     fa.cand = w.cand; fa.count = w.count; fa.k = k; fa.out_k = out_k; fa.cap = w.cap; fa.metric = key_metric; fa.ip_form = ip_form;
@@ -2458,6 +2486,7 @@ static int ensure_sq8_locked(lynse_hip_flat* h) {
         else hipLaunchKernelGGL(k_sq8_minmax<float>, dim3(gx, gy), dim3(256), 0, cur(h).stream, h->rows, h->ld, h->dim, h->n, h->sq8_mm, h->sq8_mm + h->dim);
     }
     if (r0 == 0) {   // a new fit: every row is coded (again)
+        ++h->sq8_fit;
         LY_HIP(hipMemsetAsync(h->sq8_stats, 0, 16, cur(h).stream));
         hipLaunchKernelGGL(k_sq8_scales, dim3(gx), dim3(256), 0, cur(h).stream, h->sq8_mm, h->sq8_mm + h->dim, h->dim, h->sq8_mins, h->sq8_scales);
     }
@@ -2478,6 +2507,82 @@ static int ensure_sq8_locked(lynse_hip_flat* h) {
     h->n_sq8 = h->n;
     return LYNSE_OK;
 }
+
+// LYNSE_HIP_SQ7: 0 = never, 1 = wherever the shape is eligible (any shard size, any sign), unset = auto (read per call: tests flip it)
+static int sq7_env() { return env_int("LYNSE_HIP_SQ7", -1); }
+// auto: from this many rows on — the smallest measured shard at which the gain of the whole step passes the three-spreads rule
+// (profiles/sq7_bench_ab.json: LYNSE_HIP_SQ7=0 against 1 at 2.4M / 4M / 6M / 8M rows gains 5 / 19 / 43 / 52 us, each short of three times
+// the spread of its runs (8M: 52.2 us); the 10M step gains 80 us against 58).  It loses nowhere from 2.4M rows on; LYNSE_HIP_SQ7=1 forces it.
+static const uint64_t SQ7_AUTO_MIN_ROWS = 10000000ull;
+// Does a FLAT-IP batch of nqc queries over this shard scan the SQ7 copy?  The query-stationary tiling with more than 128 queries, whole
+// 128-column slabs; auto: only over non-negative rows (the host cannot see the sign of a device-resident batch: non-negative rows are
+// the proxy for non-negative queries — a mixed-sign batch over them is still answered exactly, without the gain).
+static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked) {
+    const int e = sq7_env();
+    if (e == 0 || metric != M_IP || masked || nqc <= 128 || nqc > QCHUNK || h->qchunk > QCHUNK) return false;
+    if (scan_variant() != 3 || qs_variant() < 1 || qs_variant() > 3 || !qs_width_ok(h->ld8, (h->dim + 127) / 128, false)) return false;
+    if (sts_env_on() || fused_sample_env() != 0) return false;   // (those plans keep the SQ8 codes)
+    if (h->sq7_strikes.load() >= 3) return false;
+    return e == 1 || (h->rows_nonneg && h->n >= SQ7_AUTO_MIN_ROWS);
+}
+// The copy only changes speed: a shape that scans it gets it built here (writer lock), and a build that fails — no memory for one more byte
+// per element — leaves the batch on the SQ8 codes and switches SQ7 off for the handle.  A copy the handle will not scan again (struck
+// out, or rows that turned mixed-sign under auto) is freed.
+static void sq7_release_locked(lynse_hip_flat* h) {
+    if (h->sq7) (void)hipFree(h->sq7);
+    h->sq7 = nullptr; h->sq7_cap = 0; h->n_sq7 = 0;
+}
+static bool sq7_stale(const lynse_hip_flat* h) { return h->sq7 && (h->sq7_strikes.load() >= 3 || (!h->rows_nonneg && sq7_env() != 1)); }
+static int ensure_sq7_locked(lynse_hip_flat* h);
+static void sq7_sync_locked(lynse_hip_flat* h, int metric, uint64_t nqc, bool masked) {
+    if (sq7_stale(h)) sq7_release_locked(h);
+    if (!sq7_wanted(h, metric, nqc, masked) || !h->sq8 || h->n_sq8 != h->n || !h->sq8_finite) return;
+    if (ensure_sq7_locked(h) != LYNSE_OK) {
+        (void)hipGetLastError();
+        sq7_release_locked(h);
+        h->sq7_strikes.store(3);
+    }
+}
+// The SQ7 copy, from the fit of the SQ8 codes (which must be up to date): rows appended under an unchanged fit are coded alone and
+// raise the maxima; a new fit codes every row again.  (Callers: sq7_sync_locked.)
+static int ensure_sq7_locked(lynse_hip_flat* h) {
+    if (h->sq7 && h->n_sq7 == h->n && h->sq7_fit == h->sq8_fit) return LYNSE_OK;
+    if (!h->sq8 || h->n_sq8 != h->n) return set_error(LYNSE_ERR_INTERNAL, "the SQ7 copy is built from the fit of up-to-date SQ8 codes");
+    hipStream_t st = cur(h).stream;
+    const bool kept = h->sq7 != nullptr && h->sq7_cap >= h->n && h->sq7_fit == h->sq8_fit && h->n_sq7 < h->n;
+    if (h->sq7_cap < h->n) {
+        sq7_release_locked(h);
+        const uint64_t cap = std::max<uint64_t>(h->capacity, h->n);
+        LY_HIP(hipMalloc(&h->sq7, (size_t)cap * h->ld8 + 256));
+        h->sq7_cap = cap;
+    }
+    if (!h->sq7_scales) {
+        LY_HIP(hipMalloc(&h->sq7_scales, (size_t)h->dim * 4));
+        LY_HIP(hipMalloc(&h->sq7_stats, 16));
+    }
+    const uint64_t r0 = kept ? h->n_sq7 : 0;
+    if (r0 == 0) {
+        LY_HIP(hipMemsetAsync(h->sq7_stats, 0, 16, st));
+        hipLaunchKernelGGL(k_sq8_scales, dim3((h->dim + 255) / 256), dim3(256), 0, st, h->sq8_mm, h->sq8_mm + h->dim, h->dim, (float*)nullptr, h->sq7_scales, 127.0f);
+    }
+    const uint64_t nn = h->n - r0;
+    const uint32_t qgrid = (uint32_t)std::min<uint64_t>((nn + 3) / 4, (uint64_t)h->num_cu * 16);
+    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3(qgrid), dim3(256), 0, st, (const _Float16*)h->rows_h + r0 * h->ld16, h->ld16, h->dim, nn, h->sq8_mins, h->sq7_scales,
+                                      h->sq7 + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq7_stats, (const float*)nullptr, 0u, (const float*)nullptr, 1);
+    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3(qgrid), dim3(256), 0, st, h->rows + r0 * h->ld, h->ld, h->dim, nn, h->sq8_mins, h->sq7_scales,
+                            h->sq7 + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq7_stats, (const float*)nullptr, 0u, (const float*)nullptr, 1);
+    LY_HIP(hipGetLastError());
+    uint32_t qst[4] = {0, 0, 0, 0};
+    LY_HIP(hipMemcpyAsync(qst, h->sq7_stats, 16, hipMemcpyDeviceToHost, st));
+    LY_HIP(hipStreamSynchronize(st));
+    h->sq7_a1 = qst[0];
+    h->sq7_a2sq = qst[2];
+    memcpy(&h->sq7_eps2, &qst[3], 4);
+    h->n_sq7 = h->n;
+    h->sq7_fit = h->sq8_fit;
+    return LYNSE_OK;
+}
+static bool sq7_ready(const lynse_hip_flat* h) { return h->sq7 && h->n_sq7 == h->n && h->sq7_fit == h->sq8_fit && h->sq8 && h->n_sq8 == h->n; }
 
 // The augmented code set of the L2 form (rows [v, |v|^2]): rebuilt over all rows when rows were appended, like the SQ8 set.
 static int ensure_sq8a_locked(lynse_hip_flat* h) {
@@ -2848,7 +2953,11 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         // (filtered: what matters is the MASKED int8 scan — a gathered-rows search goes exclusive anyway)
         // a batch that takes the certified int8 pass needs its codes; every other float batch the f16 shadow (a lazy copy too).  The
         // chunks of a large batch can differ (the last one may be small): the chunk loop checks again and restarts under the writer lock
-        if (i8c_eligible(h, metric, false, std::min<uint64_t>(nq, QCHUNK), caller_holds_exclusive, filtered)) return i8c_codes_ready(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered);
+        if (i8c_eligible(h, metric, false, std::min<uint64_t>(nq, QCHUNK), caller_holds_exclusive, filtered)) {
+            // (the blocking search alone scans the SQ7 copy: a wanted copy that is missing, or a stale one, is dealt with under the writer lock)
+            if (sq7_stale(h) || (sq7_wanted(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) && h->sq8_finite && !sq7_ready(h))) return false;
+            return i8c_codes_ready(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered);
+        }
         return shadow_ready(h) || small_path_ok(h, std::min<uint64_t>(nq, QCHUNK), (uint32_t)std::min<uint64_t>(k, h->n), metric, filtered);
     };
     // k beyond the candidate capacity of one pass (k > cap / 4 over more than cap rows; the reference accepts any k, and its
@@ -3083,7 +3192,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         bool i8c = i8c_eligible(h, metric, filtered && direct, nqc, caller_holds_exclusive, filtered && !direct);
         if (i8c) {
             const bool msk = filtered && !direct;
-            if (xlk.owns_lock()) LY_TRY(ensure_i8c_codes_locked(h, metric, nqc, msk));   // lazy build: exclusive path only
+            if (xlk.owns_lock()) { LY_TRY(ensure_i8c_codes_locked(h, metric, nqc, msk)); sq7_sync_locked(h, metric, nqc, msk); }   // lazy builds: exclusive path only (a chunk without the SQ7 copy scans the SQ8 codes)
             else if (!i8c_codes_ready(h, metric, nqc, msk)) i8c = false;                    // (shared path: derived_ready() saw them built)
             if (i8c && !i8c_codes_finite(h, metric, nqc, msk)) { i8c_strike_counter(h, metric).store(-1); i8c = false; }
         }
@@ -3110,9 +3219,9 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             }
             continue;
         }
-        bool allow_sts = true;
+        bool allow_sts = true, allow_sq7 = true;
         for (int level = 0; level < 3; ++level) {  // sampled plan -> contiguous plan -> exhaustive plan (make_plan)
-            bool sampled = false, used_sts = false;
+            bool sampled = false, used_sts = false, used_sq7 = false;
             // k_final writes the results where they belong — the caller's device arrays, or the pinned (device-visible)
             // staging buffer for small host-API results: no copy kernels behind the search; only large host results go
             // through the workspace + two device-to-host copies.  One synchronisation per chunk (counts + overflow flags in
@@ -3122,7 +3231,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             uint64_t* r_dst = on_device ? out_rows + q0 * k : (staged ? reinterpret_cast<uint64_t*>(w.h_out) : nullptr);
             float* d_dst = on_device ? out_dists + q0 * k : (staged ? reinterpret_cast<float*>(w.h_out + rows_b) : nullptr);
             LY_TRY(run_chunk(h, nqc, kk, k, metric, level, st, &ev_used, &scan_events, &sampled, mask, direct ? h->g_ids32 : nullptr, i8c,
-                             r_dst, d_dst, on_device ? out_counts + q0 : nullptr, nullptr, qsrc, true, allow_sts, &used_sts));
+                             r_dst, d_dst, on_device ? out_counts + q0 : nullptr, nullptr, qsrc, true, allow_sts, &used_sts, allow_sq7, &used_sq7));
             if (!on_device && !staged) {
                 LY_HIP(hipMemcpyAsync(out_rows + q0 * k, w.out_rows, rows_b, out_kind, st));
                 LY_HIP(hipMemcpyAsync(out_dists + q0 * k, w.out_dists, dists_b, out_kind, st));
@@ -3138,6 +3247,12 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             fallback_queries += nov;
             if (used_sts) {  // the self-tightening scan overflowed (scores rising along every workgroup's chunk): the staged plan of the same coarse pass
                 allow_sts = false;
+                --level;
+                continue;
+            }
+            if (used_sq7) {  // the wider SQ7 margin overflowed: the same plan level on the SQ8 codes — a strike against SQ7, none against int8
+                allow_sq7 = false;
+                h->sq7_strikes.fetch_add(1);
                 --level;
                 continue;
             }
@@ -3169,8 +3284,8 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
 // float expressions), in the metric's own space (IP: score, L2 / cosine: distance), and the per-query bound E the prep kernel
 // certified (the margin the pipeline keeps is 2E).  coarse = 0: the f16 shadow, 1: the certified int8 pass in the form a batch of
 // this shape would take; *out_form: bit 0 int8, bit 1 augmented-L2 codes, bit 2 plain-code L2, bit 3 unit-row cosine codes.
-extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* queries, uint64_t nq, int metric, int coarse,
-                                            float* out_scores, float* out_bound, int* out_form) {
+static int coarse_scores_impl(lynse_hip_flat* h, const float* queries, uint64_t nq, int metric, int coarse,
+                              float* out_scores, float* out_bound, int* out_form, bool want_sq7) {
     if (!h || !queries || !out_scores || !out_bound) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (metric_additive(metric)) return metric_check(metric);
     if (metric < M_IP || metric > M_COS) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "float metrics only");
@@ -3186,6 +3301,9 @@ extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* quer
     if (i8c) {
         LY_TRY(ensure_i8c_codes_locked(h, metric, nq));
         if (!i8c_codes_finite(h, metric, nq)) return set_error(LYNSE_ERR_UNSUPPORTED, "the shard holds non-finite values: no int8 pass");
+        if (want_sq7) sq7_sync_locked(h, metric, nq, false);
+        if (want_sq7 && !(sq7_wanted(h, metric, nq, false) && sq7_ready(h)))
+            return set_error(LYNSE_ERR_UNSUPPORTED, "no SQ7 scan for this shape (FLAT-IP, 129..256 queries, LYNSE_HIP_SQ7 not 0)");
     }
     Workspace& w = cur(h).ws;
     hipStream_t st = cur(h).stream;
@@ -3194,13 +3312,16 @@ extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* quer
     std::vector<std::pair<size_t, uint64_t>> scan_events;
     bool sampled = false;
     tl_coarse_dump = true;
-    const int rc = run_chunk(h, (uint32_t)nq, 1, 1, metric, 1, st, &ev_used, &scan_events, &sampled, nullptr, nullptr, i8c);
+    bool used_sq7 = false;
+    const int rc = run_chunk(h, (uint32_t)nq, 1, 1, metric, 1, st, &ev_used, &scan_events, &sampled, nullptr, nullptr, i8c,
+                             nullptr, nullptr, nullptr, nullptr, nullptr, false, true, nullptr, want_sq7, &used_sq7);
     tl_coarse_dump = false;
     LY_TRY(rc);
+    if (want_sq7 && !used_sq7) return set_error(LYNSE_ERR_INTERNAL, "the diagnostics chunk did not scan the SQ7 copy");
     LY_HIP(hipStreamSynchronize(st));
     const bool l2n = i8c && metric == M_L2 && l2_plain(h, nq, false);
     const bool aug = i8c && metric == M_L2 && !l2n, cosq = i8c && metric == M_COS;
-    if (out_form) *out_form = (i8c ? 1 : 0) | (aug ? 2 : 0) | (l2n ? 4 : 0) | (cosq ? 8 : 0);
+    if (out_form) *out_form = (i8c ? 1 : 0) | (aug ? 2 : 0) | (l2n ? 4 : 0) | (cosq ? 8 : 0) | (used_sq7 ? 16 : 0);
     const bool key_asc = metric_ascending((aug || cosq) ? (int)M_IP : metric);
     std::vector<uint64_t> keys(h->n);
     std::vector<float> m2(nq);
@@ -3214,6 +3335,24 @@ extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* quer
         }
         out_bound[q] = 0.5f * m2[q];
     }
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_coarse_scores(lynse_hip_flat* h, const float* queries, uint64_t nq, int metric, int coarse,
+                                            float* out_scores, float* out_bound, int* out_form) {
+    return coarse_scores_impl(h, queries, nq, metric, coarse, out_scores, out_bound, out_form, false);
+}
+// The same diagnostics for the SQ7 form of the FLAT-IP int8 pass (129..256 queries, LYNSE_HIP_SQ7 not 0; forced with 1 on any shard):
+// coarse scores of the non-negative 7-bit copy and the bound E its prep certified; *out_form gains bit 4.
+extern "C" int lynse_hip_flat_coarse_scores_sq7(lynse_hip_flat* h, const float* queries, uint64_t nq, float* out_scores, float* out_bound, int* out_form) {
+    return coarse_scores_impl(h, queries, nq, M_IP, 1, out_scores, out_bound, out_form, true);
+}
+// SQ7 state of a shard (tests, diagnostics): rows the copy covers (0: not built) and its overflow strikes (3 switch it off).
+extern "C" int lynse_hip_flat_sq7_state(lynse_hip_flat* h, uint64_t* out_rows, int* out_strikes) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    if (out_rows) *out_rows = h->sq7 ? h->n_sq7 : 0;
+    if (out_strikes) *out_strikes = h->sq7_strikes.load();
     return LYNSE_OK;
 }
 
@@ -3256,6 +3395,7 @@ extern "C" int lynse_hip_flat_prepare(lynse_hip_flat* h, int metric, uint64_t nq
     if (i8c_eligible(h, metric, false, nqc)) {
         LY_TRY(ensure_i8c_codes_locked(h, metric, nqc));
         if (!i8c_codes_finite(h, metric, nqc)) i8c_strike_counter(h, metric).store(-1);
+        else sq7_sync_locked(h, metric, nqc, false);
     }
     // a batch that does not take the int8 pass scans the f16 shadow (unless the exact few-query kernel answers it)
     if (!i8c_eligible(h, metric, false, nqc) && !small_path_ok(h, nqc, 10, metric, false)) LY_TRY(ensure_shadow_locked(h));
@@ -3273,6 +3413,7 @@ extern "C" uint64_t lynse_hip_flat_hbm_bytes(const lynse_hip_flat* h) {
     if (h->vn2) b += 2ull * (h->stats_capacity + 256) * 4;
     if (h->packed) b += h->packed_capacity * h->words * 8ull;
     if (h->sq8) b += h->sq8_cap * h->ld8 + 2ull * (h->sq8_cap + 256) * 4;
+    if (h->sq7) b += h->sq7_cap * h->ld8;
     if (h->sq8a) b += h->sq8a_cap * h->ld8a;
     if (h->sq8c) b += h->sq8c_cap * h->ld8;
     if (h->bpm) b += h->bpm_cap * h->ld_bpm;
@@ -3565,7 +3706,7 @@ extern "C" int lynse_hip_top_k_search(const float* query, const float* candidate
     lynse_hip_flat* h = sc.h;
     {   // empty the shard (capacity and buffers stay)
         std::unique_lock<std::shared_mutex> lk(h->rw);
-        h->n = 0; h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->n_sq8 = 0; h->n_sq8a = 0; h->n_sq8c = 0; h->n_bpm = 0; h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
+        h->n = 0; h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->n_sq8 = 0; h->n_sq7 = 0; h->sq7_strikes.store(0); h->n_sq8a = 0; h->n_sq8c = 0; h->n_bpm = 0; h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
         h->amax = h->vmax = h->vmin = 0.f; h->sv = 1.f; h->cos_degenerate = 0; h->rows_integer = 0; h->rows_nonneg = 0;
         const uint32_t init[5] = {0u, 0u, 0x7f800000u, 0u, 0u};
         LY_TRY(use_device(h));

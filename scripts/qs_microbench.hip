@@ -4,6 +4,8 @@
 // 1. correctness: both kernels over a small shard (ragged last tile) against a brute-force kernel — identical key sets;
 // 2. timing: interleaved rounds over a large shard, HIP events, plus the shader clock each QS variant held
 //    (s_memtime ticks of workgroup 0 / event time) and wall-clock stamps a power sampler can be joined on.
+// 0. `qs_microbench operand [rows rounds sigma]`: the operand-distribution axis instead (row bytes uniform / non-negative / 6-bit / constant x
+//    query image non-negative / mixed sign, the library's default instantiation with and without emission; profiles/sq7_operand_energy.txt).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -pragma-unroll-threshold=262144 \
 //        [-DLYNSE_EXPERIMENTS] -o qs_microbench scripts/qs_microbench.hip
 #include <algorithm>
@@ -34,16 +36,21 @@ __device__ __host__ inline uint32_t mix(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
     return (uint32_t)x;
 }
-__global__ void k_fill_rows(int8_t* V, uint64_t nbytes, uint64_t seed) {
+// (and_mask, or_bits) shape the byte distribution: 0xffffffff / 0 = uniform int8, 0x7f7f7f7f = [0,127], 0x3f3f3f3f = [0,63], 0 / c c c c = constant
+__global__ void k_fill_rows(int8_t* V, uint64_t nbytes, uint64_t seed, uint32_t and_mask = 0xffffffffu, uint32_t or_bits = 0u) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i * 4 < nbytes; i += (uint64_t)gridDim.x * blockDim.x)
-        reinterpret_cast<uint32_t*>(V)[i] = mix(i + seed * 0x9e3779b97f4a7c15ull);
+        reinterpret_cast<uint32_t*>(V)[i] = (mix(i + seed * 0x9e3779b97f4a7c15ull) & and_mask) | or_bits;
 }
-// queries: plain [nq][D] int8 in [-127,127] and the kernel's image [nslab][qpad][8 slots ^ swizzle][16]
-__global__ void k_fill_queries(int8_t* plain, int8_t* img, uint32_t nq, uint32_t qpad, uint32_t D, uint32_t nslab) {
+// queries: plain [nq][D] int8 in [-127,127] (nonneg: [0,127]) and the kernel's image [nslab][qpad][8 slots ^ swizzle][16]
+__device__ __host__ inline int query_elem(uint32_t q, uint32_t i, bool nonneg) {
+    const uint32_t h = mix(0x1234567ull + (uint64_t)q * 100003 + i);
+    return nonneg ? (int)(h % 128u) : (int)(h % 255u) - 127;
+}
+__global__ void k_fill_queries(int8_t* plain, int8_t* img, uint32_t nq, uint32_t qpad, uint32_t D, uint32_t nslab, bool nonneg = false) {
     const uint32_t q = blockIdx.x;
     for (uint32_t i = threadIdx.x; i < nslab * 128; i += blockDim.x) {
         int u = 0;
-        if (q < nq && i < D) { u = (int)(mix(0x1234567ull + (uint64_t)q * 100003 + i) % 255u) - 127; plain[(size_t)q * D + i] = (int8_t)u; }
+        if (q < nq && i < D) { u = query_elem(q, i, nonneg); plain[(size_t)q * D + i] = (int8_t)u; }
         const uint32_t s = i / 128, k = i % 128, l = k >> 4, e = k & 15, p = l ^ ((q >> 1) & 7);
         img[(((size_t)s * qpad + q) * 8 + p) * 16 + e] = (int8_t)u;
     }
@@ -290,6 +297,9 @@ static std::vector<uint64_t> collect(const Bufs& b, uint32_t nq, uint32_t nseg, 
 }
 
 int main(int argc, char** argv) {
+    // "operand" as the first argument: the operand-distribution axis (section 0 below) instead of the variant A/B; the other arguments follow it
+    const bool operand_axis = argc > 1 && strcmp(argv[1], "operand") == 0;
+    if (operand_axis) { --argc; ++argv; }
     const uint64_t n_big = argc > 1 ? strtoull(argv[1], nullptr, 10) : 10000000ull;
     const int rounds = argc > 2 ? atoi(argv[2]) : 5;
     const double sigma_tight = argc > 3 ? atof(argv[3]) : 4.3;   // thresholds in units of the dot product's standard deviation
@@ -407,6 +417,138 @@ int main(int argc, char** argv) {
         CK(hipMemsetAsync(b.segcnt, 0, (size_t)NQ * 4096, 0));
         (void)nseg;
     };
+
+
+    // ---- 0. operand-distribution axis (first argument "operand"): the library's default instantiation, everything / no emission, over
+    // row bytes (a) uniform [-128,127] (b) uniform [0,127] (c) uniform [0,63] (d) constant, and query images in [0,127] / [-127,127].
+    // Same protocol as section 2 (long_warm launches of the SAME cell, then long_reps timed, `rounds` rounds kept after one discarded);
+    // thresholds per query at mean + sigma_tight sd of ITS dot products over the rows, so every cell emits the same sparse share.
+    if (operand_axis) {
+        struct Dist { const char* name; uint32_t and_mask, or_bits; double mean, var; };
+        const Dist dists[4] = {{"(a) rows uniform [-128,127]", 0xffffffffu, 0u, -0.5, (65536.0 - 1.0) / 12.0},
+                               {"(b) rows uniform [0,127]", 0x7f7f7f7fu, 0u, 63.5, (16384.0 - 1.0) / 12.0},
+                               {"(c) rows uniform [0,63]", 0x3f3f3f3fu, 0u, 31.5, (4096.0 - 1.0) / 12.0},
+                               {"(d) rows constant 0x55", 0u, 0x55555555u, 85.0, 0.0}};
+        const char* qkinds[2] = {"queries [0,127]", "queries [-127,127]"};
+        const Variant* two[2] = {nullptr, nullptr};
+        for (const Variant& v : vars) {
+            if (v.name == "qs RB2 SL6 NS3 noXPF NBUF8 PP1") two[0] = &v;
+            if (v.name == "qs RB2 SL6 NS3 noXPF NBUF8 PP1 | no emission") two[1] = &v;
+        }
+        if (!two[0] || !two[1]) { fprintf(stderr, "the operand axis needs -DLYNSE_EXPERIMENTS (the no-emission row)\n"); return 2; }
+        const uint32_t n = (uint32_t)n_big;
+        auto fill = [&](const Dist& d, bool nonneg) {
+            hipLaunchKernelGGL(k_fill_rows, dim3(ncu * 8), dim3(256), 0, 0, b.V, n_big * D, 7ull, d.and_mask, d.or_bits);
+            hipLaunchKernelGGL(k_fill_queries, dim3(QPAD), dim3(256), 0, 0, b.Qp, b.img, NQ, QPAD, D, NSLABS, nonneg);
+            CK(hipDeviceSynchronize());
+        };
+        auto set_thr_cell = [&](const Dist& d, bool nonneg, double sig) {   // T_q = mean_c sum(u) + sig sd_c |u| (+1: a constant shard emits nothing)
+            std::vector<float> one(NQ, 1.0f), zero(NQ, 0.0f), th(NQ);
+            std::vector<int> ti(NQ);
+            for (uint32_t q = 0; q < NQ; ++q) {
+                double su = 0.0, su2 = 0.0;
+                for (uint32_t i = 0; i < D; ++i) { const double u = query_elem(q, i, nonneg); su += u; su2 += u * u; }
+                th[q] = (float)(std::floor(d.mean * su + sig * std::sqrt(d.var * su2)) + 1.0);
+                ti[q] = (int)th[q];
+            }
+            CK(hipMemcpy(b.qinv, one.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.qn2, zero.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.thr, th.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.Ti, ti.data(), NQ * 4, hipMemcpyHostToDevice));
+        };
+        int bad0 = 0;
+        // key sets against the brute-force kernel on a small ragged shard, every cell (the default instantiation)
+        for (int di = 0; di < 4; ++di)
+            for (int qk = 0; qk < 2; ++qk) {
+                const uint32_t ns = 65536u + 37u;
+                fill(dists[di], qk == 0);
+                set_thr_cell(dists[di], qk == 0, 3.0);
+                uint64_t* ref_d; uint32_t* ref_n;
+                const uint32_t ref_cap = 4u << 20;
+                CK(hipMalloc(&ref_d, (size_t)ref_cap * 8)); CK(hipMalloc(&ref_n, 4)); CK(hipMemset(ref_n, 0, 4));
+                hipLaunchKernelGGL(k_ref, dim3((ns + 63) / 64), dim3(256), 0, 0, b.V, D, D, ns, b.Qp, NQ, b.Ti, ref_d, ref_n, ref_cap);
+                CK(hipDeviceSynchronize());
+                uint32_t rn; CK(hipMemcpy(&rn, ref_n, 4, hipMemcpyDeviceToHost));
+                std::vector<uint64_t> ref(std::min(rn, ref_cap));
+                CK(hipMemcpy(ref.data(), ref_d, ref.size() * 8, hipMemcpyDeviceToHost));
+                std::sort(ref.begin(), ref.end());
+                CK(hipFree(ref_d)); CK(hipFree(ref_n));
+                ScanArgs a = base_args(b, 0, ns, NQ);
+                a.nseg = ncu * two[0]->segs_per_wg;
+                a.seg = std::min<uint32_t>(255u, SEG_KEYS / a.nseg);
+                clear(a.nseg);
+                two[0]->launch(a, ncu, 0);
+                CK(hipDeviceSynchronize());
+                const std::vector<uint64_t> got = collect(b, NQ, a.nseg, a.seg);
+                const bool ok = got == ref;
+                bad0 += !ok;
+                printf("check %-28s %-20s n %u sigma 3.0: %zu reference keys, %zu scanned%s\n", dists[di].name, qkinds[qk], ns, ref.size(), got.size(), ok ? "" : "   <-- MISMATCH");
+            }
+        struct Cell { std::vector<float> ms; double clk = 0, watts = 0, smhz = 0, keys = -1; };
+        Cell cells[4][2][2];
+        hipEvent_t e0, e1;
+        CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        for (int r = 0; r < rounds + 1; ++r)
+            for (int di = 0; di < 4; ++di)
+                for (int qk = 0; qk < 2; ++qk) {
+                    fill(dists[di], qk == 0);
+                    set_thr_cell(dists[di], qk == 0, sigma_tight);
+                    for (int vi = 0; vi < 2; ++vi) {
+                        const Variant& v = *two[vi];
+                        Cell& c = cells[di][qk][vi];
+                        ScanArgs a = base_args(b, 0, n, NQ);
+                        a.nseg = ncu * v.segs_per_wg;
+                        a.seg = std::min<uint32_t>(255u, SEG_KEYS / a.nseg);
+                        a.debug_flags = 64 | (vi == 1 ? 2 : 0); a.dbg = b.dbg;
+                        for (int w = 0; w < long_warm; ++w) { if (w < 2) clear(a.nseg); v.launch(a, ncu, 0); }
+                        clear(a.nseg);
+                        CK(hipDeviceSynchronize());
+                        sampler.begin();
+                        CK(hipEventRecord(e0, 0));
+                        for (int i = 0; i < long_reps; ++i) v.launch(a, ncu, 0);
+                        CK(hipEventRecord(e1, 0));
+                        CK(hipEventSynchronize(e1));
+                        { double pw, mz; sampler.end(&pw, &mz); if (r == rounds) { c.watts = pw; c.smhz = mz; } }
+                        float t; CK(hipEventElapsedTime(&t, e0, e1));
+                        if (r > 0) c.ms.push_back(t / long_reps);
+                        unsigned long long tk[2];
+                        CK(hipMemcpy(tk, b.dbg, 16, hipMemcpyDeviceToHost));
+                        c.clk = (double)(tk[1] - tk[0]) / (t / long_reps * 1e3);
+                        if (r == rounds && vi == 0) {   // keys one launch emits per query
+                            clear(a.nseg); v.launch(a, ncu, 0);
+                            CK(hipDeviceSynchronize());
+                            const auto per = collect_q(b, NQ, a.nseg, a.seg);
+                            size_t tot = 0;
+                            for (auto& pq : per) tot += pq.size();
+                            c.keys = (double)tot / NQ;
+                        }
+                    }
+                }
+        printf("---- operand axis: %u rows x %u B, %u queries, thresholds at %.1f sd; us per launch: median / min / spread (max - min) of %d rounds of %d launches behind %d warm-up launches\n",
+               n, D, NQ, sigma_tight, rounds, long_reps, long_warm);
+        double med_of[4][2][2], spread_of[4][2][2];
+        for (int vi = 0; vi < 2; ++vi) {
+            printf("-- %s\n", vi == 0 ? "everything" : "no emission");
+            for (int di = 0; di < 4; ++di)
+                for (int qk = 0; qk < 2; ++qk) {
+                    Cell& c = cells[di][qk][vi];
+                    std::sort(c.ms.begin(), c.ms.end());
+                    const double med = c.ms[c.ms.size() / 2] * 1e3, mn = c.ms.front() * 1e3, sp = (c.ms.back() - c.ms.front()) * 1e3;
+                    med_of[di][qk][vi] = med; spread_of[di][qk][vi] = sp;
+                    printf("%-28s %-20s %8.1f %8.1f %7.1f   %5.2f TB/s   %6.0f MHz   hwmon %6.0f W %6.0f MHz", dists[di].name, qkinds[qk], med, mn, sp, (double)n * D / med / 1e6, c.clk, c.watts, c.smhz);
+                    if (c.keys >= 0) printf("   %.0f keys per query", c.keys);
+                    printf("\n");
+                }
+        }
+        for (int vi = 0; vi < 2; ++vi) {
+            const double gain = med_of[0][0][vi] - med_of[1][0][vi], need = 3.0 * spread_of[0][0][vi];
+            printf("DECISION (%s, queries [0,127]): (a) %.1f us - (b) %.1f us = %.1f us; three times the spread of (a)'s rounds = %.1f us -> %s\n", vi == 0 ? "everything" : "no emission",
+                   med_of[0][0][vi], med_of[1][0][vi], gain, need, gain > need ? "CONTINUE" : "STOP");
+        }
+        sampler.finish();
+        printf("mismatches: %d\n", bad0);
+        return bad0 ? 1 : 0;
+    }
 
     // ---- 1. correctness on a small shard with a ragged end, two query counts, two thresholds, full and starved segments
     int bad = 0;
