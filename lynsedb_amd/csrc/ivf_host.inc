@@ -1127,13 +1127,13 @@ static int ivf_grow(T** p, size_t* cap, size_t need) {
 }
 
 static int launch_scan_tiled(const ScanArgs& a, int metric, bool scale, uint32_t grid, hipStream_t st) {
-    if (scan_variant() == 3) return launch_scan_h16<1, 4, 1, 1, 3, 3, true>(a, metric, grid, st);
+    if (scan_variant() == 3) return launch_scan_h16<with(F16_SMALL, &H16Cfg::tiled, true)>(a, metric, grid, st);
 #ifdef LYNSE_EXPERIMENTS
     const size_t lds = (size_t)4 * (SCAN_BR * GL_BK * 4 + 32 * GL_BK * 2) + 4 * 1024;
-#define LY_GOT(M, S) return launch_lds<k_scan_glds<1, 4, 1, 1, M, S, 4, 2, true>>(grid, 256, lds, st, a)
-    if (scale) { switch (metric) { case M_IP: LY_GOT(M_IP, true); case M_L2: LY_GOT(M_L2, true); default: LY_GOT(M_COS, true); } }
-    switch (metric) { case M_IP: LY_GOT(M_IP, false); case M_L2: LY_GOT(M_L2, false); default: LY_GOT(M_COS, false); }
-#undef LY_GOT
+    auto go = [&](auto s) {
+        return with_metric(metric, [&](auto m) { return launch_lds<k_scan_glds<1, 4, 1, 1, decltype(m)::value, decltype(s)::value, 4, 2, true>>(grid, 256, lds, st, a); });
+    };
+    return scale ? go(std::true_type{}) : go(std::false_type{});
 #else
     (void)scale;
     return set_error(LYNSE_ERR_UNSUPPORTED, "superseded scan variants need make EXPERIMENTS=1");
@@ -1509,8 +1509,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         const uint32_t grid = ntiles_dev ? (uint32_t)s->num_cu * 2 : std::min<uint32_t>(a.ntiles, (uint32_t)s->num_cu * 2);
         if (i8c) {
             a.V16 = reinterpret_cast<const _Float16*>(aug ? s->sq8a : (cosq ? s->sq8c : s->sq8)); a.ld16 = aug ? s->ld8a : s->ld8;
-            constexpr size_t lds = (size_t)(3 * 128 + 3 * 32) * 128;
-            LY_TRY((launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, true, false, 0, false, 2>>(grid, 256, lds, st, a)));
+            LY_TRY((launch_h16<with(I8C_SMALL, &H16Cfg::tiled, true)>(grid, st, a)));
         } else
         LY_TRY(launch_scan_tiled(a, metric, s->sv != 1.0f, grid, st));
         }

@@ -1380,6 +1380,27 @@ __device__ __forceinline__ f32x16 ly_mfma_fp4(V a, V b, f32x16 c, int unit) {
 
 constexpr int HK = 64;  // K elements per slab
 
+// An instantiation of k_scan_h16 by name: one field per template parameter, in the template's order and with its defaults (the host
+// writes them with designated initialisers and launches through launch_h16, lynse_hip.hip).
+struct H16Cfg {
+    int wq, wr, tq, tr, metric, nsv, nsq, nt_hint;
+    bool tiled = false, rag = true;
+    int dbg = 0;
+    bool filt = false;
+    int i8q = 0, emit = -1, place = 0;
+    bool dense = false, prio = false, qcreg = true;
+    int fs = 0;
+};
+constexpr int h16_threads(H16Cfg c) { return c.wq * c.wr * 64; }
+// Dynamic LDS of an instantiation: NSV row stages + NSQ query stages of one 128-B line per row / query, + the norm ring (NSV + 1 slots
+// of 1 KiB) when it fits into the 160 KiB of a CU.  The certified int8 and FP4 forms (I8Q = 2 / 3) never have a norm ring; every other
+// form is given one, whether its kernel keeps norms in LDS (NORMS_LDS) or not.  The kernel asserts its layout against this value.
+constexpr size_t h16_lds_bytes(H16Cfg c) {
+    const size_t rings = (size_t)(c.nsv * c.wr * c.tr * 32 + c.nsq * c.wq * c.tq * 32) * (HK * 2), norms = (size_t)(c.nsv + 1) * 1024;
+    const bool norm_ring = c.i8q != 2 && c.i8q != 3 && rings + norms <= 160 * 1024;
+    return norm_ring ? rings + norms : rings;
+}
+
 // DBG (compile-time experiments, never launched by the product path): 1 no MFMA, 2 no LDS fragment reads,
 // 4 no query-image DMA, 8 no row DMA, 16 no epilogue.  FILT compiles the subset-filter paths in (mask / row_ids of ScanArgs): they
 // cost registers the unfiltered kernel does not have to spare (56 B/lane of scratch and 13 % of its speed when they
@@ -1495,6 +1516,9 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
     uint32_t qs_qslab = a.qpad * LINE;
     constexpr bool NORMS_LDS = !TILED && !I8C && (METRIC != M_IP || I8) && (NORM_RING + (NSV + 1) * 1024 <= 160 * 1024);
     constexpr int NORM_SLOTS = NSV + 1;
+    static_assert((size_t)(NORMS_LDS ? NORM_RING + NORM_SLOTS * 1024 : NORM_RING) <=
+                      h16_lds_bytes(H16Cfg{WQ, WR, TQ, TR, METRIC, NSV, NSQ, NT_HINT, TILED, RAG, DBG, FILT, I8Q, EMIT, PLACE, DENSE, PRIO, QCREG, FS}),
+                  "the LDS the body addresses ends inside what the launch asks for");
     // Per-query constants of the epilogue (1/scale, the additive term, the threshold): constant for the whole launch, so each
     // wave keeps the TQ*32 queries of its column in QCN registers per constant (query q of the column lives in lane q % 64 of
     // register q / 64) and the epilogue fetches its lane's value with ds_bpermute.  Loading them from global memory in the

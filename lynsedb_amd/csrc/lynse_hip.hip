@@ -1041,6 +1041,52 @@ static int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A
     return LYNSE_OK;
 }
 
+// ---- the three MFMA scan kernels, launched by name ----------------------------------------------------------------------------------
+// A site names an instantiation as a config value (H16Cfg, QsCfg, QhCfg: next to each kernel); these helpers are the one place that maps
+// a config to the kernel's positional template arguments, and the block size and LDS bytes of the launch follow from the config.
+template <H16Cfg C>
+static int launch_h16(dim3 grid, hipStream_t st, const ScanArgs& a) {
+    return launch_lds<k_scan_h16<C.wq, C.wr, C.tq, C.tr, C.metric, C.nsv, C.nsq, C.nt_hint, C.tiled, C.rag, C.dbg, C.filt, C.i8q, C.emit, C.place, C.dense, C.prio, C.qcreg, C.fs>>(
+        grid, h16_threads(C), h16_lds_bytes(C), st, a);
+}
+template <QsCfg C>
+static int launch_qs(dim3 grid, hipStream_t st, const ScanArgs& a) {
+    return launch_lds<k_scan_qs<C.nslab, C.rb, C.sl, C.ns, C.xpf, C.nbuf, C.dbg, C.ping, C.sts, C.met, C.smp, C.msk, C.f4>>(grid, QS_THREADS, qs_lds_bytes(C), st, a);
+}
+template <QhCfg C>
+static int launch_qh(dim3 grid, hipStream_t st, const ScanArgs& a) {
+    return launch_lds<k_scan_qh<C.nslab, C.met, C.ns, C.nbuf, C.qb, C.smp>>(grid, QH_THREADS, qh_lds_bytes(C), st, a);
+}
+// A copy of config c with some members set: with(I8C_256, &H16Cfg::emit, 1, &H16Cfg::rag, true).
+template <class C, class T, class V, class... More>
+constexpr C with(C c, T C::*member, V value, More... more) {
+    c.*member = value;
+    if constexpr (sizeof...(more) > 0) return with(c, more...);
+    else return c;
+}
+// f(std::integral_constant<int, M>{}) for the run-time metric of a float scan (IP, squared L2, everything else scores as cosine)
+template <class F>
+static int with_metric(int metric, F&& f) {
+    switch (metric) {
+    case M_IP: return f(std::integral_constant<int, M_IP>{});
+    case M_L2: return f(std::integral_constant<int, M_L2>{});
+    default: return f(std::integral_constant<int, M_COS>{});
+    }
+}
+// Timing experiments (make EXPERIMENTS=1): BASE with DBG = the run-time value dbg, which has to be one of VALUES (the ones compiled).
+// DBG is a bit set (kernels.h): 1 no MFMA, 2 no LDS fragment reads, 4 no query-image DMA, 8 no row DMA, 16 no epilogue.  What the
+// compiled combinations leave running:
+//    1 DMA + LDS reads              2 DMA + MFMA                    3 DMA only             4 everything but the query-image DMA
+//    7 row DMA only                 8 everything but the row DMA   11 query DMA only      12 MFMA + LDS reads + epilogue (no DMA)
+//   13 LDS reads only              14 MFMA only                    15 the loop and the epilogue alone
+//   16 everything but the epilogue, and without it: 17 as 1, 19 as 3, 20 as 4, 24 as 8, 28 MFMA + LDS reads only, 30 MFMA only
+template <H16Cfg BASE, int... VALUES>
+static int dispatch_dbg(int dbg, dim3 grid, hipStream_t st, const ScanArgs& a) {
+    int rc = LYNSE_OK;   // (a left fold: the kernels are instantiated, and laid out in the code object, in the order of VALUES)
+    const bool known = (... || (dbg == VALUES ? (rc = launch_h16<with(BASE, &H16Cfg::dbg, VALUES)>(grid, st, a), true) : false));
+    return known ? rc : set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
+}
+
 static int ensure_workspace(lynse_hip_flat* h, uint32_t k /* caller's k = output stride */) {
     Workspace& w = cur(h).ws;
     const uint32_t nslab = (h->dim + SCAN_BK - 1) / SCAN_BK;
@@ -1163,11 +1209,7 @@ static int launch_scan(lynse_hip_flat* h, const ScanArgs& a, int metric, uint32_
     constexpr int BQ = WQ * TQ * 32;
     const size_t lds = scan_lds_bytes(BQ);
     (void)h;
-    switch (metric) {
-    case M_IP: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_IP, PD>>(grid, NT, lds, st, a);
-    case M_L2: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_L2, PD>>(grid, NT, lds, st, a);
-    default: return launch_lds<k_scan_f16<WQ, WR, TQ, TR, M_COS, PD>>(grid, NT, lds, st, a);
-    }
+    return with_metric(metric, [&](auto m) { return launch_lds<k_scan_f16<WQ, WR, TQ, TR, decltype(m)::value, PD>>(grid, NT, lds, st, a); });
 }
 
 template <int WQ, int WR, int TQ, int TR, int NS>
@@ -1177,18 +1219,11 @@ static int launch_scan_glds(const ScanArgs& a, int metric, bool scale, uint32_t 
     constexpr int BR = WR * TR * 32;
     const size_t lds = (size_t)NS * (BR * GL_BK * 4 + BQ * GL_BK * 2) + (metric == M_IP ? 0 : (size_t)NS * 1024);  // + per-tile norm ring
     static const int nt_hint = env_int("LYNSE_HIP_SCAN_NT", 1);
-#define LY_GO(M, S, H) return launch_lds<k_scan_glds<WQ, WR, TQ, TR, M, S, NS, H>>(grid, NT, lds, st, a)
-    if (nt_hint) {
-        if (scale) {
-            switch (metric) { case M_IP: LY_GO(M_IP, true, 2); case M_L2: LY_GO(M_L2, true, 2); default: LY_GO(M_COS, true, 2); }
-        }
-        switch (metric) { case M_IP: LY_GO(M_IP, false, 2); case M_L2: LY_GO(M_L2, false, 2); default: LY_GO(M_COS, false, 2); }
-    }
-    if (scale) {
-        switch (metric) { case M_IP: LY_GO(M_IP, true, 0); case M_L2: LY_GO(M_L2, true, 0); default: LY_GO(M_COS, true, 0); }
-    }
-    switch (metric) { case M_IP: LY_GO(M_IP, false, 0); case M_L2: LY_GO(M_L2, false, 0); default: LY_GO(M_COS, false, 0); }
-#undef LY_GO
+    auto go = [&](auto s, auto hint) {
+        return with_metric(metric, [&](auto m) { return launch_lds<k_scan_glds<WQ, WR, TQ, TR, decltype(m)::value, decltype(s)::value, NS, decltype(hint)::value>>(grid, NT, lds, st, a); });
+    };
+    if (nt_hint) return scale ? go(std::true_type{}, std::integral_constant<int, 2>{}) : go(std::false_type{}, std::integral_constant<int, 2>{});
+    return scale ? go(std::true_type{}, std::integral_constant<int, 0>{}) : go(std::false_type{}, std::integral_constant<int, 0>{});
 }
 
 #endif  // LYNSE_EXPERIMENTS
@@ -1236,82 +1271,59 @@ static int scan_variant() {
 #endif
 }
 
-// k_scan_h16 launcher: LDS = NSV row stages + NSQ query stages + the norm ring (NSV+1 slots of 1 KiB) when it fits.
+// Named tilings of the float scan over the f16 shadow (launch_scan_h16 sets the metric and the ragged / filter / emission fields per
+// call).  nt_hint = 2 everywhere: the rows are streamed once.
+constexpr H16Cfg F16_SMALL{.wq = 1, .wr = 4, .tq = 1, .tr = 1, .metric = M_IP, .nsv = 3, .nsq = 3, .nt_hint = 2};      // 128 rows x 32 queries
+constexpr H16Cfg F16_IP_256{.wq = 2, .wr = 4, .tq = 4, .tr = 2, .metric = M_IP, .nsv = 3, .nsq = 2, .nt_hint = 2};     // 256 x 256, 3 + 2 stages
+constexpr H16Cfg F16_L2_256{.wq = 4, .wr = 2, .tq = 2, .tr = 4, .metric = M_L2, .nsv = 2, .nsq = 2, .nt_hint = 2};     // 256 x 256, 2 + 2 stages + norms
+
+// k_scan_h16 launcher for the tiling BASE.
 // The 256 x 256 tilings compile ONE epilogue per emission mode (EMIT template parameter: 0 threshold stages, 1 emit-all
 // first stage, 2 lane-max sample stage — one body with all three spills, kernels.h) and only the tiling / metric pairs
 // the product path uses: <2,4,4,2> for unfiltered IP, <4,2,2,4> for L2 / cosine and every subset-filtered scan.
 // The <= 32-query kernel and the IVF work-list kernel (<1,4,1,1>) keep the runtime emission switch (no spills there).
-template <int WQ, int WR, int TQ, int TR, int NSV, int NSQ, bool TILED>
+template <H16Cfg BASE>
 static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st, uint32_t grid_y = 1) {
-    constexpr int BQ = WQ * TQ * 32, BR = WR * TR * 32;
-    constexpr size_t rings = (size_t)(NSV * BR + NSQ * BQ) * (HK * 2);
-    const size_t lds = (rings + (NSV + 1) * 1024 <= 160 * 1024) ? rings + (NSV + 1) * 1024 : rings;
-    constexpr int NT = WQ * WR * 64;
     const dim3 g(grid, grid_y);
     const bool filt = a.mask != nullptr || a.row_ids != nullptr;
     const bool ragged = a.ld16 % HK != 0;
 #ifdef LYNSE_EXPERIMENTS
-    if constexpr (WQ == 2 && WR == 4 && !TILED) {  // timing experiments (LYNSE_HIP_DEBUG_FLAGS bits 8..11 = DBG << 8)
+    if constexpr (BASE.wq == 2 && BASE.wr == 4 && !BASE.tiled) {  // timing experiments (LYNSE_HIP_DEBUG_FLAGS bits 8..11 = DBG << 8)
         if (metric == M_IP && !filt && !ragged && ((a.debug_flags >> 8) & 15)) {
-            switch ((a.debug_flags >> 8) & 15) {
-            case 1: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 1>>(grid, NT, lds, st, a);
-            case 2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 2>>(grid, NT, lds, st, a);
-            case 3: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 3>>(grid, NT, lds, st, a);
-            case 7: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 7>>(grid, NT, lds, st, a);
-            case 11: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 11>>(grid, NT, lds, st, a);
-            case 12: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 12>>(grid, NT, lds, st, a);
-            case 15: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 15>>(grid, NT, lds, st, a);
-            case 14: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 14>>(grid, NT, lds, st, a);
-            case 13: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 13>>(grid, NT, lds, st, a);
-            case 4: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 4>>(grid, NT, lds, st, a);
-            case 8: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false, 8>>(grid, NT, lds, st, a);
-            default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
-            }
+            constexpr H16Cfg C = with(BASE, &H16Cfg::metric, M_IP, &H16Cfg::rag, false);
+            return dispatch_dbg<C, 1, 2, 3, 7, 11, 12, 15, 14, 13, 4, 8>((a.debug_flags >> 8) & 15, grid, st, a);
         }
     }
-#endif
-#ifdef LYNSE_EXPERIMENTS
-    if constexpr (WQ == 4 && WR == 2 && TR == 4 && !TILED) {  // decomposition of the low-D L2 scan (C3): LYNSE_HIP_DEBUG_FLAGS bits 8..12 = DBG << 8
+    if constexpr (BASE.wq == 4 && BASE.wr == 2 && BASE.tr == 4 && !BASE.tiled) {  // decomposition of the low-D L2 scan (C3): LYNSE_HIP_DEBUG_FLAGS bits 8..12 = DBG << 8
         const int dbg = (a.debug_flags >> 8) & 31;
         if (metric == M_L2 && !filt && !ragged && dbg && a.emit_all == 0) {
-            switch (dbg) {
-            case 16: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 16, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue
-            case 17: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 17, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // + no MFMA (DMA + LDS reads)
-            case 19: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 19, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // DMA only
-            case 20: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 20, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue, no query DMA
-            case 24: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 24, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // no epilogue, no row DMA
-            case 28: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 28, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA + LDS reads only
-            case 30: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 30, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA only
-            case 12: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 12, false, 0, 0, 0, true>>(grid, NT, lds, st, a);   // MFMA + LDS reads + epilogue (no DMA)
-            case 4: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, false, false, 4, false, 0, 0, 0, true>>(grid, NT, lds, st, a);     // everything but the query DMA
-            default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
-            }
+            constexpr H16Cfg C = with(BASE, &H16Cfg::metric, M_L2, &H16Cfg::rag, false, &H16Cfg::emit, 0, &H16Cfg::dense, true);
+            return dispatch_dbg<C, 16, 17, 19, 20, 24, 28, 30, 12, 4>(dbg, grid, st, a);
         }
     }
 #endif
-    if constexpr (WQ * WR == 8 && !TILED) {
+    if constexpr (BASE.wq * BASE.wr == 8 && !BASE.tiled) {
         // one kernel per (metric, ragged / filter variant, emission mode)
         auto by_emit = [&](auto mtag, auto ragtag, auto filtag) -> int {
-            constexpr int M = decltype(mtag)::value;
-            constexpr bool RG = decltype(ragtag)::value, FL = decltype(filtag)::value;
-            if constexpr (WR < 4 && !FL && M != M_IP) {  // many survivors per block expected: one-pass epilogue (kernels.h, DENSE)
-                if (a.emit_all == 0 && a.dense) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0, 0, true>>(g, NT, lds, st, a);
+            constexpr H16Cfg C = with(BASE, &H16Cfg::metric, decltype(mtag)::value, &H16Cfg::rag, decltype(ragtag)::value, &H16Cfg::filt, decltype(filtag)::value, &H16Cfg::emit, 0);
+            if constexpr (C.wr < 4 && !C.filt && C.metric != M_IP) {  // many survivors per block expected: one-pass epilogue (kernels.h, DENSE)
+                if (a.emit_all == 0 && a.dense) return launch_h16<with(C, &H16Cfg::dense, true)>(g, st, a);
             }
-            if (a.emit_all == 0) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 0>>(g, NT, lds, st, a);
-            if constexpr (!FL) {  // (the lane-max sample stage exists for the unfiltered tilings only)
-                if (a.emit_all == 2) return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 2>>(g, NT, lds, st, a);
+            if (a.emit_all == 0) return launch_h16<C>(g, st, a);
+            if constexpr (!C.filt) {  // (the lane-max sample stage exists for the unfiltered tilings only)
+                if (a.emit_all == 2) return launch_h16<with(C, &H16Cfg::emit, 2)>(g, st, a);
             }
-            return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M, NSV, NSQ, 2, false, RG, 0, FL, 0, 1>>(g, NT, lds, st, a);
+            return launch_h16<with(C, &H16Cfg::emit, 1)>(g, st, a);
         };
         auto by_variant = [&](auto mtag) -> int {
             if (filt) {  // subset filter compiled in (always the ragged-capable variant)
-                if constexpr (WR >= 4) return set_error(LYNSE_ERR_INTERNAL, "subset-filtered scans run on the <4,2,2,4> tiling");
+                if constexpr (BASE.wr >= 4) return set_error(LYNSE_ERR_INTERNAL, "subset-filtered scans run on the <4,2,2,4> tiling");
                 else return by_emit(mtag, std::true_type{}, std::true_type{});
             }
             if (ragged) return by_emit(mtag, std::true_type{}, std::false_type{});
             return by_emit(mtag, std::false_type{}, std::false_type{});  // no ragged last slab: branch-free DMA issue
         };
-        if constexpr (WR >= 4) {  // <2,4,4,2>: unfiltered IP only
+        if constexpr (BASE.wr >= 4) {  // <2,4,4,2>: unfiltered IP only
 #ifndef LYNSE_EXPERIMENTS
             if (metric != M_IP) return set_error(LYNSE_ERR_INTERNAL, "the <2,4,4,2> tiling is compiled for IP only");
 #else
@@ -1333,40 +1345,28 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
             }
         }
     } else {
-        if (!ragged && !filt) {
-            switch (metric) {
-            case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
-            case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
-            default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, false>>(g, NT, lds, st, a);
-            }
-        }
-        if (filt) {  // subset filter compiled in (always the ragged-capable variant: one instantiation per metric)
-            switch (metric) {
-            case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
-            case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
-            default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true, 0, true>>(g, NT, lds, st, a);
-            }
-        }
-        switch (metric) {
-        case M_IP: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_IP, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
-        case M_L2: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_L2, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
-        default: return launch_lds<k_scan_h16<WQ, WR, TQ, TR, M_COS, NSV, NSQ, 2, TILED, true>>(g, NT, lds, st, a);
-        }
+        auto by_metric = [&](auto ragtag, auto filtag) -> int {
+            constexpr H16Cfg C = with(BASE, &H16Cfg::rag, decltype(ragtag)::value, &H16Cfg::filt, decltype(filtag)::value);
+            return with_metric(metric, [&](auto mtag) { return launch_h16<with(C, &H16Cfg::metric, decltype(mtag)::value)>(g, st, a); });
+        };
+        if (!ragged && !filt) return by_metric(std::false_type{}, std::false_type{});
+        if (filt) return by_metric(std::true_type{}, std::true_type{});  // subset filter compiled in (always the ragged-capable variant: one instantiation per metric)
+        return by_metric(std::true_type{}, std::false_type{});
     }
 }
 
 // certified int8 coarse pass for batches of <= 32 queries: the 128-row x 32-query tiling (two workgroups per CU, 3 + 3-stage
 // rings) over the SQ8 codes — HBM-bound like its f16 twin, at half the bytes; emission mode at run time (EMIT = -1)
+constexpr H16Cfg I8C_SMALL = with(F16_SMALL, &H16Cfg::rag, false, &H16Cfg::i8q, 2);
 static int launch_scan_i8c_small(const ScanArgs& a, uint32_t grid, hipStream_t st, bool l2n = false, bool filt = false) {
-    constexpr size_t lds = (size_t)(3 * 128 + 3 * 32) * 128;
     if (filt) {   // masked scan of a small batch (row bitmask in the epilogue): whole slabs
         if (a.ld16 % 128 != 0 || a.row_ids || l2n) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>>(grid, 256, lds, st, a);
+        return launch_h16<with(I8C_SMALL, &H16Cfg::filt, true)>(grid, st, a);
     }
-    if (l2n)   // plain-code L2 (I8Q = 4): + the norm ring
-        return launch_lds<k_scan_h16<1, 4, 1, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>>(grid, 256, lds + 4 * 1024, st, a);
-    if (a.ld16 % 128 == 0) return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>>(grid, 256, lds, st, a);
-    return launch_lds<k_scan_h16<1, 4, 1, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>>(grid, 256, lds, st, a);
+    if (l2n)   // plain-code L2 (I8Q = 4): with the norm ring
+        return launch_h16<with(I8C_SMALL, &H16Cfg::metric, M_L2, &H16Cfg::i8q, 4)>(grid, st, a);
+    if (a.ld16 % 128 == 0) return launch_h16<I8C_SMALL>(grid, st, a);
+    return launch_h16<with(I8C_SMALL, &H16Cfg::rag, true)>(grid, st, a);
 }
 
 // The query-stationary tiling of the certified int8 pass (scan_qs.h): threshold stages of an unfiltered FLAT batch over whole
@@ -1383,6 +1383,23 @@ static bool qs_masked_on() { return env_on("LYNSE_HIP_QS_MASKED", true); }
 // LYNSE_HIP_AG=1: the threshold stages of the certified int8 pass with one wave per SIMD (kernels.h, AG; A/B, tests; read per call)
 static int ag_env() { return env_int("LYNSE_HIP_AG", 0); }
 
+// The tilings of k_scan_qs: 64-row tiles, whole-K stages of NSLAB slabs of 128 code columns, 3-stage ring, ping-pong roles (2..6 slabs); 1024
+// columns run 32-row tiles on a 4-stage ring (B = 128 registers).
+constexpr QsCfg qs_64(int nslab) { return {.nslab = nslab, .rb = 2, .sl = nslab, .ns = 3, .xpf = false, .nbuf = 8, .ping = 1}; }
+constexpr QsCfg QS_768 = qs_64(6);
+constexpr QsCfg QS_1024{.nslab = 8, .rb = 1, .sl = 8, .ns = 4, .xpf = false, .nbuf = 8, .ping = 1};
+// f(std::integral_constant<int, NSLAB>{}) for the 2..5-slab code rows of qs_64; every other count is the 6 slabs of 768 columns
+template <class F>
+static int with_qs_slabs(uint32_t nslab, F&& f) {
+    switch (nslab) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    default: return f(std::integral_constant<int, 6>{});
+    }
+}
+
 // Squared L2 on the query-stationary tiling (scan_qs.h, MET = 1): threshold stages of unfiltered batches of 129..256 queries over code
 // rows of 768 bytes (64-row tiles).  Rows per tile, or 0.
 static uint32_t qs_l2_rows(const ScanArgs& a) {
@@ -1398,49 +1415,43 @@ static uint32_t qs_l2_rows(const ScanArgs& a) {
     return 0;
 }
 static int launch_scan_qs_l2(const ScanArgs& a, uint32_t grid, hipStream_t st) {
-    switch (a.nslab) {
-    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + 4 * 256, st, a);
-    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128 + 4 * 256, st, a);
-    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128 + 4 * 256, st, a);
-    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128 + 4 * 256, st, a);
-    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128 + 4 * 256, st, a);
-    }
+    return with_qs_slabs(a.nslab, [&](auto n) { return launch_qs<with(qs_64(decltype(n)::value), &QsCfg::met, 1)>(grid, st, a); });
 }
 
 // squared L2 on the plain SQ8 codes (kernels.h, I8Q = 4): the <4,2,2,4> L2 tiling with 2 + 2-stage rings and the norm ring, int8
 // operands, float epilogue; whole 128-column slabs
+constexpr H16Cfg L2_PLAIN = with(F16_L2_256, &H16Cfg::rag, false, &H16Cfg::i8q, 4, &H16Cfg::emit, 0);
 static int launch_scan_i8l2(const ScanArgs& a, uint32_t grid, hipStream_t st, bool qs = false) {
     if (qs) return launch_scan_qs_l2(a, grid, st);
-    constexpr size_t lds = (size_t)(2 * 256 + 2 * 256) * 128 + 3 * 1024;
     if (a.ld16 % 128 != 0) return set_error(LYNSE_ERR_INTERNAL, "the plain-code L2 scan needs whole 128-column slabs");
-    if (a.emit_all == 1) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 1>>(grid, 512, lds, st, a);
-    if (a.emit_all == 2) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 2>>(grid, 512, lds, st, a);
-    if (a.dense) return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0, 0, true>>(grid, 512, lds, st, a);
-    return launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0>>(grid, 512, lds, st, a);
+    if (a.emit_all == 1) return launch_h16<with(L2_PLAIN, &H16Cfg::emit, 1)>(grid, st, a);
+    if (a.emit_all == 2) return launch_h16<with(L2_PLAIN, &H16Cfg::emit, 2)>(grid, st, a);
+    if (a.dense) return launch_h16<with(L2_PLAIN, &H16Cfg::dense, true)>(grid, st, a);
+    return launch_h16<L2_PLAIN>(grid, st, a);
 }
 
 // certified int8 coarse pass for batches of 33..64 queries (128 rows x 64 queries, 4 waves, two workgroups per CU, 3 + 3 stages)
 // and of 65..128 queries (256 rows x 128 queries, 8 waves as 2 x 4, 3 + 2 stages): per row byte they do a quarter / half of the
 // MFMA and fragment-read work of the 256-query tiling, which a batch of 40 or 100 queries would otherwise pay in full
+constexpr H16Cfg I8C_MID{.wq = 1, .wr = 4, .tq = 2, .tr = 1, .metric = M_IP, .nsv = 3, .nsq = 3, .nt_hint = 2, .rag = false, .i8q = 2};
+constexpr H16Cfg I8C_MID_WIDE{.wq = 2, .wr = 4, .tq = 2, .tr = 2, .metric = M_IP, .nsv = 3, .nsq = 2, .nt_hint = 2, .rag = false, .i8q = 2};
 static int launch_scan_i8c_mid(const ScanArgs& a, uint32_t grid, hipStream_t st, bool wide, bool l2n = false, bool filt = false) {
     const bool rag = a.ld16 % 128 != 0;
     if (filt) {   // masked scan (row bitmask in the epilogue): whole slabs
         if (rag || a.row_ids || l2n) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        if (!wide) return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, true, 2>>(grid, 256, (size_t)(3 * 128 + 3 * 64) * 128, st, a);
-        return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, true, 2>>(grid, 512, (size_t)(3 * 256 + 2 * 128) * 128, st, a);
+        if (!wide) return launch_h16<with(I8C_MID, &H16Cfg::filt, true)>(grid, st, a);
+        return launch_h16<with(I8C_MID_WIDE, &H16Cfg::filt, true)>(grid, st, a);
     }
-    if (l2n) {   // plain-code L2 (I8Q = 4): whole slabs, + the norm ring
-        if (!wide) return launch_lds<k_scan_h16<1, 4, 2, 1, M_L2, 3, 3, 2, false, false, 0, false, 4>>(grid, 256, (size_t)(3 * 128 + 3 * 64) * 128 + 4 * 1024, st, a);
-        return launch_lds<k_scan_h16<2, 4, 2, 2, M_L2, 3, 2, 2, false, false, 0, false, 4>>(grid, 512, (size_t)(3 * 256 + 2 * 128) * 128 + 4 * 1024, st, a);
+    if (l2n) {   // plain-code L2 (I8Q = 4): whole slabs, with the norm ring
+        if (!wide) return launch_h16<with(I8C_MID, &H16Cfg::metric, M_L2, &H16Cfg::i8q, 4)>(grid, st, a);
+        return launch_h16<with(I8C_MID_WIDE, &H16Cfg::metric, M_L2, &H16Cfg::i8q, 4)>(grid, st, a);
     }
     if (!wide) {
-        constexpr size_t lds = (size_t)(3 * 128 + 3 * 64) * 128;
-        if (!rag) return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, false, 0, false, 2>>(grid, 256, lds, st, a);
-        return launch_lds<k_scan_h16<1, 4, 2, 1, M_IP, 3, 3, 2, false, true, 0, false, 2>>(grid, 256, lds, st, a);
+        if (!rag) return launch_h16<I8C_MID>(grid, st, a);
+        return launch_h16<with(I8C_MID, &H16Cfg::rag, true)>(grid, st, a);
     }
-    constexpr size_t lds = (size_t)(3 * 256 + 2 * 128) * 128;
-    if (!rag) return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, false, 0, false, 2>>(grid, 512, lds, st, a);
-    return launch_lds<k_scan_h16<2, 4, 2, 2, M_IP, 3, 2, 2, false, true, 0, false, 2>>(grid, 512, lds, st, a);
+    if (!rag) return launch_h16<I8C_MID_WIDE>(grid, st, a);
+    return launch_h16<with(I8C_MID_WIDE, &H16Cfg::rag, true)>(grid, st, a);
 }
 
 // certified int8 coarse pass: the 256 x 256 IP tiling with 3 + 2-stage rings over 128-element slabs, one kernel per
@@ -1491,20 +1502,15 @@ static uint32_t qs_grid(const ScanArgs& a, uint32_t num_cu) {
 }
 static int launch_scan_qs(const ScanArgs& a, uint32_t grid, hipStream_t st) {
     if (a.dyn_thr)   // self-tightening thresholds: the whole shard in one launch (scan_qs.h, STS)
-        return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128 + QS_STS_LDS, st, a);
-    if (a.mask) return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);   // masked threshold stages (MSK)
-    switch (a.nslab) {   // the narrower code rows (qs_width_ok)
-    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);
-    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128, st, a);
-    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
-    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128, st, a);
-    case 8: return launch_lds<k_scan_qs<8, 1, 8, 4, false, 8, 0, 1>>(grid, 512, (size_t)4 * 8 * 32 * 128, st, a);
-    default: break;
-    }
+        return launch_qs<with(QS_768, &QsCfg::ping, 0, &QsCfg::sts, 1)>(grid, st, a);
+    if (a.mask) return launch_qs<with(QS_768, &QsCfg::msk, 1)>(grid, st, a);   // masked threshold stages (MSK)
+    if (a.nslab >= 2 && a.nslab <= 5)   // the narrower code rows (qs_width_ok)
+        return with_qs_slabs(a.nslab, [&](auto n) { return launch_qs<qs_64(decltype(n)::value)>(grid, st, a); });
+    if (a.nslab == 8) return launch_qs<QS_1024>(grid, st, a);
     switch (qs_variant()) {
-    case 2: return launch_lds<k_scan_qs<6, 1, 6, 6, true, 8, 0, 0>>(grid, 512, (size_t)6 * 6 * 32 * 128, st, a);
-    case 3: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
-    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
+    case 2: return launch_qs<QsCfg{.nslab = 6, .rb = 1, .sl = 6, .ns = 6, .xpf = true, .nbuf = 8}>(grid, st, a);
+    case 3: return launch_qs<with(QS_768, &QsCfg::ping, 0)>(grid, st, a);
+    default: return launch_qs<QS_768>(grid, st, a);
     }
 }
 
@@ -1517,13 +1523,7 @@ static bool qs_sample_ok(const ScanArgs& a, bool fs, bool filt, bool f4, uint32_
            a.skip_stride == 0 && !a.mask && !a.row_ids && a.row1 > a.row0;
 }
 static int launch_scan_qs_sample(const ScanArgs& a, uint32_t grid, hipStream_t st) {
-    switch (a.nslab) {
-    case 2: return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);
-    case 3: return launch_lds<k_scan_qs<3, 2, 3, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 3 * 64 * 128, st, a);
-    case 4: return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
-    case 5: return launch_lds<k_scan_qs<5, 2, 5, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 5 * 64 * 128, st, a);
-    default: return launch_lds<k_scan_qs<6, 2, 6, 3, false, 8, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 6 * 64 * 128, st, a);
-    }
+    return with_qs_slabs(a.nslab, [&](auto n) { return launch_qs<with(qs_64(decltype(n)::value), &QsCfg::ping, 0, &QsCfg::smp, 1)>(grid, st, a); });
 }
 
 // The query-stationary tiling of the f16 shadow at low dimension (scan_qh.h): threshold stages of an unfiltered FLAT batch of 33..256
@@ -1545,22 +1545,16 @@ static uint32_t qh_grid(const ScanArgs& a, uint32_t num_cu, uint32_t* segs_per_w
     *segs_per_wg = 1u;   // (one segment per workgroup and query: the deferred emission of scan_qh.h)
     return std::min<uint32_t>((a.row1 - a.row0 + 63u) / 64u, 2u * num_cu);
 }
-static int launch_scan_qh(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
-    // 32 queries per wave, 64-row tiles, two workgroups per CU (<= 80 KB of LDS each)
-    constexpr size_t stg1 = 8 * 144 * 24 + 1024, nrm1 = 4 * 256 + stg1;   // (three ring stages: the LDS of the fourth is the staging regions')
-    if (a.nslab == 1) {
-        switch (metric) {
-        case M_IP: return launch_lds<k_scan_qh<1, M_IP, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + stg1, st, a);
-        case M_L2: return launch_lds<k_scan_qh<1, M_L2, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
-        default: return launch_lds<k_scan_qh<1, M_COS, 3, 2, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
-        }
-    }
-    switch (metric) {
-    case M_IP: return launch_lds<k_scan_qh<2, M_IP, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + stg1, st, a);
-    case M_L2: return launch_lds<k_scan_qh<2, M_L2, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
-    default: return launch_lds<k_scan_qh<2, M_COS, 3, 2, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
-    }
+// 32 queries per wave, 64-row tiles, two workgroups per CU (<= 80 KB of LDS each; three ring stages: the LDS of the fourth is the staging regions')
+constexpr QhCfg qh_64(int nslab, int met, int smp) { return {.nslab = nslab, .met = met, .ns = 3, .nbuf = 2, .qb = 1, .smp = smp}; }
+template <int SMP>
+static int launch_scan_qh_any(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
+    auto by_metric = [&](auto n) {
+        return with_metric(metric, [&](auto m) { return launch_qh<qh_64(decltype(n)::value, decltype(m)::value, SMP)>(grid, st, a); });
+    };
+    return a.nslab == 1 ? by_metric(std::integral_constant<int, 1>{}) : by_metric(std::integral_constant<int, 2>{});
 }
+static int launch_scan_qh(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) { return launch_scan_qh_any<0>(a, metric, grid, st); }
 
 // The threshold-only SAMPLE stage of the same plans on k_scan_qh<.., SMP> (scan_qh.h): the sample rows as 64-row tiles, two workgroups per CU,
 // 4 keys per workgroup and query.  LYNSE_HIP_QH_SAMPLE=0: the 256 x 256 sample tiles of k_scan_h16<.., EMIT = 2> (A/B; read per call).
@@ -1577,90 +1571,66 @@ static uint32_t qh_sample_grid(const ScanArgs& a, uint32_t sample_tiles, bool fi
     const bool ok = (uint64_t)sgrid * 4u >= 8ull * k && sgrid * 4u <= cap && (nt64 + sgrid - 1) / sgrid <= 32u;
     return ok ? sgrid : 0u;
 }
-static int launch_scan_qh_sample(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
-    constexpr size_t stg1 = 8 * 144 * 24 + 1024, nrm1 = 4 * 256 + stg1;
-    if (a.nslab == 1) {
-        switch (metric) {
-        case M_IP: return launch_lds<k_scan_qh<1, M_IP, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + stg1, st, a);
-        case M_L2: return launch_lds<k_scan_qh<1, M_L2, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
-        default: return launch_lds<k_scan_qh<1, M_COS, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 1 * 64 * 128 + nrm1, st, a);
-        }
-    }
-    switch (metric) {
-    case M_IP: return launch_lds<k_scan_qh<2, M_IP, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + stg1, st, a);
-    case M_L2: return launch_lds<k_scan_qh<2, M_L2, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
-    default: return launch_lds<k_scan_qh<2, M_COS, 3, 2, 1, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128 + nrm1, st, a);
-    }
-}
+static int launch_scan_qh_sample(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) { return launch_scan_qh_any<1>(a, metric, grid, st); }
 
 // (round 5, measured and removed: 1024-bit Hamming on a 64-queries-per-wave form of k_scan_qh — k_scan_qh<4, M_IP, 4, 8, QB = 2, one row block
 // per wave, FP4 MFMA>: every row fragment read feeds two MFMAs, half the LDS fragment returns per MFMA.  Bit-identical, and SLOWER: C5 share
 // 1.900 / 1.916 / 1.928 against 1.705 / 1.708 / 1.725 ms per batch, same box, alternating (scripts/gpu_r5_c5.sh): with one 32-row block per
 // wave a step is 32 MFMAs between two barriers, and a wave's epilogue / DMA issue is no longer covered by its SIMD partner's MFMAs.)
+// The 256 x 256 tiling of the certified int8 pass (3 + 2-stage rings over whole 128-column slabs, threshold stages) and its one-wave-per-SIMD
+// form (kernels.h, AG)
+constexpr H16Cfg I8C_256 = with(F16_IP_256, &H16Cfg::rag, false, &H16Cfg::i8q, 2, &H16Cfg::emit, 0);
+constexpr H16Cfg I8C_AG = with(I8C_256, &H16Cfg::wr, 2, &H16Cfg::tr, 4);
 static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, bool fs = false, bool filt = false, bool f4 = false, bool qs = false) {
-    constexpr size_t lds = (size_t)(3 * 256 + 2 * 256) * 128;
     if (qs && f4) {   // batched Hamming on the query-stationary tiling (scan_qs.h, F4)
-        if (a.nslab == 2) return launch_lds<k_scan_qs<2, 2, 2, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 2 * 64 * 128, st, a);   // 512-bit rows
-        if (a.nslab == 8) return launch_lds<k_scan_qs<8, 1, 8, 4, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)4 * 8 * 32 * 128, st, a);   // 2048-bit rows: 32-row tiles
-        return launch_lds<k_scan_qs<4, 2, 4, 3, false, 8, 0, 1, 0, 0, 0, 0, 1>>(grid, 512, (size_t)3 * 4 * 64 * 128, st, a);
+        if (a.nslab == 2) return launch_qs<with(qs_64(2), &QsCfg::f4, 1)>(grid, st, a);   // 512-bit rows
+        if (a.nslab == 8) return launch_qs<with(QS_1024, &QsCfg::f4, 1)>(grid, st, a);   // 2048-bit rows: 32-row tiles
+        return launch_qs<with(qs_64(4), &QsCfg::f4, 1)>(grid, st, a);
     }
     if (qs) return launch_scan_qs(a, grid, st);
 #ifdef LYNSE_EXPERIMENTS
     if (a.ld16 % 128 == 0 && a.emit_all == 0 && ((a.debug_flags >> 8) & 31)) {  // timing experiments: DBG variants of the int8 kernel
-        switch ((a.debug_flags >> 8) & 31) {
-        case 3: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 3, false, 2, 0>>(grid, 512, lds, st, a);    // DMA only
-        case 4: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 4, false, 2, 0>>(grid, 512, lds, st, a);    // no query-image DMA
-        case 8: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 8, false, 2, 0>>(grid, 512, lds, st, a);    // no row DMA
-        case 12: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 12, false, 2, 0>>(grid, 512, lds, st, a);  // MFMA + LDS reads only
-        case 7: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 7, false, 2, 0>>(grid, 512, lds, st, a);    // row DMA only
-        case 11: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 11, false, 2, 0>>(grid, 512, lds, st, a);  // query DMA only
-        case 1: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 1, false, 2, 0>>(grid, 512, lds, st, a);    // no MFMA (DMA + LDS reads)
-        case 13: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 13, false, 2, 0>>(grid, 512, lds, st, a);  // LDS reads only
-        case 14: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 14, false, 2, 0>>(grid, 512, lds, st, a);  // MFMA only
-        case 2: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 2, false, 2, 0>>(grid, 512, lds, st, a);    // no LDS reads (DMA + MFMA)
-        case 16: return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 16, false, 2, 0>>(grid, 512, lds, st, a);  // no epilogue
-        default: return set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
-        }
+        return dispatch_dbg<I8C_256, 3, 4, 8, 12, 7, 11, 1, 13, 14, 2, 16>((a.debug_flags >> 8) & 31, grid, st, a);
     }
 #endif
     if (f4) {   // batched Hamming: FP4 +-1 operands (kernels.h, I8Q = 3); whole 128-B slabs by construction, unfiltered
         if (a.ld16 % 128 != 0 || filt || fs) return set_error(LYNSE_ERR_INTERNAL, "the FP4 Hamming scan runs unfiltered over whole slabs");
-        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 1>>(grid, 512, lds, st, a);
-        if (a.emit_all == 2) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 2>>(grid, 512, lds, st, a);
-        if (a.dense) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0, 0, true>>(grid, 512, lds, st, a);
-        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 3, 0>>(grid, 512, lds, st, a);
+        if (a.emit_all == 1) return launch_h16<with(I8C_256, &H16Cfg::i8q, 3, &H16Cfg::emit, 1)>(grid, st, a);
+        if (a.emit_all == 2) return launch_h16<with(I8C_256, &H16Cfg::i8q, 3, &H16Cfg::emit, 2)>(grid, st, a);
+        if (a.dense) return launch_h16<with(I8C_256, &H16Cfg::i8q, 3, &H16Cfg::dense, true)>(grid, st, a);
+        return launch_h16<with(I8C_256, &H16Cfg::i8q, 3)>(grid, st, a);
     }
     if (filt) {  // masked scan (subset as a row bitmask): emit-all sample with sentinels, DENSE threshold stages (kernels.h, FILT && I8C)
         if (a.ld16 % 128 != 0 || a.row_ids) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan needs whole 128-column slabs and a row bitmask");
-        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 1>>(grid, 512, lds, st, a);
+        if (a.emit_all == 1) return launch_h16<with(I8C_256, &H16Cfg::filt, true, &H16Cfg::emit, 1)>(grid, st, a);
         if (a.emit_all != 0 || !a.dense) return set_error(LYNSE_ERR_INTERNAL, "the masked int8 scan runs emit-all and DENSE threshold stages");
-        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, true, 2, 0, 0, true>>(grid, 512, lds, st, a);
+        return launch_h16<with(I8C_256, &H16Cfg::filt, true, &H16Cfg::dense, true)>(grid, st, a);
     }
     // One wave per SIMD: 4 waves x (128 queries x 128 rows), accumulators in fixed AGPR tuples (kernels.h, AG) — the threshold
     // stages over whole 128-column slabs (LYNSE_HIP_AG=1; the sample stages keep the 8-wave kernels)
     if (ag_env() && a.ld16 % 128 == 0 && a.emit_all == 0 && !fs) {
-        if (a.dense) return launch_lds<k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>>(grid, 256, lds, st, a);
-        return launch_lds<k_scan_h16<2, 2, 4, 4, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>>(grid, 256, lds, st, a);
+        if (a.dense) return launch_h16<with(I8C_AG, &H16Cfg::dense, true)>(grid, st, a);
+        return launch_h16<I8C_AG>(grid, st, a);
     }
     if (a.ld16 % 128 == 0) {
         static const int prio = env_int("LYNSE_HIP_PRIO", 0);
-        if (a.emit_all == 0 && prio) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, false, true>>(grid, 512, lds, st, a);
+        if (a.emit_all == 0 && prio) return launch_h16<with(I8C_256, &H16Cfg::prio, true)>(grid, st, a);
         static const int place = env_int("LYNSE_HIP_PLACE", 0);
-        if (a.emit_all == 0 && place == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 1>>(grid, 512, lds, st, a);
-        if (a.emit_all == 0 && place == 2) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 2>>(grid, 512, lds, st, a);
+        if (a.emit_all == 0 && place == 1) return launch_h16<with(I8C_256, &H16Cfg::place, 1)>(grid, st, a);
+        if (a.emit_all == 0 && place == 2) return launch_h16<with(I8C_256, &H16Cfg::place, 2)>(grid, st, a);
         if (fs) {  // fused sample stage: sample tile + in-launch thresholds + the first threshold stage (kernels.h, FS)
             if (a.emit_all != 0) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is a threshold stage");
             if (!a.dense) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is compiled with the DENSE epilogue");  // (the two-level body spills 12 B with it)
-            return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true, false, true, 1>>(grid, 512, lds, st, a);
+            return launch_h16<with(I8C_256, &H16Cfg::dense, true, &H16Cfg::fs, 1)>(grid, st, a);
         }
-        if (a.emit_all == 0 && a.dense) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0, 0, true>>(grid, 512, lds, st, a);
-        if (a.emit_all == 0) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 0>>(grid, 512, lds, st, a);
-        if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 1>>(grid, 512, lds, st, a);
-        return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, 0, false, 2, 2>>(grid, 512, lds, st, a);
+        if (a.emit_all == 0 && a.dense) return launch_h16<with(I8C_256, &H16Cfg::dense, true)>(grid, st, a);
+        if (a.emit_all == 0) return launch_h16<I8C_256>(grid, st, a);
+        if (a.emit_all == 1) return launch_h16<with(I8C_256, &H16Cfg::emit, 1)>(grid, st, a);
+        return launch_h16<with(I8C_256, &H16Cfg::emit, 2)>(grid, st, a);
     }
-    if (a.emit_all == 0) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 0>>(grid, 512, lds, st, a);
-    if (a.emit_all == 1) return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 1>>(grid, 512, lds, st, a);
-    return launch_lds<k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, true, 0, false, 2, 2>>(grid, 512, lds, st, a);
+    if (a.emit_all == 0) return launch_h16<with(I8C_256, &H16Cfg::rag, true)>(grid, st, a);
+    if (a.emit_all == 1) return launch_h16<with(I8C_256, &H16Cfg::rag, true, &H16Cfg::emit, 1)>(grid, st, a);
+    return launch_h16<with(I8C_256, &H16Cfg::rag, true, &H16Cfg::emit, 2)>(grid, st, a);
 }
 
 // f16 shadow rows [n16, n) (all rows again when the scale changed)
@@ -2136,7 +2106,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                 if (small) {
                     const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu * 2);
                     if (!a.emit_all) seg_geometry(grid, 4, &a.nseg, &a.seg);
-                    LY_TRY((launch_scan_h16<1, 4, 1, 1, 3, 3, false>(a, metric, grid, st)));
+                    LY_TRY((launch_scan_h16<F16_SMALL>(a, metric, grid, st)));
                 } else if (const uint32_t sgrid = qh_sample_grid(a, s.sample_tiles, filt, qchunks, level, plan_tile, k, w.cap, (uint32_t)h->num_cu)) {
                     // the threshold-only sample stage on k_scan_qh<.., SMP>: 4 keys per workgroup and query
                     a.ntiles = s.sample_tiles * 4u;
@@ -2160,11 +2130,11 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     if (qchunks > 1 && !(plan.size() == 1 && (a.emit_all == 1 || (tl_assign && a.emit_all == 2))))
                         return set_error(LYNSE_ERR_INTERNAL, "the widened pipeline runs single-stage emit-all plans only");
 #ifdef LYNSE_EXPERIMENTS
-                    if (waves16 == 2) { LY_TRY((launch_scan_h16<2, 4, 4, 2, 2, 2, false>(a, metric, grid, st))); }
+                    if (waves16 == 2) { LY_TRY((launch_scan_h16<with(F16_IP_256, &H16Cfg::nsv, 2)>(a, metric, grid, st))); }
                     else
 #endif
-                    if (waves16 == 3) { LY_TRY((launch_scan_h16<2, 4, 4, 2, 3, 2, false>(a, metric, grid, st, qchunks))); }
-                    else { LY_TRY((launch_scan_h16<4, 2, 2, 4, 2, 2, false>(a, metric, grid, st, qchunks))); }
+                    if (waves16 == 3) { LY_TRY((launch_scan_h16<F16_IP_256>(a, metric, grid, st, qchunks))); }
+                    else { LY_TRY((launch_scan_h16<F16_L2_256>(a, metric, grid, st, qchunks))); }
                 }
             }
 #ifdef LYNSE_EXPERIMENTS
@@ -2724,9 +2694,9 @@ static int run_chunk_sq8(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t ou
         const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
         a.candB = w.candB; a.segcnt = w.segcnt;
         if (!a.emit_all) seg_geometry(grid, 2, &a.nseg, &a.seg);
-        constexpr size_t lds = (size_t)(2 * 256 + 2 * 256) * 128 + 3 * 1024;
-        if (ip) LY_TRY((launch_lds<k_scan_h16<4, 2, 2, 4, M_IP, 2, 2, 2, false, true, 0, false, 1>>(grid, 512, lds, st, a)));
-        else LY_TRY((launch_lds<k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, true, 0, false, 1>>(grid, 512, lds, st, a)));
+        constexpr H16Cfg SQ8 = with(F16_L2_256, &H16Cfg::i8q, 1);   // integer scores of the u8 codes (kernels.h, I8Q = 1); may end in a ragged slab
+        if (ip) LY_TRY((launch_h16<with(SQ8, &H16Cfg::metric, M_IP)>(grid, st, a)));
+        else LY_TRY((launch_h16<SQ8>(grid, st, a)));
         SelectArgs sa{};
         sa.cand = w.cand; sa.count = w.count; sa.overflow = w.overflow; sa.thr = w.thr; sa.marg2 = w.marg2;
         sa.k = n_cand; sa.cap = w.cap; sa.keep_max = w.cap / 2; sa.metric = m1; sa.ip_form = LYNSE_IPFORM_SINGLE;

@@ -39,6 +39,20 @@ typedef float qh_f32x2 __attribute__((ext_vector_type(2)));
 // score than the row has — with the tile ordinal and the accumulator slot in the low 10 bits) and writes them to
 // cand[query][(blockIdx.x * 2 + hi) * 2 + t]: 4 keys per workgroup and query.  Any k distinct real rows bound the k-th best score, so
 // k_select's threshold-only rule turns the k-th best of these keys into a valid first threshold as it does with k_scan_qs<.., SMP>'s.
+// An instantiation by name: one field per template parameter, in the template's order and with its defaults (launch_qh, lynse_hip.hip).
+// Always 512 threads.
+struct QhCfg {
+    int nslab, met, ns, nbuf, qb;
+    int smp = 0;
+};
+constexpr int QH_THREADS = 512;
+// Dynamic LDS of an instantiation: NS ring stages of a whole tile (NSLAB slabs x 64 QB rows x 128 B), for L2 / cosine the norm ring (NS + 1
+// slots of one f32 per row), the waves' staging regions (8 x EW groups of 24 B) and the per-query key counters (u32[256]).  The kernel
+// asserts its layout against it.
+constexpr size_t qh_lds_bytes(QhCfg c) {
+    const int rt = 64 * c.qb, ew = c.qb == 1 ? (c.ns == 3 ? 144 : 64) : 128;
+    return (size_t)c.ns * c.nslab * rt * 128 + (c.met != M_IP ? (size_t)(c.ns + 1) * rt * 4 : 0) + (size_t)8 * ew * 24 + 256 * 4;
+}
 template <int NSLAB, int MET, int NS, int NBUF, int QB, int SMP = 0>
 __global__ void __launch_bounds__(512, (QB == 1 ? 4 : 2)) k_scan_qh(ScanArgs a) {
     static_assert(QB == 1, "query blocks per wave: the 64-queries-per-wave form (QB = 2) measured 10-20 % slower and is not instantiated any more");
@@ -69,6 +83,7 @@ __global__ void __launch_bounds__(512, (QB == 1 ? 4 : 2)) k_scan_qh(ScanArgs a) 
     constexpr int STG_OFF = NRM_OFF + (NORMS ? NRM_SLOTS * NRM : 0);
     constexpr int QCNT_OFF = STG_OFF + 8 * EW * 24;   // u32[256]: keys of this workgroup per query
     static_assert(QCNT_OFF + 256 * 4 <= (QB == 1 ? 80 : 160) * 1024, "LDS");
+    static_assert((size_t)(QCNT_OFF + 256 * 4) <= qh_lds_bytes(QhCfg{NSLAB, MET, NS, NBUF, QB, SMP}), "the LDS the body addresses ends inside what the launch asks for");
     constexpr int NXW = NORMS ? QB : 0;      // LDS-DMAs wave 0 issues per step on top of its ring pieces
     constexpr int WAITN = (NS - 2) * PPW;    // ring pieces that may still be in flight at the barrier
     static_assert((NS - 1) * (PPW + NXW) <= 63, "vmcnt");

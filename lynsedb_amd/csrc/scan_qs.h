@@ -43,6 +43,22 @@ typedef int qs_i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int QS_STS_LDS = 8 * 256 + 8 * 256;   // landing areas behind the ring: per wave 64 thresholds + 64 partition maxima
 
+// An instantiation of k_scan_qs by name: one field per template parameter, in the template's order and with its defaults (launch_qs,
+// lynse_hip.hip).  Always 512 threads.
+struct QsCfg {
+    int nslab, rb, sl, ns;
+    bool xpf;
+    int nbuf;
+    int dbg = 0, ping = 0, sts = 0, met = 0, smp = 0, msk = 0, f4 = 0;
+};
+constexpr int QS_THREADS = 512;
+// Dynamic LDS of an instantiation: NS ring stages of SL slabs x RB * 32 rows x 128 B, the landing areas of the self-tightening form,
+// the norm ring of the L2 form (NS + 1 slots of one f32 per row; 1 KiB for tiles of more than 64 rows).  The kernel asserts its layout against it.
+constexpr size_t qs_lds_bytes(QsCfg c) {
+    const size_t norm_slot = c.met == 1 ? (c.rb * 32 == 64 ? 256 : 1024) : 0;
+    return (size_t)c.ns * c.sl * (c.rb * 32) * 128 + (c.sts ? QS_STS_LDS : 0) + (size_t)(c.ns + 1) * norm_slot;
+}
+
 // DBG (timing experiments): 1 no MFMA, 2 no LDS fragment reads, 8 no row DMA, 16 no epilogue, 32 s_memtime phase sums, 64 waves 4-7 do not compute
 // MET: 0 = inner product / cosine (integer threshold image), 1 = squared L2 on the PLAIN codes: the int8 dot product feeds a float
 // epilogue with the exact f32 row norms (coarse distance |v|^2 - 2 s_q dot + (|q|^2 - 2 B_q), k_i8c_prep_queries l2n; the norms of a
@@ -79,6 +95,8 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     constexpr int NRM_OFF = NS * SB + (STS ? QS_STS_LDS : 0);
     static_assert(MET == 0 || (STS == 0 && TS == 1 && RT <= 256), "L2: whole-K stages; one dword / dwordx4 LDS-DMA brings a tile's norms");
     static_assert(NRM_OFF + NRM_SLOTS * NRM <= 160 * 1024, "LDS");
+    static_assert((size_t)(NRM_OFF + NRM_SLOTS * NRM) <= qs_lds_bytes(QsCfg{NSLAB, RB, SL, NS, XPF, NBUF, DBG, PING, STS, MET, SMP, MSK, F4}),
+                  "the LDS the body addresses ends inside what the launch asks for");
     static_assert(PING == 0 || TS == 1, "ping-pong: one step per tile");
     static_assert(STS == 0 || (!XPF && TS == 1), "self-tightening thresholds: whole-K stages, no cross-barrier prefetch");
     static_assert(SMP == 0 || (STS == 0 && MET == 0 && RT == 64 && TS == 1), "sample stage: 64-row tiles of the IP / cosine form");
