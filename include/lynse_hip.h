@@ -129,7 +129,9 @@ typedef struct lynse_hip_profile {
                                  stages), bits 8..15 number of scan stages, bits 16..23 wave tiling
                                  (0x24 = <2,4,4,2>, 0x42 = <4,2,2,4>, 0x14 = <1,4,1,1>, 0x81 = the query-stationary k_scan_qs), bit 24 the self-tightening
                                  single-launch scan, bit 25 the sample stage ran on the query-stationary tiling, bit 26 the stages read the
-                                 non-negative 7-bit copy of the codes (SQ7: FLAT-IP, 129..256 queries, LYNSE_HIP_SQ7) — lets a test pin
+                                 non-negative 7-bit copy of the codes (SQ7: FLAT-IP, 129..256 queries, LYNSE_HIP_SQ7), bit 27 the query-stationary
+                                 threshold stages ran on v_mfma_i32_16x16x64_i8 (same tile, four segments per workgroup and query;
+                                 LYNSE_HIP_QS_M16=0: the 32x32x32 form; results never change) — lets a test pin
                                  the kernel instantiation a benchmark configuration runs */
 } lynse_hip_profile;
 

@@ -1051,7 +1051,7 @@ static int launch_h16(dim3 grid, hipStream_t st, const ScanArgs& a) {
 }
 template <QsCfg C>
 static int launch_qs(dim3 grid, hipStream_t st, const ScanArgs& a) {
-    return launch_lds<k_scan_qs<C.nslab, C.rb, C.sl, C.ns, C.xpf, C.nbuf, C.dbg, C.ping, C.sts, C.met, C.smp, C.msk, C.f4>>(grid, QS_THREADS, qs_lds_bytes(C), st, a);
+    return launch_lds<k_scan_qs<C.nslab, C.rb, C.sl, C.ns, C.xpf, C.nbuf, C.dbg, C.ping, C.sts, C.met, C.smp, C.msk, C.f4, C.m16>>(grid, QS_THREADS, qs_lds_bytes(C), st, a);
 }
 template <QhCfg C>
 static int launch_qh(dim3 grid, hipStream_t st, const ScanArgs& a) {
@@ -1500,10 +1500,25 @@ static uint32_t qs_grid(const ScanArgs& a, uint32_t num_cu) {
     const uint32_t cus = e > 0 ? std::min<uint32_t>((uint32_t)e, num_cu) : num_cu;
     return std::min<uint32_t>((a.row1 - a.row0 + rt - 1) / rt, cus);
 }
-static int launch_scan_qs(const ScanArgs& a, uint32_t grid, hipStream_t st) {
+// LYNSE_HIP_QS_M16: the MFMA shape of the plain threshold stages on the 64-row tilings (scan_qs.h, M16): 1 / unset (auto) =
+// v_mfma_i32_16x16x64_i8, 0 = v_mfma_i32_32x32x32_i8 (A/B, tests; read per call).  Same wave tile, fragment reads, registers and key sets;
+// the chip holds a higher clock on the smaller shape (profiles/qs16_microbench.txt, profiles/qs16_bench_ab.json).
+static int qs_m16_env() { return env_int("LYNSE_HIP_QS_M16", -1); }
+// Does this query-stationary threshold stage run the 16x16x64 form?  Plain stages of the default variant only: the sample stage, the
+// masked and self-tightening stages, squared L2, FP4 Hamming and the 32-row tiles of 1024 columns keep the 32x32x32 form.  The caller
+// sizes the segments by it (four per workgroup and query instead of two), and every threshold stage of a batch gets the same answer.
+static bool qs_m16_stage(const ScanArgs& a, bool sts, bool filt, bool f4) {
+    if (qs_m16_env() == 0 || qs_variant() != 1) return false;
+    return !sts && !filt && !f4 && !a.mask && !a.dyn_thr && a.nslab >= 2 && a.nslab <= 6;
+}
+static int launch_scan_qs(const ScanArgs& a, uint32_t grid, hipStream_t st, bool m16 = false) {
     if (a.dyn_thr)   // self-tightening thresholds: the whole shard in one launch (scan_qs.h, STS)
         return launch_qs<with(QS_768, &QsCfg::ping, 0, &QsCfg::sts, 1)>(grid, st, a);
     if (a.mask) return launch_qs<with(QS_768, &QsCfg::msk, 1)>(grid, st, a);   // masked threshold stages (MSK)
+    if (m16) {   // (qs_m16_stage: 2..6 slabs, the default variant)
+        if (a.nseg != 0 && a.nseg != grid * 4u) return set_error(LYNSE_ERR_INTERNAL, "the 16x16x64 scan needs four segments per workgroup and query");
+        return with_qs_slabs(a.nslab, [&](auto n) { return launch_qs<with(qs_64(decltype(n)::value), &QsCfg::m16, 1)>(grid, st, a); });
+    }
     if (a.nslab >= 2 && a.nslab <= 5)   // the narrower code rows (qs_width_ok)
         return with_qs_slabs(a.nslab, [&](auto n) { return launch_qs<qs_64(decltype(n)::value)>(grid, st, a); });
     if (a.nslab == 8) return launch_qs<QS_1024>(grid, st, a);
@@ -1581,13 +1596,13 @@ static int launch_scan_qh_sample(const ScanArgs& a, int metric, uint32_t grid, h
 // form (kernels.h, AG)
 constexpr H16Cfg I8C_256 = with(F16_IP_256, &H16Cfg::rag, false, &H16Cfg::i8q, 2, &H16Cfg::emit, 0);
 constexpr H16Cfg I8C_AG = with(I8C_256, &H16Cfg::wr, 2, &H16Cfg::tr, 4);
-static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, bool fs = false, bool filt = false, bool f4 = false, bool qs = false) {
+static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, bool fs = false, bool filt = false, bool f4 = false, bool qs = false, bool m16 = false) {
     if (qs && f4) {   // batched Hamming on the query-stationary tiling (scan_qs.h, F4)
         if (a.nslab == 2) return launch_qs<with(qs_64(2), &QsCfg::f4, 1)>(grid, st, a);   // 512-bit rows
         if (a.nslab == 8) return launch_qs<with(QS_1024, &QsCfg::f4, 1)>(grid, st, a);   // 2048-bit rows: 32-row tiles
         return launch_qs<with(qs_64(4), &QsCfg::f4, 1)>(grid, st, a);
     }
-    if (qs) return launch_scan_qs(a, grid, st);
+    if (qs) return launch_scan_qs(a, grid, st, m16);
 #ifdef LYNSE_EXPERIMENTS
     if (a.ld16 % 128 == 0 && a.emit_all == 0 && ((a.debug_flags >> 8) & 31)) {  // timing experiments: DBG variants of the int8 kernel
         return dispatch_dbg<I8C_256, 3, 4, 8, 12, 7, 11, 1, 13, 14, 2, 16>((a.debug_flags >> 8) & 31, grid, st, a);
@@ -1951,7 +1966,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     sample.sample_tiles == (uint32_t)h->num_cu && (plan[1].r1 - plan[1].r0 + 255) / 256 >= (uint32_t)h->num_cu &&
                     (uint64_t)k * 50000ull > (uint64_t)sample.sample_tiles * plan_tile &&   // (the stage behind the sample runs the DENSE epilogue)
                     dense_env_now() != 0;
-    bool plan_used_segments = false, plan_used_qs = false, plan_qs_sample = false, plan_used_qh = false;
+    bool plan_used_segments = false, plan_used_qs = false, plan_qs_sample = false, plan_used_qh = false, plan_qs_m16 = false;
     // the select behind the last stage + exact rescoring + final order in one launch (k_select_final); LYNSE_HIP_FUSED_TAIL=0:
     // the three separate kernels (A/B)
     const int fused_tail_env = env_int("LYNSE_HIP_FUSED_TAIL", 1);   // (read per call: tests flip it)
@@ -2091,7 +2106,8 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     a.dyn_pitch = pitch;
                     launch_grid = (nt + pitch - 1) / pitch;
                 }
-                if (qs) { seg_geometry(launch_grid, 2, &a.nseg, &a.seg); plan_used_qs = true; }
+                const bool m16 = qs && qs_m16_stage(a, sts, filt, bin_mfma);   // the 16x16x64 form: four lanes share a query, four segments per workgroup and query
+                if (qs) { seg_geometry(launch_grid, m16 ? 4 : 2, &a.nseg, &a.seg); plan_used_qs = true; plan_qs_m16 = plan_qs_m16 || m16; }
                 else
                 if (!a.emit_all) seg_geometry(grid, (a.dense ? 8 : 4) / (ag ? 2 : 1), &a.nseg, &a.seg);   // (segments per workgroup: WR, or 2 WR wave halves with DENSE)
                 if (fs_stage) {
@@ -2099,7 +2115,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     a.thr_out = w.thr; a.k = k; a.ip_form = ip_form; a.metric = metric;
                     if (env_str("LYNSE_HIP_FS_STAMPS")) a.debug_flags |= 128;
                 }
-                LY_TRY(launch_scan_i8c(a, launch_grid, st, fs_stage, filt, bin_mfma, qs));
+                LY_TRY(launch_scan_i8c(a, launch_grid, st, fs_stage, filt, bin_mfma, qs, m16));
                 }
             } else if (h16) {
                 a.candB = w.candB; a.segcnt = w.segcnt;
@@ -2220,7 +2236,8 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         h->prof.last_plan = (sample.sample_tiles ? 1u : 0u) | ((sample.sample_tiles && sample_threshold_only) ? 2u : 0u) | (i8c ? 4u : 0u) |
                             (plan_used_segments ? 8u : 0u) | (small ? 16u : 0u) | (fs ? 128u : 0u) | ((uint64_t)(plan.size() & 0xff) << 8) | (tiling << 16) |
                             (sts ? (1ull << 24) : 0ull) | (plan_qs_sample ? (1ull << 25) : 0ull) |   // bit 24: self-tightening single-launch scan; bit 25: sample stage on the query-stationary tiling
-                            (sq7 ? (1ull << 26) : 0ull);   // bit 26: the stages read the non-negative 7-bit copy of the codes (SQ7)
+                            (sq7 ? (1ull << 26) : 0ull) |   // bit 26: the stages read the non-negative 7-bit copy of the codes (SQ7)
+                            (plan_qs_m16 ? (1ull << 27) : 0ull);   // bit 27: query-stationary threshold stages on v_mfma_i32_16x16x64_i8 (scan_qs.h, M16)
     }
     FinalArgs fa{};
     fa.cand = w.cand; fa.count = w.count; fa.k = k; fa.out_k = out_k; fa.cap = w.cap; fa.metric = key_metric; fa.ip_form = ip_form;

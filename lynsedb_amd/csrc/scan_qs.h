@@ -49,7 +49,7 @@ struct QsCfg {
     int nslab, rb, sl, ns;
     bool xpf;
     int nbuf;
-    int dbg = 0, ping = 0, sts = 0, met = 0, smp = 0, msk = 0, f4 = 0;
+    int dbg = 0, ping = 0, sts = 0, met = 0, smp = 0, msk = 0, f4 = 0, m16 = 0;
 };
 constexpr int QS_THREADS = 512;
 // Dynamic LDS of an instantiation: NS ring stages of SL slabs x RB * 32 rows x 128 B, the landing areas of the self-tightening form,
@@ -78,7 +78,14 @@ constexpr size_t qs_lds_bytes(QsCfg c) {
 // query image of k_bpm_prep_queries) on v_mfma_scale_f32_32x32x64_f8f6f4 with unit scales.  A 128-B line holds 256 elements = four k-steps
 // of 64, so rings, fragments and the B-register layout are those of the int8 form; the f32 accumulators hold exact integers and are
 // converted where the integer epilogue reads them.  The emit-all sample tiles of the plan (a.skip_stride) are computed but emit nothing.
-template <int NSLAB, int RB, int SL, int NS, bool XPF, int NBUF, int DBG = 0, int PING = 0, int STS = 0, int MET = 0, int SMP = 0, int MSK = 0, int F4 = 0>
+// M16 = 1: the same wave tile on v_mfma_i32_16x16x64_i8 (plain and masked threshold stages of the IP / cosine form).  Ring, LDS-DMA, barriers,
+// query image and the number of fragment reads are those of the 32x32x32 form; the fragment maps, the MFMA and the epilogue differ: a wave's 32
+// queries are two blocks of 16, one ds_read_b128 (row rb16 * 16 + lane % 16, slot k64 * 4 + lane / 16 of a slab) feeds the two MFMAs of the
+// blocks, the accumulators of a tile are RT / 16 x 2 tiles of 4 registers (as many registers), a lane holds TWO queries — each with its own
+// integer threshold and constants — and the four lanes that share a query have a private segment each (candB / segcnt index
+// blockIdx.x * 4 + lane / 16: the host sizes the segments with four per workgroup and query).  Keys are formed exactly as in the 32x32x32
+// form, so a stage emits the identical key set.  Why: the power-capped chip holds a higher clock on the smaller shape.
+template <int NSLAB, int RB, int SL, int NS, bool XPF, int NBUF, int DBG = 0, int PING = 0, int STS = 0, int MET = 0, int SMP = 0, int MSK = 0, int F4 = 0, int M16 = 0>
 __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     static_assert(NSLAB % SL == 0, "a tile is a whole number of steps");
     constexpr int TS = NSLAB / SL;          // steps per tile
@@ -95,13 +102,17 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     constexpr int NRM_OFF = NS * SB + (STS ? QS_STS_LDS : 0);
     static_assert(MET == 0 || (STS == 0 && TS == 1 && RT <= 256), "L2: whole-K stages; one dword / dwordx4 LDS-DMA brings a tile's norms");
     static_assert(NRM_OFF + NRM_SLOTS * NRM <= 160 * 1024, "LDS");
-    static_assert((size_t)(NRM_OFF + NRM_SLOTS * NRM) <= qs_lds_bytes(QsCfg{NSLAB, RB, SL, NS, XPF, NBUF, DBG, PING, STS, MET, SMP, MSK, F4}),
+    static_assert((size_t)(NRM_OFF + NRM_SLOTS * NRM) <= qs_lds_bytes(QsCfg{NSLAB, RB, SL, NS, XPF, NBUF, DBG, PING, STS, MET, SMP, MSK, F4, M16}),
                   "the LDS the body addresses ends inside what the launch asks for");
     static_assert(PING == 0 || TS == 1, "ping-pong: one step per tile");
     static_assert(STS == 0 || (!XPF && TS == 1), "self-tightening thresholds: whole-K stages, no cross-barrier prefetch");
     static_assert(SMP == 0 || (STS == 0 && MET == 0 && RT == 64 && TS == 1), "sample stage: 64-row tiles of the IP / cosine form");
     static_assert(MSK == 0 || (STS == 0 && MET == 0 && SMP == 0), "masked threshold stages: the IP / cosine form");
     static_assert(F4 == 0 || (STS == 0 && MET == 0 && SMP == 0 && MSK == 0 && DBG == 0), "FP4 Hamming: plain threshold stages");
+    static_assert(M16 == 0 || (STS == 0 && MET == 0 && F4 == 0 && SMP == 0 && (DBG & 32) == 0), "16x16x64 form: threshold stages of the IP / cosine form");
+    constexpr int R16 = RT / 16;            // M16: 16-row blocks per tile (one fragment read each per 64 columns)
+    constexpr int NKK = M16 != 0 ? 2 : 4;   // fragment addresses per slab: 64-column halves (M16) / 32-column quarters
+    constexpr int KX = M16 != 0 ? 64 : 32;  // byte distance of two of them inside a 128-B row (an XOR: it commutes with the slot swizzle)
     constexpr int WAITN = (XPF ? NS - 3 : NS - 2) * PPW;   // DMA instructions that may still be in flight at the barrier
     static_assert(WAITN <= 63, "vmcnt");
 
@@ -142,8 +153,21 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
 
     // ---- the wave's query block: B fragments of every k-step, register-resident for the whole launch
     const int swz = (l32 >> 1) & 7;
+    // M16: lane = (c, g4) = (lane & 15, lane >> 4).  v_mfma_i32_16x16x64_i8: A[row c][k = 16 g4 + j], B[k = 16 g4 + j][col c], C/D column c,
+    // row 4 g4 + reg.  The wave's 32 queries are two blocks of 16 (qb): fragment (slab, 64-column half k64, qb) holds query
+    // wave * 32 + qb * 16 + c, logical slot k64 * 4 + g4 of the slab (the image's own swizzle: (q >> 1) & 7 = (c >> 1) & 7).
+    [[maybe_unused]] const int c16 = lane & 15, g4 = lane >> 4, swz16 = (c16 >> 1) & 7;
     qs_i32x4 bq[NSLAB * 4];
-    {
+    if constexpr (M16 != 0) {
+#pragma unroll
+        for (int s = 0; s < NSLAB; ++s)
+#pragma unroll
+            for (int k64 = 0; k64 < 2; ++k64)
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb)
+                    bq[s * 4 + k64 * 2 + qb] = *reinterpret_cast<const qs_i32x4*>(reinterpret_cast<const char*>(a.Q16) + (size_t)(wave * 32 + qb * 16 + c16) * 128 +
+                                                                                  (size_t)s * a.qpad * 128 + (((k64 * 4 + g4) ^ swz16) * 16));
+    } else {
         const char* qimg = reinterpret_cast<const char*>(a.Q16) + (size_t)(wave * 32 + l32) * 128;
 #pragma unroll
         for (int s = 0; s < NSLAB; ++s)
@@ -161,6 +185,20 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     // (the threshold of this lane's query: loaded HERE, in front of the ring prologue — a load issued behind the LDS-DMA pieces returns
     // behind them, and the bisection below would wait out the first HBM round trip of the ring)
     [[maybe_unused]] const float thr_q = (q_ok && STS == 0 && SMP == 0) ? a.thr[qn] : 0.0f;
+    // M16: the lane's TWO queries (one per 16-query block), each with its own constants, threshold and private segment
+    [[maybe_unused]] uint32_t qn16[2] = {0u, 0u};
+    [[maybe_unused]] bool q_ok16[2] = {false, false};
+    [[maybe_unused]] float s_q16[2] = {0.0f, 0.0f}, b_q16[2] = {0.0f, 0.0f}, thr_q16[2] = {0.0f, 0.0f};
+    if constexpr (M16 != 0) {
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            qn16[qb] = (uint32_t)(wave * 32 + qb * 16 + c16);
+            q_ok16[qb] = qn16[qb] < a.nq;
+            s_q16[qb] = q_ok16[qb] ? a.qinv[qn16[qb]] : 0.0f;
+            b_q16[qb] = q_ok16[qb] ? a.qn2[qn16[qb]] : 0.0f;
+            thr_q16[qb] = q_ok16[qb] ? a.thr[qn16[qb]] : 0.0f;
+        }
+    }
     // Round 5: the ring prologue is issued BEFORE anything waits for the fragments and constants above.  It used to follow an
     // s_waitcnt vmcnt(0): fragments + constants (1.8 us, L2), 12 LDS-DMA pieces per wave (1.6 us of issue) and the first HBM round trip
     // (2.4 us) ran one after the other in every launch (s_memtime stamps of the sample stage: 5.8 us before its first MFMA); now the
@@ -241,6 +279,27 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
         if (a.debug_flags & 2) l2_pre = LY_INF;
 #endif
     }
+    [[maybe_unused]] int T16[2] = {0x7fffffff, 0x7fffffff};
+    if constexpr (M16 != 0) {   // (the bisection below, for both queries of the lane at once)
+        int lo[2] = {-(1 << 29), -(1 << 29)}, hi_[2] = {1 << 29, 1 << 29};
+#pragma unroll 1
+        for (int it = 0; it < 31; ++it) {
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                const int mid = lo[qb] + ((hi_[qb] - lo[qb]) >> 1);
+                const bool ge = (b_q16[qb] + s_q16[qb] * (float)mid) >= thr_q16[qb];
+                hi_[qb] = ge ? mid : hi_[qb];
+                lo[qb] = ge ? lo[qb] : mid + 1;
+            }
+        }
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+            T16[qb] = q_ok16[qb] ? lo[qb] : 0x7fffffff;
+#ifdef LYNSE_EXPERIMENTS
+            if (a.debug_flags & 2) T16[qb] = 0x7fffffff;
+#endif
+        }
+    } else
     if constexpr (STS == 0 && MET == 0 && SMP == 0) {
         // INTEGER image of the threshold (k_scan_h16, load_qc_thr): B_q + s_q * (float)dot is monotone non-decreasing in the
         // integer dot product, so "score >= thr" is exactly "dot >= T", T = the smallest passing dot (bisection over |dot| <= 2^29)
@@ -301,10 +360,24 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     // flight, which drains the NBUF-deep fragment ring once per ring revolution; LDS reads return in order, so MFMA idx only needs
     // "at most NBUF - 1 reads outstanding" after the read for MFMA idx + NBUF - 1 has been issued.
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    const uint32_t a_lane = lds0 + (uint32_t)l32 * 128u + (uint32_t)((hi ^ swz) * 16);
+    // M16: lane (c, g4) of the A fragment (sl, k64, rb16): row rb16 * 16 + c, slot k64 * 4 + g4  ->  (c * 128 + ((g4 ^ swz16) * 16)) ^ (k64 * 64);
+    // one read feeds the two MFMAs of qb = 0, 1, so a step has as many fragment reads as the 32x32x32 form (NM) and twice the MFMAs
+    const uint32_t a_lane = M16 != 0 ? lds0 + (uint32_t)c16 * 128u + (uint32_t)((g4 ^ swz16) * 16) : lds0 + (uint32_t)l32 * 128u + (uint32_t)((hi ^ swz) * 16);
     qs_i32x4 af[NBUF];
+    if constexpr ((DBG & 2) != 0) {
+        // no fragment reads: the A operands are opaque copies of query fragments (bytes of the query image's distribution).  Left undefined,
+        // the fragments are ONE value to the compiler: it merged the accumulator chains of a tile's row blocks into a single dependent
+        // chain of half the MFMAs, which is what the "MFMA only" rows measured before this was fixed.
+#pragma unroll
+        for (int i = 0; i < NBUF; ++i) asm volatile("" : "=v"(af[i]) : "0"(bq[i]));
+    }
     auto read_frag = [&](qs_i32x4& dst, const uint32_t (&ad)[4], auto idxc) {   // MFMA idx of a step: (sl, kk, rb) = (idx / (4 RB), (idx / RB) % 4, idx % RB)
         constexpr int idx = decltype(idxc)::value;
+        if constexpr (M16 != 0) {   // read idx of a step: (sl, k64, rb16) = (idx / (2 R16), (idx / R16) % 2, idx % R16)
+            constexpr int sl16 = idx / (2 * R16), k64 = (idx / R16) % 2, rb16 = idx % R16;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(ad[k64]), "n"(sl16 * (RT * 128) + rb16 * (16 * 128)));
+            return;
+        }
         constexpr int sl = idx / (4 * RB), kk = (idx / RB) % 4, rb = idx % RB;
 #ifdef LYNSE_QS_AF_AGPR   // experiment (round 5): the A fragments land in AGPRs (does the LDS return then stop blocking the matrix pipe?)
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(ad[kk]), "n"(sl * (RT * 128) + rb * (32 * 128)));
@@ -321,12 +394,18 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     [[maybe_unused]] int f4_unit = 0x7f7f7f7f;   // E8M0 scale bytes 127 = 2^0 (ly_mfma_fp4: kept opaque in a VGPR across the loop)
     if constexpr (F4 != 0) asm volatile("" : "+v"(f4_unit));
 
+    [[maybe_unused]] qs_i32x4 acc16[R16][2];   // M16: (16-row block, 16-query block); the first k-step of a tile takes C = 0
+#pragma unroll
+    for (int i = 0; i < R16; ++i)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) acc16[i][qb] = qs_i32x4{0, 0, 0, 0};
+    [[maybe_unused]] uint32_t cnt16[2] = {0u, 0u};
     uint32_t cnt = 0;            // keys in this lane's private segment
     uint32_t c_ord = 0;          // tile ordinal being computed
     uint32_t c_stage = 0;
     uint32_t ad_cur[4], ad_nxt[4];   // fragment addresses (per kk) in the stage being computed / the next one
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) ad_nxt[kk] = a_lane ^ (uint32_t)(kk * 32);
+    for (int kk = 0; kk < 4; ++kk) ad_nxt[kk] = a_lane ^ (uint32_t)((kk % NKK) * KX);
     if constexpr (XPF) {   // the first fragments of step 0 (every later step: read during the step before)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * PPW) : "memory");
         __builtin_amdgcn_s_barrier();
@@ -364,14 +443,19 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
             constexpr int ks = (s * SL + sl) * 4 + kk;
             if constexpr ((DBG & 1) != 0) {
                 asm volatile("" ::"v"(af[idx % NBUF]), "v"(bq[ks]));
-            } else if constexpr ((DBG & 128) != 0) {
-                // energy experiment (round 5): the same MACs as TWO v_mfma_i32_16x16x64_i8 (16K MACs each from the same 16 B per lane and
-                // operand) — timing / power only, the accumulators do not hold the scan's dot products
-                qs_i32x4 c0 = __builtin_shufflevector(acc[rb], acc[rb], 0, 1, 2, 3), c1 = __builtin_shufflevector(acc[rb], acc[rb], 4, 5, 6, 7);
-                c0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[ks], c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[ks], c1, 0, 0, 0);
-                acc[rb][0] = c0[0]; acc[rb][1] = c0[1]; acc[rb][2] = c0[2]; acc[rb][3] = c0[3];
-                acc[rb][4] = c1[0]; acc[rb][5] = c1[1]; acc[rb][6] = c1[2]; acc[rb][7] = c1[3];
+            } else if constexpr (M16 != 0) {
+                // the fragment (sl, k64, rb16) against the two 16-query blocks: two v_mfma_i32_16x16x64_i8 into whole 4-register accumulators
+                constexpr int k64 = (idx / R16) % 2, rb16 = idx % R16;
+                constexpr int kb = (s * SL + idx / (2 * R16)) * 4 + k64 * 2;
+                ly_static_for<2>([&](auto qbc) {
+                    constexpr int qb = decltype(qbc)::value;
+                    if constexpr (kb == 0) {   // first k-step of a tile: C = 0
+                        const qs_i32x4 z = {0, 0, 0, 0};
+                        acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[kb + qb], z, 0, 0, 0);
+                    } else {
+                        acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[kb + qb], acc16[rb16][qb], 0, 0, 0);
+                    }
+                });
             } else if constexpr (F4 != 0) {
                 if constexpr (ks == 0) {
                     const f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -419,7 +503,7 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             ad_cur[kk] = ad_nxt[kk];
-            ad_nxt[kk] = (a_lane ^ (uint32_t)(kk * 32)) + c_stage * SB;
+            ad_nxt[kk] = (a_lane ^ (uint32_t)((kk % NKK) * KX)) + c_stage * SB;
         }
     };
     // STS: re-read tau (every lane) and the helper query's partition maxima — behind the step's ring pieces, every step at first
@@ -468,7 +552,64 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     [[maybe_unused]] int smp1 = -2147483647 - 1, smp2 = -2147483647 - 1;
     // ---- tile epilogue: this lane's RB x 16 dot products all belong to query qn
     auto epilogue = [&](uint32_t e_tile, bool emit, [[maybe_unused]] uint32_t e_ord_) {
-        if constexpr (SMP != 0) {
+        if constexpr (M16 != 0 && (DBG & 16) != 0) {
+#pragma unroll
+            for (int i = 0; i < R16; ++i)
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) asm volatile("" ::"v"(acc16[i][qb][r]));
+        } else if constexpr (M16 != 0) {
+            // ---- 16x16x64 form: accumulator (i, qb) holds rows i * 16 + 4 g4 + reg of query qn16[qb] — a group of four IS an accumulator.
+            // One maximum chain per query against its integer threshold, one ballot over both; the four lanes (g4) that share a query
+            // each have a private segment of their own.  Keys exactly as the 32x32x32 form makes them.
+            int gm[R16][2];
+#pragma unroll
+            for (int i = 0; i < R16; ++i)
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb) {
+                    const qs_i32x4 v = acc16[i][qb];
+                    const int m01 = v[0] > v[1] ? v[0] : v[1];
+                    const int m012 = m01 > v[2] ? m01 : v[2];
+                    gm[i][qb] = m012 > v[3] ? m012 : v[3];
+                }
+            int mx[2] = {gm[0][0], gm[0][1]};
+#pragma unroll
+            for (int i = 1; i < R16; ++i)
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb) mx[qb] = mx[qb] > gm[i][qb] ? mx[qb] : gm[i][qb];
+            if (__builtin_expect(__ballot(mx[0] >= T16[0] || mx[1] >= T16[1]) != 0ull, 0)) {
+                const uint32_t rbase = a.row0 + e_tile * RT;
+                if constexpr (MSK != 0) {   // (uniform) a tile of the emit-all sample stage: its rows are candidates already
+                    if (a.skip_stride && rbase % a.skip_stride < 256u && rbase / a.skip_stride < a.skip_tiles) return;
+                }
+#pragma unroll
+                for (int i = 0; i < R16; ++i) {
+#pragma unroll
+                    for (int qb = 0; qb < 2; ++qb) {
+                        if (__builtin_expect(__ballot(gm[i][qb] >= T16[qb]) == 0ull, 1)) continue;
+                        uint64_t* segdst = a.candB + ((size_t)qn16[qb] * a.nseg + (blockIdx.x * 4 + g4)) * a.seg;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int v = acc16[i][qb][e];
+                            if (v >= T16[qb]) {
+                                const uint32_t m = rbase + i * 16 + 4 * g4 + e;
+                                if (m < a.row1 && (MSK == 0 || ((a.mask[m >> 5] >> (m & 31)) & 1u))) {
+                                    const uint64_t key = make_key(b_q16[qb] + s_q16[qb] * (float)v, m, false);
+                                    if (cnt16[qb] < a.seg) {
+                                        segdst[cnt16[qb]] = key;
+                                        ++cnt16[qb];
+                                    } else {
+                                        const uint32_t slot = atomicAdd(&a.count[qn16[qb]], 1u);
+                                        if (slot < a.cap) a.cand[(size_t)qn16[qb] * a.cap + slot] = key;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        } else if constexpr (SMP != 0) {
             const uint32_t rbase = tile_row0(e_tile);
             const int pos0 = (int)((e_ord_ & 31u) << 5);
             const bool whole = rbase + RT <= a.row1;   // (uniform) every row of the tile exists: all but the shard's last tile
@@ -703,6 +844,11 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
             }
         }
     }
+    if constexpr (M16 != 0) {
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+            if (a.seg && q_ok16[qb]) a.segcnt[(size_t)qn16[qb] * a.nseg + (blockIdx.x * 4 + g4)] = (uint8_t)cnt16[qb];
+    } else
     if (a.seg && q_ok) a.segcnt[(size_t)qn * a.nseg + (blockIdx.x * 2 + hi)] = (uint8_t)cnt;
     if constexpr (TIMING) {
         if (a.dbg && lane == 0 && blockIdx.x < 64) {

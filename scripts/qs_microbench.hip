@@ -6,6 +6,9 @@
 //    (s_memtime ticks of workgroup 0 / event time) and wall-clock stamps a power sampler can be joined on.
 // 0. `qs_microbench operand [rows rounds sigma]`: the operand-distribution axis instead (row bytes uniform / non-negative / 6-bit / constant x
 //    query image non-negative / mixed sign, the library's default instantiation with and without emission; profiles/sq7_operand_energy.txt).
+// 1b. `qs_microbench qs16 [rows rounds sigma]`: the MFMA-shape axis: the default instantiation against its 16x16x64 form (scan_qs.h, M16) — the check
+//    passes of both, then everything / MFMA only / MFMA + LDS reads / DMA + MFMA of both in interleaved rounds, on SQ7-like and centred operands, with
+//    the s_memtime clock, the socket power and the cycles per MFMA (profiles/qs16_microbench.txt).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -pragma-unroll-threshold=262144 \
 //        [-DLYNSE_EXPERIMENTS] -o qs_microbench scripts/qs_microbench.hip
 #include <algorithm>
@@ -215,9 +218,9 @@ struct Variant {
     bool qs;
 };
 
-template <int NSLAB, int RB, int SL, int NS, bool XPF, int NBUF, int DBG, int PP = 0, int STS = 0, int MET = 0>
+template <int NSLAB, int RB, int SL, int NS, bool XPF, int NBUF, int DBG, int PP = 0, int STS = 0, int MET = 0, int M16 = 0>
 static void launch_qs(ScanArgs a, uint32_t grid, hipStream_t st) {
-    auto k = k_scan_qs<NSLAB, RB, SL, NS, XPF, NBUF, DBG, PP, STS, MET>;
+    auto k = k_scan_qs<NSLAB, RB, SL, NS, XPF, NBUF, DBG, PP, STS, MET, 0, 0, 0, M16>;
     constexpr size_t lds = (size_t)NS * SL * RB * 32 * 128 + (STS ? QS_STS_LDS : 0) + (MET == 1 ? (NS + 1) * RB * 32 * 4 : 0);
     static bool done = false;
     if (!done) { set_lds(k, lds); done = true; }
@@ -300,6 +303,10 @@ int main(int argc, char** argv) {
     // "operand" as the first argument: the operand-distribution axis (section 0 below) instead of the variant A/B; the other arguments follow it
     const bool operand_axis = argc > 1 && strcmp(argv[1], "operand") == 0;
     if (operand_axis) { --argc; ++argv; }
+    // "qs16" as the first argument: the MFMA-shape A/B (section 1b below): the check passes of the default instantiation and of its 16x16x64
+    // form only, then both forms and their decompositions timed in interleaved rounds on SQ7-like and on centred operands
+    const bool qs16_axis = !operand_axis && argc > 1 && strcmp(argv[1], "qs16") == 0;
+    if (qs16_axis) { --argc; ++argv; }
     const uint64_t n_big = argc > 1 ? strtoull(argv[1], nullptr, 10) : 10000000ull;
     const int rounds = argc > 2 ? atoi(argv[2]) : 5;
     const double sigma_tight = argc > 3 ? atof(argv[3]) : 4.3;   // thresholds in units of the dot product's standard deviation
@@ -370,6 +377,9 @@ int main(int argc, char** argv) {
     vars.push_back({"qs RB1 SL6 NS6 XPF NBUF12 PP1", 2, launch_qs<6, 1, 6, 6, true, 12, 0, 1>, true});
     vars.push_back({"qs RB1 SL6 NS5 XPF NBUF8 PP1", 2, launch_qs<6, 1, 6, 5, true, 8, 0, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 noXPF NBUF8 PP1", 2, launch_qs<6, 2, 6, 3, false, 8, 0, 1>, true});
+    // the 16x16x64 form at the same wave tile (scan_qs.h, M16): four private segments per workgroup and query
+    vars.push_back({"qs16 RB2 SL6 NS3 noXPF NBUF8 PP1", 4, launch_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 1>, true});
+    vars.push_back({"qs16 RB2 SL6 NS3 noXPF NBUF8", 4, launch_qs<6, 2, 6, 3, false, 8, 0, 0, 0, 0, 1>, true});
     vars.push_back({"qs2 4w x 64q RB2 NS3 NBUF8", 2, launch_qs2<6, 2, 3, 8, 0>, true});
     vars.push_back({"qs2 4w x 64q RB2 NS3 NBUF12", 2, launch_qs2<6, 2, 3, 12, 0>, true});
     vars.push_back({"qs2 4w x 64q RB1 NS6 NBUF8", 2, launch_qs2<6, 1, 6, 8, 0>, true});
@@ -398,7 +408,10 @@ int main(int argc, char** argv) {
     vars.push_back({"old<2,4,4,2> | no epilogue", 4, launch_old<false, 16>, false});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | no epilogue", 2, launch_qs<6, 2, 6, 3, false, 8, 16, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | MFMA only 32x32x32", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 8 + 2, 1>, true});
-    vars.push_back({"qs RB2 SL6 NS3 PP1 | MFMA only 16x16x64", 2, launch_qs<6, 2, 6, 3, false, 8, 128 + 16 + 8 + 2, 1>, true});
+    vars.push_back({"qs16 RB2 SL6 NS3 PP1 | no epilogue", 4, launch_qs<6, 2, 6, 3, false, 8, 16, 1, 0, 0, 1>, true});
+    vars.push_back({"qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8 + 2, 1, 0, 0, 1>, true});
+    vars.push_back({"qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8, 1, 0, 0, 1>, true});
+    vars.push_back({"qs16 RB2 SL6 NS3 PP1 | DMA + MFMA", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 2, 1, 0, 0, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | MFMA + LDS reads", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 8, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | DMA + MFMA", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 2, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | DMA only", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 2 + 1, 1>, true});
@@ -584,6 +597,7 @@ int main(int argc, char** argv) {
         for (size_t vi = 0; vi < vars.size(); ++vi) {
             const Variant& v = vars[vi];
             if (v.name.find('|') != std::string::npos) continue;
+            if (qs16_axis && v.name.rfind("qs16", 0) != 0 && v.name != "qs RB2 SL6 NS3 noXPF NBUF8 PP1") continue;
             const bool l2v = v.name.rfind("L2", 0) == 0;
             if (l2v) set_thr_l2(sig, nq);
             struct Restore { std::function<void()> f; ~Restore() { f(); } } restore{[&]() { if (l2v) set_thr(sig, nq); }};
@@ -653,6 +667,7 @@ int main(int argc, char** argv) {
                 std::vector<uint64_t> got = collect(b, nq, a.nseg, a.seg);
                 const std::vector<uint64_t>& ref = ref_use;
                 const bool ok = got == ref;
+                if (ok && qs16_axis) printf("ok       pass %d %-34s starve %d: %zu keys, identical to the brute-force set\n", pass, v.name.c_str(), starve, got.size());
                 if (!ok) {
                     ++bad;
                     printf("MISMATCH pass %d %-34s starve %d: ref %zu keys, got %zu\n", pass, v.name.c_str(), starve, ref.size(), got.size());
@@ -665,6 +680,130 @@ int main(int argc, char** argv) {
             }
         }
         printf("check pass %d: n %u nq %u sigma %.1f -> %zu reference keys (L2: %zu); mismatching variants so far %d\n", pass, n, nq, sig, ref.size(), ref_l2.size(), bad);
+    }
+
+    // ---- 1b. MFMA shape (first argument "qs16"): v_mfma_i32_32x32x32_i8 against v_mfma_i32_16x16x64_i8 at the same wave tile, everything and
+    // the decompositions, on (b) SQ7-like operands (rows and query image in [0,127]) and (a) centred ones.  Protocol of section 0.
+    if (qs16_axis) {
+#ifndef LYNSE_EXPERIMENTS
+        fprintf(stderr, "the qs16 axis needs -DLYNSE_EXPERIMENTS (the decomposition rows)\n");
+        return 2;
+#else
+        struct Op { const char* name; uint32_t and_mask; bool nonneg; double mean, var; };
+        const Op ops[2] = {{"(b) rows [0,127], queries [0,127]", 0x7f7f7f7fu, true, 63.5, (16384.0 - 1.0) / 12.0},
+                           {"(a) rows [-128,127], queries [-127,127]", 0xffffffffu, false, -0.5, (65536.0 - 1.0) / 12.0}};
+        const char* names[8] = {"qs RB2 SL6 NS3 noXPF NBUF8 PP1", "qs16 RB2 SL6 NS3 noXPF NBUF8 PP1",
+                                "qs RB2 SL6 NS3 PP1 | MFMA only 32x32x32", "qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64",
+                                "qs RB2 SL6 NS3 PP1 | MFMA + LDS reads", "qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads",
+                                "qs RB2 SL6 NS3 PP1 | DMA + MFMA", "qs16 RB2 SL6 NS3 PP1 | DMA + MFMA"};
+        const Variant* vs[8] = {};
+        for (int i = 0; i < 8; ++i) {
+            for (const Variant& v : vars) if (v.name == names[i]) vs[i] = &v;
+            if (!vs[i]) { fprintf(stderr, "variant %s is not built\n", names[i]); return 2; }
+        }
+        const uint32_t n = (uint32_t)n_big;
+        auto fill = [&](const Op& o) {
+            hipLaunchKernelGGL(k_fill_rows, dim3(ncu * 8), dim3(256), 0, 0, b.V, n_big * D, 7ull, o.and_mask, 0u);
+            hipLaunchKernelGGL(k_fill_queries, dim3(QPAD), dim3(256), 0, 0, b.Qp, b.img, NQ, QPAD, D, NSLABS, o.nonneg);
+            CK(hipDeviceSynchronize());
+        };
+        auto set_thr_op = [&](const Op& o, double sig) {   // T_q = mean_c sum(u) + sig sd_c |u|
+            std::vector<float> one(NQ, 1.0f), zero(NQ, 0.0f), th(NQ);
+            std::vector<int> ti(NQ);
+            for (uint32_t q = 0; q < NQ; ++q) {
+                double su = 0.0, su2 = 0.0;
+                for (uint32_t i = 0; i < D; ++i) { const double u = query_elem(q, i, o.nonneg); su += u; su2 += u * u; }
+                th[q] = (float)(std::floor(o.mean * su + sig * std::sqrt(o.var * su2)) + 1.0);
+                ti[q] = (int)th[q];
+            }
+            CK(hipMemcpy(b.qinv, one.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.qn2, zero.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.thr, th.data(), NQ * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(b.Ti, ti.data(), NQ * 4, hipMemcpyHostToDevice));
+        };
+        // key sets of both forms against the brute-force kernel on the SQ7-like operands too (the four passes above ran on the centred ones)
+        {
+            const uint32_t ns = 65536u + 37u;
+            fill(ops[0]);
+            set_thr_op(ops[0], 3.0);
+            uint64_t* ref_d; uint32_t* ref_n;
+            const uint32_t ref_cap = 4u << 20;
+            CK(hipMalloc(&ref_d, (size_t)ref_cap * 8)); CK(hipMalloc(&ref_n, 4)); CK(hipMemset(ref_n, 0, 4));
+            hipLaunchKernelGGL(k_ref, dim3((ns + 63) / 64), dim3(256), 0, 0, b.V, D, D, ns, b.Qp, NQ, b.Ti, ref_d, ref_n, ref_cap);
+            CK(hipDeviceSynchronize());
+            uint32_t rn; CK(hipMemcpy(&rn, ref_n, 4, hipMemcpyDeviceToHost));
+            std::vector<uint64_t> ref(std::min(rn, ref_cap));
+            CK(hipMemcpy(ref.data(), ref_d, ref.size() * 8, hipMemcpyDeviceToHost));
+            std::sort(ref.begin(), ref.end());
+            CK(hipFree(ref_d)); CK(hipFree(ref_n));
+            for (int i = 0; i < 2; ++i) {
+                ScanArgs a = base_args(b, 0, ns, NQ);
+                a.nseg = ncu * vs[i]->segs_per_wg;
+                a.seg = std::min<uint32_t>(255u, SEG_KEYS / a.nseg);
+                clear(a.nseg);
+                vs[i]->launch(a, ncu, 0);
+                CK(hipDeviceSynchronize());
+                const bool ok = collect(b, NQ, a.nseg, a.seg) == ref;
+                bad += !ok;
+                printf("check %-36s %-34s n %u sigma 3.0: %zu reference keys%s\n", ops[0].name, names[i], ns, ref.size(), ok ? ", identical" : "   <-- MISMATCH");
+            }
+        }
+        struct Cell { std::vector<float> ms; double clk = 0, watts = 0, smhz = 0, ticks = 0; };
+        Cell cells[2][8];
+        hipEvent_t e0, e1;
+        CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        for (int r = 0; r < rounds + 1; ++r)
+            for (int oi = 0; oi < 2; ++oi) {
+                fill(ops[oi]);
+                set_thr_op(ops[oi], sigma_tight);
+                for (int vi = 0; vi < 8; ++vi) {
+                    const Variant& v = *vs[vi];
+                    Cell& c = cells[oi][vi];
+                    ScanArgs a = base_args(b, 0, n, NQ);
+                    a.nseg = ncu * v.segs_per_wg;
+                    a.seg = std::min<uint32_t>(255u, SEG_KEYS / a.nseg);
+                    a.debug_flags = 64; a.dbg = b.dbg;
+                    for (int w = 0; w < long_warm; ++w) { if (w < 2) clear(a.nseg); v.launch(a, ncu, 0); }
+                    clear(a.nseg);
+                    CK(hipDeviceSynchronize());
+                    sampler.begin();
+                    CK(hipEventRecord(e0, 0));
+                    for (int i = 0; i < long_reps; ++i) v.launch(a, ncu, 0);
+                    CK(hipEventRecord(e1, 0));
+                    CK(hipEventSynchronize(e1));
+                    { double pw, mz; sampler.end(&pw, &mz); if (r == rounds) { c.watts = pw; c.smhz = mz; } }
+                    float t; CK(hipEventElapsedTime(&t, e0, e1));
+                    if (r > 0) c.ms.push_back(t / long_reps);
+                    unsigned long long tk[2];
+                    CK(hipMemcpy(tk, b.dbg, 16, hipMemcpyDeviceToHost));
+                    c.ticks = (double)(tk[1] - tk[0]);
+                    c.clk = c.ticks / (t / long_reps * 1e3);
+                }
+            }
+        // MFMAs one SIMD issues in a launch of workgroup 0: its tiles x 48 (32x32x32) or 96 (16x16x64) per wave, two waves per SIMD
+        const double tiles0 = std::ceil((double)((n + 63) / 64) / ncu);
+        printf("---- MFMA shape: %u rows x %u B, %u queries, thresholds at %.1f sd; us per launch: median / min / spread of %d rounds of %d launches behind %d warm-up launches;\n"
+               "     s_memtime MHz = shader cycles of workgroup 0 / launch time; cyc/MFMA = those cycles / (MFMAs its SIMD issued: %.0f tiles x 48 or 96 x 2 waves)\n",
+               n, D, NQ, sigma_tight, rounds, long_reps, long_warm, tiles0);
+        for (int oi = 0; oi < 2; ++oi) {
+            printf("-- %s\n", ops[oi].name);
+            double med_of[8], sp_of[8];
+            for (int vi = 0; vi < 8; ++vi) {
+                Cell& c = cells[oi][vi];
+                std::sort(c.ms.begin(), c.ms.end());
+                const double med = c.ms[c.ms.size() / 2] * 1e3, mn = c.ms.front() * 1e3, sp = (c.ms.back() - c.ms.front()) * 1e3;
+                med_of[vi] = med; sp_of[vi] = sp;
+                printf("%-46s %8.1f %8.1f %7.1f   %6.0f MHz   hwmon %6.0f W %6.0f MHz   %6.1f cyc/MFMA\n", names[vi], med, mn, sp, c.clk, c.watts, c.smhz,
+                       c.ticks / (tiles0 * ((vi & 1) ? 96.0 : 48.0) * 2.0));
+            }
+            const double gain = med_of[0] - med_of[1], need = 3.0 * std::max(sp_of[0], sp_of[1]);
+            printf("GATE %s: 32x32x32 %.1f us - 16x16x64 %.1f us = %.1f us; three times the larger spread = %.1f us -> %s\n", ops[oi].name, med_of[0], med_of[1], gain, need,
+                   gain > need ? "16x16x64 WINS" : "no gain");
+        }
+        sampler.finish();
+        printf("mismatches: %d\n", bad);
+        return bad ? 1 : 0;
+#endif
     }
 
     // ---- 2. timing
