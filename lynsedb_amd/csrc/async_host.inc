@@ -36,8 +36,7 @@ struct lynse_hip_ticket {
     float* out_dists = nullptr;
     uint32_t* out_counts = nullptr;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_done = nullptr;
-    size_t ev_used = 0;
-    std::vector<std::pair<size_t, uint64_t>> scan_events;
+    ScanProf sprof;   // events of the ticket taken from the context's pool, scan launches of a profiled search
 };
 
 namespace {
@@ -102,13 +101,16 @@ int ticket_enqueue_local(lynse_hip_ticket* t, int level, bool i8c, bool allow_st
         return LYNSE_OK;
     }
     if (t->packed) LY_HIP(hipMemcpyAsync(w.QW, t->d_q, (size_t)t->nq * h->words * 8, hipMemcpyDeviceToDevice, st));
-    bool sampled = false, used_sts = false;
     // float queries are read in place (the caller keeps them valid until wait); counts + per-query overflow flags go straight
     // into the pinned header of the context (a sharded ticket looks at the status word of the exchange first)
-    LY_TRY(run_chunk(h, (uint32_t)t->nq, t->kk, t->k, t->metric, level, st, &t->ev_used, &t->scan_events, &sampled, nullptr, nullptr, i8c,
-                     d.rows, d.dists, d.counts, d.status, t->packed ? nullptr : (const float*)t->d_q, true, allow_sts, &used_sts));
-    t->sampled = sampled;
-    if (level == 0 && allow_sts) t->sts = used_sts;
+    ChunkReq rq;
+    rq.nq = (uint32_t)t->nq; rq.k = t->kk; rq.out_k = t->k; rq.metric = t->metric; rq.level = level;
+    rq.qsrc = t->packed ? nullptr : (const float*)t->d_q; rq.i8c = i8c; rq.allow_sts = allow_sts;
+    rq.out.rows = d.rows; rq.out.dists = d.dists; rq.out.counts2 = d.counts; rq.out.any_ovf = d.status; rq.out.hdr_direct = true;
+    ChunkResult res;
+    LY_TRY(run_chunk(h, rq, st, &t->sprof, &res));
+    t->sampled = res.sampled;
+    if (level == 0 && allow_sts) t->sts = res.used_sts;
     return LYNSE_OK;
 }
 
@@ -263,14 +265,14 @@ int submit_impl(lynse_hip_flat* h, lynse_hip_comm* c, const void* d_queries, boo
             LY_TRY(comm_reserve_blocks(c, slot, total));   // (c->mu is held: comm_lk)
         }
         hipStream_t st = cur(h).stream;
-        LY_TRY(get_event(h, t->ev_used++, &t->ev_done));
+        LY_TRY(get_event(h, t->sprof.ev_used++, &t->ev_done));
         auto local_part = [&]() -> int {
             if (pre_rc != LYNSE_OK) { g_last_error = pre_msg; return pre_rc; }
             LY_TRY(ensure_workspace(h, k));
             t->profiled = profile_begin_search(h);
             if (t->profiled) {
-                LY_TRY(get_event(h, t->ev_used++, &t->ev_begin));
-                LY_TRY(get_event(h, t->ev_used++, &t->ev_end));
+                LY_TRY(get_event(h, t->sprof.ev_used++, &t->ev_begin));
+                LY_TRY(get_event(h, t->sprof.ev_used++, &t->ev_end));
                 LY_HIP(hipEventRecord(t->ev_begin, st));
             }
             t->i8c = !binary && h->n > 0 && i8c_eligible(h, metric, false, nq) && i8c_codes_ready(h, metric, nq) && i8c_codes_finite(h, metric, nq);
@@ -406,6 +408,6 @@ extern "C" int lynse_hip_flat_search_wait(lynse_hip_ticket* tp) {
         }
     }
     if (t->profiled && t->ev_begin)
-        LY_TRY(prof_accumulate(h, cur(h), t->ev_begin, t->ev_end, t->scan_events, binary, fallback_queries));
+        LY_TRY(prof_accumulate(h, cur(h), t->ev_begin, t->ev_end, t->sprof.scan_events, binary, fallback_queries));
     return LYNSE_OK;
 }

@@ -140,7 +140,7 @@ extern "C" int lynse_hip_ivf_search_submit_f32_device(lynse_hip_ivf* h, lynse_hi
             comm_block_layout(nq, k, &ro, &dof, &co, &so, &total);
             LY_TRY(comm_reserve_blocks(c, slot, total));   // (c->mu is held: comm_lk)
         }
-        LY_TRY(get_event(s, t->base.ev_used++, &t->base.ev_done));
+        LY_TRY(get_event(s, t->base.sprof.ev_used++, &t->base.ev_done));
         const LocalDst d = ticket_dst(&t->base);
         if (d.status) LY_HIP(hipMemsetAsync(d.status, 0, 16, st));
         auto local_part = [&]() -> int {

@@ -1185,14 +1185,14 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
             lynse_hip_flat* cs = h->cstore;
             Workspace& cw = cur(cs).ws;
             if (small_path_ok(cs, nq, np_eff, route_metric, false)) {
-                LY_TRY(run_small(cs, nq, np_eff, np_eff, route_metric, st, nullptr, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, cw.h_hdr + cw.qcap, w.Qf));
+                LY_TRY(run_small(cs, nq, np_eff, np_eff, route_metric, st, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, cw.h_hdr + cw.qcap, w.Qf));
                 as->routed_by_chunk = false;
             } else {
-                size_t ev_used = 0;
-                std::vector<std::pair<size_t, uint64_t>> scan_events;
-                bool sampled = false;
-                LY_TRY(run_chunk(cs, nq, np_eff, np_eff, route_metric, 0, st, &ev_used, &scan_events, &sampled, nullptr, nullptr, false,
-                                 scr.d_route_rows, scr.d_route_d, scr.d_route_c, as->status, w.Qf, true, false));
+                ScanProf sprof;
+                ChunkReq rq;
+                rq.nq = nq; rq.k = rq.out_k = np_eff; rq.metric = route_metric; rq.qsrc = w.Qf; rq.allow_sts = false;
+                rq.out.rows = scr.d_route_rows; rq.out.dists = scr.d_route_d; rq.out.counts2 = scr.d_route_c; rq.out.any_ovf = as->status; rq.out.hdr_direct = true;
+                LY_TRY(run_chunk(cs, rq, st, &sprof));
                 as->routed_by_chunk = true;
             }
             *dev64 = scr.d_route_rows;
@@ -1297,9 +1297,9 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
             hipEvent_t pe0 = nullptr, pe1 = nullptr;
             const bool timed_small = s->profiling.load();
             if (timed_small) { LY_TRY(get_event(s, 0, &pe0)); LY_TRY(get_event(s, 1, &pe1)); }
-            LY_TRY(run_small(s, nq, np_f, np_f, route_metric, st, nullptr, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, w.overflow, d_q, &cr, nullptr));
+            LY_TRY(run_small(s, nq, np_f, np_f, route_metric, st, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, w.overflow, d_q, &cr, nullptr));
             if (timed_small) LY_HIP(hipEventRecord(pe0, st));
-            LY_TRY(run_small(s, nq, k, out_k, metric, st, nullptr, nullptr, r_dst, d_dst, c_dst, w.h_hdr + QCHUNK, d_q, &sr, &si));
+            LY_TRY(run_small(s, nq, k, out_k, metric, st, nullptr, r_dst, d_dst, c_dst, w.h_hdr + QCHUNK, d_q, &sr, &si));
             if (timed_small) LY_HIP(hipEventRecord(pe1, st));
             LY_HIP(hipStreamSynchronize(st));
             if (timed_small) {
@@ -1369,9 +1369,11 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     const uint32_t SK = i8c ? 128u : (h16 ? (uint32_t)HK : (uint32_t)GL_BK);  // K elements per slab of the scan kernel in use
     // squared L2 / cosine on the int8 pass: inner products of augmented resp. unit vectors in the NEGATED score space
     // (I8cPrepArgs::aug / ::cosine, kernels.h) — scan and select run as IP, the exact rescoring negates, k_final negates back
-    const bool aug = i8c && metric == M_L2, cosq = i8c && metric == M_COS;
+    const I8cForm form = i8c_form(s, metric, 0, false);   // (nqc = 0: never the plain-code L2 form, a FLAT tiling)
+    const I8cOperand opd = i8c ? i8c_operand(s, form, false) : I8cOperand{};
+    const bool aug = i8c && form == I8C_L2_AUG, cosq = i8c && form == I8C_COS;
     const int key_metric = (aug || cosq) ? (int)M_IP : metric;
-    const uint32_t D = h->dim, nslab = ((aug ? D + s->aug_cols : D) + SK - 1) / SK;
+    const uint32_t D = h->dim, nslab = ((i8c ? opd.cols : D) + SK - 1) / SK;
     const uint32_t qpad = SCAN_BQ_LARGE;
     LY_HIP(hipMemcpyAsync(w.Qf, q_host, (size_t)nq * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     if (binary) {
@@ -1389,13 +1391,10 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     } else if (i8c) {
         // ---- certified int8 coarse pass (DESIGN.md §3b) over the probed lists: the SQ8 codes of the slab, the symmetric int8
         // query image, coarse score B_q + s_q * dot within E of the exact score; survivors are rescored exactly as always
-        if (nq != qpad || (aug ? D + s->aug_cols : D) % 128 != 0) LY_HIP(hipMemsetAsync(w.Q16, 0, (size_t)nslab * qpad * 128, st));
+        if (nq != qpad || opd.cols % 128 != 0) LY_HIP(hipMemsetAsync(w.Q16, 0, (size_t)nslab * qpad * 128, st));
         I8cPrepArgs p{};
-        p.Q = w.Qf; p.D = D; p.qpad = qpad; p.nslab = nslab; p.mins = aug ? s->sq8a_mins : (cosq ? s->sq8c_mins : s->sq8_mins);
-        p.scales = aug ? s->sq8a_scales : (cosq ? s->sq8c_scales : s->sq8_scales);
-        p.a1 = aug ? s->sq8a_a1 : (cosq ? s->sq8c_a1 : s->sq8_a1); p.vmax = s->vmax;
-        if (i8c_cs_on()) { p.a2sq = aug ? s->sq8a_a2sq : (cosq ? s->sq8c_a2sq : s->sq8_a2sq); p.eps2 = aug ? s->sq8a_eps2 : (cosq ? s->sq8c_eps2 : s->sq8_eps2); }   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
-        p.cosine = cosq ? 1 : 0; p.aug = aug ? (int)s->aug_cols : 0;
+        p.Q = w.Qf; p.D = D; p.qpad = qpad; p.nslab = nslab; p.vmax = s->vmax;
+        fill_i8c_prep(p, opd, form);
         p.img = reinterpret_cast<int8_t*>(w.Q16); p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
         hipLaunchKernelGGL(k_i8c_prep_queries, dim3(nq), dim3(256), 0, st, p);
@@ -1508,7 +1507,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         a.emit_all = 0; a.debug_flags = 0; a.tiles = d_win_tiles; a.ntiles_dev = ntiles_dev; a.pair_q = scr.d_pair_q; a.mask = smask;
         const uint32_t grid = ntiles_dev ? (uint32_t)s->num_cu * 2 : std::min<uint32_t>(a.ntiles, (uint32_t)s->num_cu * 2);
         if (i8c) {
-            a.V16 = reinterpret_cast<const _Float16*>(aug ? s->sq8a : (cosq ? s->sq8c : s->sq8)); a.ld16 = aug ? s->ld8a : s->ld8;
+            a.V16 = reinterpret_cast<const _Float16*>(opd.codes); a.ld16 = opd.ld;
             LY_TRY((launch_h16<with(I8C_SMALL, &H16Cfg::tiled, true)>(grid, st, a)));
         } else
         LY_TRY(launch_scan_tiled(a, metric, s->sv != 1.0f, grid, st));

@@ -251,6 +251,29 @@ struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
 struct RbqState;  // FLAT-*-RABITQ codes + search scratch (rabitq_host.inc)
 struct RangeState;  // range search scratch (range_host.inc)
 
+// One int8 copy of a shard's rows for the certified coarse pass (lynse_hip_flat::sq8 / sq8a / sq8c / sq7) with what the prep kernel needs
+// to certify a bound over it.
+struct CodeSet {
+    int8_t* codes = nullptr;     // cap x ld signed bytes
+    uint64_t n = 0, cap = 0;     // rows covered / row capacity
+    float *mins = nullptr, *scales = nullptr;   // per column
+    uint32_t* mm = nullptr;      // 2 x cols ordered-int min / max
+    uint32_t* stats = nullptr;   // 4 words of k_sq8_quantize: [0] max row L1 of the codes, [1] non-finite elements, [2] max row sum of squares, [3] eps2
+    uint32_t a1 = 0, a2sq = 0;   // max row L1 / sum of squares of the codes
+    float eps2 = 0.0f;           // bound of the max row sum of squared quantisation residuals
+    bool finite = false;
+    uint32_t cols = 0, ld = 0;   // columns coded / pitch in bytes
+    int *sum = nullptr, *sum2 = nullptr;   // per-row sums of the codes and their squares (the plain set only: FLAT-*-SQ8)
+    bool ready(uint64_t rows) const { return codes && n == rows; }
+    uint64_t hbm_bytes() const { return codes ? cap * ld + (sum ? 2ull * (cap + 256) * 4 : 0ull) : 0ull; }
+    void release() {
+        for (void* p : {(void*)codes, (void*)mins, (void*)scales, (void*)mm, (void*)stats, (void*)sum, (void*)sum2})
+            if (p) (void)hipFree(p);
+        codes = nullptr; mins = scales = nullptr; mm = stats = nullptr; sum = sum2 = nullptr;
+        n = cap = 0;
+    }
+};
+
 struct lynse_hip_flat {
     uint32_t dim = 0, ld = 0, words = 0;
     int device = 0;
@@ -313,50 +336,24 @@ struct lynse_hip_flat {
     int dtype = LYNSE_DTYPE_F32;  // F16: rows hold f16-representable values, distances use the f16 kernels' sequential sums
     uint32_t stage0_rows = 4096, growth = 8, cap = 16384;
 
-    // SQ8 two-pass mode (FLAT-*-SQ8): signed codes (code - 128), per-dimension min / scale, per-row sums; built lazily
-    int8_t* sq8 = nullptr;
-    uint32_t ld8 = 0;
-    uint64_t n_sq8 = 0, sq8_cap = 0;
-    float *sq8_mins = nullptr, *sq8_scales = nullptr;
-    int *sq8_sum = nullptr, *sq8_sum2 = nullptr;
-    uint32_t* sq8_mm = nullptr;  // 2 x dim ordered-int min / max
-    uint32_t* sq8_stats = nullptr;  // [0] max row L1 of the signed codes, [1] non-finite elements (k_sq8_quantize)
+    // The int8 copies of the rows (CodeSet above), each built lazily and kept up to date by ensure_codes_locked (sq7: ensure_sq7_locked):
+    // sq8:  SQ8 two-pass mode (FLAT-*-SQ8) and the IP / plain-L2 forms of the certified int8 pass: signed codes (code - 128), per-dimension
+    //       min / scale, per-row sums; pitch ld8
+    // sq8a: the L2 form of the certified int8 pass: codes of the AUGMENTED rows [v, |v|^2] (k_i8c_prep_queries, aug = 1), pitch
+    //       ld8a = round_up(dim + 1, 128) (whole 128-column slabs: the non-ragged scan kernels), first L2 batch of 33..256 queries
+    // sq8c: the cosine form: codes of the UNIT rows fl(v_d * rinv[row]) (pitch ld8), first cosine batch of 33..256 queries
+    // sq7:  the NON-NEGATIVE 7-bit copy of the codes (scale 127 / range, codes [0, 127] stored without the offset; layout and pitch of `sq8`,
+    //       whose minima and min / max table it borrows: its own mins / mm stay null) the 129..256-query IP scan streams instead of `sq8` when
+    //       rows — and with them, presumably, queries — are non-negative: every MAC of the int8 pipe is then non-negative and the
+    //       power-capped scan holds a higher clock.  Follows the SQ8 life cycle; a1 / a2sq are those of the (uncentred) codes.
+    CodeSet sq8, sq8a, sq8c, sq7;
+    uint32_t ld8 = 0, ld8a = 0, aug_cols = 1;     // aug_cols: columns carrying |v|^2 (a power of two <= 32 that fits the slab padding)
     uint32_t* sq8_mm_prev = nullptr;  // scratch of the incremental append: the min / max table before the new rows were merged + a flag word
-    uint32_t sq8_a1 = 0, sq8_a2sq = 0;   // max row L1 / sum of squares of the signed codes
-    float sq8_eps2 = 0.0f;                 // bound of the max row sum of squared quantisation residuals (k_sq8_quantize stats[3])
-    bool sq8_finite = false;
-    uint64_t sq8_fit = 0;   // counts the fits of the min / max table (a new fit recodes every row: ensure_sq8_locked)
-    // SQ7: the NON-NEGATIVE 7-bit copy of the codes (scale 127 / range, codes [0, 127] stored without the offset; layout, pitch and minima
-    // of `sq8`) the 129..256-query IP scan streams instead of `sq8` when rows — and with them, presumably, queries — are non-negative: every
-    // MAC of the int8 pipe is then non-negative and the power-capped scan holds a higher clock.  Follows the SQ8 life cycle.
-    int8_t* sq7 = nullptr;
-    uint64_t n_sq7 = 0, sq7_cap = 0, sq7_fit = 0;   // sq7_fit: the sq8_fit the copy was coded under
-    float* sq7_scales = nullptr;
-    uint32_t* sq7_stats = nullptr;
-    uint32_t sq7_a1 = 0, sq7_a2sq = 0;   // max row sum / sum of squares of the (uncentred) codes
-    float sq7_eps2 = 0.0f;
+    uint64_t sq8_fit = 0;   // counts the fits of the min / max table of `sq8` (a new fit recodes every row: ensure_codes_locked)
+    uint64_t sq7_fit = 0;   // the sq8_fit the SQ7 copy was coded under
     std::atomic<int> sq7_strikes{0};       // overflows of the SQ7 scan (each re-answered on the SQ8 codes); 3 switch it off for the handle
-    // the L2 form of the certified int8 pass: SQ8 codes of the AUGMENTED rows [v, |v|^2] (k_i8c_prep_queries, aug = 1), pitch
-    // ld8a = round_up(dim + 1, 128) (whole 128-column slabs: the non-ragged scan kernels), built lazily on the first L2 batch
-    // of 33..256 queries
-    int8_t* sq8a = nullptr;
-    uint32_t ld8a = 0, aug_cols = 1;     // aug_cols: columns carrying |v|^2 (a power of two <= 32 that fits the slab padding)
-    uint64_t n_sq8a = 0, sq8a_cap = 0;
-    float *sq8a_mins = nullptr, *sq8a_scales = nullptr;
-    uint32_t *sq8a_mm = nullptr, *sq8a_stats = nullptr;
-    uint32_t sq8a_a1 = 0, sq8a_a2sq = 0;   // max row L1 / sum of squares of the signed codes
-    float sq8a_eps2 = 0.0f;                 // bound of the max row sum of squared quantisation residuals (k_sq8_quantize stats[3])
-    bool sq8a_finite = false;
+    // overflow strikes of the certified int8 pass, per METRIC (plain-code L2 reads `sq8` but strikes i8c_strikes_l2)
     std::atomic<int> i8c_strikes_l2{0};
-    // the cosine form: SQ8 codes of the UNIT rows fl(v_d * rinv[row]) (pitch ld8), built lazily on the first cosine batch of
-    // 33..256 queries
-    int8_t* sq8c = nullptr;
-    uint64_t n_sq8c = 0, sq8c_cap = 0;
-    float *sq8c_mins = nullptr, *sq8c_scales = nullptr;
-    uint32_t *sq8c_mm = nullptr, *sq8c_stats = nullptr;
-    uint32_t sq8c_a1 = 0, sq8c_a2sq = 0;   // max row L1 / sum of squares of the signed codes
-    float sq8c_eps2 = 0.0f;                 // bound of the max row sum of squared quantisation residuals (k_sq8_quantize stats[3])
-    bool sq8c_finite = false;
     std::atomic<int> i8c_strikes_cos{0};
     // certified int8 coarse pass (FLAT-IP batches of 33..256 queries): -1 = off (env / strikes), else overflow strikes so far
     std::atomic<int> i8c_strikes{0};     // (searches under the SHARED lock bump it)
@@ -490,6 +487,10 @@ extern "C" int lynse_hip_flat_create(uint32_t dim, int device, lynse_hip_flat** 
     h->ld_bpm = round_up(dim, 256) / 2;
     h->ld8a = round_up(dim + 1, 128);
     while (h->aug_cols * 2 <= 32 && dim + h->aug_cols * 2 <= h->ld8a) h->aug_cols *= 2;
+    h->sq8.cols = h->sq8c.cols = h->sq7.cols = dim;
+    h->sq8.ld = h->sq8c.ld = h->sq7.ld = h->ld8;
+    h->sq8a.cols = dim + h->aug_cols;
+    h->sq8a.ld = h->ld8a;
     h->words = (dim + 63) / 64;
     h->device = device;
     hipDeviceProp_t prop;
@@ -529,10 +530,9 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     if (h->shadow_alias) h->rows16 = nullptr;
     for (void* p : {(void*)h->rows, (void*)h->rows_h, (void*)h->rows16, (void*)h->packed, (void*)h->vn2, (void*)h->vrinv, (void*)h->d_stats,
                     (void*)h->g_rows16, (void*)h->g_vn2, (void*)h->g_vrinv, (void*)h->g_ids32,
-                    (void*)h->bpm, (void*)h->sq8c, (void*)h->sq8c_mins, (void*)h->sq8c_scales, (void*)h->sq8c_mm, (void*)h->sq8c_stats, (void*)h->sq8a, (void*)h->sq8a_mins, (void*)h->sq8a_scales, (void*)h->sq8a_mm, (void*)h->sq8a_stats,
-                    (void*)h->sq8, (void*)h->sq8_mins, (void*)h->sq8_scales, (void*)h->sq8_sum, (void*)h->sq8_sum2, (void*)h->sq8_mm, (void*)h->sq8_stats, (void*)h->sq8_mm_prev,
-                    (void*)h->sq7, (void*)h->sq7_scales, (void*)h->sq7_stats})
+                    (void*)h->bpm, (void*)h->sq8_mm_prev})
         if (p) (void)hipFree(p);
+    for (CodeSet* s : {&h->sq8, &h->sq8a, &h->sq8c, &h->sq7}) s->release();
     for (auto& c : h->ctx)
         if (c.stream) (void)hipStreamDestroy(c.stream);
     delete h;
@@ -1790,39 +1790,99 @@ template <int DFLT>
 static int scan_w16_env() { static const int v = env_int("LYNSE_HIP_SCAN_W16", DFLT); return v; }
 #endif
 
-static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked = false);   // (defined with the other int8-pass rules)
-// lynse_hip_flat_coarse_scores: one emit-all stage over the whole (small) shard, then stop — the candidate buffer then holds the
-// coarse score of every (row, query) exactly as the scan kernels compute it
-static thread_local bool tl_coarse_dump = false;
+// Squared L2 has two int8 forms: unfiltered FLAT batches over whole 128-column slabs run on the PLAIN codes with the exact f32
+// row norms in a float epilogue (k_scan_h16<.., I8Q = 4>, every tiling: 1 B per element, no second code set, IP-sized margins);
+// everything else (ragged widths, masked scans, IVF) on the codes of the AUGMENTED rows through the IP kernels.  nqc = 0: "not a FLAT
+// batch" (IVF): the augmented form.  LYNSE_HIP_L2_PLAIN=0: always the augmented form.
+static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked) {
+    static const int on = env_int("LYNSE_HIP_L2_PLAIN", 1);
+    // (1M x 128, k = 100: 0.244 ms on the f16 shadow, 0.277 on the codes with the <4,2,2,4> tiling and 0.291 with the query-stationary
+    // L2 tiling (k_scan_qs<1,4,1,6,.., MET = 1>, built and measured in round 4: at k = 100 the first threshold lets 0.8 % of all
+    // (row, query) pairs through and the scan is bound by the emission of ~8000 keys per query, not by the tiling) — from 256
+    // dimensions on)
+    return on && !masked && nqc >= 1 && nqc <= QCHUNK && h->ld8 % 128 == 0 && h->dim >= 256;
+}
+// The form of the certified int8 pass a batch of nqc queries of `metric` takes — which code set it streams and how the prep kernel
+// builds the query image (I8cPrepArgs::l2n / aug / cosine).  nqc = 0: not a FLAT batch (the IVF list scan).
+enum I8cForm { I8C_IP, I8C_L2_PLAIN, I8C_L2_AUG, I8C_COS };
+static I8cForm i8c_form(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked) {
+    if (metric == M_L2) return l2_plain(h, nqc, masked) ? I8C_L2_PLAIN : I8C_L2_AUG;
+    return metric == M_COS ? I8C_COS : I8C_IP;
+}
+static const CodeSet& i8c_code_set(const lynse_hip_flat* h, I8cForm form) {
+    return form == I8C_L2_AUG ? h->sq8a : (form == I8C_COS ? h->sq8c : h->sq8);
+}
+// What the prep and scan stages read of the code set of a form; sq7: the non-negative 7-bit copy stands in for the plain codes (its
+// own scales and maxima; minima, pitch and width are those of `sq8`).
+struct I8cOperand {
+    const int8_t* codes;
+    uint32_t ld, cols, norm_cols;   // norm_cols: the trailing columns that carry |v|^2 (the augmented form)
+    const float *mins, *scales;
+    uint32_t a1, a2sq;
+    float eps2;
+    bool sq7;
+};
+static I8cOperand i8c_operand(const lynse_hip_flat* h, I8cForm form, bool sq7) {
+    const CodeSet& s = i8c_code_set(h, form);
+    I8cOperand v{s.codes, s.ld, s.cols, s.cols - h->dim, s.mins, s.scales, s.a1, s.a2sq, s.eps2, sq7};
+    if (sq7) { v.codes = h->sq7.codes; v.scales = h->sq7.scales; v.a1 = h->sq7.a1; v.a2sq = h->sq7.a2sq; v.eps2 = h->sq7.eps2; }
+    return v;
+}
+static void fill_i8c_prep(I8cPrepArgs& p, const I8cOperand& v, I8cForm form) {
+    p.mins = v.mins; p.scales = v.scales; p.a1 = v.a1;
+    if (i8c_cs_on()) { p.a2sq = v.a2sq; p.eps2 = v.eps2; }   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
+    p.cosine = form == I8C_COS ? 1 : 0; p.aug = (int)v.norm_cols; p.l2n = form == I8C_L2_PLAIN ? 1 : 0; p.sq7 = v.sq7 ? 1 : 0;
+}
+
 static int fused_sample_env() { return env_int("LYNSE_HIP_FUSED_SAMPLE", 0); }   // (read per call: tests flip it)
 static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked);
 static bool sq7_ready(const lynse_hip_flat* h);
-// flat_assign_top1_device: the lane-max scan of the k-means assignment over EVERY tile of the (small) centroid store, then stop —
-// k_assign_pick reads the keys (kernels.h)
-static thread_local bool tl_assign = false;
+
+// What run_chunk does with the chunk.  CHUNK_ASSIGN (flat_assign_top1_device): the lane-max scan of the k-means assignment over EVERY
+// tile of the (small) centroid store, then stop — k_assign_pick reads the keys (kernels.h).  CHUNK_COARSE_DUMP
+// (lynse_hip_flat_coarse_scores): one emit-all stage over the whole (small) shard, then stop — the candidate buffer then holds the
+// coarse score of every (row, query) exactly as the scan kernels compute it.
+enum ChunkMode { CHUNK_SEARCH, CHUNK_ASSIGN, CHUNK_COARSE_DUMP };
+struct ChunkReq {
+    uint32_t nq = 0, k = 0, out_k = 0;
+    int metric = 0, level = 0;           // level selects the stage plan (make_plan)
+    const uint32_t* mask = nullptr;      // row bitmask of a subset filter
+    const uint32_t* row_ids = nullptr;   // the scanned rows are a gathered copy: their ids in the shard
+    // the float queries of the chunk when they already live in device memory that stays valid for the whole search (no staging copy into
+    // the workspace); nullptr = w.Qf
+    const float* qsrc = nullptr;
+    // the coarse pass streams the SQ8 codes (1 B / element) against the symmetric int8 query image with a certified error bound
+    // (k_i8c_prep_queries) instead of the f16 shadow — FLAT-IP batches of 33..256 queries
+    bool i8c = false;
+    bool allow_sts = true;    // the self-tightening single-launch scan may answer this chunk (an overflow of it is retried on the staged plan of the same coarse pass, without a strike)
+    bool allow_sq7 = false;   // the chunk may scan the non-negative 7-bit copy of the codes (the blocking FLAT search and the certificate diagnostics; an overflow is re-answered on the SQ8 codes, without a strike against the int8 pass)
+    struct Out {
+        // where k_final writes rows, distances (stride out_k) and a second copy of the counts — the caller's device arrays or the pinned
+        // staging buffer; nullptr = the workspace (copied out by the caller)
+        uint64_t* rows = nullptr;
+        float* dists = nullptr;
+        uint32_t* counts2 = nullptr;
+        uint32_t* any_ovf = nullptr;   // device status word k_final ORs the overflow flags into (searches in flight), or nullptr
+        bool hdr_direct = false;       // k_final writes counts + overflow flags straight into the pinned header of the context (no copy kernel behind the search)
+    } out;
+    ChunkMode mode = CHUNK_SEARCH;
+};
+struct ChunkResult { bool sampled = false, used_sts = false, used_sq7 = false; };   // the plan began with a sample stage / ran the self-tightening scan / read the SQ7 copy
+// the events of a profiled search: events taken from the context's pool so far, and (first event, rows scanned) per scan launch
+struct ScanProf { size_t ev_used = 0; std::vector<std::pair<size_t, uint64_t>> scan_events; };
 
 // One chunk (<= QCHUNK queries) whose inputs are already in the workspace (Qf for float metrics,
-// QW for binary).  Results land in ws.out_*.  `level` selects the stage plan (make_plan).
-static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k, int metric, int level, hipStream_t st,
-                     size_t* ev_used, std::vector<std::pair<size_t, uint64_t>>* scan_events, bool* sampled_plan,
-                     const uint32_t* mask = nullptr, const uint32_t* row_ids = nullptr, bool i8c = false,
-                     uint64_t* r_dst = nullptr, float* d_dst = nullptr, uint32_t* c2_dst = nullptr, uint32_t* any_ovf = nullptr,
-                     const float* qsrc = nullptr, bool hdr_direct = false, bool allow_sts = true, bool* used_sts = nullptr,
-                     bool allow_sq7 = false, bool* used_sq7 = nullptr) {
-    // allow_sq7 / used_sq7: the chunk may scan the non-negative 7-bit copy of the codes / did (the blocking FLAT search and the certificate
-    // diagnostics pass true; an overflow is re-answered on the SQ8 codes, without a strike against the int8 pass)
-    // allow_sts / used_sts: the self-tightening single-launch scan may answer this chunk / did (an overflow of it is retried on the
-    // staged plan of the same coarse pass, without a strike)
-    // qsrc: the float queries of the chunk when they already live in device memory that stays valid for the whole search (no
-    // staging copy into the workspace); nullptr = w.Qf.  hdr_direct: k_final writes counts + overflow flags straight into the
-    // pinned header of the context (no copy kernel behind the search)
-    // any_ovf: device status word k_final ORs the overflow flags into (searches in flight), or nullptr
-    // r_dst / d_dst / c2_dst: where k_final writes rows, distances (stride out_k) and a second copy of the counts — the
-    // caller's device arrays or the pinned staging buffer; nullptr = the workspace (copied out by the caller)
-    // i8c: the coarse pass streams the SQ8 codes (1 B / element) against the symmetric int8 query image with a certified
-    // error bound (k_i8c_prep_queries) instead of the f16 shadow — FLAT-IP batches of 33..256 queries
+// QW for binary).  Results land in ws.out_* or where rq.out says.
+static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, ScanProf* prof, ChunkResult* res = nullptr) {
+    ChunkResult unread;
+    if (!res) res = &unread;
+    const uint32_t nq = rq.nq, k = rq.k, out_k = rq.out_k;
+    const int metric = rq.metric, level = rq.level;
+    const uint32_t *mask = rq.mask, *row_ids = rq.row_ids;
+    const bool assign = rq.mode == CHUNK_ASSIGN, coarse_dump = rq.mode == CHUNK_COARSE_DUMP;
+    bool i8c = rq.i8c;
     Workspace& w = cur(h).ws;
-    const float* Qf = qsrc ? qsrc : w.Qf;
+    const float* Qf = rq.qsrc ? rq.qsrc : w.Qf;
     const bool binary = metric >= M_HAMMING;
     const bool asc = metric_ascending(metric);
     const bool h16 = scan_variant() == 3;
@@ -1833,11 +1893,20 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     // squared L2 on the certified int8 pass: an inner product of augmented vectors in the negated score space (kernels.h,
     // I8cPrepArgs::aug): scan, thresholds and selects run as a best-first IP search, exact scores are -|q - v|^2
     // squared L2 on the plain codes + exact row norms (l2_plain): the <4,2,2,4> L2 tiling with int8 operands and the float epilogue
-    const bool l2n = i8c && !bin_mfma && metric == M_L2 && !row_ids && l2_plain(h, nq, mask != nullptr);
-    const bool aug = i8c && !bin_mfma && metric == M_L2 && !l2n;
-    const bool cosq = i8c && !bin_mfma && metric == M_COS;   // cosine distance: unit vectors, negated score space (I8cPrepArgs::cosine)
+    const bool i8q = i8c && !bin_mfma;   // the chunk streams a code set
+    // (i8c_eligible never admits the gathered rows of a subset filter: the code sets cover the shard, not the copy)
+    if (i8q && row_ids) return set_error(LYNSE_ERR_INTERNAL, "the int8 pass does not scan gathered rows");
+    const I8cForm form = i8q ? i8c_form(h, metric, nq, mask != nullptr) : I8C_IP;
+    const bool l2n = i8q && form == I8C_L2_PLAIN;
+    const bool aug = i8q && form == I8C_L2_AUG;
+    const bool cosq = i8q && form == I8C_COS;   // cosine distance: unit vectors, negated score space (I8cPrepArgs::cosine)
+    // SQ7: same kernels, same plan — only the code rows every stage reads and the prep outputs (B_q, E) differ
+    // (sq7_wanted is the whole predicate of the shape: IP, 129..256 queries — so no small / mid tiling —, no self-tightening or fused-sample plan)
+    const bool sq7 = rq.allow_sq7 && i8q && !mask && sq7_wanted(h, metric, nq, false) && sq7_ready(h);
+    res->used_sq7 = sq7;
+    const I8cOperand opd = i8q ? i8c_operand(h, form, sq7) : I8cOperand{};
     const int key_metric = (bin_mfma || aug || cosq) ? (int)M_IP : metric;   // the order of the candidate keys
-    const uint32_t nslab = bin_mfma ? h->ld_bpm / 128 : i8c ? ((aug ? h->dim + h->aug_cols : h->dim) + 127) / 128 : glds ? (h->dim + GL_BK - 1) / GL_BK : (h->dim + SCAN_BK - 1) / SCAN_BK;  // h16: HK == SCAN_BK == 64
+    const uint32_t nslab = bin_mfma ? h->ld_bpm / 128 : i8c ? (opd.cols + 127) / 128 : glds ? (h->dim + GL_BK - 1) / GL_BK : (h->dim + SCAN_BK - 1) / SCAN_BK;  // h16: HK == SCAN_BK == 64
     const bool small = nq <= SCAN_BQ_SMALL;
     // mid-size batches on the int8 codes: 33..64 queries -> the 128 x 64 tiling, 65..128 -> the 256 x 128 tiling (LYNSE_HIP_MID_TILINGS=0: off)
     const int mid_env = env_int("LYNSE_HIP_MID_TILINGS", 1);   // (read per call: tests flip it)
@@ -1849,7 +1918,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                         !small && !row_ids && h16 && !aug && qs_width_ok(h->ld8, (h->dim + 127) / 128, mask != nullptr) && !(l2n && (h->dim + 127) / 128 == 8) && nq <= 256 &&   // (plain-L2: not on the 32-row tiles of 1024 columns)
                         (h->ld8 == 768 || nq > 64) &&   // (narrower rows: the 128 x 64 tiling keeps 33..64 queries — 6M x 256, 40 queries: 0.34 ms against 0.37)
                         (!mask || (!l2n && qs_variant() != 2 && qs_masked_on()));
-    const bool mid_ok = mid_env && !qs_mid && i8c && !bin_mfma && !small && !row_ids && h16 && (!mask || (aug ? h->ld8a : h->ld8) % 128 == 0);
+    const bool mid_ok = mid_env && !qs_mid && i8c && !bin_mfma && !small && !row_ids && h16 && (!mask || opd.ld % 128 == 0);
     const bool mid64 = mid_ok && nq <= 64, mid128 = mid_ok && !mid64 && nq <= 128;
     const bool narrow = small || mid64;   // 128-row tiles
     const uint32_t qpad = small ? SCAN_BQ_SMALL : mid64 ? 64u : mid128 ? 128u : round_up(nq, SCAN_BQ_LARGE);  // > 256 queries: a widened handle, qpad / 256 chunks per launch
@@ -1865,15 +1934,10 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
     LY_TRY(ensure_lds<k_select_final<SEL_NT>>(SEL_LDS_MAX));
 
-    const uint32_t sts_ld8 = cosq ? h->ld8 : h->ld8;
-    const bool sts = allow_sts && sts_env_on() && level == 0 && i8c && !bin_mfma && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids && h16 &&
-                     k >= 1 && k <= 32 && qs_variant() >= 1 && qs_variant() <= 3 && sts_ld8 == 768 && nslab == 6 && qpad == 256 && h->n >= 65536 &&
+    const bool sts = rq.allow_sts && sts_env_on() && level == 0 && i8c && !bin_mfma && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids && h16 &&
+                     k >= 1 && k <= 32 && qs_variant() >= 1 && qs_variant() <= 3 && opd.ld == 768 && nslab == 6 && qpad == 256 && h->n >= 65536 &&
                      h->n < 0xffffff00ull && (metric == M_IP || cosq);
-    if (used_sts) *used_sts = sts;
-    // SQ7: same kernels, same plan — only the code rows every stage reads and the prep outputs (B_q, E) differ
-    // (sq7_wanted is the whole predicate of the shape: IP, 129..256 queries — so no small / mid tiling —, no self-tightening or fused-sample plan)
-    const bool sq7 = allow_sq7 && i8c && !bin_mfma && !mask && !row_ids && sq7_wanted(h, metric, nq, false) && sq7_ready(h);
-    if (used_sq7) *used_sq7 = sq7;
+    res->used_sts = sts;
     if (bin_mfma) {
         // (the prep kernels write every byte of the image: the lines of their queries, pad columns included, and — blocks nq .. qpad - 1 of the
         // grid — zero lines for the pad queries of the tile; up to round 5 a hipMemsetAsync of the image ran in front: a launch of its own)
@@ -1890,18 +1954,12 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         LY_HIP(hipStreamSynchronize(st));  // thr0 is a stack/heap temporary
     } else if (i8c) {
         I8cPrepArgs p{};
-        p.Q = Qf; p.D = h->dim; p.qpad = qpad; p.nslab = nslab; p.nq = nq; p.mins = aug ? h->sq8a_mins : (cosq ? h->sq8c_mins : h->sq8_mins);
-        p.scales = aug ? h->sq8a_scales : (cosq ? h->sq8c_scales : h->sq8_scales);
-        p.a1 = aug ? h->sq8a_a1 : (cosq ? h->sq8c_a1 : h->sq8_a1); p.vmax = h->vmax;
-        if (i8c_cs_on()) { p.a2sq = aug ? h->sq8a_a2sq : (cosq ? h->sq8c_a2sq : h->sq8_a2sq); p.eps2 = aug ? h->sq8a_eps2 : (cosq ? h->sq8c_eps2 : h->sq8_eps2); } p.cosine = cosq ? 1 : 0; p.img = reinterpret_cast<int8_t*>(w.Q16); p.aug = aug ? (int)h->aug_cols : 0; p.l2n = l2n ? 1 : 0;
+        p.Q = Qf; p.D = h->dim; p.qpad = qpad; p.nslab = nslab; p.nq = nq; p.vmax = h->vmax; p.img = reinterpret_cast<int8_t*>(w.Q16);
+        fill_i8c_prep(p, opd, form);
         p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
-        if (sq7) {
-            p.sq7 = 1; p.scales = h->sq7_scales; p.a1 = h->sq7_a1;
-            if (i8c_cs_on()) { p.a2sq = h->sq7_a2sq; p.eps2 = h->sq7_eps2; }
-        }
         if (sts) {   // seed the partition maxima of the self-tightening scan from a few sample rows (valid thresholds from the first tile on)
-            p.codes = cosq ? h->sq8c : h->sq8; p.ld8 = sts_ld8; p.n_rows = (uint32_t)h->n; p.tile_rows = 64; p.dyn_ks = k;
+            p.codes = opd.codes; p.ld8 = opd.ld; p.n_rows = (uint32_t)h->n; p.tile_rows = 64; p.dyn_ks = k;
             p.seed_rows = std::min<uint32_t>(1024u, 32u * k);
             p.dyn_thr = w.dyn; p.dyn_marg = w.dyn + w.qcap; p.dyn_slot = w.dyn + 2 * (size_t)w.qcap;
         }
@@ -1936,18 +1994,18 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     // sample tile; up to k = 128 the sample as a whole supplies >= 8 k keys — a clustered shard may then overflow the first
     // stage and fall back to the contiguous plan)
     const bool can_threshold_only = h16 && !binary && !filt && !no_lane_max_env() && k <= 128;
-    Stage assign_stage{0u, (uint32_t)h->n};   // (tl_assign) every 256-row tile of the store as a "sample" tile: lane-max keys, no threshold
+    Stage assign_stage{0u, (uint32_t)h->n};   // (CHUNK_ASSIGN) every 256-row tile of the store as a "sample" tile: lane-max keys, no threshold
     assign_stage.sample_tiles = (uint32_t)((h->n + 255) / 256);
     assign_stage.sample_stride = 256;
-    const std::vector<Stage> plan = tl_assign ? std::vector<Stage>{assign_stage}
-                                    : (sts || tl_coarse_dump) ? std::vector<Stage>{Stage{0u, (uint32_t)h->n}}
+    const std::vector<Stage> plan = assign ? std::vector<Stage>{assign_stage}
+                                    : (sts || coarse_dump) ? std::vector<Stage>{Stage{0u, (uint32_t)h->n}}
                                         : make_plan(h, k, (level == 0 && (!plan_tile || no_sample)) ? 1 : level, plan_tile, can_threshold_only,
                                                     // large k on the float tilings: the epilogue's cost is the emissions (one sample threshold over 1M x 128,
                                                     // k = 100, admits 1400 rows per query: 87 of the stage's 163 us) — a second threshold stage a quarter of the
                                                     // way in halves them (same box, alternating: 0.241 -> 0.233 ms per batch)
                                                     (h16 && !i8c && !binary && k >= 64) ? 4u : 0u);
     const Stage sample = (!plan.empty() && plan[0].sample_tiles) ? plan[0] : Stage{0, 0};
-    *sampled_plan = sample.sample_tiles != 0;
+    res->sampled = sample.sample_tiles != 0;
     // sampled plan: the sample stage only has to produce a threshold -> one key per lane (its best row) instead of every
     // score, as long as that leaves comfortably more than k keys per query (2 WR keys per tile and query)
     const uint32_t sample_keys_per_tile = (small || mid64 || mid128 || waves16 != 0) ? 16u : 8u;  // 2 WR lanes per query and tile x their best 2 rows (WR = 4: 16, <4,2,2,4>: 8)
@@ -1980,8 +2038,8 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         uint32_t qs_sample_keys = 0;   // != 0: the sample stage ran on the query-stationary tiling and left this many keys per query
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (tl_prof) {
-            LY_TRY(get_event(h, (*ev_used)++, &e0));
-            LY_TRY(get_event(h, (*ev_used)++, &e1));
+            LY_TRY(get_event(h, prof->ev_used++, &e0));
+            LY_TRY(get_event(h, prof->ev_used++, &e1));
             LY_HIP(hipEventRecord(e0, st));
         }
         uint32_t st_nseg = 0, st_seg = 0;  // segmented emission of this stage (k_select gathers)
@@ -2026,8 +2084,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             uint32_t tile_rows = (glds && !small && big_rows == 256) ? 256u : (uint32_t)SCAN_BR;
             if (h16) tile_rows = narrow ? 128u : 256u;
             a.V16 = h->rows16; a.ld16 = h->ld16;
-            if (i8c) { a.V16 = reinterpret_cast<const _Float16*>(bin_mfma ? (const int8_t*)h->bpm : (aug ? h->sq8a : (cosq ? h->sq8c : h->sq8))); a.ld16 = bin_mfma ? h->ld_bpm : (aug ? h->ld8a : h->ld8); }
-            if (sq7) a.V16 = reinterpret_cast<const _Float16*>(h->sq7);
+            if (i8c) { a.V16 = reinterpret_cast<const _Float16*>(bin_mfma ? (const int8_t*)h->bpm : opd.codes); a.ld16 = bin_mfma ? h->ld_bpm : opd.ld; }
             if (glds && !small && big_rows == 192 && metric == M_IP) tile_rows = 192u;
             a.qpad = qpad; a.nq = nq; a.nslab = nslab; a.ntiles = (s.r1 - s.r0 + tile_rows - 1) / tile_rows;
             if (s.sample_tiles) a.ntiles = s.sample_tiles;
@@ -2143,7 +2200,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
                     // at every threshold tightness measured: 1M x 128 and 4M x 128 / 768, k = 10 and 100)
                     a.dense = (!a.emit_all && waves16 == 0 && metric != M_IP && !filt && seen_before && (dense_env() >= 0 ? dense_env() != 0 : true)) ? 1 : 0;
                     if (!a.emit_all) seg_geometry(grid, a.dense ? 4 : ((waves16 == 3 || waves16 == 2) ? 4 : 2), &a.nseg, &a.seg);
-                    if (qchunks > 1 && !(plan.size() == 1 && (a.emit_all == 1 || (tl_assign && a.emit_all == 2))))
+                    if (qchunks > 1 && !(plan.size() == 1 && (a.emit_all == 1 || (assign && a.emit_all == 2))))
                         return set_error(LYNSE_ERR_INTERNAL, "the widened pipeline runs single-stage emit-all plans only");
 #ifdef LYNSE_EXPERIMENTS
                     if (waves16 == 2) { LY_TRY((launch_scan_h16<with(F16_IP_256, &H16Cfg::nsv, 2)>(a, metric, grid, st))); }
@@ -2189,14 +2246,14 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
             st_nseg = a.seg ? a.nseg : 0; st_seg = a.seg;
             plan_used_segments = plan_used_segments || a.seg != 0;
         }
-        if (tl_coarse_dump) return LYNSE_OK;   // (diagnostics: the emit-all stage has written one key per row and query; nothing else runs)
-        if (tl_assign) {
+        if (coarse_dump) return LYNSE_OK;   // (diagnostics: the emit-all stage has written one key per row and query; nothing else runs)
+        if (assign) {
             if (a_emit_all_last != 2) return set_error(LYNSE_ERR_INTERNAL, "the assignment scan must run in lane-max mode");
             return LYNSE_OK;   // (k_assign_pick reads the lane-max keys)
         }
         if (tl_prof) {
             LY_HIP(hipEventRecord(e1, st));
-            scan_events->push_back({*ev_used - 2, s.sample_tiles ? (uint64_t)s.sample_tiles * plan_tile
+            prof->scan_events.push_back({prof->ev_used - 2, s.sample_tiles ? (uint64_t)s.sample_tiles * plan_tile
                                                                   : (uint64_t)(s.r1 - s.r0) + (fs_stage ? (uint64_t)sample.sample_tiles * plan_tile : 0ull)});
         }
         SelectArgs sa{};
@@ -2246,11 +2303,11 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     fa.exact = binary ? 1 : 0; fa.Qf = Qf; fa.V = score_rows(h); fa.ld = score_ld(h); fa.D = h->dim;
     fa.row_stride = h->row_stride; fa.row_offset = h->row_offset;
     fa.nan_rows = (!binary && !mask && !row_ids && h->n <= 0xffffffffull) ? (uint32_t)h->n : 0u;   // (FinalArgs::nan_rows: the all-NaN query of an unfiltered FLAT search)
-    fa.out_rows = r_dst ? r_dst : w.out_rows; fa.out_dists = d_dst ? d_dst : w.out_dists; fa.out_counts = w.out_counts;
-    fa.out_counts2 = c2_dst;
+    fa.out_rows = rq.out.rows ? rq.out.rows : w.out_rows; fa.out_dists = rq.out.dists ? rq.out.dists : w.out_dists; fa.out_counts = w.out_counts;
+    fa.out_counts2 = rq.out.counts2;
     fa.pool_total = tl_prof ? w.pool_total : nullptr;
-    fa.overflow = w.overflow; fa.any_overflow = any_ovf;
-    if (hdr_direct) { fa.h_hdr = w.h_hdr; fa.hdr_q = w.qcap; }
+    fa.overflow = w.overflow; fa.any_overflow = rq.out.any_ovf;
+    if (rq.out.hdr_direct) { fa.h_hdr = w.h_hdr; fa.hdr_q = w.qcap; }
     if (fused_tail) {
         TailArgs ta{sa_last, fa};
         ta.s.hand_exact = env_int("LYNSE_HIP_HAND_EXACT", 1);   // (0: the final rescoring always reads its rows, A/B)
@@ -2275,7 +2332,7 @@ static int run_chunk(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
 // kmeans::assign_metric (kmeans.rs:237-264) for the device k-means: the nearest centroid of every data row, WITHOUT the general
 // top-1 search.  `h` is the centroid store (a widened handle: h->qchunk data rows per pass, <= cap centroids), d_q the data rows in
 // device memory.  Per pass of <= qchunk data rows: query image + certified margin (k_prep_queries), ONE lane-max scan over all
-// centroid tiles (run_chunk under tl_assign), k_assign_pick.  d_ids[i] = the centroid of row i, or 0xffffffff for the rows whose two
+// centroid tiles (run_chunk in CHUNK_ASSIGN mode), k_assign_pick.  d_ids[i] = the centroid of row i, or 0xffffffff for the rows whose two
 // best coarse centroids lie within the certified margin: their indices come back in d_redo[0 .. *d_redo_count) and the caller answers
 // them with the exact top-1 search (lynse_hip_flat_search_f32_device), whose first-strictly-smaller rule they need.
 // Returns LYNSE_ERR_UNSUPPORTED when the shape is not the one this path is built for (the caller falls back to the search).
@@ -2298,17 +2355,16 @@ static int flat_assign_top1_device(lynse_hip_flat* h, const float* d_q, uint64_t
     const uint32_t nkeys = ntiles * ((metric == M_IP) ? 16u : 8u);   // 2 WR lanes per tile and data row x their best two (<2,4,4,2> / <4,2,2,4>)
     if (nkeys > w.cap) return set_error(LYNSE_ERR_UNSUPPORTED, "lane-max keys exceed the candidate slots");
     LY_HIP(hipMemsetAsync(d_redo_count, 0, 4, st));
-    size_t ev_used = 0;
-    std::vector<std::pair<size_t, uint64_t>> scan_events;
-    struct Flag { Flag() { tl_assign = true; } ~Flag() { tl_assign = false; } } flag;
+    ScanProf sprof;
+    ChunkReq rq;
+    rq.k = rq.out_k = 1; rq.metric = metric; rq.allow_sts = false; rq.mode = CHUNK_ASSIGN;
     const bool prof_prev = tl_prof;
     tl_prof = false;
     int rc = LYNSE_OK;
     for (uint64_t q0 = 0; q0 < nq && rc == LYNSE_OK; q0 += w.qcap) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(w.qcap, nq - q0);
-        bool sampled = false;
-        rc = run_chunk(h, nqc, 1, 1, metric, 0, st, &ev_used, &scan_events, &sampled, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr,
-                       d_q + q0 * h->dim, false, false, nullptr);
+        rq.nq = nqc; rq.qsrc = d_q + q0 * h->dim;
+        rc = run_chunk(h, rq, st, &sprof);
         if (rc != LYNSE_OK) break;
         int ip_form = h->ip_form;
         if (ip_form == LYNSE_IPFORM_AUTO) ip_form = h->n < 4096 ? LYNSE_IPFORM_SINGLE : LYNSE_IPFORM_BATCH8;   // (run_chunk's rule)
@@ -2336,8 +2392,7 @@ static bool small_path_ok(const lynse_hip_flat* h, uint64_t nq, uint32_t kk, int
 struct SmallRows { const float* V; uint32_t ld; uint64_t n; int ip_form; uint64_t row_stride, row_offset; };
 struct SmallIvf { const uint64_t* probes; uint32_t nprobe, nlist; const uint64_t* list_off; const uint32_t* orig; int flag_empty; };
 
-static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k, int metric, hipStream_t st, size_t* ev_used,
-                     std::vector<std::pair<size_t, uint64_t>>* scan_events, uint64_t* r_dst, float* d_dst, uint32_t* c_dst, uint32_t* o_dst,
+static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k, int metric, hipStream_t st, ScanProf* prof, uint64_t* r_dst, float* d_dst, uint32_t* c_dst, uint32_t* o_dst,
                      const float* d_q, const SmallRows* rows = nullptr, const SmallIvf* ivf = nullptr) {
     // r_dst / d_dst / c_dst / o_dst: where the last workgroup writes rows, distances, counts and overflow flags — the
     // caller's device buffers, or pinned host memory (device-visible): no copy kernels behind the search
@@ -2366,10 +2421,10 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     const size_t lds = (size_t)((h->dim + 3) / 4 * 4) * 4 + (size_t)SMALL_NT * 8 + (size_t)pow2_at_least(std::min<uint32_t>(k, grid) * k) * 8 + 64;  // the query, the wave lists (later the heads of the merge), the merge's candidate keys
     LY_TRY(ensure_lds<k_small_search>(160 * 1024 - 1024));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = tl_prof && ev_used && scan_events;
+    const bool timed = tl_prof && prof;
     if (timed) {
-        LY_TRY(get_event(h, (*ev_used)++, &e0));
-        LY_TRY(get_event(h, (*ev_used)++, &e1));
+        LY_TRY(get_event(h, prof->ev_used++, &e0));
+        LY_TRY(get_event(h, prof->ev_used++, &e1));
         LY_HIP(hipEventRecord(e0, st));
     }
     static const bool small_dbg = env_on("LYNSE_HIP_SMALL_DBG", false);
@@ -2397,7 +2452,7 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
     }
     if (timed) {
         LY_HIP(hipEventRecord(e1, st));
-        scan_events->push_back({*ev_used - 2, (uint64_t)h->n * nq});
+        prof->scan_events.push_back({prof->ev_used - 2, (uint64_t)h->n * nq});
         std::lock_guard<std::mutex> plk(h->prof_mu);
         h->prof.last_plan = 32u | (1u << 8);  // bit 5: fused single-launch search
     }
@@ -2438,62 +2493,95 @@ static int sq8_merge_new_rows(lynse_hip_flat* h, uint32_t* mm, uint32_t D, uint6
     return LYNSE_OK;
 }
 
-static int ensure_sq8_locked(lynse_hip_flat* h) {
-    if (h->n_sq8 == h->n && h->sq8) return LYNSE_OK;
-    bool kept = h->sq8 != nullptr && h->sq8_mins != nullptr && h->sq8_cap >= h->n;   // the existing codes survive (no reallocation)
-    if (h->sq8_cap < h->n) {
-        for (void* p : {(void*)h->sq8, (void*)h->sq8_sum, (void*)h->sq8_sum2})
-            if (p) (void)hipFree(p);
-        h->sq8 = nullptr; h->sq8_sum = nullptr; h->sq8_sum2 = nullptr;
+// The tail every code-set builder shares: rows r0 .. n of `s` are coded (k_sq8_quantize, minima `mins`, the set's own scales), the four
+// stats words come back into a1 / a2sq / eps2 / finite and the set covers the shard.  Synchronises the stream.
+static int quantize_rows_locked(lynse_hip_flat* h, CodeSet& s, uint64_t r0, const float* mins, const float* extra_col, uint32_t n_extra,
+                                const float* row_scale, int sq7) {
+    hipStream_t st = cur(h).stream;
+    const uint64_t nn = h->n - r0;
+    const uint32_t qgrid = (uint32_t)std::min<uint64_t>((nn + 3) / 4, (uint64_t)h->num_cu * 16);
+    int8_t* out = s.codes + r0 * s.ld;
+    int *sum = s.sum ? s.sum + r0 : nullptr, *sum2 = s.sum2 ? s.sum2 + r0 : nullptr;
+    if (extra_col) extra_col += r0;
+    if (row_scale) row_scale += r0;
+    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3(qgrid), dim3(256), 0, st, (const _Float16*)h->rows_h + r0 * h->ld16, h->ld16, h->dim, nn,
+                                      mins, s.scales, out, s.ld, sum, sum2, s.stats, extra_col, n_extra, row_scale, sq7);
+    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3(qgrid), dim3(256), 0, st, h->rows + r0 * h->ld, h->ld, h->dim, nn,
+                            mins, s.scales, out, s.ld, sum, sum2, s.stats, extra_col, n_extra, row_scale, sq7);
+    LY_HIP(hipGetLastError());
+    uint32_t qst[4] = {0, 0, 0, 0};
+    LY_HIP(hipMemcpyAsync(qst, s.stats, 16, hipMemcpyDeviceToHost, st));
+    LY_HIP(hipStreamSynchronize(st));
+    s.a1 = qst[0];
+    s.a2sq = qst[2];
+    memcpy(&s.eps2, &qst[3], 4);
+    s.finite = qst[1] == 0;
+    s.n = h->n;
+    return LYNSE_OK;
+}
+
+// What tells the three fitted code sets apart (ensure_codes_locked).
+struct CodeForm {
+    bool norm_cols;     // columns dim .. cols - 1 of the coded row hold its squared norm (vn2): the augmented rows of the L2 form
+    bool unit_rows;     // the coded row is v * vrinv[row]: the cosine form
+    bool incremental;   // rows appended inside the fitted ranges are coded alone (sq8_merge_new_rows); otherwise every append refits
+    bool keeps_sums;    // per-row sums of the codes (FLAT-*-SQ8)
+    bool bumps_fit;     // a new fit counts in sq8_fit (the SQ7 copy follows it)
+};
+static constexpr CodeForm CODES_PLAIN{false, false, true, true, true};
+static constexpr CodeForm CODES_AUG{true, false, false, false, false};
+static constexpr CodeForm CODES_UNIT{false, true, true, false, false};
+
+// Brings a fitted code set up to date with the rows: (re)allocation, per-column min / max over all rows — or merged from the appended
+// rows alone —, minima + scales, codes.
+static int ensure_codes_locked(lynse_hip_flat* h, CodeSet& s, const CodeForm& f) {
+    if (s.ready(h->n)) return LYNSE_OK;
+    hipStream_t st = cur(h).stream;
+    const uint32_t D = h->dim, DC = s.cols;
+    const float* row_scale = f.unit_rows ? h->vrinv : nullptr;
+    const bool kept = f.incremental && s.codes != nullptr && s.mins != nullptr && s.cap >= h->n;   // the existing codes survive (no reallocation)
+    if (s.cap < h->n) {
+        s.release();
         const uint64_t cap = std::max<uint64_t>(h->capacity, h->n);
-        LY_HIP(hipMalloc(&h->sq8, (size_t)cap * h->ld8 + 256));
-        LY_HIP(hipMalloc(&h->sq8_sum, ((size_t)cap + 256) * 4));
-        LY_HIP(hipMalloc(&h->sq8_sum2, ((size_t)cap + 256) * 4));
-        LY_HIP(hipMemsetAsync(h->sq8_sum, 0, ((size_t)cap + 256) * 4, cur(h).stream));
-        LY_HIP(hipMemsetAsync(h->sq8_sum2, 0, ((size_t)cap + 256) * 4, cur(h).stream));
-        h->sq8_cap = cap;
+        LY_HIP(hipMalloc(&s.codes, (size_t)cap * s.ld + 256));
+        if (f.keeps_sums) {
+            LY_HIP(hipMalloc(&s.sum, ((size_t)cap + 256) * 4));
+            LY_HIP(hipMalloc(&s.sum2, ((size_t)cap + 256) * 4));
+            LY_HIP(hipMemsetAsync(s.sum, 0, ((size_t)cap + 256) * 4, st));
+            LY_HIP(hipMemsetAsync(s.sum2, 0, ((size_t)cap + 256) * 4, st));
+        }
+        s.cap = cap;
     }
-    if (!h->sq8_mins) {
-        LY_HIP(hipMalloc(&h->sq8_mins, (size_t)h->dim * 4));
-        LY_HIP(hipMalloc(&h->sq8_scales, (size_t)h->dim * 4));
-        LY_HIP(hipMalloc(&h->sq8_mm, (size_t)h->dim * 8));
-        LY_HIP(hipMalloc(&h->sq8_stats, 16));   // (four words: k_sq8_quantize)
+    if (!s.mins) {
+        LY_HIP(hipMalloc(&s.mins, (size_t)DC * 4));
+        LY_HIP(hipMalloc(&s.scales, (size_t)DC * 4));
+        LY_HIP(hipMalloc(&s.mm, (size_t)DC * 8));
+        LY_HIP(hipMalloc(&s.stats, 16));   // (four words: k_sq8_quantize)
     }
     uint64_t r0 = 0;
     bool mm_done = false;
-    if (kept) LY_TRY(sq8_merge_new_rows(h, h->sq8_mm, h->dim, h->n_sq8, nullptr, &r0, &mm_done));
-    const uint32_t gx = (h->dim + 255) / 256;
+    if (kept) LY_TRY(sq8_merge_new_rows(h, s.mm, DC, s.n, row_scale, &r0, &mm_done));   // (appended rows inside the fitted ranges: only they are coded)
     std::vector<uint32_t> init;
     if (!mm_done) {
-        init.resize((size_t)h->dim * 2);
-        for (uint32_t d = 0; d < h->dim; ++d) { init[d] = f32_to_ord(INFINITY); init[h->dim + d] = f32_to_ord(-INFINITY); }
-        LY_HIP(hipMemcpyAsync(h->sq8_mm, init.data(), init.size() * 4, hipMemcpyHostToDevice, cur(h).stream));
+        init.resize((size_t)DC * 2);
+        for (uint32_t d = 0; d < DC; ++d) { init[d] = f32_to_ord(INFINITY); init[DC + d] = f32_to_ord(-INFINITY); }
+        LY_HIP(hipMemcpyAsync(s.mm, init.data(), init.size() * 4, hipMemcpyHostToDevice, st));
+        const uint32_t gx = (D + 255) / 256;
         const uint32_t gy = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(h->n / 256, 1), (uint64_t)h->num_cu * 8);
-        if (is_f16(h)) hipLaunchKernelGGL(k_sq8_minmax<_Float16>, dim3(gx, gy), dim3(256), 0, cur(h).stream, (const _Float16*)h->rows_h, h->ld16, h->dim, h->n, h->sq8_mm, h->sq8_mm + h->dim);
-        else hipLaunchKernelGGL(k_sq8_minmax<float>, dim3(gx, gy), dim3(256), 0, cur(h).stream, h->rows, h->ld, h->dim, h->n, h->sq8_mm, h->sq8_mm + h->dim);
+        if (is_f16(h)) hipLaunchKernelGGL(k_sq8_minmax<_Float16>, dim3(gx, gy), dim3(256), 0, st, (const _Float16*)h->rows_h, h->ld16, D, h->n, s.mm, s.mm + DC, row_scale);
+        else hipLaunchKernelGGL(k_sq8_minmax<float>, dim3(gx, gy), dim3(256), 0, st, h->rows, h->ld, D, h->n, s.mm, s.mm + DC, row_scale);
+        if (f.norm_cols)
+            hipLaunchKernelGGL(k_vec_minmax, dim3((uint32_t)std::min<uint64_t>((h->n + 255) / 256, (uint64_t)h->num_cu * 8)), dim3(256), 0, st,
+                               h->vn2, h->n, s.mm + D, s.mm + DC + D, DC - D);
     }
     if (r0 == 0) {   // a new fit: every row is coded (again)
-        ++h->sq8_fit;
-        LY_HIP(hipMemsetAsync(h->sq8_stats, 0, 16, cur(h).stream));
-        hipLaunchKernelGGL(k_sq8_scales, dim3(gx), dim3(256), 0, cur(h).stream, h->sq8_mm, h->sq8_mm + h->dim, h->dim, h->sq8_mins, h->sq8_scales);
+        if (f.bumps_fit) ++h->sq8_fit;
+        LY_HIP(hipMemsetAsync(s.stats, 0, 16, st));
+        hipLaunchKernelGGL(k_sq8_scales, dim3((DC + 255) / 256), dim3(256), 0, st, s.mm, s.mm + DC, DC, s.mins, s.scales, 255.0f);
     }
-    const uint64_t nn = h->n - r0;
-    const uint32_t qgrid = (uint32_t)std::min<uint64_t>((nn + 3) / 4, (uint64_t)h->num_cu * 16);
-    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3(qgrid), dim3(256), 0, cur(h).stream,
-                       (const _Float16*)h->rows_h + r0 * h->ld16, h->ld16, h->dim, nn, h->sq8_mins, h->sq8_scales, h->sq8 + r0 * h->ld8, h->ld8, h->sq8_sum + r0, h->sq8_sum2 + r0, h->sq8_stats);
-    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3(qgrid), dim3(256), 0, cur(h).stream,
-                       h->rows + r0 * h->ld, h->ld, h->dim, nn, h->sq8_mins, h->sq8_scales, h->sq8 + r0 * h->ld8, h->ld8, h->sq8_sum + r0, h->sq8_sum2 + r0, h->sq8_stats);
-    LY_HIP(hipGetLastError());
-    uint32_t qst[4] = {0, 0, 0, 0};
-    LY_HIP(hipMemcpyAsync(qst, h->sq8_stats, 16, hipMemcpyDeviceToHost, cur(h).stream));
-    LY_HIP(hipStreamSynchronize(cur(h).stream));  // `init` is a temporary
-    h->sq8_a1 = qst[0];
-    h->sq8_a2sq = qst[2];
-    memcpy(&h->sq8_eps2, &qst[3], 4);
-    h->sq8_finite = qst[1] == 0;
-    h->n_sq8 = h->n;
-    return LYNSE_OK;
+    return quantize_rows_locked(h, s, r0, s.mins, f.norm_cols ? h->vn2 : nullptr, DC - D, row_scale, 0);   // (synchronises: `init` is a temporary)
 }
+static int ensure_sq8_locked(lynse_hip_flat* h) { return ensure_codes_locked(h, h->sq8, CODES_PLAIN); }
 
 // LYNSE_HIP_SQ7: 0 = never, 1 = wherever the shape is eligible (any shard size, any sign), unset = auto (read per call: tests flip it)
 static int sq7_env() { return env_int("LYNSE_HIP_SQ7", -1); }
@@ -2515,160 +2603,45 @@ static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool m
 // The copy only changes speed: a shape that scans it gets it built here (writer lock), and a build that fails — no memory for one more byte
 // per element — leaves the batch on the SQ8 codes and switches SQ7 off for the handle.  A copy the handle will not scan again (struck
 // out, or rows that turned mixed-sign under auto) is freed.
-static void sq7_release_locked(lynse_hip_flat* h) {
-    if (h->sq7) (void)hipFree(h->sq7);
-    h->sq7 = nullptr; h->sq7_cap = 0; h->n_sq7 = 0;
-}
-static bool sq7_stale(const lynse_hip_flat* h) { return h->sq7 && (h->sq7_strikes.load() >= 3 || (!h->rows_nonneg && sq7_env() != 1)); }
+static bool sq7_stale(const lynse_hip_flat* h) { return h->sq7.codes && (h->sq7_strikes.load() >= 3 || (!h->rows_nonneg && sq7_env() != 1)); }
 static int ensure_sq7_locked(lynse_hip_flat* h);
 static void sq7_sync_locked(lynse_hip_flat* h, int metric, uint64_t nqc, bool masked) {
-    if (sq7_stale(h)) sq7_release_locked(h);
-    if (!sq7_wanted(h, metric, nqc, masked) || !h->sq8 || h->n_sq8 != h->n || !h->sq8_finite) return;
+    if (sq7_stale(h)) h->sq7.release();
+    if (!sq7_wanted(h, metric, nqc, masked) || !h->sq8.ready(h->n) || !h->sq8.finite) return;
     if (ensure_sq7_locked(h) != LYNSE_OK) {
         (void)hipGetLastError();
-        sq7_release_locked(h);
+        h->sq7.release();
         h->sq7_strikes.store(3);
     }
 }
 // The SQ7 copy, from the fit of the SQ8 codes (which must be up to date): rows appended under an unchanged fit are coded alone and
 // raise the maxima; a new fit codes every row again.  (Callers: sq7_sync_locked.)
 static int ensure_sq7_locked(lynse_hip_flat* h) {
-    if (h->sq7 && h->n_sq7 == h->n && h->sq7_fit == h->sq8_fit) return LYNSE_OK;
-    if (!h->sq8 || h->n_sq8 != h->n) return set_error(LYNSE_ERR_INTERNAL, "the SQ7 copy is built from the fit of up-to-date SQ8 codes");
+    CodeSet& s = h->sq7;
+    if (s.ready(h->n) && h->sq7_fit == h->sq8_fit) return LYNSE_OK;
+    if (!h->sq8.ready(h->n)) return set_error(LYNSE_ERR_INTERNAL, "the SQ7 copy is built from the fit of up-to-date SQ8 codes");
     hipStream_t st = cur(h).stream;
-    const bool kept = h->sq7 != nullptr && h->sq7_cap >= h->n && h->sq7_fit == h->sq8_fit && h->n_sq7 < h->n;
-    if (h->sq7_cap < h->n) {
-        sq7_release_locked(h);
+    const bool kept = s.codes != nullptr && s.cap >= h->n && h->sq7_fit == h->sq8_fit && s.n < h->n;
+    if (s.cap < h->n) {
+        s.release();
         const uint64_t cap = std::max<uint64_t>(h->capacity, h->n);
-        LY_HIP(hipMalloc(&h->sq7, (size_t)cap * h->ld8 + 256));
-        h->sq7_cap = cap;
+        LY_HIP(hipMalloc(&s.codes, (size_t)cap * s.ld + 256));
+        s.cap = cap;
     }
-    if (!h->sq7_scales) {
-        LY_HIP(hipMalloc(&h->sq7_scales, (size_t)h->dim * 4));
-        LY_HIP(hipMalloc(&h->sq7_stats, 16));
+    if (!s.scales) {
+        LY_HIP(hipMalloc(&s.scales, (size_t)s.cols * 4));
+        LY_HIP(hipMalloc(&s.stats, 16));
     }
-    const uint64_t r0 = kept ? h->n_sq7 : 0;
+    const uint64_t r0 = kept ? s.n : 0;
     if (r0 == 0) {
-        LY_HIP(hipMemsetAsync(h->sq7_stats, 0, 16, st));
-        hipLaunchKernelGGL(k_sq8_scales, dim3((h->dim + 255) / 256), dim3(256), 0, st, h->sq8_mm, h->sq8_mm + h->dim, h->dim, (float*)nullptr, h->sq7_scales, 127.0f);
+        LY_HIP(hipMemsetAsync(s.stats, 0, 16, st));
+        hipLaunchKernelGGL(k_sq8_scales, dim3((s.cols + 255) / 256), dim3(256), 0, st, h->sq8.mm, h->sq8.mm + s.cols, s.cols, (float*)nullptr, s.scales, 127.0f);
     }
-    const uint64_t nn = h->n - r0;
-    const uint32_t qgrid = (uint32_t)std::min<uint64_t>((nn + 3) / 4, (uint64_t)h->num_cu * 16);
-    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3(qgrid), dim3(256), 0, st, (const _Float16*)h->rows_h + r0 * h->ld16, h->ld16, h->dim, nn, h->sq8_mins, h->sq7_scales,
-                                      h->sq7 + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq7_stats, (const float*)nullptr, 0u, (const float*)nullptr, 1);
-    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3(qgrid), dim3(256), 0, st, h->rows + r0 * h->ld, h->ld, h->dim, nn, h->sq8_mins, h->sq7_scales,
-                            h->sq7 + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq7_stats, (const float*)nullptr, 0u, (const float*)nullptr, 1);
-    LY_HIP(hipGetLastError());
-    uint32_t qst[4] = {0, 0, 0, 0};
-    LY_HIP(hipMemcpyAsync(qst, h->sq7_stats, 16, hipMemcpyDeviceToHost, st));
-    LY_HIP(hipStreamSynchronize(st));
-    h->sq7_a1 = qst[0];
-    h->sq7_a2sq = qst[2];
-    memcpy(&h->sq7_eps2, &qst[3], 4);
-    h->n_sq7 = h->n;
+    LY_TRY(quantize_rows_locked(h, s, r0, h->sq8.mins, nullptr, 0u, nullptr, 1));
     h->sq7_fit = h->sq8_fit;
     return LYNSE_OK;
 }
-static bool sq7_ready(const lynse_hip_flat* h) { return h->sq7 && h->n_sq7 == h->n && h->sq7_fit == h->sq8_fit && h->sq8 && h->n_sq8 == h->n; }
-
-// The augmented code set of the L2 form (rows [v, |v|^2]): rebuilt over all rows when rows were appended, like the SQ8 set.
-static int ensure_sq8a_locked(lynse_hip_flat* h) {
-    if (h->n_sq8a == h->n && h->sq8a) return LYNSE_OK;
-    const uint32_t DA = h->dim + h->aug_cols;
-    if (h->sq8a_cap < h->n) {
-        if (h->sq8a) (void)hipFree(h->sq8a);
-        h->sq8a = nullptr;
-        const uint64_t cap = std::max<uint64_t>(h->capacity, h->n);
-        LY_HIP(hipMalloc(&h->sq8a, (size_t)cap * h->ld8a + 256));
-        h->sq8a_cap = cap;
-    }
-    if (!h->sq8a_mins) {
-        LY_HIP(hipMalloc(&h->sq8a_mins, (size_t)DA * 4));
-        LY_HIP(hipMalloc(&h->sq8a_scales, (size_t)DA * 4));
-        LY_HIP(hipMalloc(&h->sq8a_mm, (size_t)DA * 8));
-        LY_HIP(hipMalloc(&h->sq8a_stats, 16));   // (four words: k_sq8_quantize)
-    }
-    LY_HIP(hipMemsetAsync(h->sq8a_stats, 0, 16, cur(h).stream));
-    std::vector<uint32_t> init((size_t)DA * 2);
-    for (uint32_t d = 0; d < DA; ++d) { init[d] = f32_to_ord(INFINITY); init[DA + d] = f32_to_ord(-INFINITY); }
-    LY_HIP(hipMemcpyAsync(h->sq8a_mm, init.data(), init.size() * 4, hipMemcpyHostToDevice, cur(h).stream));
-    const uint32_t gx = (h->dim + 255) / 256;
-    const uint32_t gy = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(h->n / 256, 1), (uint64_t)h->num_cu * 8);
-    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_minmax<_Float16>, dim3(gx, gy), dim3(256), 0, cur(h).stream, (const _Float16*)h->rows_h, h->ld16, h->dim, h->n, h->sq8a_mm, h->sq8a_mm + DA);
-    else hipLaunchKernelGGL(k_sq8_minmax<float>, dim3(gx, gy), dim3(256), 0, cur(h).stream, h->rows, h->ld, h->dim, h->n, h->sq8a_mm, h->sq8a_mm + DA);
-    hipLaunchKernelGGL(k_vec_minmax, dim3((uint32_t)std::min<uint64_t>((h->n + 255) / 256, (uint64_t)h->num_cu * 8)), dim3(256), 0, cur(h).stream,
-                       h->vn2, h->n, h->sq8a_mm + h->dim, h->sq8a_mm + DA + h->dim, h->aug_cols);
-    hipLaunchKernelGGL(k_sq8_scales, dim3((DA + 255) / 256), dim3(256), 0, cur(h).stream, h->sq8a_mm, h->sq8a_mm + DA, DA, h->sq8a_mins, h->sq8a_scales);
-    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3((uint32_t)std::min<uint64_t>((h->n + 3) / 4, (uint64_t)h->num_cu * 16)), dim3(256), 0, cur(h).stream,
-                       (const _Float16*)h->rows_h, h->ld16, h->dim, h->n, h->sq8a_mins, h->sq8a_scales, h->sq8a, h->ld8a, (int*)nullptr, (int*)nullptr, h->sq8a_stats, h->vn2, h->aug_cols);
-    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3((uint32_t)std::min<uint64_t>((h->n + 3) / 4, (uint64_t)h->num_cu * 16)), dim3(256), 0, cur(h).stream,
-                       h->rows, h->ld, h->dim, h->n, h->sq8a_mins, h->sq8a_scales, h->sq8a, h->ld8a, (int*)nullptr, (int*)nullptr, h->sq8a_stats, h->vn2, h->aug_cols);
-    LY_HIP(hipGetLastError());
-    uint32_t qst[4] = {0, 0, 0, 0};
-    LY_HIP(hipMemcpyAsync(qst, h->sq8a_stats, 16, hipMemcpyDeviceToHost, cur(h).stream));
-    LY_HIP(hipStreamSynchronize(cur(h).stream));  // `init` is a temporary
-    h->sq8a_a1 = qst[0];
-    h->sq8a_a2sq = qst[2];
-    memcpy(&h->sq8a_eps2, &qst[3], 4);
-    h->sq8a_finite = qst[1] == 0;
-    h->n_sq8a = h->n;
-    return LYNSE_OK;
-}
-
-// The code set of the cosine form: SQ8 codes of the rows scaled to unit norm with the stored reciprocal norm.
-static int ensure_sq8c_locked(lynse_hip_flat* h) {
-    if (h->n_sq8c == h->n && h->sq8c) return LYNSE_OK;
-    const uint32_t D = h->dim;
-    const bool kept = h->sq8c != nullptr && h->sq8c_mins != nullptr && h->sq8c_cap >= h->n;
-    if (h->sq8c_cap < h->n) {
-        if (h->sq8c) (void)hipFree(h->sq8c);
-        h->sq8c = nullptr;
-        const uint64_t cap = std::max<uint64_t>(h->capacity, h->n);
-        LY_HIP(hipMalloc(&h->sq8c, (size_t)cap * h->ld8 + 256));
-        h->sq8c_cap = cap;
-    }
-    if (!h->sq8c_mins) {
-        LY_HIP(hipMalloc(&h->sq8c_mins, (size_t)D * 4));
-        LY_HIP(hipMalloc(&h->sq8c_scales, (size_t)D * 4));
-        LY_HIP(hipMalloc(&h->sq8c_mm, (size_t)D * 8));
-        LY_HIP(hipMalloc(&h->sq8c_stats, 16));   // (four words: k_sq8_quantize)
-    }
-    uint64_t r0 = 0;
-    bool mm_done = false;
-    if (kept) LY_TRY(sq8_merge_new_rows(h, h->sq8c_mm, D, h->n_sq8c, h->vrinv, &r0, &mm_done));   // (appended rows inside the fitted ranges: only they are coded)
-    const uint32_t gx = (D + 255) / 256;
-    std::vector<uint32_t> init;
-    if (!mm_done) {
-        init.resize((size_t)D * 2);
-        for (uint32_t d = 0; d < D; ++d) { init[d] = f32_to_ord(INFINITY); init[D + d] = f32_to_ord(-INFINITY); }
-        LY_HIP(hipMemcpyAsync(h->sq8c_mm, init.data(), init.size() * 4, hipMemcpyHostToDevice, cur(h).stream));
-        const uint32_t gy = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(h->n / 256, 1), (uint64_t)h->num_cu * 8);
-        if (is_f16(h)) hipLaunchKernelGGL(k_sq8_minmax<_Float16>, dim3(gx, gy), dim3(256), 0, cur(h).stream, (const _Float16*)h->rows_h, h->ld16, D, h->n, h->sq8c_mm, h->sq8c_mm + D, h->vrinv);
-        else hipLaunchKernelGGL(k_sq8_minmax<float>, dim3(gx, gy), dim3(256), 0, cur(h).stream, h->rows, h->ld, D, h->n, h->sq8c_mm, h->sq8c_mm + D, h->vrinv);
-    }
-    if (r0 == 0) {
-        LY_HIP(hipMemsetAsync(h->sq8c_stats, 0, 16, cur(h).stream));
-        hipLaunchKernelGGL(k_sq8_scales, dim3(gx), dim3(256), 0, cur(h).stream, h->sq8c_mm, h->sq8c_mm + D, D, h->sq8c_mins, h->sq8c_scales);
-    }
-    const uint64_t nn = h->n - r0;
-    const uint32_t qgrid = (uint32_t)std::min<uint64_t>((nn + 3) / 4, (uint64_t)h->num_cu * 16);
-    if (is_f16(h)) hipLaunchKernelGGL(k_sq8_quantize<_Float16>, dim3(qgrid), dim3(256), 0, cur(h).stream,
-                       (const _Float16*)h->rows_h + r0 * h->ld16, h->ld16, D, nn, h->sq8c_mins, h->sq8c_scales, h->sq8c + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq8c_stats,
-                       (const float*)nullptr, 0u, h->vrinv + r0);
-    else hipLaunchKernelGGL(k_sq8_quantize<float>, dim3(qgrid), dim3(256), 0, cur(h).stream,
-                       h->rows + r0 * h->ld, h->ld, D, nn, h->sq8c_mins, h->sq8c_scales, h->sq8c + r0 * h->ld8, h->ld8, (int*)nullptr, (int*)nullptr, h->sq8c_stats,
-                       (const float*)nullptr, 0u, h->vrinv + r0);
-    LY_HIP(hipGetLastError());
-    uint32_t qst[4] = {0, 0, 0, 0};
-    LY_HIP(hipMemcpyAsync(qst, h->sq8c_stats, 16, hipMemcpyDeviceToHost, cur(h).stream));
-    LY_HIP(hipStreamSynchronize(cur(h).stream));  // `init` is a temporary
-    h->sq8c_a1 = qst[0];
-    h->sq8c_a2sq = qst[2];
-    memcpy(&h->sq8c_eps2, &qst[3], 4);
-    h->sq8c_finite = qst[1] == 0;
-    h->n_sq8c = h->n;
-    return LYNSE_OK;
-}
+static bool sq7_ready(const lynse_hip_flat* h) { return h->sq7.ready(h->n) && h->sq7_fit == h->sq8_fit && h->sq8.ready(h->n); }
 
 extern "C" int lynse_hip_flat_sq8_params(lynse_hip_flat* h, float* mins, float* scales) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -2677,8 +2650,8 @@ extern "C" int lynse_hip_flat_sq8_params(lynse_hip_flat* h, float* mins, float* 
     if (h->packed_only || h->n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no f32 rows");
     LY_TRY(finalize_locked(h));
     LY_TRY(ensure_sq8_locked(h));
-    if (mins) LY_HIP(hipMemcpy(mins, h->sq8_mins, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
-    if (scales) LY_HIP(hipMemcpy(scales, h->sq8_scales, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
+    if (mins) LY_HIP(hipMemcpy(mins, h->sq8.mins, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
+    if (scales) LY_HIP(hipMemcpy(scales, h->sq8.scales, (size_t)h->dim * 4, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
@@ -2696,17 +2669,17 @@ static int run_chunk_sq8(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t ou
     LY_TRY(ensure_lds<k_select<SEL_NT>>(SEL_LDS_MAX));
     LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
     LY_HIP(hipMemsetAsync(w.Q16, 0, (size_t)nslab * qpad * 128, st));
-    hipLaunchKernelGGL(k_sq8_prep_queries, dim3(nq), dim3(256), 0, st, w.Qf, h->dim, qpad, nslab, h->sq8_mins, h->sq8_scales,
+    hipLaunchKernelGGL(k_sq8_prep_queries, dim3(nq), dim3(256), 0, st, w.Qf, h->dim, qpad, nslab, h->sq8.mins, h->sq8.scales,
                        reinterpret_cast<int8_t*>(w.Q16), w.qn2, w.thr, w.count, w.overflow, ip ? 1 : 0);
     LY_HIP(hipGetLastError());
     const std::vector<Stage> plan = make_plan(h, n_cand, level >= 2 ? 2 : 1, 0);  // contiguous stages: rows in ascending order
     for (size_t si = 0; si < plan.size(); ++si) {
         const Stage s = plan[si];
         ScanArgs a{};
-        a.V16 = reinterpret_cast<const _Float16*>(h->sq8); a.ld16 = h->ld8; a.D = h->dim; a.row0 = s.r0; a.row1 = s.r1;
+        a.V16 = reinterpret_cast<const _Float16*>(h->sq8.codes); a.ld16 = h->sq8.ld; a.D = h->dim; a.row0 = s.r0; a.row1 = s.r1;
         a.Q16 = w.Q16; a.qpad = qpad; a.nq = nq; a.nslab = nslab; a.ntiles = (s.r1 - s.r0 + 255) / 256;
         a.qinv = w.qinv; a.qn2 = w.qn2; a.qrinv = w.qrinv; a.thr = w.thr;
-        a.vn2 = reinterpret_cast<const float*>(ip ? h->sq8_sum : h->sq8_sum2); a.vrinv = a.vn2;
+        a.vn2 = reinterpret_cast<const float*>(ip ? h->sq8.sum : h->sq8.sum2); a.vrinv = a.vn2;
         a.sv = 1.0f; a.cand = w.cand; a.count = w.count; a.cap = w.cap; a.emit_all = si == 0 ? 1 : 0;
         const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
         a.candB = w.candB; a.segcnt = w.segcnt;
@@ -2798,28 +2771,19 @@ static int coarse_env() {
 static std::atomic<int>& i8c_strike_counter(lynse_hip_flat* h, int metric) {
     return metric == M_L2 ? h->i8c_strikes_l2 : (metric == M_COS ? h->i8c_strikes_cos : h->i8c_strikes);
 }
-// Squared L2 has two int8 forms: unfiltered FLAT batches over whole 128-column slabs run on the PLAIN codes with the exact f32
-// row norms in a float epilogue (k_scan_h16<.., I8Q = 4>, every tiling: 1 B per element, no second code set, IP-sized margins);
-// everything else (ragged widths, masked scans, IVF) on the codes of the AUGMENTED rows through the IP kernels.  nqc = 0: "not a FLAT
-// batch" (IVF): the augmented form.  LYNSE_HIP_L2_PLAIN=0: always the augmented form.
-static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked) {
-    static const int on = env_int("LYNSE_HIP_L2_PLAIN", 1);
-    // (1M x 128, k = 100: 0.244 ms on the f16 shadow, 0.277 on the codes with the <4,2,2,4> tiling and 0.291 with the query-stationary
-    // L2 tiling (k_scan_qs<1,4,1,6,.., MET = 1>, built and measured in round 4: at k = 100 the first threshold lets 0.8 % of all
-    // (row, query) pairs through and the scan is bound by the emission of ~8000 keys per query, not by the tiling) — from 256
-    // dimensions on)
-    return on && !masked && nqc >= 1 && nqc <= QCHUNK && h->ld8 % 128 == 0 && h->dim >= 256;
-}
+// (which code set a batch reads and in which form: i8c_form / i8c_code_set, with run_chunk)
 static bool i8c_codes_ready(const lynse_hip_flat* h, int metric, uint64_t nqc = 0, bool masked = false) {
-    if (metric == M_L2 && !l2_plain(h, nqc, masked)) return h->sq8a && h->n_sq8a == h->n;
-    if (metric == M_COS) return h->sq8c && h->n_sq8c == h->n;
-    return h->sq8 && h->n_sq8 == h->n;
+    return i8c_code_set(h, i8c_form(h, metric, nqc, masked)).ready(h->n);
 }
 static bool i8c_codes_finite(const lynse_hip_flat* h, int metric, uint64_t nqc = 0, bool masked = false) {
-    return (metric == M_L2 && !l2_plain(h, nqc, masked)) ? h->sq8a_finite : (metric == M_COS ? h->sq8c_finite : h->sq8_finite);
+    return i8c_code_set(h, i8c_form(h, metric, nqc, masked)).finite;
 }
 static int ensure_i8c_codes_locked(lynse_hip_flat* h, int metric, uint64_t nqc = 0, bool masked = false) {
-    return (metric == M_L2 && !l2_plain(h, nqc, masked)) ? ensure_sq8a_locked(h) : (metric == M_COS ? ensure_sq8c_locked(h) : ensure_sq8_locked(h));
+    switch (i8c_form(h, metric, nqc, masked)) {
+    case I8C_L2_AUG: return ensure_codes_locked(h, h->sq8a, CODES_AUG);
+    case I8C_COS: return ensure_codes_locked(h, h->sq8c, CODES_UNIT);
+    default: return ensure_sq8_locked(h);
+    }
 }
 static void i8c_add_strike(lynse_hip_flat* h, int metric) {
     std::atomic<int>& c = i8c_strike_counter(h, metric);
@@ -2835,7 +2799,7 @@ static bool i8c_eligible(const lynse_hip_flat* h, int metric, bool filtered, uin
     // rescoring pools ~10x wider: it pays from ~256 dimensions on (MI355X: 10M x 768 x 256 3.97 -> 2.81 ms; 1M x 128, k = 100
     // 0.24 -> 0.34 ms: stays on the f16 pass)
     const bool l2_ok = metric == M_L2 && !l2_off &&
-                       (l2_plain(h, nqc, masked) || (h->dim >= 256 && (uint64_t)h->ld8a * 4 <= (uint64_t)h->ld16 * 2 * 3));
+                       (i8c_form(h, metric, nqc, masked) == I8C_L2_PLAIN || (h->dim >= 256 && (uint64_t)h->ld8a * 4 <= (uint64_t)h->ld16 * 2 * 3));
     // cosine streams the codes of the unit rows (1 B per element, like IP); tiny-norm rows make the f16 pass go exhaustive and
     // are left to it
     const bool cos_ok = metric == M_COS && !l2_off && h->dim >= 256 && !h->cos_degenerate;
@@ -2942,7 +2906,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         // chunks of a large batch can differ (the last one may be small): the chunk loop checks again and restarts under the writer lock
         if (i8c_eligible(h, metric, false, std::min<uint64_t>(nq, QCHUNK), caller_holds_exclusive, filtered)) {
             // (the blocking search alone scans the SQ7 copy: a wanted copy that is missing, or a stale one, is dealt with under the writer lock)
-            if (sq7_stale(h) || (sq7_wanted(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) && h->sq8_finite && !sq7_ready(h))) return false;
+            if (sq7_stale(h) || (sq7_wanted(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) && h->sq8.finite && !sq7_ready(h))) return false;
             return i8c_codes_ready(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered);
         }
         return shadow_ready(h) || small_path_ok(h, std::min<uint64_t>(nq, QCHUNK), (uint32_t)std::min<uint64_t>(k, h->n), metric, filtered);
@@ -3144,11 +3108,10 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
     if (direct) { h->rows16 = h->g_rows16; h->n = n_subset; h->vn2 = h->g_vn2; h->vrinv = h->g_vrinv; }
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    size_t ev_used = 0;
-    std::vector<std::pair<size_t, uint64_t>> scan_events;
+    ScanProf sprof;
     if (tl_prof) {
-        LY_TRY(get_event(h, ev_used++, &ev_begin));
-        LY_TRY(get_event(h, ev_used++, &ev_end));
+        LY_TRY(get_event(h, sprof.ev_used++, &ev_begin));
+        LY_TRY(get_event(h, sprof.ev_used++, &ev_end));
         LY_HIP(hipEventRecord(ev_begin, st));
     }
     uint64_t fallback_queries = 0;
@@ -3196,7 +3159,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             uint64_t* r_dst = on_device ? out_rows + q0 * k : reinterpret_cast<uint64_t*>(w.h_out);
             float* d_dst = on_device ? out_dists + q0 * k : reinterpret_cast<float*>(w.h_out + rows_b);
             uint32_t* c_dst = on_device ? out_counts + q0 : w.h_hdr;
-            LY_TRY(run_small(h, nqc, kk, k, metric, st, &ev_used, &scan_events, r_dst, d_dst, c_dst, w.h_hdr + w.qcap,
+            LY_TRY(run_small(h, nqc, kk, k, metric, st, &sprof, r_dst, d_dst, c_dst, w.h_hdr + w.qcap,
                              on_device ? (const float*)q_src + q0 * h->dim : w.Qf));  // device queries are read in place
             LY_HIP(hipStreamSynchronize(st));
             if (!on_device) {
@@ -3208,17 +3171,22 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         }
         bool allow_sts = true, allow_sq7 = true;
         for (int level = 0; level < 3; ++level) {  // sampled plan -> contiguous plan -> exhaustive plan (make_plan)
-            bool sampled = false, used_sts = false, used_sq7 = false;
+            ChunkResult res;
             // k_final writes the results where they belong — the caller's device arrays, or the pinned (device-visible)
             // staging buffer for small host-API results: no copy kernels behind the search; only large host results go
             // through the workspace + two device-to-host copies.  One synchronisation per chunk (counts + overflow flags in
             // one small pinned readback); a retry on the next plan level overwrites the outputs in stream order.
             const size_t rows_b = (size_t)nqc * k * 8, dists_b = (size_t)nqc * k * 4;
             const bool staged = !on_device && rows_b + dists_b <= H_OUT_BYTES;
-            uint64_t* r_dst = on_device ? out_rows + q0 * k : (staged ? reinterpret_cast<uint64_t*>(w.h_out) : nullptr);
-            float* d_dst = on_device ? out_dists + q0 * k : (staged ? reinterpret_cast<float*>(w.h_out + rows_b) : nullptr);
-            LY_TRY(run_chunk(h, nqc, kk, k, metric, level, st, &ev_used, &scan_events, &sampled, mask, direct ? h->g_ids32 : nullptr, i8c,
-                             r_dst, d_dst, on_device ? out_counts + q0 : nullptr, nullptr, qsrc, true, allow_sts, &used_sts, allow_sq7, &used_sq7));
+            ChunkReq rq;
+            rq.nq = nqc; rq.k = kk; rq.out_k = k; rq.metric = metric; rq.level = level;
+            rq.mask = mask; rq.row_ids = direct ? h->g_ids32 : nullptr; rq.qsrc = qsrc;
+            rq.i8c = i8c; rq.allow_sts = allow_sts; rq.allow_sq7 = allow_sq7;
+            rq.out.rows = on_device ? out_rows + q0 * k : (staged ? reinterpret_cast<uint64_t*>(w.h_out) : nullptr);
+            rq.out.dists = on_device ? out_dists + q0 * k : (staged ? reinterpret_cast<float*>(w.h_out + rows_b) : nullptr);
+            rq.out.counts2 = on_device ? out_counts + q0 : nullptr;
+            rq.out.hdr_direct = true;
+            LY_TRY(run_chunk(h, rq, st, &sprof, &res));
             if (!on_device && !staged) {
                 LY_HIP(hipMemcpyAsync(out_rows + q0 * k, w.out_rows, rows_b, out_kind, st));
                 LY_HIP(hipMemcpyAsync(out_dists + q0 * k, w.out_dists, dists_b, out_kind, st));
@@ -3232,12 +3200,12 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             }
             if (level == 2) return set_error(LYNSE_ERR_INTERNAL, "candidate overflow on the exhaustive plan");
             fallback_queries += nov;
-            if (used_sts) {  // the self-tightening scan overflowed (scores rising along every workgroup's chunk): the staged plan of the same coarse pass
+            if (res.used_sts) {  // the self-tightening scan overflowed (scores rising along every workgroup's chunk): the staged plan of the same coarse pass
                 allow_sts = false;
                 --level;
                 continue;
             }
-            if (used_sq7) {  // the wider SQ7 margin overflowed: the same plan level on the SQ8 codes — a strike against SQ7, none against int8
+            if (res.used_sq7) {  // the wider SQ7 margin overflowed: the same plan level on the SQ8 codes — a strike against SQ7, none against int8
                 allow_sq7 = false;
                 h->sq7_strikes.fetch_add(1);
                 --level;
@@ -3250,14 +3218,14 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
                 --level;
                 continue;
             }
-            if (level == 0 && !sampled) level = 1;  // level 1 would repeat the same contiguous plan
+            if (level == 0 && !res.sampled) level = 1;  // level 1 would repeat the same contiguous plan
         }
         if (!on_device) memcpy(out_counts + q0, w.h_hdr, nqc * 4);
     }
 
     if (tl_prof) {
         LY_HIP(hipEventRecord(ev_end, st));
-        LY_TRY(prof_accumulate(h, cur(h), ev_begin, ev_end, scan_events, binary, fallback_queries));
+        LY_TRY(prof_accumulate(h, cur(h), ev_begin, ev_end, sprof.scan_events, binary, fallback_queries));
         if (i8c_attempted) {  // bit 6: the search STARTED on the certified int8 pass (an overflow may have sent it to the f16 pass)
             std::lock_guard<std::mutex> plk(h->prof_mu);
             h->prof.last_plan |= 64u;
@@ -3295,20 +3263,16 @@ static int coarse_scores_impl(lynse_hip_flat* h, const float* queries, uint64_t 
     Workspace& w = cur(h).ws;
     hipStream_t st = cur(h).stream;
     LY_HIP(hipMemcpyAsync(w.Qf, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, st));
-    size_t ev_used = 0;
-    std::vector<std::pair<size_t, uint64_t>> scan_events;
-    bool sampled = false;
-    tl_coarse_dump = true;
-    bool used_sq7 = false;
-    const int rc = run_chunk(h, (uint32_t)nq, 1, 1, metric, 1, st, &ev_used, &scan_events, &sampled, nullptr, nullptr, i8c,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, false, true, nullptr, want_sq7, &used_sq7);
-    tl_coarse_dump = false;
-    LY_TRY(rc);
-    if (want_sq7 && !used_sq7) return set_error(LYNSE_ERR_INTERNAL, "the diagnostics chunk did not scan the SQ7 copy");
+    ScanProf sprof;
+    ChunkReq rq;
+    rq.nq = (uint32_t)nq; rq.k = rq.out_k = 1; rq.metric = metric; rq.level = 1; rq.i8c = i8c; rq.allow_sq7 = want_sq7; rq.mode = CHUNK_COARSE_DUMP;
+    ChunkResult res;
+    LY_TRY(run_chunk(h, rq, st, &sprof, &res));
+    if (want_sq7 && !res.used_sq7) return set_error(LYNSE_ERR_INTERNAL, "the diagnostics chunk did not scan the SQ7 copy");
     LY_HIP(hipStreamSynchronize(st));
-    const bool l2n = i8c && metric == M_L2 && l2_plain(h, nq, false);
-    const bool aug = i8c && metric == M_L2 && !l2n, cosq = i8c && metric == M_COS;
-    if (out_form) *out_form = (i8c ? 1 : 0) | (aug ? 2 : 0) | (l2n ? 4 : 0) | (cosq ? 8 : 0) | (used_sq7 ? 16 : 0);
+    const I8cForm form = i8c_form(h, metric, nq, false);
+    const bool l2n = i8c && form == I8C_L2_PLAIN, aug = i8c && form == I8C_L2_AUG, cosq = i8c && form == I8C_COS;
+    if (out_form) *out_form = (i8c ? 1 : 0) | (aug ? 2 : 0) | (l2n ? 4 : 0) | (cosq ? 8 : 0) | (res.used_sq7 ? 16 : 0);
     const bool key_asc = metric_ascending((aug || cosq) ? (int)M_IP : metric);
     std::vector<uint64_t> keys(h->n);
     std::vector<float> m2(nq);
@@ -3338,7 +3302,7 @@ extern "C" int lynse_hip_flat_coarse_scores_sq7(lynse_hip_flat* h, const float* 
 extern "C" int lynse_hip_flat_sq7_state(lynse_hip_flat* h, uint64_t* out_rows, int* out_strikes) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     std::shared_lock<std::shared_mutex> lk(h->rw);
-    if (out_rows) *out_rows = h->sq7 ? h->n_sq7 : 0;
+    if (out_rows) *out_rows = h->sq7.codes ? h->sq7.n : 0;
     if (out_strikes) *out_strikes = h->sq7_strikes.load();
     return LYNSE_OK;
 }
@@ -3350,7 +3314,7 @@ extern "C" int lynse_hip_flat_coarse_state(lynse_hip_flat* h, int* out_strikes, 
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     std::shared_lock<std::shared_mutex> lk(h->rw);
     if (out_strikes) *out_strikes = h->i8c_strikes.load();
-    if (out_sq8_rows) *out_sq8_rows = h->sq8 ? h->n_sq8 : 0;
+    if (out_sq8_rows) *out_sq8_rows = h->sq8.codes ? h->sq8.n : 0;
     return LYNSE_OK;
 }
 
@@ -3399,10 +3363,7 @@ extern "C" uint64_t lynse_hip_flat_hbm_bytes(const lynse_hip_flat* h) {
     if (h->rows16 && !h->shadow_alias) b += h->cap16 * h->ld16 * 2ull;
     if (h->vn2) b += 2ull * (h->stats_capacity + 256) * 4;
     if (h->packed) b += h->packed_capacity * h->words * 8ull;
-    if (h->sq8) b += h->sq8_cap * h->ld8 + 2ull * (h->sq8_cap + 256) * 4;
-    if (h->sq7) b += h->sq7_cap * h->ld8;
-    if (h->sq8a) b += h->sq8a_cap * h->ld8a;
-    if (h->sq8c) b += h->sq8c_cap * h->ld8;
+    for (const CodeSet* s : {&h->sq8, &h->sq7, &h->sq8a, &h->sq8c}) b += s->hbm_bytes();
     if (h->bpm) b += h->bpm_cap * h->ld_bpm;
     return b;
 }
@@ -3552,14 +3513,14 @@ static int search_sq8_large(lynse_hip_flat* h, std::unique_lock<std::shared_mute
     hipStream_t st = cur(h).stream;
     struct Sq8View {  // the pass-1 side of the handle advanced to one row range; rows come back as RAW shard rows
         lynse_hip_flat* h;
-        float* rows; int8_t* sq8; int *sum, *sum2; uint64_t n, n_sq8, stride, offset;
-        explicit Sq8View(lynse_hip_flat* hh) : h(hh), rows(hh->rows), sq8(hh->sq8), sum(hh->sq8_sum), sum2(hh->sq8_sum2), n(hh->n), n_sq8(hh->n_sq8),
+        float* rows; CodeSet sq8; uint64_t n, stride, offset;
+        explicit Sq8View(lynse_hip_flat* hh) : h(hh), rows(hh->rows), sq8(hh->sq8), n(hh->n),
                                                stride(hh->row_stride), offset(hh->row_offset) {}
         void set(uint64_t r0, uint64_t r1) {
-            h->rows = rows + r0 * h->ld; h->sq8 = sq8 + r0 * h->ld8; h->sq8_sum = sum + r0; h->sq8_sum2 = sum2 + r0;
-            h->n = r1 - r0; h->n_sq8 = h->n; h->row_stride = 1; h->row_offset = r0;
+            h->rows = rows + r0 * h->ld; h->sq8.codes = sq8.codes + r0 * sq8.ld; h->sq8.sum = sq8.sum + r0; h->sq8.sum2 = sq8.sum2 + r0;
+            h->n = r1 - r0; h->sq8.n = h->n; h->row_stride = 1; h->row_offset = r0;
         }
-        void restore() { h->rows = rows; h->sq8 = sq8; h->sq8_sum = sum; h->sq8_sum2 = sum2; h->n = n; h->n_sq8 = n_sq8; h->row_stride = stride; h->row_offset = offset; }
+        void restore() { h->rows = rows; h->sq8 = sq8; h->n = n; h->row_stride = stride; h->row_offset = offset; }
         ~Sq8View() { restore(); }
     };
     std::vector<std::vector<uint64_t>> cand(nq);   // per query: the top-n_cand rows of pass 1
@@ -3693,7 +3654,7 @@ extern "C" int lynse_hip_top_k_search(const float* query, const float* candidate
     lynse_hip_flat* h = sc.h;
     {   // empty the shard (capacity and buffers stay)
         std::unique_lock<std::shared_mutex> lk(h->rw);
-        h->n = 0; h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->n_sq8 = 0; h->n_sq7 = 0; h->sq7_strikes.store(0); h->n_sq8a = 0; h->n_sq8c = 0; h->n_bpm = 0; h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
+        h->n = 0; h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->sq8.n = 0; h->sq7.n = 0; h->sq7_strikes.store(0); h->sq8a.n = 0; h->sq8c.n = 0; h->n_bpm = 0; h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
         h->amax = h->vmax = h->vmin = 0.f; h->sv = 1.f; h->cos_degenerate = 0; h->rows_integer = 0; h->rows_nonneg = 0;
         const uint32_t init[5] = {0u, 0u, 0x7f800000u, 0u, 0u};
         LY_TRY(use_device(h));

@@ -78,11 +78,15 @@ def check_bound(L, orc, data, queries, metric_name, metric, coarse, f16_rows=Fal
     if want_form is not None:
         assert form == want_form, (form, want_form)
     exact = exact_scores(orc, queries, data, metric, False)   # (f32 kernels; the f16 kernels' sequential sums differ by less than the bound's rounding term)
+    return assert_within_bound(scores, bound, exact, (metric_name, coarse, "f16 rows" if f16_rows else "f32 rows"))
+
+
+def assert_within_bound(scores, bound, exact, label):
     err = np.abs(scores.astype(np.float64) - exact)
     ratio = err / bound.astype(np.float64)[:, None]
     worst = np.unravel_index(np.argmax(ratio), ratio.shape)
     assert np.all(np.isfinite(scores)) and np.all(bound > 0)
-    assert ratio.max() <= 1.0, (metric_name, coarse, "f16 rows" if f16_rows else "f32 rows", float(ratio.max()), worst, float(err[worst]), float(bound[worst[0]]))
+    assert ratio.max() <= 1.0, (*label, float(ratio.max()), worst, float(err[worst]), float(bound[worst[0]]))
     return float(ratio.max()), worst
 
 
@@ -221,3 +225,70 @@ def test_cauchy_schwarz_term_is_binding_and_met_on_a_fresh_shard_and_after_an_ap
     assert worst == (0, n - 1) and ratio.max() > 0.9, (float(ratio.max()), worst)      # met by the constructed pair, to within the 2 % safety factor + the f32 terms
     if appended:
         assert float(bound[0]) > 1.5 * float(b0[0]), (float(bound[0]), float(b0[0]))   # the append raised the statistic the bound is made of
+
+
+# ---- every code set after an append: the codes of a shard that grew must be the codes of a shard written in one go ------------------
+# The plain set merges appended rows into its fit and codes them alone while no fitted range moves, the unit-row (cosine) set does the
+# same on the rows scaled by their reciprocal norms, the augmented (L2) set always refits.  Same codes, same scales and same statistics
+# give the same integer dot products and the same certified bound: coarse scores and bounds are compared bit for bit.
+APPEND_N0, APPEND_DUPS, APPEND_CAP = 4096, 512, 16384
+
+
+@pytest.fixture(scope="module")
+def append_rows():
+    """Per width: APPEND_CAP random rows with lognormal row scales (read-only) and 8 queries."""
+    cache = {}
+
+    def get(dim):
+        if dim not in cache:
+            rng = np.random.default_rng(31 + dim)
+            rows = rng.standard_normal((APPEND_CAP, dim)).astype(f32) * np.exp(rng.normal(0.0, 0.5, (APPEND_CAP, 1))).astype(f32)
+            queries = rng.standard_normal((8, dim)).astype(f32)
+            rows.setflags(write=False)
+            queries.setflags(write=False)
+            cache[dim] = rows, queries
+        return cache[dim]
+
+    return get
+
+
+@pytest.mark.parametrize("append", ["inside", "outside", "regrow"])
+@pytest.mark.parametrize("metric_name,metric,dim,want_form", [("ip", O.IP, 256, FORM_I8), ("l2", O.L2, 256, FORM_I8 | FORM_L2N),
+                                                             ("l2", O.L2, 200, FORM_I8 | FORM_AUG), ("cosine", O.COS, 256, FORM_I8 | FORM_COSQ),
+                                                             ("cosine", O.COS, 100, FORM_I8 | FORM_COSQ)])
+def test_appended_code_sets_equal_a_fresh_build(L, oracle, append_rows, metric_name, metric, dim, want_form, append):
+    rows, queries = append_rows(dim)
+    first = rows[:APPEND_N0]
+    rng = np.random.default_rng(32)
+    if append == "regrow":       # no reserve: the row matrix and with it every code buffer is reallocated
+        extra = rows[APPEND_N0:]
+    else:                        # exact duplicates of stored rows in shuffled order: no fitted range can move
+        extra = first[rng.permutation(APPEND_N0)[:APPEND_DUPS]]
+        if append == "outside":  # ... plus one (short) row with one element at twice its column's maximum: a new fit for the plain and unit-row sets
+            out = 0.01 * first[7]
+            out[5] = 2.0 * first[:, 5].max()
+            assert out[5] > 0
+            extra = np.vstack([extra, out[None, :]])
+    grown = L.FlatIndex(None, dim)
+    if append != "regrow":
+        grown.reserve(APPEND_N0 + extra.shape[0])
+    grown.write(first)
+    grown.finalize()
+    _, _, form0 = grown.coarse_scores(queries, metric_name, "i8")      # the codes of the first rows exist before the append
+    assert form0 == want_form, (form0, want_form)
+    grown.write(extra)
+    grown.finalize()
+    data = np.vstack([first, extra])
+    fresh = L.FlatIndex(None, dim)
+    fresh.write(data)
+    fresh.finalize()
+    sg, bg, fg = grown.coarse_scores(queries, metric_name, "i8")
+    sf, bf, ff = fresh.coarse_scores(queries, metric_name, "i8")
+    assert fg == want_form and ff == want_form, (fg, ff, want_form)
+    diff = np.flatnonzero(sg.view(np.uint32).ravel() != sf.view(np.uint32).ravel())
+    print(f"appended code set {metric_name} dim {dim} {append}: {diff.size} of {sg.size} coarse scores differ, bounds {bg.tolist()} / {bf.tolist()}")
+    assert diff.size == 0, (metric_name, dim, append, diff[:8])
+    assert np.array_equal(bg.view(np.uint32), bf.view(np.uint32)), (metric_name, dim, append, bg, bf)
+    exact = exact_scores(oracle, queries, data, metric, False)
+    assert_within_bound(sg, bg, exact, (metric_name, "i8", append, "grown"))
+    assert_within_bound(sf, bf, exact, (metric_name, "i8", append, "fresh"))
