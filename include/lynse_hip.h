@@ -304,6 +304,66 @@ int lynse_hip_flat_search_rabitq_f32(lynse_hip_flat *h, const float *queries, ui
                                      uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
 int lynse_hip_flat_rabitq_stage_times(lynse_hip_flat *h, double *out3, int reset);
 int lynse_hip_rabitq_sign_words(uint64_t seed, uint64_t count, uint64_t *out);
+/* HNSW-{IP,L2,COS,COSINE} (HNSWIndex, src/index/hnsw.rs; Collection, engine.rs:4606-4655, :4743-4745): a layered neighbour graph over
+ * the rows of a FLAT handle — the graph holds ids, the rows stay the handle's — a deterministic bulk build from exact neighbour lists,
+ * and the reference's beam search.  f32 handles and ip / l2 / cosine only.  The reference's search is a function of the graph, the
+ * levels, the entry point and the query (ties aside) and is restated here; its build (SmallRng::from_entropy, concurrent inserts,
+ * hnsw.rs:952-1031) differs from run to run and is no parity target: rules 1-4 define this library's own.  The rules:
+ *  0. The graph distance d(a, b) is compute_distance_f32 in the single-row form of the metric (for ip the two-accumulator kernel,
+ *     whatever lynse_hip_flat_set_ip_form says), negated for ip (hnsw.rs:536-543).  A NaN distance becomes +inf the moment it is
+ *     computed, in the build and in the search.  The three forms are symmetric bit for bit, so d(i, j) stands for d(j, i).
+ *     Parameters: m in 2..32 (1 / ln(1) is infinite; m0 = 2 m <= 64), ef_construction and ef_search in 1..4096, max_level (< 0 = no
+ *     cap), seed.  The reference's defaults: m 16, ef_construction 128, ef_search 50 (src/index/mod.rs:503, :681-686); the Collection
+ *     passes seed 42.
+ *  1. Levels, in integers only: w_i = the i-th next_u64() of SmallRng::seed_from_u64(seed) (the stream of lynse_hip_rabitq_sign_words);
+ *     t = max(w_i >> 11, 1), level = 0; while level < max_level (when capped) and t * m < 2^53: t *= m, ++level.  P(level >= l) = m^-l,
+ *     the distribution of floor(-ln U / ln m), without libm.  The entry point is the first row of the highest level (hnsw.rs:967-975).
+ *     lynse_hip_hnsw_levels exposes this host code for known-answer tests.
+ *  2. Candidates at level l: S_l = {i : level_i >= l}; cand_l(i) = the best ef_construction of S_l \ {i} by (d, row ascending): the
+ *     exact FLAT search of the handle (over the BitSet of S_l above level 0) asked for ef_construction + 1 rows, i removed — the last
+ *     entry dropped instead when i did not come back.
+ *  3. Forward lists: F_l(i) = select_neighbors_heuristic(cand_l(i), cap) (hnsw.rs:550-602), cap = 2 m at level 0 and m above: all
+ *     candidates when there are no more than cap; else walk them nearest first, keep c unless some already kept s has
+ *     d(c, s) < d(i, c), stop at cap, then fill the free slots with the nearest candidates not kept.
+ *  4. Adjacency: U(i) = F(i) and every j with i in F(j), each member once, ordered by (d(i, .), node).  No more than cap: that list.
+ *     Else the heuristic's output on it, in selection order.  Stored order matters: the search admits neighbours in stored order.
+ *  5. Search (hnsw.rs:1040-1140, unfiltered): ef = max(ef_query > 0 ? ef_query : ef_search, k).  Greedy descent on levels top .. 1
+ *     (:758-777): a pass scans the list of the node it started from and moves to every neighbour strictly closer than the best so far;
+ *     passes repeat until one moves nothing.  Beam at level 0 (:625-699): C a min-heap of candidates, R a max-heap of at most ef
+ *     results, both start with the node the descent ended on; pop the closest c of C; stop when c.dist > worst.dist and R is full; for
+ *     each unvisited neighbour in stored order: mark it visited, compute d, admit it to C and R iff R is not full or d < worst.dist
+ *     (strict, on the distance alone), then evict R's maximum when |R| > ef.  The reference orders its heaps by distance alone, which
+ *     leaves ties to BinaryHeap internals; here every pop, eviction and the final sort use the total order (dist, node), so results
+ *     equal the reference's whenever no two visited nodes tie.  Output: the best min(k, |R|) of R by (dist, node), ip distances
+ *     un-negated, in the layout of lynse_hip_flat_search_f32 (row ~0 and the worst distance after out_counts[q] entries).
+ *  6. The graph covers the first n_hnsw rows: rows appended after a build or a load stay outside it.  Build and load replace an earlier
+ *     graph; lynse_hip_flat_drop_hnsw removes it.  The exact searches of the handle are unchanged.
+ *  Refused with LYNSE_ERR_UNSUPPORTED: an F16 shard, a packed-only handle, a row-mapped handle, the binary and additive metrics, m or
+ *  an ef outside its bounds, a build, load or search while tickets of lynse_hip_flat_search_submit_* are outstanding, a beam (24 bytes per ef, ef >= k)
+ *  that does not share the 160 KiB of LDS with the query, and a build with ef_construction + 1 > 4096 over more than 16,384 rows (the
+ *  exact search's candidate capacity).  A search metric other than the build metric: LYNSE_ERR_INVALID_ARGUMENT.  There is no ticket,
+ *  _device, sharded, filtered or incremental form.  Build, load, drop and search hold the handle's lock exclusively and run on context 0.
+ * lynse_hip_flat_load_hnsw takes levels[n], adj0[n][2 m], and the n_upper = sum of the levels upper lists upper_adj[n_upper][m] with
+ * their upper_node[] / upper_level[] in ascending (node, level) order, lists padded with 0xFFFFFFFF, n <= the handle's rows.  It
+ * answers LYNSE_ERR_INVALID_ARGUMENT unless every neighbour is < n, a neighbour of a level-l list has level >= l, the upper lists match
+ * the levels and the entry has the top level.  Pad entries inside a list and a neighbour named twice are dropped (first place kept):
+ * neither changes a search.  lynse_hip_flat_hnsw_params returns info = {metric, m, ef_search, entry, top_level, n_upper} and n_hnsw
+ * (all 0 without an index) and, for the pointers that are not NULL, the same arrays.  lynse_hip_flat_hnsw_stage_times: out6[0..2] the
+ * candidate-list, selection and reverse-edge microseconds of the last build (host clock around synchronised stages), then, with
+ * profiling on, out6[3] searches, out6[4] their kernel microseconds (HIP events) and out6[5] the distances they scored; reset != 0
+ * clears the last three. */
+int lynse_hip_flat_build_hnsw(lynse_hip_flat *h, int metric, uint32_t m, uint32_t ef_construction, uint32_t ef_search,
+                              int32_t max_level, uint64_t seed);
+int lynse_hip_flat_load_hnsw(lynse_hip_flat *h, int metric, uint32_t m, uint32_t ef_search, const uint32_t *levels, uint64_t n,
+                             const uint32_t *adj0, uint64_t n_upper, const uint32_t *upper_node, const uint32_t *upper_level,
+                             const uint32_t *upper_adj, uint32_t entry);
+int lynse_hip_flat_hnsw_params(lynse_hip_flat *h, uint32_t *info, uint64_t *n_hnsw, uint32_t *levels, uint32_t *adj0,
+                               uint32_t *upper_node, uint32_t *upper_level, uint32_t *upper_adj);
+int lynse_hip_flat_drop_hnsw(lynse_hip_flat *h);
+int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric, uint32_t ef_query,
+                                   uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
+int lynse_hip_flat_hnsw_stage_times(lynse_hip_flat *h, double *out6, int reset);
+int lynse_hip_hnsw_levels(uint64_t seed, uint32_t m, int32_t max_level, uint64_t n, uint32_t *out);
 /* Range search (Collection::search_range, src/engine.rs:6410-6483): every row of the handle is scored with the single-row kernel
  * (compute_distance_f32) and the rows on the passing side of the caller's threshold come back, best first, at most max_results of
  * them.  One threshold per query.  The rules:

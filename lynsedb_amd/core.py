@@ -196,6 +196,44 @@ def spann_build_options(params: Optional[dict]) -> dict:
     return out
 
 
+HNSW_MODES = {"HNSW-IP": _lib.METRIC_IP, "HNSW-L2": _lib.METRIC_L2, "HNSW-COS": _lib.METRIC_COSINE, "HNSW-COSINE": _lib.METRIC_COSINE}
+HNSW_DEFAULTS = {"m": 16, "ef_construction": 128, "ef_search": 50}   # src/index/mod.rs:503, :681-686
+HNSW_SEED = 42
+# IndexBuildOptions::is_known_key (src/index/mod.rs:572-592)
+INDEX_BUILD_KEYS = ("n_clusters", "n_centroids", "m", "ef_construction", "ef_search", "max_level", "r", "l", "alpha", "max_degree", "nprobe",
+                    "replica_count")
+
+
+def hnsw_mode_of(mode: str) -> Optional[int]:
+    """The metric id of HNSW-{IP,L2,COS,COSINE} (any letter case), None for every other mode — HNSW-*-SQ8, HNSW over the domain metrics
+    and DiskANN keep the answers they had (outside this path)."""
+    return HNSW_MODES.get(str(mode).upper())
+
+
+def hnsw_build_options(params: Optional[dict]) -> dict:
+    """IndexBuildOptions for an HNSW mode (src/index/mod.rs:545-655): m = 16, ef_construction = 128, ef_search = 50, max_level = None
+    (uncapped).  An unknown key and a value of 0 are refused with the reference's messages (ValueError, InvalidArgument); keys of the
+    other index families are ignored (filtered_for).  The bounds on m and the ef values are the library's (LYNSE_ERR_UNSUPPORTED)."""
+    p = dict(params or {})
+    for key in p:
+        if key not in INDEX_BUILD_KEYS:
+            raise ValueError(f"Invalid argument: unknown index build parameter '{key}'; supported keys: {', '.join(INDEX_BUILD_KEYS)}")
+    if "n_centroids" in p and "n_clusters" not in p:
+        p["n_clusters"] = p.pop("n_centroids")
+    for name in ("n_clusters", "m", "ef_construction", "ef_search", "r", "l", "max_degree", "nprobe", "replica_count"):   # validate()'s order
+        if p.get(name) is not None and int(p[name]) == 0:
+            raise ValueError(f"Invalid argument: {name} must be greater than 0")
+    out = {name: (default if p.get(name) is None else int(p[name])) for name, default in HNSW_DEFAULTS.items()}
+    for name, v in out.items():
+        if v < 0:
+            raise ValueError(f"Invalid argument: invalid index build parameter value: {name} = {v}")
+    ml = p.get("max_level")
+    if ml is not None and int(ml) < 0:
+        raise ValueError(f"Invalid argument: invalid index build parameter value: max_level = {ml}")
+    out["max_level"] = None if ml is None else int(ml)
+    return out
+
+
 def spann_posting_rule(ranks, replica_count: int) -> list:
     """posting_centroids_for_vector (src/index/spann.rs:130-186) over one row's centroid ranks (distance, negated for IP; f32): the
     lists the row sits in, the primary first.  The restatement the device kernels are checked against."""
@@ -504,6 +542,67 @@ class FlatIndex:
         out = np.zeros(3, np.float64)
         check(lib.lynse_hip_flat_rabitq_stage_times(self._h, _ptr(out), 1 if reset else 0))
         return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+
+    # -- HNSW-* (HNSWIndex, src/index/hnsw.rs; include/lynse_hip.h states the contract) ---------------------------------------
+    def build_hnsw(self, metric, m: int = HNSW_DEFAULTS["m"], ef_construction: int = HNSW_DEFAULTS["ef_construction"],
+                   ef_search: int = HNSW_DEFAULTS["ef_search"], max_level: Optional[int] = None, seed: int = HNSW_SEED) -> None:
+        """Build the graph over the rows held now from their exact neighbour lists (rows appended later stay outside it)."""
+        mt = metric if isinstance(metric, int) else metric_from_str(metric)
+        check(lib.lynse_hip_flat_build_hnsw(self._h, mt, int(m), int(ef_construction), int(ef_search),
+                                            -1 if max_level is None else int(max_level), int(seed)))
+
+    def load_hnsw(self, metric, m: int, ef_search: int, levels, adj0, upper_node, upper_level, upper_adj, entry: int) -> None:
+        """Install a graph as hnsw_params exports it: levels u32 [n], adj0 u32 [n][2 m], the upper lists u32 [n_upper][m] with their
+        (node, level) in ascending order, lists padded with 0xFFFFFFFF."""
+        mt = metric if isinstance(metric, int) else metric_from_str(metric)
+        lv = np.ascontiguousarray(levels, dtype=np.uint32).reshape(-1)
+        a0 = np.ascontiguousarray(adj0, dtype=np.uint32)
+        un = np.ascontiguousarray(upper_node, dtype=np.uint32).reshape(-1)
+        ul = np.ascontiguousarray(upper_level, dtype=np.uint32).reshape(-1)
+        ua = np.ascontiguousarray(upper_adj, dtype=np.uint32).reshape(-1, int(m))
+        if a0.ndim != 2 or a0.shape != (lv.shape[0], 2 * int(m)) or ul.shape != un.shape or ua.shape[0] != un.shape[0]:
+            raise ValueError("adj0 must be [n][2 m], upper_adj [n_upper][m] with upper_node / upper_level [n_upper]")
+        check(lib.lynse_hip_flat_load_hnsw(self._h, mt, int(m), int(ef_search), _ptr(lv), lv.shape[0], _ptr(a0), un.shape[0], _ptr(un), _ptr(ul),
+                                           _ptr(ua), int(entry)))
+
+    def drop_hnsw(self) -> None:
+        check(lib.lynse_hip_flat_drop_hnsw(self._h))
+
+    def hnsw_params(self, arrays: bool = True) -> dict:
+        """{"metric", "m", "ef_search", "entry", "top_level", "n_upper", "n"} and, with `arrays`, "levels", "adj0", "upper_node",
+        "upper_level", "upper_adj"; m == 0 without an index."""
+        info = np.zeros(6, np.uint32)
+        n = C.c_uint64(0)
+        check(lib.lynse_hip_flat_hnsw_params(self._h, _ptr(info), C.byref(n), None, None, None, None, None))
+        metric, m, efs, entry, top, nu = (int(x) for x in info)
+        out = {"metric": metric, "m": m, "ef_search": efs, "entry": entry, "top_level": top, "n_upper": nu, "n": int(n.value)}
+        if arrays and m:
+            lv, a0 = np.empty(out["n"], np.uint32), np.empty((out["n"], 2 * m), np.uint32)
+            un, ul, ua = np.empty(nu, np.uint32), np.empty(nu, np.uint32), np.empty((nu, m), np.uint32)
+            check(lib.lynse_hip_flat_hnsw_params(self._h, _ptr(info), C.byref(n), _ptr(lv), _ptr(a0), _ptr(un), _ptr(ul), _ptr(ua)))
+            out.update(levels=lv, adj0=a0, upper_node=un, upper_level=ul, upper_adj=ua)
+        return out
+
+    def search_hnsw_batch_arrays(self, queries, k: int, metric, ef: int = 0):
+        """Greedy descent and the beam search at level 0 with ef = max(ef or the index's ef_search, k)."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_flat_search_hnsw_f32(self._h, _ptr(q), nq, k, m, int(ef), _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+    def hnsw_stage_times(self, reset: bool = True) -> dict:
+        """The stages of the last build (microseconds) and, with profiling on, the searches timed, their kernel microseconds and the
+        distances they scored."""
+        out = np.zeros(6, np.float64)
+        check(lib.lynse_hip_flat_hnsw_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"candidates_us": float(out[0]), "select_us": float(out[1]), "reverse_us": float(out[2]), "searches": int(out[3]),
+                "search_us": float(out[4]), "scored": int(out[5])}
 
     def search_range_batch_arrays(self, queries, thresholds, max_results: int, metric, bitset_words=None):
         """Range search (Collection::search_range, engine.rs:6410-6483) for a batch, one threshold per query: the exact scan of every
@@ -1386,6 +1485,9 @@ class Collection:
         self._tombstone: set = set()    # user ids (engine.rs:3182-3194)
         self._pq = False                # FLAT-*-PQ built over the rows flushed at build time (FlatIndex.build_pq)
         self._rabitq = False            # FLAT-*-RABITQ, likewise (FlatIndex.build_rabitq); at most one of the two exists
+        self._hnsw = False              # HNSW-*: a graph over the flushed rows (FlatIndex.build_hnsw); replaces and is replaced by the two above
+        self._hnsw_rows = 0             # rows the graph was built over
+        self._hnsw_opts: dict = {}
         self._sparse: dict = {}         # user id -> (indices u32, values f32), normalised (SparseVectorStore.vectors)
         self._sparse_ids = np.zeros(0, np.int64)   # the ids of the uploaded sparse rows, ascending: sparse row -> user id
         self._sparse_index = None       # SparseIndex, created by the first sparse search
@@ -1477,6 +1579,15 @@ class Collection:
                 self._flat.build_rabitq()
                 self._rabitq = True
                 self._save_rabitq()
+        elif hnsw_mode_of(mode) is not None:   # HNSW-{IP,L2,COS,COSINE}; every other HNSW-* name falls through to the refusal below
+            opts = hnsw_build_options(params)
+            self._ivf = None
+            self._drop_aux()
+            if len(self._flat) == 0:   # graph / partition indexes need data (engine.rs:4606-4612)
+                raise ValueError("Empty database")
+            self._hnsw_opts = opts
+            self._metric = metric
+            self._build_hnsw()
         elif mode.startswith("SPANN"):
             metric, sq8 = spann_mode_of(mode)
             opts = spann_build_options(params)
@@ -1502,7 +1613,8 @@ class Collection:
         """At most one auxiliary quantised index exists: whatever is built next, the earlier one and its file go."""
         self._flat.drop_pq()
         self._flat.drop_rabitq()
-        self._pq = self._rabitq = False
+        self._flat.drop_hnsw()
+        self._pq = self._rabitq = self._hnsw = False
         if self._path is not None:
             (self._path / RABITQ_INDEX_FILE).unlink(missing_ok=True)
 
@@ -1536,6 +1648,13 @@ class Collection:
         self._rabitq = True
         self._index_mode, self._metric = mode, metric_from_index_mode(mode)
         return True
+
+    def _build_hnsw(self) -> None:
+        """The graph over every flushed row.  There is no incremental insert and no on-disk form: rows flushed after a build, and a
+        reopened collection, build it again."""
+        o = self._hnsw_opts
+        self._flat.build_hnsw(self._metric, o["m"], o["ef_construction"], o["ef_search"], o["max_level"], HNSW_SEED)
+        self._hnsw, self._hnsw_rows = True, len(self._flat)
 
     def _build_ivf(self) -> None:
         n = len(self._flat)
@@ -1610,6 +1729,10 @@ class Collection:
             if subset_rows.size == 0:
                 return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
             return self._flat.search_filtered_batch_arrays(q, search_k, self._metric, subset_rows)
+        if self._hnsw:   # nprobe > 0 is the query-time ef (engine.rs:4743-4745); a subset took the exact filtered scan above
+            if self._hnsw_rows != len(self._flat):   # rows were flushed after the build
+                self._build_hnsw()
+            return self._flat.search_hnsw_batch_arrays(q, search_k, self._metric, int(nprobe))
         if self._pq:   # search_auxiliary_quantized (engine.rs:5504-5526): rows committed after the build are not in the index
             return self._flat.search_pq_batch_arrays(q, search_k, self._metric, PQ_OVERSAMPLE)
         if self._rabitq:
@@ -1647,6 +1770,7 @@ class Collection:
         sq8 = self._ivf is not None and self._ivf.is_sq8
         pq = self._ivf is None and self._pq and subset is None
         rabitq = self._ivf is None and self._rabitq and subset is None
+        hnsw = self._ivf is None and self._hnsw and subset is None
         target.profile_enable(True)
         target.profile_get(reset=True)
         if sq8:
@@ -1655,7 +1779,9 @@ class Collection:
             self._flat.pq_stage_times(reset=True)
         if rabitq:
             self._flat.rabitq_stage_times(reset=True)
-        stage_us = None
+        if hnsw:
+            self._flat.hnsw_stage_times(reset=True)
+        stage_us = hnsw_us = None
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
@@ -1668,11 +1794,14 @@ class Collection:
             if rabitq:   # FLAT-*-RABITQ: both stages of the two-pass search
                 t = self._flat.rabitq_stage_times(reset=True)
                 rerank_us, stage_us = int(t["rescore_us"]), {"scan_us": float(t["scan_us"]), "rescore_us": float(t["rescore_us"])}
+            if hnsw:
+                t = self._flat.hnsw_stage_times(reset=True)
+                hnsw_us = {"search_us": float(t["search_us"]), "scored": int(t["scored"])}
             target.profile_enable(False)
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
-                   "index_path": "ann_index" if self._ivf is not None else ("flat_mmap_filtered" if subset is not None else
+                   "index_path": "ann_index" if self._ivf is not None or hnsw else ("flat_mmap_filtered" if subset is not None else
                                                                             ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else "flat_mmap"))),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
@@ -1682,6 +1811,8 @@ class Collection:
                               "fallback_queries": int(dev["fallback_queries"]), "plan": int(dev["last_plan"])}}
         if stage_us is not None:
             profile["device"]["rabitq_stages"] = stage_us
+        if hnsw_us is not None:
+            profile["device"]["hnsw"] = hnsw_us
         return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
                 "profile": profile}
 

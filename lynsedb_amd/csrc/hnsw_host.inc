@@ -1,0 +1,461 @@
+// hnsw_host.inc — HNSW-{IP,L2,COS} on a FLAT handle (HNSWIndex, src/index/hnsw.rs; Collection, src/engine.rs:4606-4655, :4743-4745).
+// Included at the end of lynse_hip.hip after rabitq_host.inc (the SmallRng restatement is pqrng); kernels in hnsw.h.  The rule block of
+// include/lynse_hip.h states the contract, DESIGN.md §19 the reasoning.  The graph shares the handle's rows: it holds ids only.
+
+struct HnswState {
+    int metric = -1;
+    uint32_t m = 0, ef_search = 0, entry = 0, top_level = 0;
+    uint64_t n = 0;                       // the graph covers the first n rows of the handle
+    std::vector<uint32_t> levels;         // [n]
+    std::vector<uint32_t> upper_node, upper_level;   // ascending (node, level), levels >= 1
+    uint32_t *d_adj0 = nullptr, *d_upper_off = nullptr, *d_upper_adj = nullptr;
+    // search scratch
+    float *d_q = nullptr, *d_dists = nullptr;
+    uint64_t* d_rows = nullptr;
+    uint32_t *d_vis = nullptr, *d_counts = nullptr, *d_status = nullptr;
+    size_t q_cap = 0, dists_cap = 0, rows_cap = 0, vis_cap = 0, counts_cap = 0;
+    // the last build, microseconds of host time around synchronised stages; the searches timed with profiling on
+    double cand_us = 0.0, select_us = 0.0, reverse_us = 0.0, searches = 0.0, search_us = 0.0, scored = 0.0;
+
+    bool built() const { return d_adj0 != nullptr; }
+    void free_index() {
+        for (void* p : {(void*)d_adj0, (void*)d_upper_off, (void*)d_upper_adj})
+            if (p) (void)hipFree(p);
+        d_adj0 = d_upper_off = d_upper_adj = nullptr;
+        levels.clear(); upper_node.clear(); upper_level.clear();
+        metric = -1;
+        m = ef_search = entry = top_level = 0;
+        n = 0;
+    }
+    ~HnswState() {
+        free_index();
+        for (void* p : {(void*)d_q, (void*)d_dists, (void*)d_rows, (void*)d_vis, (void*)d_counts, (void*)d_status})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static void hnsw_release(lynse_hip_flat* h) {
+    delete h->hnsw;
+    h->hnsw = nullptr;
+}
+
+constexpr uint32_t HNSW_M_MIN = 2, HNSW_M_MAX = 32, HNSW_EF_MAX = 4096, HNSW_LEVEL_MAX = 52;   // t * m < 2^53 with m >= 2 ends at 52
+
+// rule 1: level i from the i-th next_u64 of SmallRng::seed_from_u64(seed), integers only; max_level < 0 = no cap
+static void hnsw_levels(uint64_t seed, uint32_t m, int32_t max_level, uint64_t n, uint32_t* out) {
+    pqrng::Xoshiro256pp rng = pqrng::Xoshiro256pp::seed_from_u64(seed);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t t = std::max<uint64_t>(rng.next() >> 11, 1);
+        uint32_t level = 0;
+        while ((max_level < 0 || level < (uint32_t)max_level) && t * m < (1ull << 53)) { t *= m; ++level; }
+        out[i] = level;
+    }
+}
+
+extern "C" int lynse_hip_hnsw_levels(uint64_t seed, uint32_t m, int32_t max_level, uint64_t n, uint32_t* out) {
+    if (n && !out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m < HNSW_M_MIN || m > HNSW_M_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: m must be between 2 and 32");
+    hnsw_levels(seed, m, max_level, n, out);
+    return LYNSE_OK;
+}
+
+static int hnsw_check_metric(int metric) {
+    LY_TRY(metric_check(metric));
+    if (metric_binary(metric)) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW is defined for ip / l2 / cosine");
+    return LYNSE_OK;
+}
+static int hnsw_check_handle(const lynse_hip_flat* h) {
+    if (h->dtype != LYNSE_DTYPE_F32) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW on an F16 shard is not supported");
+    if (h->packed_only) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW is defined for float rows (ip / l2 / cosine)");
+    if (h->row_stride != 1 || h->row_offset != 0) return set_error(LYNSE_ERR_UNSUPPORTED, "an HNSW index is not row-sharded");
+    return LYNSE_OK;
+}
+static int hnsw_check_params(uint32_t m, uint32_t ef_construction, uint32_t ef_search) {
+    if (m < HNSW_M_MIN || m > HNSW_M_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: m must be between 2 and 32");
+    if (ef_construction < 1 || ef_construction > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef_construction must be between 1 and 4096");
+    if (ef_search < 1 || ef_search > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef_search must be between 1 and 4096");
+    return LYNSE_OK;
+}
+// the exclusive lock of the HNSW entries: tickets outstanding are a refusal of this index, not a bad argument
+static int hnsw_lock(lynse_hip_flat* h, std::unique_lock<std::shared_mutex>& lk) {
+    lk = std::unique_lock<std::shared_mutex>(h->rw);
+    if (h->inflight.load(std::memory_order_acquire) != 0) {
+        lk.unlock();
+        return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: searches are in flight on this handle: wait for the outstanding tickets first");
+    }
+    return LYNSE_OK;
+}
+
+// A graph on the host: adj0[n][2 m], upper lists in ascending (node, level) order.  Installing uploads it.
+struct HnswGraph {
+    uint32_t m = 0, entry = 0, top_level = 0;
+    uint64_t n = 0;
+    std::vector<uint32_t> levels, adj0, upper_off, upper_node, upper_level, upper_adj;
+    void shape(uint32_t mm, const uint32_t* lv, uint64_t nn) {
+        m = mm; n = nn;
+        levels.assign(lv, lv + nn);
+        upper_off.assign(nn, HNSW_PAD);
+        uint64_t nu = 0;
+        top_level = 0;
+        for (uint64_t i = 0; i < nn; ++i) {
+            if (lv[i]) upper_off[i] = (uint32_t)nu;
+            for (uint32_t l = 1; l <= lv[i]; ++l) { upper_node.push_back((uint32_t)i); upper_level.push_back(l); }
+            nu += lv[i];
+            top_level = std::max(top_level, lv[i]);
+        }
+        for (uint64_t i = 0; i < nn; ++i)
+            if (lv[i] == top_level) { entry = (uint32_t)i; break; }   // the first row of the highest level (hnsw.rs:967-975)
+        adj0.assign((size_t)nn * 2 * mm, HNSW_PAD);
+        upper_adj.assign((size_t)nu * mm, HNSW_PAD);
+    }
+    uint32_t* list(uint32_t node, uint32_t level) {
+        return level == 0 ? &adj0[(size_t)node * 2 * m] : &upper_adj[((size_t)upper_off[node] + level - 1) * m];
+    }
+};
+
+static int hnsw_install(lynse_hip_flat* h, HnswGraph& gph, int metric, uint32_t ef_search) {
+    if (!h->hnsw) h->hnsw = new HnswState();
+    HnswState& s = *h->hnsw;
+    s.free_index();
+    uint32_t *d_adj0 = nullptr, *d_off = nullptr, *d_up = nullptr;
+    auto fail = [&](int rc) {
+        for (void* p : {(void*)d_adj0, (void*)d_off, (void*)d_up})
+            if (p) (void)hipFree(p);
+        return rc;
+    };
+    auto up = [&](uint32_t** d, const std::vector<uint32_t>& v) -> int {
+        LY_HIP(hipMalloc(d, std::max<size_t>(v.size(), 1) * 4));
+        if (!v.empty()) LY_TRY(h2d_done(*d, v.data(), v.size() * 4));
+        return LYNSE_OK;
+    };
+    int rc = up(&d_adj0, gph.adj0);
+    if (rc == LYNSE_OK) rc = up(&d_off, gph.upper_off);
+    if (rc == LYNSE_OK) rc = up(&d_up, gph.upper_adj);
+    if (rc != LYNSE_OK) return fail(rc);
+    s.metric = metric; s.m = gph.m; s.ef_search = ef_search; s.entry = gph.entry; s.top_level = gph.top_level; s.n = gph.n;
+    s.levels.swap(gph.levels); s.upper_node.swap(gph.upper_node); s.upper_level.swap(gph.upper_level);
+    s.d_adj0 = d_adj0; s.d_upper_off = d_off; s.d_upper_adj = d_up;
+    return LYNSE_OK;
+}
+
+static inline double hnsw_now_us() {
+    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3;
+}
+
+// Rules 2-4 for one level: `items` = S_l ascending.  Fills the level's lists of `gph`.
+static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint32_t level, const std::vector<uint32_t>& items,
+                            uint32_t ef_construction, double* times3) {
+    const uint32_t ns = (uint32_t)items.size(), cap = level == 0 ? 2 * gph.m : gph.m, D = h->dim;
+    const uint64_t n = gph.n;
+    if (ns <= 1) return LYNSE_OK;   // a node alone on its level has no candidates
+    hipStream_t st = cur(h).stream;
+    const uint32_t ask = ef_construction + 1;
+    std::vector<uint64_t> words;
+    uint32_t* d_items = nullptr;
+    float *d_q = nullptr, *d_cd = nullptr, *d_fd = nullptr;
+    uint64_t* d_cr = nullptr;
+    uint32_t *d_cc = nullptr, *d_fid = nullptr;
+    uint32_t *d_uid = nullptr; float* d_ud = nullptr; uint64_t* d_uoff = nullptr; uint32_t* d_oid = nullptr; float* d_od = nullptr;
+    struct Free { std::vector<void**> ps; ~Free() { for (void** p : ps) if (*p) (void)hipFree(*p); } } fr;
+    fr.ps = {(void**)&d_items, (void**)&d_q, (void**)&d_cd, (void**)&d_fd, (void**)&d_cr, (void**)&d_cc, (void**)&d_fid,
+             (void**)&d_uid, (void**)&d_ud, (void**)&d_uoff, (void**)&d_oid, (void**)&d_od};
+    if (level > 0) {
+        words.assign((n + 63) / 64, 0ull);
+        for (uint32_t r : items) words[r >> 6] |= 1ull << (r & 63u);
+    }
+    LY_HIP(hipMalloc(&d_items, (size_t)ns * 4));
+    LY_TRY(h2d_done(d_items, items.data(), (size_t)ns * 4));
+    // queries per pass: the candidate lists of a pass stay under 256 MiB, its queries under 128 MiB
+    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)ns, (256ull << 20) / ((uint64_t)ask * 12), (128ull << 20) / ((uint64_t)D * 4)}));
+    LY_HIP(hipMalloc(&d_q, (size_t)qc * D * 4));
+    LY_HIP(hipMalloc(&d_cr, (size_t)qc * ask * 8));
+    LY_HIP(hipMalloc(&d_cd, (size_t)qc * ask * 4));
+    LY_HIP(hipMalloc(&d_cc, (size_t)qc * 4));
+    LY_HIP(hipMalloc(&d_fid, (size_t)ns * cap * 4));
+    LY_HIP(hipMalloc(&d_fd, (size_t)ns * cap * 4));
+    const size_t sel_lds = 512 + (size_t)D * 4;
+    for (uint64_t q0 = 0; q0 < ns; q0 += qc) {
+        const uint64_t nqc = std::min<uint64_t>(qc, ns - q0);
+        double t0 = hnsw_now_us();
+        hipLaunchKernelGGL(k_hnsw_gather, dim3((uint32_t)std::min<uint64_t>((nqc * D + 255) / 256, (uint64_t)h->num_cu * 32)), dim3(256), 0, st,
+                           h->rows, h->ld, D, d_items + q0, 0u, nqc, d_q);
+        LY_HIP(hipGetLastError());
+        LY_HIP(hipStreamSynchronize(st));
+        // rule 2: the exact searches of the handle, single-row kernels (the caller pinned the SINGLE ip form), canonical (d, row) order
+        LY_TRY(search_impl(h, d_q, false, nqc, ask, metric, d_cr, d_cd, d_cc, true, nullptr, nullptr, level > 0 ? (uint64_t)ns : 0, level > 0,
+                           level > 0 ? words.data() : nullptr, words.size(), true));
+        LY_HIP(hipStreamSynchronize(st));
+        double t1 = hnsw_now_us();
+        times3[0] += t1 - t0;
+        // rule 3: the forward lists
+        HnswSelectArgs sa{};
+        sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = metric; sa.cap = cap;
+        sa.item_node = d_items + q0; sa.rows64 = d_cr; sa.d64 = d_cd; sa.cnt64 = d_cc; sa.stride = ask;
+        sa.out_ids = d_fid + q0 * cap; sa.out_d = d_fd + q0 * cap;
+        LY_TRY(launch_lds<k_hnsw_select>(dim3((uint32_t)nqc), dim3(64), sel_lds, st, sa));
+        LY_HIP(hipStreamSynchronize(st));
+        times3[1] += hnsw_now_us() - t1;
+    }
+    std::vector<uint32_t> fid((size_t)ns * cap);
+    std::vector<float> fd((size_t)ns * cap);
+    double t2 = hnsw_now_us();
+    LY_HIP(hipMemcpy(fid.data(), d_fid, fid.size() * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(fd.data(), d_fd, fd.size() * 4, hipMemcpyDeviceToHost));
+    // rule 4: U(i) = F(i) and the reverse edges, each member once, ordered by (d, node) — as keys, so one integer sort per node
+    std::vector<uint32_t> item_of;
+    if (level > 0) {
+        item_of.assign(n, HNSW_PAD);
+        for (uint32_t t = 0; t < ns; ++t) item_of[items[t]] = t;
+    }
+    auto item = [&](uint32_t node) { return level > 0 ? item_of[node] : node; };
+    std::vector<uint64_t> off((size_t)ns + 1, 0);
+    for (uint32_t t = 0; t < ns; ++t)
+        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != HNSW_PAD; ++s) {
+            ++off[t + 1];
+            ++off[item(fid[(size_t)t * cap + s]) + 1];
+        }
+    for (uint32_t t = 0; t < ns; ++t) off[t + 1] += off[t];
+    std::vector<uint64_t> keys(off[ns]), fill(off.begin(), off.end() - 1);
+    for (uint32_t t = 0; t < ns; ++t)
+        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != HNSW_PAD; ++s) {
+            const uint32_t j = fid[(size_t)t * cap + s];
+            const float d = fd[(size_t)t * cap + s];
+            keys[fill[t]++] = make_key(d, j, true);
+            keys[fill[item(j)]++] = make_key(d, items[t], true);   // d(j, i) = d(i, j) bit for bit (rule block: symmetric forms)
+        }
+    std::vector<uint64_t> uoff(1, 0);
+    std::vector<uint32_t> over, uid;
+    std::vector<float> ud;
+    for (uint32_t t = 0; t < ns; ++t) {
+        uint64_t* b = keys.data() + off[t];
+        uint64_t* e = keys.data() + off[t + 1];
+        std::sort(b, e);
+        e = std::unique(b, e);
+        const size_t cnt = (size_t)(e - b);
+        uint32_t* dst = gph.list(items[t], level);
+        if (cnt <= cap) {
+            for (size_t s = 0; s < cnt; ++s) dst[s] = key_row(b[s]);
+        } else {   // more than cap: the heuristic again, over U(i)
+            over.push_back(t);
+            for (size_t s = 0; s < cnt; ++s) { uid.push_back(key_row(b[s])); ud.push_back(key_score(b[s], true)); }
+            uoff.push_back(uid.size());
+        }
+    }
+    times3[2] += hnsw_now_us() - t2;
+    if (!over.empty()) {
+        double t3 = hnsw_now_us();
+        const size_t no = over.size();
+        LY_HIP(hipMalloc(&d_uid, uid.size() * 4));
+        LY_HIP(hipMalloc(&d_ud, ud.size() * 4));
+        LY_HIP(hipMalloc(&d_uoff, uoff.size() * 8));
+        LY_HIP(hipMalloc(&d_oid, no * cap * 4));
+        LY_HIP(hipMalloc(&d_od, no * cap * 4));
+        LY_TRY(h2d_done(d_uid, uid.data(), uid.size() * 4));
+        LY_TRY(h2d_done(d_ud, ud.data(), ud.size() * 4));
+        LY_TRY(h2d_done(d_uoff, uoff.data(), uoff.size() * 8));
+        HnswSelectArgs sa{};
+        sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = metric; sa.cap = cap;
+        sa.ids32 = d_uid; sa.d32 = d_ud; sa.offs = d_uoff; sa.out_ids = d_oid; sa.out_d = d_od;
+        LY_TRY(launch_lds<k_hnsw_select>(dim3((uint32_t)no), dim3(64), sel_lds, st, sa));
+        LY_HIP(hipStreamSynchronize(st));
+        std::vector<uint32_t> oid(no * cap);
+        LY_HIP(hipMemcpy(oid.data(), d_oid, oid.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t o = 0; o < no; ++o) memcpy(gph.list(items[over[o]], level), &oid[o * cap], (size_t)cap * 4);
+        times3[1] += hnsw_now_us() - t3;
+    }
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_build_hnsw(lynse_hip_flat* h, int metric, uint32_t m, uint32_t ef_construction, uint32_t ef_search,
+                                         int32_t max_level, uint64_t seed) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_TRY(hnsw_check_metric(metric));
+    LY_TRY(hnsw_check_params(m, ef_construction, ef_search));
+    std::unique_lock<std::shared_mutex> lk;
+    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(use_device(h));
+    LY_TRY(hnsw_check_handle(h));
+    const uint64_t n = h->n;
+    if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
+    if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "an HNSW index holds fewer than 2^32 - 1 rows");
+    if ((size_t)h->dim * 4 + 512 > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: the vector does not fit in LDS");
+    if (n > h->cap && ef_construction + 1 > h->cap / 4)
+        return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef_construction + 1 beyond a quarter of the scan's candidate capacity over a shard larger than it");
+    std::vector<uint32_t> lv(n);
+    hnsw_levels(seed, m, max_level, n, lv.data());
+    HnswGraph gph;
+    gph.shape(m, lv.data(), n);
+    // every distance of the build is the single-row form (rule block): the exact searches follow the handle's ip form
+    struct FormGuard { lynse_hip_flat* h; int f; ~FormGuard() { h->ip_form = f; } } form_guard{h, h->ip_form};
+    h->ip_form = LYNSE_IPFORM_SINGLE;
+    double times3[3] = {0.0, 0.0, 0.0};
+    std::vector<uint32_t> items;
+    for (uint32_t level = 0; level <= gph.top_level; ++level) {
+        items.clear();
+        for (uint64_t i = 0; i < n; ++i)
+            if (lv[i] >= level) items.push_back((uint32_t)i);
+        LY_TRY(hnsw_build_level(h, gph, metric, level, items, ef_construction, times3));
+    }
+    LY_TRY(hnsw_install(h, gph, metric, ef_search));
+    h->hnsw->cand_us = times3[0]; h->hnsw->select_us = times3[1]; h->hnsw->reverse_us = times3[2];
+    return LYNSE_OK;
+}
+
+// A graph as hnsw_params exports it.  Lists are brought into the stored form: HNSW_PAD entries dropped, a neighbour named twice kept
+// once (its first place) — neither changes a search: the second visit of a node is skipped at level 0 and moves nothing above.
+extern "C" int lynse_hip_flat_load_hnsw(lynse_hip_flat* h, int metric, uint32_t m, uint32_t ef_search, const uint32_t* levels, uint64_t n,
+                                        const uint32_t* adj0, uint64_t n_upper, const uint32_t* upper_node, const uint32_t* upper_level,
+                                        const uint32_t* upper_adj, uint32_t entry) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_TRY(hnsw_check_metric(metric));
+    LY_TRY(hnsw_check_params(m, 1, ef_search));
+    std::unique_lock<std::shared_mutex> lk;
+    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(use_device(h));
+    LY_TRY(hnsw_check_handle(h));
+    if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
+    if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "an HNSW index holds fewer than 2^32 - 1 rows");
+    if (n > h->n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the HNSW index covers more rows than the handle holds");
+    if (!levels || !adj0 || (n_upper && (!upper_node || !upper_level || !upper_adj))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if ((size_t)h->dim * 4 + 512 > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: the vector does not fit in LDS");
+    uint64_t nu = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (levels[i] > HNSW_LEVEL_MAX) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a level beyond 52");
+        nu += levels[i];
+    }
+    if (nu != n_upper) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: the upper lists do not match the levels");
+    HnswGraph gph;
+    gph.shape(m, levels, n);
+    for (uint64_t u = 0; u < n_upper; ++u)
+        if (upper_node[u] != gph.upper_node[u] || upper_level[u] != gph.upper_level[u])
+            return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: the upper lists are not in ascending (node, level) order of the levels");
+    if (entry >= n || levels[entry] != gph.top_level) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: the entry point is not a row of the top level");
+    gph.entry = entry;
+    auto take = [&](const uint32_t* src, uint32_t cap, uint32_t level, uint32_t* dst) -> int {
+        uint32_t w = 0;
+        for (uint32_t s = 0; s < cap; ++s) {
+            const uint32_t v = src[s];
+            if (v == HNSW_PAD) continue;
+            if (v >= n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a neighbour beyond the rows of the graph");
+            if (levels[v] < level) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a neighbour below the level of its list");
+            if (std::find(dst, dst + w, v) == dst + w) dst[w++] = v;
+        }
+        return LYNSE_OK;
+    };
+    for (uint64_t i = 0; i < n; ++i) LY_TRY(take(adj0 + i * 2 * m, 2 * m, 0, gph.list((uint32_t)i, 0)));
+    for (uint64_t u = 0; u < n_upper; ++u) LY_TRY(take(upper_adj + u * m, m, upper_level[u], &gph.upper_adj[u * m]));
+    return hnsw_install(h, gph, metric, ef_search);
+}
+
+// info = {metric, m, ef_search, entry, top_level, n_upper}, all 0 (and n_hnsw 0) without an index
+extern "C" int lynse_hip_flat_hnsw_params(lynse_hip_flat* h, uint32_t* info, uint64_t* n_hnsw, uint32_t* levels, uint32_t* adj0,
+                                          uint32_t* upper_node, uint32_t* upper_level, uint32_t* upper_adj) {
+    if (!h || !info || !n_hnsw) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    if (!h->hnsw || !h->hnsw->built()) {
+        for (int i = 0; i < 6; ++i) info[i] = 0;
+        *n_hnsw = 0;
+        return LYNSE_OK;
+    }
+    const HnswState& s = *h->hnsw;
+    const size_t nu = s.upper_node.size();
+    info[0] = (uint32_t)s.metric; info[1] = s.m; info[2] = s.ef_search; info[3] = s.entry; info[4] = s.top_level; info[5] = (uint32_t)nu;
+    *n_hnsw = s.n;
+    LY_TRY(use_device(h));
+    if (levels) memcpy(levels, s.levels.data(), s.levels.size() * 4);
+    if (upper_node && nu) memcpy(upper_node, s.upper_node.data(), nu * 4);
+    if (upper_level && nu) memcpy(upper_level, s.upper_level.data(), nu * 4);
+    if (adj0) LY_HIP(hipMemcpy(adj0, s.d_adj0, (size_t)s.n * 2 * s.m * 4, hipMemcpyDeviceToHost));
+    if (upper_adj && nu) LY_HIP(hipMemcpy(upper_adj, s.d_upper_adj, nu * s.m * 4, hipMemcpyDeviceToHost));
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_flat_drop_hnsw(lynse_hip_flat* h) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_WRITER(h, lk);
+    LY_TRY(use_device(h));
+    if (h->hnsw) h->hnsw->free_index();
+    return LYNSE_OK;
+}
+
+// out6 = {candidate lists, selection, reverse edges} of the last build (microseconds of host time around synchronised stages), then
+// with profiling on: searches timed, their kernel microseconds (HIP events) and the distances they scored
+extern "C" int lynse_hip_flat_hnsw_stage_times(lynse_hip_flat* h, double* out6, int reset) {
+    if (!h || !out6) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    LY_WRITER(h, lk);
+    if (!h->hnsw) { for (int i = 0; i < 6; ++i) out6[i] = 0.0; return LYNSE_OK; }
+    HnswState& s = *h->hnsw;
+    out6[0] = s.cand_us; out6[1] = s.select_us; out6[2] = s.reverse_us; out6[3] = s.searches; out6[4] = s.search_us; out6[5] = s.scored;
+    if (reset) s.searches = s.search_us = s.scored = 0.0;
+    return LYNSE_OK;
+}
+
+// rule 5.  Queries go in chunks that keep the visited bitmaps (n_hnsw bits per query) and the results under 256 MiB each.
+extern "C" int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t ef_query,
+                                              uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    LY_TRY(hnsw_check_metric(metric));
+    if (nq == 0) return LYNSE_OK;
+    if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::unique_lock<std::shared_mutex> lk;
+    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(use_device(h));
+    LY_TRY(hnsw_check_handle(h));
+    if (!h->hnsw || !h->hnsw->built()) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no HNSW index on this handle: build or load one first");
+    HnswState& s = *h->hnsw;
+    if (metric != s.metric) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the HNSW index was built for another metric");
+    if (ef_query > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef must be between 1 and 4096");
+    if (k == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
+    const uint32_t D = h->dim;
+    // ef = max(ef, k); beyond the rows of the graph R never fills, so min(ef, n) answers the same
+    const uint32_t ef = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(ef_query ? ef_query : s.ef_search, k), s.n);
+    const size_t lds = (size_t)ef * 24 + 64 + 256 + (size_t)D * 4;   // R: ef keys, C: 2 ef + 8 keys, 64 neighbour slots, the query
+    if (lds > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: the beam (24 bytes per ef, ef >= k) and the query do not fit in LDS");
+    const uint32_t vis_words = (uint32_t)((s.n + 31) / 32);
+    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (256ull << 20) / ((uint64_t)vis_words * 4), (256ull << 20) / ((uint64_t)k * 12), 1ull << 20}));
+    LY_TRY(ivf_grow(&s.d_q, &s.q_cap, (size_t)qc * D));
+    LY_TRY(ivf_grow(&s.d_vis, &s.vis_cap, (size_t)qc * vis_words));
+    LY_TRY(ivf_grow(&s.d_rows, &s.rows_cap, (size_t)qc * k));
+    LY_TRY(ivf_grow(&s.d_dists, &s.dists_cap, (size_t)qc * k));
+    LY_TRY(ivf_grow(&s.d_counts, &s.counts_cap, (size_t)qc * 2));   // counts, then the distances scored
+    if (!s.d_status) LY_HIP(hipMalloc(&s.d_status, 4));
+    hipStream_t st = cur(h).stream;
+    const bool timed = h->profiling.load();
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timed) { LY_HIP(hipEventCreate(&e0)); LY_HIP(hipEventCreate(&e1)); }
+    struct EvFree { hipEvent_t &a, &b; ~EvFree() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evfree{e0, e1};
+    std::vector<uint32_t> scored;
+    LY_HIP(hipMemsetAsync(s.d_status, 0, 4, st));
+    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
+        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
+        LY_HIP(hipMemcpyAsync(s.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(s.d_vis, 0, (size_t)nqc * vis_words * 4, st));
+        HnswSearchArgs a{};
+        a.V = h->rows; a.ld = h->ld; a.D = D; a.metric = metric; a.Q = s.d_q; a.k = k; a.ef = ef; a.m = s.m;
+        a.entry = s.entry; a.top_level = s.top_level; a.adj0 = s.d_adj0; a.upper_off = s.d_upper_off; a.upper_adj = s.d_upper_adj;
+        a.vis = s.d_vis; a.vis_words = vis_words; a.out_rows = s.d_rows; a.out_dists = s.d_dists; a.out_counts = s.d_counts;
+        a.out_scored = s.d_counts + qc; a.status = s.d_status;
+        if (timed) LY_HIP(hipEventRecord(e0, st));
+        LY_TRY(launch_lds<k_hnsw_search>(dim3(nqc), dim3(64), lds, st, a));
+        if (timed) LY_HIP(hipEventRecord(e1, st));
+        LY_HIP(hipMemcpyAsync(out_rows + q0 * k, s.d_rows, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(out_dists + q0 * k, s.d_dists, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(out_counts + q0, s.d_counts, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+        if (timed) {
+            scored.resize(nqc);
+            LY_HIP(hipMemcpyAsync(scored.data(), s.d_counts + qc, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+        }
+        LY_TRY(stream_wait(st));
+        if (timed) {
+            float ms = 0.0f;
+            LY_HIP(hipEventElapsedTime(&ms, e0, e1));
+            s.search_us += (double)ms * 1e3;
+            for (uint32_t v : scored) s.scored += (double)v;
+        }
+    }
+    uint32_t status = 0;
+    LY_HIP(hipMemcpy(&status, s.d_status, 4, hipMemcpyDeviceToHost));
+    if (status) return set_error(LYNSE_ERR_INTERNAL, "HNSW: the candidate set outgrew its 2 ef slots");
+    if (timed) s.searches += 1;
+    return LYNSE_OK;
+}

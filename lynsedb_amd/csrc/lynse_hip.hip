@@ -29,6 +29,7 @@
 #include "ivf.h"
 #include "pq.h"
 #include "rabitq.h"
+#include "hnsw.h"
 #include "range.h"
 #include "additive.h"
 #include "sparse.h"
@@ -250,6 +251,7 @@ struct Workspace {
 struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
 struct RbqState;  // FLAT-*-RABITQ codes + search scratch (rabitq_host.inc)
 struct RangeState;  // range search scratch (range_host.inc)
+struct HnswState;  // HNSW-* graph + search scratch (hnsw_host.inc)
 
 // One int8 copy of a shard's rows for the certified coarse pass (lynse_hip_flat::sq8 / sq8a / sq8c / sq7) with what the prep kernel needs
 // to certify a bound over it.
@@ -372,6 +374,7 @@ struct lynse_hip_flat {
     PqState* pq = nullptr;                // FLAT-{IP,L2,COS}-PQ index over the first pq->n rows (pq_host.inc); NULL = none
     RbqState* rbq = nullptr;              // FLAT-{IP,L2,COS}-RABITQ index over the first rbq->n rows (rabitq_host.inc); NULL = none
     RangeState* range = nullptr;          // scratch of lynse_hip_flat_search_range_f32 (range_host.inc); NULL until the first one
+    HnswState* hnsw = nullptr;            // HNSW-{IP,L2,COS} graph over the first hnsw->n rows (hnsw_host.inc); NULL = none
 
     std::atomic<bool> profiling{false};   // (read by searches without the lock: atomics)
     std::atomic<uint32_t> prof_rate{1};              // every prof_rate-th search records its events (lynse_hip_flat_profile_enable(h, n))
@@ -382,6 +385,7 @@ struct lynse_hip_flat {
 static void pq_release(lynse_hip_flat* h);
 static void rbq_release(lynse_hip_flat* h);
 static void range_release(lynse_hip_flat* h);
+static void hnsw_release(lynse_hip_flat* h);
 
 static inline bool is_f16(const lynse_hip_flat* h) { return h->dtype == LYNSE_DTYPE_F16; }
 // the row matrix the exact-scoring kernels read: f32 rows, or the f16 bits of an F16 shard handed in as float* with a pitch
@@ -520,6 +524,7 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     pq_release(h);
     rbq_release(h);
     range_release(h);
+    hnsw_release(h);
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
@@ -3801,6 +3806,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "ivf_async.inc"
 #include "pq_host.inc"
 #include "rabitq_host.inc"
+#include "hnsw_host.inc"
 #include "range_host.inc"
 #include "additive_host.inc"
 #include "sparse_host.inc"
