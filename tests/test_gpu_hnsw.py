@@ -7,6 +7,7 @@ import pytest
 
 import hnsw_common as H
 import oracle as O
+from hnsw_common import assert_same_graph, check, combos_for, load, make_data, sweep
 
 pytestmark = pytest.mark.gpu
 IP, L2, COS = O.IP, O.L2, O.COS
@@ -26,56 +27,6 @@ def L():
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory, oracle):
     return H.build_ref(tmp_path_factory.mktemp("hnsw_ref"), oracle)
-
-
-# ------------------------------------------------------------------------------------------- data ----
-def make_data(kind, rng, n, dim, nq):
-    if kind == "gauss":
-        return rng.standard_normal((n, dim)).astype(f32), rng.standard_normal((nq, dim)).astype(f32)
-    if kind == "int":   # integer-valued rows: exact ties and exact zeros
-        return rng.integers(-3, 4, (n, dim)).astype(f32), rng.integers(-3, 4, (nq, dim)).astype(f32)
-    if kind == "dup":   # rows drawn from 40 distinct vectors: ties everywhere
-        base = rng.standard_normal((40, dim)).astype(f32)
-        return base[rng.integers(0, 40, n)], base[rng.integers(0, 40, nq)]
-    assert kind == "nonfinite"
-    data, q = rng.standard_normal((n, dim)).astype(f32), rng.standard_normal((nq, dim)).astype(f32)
-    for a in (data, q):
-        r = a.shape[0]
-        a[rng.integers(0, r, max(1, r // 7)), rng.integers(0, dim, max(1, r // 7))] = np.nan
-        a[rng.integers(0, r, max(1, r // 9)), rng.integers(0, dim, max(1, r // 9))] = np.inf
-        a[rng.integers(0, r, max(1, r // 9)), rng.integers(0, dim, max(1, r // 9))] = -np.inf
-    return data, q
-
-
-def load(idx, g, metric, ef_search=50):
-    idx.load_hnsw(metric, g.m, ef_search, g.levels, g.adj0, g.upper_node, g.upper_level, g.upper_adj, g.entry)
-
-
-def check(got, exp, k, metric, what):
-    rows, dists, counts = got
-    worst = -np.inf if metric == IP else np.inf
-    for qi, (e_rows, e_d) in enumerate(exp):
-        c = int(counts[qi])
-        assert c == e_rows.size, (what, qi, c, e_rows.size)
-        assert np.array_equal(rows[qi, :c], e_rows), (what, qi, rows[qi, :c], e_rows)
-        assert np.array_equal(dists[qi, :c].view(np.uint32), e_d.view(np.uint32)), (what, qi, dists[qi, :c], e_d)
-        assert (rows[qi, c:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all() and (dists[qi, c:] == worst).all(), (what, qi)
-
-
-def sweep(idx, ref, data, g, metric, queries, combos, ef_search=50):
-    """combos: (k, ef_query, nq); ef_query 0 = the index's ef_search"""
-    load(idx, g, metric, ef_search)
-    n = data.shape[0]
-    for k, efq, nq in combos:
-        q = queries[np.arange(nq) % queries.shape[0]]
-        ef = max(efq if efq else ef_search, k)
-        exp = H.ref_search(ref, data[:n], metric, g, q, k, ef)
-        check(idx.search_hnsw_batch_arrays(q, k, metric, efq), exp, k, metric, (NAME[metric], n, g.m, k, efq, nq))
-
-
-def combos_for(n):
-    """k in {1, 10, ef, N + 3}, ef in {k, 50 (the index's), N + 5}, nq in {1, 5, 300}"""
-    return [(1, 1, 5), (10, 10, 300), (10, 0, 5), (50, 0, 1), (n + 3, n + 3, 5), (10, n + 5, 5), (n + 3, n + 5, 1), (n + 5, n + 5, 5), (1, n + 5, 1)]
 
 
 # -------------------------------------------------------------------- search over loaded graphs ----
@@ -152,16 +103,6 @@ def test_graph_covers_the_first_rows_only(L, ref):
 
 
 # ------------------------------------------------------------------------------------------ build ----
-def assert_same_graph(p, g, what):
-    assert np.array_equal(p["levels"], g.levels), what
-    assert p["entry"] == g.entry and p["top_level"] == int(g.levels.max()), what
-    assert np.array_equal(p["upper_node"], g.upper_node) and np.array_equal(p["upper_level"], g.upper_level), what
-    bad = np.nonzero((p["adj0"] != g.adj0).any(axis=1))[0]
-    assert bad.size == 0, (what, "level 0", bad[:5], p["adj0"][bad[:2]], g.adj0[bad[:2]])
-    bad = np.nonzero((p["upper_adj"] != g.upper_adj).any(axis=1))[0]
-    assert bad.size == 0, (what, "upper", bad[:5])
-
-
 @pytest.mark.parametrize("n,dim,m,efc,kind", [(1, 8, 2, 8, "gauss"), (17, 24, 4, 128, "gauss"), (17, 8, 16, 8, "dup"), (600, 24, 4, 8, "gauss"),
                                               (600, 100, 16, 128, "gauss"), (600, 8, 2, 128, "dup"), (600, 24, 2, 8, "int"),
                                               (1500, 24, 16, 8, "dup"), (1500, 100, 4, 128, "gauss")])

@@ -184,3 +184,58 @@ def test_ref_recall_on_clustered_data(ref, oracle):
     recall = hit / (10 * queries.shape[0])
     print(f"restatement recall@10 = {recall:.4f}, distances scored per query = {np.mean(scored):.0f}, levels = {int(g.levels.max()) + 1}")
     assert recall >= 0.90
+
+
+# ---- the designed cases of the limits tests: the restatement against answers derived by hand ------------------------------------------
+def beam_model(x, lists0, ef, k, drop_ties=False):
+    """The level-0 walk with the kernel's bounded candidate set, for the 1-D cases (L2, query 0, entry 0): C has 2 ef + 8 slots; before a
+    scoring step of 8 that might not fit, the entries beyond worst.dist are dropped.  drop_ties: the faulty comparison (`<` for `<=`)."""
+    d = [float(f32(v) * f32(v)) for v in x]
+    R, C, seen = [(d[0], 0)], [(d[0], 0)], {0}
+    while C:
+        c = min(C)
+        C.remove(c)
+        if len(R) >= ef and c[0] > max(R)[0]:
+            break
+        fresh = [j for j in lists0.get(c[1], []) if j not in seen]
+        seen.update(fresh)
+        for b in range(0, len(fresh), 8):
+            if len(C) + 8 > 2 * ef + 8:
+                w = max(R)[0]
+                C = [e for e in C if (e[0] < w if drop_ties else e[0] <= w)]
+            for j in fresh[b:b + 8]:
+                if len(R) < ef or d[j] < max(R)[0]:
+                    C.append((d[j], j))
+                    R.append((d[j], j))
+                    if len(R) > ef:
+                        R.remove(max(R))
+    return [j for _, j in sorted(R)[:k]]
+
+
+def test_tie_bridge_needs_the_ties_kept():
+    """the case discriminates: the bounded set that keeps ties at worst.dist finds row 10 through row 6, the one that drops them does not"""
+    c = H.tie_bridge()
+    lists0 = {0: list(range(1, 10)), 6: [10]}
+    assert beam_model(c.data[:, 0], lists0, 3, 3) == [10, 8, 7] == c.rows.tolist()
+    assert beam_model(c.data[:, 0], lists0, 3, 3, drop_ties=True) == [8, 7, 4]
+
+
+@pytest.mark.parametrize("case", H.designed_cases(), ids=lambda c: c.name)
+def test_ref_designed_cases(ref, case):
+    """rows, distance bits and the distances scored, each written out by hand in tests/hnsw_common.py"""
+    sc = []
+    (rows, d), = H.ref_search(ref, case.data, O.L2, case.g, case.query, case.k, case.ef, scored=sc)
+    assert rows.tolist() == case.rows.tolist(), (case.name, rows, case.rows)
+    assert np.array_equal(d.view(np.uint32), case.dists.view(np.uint32)), (case.name, d, case.dists)
+    assert sc == [case.scored], (case.name, sc, case.scored)
+
+
+def test_ref_nan_query_ties_everything(ref):
+    """a NaN query: every distance is +inf at once (ip: reported as -inf), so the walk is the all-ties walk whatever the rows"""
+    data = np.random.default_rng(3).standard_normal((600, 8)).astype(f32)
+    q = np.full((1, 8), np.nan, f32)
+    for metric, far in ((O.IP, -np.inf), (O.L2, np.inf), (O.COS, np.inf)):
+        for k, ef in H.ALL_TIES:
+            sc = []
+            (rows, d), = H.ref_search(ref, data, metric, H.path_graph(600), q, k, ef, scored=sc)
+            assert rows.tolist() == list(range(k)) and (d == far).all() and sc == [ef + 1], (metric, k, ef, rows, d, sc)
