@@ -38,7 +38,7 @@ bool ivf_async_shape_ok(lynse_hip_ivf* h, uint32_t nq, uint32_t nprobe) {
     const uint32_t np_eff = std::min<uint32_t>(nprobe, h->nlist);
     const uint32_t pass_lists = std::max<uint32_t>(1, w.cap / 16);
     const uint64_t win_bound = (uint64_t)nq * (h->worst_rows[np_eff] / (uint32_t)SCAN_BR + 2ull * np_eff) + 16;
-    return dg_env && !h->binary && scan_variant() == 3 && np_eff < h->nlist && np_eff <= pass_lists && (uint64_t)nq * np_eff <= IVF_GROUP_MAX_PAIRS &&
+    return dg_env && !h->binary && np_eff < h->nlist && np_eff <= pass_lists && (uint64_t)nq * np_eff <= IVF_GROUP_MAX_PAIRS &&
            h->nlist <= IVF_GROUP_MAX_LISTS && win_bound * 3 * sizeof(IvfTile) <= (512ull << 20);
 }
 

@@ -5,7 +5,7 @@
 // IvfFlatMmap one: rows physically reordered into contiguous per-partition slabs
 // (ivf_flat_mmap.rs:115-130) + partition offsets + original row ids; centroids in a small matrix.
 // Search: k_ivf_route ranks centroids (exact, reference order) -> the host groups the (query, list)
-// probes by list -> k_scan_glds in work-list mode scans each probed slab ONCE per query group
+// probes by list -> k_scan_h16 in work-list mode scans each probed slab ONCE per query group
 // (a slab shared by several queries of the batch is not re-read per query) in three position
 // windows with the same threshold / select / exact-rescore machinery as FLAT -> k_final maps slab
 // positions to original rows and orders by (distance, original row).
@@ -590,7 +590,6 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
     LY_HIP(hipMalloc(&d_c, AQ * 4)); guard.bufs.push_back(d_c);
     std::vector<uint64_t> hrows(AQ);
     float* d_q2 = nullptr;          // the undecided rows of an assignment call, gathered (allocated on first use)
-    uint64_t assign_redo = 0;       // rows answered by the exact search so far (diagnostics)
 
     auto assign = [&](std::vector<uint32_t>& out) -> int {  // assign_metric (kmeans.rs:237-264)
         if (guard.cen) { lynse_hip_flat_destroy(guard.cen); guard.cen = nullptr; }
@@ -639,15 +638,12 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
                     for (uint32_t i = 0; i < nredo; ++i) hids[hredo[i]] = (uint32_t)hrows[i];
                 }
                 for (uint64_t i = 0; i < nr; ++i) out[r0 + i] = hids[i];
-                assign_redo += nredo;
                 continue;
             }
             LY_TRY(lynse_hip_flat_search_f32_device(guard.cen, d_q, nr, 1, metric, d_r, d_d, d_c, nullptr));
             LY_HIP(hipMemcpy(hrows.data(), d_r, nr * 8, hipMemcpyDeviceToHost));
             for (uint64_t i = 0; i < nr; ++i) out[r0 + i] = (uint32_t)hrows[i];
         }
-        if (env_str("LYNSE_HIP_ASSIGN_DBG")) fprintf(stderr, "[lynse] assignment pass: %llu rows, fast path %d, %llu rows through the exact search so far\n",
-                                                    (unsigned long long)n, fast ? 1 : 0, (unsigned long long)assign_redo);
         return LYNSE_OK;
     };
 
@@ -1126,18 +1122,8 @@ static int ivf_grow(T** p, size_t* cap, size_t need) {
     return LYNSE_OK;
 }
 
-static int launch_scan_tiled(const ScanArgs& a, int metric, bool scale, uint32_t grid, hipStream_t st) {
-    if (scan_variant() == 3) return launch_scan_h16<with(F16_SMALL, &H16Cfg::tiled, true)>(a, metric, grid, st);
-#ifdef LYNSE_EXPERIMENTS
-    const size_t lds = (size_t)4 * (SCAN_BR * GL_BK * 4 + 32 * GL_BK * 2) + 4 * 1024;
-    auto go = [&](auto s) {
-        return with_metric(metric, [&](auto m) { return launch_lds<k_scan_glds<1, 4, 1, 1, decltype(m)::value, decltype(s)::value, 4, 2, true>>(grid, 256, lds, st, a); });
-    };
-    return scale ? go(std::true_type{}) : go(std::false_type{});
-#else
-    (void)scale;
-    return set_error(LYNSE_ERR_UNSUPPORTED, "superseded scan variants need make EXPERIMENTS=1");
-#endif
+static int launch_scan_tiled(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
+    return launch_scan_h16<with(F16_SMALL, &H16Cfg::tiled, true)>(a, metric, grid, st);
 }
 
 // The probed lists of nq queries staged in the workspace (w.Qf): probes[q * np_eff + r] = the r-th list of query q.
@@ -1166,7 +1152,7 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
     if (np_eff >= h->nlist) {
         for (uint32_t q = 0; q < nq; ++q)
             for (uint32_t c = 0; c < h->nlist; ++c) probes[(size_t)q * np_eff + c] = c;  // ivf_flat_mmap.rs:390-392
-    } else if (!heuristic && scan_variant() == 3) {
+    } else if (!heuristic) {
         // ---- exact ranking of all centroids (ivf.rs:227-249) = the (score, centroid id) top-nprobe of a FLAT search
         // over the centroid matrix: MFMA coarse pass + exact rescoring instead of nlist sequential scores per query
         if ((size_t)nq * np_eff > scr.route_cap) {
@@ -1252,7 +1238,6 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
     IvfScratch& scr = iscr(h);
     const bool binary = h->binary;
     const int route_metric = binary ? M_L2 : metric;  // routing_metric (ivf.rs:77-87)
-    const bool h16 = scan_variant() == 3;
     const uint32_t D = h->dim;
 
     // ---- a few queries (single-query latency is the reference's usual IVF call): TWO launches, no host round trip —
@@ -1263,7 +1248,7 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
     {
         const uint32_t np_f = std::min<uint32_t>(nprobe, h->nlist);
         const bool heuristic_f = h->ivfflat_routing && metric == M_IP && D >= 64 && h->nlist >= 64 && !h->rdims.empty();
-        if (fused_env() && !s->no_fused && !binary && !smask && !safe && h16 && nq <= (uint32_t)SMALL_MAX_Q && k <= (uint32_t)SMALL_MAX_K &&
+        if (fused_env() && !s->no_fused && !binary && !smask && !safe && nq <= (uint32_t)SMALL_MAX_Q && k <= (uint32_t)SMALL_MAX_K &&
             np_f < h->nlist && np_f <= (uint32_t)SMALL_MAX_K && !heuristic_f && s->dtype == LYNSE_DTYPE_F32 &&
             // (the probed lists are scored exactly from the f32 slab: at most the np_f largest lists — 1 GB is ~0.3 ms of this kernel;
             // the bound used to be max_list_len x nprobe <= 256 MB, which uneven k-means lists exceed long before the rows do)
@@ -1364,9 +1349,8 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     const int metric = h->search_metric >= 0 ? h->search_metric : h->metric;
     const bool binary = h->binary;
     const int route_metric = binary ? M_L2 : metric;
-    const bool h16 = scan_variant() == 3;
     IvfScratch& scr = iscr(h);
-    const uint32_t SK = i8c ? 128u : (h16 ? (uint32_t)HK : (uint32_t)GL_BK);  // K elements per slab of the scan kernel in use
+    const uint32_t SK = i8c ? 128u : (uint32_t)HK;  // K elements per slab of the scan kernel in use
     // squared L2 / cosine on the int8 pass: inner products of augmented resp. unit vectors in the NEGATED score space
     // (I8cPrepArgs::aug / ::cosine, kernels.h) — scan and select run as IP, the exact rescoring negates, k_final negates back
     const I8cForm form = i8c_form(s, metric, 0, false);   // (nqc = 0: never the plain-code L2 form, a FLAT tiling)
@@ -1403,7 +1387,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         // ---- queries: device copy + prep (image layout 1, thresholds, margins)
         LY_HIP(hipMemsetAsync(w.Q16, 0, (size_t)nslab * qpad * SK * sizeof(_Float16), st));
         PrepArgs p{};
-        p.Q = w.Qf; p.D = D; p.nq = nq; p.qpad = qpad; p.nslab = nslab; p.metric = metric; p.layout = h16 ? 2 : 1;
+        p.Q = w.Qf; p.D = D; p.nq = nq; p.qpad = qpad; p.nslab = nslab; p.metric = metric; p.layout = 2;
         p.sv = s->sv; p.vmax = s->vmax; p.vmin = s->vmin; p.cos_degenerate = s->cos_degenerate;
         p.Q16 = w.Q16; p.qinv = w.qinv; p.qn2 = w.qn2; p.qrinv = w.qrinv; p.marg2 = w.marg2; p.thr = w.thr;
         p.count = w.count; p.overflow = w.overflow;
@@ -1421,7 +1405,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     const int dg_env = ivf_device_grouping();
     const uint32_t pass_lists = std::max<uint32_t>(1, w.cap / 16);
     const uint64_t win_bound = (uint64_t)nq * (h->worst_rows[std::min<uint32_t>(np_eff, h->nlist)] / tile_rows + 2ull * np_eff) + 16;
-    const bool dev_group = dg_env && !force_host && !binary && !smask && !list_matches && !safe && h16 && np_eff < h->nlist && np_eff <= pass_lists &&
+    const bool dev_group = dg_env && !force_host && !binary && !smask && !list_matches && !safe && np_eff < h->nlist && np_eff <= pass_lists &&
                            (uint64_t)nq * np_eff <= IVF_GROUP_MAX_PAIRS && h->nlist <= IVF_GROUP_MAX_LISTS && win_bound * 3 * sizeof(IvfTile) <= (512ull << 20);
     if (as && !dev_group) return set_error(LYNSE_ERR_INTERNAL, "a search in flight needs the device-side grouping");   // (ivf_async_shape_ok said yes)
     std::vector<uint32_t> probes;
@@ -1478,7 +1462,6 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     std::vector<size_t> scan_ev;
     uint64_t host_tile_rows = 0;
     size_t ev_next = 0;
-    uint32_t win_no = 0;
     auto run_window = [&](const IvfTile* d_win_tiles, uint32_t ntiles_host, const uint32_t* ntiles_dev) -> int {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) {
@@ -1510,7 +1493,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
             a.V16 = reinterpret_cast<const _Float16*>(opd.codes); a.ld16 = opd.ld;
             LY_TRY((launch_h16<with(I8C_SMALL, &H16Cfg::tiled, true)>(grid, st, a)));
         } else
-        LY_TRY(launch_scan_tiled(a, metric, s->sv != 1.0f, grid, st));
+        LY_TRY(launch_scan_tiled(a, metric, grid, st));
         }
         if (timed) LY_HIP(hipEventRecord(e1, st));
         SelectArgs sa{};
@@ -1519,8 +1502,6 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         sa.neg_metric1 = (aug || cosq) ? metric + 1 : 0;
         sa.exact = binary ? 1 : 0; sa.tighten = binary ? 0 : 1; sa.emit_all_n = -1; sa.keep_ties = 1; sa.Qf = w.Qf; sa.V = s->rows; sa.ld = s->ld; sa.D = D;
         sa.lds_bytes = sel_lds_bytes(w.cap, nq);
-        if (sel_stamps_on() && nq <= 256)   // debugging: phase stamps of the select behind window win_no (lynse_hip_debug_ivf_sel_stamps)
-            sa.stamps = reinterpret_cast<unsigned long long*>(w.gsync + 64) + (size_t)(win_no++ & 3) * 256 * 8;
         hipLaunchKernelGGL(k_select<SEL_NT>, dim3(nq), dim3(SEL_NT), sa.lds_bytes, st, sa);
         LY_HIP(hipGetLastError());
         return LYNSE_OK;
@@ -1852,8 +1833,6 @@ static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq
         LY_TRY(ensure_workspace(s, 1));
         return ivf_search_large_k(h, queries, nq, k, kk, nprobe, out_rows, out_dists, out_counts, on_device, filtered ? &allowed : nullptr);
     }
-    if (filtered && scan_variant() != 3 && !h->binary)
-        return set_error(LYNSE_ERR_UNSUPPORTED, "filtered IVF search needs the default scan kernel");
     LY_TRY(finalize_locked(s)); LY_TRY(ensure_shadow_locked(s));   // (the slab scans read the f16 shadow unless a batch takes the int8 pass; built once)
     LY_TRY(ensure_workspace(s, k));
     const uint32_t* smask = nullptr;
@@ -2029,13 +2008,6 @@ extern "C" int lynse_hip_ivf_profile_enable(lynse_hip_ivf* h, int on) {
     if (!h->store) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     return lynse_hip_flat_profile_enable(h->store, on);
 }
-extern "C" int lynse_hip_debug_ivf_sel_stamps(lynse_hip_ivf* h, unsigned long long* out /* [4][256][8] */) {   // development (not in the header)
-    if (!h) return 1;
-    IVF_GUARD(h);
-    if (!h->store) return 1;
-    return lynse_hip_debug_sel_stamps(h->store, out);
-}
-
 extern "C" int lynse_hip_ivf_profile_get(lynse_hip_ivf* h, lynse_hip_profile* out, int reset) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     IVF_GUARD(h);

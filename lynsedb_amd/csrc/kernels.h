@@ -4,7 +4,6 @@
 //   k_prep_queries        per-query scale / norms / certified error margin, f16 query image
 //   k_scan_h16            THE HOT KERNEL (default): the f16 shadow rows streamed once from HBM by LDS-DMA, Q·Vᵀ on
 //                         MFMA 32x32x16 f16, threshold-filter epilogue appending (score,row) keys per query
-//   k_scan_glds / _f16    its predecessors over the f32 rows (LDS-DMA ring / register-staged), kept as A/B references
 //   k_scan_binary_rows    packed-binary rows: lane-per-row xor/and + popcount with scalar query words (exact ints);
 //   k_scan_binary         the 8-lanes-per-row predecessor
 //   k_select              per query: radix-select the k-th best candidate key in LDS, new threshold, prune
@@ -368,7 +367,7 @@ __global__ void __launch_bounds__(256) k_pack_bits(const T* __restrict__ V, uint
 struct PrepArgs {
     const float* Q;      // nq x D f32
     uint32_t D, nq, qpad, nslab;
-    int layout;          // 0: [slab64][q][72] (k_scan_f16)   1: [slab32][q][4 slots ^ ((q>>2)&3)][8] (k_scan_glds)   2: [slab64][q][8 slots ^ ((q>>1)&7)][8] (k_scan_h16)
+    int layout;          // 2: [slab64][q][8 slots ^ ((q>>1)&7)][8] (k_scan_h16, what the host passes)   0: [slab64][q][72]   1: [slab32][q][4 slots ^ ((q>>2)&3)][8] (the superseded f32-row scans)
     int metric;
     float sv;            // row scale (power of two)
     float vmax, vmin;    // max / min-nonzero row norm
@@ -500,20 +499,10 @@ __global__ void __launch_bounds__(256) k_prep_queries(PrepArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_scan_f16 — the hot kernel.
-//
-// Tile: BR=128 rows x BQ queries (256: 8 waves as 4(q) x 2(r), each 64x64; 32: 4 waves as 1 x 4,
-// each 32x32).  Persistent blocks walk row tiles; for each K slab of 64:
-//   HBM  -> VGPR : 16 consecutive lanes read one row's 256 contiguous bytes (float4 each)
-//   VGPR -> LDS  : scale (power of two), cvt f32->f16 (RNE), ds_write_b64, row stride 144 B
-//   L2   -> LDS  : the pre-built f16 query slab image, linear 16-B copies
-//   LDS  -> MFMA : ds_read_b128 fragments (stride 144 B is conflict-free), v_mfma_f32_32x32x16_f16,
-//                  A = rows (M), B = queries (N) so that each lane owns ONE query column per block
-// LDS is double buffered with register prefetch of the next slab (also across tile boundaries), one
-// barrier per slab.  Epilogue: score transform (IP / L2 via norms / cosine via reciprocal norms),
-// compare with the per-query threshold, append passing (score,row) keys with a global atomic slot
-// (stage 0: slot = row, no atomics).  Every row byte is read from HBM exactly once per batch.
-// Algorithmic bytes per launch = rows * D * 4.
+// ScanArgs — the arguments of the MFMA scan kernels (k_scan_h16 below, k_scan_qs, k_scan_qh).
+// Persistent blocks walk row tiles; A = rows (M), B = queries (N), so that each lane owns ONE query column per block.
+// Epilogue: score transform (IP / L2 via norms / cosine via reciprocal norms), compare with the per-query threshold, append
+// passing (score,row) keys (stage 0: slot = row, no atomics).  Every row byte is read from HBM exactly once per batch.
 // ------------------------------------------------------------------------------------------------
 struct ScanArgs {
     const float* V;
@@ -548,7 +537,7 @@ struct ScanArgs {
     uint32_t cap;
     int emit_all;
     int dense;        // host-side dispatch only: this threshold stage expects many survivors per block -> the DENSE epilogue
-    int debug_flags;  // timing experiments only: 1 = linear (blocked-layout-like) row addressing, 2 = no emission
+    int debug_flags;  // development stamps (bit 6: the sample stage and k_scan_qh; bit 7: the fused sample stage); the host leaves it 0
     // work-list mode (IVF slabs): tile t covers rows [tiles[t].row0, +nrows) for the query group whose
     // f16 image starts at Q16 + qimg_off halves; local query n of the group is query pair_q[pair0+n]
     const struct IvfTile* tiles;
@@ -584,541 +573,12 @@ struct IvfTile {
     uint32_t pair0, nq;
 };
 
-#ifdef LYNSE_EXPERIMENTS  // the register-staged predecessor (A/B reference only: make EXPERIMENTS=1)
-template <int WQ, int WR, int TQ, int TR, int METRIC, int PD>
-__global__ void __launch_bounds__(WQ * WR * 64, 2) k_scan_f16(ScanArgs a) {
-    constexpr int NT = WQ * WR * 64;
-    constexpr int BQ = WQ * TQ * 32;
-    constexpr int BR = WR * TR * 32;
-    static_assert(BR == SCAN_BR, "tile rows");
-    static_assert(PD == 1 || PD == 2, "prefetch depth");
-    constexpr int ROWS_PER_PASS = NT / 16;
-    constexpr int PV = BR / ROWS_PER_PASS;             // float4 loads per thread per slab
-    constexpr int QCHUNKS = BQ * (SCAN_LDK * 2 / 16);  // 16-B chunks of one Q slab image
-    constexpr int PQ = (QCHUNKS + NT - 1) / NT;
-    constexpr int VBUF = BR * SCAN_LDK;  // halves per V buffer
-    constexpr int QBUF = BQ * SCAN_LDK;
-    constexpr bool ASC = METRIC != M_IP;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* Vl = reinterpret_cast<_Float16*>(smem);             // [2][VBUF]
-    _Float16* Ql = reinterpret_cast<_Float16*>(smem) + 2 * VBUF;  // [2][QBUF]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wq = wave % WQ, wr = wave / WQ;
-    const int vrow = tid >> 4, vk = (tid & 15) * 4;
-
-    if (blockIdx.x >= a.ntiles) return;
-
-    // Register staging: vA / vB hold the f32 row pieces of the next one (PD=1) or two (PD=2) K slabs
-    // while they are in flight from HBM; qreg holds the next f16 query slab (L2-resident).
-    f32x4 vA[PV], vB[PV];
-    u32x4 qreg[PQ];
-
-    // Branch-free loads (a divergent branch around a load makes hipcc drain vmcnt(0) and kills the
-    // prefetch pipeline): rows past the stage end are clamped to the last row (their scores are
-    // masked in the epilogue), columns past ld are clamped here and zeroed in store_v.
-    const uint32_t last_row = a.row1 - 1;
-    auto load_v = [&](f32x4(&v)[PV], uint32_t t, uint32_t s) {
-        const uint32_t rbase = a.row0 + t * BR;
-        uint32_t k = s * SCAN_BK + vk;
-        k = k < a.ld ? k : a.ld - 4;
-#pragma unroll
-        for (int p = 0; p < PV; ++p) {
-            uint32_t row = rbase + p * ROWS_PER_PASS + vrow;
-            row = row < last_row ? row : last_row;
-            v[p] = *reinterpret_cast<const f32x4*>(a.V + (size_t)row * a.ld + k);
-        }
-    };
-    auto load_q = [&](uint32_t s) {
-        const u32x4* qsrc = reinterpret_cast<const u32x4*>(a.Q16 + (size_t)s * a.qpad * SCAN_LDK);
-#pragma unroll
-        for (int j = 0; j < PQ; ++j) {
-            const int c = tid + j * NT;
-            qreg[j] = qsrc[c < QCHUNKS ? c : QCHUNKS - 1];  // unconditional: keeps qreg in VGPRs
-        }
-    };
-    auto store_v = [&](const f32x4(&v)[PV], int buf, uint32_t s) {
-        _Float16* vb = Vl + buf * VBUF;
-        const float scale = (s * SCAN_BK + vk < a.ld) ? a.sv : 0.0f;  // zero the K padding of the last slab
-        const bool kin = s * SCAN_BK + vk < a.ld;
-#pragma unroll
-        for (int p = 0; p < PV; ++p) {
-            half4 h;
-            h[0] = kin ? (_Float16)(v[p][0] * scale) : (_Float16)0.0f;
-            h[1] = kin ? (_Float16)(v[p][1] * scale) : (_Float16)0.0f;
-            h[2] = kin ? (_Float16)(v[p][2] * scale) : (_Float16)0.0f;
-            h[3] = kin ? (_Float16)(v[p][3] * scale) : (_Float16)0.0f;
-            *reinterpret_cast<half4*>(vb + (p * ROWS_PER_PASS + vrow) * SCAN_LDK + vk) = h;
-        }
-    };
-    auto store_q = [&](int buf) {
-        u32x4* qb = reinterpret_cast<u32x4*>(Ql + buf * QBUF);
-#pragma unroll
-        for (int j = 0; j < PQ; ++j) {
-            const int c = tid + j * NT;
-            if (c < QCHUNKS) qb[c] = qreg[j];
-        }
-    };
-
-    f32x16 acc[TR][TQ];
-#pragma unroll
-    for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TQ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    const int frag_k = (lane >> 5) * 8;
-    const int a_row = wr * (TR * 32) + (lane & 31);
-    const int b_row = wq * (TQ * 32) + (lane & 31);
-
-    auto compute = [&](int buf) {
-        const _Float16* vb = Vl + buf * VBUF;
-        const _Float16* qb = Ql + buf * QBUF;
-#pragma unroll
-        for (int kk = 0; kk < SCAN_BK / 16; ++kk) {
-            half8 af[TR], bf[TQ];
-#pragma unroll
-            for (int i = 0; i < TR; ++i)
-                af[i] = *reinterpret_cast<const half8*>(vb + (a_row + i * 32) * SCAN_LDK + kk * 16 + frag_k);
-#pragma unroll
-            for (int j = 0; j < TQ; ++j)
-                bf[j] = *reinterpret_cast<const half8*>(qb + (b_row + j * 32) * SCAN_LDK + kk * 16 + frag_k);
-#pragma unroll
-            for (int i = 0; i < TR; ++i)
-#pragma unroll
-                for (int j = 0; j < TQ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    // epilogue for one finished tile: C[row m][query n]; a lane owns column n = lane&31 of each block
-    auto epilogue = [&](uint32_t tile) {
-        const uint32_t rbase = a.row0 + tile * BR;
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) {
-            const uint32_t n = wq * (TQ * 32) + j * 32 + (lane & 31);
-            const bool qok = n < a.nq;
-            const float qinv = qok ? a.qinv[n] : 0.0f;
-            const float thr = qok ? a.thr[n] : 0.0f;
-            float qextra = 0.0f;
-            if (METRIC == M_L2) qextra = qok ? a.qn2[n] : 0.0f;
-            if (METRIC == M_COS) qextra = qok ? a.qrinv[n] : 0.0f;
-#pragma unroll
-            for (int i = 0; i < TR; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const uint32_t m = rbase + wr * (TR * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    const bool rok = m < a.row1;
-                    float sc = acc[i][j][r] * qinv;
-                    if (METRIC == M_L2) sc = (rok ? a.vn2[m] : 0.0f) - 2.0f * sc + qextra;
-                    if (METRIC == M_COS) sc = 1.0f - sc * (rok ? a.vrinv[m] : 0.0f) * qextra;
-                    acc[i][j][r] = 0.0f;
-                    const bool pass = ASC ? (sc <= thr) : (sc >= thr);
-                    if (qok && rok && (a.emit_all || pass)) {
-                        const uint32_t slot = a.emit_all ? (m - a.row0) : atomicAdd(&a.count[n], 1u);
-                        if (slot < a.cap) a.cand[(size_t)n * a.cap + slot] = make_key(sc, m, ASC);
-                    }
-                }
-            }
-        }
-    };
-
-    // Flat sequence of (tile, slab) steps of this persistent block; the pipeline runs across tile
-    // boundaries.  cur = step being computed, n1 / n2 = the next two steps.
-    uint32_t cur_t = blockIdx.x, cur_s = 0;
-    uint32_t n1_t = cur_t, n1_s = 1;
-    if (n1_s == a.nslab) { n1_s = 0; n1_t += gridDim.x; }
-    uint32_t n2_t = n1_t, n2_s = n1_s + 1;
-    if (n2_s == a.nslab) { n2_s = 0; n2_t += gridDim.x; }
-
-    load_v(vA, cur_t, cur_s);
-    load_q(cur_s);
-    store_v(vA, 0, cur_s);
-    store_q(0);
-    if (PD == 2 && n1_t < a.ntiles) load_v(vB, n1_t, n1_s);
-    __syncthreads();
-    int buf = 0;
-
-    // X: registers whose slab goes to LDS at the end of this iteration; Y: registers free to receive
-    // the slab two steps ahead (PD=2).  With PD=1, X is loaded and stored within the iteration.
-    auto iteration = [&](f32x4(&X)[PV], f32x4(&Y)[PV]) {
-        const bool v1 = n1_t < a.ntiles, v2 = n2_t < a.ntiles;
-        if (v1) load_q(n1_s);
-        if (PD == 2) {
-            if (v2) load_v(Y, n2_t, n2_s);
-        } else {
-            if (v1) load_v(X, n1_t, n1_s);
-        }
-        compute(buf);
-        if (v1) {
-            store_v(X, buf ^ 1, n1_s);
-            store_q(buf ^ 1);
-        }
-        __syncthreads();
-        buf ^= 1;
-        if (cur_s == a.nslab - 1) epilogue(cur_t);
-        cur_t = n1_t; cur_s = n1_s;
-        n1_t = n2_t; n1_s = n2_s;
-        n2_s += 1;
-        if (n2_s == a.nslab) { n2_s = 0; n2_t += gridDim.x; }
-    };
-    while (true) {
-        if (PD == 2) iteration(vB, vA); else iteration(vA, vA);
-        if (cur_t >= a.ntiles) break;
-        iteration(vA, vB);
-        if (cur_t >= a.ntiles) break;
-    }
-}
-
-#endif  // LYNSE_EXPERIMENTS
-// ------------------------------------------------------------------------------------------------
-// k_scan_glds — the hot kernel, LDS-DMA edition (default).
-//
-// Same tile / MFMA / epilogue structure as k_scan_f16, but every operand byte travels HBM/L2 -> LDS
-// with `global_load_lds_dwordx4` (no VGPR staging), through a 4-stage LDS ring of K=32 slabs, so up
-// to three slabs (48 KB of rows + 48 KB of query image per CU) are in flight while one is computed:
-//   per slab and wave: VPW + QPW LDS-DMA instructions (1 KiB each) -> s_waitcnt vmcnt((NS-2)*OPS)
-//   -> ONE raw s_barrier -> issue slab g+3 into the stage that was computed last -> MFMA on slab g.
-// Rows sit in LDS as f32 (the DMA cannot convert): the A fragment is two ds_read_b128 + cvt to f16 in
-// registers.  Bank conflicts are removed by an XOR swizzle of the 16-B slot index applied on the
-// per-lane SOURCE address (the DMA destination is lane-linear): rows use slot ^ ((row>>1)&7), the
-// query image is stored pre-swizzled in global memory (slot ^ ((q>>2)&3)) by k_prep_queries.
-// Out-of-range rows / K columns are clamped to valid addresses: clamped rows are masked in the
-// epilogue, clamped columns meet zeros in the query image.
-// ------------------------------------------------------------------------------------------------
-constexpr int GL_BK = 32;   // K elements per slab
-constexpr int GL_NS = 4;    // ring stages
-
+// 16 bytes per lane HBM / L2 -> LDS without VGPR staging (`global_load_lds_dwordx4`); the destination is lane-linear
 template <int AUX>
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, AUX);
 }
-
-#ifdef LYNSE_EXPERIMENTS  // the f32-row LDS-DMA predecessor of k_scan_h16 (A/B reference only: make EXPERIMENTS=1)
-// NS ring stages; NT_HINT = 2 marks the row stream non-temporal (each row byte is read once per
-// batch by exactly one CU), the query image keeps the default policy (re-read by every CU from L2).
-// TILED = work-list mode for IVF slabs (tile descriptors + per-group query images).
-template <int WQ, int WR, int TQ, int TR, int METRIC, bool SCALE, int NS, int NT_HINT, bool TILED = false>
-__global__ void __launch_bounds__(WQ * WR * 64, (WQ * WR >= 8) ? (WQ * WR / 4) : 2) k_scan_glds(ScanArgs a) {
-    constexpr int NW = WQ * WR;
-    constexpr int BQ = WQ * TQ * 32;
-    constexpr int BR = WR * TR * 32;
-    static_assert(NS >= 3, "ring depth");
-    constexpr int V_BYTES = BR * GL_BK * 4;   // f32 rows per stage
-    constexpr int Q_BYTES = BQ * GL_BK * 2;   // f16 query slab
-    constexpr int STAGE = V_BYTES + Q_BYTES;
-    constexpr int V_INSTR = V_BYTES / 1024;
-    constexpr int Q_INSTR = Q_BYTES / 1024;
-    static_assert(V_INSTR % NW == 0, "row DMA split");
-    constexpr int VPW = V_INSTR / NW;
-    constexpr int QPW = (Q_INSTR + NW - 1) / NW;
-    constexpr int OPS = VPW + QPW;  // LDS-DMA instructions per wave per slab
-    constexpr bool ASC = METRIC != M_IP;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wq = wave % WQ, wr = wave / WQ;
-
-    if (blockIdx.x >= a.ntiles) return;
-    const uint32_t my_tiles = (a.ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
-    const uint32_t G = my_tiles * a.nslab;  // slab steps of this persistent block
-    const bool ragged_k = (a.ld % GL_BK) != 0;  // last slab reaches past ld: clamp columns (they meet zeros in the query image)
-
-    // ---- DMA issue stream: position (tile, slab), ring stage, per-lane source pointers of the tile.
-    // Addresses advance incrementally (one 64-bit add per DMA); everything else is recomputed only at
-    // tile changes — the per-slab SALU/VALU overhead of the first version cost more than the MFMAs.
-    uint32_t v_rowoff[VPW], v_col[VPW];
-#pragma unroll
-    for (int j = 0; j < VPW; ++j) {
-        const uint32_t r = (wave * VPW + j) * 8 + (lane >> 3);  // row inside the tile
-        v_rowoff[j] = r;
-        v_col[j] = ((lane & 7) ^ ((r >> 1) & 7)) * 4;            // physical 16-B slot -> logical f32 column
-    }
-    const float* v_src[VPW];  // row pointers (incl. swizzled column) of the tile being issued
-    const char* q_src[QPW];
-    uint32_t q_dst[QPW];
-#pragma unroll
-    for (int j = 0; j < QPW; ++j) q_dst[j] = V_BYTES + ((wave * QPW + j) % Q_INSTR) * 1024;
-    uint32_t is_tile = blockIdx.x, is_slab = 0, is_stage = 0, is_count = 0, is_tileseq = 0;
-    uint32_t is_qslab = a.qpad * (GL_BK * 2);
-    uint32_t is_rbase = 0, is_last = 0;
-    // Per-row norms of a tile (L2: |v|^2, cosine: 1/|v|) travel by LDS-DMA too: one 1-KiB DMA per tile
-    // into a small ring after the stages — an ordinary load in the epilogue would drain the pipeline.
-    constexpr bool NORMS_LDS = !TILED && METRIC != M_IP;
-    constexpr int NORM_RING = NS * STAGE;
-    const float* norm_src = METRIC == M_L2 ? a.vn2 : a.vrinv;
-
-    auto issue_enter_tile = [&]() {
-        const char* qbase = reinterpret_cast<const char*>(a.Q16);
-        if (TILED) {
-            const IvfTile td = a.tiles[is_tile];  // uniform -> scalar loads
-            is_rbase = td.row0;
-            is_last = td.row0 + td.nrows - 1;
-            qbase += (size_t)td.qimg_off * 2;
-            is_qslab = BQ * (GL_BK * 2);
-        } else {
-            is_rbase = a.row0 + is_tile * BR;
-            is_last = a.row1 - 1;
-        }
-        if (NORMS_LDS) {
-            if (wave == 0)  // extra VM ops only make the counted waits more conservative (in-order retirement)
-                glds16<0>(norm_src + is_rbase + lane * 4, smem + NORM_RING + (is_tileseq % NS) * 1024);
-            ++is_tileseq;
-        }
-#pragma unroll
-        for (int j = 0; j < VPW; ++j) {
-            uint32_t row = is_rbase + v_rowoff[j];
-            row = row < is_last ? row : is_last;  // clamped rows are masked in the epilogue
-            v_src[j] = a.V + (size_t)row * a.ld + v_col[j];
-        }
-#pragma unroll
-        for (int j = 0; j < QPW; ++j) q_src[j] = qbase + ((wave * QPW + j) % Q_INSTR) * 1024 + lane * 16;
-    };
-    // One DMA piece (1 KiB per wave) of the slab at the issue position: pieces 0..VPW-1 are row pieces,
-    // VPW..OPS-1 query-image pieces.  Pieces are interleaved with the MFMA groups of the compute phase:
-    // a global_load_lds stalls ~100 cycles at issue when all waves fire at once (measured 500-1000
-    // cycles per slab right after the barrier) — behind MFMAs that stall is hidden.
-    auto issue_piece = [&](int p) {
-        char* stage = smem + is_stage * STAGE;
-        if (p < VPW) {
-            const uint32_t koff = is_slab * GL_BK;
-            const float* src = v_src[p] + koff;
-            if (ragged_k) {
-                uint32_t col = koff + v_col[p];
-                col = col < a.ld ? col : a.ld - 4;
-                src = v_src[p] - v_col[p] + col;
-            }
-            glds16<NT_HINT>(src, stage + (wave * VPW + p) * 1024);
-        } else {
-            const int j = p - VPW;
-            glds16<0>(q_src[j] + is_slab * is_qslab, stage + q_dst[j]);
-        }
-    };
-    auto issue_advance = [&]() {
-        // past the end the last real step is re-issued (keeps the per-wave DMA count uniform)
-        is_stage = is_stage + 1 == NS ? 0 : is_stage + 1;
-        if (++is_count < G) {
-            if (++is_slab == a.nslab) {
-                is_slab = 0;
-                is_tile += gridDim.x;
-                issue_enter_tile();
-            }
-        }
-    };
-    auto issue = [&]() {
-#pragma unroll
-        for (int p = 0; p < OPS; ++p) issue_piece(p);
-        issue_advance();
-    };
-
-    f32x16 acc[TR][TQ];
-#pragma unroll
-    for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TQ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // fragment geometry
-    const int l32 = lane & 31, hi = lane >> 5;
-    const int a_swz = (l32 >> 1) & 7;   // (row>>1)&7 — tile-row offsets are multiples of 32
-    const int b_swz = (l32 >> 2) & 3;   // (q>>2)&3
-    const int a_base = (wr * (TR * 32) + l32) * (GL_BK * 4);
-    const int b_base = V_BYTES + (wq * (TQ * 32) + l32) * (GL_BK * 2);
-
-    // per-query constants of this lane's columns (loaded once: no ordinary loads inside the ring loop)
-    float c_qinv[TQ], c_thr[TQ], c_extra[TQ];
-    bool c_ok[TQ];
-#pragma unroll
-    for (int j = 0; j < TQ; ++j) {
-        const uint32_t n = wq * (TQ * 32) + j * 32 + l32;
-        c_ok[j] = !TILED && n < a.nq;
-        c_qinv[j] = c_ok[j] ? a.qinv[n] : 0.0f;
-        c_thr[j] = c_ok[j] ? a.thr[n] : 0.0f;
-        if (a.debug_flags & 2) c_thr[j] = ASC ? -LY_INF : LY_INF;
-        c_extra[j] = 0.0f;
-        if (METRIC == M_L2) c_extra[j] = c_ok[j] ? a.qn2[n] : 0.0f;
-        if (METRIC == M_COS) c_extra[j] = c_ok[j] ? a.qrinv[n] : 0.0f;
-    }
-    // Make the compiler wait for these ordinary loads HERE: a first use inside the ring loop would
-    // cost an s_waitcnt vmcnt(0) per tile, draining the in-flight LDS-DMA slabs.
-#pragma unroll
-    for (int j = 0; j < TQ; ++j) asm volatile("" : "+v"(c_qinv[j]), "+v"(c_thr[j]), "+v"(c_extra[j]));
-
-    // Ring protocol: wait until at most (NS-2)*OPS of this wave's DMAs are outstanding (slab g landed)
-    // -> ONE raw barrier (everyone's pieces landed, everyone finished slab g-1) -> refill the stage
-    // that was computed last with slab g+NS-1 -> compute slab g.
-    issue_enter_tile();
-#pragma unroll
-    for (int g0 = 0; g0 < NS - 1; ++g0) issue();
-
-    uint32_t s_in_tile = 0, tile = blockIdx.x, c_stage = 0, c_tileseq = 0;
-    const bool timing = (a.debug_flags & 64) && a.dbg;
-    unsigned long long t_wait = 0, t_bar = 0, t_issue = 0, t_comp = 0, tp = timing ? __builtin_amdgcn_s_memtime() : 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * OPS) : "memory");
-        if (timing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_wait += t - tp; tp = t; }
-        __builtin_amdgcn_s_barrier();
-        if (timing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_bar += t - tp; tp = t; }
-        if (a.debug_flags & 4) issue();  // DMA-only experiment: no compute phase to interleave with
-
-        const char* st = smem + c_stage * STAGE;
-        c_stage = c_stage + 1 == NS ? 0 : c_stage + 1;
-        if (!(a.debug_flags & 4)) {  // EXPERIMENT flag 4: DMA stream only, no LDS reads / MFMA
-#pragma unroll
-            for (int kk = 0; kk < GL_BK / 16; ++kk) {
-                if ((a.debug_flags & 16) && kk == 1) break;  // EXPERIMENT: half the LDS reads + MFMAs
-                half8 bf[TQ];
-                const int lb = (kk * 2 + hi) ^ b_swz;
-#pragma unroll
-                for (int j = 0; j < TQ; ++j)
-                    bf[j] = *reinterpret_cast<const half8*>(st + b_base + j * 32 * (GL_BK * 2) + lb * 16);
-                const int la = (kk * 4 + hi * 2) ^ a_swz;  // physical slot of the first 16 B
-#pragma unroll
-                for (int i = 0; i < TR; ++i) {
-                    const char* rp = st + a_base + i * 32 * (GL_BK * 4);
-                    const f32x4 x0 = *reinterpret_cast<const f32x4*>(rp + la * 16);
-                    const f32x4 x1 = *reinterpret_cast<const f32x4*>(rp + (la ^ 1) * 16);
-                    half8 h;
-                    if (SCALE) {
-                        h[0] = (_Float16)(x0[0] * a.sv); h[1] = (_Float16)(x0[1] * a.sv);
-                        h[2] = (_Float16)(x0[2] * a.sv); h[3] = (_Float16)(x0[3] * a.sv);
-                        h[4] = (_Float16)(x1[0] * a.sv); h[5] = (_Float16)(x1[1] * a.sv);
-                        h[6] = (_Float16)(x1[2] * a.sv); h[7] = (_Float16)(x1[3] * a.sv);
-                    } else {
-                        h[0] = (_Float16)x0[0]; h[1] = (_Float16)x0[1]; h[2] = (_Float16)x0[2]; h[3] = (_Float16)x0[3];
-                        h[4] = (_Float16)x1[0]; h[5] = (_Float16)x1[1]; h[6] = (_Float16)x1[2]; h[7] = (_Float16)x1[3];
-                    }
-                    if (a.debug_flags & 32) {  // EXPERIMENT: LDS reads + cvt only, no MFMA
-                        asm volatile("" ::"v"(h));
-#pragma unroll
-                        for (int j = 0; j < TQ; ++j) asm volatile("" ::"v"(bf[j]));
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < TQ; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h, bf[j], acc[i][j], 0, 0, 0);
-                    }
-                    // refill pieces scheduled behind this MFMA group (slot kk*TR+i of NSLOT)
-                    {
-                        constexpr int NSLOT = (GL_BK / 16) * TR;
-                        const int slot = kk * TR + i;
-                        if (a.debug_flags & 128) {  // EXPERIMENT: all pieces behind the first MFMA group
-                            if (slot == 0) {
-#pragma unroll
-                                for (int p = 0; p < OPS; ++p) issue_piece(p);
-                            }
-                        } else if (a.debug_flags & 256) {  // EXPERIMENT: all pieces behind the last MFMA group
-                            if (slot == NSLOT - 1) {
-#pragma unroll
-                                for (int p = 0; p < OPS; ++p) issue_piece(p);
-                            }
-                        } else {
-#pragma unroll
-                            for (int p = 0; p < OPS; ++p)
-                                if (p % NSLOT == slot) issue_piece(p);
-                        }
-                    }
-                }
-            }
-            issue_advance();
-        }
-
-        if (++s_in_tile == a.nslab) {
-            // ---- epilogue of a finished tile: score transform, threshold filter, candidate append.
-            // Two passes: (1) build a per-lane bit mask of passing rows per query column, (2) ONE
-            // returning atomic per (lane, column) reserves the slots, then the keys are written.
-            uint32_t rbase = a.row0 + tile * BR;
-            uint32_t row_end = a.row1;
-            IvfTile td{};
-            if (TILED) {
-                td = a.tiles[tile];
-                rbase = td.row0;
-                row_end = td.row0 + td.nrows;
-            }
-            const float* nrm = reinterpret_cast<const float*>(smem + NORM_RING + (c_tileseq % NS) * 1024);
-            ++c_tileseq;
-            auto score = [&](int i, int j, int r, uint32_t m, bool rok) -> float {
-                float sc = acc[i][j][r] * c_qinv[j];
-                if (METRIC != M_IP) {
-                    float nv;
-                    if (NORMS_LDS) nv = nrm[m - rbase];
-                    else nv = rok ? (METRIC == M_L2 ? a.vn2[m] : a.vrinv[m]) : 0.0f;
-                    if (METRIC == M_L2) sc = nv - 2.0f * sc + c_extra[j];
-                    else sc = 1.0f - sc * nv * c_extra[j];
-                }
-                return sc;
-            };
-#pragma unroll
-            for (int j = 0; j < TQ; ++j) {
-                uint32_t n = wq * (TQ * 32) + j * 32 + l32;
-                if (TILED) {  // group-local query -> global query id and its per-query constants
-                    c_ok[j] = n < td.nq;
-                    n = c_ok[j] ? a.pair_q[td.pair0 + n] : 0u;
-                    c_qinv[j] = c_ok[j] ? a.qinv[n] : 0.0f;
-                    c_thr[j] = c_ok[j] ? a.thr[n] : 0.0f;
-                    if (METRIC == M_L2) c_extra[j] = c_ok[j] ? a.qn2[n] : 0.0f;
-                    if (METRIC == M_COS) c_extra[j] = c_ok[j] ? a.qrinv[n] : 0.0f;
-                }
-                if (a.emit_all && !TILED) {  // stage 0: slot = row, no atomics
-#pragma unroll
-                    for (int i = 0; i < TR; ++i)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const uint32_t m = rbase + wr * (TR * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                            const bool rok = m < row_end;
-                            const float sc = score(i, j, r, m, rok);
-                            if (c_ok[j] && rok && (m - a.row0) < a.cap)
-                                a.cand[(size_t)n * a.cap + (m - a.row0)] = make_key(sc, m, ASC);
-                        }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < TR; ++i) {  // one 32x32 block at a time keeps only 16 scores live
-                        uint32_t msk = 0;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const uint32_t m = rbase + wr * (TR * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                            const bool rok = m < row_end;
-                            const float sc = score(i, j, r, m, rok);
-                            const bool pass = ASC ? (sc <= c_thr[j]) : (sc >= c_thr[j]);
-                            if (c_ok[j] && rok && pass) msk |= 1u << r;
-                        }
-                        if (msk) {
-                            const uint32_t base = atomicAdd(&a.count[n], (uint32_t)__popc(msk));
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                if ((msk >> r) & 1u) {
-                                    const uint32_t m = rbase + wr * (TR * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                                    const uint32_t slot = base + (uint32_t)__popc(msk & ((1u << r) - 1u));
-                                    if (slot < a.cap) a.cand[(size_t)n * a.cap + slot] = make_key(score(i, j, r, m, true), m, ASC);
-                                }
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < TR; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-            }
-            s_in_tile = 0;
-            tile += gridDim.x;
-        }
-        if (timing) {
-            asm volatile("" ::"v"(acc[0][0][0]));
-            const unsigned long long t = __builtin_amdgcn_s_memtime(); t_comp += t - tp; tp = t;
-        }
-    }
-    if (timing && lane == 0) {
-        unsigned long long* o = a.dbg + ((size_t)blockIdx.x * NW + wave) * 4;
-        o[0] = t_wait; o[1] = t_bar; o[2] = t_issue; o[3] = t_comp;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the clamped tail DMAs before the LDS is released
-}
-#endif  // LYNSE_EXPERIMENTS
 
 // f16 storage: rows [r0,r1) <- f16::to_f32(f16::from_f32(row)) in place (encode_f32_slice_as_le_bytes F16, RNE)
 // F16 shards: f32 rows in -> f16 bits (RNE, what an F16 segment file keeps: src/storage/dtype.rs, flat_mmap.rs:187-221),
@@ -1152,7 +612,7 @@ __global__ void __launch_bounds__(256) k_round_rows_f16(float* __restrict__ V, u
 
 // ------------------------------------------------------------------------------------------------
 // k_rows_to_f16: the f16 SHADOW of the f32 rows that k_scan_h16 streams: out[r][c] = (half)(v[r][c] * sv),
-// RNE — bit for bit the conversion k_scan_glds does in flight, done once per appended row at finalize.
+// RNE, done once per appended row at finalize.
 // One thread per 8 output halves (16 B); columns [D, ld16) are zero.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -1172,16 +632,21 @@ __global__ void __launch_bounds__(256) k_rows_to_f16(const T* __restrict__ V, ui
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_scan_h16 — the hot kernel (default): k_scan_glds over the f16 shadow rows.
+// k_scan_h16 — the hot kernel: the LDS-DMA ring scan over the f16 shadow rows.
 //
 // The coarse pass only ever used the rows rounded to f16 (the certified margin E is built on exactly
 // that rounding), so the scan streams a resident f16 copy instead of converting f32 in flight: HALF
 // the HBM bytes per row, half the LDS bytes per MFMA operand, no cvt instructions.  Exactness is
 // untouched: survivors are rescored from the f32 rows in the reference's accumulation order.
+// Every operand byte travels HBM/L2 -> LDS with `global_load_lds_dwordx4` (glds16: no VGPR staging) through
+// rings of NSV row stages and NSQ query-image stages (>= 2 each), so up to NS - 1 slabs are in flight while one is computed:
+//   per slab and wave: VPW + QPW LDS-DMA instructions (1 KiB each) -> s_waitcnt vmcnt((NS-2)*OPS)
+//   -> ONE raw s_barrier -> issue the slab NS - 1 ahead into the stage that was computed last -> MFMA on slab g.
 // Geometry: K slab = 64 halves = 128 B per row AND per query, so rows and query image share one LDS
-// format: 8 16-B slots per line, physical slot = logical ^ ((line>>1)&7) (applied on the DMA source
-// address for rows, pre-applied in the image for queries).  A and B fragments are single
-// ds_read_b128s.  Ring protocol as k_scan_glds, NS >= 2 stages.
+// format: 8 16-B slots per line, physical slot = logical ^ ((line>>1)&7) (the bank-conflict swizzle, applied on the DMA
+// source address for rows — the DMA destination is lane-linear —, pre-applied in the image for queries by k_prep_queries).
+// A and B fragments are single ds_read_b128s.  Out-of-range rows / K columns are clamped to valid addresses: clamped rows
+// are masked in the epilogue, clamped columns meet zeros in the query image.
 // ------------------------------------------------------------------------------------------------
 
 // ---- fused sample stage of k_scan_h16 (FS = 1) ----------------------------------------------------
@@ -1381,14 +846,14 @@ __device__ __forceinline__ f32x16 ly_mfma_fp4(V a, V b, f32x16 c, int unit) {
 constexpr int HK = 64;  // K elements per slab
 
 // An instantiation of k_scan_h16 by name: one field per template parameter, in the template's order and with its defaults (the host
-// writes them with designated initialisers and launches through launch_h16, lynse_hip.hip).
+// writes them with designated initialisers and launches through launch_h16, lynse_hip.hip).  DBG has no field: the library launches
+// DBG = 0 only.
 struct H16Cfg {
     int wq, wr, tq, tr, metric, nsv, nsq, nt_hint;
     bool tiled = false, rag = true;
-    int dbg = 0;
     bool filt = false;
-    int i8q = 0, emit = -1, place = 0;
-    bool dense = false, prio = false, qcreg = true;
+    int i8q = 0, emit = -1;
+    bool dense = false, qcreg = true;
     int fs = 0;
 };
 constexpr int h16_threads(H16Cfg c) { return c.wq * c.wr * 64; }
@@ -1401,7 +866,7 @@ constexpr size_t h16_lds_bytes(H16Cfg c) {
     return norm_ring ? rings + norms : rings;
 }
 
-// DBG (compile-time experiments, never launched by the product path): 1 no MFMA, 2 no LDS fragment reads,
+// DBG (compile-time experiments of the microbenchmark, never launched by the library): 1 no MFMA, 2 no LDS fragment reads,
 // 4 no query-image DMA, 8 no row DMA, 16 no epilogue.  FILT compiles the subset-filter paths in (mask / row_ids of ScanArgs): they
 // cost registers the unfiltered kernel does not have to spare (56 B/lane of scratch and 13 % of its speed when they
 // were runtime branches).
@@ -1409,7 +874,7 @@ constexpr size_t h16_lds_bytes(H16Cfg c) {
 #define LYNSE_ZEROC 1   // (0: the DENSE float epilogue clears its accumulators, A/B build)
 #endif
 template <int WQ, int WR, int TQ, int TR, int METRIC, int NSV, int NSQ, int NT_HINT, bool TILED = false, bool RAG = true, int DBG = 0, bool FILT = false,
-          int I8Q = 0, int EMIT = -1, int PLACE = 0, bool DENSE = false, bool PRIO = false, bool QCREG = true, int FS = 0>
+          int I8Q = 0, int EMIT = -1, bool DENSE = false, bool QCREG = true, int FS = 0>
 __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR >= 8) ? (WQ * WR / 4) : 2)) k_scan_h16(ScanArgs a) {
     // Two LDS rings: NSV stages of row slabs (HBM latency: deeper) and NSQ <= NSV stages of query-image
     // slabs (L2 latency) — 3 + 2 stages of 32 KiB fill the 160 KiB of a CU for the 256 x 256 tile.
@@ -1517,7 +982,7 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
     constexpr bool NORMS_LDS = !TILED && !I8C && (METRIC != M_IP || I8) && (NORM_RING + (NSV + 1) * 1024 <= 160 * 1024);
     constexpr int NORM_SLOTS = NSV + 1;
     static_assert((size_t)(NORMS_LDS ? NORM_RING + NORM_SLOTS * 1024 : NORM_RING) <=
-                      h16_lds_bytes(H16Cfg{WQ, WR, TQ, TR, METRIC, NSV, NSQ, NT_HINT, TILED, RAG, DBG, FILT, I8Q, EMIT, PLACE, DENSE, PRIO, QCREG, FS}),
+                      h16_lds_bytes(H16Cfg{WQ, WR, TQ, TR, METRIC, NSV, NSQ, NT_HINT, TILED, RAG, FILT, I8Q, EMIT, DENSE, QCREG, FS}),
                   "the LDS the body addresses ends inside what the launch asks for");
     // Per-query constants of the epilogue (1/scale, the additive term, the threshold): constant for the whole launch, so each
     // wave keeps the TQ*32 queries of its column in QCN registers per constant (query q of the column lives in lane q % 64 of
@@ -1746,18 +1211,8 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
         v_advance();
     }
 
-    // static priority for the second-dispatched half of an 8-wave workgroup (MI355X_MICROARCH.md, "Two waves per SIMD", item 4):
-    // it is the arbitration loser on every slab step (s_memtime: 3500-3900 cycles per step against 2600-3500 for waves 0-3,
-    // which then wait at the barrier)
-    if (PRIO && NW == 8 && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
     uint32_t s_in_tile = 0, tile = FS ? blockIdx.x - gridDim.x : blockIdx.x, cv_stage = 0, cq_stage = 0, c_tileseq = 0;
     bool c_first = FS != 0;   // FS: the tile being computed is the workgroup's sample tile
-#ifdef LYNSE_EXPERIMENTS
-    const bool timing = (a.debug_flags & 64) && a.dbg;
-#else
-    constexpr bool timing = false;  // (phase timing lives in the EXPERIMENTS build: its flag and counters cost SGPRs in the hot loop)
-#endif
-    [[maybe_unused]] unsigned long long t_wait = 0, t_bar = 0, t_comp = 0, t_iq = 0, t_iv = 0, tp = timing ? __builtin_amdgcn_s_memtime() : 0;  // (EXPERIMENTS build only)
     half8 af[2][TR], bf[2][TQ];          // (DEFER: buffer 1 carries the last k-step's fragments across the loop edge)
     const char *stv = smem, *stq = smem;
     bool pend_done = false;              // DEFER: the deferred MFMA group completes a tile
@@ -1766,9 +1221,7 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
         if (!DEFER || g < G) {
         if constexpr (DEFER) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the deferred k-step's fragments are in registers: this wave is done with the old slab
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_OPS) : "memory");
-        if (timing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_wait += t - tp; tp = t; }
         __builtin_amdgcn_s_barrier();
-        if (timing) { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_bar += t - tp; tp = t; }
 
         stv = smem + cv_stage * V_BYTES;
         stq = smem + Q_RING + cq_stage * Q_BYTES;
@@ -1877,18 +1330,7 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
                     const int slot = kk * TR + i;
 #pragma unroll
                     for (int p = 0; p < OPS; ++p)
-                        if (PLACE == 0 ? (p % NSLOT == slot)                                   // spread: one piece behind every MFMA group
-                                       : PLACE == 1 ? (slot == 0)                              // all pieces behind the first MFMA group
-                                                    : (slot == ((wave < NW / 2) ? 0 : NSLOT / 2))) {  // half the waves early, half mid-phase
-                            if (timing) {  // (experiments) issue time of this DMA instruction: query-image vs row pieces
-                                const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-                                issue_piece(p);
-                                const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-                                if (p < QPW) t_iq += t1 - t0; else t_iv += t1 - t0;
-                            } else {
-                                issue_piece(p);
-                            }
-                        }
+                        if (p % NSLOT == slot) issue_piece(p);   // spread: one piece behind every MFMA group
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -2011,9 +1453,6 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
                     if (METRIC == M_COS && !I8) c_extra[j] = c_ok[j] ? ea->qrinv[n] : 0.0f;
                     c_thr[j] = c_ok[j] ? ea->thr[n] : 0.0f;
                 }
-#ifdef LYNSE_EXPERIMENTS
-                if (ea->debug_flags & 2) c_thr[j] = (I8C && QC_REG) ? __int_as_float(0x7fffffff) : (ASC ? -LY_INF : LY_INF);
-#endif
                 set_pre(j, c_thr[j], e_vmax2);
                 n_j[j] = n;
                 if (DENSEF && !e_emit_all) continue;   // scored after this loop (all columns per norm load)
@@ -2379,17 +1818,7 @@ __global__ void __launch_bounds__(WQ * WR * 64, (TQ * TR >= 16) ? 1 : ((WQ * WR 
             pend_done = ++s_in_tile == a.nslab;
             if (pend_done) s_in_tile = 0;
         }
-        if (timing) {
-            asm volatile("" ::"v"(acc[0][0][0]));
-            const unsigned long long t = __builtin_amdgcn_s_memtime(); t_comp += t - tp; tp = t;
-        }
     }
-#ifdef LYNSE_EXPERIMENTS
-    if (timing && lane == 0) {
-        unsigned long long* o = a.dbg + ((size_t)blockIdx.x * NW + wave) * 4;
-        o[0] = t_wait; o[1] = t_bar; o[2] = (t_iq << 32) | (t_iv & 0xffffffffull); o[3] = t_comp;
-    }
-#endif
     if (!TILED) {
         const EpiArgsPtr ea = epi_args();
         if (FS && (ea->debug_flags & 128) && tid == 0) reinterpret_cast<unsigned long long*>(ea->gsync + 64)[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memtime();
@@ -4006,7 +3435,7 @@ struct SmallArgs {
     const uint64_t* list_off;
     const uint32_t* orig;
     int flag_empty;
-    unsigned long long* dbg;   // development (LYNSE_HIP_SMALL_DBG=1): s_memtime stamps [workgroup][4] + the last workgroup's [2]; NULL otherwise
+    unsigned long long* dbg;   // development: s_memtime stamps [workgroup][4] + the last workgroup's [2]; the host leaves it NULL
 };
 
 __global__ void __launch_bounds__(SMALL_NT, 4) k_small_search(SmallArgs a) {   // (4 waves per SIMD = two workgroups per CU: the grid of run_small is sized for that)

@@ -751,7 +751,6 @@ extern "C" int lynse_hip_flat_append_packed_u64_device(lynse_hip_flat* h, const 
 static int ensure_shadow_locked(lynse_hip_flat* h);
 static bool shadow_ready(const lynse_hip_flat* h) { return h->packed_only || h->n == 0 || (h->rows16 && h->n16 == h->n && h->sv16 == h->sv); }
 constexpr int LY_RESTART_EXCLUSIVE = 10001;   // search_impl_once: the f16 shadow is missing and only a shared lock is held — run again under the writer lock
-static int scan_variant();
 
 static int finalize_locked(lynse_hip_flat* h) {
     if (h->packed_only || h->n_stats == h->n) return LYNSE_OK;
@@ -840,7 +839,7 @@ static uint32_t bin_mfma_minq() {
 }
 static bool bin_mfma_eligible(const lynse_hip_flat* h, int metric, bool filtered, uint64_t nq) {
     return metric == M_HAMMING && !filtered && bin_mfma_minq() > 0 && nq >= bin_mfma_minq() && nq > SCAN_BQ_SMALL && !h->bpm_failed &&
-           h->n >= 65536 && scan_variant() == 3;
+           h->n >= 65536;
 }
 static int ensure_bpm_locked(lynse_hip_flat* h) {
     if (h->bpm_failed || (h->bpm && h->n_bpm == h->n)) return LYNSE_OK;
@@ -1007,12 +1006,9 @@ constexpr uint32_t SEG_MAX = 2048;    // most segments per query (grid x row-wav
 static void seg_geometry(uint32_t grid, uint32_t wr, uint32_t* nseg, uint32_t* seg) {
     *nseg = grid * wr;
     *seg = 0;
-    static const int off = env_int("LYNSE_HIP_NO_SEGMENTS", 0);
-    if (off || *nseg == 0 || *nseg > SEG_MAX) { *nseg = 0; return; }
+    if (*nseg == 0 || *nseg > SEG_MAX) { *nseg = 0; return; }
     *seg = std::min<uint32_t>(255u, SEG_KEYS / *nseg);
 }
-
-static size_t scan_lds_bytes(int bq) { return (size_t)2 * (SCAN_BR + bq) * SCAN_LDK * sizeof(_Float16); }
 
 template <typename K>
 static int set_max_lds(K kernel, size_t bytes) {
@@ -1051,7 +1047,7 @@ static int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A
 // a config to the kernel's positional template arguments, and the block size and LDS bytes of the launch follow from the config.
 template <H16Cfg C>
 static int launch_h16(dim3 grid, hipStream_t st, const ScanArgs& a) {
-    return launch_lds<k_scan_h16<C.wq, C.wr, C.tq, C.tr, C.metric, C.nsv, C.nsq, C.nt_hint, C.tiled, C.rag, C.dbg, C.filt, C.i8q, C.emit, C.place, C.dense, C.prio, C.qcreg, C.fs>>(
+    return launch_lds<k_scan_h16<C.wq, C.wr, C.tq, C.tr, C.metric, C.nsv, C.nsq, C.nt_hint, C.tiled, C.rag, 0, C.filt, C.i8q, C.emit, C.dense, C.qcreg, C.fs>>(
         grid, h16_threads(C), h16_lds_bytes(C), st, a);
 }
 template <QsCfg C>
@@ -1078,20 +1074,6 @@ static int with_metric(int metric, F&& f) {
     default: return f(std::integral_constant<int, M_COS>{});
     }
 }
-// Timing experiments (make EXPERIMENTS=1): BASE with DBG = the run-time value dbg, which has to be one of VALUES (the ones compiled).
-// DBG is a bit set (kernels.h): 1 no MFMA, 2 no LDS fragment reads, 4 no query-image DMA, 8 no row DMA, 16 no epilogue.  What the
-// compiled combinations leave running:
-//    1 DMA + LDS reads              2 DMA + MFMA                    3 DMA only             4 everything but the query-image DMA
-//    7 row DMA only                 8 everything but the row DMA   11 query DMA only      12 MFMA + LDS reads + epilogue (no DMA)
-//   13 LDS reads only              14 MFMA only                    15 the loop and the epilogue alone
-//   16 everything but the epilogue, and without it: 17 as 1, 19 as 3, 20 as 4, 24 as 8, 28 MFMA + LDS reads only, 30 MFMA only
-template <H16Cfg BASE, int... VALUES>
-static int dispatch_dbg(int dbg, dim3 grid, hipStream_t st, const ScanArgs& a) {
-    int rc = LYNSE_OK;   // (a left fold: the kernels are instantiated, and laid out in the code object, in the order of VALUES)
-    const bool known = (... || (dbg == VALUES ? (rc = launch_h16<with(BASE, &H16Cfg::dbg, VALUES)>(grid, st, a), true) : false));
-    return known ? rc : set_error(LYNSE_ERR_INVALID_ARGUMENT, "unknown experiment");
-}
-
 static int ensure_workspace(lynse_hip_flat* h, uint32_t k /* caller's k = output stride */) {
     Workspace& w = cur(h).ws;
     const uint32_t nslab = (h->dim + SCAN_BK - 1) / SCAN_BK;
@@ -1131,7 +1113,7 @@ static int ensure_workspace(lynse_hip_flat* h, uint32_t k /* caller's k = output
     LY_HIP(hipMalloc(&w.pool_total, 8));
     LY_TRY(memset_done(w.pool_total, 0, 8));
     LY_HIP(hipMalloc(&w.dyn, (size_t)QC * 34 * sizeof(int)));
-    LY_HIP(hipMalloc(&w.gsync, 256 + 1024 * 64));   // hand-over words + (debugging) 8 time stamps per workgroup / per (stage, query)
+    LY_HIP(hipMalloc(&w.gsync, 256 + 1024 * 64));   // hand-over words
     LY_TRY(memset_done(w.gsync, 0, 256 + 1024 * 64));
     LY_HIP(hipMalloc(&w.small_part, (size_t)SMALL_NT * SMALL_MAX_Q * SMALL_MAX_K * 8));
     LY_HIP(hipMalloc(&w.small_ticket, 16));
@@ -1161,15 +1143,13 @@ static std::vector<Stage> make_plan(const lynse_hip_flat* h, uint32_t k, int lev
         return plan;
     }
     if (level == 0 && tile_rows && n > 4ull * h->cap) {
-        static const uint32_t s_env = (uint32_t)env_int("LYNSE_HIP_SAMPLE_ROWS", 0);
         // emit-all sample: every sample row becomes a key (S <= cap / 2).  Threshold-only sample: 16 keys per tile, and a
         // tile per CU costs the same latency as 32 tiles — a larger sample gives a tighter first threshold for free
         // (its rows are scanned again: keep it <= n / 16).
-        uint32_t S = s_env ? std::min<uint32_t>(s_env, h->cap / 2) : h->cap / 2;
+        uint32_t S = h->cap / 2;
         if (threshold_only_sample) {
-            static const uint32_t big_env = (uint32_t)env_int("LYNSE_HIP_SAMPLE_ROWS_TO", 0);
-            const uint64_t want = big_env ? big_env : (uint64_t)h->num_cu * tile_rows;
-            S = (uint32_t)std::max<uint64_t>(S, std::min<uint64_t>(std::min<uint64_t>(want, big_env ? n / 4 : n / 16), (uint64_t)h->cap / 16 * tile_rows));
+            const uint64_t want = (uint64_t)h->num_cu * tile_rows;
+            S = (uint32_t)std::max<uint64_t>(S, std::min<uint64_t>(std::min<uint64_t>(want, n / 16), (uint64_t)h->cap / 16 * tile_rows));
             S = S / tile_rows * tile_rows;
         }
         const uint32_t nt = S / tile_rows;
@@ -1179,8 +1159,7 @@ static std::vector<Stage> make_plan(const lynse_hip_flat* h, uint32_t k, int lev
             s0.sample_tiles = nt;
             s0.sample_stride = (uint32_t)stride;
             plan.push_back(s0);
-            static const uint64_t genv = (uint64_t)env_int("LYNSE_HIP_SAMPLE_GROWTH", 0);
-            const uint64_t gmax = genv ? genv : growth_hint ? growth_hint : (threshold_only_sample ? 32ull : 16ull);  // measured best on 10M and 1.25M rows
+            const uint64_t gmax = growth_hint ? growth_hint : (threshold_only_sample ? 32ull : 16ull);  // measured best on 10M and 1.25M rows
             const uint64_t g = std::max<uint64_t>(2, std::min<uint64_t>(gmax, h->cap / (8ull * std::max<uint32_t>(k, 1))));
             uint64_t seen = S, b = 0;
             while (b < n) {
@@ -1207,75 +1186,6 @@ static std::vector<Stage> make_plan(const lynse_hip_flat* h, uint32_t k, int lev
     return plan;
 }
 
-#ifdef LYNSE_EXPERIMENTS  // launchers of the superseded scan kernels (A/B references)
-template <int WQ, int WR, int TQ, int TR, int PD>
-static int launch_scan(lynse_hip_flat* h, const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
-    constexpr int NT = WQ * WR * 64;
-    constexpr int BQ = WQ * TQ * 32;
-    const size_t lds = scan_lds_bytes(BQ);
-    (void)h;
-    return with_metric(metric, [&](auto m) { return launch_lds<k_scan_f16<WQ, WR, TQ, TR, decltype(m)::value, PD>>(grid, NT, lds, st, a); });
-}
-
-template <int WQ, int WR, int TQ, int TR, int NS>
-static int launch_scan_glds(const ScanArgs& a, int metric, bool scale, uint32_t grid, hipStream_t st) {
-    constexpr int NT = WQ * WR * 64;
-    constexpr int BQ = WQ * TQ * 32;
-    constexpr int BR = WR * TR * 32;
-    const size_t lds = (size_t)NS * (BR * GL_BK * 4 + BQ * GL_BK * 2) + (metric == M_IP ? 0 : (size_t)NS * 1024);  // + per-tile norm ring
-    static const int nt_hint = env_int("LYNSE_HIP_SCAN_NT", 1);
-    auto go = [&](auto s, auto hint) {
-        return with_metric(metric, [&](auto m) { return launch_lds<k_scan_glds<WQ, WR, TQ, TR, decltype(m)::value, decltype(s)::value, NS, decltype(hint)::value>>(grid, NT, lds, st, a); });
-    };
-    if (nt_hint) return scale ? go(std::true_type{}, std::integral_constant<int, 2>{}) : go(std::false_type{}, std::integral_constant<int, 2>{});
-    return scale ? go(std::true_type{}, std::integral_constant<int, 0>{}) : go(std::false_type{}, std::integral_constant<int, 0>{});
-}
-
-#endif  // LYNSE_EXPERIMENTS
-
-// debugging only (not in the header): per-query thresholds / shared-region counts / overflow flags and the hand-over words of
-// context 0's workspace
-extern "C" int lynse_hip_debug_workspace(lynse_hip_flat* h, float* thr, uint32_t* count, uint32_t* overflow, uint32_t* gsync, uint32_t nq) {
-    if (!h || !h->ctx[0].ws.thr) return 1;
-    Workspace& w = h->ctx[0].ws;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->ctx[0].stream);
-    if (thr && hipMemcpy(thr, w.thr, nq * 4, hipMemcpyDeviceToHost) != hipSuccess) return 2;
-    if (count && hipMemcpy(count, w.count, nq * 4, hipMemcpyDeviceToHost) != hipSuccess) return 2;
-    if (overflow && hipMemcpy(overflow, w.overflow, nq * 4, hipMemcpyDeviceToHost) != hipSuccess) return 2;
-    if (gsync && hipMemcpy(gsync, w.gsync, 16, hipMemcpyDeviceToHost) != hipSuccess) return 2;
-    return 0;
-}
-extern "C" int lynse_hip_debug_fs_stamps(lynse_hip_flat* h, unsigned long long* out /* [512][8] */) {
-    if (!h || !h->ctx[0].ws.gsync) return 1;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->ctx[0].stream);
-    return hipMemcpy(out, h->ctx[0].ws.gsync + 64, 512 * 64, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-extern "C" int lynse_hip_debug_sel_stamps(lynse_hip_flat* h, unsigned long long* out /* [4][256][8] */) {
-    if (!h || !h->ctx[0].ws.gsync) return 1;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->ctx[0].stream);
-    return hipMemcpy(out, h->ctx[0].ws.gsync + 64, 1024 * 64, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-
-static unsigned long long* g_dbg_ptr = nullptr;
-extern "C" int lynse_hip_debug_phase_cycles(unsigned long long* out, int n) {  // experiments only (not in the header)
-    if (!g_dbg_ptr) return 1;
-    return hipMemcpy(out, g_dbg_ptr, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-
-// 3 = LDS-DMA ring kernel over the f16 shadow rows (default), 0 = LDS-DMA ring kernel over the f32 rows,
-// 1 / 2 = register-staged kernel with prefetch depth 1 / 2
-static int scan_variant() {
-#ifdef LYNSE_EXPERIMENTS
-    static const int v = env_int("LYNSE_HIP_SCAN_VARIANT", 3);
-    return v;
-#else
-    return 3;  // the superseded variants are only compiled with make EXPERIMENTS=1
-#endif
-}
-
 // Named tilings of the float scan over the f16 shadow (launch_scan_h16 sets the metric and the ragged / filter / emission fields per
 // call).  nt_hint = 2 everywhere: the rows are streamed once.
 constexpr H16Cfg F16_SMALL{.wq = 1, .wr = 4, .tq = 1, .tr = 1, .metric = M_IP, .nsv = 3, .nsq = 3, .nt_hint = 2};      // 128 rows x 32 queries
@@ -1292,21 +1202,6 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
     const dim3 g(grid, grid_y);
     const bool filt = a.mask != nullptr || a.row_ids != nullptr;
     const bool ragged = a.ld16 % HK != 0;
-#ifdef LYNSE_EXPERIMENTS
-    if constexpr (BASE.wq == 2 && BASE.wr == 4 && !BASE.tiled) {  // timing experiments (LYNSE_HIP_DEBUG_FLAGS bits 8..11 = DBG << 8)
-        if (metric == M_IP && !filt && !ragged && ((a.debug_flags >> 8) & 15)) {
-            constexpr H16Cfg C = with(BASE, &H16Cfg::metric, M_IP, &H16Cfg::rag, false);
-            return dispatch_dbg<C, 1, 2, 3, 7, 11, 12, 15, 14, 13, 4, 8>((a.debug_flags >> 8) & 15, grid, st, a);
-        }
-    }
-    if constexpr (BASE.wq == 4 && BASE.wr == 2 && BASE.tr == 4 && !BASE.tiled) {  // decomposition of the low-D L2 scan (C3): LYNSE_HIP_DEBUG_FLAGS bits 8..12 = DBG << 8
-        const int dbg = (a.debug_flags >> 8) & 31;
-        if (metric == M_L2 && !filt && !ragged && dbg && a.emit_all == 0) {
-            constexpr H16Cfg C = with(BASE, &H16Cfg::metric, M_L2, &H16Cfg::rag, false, &H16Cfg::emit, 0, &H16Cfg::dense, true);
-            return dispatch_dbg<C, 16, 17, 19, 20, 24, 28, 30, 12, 4>(dbg, grid, st, a);
-        }
-    }
-#endif
     if constexpr (BASE.wq * BASE.wr == 8 && !BASE.tiled) {
         // one kernel per (metric, ragged / filter variant, emission mode)
         auto by_emit = [&](auto mtag, auto ragtag, auto filtag) -> int {
@@ -1329,22 +1224,13 @@ static int launch_scan_h16(const ScanArgs& a, int metric, uint32_t grid, hipStre
             return by_emit(mtag, std::false_type{}, std::false_type{});  // no ragged last slab: branch-free DMA issue
         };
         if constexpr (BASE.wr >= 4) {  // <2,4,4,2>: unfiltered IP only
-#ifndef LYNSE_EXPERIMENTS
             if (metric != M_IP) return set_error(LYNSE_ERR_INTERNAL, "the <2,4,4,2> tiling is compiled for IP only");
-#else
-            if (metric == M_L2) return by_variant(std::integral_constant<int, M_L2>{});
-            if (metric == M_COS) return by_variant(std::integral_constant<int, M_COS>{});
-#endif
             return by_variant(std::integral_constant<int, M_IP>{});
         } else {
             switch (metric) {
             case M_IP:
-#ifndef LYNSE_EXPERIMENTS
                 if (!filt) return set_error(LYNSE_ERR_INTERNAL, "unfiltered IP scans run on the <2,4,4,2> tiling");
                 return by_emit(std::integral_constant<int, M_IP>{}, std::true_type{}, std::true_type{});
-#else
-                return by_variant(std::integral_constant<int, M_IP>{});
-#endif
             case M_L2: return by_variant(std::integral_constant<int, M_L2>{});
             default: return by_variant(std::integral_constant<int, M_COS>{});
             }
@@ -1496,14 +1382,11 @@ static bool qs_scan_ok(const ScanArgs& a, bool fs, bool filt, bool f4) {
     return !fs && a.emit_all == 0 && qs_width_ok(a.ld16, a.nslab, filt) && a.qpad == 256 && a.nq <= 256 && a.tile_stride == 0 &&
            (filt || (a.skip_stride == 0 && !a.mask)) && !a.row_ids && a.row1 > a.row0;
 }
-// LYNSE_HIP_SCAN_CUS: workgroups (= CUs: one 144-KB workgroup per CU) of the persistent threshold-stage scans.  The scan is bound by the
-// power the chip may draw, not by its CU count: a few CUs left free cost it little and let the short latency-bound kernels of ANOTHER
-// batch in flight (query image, sample stage, selects, final rescoring) run beside it instead of between its launches.
+// Workgroups of the persistent threshold-stage scans: one 144-KB workgroup per CU, on every CU (the scan is bound by the power the chip
+// may draw, not by its CU count: leaving a few CUs free for the short kernels of another batch in flight gained nothing).
 static uint32_t qs_grid(const ScanArgs& a, uint32_t num_cu) {
     const uint32_t rt = a.nslab == 8 ? 32u : qs_rows(qs_variant());   // (1024 columns: 32-row tiles)
-    const int e = env_int("LYNSE_HIP_SCAN_CUS", 0);
-    const uint32_t cus = e > 0 ? std::min<uint32_t>((uint32_t)e, num_cu) : num_cu;
-    return std::min<uint32_t>((a.row1 - a.row0 + rt - 1) / rt, cus);
+    return std::min<uint32_t>((a.row1 - a.row0 + rt - 1) / rt, num_cu);
 }
 // LYNSE_HIP_QS_M16: the MFMA shape of the plain threshold stages on the 64-row tilings (scan_qs.h, M16): 1 / unset (auto) =
 // v_mfma_i32_16x16x64_i8, 0 = v_mfma_i32_32x32x32_i8 (A/B, tests; read per call).  Same wave tile, fragment reads, registers and key sets;
@@ -1577,9 +1460,9 @@ static int launch_scan_qh_any(const ScanArgs& a, int metric, uint32_t grid, hipS
 static int launch_scan_qh(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) { return launch_scan_qh_any<0>(a, metric, grid, st); }
 
 // The threshold-only SAMPLE stage of the same plans on k_scan_qh<.., SMP> (scan_qh.h): the sample rows as 64-row tiles, two workgroups per CU,
-// 4 keys per workgroup and query.  LYNSE_HIP_QH_SAMPLE=0: the 256 x 256 sample tiles of k_scan_h16<.., EMIT = 2> (A/B; read per call).
+// 4 keys per workgroup and query.
 static bool qh_sample_ok(const ScanArgs& a, bool filt, uint32_t qchunks, int level, uint32_t plan_tile) {
-    if (!env_on("LYNSE_HIP_QH_SAMPLE", true) || qh_variant() != 1 || level != 0) return false;
+    if (qh_variant() != 1 || level != 0) return false;
     return !filt && a.emit_all == 2 && plan_tile == 256 && qchunks == 1 && a.qpad == 256 && a.nq <= 256 && a.tile_stride >= 256 && a.skip_stride == 0 && !a.mask && !a.row_ids &&
            !a.tiles && a.row1 > a.row0 && (a.nslab == 1 || a.nslab == 2) && a.ld16 == a.nslab * 64u;
 }
@@ -1608,11 +1491,6 @@ static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, boo
         return launch_qs<with(qs_64(4), &QsCfg::f4, 1)>(grid, st, a);
     }
     if (qs) return launch_scan_qs(a, grid, st, m16);
-#ifdef LYNSE_EXPERIMENTS
-    if (a.ld16 % 128 == 0 && a.emit_all == 0 && ((a.debug_flags >> 8) & 31)) {  // timing experiments: DBG variants of the int8 kernel
-        return dispatch_dbg<I8C_256, 3, 4, 8, 12, 7, 11, 1, 13, 14, 2, 16>((a.debug_flags >> 8) & 31, grid, st, a);
-    }
-#endif
     if (f4) {   // batched Hamming: FP4 +-1 operands (kernels.h, I8Q = 3); whole 128-B slabs by construction, unfiltered
         if (a.ld16 % 128 != 0 || filt || fs) return set_error(LYNSE_ERR_INTERNAL, "the FP4 Hamming scan runs unfiltered over whole slabs");
         if (a.emit_all == 1) return launch_h16<with(I8C_256, &H16Cfg::i8q, 3, &H16Cfg::emit, 1)>(grid, st, a);
@@ -1633,11 +1511,6 @@ static int launch_scan_i8c(const ScanArgs& a, uint32_t grid, hipStream_t st, boo
         return launch_h16<I8C_AG>(grid, st, a);
     }
     if (a.ld16 % 128 == 0) {
-        static const int prio = env_int("LYNSE_HIP_PRIO", 0);
-        if (a.emit_all == 0 && prio) return launch_h16<with(I8C_256, &H16Cfg::prio, true)>(grid, st, a);
-        static const int place = env_int("LYNSE_HIP_PLACE", 0);
-        if (a.emit_all == 0 && place == 1) return launch_h16<with(I8C_256, &H16Cfg::place, 1)>(grid, st, a);
-        if (a.emit_all == 0 && place == 2) return launch_h16<with(I8C_256, &H16Cfg::place, 2)>(grid, st, a);
         if (fs) {  // fused sample stage: sample tile + in-launch thresholds + the first threshold stage (kernels.h, FS)
             if (a.emit_all != 0) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is a threshold stage");
             if (!a.dense) return set_error(LYNSE_ERR_INTERNAL, "the fused sample stage is compiled with the DENSE epilogue");  // (the two-level body spills 12 B with it)
@@ -1757,8 +1630,7 @@ static inline uint32_t sel_lds_bytes(uint32_t cap, uint32_t nq = 0) {
     // (a widened pass — thousands of queries per launch, the k-means assignment — is bound by how many of its one-per-query workgroups
     // fit a CU: no scratch there, 4096 key slots stay 32 KB instead of 80 KB)
     if (nq > 512) return cap * 8u;
-    static const size_t extra = (size_t)env_int("LYNSE_HIP_SEL_SCRATCH_KB", 48) * 1024;   // (0: the direct loads, A/B)
-    return (uint32_t)std::min<size_t>((size_t)cap * 8 + extra, SEL_LDS_MAX);
+    return (uint32_t)std::min<size_t>((size_t)cap * 8 + 48 * 1024, SEL_LDS_MAX);
 }
 
 static int get_event(lynse_hip_flat* h, size_t idx, hipEvent_t* out) {
@@ -1772,40 +1644,19 @@ static int get_event(lynse_hip_flat* h, size_t idx, hipEvent_t* out) {
 }
 
 // The knobs of run_chunk that more than one place reads.
-// LYNSE_HIP_DENSE: 1 / 0 = the threshold stages always / never on the DENSE epilogue (kernels.h), unset = the rule of each pass.  Read once
-// per process by the scan stages of run_chunk (dense_env()); read per call where the fused sample stage asks whether DENSE is off at
-// all (dense_env_now()) — both as before.
-static int dense_env_now() { return env_int("LYNSE_HIP_DENSE", -1); }
-static int dense_env() { static const int v = dense_env_now(); return v; }
-// LYNSE_HIP_DEBUG_FLAGS: ScanArgs::debug_flags of every scan launch (bit 1: no emit-all, bit 6: phase stamps, bits 8..12: the timing
-// variants of an EXPERIMENTS build); read once per process
-static int debug_flags_env() { static const int v = env_int("LYNSE_HIP_DEBUG_FLAGS", 0); return v; }
-// LYNSE_HIP_NO_LANE_MAX=1: the sample stage emits every score instead of one key per lane (A/B); read once per process
-static int no_lane_max_env() { static const int v = env_int("LYNSE_HIP_NO_LANE_MAX", 0); return v; }
-// LYNSE_HIP_I8C_CS=0: the Hoelder terms of the int8 bound alone, without the Cauchy-Schwarz terms (A/B); read once per process
-static bool i8c_cs_on() { static const bool v = env_on("LYNSE_HIP_I8C_CS", true); return v; }
-// LYNSE_HIP_SEL_STAMPS (set): phase stamps of the selects (lynse_hip_debug_sel_stamps / _ivf_sel_stamps); read per call
-static bool sel_stamps_on() { return env_str("LYNSE_HIP_SEL_STAMPS") != nullptr; }
 // LYNSE_HIP_FUSED=0: no fused single-launch search (k_small_search), FLAT and IVF (A/B); read once per process
 static int fused_env() { static const int v = env_int("LYNSE_HIP_FUSED", 1); return v; }
-#ifdef LYNSE_EXPERIMENTS
-// LYNSE_HIP_SCAN_W16: the wave tiling of the 256 x 256 tile — of the f16 kernel (default -1: by metric) and of the superseded f32 ring
-// kernel (default 2); each read once per process
-template <int DFLT>
-static int scan_w16_env() { static const int v = env_int("LYNSE_HIP_SCAN_W16", DFLT); return v; }
-#endif
 
 // Squared L2 has two int8 forms: unfiltered FLAT batches over whole 128-column slabs run on the PLAIN codes with the exact f32
 // row norms in a float epilogue (k_scan_h16<.., I8Q = 4>, every tiling: 1 B per element, no second code set, IP-sized margins);
 // everything else (ragged widths, masked scans, IVF) on the codes of the AUGMENTED rows through the IP kernels.  nqc = 0: "not a FLAT
-// batch" (IVF): the augmented form.  LYNSE_HIP_L2_PLAIN=0: always the augmented form.
+// batch" (IVF): the augmented form.
 static bool l2_plain(const lynse_hip_flat* h, uint64_t nqc, bool masked) {
-    static const int on = env_int("LYNSE_HIP_L2_PLAIN", 1);
     // (1M x 128, k = 100: 0.244 ms on the f16 shadow, 0.277 on the codes with the <4,2,2,4> tiling and 0.291 with the query-stationary
     // L2 tiling (k_scan_qs<1,4,1,6,.., MET = 1>, built and measured in round 4: at k = 100 the first threshold lets 0.8 % of all
     // (row, query) pairs through and the scan is bound by the emission of ~8000 keys per query, not by the tiling) — from 256
     // dimensions on)
-    return on && !masked && nqc >= 1 && nqc <= QCHUNK && h->ld8 % 128 == 0 && h->dim >= 256;
+    return !masked && nqc >= 1 && nqc <= QCHUNK && h->ld8 % 128 == 0 && h->dim >= 256;
 }
 // The form of the certified int8 pass a batch of nqc queries of `metric` takes — which code set it streams and how the prep kernel
 // builds the query image (I8cPrepArgs::l2n / aug / cosine).  nqc = 0: not a FLAT batch (the IVF list scan).
@@ -1835,7 +1686,7 @@ static I8cOperand i8c_operand(const lynse_hip_flat* h, I8cForm form, bool sq7) {
 }
 static void fill_i8c_prep(I8cPrepArgs& p, const I8cOperand& v, I8cForm form) {
     p.mins = v.mins; p.scales = v.scales; p.a1 = v.a1;
-    if (i8c_cs_on()) { p.a2sq = v.a2sq; p.eps2 = v.eps2; }   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
+    p.a2sq = v.a2sq; p.eps2 = v.eps2;   // (the Cauchy-Schwarz terms, k_i8c_prep_queries)
     p.cosine = form == I8C_COS ? 1 : 0; p.aug = (int)v.norm_cols; p.l2n = form == I8C_L2_PLAIN ? 1 : 0; p.sq7 = v.sq7 ? 1 : 0;
 }
 
@@ -1890,10 +1741,8 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     const float* Qf = rq.qsrc ? rq.qsrc : w.Qf;
     const bool binary = metric >= M_HAMMING;
     const bool asc = metric_ascending(metric);
-    const bool h16 = scan_variant() == 3;
-    const bool glds = scan_variant() == 0;
     // batched Hamming on the int8 MFMA: the +-1 copy of the rows is there and the batch is large enough (search_impl builds it)
-    const bool bin_mfma = h16 && bin_mfma_eligible(h, metric, mask != nullptr || row_ids != nullptr, nq) && h->bpm && h->n_bpm == h->n;
+    const bool bin_mfma = bin_mfma_eligible(h, metric, mask != nullptr || row_ids != nullptr, nq) && h->bpm && h->n_bpm == h->n;
     if (bin_mfma) i8c = true;   // the scan side IS the certified-int8 IP scan (exact here: margin 0)
     // squared L2 on the certified int8 pass: an inner product of augmented vectors in the negated score space (kernels.h,
     // I8cPrepArgs::aug): scan, thresholds and selects run as a best-first IP search, exact scores are -|q - v|^2
@@ -1911,7 +1760,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     res->used_sq7 = sq7;
     const I8cOperand opd = i8q ? i8c_operand(h, form, sq7) : I8cOperand{};
     const int key_metric = (bin_mfma || aug || cosq) ? (int)M_IP : metric;   // the order of the candidate keys
-    const uint32_t nslab = bin_mfma ? h->ld_bpm / 128 : i8c ? (opd.cols + 127) / 128 : glds ? (h->dim + GL_BK - 1) / GL_BK : (h->dim + SCAN_BK - 1) / SCAN_BK;  // h16: HK == SCAN_BK == 64
+    const uint32_t nslab = bin_mfma ? h->ld_bpm / 128 : i8c ? (opd.cols + 127) / 128 : (h->dim + SCAN_BK - 1) / SCAN_BK;  // HK == SCAN_BK == 64
     const bool small = nq <= SCAN_BQ_SMALL;
     // mid-size batches on the int8 codes: 33..64 queries -> the 128 x 64 tiling, 65..128 -> the 256 x 128 tiling (LYNSE_HIP_MID_TILINGS=0: off)
     const int mid_env = env_int("LYNSE_HIP_MID_TILINGS", 1);   // (read per call: tests flip it)
@@ -1920,15 +1769,15 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     // 40 / 64 / 100 / 128 queries 1.28 / 1.32 / 1.48 / 1.49 -> 1.22 / 1.25 / 1.29 / 1.31 ms; L2 1.39 / 1.43 / 1.81 / 1.89 -> 1.34 / 1.38 / 1.57 /
     // 1.62).  LYNSE_HIP_QS_MID=0: the mid tilings (A/B, tests; read per call)
     const bool qs_mid = env_on("LYNSE_HIP_QS_MID", true) && qs_variant() >= 1 && qs_variant() <= 3 && i8c && !bin_mfma &&
-                        !small && !row_ids && h16 && !aug && qs_width_ok(h->ld8, (h->dim + 127) / 128, mask != nullptr) && !(l2n && (h->dim + 127) / 128 == 8) && nq <= 256 &&   // (plain-L2: not on the 32-row tiles of 1024 columns)
+                        !small && !row_ids && !aug && qs_width_ok(h->ld8, (h->dim + 127) / 128, mask != nullptr) && !(l2n && (h->dim + 127) / 128 == 8) && nq <= 256 &&   // (plain-L2: not on the 32-row tiles of 1024 columns)
                         (h->ld8 == 768 || nq > 64) &&   // (narrower rows: the 128 x 64 tiling keeps 33..64 queries — 6M x 256, 40 queries: 0.34 ms against 0.37)
                         (!mask || (!l2n && qs_variant() != 2 && qs_masked_on()));
-    const bool mid_ok = mid_env && !qs_mid && i8c && !bin_mfma && !small && !row_ids && h16 && (!mask || opd.ld % 128 == 0);
+    const bool mid_ok = mid_env && !qs_mid && i8c && !bin_mfma && !small && !row_ids && (!mask || opd.ld % 128 == 0);
     const bool mid64 = mid_ok && nq <= 64, mid128 = mid_ok && !mid64 && nq <= 128;
     const bool narrow = small || mid64;   // 128-row tiles
     const uint32_t qpad = small ? SCAN_BQ_SMALL : mid64 ? 64u : mid128 ? 128u : round_up(nq, SCAN_BQ_LARGE);  // > 256 queries: a widened handle, qpad / 256 chunks per launch
     const uint32_t qchunks = (small || mid64 || mid128) ? 1u : qpad / SCAN_BQ_LARGE;
-    if (qchunks > 1 && (binary || i8c || mask || row_ids || !h16 || h->n > w.cap || nq > w.qcap))
+    if (qchunks > 1 && (binary || i8c || mask || row_ids || h->n > w.cap || nq > w.qcap))
         return set_error(LYNSE_ERR_INTERNAL, "more than 256 queries per pass need the widened float pipeline over <= cap rows");
     int ip_form = h->ip_form;
     if (ip_form == LYNSE_IPFORM_AUTO) ip_form = h->n < 4096 ? LYNSE_IPFORM_SINGLE : LYNSE_IPFORM_BATCH8;
@@ -1939,7 +1788,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
     LY_TRY(ensure_lds<k_select_final<SEL_NT>>(SEL_LDS_MAX));
 
-    const bool sts = rq.allow_sts && sts_env_on() && level == 0 && i8c && !bin_mfma && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids && h16 &&
+    const bool sts = rq.allow_sts && sts_env_on() && level == 0 && i8c && !bin_mfma && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids &&
                      k >= 1 && k <= 32 && qs_variant() >= 1 && qs_variant() <= 3 && opd.ld == 768 && nslab == 6 && qpad == 256 && h->n >= 65536 &&
                      h->n < 0xffffff00ull && (metric == M_IP || cosq);
     res->used_sts = sts;
@@ -1973,7 +1822,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     } else {
         // queries with index >= nq inside the padded tile must be finite: blocks nq .. qpad - 1 of the grid write zero lines
         PrepArgs p{};
-        p.Q = Qf; p.D = h->dim; p.nq = nq; p.qpad = qpad; p.nslab = nslab; p.metric = metric; p.layout = glds ? 1 : (h16 ? 2 : 0);
+        p.Q = Qf; p.D = h->dim; p.nq = nq; p.qpad = qpad; p.nslab = nslab; p.metric = metric; p.layout = 2;
         p.sv = h->sv; p.vmax = h->vmax; p.vmin = h->vmin; p.cos_degenerate = h->cos_degenerate; p.rows_integer = h->rows_integer; p.rows_nonneg = h->rows_nonneg; p.amax_v = h->amax;
         p.Q16 = w.Q16; p.qinv = w.qinv; p.qn2 = w.qn2; p.qrinv = w.qrinv; p.marg2 = w.marg2; p.thr = w.thr;
         p.count = w.count; p.overflow = w.overflow;
@@ -1981,54 +1830,48 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
         LY_HIP(hipGetLastError());
     }
 
-    // the sampled plan needs the strided-tile support of k_scan_h16; every other kernel starts at level 1
-    const uint32_t plan_tile = (h16 && !binary) ? (narrow ? 128u : 256u) : 0u;
-    static const int no_sample = env_int("LYNSE_HIP_NO_SAMPLE_PLAN", 0);
+    // the sampled plan needs the strided-tile support of k_scan_h16; the popcount kernels start at level 1
+    const uint32_t plan_tile = binary ? 0u : (narrow ? 128u : 256u);
     // wave tiling of the 256 x 256 tile (measured on MI355X, 10M x 768, 256 queries): IP is fastest with <2,4,4,2> and the
     // 3+2-stage split rings, L2 / cosine (norm ring in LDS, more registers in the epilogue) with <4,2,2,4> and 2+2 stages
-#ifdef LYNSE_EXPERIMENTS
-    const int w16env = scan_w16_env<-1>();
-#else
-    constexpr int w16env = -1;  // (the product build compiles each tiling only for the metrics it is the default of)
-#endif
+    // (each tiling is compiled only for the metrics it is the default of)
     const bool filt = mask != nullptr || row_ids != nullptr;
     // (the subset-filter variants of <2,4,4,2> spill 96 B into the MFMA loop: masked 10M x 768 scan 7.5 ms vs 4.9 ms with <4,2,2,4>)
-    const int waves16 = l2n ? 0 : i8c ? 3 : (w16env >= 0 ? w16env : ((metric == M_IP && !filt) ? 3 : 0));
+    const int waves16 = l2n ? 0 : i8c ? 3 : ((metric == M_IP && !filt) ? 3 : 0);
     // the subset-filter kernel variants carry no lane-max code (registers)
     // (k <= 16: the best tile alone supplies k keys, so even a shard sorted by score gets a tight threshold from its best
     // sample tile; up to k = 128 the sample as a whole supplies >= 8 k keys — a clustered shard may then overflow the first
     // stage and fall back to the contiguous plan)
-    const bool can_threshold_only = h16 && !binary && !filt && !no_lane_max_env() && k <= 128;
+    const bool can_threshold_only = !binary && !filt && k <= 128;
     Stage assign_stage{0u, (uint32_t)h->n};   // (CHUNK_ASSIGN) every 256-row tile of the store as a "sample" tile: lane-max keys, no threshold
     assign_stage.sample_tiles = (uint32_t)((h->n + 255) / 256);
     assign_stage.sample_stride = 256;
     const std::vector<Stage> plan = assign ? std::vector<Stage>{assign_stage}
                                     : (sts || coarse_dump) ? std::vector<Stage>{Stage{0u, (uint32_t)h->n}}
-                                        : make_plan(h, k, (level == 0 && (!plan_tile || no_sample)) ? 1 : level, plan_tile, can_threshold_only,
+                                        : make_plan(h, k, (level == 0 && !plan_tile) ? 1 : level, plan_tile, can_threshold_only,
                                                     // large k on the float tilings: the epilogue's cost is the emissions (one sample threshold over 1M x 128,
                                                     // k = 100, admits 1400 rows per query: 87 of the stage's 163 us) — a second threshold stage a quarter of the
                                                     // way in halves them (same box, alternating: 0.241 -> 0.233 ms per batch)
-                                                    (h16 && !i8c && !binary && k >= 64) ? 4u : 0u);
+                                                    (!i8c && !binary && k >= 64) ? 4u : 0u);
     const Stage sample = (!plan.empty() && plan[0].sample_tiles) ? plan[0] : Stage{0, 0};
     res->sampled = sample.sample_tiles != 0;
     // sampled plan: the sample stage only has to produce a threshold -> one key per lane (its best row) instead of every
     // score, as long as that leaves comfortably more than k keys per query (2 WR keys per tile and query)
     const uint32_t sample_keys_per_tile = (small || mid64 || mid128 || waves16 != 0) ? 16u : 8u;  // 2 WR lanes per query and tile x their best 2 rows (WR = 4: 16, <4,2,2,4>: 8)
     // k <= keys per tile: the best sample tile alone supplies k keys (a shard sorted by score still gets a tight threshold)
-    const bool sample_threshold_only = h16 && !binary && !filt && sample.sample_tiles && !no_lane_max_env() && sample_keys_per_tile &&
+    const bool sample_threshold_only = !binary && !filt && sample.sample_tiles && sample_keys_per_tile &&
                                        (k <= sample_keys_per_tile || (uint64_t)sample.sample_tiles * sample_keys_per_tile >= 8ull * k);
     // Fused sample stage (k_scan_h16<.., FS>, LYNSE_HIP_FUSED_SAMPLE=1; OFF by default): the sample tiles are scored by the
     // workgroups of the FIRST threshold stage (one each) and the grid agrees on the thresholds inside that launch — no
     // sample launch, no k_select between.  Needs one sample tile per workgroup, every workgroup resident (grid = CUs) and
     // the register-resident query constants of the certified int8 pass.  Bit-identical results (tests), but MEASURED SLOWER
-    // than the two launches it replaces (MI355X, 1.25M x 768 x 256: 366 us against 33 + 26 + 261 us; s_memtime stamps,
-    // scripts/dbg_fs_stamps.py: first tile 32 us, hand-over 1 27 us, select 15 us, hand-over 2 17 us, restart): a grid-wide
+    // than the two launches it replaces (MI355X, 1.25M x 768 x 256: 366 us against 33 + 26 + 261 us; s_memtime stamps:
+    // first tile 32 us, hand-over 1 27 us, select 15 us, hand-over 2 17 us, restart): a grid-wide
     // hand-over drains the LDS-DMA ring of every CU and idles the chip twice, which costs more than a kernel boundary.
     const int fs_env = fused_sample_env();
-    const bool fs = fs_env != 0 && !debug_flags_env() && i8c && !aug && !cosq && !l2n && !bin_mfma && !mid64 && !mid128 && h->ld8 % 128 == 0 && sample_threshold_only && plan.size() >= 2 && k <= 32 &&
+    const bool fs = fs_env != 0 && i8c && !aug && !cosq && !l2n && !bin_mfma && !mid64 && !mid128 && h->ld8 % 128 == 0 && sample_threshold_only && plan.size() >= 2 && k <= 32 &&
                     sample.sample_tiles == (uint32_t)h->num_cu && (plan[1].r1 - plan[1].r0 + 255) / 256 >= (uint32_t)h->num_cu &&
-                    (uint64_t)k * 50000ull > (uint64_t)sample.sample_tiles * plan_tile &&   // (the stage behind the sample runs the DENSE epilogue)
-                    dense_env_now() != 0;
+                    (uint64_t)k * 50000ull > (uint64_t)sample.sample_tiles * plan_tile;   // (the stage behind the sample runs the DENSE epilogue)
     bool plan_used_segments = false, plan_used_qs = false, plan_qs_sample = false, plan_used_qh = false, plan_qs_m16 = false;
     // the select behind the last stage + exact rescoring + final order in one launch (k_select_final); LYNSE_HIP_FUSED_TAIL=0:
     // the three separate kernels (A/B)
@@ -2085,12 +1928,9 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
             a.row_ids = row_ids;
             a.tile_stride = s.sample_stride;  // 0 = contiguous
             if (!s.sample_tiles && sample.sample_tiles && !sample_threshold_only) { a.skip_stride = sample.sample_stride; a.skip_tiles = sample.sample_tiles; }
-            static const int big_rows = env_int("LYNSE_HIP_SCAN_BR", 256);
-            uint32_t tile_rows = (glds && !small && big_rows == 256) ? 256u : (uint32_t)SCAN_BR;
-            if (h16) tile_rows = narrow ? 128u : 256u;
+            const uint32_t tile_rows = narrow ? 128u : 256u;
             a.V16 = h->rows16; a.ld16 = h->ld16;
             if (i8c) { a.V16 = reinterpret_cast<const _Float16*>(bin_mfma ? (const int8_t*)h->bpm : opd.codes); a.ld16 = bin_mfma ? h->ld_bpm : opd.ld; }
-            if (glds && !small && big_rows == 192 && metric == M_IP) tile_rows = 192u;
             a.qpad = qpad; a.nq = nq; a.nslab = nslab; a.ntiles = (s.r1 - s.r0 + tile_rows - 1) / tile_rows;
             if (s.sample_tiles) a.ntiles = s.sample_tiles;
             a.qinv = w.qinv; a.qn2 = w.qn2; a.qrinv = w.qrinv; a.thr = w.thr; a.vn2 = h->vn2; a.vrinv = h->vrinv;
@@ -2098,18 +1938,6 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
             // sampled plan: the sample stage only has to produce a threshold -> one key per lane (its best row) instead of
             // every score, as long as that leaves at least k keys per query
             if (sample_threshold_only && s.sample_tiles) a.emit_all = 2;
-            const int dbg = debug_flags_env();
-            a.debug_flags = dbg;
-            if (dbg & 2) a.emit_all = 0;
-            if (dbg & 64) {  // phase timing of the LAST (largest) stage: 256 blocks x 8 waves x 4 counters, printed by the host
-                // one region of 8192 words per stage, the LAST stage first (scripts/phase_timing.py reads it at offset 0), cleared per batch
-                static unsigned long long* d_dbg = nullptr;
-                if (!d_dbg) LY_HIP(hipMalloc(&d_dbg, 4096 * 32 * 8));
-                if (si == 0) LY_HIP(hipMemsetAsync(d_dbg, 0, 4096 * 32 * 8, st));
-                a.dbg = d_dbg + (size_t)std::min<size_t>(plan.size() - 1 - si, 15) * 8192;
-                g_dbg_ptr = d_dbg;
-            }
-            const int variant = scan_variant();
             if (i8c && small) {
                 a.candB = w.candB; a.segcnt = w.segcnt;
                 const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu * 2);
@@ -2140,7 +1968,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
                 // ~0.2 one integer compare per accumulator beats level 1 + (mostly) level 2.  Segments are per wave half then.
                 const uint64_t seen_before = s.sample_tiles ? 0 : (sample.sample_tiles ? std::max<uint64_t>((uint64_t)sample.sample_tiles * plan_tile, s.r0) : s.r0);
                 a.dense = (!a.emit_all && a.ld16 % 128 == 0 && seen_before &&
-                           (filt || (dense_env() >= 0 ? dense_env() != 0 : (uint64_t)k * 50000ull > seen_before))) ? 1 : 0;   // (masked: DENSE is the one epilogue compiled with the mask)
+                           (filt || (uint64_t)k * 50000ull > seen_before)) ? 1 : 0;   // (masked: DENSE is the one epilogue compiled with the mask)
                 const bool ag = ag_env() && a.ld16 % 128 == 0 && !a.emit_all && !fs_stage && !filt && !bin_mfma;
                 if (sts) {
                     a.dyn_thr = w.dyn; a.dyn_marg = w.dyn + w.qcap; a.dyn_slot = w.dyn + 2 * (size_t)w.qcap; a.dyn_ks = k;
@@ -2175,11 +2003,10 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
                 if (fs_stage) {
                     a.fs_stride = sample.sample_stride; a.fs_rows = (uint32_t)h->n; a.gsync = w.gsync; a.Qf = Qf; a.marg2 = w.marg2;
                     a.thr_out = w.thr; a.k = k; a.ip_form = ip_form; a.metric = metric;
-                    if (env_str("LYNSE_HIP_FS_STAMPS")) a.debug_flags |= 128;
                 }
                 LY_TRY(launch_scan_i8c(a, launch_grid, st, fs_stage, filt, bin_mfma, qs, m16));
                 }
-            } else if (h16) {
+            } else {
                 a.candB = w.candB; a.segcnt = w.segcnt;
                 if (small) {
                     const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu * 2);
@@ -2203,50 +2030,14 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
                     const uint64_t seen_before = s.sample_tiles ? 0 : (sample.sample_tiles ? std::max<uint64_t>((uint64_t)sample.sample_tiles * plan_tile, s.r0) : s.r0);
                     // (since the grouped branches + shared, prefetched norm loads of the DENSE epilogue it beats the two-level filter
                     // at every threshold tightness measured: 1M x 128 and 4M x 128 / 768, k = 10 and 100)
-                    a.dense = (!a.emit_all && waves16 == 0 && metric != M_IP && !filt && seen_before && (dense_env() >= 0 ? dense_env() != 0 : true)) ? 1 : 0;
-                    if (!a.emit_all) seg_geometry(grid, a.dense ? 4 : ((waves16 == 3 || waves16 == 2) ? 4 : 2), &a.nseg, &a.seg);
+                    a.dense = (!a.emit_all && waves16 == 0 && metric != M_IP && !filt && seen_before) ? 1 : 0;
+                    if (!a.emit_all) seg_geometry(grid, (a.dense || waves16 == 3) ? 4 : 2, &a.nseg, &a.seg);
                     if (qchunks > 1 && !(plan.size() == 1 && (a.emit_all == 1 || (assign && a.emit_all == 2))))
                         return set_error(LYNSE_ERR_INTERNAL, "the widened pipeline runs single-stage emit-all plans only");
-#ifdef LYNSE_EXPERIMENTS
-                    if (waves16 == 2) { LY_TRY((launch_scan_h16<with(F16_IP_256, &H16Cfg::nsv, 2)>(a, metric, grid, st))); }
-                    else
-#endif
                     if (waves16 == 3) { LY_TRY((launch_scan_h16<F16_IP_256>(a, metric, grid, st, qchunks))); }
                     else { LY_TRY((launch_scan_h16<F16_L2_256>(a, metric, grid, st, qchunks))); }
                 }
             }
-#ifdef LYNSE_EXPERIMENTS
-            else if (glds) {
-                const bool scale = h->sv != 1.0f;
-                if (small) {
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu * 2);
-                    LY_TRY((launch_scan_glds<1, 4, 1, 1, 4>(a, metric, scale, grid, st)));
-                } else if (tile_rows == 192) {
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
-                    LY_TRY((launch_scan_glds<4, 2, 2, 3, 4>(a, metric, scale, grid, st)));
-                } else if (tile_rows == 256) {
-                    const int gw16 = scan_w16_env<2>();
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
-                    if (gw16 == 3) LY_TRY((launch_scan_glds<1, 8, 8, 1, 3>(a, metric, scale, grid, st)));
-                    else if (gw16 == 0) LY_TRY((launch_scan_glds<4, 2, 2, 4, 3>(a, metric, scale, grid, st)));
-                    else LY_TRY((launch_scan_glds<2, 4, 4, 2, 3>(a, metric, scale, grid, st)));
-                } else {
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
-                    LY_TRY((launch_scan_glds<4, 2, 2, 2, 4>(a, metric, scale, grid, st)));
-                }
-            } else {
-                if (small) {
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu * 3);
-                    if (variant == 1) LY_TRY((launch_scan<1, 4, 1, 1, 1>(h, a, metric, grid, st)));
-                    else LY_TRY((launch_scan<1, 4, 1, 1, 2>(h, a, metric, grid, st)));
-                } else {
-                    const uint32_t grid = std::min<uint32_t>(a.ntiles, (uint32_t)h->num_cu);
-                    if (variant == 1) LY_TRY((launch_scan<4, 2, 2, 2, 1>(h, a, metric, grid, st)));
-                    else LY_TRY((launch_scan<4, 2, 2, 2, 2>(h, a, metric, grid, st)));
-                }
-            }
-#endif
-            (void)variant;
             a_emit_all_last = (int)a.emit_all;
             st_nseg = a.seg ? a.nseg : 0; st_seg = a.seg;
             plan_used_segments = plan_used_segments || a.seg != 0;
@@ -2266,9 +2057,8 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
         sa.k = k; sa.cap = w.cap; sa.keep_max = w.cap / 2; sa.metric = key_metric; sa.ip_form = ip_form;   // (bin_mfma: best-first +-1 dot products; aug: negated squared L2)
         sa.neg_metric1 = (aug || cosq) ? metric + 1 : 0;
         sa.exact = binary ? 1 : 0;
-        static const int tighten_env = env_int("LYNSE_HIP_TIGHTEN", 1);
         // (worth its ~k exact rescorings per query and stage where the margin is wide — the int8 pass — or k is small)
-        sa.tighten = (!binary && tighten_env && (i8c || k <= 32)) ? 1 : 0;
+        sa.tighten = (!binary && (i8c || k <= 32)) ? 1 : 0;
         sa.drop_sentinels = (mask && emit_all) ? 1 : 0;
         sa.emit_all_n = emit_all ? (s.sample_tiles ? (int)(s.sample_tiles * plan_tile) : (int)(s.r1 - s.r0)) : -1;
         if (!binary && emit_all && sample_threshold_only) {
@@ -2279,9 +2069,6 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
         sa.Qf = Qf; sa.V = score_rows(h); sa.ld = score_ld(h); sa.D = h->dim;
         sa.candB = w.candB; sa.segcnt = w.segcnt; sa.seg = st_seg; sa.nseg = st_nseg;
         sa.abort_word = fs_stage ? w.gsync + 2 : nullptr;
-        if (sel_stamps_on())   // debugging: phase stamps of the select behind stage si ([stage][query][8] behind the fs stamps)
-            sa.stamps = reinterpret_cast<unsigned long long*>(w.gsync + 64) + (size_t)si * 256 * 8;
-        if (fs_stage && env_str("LYNSE_HIP_DEBUG_FS")) return LYNSE_OK;   // debugging: stop behind the fused stage (lynse_hip_debug_workspace)
         if (fused_tail && si + 1 == plan.size()) { sa_last = sa; continue; }  // the last select runs inside k_select_final
         // (round 5, tried: the survivors of the last select handed to the final rescoring in LDS instead of through cand[q] — a store, its
         // acknowledgement and a load less in the tail's chain: 10M 1.8216 / 1.8213 / 1.8527 against 1.8206 / 1.8455 / 1.8381 ms, shard
@@ -2293,7 +2080,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
         LY_HIP(hipGetLastError());
     }
     if (tl_prof && (!binary || bin_mfma)) {   // (batched Hamming on the matrix pipe runs the float pipeline's plans)
-        const uint64_t tiling = plan_used_qs ? 0x81u : plan_used_qh ? 0x82u : (small || mid64) ? 0x14u : ((mid128 || waves16 == 3 || waves16 == 2) ? 0x24u : 0x42u);   // (0x81: query-stationary threshold stages; 0x82: those of the low-dimensional f16 shadow, scan_qh.h)
+        const uint64_t tiling = plan_used_qs ? 0x81u : plan_used_qh ? 0x82u : (small || mid64) ? 0x14u : ((mid128 || waves16 == 3) ? 0x24u : 0x42u);   // (0x81: query-stationary threshold stages; 0x82: those of the low-dimensional f16 shadow, scan_qh.h)
         std::lock_guard<std::mutex> plk(h->prof_mu);
         h->prof.last_plan = (sample.sample_tiles ? 1u : 0u) | ((sample.sample_tiles && sample_threshold_only) ? 2u : 0u) | (i8c ? 4u : 0u) |
                             (plan_used_segments ? 8u : 0u) | (small ? 16u : 0u) | (fs ? 128u : 0u) | ((uint64_t)(plan.size() & 0xff) << 8) | (tiling << 16) |
@@ -2347,7 +2134,7 @@ static int flat_assign_top1_device(lynse_hip_flat* h, const float* d_q, uint64_t
     if (metric < M_IP || metric > M_COS) return set_error(LYNSE_ERR_UNSUPPORTED, "float metrics only");
     LY_WRITER(h, lk);
     LY_TRY(use_device(h));
-    if (scan_variant() != 3 || h->n == 0 || h->n > h->cap || h->qchunk <= QCHUNK || h->packed_only || h->dtype != LYNSE_DTYPE_F32)
+    if (h->n == 0 || h->n > h->cap || h->qchunk <= QCHUNK || h->packed_only || h->dtype != LYNSE_DTYPE_F32)
         return set_error(LYNSE_ERR_UNSUPPORTED, "not the widened float shape of the assignment pass");
     struct Slot0 { int prev; Slot0() : prev(tl_ctx_slot) { tl_ctx_slot = 0; } ~Slot0() { tl_ctx_slot = prev; } } scope;
     LY_TRY(finalize_locked(h));
@@ -2421,7 +2208,6 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         const uint64_t passes = (n_scan + (uint64_t)grid * 128 - 1) / ((uint64_t)grid * 128);
         if (passes > 1) grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, (n_scan + 128 * passes - 1) / (128 * passes)));
     }
-    if (const char* ge = env_str("LYNSE_HIP_SMALL_GRID")) grid = std::max(1u, std::min<uint32_t>(grid, (uint32_t)atoi(ge)));   // development
     auto pow2_at_least = [](uint32_t v) { uint32_t p = 2; while (p < v) p <<= 1; return p; };
     const size_t lds = (size_t)((h->dim + 3) / 4 * 4) * 4 + (size_t)SMALL_NT * 8 + (size_t)pow2_at_least(std::min<uint32_t>(k, grid) * k) * 8 + 64;  // the query, the wave lists (later the heads of the merge), the merge's candidate keys
     LY_TRY(ensure_lds<k_small_search>(160 * 1024 - 1024));
@@ -2432,29 +2218,8 @@ static int run_small(lynse_hip_flat* h, uint32_t nq, uint32_t k, uint32_t out_k,
         LY_TRY(get_event(h, prof->ev_used++, &e1));
         LY_HIP(hipEventRecord(e0, st));
     }
-    static const bool small_dbg = env_on("LYNSE_HIP_SMALL_DBG", false);
-    static unsigned long long* d_dbg = nullptr;
-    if (small_dbg) {   // development: where the time of the fused search goes (stderr; synchronises)
-        if (!d_dbg) LY_HIP(hipMalloc(&d_dbg, (size_t)SMALL_NT * 4 * 8));
-        LY_HIP(hipMemsetAsync(d_dbg, 0, (size_t)SMALL_NT * 4 * 8, st));
-        a.dbg = d_dbg;
-    }
     hipLaunchKernelGGL(k_small_search, dim3(grid), dim3(SMALL_NT), lds, st, a);
     LY_HIP(hipGetLastError());
-    if (small_dbg) {
-        std::vector<unsigned long long> hd((size_t)grid * 4);
-        LY_HIP(hipMemcpyAsync(hd.data(), d_dbg, hd.size() * 8, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipStreamSynchronize(st));
-        unsigned long long t0 = ~0ull, s_last = 0, scan_end = 0, tick = 0, fin = 0, scan_end_min = ~0ull, scan_sum = 0, merge_sum = 0;
-        for (uint32_t b = 0; b < grid; ++b) {
-            t0 = std::min(t0, hd[b * 4]); s_last = std::max(s_last, hd[b * 4]);
-            scan_end = std::max(scan_end, hd[b * 4 + 1]); scan_end_min = std::min(scan_end_min, hd[b * 4 + 1]);
-            tick = std::max(tick, hd[b * 4 + 2]); fin = std::max(fin, hd[b * 4 + 3]);
-            scan_sum += hd[b * 4 + 1] - hd[b * 4]; merge_sum += hd[b * 4 + 2] - hd[b * 4 + 1];
-        }
-        fprintf(stderr, "k_small_search grid %u lds %zu (10 ns ticks from the first start): last start %llu, first scan end %llu, last scan end %llu, last ticket %llu, end %llu; "
-                        "mean scan %llu, mean wave merge %llu\n", grid, lds, s_last - t0, scan_end_min - t0, scan_end - t0, tick - t0, fin - t0, scan_sum / grid, merge_sum / grid);
-    }
     if (timed) {
         LY_HIP(hipEventRecord(e1, st));
         prof->scan_events.push_back({prof->ev_used - 2, (uint64_t)h->n * nq});
@@ -2600,7 +2365,7 @@ static const uint64_t SQ7_AUTO_MIN_ROWS = 10000000ull;
 static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked) {
     const int e = sq7_env();
     if (e == 0 || metric != M_IP || masked || nqc <= 128 || nqc > QCHUNK || h->qchunk > QCHUNK) return false;
-    if (scan_variant() != 3 || qs_variant() < 1 || qs_variant() > 3 || !qs_width_ok(h->ld8, (h->dim + 127) / 128, false)) return false;
+    if (qs_variant() < 1 || qs_variant() > 3 || !qs_width_ok(h->ld8, (h->dim + 127) / 128, false)) return false;
     if (sts_env_on() || fused_sample_env() != 0) return false;   // (those plans keep the SQ8 codes)
     if (h->sq7_strikes.load() >= 3) return false;
     return e == 1 || (h->rows_nonneg && h->n >= SQ7_AUTO_MIN_ROWS);
@@ -2827,7 +2592,7 @@ static bool i8c_eligible(const lynse_hip_flat* h, int metric, bool filtered, uin
     if (metric == M_IP && !lowd_i8 && !ivf && !masked && !filtered && !view && coarse_env() != 2 && h->qchunk <= QCHUNK && qh_shape(h->ld16, nqc))
         return false;
     return (metric == M_IP || l2_ok || cos_ok) && !filtered && !view && nq_ok &&
-           scan_variant() == 3 && coarse_env() != 1 && strikes >= 0 && strikes < 3 && (coarse_env() == 2 || h->n >= 65536);
+           coarse_env() != 1 && strikes >= 0 && strikes < 3 && (coarse_env() == 2 || h->n >= 65536);
 }
 
 // Shared driver: q_src is nq x dim f32 (float metrics / f32 binary queries) or nq x words u64
@@ -2971,8 +2736,6 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
     if (packed_queries && !binary) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "packed queries need a binary metric");
     if (!binary && h->packed_only) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "store holds packed rows; float metrics unavailable");
 
-    if (filtered && !binary && scan_variant() != 3)
-        return set_error(LYNSE_ERR_UNSUPPORTED, "filtered search needs the default scan kernel (LYNSE_HIP_SCAN_VARIANT=3)");
     if (filtered && n_subset && !subset && !bitset_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "subset is NULL");
     // empty store, k == 0 or an empty subset -> empty results, not an error (flat_mmap.rs:832-835, :498-500)
     if (h->n == 0 || k == 0 || (filtered && n_subset == 0)) {
@@ -3124,7 +2887,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
 
     // queries per pipeline pass: QCHUNK; a widened handle (the k-means assignment's centroid store: unfiltered float search of
     // a shard of <= cap rows) takes h->qchunk queries per pass, one k_scan_h16 launch scoring qchunk / 256 chunks (blockIdx.y)
-    const bool wide = h->qchunk > QCHUNK && !binary && !filtered && scan_variant() == 3 && h->n <= h->cap;
+    const bool wide = h->qchunk > QCHUNK && !binary && !filtered && h->n <= h->cap;
     const uint32_t QC = wide ? w.qcap : QCHUNK;
     for (uint64_t q0 = 0; q0 < nq; q0 += QC) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(QC, nq - q0);

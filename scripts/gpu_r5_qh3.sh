@@ -8,5 +8,3 @@ for r in 1 2; do
   LYNSE_HIP_QH=0 c3 "exact QH=0"
   LYNSE_HIP_QH=1 c3 "exact QH=1"
 done
-for g in 3 6 8 32; do LYNSE_HIP_QH=0 LYNSE_HIP_SAMPLE_GROWTH=$g c3 "exact QH=0 growth=$g"; LYNSE_HIP_QH=1 LYNSE_HIP_SAMPLE_GROWTH=$g c3 "exact QH=1 growth=$g"; done
-echo "== qh phases k=100 (exact)"; timeout 300 python scripts/qh_phase_timing.py 2>&1 | grep -v amdgpu.ids | head -4

@@ -9,6 +9,3 @@ for r in 1 2 3; do
   LYNSE_HIP_QH=1 c3 "QH=1"
   LYNSE_HIP_QH=2 c3 "QH=2"
 done
-for g in 6 8 32; do LYNSE_HIP_QH=1 LYNSE_HIP_SAMPLE_GROWTH=$g c3 "QH=1 growth=$g"; done
-echo "== qh=1 phases k=100"; LYNSE_HIP_QH=1 timeout 300 python scripts/qh_phase_timing.py 2>&1 | grep -v amdgpu.ids | head -12
-echo "== qh=1 phases k=100 no emission"; QH_NOEMIT=1 LYNSE_HIP_QH=1 timeout 300 python scripts/qh_phase_timing.py 2>&1 | grep -v amdgpu.ids | head -12

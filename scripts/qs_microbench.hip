@@ -247,7 +247,7 @@ static void launch_qs2(ScanArgs a, uint32_t grid, hipStream_t st) {
 }
 // the round-3 squared-L2 kernel on the plain codes (<4,2,2,4> tiling, DENSE float epilogue, norm ring)
 static void launch_old_l2(ScanArgs a, uint32_t grid, hipStream_t st) {
-    auto k = k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0, 0, true>;
+    auto k = k_scan_h16<4, 2, 2, 4, M_L2, 2, 2, 2, false, false, 0, false, 4, 0, true>;
     constexpr size_t lds = (size_t)(2 * 256 + 2 * 256) * 128 + 4 * 1024;
     static bool done = false;
     if (!done) { set_lds(k, lds); done = true; }
@@ -257,7 +257,7 @@ static void launch_old_l2(ScanArgs a, uint32_t grid, hipStream_t st) {
 }
 template <bool DENSE, int DBG>
 static void launch_old(ScanArgs a, uint32_t grid, hipStream_t st) {
-    auto k = k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, DBG, false, 2, 0, 0, DENSE>;
+    auto k = k_scan_h16<2, 4, 4, 2, M_IP, 3, 2, 2, false, false, DBG, false, 2, 0, DENSE>;
     constexpr size_t lds = (size_t)(3 * 256 + 2 * 256) * 128;
     static bool done = false;
     if (!done) { set_lds(k, lds); done = true; }

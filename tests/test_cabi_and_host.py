@@ -28,6 +28,12 @@ def test_header_symbols_exported_and_bound():
         assert hasattr(raw, s), f"{s} declared in include/lynse_hip.h but not exported"
         assert s in lb.SIGNATURES, f"{s} has no ctypes signature in lynsedb_amd/_lib.py"
     assert set(lb.SIGNATURES) == set(syms)
+    # ... and the converse: the library exports no lynse_hip_* entry point the header does not declare
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", str(lb.LIB_PATH)], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("lynse_hip_")}
+    assert exported == set(syms), f"exported but not declared: {sorted(exported - set(syms))}"
     assert lb.lib.lynse_hip_abi_version() == 1
 
 
