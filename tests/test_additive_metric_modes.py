@@ -1,19 +1,16 @@
 """Host side of the additive metrics (ids 7-10: Manhattan, Chebyshev, Canberra, Bray-Curtis): names, index modes, flags, the host merges,
 and the restatement the GPU tests compare against (tests/additive_ref/additive_ref.c) checked on its own.  No GPU."""
 import ctypes as C
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import lynsedb_amd as L
+from additive_common import build_ref
 from lynsedb_amd import _lib
 from lynsedb_amd.core import ADDITIVE_FLAT_MODES, additive_mode_of
 from lynsedb_amd.shard_node import merge_row_results
 
-HERE = Path(__file__).resolve().parent
 f32 = np.float32
 L1, CHEB, CANB, BRAY = 7, 8, 9, 10
 ALIASES = {L1: ["l1", "manhattan", "cityblock", "L1", "Manhattan"],
@@ -132,20 +129,8 @@ def test_entries_without_an_additive_form_refuse_before_they_touch_a_device():
 # ---- the restatement itself -------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if shutil.which(c)), None)
-    assert cc, "no C compiler for tests/additive_ref/additive_ref.c"
-    so = tmp_path_factory.mktemp("additive_ref") / "libadditive_ref.so"
-    subprocess.run([cc, "-O2", "-shared", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-o", str(so),
-                    str(HERE / "additive_ref" / "additive_ref.c"), "-lm"], check=True)
-    lib = C.CDLL(str(so))
-    lib.add_dist.restype = C.c_float
-    lib.add_dist.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-
-    def dist(m, a, b):
-        a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-        return float(lib.add_dist(m, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), a.size))
-
-    return dist
+    r = build_ref(tmp_path_factory.mktemp("additive_ref"))
+    return lambda m, a, b: float(r.dist(m, a, b))
 
 
 def test_restatement_known_answers(ref):

@@ -3,22 +3,16 @@ C ABI, FlatIndex and the Collection, against a restatement of the four forms (te
 lanes; checked on its own in tests/test_additive_metric_modes.py).  A NaN distance is compared as +inf, the order is (distance, row);
 result ids and f32 distance bits are compared exactly, there are no tolerances."""
 import ctypes as C
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from conftest import oracle_for_every_query
+from additive_common import BRAY, CANB, CHEB, L1, NAME, build_ref
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-HERE = Path(__file__).resolve().parent
 _vp = C.c_void_p
-L1, CHEB, CANB, BRAY = 7, 8, 9, 10
 METRICS = [L1, CHEB, CANB, BRAY]
-NAME = {L1: "l1", CHEB: "chebyshev", CANB: "canberra", BRAY: "bray_curtis"}
 UNSUPPORTED = 9   # LYNSE_ERR_UNSUPPORTED
 
 
@@ -30,41 +24,9 @@ def L():
     return L_
 
 
-class Ref:
-    def __init__(self, lib):
-        self.lib = lib
-
-    def dist(self, m, a, b):
-        a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-        return np.float32(self.lib.add_dist(m, a.ctypes.data_as(_vp), b.ctypes.data_as(_vp), a.size))
-
-    def dists(self, m, queries, data):
-        """[nq, n] distances as the searches report them: a NaN is +inf"""
-        queries, data = np.ascontiguousarray(queries, f32), np.ascontiguousarray(data, f32)
-        out = np.empty((queries.shape[0], data.shape[0]), f32)
-
-        def one(i):
-            self.lib.add_dists(m, queries[i].ctypes.data_as(_vp), data.ctypes.data_as(_vp), data.shape[0], data.shape[1],
-                               out[i].ctypes.data_as(_vp))
-
-        oracle_for_every_query(one, queries.shape[0])
-        out[np.isnan(out)] = np.inf
-        return out
-
-
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if shutil.which(c)), None)
-    assert cc, "no C compiler for tests/additive_ref/additive_ref.c"
-    so = tmp_path_factory.mktemp("additive_ref") / "libadditive_ref.so"
-    subprocess.run([cc, "-O2", "-shared", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-o", str(so),
-                    str(HERE / "additive_ref" / "additive_ref.c"), "-lm"], check=True)
-    lib = C.CDLL(str(so))
-    lib.add_dist.restype = C.c_float
-    lib.add_dist.argtypes = [C.c_int, _vp, _vp, C.c_size_t]
-    lib.add_dists.restype = None
-    lib.add_dists.argtypes = [C.c_int, _vp, _vp, C.c_size_t, C.c_size_t, _vp]
-    return Ref(lib)
+    return build_ref(tmp_path_factory.mktemp("additive_ref"))
 
 
 def topk(d, k, live=None):

@@ -1,16 +1,19 @@
 """GPU parity tests for range search (Collection::search_range, src/engine.rs:6410-6483) through the C ABI and the Collection.  The
 expected answer is built in numpy from the oracle: all_distances(..., IPFORM_SINGLE) on the f32 rows (on the round_f16-decoded rows
 for an F16 shard), packed_distance for the binary metrics, then the pass test, a lexsort by (distance in metric order, row) and the
-cut at max_results.  Row ids, counts, `passed` and f32 distance bits are compared with array_equal; there are no tolerances."""
+cut at max_results.  Row ids, counts, `passed` and f32 distance bits are compared with array_equal; there are no tolerances.  The wide-row
+tests walk every branch of range_plan (a restatement of it next to them asserts which one a width takes) and add L1 and Canberra against the
+additive restatement (tests/additive_ref/additive_ref.c)."""
 import numpy as np
 import pytest
 
 import oracle as O
+from additive_common import CANB, L1, build_ref
 from conftest import oracle_for_every_query
 
 pytestmark = pytest.mark.gpu
 IP, L2, COS = O.IP, O.L2, O.COS
-NAME = {IP: "ip", L2: "l2", COS: "cosine", O.HAMMING: "hamming", O.JACCARD: "jaccard", O.DICE: "dice"}
+NAME = {IP: "ip", L2: "l2", COS: "cosine", O.HAMMING: "hamming", O.JACCARD: "jaccard", O.DICE: "dice", L1: "l1", CANB: "canberra"}
 f32 = np.float32
 NO_ROW = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -211,6 +214,103 @@ def test_f16_shard_scores_its_decoded_rows_with_the_f32_kernels(L, oracle, dim, 
         idx = L.FlatIndex(None, dim, device=0, dtype="f16")
         idx.write(data)
         sweep(idx, case, caps=[n, 9])
+
+
+# ------------------------------------------------------------------------------------- wide rows ----
+RANGE_MAX_Q, RANGE_MAX_ROWS, LDS_78K, LDS_MAX = 16, 128, 78 * 1024, 160 * 1024
+
+
+def range_plan(D, qc):
+    """range_plan of csrc/range_host.inc restated: (TQ, R, budget, LDS bytes) of k_range_scan for rows of D floats and chunks of qc
+    queries, None where a query and a row do not fit"""
+    st = (D + 7) // 8 * 8 + 8
+    row_b, q_b = st * 4, D * 4
+    size = lambda tq, r: (tq * D + 3) // 4 * 16 + r * row_b + tq * 8
+    tq = max(1, min(RANGE_MAX_Q, qc, (24 * 1024) // q_b))
+    budget = LDS_78K
+    if size(tq, 8) > budget:
+        budget = LDS_MAX
+    if size(tq, 1) > budget:
+        tq = 1
+    if size(tq, 1) > budget:
+        return None
+    r = min(RANGE_MAX_ROWS, (budget - size(tq, 0)) // row_b)
+    return tq, r, budget, size(tq, r)
+
+
+# dim -> the (TQ, R, budget) its chunks of 5 queries and of 1 query are meant to hit: fewer than 8 queries at 8 rows under 78 KiB, the
+# whole LDS at 3 / 2 / 1 queries, R down to 1, and the widest row that fits (163,816 of the 163,840 bytes)
+WIDE_PLANS = {
+    769: ((5, 20, LDS_78K), (1, 24, LDS_78K)),
+    1536: ((4, 8, LDS_78K), (1, 11, LDS_78K)),
+    2048: ((3, 16, LDS_MAX), (1, 8, LDS_78K)),
+    2049: ((2, 17, LDS_MAX), (1, 8, LDS_78K)),
+    3073: ((1, 12, LDS_MAX), (1, 12, LDS_MAX)),
+    6145: ((1, 5, LDS_MAX), (1, 5, LDS_MAX)),
+    20000: ((1, 1, LDS_MAX), (1, 1, LDS_MAX)),
+    20472: ((1, 1, LDS_MAX), (1, 1, LDS_MAX)),
+}
+WIDE_ADDITIVE, WIDE_F16 = (2048, 6145, 20472), (1536, 3073, 20472)
+
+
+@pytest.fixture(scope="module")
+def additive_ref(tmp_path_factory):
+    return build_ref(tmp_path_factory.mktemp("additive_ref"))
+
+
+def wide_sweep(L, oracle, additive_ref, dim, dtype="f32"):
+    """n = 70 rows (no multiple of 32, nor of any R but 5 and 1: the last tile is partial; at R = 5, dim 6145, 73 rows as well) against
+    5 queries and against 1: the plan depends on the chunk's query count"""
+    ns = [70]
+    for nq, want in zip((5, 1), WIDE_PLANS[dim]):
+        plan = range_plan(dim, nq)
+        print(f"\ndim {dim}, {nq} queries: TQ {plan[0]}, R {plan[1]}, budget {plan[2]}, LDS bytes {plan[3]}")
+        assert plan[:3] == want and plan[3] <= plan[2], (dim, nq, plan)
+        if plan[1] > 1 and 70 % plan[1] == 0 and 73 not in ns:
+            ns.append(73)
+        assert any(n % plan[1] for n in ns) or plan[1] == 1
+    assert 70 % 32 and range_plan(20472, 1)[3] == 163816 and range_plan(20473, 1) is None and range_plan(20473, 5) is None
+    rng = np.random.default_rng(dim)
+    for n in ns:
+        data = rng.standard_normal((n, dim)).astype(f32)
+        queries = rng.standard_normal((5, dim)).astype(f32)
+        rows = oracle.round_f16(data) if dtype == "f16" else data
+        idx = L.FlatIndex(None, dim, device=0, dtype=dtype)
+        idx.write(data)
+        cases = [Case(queries, all_dists(oracle, queries, rows, m), m) for m in (IP, L2, COS)]
+        if dim in WIDE_ADDITIVE:
+            cases += [Case(queries, additive_ref.raw_dists(m, queries, rows), m) for m in (L1, CANB)]
+        for case in cases:
+            assert np.isfinite(case.D).all()
+            sweep(idx, case, caps=[n + 5, 7])
+            sweep(idx, Case(case.queries[:1], case.D[:1], case.metric), caps=[n + 5, 7])
+
+
+@pytest.mark.parametrize("dim", sorted(WIDE_PLANS))
+def test_wide_rows_take_every_plan(L, oracle, additive_ref, dim):
+    wide_sweep(L, oracle, additive_ref, dim)
+
+
+@pytest.mark.parametrize("dim", WIDE_F16)
+def test_wide_rows_take_every_plan_on_an_f16_shard(L, oracle, additive_ref, dim):
+    wide_sweep(L, oracle, additive_ref, dim, dtype="f16")
+
+
+def test_widest_row_and_the_refusal(L, oracle, additive_ref):
+    """one float more than the widest row: refused on the host before any launch; the handle next to it still answers"""
+    rng = np.random.default_rng(20473)
+    too_wide = L.FlatIndex(None, 20473, device=0)
+    too_wide.write(rng.standard_normal((3, 20473)).astype(f32))
+    widest = L.FlatIndex(None, 20472, device=0)
+    data = rng.standard_normal((70, 20472)).astype(f32)
+    widest.write(data)
+    queries = rng.standard_normal((2, 20472)).astype(f32)
+    case = Case(queries, all_dists(oracle, queries, data, L2), L2)
+    for nq in (2, 1):
+        for name in ("ip", "l2", "cosine", "l1", "canberra"):
+            with pytest.raises(L._lib.LynseUnsupportedError, match="do not fit in LDS"):
+                too_wide.search_range_batch_arrays(np.ones((nq, 20473), f32), np.zeros(nq, f32), 5, name)
+        sweep(widest, case, caps=[75, 7])
 
 
 def packed_dists(oracle, qw, words, metric):
