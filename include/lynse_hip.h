@@ -800,6 +800,64 @@ int lynse_hip_sparse_search(lynse_hip_sparse *h, const uint64_t *q_indptr /* nq+
 int lynse_hip_sparse_profile_enable(lynse_hip_sparse *h, int on);
 int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, int reset);
 
+/* ---- text search: InvertedTextIndex (src/engine.rs:720-1118), index mode BM25-INVERTED ---- */
+
+/* TEXT SEARCH (Collection::text_search, src/engine.rs:5056-5076, over InvertedTextIndex::search, :927-1054).  The caller tokenises
+ * (tokenize_text, :7031-7049), indexes the documents (index_document, :1077-1107) and applies the field selection
+ * (TextFieldSelection, :6967-6989); the library holds the postings of ONE selection and answers BM25 queries over term ids.  The rules:
+ *  1. Store (lynse_hip_text_set, replaces the whole store).  Rows 0 .. n - 1 are the documents of selected length > 0 — in ascending
+ *     user id the library's (score, row) order is the reference's (score, id) order.  doc_len u32[n], every entry >= 1.  Postings in
+ *     CSC form: term_ptr u64[V + 1], post_row u32[nnz] strictly ascending within a term, post_tf u32[nnz] >= 1.  Checked on the host
+ *     before any device work: term_ptr[0] == 0 and non-decreasing, rows < n, n < 2^32 and V < 2^32, tf >= 1, and per row the tf values
+ *     sum to doc_len[row] — LYNSE_ERR_INVALID_ARGUMENT otherwise.  n == 0 or V == 0 empties the store.  doc_len, post_row and post_tf
+ *     live in HBM; term_ptr stays on the host (a query's slot table carries its posting ranges to the device).
+ *  2. A query is its distinct KNOWN terms as (term id, count >= 1) in SLOT ORDER — the order of first occurrence in the query text;
+ *     terms the store has never seen are dropped by the caller (in the reference they have df = 0 and no effect).  nq queries go as
+ *     CSR (q_ptr u64[nq + 1], q_terms, q_counts).  A term id >= V, a term id twice in one query or a count of 0:
+ *     LYNSE_ERR_INVALID_ARGUMENT.
+ *  3. Search.  "Live" = a row the mask leaves in; bitset_words are BitSet words over text rows, treated as lynse_hip_sparse_search
+ *     treats its words (NULL = every row, rows the words do not cover are out, bits at or beyond n are ignored); tombstones and
+ *     subsets are folded in by the caller.  Every f32 step below is a separate round-to-nearest operation, never fused.
+ *     a. docs = live rows, total = the sum of doc_len over them; docs == 0: an empty result.
+ *     b. n_docs = (f32)docs, avg = max((f32)total / (f32)docs, 1.0f).
+ *     c. df_t = live postings of term t; terms with df_t == 0 are ignored from here on; none left: an empty result.
+ *     d. min_df = the least df_t, cutoff = max(sat_mul(min_df, 4), sat_mul(k, 8)) in 64-bit unsigned arithmetic; term t is a
+ *        CANDIDATE TERM if df_t < docs && df_t <= cutoff; if no term qualifies, every term is one.
+ *     e. idf_t = logf(((n_docs - df_t) + 0.5f) / (df_t + 0.5f) + 1.0f) with df_t as f32, by the host's libm; w_t = (f32)count_t * idf_t.
+ *     f. score(row) = 0.0f; then for each slot IN SLOT ORDER whose term occurs in the row with frequency tf:
+ *          score += (w_t * (tf * K)) / (tf + 1.2f * (0.25f + (0.75f * dl) / avg)),  K = 1.2f + 1.0f, tf and dl = doc_len[row] as f32.
+ *        The reference sums in the iteration order of a HashMap, which varies from run to run; SLOT ORDER IS THIS LIBRARY'S PIN.
+ *     g. A row is a result iff it is live, contains at least one candidate term and score > 0.0f; order: score descending, row
+ *        ascending; at most k come back.  k == 0 or a batch of empty queries: an empty result without touching the device.  Layout as
+ *        lynse_hip_sparse_search: stride k, out_counts[q] entries valid, the rest padded with row ~0 and -inf; out_passed[q] (may be
+ *        NULL) = the results before the cut.
+ *     h. Limit: a query of more than 256 distinct known terms is refused with LYNSE_ERR_UNSUPPORTED before any launch (the scan's
+ *        prologue places one slot per lane of its 256-thread workgroup).
+ *     Rules a and c under a mask are exact integer counts from the device (k_text_stats); without a mask df_t is the length of the
+ *     posting list and the corpus totals are kept from set.  Rules b, d and e run on the host: lynse_hip_text_weights is that step
+ *     alone (no handle, no device): out_w[t] = 0 and out_cand[t] = 0 for df[t] == 0, *out_avg = 1 and nothing else for docs == 0.
+ *     The call holds the handle's lock EXCLUSIVELY (the scratch is per handle) and goes in query chunks that keep the score matrix
+ *     at or under 512 MiB.
+ *  4. Profile: scan_launches, scan_us and scan_rows (n per query) of k_text_scan; scan_bytes = what the scan reads = 12 bytes per
+ *     posting of the query's terms with a live posting (row 4 + tf 4 + the gathered doc_len 4; the binary searches of the prologue
+ *     and the mask words are not counted); total_us = first launch to last launch of a chunk.
+ * Without a usable HIP device lynse_hip_text_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+typedef struct lynse_hip_text lynse_hip_text;
+int lynse_hip_text_weights(uint64_t docs, uint64_t total, const uint64_t *df /* T */, const uint32_t *count /* T */, uint32_t T,
+                           uint32_t k, float *out_avg, float *out_w /* T */, uint32_t *out_cand /* T */);
+int lynse_hip_text_create(int device, lynse_hip_text **out);
+int lynse_hip_text_destroy(lynse_hip_text *h);
+int lynse_hip_text_set(lynse_hip_text *h, const uint32_t *doc_len /* n */, uint64_t n, const uint64_t *term_ptr /* V+1 */, uint64_t V,
+                       const uint32_t *post_row, const uint32_t *post_tf);
+int lynse_hip_text_len(lynse_hip_text *h, uint64_t *out_rows, uint64_t *out_terms, uint64_t *out_nnz);
+uint64_t lynse_hip_text_hbm_bytes(lynse_hip_text *h);
+int lynse_hip_text_search(lynse_hip_text *h, const uint64_t *q_ptr /* nq+1 */, const uint32_t *q_terms, const uint32_t *q_counts,
+                          uint64_t nq, uint32_t k, const uint64_t *bitset_words /* NULL = every row */, uint64_t n_words,
+                          uint64_t *out_rows /* nq*k */, float *out_scores, uint32_t *out_counts /* nq */,
+                          uint64_t *out_passed /* nq, may be NULL */);
+int lynse_hip_text_profile_enable(lynse_hip_text *h, int on);
+int lynse_hip_text_profile_get(lynse_hip_text *h, lynse_hip_profile *out, int reset);
+
 /* ---- shard-node glue around a search (host only, no device work) ---- */
 
 /* Collection::filter_tombstoned_limit (src/engine.rs:3286-3308): drop the tombstoned ids, keep the order, at most

@@ -4,10 +4,10 @@ Importing this package loads liblynse_hip.so (hand-written HIP kernels for gfx95
 CPU fallback: the import fails loudly if the extension has not been built.
 """
 from . import _lib  # noqa: F401  (raises ImportError when the HIP extension is missing)
-from .core import (BitSet, Collection, DatabaseManager, FlatIndex, IvfFlatIndex, SearchResult, SparseIndex, SpannIndex,  # noqa: F401
+from .core import (BitSet, Collection, DatabaseManager, FlatIndex, IvfFlatIndex, SearchResult, SparseIndex, SpannIndex, TextIndex,  # noqa: F401
                    default_device, visible_devices, merge_topk, metric_from_index_mode, metric_from_str, normalize_sparse_vector,
-                   py_compute_distance, py_top_k_search)
+                   py_compute_distance, py_top_k_search, tokenize_text)
 
-__all__ = ["BitSet", "Collection", "DatabaseManager", "FlatIndex", "IvfFlatIndex", "SearchResult", "SparseIndex", "SpannIndex", "default_device", "visible_devices",
-           "merge_topk", "metric_from_index_mode", "metric_from_str", "normalize_sparse_vector", "py_compute_distance", "py_top_k_search"]
+__all__ = ["BitSet", "Collection", "DatabaseManager", "FlatIndex", "IvfFlatIndex", "SearchResult", "SparseIndex", "SpannIndex", "TextIndex", "default_device", "visible_devices",
+           "merge_topk", "metric_from_index_mode", "metric_from_str", "normalize_sparse_vector", "py_compute_distance", "py_top_k_search", "tokenize_text"]
 __version__ = "0.1.0"

@@ -179,6 +179,15 @@ SIGNATURES = {
     "lynse_hip_sparse_search": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "lynse_hip_sparse_profile_enable": (C.c_int, [_vp, C.c_int]),
     "lynse_hip_sparse_profile_get": (C.c_int, [_vp, C.POINTER(Profile), C.c_int]),
+    "lynse_hip_text_weights": (C.c_int, [C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _vp, _vp]),
+    "lynse_hip_text_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_text_destroy": (C.c_int, [_vp]),
+    "lynse_hip_text_set": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "lynse_hip_text_len": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "lynse_hip_text_hbm_bytes": (C.c_uint64, [_vp]),
+    "lynse_hip_text_search": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "lynse_hip_text_profile_enable": (C.c_int, [_vp, C.c_int]),
+    "lynse_hip_text_profile_get": (C.c_int, [_vp, C.POINTER(Profile), C.c_int]),
 }
 
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int)   # lynse_hip_reduce_fn

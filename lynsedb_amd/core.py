@@ -1348,6 +1348,195 @@ class SparseIndex:
         return {f: getattr(p, f) for f, _ in _lib.Profile._fields_}
 
 
+# ---------------------------------------------------------------------------------------------
+# Text search (InvertedTextIndex, src/engine.rs:720-1118; index modes BM25-INVERTED, HYBRID-RRF, HYBRID-WEIGHTED)
+# ---------------------------------------------------------------------------------------------
+TEXT_INDEX_MODE = "BM25-INVERTED"
+TEXT_SCAN_MODE = "BM25-SCAN"      # what the reference reports while no document holds text (engine.rs:5219-5223)
+TEXT_MAX_TERMS = 256              # include/lynse_hip.h, TEXT SEARCH rule 3h
+
+
+def tokenize_text(text: str) -> list:
+    """`tokenize_text` / `normalize_text_token` (engine.rs:7031-7049): split at every character that is not alphanumeric, drop the
+    empty pieces, keep an ASCII token without an upper-case letter as it is and lower-case any other.  `str.isalnum` stands for
+    Rust's `char::is_alphanumeric`: equal on ASCII and wherever Alphabetic ∪ N* coincides with it (DESIGN §20 names the divergence)."""
+    out, cur = [], []
+    for ch in text:
+        if ch.isalnum():
+            cur.append(ch)
+        elif cur:
+            out.append("".join(cur))
+            cur = []
+    if cur:
+        out.append("".join(cur))
+    return [t if t.isascii() and not any("A" <= c <= "Z" for c in t) else t.lower() for t in out]
+
+
+def text_term_counts(value, counts: Optional[dict] = None) -> dict:
+    """`append_searchable_json_terms` (engine.rs:7051-7068): the term counts of the strings in a JSON-like value, lists and dict
+    values followed; None, bool, int and float contribute nothing."""
+    counts = {} if counts is None else counts
+    if isinstance(value, str):
+        for t in tokenize_text(value):
+            counts[t] = counts.get(t, 0) + 1
+    elif isinstance(value, (list, tuple)):
+        for v in value:
+            text_term_counts(v, counts)
+    elif isinstance(value, dict):
+        for v in value.values():
+            text_term_counts(v, counts)
+    return counts   # (None, bool — tested before int by not being tested at all —, int, float: nothing)
+
+
+def index_text_document(fields: dict) -> dict:
+    """`index_document` (engine.rs:1077-1107): {field: {term: tf}} for the top-level fields of length > 0; {} = not indexed."""
+    doc = {}
+    for name, value in fields.items():
+        counts = text_term_counts(value)
+        if counts:
+            doc[str(name)] = counts
+    return doc
+
+
+def text_weights(docs: int, total: int, df, count, k: int) -> tuple:
+    """Rules b, d and e of TEXT SEARCH by lynse_hip_text_weights (host code, no device) -> (avg f32, w f32[T], cand u32[T])."""
+    df = np.ascontiguousarray(np.asarray(df).reshape(-1), dtype=np.uint64)
+    count = np.ascontiguousarray(np.asarray(count).reshape(-1), dtype=np.uint32)
+    if df.size != count.size:
+        raise ValueError("df and count must have one entry per term")
+    avg = C.c_float(0.0)
+    w, cand = np.zeros(max(df.size, 1), np.float32), np.zeros(max(df.size, 1), np.uint32)
+    check(lib.lynse_hip_text_weights(int(docs), int(total), _ptr(df), _ptr(count), df.size, int(k), C.byref(avg), _ptr(w), _ptr(cand)))
+    return np.float32(avg.value), w[:df.size], cand[:df.size]
+
+
+def normalize_scores(scores, ascending: bool) -> np.ndarray:
+    """`normalize_scores` (engine.rs:7188-7217) on f32: min and max over the finite scores; all 1.0 when there is none or
+    |max - min| <= FLT_EPSILON; else clamp((s - min) / (max - min), 0, 1), and 1 - x for an ascending metric."""
+    s = np.asarray(scores, dtype=np.float32).reshape(-1)
+    fin = s[np.isfinite(s)]
+    if s.size == 0:
+        return s.copy()
+    if fin.size == 0 or np.abs(np.float32(fin.max() - fin.min())) <= np.finfo(np.float32).eps:
+        return np.ones(s.size, np.float32)
+    lo, span = fin.min(), np.float32(fin.max() - fin.min())
+    with np.errstate(all="ignore"):
+        x = np.clip(((s - lo) / span).astype(np.float32), np.float32(0.0), np.float32(1.0))
+        return (np.float32(1.0) - x).astype(np.float32) if ascending else x
+
+
+def hybrid_fuse(vector_leg, text_leg, k: int, fusion: str = "rrf", vector_weight: float = 1.0, text_weight: float = 1.0,
+                rrf_k: float = 60.0, ascending: bool = False) -> tuple:
+    """The fusion of `hybrid_search` (engine.rs:5100-5145; add_fused_scores, :7219-7237) on numpy f32 scalars in the reference's
+    operation order.  A leg is (ids, scores) best first, or None; the vector leg is normalised with `ascending`, the text leg never
+    is ascending.  Rank r (from 0) of a leg adds score * weight ("weighted", case-insensitive) or weight / ((max(rrf_k, 1) + r) + 1)
+    to its id; sums start at 0 and take the vector leg first.  Order: fused descending, id ascending (the reference leaves ties to
+    hash order); cut at k -> (ids i64, fused f32)."""
+    f32 = np.float32
+    weighted = str(fusion).lower() == "weighted"
+    fused: dict = {}
+    for leg, weight, asc in ((vector_leg, vector_weight, ascending), (text_leg, text_weight, False)):
+        if leg is None:
+            continue
+        ids, scores = leg
+        norm = normalize_scores(scores, asc)
+        wt = max(f32(weight), f32(0.0))
+        base = max(f32(rrf_k), f32(1.0))
+        for r, i in enumerate(np.asarray(ids).reshape(-1)):
+            c = f32(norm[r] * wt) if weighted else f32(wt / f32(f32(base + f32(r)) + f32(1.0)))
+            fused[int(i)] = f32(fused.get(int(i), f32(0.0)) + c)
+    order = sorted(fused.items(), key=lambda e: (-float(e[1]), e[0]))[:max(int(k), 0)]
+    return np.array([e[0] for e in order], np.int64), np.array([e[1] for e in order], np.float32)
+
+
+class TextIndex:
+    """The posting lists of one field selection in HBM and their BM25 scan (include/lynse_hip.h, TEXT SEARCH): this build's device
+    half of the reference's InvertedTextIndex.  Rows are documents, terms are ids; tokenising and field selection are the caller's."""
+
+    def __init__(self, device: Optional[int] = None):
+        self._h = C.c_void_p()
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_text_create(dev, C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.lynse_hip_text_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set(self, doc_len, term_ptr, post_row, post_tf) -> None:
+        """Replaces the whole store: doc_len u32[n], and the postings in CSC form (term_ptr u64[V + 1], post_row u32, post_tf u32)."""
+        doc_len = np.ascontiguousarray(np.asarray(doc_len).reshape(-1), dtype=np.uint32)
+        term_ptr = np.ascontiguousarray(np.asarray(term_ptr).reshape(-1), dtype=np.uint64)
+        post_row = np.ascontiguousarray(np.asarray(post_row).reshape(-1), dtype=np.uint32)
+        post_tf = np.ascontiguousarray(np.asarray(post_tf).reshape(-1), dtype=np.uint32)
+        if term_ptr.size == 0:
+            term_ptr = np.zeros(1, np.uint64)
+        if post_row.size != post_tf.size or int(term_ptr.max()) > post_row.size:
+            raise ValueError("text postings do not match: term_ptr must stay within len(post_row) == len(post_tf)")
+        check(lib.lynse_hip_text_set(self._h, _ptr(doc_len), doc_len.size, _ptr(term_ptr), term_ptr.size - 1, _ptr(post_row), _ptr(post_tf)))
+
+    def _len(self) -> tuple:
+        rows, terms, nnz = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib.lynse_hip_text_len(self._h, C.byref(rows), C.byref(terms), C.byref(nnz)))
+        return int(rows.value), int(terms.value), int(nnz.value)
+
+    def __len__(self) -> int:
+        return self._len()[0]
+
+    @property
+    def terms(self) -> int:
+        return self._len()[1]
+
+    @property
+    def nnz(self) -> int:
+        return self._len()[2]
+
+    def hbm_bytes(self) -> int:
+        return int(lib.lynse_hip_text_hbm_bytes(self._h))
+
+    def search_batch_arrays(self, q_ptr, q_terms, q_counts, k: int, words=None):
+        """BM25 for nq queries in CSR of (term id, count) in slot order -> (rows u64[nq, k], scores f32[nq, k], counts u32[nq],
+        passed u64[nq]): counts[q] = min(passed[q], k) entries valid, best first by (score descending, row ascending), the rest row
+        ~0 and -inf.  `words` are BitSet words over the text rows (None = every row)."""
+        q_ptr = np.ascontiguousarray(np.asarray(q_ptr).reshape(-1), dtype=np.uint64)
+        q_terms = np.ascontiguousarray(np.asarray(q_terms).reshape(-1), dtype=np.uint32)
+        q_counts = np.ascontiguousarray(np.asarray(q_counts).reshape(-1), dtype=np.uint32)
+        if q_ptr.size == 0:
+            q_ptr = np.zeros(1, np.uint64)
+        if q_terms.size != q_counts.size or int(q_ptr.max()) > q_terms.size:
+            raise ValueError("text query arrays do not match: q_ptr must stay within len(q_terms) == len(q_counts)")
+        nq, k = q_ptr.size - 1, int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        rows = np.full((nq, k), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        scores = np.full((nq, k), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        passed = np.zeros(nq, np.uint64)
+        if nq == 0:
+            return rows, scores, counts, passed
+        n_words = 0
+        if words is not None:
+            words = np.ascontiguousarray(np.asarray(words).reshape(-1), dtype=np.uint64)
+            n_words = int(words.size)
+            if n_words == 0:   # an empty mask is still a mask (NULL would mean every row)
+                words = np.zeros(1, np.uint64)
+        check(lib.lynse_hip_text_search(self._h, _ptr(q_ptr), _ptr(q_terms), _ptr(q_counts), nq, k,
+                                        None if words is None else _ptr(words), n_words, _ptr(rows), _ptr(scores), _ptr(counts), _ptr(passed)))
+        return rows, scores, counts, passed
+
+    def profile_enable(self, on=True) -> None:
+        check(lib.lynse_hip_text_profile_enable(self._h, int(bool(on))))
+
+    def profile_get(self, reset: bool = True) -> dict:
+        p = _lib.Profile()
+        check(lib.lynse_hip_text_profile_get(self._h, C.byref(p), 1 if reset else 0))
+        return {f: getattr(p, f) for f, _ in _lib.Profile._fields_}
+
+
 def py_compute_distance(a, b, metric: str) -> float:
     """src/python/mod.rs:2161-2185."""
     m = metric_from_str(metric)
@@ -1492,6 +1681,12 @@ class Collection:
         self._sparse_ids = np.zeros(0, np.int64)   # the ids of the uploaded sparse rows, ascending: sparse row -> user id
         self._sparse_index = None       # SparseIndex, created by the first sparse search
         self._sparse_dirty = False      # the store changed since the last upload
+        self._docs: dict = {}           # user id -> {field: {term: tf}} (InvertedTextIndex.postings / doc_lengths), flushed or pending rows alike
+        self._text_index = None         # TextIndex, created by the first text search
+        self._text_key = None           # the field selection the device store holds: () = all fields, else the sorted names
+        self._text_dirty = True         # the documents changed since the last upload
+        self._text_ids = np.zeros(0, np.int64)   # the ids of the uploaded text rows, ascending: text row -> user id
+        self._text_vocab: dict = {}     # term -> term id of the uploaded store
 
     def name(self) -> str:
         return self._name
@@ -1506,8 +1701,19 @@ class Collection:
             raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {a.shape[1]}")
         if len(ids) != a.shape[0]:
             raise RuntimeError("ids length must match the number of vectors")
-        if fields is not None:
-            raise NotImplementedError("field metadata is outside the FLAT/IVF hot path (SURVEY.md §2 #20)")
+        if fields is not None:   # the text index only (insert_documents, engine.rs:882-908): the field store and its filters are out of scope
+            fields = list(fields)
+            if len(fields) != len(ids):
+                raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match field count ({len(fields)})")
+            if not all(isinstance(f, dict) for f in fields):
+                raise TypeError("fields must be a list of dicts, one per id")
+            for i, f in zip(ids, fields):
+                doc = index_text_document(f)
+                if doc:
+                    self._docs[int(i)] = doc
+                    self._text_dirty = True
+                elif self._docs.pop(int(i), None) is not None:   # a document with no text field left is not indexed: a re-added id loses its old one
+                    self._text_dirty = True
         if a.shape[0] == 0:
             return
         self._pending_vecs.append(np.array(a, dtype=np.float32, copy=True))
@@ -1961,6 +2167,128 @@ class Collection:
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
         return self.batch_search_sparse([vector], k, subset=subset)[0]
+
+    # -- text search (engine.rs:5056-5161, :927-1054) -------------------------------------------
+    def text_len(self) -> int:
+        return len(self._docs)
+
+    def _text_upload(self, text_fields) -> None:
+        """The postings of the documents under one field selection (TextFieldSelection, engine.rs:6967-6989: None or [] = all fields),
+        rows in ascending id order so that (score, row ascending) is the reference's (score, id ascending); rebuilt when the
+        selection or the documents changed."""
+        key = tuple(sorted({str(f) for f in text_fields})) if text_fields else ()
+        if self._text_index is None:
+            self._text_index = TextIndex(self._device)
+        if not self._text_dirty and key == self._text_key:
+            return
+        ids, lens, triples, vocab = [], [], [], {}
+        for i in sorted(self._docs):
+            tf: dict = {}
+            for name, counts in self._docs[i].items():
+                if not key or name in key:
+                    for t, c in counts.items():
+                        tf[t] = tf.get(t, 0) + c
+            if not tf:   # selected length 0: the document does not exist for this selection
+                continue
+            row = len(ids)
+            ids.append(i)
+            lens.append(sum(tf.values()))
+            for t, c in tf.items():
+                triples.append((vocab.setdefault(t, len(vocab)), row, c))
+        tr = np.array(triples, dtype=np.int64).reshape(-1, 3)
+        tr = tr[np.lexsort((tr[:, 1], tr[:, 0]))]
+        term_ptr = np.zeros(len(vocab) + 1, np.uint64)
+        np.cumsum(np.bincount(tr[:, 0], minlength=len(vocab)), out=term_ptr[1:])
+        self._text_index.set(np.array(lens, np.uint32), term_ptr, tr[:, 1].astype(np.uint32), tr[:, 2].astype(np.uint32))
+        self._text_ids, self._text_vocab, self._text_key, self._text_dirty = np.array(ids, np.int64), vocab, key, False
+
+    def _text_words(self, subset) -> Optional[np.ndarray]:
+        """the BitSet words over text rows of a dense-row subset minus the tombstoned ids; None = every row"""
+        n = int(self._text_ids.size)
+        words = None
+        if subset is not None:
+            rows = self._subset_rows(subset).astype(np.int64)
+            rows = rows[rows < len(self._flat) + self._pending_rows]
+            allowed = self._user_ids(rows)
+            words = BitSet.from_rows(np.nonzero(np.isin(self._text_ids, allowed))[0], n).words
+        if self._tombstone:
+            dead = np.nonzero(np.isin(self._text_ids, np.fromiter(self._tombstone, dtype=np.int64, count=len(self._tombstone))))[0]
+            if dead.size:
+                if words is None:
+                    words = BitSet.from_rows(np.arange(n, dtype=np.uint64), n).words
+                words = words & ~BitSet.from_rows(dead, n).words
+        return words
+
+    def batch_text_search(self, texts, text_fields=None, k: Optional[int] = None, subset=None) -> list:
+        """`text_search` for a batch of query texts sharing one field selection and one subset, in ONE device call (this build's
+        addition)."""
+        k = 10 if k is None else int(k)
+        if k < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        texts = [str(t) for t in texts]
+        if not self._docs:   # no document holds text: the reference's scan fallback over nothing
+            return [SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), TEXT_SCAN_MODE, self._dim, k) for _ in texts]
+        empty = lambda: SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), TEXT_INDEX_MODE, self._dim, k)   # noqa: E731
+        if k == 0 or not texts:
+            return [empty() for _ in texts]
+        self._text_upload(text_fields)
+        q_ptr, q_terms, q_counts = [0], [], []
+        for text in texts:   # the distinct known terms in the order of their first occurrence, with their counts
+            counts: dict = {}
+            for t in tokenize_text(text):
+                tid = self._text_vocab.get(t)
+                if tid is not None:   # a term the store has never seen has df = 0: no effect
+                    counts[tid] = counts.get(tid, 0) + 1
+            q_terms.extend(counts.keys())
+            q_counts.extend(counts.values())
+            q_ptr.append(len(q_terms))
+        if not q_terms or self._text_ids.size == 0:
+            return [empty() for _ in texts]
+        rows, scores, counts_, _ = self._text_index.search_batch_arrays(q_ptr, q_terms, q_counts, k, self._text_words(subset))
+        out = []
+        for i in range(len(texts)):
+            c = int(counts_[i])
+            out.append(SearchResult(self._text_ids[rows[i, :c].astype(np.int64)], scores[i, :c].copy(), TEXT_INDEX_MODE, self._dim, k))
+        return out
+
+    def text_search(self, text: str, text_fields=None, k: Optional[int] = 10, where_expr: Optional[str] = None, subset=None) -> SearchResult:
+        """`Collection.bm25_search` / `text_search` (src/python/mod.rs:1273-1300 over engine.rs:5060-5076 and InvertedTextIndex::search,
+        :927-1054): BM25 over the `fields` given to add_items, by (score descending, id ascending), at most k; the scores are in
+        `distances()`, the mode is BM25-INVERTED (BM25-SCAN and empty while no document holds text), the dimension the collection's.
+        Tombstoned ids leave the corpus statistics too.  `subset=` (a BitSet or dense row indices) stands in for the resolved
+        `where_expr`, as on `search`.  The sums run in the order of the terms' first occurrence in `text` (include/lynse_hip.h, TEXT
+        SEARCH rule 3f)."""
+        if where_expr:
+            raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
+        return self.batch_text_search([text], text_fields, k, subset=subset)[0]
+
+    def hybrid_search(self, vector=None, text: Optional[str] = None, k: Optional[int] = 10, where_expr: Optional[str] = None, text_fields=None,
+                      fusion: str = "rrf", vector_weight: float = 1.0, text_weight: float = 1.0, rrf_k: float = 60.0,
+                      candidate_limit: Optional[int] = None, nprobe: int = 10, subset=None) -> SearchResult:
+        """`Collection.hybrid_search` (src/python/mod.rs:1302-1340 over engine.rs:5079-5161): the vector search and the text search,
+        each with k = candidate_limit (default max(4k, k), at least k and 1), fused by reciprocal rank ("rrf") or by normalised
+        weighted scores ("weighted") — `hybrid_fuse`.  A blank text with a vector is the vector leg alone.  The mode is HYBRID-RRF or
+        HYBRID-WEIGHTED."""
+        if where_expr:
+            raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
+        k = 10 if k is None else int(k)
+        if k < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        has_text = text is not None and bool(str(text).strip())
+        if vector is None and not has_text:
+            raise RuntimeError("Invalid argument: hybrid_search requires a vector, text, or both")
+        limit = max(int(candidate_limit) if candidate_limit else max(4 * k, k), k, 1)
+        v_leg = t_leg = None
+        if vector is not None:
+            r = self.search(vector, limit, None, nprobe, subset=subset)
+            v_leg = (r.ids(), r.distances())
+        if has_text:
+            r = self.text_search(str(text), text_fields, limit, subset=subset)
+            t_leg = (r.ids(), r.distances())
+        ascending = bool(lib.lynse_hip_metric_is_ascending(self._metric))
+        ids, fused = hybrid_fuse(v_leg, t_leg, k, fusion, vector_weight, text_weight, rrf_k, ascending)
+        mode = "HYBRID-WEIGHTED" if str(fusion).lower() == "weighted" else "HYBRID-RRF"
+        return SearchResult(ids, fused, mode, self._dim, k)
 
     def search_range(self, vector, threshold: float, max_results: int = 1000, subset=None):
         """`Collection.search_range` (src/python/mod.rs:1784-1795 over Collection::search_range, src/engine.rs:6410-6483): the exact scan

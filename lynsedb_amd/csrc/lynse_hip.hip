@@ -33,6 +33,7 @@
 #include "range.h"
 #include "additive.h"
 #include "sparse.h"
+#include "text.h"
 #include "spann.h"
 
 using namespace lynse;
@@ -3573,3 +3574,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "range_host.inc"
 #include "additive_host.inc"
 #include "sparse_host.inc"
+#include "text_host.inc"
