@@ -364,6 +364,66 @@ int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat *h, const float *queries, uint
                                    uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
 int lynse_hip_flat_hnsw_stage_times(lynse_hip_flat *h, double *out6, int reset);
 int lynse_hip_hnsw_levels(uint64_t seed, uint32_t m, int32_t max_level, uint64_t n, uint32_t *out);
+/* DISKANN-{L2,COS,COSINE} (DiskANNIndex, src/index/diskann.rs, its in-memory full-precision form: search_graph over the rows
+ * themselves): a flat neighbour graph of degree r over the rows of a FLAT handle, built by the reference's batched Vamana passes and
+ * searched by its beam search.  f32 handles and l2 / cosine only.  The build is a function of the rows, the parameters and a random
+ * stream, and is restated here list for list; the reference draws from StdRng, this library from its own stream (rule 1).  The rules:
+ *  0. d(a, b) is the graph distance of the HNSW block (compute_distance_f32 in the single-row form, NaN -> +inf at once, symmetric bit
+ *     for bit).  r in 1..64 (one lane per stored neighbour), l in 1..4096 and l := max(l, r), alpha a finite f32 >= 1,
+ *     max_degree := max(max_degree, r), which makes the stored degree r (diskann.rs:236-237, :980).  The reference's defaults: r 16,
+ *     l 64, alpha 1.2; the Collection passes seed 42.  No environment variable is read.
+ *  1. Random stream: w_i = the i-th next_u64() of SmallRng::seed_from_u64(seed) (the stream of lynse_hip_rabitq_sign_words).
+ *     draw(b) = ((w >> 32) * b) >> 32 for 1 <= b <= 2^32, one word.  shuffle(a): for i = len - 1 down to 1: j = draw(i + 1), swap a[i]
+ *     and a[j].  n <= 1 consumes no word; otherwise, in this order: shuffle A of 0..n, shuffle B of 0..n, the initial graph, shuffle C.
+ *  2. Entry point (choose_medoid, :767-795): refs = the first min(32, n) of A, cands = the first min(64, n) of B; for each candidate in
+ *     order sum = 0.0f, sum += d(c, ref) over the refs in order (f32); the entry is the first candidate with sum < best_sum (from
+ *     +inf), cands[0] when no sum is finite.
+ *  3. Initial graph (:798-816): for i = 0 .. n - 1 draw j = draw(n) until min(r, n - 1) distinct j != i are chosen, stored as drawn.
+ *  4. Order: C, then the entry swapped into position 0 with whatever is there (:1103-1107).
+ *  5. Passes (:1084-1113, :1025-1076): one with alpha' = 1, a second with alpha' = alpha iff alpha > 1 + FLT_EPSILON.  A pass walks the
+ *     order in batches of 256; for every p of a batch, against the graph as it stood when the batch began: the search of rule 8 with
+ *     the row of p as the query, ef = L_b = max(min(l, 128), r) and 32 anchors; candidates = its results and (d(p, nb), nb) for nb in
+ *     adj[p]; the forward list is prune(p, candidates, alpha').
+ *  6. prune (robust_prune, :830-875, ascending branch): drop p, keep one entry per node (equal nodes carry equal bits), order by
+ *     (d, node) — the reference's unstable sort leaves ties open, this order is the library's pin; until r are selected or none remain:
+ *     select the first remaining b, keep a remaining v != b iff alpha' * d(b, v) > d(p, v) (one f32 multiply rounded once, then the
+ *     comparison).  The output is in selection order.
+ *  7. Commit (apply_vamana_updates, :979-1017), in batch order: install all forward lists; for each (src, list) in batch order and each
+ *     dst != src in list order append src to adj[dst] unless it is there (after the installs: every src of a batch is another node) —
+ *     the append slot is the number of earlier effective edges to the same dst, computed as such (a sort), never the arrival order of
+ *     an atomic; every dst whose list is now longer than r (at most r + 256): adj[dst] = prune(dst, {(d(dst, x), x)}, alpha').  A list
+ *     of at most r entries keeps its stored order, which the search follows.
+ *  8. Search (search_graph, :880-973, unfiltered; search, :1258-1269, :1326): ef = min(max(ef_query, l, 10 k), n).  Starts
+ *     (search_entry_points, :159-174): the entry, then a n / A for a = 0 .. A - 1, A = min(anchors, n), in u64, skipping a value equal
+ *     to the entry; anchors = 8 for queries and 32 in the build.  Every start is marked visited, scored and pushed to C; R is the best
+ *     ef of the starts by (d, node), no admission test.  Then the loop of HNSW rule 5 unchanged, every pop, eviction and the final
+ *     sort by (dist, node).  Output: the best min(k, |R|), in the layout of lynse_hip_flat_search_f32.
+ *  9. The graph covers the first n_diskann rows.  Build and load replace an earlier DiskANN graph; an HNSW graph on the handle is a
+ *     separate state and is left alone.  The exact searches of the handle are unchanged.
+ *  Refused with LYNSE_ERR_UNSUPPORTED: an F16 shard, a packed-only or row-mapped handle, any metric but l2 / cosine, r, l, alpha or an
+ *  ef outside its bounds, outstanding tickets, a beam (24 bytes per ef) or a row that does not fit the 160 KiB of LDS.
+ *  LYNSE_ERR_INVALID_ARGUMENT: a search metric other than the build metric; in load, a neighbour >= n or an entry >= n.
+ * lynse_hip_flat_build_diskann: max_batches = 0 is the whole build; otherwise the build stops after that many batches, counted across
+ * both passes, and the graph is installed as it stands (a test instrument: a build is some 2 n / 256 dependent steps).
+ * lynse_hip_flat_load_diskann takes adj[n][r] padded with 0xFFFFFFFF; pads inside a list and a neighbour named twice are dropped.
+ * lynse_hip_flat_diskann_params: info = {metric, r, l, entry}, alpha (0 for a loaded graph) and n_diskann, all 0 without an index, and
+ * adj when it is not NULL.  lynse_hip_flat_diskann_stage_times: out8[0..2] the search / prune / commit microseconds of the last build
+ * (host clock; measured only by a build that ran with profiling on, which waits after every stage — a plain build enqueues every
+ * batch without a host round trip and reports 0), out8[3] its host random draws, out8[4] the whole build; with profiling on,
+ * out8[5] searches, out8[6] their kernel microseconds (HIP events), out8[7] the distances they scored; reset != 0 clears the last three.
+ * lynse_hip_vamana_draws (host only): the products of rules 1-4 that do not depend on the rows — refs[min(32, n)], cands[min(64, n)],
+ * the order before the entry swap [n] and the initial graph adj0[n][r], padded — for known-answer tests. */
+int lynse_hip_flat_build_diskann(lynse_hip_flat *h, int metric, uint32_t r, uint32_t l, float alpha, uint32_t max_degree,
+                                 uint64_t seed, uint64_t max_batches);
+int lynse_hip_flat_load_diskann(lynse_hip_flat *h, int metric, uint32_t r, uint32_t l, const uint32_t *adj, uint64_t n,
+                                uint32_t entry);
+int lynse_hip_flat_diskann_params(lynse_hip_flat *h, uint32_t *info, float *alpha, uint64_t *n_diskann, uint32_t *adj);
+int lynse_hip_flat_drop_diskann(lynse_hip_flat *h);
+int lynse_hip_flat_search_diskann_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric,
+                                      uint32_t ef_query, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
+int lynse_hip_flat_diskann_stage_times(lynse_hip_flat *h, double *out8, int reset);
+int lynse_hip_vamana_draws(uint64_t seed, uint64_t n, uint32_t r, uint32_t *refs, uint32_t *cands, uint32_t *order,
+                           uint32_t *adj0);
 /* Range search (Collection::search_range, src/engine.rs:6410-6483): every row of the handle is scored with the single-row kernel
  * (compute_distance_f32) and the rows on the passing side of the caller's threshold come back, best first, at most max_results of
  * them.  One threshold per query.  The rules:

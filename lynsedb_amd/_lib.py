@@ -89,6 +89,13 @@ SIGNATURES = {
     "lynse_hip_flat_search_hnsw_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp]),
     "lynse_hip_flat_hnsw_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
     "lynse_hip_hnsw_levels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int32, C.c_uint64, _vp]),
+    "lynse_hip_flat_build_diskann": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "lynse_hip_flat_load_diskann": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32]),
+    "lynse_hip_flat_diskann_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "lynse_hip_flat_drop_diskann": (C.c_int, [_vp]),
+    "lynse_hip_flat_search_diskann_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp]),
+    "lynse_hip_flat_diskann_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
+    "lynse_hip_vamana_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
     "lynse_hip_flat_search_range_f32": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "lynse_hip_flat_set_dtype": (C.c_int, [_vp, C.c_int]),
     "lynse_hip_flat_append_f16_bits": (C.c_int, [_vp, _vp, C.c_uint64]),

@@ -205,9 +205,48 @@ INDEX_BUILD_KEYS = ("n_clusters", "n_centroids", "m", "ef_construction", "ef_sea
 
 
 def hnsw_mode_of(mode: str) -> Optional[int]:
-    """The metric id of HNSW-{IP,L2,COS,COSINE} (any letter case), None for every other mode — HNSW-*-SQ8, HNSW over the domain metrics
-    and DiskANN keep the answers they had (outside this path)."""
+    """The metric id of HNSW-{IP,L2,COS,COSINE} (any letter case), None for every other mode — HNSW-*-SQ8 and HNSW over the domain
+    metrics keep the answers they had (outside this path); the DiskANN modes are diskann_mode_of's."""
     return HNSW_MODES.get(str(mode).upper())
+
+
+DISKANN_MODES = {"DISKANN-L2": _lib.METRIC_L2, "DISKANN-COS": _lib.METRIC_COSINE, "DISKANN-COSINE": _lib.METRIC_COSINE}
+DISKANN_DEFAULTS = {"r": 16, "l": 64, "alpha": 1.2}   # src/index/mod.rs:504-506
+DISKANN_SEED = 42
+
+
+def diskann_mode_of(mode: str) -> Optional[int]:
+    """The metric id of DISKANN-{L2,COS,COSINE} (any letter case), None for every other mode — DISKANN-IP (the reference leaves Vamana's
+    rule for it) and the -PQ* / -SQ8 names keep the answers they had (outside this path)."""
+    return DISKANN_MODES.get(str(mode).upper())
+
+
+def diskann_build_options(params: Optional[dict]) -> dict:
+    """IndexBuildOptions for a DiskANN mode (src/index/mod.rs:545-655): r = 16, l = 64, alpha = 1.2, max_degree = r.  An unknown key, a
+    value of 0 and a bad alpha are refused in validate()'s order with the reference's messages (ValueError, InvalidArgument); keys of the
+    other index families are ignored (filtered_for).  The bounds on r and l are the library's (LYNSE_ERR_UNSUPPORTED)."""
+    p = dict(params or {})
+    for key in p:
+        if key not in INDEX_BUILD_KEYS:
+            raise ValueError(f"Invalid argument: unknown index build parameter '{key}'; supported keys: {', '.join(INDEX_BUILD_KEYS)}")
+    if "n_centroids" in p and "n_clusters" not in p:
+        p["n_clusters"] = p.pop("n_centroids")
+    for name in ("n_clusters", "m", "ef_construction", "ef_search", "r", "l", "max_degree", "nprobe", "replica_count"):   # validate()'s order
+        if p.get(name) is not None and int(p[name]) == 0:
+            raise ValueError(f"Invalid argument: {name} must be greater than 0")
+    alpha = p.get("alpha")
+    if alpha is not None and not (np.isfinite(np.float32(alpha)) and np.float32(alpha) >= 1.0):
+        raise ValueError("Invalid argument: alpha must be a finite value >= 1.0")
+    out = {name: (DISKANN_DEFAULTS[name] if p.get(name) is None else int(p[name])) for name in ("r", "l")}
+    for name, v in out.items():
+        if v < 0:
+            raise ValueError(f"Invalid argument: invalid index build parameter value: {name} = {v}")
+    out["alpha"] = float(np.float32(DISKANN_DEFAULTS["alpha"] if alpha is None else alpha))
+    md = p.get("max_degree")
+    if md is not None and int(md) < 0:
+        raise ValueError(f"Invalid argument: invalid index build parameter value: max_degree = {md}")
+    out["max_degree"] = out["r"] if md is None else int(md)
+    return out
 
 
 def hnsw_build_options(params: Optional[dict]) -> dict:
@@ -603,6 +642,60 @@ class FlatIndex:
         check(lib.lynse_hip_flat_hnsw_stage_times(self._h, _ptr(out), 1 if reset else 0))
         return {"candidates_us": float(out[0]), "select_us": float(out[1]), "reverse_us": float(out[2]), "searches": int(out[3]),
                 "search_us": float(out[4]), "scored": int(out[5])}
+
+    # -- DISKANN-* (DiskANNIndex, src/index/diskann.rs; include/lynse_hip.h states the contract) --------------------------------
+    def build_diskann(self, metric, r: int = DISKANN_DEFAULTS["r"], l: int = DISKANN_DEFAULTS["l"], alpha: float = DISKANN_DEFAULTS["alpha"],
+                      max_degree: Optional[int] = None, seed: int = DISKANN_SEED, max_batches: int = 0) -> None:
+        """The batched Vamana build over the rows held now (rows appended later stay outside the graph).  max_batches > 0 stops after
+        that many batches, counted across both passes, and installs the graph as it stands: a test instrument."""
+        mt = metric if isinstance(metric, int) else metric_from_str(metric)
+        check(lib.lynse_hip_flat_build_diskann(self._h, mt, int(r), int(l), float(alpha), int(r if max_degree is None else max_degree), int(seed),
+                                               int(max_batches)))
+
+    def load_diskann(self, metric, r: int, l: int, adj, entry: int) -> None:
+        """Install a graph as diskann_params exports it: adj u32 [n][r], lists padded with 0xFFFFFFFF."""
+        mt = metric if isinstance(metric, int) else metric_from_str(metric)
+        a = np.ascontiguousarray(adj, dtype=np.uint32)
+        if a.ndim != 2 or a.shape[1] != int(r):
+            raise ValueError("adj must be [n][r]")
+        check(lib.lynse_hip_flat_load_diskann(self._h, mt, int(r), int(l), _ptr(a), a.shape[0], int(entry)))
+
+    def drop_diskann(self) -> None:
+        check(lib.lynse_hip_flat_drop_diskann(self._h))
+
+    def diskann_params(self, arrays: bool = True) -> dict:
+        """{"metric", "r", "l", "entry", "alpha", "n"} and, with `arrays`, "adj"; r == 0 without an index."""
+        info = np.zeros(4, np.uint32)
+        alpha, n = C.c_float(0.0), C.c_uint64(0)
+        check(lib.lynse_hip_flat_diskann_params(self._h, _ptr(info), C.byref(alpha), C.byref(n), None))
+        metric, r, l, entry = (int(x) for x in info)
+        out = {"metric": metric, "r": r, "l": l, "entry": entry, "alpha": float(alpha.value), "n": int(n.value)}
+        if arrays and r:
+            adj = np.empty((out["n"], r), np.uint32)
+            check(lib.lynse_hip_flat_diskann_params(self._h, _ptr(info), C.byref(alpha), C.byref(n), _ptr(adj)))
+            out["adj"] = adj
+        return out
+
+    def search_diskann_batch_arrays(self, queries, k: int, metric, ef: int = 0):
+        """The beam search from the entry and 8 anchors with ef = min(max(ef, the index's l, 10 k), n)."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(queries, 2, "queries")
+        if q.shape[1] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        rows = np.empty((nq, max(k, 1)), np.uint64)
+        dists = np.empty((nq, max(k, 1)), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        check(lib.lynse_hip_flat_search_diskann_f32(self._h, _ptr(q), nq, k, m, int(ef), _ptr(rows), _ptr(dists), _ptr(counts)))
+        return rows[:, :k], dists[:, :k], counts
+
+    def diskann_stage_times(self, reset: bool = True) -> dict:
+        """The last build (microseconds: the three stages only from a build that ran with profiling on, the host draws, the whole) and,
+        with profiling on, the searches timed, their kernel microseconds and the distances they scored."""
+        out = np.zeros(8, np.float64)
+        check(lib.lynse_hip_flat_diskann_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"build_search_us": float(out[0]), "build_prune_us": float(out[1]), "build_commit_us": float(out[2]), "build_draws_us": float(out[3]),
+                "build_us": float(out[4]), "searches": int(out[5]), "search_us": float(out[6]), "scored": int(out[7])}
 
     def search_range_batch_arrays(self, queries, thresholds, max_results: int, metric, bitset_words=None):
         """Range search (Collection::search_range, engine.rs:6410-6483) for a batch, one threshold per query: the exact scan of every
@@ -1677,6 +1770,9 @@ class Collection:
         self._hnsw = False              # HNSW-*: a graph over the flushed rows (FlatIndex.build_hnsw); replaces and is replaced by the two above
         self._hnsw_rows = 0             # rows the graph was built over
         self._hnsw_opts: dict = {}
+        self._diskann = False           # DISKANN-*: likewise (FlatIndex.build_diskann); at most one of the four exists
+        self._diskann_rows = 0
+        self._diskann_opts: dict = {}
         self._sparse: dict = {}         # user id -> (indices u32, values f32), normalised (SparseVectorStore.vectors)
         self._sparse_ids = np.zeros(0, np.int64)   # the ids of the uploaded sparse rows, ascending: sparse row -> user id
         self._sparse_index = None       # SparseIndex, created by the first sparse search
@@ -1794,6 +1890,15 @@ class Collection:
             self._hnsw_opts = opts
             self._metric = metric
             self._build_hnsw()
+        elif diskann_mode_of(mode) is not None:   # DISKANN-{L2,COS,COSINE}; DISKANN-IP and the -PQ* / -SQ8 names fall through to the refusal below
+            opts = diskann_build_options(params)
+            self._ivf = None
+            self._drop_aux()
+            if len(self._flat) == 0:   # graph / partition indexes need data (engine.rs:4606-4612)
+                raise ValueError("Empty database")
+            self._diskann_opts = opts
+            self._metric = metric
+            self._build_diskann()
         elif mode.startswith("SPANN"):
             metric, sq8 = spann_mode_of(mode)
             opts = spann_build_options(params)
@@ -1820,7 +1925,8 @@ class Collection:
         self._flat.drop_pq()
         self._flat.drop_rabitq()
         self._flat.drop_hnsw()
-        self._pq = self._rabitq = self._hnsw = False
+        self._flat.drop_diskann()
+        self._pq = self._rabitq = self._hnsw = self._diskann = False
         if self._path is not None:
             (self._path / RABITQ_INDEX_FILE).unlink(missing_ok=True)
 
@@ -1861,6 +1967,12 @@ class Collection:
         o = self._hnsw_opts
         self._flat.build_hnsw(self._metric, o["m"], o["ef_construction"], o["ef_search"], o["max_level"], HNSW_SEED)
         self._hnsw, self._hnsw_rows = True, len(self._flat)
+
+    def _build_diskann(self) -> None:
+        """The graph over every flushed row; like the HNSW graph it has no incremental insert and no on-disk form."""
+        o = self._diskann_opts
+        self._flat.build_diskann(self._metric, o["r"], o["l"], o["alpha"], o["max_degree"], DISKANN_SEED)
+        self._diskann, self._diskann_rows = True, len(self._flat)
 
     def _build_ivf(self) -> None:
         n = len(self._flat)
@@ -1939,6 +2051,10 @@ class Collection:
             if self._hnsw_rows != len(self._flat):   # rows were flushed after the build
                 self._build_hnsw()
             return self._flat.search_hnsw_batch_arrays(q, search_k, self._metric, int(nprobe))
+        if self._diskann:   # nprobe > 0 is ef_query; the store rescore of the candidates is the identity: the beam scored the full-precision rows
+            if self._diskann_rows != len(self._flat):   # rows were flushed after the build
+                self._build_diskann()
+            return self._flat.search_diskann_batch_arrays(q, search_k, self._metric, int(nprobe))
         if self._pq:   # search_auxiliary_quantized (engine.rs:5504-5526): rows committed after the build are not in the index
             return self._flat.search_pq_batch_arrays(q, search_k, self._metric, PQ_OVERSAMPLE)
         if self._rabitq:
@@ -1977,6 +2093,7 @@ class Collection:
         pq = self._ivf is None and self._pq and subset is None
         rabitq = self._ivf is None and self._rabitq and subset is None
         hnsw = self._ivf is None and self._hnsw and subset is None
+        diskann = self._ivf is None and self._diskann and subset is None
         target.profile_enable(True)
         target.profile_get(reset=True)
         if sq8:
@@ -1987,7 +2104,9 @@ class Collection:
             self._flat.rabitq_stage_times(reset=True)
         if hnsw:
             self._flat.hnsw_stage_times(reset=True)
-        stage_us = hnsw_us = None
+        if diskann:
+            self._flat.diskann_stage_times(reset=True)
+        stage_us = hnsw_us = diskann_us = None
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
@@ -2003,11 +2122,14 @@ class Collection:
             if hnsw:
                 t = self._flat.hnsw_stage_times(reset=True)
                 hnsw_us = {"search_us": float(t["search_us"]), "scored": int(t["scored"])}
+            if diskann:
+                t = self._flat.diskann_stage_times(reset=True)
+                diskann_us = {"search_us": float(t["search_us"]), "scored": int(t["scored"])}
             target.profile_enable(False)
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
-                   "index_path": "ann_index" if self._ivf is not None or hnsw else ("flat_mmap_filtered" if subset is not None else
+                   "index_path": "ann_index" if self._ivf is not None or hnsw or diskann else ("flat_mmap_filtered" if subset is not None else
                                                                             ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else "flat_mmap"))),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
@@ -2019,6 +2141,8 @@ class Collection:
             profile["device"]["rabitq_stages"] = stage_us
         if hnsw_us is not None:
             profile["device"]["hnsw"] = hnsw_us
+        if diskann_us is not None:
+            profile["device"]["diskann"] = diskann_us
         return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
                 "profile": profile}
 

@@ -30,6 +30,7 @@
 #include "pq.h"
 #include "rabitq.h"
 #include "hnsw.h"
+#include "diskann.h"
 #include "range.h"
 #include "additive.h"
 #include "sparse.h"
@@ -253,6 +254,7 @@ struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
 struct RbqState;  // FLAT-*-RABITQ codes + search scratch (rabitq_host.inc)
 struct RangeState;  // range search scratch (range_host.inc)
 struct HnswState;  // HNSW-* graph + search scratch (hnsw_host.inc)
+struct DiskannState;  // DISKANN-* graph + search scratch (diskann_host.inc)
 
 // One int8 copy of a shard's rows for the certified coarse pass (lynse_hip_flat::sq8 / sq8a / sq8c / sq7) with what the prep kernel needs
 // to certify a bound over it.
@@ -376,6 +378,7 @@ struct lynse_hip_flat {
     RbqState* rbq = nullptr;              // FLAT-{IP,L2,COS}-RABITQ index over the first rbq->n rows (rabitq_host.inc); NULL = none
     RangeState* range = nullptr;          // scratch of lynse_hip_flat_search_range_f32 (range_host.inc); NULL until the first one
     HnswState* hnsw = nullptr;            // HNSW-{IP,L2,COS} graph over the first hnsw->n rows (hnsw_host.inc); NULL = none
+    DiskannState* diskann = nullptr;      // DISKANN-{L2,COS} graph over the first diskann->n rows (diskann_host.inc); NULL = none
 
     std::atomic<bool> profiling{false};   // (read by searches without the lock: atomics)
     std::atomic<uint32_t> prof_rate{1};              // every prof_rate-th search records its events (lynse_hip_flat_profile_enable(h, n))
@@ -387,6 +390,7 @@ static void pq_release(lynse_hip_flat* h);
 static void rbq_release(lynse_hip_flat* h);
 static void range_release(lynse_hip_flat* h);
 static void hnsw_release(lynse_hip_flat* h);
+static void diskann_release(lynse_hip_flat* h);
 
 static inline bool is_f16(const lynse_hip_flat* h) { return h->dtype == LYNSE_DTYPE_F16; }
 // the row matrix the exact-scoring kernels read: f32 rows, or the f16 bits of an F16 shard handed in as float* with a pitch
@@ -526,6 +530,7 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     rbq_release(h);
     range_release(h);
     hnsw_release(h);
+    diskann_release(h);
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
@@ -3571,6 +3576,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "pq_host.inc"
 #include "rabitq_host.inc"
 #include "hnsw_host.inc"
+#include "diskann_host.inc"
 #include "range_host.inc"
 #include "additive_host.inc"
 #include "sparse_host.inc"
