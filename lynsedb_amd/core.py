@@ -449,8 +449,8 @@ class FlatIndex:
         return out
 
     # -- search -------------------------------------------------------------------------------
-    def search_batch_arrays(self, queries, k: int, metric):
-        """Batched search returning padded arrays (rows u64[nq,k], dists f32[nq,k], counts u32[nq])."""
+    def _search_f32(self, fn, queries, k: int, metric, *extra):
+        """One `lynse_hip_flat_search_*_f32` entry over f32 queries; `extra` goes between the metric and the outputs."""
         m = metric if isinstance(metric, int) else metric_from_str(metric)
         q = _f32(queries, 2, "queries")
         if q.shape[1] != self._dim:
@@ -459,21 +459,16 @@ class FlatIndex:
         rows = np.empty((nq, max(k, 1)), np.uint64)
         dists = np.empty((nq, max(k, 1)), np.float32)
         counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_f32(self._h, _ptr(q), nq, k, m, _ptr(rows), _ptr(dists), _ptr(counts)))
+        check(fn(self._h, _ptr(q), nq, k, m, *extra, _ptr(rows), _ptr(dists), _ptr(counts)))
         return rows[:, :k], dists[:, :k], counts
+
+    def search_batch_arrays(self, queries, k: int, metric):
+        """Batched search returning padded arrays (rows u64[nq,k], dists f32[nq,k], counts u32[nq])."""
+        return self._search_f32(lib.lynse_hip_flat_search_f32, queries, k, metric)
 
     def search_sq8_batch_arrays(self, queries, k: int, metric):
         """`FlatMmap::search(.., use_sq8 = true, ..)` — the FLAT-*-SQ8 index modes (flat_mmap.rs:891-905, :5868-5926)."""
-        m = metric if isinstance(metric, int) else metric_from_str(metric)
-        q = _f32(queries, 2, "queries")
-        if q.shape[1] != self._dim:
-            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
-        nq, k = q.shape[0], int(k)
-        rows = np.empty((nq, max(k, 1)), np.uint64)
-        dists = np.empty((nq, max(k, 1)), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_sq8_f32(self._h, _ptr(q), nq, k, m, _ptr(rows), _ptr(dists), _ptr(counts)))
-        return rows[:, :k], dists[:, :k], counts
+        return self._search_f32(lib.lynse_hip_flat_search_sq8_f32, queries, k, metric)
 
     def sq8_params(self):
         mins, scales = np.empty(self._dim, np.float32), np.empty(self._dim, np.float32)
@@ -512,16 +507,7 @@ class FlatIndex:
 
     def search_pq_batch_arrays(self, queries, k: int, metric, oversample: int = PQ_OVERSAMPLE):
         """ADC scan over the codes, the N = min(k' * oversample, n_pq) best by (ADC score, row), exact rescore of those rows."""
-        m = metric if isinstance(metric, int) else metric_from_str(metric)
-        q = _f32(queries, 2, "queries")
-        if q.shape[1] != self._dim:
-            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
-        nq, k = q.shape[0], int(k)
-        rows = np.empty((nq, max(k, 1)), np.uint64)
-        dists = np.empty((nq, max(k, 1)), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_pq_f32(self._h, _ptr(q), nq, k, m, int(oversample), _ptr(rows), _ptr(dists), _ptr(counts)))
-        return rows[:, :k], dists[:, :k], counts
+        return self._search_f32(lib.lynse_hip_flat_search_pq_f32, queries, k, metric, int(oversample))
 
     def pq_stage_times(self, reset: bool = True) -> dict:
         """With profiling on: PQ searches timed and the summed microseconds of the scan stage and of the rescore."""
@@ -565,16 +551,7 @@ class FlatIndex:
 
     def search_rabitq_batch_arrays(self, queries, k: int, metric, oversample: int = RABITQ_OVERSAMPLE):
         """Scan of the 1-bit codes, the N = min(k' * oversample, n_rbq) best by (score, row), exact rescore of those rows."""
-        m = metric if isinstance(metric, int) else metric_from_str(metric)
-        q = _f32(queries, 2, "queries")
-        if q.shape[1] != self._dim:
-            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
-        nq, k = q.shape[0], int(k)
-        rows = np.empty((nq, max(k, 1)), np.uint64)
-        dists = np.empty((nq, max(k, 1)), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_rabitq_f32(self._h, _ptr(q), nq, k, m, int(oversample), _ptr(rows), _ptr(dists), _ptr(counts)))
-        return rows[:, :k], dists[:, :k], counts
+        return self._search_f32(lib.lynse_hip_flat_search_rabitq_f32, queries, k, metric, int(oversample))
 
     def rabitq_stage_times(self, reset: bool = True) -> dict:
         """With profiling on: RaBitQ searches timed and the summed microseconds of the scan stage and of the rescore."""
@@ -624,16 +601,7 @@ class FlatIndex:
 
     def search_hnsw_batch_arrays(self, queries, k: int, metric, ef: int = 0):
         """Greedy descent and the beam search at level 0 with ef = max(ef or the index's ef_search, k)."""
-        m = metric if isinstance(metric, int) else metric_from_str(metric)
-        q = _f32(queries, 2, "queries")
-        if q.shape[1] != self._dim:
-            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
-        nq, k = q.shape[0], int(k)
-        rows = np.empty((nq, max(k, 1)), np.uint64)
-        dists = np.empty((nq, max(k, 1)), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_hnsw_f32(self._h, _ptr(q), nq, k, m, int(ef), _ptr(rows), _ptr(dists), _ptr(counts)))
-        return rows[:, :k], dists[:, :k], counts
+        return self._search_f32(lib.lynse_hip_flat_search_hnsw_f32, queries, k, metric, int(ef))
 
     def hnsw_stage_times(self, reset: bool = True) -> dict:
         """The stages of the last build (microseconds) and, with profiling on, the searches timed, their kernel microseconds and the
@@ -678,16 +646,7 @@ class FlatIndex:
 
     def search_diskann_batch_arrays(self, queries, k: int, metric, ef: int = 0):
         """The beam search from the entry and 8 anchors with ef = min(max(ef, the index's l, 10 k), n)."""
-        m = metric if isinstance(metric, int) else metric_from_str(metric)
-        q = _f32(queries, 2, "queries")
-        if q.shape[1] != self._dim:
-            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[1]}")
-        nq, k = q.shape[0], int(k)
-        rows = np.empty((nq, max(k, 1)), np.uint64)
-        dists = np.empty((nq, max(k, 1)), np.float32)
-        counts = np.zeros(nq, np.uint32)
-        check(lib.lynse_hip_flat_search_diskann_f32(self._h, _ptr(q), nq, k, m, int(ef), _ptr(rows), _ptr(dists), _ptr(counts)))
-        return rows[:, :k], dists[:, :k], counts
+        return self._search_f32(lib.lynse_hip_flat_search_diskann_f32, queries, k, metric, int(ef))
 
     def diskann_stage_times(self, reset: bool = True) -> dict:
         """The last build (microseconds: the three stages only from a build that ran with profiling on, the host draws, the whole) and,

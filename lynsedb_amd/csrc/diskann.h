@@ -1,20 +1,26 @@
 // diskann.h — DISKANN-{L2,COS} on a FLAT handle (DiskANNIndex, src/index/diskann.rs, the in-memory full-precision form): the batched
 // Vamana build and the beam search.  include/lynse_hip.h states the contract (the DiskANN rule block), DESIGN.md §21 the reasoning.
-//   k_vamana_search   one wave per query: the start phase (the entry and the evenly spaced anchors), then the two-heap beam of
-//                     k_hnsw_search unchanged.  Two outputs: the top k (queries) or the whole of R as keys (the build).
+//   k_vamana_search   one wave per query: the start phase (the entry and the evenly spaced anchors), then the two-heap beam
+//                     (graph_beam, graph.h) over lists of r.  Two outputs: the top k (queries) or the whole of R as keys (the build).
 //   k_vamana_prune    one wave per item: robust_prune.  Forward form: the beam of a batch member plus its current list, the result is
 //                     installed as its new list.  Commit form: an over-long destination list, scored first.
 //   k_vamana_commit   one block per batch: the effective reverse edges of the batch as keys (dst, degree, edge), sorted in LDS; the
 //                     append slot of an edge is its place in the run of its dst — no atomic, no arrival order.
 //   k_vamana_pairs    d(candidate, ref) for the entry-point sums of rule 2
-// The device helpers (hnsw_dist, hnsw_argmax, hnsw_compact, ...) and the reasons for their form are hnsw.h's.
+// The distance, the wave helpers, the beam and the LDS layout of the search (GraphSearchLds) are graph.h's, shared with hnsw.h.
 #pragma once
 
-#include "hnsw.h"
+#include "graph.h"
 
 namespace lynse {
 
 constexpr uint32_t VAMANA_BATCH = 256, VAMANA_STARTS = 33;   // a build batch; the entry + at most 32 anchors
+
+// the slots of C; the host sizes the kernel's LDS with the same count
+__host__ __device__ constexpr uint32_t vamana_c_cap(uint32_t ef) { return 2 * ef + 8 + VAMANA_STARTS; }
+static_assert(GraphSearchLds::bytes(1, vamana_c_cap(1), 2) == 1 * 24 + (8 + 33) * 8 + 256 + 2 * 4 &&
+              GraphSearchLds::bytes(4096, vamana_c_cap(4096), 768) == (size_t)4096 * 24 + (8 + 33) * 8 + 256 + 768 * 4,
+              "R: ef keys, C: 2 ef + 8 + 33 keys, 64 node slots, the query");
 
 struct VamanaSearchArgs {
     const float* V;              // the handle's rows
@@ -25,7 +31,7 @@ struct VamanaSearchArgs {
     uint32_t k, ef, r, anchors;  // anchors <= 32
     uint32_t entry;
     uint64_t n;
-    const uint32_t* adj;         // [n][r], HNSW_PAD after the last neighbour, no neighbour twice
+    const uint32_t* adj;         // [n][r], GRAPH_PAD after the last neighbour, no neighbour twice
     uint32_t* vis;               // [nq][vis_words] visited bits, zero on entry
     uint32_t vis_words;
     uint64_t* out_rows;          // [nq][k]; NULL in the build
@@ -39,11 +45,12 @@ struct VamanaSearchArgs {
 
 __global__ void __launch_bounds__(64) k_vamana_search(VamanaSearchArgs a) {
     extern __shared__ __align__(16) unsigned char vam_smem[];
-    const uint32_t ef = a.ef, c_cap = 2 * a.ef + 8 + VAMANA_STARTS;
-    uint64_t* Rk = reinterpret_cast<uint64_t*>(vam_smem);   // ef result keys, unordered
-    uint64_t* Ck = Rk + ef;                                  // c_cap candidate keys, unordered
-    uint32_t* lst = reinterpret_cast<uint32_t*>(Ck + c_cap); // the starts, then the unvisited neighbours of one expansion, stored order
-    float* qv = reinterpret_cast<float*>(lst + 64);
+    const uint32_t ef = a.ef, c_cap = vamana_c_cap(a.ef);
+    const GraphSearchLds lds(vam_smem, ef, c_cap);
+    uint64_t* Rk = lds.Rk;
+    uint64_t* Ck = lds.Ck;
+    uint32_t* lst = lds.lst;   // the starts first
+    float* qv = lds.qv;
     const int lane = threadIdx.x, g = lane & 7, grp = lane >> 3;
     const uint32_t q = blockIdx.x;
     const float* qsrc = a.Q ? a.Q + (size_t)q * a.D : a.V + (size_t)a.qids[q] * a.ld;
@@ -52,23 +59,23 @@ __global__ void __launch_bounds__(64) k_vamana_search(VamanaSearchArgs a) {
 
     // the starts (search_entry_points): the entry, then a n / A for a = 0 .. A - 1 unless it is the entry; all distinct
     const uint32_t A = (uint32_t)(a.n < a.anchors ? a.n : a.anchors);
-    uint32_t snode = HNSW_PAD;
+    uint32_t snode = GRAPH_PAD;
     if (lane == 0) snode = a.entry;
     else if ((uint32_t)lane <= A) {
         const uint32_t idx = (uint32_t)((uint64_t)(lane - 1) * a.n / A);
         if (idx != a.entry) snode = idx;
     }
-    const uint64_t sm = __ballot(snode != HNSW_PAD);
+    const uint64_t sm = __ballot(snode != GRAPH_PAD);
     const uint32_t ns = (uint32_t)__popcll(sm);
-    if (snode != HNSW_PAD) {
-        lst[hnsw_rank(sm, lane)] = snode;
+    if (snode != GRAPH_PAD) {
+        lst[graph_rank(sm, lane)] = snode;
         atomicOr(&vis[snode >> 5], 1u << (snode & 31u));
     }
     __syncthreads();
     for (uint32_t b = 0; b < ns; b += 8) {   // every start is scored and pushed to C
         const uint32_t idx = b + grp;
         const uint32_t node = lst[idx < ns ? idx : b];
-        const float d = hnsw_dist(a.metric, qv, a.V + (size_t)node * a.ld, a.D, g);
+        const float d = graph_dist(a.metric, qv, a.V + (size_t)node * a.ld, a.D, g);
         if (g == 0 && idx < ns) Ck[idx] = make_key(d, node, true);
     }
     __syncthreads();
@@ -80,93 +87,21 @@ __global__ void __launch_bounds__(64) k_vamana_search(VamanaSearchArgs a) {
         if (rank < ef) Rk[rank] = kx;
     }
     __syncthreads();
-    uint32_t Rn = ns < ef ? ns : ef, Cn = ns, worst_pos = Rn - 1, scored = ns;
-    uint64_t worst = hnsw_uniform(Rk[worst_pos]);
-
-    // the beam (k_hnsw_search at level 0, lists of r)
-    bool broken = false;
-    while (Cn && !broken) {
-        uint64_t best = KEY_SENTINEL;
-        uint32_t bpos = 0;
-        for (uint32_t i = lane; i < Cn; i += 64) {
-            const uint64_t kx = Ck[i];
-            if (kx < best) { best = kx; bpos = i; }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t ok = __shfl_xor(best, o);
-            const uint32_t op = __shfl_xor(bpos, o);
-            if (ok < best) { best = ok; bpos = op; }
-        }
-        best = hnsw_uniform(best);
-        bpos = (uint32_t)__builtin_amdgcn_readfirstlane((int)bpos);
-        __syncthreads();
-        if (lane == 0) Ck[bpos] = Ck[Cn - 1];
-        --Cn;
-        __syncthreads();
-        if (Rn >= ef && (uint32_t)(best >> 32) > (uint32_t)(worst >> 32)) break;   // c.dist > worst.dist, on the order-preserving images
-        const uint32_t c = key_row(best);
-        const uint32_t nb = (uint32_t)lane < a.r ? a.adj[(size_t)c * a.r + lane] : HNSW_PAD;
-        bool fresh = false;
-        if (nb != HNSW_PAD) fresh = ((atomicOr(&vis[nb >> 5], 1u << (nb & 31u)) >> (nb & 31u)) & 1u) == 0u;
-        const uint64_t um = __ballot(fresh);
-        const uint32_t cnt = (uint32_t)__popcll(um);
-        if (fresh) lst[hnsw_rank(um, lane)] = nb;
-        __syncthreads();
-        scored += cnt;
-        for (uint32_t b = 0; b < cnt && !broken; b += 8) {
-            // Room for the 8 admissions of this step.  While R is not full C holds nothing R does not (fewer than ef entries).  With R
-            // full, what a compaction keeps is in R, was evicted from R at worst.dist (at most ef - 1) or is a start that lost the
-            // start phase and ties with worst.dist (at most 32): 2 ef + 31 entries.
-            if (Cn + 8 > c_cap) {
-                Cn = hnsw_compact(Ck, Cn, (uint32_t)(worst >> 32), lane);
-                if (Cn + 8 > c_cap) {
-                    if (lane == 0) *a.status = 1u;
-                    broken = true;
-                }
-            }
-            if (!broken) {
-                const uint32_t idx = b + grp;
-                const uint32_t node = lst[idx < cnt ? idx : b];
-                const float d = hnsw_dist(a.metric, qv, a.V + (size_t)node * a.ld, a.D, g);
-                const uint32_t nbt = cnt - b < 8u ? cnt - b : 8u;
-                for (uint32_t t = 0; t < nbt; ++t) {
-                    const float dt = hnsw_lane(d, t * 8);
-                    const uint32_t nt = hnsw_lane(node, t * 8);
-                    const bool full = Rn >= ef;
-                    const uint64_t key = make_key(dt, nt, true);
-                    if (!full || (uint32_t)(key >> 32) < (uint32_t)(worst >> 32)) {   // d < worst.dist, strict and on the distance alone
-                        if (lane == 0) {
-                            Ck[Cn] = key;
-                            Rk[full ? worst_pos : Rn] = key;
-                        }
-                        ++Cn;
-                        if (!full) ++Rn;
-                        __syncthreads();
-                        worst_pos = hnsw_argmax(Rk, Rn, lane);
-                        worst = hnsw_uniform(Rk[worst_pos]);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
+    const uint32_t Rn0 = ns < ef ? ns : ef;
+    GraphBeamState bs{Rn0, ns, Rn0 - 1, graph_uniform(Rk[Rn0 - 1]), ns, false};
+    graph_beam(a.V, a.ld, a.D, a.metric, a.adj, a.r, lds, ef, c_cap, vis, a.status, bs);
 
     // R by (dist, node): the best min(k, |R|) for a query, all of it for the build
     const uint32_t want = a.out_beam ? ef : a.k;
-    const uint32_t n_out = broken ? 0u : (want < Rn ? want : Rn);
-    if (!broken) {
-        for (uint32_t i = lane; i < Rn; i += 64) {
-            const uint64_t kx = Rk[i];
-            uint32_t rank = 0;
-            for (uint32_t j = 0; j < Rn; ++j) rank += Rk[j] < kx ? 1u : 0u;
-            if (rank < want) {
-                if (a.out_beam) a.out_beam[(size_t)q * ef + rank] = kx;
-                else {
-                    a.out_rows[(size_t)q * a.k + rank] = key_row(kx);
-                    a.out_dists[(size_t)q * a.k + rank] = key_score(kx, true);
-                }
-            }
-        }
+    const uint32_t n_out = bs.broken ? 0u : (want < bs.Rn ? want : bs.Rn);
+    if (!bs.broken) {
+        auto beam_key = [&](uint32_t rank, uint64_t kx) { a.out_beam[(size_t)q * ef + rank] = kx; };
+        auto row_and_dist = [&](uint32_t rank, uint64_t kx) {
+            a.out_rows[(size_t)q * a.k + rank] = key_row(kx);
+            a.out_dists[(size_t)q * a.k + rank] = key_score(kx, true);
+        };
+        // (one rank sort in the kernel's code, the form chosen per entry)
+        graph_emit_ranked(Rk, bs.Rn, want, [&](uint32_t rank, uint64_t kx) { a.out_beam ? beam_key(rank, kx) : row_and_dist(rank, kx); });
     }
     if (!a.out_beam) {
         for (uint32_t i = n_out + lane; i < a.k; i += 64) {
@@ -177,7 +112,7 @@ __global__ void __launch_bounds__(64) k_vamana_search(VamanaSearchArgs a) {
     if (lane == 0) {
         if (a.out_beam) a.out_beam_n[q] = n_out;
         else a.out_counts[q] = n_out;
-        a.out_scored[q] = scored;
+        a.out_scored[q] = bs.scored;
     }
 }
 
@@ -216,9 +151,9 @@ __global__ void __launch_bounds__(64) k_vamana_prune(VamanaPruneArgs a) {
         const uint32_t bn = a.beam_n[t];
         for (uint32_t i = lane; i < bn; i += 64) K0[i] = a.beam[(size_t)t * a.beam_stride + i];
         m = bn;
-        const uint32_t nb = (uint32_t)lane < r ? a.adj[(size_t)p * r + lane] : HNSW_PAD;
-        const uint64_t nm = __ballot(nb != HNSW_PAD);
-        if (nb != HNSW_PAD) raw[hnsw_rank(nm, lane)] = nb;
+        const uint32_t nb = (uint32_t)lane < r ? a.adj[(size_t)p * r + lane] : GRAPH_PAD;
+        const uint64_t nm = __ballot(nb != GRAPH_PAD);
+        if (nb != GRAPH_PAD) raw[graph_rank(nm, lane)] = nb;
         nraw = (uint32_t)__popcll(nm);
     } else {
         // the grid covers every key slot; a wave works only at the head of the run of a destination whose list outgrew r
@@ -246,7 +181,7 @@ __global__ void __launch_bounds__(64) k_vamana_prune(VamanaPruneArgs a) {
     for (uint32_t b = 0; b < nraw; b += 8) {
         const uint32_t idx = b + grp;
         const uint32_t node = raw[idx < nraw ? idx : b];
-        const float d = hnsw_dist(a.metric, pvec, a.V + (size_t)node * a.ld, a.D, g);
+        const float d = graph_dist(a.metric, pvec, a.V + (size_t)node * a.ld, a.D, g);
         if (g == 0 && idx < nraw) K0[m + idx] = make_key(d, node, true);
     }
     m += nraw;
@@ -272,9 +207,9 @@ __global__ void __launch_bounds__(64) k_vamana_prune(VamanaPruneArgs a) {
     }
     __syncthreads();
     // the walk: select the first remaining b, keep v iff alpha d(b, v) > d(p, v) (one f32 multiply, then the comparison)
-    uint32_t sel = 0, my_id = HNSW_PAD;
+    uint32_t sel = 0, my_id = GRAPH_PAD;
     while (cnt && sel < r) {
-        const uint32_t bnode = key_row(hnsw_uniform(K0[0]));
+        const uint32_t bnode = key_row(graph_uniform(K0[0]));
         if ((uint32_t)lane == sel) my_id = bnode;
         ++sel;
         if (sel == r) break;
@@ -286,11 +221,11 @@ __global__ void __launch_bounds__(64) k_vamana_prune(VamanaPruneArgs a) {
             const uint32_t idx = i0 + grp;
             const bool valid = idx < cnt;
             const uint64_t kx = K0[valid ? idx : i0];
-            const float d = hnsw_dist(a.metric, bvec, a.V + (size_t)key_row(kx) * a.ld, a.D, g);
+            const float d = graph_dist(a.metric, bvec, a.V + (size_t)key_row(kx) * a.ld, a.D, g);
             const bool keep = valid && g == 0 && __fmul_rn(a.alpha, d) > key_score(kx, true);
             const uint64_t km = __ballot(keep);
             __syncthreads();
-            if (keep) K0[w + hnsw_rank(km, lane)] = kx;
+            if (keep) K0[w + graph_rank(km, lane)] = kx;
             w += (uint32_t)__popcll(km);
             __syncthreads();
         }
@@ -317,12 +252,12 @@ __global__ void __launch_bounds__(1024) k_vamana_commit(VamanaCommitArgs a) {
         uint64_t key = KEY_SENTINEL;
         if (e < E) {
             const uint32_t src = a.items[e / r], dst = a.adj[(size_t)src * r + e % r];
-            if (dst != HNSW_PAD && dst != src) {
+            if (dst != GRAPH_PAD && dst != src) {
                 bool found = false;
                 uint32_t deg = 0;
                 for (; deg < r; ++deg) {
                     const uint32_t x = a.adj[(size_t)dst * r + deg];
-                    if (x == HNSW_PAD) break;
+                    if (x == GRAPH_PAD) break;
                     found |= x == src;
                 }
                 if (!found) key = vamana_ckey(dst, deg, e);
@@ -373,7 +308,7 @@ __global__ void __launch_bounds__(64) k_vamana_pairs(const float* __restrict__ V
     for (uint32_t b = 0; b < nr; b += 8) {
         const uint32_t idx = b + grp;
         const uint32_t node = refs[idx < nr ? idx : b];
-        const float d = hnsw_dist(metric, cvec, V + (size_t)node * ld, D, g);
+        const float d = graph_dist(metric, cvec, V + (size_t)node * ld, D, g);
         if (g == 0 && idx < nr) out[(size_t)c * nr + idx] = d;
     }
 }

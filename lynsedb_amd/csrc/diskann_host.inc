@@ -1,5 +1,6 @@
 // diskann_host.inc — DISKANN-{L2,COS} on a FLAT handle (DiskANNIndex, src/index/diskann.rs, in memory and at full precision).
-// Included from lynse_hip.hip after hnsw_host.inc, whose checks, lock and clock it shares; kernels in diskann.h.  The rule block of
+// Included from lynse_hip.hip after graph_host.inc, whose lock, handle check, clock, list normaliser and search driver it shares with
+// hnsw_host.inc; kernels in diskann.h.  The rule block of
 // include/lynse_hip.h states the contract, DESIGN.md §21 the reasoning.  The graph shares the handle's rows: it holds ids only.
 
 struct DiskannState {
@@ -8,15 +9,9 @@ struct DiskannState {
     float alpha = 0.0f;
     uint64_t n = 0;                       // the graph covers the first n rows of the handle
     uint32_t* d_adj = nullptr;            // [n][r]
-    // search scratch
-    float *d_q = nullptr, *d_dists = nullptr;
-    uint64_t* d_rows = nullptr;
-    uint32_t *d_vis = nullptr, *d_counts = nullptr, *d_status = nullptr;
-    size_t q_cap = 0, dists_cap = 0, rows_cap = 0, vis_cap = 0, counts_cap = 0;
-    // the last build (microseconds of host time; the three stages only when it ran with profiling on, which synchronises them);
-    // the searches timed with profiling on
+    GraphSearchScratch search;            // with the searches timed with profiling on
+    // the last build (microseconds of host time; the three stages only when it ran with profiling on, which synchronises them)
     double b_search_us = 0.0, b_prune_us = 0.0, b_commit_us = 0.0, b_draws_us = 0.0, b_total_us = 0.0;
-    double searches = 0.0, search_us = 0.0, scored = 0.0;
 
     bool built() const { return d_adj != nullptr; }
     void free_index() {
@@ -27,11 +22,7 @@ struct DiskannState {
         alpha = 0.0f;
         n = 0;
     }
-    ~DiskannState() {
-        free_index();
-        for (void* p : {(void*)d_q, (void*)d_dists, (void*)d_rows, (void*)d_vis, (void*)d_counts, (void*)d_status})
-            if (p) (void)hipFree(p);
-    }
+    ~DiskannState() { free_index(); }
 };
 
 static void diskann_release(lynse_hip_flat* h) {
@@ -53,7 +44,7 @@ static void vamana_draws(uint64_t seed, uint64_t n, uint32_t r, VamanaDraws& out
         for (uint64_t i = n; i-- > 1;) std::swap(v[i], v[draw(i + 1)]);
         return v;
     };
-    out.adj0.assign((size_t)n * r, HNSW_PAD);
+    out.adj0.assign((size_t)n * r, GRAPH_PAD);
     if (n <= 1) {   // no word is consumed
         out.refs.assign(n, 0); out.cands.assign(n, 0); out.order.assign(n, 0);
         return;
@@ -98,9 +89,6 @@ static int diskann_check_params(uint32_t r, uint32_t l) {
     if (l < 1 || l > DISKANN_L_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: l must be between 1 and 4096");
     return LYNSE_OK;
 }
-static size_t diskann_search_lds(uint32_t ef, uint32_t D) {   // R: ef keys, C: 2 ef + 8 + 33 keys, 64 node slots, the query
-    return (size_t)ef * 24 + (8 + VAMANA_STARTS) * 8 + 256 + (size_t)D * 4;
-}
 static size_t diskann_prune_lds(uint32_t cap, uint32_t D) { return (size_t)cap * 16 + (size_t)D * 8; }   // two key arrays, the rows of p and b
 
 static int diskann_install(lynse_hip_flat* h, uint32_t* d_adj, int metric, uint32_t r, uint32_t l, float alpha, uint64_t n, uint32_t entry) {
@@ -120,21 +108,21 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
     (void)max_degree;   // max(max_degree, r) bounds the stored degree min(r, max_degree) = r
     l = std::max(l, r);
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     const uint64_t n = h->n;
     const uint32_t D = h->dim;
     if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
     if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "a DiskANN index holds fewer than 2^32 - 1 rows");
     const uint32_t Lb = std::max(std::min(l, DISKANN_L_BUILD_CAP), r), ef_b = (uint32_t)std::min<uint64_t>(Lb, n);
     const uint32_t cap = r + VAMANA_BATCH;   // the longest list a commit prunes; a forward prune sees at most Lb + r <= 128 + 64
-    const size_t s_lds = diskann_search_lds(ef_b, D), p_lds = diskann_prune_lds(cap, D);
+    const size_t s_lds = GraphSearchLds::bytes(ef_b, vamana_c_cap(ef_b), D), p_lds = diskann_prune_lds(cap, D);
     if (std::max(s_lds, p_lds) > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: the vector does not fit in LDS");
-    const double t_begin = hnsw_now_us();
+    const double t_begin = graph_now_us();
     VamanaDraws dr;
     vamana_draws(seed, n, r, dr);
-    const double draws_us = hnsw_now_us() - t_begin;
+    const double draws_us = graph_now_us() - t_begin;
     hipStream_t st = cur(h).stream;
     const uint32_t vis_words = (uint32_t)((n + 31) / 32);
     const uint32_t Bmax = (uint32_t)std::min<uint64_t>(VAMANA_BATCH, n);
@@ -143,7 +131,7 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
     uint32_t *d_adj = nullptr, *d_order = nullptr, *d_small = nullptr, *d_vis = nullptr, *d_beam_n = nullptr, *d_scored = nullptr, *d_status = nullptr;
     uint64_t *d_beam = nullptr, *d_ckeys = nullptr;
     float* d_pairs = nullptr;
-    struct Free { std::vector<void**> ps; ~Free() { for (void** p : ps) if (*p) (void)hipFree(*p); } } fr;
+    GraphFree fr;
     fr.ps = {(void**)&d_adj, (void**)&d_order, (void**)&d_small, (void**)&d_vis, (void**)&d_beam_n, (void**)&d_scored, (void**)&d_status,
              (void**)&d_beam, (void**)&d_ckeys, (void**)&d_pairs};
     LY_HIP(hipMalloc(&d_adj, std::max<size_t>((size_t)n * r, 1) * 4));
@@ -193,19 +181,19 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
         const float al = pass == 0 ? 1.0f : alpha;
         for (uint64_t b0 = 0; b0 < n && !stop; b0 += VAMANA_BATCH) {
             const uint32_t B = (uint32_t)std::min<uint64_t>(VAMANA_BATCH, n - b0);
-            double t0 = timed ? hnsw_now_us() : 0.0;
+            double t0 = timed ? graph_now_us() : 0.0;
             LY_HIP(hipMemsetAsync(d_vis, 0, (size_t)B * vis_words * 4, st));
             VamanaSearchArgs sa{};
             sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = metric; sa.Q = nullptr; sa.qids = d_order + b0; sa.k = 0; sa.ef = ef_b; sa.r = r;
             sa.anchors = DISKANN_BUILD_ANCHORS; sa.entry = entry; sa.n = n; sa.adj = d_adj; sa.vis = d_vis; sa.vis_words = vis_words;
             sa.out_beam = d_beam; sa.out_beam_n = d_beam_n; sa.out_scored = d_scored; sa.status = d_status;
             LY_TRY(launch_lds<k_vamana_search>(dim3(B), dim3(64), s_lds, st, sa));
-            if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = hnsw_now_us(); st_us[0] += t1 - t0; t0 = t1; }
+            if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = graph_now_us(); st_us[0] += t1 - t0; t0 = t1; }
             VamanaPruneArgs pa{};
             pa.V = h->rows; pa.ld = h->ld; pa.D = D; pa.metric = metric; pa.r = r; pa.cap = cap; pa.alpha = al; pa.adj = d_adj; pa.items = d_order + b0;
             pa.beam = d_beam; pa.beam_n = d_beam_n; pa.beam_stride = ef_b;
             LY_TRY(launch_lds<k_vamana_prune>(dim3(B), dim3(64), p_lds, st, pa));
-            if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = hnsw_now_us(); st_us[1] += t1 - t0; t0 = t1; }
+            if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = graph_now_us(); st_us[1] += t1 - t0; t0 = t1; }
             uint32_t Pb = 2;
             while (Pb < B * r) Pb <<= 1;
             VamanaCommitArgs ca{};
@@ -213,7 +201,7 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
             LY_TRY(launch_lds<k_vamana_commit>(dim3(1), dim3(1024), (size_t)Pb * 8, st, ca));
             pa.ckeys = d_ckeys; pa.n_ckeys = Pb; pa.beam = nullptr; pa.beam_n = nullptr;
             LY_TRY(launch_lds<k_vamana_prune>(dim3(Pb), dim3(64), p_lds, st, pa));   // every slot: a wave that heads no over-long run exits at once
-            if (timed) { LY_HIP(hipStreamSynchronize(st)); st_us[2] += hnsw_now_us() - t0; }
+            if (timed) { LY_HIP(hipStreamSynchronize(st)); st_us[2] += graph_now_us() - t0; }
             stop = ++batches == max_batches;
         }
     }
@@ -224,7 +212,7 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
     LY_TRY(diskann_install(h, d_adj, metric, r, l, alpha, n, entry));
     d_adj = nullptr;
     DiskannState& s = *h->diskann;
-    s.b_search_us = st_us[0]; s.b_prune_us = st_us[1]; s.b_commit_us = st_us[2]; s.b_draws_us = draws_us; s.b_total_us = hnsw_now_us() - t_begin;
+    s.b_search_us = st_us[0]; s.b_prune_us = st_us[1]; s.b_commit_us = st_us[2]; s.b_draws_us = draws_us; s.b_total_us = graph_now_us() - t_begin;
     return LYNSE_OK;
 }
 
@@ -237,26 +225,18 @@ extern "C" int lynse_hip_flat_load_diskann(lynse_hip_flat* h, int metric, uint32
     LY_TRY(diskann_check_params(r, l));
     l = std::max(l, r);
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
     if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "a DiskANN index holds fewer than 2^32 - 1 rows");
     if (n > h->n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the DiskANN index covers more rows than the handle holds");
     if (!adj) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (entry >= n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "DiskANN: the entry point is beyond the rows of the graph");
-    if (diskann_search_lds(1, h->dim) > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: the vector does not fit in LDS");
-    std::vector<uint32_t> lists((size_t)n * r, HNSW_PAD);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint32_t* dst = &lists[(size_t)i * r];
-        uint32_t w = 0;
-        for (uint32_t s = 0; s < r; ++s) {
-            const uint32_t v = adj[(size_t)i * r + s];
-            if (v == HNSW_PAD) continue;
-            if (v >= n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "DiskANN: a neighbour beyond the rows of the graph");
-            if (std::find(dst, dst + w, v) == dst + w) dst[w++] = v;
-        }
-    }
+    if (GraphSearchLds::bytes(1, vamana_c_cap(1), h->dim) > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: the vector does not fit in LDS");
+    std::vector<uint32_t> lists((size_t)n * r, GRAPH_PAD);
+    for (uint64_t i = 0; i < n; ++i)
+        LY_TRY(graph_take_list(adj + (size_t)i * r, r, n, "DiskANN: a neighbour beyond the rows of the graph", &lists[(size_t)i * r]));
     uint32_t* d_adj = nullptr;
     LY_HIP(hipMalloc(&d_adj, lists.size() * 4));
     const int rc = h2d_done(d_adj, lists.data(), lists.size() * 4);
@@ -300,12 +280,12 @@ extern "C" int lynse_hip_flat_diskann_stage_times(lynse_hip_flat* h, double* out
     if (!h->diskann) { for (int i = 0; i < 8; ++i) out8[i] = 0.0; return LYNSE_OK; }
     DiskannState& s = *h->diskann;
     out8[0] = s.b_search_us; out8[1] = s.b_prune_us; out8[2] = s.b_commit_us; out8[3] = s.b_draws_us; out8[4] = s.b_total_us;
-    out8[5] = s.searches; out8[6] = s.search_us; out8[7] = s.scored;
-    if (reset) s.searches = s.search_us = s.scored = 0.0;
+    out8[5] = s.search.searches; out8[6] = s.search.search_us; out8[7] = s.search.scored;
+    if (reset) s.search.searches = s.search.search_us = s.search.scored = 0.0;
     return LYNSE_OK;
 }
 
-// rule 8.  Queries go in chunks that keep the visited bitmaps (n_diskann bits per query) and the results under 256 MiB each.
+// rule 8; graph_search (graph_host.inc) runs the queries in chunks
 extern "C" int lynse_hip_flat_search_diskann_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t ef_query,
                                                  uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -313,62 +293,23 @@ extern "C" int lynse_hip_flat_search_diskann_f32(lynse_hip_flat* h, const float*
     if (nq == 0) return LYNSE_OK;
     if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     if (!h->diskann || !h->diskann->built()) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no DiskANN index on this handle: build or load one first");
     DiskannState& s = *h->diskann;
     if (metric != s.metric) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the DiskANN index was built for another metric");
     if (ef_query > DISKANN_L_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: ef must be between 1 and 4096");
     if (k == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
-    const uint32_t D = h->dim;
     const uint32_t ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>({(uint64_t)ef_query, (uint64_t)s.l, 10ull * k}), s.n);
-    const size_t lds = diskann_search_lds(ef, D);
+    const size_t lds = GraphSearchLds::bytes(ef, vamana_c_cap(ef), h->dim);
     if (lds > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "DiskANN: the beam (24 bytes per ef, ef >= 10 k) and the query do not fit in LDS");
-    const uint32_t vis_words = (uint32_t)((s.n + 31) / 32);
-    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (256ull << 20) / ((uint64_t)vis_words * 4), (256ull << 20) / ((uint64_t)k * 12), 1ull << 20}));
-    LY_TRY(ivf_grow(&s.d_q, &s.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&s.d_vis, &s.vis_cap, (size_t)qc * vis_words));
-    LY_TRY(ivf_grow(&s.d_rows, &s.rows_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_dists, &s.dists_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_counts, &s.counts_cap, (size_t)qc * 2));   // counts, then the distances scored
-    if (!s.d_status) LY_HIP(hipMalloc(&s.d_status, 4));
-    hipStream_t st = cur(h).stream;
-    const bool timed = h->profiling.load();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timed) { LY_HIP(hipEventCreate(&e0)); LY_HIP(hipEventCreate(&e1)); }
-    struct EvFree { hipEvent_t &a, &b; ~EvFree() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evfree{e0, e1};
-    std::vector<uint32_t> scored;
-    LY_HIP(hipMemsetAsync(s.d_status, 0, 4, st));
-    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
-        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(s.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemsetAsync(s.d_vis, 0, (size_t)nqc * vis_words * 4, st));
+    return graph_search(h, s.search, s.n, lds, "DiskANN: the candidate set outgrew its 2 ef + 41 slots", queries, nq, k, out_rows, out_dists, out_counts,
+                        [&](const GraphSearchChunk& c) {
         VamanaSearchArgs a{};
-        a.V = h->rows; a.ld = h->ld; a.D = D; a.metric = metric; a.Q = s.d_q; a.k = k; a.ef = ef; a.r = s.r; a.anchors = DISKANN_QUERY_ANCHORS;
-        a.entry = s.entry; a.n = s.n; a.adj = s.d_adj; a.vis = s.d_vis; a.vis_words = vis_words; a.out_rows = s.d_rows; a.out_dists = s.d_dists;
-        a.out_counts = s.d_counts; a.out_scored = s.d_counts + qc; a.status = s.d_status;
-        if (timed) LY_HIP(hipEventRecord(e0, st));
-        LY_TRY(launch_lds<k_vamana_search>(dim3(nqc), dim3(64), lds, st, a));
-        if (timed) LY_HIP(hipEventRecord(e1, st));
-        LY_HIP(hipMemcpyAsync(out_rows + q0 * k, s.d_rows, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_dists + q0 * k, s.d_dists, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_counts + q0, s.d_counts, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-        if (timed) {
-            scored.resize(nqc);
-            LY_HIP(hipMemcpyAsync(scored.data(), s.d_counts + qc, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-        }
-        LY_TRY(stream_wait(st));
-        if (timed) {
-            float ms = 0.0f;
-            LY_HIP(hipEventElapsedTime(&ms, e0, e1));
-            s.search_us += (double)ms * 1e3;
-            for (uint32_t v : scored) s.scored += (double)v;
-        }
-    }
-    uint32_t status = 0;
-    LY_HIP(hipMemcpy(&status, s.d_status, 4, hipMemcpyDeviceToHost));
-    if (status) return set_error(LYNSE_ERR_INTERNAL, "DiskANN: the candidate set outgrew its 2 ef + 41 slots");
-    if (timed) s.searches += 1;
-    return LYNSE_OK;
+        a.V = h->rows; a.ld = h->ld; a.D = h->dim; a.metric = metric; a.Q = c.Q; a.k = k; a.ef = ef; a.r = s.r; a.anchors = DISKANN_QUERY_ANCHORS;
+        a.entry = s.entry; a.n = s.n; a.adj = s.d_adj; a.vis = c.vis; a.vis_words = c.vis_words; a.out_rows = c.out_rows; a.out_dists = c.out_dists;
+        a.out_counts = c.out_counts; a.out_scored = c.out_scored; a.status = c.status;
+        return launch_lds<k_vamana_search>(dim3(c.nqc), dim3(64), c.lds, c.st, a);
+    });
 }

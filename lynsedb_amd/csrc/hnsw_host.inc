@@ -1,5 +1,6 @@
 // hnsw_host.inc — HNSW-{IP,L2,COS} on a FLAT handle (HNSWIndex, src/index/hnsw.rs; Collection, src/engine.rs:4606-4655, :4743-4745).
-// Included at the end of lynse_hip.hip after rabitq_host.inc (the SmallRng restatement is pqrng); kernels in hnsw.h.  The rule block of
+// Included at the end of lynse_hip.hip after rabitq_host.inc (the SmallRng restatement is pqrng) and graph_host.inc, whose lock, handle
+// check, clock, list normaliser and search driver it shares with diskann_host.inc; kernels in hnsw.h.  The rule block of
 // include/lynse_hip.h states the contract, DESIGN.md §19 the reasoning.  The graph shares the handle's rows: it holds ids only.
 
 struct HnswState {
@@ -9,13 +10,9 @@ struct HnswState {
     std::vector<uint32_t> levels;         // [n]
     std::vector<uint32_t> upper_node, upper_level;   // ascending (node, level), levels >= 1
     uint32_t *d_adj0 = nullptr, *d_upper_off = nullptr, *d_upper_adj = nullptr;
-    // search scratch
-    float *d_q = nullptr, *d_dists = nullptr;
-    uint64_t* d_rows = nullptr;
-    uint32_t *d_vis = nullptr, *d_counts = nullptr, *d_status = nullptr;
-    size_t q_cap = 0, dists_cap = 0, rows_cap = 0, vis_cap = 0, counts_cap = 0;
-    // the last build, microseconds of host time around synchronised stages; the searches timed with profiling on
-    double cand_us = 0.0, select_us = 0.0, reverse_us = 0.0, searches = 0.0, search_us = 0.0, scored = 0.0;
+    GraphSearchScratch search;            // with the searches timed with profiling on
+    // the last build, microseconds of host time around synchronised stages
+    double cand_us = 0.0, select_us = 0.0, reverse_us = 0.0;
 
     bool built() const { return d_adj0 != nullptr; }
     void free_index() {
@@ -27,11 +24,7 @@ struct HnswState {
         m = ef_search = entry = top_level = 0;
         n = 0;
     }
-    ~HnswState() {
-        free_index();
-        for (void* p : {(void*)d_q, (void*)d_dists, (void*)d_rows, (void*)d_vis, (void*)d_counts, (void*)d_status})
-            if (p) (void)hipFree(p);
-    }
+    ~HnswState() { free_index(); }
 };
 
 static void hnsw_release(lynse_hip_flat* h) {
@@ -64,28 +57,12 @@ static int hnsw_check_metric(int metric) {
     if (metric_binary(metric)) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW is defined for ip / l2 / cosine");
     return LYNSE_OK;
 }
-static int hnsw_check_handle(const lynse_hip_flat* h) {
-    if (h->dtype != LYNSE_DTYPE_F32) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW on an F16 shard is not supported");
-    if (h->packed_only) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW is defined for float rows (ip / l2 / cosine)");
-    if (h->row_stride != 1 || h->row_offset != 0) return set_error(LYNSE_ERR_UNSUPPORTED, "an HNSW index is not row-sharded");
-    return LYNSE_OK;
-}
 static int hnsw_check_params(uint32_t m, uint32_t ef_construction, uint32_t ef_search) {
     if (m < HNSW_M_MIN || m > HNSW_M_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: m must be between 2 and 32");
     if (ef_construction < 1 || ef_construction > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef_construction must be between 1 and 4096");
     if (ef_search < 1 || ef_search > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef_search must be between 1 and 4096");
     return LYNSE_OK;
 }
-// the exclusive lock of the HNSW entries: tickets outstanding are a refusal of this index, not a bad argument
-static int hnsw_lock(lynse_hip_flat* h, std::unique_lock<std::shared_mutex>& lk) {
-    lk = std::unique_lock<std::shared_mutex>(h->rw);
-    if (h->inflight.load(std::memory_order_acquire) != 0) {
-        lk.unlock();
-        return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: searches are in flight on this handle: wait for the outstanding tickets first");
-    }
-    return LYNSE_OK;
-}
-
 // A graph on the host: adj0[n][2 m], upper lists in ascending (node, level) order.  Installing uploads it.
 struct HnswGraph {
     uint32_t m = 0, entry = 0, top_level = 0;
@@ -94,7 +71,7 @@ struct HnswGraph {
     void shape(uint32_t mm, const uint32_t* lv, uint64_t nn) {
         m = mm; n = nn;
         levels.assign(lv, lv + nn);
-        upper_off.assign(nn, HNSW_PAD);
+        upper_off.assign(nn, GRAPH_PAD);
         uint64_t nu = 0;
         top_level = 0;
         for (uint64_t i = 0; i < nn; ++i) {
@@ -105,8 +82,8 @@ struct HnswGraph {
         }
         for (uint64_t i = 0; i < nn; ++i)
             if (lv[i] == top_level) { entry = (uint32_t)i; break; }   // the first row of the highest level (hnsw.rs:967-975)
-        adj0.assign((size_t)nn * 2 * mm, HNSW_PAD);
-        upper_adj.assign((size_t)nu * mm, HNSW_PAD);
+        adj0.assign((size_t)nn * 2 * mm, GRAPH_PAD);
+        upper_adj.assign((size_t)nu * mm, GRAPH_PAD);
     }
     uint32_t* list(uint32_t node, uint32_t level) {
         return level == 0 ? &adj0[(size_t)node * 2 * m] : &upper_adj[((size_t)upper_off[node] + level - 1) * m];
@@ -138,10 +115,6 @@ static int hnsw_install(lynse_hip_flat* h, HnswGraph& gph, int metric, uint32_t 
     return LYNSE_OK;
 }
 
-static inline double hnsw_now_us() {
-    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3;
-}
-
 // Rules 2-4 for one level: `items` = S_l ascending.  Fills the level's lists of `gph`.
 static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint32_t level, const std::vector<uint32_t>& items,
                             uint32_t ef_construction, double* times3) {
@@ -156,7 +129,7 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
     uint64_t* d_cr = nullptr;
     uint32_t *d_cc = nullptr, *d_fid = nullptr;
     uint32_t *d_uid = nullptr; float* d_ud = nullptr; uint64_t* d_uoff = nullptr; uint32_t* d_oid = nullptr; float* d_od = nullptr;
-    struct Free { std::vector<void**> ps; ~Free() { for (void** p : ps) if (*p) (void)hipFree(*p); } } fr;
+    GraphFree fr;
     fr.ps = {(void**)&d_items, (void**)&d_q, (void**)&d_cd, (void**)&d_fd, (void**)&d_cr, (void**)&d_cc, (void**)&d_fid,
              (void**)&d_uid, (void**)&d_ud, (void**)&d_uoff, (void**)&d_oid, (void**)&d_od};
     if (level > 0) {
@@ -176,7 +149,7 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
     const size_t sel_lds = 512 + (size_t)D * 4;
     for (uint64_t q0 = 0; q0 < ns; q0 += qc) {
         const uint64_t nqc = std::min<uint64_t>(qc, ns - q0);
-        double t0 = hnsw_now_us();
+        double t0 = graph_now_us();
         hipLaunchKernelGGL(k_hnsw_gather, dim3((uint32_t)std::min<uint64_t>((nqc * D + 255) / 256, (uint64_t)h->num_cu * 32)), dim3(256), 0, st,
                            h->rows, h->ld, D, d_items + q0, 0u, nqc, d_q);
         LY_HIP(hipGetLastError());
@@ -185,7 +158,7 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
         LY_TRY(search_impl(h, d_q, false, nqc, ask, metric, d_cr, d_cd, d_cc, true, nullptr, nullptr, level > 0 ? (uint64_t)ns : 0, level > 0,
                            level > 0 ? words.data() : nullptr, words.size(), true));
         LY_HIP(hipStreamSynchronize(st));
-        double t1 = hnsw_now_us();
+        double t1 = graph_now_us();
         times3[0] += t1 - t0;
         // rule 3: the forward lists
         HnswSelectArgs sa{};
@@ -194,30 +167,30 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
         sa.out_ids = d_fid + q0 * cap; sa.out_d = d_fd + q0 * cap;
         LY_TRY(launch_lds<k_hnsw_select>(dim3((uint32_t)nqc), dim3(64), sel_lds, st, sa));
         LY_HIP(hipStreamSynchronize(st));
-        times3[1] += hnsw_now_us() - t1;
+        times3[1] += graph_now_us() - t1;
     }
     std::vector<uint32_t> fid((size_t)ns * cap);
     std::vector<float> fd((size_t)ns * cap);
-    double t2 = hnsw_now_us();
+    double t2 = graph_now_us();
     LY_HIP(hipMemcpy(fid.data(), d_fid, fid.size() * 4, hipMemcpyDeviceToHost));
     LY_HIP(hipMemcpy(fd.data(), d_fd, fd.size() * 4, hipMemcpyDeviceToHost));
     // rule 4: U(i) = F(i) and the reverse edges, each member once, ordered by (d, node) — as keys, so one integer sort per node
     std::vector<uint32_t> item_of;
     if (level > 0) {
-        item_of.assign(n, HNSW_PAD);
+        item_of.assign(n, GRAPH_PAD);
         for (uint32_t t = 0; t < ns; ++t) item_of[items[t]] = t;
     }
     auto item = [&](uint32_t node) { return level > 0 ? item_of[node] : node; };
     std::vector<uint64_t> off((size_t)ns + 1, 0);
     for (uint32_t t = 0; t < ns; ++t)
-        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != HNSW_PAD; ++s) {
+        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != GRAPH_PAD; ++s) {
             ++off[t + 1];
             ++off[item(fid[(size_t)t * cap + s]) + 1];
         }
     for (uint32_t t = 0; t < ns; ++t) off[t + 1] += off[t];
     std::vector<uint64_t> keys(off[ns]), fill(off.begin(), off.end() - 1);
     for (uint32_t t = 0; t < ns; ++t)
-        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != HNSW_PAD; ++s) {
+        for (uint32_t s = 0; s < cap && fid[(size_t)t * cap + s] != GRAPH_PAD; ++s) {
             const uint32_t j = fid[(size_t)t * cap + s];
             const float d = fd[(size_t)t * cap + s];
             keys[fill[t]++] = make_key(d, j, true);
@@ -241,9 +214,9 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
             uoff.push_back(uid.size());
         }
     }
-    times3[2] += hnsw_now_us() - t2;
+    times3[2] += graph_now_us() - t2;
     if (!over.empty()) {
-        double t3 = hnsw_now_us();
+        double t3 = graph_now_us();
         const size_t no = over.size();
         LY_HIP(hipMalloc(&d_uid, uid.size() * 4));
         LY_HIP(hipMalloc(&d_ud, ud.size() * 4));
@@ -261,7 +234,7 @@ static int hnsw_build_level(lynse_hip_flat* h, HnswGraph& gph, int metric, uint3
         std::vector<uint32_t> oid(no * cap);
         LY_HIP(hipMemcpy(oid.data(), d_oid, oid.size() * 4, hipMemcpyDeviceToHost));
         for (size_t o = 0; o < no; ++o) memcpy(gph.list(items[over[o]], level), &oid[o * cap], (size_t)cap * 4);
-        times3[1] += hnsw_now_us() - t3;
+        times3[1] += graph_now_us() - t3;
     }
     return LYNSE_OK;
 }
@@ -272,9 +245,9 @@ extern "C" int lynse_hip_flat_build_hnsw(lynse_hip_flat* h, int metric, uint32_t
     LY_TRY(hnsw_check_metric(metric));
     LY_TRY(hnsw_check_params(m, ef_construction, ef_search));
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     const uint64_t n = h->n;
     if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
     if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "an HNSW index holds fewer than 2^32 - 1 rows");
@@ -301,7 +274,7 @@ extern "C" int lynse_hip_flat_build_hnsw(lynse_hip_flat* h, int metric, uint32_t
     return LYNSE_OK;
 }
 
-// A graph as hnsw_params exports it.  Lists are brought into the stored form: HNSW_PAD entries dropped, a neighbour named twice kept
+// A graph as hnsw_params exports it.  Lists are brought into the stored form: GRAPH_PAD entries dropped, a neighbour named twice kept
 // once (its first place) — neither changes a search: the second visit of a node is skipped at level 0 and moves nothing above.
 extern "C" int lynse_hip_flat_load_hnsw(lynse_hip_flat* h, int metric, uint32_t m, uint32_t ef_search, const uint32_t* levels, uint64_t n,
                                         const uint32_t* adj0, uint64_t n_upper, const uint32_t* upper_node, const uint32_t* upper_level,
@@ -310,9 +283,9 @@ extern "C" int lynse_hip_flat_load_hnsw(lynse_hip_flat* h, int metric, uint32_t 
     LY_TRY(hnsw_check_metric(metric));
     LY_TRY(hnsw_check_params(m, 1, ef_search));
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     if (n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "need at least one vector");
     if (n >= 0xffffffffull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "an HNSW index holds fewer than 2^32 - 1 rows");
     if (n > h->n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the HNSW index covers more rows than the handle holds");
@@ -332,15 +305,9 @@ extern "C" int lynse_hip_flat_load_hnsw(lynse_hip_flat* h, int metric, uint32_t 
     if (entry >= n || levels[entry] != gph.top_level) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: the entry point is not a row of the top level");
     gph.entry = entry;
     auto take = [&](const uint32_t* src, uint32_t cap, uint32_t level, uint32_t* dst) -> int {
-        uint32_t w = 0;
-        for (uint32_t s = 0; s < cap; ++s) {
-            const uint32_t v = src[s];
-            if (v == HNSW_PAD) continue;
-            if (v >= n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a neighbour beyond the rows of the graph");
-            if (levels[v] < level) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a neighbour below the level of its list");
-            if (std::find(dst, dst + w, v) == dst + w) dst[w++] = v;
-        }
-        return LYNSE_OK;
+        return graph_take_list(src, cap, n, "HNSW: a neighbour beyond the rows of the graph", dst, [&](uint32_t v) {
+            return levels[v] < level ? set_error(LYNSE_ERR_INVALID_ARGUMENT, "HNSW: a neighbour below the level of its list") : LYNSE_OK;
+        });
     };
     for (uint64_t i = 0; i < n; ++i) LY_TRY(take(adj0 + i * 2 * m, 2 * m, 0, gph.list((uint32_t)i, 0)));
     for (uint64_t u = 0; u < n_upper; ++u) LY_TRY(take(upper_adj + u * m, m, upper_level[u], &gph.upper_adj[u * m]));
@@ -385,12 +352,12 @@ extern "C" int lynse_hip_flat_hnsw_stage_times(lynse_hip_flat* h, double* out6, 
     LY_WRITER(h, lk);
     if (!h->hnsw) { for (int i = 0; i < 6; ++i) out6[i] = 0.0; return LYNSE_OK; }
     HnswState& s = *h->hnsw;
-    out6[0] = s.cand_us; out6[1] = s.select_us; out6[2] = s.reverse_us; out6[3] = s.searches; out6[4] = s.search_us; out6[5] = s.scored;
-    if (reset) s.searches = s.search_us = s.scored = 0.0;
+    out6[0] = s.cand_us; out6[1] = s.select_us; out6[2] = s.reverse_us; out6[3] = s.search.searches; out6[4] = s.search.search_us; out6[5] = s.search.scored;
+    if (reset) s.search.searches = s.search.search_us = s.search.scored = 0.0;
     return LYNSE_OK;
 }
 
-// rule 5.  Queries go in chunks that keep the visited bitmaps (n_hnsw bits per query) and the results under 256 MiB each.
+// rule 5; graph_search (graph_host.inc) runs the queries in chunks
 extern "C" int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t ef_query,
                                               uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -398,64 +365,25 @@ extern "C" int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat* h, const float* qu
     if (nq == 0) return LYNSE_OK;
     if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     std::unique_lock<std::shared_mutex> lk;
-    LY_TRY(hnsw_lock(h, lk));
+    LY_TRY(graph_lock(h, lk));
     LY_TRY(use_device(h));
-    LY_TRY(hnsw_check_handle(h));
+    LY_TRY(graph_check_handle(h));
     if (!h->hnsw || !h->hnsw->built()) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no HNSW index on this handle: build or load one first");
     HnswState& s = *h->hnsw;
     if (metric != s.metric) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "the HNSW index was built for another metric");
     if (ef_query > HNSW_EF_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: ef must be between 1 and 4096");
     if (k == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
-    const uint32_t D = h->dim;
     // ef = max(ef, k); beyond the rows of the graph R never fills, so min(ef, n) answers the same
     const uint32_t ef = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(ef_query ? ef_query : s.ef_search, k), s.n);
-    const size_t lds = (size_t)ef * 24 + 64 + 256 + (size_t)D * 4;   // R: ef keys, C: 2 ef + 8 keys, 64 neighbour slots, the query
+    const size_t lds = GraphSearchLds::bytes(ef, hnsw_c_cap(ef), h->dim);
     if (lds > PoolRerank::LDS_MAX) return set_error(LYNSE_ERR_UNSUPPORTED, "HNSW: the beam (24 bytes per ef, ef >= k) and the query do not fit in LDS");
-    const uint32_t vis_words = (uint32_t)((s.n + 31) / 32);
-    const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (256ull << 20) / ((uint64_t)vis_words * 4), (256ull << 20) / ((uint64_t)k * 12), 1ull << 20}));
-    LY_TRY(ivf_grow(&s.d_q, &s.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&s.d_vis, &s.vis_cap, (size_t)qc * vis_words));
-    LY_TRY(ivf_grow(&s.d_rows, &s.rows_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_dists, &s.dists_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_counts, &s.counts_cap, (size_t)qc * 2));   // counts, then the distances scored
-    if (!s.d_status) LY_HIP(hipMalloc(&s.d_status, 4));
-    hipStream_t st = cur(h).stream;
-    const bool timed = h->profiling.load();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timed) { LY_HIP(hipEventCreate(&e0)); LY_HIP(hipEventCreate(&e1)); }
-    struct EvFree { hipEvent_t &a, &b; ~EvFree() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evfree{e0, e1};
-    std::vector<uint32_t> scored;
-    LY_HIP(hipMemsetAsync(s.d_status, 0, 4, st));
-    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
-        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(s.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemsetAsync(s.d_vis, 0, (size_t)nqc * vis_words * 4, st));
+    return graph_search(h, s.search, s.n, lds, "HNSW: the candidate set outgrew its 2 ef slots", queries, nq, k, out_rows, out_dists, out_counts,
+                        [&](const GraphSearchChunk& c) {
         HnswSearchArgs a{};
-        a.V = h->rows; a.ld = h->ld; a.D = D; a.metric = metric; a.Q = s.d_q; a.k = k; a.ef = ef; a.m = s.m;
+        a.V = h->rows; a.ld = h->ld; a.D = h->dim; a.metric = metric; a.Q = c.Q; a.k = k; a.ef = ef; a.m = s.m;
         a.entry = s.entry; a.top_level = s.top_level; a.adj0 = s.d_adj0; a.upper_off = s.d_upper_off; a.upper_adj = s.d_upper_adj;
-        a.vis = s.d_vis; a.vis_words = vis_words; a.out_rows = s.d_rows; a.out_dists = s.d_dists; a.out_counts = s.d_counts;
-        a.out_scored = s.d_counts + qc; a.status = s.d_status;
-        if (timed) LY_HIP(hipEventRecord(e0, st));
-        LY_TRY(launch_lds<k_hnsw_search>(dim3(nqc), dim3(64), lds, st, a));
-        if (timed) LY_HIP(hipEventRecord(e1, st));
-        LY_HIP(hipMemcpyAsync(out_rows + q0 * k, s.d_rows, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_dists + q0 * k, s.d_dists, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_counts + q0, s.d_counts, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-        if (timed) {
-            scored.resize(nqc);
-            LY_HIP(hipMemcpyAsync(scored.data(), s.d_counts + qc, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
-        }
-        LY_TRY(stream_wait(st));
-        if (timed) {
-            float ms = 0.0f;
-            LY_HIP(hipEventElapsedTime(&ms, e0, e1));
-            s.search_us += (double)ms * 1e3;
-            for (uint32_t v : scored) s.scored += (double)v;
-        }
-    }
-    uint32_t status = 0;
-    LY_HIP(hipMemcpy(&status, s.d_status, 4, hipMemcpyDeviceToHost));
-    if (status) return set_error(LYNSE_ERR_INTERNAL, "HNSW: the candidate set outgrew its 2 ef slots");
-    if (timed) s.searches += 1;
-    return LYNSE_OK;
+        a.vis = c.vis; a.vis_words = c.vis_words; a.out_rows = c.out_rows; a.out_dists = c.out_dists; a.out_counts = c.out_counts;
+        a.out_scored = c.out_scored; a.status = c.status;
+        return launch_lds<k_hnsw_search>(dim3(c.nqc), dim3(64), c.lds, c.st, a);
+    });
 }

@@ -3575,6 +3575,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "ivf_async.inc"
 #include "pq_host.inc"
 #include "rabitq_host.inc"
+#include "graph_host.inc"
 #include "hnsw_host.inc"
 #include "diskann_host.inc"
 #include "range_host.inc"

@@ -219,3 +219,23 @@ def test_restatement_build_invariants(ref):
     assert all(not np.array_equal(graphs[i], graphs[i + 1]) for i in range(3))
     hub = D.ref_build(ref, D.hub_data(), L2, 4, 8, 1.2)
     assert hub.longest > 4 + 200, hub.longest
+
+
+# ---- the build's resource report ------------------------------------------------------------------------------------------------------
+def test_search_kernel_keeps_its_registers():
+    """k_vamana_search in csrc/resource_usage.txt, read the way tests/test_text_modes.py reads it: no scratch, no spilled register, three waves
+    per SIMD or more — what the beam shared through csrc/graph.h (graph_beam, forced inline, its state in registers) has to keep."""
+    import re
+    from pathlib import Path
+
+    import lynsedb_amd
+
+    rep = Path(lynsedb_amd.__file__).parent / "csrc" / "resource_usage.txt"
+    assert rep.exists(), "the build writes csrc/resource_usage.txt"
+    blocks = re.findall(r"Function Name: (\S+)(.*?)LDS Size", rep.read_text(), flags=re.S)
+    mine = [(n, {k: int(v) for k, v in re.findall(r"(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\d+)", body)})
+            for n, body in blocks if "k_vamana_search" in n]
+    assert mine, "k_vamana_search is not in the report"
+    for name, f in mine:
+        assert f["ScratchSize [bytes/lane]"] == 0 and f["SGPRs Spill"] == 0 and f["VGPRs Spill"] == 0, (name, f)
+        assert f["Occupancy [waves/SIMD]"] >= 3, (name, f)

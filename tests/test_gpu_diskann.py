@@ -110,7 +110,8 @@ def test_search_designed_graphs(L, ref):
 
 def test_search_ties_through_compactions(L, ref):
     """integer rows in two dimensions: most distances tie, lists of 64 and ef = 10: C passes its 2 ef + 41 slots with ties at worst.dist
-    among its entries, so the compaction's `<=` and the (dist, node) order of every pop and eviction decide the answer"""
+    among its entries, so the compaction's `<=` (graph_beam, csrc/graph.h: `if (Cn + 8 > c_cap)` -> graph_compact with `(kx >> 32) <= wd`)
+    and the (dist, node) order of every pop and eviction decide the answer"""
     rng = np.random.default_rng(6)
     data = rng.integers(-6, 7, (600, 2)).astype(f32)
     queries = rng.integers(-6, 7, (20, 2)).astype(f32)
@@ -222,8 +223,37 @@ def test_build_seed_and_stage_times(L, ref):
 
 
 # ----------------------------------------------------------------------------------------- limits ----
+def test_search_in_two_chunks(L):
+    """graph_search (csrc/graph_host.inc): qc = min(nq, 256 MiB / (4 vis_words), ...).  n = 2^22 rows give vis_words = 131,072 (512 KiB of
+    visited bits per query) and qc = 512, so 513 queries go as chunks of 512 and 1: the second uploads `queries + q0 * D` and copies
+    back to `out_rows + q0 * k`, `out_dists + q0 * k` and `out_counts + q0`.  Every list is a pad (r = l = 1, entry 1): a query sees its 9
+    starts — row 1 and rows a n / 8 — and answers the 3 nearest by (distance, row); integer coordinates, so every L2 distance is exact
+    in f32."""
+    n, nq, k = 1 << 22, 513, 3
+    assert (256 << 20) // (4 * ((n + 31) // 32)) == nq - 1
+    rng = np.random.default_rng(22)
+    data = rng.integers(-8, 9, (n, 2)).astype(f32)
+    queries = np.stack([np.arange(nq) % 32 - 16, np.arange(nq) // 32 - 8], axis=1).astype(f32)
+    assert np.unique(queries, axis=0).shape[0] == nq
+    starts = np.array(D.starts_py(n, 1, D.QUERY_ANCHORS))
+    assert starts.tolist() == [1] + [a * n // 8 for a in range(8)]
+    idx = flat(L, data)
+    load(idx, D.Graph(1, 1, np.full((n, 1), PAD, np.uint32), 1), L2)
+    idx.profile_enable(True)
+    idx.diskann_stage_times(reset=True)
+    rows, dists, counts = idx.search_diskann_batch_arrays(queries, k, L2)
+    t = idx.diskann_stage_times(reset=True)
+    idx.profile_enable(False)
+    d = ((queries[:, None, :] - data[starts][None, :, :]) ** 2).sum(axis=2, dtype=f32)   # [nq][9]
+    order = np.stack([np.lexsort((starts, d[qi]))[:k] for qi in range(nq)])
+    assert counts.tolist() == [k] * nq, np.nonzero(counts != k)[0][:5]
+    assert np.array_equal(rows, starts[order].astype(np.uint64)), np.nonzero((rows != starts[order]).any(axis=1))[0][:5]
+    assert np.array_equal(dists.view(np.uint32), np.take_along_axis(d, order, axis=1).view(np.uint32))
+    assert (t["searches"], t["scored"]) == (1, 9 * nq), t
+
+
 def test_largest_beam(L, ref):
-    """lynse_hip_flat_search_diskann_f32: 24 ef + 584 + 4 D bytes of LDS.  D = 16: ef = 6,790 (k = 679) fits, ef = 6,800 (k = 680) is the
+    """lynse_hip_flat_search_diskann_f32: GraphSearchLds::bytes(ef, vamana_c_cap(ef), D) (csrc/graph.h) = 24 ef + 584 + 4 D bytes of LDS.  D = 16: ef = 6,790 (k = 679) fits, ef = 6,800 (k = 680) is the
     first that does not: refused, and the next search still answers."""
     assert 24 * 6790 + 584 + 64 <= LDS_MAX < 24 * 6800 + 584 + 64
     rng = np.random.default_rng(9)

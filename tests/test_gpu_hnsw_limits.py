@@ -1,5 +1,5 @@
-"""HNSW-{IP,L2,COS} at its limits: the code paths of csrc/hnsw.h and csrc/hnsw_host.inc that the shapes of tests/test_gpu_hnsw.py never
-reach — builds whose candidate lists come from the staged plan, a build level in more than one pass, beams beyond 64 KiB of LDS up to the
+"""HNSW-{IP,L2,COS} at its limits: the code paths of csrc/hnsw.h and csrc/hnsw_host.inc, and of the beam and the search driver they
+share with DiskANN (csrc/graph.h, csrc/graph_host.inc), that the shapes of tests/test_gpu_hnsw.py never reach — builds whose candidate lists come from the staged plan, a build level in more than one pass, beams beyond 64 KiB of LDS up to the
 160 KiB limit and the refusal behind it, m = 31 / 32, the tie-keeping compaction of the bounded candidate set, the count of distances
 scored, the widest row the select kernel holds, and level 52.  The method is that of tests/test_gpu_hnsw.py: levels, adjacency, entry
 point, result ids, f32 distance bits and counts are compared exactly with the restatement (tests/hnsw_ref/hnsw_ref.c); the designed
@@ -95,7 +95,7 @@ def test_build_level_in_two_passes(deep):
 
 
 def test_beams_beyond_64_kib(deep, ref):
-    """lynse_hip_flat_search_hnsw_f32: lds = 24 ef + 320 + 4 D with ef = min(max(ef, k), n).  (k 10, ef 4096): 98,640 B, the first beam that
+    """lynse_hip_flat_search_hnsw_f32: lds = GraphSearchLds::bytes(ef, hnsw_c_cap(ef), D) = 24 ef + 320 + 4 D with ef = min(max(ef, k), n).  (k 10, ef 4096): 98,640 B, the first beam that
     needs the raised LDS attribute (launch_lds -> ensure_lds beyond 64 KiB); (k 5400, the index's ef): ef = 5400, 129,936 B.  The descent
     runs from level 13.  The scored count of both batches equals the restatement's."""
     idx, data, queries, g = deep
@@ -128,7 +128,8 @@ def test_largest_beam_and_the_refusal(L, ref):
                                                     (65, 128, 32, 1.0, None, "gauss"), (600, 20, 3, 1.0, None, "dup"), (600, 8, 5, 0.8, None, "nonfinite"),
                                                     (600, 3, 31, 1.0, None, "int"), (600, 24, 32, 0.8, None, "gauss"), (600, 8, 32, 1.0, 0.5, "gauss")])
 def test_search_at_the_ends_of_m(L, ref, n, dim, m, fill, p_up, kind):
-    """k_hnsw_search with 2 m = 62 / 64 stored level-0 neighbours (`lane < 2 * a.m`: one per lane, all 64 lanes at m = 32) and upper lists
+    """k_hnsw_search with 2 m = 62 / 64 stored level-0 neighbours (graph_beam, csrc/graph.h, `lane < width` with width = 2 m: one per lane,
+    all 64 lanes at m = 32) and upper lists
     of 31 / 32 scored in four steps of 8 (`lane < a.m`), beside the odd m = 3 / 5 whose lists end inside a step.  fill = 1.0: every
     level-0 list holds 2 m ids; with p_up = 0.5 half the nodes of a level are on the next, so every upper list holds 32 too.  Every batch's
     scored count is compared as well."""
@@ -183,7 +184,7 @@ def run_designed(L, ref, case):
 
 
 def test_compaction_keeps_ties(L, ref):
-    """k_hnsw_search, `if (Cn + 8 > c_cap)` -> hnsw_compact with `(kx >> 32) <= wd`: with ef = 3 (c_cap = 14) the ninth neighbour of the
+    """k_hnsw_search's beam (graph_beam, csrc/graph.h), `if (Cn + 8 > c_cap)` -> graph_compact with `(kx >> 32) <= wd`: with ef = 3 (c_cap = 14) the ninth neighbour of the
     entry finds C at 8 entries and forces the compaction while rows 5 and 6, out of R, tie with worst.dist; row 10 is reachable through
     row 6 only.  `<` for `<=` answers [8, 7, 4] (tests/test_hnsw_modes.py shows it on a model)."""
     run_designed(L, ref, H.tie_bridge())
@@ -191,7 +192,7 @@ def test_compaction_keeps_ties(L, ref):
 
 @pytest.mark.parametrize("kind", ["descending", "ascending", "ties"])
 def test_fans(L, ref, kind):
-    """k_hnsw_search admission, `!full || (key >> 32) < (worst >> 32)`, over one expansion of 64 (m = 32): descending distances — every
+    """k_hnsw_search's beam (graph_beam, csrc/graph.h), admission, `!full || (key >> 32) < (worst >> 32)`, over one expansion of 64 (m = 32): descending distances — every
     neighbour is admitted and, with c_cap = 2 ef + 8 <= 26, every scoring step after the first compacts; ascending — nothing is admitted
     once R is full; 64 neighbours at exactly worst.dist — none is admitted (strict, on the distance alone).  ef = k on both sides of 8."""
     for ef in H.FAN_EFS:
@@ -199,7 +200,7 @@ def test_fans(L, ref, kind):
 
 
 def test_all_ties(L, ref):
-    """k_hnsw_search, `Rn >= ef && (best >> 32) > (worst >> 32)`: with every distance equal nothing is ever beyond worst.dist, so the
+    """k_hnsw_search's beam (graph_beam, csrc/graph.h), `Rn >= ef && (best >> 32) > (worst >> 32)`: with every distance equal nothing is ever beyond worst.dist, so the
     loop `while (Cn && !broken)` ends by C running empty, after each admitted node was popped and expanded.  600 copies of one row on
     the path graph, and a NaN query (every distance +inf at once) over Gaussian rows on the path graph and on a random graph."""
     for k, ef in H.ALL_TIES:
@@ -241,10 +242,38 @@ def test_level_53_is_refused(L):
 
 @pytest.mark.parametrize("n", H.VISITED_NS)
 def test_visited_words(L, ref, n):
-    """k_hnsw_search, `atomicOr(&vis[nb >> 5], 1u << (nb & 31u))` with vis_words = (n + 31) / 32: one expansion marks rows 31 | 32, 63 |
+    """k_hnsw_search's beam (graph_beam, csrc/graph.h), `atomicOr(&vis[nb >> 5], 1u << (nb & 31u))` with vis_words = (n + 31) / 32: one expansion marks rows 31 | 32, 63 |
     64 — two lanes on one word, words 0, 1 and 2 — at n = 32 / 33 / 64 / 65, where the last word is full or holds one bit; rows named
     again by later lists are not scored twice (the scored count)."""
     run_designed(L, ref, H.visited_words(n))
+
+
+# --------------------------------------------------------------------- 6b. the chunks of a search ----
+def test_search_in_two_chunks(L):
+    """graph_search (csrc/graph_host.inc): qc = min(nq, 256 MiB / (4 vis_words), ...).  n = 2^22 rows give vis_words = 131,072 (512 KiB of
+    visited bits per query) and qc = 512, so 513 queries go as chunks of 512 and 1: the second uploads `queries + q0 * D` and copies
+    back to `out_rows + q0 * k`, `out_dists + q0 * k` and `out_counts + q0`.  Every list is pads and every level 0 (m = 2): the entry is row 0,
+    each query scores it alone and answers it with its own distance — integer coordinates, so every L2 distance is exact in f32."""
+    n, nq, k = 1 << 22, 513, 3
+    assert (256 << 20) // (4 * ((n + 31) // 32)) == nq - 1
+    rng = np.random.default_rng(22)
+    data = rng.integers(-8, 9, (n, 2)).astype(f32)
+    queries = np.stack([np.arange(nq) % 32 - 16, np.arange(nq) // 32 - 8], axis=1).astype(f32)
+    assert np.unique(queries, axis=0).shape[0] == nq
+    idx = flat(L, data)
+    g = H.Graph(2, np.zeros(n, np.uint32), np.full((n, 4), H.PAD, np.uint32), np.zeros((0, 2), np.uint32), 0)
+    load(idx, g, L2)
+    idx.profile_enable(True)
+    idx.hnsw_stage_times(reset=True)
+    rows, dists, counts = idx.search_hnsw_batch_arrays(queries, k, L2)
+    t = idx.hnsw_stage_times(reset=True)
+    idx.profile_enable(False)
+    exp = ((queries - data[0]) ** 2).sum(axis=1, dtype=f32)
+    assert counts.tolist() == [1] * nq, np.nonzero(counts != 1)[0][:5]
+    assert (rows[:, 0] == 0).all() and (rows[:, 1:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+    assert np.array_equal(dists[:, 0].view(np.uint32), exp.view(np.uint32)), np.nonzero(dists[:, 0] != exp)[0][:5]
+    assert (dists[:, 1:] == np.inf).all()
+    assert (t["searches"], t["scored"]) == (1, nq), t
 
 
 # -------------------------------------------------------------------------------- 7. the widest row ----
