@@ -182,6 +182,41 @@ int lynse_hip_flat_copy_rows_device(const lynse_hip_flat *h, uint64_t first, uin
 /* ensure_binary (flat_mmap.rs:388-401) contents: packed words of rows [first, first+n). */
 int lynse_hip_flat_read_packed(lynse_hip_flat *h, uint64_t first, uint64_t n, uint64_t *out_words);
 
+/* ROW MUTATION (Collection::upsert_items / update_items, src/engine.rs:5880-6103; compact, :6494-6596; read_vectors_by_ids_only,
+ * :6353-6401): rows of a float shard rewritten in place, dropped in place, and read by index.  The rules:
+ *  1. lynse_hip_flat_update_rows_f32: data is n x dim dense f32, rows are shard rows, each < len and pairwise distinct — both checked on
+ *     the host before anything is written (LYNSE_ERR_INVALID_ARGUMENT, the shard unchanged).  An f32 shard gets the row at its pitch
+ *     with zero pad columns; an F16 shard gets the f16 bits lynse_hip_flat_append_f32 would store (one conversion, RNE).  Host data
+ *     goes through a staging buffer of at most 64 MiB per step.  Distinct rows: no two items write one address, no atomics.
+ *  2. lynse_hip_flat_compact_rows: keep_words is a BitSet in the convention of lynse_hip_flat_search_filtered_bitset_f32, a set bit =
+ *     the row stays; n_words < ceil(len / 64) is LYNSE_ERR_INVALID_ARGUMENT, bits at or beyond len are ignored.  New row j is the j-th
+ *     kept old row (stable; the reference's id_map, :6509-6514).  In place: the call allocates the keep words, 4 bytes per 64 rows
+ *     and a scratch of at most one window of rows, never a second shard; the capacity is kept.  *out_len (may be NULL) = the new len.
+ *     window_rows must be a multiple of 64; 0 = the default, 64 MiB over the row's bytes rounded down to a multiple of 64, at least 64.
+ *     When every row stays the call changes nothing at all (rule 4 does not apply).
+ *  3. The plan (lynse_hip_compact_plan, host only, no device; the compaction runs this very function): live = the kept rows below n;
+ *     word_base[w] = the kept rows below 64 w (the destination of the first kept row of word w); window j covers source rows
+ *     [j W, min((j + 1) W, n)) and is {src = j W, dst = word_base[j W / 64], live, path}, four u64 each: path 0 = untouched (dst == src
+ *     and every row kept: the prefix before the first cleared bit), 1 = direct iff dst + live <= src (destinations and sources of the
+ *     window are disjoint, rows are written straight to their place), 2 = staged (the live rows go densely to the scratch, then one
+ *     device copy puts them at dst; stream order makes it safe: it writes only rows below (j + 1) W, all read by then).
+ *     row_bytes only sizes the default window.  out_word_base (ceil(n / 64)) and out_windows (4 x ceil(n / W)) may be NULL.
+ *  4. After an update of n > 0 rows or a compaction that dropped a row, everything derived from the rows is what a fresh handle
+ *     holding the final rows would build: norms, statistics and flags are recomputed over ALL rows, the f16 shadow, the packed words
+ *     and their copy and the four int8 code sets are rebuilt (the code sets from a NEW fit), overflow strikes start at 0 — all lazily,
+ *     by the next search that needs them.  PQ, RaBitQ, HNSW and DiskANN indexes of the handle are dropped.
+ *  5. lynse_hip_flat_gather_rows: out[i] = row rows[i] as f32 (an F16 shard decoded exactly), any order, repeats allowed; a row >= len is
+ *     LYNSE_ERR_INVALID_ARGUMENT.  Lock discipline of lynse_hip_flat_read_rows.
+ *  Update and compact are writers: refused while tickets are outstanding ("in flight").  LYNSE_ERR_UNSUPPORTED: a packed-only handle
+ *  (both), a row-mapped handle (compaction renumbers rows).  There are no sharded, _device or ticket forms. */
+int lynse_hip_flat_update_rows_f32(lynse_hip_flat *h, const uint64_t *rows, const float *data, uint64_t n);
+int lynse_hip_flat_compact_rows(lynse_hip_flat *h, const uint64_t *keep_words, uint64_t n_words, uint32_t window_rows,
+                                uint64_t *out_len);
+int lynse_hip_flat_gather_rows(const lynse_hip_flat *h, const uint64_t *rows, uint64_t n, float *out);
+int lynse_hip_compact_plan(const uint64_t *keep_words, uint64_t n_words, uint64_t n, uint32_t window_rows, uint64_t row_bytes,
+                           uint64_t *out_live, uint32_t *out_window_rows, uint64_t *out_n_windows, uint32_t *out_word_base,
+                           uint64_t *out_windows);
+
 /* FlatMmap::search (flat_mmap.rs:824-923) for a batch of queries (Collection::batch_search,
  * engine.rs:5352-5498).  queries: nq*dim f32.  Binary metrics threshold the f32 query at 0.5
  * (pack_binary_query, flat_mmap.rs:1292-1296).  out_rows/out_dists: nq*k; out_counts: nq. */

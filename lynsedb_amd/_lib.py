@@ -63,6 +63,10 @@ SIGNATURES = {
     "lynse_hip_flat_read_rows": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "lynse_hip_flat_copy_rows_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "lynse_hip_flat_read_packed": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "lynse_hip_flat_update_rows_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "lynse_hip_flat_compact_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _u64p]),
+    "lynse_hip_flat_gather_rows": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "lynse_hip_compact_plan": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _u64p, _u32p, _u64p, _vp, _vp]),
     "lynse_hip_flat_search_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "lynse_hip_flat_search_sq8_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "lynse_hip_flat_sq8_params": (C.c_int, [_vp, _vp, _vp]),

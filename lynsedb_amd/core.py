@@ -448,6 +448,55 @@ class FlatIndex:
         check(lib.lynse_hip_flat_read_packed(self._h, first, n, _ptr(out)))
         return out
 
+    # -- row mutation (the ROW MUTATION block of include/lynse_hip.h) -----------------------------------------------------------
+    def update_rows(self, rows, data) -> None:
+        """Rewrite the listed shard rows in place (distinct, each < len); every derived copy and auxiliary index is dropped and
+        built again from the final rows by the searches that need it."""
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.uint64)
+        a = _f32(data, 2, "data")
+        if a.shape[1] != self._dim:
+            raise ValueError(f"data dimension mismatch: expected {self._dim}, got {a.shape[1]}")
+        if a.shape[0] != r.size:
+            raise ValueError("rows length must match the number of vectors")
+        check(lib.lynse_hip_flat_update_rows_f32(self._h, _ptr(r), _ptr(a), r.size))
+
+    @staticmethod
+    def _keep_words(keep) -> np.ndarray:
+        if isinstance(keep, BitSet):
+            return keep.words
+        b = np.asarray(keep)
+        if b.dtype != np.bool_ or b.ndim != 1:
+            raise ValueError("keep must be a BitSet or a one-dimensional boolean array")
+        return np.packbits(np.concatenate([b, np.zeros(-b.size % 64, np.bool_)]), bitorder="little").view(np.uint64)
+
+    def compact(self, keep, window_rows: int = 0) -> int:
+        """Drop the rows whose `keep` bit is clear, in place and in order (new row j = the j-th kept row) -> the new length.
+        `keep` is a BitSet or a boolean array over the rows."""
+        w = np.ascontiguousarray(self._keep_words(keep), dtype=np.uint64)
+        out = C.c_uint64(0)
+        check(lib.lynse_hip_flat_compact_rows(self._h, _ptr(w), w.size, int(window_rows), C.byref(out)))
+        return int(out.value)
+
+    def gather_rows(self, rows) -> np.ndarray:
+        """The listed rows as f32, in the order given (repeats allowed)."""
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.uint64)
+        out = np.empty((r.size, self._dim), np.float32)
+        check(lib.lynse_hip_flat_gather_rows(self._h, _ptr(r), r.size, _ptr(out)))
+        return out
+
+    @staticmethod
+    def compact_plan(keep, n: int, window_rows: int = 0, row_bytes: int = 0) -> dict:
+        """What `compact` will do to a shard of n rows (host only): the live count, the window size, per 64-row word the destination of
+        its first kept row, and per window (src, dst, live, path) with path 0 untouched / 1 direct / 2 staged."""
+        w = np.ascontiguousarray(FlatIndex._keep_words(keep), dtype=np.uint64)
+        live, wrows, nwin = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        args = (_ptr(w), w.size, int(n), int(window_rows), int(row_bytes), C.byref(live), C.byref(wrows), C.byref(nwin))
+        check(lib.lynse_hip_compact_plan(*args, None, None))
+        base = np.zeros((int(n) + 63) // 64, np.uint32)
+        win = np.zeros((nwin.value, 4), np.uint64)
+        check(lib.lynse_hip_compact_plan(*args, _ptr(base), _ptr(win)))
+        return {"live": int(live.value), "window_rows": int(wrows.value), "word_base": base, "windows": win}
+
     # -- search -------------------------------------------------------------------------------
     def _search_f32(self, fn, queries, k: int, metric, *extra):
         """One `lynse_hip_flat_search_*_f32` entry over f32 queries; `extra` goes between the metric and the outputs."""
@@ -1725,6 +1774,8 @@ class Collection:
         self._pending_rows = 0
         self._tombstone: set = set()    # user ids (engine.rs:3182-3194)
         self._pq = False                # FLAT-*-PQ built over the rows flushed at build time (FlatIndex.build_pq)
+        self._pq_clusters = 256         # the n_clusters it was built with (a rebuild after a mutation uses it again)
+        self._index_dirty = False       # rows changed under an index while the shard was empty: rebuilt by the first search over rows
         self._rabitq = False            # FLAT-*-RABITQ, likewise (FlatIndex.build_rabitq); at most one of the two exists
         self._hnsw = False              # HNSW-*: a graph over the flushed rows (FlatIndex.build_hnsw); replaces and is replaced by the two above
         self._hnsw_rows = 0             # rows the graph was built over
@@ -1762,13 +1813,7 @@ class Collection:
                 raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match field count ({len(fields)})")
             if not all(isinstance(f, dict) for f in fields):
                 raise TypeError("fields must be a list of dicts, one per id")
-            for i, f in zip(ids, fields):
-                doc = index_text_document(f)
-                if doc:
-                    self._docs[int(i)] = doc
-                    self._text_dirty = True
-                elif self._docs.pop(int(i), None) is not None:   # a document with no text field left is not indexed: a re-added id loses its old one
-                    self._text_dirty = True
+            self._index_docs(ids, fields)
         if a.shape[0] == 0:
             return
         self._pending_vecs.append(np.array(a, dtype=np.float32, copy=True))
@@ -1776,6 +1821,16 @@ class Collection:
         self._pending_rows += a.shape[0]
         if self._pending_rows >= PENDING_INGEST_FLUSH_ROWS or self._pending_rows * self._dim * 4 >= PENDING_INGEST_FLUSH_BYTES:
             self._flush_pending()
+
+    def _index_docs(self, ids, fields) -> None:
+        """The text documents of a batch (insert_documents / upsert_documents): one document per id replaces the id's earlier one."""
+        for i, f in zip(ids, fields):
+            doc = index_text_document(f)
+            if doc:
+                self._docs[int(i)] = doc
+                self._text_dirty = True
+            elif self._docs.pop(int(i), None) is not None:   # a document with no text field left is not indexed: a re-added id loses its old one
+                self._text_dirty = True
 
     def pending_len(self) -> int:
         return self._pending_rows
@@ -1808,6 +1863,146 @@ class Collection:
     def list_deleted_ids(self) -> list:
         return sorted(self._tombstone)
 
+    # -- mutation (engine.rs:5880-6103, :6353-6401, :6494-6596) ---------------------------------
+    def _rows_of_ids(self, ids: np.ndarray) -> np.ndarray:
+        """The flushed row of each id, -1 for an id without one.  This mirror's add_items accepts an id twice (the reference does
+        not, engine.rs:3505-3512): an id of the call that is stored in more than one row is an error here."""
+        id_map = self._id_map()
+        order = np.argsort(id_map, kind="stable")
+        sorted_ids = id_map[order]
+        lo, hi = np.searchsorted(sorted_ids, ids, "left"), np.searchsorted(sorted_ids, ids, "right")
+        twice = np.nonzero(hi - lo > 1)[0]
+        if twice.size:
+            raise RuntimeError(f"Invalid argument: id {int(ids[twice[0]])} is stored in more than one row")
+        rows = np.full(ids.size, -1, np.int64)
+        hit = hi > lo
+        rows[hit] = order[lo[hit]]
+        return rows
+
+    @staticmethod
+    def _unique_ids(ids) -> np.ndarray:
+        ids = np.asarray([int(i) for i in ids], dtype=np.int64)   # validate_unique_ids
+        seen = set()
+        for i in ids.tolist():
+            if i in seen:
+                raise RuntimeError(f"Invalid argument: duplicate id {i} within the same insert batch")
+            seen.add(i)
+        return ids
+
+    def _rebuild_index(self) -> None:
+        """Whatever index the collection holds, built again over the flushed rows with the mode and options it was built with: a search
+        after a mutation equals a search on a collection that was given the final rows.  Over an empty shard nothing can be built:
+        the first search that finds rows does it."""
+        self._index_dirty = len(self._flat) == 0 and (self._ivf is not None or self._pq or self._rabitq or self._hnsw or self._diskann)
+        if len(self._flat) == 0:
+            return
+        if self._ivf is not None:
+            self._build_ivf()
+        elif self._hnsw:
+            self._build_hnsw()
+        elif self._diskann:
+            self._build_diskann()
+        elif self._pq:
+            self._flat.build_pq(parse_n_subspaces(self._index_mode, self._dim), self._pq_clusters)
+        elif self._rabitq:
+            self._flat.build_rabitq()
+            self._save_rabitq()
+
+    def upsert_items(self, vectors, ids: Sequence[int], fields=None) -> None:
+        """Collection::upsert_items (engine.rs:5949-6066): existing ids are rewritten in place on the device and leave the tombstone
+        set, new ids are appended and flushed.  With `fields`, an id's text document is replaced by the rule of add_items.  When an
+        existing row changed, the index of the collection is built again (the reference rebuilds the quantised modes only and leaves
+        IVF and HNSW on the old vectors: DESIGN.md §22)."""
+        self._flush_pending()
+        a = _f32(vectors, 2, "vectors")
+        if a.shape[1] != self._dim:
+            raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {a.shape[1]}")
+        if len(ids) != a.shape[0]:
+            raise RuntimeError("Invalid argument: ids length must match n_vectors")
+        if fields is not None:
+            fields = list(fields)
+            if len(fields) != len(ids):
+                raise RuntimeError(f"Invalid argument: fields length ({len(fields)}) must match n_vectors ({len(ids)})")
+            if not all(isinstance(f, dict) for f in fields):
+                raise TypeError("fields must be a list of dicts, one per id")
+        ids = self._unique_ids(ids)
+        rows = self._rows_of_ids(ids)
+        old, new = np.nonzero(rows >= 0)[0], np.nonzero(rows < 0)[0]
+        if old.size:
+            self._flat.update_rows(rows[old].astype(np.uint64), a[old])
+            self._tombstone.difference_update(ids[old].tolist())
+            if fields is not None:
+                self._index_docs(ids[old].tolist(), [fields[j] for j in old.tolist()])
+        if new.size:
+            self.add_items(a[new], ids[new], None if fields is None else [fields[j] for j in new.tolist()])
+            self._flush_pending()
+        if old.size:
+            self._rebuild_index()
+
+    def update_items(self, vectors, ids: Sequence[int], fields=None) -> None:
+        """Collection::update_items (engine.rs:6072-6103): every id must exist; then upsert_items."""
+        self._flush_pending()
+        a = _f32(vectors, 2, "vectors")
+        if a.shape[1] != self._dim:
+            raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {a.shape[1]}")
+        if len(ids) != a.shape[0]:
+            raise RuntimeError("Invalid argument: ids length must match n_vectors")
+        uids = self._unique_ids(ids)
+        missing = np.nonzero(self._rows_of_ids(uids) < 0)[0]
+        if missing.size:
+            raise RuntimeError(f"Invalid argument: id {int(uids[missing[0]])} does not exist; use upsert_items to insert missing IDs")
+        self.upsert_items(a, uids, fields)
+
+    def compact(self) -> int:
+        """Collection::compact (engine.rs:6494-6596): every flushed row of a tombstoned id is dropped on the device, in place; the id
+        map follows, the ids leave the sparse store and the text documents, the tombstone set is cleared (an id without a row is
+        simply forgotten) and the index is built again.  Returns the rows removed; 0, and no change, without tombstones."""
+        self._flush_pending()
+        if not self._tombstone:
+            return 0
+        dead_ids = np.fromiter(self._tombstone, dtype=np.int64, count=len(self._tombstone))
+        id_map = self._id_map()
+        keep = ~np.isin(id_map, dead_ids)
+        removed = int(id_map.size - np.count_nonzero(keep))
+        if removed:
+            new_len = self._flat.compact(keep)
+            self._id_arrays = [id_map[keep]]
+            assert new_len == self._id_arrays[0].size
+        for i in self._tombstone:
+            if self._sparse.pop(i, None) is not None:
+                self._sparse_dirty = True
+            if self._docs.pop(i, None) is not None:
+                self._text_dirty = True
+        if self._sparse_dirty and self._path is not None:
+            from .storage import save_sparse_vectors
+
+            save_sparse_vectors(self._path / SPARSE_VECTORS_FILE, self._sparse)
+        self._tombstone.clear()
+        self._rebuild_index()
+        return removed
+
+    def read_vectors_by_ids(self, ids: Sequence[int]) -> np.ndarray:
+        """read_vectors_by_ids_only (engine.rs:6353-6401): the vector of each id, flushed rows gathered on the device, pending rows from
+        the buffer."""
+        ids = np.asarray([int(i) for i in ids], dtype=np.int64)
+        rows = self._rows_of_ids(ids)
+        out = np.empty((ids.size, self._dim), np.float32)
+        flushed = np.nonzero(rows >= 0)[0]
+        if flushed.size:
+            out[flushed] = self._flat.gather_rows(rows[flushed].astype(np.uint64))
+        rest = np.nonzero(rows < 0)[0]
+        if rest.size:
+            p_ids = np.concatenate(self._pending_ids) if self._pending_ids else np.zeros(0, np.int64)
+            p_vecs = np.concatenate(self._pending_vecs) if self._pending_vecs else np.zeros((0, self._dim), np.float32)
+            for j in rest.tolist():
+                at = np.nonzero(p_ids == ids[j])[0]
+                if at.size == 0:
+                    raise RuntimeError(f"Invalid argument: vector id {int(ids[j])} does not exist")
+                if at.size > 1:
+                    raise RuntimeError(f"Invalid argument: id {int(ids[j])} is stored in more than one row")
+                out[j] = p_vecs[at[0]]
+        return out
+
     # -- index --------------------------------------------------------------------------------
     def build_index(self, index_type: str, params: Optional[dict] = None) -> None:
         """Collection::build_index_with_build_options (engine.rs:4515-4655): flushes the pending rows (:4521); FLAT-*
@@ -1834,7 +2029,8 @@ class Collection:
             self._ivf = None
             self._drop_aux()   # building any mode drops an earlier PQ / RaBitQ index (engine.rs:4476, :4552, :4559-4600)
             if pq and len(self._flat) > 0:   # over 0 rows nothing is built and searches stay exact
-                self._flat.build_pq(parse_n_subspaces(mode, self._dim), int(params.get("n_clusters", 256)))
+                self._pq_clusters = int(params.get("n_clusters", 256))
+                self._flat.build_pq(parse_n_subspaces(mode, self._dim), self._pq_clusters)
                 self._pq = True
             elif rabitq and len(self._flat) > 0:
                 self._flat.build_rabitq()
@@ -1878,6 +2074,7 @@ class Collection:
         else:
             raise NotImplementedError(f"index type {index_type} is outside the FLAT/IVF hot path")
         self._index_mode, self._metric = mode, metric
+        self._index_dirty = False
 
     def _drop_aux(self) -> None:
         """At most one auxiliary quantised index exists: whatever is built next, the earlier one and its file go."""
@@ -1989,6 +2186,8 @@ class Collection:
         nq = q.shape[0]
         if len(self._flat) == 0 or search_k == 0:
             return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
+        if self._index_dirty:
+            self._rebuild_index()
         if self._ivf is not None:
             if self._ivf_rows != len(self._flat):
                 # rows were committed after the build: Collection::flush hands them to idx.insert (engine.rs:3642-3645, :3858) —

@@ -36,6 +36,7 @@
 #include "sparse.h"
 #include "text.h"
 #include "spann.h"
+#include "mutate.h"
 
 using namespace lynse;
 
@@ -3582,3 +3583,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "additive_host.inc"
 #include "sparse_host.inc"
 #include "text_host.inc"
+#include "mutate_host.inc"
