@@ -55,12 +55,27 @@ def assert_searches(L, orc, idx, model, tag, f16=False, queries=None, k=10):
     return fresh
 
 
+def warm_up(idx, stored):
+    """The lazy copies exist before the mutation: 16 queries of l2 and cosine run the staged pipeline (row statistics and norms, the f16
+    shadow — an F16 shard's is an alias of its rows), a Hamming search packs the sign words.  Asserted from the profile not to be the fused
+    single-launch search (last_plan bit 5), which reads the f32 rows alone."""
+    q = stored[:16].copy()
+    idx.profile_enable(True)
+    for name in ("l2", "cosine"):
+        idx.profile_get(reset=True)
+        idx.search_batch_arrays(q, 5, name)
+        p = idx.profile_get(reset=True)
+        assert not int(p["last_plan"]) & 32 and p["scan_launches"] >= 1, (name, p)
+    idx.search_batch_arrays(q, 5, "hamming")
+    idx.profile_enable(False)
+
+
 def compaction_case(L, orc, data, keep, window_rows, tag, f16=False, n_words=None, garbage=False):
     n, dim = data.shape
     idx = L.FlatIndex(None, dim, dtype="f16" if f16 else "f32")
     idx.write(data)
     stored = idx.read_rows(0, n)   # (an F16 shard: the decoded f16 values)
-    idx.search_batch_arrays(stored[:3].copy(), 5, "l2")   # the lazy copies exist before the compaction
+    warm_up(idx, stored)
     row_bytes = (-(-dim // 8) * 8 * 2) if f16 else (-(-dim // 4) * 4 * 4)
     if n_words is None:
         new_len = idx.compact(keep, window_rows)
@@ -103,7 +118,7 @@ def test_compact_window_edges(L, oracle, small, n, case):
 def test_compact_everything_then_write(L, oracle, small):
     idx = L.FlatIndex(None, 5)
     idx.write(small)
-    idx.search_batch_arrays(small[:2].copy(), 3, "ip")
+    warm_up(idx, small)
     assert idx.compact(np.zeros(1001, bool), 64) == 0 and len(idx) == 0
     for name, _ in METRICS:
         rows, dists, counts = idx.search_batch_arrays(small[:4].copy(), 3, name)
@@ -166,7 +181,7 @@ def test_update_rows(L, oracle, dim):
     data = rng.standard_normal((n, dim)).astype(f32)
     idx = L.FlatIndex(None, dim)
     idx.write(data)
-    idx.search_batch_arrays(data[:3].copy(), 5, "cosine")
+    warm_up(idx, data)
     rows = np.concatenate([[0, 63, 64, n - 1], rng.choice(np.setdiff1d(np.arange(n), [0, 63, 64, n - 1]), 100, replace=False)])
     rng.shuffle(rows)
     new = rng.standard_normal((rows.size, dim)).astype(f32)
