@@ -204,7 +204,7 @@ int lynse_hip_flat_read_packed(lynse_hip_flat *h, uint64_t first, uint64_t n, ui
  *  4. After an update of n > 0 rows or a compaction that dropped a row, everything derived from the rows is what a fresh handle
  *     holding the final rows would build: norms, statistics and flags are recomputed over ALL rows, the f16 shadow, the packed words
  *     and their copy and the four int8 code sets are rebuilt (the code sets from a NEW fit), overflow strikes start at 0 — all lazily,
- *     by the next search that needs them.  PQ, RaBitQ, HNSW and DiskANN indexes of the handle are dropped.
+ *     by the next search that needs them.  PQ, RaBitQ, PolarVec, HNSW and DiskANN indexes of the handle are dropped.
  *  5. lynse_hip_flat_gather_rows: out[i] = row rows[i] as f32 (an F16 shard decoded exactly), any order, repeats allowed; a row >= len is
  *     LYNSE_ERR_INVALID_ARGUMENT.  Lock discipline of lynse_hip_flat_read_rows.
  *  Update and compact are writers: refused while tickets are outstanding ("in flight").  LYNSE_ERR_UNSUPPORTED: a packed-only handle
@@ -339,6 +339,45 @@ int lynse_hip_flat_search_rabitq_f32(lynse_hip_flat *h, const float *queries, ui
                                      uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
 int lynse_hip_flat_rabitq_stage_times(lynse_hip_flat *h, double *out3, int reset);
 int lynse_hip_rabitq_sign_words(uint64_t seed, uint64_t count, uint64_t *out);
+/* FLAT-{IP,L2,COS,COSINE}-POLARVEC<b> (PolarVecIndex, src/storage/polarvec_mmap.rs; Collection, engine.rs:4593-4602, :5514-5515):
+ * b-bit codes (b = 1..8) of the randomised Hadamard rotation on a per-dimension grid, scanned whole through per-dimension tables of
+ * the query, and an exact rescore.  f32 handles and ip / l2 / cosine only; no training.  Every sum is a chain of separate f32
+ * operations in the order given, no FMA contraction anywhere.  The rules:
+ *  1. padded_dim P = next_power_of_two(dim), levels = 1 << bits, bytes_per_vec = ceil(P * bits / 8); the sign words and the rotation
+ *     (zero-pad, signs, unnormalised FWHT) are RaBitQ's, rules 1 and 2 above.
+ *  2. Fit (:137-208): sample rows si * stride for si < min(n, 50000), stride = 1 for n <= 50000, else n / 50000 (integer).  Per
+ *     rotated dimension min and max over the samples by strict < / > from +inf / -inf: a NaN is never taken, and of values that
+ *     compare equal (+0, -0) the earliest sample row's stays.  range = max - min; if range > 1e-8f: dim_min = min - 0.05f * range,
+ *     dim_scale = (range * (1.0f + 2.0f * 0.05f)) / (float)(levels - 1); else dim_min = min, dim_scale = 1.0f.
+ *  3. Encode (:703-777): per d ascending over all P rotated values, code = (u8)min(max(roundf((val - dim_min) / dim_scale), 0),
+ *     levels - 1) (half away from zero; a NaN codes as 0), v_hat = dim_min + (float)code * dim_scale, residual_sq = sum (val - v_hat)^2,
+ *     v_hat_sq = sum v_hat^2, inv_v_hat_norm = 1.0f / fmaxf(sqrtf(v_hat_sq), 1e-12f).  residual_sq is kept only by an index built for
+ *     L2, inv_v_hat_norms only by one built for cosine.  The code stream is LSB-first: dimension d at bits [d * bits, (d + 1) * bits).
+ *  4. Query (:310-332, :926-972): for cosine the query is first divided by fmaxf(sqrtf(sum x^2), 1e-12f); rotate; lut[d][c] from
+ *     v = dim_min + (float)c * dim_scale: IP q * v, L2 (q - v)^2, cosine -(q * v).
+ *  5. Row score (:1010-1135): bits 4: byte b contributes lut[2b][low nibble] + lut[2b+1][high nibble] (the second only if 2b + 1 < P)
+ *     to s[b % 4] over the first (bytes / 4) * 4 bytes, leftover bytes to s0, score ((s0 + s1) + s2) + s3; bits 8: the same over
+ *     lut[b][code_b]; bits 3: groups of 8 dimensions, dimension j of a group to s[j % 4], P / 8 groups (none below P = 8: the sum
+ *     is 0.0f); bits 1, 2, 5, 6, 7: one chain over d.  Then + residual_sq[row] when searching L2 and the array exists, *
+ *     inv_v_hat_norms[row] when searching cosine and it exists: a search with another metric than the build's finds it absent.
+ *  6. Search: k' = min(k, n_plv), N = min(k' * oversample, n_plv) (the Collection passes 20, DEFAULT_OVERSAMPLE); pool, rescore,
+ *     cuts, ordering and output as RaBitQ's rule 5; coverage, replacement and drop as its rule 6.
+ *  Refused: what RaBitQ refuses, and bits outside 1..8 ("bits must be in [1, 8]").  The search holds the handle's lock exclusively.
+ * lynse_hip_flat_load_polarvec takes what a version-5 polarvec_index.bin holds: dim (must be the handle's: "Invalid PolarVec index
+ * dimensions"), bits, the sign words, dim_mins[P], dim_scales[P], codes[n][bytes_per_vec] and the two optional arrays [n] (NULL =
+ * absent); n <= the handle's rows.  lynse_hip_flat_polarvec_params returns dims = {dim, padded_dim, bits, bytes_per_vec, flags} (flags:
+ * 1 = residual_sq, 2 = inv_v_hat_norms) and n_plv (all 0 without an index) and, for the pointers that are not NULL, the arrays in the
+ * file's layout (an absent optional array is left untouched).  lynse_hip_flat_polarvec_stage_times: as lynse_hip_flat_rabitq_stage_times. */
+int lynse_hip_flat_build_polarvec(lynse_hip_flat *h, uint32_t bits, int metric);
+int lynse_hip_flat_load_polarvec(lynse_hip_flat *h, uint32_t dim, uint32_t bits, const uint64_t *sign_words, uint32_t n_sign_words,
+                                 const float *dim_mins, const float *dim_scales, const uint8_t *codes, const float *residual_sq,
+                                 const float *inv_v_hat_norms, uint64_t n);
+int lynse_hip_flat_polarvec_params(lynse_hip_flat *h, uint32_t *dims, uint64_t *n_plv, uint64_t *sign_words, float *dim_mins,
+                                   float *dim_scales, uint8_t *codes, float *residual_sq, float *inv_v_hat_norms);
+int lynse_hip_flat_drop_polarvec(lynse_hip_flat *h);
+int lynse_hip_flat_search_polarvec_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric,
+                                       uint32_t oversample, uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
+int lynse_hip_flat_polarvec_stage_times(lynse_hip_flat *h, double *out3, int reset);
 /* HNSW-{IP,L2,COS,COSINE} (HNSWIndex, src/index/hnsw.rs; Collection, engine.rs:4606-4655, :4743-4745): a layered neighbour graph over
  * the rows of a FLAT handle — the graph holds ids, the rows stay the handle's — a deterministic bulk build from exact neighbour lists,
  * and the reference's beam search.  f32 handles and ip / l2 / cosine only.  The reference's search is a function of the graph, the

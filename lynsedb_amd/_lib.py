@@ -86,6 +86,12 @@ SIGNATURES = {
     "lynse_hip_flat_search_rabitq_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp]),
     "lynse_hip_flat_rabitq_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
     "lynse_hip_rabitq_sign_words": (C.c_int, [C.c_uint64, C.c_uint64, _vp]),
+    "lynse_hip_flat_build_polarvec": (C.c_int, [_vp, C.c_uint32, C.c_int]),
+    "lynse_hip_flat_load_polarvec": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint64]),
+    "lynse_hip_flat_polarvec_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lynse_hip_flat_drop_polarvec": (C.c_int, [_vp]),
+    "lynse_hip_flat_search_polarvec_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp]),
+    "lynse_hip_flat_polarvec_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
     "lynse_hip_flat_build_hnsw": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint64]),
     "lynse_hip_flat_load_hnsw": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32]),
     "lynse_hip_flat_hnsw_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -140,6 +140,29 @@ def flat_rabitq_mode(mode: str) -> bool:
     return True
 
 
+POLARVEC_OVERSAMPLE = 20   # polarvec_mmap.rs DEFAULT_OVERSAMPLE
+POLARVEC_DEFAULT_BITS = 4
+POLARVEC_INDEX_FILE = "polarvec_index.bin"
+
+
+def flat_polarvec_mode(mode: str) -> Optional[int]:
+    """The bit count of FLAT-{IP,L2,COS,COSINE}-POLARVEC<digits> (any letter case), None for a mode without such a token.  Digits
+    outside 1..8 mean 4 (parse_bits, polarvec_mmap.rs:1269-1282); binary and additive metrics are refused.  The reference reads the
+    bare token POLARVEC as 4 bits too; this build refuses it, as flat_rabitq_mode always has: ask for POLARVEC4."""
+    parts = str(mode).upper().split("-")
+    if not parts or parts[0] != "FLAT":
+        return None
+    if "POLARVEC" in parts[1:]:
+        raise NotImplementedError(f"{mode}: name the bit count (FLAT-*-POLARVEC4); the bare token is refused (DESIGN.md §23)")
+    tok = next((p for p in parts[1:] if p.startswith("POLARVEC") and p[8:].isdigit()), None)
+    if tok is None:
+        return None
+    if metric_from_index_mode(mode) not in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
+        raise NotImplementedError(f"{mode}: FLAT-*-POLARVEC is defined for ip / l2 / cosine")
+    bits = int(tok[8:])
+    return bits if 1 <= bits <= 8 else POLARVEC_DEFAULT_BITS
+
+
 SPANN_MODES = {"SPANN-IP": (_lib.METRIC_IP, False), "SPANN-L2": (_lib.METRIC_L2, False), "SPANN-COS": (_lib.METRIC_COSINE, False),
                "SPANN-COSINE": (_lib.METRIC_COSINE, False), "SPANN-IP-SQ8": (_lib.METRIC_IP, True), "SPANN-L2-SQ8": (_lib.METRIC_L2, True),
                "SPANN-COS-SQ8": (_lib.METRIC_COSINE, True), "SPANN-COSINE-SQ8": (_lib.METRIC_COSINE, True)}
@@ -606,6 +629,73 @@ class FlatIndex:
         """With profiling on: RaBitQ searches timed and the summed microseconds of the scan stage and of the rescore."""
         out = np.zeros(3, np.float64)
         check(lib.lynse_hip_flat_rabitq_stage_times(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+
+    # -- FLAT-*-POLARVEC<b> (PolarVecIndex, src/storage/polarvec_mmap.rs; include/lynse_hip.h states the contract) --------------
+    def build_polarvec(self, bits: int, metric) -> None:
+        """Fit the per-dimension grid on the rows held now and encode them into `bits`-bit codes (no training; rows appended later
+        stay outside the index).  The metric decides which correction array is kept: residual_sq for l2, inv_v_hat_norms for cosine."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        bits = int(bits)
+        if not 0 <= bits < 1 << 32:
+            raise ValueError("bits must be in [1, 8]")
+        check(lib.lynse_hip_flat_build_polarvec(self._h, bits, m))
+
+    def load_polarvec(self, bits: int, sign_words, dim_mins, dim_scales, codes, residual_sq=None, inv_v_hat_norms=None) -> None:
+        """Install an index as polarvec_index.bin holds it: u64 sign words, f32 dim_mins / dim_scales [padded_dim], codes u8
+        [n][bytes_per_vec] for the first n rows and the optional f32 [n] correction arrays."""
+        bits = int(bits)
+        if not 1 <= bits <= 8:
+            raise ValueError("bits must be in [1, 8]")
+        sw = np.ascontiguousarray(sign_words, dtype=np.uint64).reshape(-1)
+        mn = np.ascontiguousarray(dim_mins, dtype=np.float32).reshape(-1)
+        sc = np.ascontiguousarray(dim_scales, dtype=np.float32).reshape(-1)
+        cd = np.ascontiguousarray(codes, dtype=np.uint8)
+        padded = 1 << max(self._dim - 1, 0).bit_length()
+        if cd.ndim != 2 or cd.shape[1] != (padded * bits + 7) // 8 or mn.shape[0] != padded or sc.shape[0] != padded:
+            raise ValueError("codes must be [n][ceil(next_pow2(dim) * bits / 8)], dim_mins and dim_scales [next_pow2(dim)]")
+        opt = []
+        for a in (residual_sq, inv_v_hat_norms):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if a is not None and a.shape[0] != cd.shape[0]:
+                raise ValueError("a correction array holds one value per code row")
+            opt.append(a)
+        check(lib.lynse_hip_flat_load_polarvec(self._h, self._dim, bits, _ptr(sw), sw.shape[0], _ptr(mn), _ptr(sc), _ptr(cd),
+                                               None if opt[0] is None else _ptr(opt[0]), None if opt[1] is None else _ptr(opt[1]),
+                                               cd.shape[0]))
+
+    def drop_polarvec(self) -> None:
+        check(lib.lynse_hip_flat_drop_polarvec(self._h))
+
+    def polarvec_params(self, arrays: bool = True) -> dict:
+        """{"dim", "padded_dim", "bits", "bytes_per_vec", "flags", "n"} and, with `arrays`, "sign_words" u64, "dim_mins" / "dim_scales"
+        f32 [padded_dim], "codes" u8 [n][bytes_per_vec], "residual_sq" and "inv_v_hat_norms" f32 [n] or None (flags 1 and 2);
+        padded_dim == 0 without an index."""
+        dims = np.zeros(5, np.uint32)
+        n = C.c_uint64(0)
+        check(lib.lynse_hip_flat_polarvec_params(self._h, _ptr(dims), C.byref(n), None, None, None, None, None, None))
+        dim, padded, bits, bpv, flags = (int(x) for x in dims)
+        out = {"dim": dim, "padded_dim": padded, "bits": bits, "bytes_per_vec": bpv, "flags": flags, "n": int(n.value)}
+        if arrays and padded:
+            nv = int(n.value)
+            sw = np.empty((padded + 63) // 64, np.uint64)
+            mn, sc = np.empty(padded, np.float32), np.empty(padded, np.float32)
+            cd = np.empty((nv, bpv), np.uint8)
+            rs = np.empty(nv, np.float32) if flags & 1 else None
+            iv = np.empty(nv, np.float32) if flags & 2 else None
+            check(lib.lynse_hip_flat_polarvec_params(self._h, _ptr(dims), C.byref(n), _ptr(sw), _ptr(mn), _ptr(sc), _ptr(cd),
+                                                     None if rs is None else _ptr(rs), None if iv is None else _ptr(iv)))
+            out.update(sign_words=sw, dim_mins=mn, dim_scales=sc, codes=cd, residual_sq=rs, inv_v_hat_norms=iv)
+        return out
+
+    def search_polarvec_batch_arrays(self, queries, k: int, metric, oversample: int = POLARVEC_OVERSAMPLE):
+        """Table scan of the b-bit codes, the N = min(k' * oversample, n_plv) best by (score, row), exact rescore of those rows."""
+        return self._search_f32(lib.lynse_hip_flat_search_polarvec_f32, queries, k, metric, int(oversample))
+
+    def polarvec_stage_times(self, reset: bool = False) -> dict:
+        """With profiling on: PolarVec searches timed and the summed microseconds of the scan stage and of the rescore."""
+        out = np.zeros(3, np.float64)
+        check(lib.lynse_hip_flat_polarvec_stage_times(self._h, _ptr(out), 1 if reset else 0))
         return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
 
     # -- HNSW-* (HNSWIndex, src/index/hnsw.rs; include/lynse_hip.h states the contract) ---------------------------------------
@@ -1760,7 +1850,7 @@ class Collection:
     def __init__(self, name: str, dim: int, device: Optional[int] = None, path=None):
         self._name, self._dim = name, int(dim)
         self._device = device
-        self._path = None if path is None else Path(path)   # where the auxiliary index file (rabitq_index.bin) persists; None = nowhere
+        self._path = None if path is None else Path(path)   # where the auxiliary index file (rabitq_index.bin, polarvec_index.bin) persists; None = nowhere
         self._flat = FlatIndex(None, dim, device)
         self._id_arrays: list = []     # row -> user id (engine.rs:3071-3073)
         self._index_mode = "FLAT-IP"   # resolve_metric default IP (engine.rs:5529-5534)
@@ -1777,6 +1867,7 @@ class Collection:
         self._pq_clusters = 256         # the n_clusters it was built with (a rebuild after a mutation uses it again)
         self._index_dirty = False       # rows changed under an index while the shard was empty: rebuilt by the first search over rows
         self._rabitq = False            # FLAT-*-RABITQ, likewise (FlatIndex.build_rabitq); at most one of the two exists
+        self._polarvec = 0              # FLAT-*-POLARVEC<b>, likewise: the bit count (FlatIndex.build_polarvec), 0 = none
         self._hnsw = False              # HNSW-*: a graph over the flushed rows (FlatIndex.build_hnsw); replaces and is replaced by the two above
         self._hnsw_rows = 0             # rows the graph was built over
         self._hnsw_opts: dict = {}
@@ -1893,7 +1984,7 @@ class Collection:
         """Whatever index the collection holds, built again over the flushed rows with the mode and options it was built with: a search
         after a mutation equals a search on a collection that was given the final rows.  Over an empty shard nothing can be built:
         the first search that finds rows does it."""
-        self._index_dirty = len(self._flat) == 0 and (self._ivf is not None or self._pq or self._rabitq or self._hnsw or self._diskann)
+        self._index_dirty = len(self._flat) == 0 and (self._ivf is not None or self._pq or self._rabitq or self._polarvec or self._hnsw or self._diskann)
         if len(self._flat) == 0:
             return
         if self._ivf is not None:
@@ -1907,6 +1998,9 @@ class Collection:
         elif self._rabitq:
             self._flat.build_rabitq()
             self._save_rabitq()
+        elif self._polarvec:   # (the reference rebuilds it after a mutation too: engine.rs:5921-5934)
+            self._flat.build_polarvec(self._polarvec, self._metric)
+            self._save_polarvec()
 
     def upsert_items(self, vectors, ids: Sequence[int], fields=None) -> None:
         """Collection::upsert_items (engine.rs:5949-6066): existing ids are rewritten in place on the device and leave the tombstone
@@ -2024,8 +2118,9 @@ class Collection:
             self._drop_aux()
             metric = additive
         elif mode.startswith("FLAT"):
-            rabitq = flat_rabitq_mode(mode)   # (refuses PolarVec)
+            rabitq = flat_rabitq_mode(mode)   # (refuses the bare POLARVEC token)
             pq = flat_pq_mode(mode)
+            polarvec = flat_polarvec_mode(mode)
             self._ivf = None
             self._drop_aux()   # building any mode drops an earlier PQ / RaBitQ index (engine.rs:4476, :4552, :4559-4600)
             if pq and len(self._flat) > 0:   # over 0 rows nothing is built and searches stay exact
@@ -2036,6 +2131,10 @@ class Collection:
                 self._flat.build_rabitq()
                 self._rabitq = True
                 self._save_rabitq()
+            elif polarvec and len(self._flat) > 0:   # PQ, then RaBitQ, then PolarVec (engine.rs:4559-4600)
+                self._flat.build_polarvec(polarvec, metric)
+                self._polarvec = polarvec
+                self._save_polarvec()
         elif hnsw_mode_of(mode) is not None:   # HNSW-{IP,L2,COS,COSINE}; every other HNSW-* name falls through to the refusal below
             opts = hnsw_build_options(params)
             self._ivf = None
@@ -2080,11 +2179,14 @@ class Collection:
         """At most one auxiliary quantised index exists: whatever is built next, the earlier one and its file go."""
         self._flat.drop_pq()
         self._flat.drop_rabitq()
+        self._flat.drop_polarvec()
         self._flat.drop_hnsw()
         self._flat.drop_diskann()
         self._pq = self._rabitq = self._hnsw = self._diskann = False
+        self._polarvec = 0
         if self._path is not None:
             (self._path / RABITQ_INDEX_FILE).unlink(missing_ok=True)
+            (self._path / POLARVEC_INDEX_FILE).unlink(missing_ok=True)
 
     def _save_rabitq(self) -> None:
         if self._path is None:
@@ -2114,6 +2216,40 @@ class Collection:
         self._flat.load_rabitq(idx.sign_words, idx.codes, idx.norms)
         self._ivf = None
         self._rabitq = True
+        self._index_mode, self._metric = mode, metric_from_index_mode(mode)
+        return True
+
+    def _save_polarvec(self) -> None:
+        if self._path is None:
+            return
+        from .storage import PolarvecIndexFile, save_polarvec_index
+
+        p = self._flat.polarvec_params()
+        save_polarvec_index(self._path / POLARVEC_INDEX_FILE,
+                            PolarvecIndexFile(p["dim"], p["padded_dim"], p["bits"], p["sign_words"], p["dim_mins"], p["dim_scales"], p["codes"],
+                                              p["residual_sq"], p["inv_v_hat_norms"]))
+
+    def try_load_polarvec(self, index_type: str) -> bool:
+        """try_load_rabitq's rules for polarvec_index.bin: installed when the stored mode names PolarVec with the file's bit count, the
+        file is there, its dim is the collection's and it covers no more rows than are flushed.  False (and exact search) otherwise."""
+        from .storage import load_polarvec_index
+
+        mode = str(index_type).upper()
+        if self._path is None or flat_pq_mode(mode) or flat_rabitq_mode(mode):
+            return False
+        bits = flat_polarvec_mode(mode)
+        f = self._path / POLARVEC_INDEX_FILE
+        if not bits or not f.exists():
+            return False
+        idx = load_polarvec_index(f)
+        if idx.dim != self._dim or idx.bits != bits or idx.n_vectors == 0 or idx.n_vectors > len(self._flat):
+            return False
+        self._flat.drop_pq()
+        self._flat.drop_rabitq()
+        self._pq = self._rabitq = False
+        self._flat.load_polarvec(idx.bits, idx.sign_words, idx.dim_mins, idx.dim_scales, idx.codes, idx.residual_sq, idx.inv_v_hat_norms)
+        self._ivf = None
+        self._polarvec = bits
         self._index_mode, self._metric = mode, metric_from_index_mode(mode)
         return True
 
@@ -2217,6 +2353,8 @@ class Collection:
             return self._flat.search_pq_batch_arrays(q, search_k, self._metric, PQ_OVERSAMPLE)
         if self._rabitq:
             return self._flat.search_rabitq_batch_arrays(q, search_k, self._metric, RABITQ_OVERSAMPLE)
+        if self._polarvec:
+            return self._flat.search_polarvec_batch_arrays(q, search_k, self._metric, POLARVEC_OVERSAMPLE)
         if self._use_sq8() and self._metric in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
             return self._flat.search_sq8_batch_arrays(q, search_k, self._metric)
         return self._flat.search_batch_arrays(q, search_k, self._metric)
@@ -2250,6 +2388,7 @@ class Collection:
         sq8 = self._ivf is not None and self._ivf.is_sq8
         pq = self._ivf is None and self._pq and subset is None
         rabitq = self._ivf is None and self._rabitq and subset is None
+        polarvec = self._ivf is None and bool(self._polarvec) and subset is None
         hnsw = self._ivf is None and self._hnsw and subset is None
         diskann = self._ivf is None and self._diskann and subset is None
         target.profile_enable(True)
@@ -2260,11 +2399,13 @@ class Collection:
             self._flat.pq_stage_times(reset=True)
         if rabitq:
             self._flat.rabitq_stage_times(reset=True)
+        if polarvec:
+            self._flat.polarvec_stage_times(reset=True)
         if hnsw:
             self._flat.hnsw_stage_times(reset=True)
         if diskann:
             self._flat.diskann_stage_times(reset=True)
-        stage_us = hnsw_us = diskann_us = None
+        stage_us = plv_us = hnsw_us = diskann_us = None
         t0 = time.perf_counter()
         try:
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
@@ -2277,6 +2418,9 @@ class Collection:
             if rabitq:   # FLAT-*-RABITQ: both stages of the two-pass search
                 t = self._flat.rabitq_stage_times(reset=True)
                 rerank_us, stage_us = int(t["rescore_us"]), {"scan_us": float(t["scan_us"]), "rescore_us": float(t["rescore_us"])}
+            if polarvec:   # FLAT-*-POLARVEC<b>: likewise
+                t = self._flat.polarvec_stage_times(reset=True)
+                rerank_us, plv_us = int(t["rescore_us"]), {"scan_us": float(t["scan_us"]), "rescore_us": float(t["rescore_us"])}
             if hnsw:
                 t = self._flat.hnsw_stage_times(reset=True)
                 hnsw_us = {"search_us": float(t["search_us"]), "scored": int(t["scored"])}
@@ -2288,7 +2432,7 @@ class Collection:
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
                    "index_path": "ann_index" if self._ivf is not None or hnsw or diskann else ("flat_mmap_filtered" if subset is not None else
-                                                                            ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else "flat_mmap"))),
+                                                                            ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else ("polarvec_two_pass" if polarvec else "flat_mmap")))),
                    "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
                    "filter_us": filter_us, "search_us": search_us, "rerank_us": rerank_us, "total_us": int((time.perf_counter() - started) * 1e6),
@@ -2297,6 +2441,8 @@ class Collection:
                               "fallback_queries": int(dev["fallback_queries"]), "plan": int(dev["last_plan"])}}
         if stage_us is not None:
             profile["device"]["rabitq_stages"] = stage_us
+        if plv_us is not None:
+            profile["device"]["polarvec_stages"] = plv_us
         if hnsw_us is not None:
             profile["device"]["hnsw"] = hnsw_us
         if diskann_us is not None:

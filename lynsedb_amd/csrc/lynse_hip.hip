@@ -29,6 +29,7 @@
 #include "ivf.h"
 #include "pq.h"
 #include "rabitq.h"
+#include "polarvec.h"
 #include "hnsw.h"
 #include "diskann.h"
 #include "range.h"
@@ -253,6 +254,7 @@ struct Workspace {
 
 struct PqState;   // FLAT-*-PQ quantiser + search scratch (pq_host.inc)
 struct RbqState;  // FLAT-*-RABITQ codes + search scratch (rabitq_host.inc)
+struct PlvState;  // FLAT-*-POLARVEC<b> codes + search scratch (polarvec_host.inc)
 struct RangeState;  // range search scratch (range_host.inc)
 struct HnswState;  // HNSW-* graph + search scratch (hnsw_host.inc)
 struct DiskannState;  // DISKANN-* graph + search scratch (diskann_host.inc)
@@ -377,6 +379,7 @@ struct lynse_hip_flat {
 
     PqState* pq = nullptr;                // FLAT-{IP,L2,COS}-PQ index over the first pq->n rows (pq_host.inc); NULL = none
     RbqState* rbq = nullptr;              // FLAT-{IP,L2,COS}-RABITQ index over the first rbq->n rows (rabitq_host.inc); NULL = none
+    PlvState* plv = nullptr;              // FLAT-{IP,L2,COS}-POLARVEC<b> index over the first plv->n rows (polarvec_host.inc); NULL = none
     RangeState* range = nullptr;          // scratch of lynse_hip_flat_search_range_f32 (range_host.inc); NULL until the first one
     HnswState* hnsw = nullptr;            // HNSW-{IP,L2,COS} graph over the first hnsw->n rows (hnsw_host.inc); NULL = none
     DiskannState* diskann = nullptr;      // DISKANN-{L2,COS} graph over the first diskann->n rows (diskann_host.inc); NULL = none
@@ -389,6 +392,7 @@ struct lynse_hip_flat {
 
 static void pq_release(lynse_hip_flat* h);
 static void rbq_release(lynse_hip_flat* h);
+static void plv_release(lynse_hip_flat* h);
 static void range_release(lynse_hip_flat* h);
 static void hnsw_release(lynse_hip_flat* h);
 static void diskann_release(lynse_hip_flat* h);
@@ -529,6 +533,7 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     (void)hipSetDevice(h->device);
     pq_release(h);
     rbq_release(h);
+    plv_release(h);
     range_release(h);
     hnsw_release(h);
     diskann_release(h);
@@ -3576,6 +3581,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "ivf_async.inc"
 #include "pq_host.inc"
 #include "rabitq_host.inc"
+#include "polarvec_host.inc"
 #include "graph_host.inc"
 #include "hnsw_host.inc"
 #include "diskann_host.inc"

@@ -26,6 +26,7 @@ static int reset_derived_locked(lynse_hip_flat* h) {
     LY_HIP(hipStreamSynchronize(st));
     pq_release(h);
     rbq_release(h);
+    plv_release(h);
     hnsw_release(h);
     diskann_release(h);
     return LYNSE_OK;

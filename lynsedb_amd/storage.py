@@ -421,6 +421,117 @@ def load_rabitq_index(path) -> RabitqIndexFile:
     return RabitqIndexFile(dim, padded, sw.astype(np.uint64), codes.reshape(n, cb).copy(), norms.astype(np.float32))
 
 
+# ---- polarvec_index.bin (PolarVecIndex::save / load, src/storage/polarvec_mmap.rs:379-581) -------------------------------------
+POLARVEC_MAGIC = 0x504C_5651   # "PLVQ"
+POLARVEC_VERSION = 5
+POLARVEC_FLAG_RESIDUAL_SQ, POLARVEC_FLAG_INV_V_HAT_NORMS = 1, 2
+
+
+@dataclass
+class PolarvecIndexFile:
+    dim: int
+    padded_dim: int
+    bits: int
+    sign_words: np.ndarray    # u64 [ceil(padded_dim / 64)]
+    dim_mins: np.ndarray      # f32 [padded_dim]
+    dim_scales: np.ndarray    # f32 [padded_dim]
+    codes: np.ndarray         # u8 [n][ceil(padded_dim * bits / 8)]
+    residual_sq: Optional[np.ndarray] = None       # f32 [n], kept by an index built for L2 (flag 1)
+    inv_v_hat_norms: Optional[np.ndarray] = None   # f32 [n], kept by an index built for cosine (flag 2)
+
+    @property
+    def n_vectors(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def bytes_per_vec(self) -> int:
+        return (self.padded_dim * self.bits + 7) // 8
+
+    @property
+    def flags(self) -> int:
+        return ((POLARVEC_FLAG_RESIDUAL_SQ if self.residual_sq is not None else 0) |
+                (POLARVEC_FLAG_INV_V_HAT_NORMS if self.inv_v_hat_norms is not None else 0))
+
+
+def save_polarvec_index(path, idx: PolarvecIndexFile) -> None:
+    """Version 5, little endian: u32 magic, version, dim, padded_dim, bits; u64 n; u32 flags; u32 n_sign_words; the u64 sign words; the
+    f32 dim_mins and dim_scales [padded_dim]; the u8 codes [n][bytes_per_vec]; then the f32 [n] arrays the flags name, residual_sq
+    first.  (The reference leaves out an EMPTY array; an index holds at least one row here, so present and non-empty are the same.)"""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    n = idx.n_vectors
+    sw = np.ascontiguousarray(idx.sign_words, dtype="<u8").reshape(-1)
+    mins = np.ascontiguousarray(idx.dim_mins, dtype="<f4").reshape(-1)
+    scales = np.ascontiguousarray(idx.dim_scales, dtype="<f4").reshape(-1)
+    codes = np.ascontiguousarray(idx.codes, dtype=np.uint8).reshape(n, idx.bytes_per_vec)
+    if mins.shape[0] != idx.padded_dim or scales.shape[0] != idx.padded_dim:
+        raise ValueError("dim_mins and dim_scales must hold one value per padded dimension")
+    tail = []
+    for a in (idx.residual_sq, idx.inv_v_hat_norms):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype="<f4").reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError("a correction array must hold one value per code row")
+            tail.append(a)
+    header = np.array([POLARVEC_MAGIC, POLARVEC_VERSION, idx.dim, idx.padded_dim, idx.bits], "<u4").tobytes()
+    header += np.array([n], "<u8").tobytes() + np.array([idx.flags, sw.shape[0]], "<u4").tobytes()
+    with open(path, "wb") as f:
+        f.write(header)
+        f.write(sw.tobytes())
+        f.write(mins.tobytes())
+        f.write(scales.tobytes())
+        f.write(codes.tobytes())
+        for a in tail:
+            f.write(a.tobytes())
+
+
+def load_polarvec_index(path) -> PolarvecIndexFile:
+    """PolarVecIndex::load with the reference's checks, in its order, and its messages (IOError = its io::Error).  Only version 5 is
+    read: versions 1-4 (which carry norms, sign sketches and implied arrays) are refused as unsupported."""
+    raw = Path(path).read_bytes()
+
+    def take(off, count, fmt):
+        size = count * np.dtype(fmt).itemsize
+        if len(raw) < off + size:
+            raise IOError("failed to fill whole buffer")
+        return np.frombuffer(raw, fmt, count, off), off + size
+
+    v, off = take(0, 1, "<u4")
+    if int(v[0]) != POLARVEC_MAGIC:
+        raise IOError("Invalid PolarVec magic bytes")
+    v, off = take(off, 1, "<u4")
+    version = int(v[0])
+    if version != POLARVEC_VERSION:
+        raise IOError(f"Unsupported PolarVec version: {version}")
+    v, off = take(off, 3, "<u4")
+    dim, padded, bits = (int(x) for x in v)
+    v, off = take(off, 1, "<u8")
+    n = int(v[0])
+    if dim == 0 or padded != next_power_of_two(dim) or not (1 <= bits <= 8) or n > 0xFFFFFFFF:
+        raise IOError("Invalid PolarVec index dimensions")
+    v, off = take(off, 1, "<u4")
+    flags = int(v[0])
+    if flags & ~(POLARVEC_FLAG_RESIDUAL_SQ | POLARVEC_FLAG_INV_V_HAT_NORMS):
+        raise IOError("PolarVec index contains unknown flags")
+    v, off = take(off, 1, "<u4")
+    if int(v[0]) != (padded + 63) // 64:
+        raise IOError("Invalid PolarVec sign-word count")
+    sw, off = take(off, int(v[0]), "<u8")
+    mins, off = take(off, padded, "<f4")
+    scales, off = take(off, padded, "<f4")
+    bpv = (padded * bits + 7) // 8
+    codes, off = take(off, n * bpv, np.uint8)
+    residual = inv = None
+    if flags & POLARVEC_FLAG_RESIDUAL_SQ:
+        residual, off = take(off, n, "<f4")
+        residual = residual.astype(np.float32)
+    if flags & POLARVEC_FLAG_INV_V_HAT_NORMS:
+        inv, off = take(off, n, "<f4")
+        inv = inv.astype(np.float32)
+    return PolarvecIndexFile(dim, padded, bits, sw.astype(np.uint64), mins.astype(np.float32), scales.astype(np.float32),
+                             codes.reshape(n, bpv).copy(), residual, inv)
+
+
 # ---- sparse vectors: sparse_vectors.jsonl (SparseVectorRecord / SparseVectorStore, src/engine.rs:550-718) ----
 
 def _f32_json(x) -> str:
