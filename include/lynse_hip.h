@@ -131,8 +131,13 @@ typedef struct lynse_hip_profile {
                                  single-launch scan, bit 25 the sample stage ran on the query-stationary tiling, bit 26 the stages read the
                                  non-negative 7-bit copy of the codes (SQ7: FLAT-IP, 129..256 queries, LYNSE_HIP_SQ7), bit 27 the query-stationary
                                  threshold stages ran on v_mfma_i32_16x16x64_i8 (same tile, four segments per workgroup and query;
-                                 LYNSE_HIP_QS_M16=0: the 32x32x32 form; results never change) — lets a test pin
-                                 the kernel instantiation a benchmark configuration runs */
+                                 LYNSE_HIP_QS_M16=0: the 32x32x32 form; results never change), bit 28 the PREDICTED plan: one threshold
+                                 stage over all rows on a threshold predicted from the column statistics of the codes and verified
+                                 afterwards (FLAT-IP / cosine, 129..256 queries, k <= 32, LYNSE_HIP_PREDICT; with it bits 0 / 1 read 0 and the
+                                 stage count reads 1; a chunk it missed on is answered again on the sampled plan, which then is the last
+                                 plan) — lets a test pin the kernel instantiation a benchmark configuration runs */
+    uint64_t predicted_queries;    /* queries of chunks that ran the predicted plan */
+    uint64_t predict_miss_queries; /* of those, queries whose predicted threshold failed its verification (their chunks were re-answered) */
 } lynse_hip_profile;
 
 /* ---- library ---- */
@@ -885,6 +890,32 @@ int lynse_hip_flat_coarse_scores_sq7(lynse_hip_flat *h, const float *queries, ui
 /* SQ7 state of a shard: rows the copy covers (0 = not built) and the overflows of its scan so far (each is re-answered on the SQ8 codes;
  * 3 switch SQ7 off for the handle). */
 int lynse_hip_flat_sq7_state(lynse_hip_flat *h, uint64_t *out_rows, int *out_strikes);
+
+/* THE PREDICTED PLAN of the certified int8 pass (FLAT-IP / cosine, 129..256 queries, k <= 32, unfiltered, blocking searches; last_plan
+ * bit 28).  Each code set keeps the exact 64-bit column sums of its codes and of their squares; for a query image u the integer dot
+ * product over the rows then has mean m_q = sum u_d mu_d and, on the diagonal model, variance v_q = sum u_d^2 sigma_d^2, and the search
+ * runs prep -> ONE threshold stage over every row on thr = B_q + s_q (m_q + z sqrt(v_q)), n (1 - Phi(z)) = 40 k -> the select / rescoring
+ * launch, which checks from the emitted keys that the threshold was valid (k keys arrived and the final cut tau_x - E is not below it).  A
+ * chunk with a query that fails the check, or overflows, is answered again on the sampled plan: results never depend on the model.  Three
+ * such chunks switch prediction off until the codes are fitted again.  LYNSE_HIP_PREDICT=1 / 0 forces / disables it; unset: shards of
+ * >= 4M rows.  Tickets (lynse_hip_flat_search_submit_*), IVF, subset filters, squared L2 and the binary metrics keep their plans.
+ *
+ * The model on the host — no device involved: z for n rows and a target of keys_per_query emitted rows per query (0 when the target is
+ * n / 2 or more); mu_d / sigma_d^2 (clamped at 0) from sums[0 .. cols) = sum c_d and sums[cols .. 2 cols) = sum c_d^2 over n rows; and
+ * the threshold of one image u (sequential f64 sums, one f32 rounding of bq + sq (m + z sqrt(v))). */
+int lynse_hip_predict_z(uint64_t n, double keys_per_query, double *out_z);
+int lynse_hip_predict_col_stats(const int64_t *sums, uint32_t cols, uint64_t n, double *out_mu, double *out_var);
+int lynse_hip_predict_threshold(const int8_t *u, const double *mu, const double *var, uint32_t cols, double z, float bq, float sq,
+                                double *out_m, double *out_v, float *out_thr);
+/* Diagnostics: what the prep kernel of a predicted batch computes for `queries` (129..256) at this k — the int8 image out_u[nq][cols],
+ * B_q, s_q, m_q, v_q, the threshold and z — and the column statistics it read (out_mu / out_var[cols]; *out_cols = cols).  Builds the
+ * codes and statistics a search of the shape would; LYNSE_ERR_UNSUPPORTED where such a search would not predict.  Outputs may be NULL. */
+int lynse_hip_flat_predict_debug(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric, int8_t *out_u, double *out_mu,
+                                 double *out_var, float *out_bq, float *out_sq, double *out_m, double *out_v, float *out_thr, double *out_z,
+                                 uint32_t *out_cols);
+/* Strikes of the predicted plan so far (3 switch it off) and the rows the column statistics of the SQ8 / unit-row / SQ7 code sets cover
+ * (0 = not collected). */
+int lynse_hip_flat_predict_state(lynse_hip_flat *h, int *out_strikes, uint64_t *out_rows_sq8, uint64_t *out_rows_cos, uint64_t *out_rows_sq7);
 
 /* ---- sparse vectors: SparseVectorStore (src/engine.rs:550-718), index mode SPARSE-FLAT-IP ---- */
 

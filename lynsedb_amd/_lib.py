@@ -32,7 +32,8 @@ IPFORM_AUTO, IPFORM_SINGLE, IPFORM_BATCH8 = 0, 1, 2
 class Profile(C.Structure):
     _fields_ = [("searches", C.c_uint64), ("scan_launches", C.c_uint64), ("scan_us", C.c_double),
                 ("scan_rows", C.c_uint64), ("scan_bytes", C.c_uint64), ("total_us", C.c_double),
-                ("fallback_queries", C.c_uint64), ("pool_entries", C.c_uint64), ("last_plan", C.c_uint64)]
+                ("fallback_queries", C.c_uint64), ("pool_entries", C.c_uint64), ("last_plan", C.c_uint64),
+                ("predicted_queries", C.c_uint64), ("predict_miss_queries", C.c_uint64)]
 
 
 _f32p, _u32p, _u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -187,6 +188,13 @@ SIGNATURES = {
     "lynse_hip_flat_coarse_scores": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
     "lynse_hip_flat_coarse_scores_sq7": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_int)]),
     "lynse_hip_flat_sq7_state": (C.c_int, [_vp, _u64p, C.POINTER(C.c_int)]),
+    "lynse_hip_predict_z": (C.c_int, [C.c_uint64, C.c_double, C.POINTER(C.c_double)]),
+    "lynse_hip_predict_col_stats": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "lynse_hip_predict_threshold": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_double, C.c_float, C.c_float,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "lynse_hip_flat_predict_debug": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               C.POINTER(C.c_double), _u32p]),
+    "lynse_hip_flat_predict_state": (C.c_int, [_vp, C.POINTER(C.c_int), _u64p, _u64p, _u64p]),
     "lynse_hip_sparse_normalize": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "lynse_hip_sparse_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "lynse_hip_sparse_destroy": (C.c_int, [_vp]),

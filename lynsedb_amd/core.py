@@ -973,6 +973,30 @@ class FlatIndex:
         check(lib.lynse_hip_flat_sq7_state(self._h, C.byref(rows), C.byref(strikes)))
         return {"sq7_rows": rows.value, "sq7_strikes": strikes.value}
 
+    def predict_debug(self, queries, k: int, metric) -> dict:
+        """Diagnostics of the predicted plan (`lynse_hip_flat_predict_debug`): the int8 image, B_q, s_q, m_q, v_q and the threshold the prep
+        kernel computes for 129..256 queries at this k, z, and the column statistics (mu, var) of the code set it read."""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        nq, cap = q.shape[0], (self.dim + 127) // 128 * 128
+        u = np.zeros((nq, cap), np.int8)
+        mu, var = np.zeros(cap, np.float64), np.zeros(cap, np.float64)
+        bq, sq, thr = (np.zeros(nq, np.float32) for _ in range(3))
+        mq, vq = np.zeros(nq, np.float64), np.zeros(nq, np.float64)
+        z, cols = C.c_double(0.0), C.c_uint32(0)
+        flat = np.zeros(nq * cap, np.int8)
+        check(lib.lynse_hip_flat_predict_debug(self._h, _ptr(q), nq, int(k), m, _ptr(flat), _ptr(mu), _ptr(var), _ptr(bq), _ptr(sq), _ptr(mq), _ptr(vq),
+                                               _ptr(thr), C.byref(z), C.byref(cols)))
+        c = cols.value
+        u = flat[:nq * c].reshape(nq, c).copy()
+        return {"u": u, "mu": mu[:c].copy(), "var": var[:c].copy(), "bq": bq, "sq": sq, "m": mq, "v": vq, "thr": thr, "z": z.value, "cols": c}
+
+    def predict_state(self) -> dict:
+        """Strikes of the predicted plan (3 = switched off until the codes are fitted again) and the rows its column statistics cover."""
+        strikes, r8, rc, r7 = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib.lynse_hip_flat_predict_state(self._h, C.byref(strikes), C.byref(r8), C.byref(rc), C.byref(r7)))
+        return {"predict_strikes": strikes.value, "stats_rows_sq8": r8.value, "stats_rows_cos": rc.value, "stats_rows_sq7": r7.value}
+
     def coarse_state(self) -> dict:
         """State of the coarse-pass selection: overflow strikes of the certified int8 pass (3 = switched off, -1 = off because the
         rows are not finite) and the rows covered by the SQ8 codes built so far."""

@@ -2056,6 +2056,17 @@ struct I8cPrepArgs {
     // the first part goes into B_q, the second is bounded as before with a1 / a2sq taken over c - 64 (k_sq8_quantize) — without the split
     // the query term carries the codes' mean (2-4x the margin on centred data).  mins / scales / eps2: the SQ7 copy's.
     int sq7;
+    // Predicted first threshold (predict.h; pred_mu == nullptr: off — the threshold opens as above): with mu_d / sigma_d^2 of the stored
+    // codes' columns, m_q = sum u_d mu_d and v_q = sum u_d^2 sigma_d^2 are the mean and the diagonal-model variance of this query's
+    // integer dot product over the rows, and thr[q] = fl(B_q + s_q (m_q + z sqrt(v_q))) (ONE f32 rounding; B_q, s_q the f32 values the scan
+    // reads).  pred_chk[q] = that threshold raised by the float evaluation error of the coarse score on both sides: the value
+    // k_select_final's final cut must reach for the plan to count as complete (TailArgs::pred_chk).  A query the model cannot serve — a
+    // non-finite image, v_q = 0 — gets thr = pred_chk = +inf: nothing is emitted and the verification reports it as unpredicted.
+    // pred_dbg (optional): [q][2] = m_q, v_q.
+    const double *pred_mu, *pred_var;
+    double pred_z;
+    float* pred_chk;
+    double* pred_dbg;
     const int8_t* codes;   // the rows the scan streams: [n_rows][ld8] signed SQ8 codes
     uint32_t ld8, n_rows, tile_rows, dyn_ks, seed_rows;
     int *dyn_thr, *dyn_slot, *dyn_marg;
@@ -2128,7 +2139,7 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
     // ---- the int8 image + sum eta_d^2 (eta_d = w_d / s_q - u_d: the residual of the query's own quantisation)
     const double inv = 1.0 / (double)s_sq;
     const uint32_t total = a.nslab * 128;
-    double eta2 = 0.0, eta1 = 0.0;
+    double eta2 = 0.0, eta1 = 0.0, pm = 0.0, pv = 0.0;
     for (uint32_t i = tid; i < total; i += 256) {
         int u = 0;
         if (i < DA) {
@@ -2140,13 +2151,18 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
             u = (r == r) ? (int)r : 0;
             const double eta = t - (double)u;
             if (eta == eta) { eta2 += eta * eta; eta1 += eta; }
+            if (a.pred_mu) { const double ud = (double)u; pm += ud * a.pred_mu[i]; pv += ud * ud * a.pred_var[i]; }
         }
         const uint32_t s = i / 128, k = i % 128, l = k >> 4, e = k & 15, p = l ^ ((q >> 1) & 7);
         a.img[(((size_t)s * a.qpad + q) * 8 + p) * 16 + e] = (int8_t)u;
         if (a.dyn_thr) s_u[i] = (int8_t)u;
     }
     for (int o = 32; o > 0; o >>= 1) { eta2 += __shfl_xor(eta2, o, 64); eta1 += __shfl_xor(eta1, o, 64); }
-    __shared__ double red3[4];
+    __shared__ double red3[4], redp[2][4];
+    if (a.pred_mu) {   // (uniform)
+        for (int o = 32; o > 0; o >>= 1) { pm += __shfl_xor(pm, o, 64); pv += __shfl_xor(pv, o, 64); }
+        if (lane == 0) { redp[0][wave] = pm; redp[1][wave] = pv; }
+    }
     if (lane == 0) { red2[1][wave] = eta2; red3[wave] = eta1; }
     __syncthreads();
     if (tid == 0) {
@@ -2190,6 +2206,17 @@ __global__ void __launch_bounds__(256) k_i8c_prep_queries(I8cPrepArgs a) {
         a.bq[q] = bq_out;
         a.marg2[q] = (float)(2.0 * E);
         a.thr[q] = a.l2n ? LY_INF : -LY_INF;
+        if (a.pred_mu) {
+            pm = (redp[0][0] + redp[0][1]) + (redp[0][2] + redp[0][3]);
+            pv = (redp[1][0] + redp[1][1]) + (redp[1][2] + redp[1][3]);
+            const float thr = (float)((double)bq_out + (double)sq * (pm + a.pred_z * sqrt(pv)));
+            // (the scan tests fl(B_q + s_q fl(dot)) >= thr and the keys carry that value: a few ulps of its magnitude cover either rounding)
+            const float slack = (float)(1.0e-6 * (fabs(bq) + 127.0 * (double)sq * a1mag));
+            const bool ok = wmax < 1.0e30 && E < 3.0e38 && pv > 0.0 && fabsf(thr) < LY_INF && slack == slack;
+            a.thr[q] = ok ? thr : LY_INF;
+            a.pred_chk[q] = ok ? nextafterf(thr + slack, LY_INF) : LY_INF;
+            if (a.pred_dbg) { a.pred_dbg[2 * (size_t)q] = pm; a.pred_dbg[2 * (size_t)q + 1] = pv; }
+        }
         a.count[q] = 0u;
         a.overflow[q] = 0u;
         if (q == 0 && a.gsync) { a.gsync[0] = 0u; a.gsync[1] = 0u; a.gsync[2] = 0u; }
@@ -3830,9 +3857,16 @@ __global__ void __launch_bounds__(NT) k_final(FinalArgs a) {
 // launch per batch (they were three: k_select, k_rescore_pool / the rescoring half of k_final, k_final — 40 us of a 345 us
 // step on a 1.25M-row shard, two kernel boundaries and two trips of the survivors through HBM).  The survivors go to
 // cand[q] as before (same workgroup: visible behind the barrier) and come back into LDS for the rescoring and the sort.
+// pred_chk != nullptr: the ONE threshold stage ran on a PREDICTED threshold (k_i8c_prep_queries, I8cPrepArgs::pred_mu) that no scored row
+// backs.  It was valid for query q if and only if k keys arrived and the cut the select forms from them — tau_x - E, k rows with an exact
+// score >= tau_x exist — is not below it: every row that can be in the exact top-k has a coarse score >= that cut, and every row whose
+// coarse score reaches the predicted threshold was emitted.  Otherwise the query's overflow word gains PRED_MISS (pred_chk = +inf: the
+// prep kernel could not predict, PRED_NONE) beside the overflow bit 1, and the host answers the chunk again on the sampled plan.
+constexpr uint32_t PRED_MISS = 2u, PRED_NONE = 4u;
 struct TailArgs {
     SelectArgs s;
     FinalArgs f;
+    const float* pred_chk;
 };
 
 template <int NT>
@@ -3842,6 +3876,11 @@ __global__ void __launch_bounds__(NT) k_select_final(TailArgs a) {
     const uint32_t q = blockIdx.x;
     bool rescored;
     const uint32_t n = select_body<NT>(a.s, keys, q, &rescored);
+    if (a.pred_chk && threadIdx.x == 0) {   // (thread 0 wrote a.s.thr[q] — the final cut — and reads the overflow word in final_body)
+        const float chk = a.pred_chk[q];
+        if (!(chk < LY_INF)) a.s.overflow[q] |= PRED_NONE;
+        else if (!(n >= a.s.k && a.s.thr[q] >= chk)) a.s.overflow[q] |= PRED_MISS;
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's survivor stores have reached L2 (they are read back sc1)
     __syncthreads();
     final_body<NT>(a.f, keys, q, n, a.f.exact != 0 || rescored, true);

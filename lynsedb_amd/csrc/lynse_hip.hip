@@ -38,6 +38,7 @@
 #include "text.h"
 #include "spann.h"
 #include "mutate.h"
+#include "predict.h"
 
 using namespace lynse;
 
@@ -226,6 +227,8 @@ struct Workspace {
     uint8_t* segcnt = nullptr;   // [QCHUNK][SEG_MAX] per-segment key counts
     uint32_t *count = nullptr, *overflow = nullptr;
     float *thr = nullptr, *qinv = nullptr, *qn2 = nullptr, *qrinv = nullptr, *marg2 = nullptr;
+    float* pred_chk = nullptr;   // predicted plan: the value each query's final cut must reach (I8cPrepArgs::pred_chk)
+    double* pred_dbg = nullptr;  // [qcap][2] m_q, v_q of the last predicted chunk (diagnostics)
     _Float16* Q16 = nullptr;
     size_t q16_halves = 0;
     float* Qf = nullptr;
@@ -246,7 +249,7 @@ struct Workspace {
         if (h_out) (void)hipHostFree(h_out);
         for (void* p : {(void*)cand, (void*)candB, (void*)segcnt, (void*)count, (void*)thr, (void*)qinv, (void*)qn2,
                         (void*)qrinv, (void*)marg2, (void*)Q16, (void*)Qf, (void*)QW, (void*)QWp, (void*)out_rows,
-                        (void*)out_dists, (void*)out_counts, (void*)pool_total, (void*)small_part, (void*)small_ticket, (void*)gsync, (void*)dyn})
+                        (void*)out_dists, (void*)out_counts, (void*)pool_total, (void*)small_part, (void*)small_ticket, (void*)gsync, (void*)dyn, (void*)pred_chk, (void*)pred_dbg})
             if (p) (void)hipFree(p);
         *this = Workspace();
     }
@@ -272,12 +275,21 @@ struct CodeSet {
     bool finite = false;
     uint32_t cols = 0, ld = 0;   // columns coded / pitch in bytes
     int *sum = nullptr, *sum2 = nullptr;   // per-row sums of the codes and their squares (the plain set only: FLAT-*-SQ8)
+    // Column statistics of the stored codes for the predicted first threshold (predict.h; the plain, unit-row and SQ7 sets): the exact
+    // 64-bit sums of c_d and c_d^2 over rows [0, colsum_n) on the device, and mu_d / sigma_d^2 formed from them on the host (f64) and
+    // uploaded.  colsum_n == n: up to date (code_stats_locked); 0: not collected.
+    unsigned long long* colsum = nullptr;  // 2 x cols
+    double *mu = nullptr, *var = nullptr;  // cols each
+    uint64_t colsum_n = 0;
+    std::vector<double> h_mu, h_var;       // host copies (lynse_hip_flat_predict_debug)
     bool ready(uint64_t rows) const { return codes && n == rows; }
+    bool stats_ready() const { return codes && mu && colsum_n == n && n != 0; }
     uint64_t hbm_bytes() const { return codes ? cap * ld + (sum ? 2ull * (cap + 256) * 4 : 0ull) : 0ull; }
     void release() {
-        for (void* p : {(void*)codes, (void*)mins, (void*)scales, (void*)mm, (void*)stats, (void*)sum, (void*)sum2})
+        for (void* p : {(void*)codes, (void*)mins, (void*)scales, (void*)mm, (void*)stats, (void*)sum, (void*)sum2, (void*)colsum, (void*)mu, (void*)var})
             if (p) (void)hipFree(p);
         codes = nullptr; mins = scales = nullptr; mm = stats = nullptr; sum = sum2 = nullptr;
+        colsum = nullptr; mu = var = nullptr; colsum_n = 0;
         n = cap = 0;
     }
 };
@@ -360,6 +372,7 @@ struct lynse_hip_flat {
     uint64_t sq8_fit = 0;   // counts the fits of the min / max table of `sq8` (a new fit recodes every row: ensure_codes_locked)
     uint64_t sq7_fit = 0;   // the sq8_fit the SQ7 copy was coded under
     std::atomic<int> sq7_strikes{0};       // overflows of the SQ7 scan (each re-answered on the SQ8 codes); 3 switch it off for the handle
+    std::atomic<int> predict_strikes{0};   // chunks the predicted first threshold missed or overflowed on (each re-answered on the sampled plan); 3 switch it off until the codes are fitted again
     // overflow strikes of the certified int8 pass, per METRIC (plain-code L2 reads `sq8` but strikes i8c_strikes_l2)
     std::atomic<int> i8c_strikes_l2{0};
     std::atomic<int> i8c_strikes_cos{0};
@@ -1106,6 +1119,8 @@ static int ensure_workspace(lynse_hip_flat* h, uint32_t k /* caller's k = output
     LY_HIP(hipMalloc(&w.qn2, (size_t)QC * 4));
     LY_HIP(hipMalloc(&w.qrinv, (size_t)QC * 4));
     LY_HIP(hipMalloc(&w.marg2, (size_t)QC * 4));
+    LY_HIP(hipMalloc(&w.pred_chk, (size_t)QC * 4));
+    LY_HIP(hipMalloc(&w.pred_dbg, (size_t)QC * 16));
     w.q16_halves = (size_t)nslab * QC * SCAN_LDK;
     LY_HIP(hipMalloc(&w.Q16, w.q16_halves * sizeof(_Float16)));
     LY_TRY(memset_done(w.Q16, 0, w.q16_halves * sizeof(_Float16)));
@@ -1705,6 +1720,8 @@ static void fill_i8c_prep(I8cPrepArgs& p, const I8cOperand& v, I8cForm form) {
 static int fused_sample_env() { return env_int("LYNSE_HIP_FUSED_SAMPLE", 0); }   // (read per call: tests flip it)
 static bool sq7_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, bool masked);
 static bool sq7_ready(const lynse_hip_flat* h);
+static bool predict_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, uint32_t k, bool masked);
+static double predict_keys_per_query(uint32_t k);
 
 // What run_chunk does with the chunk.  CHUNK_ASSIGN (flat_assign_top1_device): the lane-max scan of the k-means assignment over EVERY
 // tile of the (small) centroid store, then stop — k_assign_pick reads the keys (kernels.h).  CHUNK_COARSE_DUMP
@@ -1723,6 +1740,7 @@ struct ChunkReq {
     // (k_i8c_prep_queries) instead of the f16 shadow — FLAT-IP batches of 33..256 queries
     bool i8c = false;
     bool allow_sts = true;    // the self-tightening single-launch scan may answer this chunk (an overflow of it is retried on the staged plan of the same coarse pass, without a strike)
+    bool allow_predict = false;   // the chunk may run the predicted plan: one threshold stage on a threshold k_select_final verifies afterwards (the blocking FLAT search; a miss or an overflow is re-answered on the sampled plan)
     bool allow_sq7 = false;   // the chunk may scan the non-negative 7-bit copy of the codes (the blocking FLAT search and the certificate diagnostics; an overflow is re-answered on the SQ8 codes, without a strike against the int8 pass)
     struct Out {
         // where k_final writes rows, distances (stride out_k) and a second copy of the counts — the caller's device arrays or the pinned
@@ -1735,7 +1753,7 @@ struct ChunkReq {
     } out;
     ChunkMode mode = CHUNK_SEARCH;
 };
-struct ChunkResult { bool sampled = false, used_sts = false, used_sq7 = false; };   // the plan began with a sample stage / ran the self-tightening scan / read the SQ7 copy
+struct ChunkResult { bool sampled = false, used_sts = false, used_sq7 = false, used_predict = false; };   // the plan began with a sample stage / ran the self-tightening scan / read the SQ7 copy / ran on a predicted threshold
 // the events of a profiled search: events taken from the context's pool so far, and (first event, rows scanned) per scan launch
 struct ScanProf { size_t ev_used = 0; std::vector<std::pair<size_t, uint64_t>> scan_events; };
 
@@ -1804,6 +1822,14 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
                      k >= 1 && k <= 32 && qs_variant() >= 1 && qs_variant() <= 3 && opd.ld == 768 && nslab == 6 && qpad == 256 && h->n >= 65536 &&
                      h->n < 0xffffff00ull && (metric == M_IP || cosq);
     res->used_sts = sts;
+    // Predicted plan: prep -> ONE threshold stage over [0, n) on the threshold the prep kernel predicts from the column statistics
+    // of the code set the stage reads -> k_select_final, which verifies it.  (predict_wanted is the predicate of the shape; the statistics
+    // must be up to date: code_stats_locked)
+    const bool fused_tail_on = env_int("LYNSE_HIP_FUSED_TAIL", 1) != 0;   // (the verification lives in k_select_final)
+    const CodeSet* pred_set = !i8q ? nullptr : (sq7 ? &h->sq7 : &i8c_code_set(h, form));
+    const bool predict = rq.allow_predict && rq.mode == CHUNK_SEARCH && !sts && level == 0 && i8q && !aug && !l2n && !small && !mid64 && !mid128 && !mask && !row_ids &&
+                         fused_tail_on && qpad == 256 && predict_wanted(h, metric, nq, k, false) && pred_set->stats_ready() && h->n < 0xffffff00ull;
+    res->used_predict = predict;
     if (bin_mfma) {
         // (the prep kernels write every byte of the image: the lines of their queries, pad columns included, and — blocks nq .. qpad - 1 of the
         // grid — zero lines for the pad queries of the tile; up to round 5 a hipMemsetAsync of the image ran in front: a launch of its own)
@@ -1824,6 +1850,10 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
         fill_i8c_prep(p, opd, form);
         p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow;
         p.gsync = w.gsync;
+        if (predict) {
+            p.pred_mu = pred_set->mu; p.pred_var = pred_set->var; p.pred_chk = w.pred_chk; p.pred_dbg = w.pred_dbg;
+            p.pred_z = predict_z(h->n, predict_keys_per_query(k));
+        }
         if (sts) {   // seed the partition maxima of the self-tightening scan from a few sample rows (valid thresholds from the first tile on)
             p.codes = opd.codes; p.ld8 = opd.ld; p.n_rows = (uint32_t)h->n; p.tile_rows = 64; p.dyn_ks = k;
             p.seed_rows = std::min<uint32_t>(1024u, 32u * k);
@@ -1859,7 +1889,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     assign_stage.sample_tiles = (uint32_t)((h->n + 255) / 256);
     assign_stage.sample_stride = 256;
     const std::vector<Stage> plan = assign ? std::vector<Stage>{assign_stage}
-                                    : (sts || coarse_dump) ? std::vector<Stage>{Stage{0u, (uint32_t)h->n}}
+                                    : (sts || coarse_dump || predict) ? std::vector<Stage>{Stage{0u, (uint32_t)h->n}}
                                         : make_plan(h, k, (level == 0 && !plan_tile) ? 1 : level, plan_tile, can_threshold_only,
                                                     // large k on the float tilings: the epilogue's cost is the emissions (one sample threshold over 1M x 128,
                                                     // k = 100, admits 1400 rows per query: 87 of the stage's 163 us) — a second threshold stage a quarter of the
@@ -1892,7 +1922,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     SelectArgs sa_last{};
     for (size_t si = 0; si < plan.size(); ++si) {
         const Stage s = plan[si];
-        const bool emit_all = si == 0 && !sts;   // (sts: the one stage is a threshold stage — its thresholds live in w.dyn and tighten while it runs)
+        const bool emit_all = si == 0 && !sts && !predict;   // (predict: the one stage is a threshold stage on the predicted a.thr; sts: the one stage is a threshold stage — its thresholds live in w.dyn and tighten while it runs)
         if (fs && si == 0) continue;   // scored inside the launch of stage 1
         const bool fs_stage = fs && si == 1;
         uint32_t qs_sample_keys = 0;   // != 0: the sample stage ran on the query-stationary tiling and left this many keys per query
@@ -2098,6 +2128,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
                             (plan_used_segments ? 8u : 0u) | (small ? 16u : 0u) | (fs ? 128u : 0u) | ((uint64_t)(plan.size() & 0xff) << 8) | (tiling << 16) |
                             (sts ? (1ull << 24) : 0ull) | (plan_qs_sample ? (1ull << 25) : 0ull) |   // bit 24: self-tightening single-launch scan; bit 25: sample stage on the query-stationary tiling
                             (sq7 ? (1ull << 26) : 0ull) |   // bit 26: the stages read the non-negative 7-bit copy of the codes (SQ7)
+                            (predict ? (1ull << 28) : 0ull) |   // bit 28: one threshold stage on a predicted threshold, verified in k_select_final
                             (plan_qs_m16 ? (1ull << 27) : 0ull);   // bit 27: query-stationary threshold stages on v_mfma_i32_16x16x64_i8 (scan_qs.h, M16)
     }
     FinalArgs fa{};
@@ -2113,7 +2144,7 @@ static int run_chunk(lynse_hip_flat* h, const ChunkReq& rq, hipStream_t st, Scan
     fa.overflow = w.overflow; fa.any_overflow = rq.out.any_ovf;
     if (rq.out.hdr_direct) { fa.h_hdr = w.h_hdr; fa.hdr_q = w.qcap; }
     if (fused_tail) {
-        TailArgs ta{sa_last, fa};
+        TailArgs ta{sa_last, fa, predict ? w.pred_chk : nullptr};
         ta.s.hand_exact = env_int("LYNSE_HIP_HAND_EXACT", 1);   // (0: the final rescoring always reads its rows, A/B)
         ta.s.lds_bytes = ta.f.lds_bytes = sel_lds_bytes(w.cap, nq);
         hipLaunchKernelGGL(k_select_final<SEL_NT>, dim3(nq), dim3(SEL_NT), ta.s.lds_bytes, st, ta);
@@ -2275,8 +2306,48 @@ static int sq8_merge_new_rows(lynse_hip_flat* h, uint32_t* mm, uint32_t D, uint6
     return LYNSE_OK;
 }
 
+// LYNSE_HIP_PREDICT: the predicted first threshold of the certified int8 pass (predict.h): 0 = never, 1 = wherever the shape is
+// eligible, unset = auto (read per call: tests flip it)
+static int predict_env() { return env_int("LYNSE_HIP_PREDICT", -1); }
+// auto: from this many rows on.  Forced, the plan gains at every measured shard size (profiles/predict_size_sweep.json: 1.25M / 2.4M / 4M /
+// 6M / 8M / 10M rows gain 36 / 61 / 58 / 38 / 37 / 56 us per step, each beyond three times the spread of its runs); the plans the tests pin
+// without a knob go up to 2.4M rows, so auto starts at the next measured size.
+static const uint64_t PREDICT_AUTO_MIN_ROWS = 4000000ull;
+static bool predict_size_ok(const lynse_hip_flat* h) { const int e = predict_env(); return e == 1 || (e != 0 && h->n >= PREDICT_AUTO_MIN_ROWS); }
+
+// Brings the column statistics of a code set up to date with its codes: the sums take in rows colsum_n .. n (all of them after a new
+// fit, which resets colsum_n), then mu / sigma^2 are formed on the host and uploaded.  Synchronises the stream.
+static int code_stats_locked(lynse_hip_flat* h, CodeSet& s) {
+    if (!s.codes || s.n == 0 || s.ld % 4 != 0 || s.stats_ready()) return LYNSE_OK;
+    hipStream_t st = cur(h).stream;
+    const uint32_t DC = s.cols;
+    if (!s.colsum) {
+        LY_HIP(hipMalloc(&s.colsum, (size_t)DC * 16));
+        LY_HIP(hipMalloc(&s.mu, (size_t)DC * 8));
+        LY_HIP(hipMalloc(&s.var, (size_t)DC * 8));
+        s.colsum_n = 0;
+    }
+    if (s.colsum_n > s.n) s.colsum_n = 0;
+    if (s.colsum_n == 0) LY_HIP(hipMemsetAsync(s.colsum, 0, (size_t)DC * 16, st));
+    const uint64_t nn = s.n - s.colsum_n;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nn + 1023) / 1024, (uint64_t)h->num_cu * 8);
+    hipLaunchKernelGGL(k_code_colsums, dim3(grid), dim3(256), 0, st, s.codes + s.colsum_n * s.ld, s.ld, DC, nn, s.colsum);
+    LY_HIP(hipGetLastError());
+    std::vector<long long> sums((size_t)DC * 2);
+    LY_HIP(hipMemcpyAsync(sums.data(), s.colsum, (size_t)DC * 16, hipMemcpyDeviceToHost, st));
+    LY_HIP(hipStreamSynchronize(st));
+    s.h_mu.resize(DC); s.h_var.resize(DC);
+    predict_col_stats(sums.data(), DC, s.n, s.h_mu.data(), s.h_var.data());
+    LY_HIP(hipMemcpyAsync(s.mu, s.h_mu.data(), (size_t)DC * 8, hipMemcpyHostToDevice, st));
+    LY_HIP(hipMemcpyAsync(s.var, s.h_var.data(), (size_t)DC * 8, hipMemcpyHostToDevice, st));
+    LY_HIP(hipStreamSynchronize(st));
+    s.colsum_n = s.n;
+    return LYNSE_OK;
+}
+
 // The tail every code-set builder shares: rows r0 .. n of `s` are coded (k_sq8_quantize, minima `mins`, the set's own scales), the four
-// stats words come back into a1 / a2sq / eps2 / finite and the set covers the shard.  Synchronises the stream.
+// stats words come back into a1 / a2sq / eps2 / finite and the set covers the shard; the column statistics of the predicted threshold
+// follow where a shard of this size may use them (not for the augmented rows of the L2 form).  Synchronises the stream.
 static int quantize_rows_locked(lynse_hip_flat* h, CodeSet& s, uint64_t r0, const float* mins, const float* extra_col, uint32_t n_extra,
                                 const float* row_scale, int sq7) {
     hipStream_t st = cur(h).stream;
@@ -2299,6 +2370,8 @@ static int quantize_rows_locked(lynse_hip_flat* h, CodeSet& s, uint64_t r0, cons
     memcpy(&s.eps2, &qst[3], 4);
     s.finite = qst[1] == 0;
     s.n = h->n;
+    if (r0 == 0) { s.colsum_n = 0; if (!extra_col) h->predict_strikes.store(0); }   // a new fit: the sums start again, and so does the model's record
+    if (!extra_col && s.finite && predict_size_ok(h)) LY_TRY(code_stats_locked(h, s));
     return LYNSE_OK;
 }
 
@@ -2424,6 +2497,32 @@ static int ensure_sq7_locked(lynse_hip_flat* h) {
     return LYNSE_OK;
 }
 static bool sq7_ready(const lynse_hip_flat* h) { return h->sq7.ready(h->n) && h->sq7_fit == h->sq8_fit && h->sq8.ready(h->n); }
+
+// Does a batch of nqc queries over this shard run the predicted plan (run_chunk)?  The shapes the query-stationary tiling answers with
+// more than 128 queries — IP and cosine, whole 128-column slabs, k <= 32 —, unmasked; a shard large enough that the C keys per query
+// the threshold aims at are a far tail of its rows; not beside the self-tightening or fused-sample plans; not after three strikes.
+// LYNSE_HIP_PREDICT_C: the target key count per query in units of k (A/B; default 40, the best of profiles/predict_c_sweep.json).
+static double predict_keys_per_query(uint32_t k) { return (double)std::max(1, env_int("LYNSE_HIP_PREDICT_C", 40)) * (double)k; }
+static bool predict_wanted(const lynse_hip_flat* h, int metric, uint64_t nqc, uint32_t k, bool masked) {
+    if (predict_env() == 0 || (metric != M_IP && metric != M_COS) || masked || nqc <= 128 || nqc > QCHUNK || h->qchunk > QCHUNK) return false;
+    if (k < 1 || k > 32 || h->n < 65536 || (double)h->n < 8.0 * predict_keys_per_query(k)) return false;
+    if (qs_variant() < 1 || qs_variant() > 3 || !qs_width_ok(h->ld8, (h->dim + 127) / 128, false)) return false;
+    if (sts_env_on() || fused_sample_env() != 0) return false;
+    if (h->predict_strikes.load() >= 3) return false;
+    return predict_size_ok(h);
+}
+// The code set a predicted chunk of this shape would read, as run_chunk picks it.
+static CodeSet& predict_code_set(lynse_hip_flat* h, int metric, uint64_t nqc) {
+    if (sq7_wanted(h, metric, nqc, false) && sq7_ready(h)) return h->sq7;
+    return metric == M_COS ? h->sq8c : h->sq8;
+}
+// Statistics only change speed: a shape that wants them gets them built here (writer lock), after the code sets themselves.
+static int predict_sync_locked(lynse_hip_flat* h, int metric, uint64_t nqc, uint32_t k, bool masked) {
+    if (!predict_wanted(h, metric, nqc, k, masked)) return LYNSE_OK;
+    CodeSet& s = predict_code_set(h, metric, nqc);
+    if (!s.ready(h->n) || !s.finite) return LYNSE_OK;
+    return code_stats_locked(h, s);
+}
 
 extern "C" int lynse_hip_flat_sq8_params(lynse_hip_flat* h, float* mins, float* scales) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -2689,6 +2788,10 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         if (i8c_eligible(h, metric, false, std::min<uint64_t>(nq, QCHUNK), caller_holds_exclusive, filtered)) {
             // (the blocking search alone scans the SQ7 copy: a wanted copy that is missing, or a stale one, is dealt with under the writer lock)
             if (sq7_stale(h) || (sq7_wanted(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) && h->sq8.finite && !sq7_ready(h))) return false;
+            // (so does the predicted plan: column statistics that are wanted and missing are built under the writer lock)
+            if (predict_wanted(h, metric, std::min<uint64_t>(nq, QCHUNK), (uint32_t)std::min<uint64_t>(k, h->n), filtered) &&
+                i8c_codes_ready(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) && i8c_codes_finite(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered) &&
+                !predict_code_set(h, metric, std::min<uint64_t>(nq, QCHUNK)).stats_ready()) return false;
             return i8c_codes_ready(h, metric, std::min<uint64_t>(nq, QCHUNK), filtered);
         }
         return shadow_ready(h) || small_path_ok(h, std::min<uint64_t>(nq, QCHUNK), (uint32_t)std::min<uint64_t>(k, h->n), metric, filtered);
@@ -2894,7 +2997,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         LY_TRY(get_event(h, sprof.ev_used++, &ev_end));
         LY_HIP(hipEventRecord(ev_begin, st));
     }
-    uint64_t fallback_queries = 0;
+    uint64_t fallback_queries = 0, predicted_queries = 0, predict_miss_queries = 0;
     bool i8c_attempted = false;
 
     // queries per pipeline pass: QCHUNK; a widened handle (the k-means assignment's centroid store: unfiltered float search of
@@ -2922,7 +3025,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         bool i8c = i8c_eligible(h, metric, filtered && direct, nqc, caller_holds_exclusive, filtered && !direct);
         if (i8c) {
             const bool msk = filtered && !direct;
-            if (xlk.owns_lock()) { LY_TRY(ensure_i8c_codes_locked(h, metric, nqc, msk)); sq7_sync_locked(h, metric, nqc, msk); }   // lazy builds: exclusive path only (a chunk without the SQ7 copy scans the SQ8 codes)
+            if (xlk.owns_lock()) { LY_TRY(ensure_i8c_codes_locked(h, metric, nqc, msk)); sq7_sync_locked(h, metric, nqc, msk); LY_TRY(predict_sync_locked(h, metric, nqc, kk, msk)); }   // lazy builds: exclusive path only (a chunk without the SQ7 copy scans the SQ8 codes, one without column statistics runs the sampled plan)
             else if (!i8c_codes_ready(h, metric, nqc, msk)) i8c = false;                    // (shared path: derived_ready() saw them built)
             if (i8c && !i8c_codes_finite(h, metric, nqc, msk)) { i8c_strike_counter(h, metric).store(-1); i8c = false; }
         }
@@ -2949,7 +3052,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             }
             continue;
         }
-        bool allow_sts = true, allow_sq7 = true;
+        bool allow_sts = true, allow_sq7 = true, allow_predict = true;
         for (int level = 0; level < 3; ++level) {  // sampled plan -> contiguous plan -> exhaustive plan (make_plan)
             ChunkResult res;
             // k_final writes the results where they belong — the caller's device arrays, or the pinned (device-visible)
@@ -2961,7 +3064,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             ChunkReq rq;
             rq.nq = nqc; rq.k = kk; rq.out_k = k; rq.metric = metric; rq.level = level;
             rq.mask = mask; rq.row_ids = direct ? h->g_ids32 : nullptr; rq.qsrc = qsrc;
-            rq.i8c = i8c; rq.allow_sts = allow_sts; rq.allow_sq7 = allow_sq7;
+            rq.i8c = i8c; rq.allow_sts = allow_sts; rq.allow_sq7 = allow_sq7; rq.allow_predict = allow_predict;
             rq.out.rows = on_device ? out_rows + q0 * k : (staged ? reinterpret_cast<uint64_t*>(w.h_out) : nullptr);
             rq.out.dists = on_device ? out_dists + q0 * k : (staged ? reinterpret_cast<float*>(w.h_out + rows_b) : nullptr);
             rq.out.counts2 = on_device ? out_counts + q0 : nullptr;
@@ -2972,14 +3075,24 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
                 LY_HIP(hipMemcpyAsync(out_dists + q0 * k, w.out_dists, dists_b, out_kind, st));
             }
             LY_TRY(stream_wait(st));  // (counts + overflow flags: written into the pinned header by k_final)
-            uint32_t nov = 0;
-            for (uint32_t i = 0; i < nqc; ++i) nov += w.h_hdr[w.qcap + i] ? 1 : 0;
+            uint32_t nov = 0, nmiss = 0, nover = 0;
+            for (uint32_t i = 0; i < nqc; ++i) {
+                const uint32_t f = w.h_hdr[w.qcap + i];
+                nov += f ? 1 : 0; nover += (f & 1u) ? 1 : 0; nmiss += (f & PRED_MISS) ? 1 : 0;
+            }
+            if (res.used_predict) { predicted_queries += nqc; predict_miss_queries += nmiss; }
             if (nov == 0) {
                 if (staged) { memcpy(out_rows + q0 * k, w.h_out, rows_b); memcpy(out_dists + q0 * k, w.h_out + rows_b, dists_b); }
                 break;
             }
             if (level == 2) return set_error(LYNSE_ERR_INTERNAL, "candidate overflow on the exhaustive plan");
             fallback_queries += nov;
+            if (res.used_predict) {  // the predicted threshold was too high for some query (a miss), too low (an overflow), or the model had nothing to say: the sampled plan of the same coarse pass.  A strike against prediction alone — none against int8 or SQ7
+                allow_predict = false;
+                if (nmiss || nover) h->predict_strikes.fetch_add(1);
+                --level;
+                continue;
+            }
             if (res.used_sts) {  // the self-tightening scan overflowed (scores rising along every workgroup's chunk): the staged plan of the same coarse pass
                 allow_sts = false;
                 --level;
@@ -3009,6 +3122,11 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         if (i8c_attempted) {  // bit 6: the search STARTED on the certified int8 pass (an overflow may have sent it to the f16 pass)
             std::lock_guard<std::mutex> plk(h->prof_mu);
             h->prof.last_plan |= 64u;
+        }
+        if (predicted_queries) {
+            std::lock_guard<std::mutex> plk(h->prof_mu);
+            h->prof.predicted_queries += predicted_queries;
+            h->prof.predict_miss_queries += predict_miss_queries;
         }
     }
     return LYNSE_OK;
@@ -3084,6 +3202,98 @@ extern "C" int lynse_hip_flat_sq7_state(lynse_hip_flat* h, uint64_t* out_rows, i
     std::shared_lock<std::shared_mutex> lk(h->rw);
     if (out_rows) *out_rows = h->sq7.codes ? h->sq7.n : 0;
     if (out_strikes) *out_strikes = h->sq7_strikes.load();
+    return LYNSE_OK;
+}
+
+// The model of the predicted threshold on the host (predict.h; no device involved): tests restate it in numpy.
+extern "C" int lynse_hip_predict_z(uint64_t n, double keys_per_query, double* out_z) {
+    if (!out_z) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_z = predict_z(n, keys_per_query);
+    return LYNSE_OK;
+}
+extern "C" int lynse_hip_predict_col_stats(const int64_t* sums, uint32_t cols, uint64_t n, double* out_mu, double* out_var) {
+    if (!sums || !out_mu || !out_var) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    static_assert(sizeof(long long) == sizeof(int64_t), "64-bit sums");
+    predict_col_stats(reinterpret_cast<const long long*>(sums), cols, n, out_mu, out_var);
+    return LYNSE_OK;
+}
+extern "C" int lynse_hip_predict_threshold(const int8_t* u, const double* mu, const double* var, uint32_t cols, double z, float bq, float sq,
+                                           double* out_m, double* out_v, float* out_thr) {
+    if (!u || !mu || !var || !out_thr) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_thr = predict_threshold(u, mu, var, cols, z, bq, sq, out_m, out_v);
+    return LYNSE_OK;
+}
+
+// Diagnostics of the predicted threshold (tests/test_gpu_predict.py): what k_i8c_prep_queries computes for a batch of the predicted shape
+// — the int8 image u, B_q, s_q, m_q, v_q and the threshold, with z as the search forms it for k — and the column statistics it read.
+// Builds codes and statistics like a search of the shape would; LYNSE_ERR_UNSUPPORTED where that search would not predict.
+extern "C" int lynse_hip_flat_predict_debug(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, int8_t* out_u, double* out_mu,
+                                            double* out_var, float* out_bq, float* out_sq, double* out_m, double* out_v, float* out_thr, double* out_z,
+                                            uint32_t* out_cols) {
+    if (!h || !queries) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (nq == 0 || nq > QCHUNK) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "1..256 queries");
+    LY_TRY(use_device(h));
+    LY_WRITER(h, xlk);
+    if (h->packed_only || h->n == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no float rows");
+    LY_TRY(finalize_locked(h));
+    LY_TRY(ensure_workspace(h, 1));
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, h->n);
+    if (!predict_wanted(h, metric, nq, kk, false) || !i8c_eligible(h, metric, false, nq))
+        return set_error(LYNSE_ERR_UNSUPPORTED, "no predicted plan for this shape (FLAT-IP / cosine, 129..256 queries, k <= 32, LYNSE_HIP_PREDICT not 0)");
+    LY_TRY(ensure_i8c_codes_locked(h, metric, nq));
+    if (!i8c_codes_finite(h, metric, nq)) return set_error(LYNSE_ERR_UNSUPPORTED, "the shard holds non-finite values: no int8 pass");
+    sq7_sync_locked(h, metric, nq, false);
+    LY_TRY(predict_sync_locked(h, metric, nq, kk, false));
+    const bool sq7 = sq7_wanted(h, metric, nq, false) && sq7_ready(h);
+    const CodeSet& s = predict_code_set(h, metric, nq);
+    if (!s.stats_ready()) return set_error(LYNSE_ERR_UNSUPPORTED, "no column statistics for this code set");
+    const I8cForm form = i8c_form(h, metric, nq, false);
+    const I8cOperand opd = i8c_operand(h, form, sq7);
+    Workspace& w = cur(h).ws;
+    hipStream_t st = cur(h).stream;
+    const uint32_t qpad = 256, nslab = (opd.cols + 127) / 128;
+    LY_HIP(hipMemcpyAsync(w.Qf, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, st));
+    I8cPrepArgs p{};
+    p.Q = w.Qf; p.D = h->dim; p.qpad = qpad; p.nslab = nslab; p.nq = (uint32_t)nq; p.vmax = h->vmax; p.img = reinterpret_cast<int8_t*>(w.Q16);
+    fill_i8c_prep(p, opd, form);
+    p.sq = w.qinv; p.bq = w.qn2; p.marg2 = w.marg2; p.thr = w.thr; p.count = w.count; p.overflow = w.overflow; p.gsync = w.gsync;
+    p.pred_mu = s.mu; p.pred_var = s.var; p.pred_chk = w.pred_chk; p.pred_dbg = w.pred_dbg;
+    const double z = predict_z(h->n, predict_keys_per_query(kk));
+    p.pred_z = z;
+    hipLaunchKernelGGL(k_i8c_prep_queries, dim3(qpad), dim3(256), 0, st, p);
+    LY_HIP(hipGetLastError());
+    std::vector<int8_t> img((size_t)nslab * qpad * 128);
+    std::vector<double> dbg((size_t)nq * 2);
+    LY_HIP(hipMemcpyAsync(img.data(), w.Q16, img.size(), hipMemcpyDeviceToHost, st));
+    LY_HIP(hipMemcpyAsync(dbg.data(), w.pred_dbg, dbg.size() * 8, hipMemcpyDeviceToHost, st));
+    if (out_bq) LY_HIP(hipMemcpyAsync(out_bq, w.qn2, nq * 4, hipMemcpyDeviceToHost, st));
+    if (out_sq) LY_HIP(hipMemcpyAsync(out_sq, w.qinv, nq * 4, hipMemcpyDeviceToHost, st));
+    if (out_thr) LY_HIP(hipMemcpyAsync(out_thr, w.thr, nq * 4, hipMemcpyDeviceToHost, st));
+    LY_HIP(hipStreamSynchronize(st));
+    for (uint64_t q = 0; q < nq; ++q) {
+        if (out_m) out_m[q] = dbg[2 * q];
+        if (out_v) out_v[q] = dbg[2 * q + 1];
+        if (out_u)
+            for (uint32_t i = 0; i < s.cols; ++i) {   // (the image layout of k_i8c_prep_queries)
+                const uint32_t sl = i / 128, kc = i % 128, l = kc >> 4, e = kc & 15, pp = l ^ (((uint32_t)q >> 1) & 7);
+                out_u[q * s.cols + i] = img[(((size_t)sl * qpad + q) * 8 + pp) * 16 + e];
+            }
+    }
+    if (out_mu) memcpy(out_mu, s.h_mu.data(), (size_t)s.cols * 8);
+    if (out_var) memcpy(out_var, s.h_var.data(), (size_t)s.cols * 8);
+    if (out_z) *out_z = z;
+    if (out_cols) *out_cols = s.cols;
+    return LYNSE_OK;
+}
+// State of the predicted plan of a shard (tests, diagnostics): strikes so far (3 switch it off until the codes are fitted again) and the
+// rows the column statistics of the plain / unit-row / SQ7 code sets cover (0: not collected).
+extern "C" int lynse_hip_flat_predict_state(lynse_hip_flat* h, int* out_strikes, uint64_t* out_rows_sq8, uint64_t* out_rows_cos, uint64_t* out_rows_sq7) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    if (out_strikes) *out_strikes = h->predict_strikes.load();
+    if (out_rows_sq8) *out_rows_sq8 = h->sq8.mu ? h->sq8.colsum_n : 0;
+    if (out_rows_cos) *out_rows_cos = h->sq8c.mu ? h->sq8c.colsum_n : 0;
+    if (out_rows_sq7) *out_rows_sq7 = h->sq7.mu ? h->sq7.colsum_n : 0;
     return LYNSE_OK;
 }
 

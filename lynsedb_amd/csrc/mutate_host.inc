@@ -17,7 +17,7 @@ static int reset_derived_locked(lynse_hip_flat* h) {
     h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->n_bpm = 0;
     for (CodeSet* s : {&h->sq8, &h->sq8a, &h->sq8c, &h->sq7}) s->release();
     h->sq7_fit = 0;   // (never equal to a later sq8_fit: that counter only grows and a built SQ8 set has bumped it)
-    h->sq7_strikes.store(0); h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
+    h->sq7_strikes.store(0); h->predict_strikes.store(0); h->i8c_strikes.store(0); h->i8c_strikes_l2.store(0); h->i8c_strikes_cos.store(0);
     h->amax = h->vmax = h->vmin = 0.f; h->sv = 1.f; h->cos_degenerate = 0; h->rows_integer = 0; h->rows_nonneg = 0;
     static const uint32_t init[5] = {0u, 0u, 0x7f800000u, 0u, 0u};
     LY_HIP(hipMemcpyAsync(h->d_stats, init, sizeof init, hipMemcpyHostToDevice, st));
