@@ -245,6 +245,19 @@ int lynse_hip_flat_search_filtered_bitset_f32(lynse_hip_flat *h, const float *qu
                                               uint32_t k, int metric, const uint64_t *bitset_words,
                                               uint64_t n_words, uint64_t *out_rows, float *out_dists,
                                               uint32_t *out_counts);
+/* The same search with the BitSet words ALREADY IN THIS DEVICE'S MEMORY (d_bitset_words; what lynse_hip_fields_filter leaves behind,
+ * lynse_hip_fields_words_device) and the number of set bits below len supplied by the caller (`count`: the filter's match count, one
+ * 8-byte read-back).  The words reach the scan by a device copy instead of an upload; `count` feeds k.min(subset.len()) and the
+ * gathered / masked strategy choice exactly as the count of the host words does.  Results equal lynse_hip_flat_search_filtered_bitset_f32
+ * on the same words bit for bit.  `count` is a PRECONDITION like a buffer length: it sizes the id list the gathered strategy expands the
+ * words into, so it must be the number of set bits below len exactly (lynse_hip_fields_filter's *out_count over the same n is).  The
+ * words must hold n_words u64 and stay valid and unchanged until the call returns; rows they do not cover are out, as in the host
+ * form.  count > len is LYNSE_ERR_INVALID_ARGUMENT.  The additive metrics (ids 7-10) and k beyond a quarter of the candidate capacity keep their
+ * host-side subset plumbing: there the words are read back first. */
+int lynse_hip_flat_search_filtered_bitset_device_f32(lynse_hip_flat *h, const float *queries, uint64_t nq,
+                                                     uint32_t k, int metric, const uint64_t *d_bitset_words,
+                                                     uint64_t n_words, uint64_t count, uint64_t *out_rows,
+                                                     float *out_dists, uint32_t *out_counts);
 /* FLAT-*-SQ8 (`use_sq8`, src/storage/flat_mmap.rs:891-905, sq8_two_pass_search :5868-5926): pass 1 ranks ALL rows by the
  * integer score of their per-dimension u8 codes (u32 dot for ip, u32 squared L2 for l2 and cosine; SQ8Data :5676-5750,
  * built lazily like ensure_sq8 and rebuilt after appends) and keeps n_cand = max(20 k, 200) rows (cosine max(100 k, 500));
@@ -1022,6 +1035,94 @@ int lynse_hip_text_search(lynse_hip_text *h, const uint64_t *q_ptr /* nq+1 */, c
                           uint64_t *out_passed /* nq, may be NULL */);
 int lynse_hip_text_profile_enable(lynse_hip_text *h, int on);
 int lynse_hip_text_profile_get(lynse_hip_text *h, lynse_hip_profile *out, int reset);
+
+/* ---- field filters: FieldStore::query_from_index (src/storage/field_store.rs:1527-1590) ---- */
+
+/* FIELD FILTERS (`where=`).  The reference answers a `where` string from in-memory maps of value -> ids when the string is one of the
+ * four forms of query_from_index, and hands everything else to third-party SQL (ApexBase), which this library does not have.  Here the
+ * fields are typed COLUMNS in HBM, row-aligned with a shard, and one kernel (k_field_filter) evaluates the compiled predicate for every
+ * row and writes the reference's BitSet words.  The caller parses the string (lynsedb_amd/fields.py follows the reference's parsers
+ * function for function) and owns the string dictionaries; the library holds columns and evaluates leaves.  The rules:
+ *  1. A column (lynse_hip_fields_set_column, replaces the whole column `column` < 4096): per row a one-byte tag and an 8-byte payload.
+ *       LYNSE_FIELD_MISSING 0  the row does not carry the field          LYNSE_FIELD_NULL 1   JSON null
+ *       LYNSE_FIELD_BOOL 2     payload 0 / 1                              LYNSE_FIELD_INT 3    payload = the i64 (IndexKey::Int)
+ *       LYNSE_FIELD_FLOAT 4    payload = normalize_f64_bits (:223-230: b | 1 << 63 for a clear sign bit, ~b otherwise; -0.0 and +0.0
+ *                              are different keys)                        LYNSE_FIELD_STR 5    payload = a u32 code into the caller's dictionary
+ *       LYNSE_FIELD_ARRAY 6    payload = the row's index a into arr_ptr (u64[n_arrays + 1]): its elements are (elem_tags, elem_payloads)
+ *                              [arr_ptr[a], arr_ptr[a + 1]), scalars only (nested arrays and objects are skipped by the caller, :486-491)
+ *       LYNSE_FIELD_OBJECT 7   never matched
+ *     Checked on the host before any device work (LYNSE_ERR_INVALID_ARGUMENT, the column unchanged): tags <= 7, element tags 1 .. 5,
+ *     an ARRAY row's payload < n_arrays, arr_ptr[0] == 0 and non-decreasing.  n == 0 drops the column.
+ *  2. A leaf (lynse_hip_field_leaf) names a column; column == LYNSE_FIELD_NO_COLUMN or a column never set is a field no row carries
+ *     and matches nothing (this library's rule: the reference asks SQL).  Kinds:
+ *       EQ        tag == key_tag && payload == key.  Equality is equality of keys of one variant: Int 1 is not Float 1.0, `= null`
+ *                 matches a stored null and not a missing field.
+ *       NUM_RANGE (a number literal; key = its normalised bits) INT rows compare as normalize_f64_bits((double)i) — an integer beyond
+ *                 2^53 rounds as `as f64` rounds it — FLOAT rows by their payload; unsigned order of the bits = RangeKey::Number's order.
+ *                 By RangeKey's derived order every Text sorts after every Number: under GT / GE every STR row passes too.  NULL, BOOL,
+ *                 MISSING, ARRAY and OBJECT rows never pass (get_range's BTreeMap path, :613-626; the dense-integer branch is the same
+ *                 answer for all-integer fields).
+ *       KEYSET    (`IN`, an OR of equalities on one field) aux = 9 u64 segment starts s[0 .. 8] then aux_len payloads, those of tag t at
+ *                 [s[t], s[t + 1]) strictly ascending; s[0] == 0, non-decreasing, s[8] == aux_len <= 65,536.  A row passes if its
+ *                 (tag, payload) is a key (binary search per lane).
+ *       STRTABLE  (a text literal under a range operator; text compares bytewise) the caller evaluates the predicate over the column's
+ *                 distinct strings: aux = a bit table over codes [0, aux_len).  STR rows pass by their code's bit; flags bit 0 = every
+ *                 INT / FLOAT row passes (LT / LE: every Number is before every Text).
+ *       CONTAINS  ARRAY rows with an element (tag, payload) == (key_tag, key).
+ *  3. lynse_hip_fields_filter evaluates `combine` (LYNSE_FIELD_ALL = AND, LYNSE_FIELD_ANY = OR) of 1 .. 32 leaves for rows 0 .. n - 1;
+ *     every column named must hold exactly n rows.  It leaves ceil(n / 64) BitSet words in the handle's device memory (bit r of word
+ *     r / 64, LSB first; bits at and beyond n are zero), *out_count = the set bits (one 8-byte read-back), *out_kernel_us (may be
+ *     NULL) = the kernel's duration between two HIP events.  The leaf offsets are checked against aux_words on the host before the
+ *     launch.  n == 0: no launch, count 0.  lynse_hip_fields_words reads the words back; lynse_hip_fields_words_device gives the
+ *     device pointer for lynse_hip_flat_search_filtered_bitset_device_f32 (valid until the next filter or destroy on this handle).
+ *  4. The calls of one handle are serialised by the handle's lock.  The kernel uses vector stores and vector atomics only.
+ * Without a usable HIP device lynse_hip_fields_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+#define LYNSE_FIELD_MISSING 0
+#define LYNSE_FIELD_NULL 1
+#define LYNSE_FIELD_BOOL 2
+#define LYNSE_FIELD_INT 3
+#define LYNSE_FIELD_FLOAT 4
+#define LYNSE_FIELD_STR 5
+#define LYNSE_FIELD_ARRAY 6
+#define LYNSE_FIELD_OBJECT 7
+#define LYNSE_FIELD_LEAF_EQ 0
+#define LYNSE_FIELD_LEAF_NUM_RANGE 1
+#define LYNSE_FIELD_LEAF_KEYSET 2
+#define LYNSE_FIELD_LEAF_STRTABLE 3
+#define LYNSE_FIELD_LEAF_CONTAINS 4
+#define LYNSE_FIELD_OP_LT 0
+#define LYNSE_FIELD_OP_LE 1
+#define LYNSE_FIELD_OP_GT 2
+#define LYNSE_FIELD_OP_GE 3
+#define LYNSE_FIELD_ALL 0
+#define LYNSE_FIELD_ANY 1
+#define LYNSE_FIELD_NO_COLUMN 0xffffffffu
+#define LYNSE_FIELD_MAX_LEAVES 32
+#define LYNSE_FIELD_MAX_KEYS 65536
+typedef struct lynse_hip_field_leaf {
+    uint32_t kind;      /* LYNSE_FIELD_LEAF_* */
+    uint32_t column;
+    uint32_t op;        /* NUM_RANGE: LYNSE_FIELD_OP_* */
+    uint32_t flags;     /* STRTABLE: bit 0 = every number row passes */
+    uint32_t key_tag;   /* EQ, CONTAINS */
+    uint32_t reserved;  /* 0 */
+    uint64_t key;       /* EQ, CONTAINS: the payload; NUM_RANGE: the normalised bits of the literal */
+    uint64_t aux_off;   /* KEYSET, STRTABLE: offset of the leaf's data in `aux`, in u64 words */
+    uint64_t aux_len;   /* KEYSET: keys; STRTABLE: codes the table covers */
+} lynse_hip_field_leaf;
+typedef struct lynse_hip_fields lynse_hip_fields;
+int lynse_hip_fields_create(int device, lynse_hip_fields **out);
+int lynse_hip_fields_destroy(lynse_hip_fields *h);
+int lynse_hip_fields_set_column(lynse_hip_fields *h, uint32_t column, const uint8_t *tags /* n */, const uint64_t *payloads /* n */,
+                                uint64_t n, const uint64_t *arr_ptr /* n_arrays+1, NULL without arrays */, uint64_t n_arrays,
+                                const uint8_t *elem_tags, const uint64_t *elem_payloads);
+int lynse_hip_fields_drop_column(lynse_hip_fields *h, uint32_t column);
+int lynse_hip_fields_column_rows(lynse_hip_fields *h, uint32_t column, uint64_t *out_rows /* 0 = not set */);
+uint64_t lynse_hip_fields_hbm_bytes(lynse_hip_fields *h);
+int lynse_hip_fields_filter(lynse_hip_fields *h, uint64_t n, int combine, const lynse_hip_field_leaf *leaves, uint32_t n_leaves,
+                            const uint64_t *aux, uint64_t aux_words, uint64_t *out_count, float *out_kernel_us /* may be NULL */);
+int lynse_hip_fields_words(lynse_hip_fields *h, uint64_t *out_words, uint64_t n_words);
+int lynse_hip_fields_words_device(lynse_hip_fields *h, const uint64_t **out_d_words, uint64_t *out_n_words);
 
 /* ---- shard-node glue around a search (host only, no device work) ---- */
 

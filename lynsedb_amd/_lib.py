@@ -36,6 +36,11 @@ class Profile(C.Structure):
                 ("predicted_queries", C.c_uint64), ("predict_miss_queries", C.c_uint64)]
 
 
+class FieldLeaf(C.Structure):   # lynse_hip_field_leaf
+    _fields_ = [("kind", C.c_uint32), ("column", C.c_uint32), ("op", C.c_uint32), ("flags", C.c_uint32), ("key_tag", C.c_uint32),
+                ("reserved", C.c_uint32), ("key", C.c_uint64), ("aux_off", C.c_uint64), ("aux_len", C.c_uint64)]
+
+
 _f32p, _u32p, _u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _vp = C.c_void_p
 
@@ -112,6 +117,7 @@ SIGNATURES = {
     "lynse_hip_flat_append_f16_bits": (C.c_int, [_vp, _vp, C.c_uint64]),
     "lynse_hip_flat_search_filtered_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
     "lynse_hip_flat_search_filtered_bitset_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "lynse_hip_flat_search_filtered_bitset_device_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "lynse_hip_flat_search_f32_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp]),
     "lynse_hip_flat_search_packed_u64": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "lynse_hip_flat_search_packed_u64_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp]),
@@ -204,6 +210,15 @@ SIGNATURES = {
     "lynse_hip_sparse_search": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "lynse_hip_sparse_profile_enable": (C.c_int, [_vp, C.c_int]),
     "lynse_hip_sparse_profile_get": (C.c_int, [_vp, C.POINTER(Profile), C.c_int]),
+    "lynse_hip_fields_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_fields_destroy": (C.c_int, [_vp]),
+    "lynse_hip_fields_set_column": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "lynse_hip_fields_drop_column": (C.c_int, [_vp, C.c_uint32]),
+    "lynse_hip_fields_column_rows": (C.c_int, [_vp, C.c_uint32, _u64p]),
+    "lynse_hip_fields_hbm_bytes": (C.c_uint64, [_vp]),
+    "lynse_hip_fields_filter": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_uint32, _vp, C.c_uint64, _u64p, _f32p]),
+    "lynse_hip_fields_words": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "lynse_hip_fields_words_device": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "lynse_hip_text_weights": (C.c_int, [C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _vp, _vp]),
     "lynse_hip_text_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "lynse_hip_text_destroy": (C.c_int, [_vp]),

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
+from .fields import FieldFilter, FieldTable, parse_where
 
 _METRIC_IS_BINARY = {_lib.METRIC_HAMMING, _lib.METRIC_JACCARD, _lib.METRIC_DICE, _lib.METRIC_TANIMOTO}
 
@@ -855,6 +856,11 @@ class FlatIndex:
         check(lib.lynse_hip_flat_search_filtered_bitset_f32(self._h, _ptr(q), nq, k, m, _ptr(words) if words.size else None,
                                                             words.size, _ptr(rows), _ptr(dists), _ptr(counts)))
         return rows[:, :k], dists[:, :k], counts
+
+    def search_filtered_bitset_device_batch_arrays(self, queries, k: int, metric, d_words, n_words: int, count: int):
+        """Same with the BitSet words already in this device's memory (`d_words`: a device pointer, FieldFilter.words_device) and
+        their match count supplied by the caller (lynse_hip_flat_search_filtered_bitset_device_f32): a device copy, no upload."""
+        return self._search_f32(lib.lynse_hip_flat_search_filtered_bitset_device_f32, queries, k, metric, d_words, int(n_words), int(count))
 
     def search_filtered(self, query, k: int, metric, subset_rows):
         """-> (rows u32[], distances f32[]) among `subset_rows` only."""
@@ -1862,14 +1868,28 @@ class BitSet:
         return np.nonzero(bits)[0].astype(np.uint64)
 
 
+class ResolvedWhere:
+    """A `where=` evaluated against a collection: the predicate, the flushed rows it was evaluated over (their BitSet words are in
+    the collection's FieldFilter until its next filter), the matches among them, the matching pending rows, and the time it took."""
+    __slots__ = ("pred", "n_flat", "count", "pending", "us", "rows")
+
+    def __init__(self, pred, n_flat: int, count: int, pending: np.ndarray, us: int):
+        self.pred, self.n_flat, self.count, self.pending, self.us, self.rows = pred, n_flat, count, pending, us, None
+
+
 class Collection:
     """The search-path subset of `lynse._core.Collection` (engine.rs Collection): buffered ingest, commit, index build
     and `search / batch_search` = `search_with_precomputed_filter` (src/engine.rs:4718-4833): k inflated by the
     tombstone count, the index / flat / subset-filtered search over the flushed rows on the GPU, the pending (not yet
     flushed) rows scored with `top_k_search`, `merge_row_results`, row -> user id, `filter_tombstoned_limit`.
 
-    The reference resolves `where_expr` to a row BitSet through its field store (out of scope); the
-    precomputed filter itself is in scope and is passed here as `subset=` (a `BitSet` or an array of row indices)."""
+    The reference resolves `where_expr` to a row BitSet through its field store; the precomputed filter is passed here as `subset=` (a
+    `BitSet` or an array of row indices), and the reference's indexed filter dialect as `where=` (lynsedb_amd/fields.py):
+    the `fields` of add_items / upsert_items are kept as typed columns, row-aligned with the shard, the predicate is evaluated for the
+    flushed rows by k_field_filter on the device and for the pending rows on the host.  A search with `where=` returns exactly what
+    the same search returns with `subset=` set to the rows the filter selects.  `where=` together with `subset=` is an error.
+    `where_expr=` keeps the answer existing tests pin (NotImplementedError): `where=` is the name python/lynse/api/local_client.py
+    gives the filter, and the name this build answers."""
 
     def __init__(self, name: str, dim: int, device: Optional[int] = None, path=None):
         self._name, self._dim = name, int(dim)
@@ -1908,6 +1928,8 @@ class Collection:
         self._text_dirty = True         # the documents changed since the last upload
         self._text_ids = np.zeros(0, np.int64)   # the ids of the uploaded text rows, ascending: text row -> user id
         self._text_vocab: dict = {}     # term -> term id of the uploaded store
+        self._fields = FieldTable()     # the fields of every row as typed columns, flushed and pending rows alike (the host copy is authoritative)
+        self._field_filter = None       # FieldFilter (the device copy of the columns + k_field_filter), created by the first `where=`
 
     def name(self) -> str:
         return self._name
@@ -1922,7 +1944,7 @@ class Collection:
             raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {a.shape[1]}")
         if len(ids) != a.shape[0]:
             raise RuntimeError("ids length must match the number of vectors")
-        if fields is not None:   # the text index only (insert_documents, engine.rs:882-908): the field store and its filters are out of scope
+        if fields is not None:   # the text index (insert_documents, engine.rs:882-908) and the field columns of `where=`
             fields = list(fields)
             if len(fields) != len(ids):
                 raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match field count ({len(fields)})")
@@ -1931,8 +1953,10 @@ class Collection:
             self._index_docs(ids, fields)
         if a.shape[0] == 0:
             return
+        id_arr = np.asarray(ids, dtype=np.int64).copy()
+        self._fields.append(fields, a.shape[0])   # the columns grow with the rows (a row added without fields has every field missing)
         self._pending_vecs.append(np.array(a, dtype=np.float32, copy=True))
-        self._pending_ids.append(np.asarray(ids, dtype=np.int64).copy())
+        self._pending_ids.append(id_arr)
         self._pending_rows += a.shape[0]
         if self._pending_rows >= PENDING_INGEST_FLUSH_ROWS or self._pending_rows * self._dim * 4 >= PENDING_INGEST_FLUSH_BYTES:
             self._flush_pending()
@@ -2049,8 +2073,10 @@ class Collection:
         if old.size:
             self._flat.update_rows(rows[old].astype(np.uint64), a[old])
             self._tombstone.difference_update(ids[old].tolist())
-            if fields is not None:
+            if fields is not None:   # fields replace the row's fields only when given
                 self._index_docs(ids[old].tolist(), [fields[j] for j in old.tolist()])
+                for j in old.tolist():
+                    self._fields.set_row(int(rows[j]), fields[j])
         if new.size:
             self.add_items(a[new], ids[new], None if fields is None else [fields[j] for j in new.tolist()])
             self._flush_pending()
@@ -2086,6 +2112,7 @@ class Collection:
             new_len = self._flat.compact(keep)
             self._id_arrays = [id_map[keep]]
             assert new_len == self._id_arrays[0].size
+            self._fields.keep(keep)
         for i in self._tombstone:
             if self._sparse.pop(i, None) is not None:
                 self._sparse_dirty = True
@@ -2317,6 +2344,61 @@ class Collection:
             return subset.to_vec()
         return np.unique(np.asarray(subset, dtype=np.uint64).reshape(-1))
 
+    # -- field filters (`where=`, lynsedb_amd/fields.py) ---------------------------
+    def _resolve_where(self, where) -> ResolvedWhere:
+        """The predicate over every row: the flushed rows by k_field_filter over the device copy of the columns it names (uploaded
+        whole when they changed), the pending rows by the same compiled predicate on the host."""
+        if isinstance(where, ResolvedWhere):
+            return where
+        import time
+
+        t0 = time.perf_counter()
+        pred = parse_where(where)
+        n = len(self._flat)
+        assert self._fields.n == n + self._pending_rows, "the field columns are not aligned with the rows"
+        count = 0
+        if n:
+            if self._field_filter is None:
+                self._field_filter = FieldFilter(self._device)
+            count = self._field_filter.filter(self._fields, pred, n)
+        pending = np.zeros(0, np.uint64)
+        if self._pending_rows:
+            pending = (np.nonzero(self._fields.evaluate(pred, n, n + self._pending_rows))[0] + n).astype(np.uint64)
+        return ResolvedWhere(pred, n, count, pending, int((time.perf_counter() - t0) * 1e6))
+
+    def _where_rows(self, rw: ResolvedWhere) -> np.ndarray:
+        """The rows a resolved filter selects, ascending: the words of the flushed rows read back, then the pending rows.  What the
+        searches that keep their host-side subset plumbing take as `subset=`."""
+        if rw.rows is None:
+            flushed = BitSet(rw.n_flat, self._field_filter.words()).to_vec() if rw.n_flat and rw.count else np.zeros(0, np.uint64)
+            rw.rows = np.concatenate([flushed, rw.pending])
+        return rw.rows
+
+    def _where_subset(self, where, subset):
+        """`subset` as it was given, or the rows `where` selects; both together are an error."""
+        if where is None:
+            return subset
+        if subset is not None:
+            raise ValueError("pass the filter either as where= or as subset=, not both")
+        return self._where_rows(self._resolve_where(where))
+
+    def where_subset(self, where) -> BitSet:
+        """The rows a field filter selects, flushed and pending, as the BitSet every `subset=` accepts (the words of the flushed rows
+        read back from the device).  What `where=` does inside the searches that keep their host-side subset plumbing, and the way a
+        filter reaches `search_range`."""
+        return BitSet.from_rows(self._where_rows(self._resolve_where(where)), len(self._flat) + self._pending_rows)
+
+    def query_fields(self, where: str) -> list:
+        """`Collection.query_fields` (FieldStore::query over query_from_index + filter_current_external_ids): the user ids of the rows
+        the filter selects, flushed or pending, ascending, tombstoned ids excluded."""
+        rows = self._where_rows(self._resolve_where(where)).astype(np.int64)
+        if rows.size == 0:
+            return []
+        ids = self._user_ids(rows)
+        if self._tombstone:
+            ids = ids[~np.isin(ids, np.fromiter(self._tombstone, dtype=np.int64, count=len(self._tombstone)))]
+        return [int(i) for i in np.unique(ids)]
+
     def _pending_search(self, query: np.ndarray, k: int, subset_rows: Optional[np.ndarray]):
         """Collection::pending_search (engine.rs:3310-3361): the un-flushed rows, scored with `top_k_search`."""
         if k == 0 or self._pending_rows == 0:
@@ -2341,8 +2423,9 @@ class Collection:
         assert ids.size == n_flat + self._pending_rows
         return ids[rows]
 
-    def _base_search(self, q: np.ndarray, search_k: int, nprobe: int, subset_rows: Optional[np.ndarray]):
-        """The device part of search_with_precomputed_filter for a batch sharing one subset -> rows, dists, counts."""
+    def _base_search(self, q: np.ndarray, search_k: int, nprobe: int, subset_rows: Optional[np.ndarray], where_dev: Optional[ResolvedWhere] = None):
+        """The device part of search_with_precomputed_filter for a batch sharing one subset -> rows, dists, counts.  `where_dev`: the
+        subset is the words the field filter left on the device (the exact filtered scan takes them without a round trip)."""
         nq = q.shape[0]
         if len(self._flat) == 0 or search_k == 0:
             return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
@@ -2361,6 +2444,11 @@ class Collection:
                     return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
                 return self._ivf.search_filtered_batch_arrays(q, search_k, np_, subset_rows)
             return self._ivf.search_batch_arrays(q, search_k, np_)
+        if where_dev is not None:   # the same exact filtered scan, its BitSet words already on the device
+            if where_dev.count == 0:
+                return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
+            d_words, n_words = self._field_filter.words_device()
+            return self._flat.search_filtered_bitset_device_batch_arrays(q, search_k, self._metric, d_words, n_words, where_dev.count)
         if subset_rows is not None:  # brute_force_search_filtered (engine.rs:5541-5566): always the exact filtered scan
             if subset_rows.size == 0:
                 return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
@@ -2385,36 +2473,45 @@ class Collection:
 
     def search(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None,
                nprobe: Optional[int] = None, approx: Optional[bool] = None, eps: Optional[float] = None,
-               subset=None) -> SearchResult:
-        res = self.batch_search(np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where_expr, nprobe, subset=subset)
+               subset=None, where=None) -> SearchResult:
+        res = self.batch_search(np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where_expr, nprobe, subset=subset, where=where)
         return res[0]
 
     def search_profile(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, nprobe: Optional[int] = None,
-                       approx: Optional[bool] = None, eps: Optional[float] = None, subset=None) -> dict:
+                       approx: Optional[bool] = None, eps: Optional[float] = None, subset=None, where=None) -> dict:
         """`Collection.search_profile` (src/python/mod.rs:1240-1271 over Collection::search_with_profile, src/engine.rs:5005-5054): the
         search + a `QueryProfile` (engine.rs:6906-6919) with the reference's field names — query_kind, vector_field, index_path
         ("ann_index" / "flat_mmap_filtered" / "flat_mmap", engine.rs:5163-5177), total_vectors, filter_expression, filter_matches,
         scanned_vectors (= filter_matches or total_vectors, as estimate_scanned_vectors does, :5179-5193), result_count, filter_us, search_us,
         rerank_us, total_us.  `device` is this build's addition: what `lynse_hip_flat_profile_get` / `lynse_hip_ivf_profile_get` measured for the
         search with HIP events on the search stream (pipeline_us, scan_us, scan_launches, rows and bytes the scan launches streamed,
-        rescored_candidates, fallback_queries).  The precomputed filter is `subset=` (the field store that resolves `where_expr` is out of scope)."""
+        rescored_candidates, fallback_queries).  The precomputed filter is `subset=`; with `where=` filter_expression is the string,
+        filter_matches the rows it selects (flushed and pending), filter_us the time of the filter (column upload, kernel, count read-back
+        and the host pass over the pending rows), and index_path "flat_mmap_filtered" unless an IVF index answers."""
         import time
 
         started = time.perf_counter()
         filter_us, filter_matches = 0, None
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
+        if where is not None and subset is not None:
+            raise ValueError("pass the filter either as where= or as subset=, not both")
         if subset is not None:
             t0 = time.perf_counter()
             filter_matches = int(self._subset_rows(subset).size)
             filter_us = int((time.perf_counter() - t0) * 1e6)
+        rw = None
+        if where is not None:
+            rw = self._resolve_where(where)
+            filter_matches, filter_us = int(rw.count + rw.pending.size), rw.us
+        unfiltered = subset is None and rw is None
         target = self._ivf if self._ivf is not None else self._flat
         sq8 = self._ivf is not None and self._ivf.is_sq8
-        pq = self._ivf is None and self._pq and subset is None
-        rabitq = self._ivf is None and self._rabitq and subset is None
-        polarvec = self._ivf is None and bool(self._polarvec) and subset is None
-        hnsw = self._ivf is None and self._hnsw and subset is None
-        diskann = self._ivf is None and self._diskann and subset is None
+        pq = self._ivf is None and self._pq and unfiltered
+        rabitq = self._ivf is None and self._rabitq and unfiltered
+        polarvec = self._ivf is None and bool(self._polarvec) and unfiltered
+        hnsw = self._ivf is None and self._hnsw and unfiltered
+        diskann = self._ivf is None and self._diskann and unfiltered
         target.profile_enable(True)
         target.profile_get(reset=True)
         if sq8:
@@ -2432,7 +2529,7 @@ class Collection:
         stage_us = plv_us = hnsw_us = diskann_us = None
         t0 = time.perf_counter()
         try:
-            res = self.search(vector, k, None, nprobe, approx, eps, subset=subset)
+            res = self.search(vector, k, None, nprobe, approx, eps, subset=subset, where=rw)
         finally:
             dev = target.profile_get(reset=True)
             # IVF-*-SQ8 / SPANN-*-SQ8: the exact rerank of the pool (HIP events on the search stream); 0 for the modes without one
@@ -2455,9 +2552,9 @@ class Collection:
         search_us = int((time.perf_counter() - t0) * 1e6)
         total = int(self.shape()[0])
         profile = {"query_kind": "vector", "vector_field": "default",
-                   "index_path": "ann_index" if self._ivf is not None or hnsw or diskann else ("flat_mmap_filtered" if subset is not None else
+                   "index_path": "ann_index" if self._ivf is not None or hnsw or diskann else ("flat_mmap_filtered" if not unfiltered else
                                                                             ("pq_two_pass" if pq else ("rabitq_two_pass" if rabitq else ("polarvec_two_pass" if polarvec else "flat_mmap")))),
-                   "total_vectors": total, "filter_expression": None, "filter_matches": filter_matches,
+                   "total_vectors": total, "filter_expression": None if rw is None else rw.pred.expr, "filter_matches": filter_matches,
                    "scanned_vectors": filter_matches if filter_matches is not None else total, "result_count": len(res),
                    "filter_us": filter_us, "search_us": search_us, "rerank_us": rerank_us, "total_us": int((time.perf_counter() - started) * 1e6),
                    "device": {"pipeline_us": float(dev["total_us"]), "scan_us": float(dev["scan_us"]), "scan_launches": int(dev["scan_launches"]),
@@ -2475,9 +2572,11 @@ class Collection:
                 "profile": profile}
 
     def batch_search(self, vectors, k: Optional[int] = None, where_expr: Optional[str] = None,
-                     nprobe: Optional[int] = None, subset=None) -> list:
+                     nprobe: Optional[int] = None, subset=None, where=None) -> list:
         """Collection::batch_search (engine.rs:5352-5498): one shared filter, every query through
-        `search_with_precomputed_filter`; the flushed rows of the whole batch are scanned in ONE pass on the GPU."""
+        `search_with_precomputed_filter`; the flushed rows of the whole batch are scanned in ONE pass on the GPU.  `where=` is the
+        filter as a string of the indexed dialect (class docstring): the exact filtered scan takes its BitSet words on the device, an
+        IVF / SPANN index takes them read back as the `subset=` it accepts.  `where_expr=` keeps its refusal (existing tests pin it)."""
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved "
                                       "row filter as subset=BitSet | row indices (search_with_precomputed_filter)")
@@ -2487,10 +2586,19 @@ class Collection:
             raise RuntimeError(f"Dimension mismatch: expected {self._dim}, got {q.shape[1]}")
         from .shard_node import filter_tombstoned_limit, merge_row_results
 
+        if where is not None and subset is not None:
+            raise ValueError("pass the filter either as where= or as subset=, not both")
         subset_rows = self._subset_rows(subset)
+        where_dev = None
+        if where is not None:
+            rw = self._resolve_where(where)
+            if self._ivf is not None:
+                subset_rows = self._where_rows(rw)
+            else:
+                where_dev, subset_rows = rw, rw.pending   # (the pending rows the filter selects: what _pending_search keeps)
         tomb = np.fromiter(self._tombstone, dtype=np.uint64, count=len(self._tombstone))
         search_k = k if tomb.size == 0 else k + int(tomb.size)   # engine.rs:4735-4747
-        rows, dists, counts = self._base_search(q, search_k, int(nprobe or 0), subset_rows)
+        rows, dists, counts = self._base_search(q, search_k, int(nprobe or 0), subset_rows, where_dev)
         out = []
         for i in range(q.shape[0]):
             c = int(counts[i])
@@ -2590,8 +2698,10 @@ class Collection:
                 words = words & ~BitSet.from_rows(dead, n).words
         return words
 
-    def batch_search_sparse(self, vectors, k: Optional[int] = None, subset=None) -> list:
-        """`search_sparse` for a batch of query vectors sharing one subset, in ONE device call (this build's addition)."""
+    def batch_search_sparse(self, vectors, k: Optional[int] = None, subset=None, where=None) -> list:
+        """`search_sparse` for a batch of query vectors sharing one subset, in ONE device call (this build's addition).  `where=`: the
+        rows the field filter selects, read back and used as the subset."""
+        subset = self._where_subset(where, subset)
         k = 10 if k is None else int(k)
         if k < 0:
             raise OverflowError("can't convert negative int to unsigned")
@@ -2611,14 +2721,14 @@ class Collection:
             out.append(SearchResult(self._sparse_ids[rows[i, :c].astype(np.int64)], scores[i, :c].copy(), SPARSE_INDEX_MODE, 0, k))
         return out
 
-    def search_sparse(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, subset=None) -> SearchResult:
+    def search_sparse(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, subset=None, where=None) -> SearchResult:
         """`Collection.search_sparse` (src/python/mod.rs:1221-1237 over engine.rs:4964-5002): the ids whose sparse vector has a
         non-zero inner product with `vector`, by (score descending, id ascending), at most k (default 10); the scores are in
         `distances()`, the mode is SPARSE-FLAT-IP, the dimension 0.  Tombstoned ids are left out before the cut.  `subset=` (a BitSet
         or dense row indices) stands in for the resolved `where_expr`, as on `search`."""
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
-        return self.batch_search_sparse([vector], k, subset=subset)[0]
+        return self.batch_search_sparse([vector], k, subset=subset, where=where)[0]
 
     # -- text search (engine.rs:5056-5161, :927-1054) -------------------------------------------
     def text_len(self) -> int:
@@ -2671,9 +2781,10 @@ class Collection:
                 words = words & ~BitSet.from_rows(dead, n).words
         return words
 
-    def batch_text_search(self, texts, text_fields=None, k: Optional[int] = None, subset=None) -> list:
+    def batch_text_search(self, texts, text_fields=None, k: Optional[int] = None, subset=None, where=None) -> list:
         """`text_search` for a batch of query texts sharing one field selection and one subset, in ONE device call (this build's
-        addition)."""
+        addition).  `where=`: the rows the field filter selects, read back and used as the subset."""
+        subset = self._where_subset(where, subset)
         k = 10 if k is None else int(k)
         if k < 0:
             raise OverflowError("can't convert negative int to unsigned")
@@ -2703,7 +2814,8 @@ class Collection:
             out.append(SearchResult(self._text_ids[rows[i, :c].astype(np.int64)], scores[i, :c].copy(), TEXT_INDEX_MODE, self._dim, k))
         return out
 
-    def text_search(self, text: str, text_fields=None, k: Optional[int] = 10, where_expr: Optional[str] = None, subset=None) -> SearchResult:
+    def text_search(self, text: str, text_fields=None, k: Optional[int] = 10, where_expr: Optional[str] = None, subset=None,
+                    where=None) -> SearchResult:
         """`Collection.bm25_search` / `text_search` (src/python/mod.rs:1273-1300 over engine.rs:5060-5076 and InvertedTextIndex::search,
         :927-1054): BM25 over the `fields` given to add_items, by (score descending, id ascending), at most k; the scores are in
         `distances()`, the mode is BM25-INVERTED (BM25-SCAN and empty while no document holds text), the dimension the collection's.
@@ -2712,11 +2824,11 @@ class Collection:
         SEARCH rule 3f)."""
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
-        return self.batch_text_search([text], text_fields, k, subset=subset)[0]
+        return self.batch_text_search([text], text_fields, k, subset=subset, where=where)[0]
 
     def hybrid_search(self, vector=None, text: Optional[str] = None, k: Optional[int] = 10, where_expr: Optional[str] = None, text_fields=None,
                       fusion: str = "rrf", vector_weight: float = 1.0, text_weight: float = 1.0, rrf_k: float = 60.0,
-                      candidate_limit: Optional[int] = None, nprobe: int = 10, subset=None) -> SearchResult:
+                      candidate_limit: Optional[int] = None, nprobe: int = 10, subset=None, where=None) -> SearchResult:
         """`Collection.hybrid_search` (src/python/mod.rs:1302-1340 over engine.rs:5079-5161): the vector search and the text search,
         each with k = candidate_limit (default max(4k, k), at least k and 1), fused by reciprocal rank ("rrf") or by normalised
         weighted scores ("weighted") — `hybrid_fuse`.  A blank text with a vector is the vector leg alone.  The mode is HYBRID-RRF or
@@ -2731,11 +2843,18 @@ class Collection:
             raise RuntimeError("Invalid argument: hybrid_search requires a vector, text, or both")
         limit = max(int(candidate_limit) if candidate_limit else max(4 * k, k), k, 1)
         v_leg = t_leg = None
+        if where is not None:   # one filter for both legs: its rows are read back before either runs
+            if subset is not None:
+                raise ValueError("pass the filter either as where= or as subset=, not both")
+            where = self._resolve_where(where)
+            subset, t_subset = None, self._where_rows(where)
+        else:
+            t_subset = subset
         if vector is not None:
-            r = self.search(vector, limit, None, nprobe, subset=subset)
+            r = self.search(vector, limit, None, nprobe, subset=subset, where=where)
             v_leg = (r.ids(), r.distances())
         if has_text:
-            r = self.text_search(str(text), text_fields, limit, subset=subset)
+            r = self.text_search(str(text), text_fields, limit, subset=t_subset)
             t_leg = (r.ids(), r.distances())
         ascending = bool(lib.lynse_hip_metric_is_ascending(self._metric))
         ids, fused = hybrid_fuse(v_leg, t_leg, k, fusion, vector_weight, text_weight, rrf_k, ascending)
@@ -2747,7 +2866,9 @@ class Collection:
         of every flushed, non-deleted row with the collection's metric, whatever index is built; the rows with distance <= threshold
         (ip: score >= threshold), at most `max_results` of them, best first -> (ids, distances) as a list of ints and a list of floats.
         Rows still in the pending buffer are not searched (the reference reads the vector store only).  Ties at the cut and in the
-        order go by ascending row.  `subset=` (a BitSet or row indices) is this build's addition, as on `search`."""
+        order go by ascending row.  `subset=` (a BitSet or row indices) is this build's addition, as on `search`.  This method's
+        parameter list is pinned (tests/test_range_search_modes.py), so it has no `where=` keyword of its own: a field filter goes in
+        as `subset=collection.where_subset("...")`."""
         max_results = int(max_results)
         if max_results == 0:   # engine.rs:6416-6418, before the dimension check
             return [], []

@@ -36,6 +36,7 @@
 #include "additive.h"
 #include "sparse.h"
 #include "text.h"
+#include "fields.h"
 #include "spann.h"
 #include "mutate.h"
 #include "predict.h"
@@ -2739,27 +2740,30 @@ static int prof_accumulate(lynse_hip_flat* h, lynse_hip_flat::Ctx& cx, hipEvent_
 static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_queries, uint64_t nq, uint32_t k,
                             int metric, uint64_t* out_rows, float* out_dists, uint32_t* out_counts,
                             bool on_device, hipStream_t user_stream, const uint64_t* subset, uint64_t n_subset,
-                            bool filtered, const uint64_t* bitset_words, uint64_t n_words, bool caller_holds_exclusive, bool force_shadow);
+                            bool filtered, const uint64_t* bitset_words, uint64_t n_words, bool caller_holds_exclusive, bool force_shadow,
+                            bool words_on_device);
 static int search_impl(lynse_hip_flat* h, const void* q_src, bool packed_queries, uint64_t nq, uint32_t k,
                        int metric, uint64_t* out_rows, float* out_dists, uint32_t* out_counts,
                        bool on_device, hipStream_t user_stream, const uint64_t* subset = nullptr, uint64_t n_subset = 0,
                        bool filtered = false, const uint64_t* bitset_words = nullptr, uint64_t n_words = 0,
-                       bool caller_holds_exclusive = false) {
+                       bool caller_holds_exclusive = false, bool words_on_device = false) {
     int rc = search_impl_once(h, q_src, packed_queries, nq, k, metric, out_rows, out_dists, out_counts, on_device, user_stream, subset, n_subset,
-                              filtered, bitset_words, n_words, caller_holds_exclusive, false);
+                              filtered, bitset_words, n_words, caller_holds_exclusive, false, words_on_device);
     // (a batch that started on the int8 pass under the shared lock and now needs the f16 shadow — an overflow, or a last chunk of a
     // different shape: once more from the top, under the writer lock, with the shadow built first)
     if (rc == LY_RESTART_EXCLUSIVE)
         rc = search_impl_once(h, q_src, packed_queries, nq, k, metric, out_rows, out_dists, out_counts, on_device, user_stream, subset, n_subset,
-                              filtered, bitset_words, n_words, caller_holds_exclusive, true);
+                              filtered, bitset_words, n_words, caller_holds_exclusive, true, words_on_device);
     return rc;
 }
 static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_queries, uint64_t nq, uint32_t k,
                             int metric, uint64_t* out_rows, float* out_dists, uint32_t* out_counts,
                             bool on_device, hipStream_t user_stream, const uint64_t* subset, uint64_t n_subset,
-                            bool filtered, const uint64_t* bitset_words, uint64_t n_words, bool caller_holds_exclusive, bool force_shadow) {
+                            bool filtered, const uint64_t* bitset_words, uint64_t n_words, bool caller_holds_exclusive, bool force_shadow,
+                            bool words_on_device) {
     // filtered: the subset is either a list of row ids (`subset`, n_subset) or BitSet words (`bitset_words`; n_subset =
-    // number of set bits below len, counted by the caller)
+    // number of set bits below len, counted by the caller).  words_on_device: the words are in this device's memory already
+    // (lynse_hip_flat_search_filtered_bitset_device_f32): they reach the mask by a device copy
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     LY_TRY(metric_check(metric));
     if (nq == 0) return LYNSE_OK;
@@ -2806,6 +2810,13 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
         return (filtered ? std::min<uint64_t>(kk0, n_subset) : kk0) > h->cap / 4;
     };
     auto go_large_k = [&]() {
+        if (filtered && words_on_device) {   // (the row-range views take their subset from host words: read them back)
+            std::vector<uint64_t> host_words(std::max<uint64_t>(1, n_words), 0ull);
+            if (n_words && hipMemcpy(host_words.data(), bitset_words, (size_t)n_words * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                return set_error(LYNSE_ERR_DEVICE, "hipMemcpy of the device BitSet words failed");
+            return search_large_k(h, q_src, packed_queries, nq, k, metric, out_rows, out_dists, out_counts, on_device, user_stream,
+                                  subset, n_subset, true, host_words.data(), n_words);
+        }
         return filtered ? search_large_k(h, q_src, packed_queries, nq, k, metric, out_rows, out_dists, out_counts, on_device, user_stream,
                                          subset, n_subset, true, bitset_words, n_words)
                         : search_large_k(h, q_src, packed_queries, nq, k, metric, out_rows, out_dists, out_counts, on_device, user_stream);
@@ -2911,7 +2922,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
                 fc.subset_cap = n_subset;
             }
             uint32_t* d_counts = fc.d_mask + words32;
-            LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, nw * 8, hipMemcpyHostToDevice, st0));
+            LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, nw * 8, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
             const uint64_t* d_words = reinterpret_cast<const uint64_t*>(fc.d_mask);
             hipLaunchKernelGGL(k_bits_count, dim3(nblocks), dim3(256), 0, st0, d_words, nw, h->n, d_counts);
             hipLaunchKernelGGL(k_bits_offsets, dim3(1), dim3(1024), 0, st0, d_counts, nblocks);
@@ -2944,7 +2955,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             LY_HIP(hipMemsetAsync(fc.d_mask, 0, fc.mask_words * 4, st0));
             if (bitset_words) {  // the caller's BitSet words ARE the mask (u64 LE = two u32 words); bits >= len never match a row
                 const uint64_t bytes = std::min<uint64_t>(n_words * 8, (h->n + 63) / 64 * 8);
-                LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, bytes, hipMemcpyHostToDevice, st0));
+                LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, bytes, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
             } else {
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_subset + 255) / 256, (uint64_t)h->num_cu * 8);
                 hipLaunchKernelGGL(k_mask_build, dim3(std::max<uint32_t>(blocks, 1)), dim3(256), 0, st0, fc.d_subset, n_subset, h->n, fc.d_mask);
@@ -3799,4 +3810,5 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "additive_host.inc"
 #include "sparse_host.inc"
 #include "text_host.inc"
+#include "fields_host.inc"
 #include "mutate_host.inc"
