@@ -4,20 +4,17 @@ never / auto from 4M rows): prep -> one threshold stage over every row on a thre
 distance bits, with the CPU oracle and with the same handle answered with LYNSE_HIP_PREDICT=0; `last_plan` bit 28 tells which plan ran.
 """
 import math
-import os
 
 import numpy as np
 import pytest
 
 import oracle as O
 from conftest import oracle_for_every_query
+from predict_common import (CAP, PLAN_I8C, PLAN_PREDICT, PLAN_SAMPLED, PLAN_SQ7, PLAN_THR_ONLY, admitted, assert_exact, assert_predicted,  # noqa: F401
+                            assert_same, between_clusters, build, check_inputs, clustered, knobs, perturbed, planted_tail, search, stages)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-PLAN_SAMPLED, PLAN_THR_ONLY, PLAN_I8C = 1, 2, 4
-PLAN_SQ7, PLAN_PREDICT = 1 << 26, 1 << 28
-CAP = 16384   # keys per query the candidate buffer holds (the default plan)
 
 
 @pytest.fixture(scope="module")
@@ -26,95 +23,6 @@ def L():
 
     assert L_._lib.device_count() >= 1
     return L_
-
-
-class knobs:
-    """LYNSE_HIP_PREDICT / LYNSE_HIP_SQ7 for the duration of a block (None: unset)."""
-
-    def __init__(self, predict, sq7=0):
-        self.want = {"LYNSE_HIP_PREDICT": predict, "LYNSE_HIP_SQ7": sq7}
-
-    def __enter__(self):
-        self.old = {k: os.environ.pop(k, None) for k in self.want}
-        for k, v in self.want.items():
-            if v is not None:
-                os.environ[k] = str(v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def search(idx, queries, k, metric, predict, sq7=0):
-    """One profiled blocking batch -> (rows, dists, counts, profile)."""
-    with knobs(predict, sq7):
-        idx.profile_enable(True)
-        idx.profile_get(reset=True)
-        r, d, c = idx.search_batch_arrays(queries, k, metric)
-        return r, d, c, idx.profile_get(reset=True)
-
-
-def stages(p):
-    return (int(p["last_plan"]) >> 8) & 0xff
-
-
-def assert_exact(want, rows, dists, counts, tag):
-    for qi, (e_ids, e_d) in enumerate(want):
-        c = int(counts[qi])
-        assert c == len(e_ids), (tag, qi, c, len(e_ids))
-        assert np.array_equal(dists[qi, :c].view(np.uint32), e_d.view(np.uint32)), (tag, qi, dists[qi, :c], e_d)
-        assert np.array_equal(rows[qi, :c].astype(np.uint64), e_ids.astype(np.uint64)), (tag, qi, rows[qi, :c], e_ids)
-
-
-def assert_same(a, b, tag):
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and np.array_equal(a[2], b[2]), tag
-
-
-def build(L, data):
-    idx = L.FlatIndex(None, data.shape[1])
-    idx.write(data)
-    idx.finalize()
-    return idx
-
-
-def assert_predicted(p, nq, tag):
-    lp = int(p["last_plan"])
-    assert lp & PLAN_PREDICT and lp & PLAN_I8C and not lp & (PLAN_SAMPLED | PLAN_THR_ONLY), (tag, hex(lp))
-    assert stages(p) == 1 and p["scan_launches"] == 1 and ((lp >> 16) & 0xff) == 0x81, (tag, p)
-    assert p["fallback_queries"] == 0 and p["predicted_queries"] == nq and p["predict_miss_queries"] == 0, (tag, p)
-
-
-def admitted(idx, data, queries, k, metric, sq7=0):
-    """Rows per query whose exact score reaches the predicted threshold (numpy, f32 matmul in blocks; cosine: similarity - 1)."""
-    with knobs(1, sq7):
-        dbg = idx.predict_debug(queries, k, metric)
-    q = queries.astype(f32)
-    if metric == "cosine":
-        q = q / np.linalg.norm(q.astype(np.float64), axis=1, keepdims=True).astype(f32)
-    cnt = np.zeros(len(q), np.int64)
-    for r0 in range(0, len(data), 65536):
-        blk = data[r0:r0 + 65536]
-        if metric == "cosine":
-            blk = blk / np.maximum(np.linalg.norm(blk, axis=1, keepdims=True), f32(1e-30))
-        s = q @ blk.T - (f32(1.0) if metric == "cosine" else f32(0.0))
-        cnt += (s >= dbg["thr"][:, None]).sum(axis=1)
-    return cnt, dbg
-
-
-def check_inputs(idx, data, queries, k, metric, sq7=0):
-    """Before relying on "no fallback": the predicted threshold admits comfortably >= k and <= cap rows for every query of the set
-    (a factor 3 either way stands in for the int8 margin, which moves a row's coarse score by a fraction of the threshold's distance
-    to the k-th best)."""
-    cnt, dbg = admitted(idx, data, queries, k, metric, sq7)
-    assert cnt.min() >= 3 * k and cnt.max() <= CAP // 3, (metric, k, int(cnt.min()), int(cnt.max()))
-    return cnt, dbg
-
-
-def perturbed(rng, data, nq, eps):
-    rows = np.sort(rng.choice(len(data), nq, replace=False))
-    return (data[rows] + eps * rng.standard_normal((nq, data.shape[1])).astype(f32)).astype(f32)
 
 
 # ---- parity and plan: one shard and one oracle answer per (distribution, size, width), shared by the batch sizes
@@ -252,21 +160,6 @@ def test_cosine_over_non_negative_rows_is_a_systematic_miss(L, oracle):
     assert cnt.max() < k, int(cnt.max())
 
 
-def clustered(rng, n, dim, blocks):
-    """Clusters on disjoint coordinate blocks: a row of cluster j is 1 + noise on block j and noise elsewhere — the columns of different
-    blocks are NEGATIVELY correlated, which the diagonal model does not know."""
-    data = (0.1 * rng.standard_normal((n, dim))).astype(f32)
-    w = dim // blocks
-    lab = rng.integers(0, blocks, n)
-    for j in range(blocks):
-        data[lab == j, j * w:(j + 1) * w] += f32(1.0)
-    return data
-
-
-def between_clusters(rng, nq, dim):
-    return (1.0 + 0.02 * rng.standard_normal((nq, dim))).astype(f32)      # equal weight on every cluster's block
-
-
 def test_clustered_shard_with_queries_between_the_clusters(L, oracle):
     """Every row scores about dim / blocks against a query that weighs all blocks alike, so the true spread is the noise alone, while the
     diagonal model adds the block variances up: its tail — and the threshold — lies far above every row.  Nothing is emitted."""
@@ -284,15 +177,7 @@ def test_fewer_than_k_rows_above_the_prediction(L, oracle):
     above ~2.5 sigma holds the five planted rows only — fewer than k.  The other queries are unrelated directions and predict fine."""
     rng = np.random.default_rng(2723)
     n, dim, nq, k = 70_000, 256, 130, 10
-    data = rng.standard_normal((n, dim)).astype(f32)
-    q0 = rng.standard_normal(dim).astype(f32)
-    qn = q0.astype(np.float64) / np.linalg.norm(q0.astype(np.float64))
-    s = data.astype(np.float64) @ qn                                         # unit-variance scores along q0
-    high = np.flatnonzero(s > 1.2)
-    keep = rng.choice(high, 5, replace=False)
-    push = np.setdiff1d(high, keep)
-    data[push] -= np.outer(s[push] - rng.uniform(0.0, 1.2, len(push)), qn).astype(f32)
-    data[keep] += np.outer(4.0 - s[keep] + 0.1 * np.arange(5), qn).astype(f32)      # the planted five: far out, distinct scores
+    data, q0, keep = planted_tail(rng, n, dim)
     queries = rng.standard_normal((nq, dim)).astype(f32)
     queries[0] = q0
     idx, rp, want = miss_case(L, oracle, data, queries, k, "ip", "planted tail")
