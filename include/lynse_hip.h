@@ -1124,6 +1124,46 @@ int lynse_hip_fields_filter(lynse_hip_fields *h, uint64_t n, int combine, const 
 int lynse_hip_fields_words(lynse_hip_fields *h, uint64_t *out_words, uint64_t n_words);
 int lynse_hip_fields_words_device(lynse_hip_fields *h, const uint64_t **out_d_words, uint64_t *out_n_words);
 
+/* ---- named vector fields: create_vector_field / add_named_vectors / search_vector_field (src/engine.rs:4042-4420, :4836-4960) ---- */
+
+/* NAMED VECTOR FIELDS.  A named field is a further vector per record with its own dimension, metric and dtype; its shard is an
+ * ordinary lynse_hip_flat handle (the caller owns it and the field row -> user id map).  A field's rows are a SUBSET of the
+ * collection's rows in ANOTHER ORDER, so a filter over collection rows (lynse_hip_fields_filter's BitSet words, or a caller's subset)
+ * has to be renumbered before the field's filtered scan can take it.  The reference ranks every row of the field and drops the
+ * disallowed ones on the host (search_k = id_map.len(), :4881-4947); here one kernel (k_bitset_remap) rewrites the words on the device
+ * and lynse_hip_flat_search_filtered_bitset_device_f32 takes them without a round trip.  The rules:
+ *  1. lynse_hip_rowmap_set uploads row_of (u32[n_out], n_out < 2^32 - 1) WHOLE: field row r belongs to collection row row_of[r];
+ *     LYNSE_ROWMAP_NONE (0xffffffff) = to none.  It replaces the earlier map and drops the words of an earlier remap.  The host keeps
+ *     1 + the largest entry that is not NONE (lynse_hip_rowmap_len reports it with n_out).
+ *  2. lynse_hip_rowmap_remap takes the source mask in two parts: `src_words` covering n_src bits (the flushed collection rows; a
+ *     pointer into this device's memory when src_on_device != 0, e.g. what lynse_hip_fields_words_device returns, else host memory,
+ *     which is uploaded) and optionally `tail_words` in host memory covering n_tail bits (the pending collection rows: the caller
+ *     evaluates those itself), numbered n_src .. n_src + n_tail - 1.  Output bit r = source bit row_of[r]; NONE gives 0.  It leaves
+ *     ceil(n_out / 64) BitSet words in the handle's device memory (bit r of word r / 64, LSB first; bits at and beyond n_out are
+ *     zero), *out_count = the set bits (one 8-byte read-back), *out_kernel_us (may be NULL) = the kernel's duration between two HIP
+ *     events.  n_out == 0: no launch, no words, count 0.
+ *  3. Checked on the host before anything is uploaded or launched (LYNSE_ERR_INVALID_ARGUMENT, nothing launched, the handle still
+ *     usable): a map has been set; n_src_words == ceil(n_src / 64) and n_tail_words == ceil(n_tail / 64); n_src + n_tail < 2^32;
+ *     every row_of entry is NONE or < n_src + n_tail.  A device `src_words` must hold n_src_words words: that is the caller's
+ *     contract, as for lynse_hip_flat_search_filtered_bitset_device_f32.
+ *  4. lynse_hip_rowmap_words reads the words back; lynse_hip_rowmap_words_device gives the device pointer (valid until the next
+ *     set, remap or destroy on this handle).  When row_of is the identity over n_out == n_src rows and there is no tail, the
+ *     remapped words ARE the source words: callers may skip the remap and hand the source words on (lynsedb_amd does).
+ *  5. The calls of one handle are serialised by the handle's lock.  The kernel uses vector stores and vector atomics only, no LDS.
+ * Without a usable HIP device lynse_hip_rowmap_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+#define LYNSE_ROWMAP_NONE 0xffffffffu
+typedef struct lynse_hip_rowmap lynse_hip_rowmap;
+int lynse_hip_rowmap_create(int device, lynse_hip_rowmap **out);
+int lynse_hip_rowmap_destroy(lynse_hip_rowmap *h);
+int lynse_hip_rowmap_set(lynse_hip_rowmap *h, const uint32_t *row_of /* n_out */, uint64_t n_out);
+int lynse_hip_rowmap_len(lynse_hip_rowmap *h, uint64_t *out_rows, uint64_t *out_bound /* 1 + the largest entry, 0 without one */);
+uint64_t lynse_hip_rowmap_hbm_bytes(lynse_hip_rowmap *h);
+int lynse_hip_rowmap_remap(lynse_hip_rowmap *h, const uint64_t *src_words, uint64_t n_src_words, uint64_t n_src, int src_on_device,
+                           const uint64_t *tail_words /* host; NULL when n_tail == 0 */, uint64_t n_tail_words, uint64_t n_tail,
+                           uint64_t *out_count, float *out_kernel_us /* may be NULL */);
+int lynse_hip_rowmap_words(lynse_hip_rowmap *h, uint64_t *out_words, uint64_t n_words);
+int lynse_hip_rowmap_words_device(lynse_hip_rowmap *h, const uint64_t **out_d_words, uint64_t *out_n_words);
+
 /* ---- shard-node glue around a search (host only, no device work) ---- */
 
 /* Collection::filter_tombstoned_limit (src/engine.rs:3286-3308): drop the tombstoned ids, keep the order, at most

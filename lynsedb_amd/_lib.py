@@ -219,6 +219,14 @@ SIGNATURES = {
     "lynse_hip_fields_filter": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, C.c_uint32, _vp, C.c_uint64, _u64p, _f32p]),
     "lynse_hip_fields_words": (C.c_int, [_vp, _vp, C.c_uint64]),
     "lynse_hip_fields_words_device": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
+    "lynse_hip_rowmap_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "lynse_hip_rowmap_destroy": (C.c_int, [_vp]),
+    "lynse_hip_rowmap_set": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "lynse_hip_rowmap_len": (C.c_int, [_vp, _u64p, _u64p]),
+    "lynse_hip_rowmap_hbm_bytes": (C.c_uint64, [_vp]),
+    "lynse_hip_rowmap_remap": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_int, _vp, C.c_uint64, C.c_uint64, _u64p, _f32p]),
+    "lynse_hip_rowmap_words": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "lynse_hip_rowmap_words_device": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "lynse_hip_text_weights": (C.c_int, [C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _vp, _vp]),
     "lynse_hip_text_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "lynse_hip_text_destroy": (C.c_int, [_vp]),

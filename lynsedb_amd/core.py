@@ -26,6 +26,9 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .fields import FieldFilter, FieldTable, parse_where
+from .vector_fields import (DEFAULT_VECTOR_FIELD_NAME, KNOWN_INDEX_MODES, ROWMAP_NONE, NamedVectorField, RowMap, field_mode_kind,
+                            normalize_field_index_mode, resolve_named_vector_metric, validate_vector_field_name, vector_dtype_name,
+                            words_of_rows)
 
 _METRIC_IS_BINARY = {_lib.METRIC_HAMMING, _lib.METRIC_JACCARD, _lib.METRIC_DICE, _lib.METRIC_TANIMOTO}
 
@@ -1930,6 +1933,8 @@ class Collection:
         self._text_vocab: dict = {}     # term -> term id of the uploaded store
         self._fields = FieldTable()     # the fields of every row as typed columns, flushed and pending rows alike (the host copy is authoritative)
         self._field_filter = None       # FieldFilter (the device copy of the columns + k_field_filter), created by the first `where=`
+        self._vfields: dict = {}        # name -> NamedVectorField (the named vector fields)
+        self._row_stamp = 0             # bumped when the id -> row resolution may have changed (flush, upsert, compact): the fields' row_of follow
 
     def name(self) -> str:
         return self._name
@@ -1979,6 +1984,7 @@ class Collection:
             self._flat.write(a)
             self._id_arrays.append(i)
         self._pending_vecs, self._pending_ids, self._pending_rows = [], [], 0
+        self._row_stamp += 1
 
     def commit(self) -> None:
         self._flush_pending()
@@ -2080,6 +2086,7 @@ class Collection:
         if new.size:
             self.add_items(a[new], ids[new], None if fields is None else [fields[j] for j in new.tolist()])
             self._flush_pending()
+        self._row_stamp += 1   # (the named fields keep their vectors: the reference's upsert paths never touch named_vector_fields)
         if old.size:
             self._rebuild_index()
 
@@ -2122,6 +2129,9 @@ class Collection:
             from .storage import save_sparse_vectors
 
             save_sparse_vectors(self._path / SPARSE_VECTORS_FILE, self._sparse)
+        if self._vfields:
+            self._compact_vector_fields(dead_ids)
+        self._row_stamp += 1
         self._tombstone.clear()
         self._rebuild_index()
         return removed
@@ -2611,6 +2621,222 @@ class Collection:
             out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), self._index_mode, self._dim, k))
         return out
 
+    # -- named vector fields (engine.rs:4042-4420, :4836-4960; lynsedb_amd/vector_fields.py) ---------------------
+    def remove_index(self) -> None:
+        """Collection::remove_index (engine.rs:6106-6143): whatever index the collection holds goes, and with it the index mode —
+        searches are the exact inner-product scan the reference falls back to without one."""
+        self._flush_pending()
+        self._ivf = None
+        self._drop_aux()
+        self._index_mode, self._metric = "FLAT-IP", _lib.METRIC_IP
+        self._index_dirty = False
+
+    def _vector_field(self, field_name: str) -> NamedVectorField:
+        name = validate_vector_field_name(field_name)
+        f = self._vfields.get(name)
+        if f is None:
+            raise RuntimeError(f"Invalid argument: vector field '{name}' does not exist")
+        return f
+
+    def create_vector_field(self, name: str, dimension: int, metric: Optional[str] = None, index_mode: Optional[str] = None,
+                            dtypes: Optional[str] = None) -> dict:
+        """`Collection.create_vector_field` (create_vector_field_with_dtype, engine.rs:4052-4121) -> the field's config.  A field takes
+        the exact FLAT modes and HNSW-{IP,L2,COS,COSINE} (an HNSW mode is built by build_vector_field_index, as in the reference);
+        every other mode the reference knows is NotImplementedError."""
+        if int(dimension) == 0:
+            raise RuntimeError("Invalid argument: vector field dimension must be greater than zero")
+        name = validate_vector_field_name(name)
+        m = resolve_named_vector_metric(metric, index_mode)
+        mode = normalize_field_index_mode(index_mode, m)
+        dtype = vector_dtype_name(dtypes, "float16" if self._flat.dtype == "f16" else "float32")
+        field_mode_kind(mode)
+        old = self._vfields.get(name)
+        if old is not None:
+            if (old.dimension, old.metric, old.index_mode, old.dtypes) == (int(dimension), m, mode, dtype):
+                return old.config()
+            raise RuntimeError(f"Invalid argument: vector field '{name}' already exists with a different configuration")
+        f = self._vfields[name] = NamedVectorField(name, int(dimension), m, mode, dtype, self._device)
+        return f.config()
+
+    def list_vector_fields(self) -> list:
+        """`Collection.list_vector_fields` (engine.rs:4125-4144): the primary vector as `default`, then the named fields by name."""
+        out = [{"name": DEFAULT_VECTOR_FIELD_NAME, "dimension": self._dim, "metric": _METRIC_NAMES[self._metric], "index_mode": self._index_mode,
+                "dtypes": "float16" if self._flat.dtype == "f16" else "float32"}]
+        return out + [self._vfields[n].config() for n in sorted(self._vfields)]
+
+    def vector_field_shape(self, field_name: str):
+        if field_name == DEFAULT_VECTOR_FIELD_NAME or not str(field_name).strip():
+            return self.shape()
+        f = self._vector_field(field_name)
+        return (len(f), f.dimension)
+
+    def _rows_of_all_ids(self, ids: np.ndarray) -> np.ndarray:
+        """The collection row of each id over flushed and pending rows (the pending rows are numbered after the flushed ones), -1 for
+        an id without one: the sorted-id lookup of update_items (_rows_of_ids) over both.  This mirror's add_items accepts an id twice
+        (the reference does not, engine.rs:3505-3512); where update_items refuses such an id, a search must still answer, so an id
+        stored in more than one row resolves to its FIRST row (the stable sort keeps the rows of one id in order)."""
+        all_ids = np.concatenate([self._id_map()] + self._pending_ids) if self._pending_rows else self._id_map()
+        rows = np.full(ids.size, -1, np.int64)
+        if all_ids.size == 0 or ids.size == 0:
+            return rows
+        order = np.argsort(all_ids, kind="stable")
+        sorted_ids = all_ids[order]
+        lo = np.minimum(np.searchsorted(sorted_ids, ids, "left"), all_ids.size - 1)
+        hit = sorted_ids[lo] == ids
+        rows[hit] = order[lo[hit]]
+        return rows
+
+    def add_named_vectors(self, field_name: str, vectors, ids: Sequence[int]) -> None:
+        """`Collection.add_named_vectors` (engine.rs:4181-4248): attaches one vector of the field to ids that exist, flushed or
+        pending.  The rows go straight to the field's shard (the reference has no pending buffer for named vectors); a failed call
+        changes nothing."""
+        f = self._vector_field(field_name)
+        a = _f32(vectors, 2, "vectors")
+        n_ids = len(ids)
+        if a.shape[1] != f.dimension:
+            raise RuntimeError(f"Dimension mismatch: expected {f.dimension}, got {a.shape[1]}")
+        if n_ids != a.shape[0]:
+            raise RuntimeError(f"Invalid argument: ids length ({n_ids}) must match n_vectors ({a.shape[0]})")
+        id_arr = np.asarray([int(i) for i in ids], dtype=np.int64)
+        seen, known = set(), self._ids_known(id_arr)
+        for i, ok in zip(id_arr.tolist(), known.tolist()):
+            if i in seen:
+                raise RuntimeError(f"Invalid argument: duplicate id {i} within named vector batch")
+            seen.add(i)
+            if not ok:
+                raise RuntimeError(f"Invalid argument: cannot add named vector for unknown id {i}")
+            if i in f.reverse:
+                raise RuntimeError(f"Invalid argument: id {i} already has a vector for field '{f.name}'")
+        if id_arr.size:
+            f.append(np.ascontiguousarray(a), id_arr)
+
+    def _field_rowmap(self, f: NamedVectorField) -> RowMap:
+        """The field's row_of on the device, rebuilt whole when the collection's rows or the field's rows changed since the last one."""
+        stamp = (self._row_stamp, len(f))
+        if f.rowmap is None:
+            f.rowmap = RowMap(self._device)
+        if f.rowmap_stamp != stamp:
+            rows = self._rows_of_all_ids(f.id_map())
+            row_of = np.where(rows < 0, ROWMAP_NONE, rows).astype(np.uint32)
+            f.rowmap.set(row_of)
+            f.rowmap_stamp = stamp
+        return f.rowmap
+
+    def _field_mask(self, f: NamedVectorField, where, subset):
+        """The filter over collection rows as BitSet words over the field's rows, on the device -> (d_words, n_words, count).
+        `where=`: k_field_filter over the flushed rows exactly as `search` resolves it, the pending rows evaluated on the host and
+        uploaded as the tail; `subset=`: its words uploaded.  Then k_bitset_remap."""
+        n_flat, n_pend = len(self._flat), self._pending_rows
+        rm = self._field_rowmap(f)
+        if where is not None:
+            rw = self._resolve_where(where)
+            tail = words_of_rows(rw.pending - np.uint64(n_flat), n_pend) if n_pend else None
+            if n_flat:
+                d_src, n_src_words = self._field_filter.words_device()
+                return rm.remap(d_src, n_flat, tail, n_pend, src_count=rw.count, n_src_words=n_src_words)
+            return rm.remap(np.zeros(0, np.uint64), 0, tail, n_pend)
+        rows = self._subset_rows(subset)
+        n = n_flat + n_pend
+        return rm.remap(words_of_rows(rows[rows < np.uint64(n)], n), n)
+
+    def batch_search_vector_field(self, field_name: str, vectors, k: Optional[int] = None, where=None, subset=None,
+                                  nprobe: Optional[int] = None, where_expr: Optional[str] = None) -> list:
+        """`search_vector_field` (engine.rs:4836-4960) for a batch sharing one filter.  Without a filter and without tombstones the
+        field's graph answers if it has one, else the exact scan of the field's shard.  With `where=` / `subset=` (collection rows) the
+        mask is rewritten into field-row space on the device (k_bitset_remap) and the exact filtered scan of the field's shard takes the
+        words without a round trip; for the additive metrics and a k beyond a quarter of the candidate capacity that entry reads the
+        REMAPPED words back itself and takes its host-side path.  Tombstones: k grows by the tombstoned ids that carry a vector in this
+        field, the host drops them and cuts to k (the reference ranks every row of the field instead).  Ties: (distance, field row)."""
+        if field_name == DEFAULT_VECTOR_FIELD_NAME or not str(field_name).strip():
+            return self.batch_search(vectors, k, where_expr, nprobe, subset=subset, where=where)
+        if where_expr:
+            raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the filter as where= or as "
+                                      "subset=BitSet | row indices")
+        f = self._vector_field(field_name)
+        k = 10 if k is None else int(k)
+        q = _f32(vectors, 2, "vectors")
+        if q.shape[1] != f.dimension:
+            raise RuntimeError(f"Dimension mismatch: expected {f.dimension}, got {q.shape[1]}")
+        if where is not None and subset is not None:
+            raise ValueError("pass the filter either as where= or as subset=, not both")
+        from .shard_node import filter_tombstoned_limit
+
+        nq = q.shape[0]
+        tomb = np.array(sorted(i for i in self._tombstone if i in f.reverse), dtype=np.uint64)
+        search_k = k + int(tomb.size)
+        empty = (np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32))
+        if len(f) == 0 or k == 0:
+            rows, dists, counts = empty
+        elif where is not None or subset is not None:
+            d_words, n_words, count = self._field_mask(f, where, subset)
+            if count == 0:
+                rows, dists, counts = empty
+            else:
+                rows, dists, counts = f.flat.search_filtered_bitset_device_batch_arrays(q, search_k, f.metric, d_words, n_words, count)
+        elif f.hnsw and not self._tombstone:   # use_field_index (engine.rs:4880): no filter and no tombstone
+            if f.hnsw_rows != len(f.flat):     # vectors were added after the build
+                f.build_hnsw()
+            rows, dists, counts = f.flat.search_hnsw_batch_arrays(q, search_k, f.metric, int(nprobe or 0))
+        else:
+            rows, dists, counts = f.flat.search_batch_arrays(q, search_k, f.metric)
+        id_map = f.id_map()
+        out = []
+        for i in range(nq):
+            c = int(counts[i])
+            ids = id_map[rows[i, :c].astype(np.int64)].astype(np.uint64)
+            ids, d_i = filter_tombstoned_limit(ids, dists[i, :c], tomb, k)
+            out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), f.index_mode, f.dimension, k))
+        return out
+
+    def search_vector_field(self, field_name: str, vector, k: Optional[int] = None, where=None, subset=None,
+                            nprobe: Optional[int] = None, where_expr: Optional[str] = None) -> SearchResult:
+        """`Collection.search_vector_field` (src/python/mod.rs:1199 over engine.rs:4836-4960); `default` or a blank name is `search`."""
+        return self.batch_search_vector_field(field_name, np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where, subset, nprobe,
+                                              where_expr)[0]
+
+    def build_vector_field_index(self, field_name: str, index_type: str, params: Optional[dict] = None) -> None:
+        """`Collection.build_vector_field_index` (engine.rs:4303-4385).  A FLAT mode of a metric the exact scan serves changes the
+        field's metric and mode and drops its graph; HNSW-{IP,L2,COS,COSINE} builds the graph over the field's rows (it is built again
+        by the first search after vectors were added).  `default` or a blank name is `build_index`."""
+        if field_name == DEFAULT_VECTOR_FIELD_NAME or not str(field_name).strip():
+            return self.build_index(index_type, params)
+        name = validate_vector_field_name(field_name)
+        mode = str(index_type).strip().upper()
+        if mode not in KNOWN_INDEX_MODES:
+            raise RuntimeError(f"Invalid argument: unknown vector field index mode '{mode}'")
+        kind = field_mode_kind(mode)
+        metric = resolve_named_vector_metric(None, mode)
+        opts = hnsw_build_options(params)   # (IndexBuildOptions::validate for every mode)
+        f = self._vector_field(name)
+        f.drop_hnsw()
+        if kind == "hnsw":
+            if len(f) == 0:
+                raise ValueError("Empty database")
+            f.build_hnsw(metric, opts)   # (a failed build leaves the field's metric, options and mode as they were, without a graph)
+        f.metric, f.index_mode = metric, mode
+
+    def remove_vector_field_index(self, field_name: str) -> None:
+        """`Collection.remove_vector_field_index` (engine.rs:4388-4422): the field's graph goes, its mode is its metric's flat mode."""
+        if field_name == DEFAULT_VECTOR_FIELD_NAME or not str(field_name).strip():
+            return self.remove_index()
+        f = self._vector_field(field_name)
+        f.drop_hnsw()
+        f.index_mode = normalize_field_index_mode(None, f.metric)
+
+    def _compact_vector_fields(self, dead_ids: np.ndarray) -> None:
+        """compact's part for the named fields (engine.rs:6543-...): the field rows of the dropped ids go, through the field handle's
+        own compact; id_map follows and a field's graph is built again."""
+        for f in self._vfields.values():
+            keep = ~np.isin(f.id_map(), dead_ids)
+            if keep.all():
+                continue
+            f.keep(keep)
+            if f.hnsw:
+                f.drop_hnsw()
+                if len(f):
+                    f.build_hnsw()
+                else:
+                    f.index_mode = normalize_field_index_mode(None, f.metric)
 
     # -- sparse vectors (engine.rs:4250-4279, :4962-5002) ---------------------------------------
     def _ids_known(self, ids: np.ndarray) -> np.ndarray:

@@ -114,4 +114,51 @@ __global__ void __launch_bounds__(FIELD_NT) k_field_filter(FieldFilterArgs a) {
     if (lane == 0 && mine) atomicAdd(a.count, (unsigned long long)mine);
 }
 
+// Named vector fields (include/lynse_hip.h NAMED VECTOR FIELDS): a field's rows are a subset of the collection's rows in
+// another order, so the BitSet words of a filter over collection rows are rewritten into field-row space.
+//   k_bitset_remap   one lane per field row, grid-stride in whole waves.  A coalesced load of row_of[r], a gather of the 8-byte source
+//                    word that holds bit row_of[r] (from `src` below n_src, from `tail` at row_of[r] - n_src above it) and a bit test;
+//                    ROWMAP_NONE gives 0.  The wave64 ballot of 64 consecutive field rows IS the output word, as in k_field_filter:
+//                    ceil(n_out / 64) words are written, bits at and beyond n_out are zero, the count is a popcount per wave and one
+//                    vector atomic per wave.  The host has checked every row_of[r] against n_src + n_tail before the launch.
+constexpr uint32_t ROWMAP_NONE = 0xFFFFFFFFu;
+
+struct BitsetRemapArgs {
+    const uint32_t* row_of;      // [n_out]
+    uint64_t n_out;
+    const uint64_t* src;         // [(n_src + 63) / 64]
+    uint64_t n_src;
+    const uint64_t* tail;        // [(n_tail + 63) / 64]; NULL when n_tail == 0
+    uint64_t n_tail;
+    uint64_t* words;             // [(n_out + 63) / 64]
+    unsigned long long* count;   // zeroed by the caller
+};
+
+__global__ void __launch_bounds__(FIELD_NT) k_bitset_remap(BitsetRemapArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n64 = (a.n_out + 63ull) & ~63ull;
+    const uint64_t step = (uint64_t)gridDim.x * FIELD_NT;
+    uint32_t mine = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * FIELD_NT + threadIdx.x; r < n64; r += step) {
+        bool pass = false;
+        if (r < a.n_out) {
+            const uint32_t j = a.row_of[r];
+            if (j != ROWMAP_NONE) {
+                if (j < a.n_src) {
+                    pass = ((a.src[j >> 6] >> (j & 63u)) & 1ull) != 0ull;
+                } else {
+                    const uint64_t t = (uint64_t)j - a.n_src;
+                    if (t < a.n_tail) pass = ((a.tail[t >> 6] >> (t & 63ull)) & 1ull) != 0ull;
+                }
+            }
+        }
+        const uint64_t b = __ballot(pass);
+        if (lane == 0) {
+            a.words[r >> 6] = b;
+            mine += (uint32_t)__popcll(b);
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(a.count, (unsigned long long)mine);
+}
+
 }  // namespace lynse

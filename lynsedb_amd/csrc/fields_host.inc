@@ -276,3 +276,184 @@ extern "C" int lynse_hip_flat_search_filtered_bitset_device_f32(lynse_hip_flat* 
     return search_impl(h, queries, false, nq, k, metric, out_rows, out_dists, out_counts, false, nullptr, nullptr, count, true,
                        d_bitset_words, n_words, false, true);
 }
+
+// ---- named vector fields: the device mask remap (include/lynse_hip.h NAMED VECTOR FIELDS, DESIGN.md §26) ----------------------------
+// A handle of its own that holds row_of (field row -> collection row) in HBM and rewrites BitSet words over collection rows into
+// BitSet words over field rows (k_bitset_remap, fields.h).  The map is uploaded whole; a remap leaves its words in the handle.
+
+struct lynse_hip_rowmap {
+    std::mutex mu;   // every call is a writer: the words are per handle
+    int device = 0;
+    uint32_t num_cu = 256;
+    hipStream_t stream = nullptr;
+    uint32_t* d_row_of = nullptr;
+    size_t row_cap = 0;
+    uint64_t n_out = 0;
+    uint64_t bound = 0;      // 1 + the largest row_of entry that is not ROWMAP_NONE, 0 without one: what n_src + n_tail must reach
+    bool has_map = false;
+    uint64_t* d_src = nullptr;   // source words given from host memory
+    size_t src_cap = 0;
+    uint64_t* d_tail = nullptr;
+    size_t tail_cap = 0;
+    uint64_t* d_words = nullptr;
+    size_t words_cap = 0;
+    uint64_t n_words = 0;
+    bool has_words = false;
+    unsigned long long* d_count = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+extern "C" int lynse_hip_rowmap_create(int device, lynse_hip_rowmap** out) {
+    if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    int ndev = 0;
+    LY_TRY(lynse_hip_device_count(&ndev));
+    if (ndev <= 0) return set_error(LYNSE_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    LY_HIP(hipSetDevice(device));
+    auto* h = new lynse_hip_rowmap();
+    h->device = device;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&h->d_count, 8);
+    if (e != hipSuccess) {
+        lynse_hip_rowmap_destroy(h);
+        return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_rowmap_create: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_rowmap_destroy(lynse_hip_rowmap* h) {
+    if (!h) return LYNSE_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (void* p : {(void*)h->d_row_of, (void*)h->d_src, (void*)h->d_tail, (void*)h->d_words, (void*)h->d_count})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return LYNSE_OK;
+}
+
+// Replaces the whole map.  A failed upload leaves the handle without a map, not with a torn one.
+extern "C" int lynse_hip_rowmap_set(lynse_hip_rowmap* h, const uint32_t* row_of, uint64_t n_out) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (n_out && !row_of) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_out >= (uint64_t)ROWMAP_NONE) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: at most 2^32 - 2 rows");
+    uint64_t bound = 0;
+    for (uint64_t r = 0; r < n_out; ++r)
+        if (row_of[r] != ROWMAP_NONE) bound = std::max<uint64_t>(bound, (uint64_t)row_of[r] + 1);
+    std::lock_guard<std::mutex> lk(h->mu);
+    LY_HIP(hipSetDevice(h->device));
+    h->has_map = false;
+    h->has_words = false;
+    h->n_words = 0;
+    LY_TRY(ivf_grow(&h->d_row_of, &h->row_cap, (size_t)std::max<uint64_t>(1, n_out)));
+    if (n_out) LY_TRY(h2d_done(h->d_row_of, row_of, (size_t)n_out * 4));
+    h->n_out = n_out;
+    h->bound = bound;
+    h->has_map = true;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_rowmap_len(lynse_hip_rowmap* h, uint64_t* out_rows, uint64_t* out_bound) {
+    if (!h || !out_rows || !out_bound) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *out_rows = h->has_map ? h->n_out : 0;
+    *out_bound = h->has_map ? h->bound : 0;
+    return LYNSE_OK;
+}
+
+extern "C" uint64_t lynse_hip_rowmap_hbm_bytes(lynse_hip_rowmap* h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return (uint64_t)h->row_cap * 4 + ((uint64_t)h->src_cap + h->tail_cap + h->words_cap) * 8;
+}
+
+extern "C" int lynse_hip_rowmap_remap(lynse_hip_rowmap* h, const uint64_t* src_words, uint64_t n_src_words, uint64_t n_src, int src_on_device,
+                                      const uint64_t* tail_words, uint64_t n_tail_words, uint64_t n_tail, uint64_t* out_count,
+                                      float* out_kernel_us) {
+    if (!h || !out_count) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out_count = 0;
+    if (out_kernel_us) *out_kernel_us = 0.f;
+    // everything the kernel indexes with, before anything is queued
+    if (n_src_words != (n_src + 63) / 64) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: n_src_words is not the word count of n_src bits");
+    if (n_tail_words != (n_tail + 63) / 64) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: n_tail_words is not the word count of n_tail bits");
+    if ((n_src_words && !src_words) || (n_tail_words && !tail_words)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_src > (uint64_t)ROWMAP_NONE || n_tail > (uint64_t)ROWMAP_NONE || n_src + n_tail > (uint64_t)ROWMAP_NONE)
+        return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: the source rows must be numbered below 2^32 - 1");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_map) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: remap before set");
+    if (h->bound > n_src + n_tail) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: a row_of entry lies at or beyond n_src + n_tail");
+    LY_HIP(hipSetDevice(h->device));
+    const uint64_t n_out = h->n_out, nw = (n_out + 63) / 64;
+    h->has_words = false;
+    h->n_words = 0;
+    if (n_out == 0) {
+        h->has_words = true;
+        return LYNSE_OK;
+    }
+    LY_TRY(ivf_grow(&h->d_words, &h->words_cap, (size_t)nw));
+    if (n_tail_words) LY_TRY(ivf_grow(&h->d_tail, &h->tail_cap, (size_t)n_tail_words));
+    if (!src_on_device && n_src_words) LY_TRY(ivf_grow(&h->d_src, &h->src_cap, (size_t)n_src_words));
+    for (hipEvent_t& e : h->ev)
+        if (!e) LY_HIP(hipEventCreate(&e));
+    hipStream_t st = h->stream;
+    auto queued = [&](hipError_t e) -> int {   // (the copies of caller memory must not outlive the call)
+        if (e == hipSuccess) return LYNSE_OK;
+        (void)hipStreamSynchronize(st);
+        return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_rowmap_remap: ") + hipGetErrorString(e));
+    };
+    if (!src_on_device && n_src_words) LY_TRY(queued(hipMemcpyAsync(h->d_src, src_words, (size_t)n_src_words * 8, hipMemcpyHostToDevice, st)));
+    if (n_tail_words) LY_TRY(queued(hipMemcpyAsync(h->d_tail, tail_words, (size_t)n_tail_words * 8, hipMemcpyHostToDevice, st)));
+    LY_TRY(queued(hipMemsetAsync(h->d_count, 0, 8, st)));
+    BitsetRemapArgs a{};
+    a.row_of = h->d_row_of;
+    a.n_out = n_out;
+    a.src = src_on_device ? src_words : h->d_src;
+    a.n_src = n_src;
+    a.tail = n_tail_words ? h->d_tail : nullptr;
+    a.n_tail = n_tail;
+    a.words = h->d_words;
+    a.count = h->d_count;
+    // (grid-stride as k_field_filter: at most 4 workgroups per CU, 262,144 rows a pass on 256 CUs)
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_out + FIELD_NT - 1) / FIELD_NT, (uint64_t)h->num_cu * 4);
+    LY_TRY(queued(hipEventRecord(h->ev[0], st)));
+    hipLaunchKernelGGL(k_bitset_remap, dim3(blocks), dim3(FIELD_NT), 0, st, a);
+    LY_TRY(queued(hipGetLastError()));
+    LY_TRY(queued(hipEventRecord(h->ev[1], st)));
+    unsigned long long count = 0;
+    LY_TRY(queued(hipMemcpyAsync(&count, h->d_count, 8, hipMemcpyDeviceToHost, st)));
+    LY_HIP(hipStreamSynchronize(st));
+    if (out_kernel_us) {
+        float ms = 0.f;
+        LY_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        *out_kernel_us = ms * 1000.0f;
+    }
+    h->n_words = nw;
+    h->has_words = true;
+    *out_count = (uint64_t)count;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_rowmap_words(lynse_hip_rowmap* h, uint64_t* out_words, uint64_t n_words) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_words || n_words != h->n_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row map: n_words is not the word count of the last remap");
+    if (n_words == 0) return LYNSE_OK;
+    if (!out_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    LY_HIP(hipSetDevice(h->device));
+    LY_HIP(hipMemcpy(out_words, h->d_words, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_rowmap_words_device(lynse_hip_rowmap* h, const uint64_t** out_d_words, uint64_t* out_n_words) {
+    if (!h || !out_d_words || !out_n_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *out_d_words = h->n_words ? h->d_words : nullptr;
+    *out_n_words = h->n_words;
+    return LYNSE_OK;
+}
