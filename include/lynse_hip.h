@@ -99,6 +99,51 @@ enum {
  * decoded rows), a packed-only handle, a row-mapped handle, a row too wide for a query and a row to share the LDS — and every other
  * entry that takes a metric id (IVF / SPANN, SQ8, PQ, RaBitQ, packed queries, the _device, submit and sharded forms, prepare,
  * coarse_scores, merge_topk_device).  Ids outside 0-10 stay LYNSE_ERR_UNKNOWN_METRIC. */
+/* THE APPROXIMATE FLAT SEARCH (Collection::search(approx = true, eps); FlatMmap::search's approx branch, src/storage/flat_mmap.rs:847-889,
+ * src/storage/approx_search.rs).  Nothing is quantised: a coarse pass reads fewer bytes of the f32 rows — some of each row's dimensions,
+ * or a cached order of the rows by their sums — and a pool of the best coarse rows is scored exactly.  One query per call, for ip, l2,
+ * cosine and ids 7-10.  The shard is ONE segment (the reference applies the size tests per <= 256 MiB segment).  eps is normalised by
+ * lynse_hip_normalize_eps first; it sizes the pool and the sample and rounds nothing here: the distances that come back are RAW, the
+ * caller merges on them and rounds last (lynse_hip_round_distances_to_eps: v / eps, roundf — half away from zero —, times eps, in f32;
+ * a non-finite value, quotient or product passes through).  big = dim > 16 and n > 65,536.  The paths, in the order they are tested:
+ *   3  ip and big.  pool = lynse_hip_approx_ip_order_pool(k, n, eps) (<= 20,000).
+ *        every query element >= 0: the pool is the `pool` rows with the LARGEST row sums, (sum descending, row ascending); every element
+ *        <= 0 (and not the case before): the SMALLEST sums, (sum ascending, row ascending).  A row with a non-finite sum is left out.
+ *        row sum: four 8-lane accumulators over chunks of 32 elements (accumulator j, lane g: element 32 c + 8 j + g), (acc0 + acc1) +
+ *        (acc2 + acc3) per lane, the lanes added 0 -> 7 from 0.0, then the dim % 32 tail elements one by one.
+ *        mixed signs (or a NaN): sample = lynse_hip_approx_hybrid_ip_sample_dims(dim, eps), pool = lynse_hip_approx_hybrid_ip_pool(k, n,
+ *        eps); sample >= dim or pool >= n FALLS BACK to the exact search.  Else the coarse score of a row is acc = 0.0; acc += ip(q[block],
+ *        row[block]) over the blocks of lynse_hip_approx_sampled_dim_blocks(dim, sample) in order, ip in the shard's IP form (below) on the
+ *        block slice; the pool is the `pool` highest coarse scores.
+ *        In all three cases the pool is scored with the single-row IP form; best k by (distance descending, row ascending).
+ *   1  l2 and cosine, any size.  norm2[row] = the single-row IP form of the row with itself, inv[row] = norm2 > 1e-30 ? 1 / sqrt(norm2) : 0;
+ *        q_norm2 / q_inv the same for the query.  dot = ip(q, row) in the shard's IP form.  l2: d = (q_norm2 + norm2[row]) - 2.0 * dot, three f32
+ *        operations, then f32::max(d, 0.0) (a NaN becomes 0.0).  cosine: q_inv <= 0 answers rows 0 .. min(k, n) - 1 at 1.0; else d =
+ *        inv[row] <= 0 ? 1.0 : 1.0 - (dot * q_inv) * inv[row].  Every row is scored; best k by (distance, row).
+ *   4  ids 7-10 and big.  sample = lynse_hip_approx_hybrid_sample_dims(dim, eps), pool = lynse_hip_approx_hybrid_pool(k, n, eps); sample >= dim or
+ *        pool >= n FALLS BACK to the exact search.  Coarse score over the blocks, each block slice in the metric's form above (THE ADDITIVE
+ *        METRICS): l1 and canberra: (0.0 + s_0 + s_1 + s_2) * scale, scale = (f32)dim / (f32)sample; chebyshev: f32::max over the blocks from
+ *        0.0; bray-curtis: ONE sequential chain over the blocks' elements in order (num += |a - b|, den += |a + b|, no lanes), then as above.
+ *        The pool is the `pool` lowest coarse scores, scored exactly in the metric's form; best k by (distance, row).
+ *   2  everything else (n <= 65,536 or dim <= 16; ip and ids 7-10).  Every row is scored exactly — ip ALWAYS in the single-row form, whatever n
+ *        and lynse_hip_flat_set_ip_form say (the exact search uses the batch-of-8 form from 4,096 rows on), ids 7-10 as the exact search
+ *        does —; best k by (distance, row).
+ * The shard's IP form: what lynse_hip_flat_set_ip_form set, LYNSE_IPFORM_AUTO = single below 4,096 rows, batch-of-8 from there on.
+ * Ties: wherever the reference leaves the order open (a selection on the score alone at the pool boundary, per-thread merges), the pool
+ * is the best `pool` rows by the canonical key (coarse score in metric order, row ascending); a NaN coarse score orders last, with the
+ * worst infinity, and -0.0 is +0.0.  Results follow the NON-FINITE VALUES rule like every search: min(k, n) entries.
+ * out_info (may be NULL) tells what ran.  Derived copies (row sums, norms, the two sum orders per (n, pool)) are built by the first search
+ * that needs them and dropped by append, update, compact and destroy.  Locking follows the additive search: the handle's lock held
+ * exclusively, context 0, refused while tickets are outstanding; a path that is the exact search's (path 2 under ids 7-10, a fall-back)
+ * runs lynse_hip_flat_search_f32 after the lock is released.  LYNSE_ERR_UNSUPPORTED: the binary metrics, an F16 shard, a packed-only
+ * handle, a row-mapped handle, a row too wide for the LDS. */
+typedef struct lynse_hip_approx_info {
+    uint32_t path;        /* 1-4 as above; 0: nothing ran (n == 0 or k == 0) */
+    uint32_t ip_case;     /* path 3: 1 = sum descending, 2 = sum ascending, 3 = hybrid; else 0 */
+    uint32_t pool;        /* rows scored exactly after the coarse pass (paths 3 and 4; else 0) */
+    uint32_t sample_dims; /* dimensions the coarse pass read per row (path 3 hybrid, path 4; else 0) */
+    uint32_t fell_back;   /* 1: the size policy sent paths 3 / 4 to the exact search */
+} lynse_hip_approx_info;
 
 /* IP accumulation form of the exact rescoring pass. */
 enum { LYNSE_IPFORM_AUTO = 0, LYNSE_IPFORM_SINGLE = 1, LYNSE_IPFORM_BATCH8 = 2,
@@ -558,6 +603,23 @@ int lynse_hip_flat_search_packed_u64_device(lynse_hip_flat *h, const uint64_t *d
                                             uint64_t nq, uint32_t k, int metric,
                                             uint64_t *d_out_rows, float *d_out_dists,
                                             uint32_t *d_out_counts, void *stream);
+/* THE APPROXIMATE FLAT SEARCH (the contract block next to the metric enum).  One query of dim f32; out_rows / out_dists hold k entries,
+ * *out_count = min(k, len) of them valid, best first, distances unrounded. */
+int lynse_hip_flat_search_approx_f32(lynse_hip_flat *h, const float *query, uint32_t k, int metric, float eps,
+                                     uint64_t *out_rows, float *out_dists, uint32_t *out_count,
+                                     lynse_hip_approx_info *out_info /* may be NULL */);
+/* normalize_eps (approx_search.rs:113-119): non-finite or <= 0 -> 1e-4, else max(eps, 1e-8). */
+float lynse_hip_normalize_eps(float eps);
+/* round_distances_to_eps (approx_search.rs:123-143), in place; eps <= 0 or NaN changes nothing. */
+void lynse_hip_round_distances_to_eps(float *dists, size_t n, float eps);
+/* The size policy of the approximate search (host only, eps already normalised): flat_mmap.rs:3739-3771, :3930-3962, :4024-4056,
+ * :3911-3927, :4003-4021 and sampled_dim_blocks, :4468-4496 (out_start / out_len hold three entries; returns the number of blocks). */
+uint64_t lynse_hip_approx_ip_order_pool(uint64_t k, uint64_t n, float eps);
+uint64_t lynse_hip_approx_hybrid_ip_pool(uint64_t k, uint64_t n, float eps);
+uint64_t lynse_hip_approx_hybrid_pool(uint64_t k, uint64_t n, float eps);
+uint32_t lynse_hip_approx_hybrid_ip_sample_dims(uint32_t dim, float eps);
+uint32_t lynse_hip_approx_hybrid_sample_dims(uint32_t dim, float eps);
+uint32_t lynse_hip_approx_sampled_dim_blocks(uint32_t dim, uint32_t sample, uint32_t *out_start, uint32_t *out_len);
 
 /* Profiling: when enabled, searches bracket the scan kernel with HIP events on its stream.  on = n > 1 times every n-th
  * search only (an event recorded between two kernels costs a few microseconds of the stream's time). */

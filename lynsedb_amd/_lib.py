@@ -36,6 +36,10 @@ class Profile(C.Structure):
                 ("predicted_queries", C.c_uint64), ("predict_miss_queries", C.c_uint64)]
 
 
+class ApproxInfo(C.Structure):   # lynse_hip_approx_info
+    _fields_ = [("path", C.c_uint32), ("ip_case", C.c_uint32), ("pool", C.c_uint32), ("sample_dims", C.c_uint32), ("fell_back", C.c_uint32)]
+
+
 class FieldLeaf(C.Structure):   # lynse_hip_field_leaf
     _fields_ = [("kind", C.c_uint32), ("column", C.c_uint32), ("op", C.c_uint32), ("flags", C.c_uint32), ("key_tag", C.c_uint32),
                 ("reserved", C.c_uint32), ("key", C.c_uint64), ("aux_off", C.c_uint64), ("aux_len", C.c_uint64)]
@@ -113,6 +117,15 @@ SIGNATURES = {
     "lynse_hip_flat_diskann_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
     "lynse_hip_vamana_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
     "lynse_hip_flat_search_range_f32": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "lynse_hip_flat_search_approx_f32": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, C.c_float, _vp, _vp, _u32p, C.POINTER(ApproxInfo)]),
+    "lynse_hip_normalize_eps": (C.c_float, [C.c_float]),
+    "lynse_hip_round_distances_to_eps": (None, [_vp, C.c_size_t, C.c_float]),
+    "lynse_hip_approx_ip_order_pool": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_float]),
+    "lynse_hip_approx_hybrid_ip_pool": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_float]),
+    "lynse_hip_approx_hybrid_pool": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_float]),
+    "lynse_hip_approx_hybrid_ip_sample_dims": (C.c_uint32, [C.c_uint32, C.c_float]),
+    "lynse_hip_approx_hybrid_sample_dims": (C.c_uint32, [C.c_uint32, C.c_float]),
+    "lynse_hip_approx_sampled_dim_blocks": (C.c_uint32, [C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "lynse_hip_flat_set_dtype": (C.c_int, [_vp, C.c_int]),
     "lynse_hip_flat_append_f16_bits": (C.c_int, [_vp, _vp, C.c_uint64]),
     "lynse_hip_flat_search_filtered_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),

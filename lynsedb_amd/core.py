@@ -190,6 +190,22 @@ ADDITIVE_FLAT_MODES = {"FLAT-L1": _lib.METRIC_L1, "FLAT-MANHATTAN": _lib.METRIC_
                        "FLAT-CHEBYSHEV": _lib.METRIC_CHEBYSHEV, "FLAT-CHEBYCHEV": _lib.METRIC_CHEBYSHEV, "FLAT-LINF": _lib.METRIC_CHEBYSHEV,
                        "FLAT-CANBERRA": _lib.METRIC_CANBERRA, "FLAT-BRAY-CURTIS": _lib.METRIC_BRAY_CURTIS,
                        "FLAT-BRAYCURTIS": _lib.METRIC_BRAY_CURTIS}
+# supports_flat_approx (src/distance/mod.rs:177-188): the metrics `search(approx=True)` takes the approximate flat search under
+APPROX_FLAT_METRICS = (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE) + ADDITIVE_METRICS
+
+
+def normalize_eps(eps: Optional[float]) -> float:
+    """normalize_eps (approx_search.rs:113-119): None, non-finite or <= 0 -> 1e-4, else max(eps, 1e-8), as f32."""
+    return float(lib.lynse_hip_normalize_eps(np.float32(np.nan if eps is None else eps)))
+
+
+def round_distances_to_eps(dists, eps: float) -> np.ndarray:
+    """round_distances_to_eps (approx_search.rs:123-143) -> a new f32 array: (v / eps).round() * eps in f32, half away from zero (not
+    numpy's half-to-even); a non-finite value, quotient or product passes through."""
+    out = np.array(dists, dtype=np.float32).reshape(-1)
+    if out.size:
+        lib.lynse_hip_round_distances_to_eps(_ptr(out), out.size, np.float32(eps))
+    return out
 
 
 def additive_mode_of(mode: str) -> Optional[int]:
@@ -545,6 +561,23 @@ class FlatIndex:
     def search_sq8_batch_arrays(self, queries, k: int, metric):
         """`FlatMmap::search(.., use_sq8 = true, ..)` — the FLAT-*-SQ8 index modes (flat_mmap.rs:891-905, :5868-5926)."""
         return self._search_f32(lib.lynse_hip_flat_search_sq8_f32, queries, k, metric)
+
+    def search_approx(self, query, k: int, metric, eps: Optional[float] = None):
+        """The approximate flat search of one query (FlatMmap::search with an ApproxSearchConfig, flat_mmap.rs:847-889; the contract
+        block of include/lynse_hip.h) -> rows u64[c], RAW distances f32[c] (round them last: round_distances_to_eps) and what ran:
+        {"path": 1-4, "ip_case": 0 | "sum_desc" | "sum_asc" | "hybrid", "pool", "sample_dims", "fell_back", "eps"}."""
+        m = metric if isinstance(metric, int) else metric_from_str(metric)
+        q = _f32(query, 1, "query")
+        if q.shape[0] != self._dim:
+            raise ValueError(f"query dimension mismatch: expected {self._dim}, got {q.shape[0]}")
+        k = int(k)
+        e = normalize_eps(eps)
+        rows, dists = np.empty(max(k, 1), np.uint64), np.empty(max(k, 1), np.float32)
+        count, info = C.c_uint32(0), _lib.ApproxInfo()
+        check(lib.lynse_hip_flat_search_approx_f32(self._h, _ptr(q), k, m, e, _ptr(rows), _ptr(dists), C.byref(count), C.byref(info)))
+        c = int(count.value)
+        return rows[:c], dists[:c], {"path": int(info.path), "ip_case": (0, "sum_desc", "sum_asc", "hybrid")[int(info.ip_case)], "pool": int(info.pool),
+                                     "sample_dims": int(info.sample_dims), "fell_back": bool(info.fell_back), "eps": e}
 
     def sq8_params(self):
         mins, scales = np.empty(self._dim, np.float32), np.empty(self._dim, np.float32)
@@ -1918,6 +1951,7 @@ class Collection:
         self._hnsw = False              # HNSW-*: a graph over the flushed rows (FlatIndex.build_hnsw); replaces and is replaced by the two above
         self._hnsw_rows = 0             # rows the graph was built over
         self._hnsw_opts: dict = {}
+        self._approx_info = None        # what the last approximate flat search ran (FlatIndex.search_approx), for search_profile
         self._diskann = False           # DISKANN-*: likewise (FlatIndex.build_diskann); at most one of the four exists
         self._diskann_rows = 0
         self._diskann_opts: dict = {}
@@ -2433,9 +2467,11 @@ class Collection:
         assert ids.size == n_flat + self._pending_rows
         return ids[rows]
 
-    def _base_search(self, q: np.ndarray, search_k: int, nprobe: int, subset_rows: Optional[np.ndarray], where_dev: Optional[ResolvedWhere] = None):
+    def _base_search(self, q: np.ndarray, search_k: int, nprobe: int, subset_rows: Optional[np.ndarray], where_dev: Optional[ResolvedWhere] = None,
+                     approx_eps: Optional[float] = None):
         """The device part of search_with_precomputed_filter for a batch sharing one subset -> rows, dists, counts.  `where_dev`: the
-        subset is the words the field filter left on the device (the exact filtered scan takes them without a round trip)."""
+        subset is the words the field filter left on the device (the exact filtered scan takes them without a round trip).
+        `approx_eps` (from _approx_eps: one unfiltered query on a plain flat collection): the approximate flat search, raw distances."""
         nq = q.shape[0]
         if len(self._flat) == 0 or search_k == 0:
             return np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32)
@@ -2477,6 +2513,9 @@ class Collection:
             return self._flat.search_rabitq_batch_arrays(q, search_k, self._metric, RABITQ_OVERSAMPLE)
         if self._polarvec:
             return self._flat.search_polarvec_batch_arrays(q, search_k, self._metric, POLARVEC_OVERSAMPLE)
+        if approx_eps is not None:   # before the SQ8 branch, as in FlatMmap::search
+            rows, dists, self._approx_info = self._flat.search_approx(q[0], search_k, self._metric, approx_eps)
+            return rows.reshape(1, -1), dists.reshape(1, -1), np.array([rows.size], np.uint32)
         if self._use_sq8() and self._metric in (_lib.METRIC_IP, _lib.METRIC_L2, _lib.METRIC_COSINE):
             return self._flat.search_sq8_batch_arrays(q, search_k, self._metric)
         return self._flat.search_batch_arrays(q, search_k, self._metric)
@@ -2484,8 +2523,21 @@ class Collection:
     def search(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None,
                nprobe: Optional[int] = None, approx: Optional[bool] = None, eps: Optional[float] = None,
                subset=None, where=None) -> SearchResult:
-        res = self.batch_search(np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where_expr, nprobe, subset=subset, where=where)
+        """`Collection.search` (src/python/mod.rs:1171-1193 over engine.rs:4718-4833).  `approx=True` takes the approximate flat search
+        (FlatIndex.search_approx) where the reference does — a metric of APPROX_FLAT_METRICS, no IVF / SPANN / HNSW / DiskANN index, no PQ /
+        RaBitQ / PolarVec index, no `subset=` / `where=` (FLAT-*-SQ8 does not stand in its way) — and is ignored everywhere else, as on an
+        F16 collection (a gap).  Pending rows and tombstones merge on the raw scores; the distances that come back are rounded
+        to multiples of eps (None, non-finite or <= 0: 1e-4; at least 1e-8), half away from zero."""
+        res = self._batch_search(np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where_expr, nprobe, subset=subset, where=where,
+                                 approx=approx, eps=eps)
         return res[0]
+
+    def _approx_eps(self, approx, eps, filtered: bool) -> Optional[float]:
+        """The normalised eps when the approximate flat search answers this collection's searches (engine.rs:4757-4798), else None."""
+        if (not approx or filtered or self._metric not in APPROX_FLAT_METRICS or self._flat.dtype == "f16" or self._ivf is not None
+                or self._hnsw or self._diskann or self._pq or self._rabitq or self._polarvec):
+            return None
+        return normalize_eps(eps)
 
     def search_profile(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, nprobe: Optional[int] = None,
                        approx: Optional[bool] = None, eps: Optional[float] = None, subset=None, where=None) -> dict:
@@ -2539,6 +2591,7 @@ class Collection:
         stage_us = plv_us = hnsw_us = diskann_us = None
         t0 = time.perf_counter()
         try:
+            self._approx_info = None
             res = self.search(vector, k, None, nprobe, approx, eps, subset=subset, where=rw)
         finally:
             dev = target.profile_get(reset=True)
@@ -2578,6 +2631,8 @@ class Collection:
             profile["device"]["hnsw"] = hnsw_us
         if diskann_us is not None:
             profile["device"]["diskann"] = diskann_us
+        if self._approx_info is not None:   # the approximate flat search answered the flushed rows
+            profile["device"]["approx"] = self._approx_info
         return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
                 "profile": profile}
 
@@ -2587,6 +2642,10 @@ class Collection:
         `search_with_precomputed_filter`; the flushed rows of the whole batch are scanned in ONE pass on the GPU.  `where=` is the
         filter as a string of the indexed dialect (class docstring): the exact filtered scan takes its BitSet words on the device, an
         IVF / SPANN index takes them read back as the `subset=` it accepts.  `where_expr=` keeps its refusal (existing tests pin it)."""
+        return self._batch_search(vectors, k, where_expr, nprobe, subset=subset, where=where)
+
+    def _batch_search(self, vectors, k, where_expr, nprobe, subset=None, where=None, approx=None, eps=None) -> list:
+        """batch_search; `approx` / `eps` are `search`'s (one query: the reference's batch_search has neither)."""
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved "
                                       "row filter as subset=BitSet | row indices (search_with_precomputed_filter)")
@@ -2608,7 +2667,8 @@ class Collection:
                 where_dev, subset_rows = rw, rw.pending   # (the pending rows the filter selects: what _pending_search keeps)
         tomb = np.fromiter(self._tombstone, dtype=np.uint64, count=len(self._tombstone))
         search_k = k if tomb.size == 0 else k + int(tomb.size)   # engine.rs:4735-4747
-        rows, dists, counts = self._base_search(q, search_k, int(nprobe or 0), subset_rows, where_dev)
+        approx_eps = self._approx_eps(approx, eps, subset is not None or where is not None)
+        rows, dists, counts = self._base_search(q, search_k, int(nprobe or 0), subset_rows, where_dev, approx_eps)
         out = []
         for i in range(q.shape[0]):
             c = int(counts[i])
@@ -2618,6 +2678,8 @@ class Collection:
                 r_i, d_i = merge_row_results(r_i, d_i, p_r, p_d, search_k, self._metric)   # engine.rs:4800-4813
             ids = self._user_ids(r_i).astype(np.uint64)
             ids, d_i = filter_tombstoned_limit(ids, d_i, tomb, k)                              # engine.rs:4819-4820
+            if approx_eps is not None:                                                         # engine.rs:4821-4823: rounded last
+                d_i = round_distances_to_eps(d_i, approx_eps)
             out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), self._index_mode, self._dim, k))
         return out
 
@@ -2741,6 +2803,9 @@ class Collection:
 
     def batch_search_vector_field(self, field_name: str, vectors, k: Optional[int] = None, where=None, subset=None,
                                   nprobe: Optional[int] = None, where_expr: Optional[str] = None) -> list:
+        return self._batch_search_vector_field(field_name, vectors, k, where, subset, nprobe, where_expr)
+
+    def _batch_search_vector_field(self, field_name: str, vectors, k, where, subset, nprobe, where_expr, approx=None, eps=None) -> list:
         """`search_vector_field` (engine.rs:4836-4960) for a batch sharing one filter.  Without a filter and without tombstones the
         field's graph answers if it has one, else the exact scan of the field's shard.  With `where=` / `subset=` (collection rows) the
         mask is rewritten into field-row space on the device (k_bitset_remap) and the exact filtered scan of the field's shard takes the
@@ -2748,7 +2813,7 @@ class Collection:
         REMAPPED words back itself and takes its host-side path.  Tombstones: k grows by the tombstoned ids that carry a vector in this
         field, the host drops them and cuts to k (the reference ranks every row of the field instead).  Ties: (distance, field row)."""
         if field_name == DEFAULT_VECTOR_FIELD_NAME or not str(field_name).strip():
-            return self.batch_search(vectors, k, where_expr, nprobe, subset=subset, where=where)
+            return self._batch_search(vectors, k, where_expr, nprobe, subset=subset, where=where, approx=approx, eps=eps)
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the filter as where= or as "
                                       "subset=BitSet | row indices")
@@ -2765,6 +2830,11 @@ class Collection:
         tomb = np.array(sorted(i for i in self._tombstone if i in f.reverse), dtype=np.uint64)
         search_k = k + int(tomb.size)
         empty = (np.zeros((nq, 0), np.uint64), np.zeros((nq, 0), np.float32), np.zeros(nq, np.uint32))
+        # the approximate flat search of the field's shard (engine.rs:4908-4924): no filter, the field's graph not in use, an f32 field
+        approx_eps = None
+        if (approx and where is None and subset is None and not (f.hnsw and not self._tombstone) and f.metric in APPROX_FLAT_METRICS
+                and f.flat.dtype != "f16"):
+            approx_eps = normalize_eps(eps)
         if len(f) == 0 or k == 0:
             rows, dists, counts = empty
         elif where is not None or subset is not None:
@@ -2777,6 +2847,9 @@ class Collection:
             if f.hnsw_rows != len(f.flat):     # vectors were added after the build
                 f.build_hnsw()
             rows, dists, counts = f.flat.search_hnsw_batch_arrays(q, search_k, f.metric, int(nprobe or 0))
+        elif approx_eps is not None:
+            r, d, _ = f.flat.search_approx(q[0], search_k, f.metric, approx_eps)
+            rows, dists, counts = r.reshape(1, -1), d.reshape(1, -1), np.array([r.size], np.uint32)
         else:
             rows, dists, counts = f.flat.search_batch_arrays(q, search_k, f.metric)
         id_map = f.id_map()
@@ -2785,14 +2858,18 @@ class Collection:
             c = int(counts[i])
             ids = id_map[rows[i, :c].astype(np.int64)].astype(np.uint64)
             ids, d_i = filter_tombstoned_limit(ids, dists[i, :c], tomb, k)
+            if approx_eps is not None:
+                d_i = round_distances_to_eps(d_i, approx_eps)
             out.append(SearchResult(ids.astype(np.int64), np.asarray(d_i, np.float32), f.index_mode, f.dimension, k))
         return out
 
     def search_vector_field(self, field_name: str, vector, k: Optional[int] = None, where=None, subset=None,
-                            nprobe: Optional[int] = None, where_expr: Optional[str] = None) -> SearchResult:
-        """`Collection.search_vector_field` (src/python/mod.rs:1199 over engine.rs:4836-4960); `default` or a blank name is `search`."""
-        return self.batch_search_vector_field(field_name, np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where, subset, nprobe,
-                                              where_expr)[0]
+                            nprobe: Optional[int] = None, where_expr: Optional[str] = None, *, approx: Optional[bool] = None,
+                            eps: Optional[float] = None) -> SearchResult:
+        """`Collection.search_vector_field` (src/python/mod.rs:1199 over engine.rs:4836-4960); `default` or a blank name is `search`.
+        `approx` / `eps`: as `search`, on the field's shard."""
+        return self._batch_search_vector_field(field_name, np.asarray(vector, dtype=np.float32).reshape(1, -1), k, where, subset, nprobe,
+                                               where_expr, approx, eps)[0]
 
     def build_vector_field_index(self, field_name: str, index_type: str, params: Optional[dict] = None) -> None:
         """`Collection.build_vector_field_index` (engine.rs:4303-4385).  A FLAT mode of a metric the exact scan serves changes the

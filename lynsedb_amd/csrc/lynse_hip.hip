@@ -34,6 +34,7 @@
 #include "diskann.h"
 #include "range.h"
 #include "additive.h"
+#include "approx.h"
 #include "sparse.h"
 #include "text.h"
 #include "fields.h"
@@ -262,6 +263,7 @@ struct PlvState;  // FLAT-*-POLARVEC<b> codes + search scratch (polarvec_host.in
 struct RangeState;  // range search scratch (range_host.inc)
 struct HnswState;  // HNSW-* graph + search scratch (hnsw_host.inc)
 struct DiskannState;  // DISKANN-* graph + search scratch (diskann_host.inc)
+struct ApproxState;  // approximate flat search: row sums, norms, sum orders (approx_host.inc)
 
 // One int8 copy of a shard's rows for the certified coarse pass (lynse_hip_flat::sq8 / sq8a / sq8c / sq7) with what the prep kernel needs
 // to certify a bound over it.
@@ -397,6 +399,7 @@ struct lynse_hip_flat {
     RangeState* range = nullptr;          // scratch of lynse_hip_flat_search_range_f32 (range_host.inc); NULL until the first one
     HnswState* hnsw = nullptr;            // HNSW-{IP,L2,COS} graph over the first hnsw->n rows (hnsw_host.inc); NULL = none
     DiskannState* diskann = nullptr;      // DISKANN-{L2,COS} graph over the first diskann->n rows (diskann_host.inc); NULL = none
+    ApproxState* approx = nullptr;        // derived copies of the approximate flat search over approx->n rows (approx_host.inc); NULL = none
 
     std::atomic<bool> profiling{false};   // (read by searches without the lock: atomics)
     std::atomic<uint32_t> prof_rate{1};              // every prof_rate-th search records its events (lynse_hip_flat_profile_enable(h, n))
@@ -410,6 +413,7 @@ static void plv_release(lynse_hip_flat* h);
 static void range_release(lynse_hip_flat* h);
 static void hnsw_release(lynse_hip_flat* h);
 static void diskann_release(lynse_hip_flat* h);
+static void approx_release(lynse_hip_flat* h);
 
 static inline bool is_f16(const lynse_hip_flat* h) { return h->dtype == LYNSE_DTYPE_F16; }
 // the row matrix the exact-scoring kernels read: f32 rows, or the f16 bits of an F16 shard handed in as float* with a pitch
@@ -551,6 +555,7 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     range_release(h);
     hnsw_release(h);
     diskann_release(h);
+    approx_release(h);
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
@@ -3659,6 +3664,7 @@ extern "C" int lynse_hip_top_k_search(const float* query, const float* candidate
         h->amax = h->vmax = h->vmin = 0.f; h->sv = 1.f; h->cos_degenerate = 0; h->rows_integer = 0; h->rows_nonneg = 0;
         const uint32_t init[5] = {0u, 0u, 0x7f800000u, 0u, 0u};
         LY_TRY(use_device(h));
+        approx_release(h);
         LY_TRY(h2d_done(h->d_stats, init, sizeof init));
     }
     int rc = lynse_hip_flat_append_f32(h, candidates, n);
@@ -3808,6 +3814,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "diskann_host.inc"
 #include "range_host.inc"
 #include "additive_host.inc"
+#include "approx_host.inc"
 #include "sparse_host.inc"
 #include "text_host.inc"
 #include "fields_host.inc"

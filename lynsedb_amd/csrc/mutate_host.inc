@@ -11,7 +11,7 @@
 //    moves one way: they and their device words start again, and the norms are cleared up to their capacity;
 //  - a code set with n = 0 that keeps its min / max table is not a new fit for a builder that merges rows into that table: the four
 //    sets are released, so the next build fits, allocates and counts (sq8_fit) as on a fresh handle.
-// The auxiliary indexes cover "the first n rows" as they were: released.  Locked by the caller (exclusive); synchronises the stream.
+// The auxiliary indexes cover "the first n rows" as they were: released, and so are the derived copies of the approximate search.  Locked by the caller (exclusive); synchronises the stream.
 static int reset_derived_locked(lynse_hip_flat* h) {
     hipStream_t st = cur(h).stream;
     h->n_stats = 0; h->n16 = 0; h->n_packed = 0; h->n_bpm = 0;
@@ -29,6 +29,7 @@ static int reset_derived_locked(lynse_hip_flat* h) {
     plv_release(h);
     hnsw_release(h);
     diskann_release(h);
+    approx_release(h);
     return LYNSE_OK;
 }
 
