@@ -473,13 +473,34 @@ int lynse_hip_flat_polarvec_stage_times(lynse_hip_flat *h, double *out3, int res
  *     leaves ties to BinaryHeap internals; here every pop, eviction and the final sort use the total order (dist, node), so results
  *     equal the reference's whenever no two visited nodes tie.  Output: the best min(k, |R|) of R by (dist, node), ip distances
  *     un-negated, in the layout of lynse_hip_flat_search_f32 (row ~0 and the worst distance after out_counts[q] entries).
- *  6. The graph covers the first n_hnsw rows: rows appended after a build or a load stay outside it.  Build and load replace an earlier
- *     graph; lynse_hip_flat_drop_hnsw removes it.  The exact searches of the handle are unchanged.
+ *  6. The graph covers the first n_hnsw rows: rows appended after a build or a load stay outside it until
+ *     lynse_hip_flat_hnsw_extend takes them in (rule 7).  Build and load replace an earlier graph; lynse_hip_flat_drop_hnsw removes
+ *     it.  The exact searches of the handle are unchanged.
+ *  7. Incremental insert: lynse_hip_flat_hnsw_extend(h, mode) leaves a graph over all rows of the handle whose
+ *     lynse_hip_flat_hnsw_params output (info, n_hnsw, levels, adj0, upper_node, upper_level, upper_adj, stored order included) equals
+ *     what lynse_hip_flat_build_hnsw gives over the same rows with the metric, m, ef_construction, ef_search, max_level and seed of the
+ *     build the graph came from: rules 1-4 make the graph a function of the rows and those, and level i is the i-th draw of one
+ *     stream.  A build keeps, in host memory, those parameters, every level's forward lists with their graph distances (8 bytes per
+ *     slot) and one threshold per (node, level): the raw score of the last of the ef_construction + 1 entries its exact search
+ *     returned, "short" when it returned fewer or that score is NaN.  For new rows N and a level l with N_l = N in S_l not empty: an
+ *     old member i is searched again when its threshold is short or some x in N_l scores against it not strictly worse than the
+ *     threshold (ties and NaN count; the score is the single-row form the search ranks by; x has a higher row number than every old
+ *     row, so it enters a list only by a strictly better score) — a superset of the members whose candidates change.  They and N_l go
+ *     through rules 2-3 over the new S_l; rule 4 is recomputed for the lists whose forward list changed or that are in
+ *     F_old(i) xor F_new(i) of such an i.  mode 0 = auto: the plain build when (n - n_hnsw) * ef_construction >= n_hnsw (the mean
+ *     in-degree of the candidate digraph is ef_construction, so most old rows are searched again from there), the incremental path
+ *     otherwise; mode 1 = always incremental; any other mode: LYNSE_ERR_INVALID_ARGUMENT.  The result is the same on either path.  No
+ *     new rows: LYNSE_OK, nothing changes.  No graph: LYNSE_ERR_INVALID_ARGUMENT.  A graph installed by lynse_hip_flat_load_hnsw:
+ *     LYNSE_ERR_UNSUPPORTED (no forward lists, no thresholds).  Every refusal of the build holds with its code and message.  A failed
+ *     extend leaves the graph as it was, still searchable.  Lock and context as for the build, the ip form pinned to SINGLE.
+ *     lynse_hip_flat_hnsw_extend_stats: out12 = {rows_before, rows_after, path (0 incremental, 1 plain build, 2 nothing to do),
+ *     new_items (sum of |N_l|), researched (old members searched again), dirty_lists, reselected (lists through the heuristic again),
+ *     scan_us (the reverse scan), cand_us, select_us, reverse_us, total_us} of the last extend.
  *  Refused with LYNSE_ERR_UNSUPPORTED: an F16 shard, a packed-only handle, a row-mapped handle, the binary and additive metrics, m or
  *  an ef outside its bounds, a build, load or search while tickets of lynse_hip_flat_search_submit_* are outstanding, a beam (24 bytes per ef, ef >= k)
  *  that does not share the 160 KiB of LDS with the query, and a build with ef_construction + 1 > 4096 over more than 16,384 rows (the
  *  exact search's candidate capacity).  A search metric other than the build metric: LYNSE_ERR_INVALID_ARGUMENT.  There is no ticket,
- *  _device, sharded, filtered or incremental form.  Build, load, drop and search hold the handle's lock exclusively and run on context 0.
+ *  _device, sharded or filtered form.  Build, load, drop and search hold the handle's lock exclusively and run on context 0.
  * lynse_hip_flat_load_hnsw takes levels[n], adj0[n][2 m], and the n_upper = sum of the levels upper lists upper_adj[n_upper][m] with
  * their upper_node[] / upper_level[] in ascending (node, level) order, lists padded with 0xFFFFFFFF, n <= the handle's rows.  It
  * answers LYNSE_ERR_INVALID_ARGUMENT unless every neighbour is < n, a neighbour of a level-l list has level >= l, the upper lists match
@@ -500,6 +521,8 @@ int lynse_hip_flat_drop_hnsw(lynse_hip_flat *h);
 int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat *h, const float *queries, uint64_t nq, uint32_t k, int metric, uint32_t ef_query,
                                    uint64_t *out_rows, float *out_dists, uint32_t *out_counts);
 int lynse_hip_flat_hnsw_stage_times(lynse_hip_flat *h, double *out6, int reset);
+int lynse_hip_flat_hnsw_extend(lynse_hip_flat *h, int mode);
+int lynse_hip_flat_hnsw_extend_stats(lynse_hip_flat *h, double *out12);
 int lynse_hip_hnsw_levels(uint64_t seed, uint32_t m, int32_t max_level, uint64_t n, uint32_t *out);
 /* DISKANN-{L2,COS,COSINE} (DiskANNIndex, src/index/diskann.rs, its in-memory full-precision form: search_graph over the rows
  * themselves): a flat neighbour graph of degree r over the rows of a FLAT handle, built by the reference's batched Vamana passes and

@@ -108,6 +108,8 @@ SIGNATURES = {
     "lynse_hip_flat_drop_hnsw": (C.c_int, [_vp]),
     "lynse_hip_flat_search_hnsw_f32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp]),
     "lynse_hip_flat_hnsw_stage_times": (C.c_int, [_vp, _vp, C.c_int]),
+    "lynse_hip_flat_hnsw_extend": (C.c_int, [_vp, C.c_int]),
+    "lynse_hip_flat_hnsw_extend_stats": (C.c_int, [_vp, _vp]),
     "lynse_hip_hnsw_levels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int32, C.c_uint64, _vp]),
     "lynse_hip_flat_build_diskann": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint64, C.c_uint64]),
     "lynse_hip_flat_load_diskann": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32]),

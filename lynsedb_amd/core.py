@@ -738,10 +738,28 @@ class FlatIndex:
     # -- HNSW-* (HNSWIndex, src/index/hnsw.rs; include/lynse_hip.h states the contract) ---------------------------------------
     def build_hnsw(self, metric, m: int = HNSW_DEFAULTS["m"], ef_construction: int = HNSW_DEFAULTS["ef_construction"],
                    ef_search: int = HNSW_DEFAULTS["ef_search"], max_level: Optional[int] = None, seed: int = HNSW_SEED) -> None:
-        """Build the graph over the rows held now from their exact neighbour lists (rows appended later stay outside it)."""
+        """Build the graph over the rows held now from their exact neighbour lists (rows appended later stay outside it until
+        extend_hnsw takes them in)."""
         mt = metric if isinstance(metric, int) else metric_from_str(metric)
         check(lib.lynse_hip_flat_build_hnsw(self._h, mt, int(m), int(ef_construction), int(ef_search),
                                             -1 if max_level is None else int(max_level), int(seed)))
+
+    def extend_hnsw(self, mode: int = 0) -> None:
+        """Take the rows appended since the build into its graph: afterwards the graph equals a build over every row held now (rule 7).
+        mode 0 picks between the incremental path and the plain build, mode 1 always takes the incremental path.  A loaded graph
+        answers NotImplementedError."""
+        check(lib.lynse_hip_flat_hnsw_extend(self._h, int(mode)))
+
+    def hnsw_extend_stats(self) -> dict:
+        """The last extend_hnsw: rows before and after, path (0 incremental, 1 plain build, 2 nothing to do), the new (node, level)
+        items, the old ones searched again, the adjacency lists recomputed and those that went through the heuristic again, and the
+        microseconds of the reverse scan, the candidate searches, the selection, the reverse edges and the whole call."""
+        out = np.zeros(12, np.float64)
+        check(lib.lynse_hip_flat_hnsw_extend_stats(self._h, _ptr(out)))
+        names = ("rows_before", "rows_after", "path", "new_items", "researched", "dirty_lists", "reselected")
+        d = {k: int(out[i]) for i, k in enumerate(names)}
+        d.update({k: float(out[7 + i]) for i, k in enumerate(("scan_us", "cand_us", "select_us", "reverse_us", "total_us"))})
+        return d
 
     def load_hnsw(self, metric, m: int, ef_search: int, levels, adj0, upper_node, upper_level, upper_adj, entry: int) -> None:
         """Install a graph as hnsw_params exports it: levels u32 [n], adj0 u32 [n][2 m], the upper lists u32 [n_upper][m] with their
@@ -2349,14 +2367,24 @@ class Collection:
         return True
 
     def _build_hnsw(self) -> None:
-        """The graph over every flushed row.  There is no incremental insert and no on-disk form: rows flushed after a build, and a
-        reopened collection, build it again."""
+        """The graph over every flushed row.  There is no on-disk form: a reopened collection builds it again.  Rows flushed after a
+        build are linked in by _extend_hnsw; mutations go through _rebuild_index."""
         o = self._hnsw_opts
         self._flat.build_hnsw(self._metric, o["m"], o["ef_construction"], o["ef_search"], o["max_level"], HNSW_SEED)
         self._hnsw, self._hnsw_rows = True, len(self._flat)
 
+    def _extend_hnsw(self) -> None:
+        """Rows were flushed after the build: the graph is brought up to date in place (FlatIndex.extend_hnsw, equal to a build over
+        every row); a handle that cannot extend its graph builds it again."""
+        try:
+            self._flat.extend_hnsw()
+        except NotImplementedError:
+            self._build_hnsw()
+        self._hnsw_rows = len(self._flat)
+
     def _build_diskann(self) -> None:
-        """The graph over every flushed row; like the HNSW graph it has no incremental insert and no on-disk form."""
+        """The graph over every flushed row.  It has no on-disk form and, unlike the HNSW graph, no incremental insert: the batched
+        Vamana build depends on its batch order, so rows flushed after a build build it again."""
         o = self._diskann_opts
         self._flat.build_diskann(self._metric, o["r"], o["l"], o["alpha"], o["max_degree"], DISKANN_SEED)
         self._diskann, self._diskann_rows = True, len(self._flat)
@@ -2501,7 +2529,7 @@ class Collection:
             return self._flat.search_filtered_batch_arrays(q, search_k, self._metric, subset_rows)
         if self._hnsw:   # nprobe > 0 is the query-time ef (engine.rs:4743-4745); a subset took the exact filtered scan above
             if self._hnsw_rows != len(self._flat):   # rows were flushed after the build
-                self._build_hnsw()
+                self._extend_hnsw()
             return self._flat.search_hnsw_batch_arrays(q, search_k, self._metric, int(nprobe))
         if self._diskann:   # nprobe > 0 is ef_query; the store rescore of the candidates is the identity: the beam scored the full-precision rows
             if self._diskann_rows != len(self._flat):   # rows were flushed after the build
@@ -2845,7 +2873,7 @@ class Collection:
                 rows, dists, counts = f.flat.search_filtered_bitset_device_batch_arrays(q, search_k, f.metric, d_words, n_words, count)
         elif f.hnsw and not self._tombstone:   # use_field_index (engine.rs:4880): no filter and no tombstone
             if f.hnsw_rows != len(f.flat):     # vectors were added after the build
-                f.build_hnsw()
+                f.extend_hnsw()
             rows, dists, counts = f.flat.search_hnsw_batch_arrays(q, search_k, f.metric, int(nprobe or 0))
         elif approx_eps is not None:
             r, d, _ = f.flat.search_approx(q[0], search_k, f.metric, approx_eps)

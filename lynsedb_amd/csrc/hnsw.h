@@ -4,6 +4,7 @@
 //                   from the node the descent ends at.  The query, R (results) and C (candidates) live in LDS (GraphSearchLds).
 //   k_hnsw_select   one wave per (node, level): select_neighbors_heuristic (hnsw.rs:550-602) over a sorted candidate list
 //   k_hnsw_gather   rows by id into a dense query matrix (the build's queries are the shard's own rows)
+//   k_hnsw_reverse_scan   the incremental insert (rule 7): which old members of a level may see a new row enter their candidate list
 // The distance, the wave helpers, the beam and the order of its keys are graph.h's, shared with diskann.h.
 #pragma once
 
@@ -120,6 +121,7 @@ struct HnswSelectArgs {
     const uint64_t* offs;          // [items + 1]
     uint32_t* out_ids;             // [items][cap] in selection order, GRAPH_PAD after the last
     float* out_d;                  // the graph distances d(node, out_ids)
+    float* out_thr;                // dense lists, may be NULL: the raw score of entry `stride` of the search, NaN when it returned fewer (rule 7)
 };
 
 __global__ void __launch_bounds__(64) k_hnsw_select(HnswSelectArgs a) {
@@ -141,6 +143,7 @@ __global__ void __launch_bounds__(64) k_hnsw_select(HnswSelectArgs a) {
             if (hit) { self_pos = p0 + (uint32_t)__builtin_ctzll(hit); break; }
         }
         ec = self_pos != 0xffffffffu ? cnt - 1 : (cnt < a.stride - 1 ? cnt : a.stride - 1);
+        if (a.out_thr && lane == 0) a.out_thr[t] = cnt == a.stride ? a.d64[base + a.stride - 1] : __int_as_float(0x7fc00000);
     } else {
         base = (size_t)a.offs[t];
         ec = (uint32_t)(a.offs[t + 1] - a.offs[t]);
@@ -209,6 +212,56 @@ __global__ void __launch_bounds__(256) k_hnsw_gather(const float* __restrict__ V
         const uint32_t d = (uint32_t)(e % D);
         const uint32_t r = ids ? ids[t] : first + (uint32_t)t;
         out[e] = V[(size_t)r * ld + d];
+    }
+}
+
+// Rule 7, the reverse scan of one level: old member t (row old_ids[t], or t itself at level 0) is flagged when some new row x of the
+// tile scores against it not strictly worse than thr[t], the last entry its exact search returned (NaN: the search came back short,
+// so every comparison flags) — ties and NaN scores flag.  The score is exact_score in the single-row form, the bits the candidate
+// search ranks by, on the raw metric value (ip: larger is better); the forms are symmetric bit for bit, so the new row may stand in the
+// query's place.  A tile of `tn` new rows sits in LDS (the host sizes it from the 160 KiB the graph kernels share); waves stream the
+// old members, 8 at a time on the 8 lane groups as graph_beam does, each row against the whole tile while it is hot in the caches.
+// A wave whose 8 members are all flagged (by an earlier tile too) moves on.  Control flow is wave-uniform: exact_score shuffles.
+struct HnswReverseArgs {
+    const float* V;
+    uint32_t ld, D;
+    int metric;
+    const uint32_t* old_ids;     // NULL at level 0: member t is row t
+    uint32_t n_old;
+    const float* thr;            // [n_old]
+    const uint32_t* new_ids;     // the level's new rows; the tile is new_ids[tile0 .. tile0 + tn)
+    uint32_t tile0, tn;
+    uint8_t* flags;              // [n_old], zero before the first tile
+};
+constexpr uint32_t HNSW_REVERSE_THREADS = 1024;   // 16 waves: one block holds a CU's LDS, 4 waves per SIMD hide the row loads
+
+__global__ void __launch_bounds__(HNSW_REVERSE_THREADS) k_hnsw_reverse_scan(HnswReverseArgs a) {
+    extern __shared__ __align__(16) unsigned char hnsw_smem[];
+    float* tile = reinterpret_cast<float*>(hnsw_smem);   // [tn][D]
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t j = 0; j < a.tn; ++j) {
+        const float* src = a.V + (size_t)a.new_ids[a.tile0 + j] * a.ld;
+        for (uint32_t e = tid; e < a.D; e += HNSW_REVERSE_THREADS) tile[(size_t)j * a.D + e] = src[e];
+    }
+    __syncthreads();
+    const int lane = tid & 63, g = lane & 7, grp = lane >> 3;
+    const uint32_t waves = HNSW_REVERSE_THREADS / 64;
+    const uint64_t step = (uint64_t)gridDim.x * waves * 8;
+    for (uint64_t base = ((uint64_t)blockIdx.x * waves + (tid >> 6)) * 8; base < a.n_old; base += step) {
+        const uint64_t idx = base + grp;
+        const bool valid = idx < a.n_old;
+        const uint32_t t = (uint32_t)(valid ? idx : base);
+        bool flag = a.flags[t] != 0;
+        if (__all(flag)) continue;
+        const float th = a.thr[t];
+        const float* v = a.V + (size_t)(a.old_ids ? a.old_ids[t] : t) * a.ld;
+        for (uint32_t j = 0; j < a.tn; ++j) {
+            const float s = exact_score<32>(a.metric, LYNSE_IPFORM_SINGLE, tile + (size_t)j * a.D, v, a.D, g);
+            const bool worse = a.metric == M_IP ? s < th : s > th;   // false for a tie, a NaN score and a short list
+            flag = flag || !worse;
+            if (__all(flag)) break;
+        }
+        if (valid && g == 0 && flag) a.flags[t] = 1;
     }
 }
 

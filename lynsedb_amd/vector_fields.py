@@ -289,6 +289,15 @@ class NamedVectorField:
         self.metric, self.hnsw_opts = metric, o
         self.hnsw, self.hnsw_rows = True, len(self.flat)
 
+    def extend_hnsw(self) -> None:
+        """Vectors were added after the build: the graph takes them in (FlatIndex.extend_hnsw, equal to a build over every row); a
+        handle that cannot extend its graph builds it again."""
+        try:
+            self.flat.extend_hnsw()
+        except NotImplementedError:
+            self.build_hnsw()
+        self.hnsw_rows = len(self.flat)
+
     def drop_hnsw(self) -> None:
         self.flat.drop_hnsw()
         self.hnsw, self.hnsw_rows = False, 0
