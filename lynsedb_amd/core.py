@@ -584,6 +584,12 @@ class FlatIndex:
         check(lib.lynse_hip_flat_sq8_params(self._h, _ptr(mins), _ptr(scales)))
         return mins, scales
 
+    def _two_pass_stage_times(self, fn, reset: bool) -> dict:
+        """The stage counters the PQ, RaBitQ and PolarVec searches share (CodedScratch::stage_times, csrc/coded_host.inc)."""
+        out = np.zeros(3, np.float64)
+        check(fn(self._h, _ptr(out), 1 if reset else 0))
+        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+
     # -- FLAT-*-PQ (PQIndex, src/storage/pq_mmap.rs; include/lynse_hip.h states the contract) --------------------------------
     def build_pq(self, n_subspaces: int, n_clusters: int = 256) -> None:
         """Train the product quantiser on the rows held now and encode them (rows appended later stay outside the index)."""
@@ -620,9 +626,7 @@ class FlatIndex:
 
     def pq_stage_times(self, reset: bool = True) -> dict:
         """With profiling on: PQ searches timed and the summed microseconds of the scan stage and of the rescore."""
-        out = np.zeros(3, np.float64)
-        check(lib.lynse_hip_flat_pq_stage_times(self._h, _ptr(out), 1 if reset else 0))
-        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+        return self._two_pass_stage_times(lib.lynse_hip_flat_pq_stage_times, reset)
 
     # -- FLAT-*-RABITQ (RaBitQIndex, src/storage/rabitq_mmap.rs; include/lynse_hip.h states the contract) ----------------------
     def build_rabitq(self) -> None:
@@ -664,9 +668,7 @@ class FlatIndex:
 
     def rabitq_stage_times(self, reset: bool = True) -> dict:
         """With profiling on: RaBitQ searches timed and the summed microseconds of the scan stage and of the rescore."""
-        out = np.zeros(3, np.float64)
-        check(lib.lynse_hip_flat_rabitq_stage_times(self._h, _ptr(out), 1 if reset else 0))
-        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+        return self._two_pass_stage_times(lib.lynse_hip_flat_rabitq_stage_times, reset)
 
     # -- FLAT-*-POLARVEC<b> (PolarVecIndex, src/storage/polarvec_mmap.rs; include/lynse_hip.h states the contract) --------------
     def build_polarvec(self, bits: int, metric) -> None:
@@ -731,9 +733,7 @@ class FlatIndex:
 
     def polarvec_stage_times(self, reset: bool = False) -> dict:
         """With profiling on: PolarVec searches timed and the summed microseconds of the scan stage and of the rescore."""
-        out = np.zeros(3, np.float64)
-        check(lib.lynse_hip_flat_polarvec_stage_times(self._h, _ptr(out), 1 if reset else 0))
-        return {"searches": int(out[0]), "scan_us": float(out[1]), "rescore_us": float(out[2])}
+        return self._two_pass_stage_times(lib.lynse_hip_flat_polarvec_stage_times, reset)
 
     # -- HNSW-* (HNSWIndex, src/index/hnsw.rs; include/lynse_hip.h states the contract) ---------------------------------------
     def build_hnsw(self, metric, m: int = HNSW_DEFAULTS["m"], ef_construction: int = HNSW_DEFAULTS["ef_construction"],

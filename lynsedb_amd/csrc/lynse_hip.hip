@@ -407,9 +407,7 @@ struct lynse_hip_flat {
     lynse_hip_profile prof{};
 };
 
-static void pq_release(lynse_hip_flat* h);
-static void rbq_release(lynse_hip_flat* h);
-static void plv_release(lynse_hip_flat* h);
+static void coded_release(lynse_hip_flat* h);   // pq, rbq and plv (polarvec_host.inc, the last of the three)
 static void range_release(lynse_hip_flat* h);
 static void hnsw_release(lynse_hip_flat* h);
 static void diskann_release(lynse_hip_flat* h);
@@ -549,9 +547,7 @@ extern "C" int lynse_hip_flat_create(uint32_t dim, int device, lynse_hip_flat** 
 extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
-    pq_release(h);
-    rbq_release(h);
-    plv_release(h);
+    coded_release(h);
     range_release(h);
     hnsw_release(h);
     diskann_release(h);
@@ -3806,6 +3802,7 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "comm_host.inc"
 #include "async_host.inc"
 #include "ivf_async.inc"
+#include "coded_host.inc"
 #include "pq_host.inc"
 #include "rabitq_host.inc"
 #include "polarvec_host.inc"

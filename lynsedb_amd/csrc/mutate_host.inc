@@ -24,9 +24,7 @@ static int reset_derived_locked(lynse_hip_flat* h) {
     if (h->vn2) LY_HIP(hipMemsetAsync(h->vn2, 0, ((size_t)h->stats_capacity + 256) * sizeof(float), st));
     if (h->vrinv) LY_HIP(hipMemsetAsync(h->vrinv, 0, ((size_t)h->stats_capacity + 256) * sizeof(float), st));
     LY_HIP(hipStreamSynchronize(st));
-    pq_release(h);
-    rbq_release(h);
-    plv_release(h);
+    coded_release(h);
     hnsw_release(h);
     diskann_release(h);
     approx_release(h);

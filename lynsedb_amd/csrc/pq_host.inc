@@ -1,41 +1,20 @@
 // pq_host.inc — FLAT-{IP,L2,COS}-PQ on a FLAT handle (PQIndex, src/storage/pq_mmap.rs; Collection, src/engine.rs:4559-4600,
-// :5504-5526).  Included at the end of lynse_hip.hip; kernels in pq.h, the exact rescore is k_pool_rerank (kernels.h).
-// DESIGN.md §12.
+// :5504-5526): the SmallRng restatement, the device training and encoding, the ADC table and scan launches.  Included at the end of
+// lynse_hip.hip after coded_host.inc, which holds the frame it shares with RaBitQ and PolarVec (DevBuf, CodedScratch, the handle check,
+// the search driver around ScoreCut and PoolRerank); kernels in pq.h.  DESIGN.md §12.
 
-// The quantiser and the per-handle search scratch.  Codes cover the first n rows of the handle: rows appended after a build or a
-// load stay outside the index (the reference neither re-encodes nor drops them on flush).
-struct PqState {
+// The quantiser.  Codes cover the first n rows of the handle: rows appended after a build or a load stay outside the index (the
+// reference neither re-encodes nor drops them on flush).
+struct PqIndex {
     uint32_t M = 0, K = 0, ss = 0;
     uint64_t n = 0;
-    float* cb = nullptr;          // [M][K][ss] f32 codebooks
-    uint8_t* codes = nullptr;     // [n][M] u8 codes
-    float *d_q = nullptr, *d_lut = nullptr;
-    size_t q_cap = 0, lut_cap = 0;
-    ScoreCut cut;                 // the [chunk][n] score matrix and its radix selection (rerank_host.inc)
-    PoolRerank rr;                // the pool's rows and counts, the rescore's buffers and timing events
-    double searches = 0.0, scan_us = 0.0, rescore_us = 0.0;
-
-    void free_index() {
-        if (cb) (void)hipFree(cb);
-        if (codes) (void)hipFree(codes);
-        cb = nullptr;
-        codes = nullptr;
-        M = K = ss = 0;
-        n = 0;
-    }
-    ~PqState() {
-        free_index();
-        for (void* p : {(void*)d_q, (void*)d_lut})
-            if (p) (void)hipFree(p);
-        cut.release();
-        rr.release();
-    }
+    DevBuf<float> cb;        // [M][K][ss] f32 codebooks
+    DevBuf<uint8_t> codes;   // [n][M] u8 codes
 };
-
-static void pq_release(lynse_hip_flat* h) {
-    delete h->pq;
-    h->pq = nullptr;
-}
+struct PqState {
+    PqIndex ix;
+    CodedScratch s;   // (coded_host.inc)
+};
 
 // ---- SmallRng (rand 0.8.5 on 64-bit: Xoshiro256PlusPlus) and random_init_centroids' draws --------------------------------
 namespace pqrng {
@@ -118,13 +97,6 @@ extern "C" int lynse_hip_pq_init_indices(uint64_t seed, uint64_t n, uint32_t k, 
 }
 
 // ---- build / load ------------------------------------------------------------------------------------------------------------
-static int pq_check_handle(const lynse_hip_flat* h) {
-    if (h->dtype != LYNSE_DTYPE_F32) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ on an F16 shard is not supported");
-    if (h->packed_only) return set_error(LYNSE_ERR_UNSUPPORTED, "PQ is defined for float rows (ip / l2 / cosine)");
-    if (h->row_stride != 1 || h->row_offset != 0) return set_error(LYNSE_ERR_UNSUPPORTED, "a PQ index is not row-sharded");
-    return LYNSE_OK;
-}
-
 // encode (pq_mmap.rs:696-735): codes[i][m] = argmin over the K codewords of l2_squared_f32, first strictly smaller wins
 static int pq_launch_assign(PqAssignArgs a, uint64_t n_rows, hipStream_t st) {
     const size_t lds = (size_t)a.K * a.ss * 4;
@@ -141,17 +113,13 @@ static int pq_launch_assign(PqAssignArgs a, uint64_t n_rows, hipStream_t st) {
     return LYNSE_OK;
 }
 
-template <typename T>
-struct PqDevBuf {   // scratch of one build, freed on every exit path
-    T* p = nullptr;
-    int alloc(size_t count) {
-        LY_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-        return LYNSE_OK;
-    }
-    ~PqDevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
+// a fresh index with its two device arrays
+static int pq_alloc(PqIndex& out, uint32_t M, uint32_t K, uint32_t ss, uint64_t n) {
+    out.M = M; out.K = K; out.ss = ss; out.n = n;
+    LY_TRY(out.cb.alloc((size_t)M * K * ss));
+    if (out.codes.alloc((size_t)n * M) != LYNSE_OK) return set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(PQ codes)");
+    return LYNSE_OK;
+}
 
 // PQIndex::build_with_clusters (pq_mmap.rs:73-149) over the handle's rows, the writer lock held
 static int pq_build_locked(lynse_hip_flat* h, uint32_t M, uint32_t n_clusters) {
@@ -165,8 +133,8 @@ static int pq_build_locked(lynse_hip_flat* h, uint32_t M, uint32_t n_clusters) {
     const uint64_t stride = train_n < n ? std::max<uint64_t>(n / train_n, 1) : 1;
     const uint32_t iters = K <= 64 ? 6 : 15;
     hipStream_t st = cur(h).stream;
-    PqDevBuf<float> T, raw;
-    PqDevBuf<uint32_t> idx, chosen, asg, active, changed, count;
+    DevBuf<float> T, raw;   // scratch of the build
+    DevBuf<uint32_t> idx, chosen, asg, active, changed, count;
     LY_TRY(T.alloc((size_t)train_n * D));
     LY_TRY(raw.alloc((size_t)M * K * ss));
     LY_TRY(idx.alloc((size_t)M * K));
@@ -175,21 +143,15 @@ static int pq_build_locked(lynse_hip_flat* h, uint32_t M, uint32_t n_clusters) {
     LY_TRY(active.alloc(M));
     LY_TRY(changed.alloc(M));
     LY_TRY(count.alloc((size_t)M * K));
-    float* cb = nullptr;
-    uint8_t* codes = nullptr;
-    LY_HIP(hipMalloc(&cb, (size_t)M * K * ss * 4));
-    if (hipMalloc(&codes, (size_t)n * M) != hipSuccess) {
-        (void)hipFree(cb);
-        return set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(PQ codes)");
-    }
-    auto fail = [&](int rc) { (void)hipFree(cb); (void)hipFree(codes); return rc; };
+    PqIndex fresh;   // (freed on every failing path)
+    LY_TRY(pq_alloc(fresh, M, K, ss, n));
+    float* cb = fresh.cb.p;
     const uint32_t gather_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((train_n * D + 255) / 256, (uint64_t)h->num_cu * 32));
     hipLaunchKernelGGL(k_pq_gather, dim3(gather_blocks), dim3(256), 0, st, h->rows, h->ld, D, stride, train_n, T.p);
-    if (hipGetLastError() != hipSuccess) return fail(set_error(LYNSE_ERR_DEVICE, "k_pq_gather launch"));
+    if (hipGetLastError() != hipSuccess) return set_error(LYNSE_ERR_DEVICE, "k_pq_gather launch");
     // the K draws of each subspace (seed m) on the host
     std::vector<uint32_t> h_idx((size_t)M * K, 0u), h_chosen(M), h_active(M, 1u), h_changed(M);
     for (uint32_t m = 0; m < M; ++m) h_chosen[m] = pqrng::init_indices(m, train_n, K, h_idx.data() + (size_t)m * K);
-    int rc = LYNSE_OK;
     auto run = [&]() -> int {
         LY_HIP(hipMemcpyAsync(idx.p, h_idx.data(), h_idx.size() * 4, hipMemcpyHostToDevice, st));
         LY_HIP(hipMemcpyAsync(chosen.p, h_chosen.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
@@ -215,22 +177,17 @@ static int pq_build_locked(lynse_hip_flat* h, uint32_t M, uint32_t n_clusters) {
             hipLaunchKernelGGL(k_pq_empty, dim3(M), dim3(64), 0, st, ss, K, active.p, raw.p, cb, count.p);
             LY_HIP(hipGetLastError());
         }
-        PqAssignArgs e{h->rows, h->ld, n, M, ss, K, cb, 0, nullptr, nullptr, nullptr, codes};
+        PqAssignArgs e{h->rows, h->ld, n, M, ss, K, cb, 0, nullptr, nullptr, nullptr, fresh.codes.p};
         LY_TRY(pq_launch_assign(e, n, st));
         LY_HIP(hipStreamSynchronize(st));
         return LYNSE_OK;
     };
-    rc = run();
+    const int rc = run();
     if (rc != LYNSE_OK) {
-        (void)hipStreamSynchronize(st);
-        return fail(rc);
+        (void)hipStreamSynchronize(st);   // (the buffers go with this frame)
+        return rc;
     }
-    if (!h->pq) h->pq = new PqState();
-    PqState& p = *h->pq;
-    p.free_index();
-    p.M = M; p.K = K; p.ss = ss; p.n = n;
-    p.cb = cb;
-    p.codes = codes;
+    coded_install(h->pq, fresh);
     return LYNSE_OK;
 }
 
@@ -238,7 +195,7 @@ extern "C" int lynse_hip_flat_build_pq(lynse_hip_flat* h, uint32_t n_subspaces, 
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     LY_WRITER(h, lk);
     LY_TRY(use_device(h));
-    LY_TRY(pq_check_handle(h));
+    LY_TRY(coded_check_handle(h, "PQ", false));
     return pq_build_locked(h, n_subspaces, n_clusters);
 }
 
@@ -246,7 +203,7 @@ extern "C" int lynse_hip_flat_load_pq(lynse_hip_flat* h, uint32_t M, uint32_t K,
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     LY_WRITER(h, lk);
     LY_TRY(use_device(h));
-    LY_TRY(pq_check_handle(h));
+    LY_TRY(coded_check_handle(h, "PQ", false));
     // PQIndex::load's checks (pq_mmap.rs:481-494, :526-531)
     if (M == 0 || K == 0 || K > 256 || h->dim % M != 0 || n > 0xffffffffull)
         return set_error(LYNSE_ERR_INVALID_ARGUMENT, "Invalid PQ index dimensions");
@@ -256,67 +213,42 @@ extern "C" int lynse_hip_flat_load_pq(lynse_hip_flat* h, uint32_t M, uint32_t K,
     for (uint64_t i = 0; i < n * M; ++i)
         if (codes[i] >= K) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "PQ index contains an out-of-range code");
     const uint32_t ss = h->dim / M;
-    float* cb = nullptr;
-    uint8_t* cd = nullptr;
-    LY_HIP(hipMalloc(&cb, (size_t)M * K * ss * 4));
-    if (hipMalloc(&cd, (size_t)n * M) != hipSuccess) {
-        (void)hipFree(cb);
-        return set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(PQ codes)");
-    }
-    if (h2d_done(cb, codebooks, (size_t)M * K * ss * 4) != LYNSE_OK || h2d_done(cd, codes, (size_t)n * M) != LYNSE_OK) {
-        (void)hipFree(cb);
-        (void)hipFree(cd);
+    PqIndex fresh;
+    LY_TRY(pq_alloc(fresh, M, K, ss, n));
+    if (h2d_done(fresh.cb.p, codebooks, (size_t)M * K * ss * 4) != LYNSE_OK || h2d_done(fresh.codes.p, codes, (size_t)n * M) != LYNSE_OK)
         return LYNSE_ERR_DEVICE;
-    }
-    if (!h->pq) h->pq = new PqState();
-    PqState& p = *h->pq;
-    p.free_index();
-    p.M = M; p.K = K; p.ss = ss; p.n = n;
-    p.cb = cb;
-    p.codes = cd;
+    coded_install(h->pq, fresh);
     return LYNSE_OK;
 }
 
 extern "C" int lynse_hip_flat_pq_params(lynse_hip_flat* h, uint32_t* mks, uint64_t* n_pq, float* codebooks, uint8_t* codes) {
     if (!h || !mks || !n_pq) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     std::shared_lock<std::shared_mutex> lk(h->rw);
-    if (!h->pq || !h->pq->cb) {
+    if (!h->pq || !h->pq->ix.cb.p) {
         mks[0] = mks[1] = mks[2] = 0;
         *n_pq = 0;
         return LYNSE_OK;
     }
-    const PqState& p = *h->pq;
+    const PqIndex& p = h->pq->ix;
     mks[0] = p.M; mks[1] = p.K; mks[2] = p.ss;
     *n_pq = p.n;
     LY_TRY(use_device(h));
-    if (codebooks) LY_HIP(hipMemcpy(codebooks, p.cb, (size_t)p.M * p.K * p.ss * 4, hipMemcpyDeviceToHost));
-    if (codes) LY_HIP(hipMemcpy(codes, p.codes, (size_t)p.n * p.M, hipMemcpyDeviceToHost));
+    if (codebooks) LY_HIP(hipMemcpy(codebooks, p.cb.p, (size_t)p.M * p.K * p.ss * 4, hipMemcpyDeviceToHost));
+    if (codes) LY_HIP(hipMemcpy(codes, p.codes.p, (size_t)p.n * p.M, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
-extern "C" int lynse_hip_flat_drop_pq(lynse_hip_flat* h) {
-    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    LY_WRITER(h, lk);
-    LY_TRY(use_device(h));
-    if (h->pq) h->pq->free_index();
-    return LYNSE_OK;
-}
+extern "C" int lynse_hip_flat_drop_pq(lynse_hip_flat* h) { return coded_drop(h, &lynse_hip_flat::pq); }
 
 extern "C" int lynse_hip_flat_pq_stage_times(lynse_hip_flat* h, double* out3, int reset) {
     if (!h || !out3) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     LY_WRITER(h, lk);
-    if (!h->pq) { out3[0] = out3[1] = out3[2] = 0.0; return LYNSE_OK; }
-    out3[0] = h->pq->searches;
-    out3[1] = h->pq->scan_us;
-    out3[2] = h->pq->rescore_us;
-    if (reset) h->pq->searches = h->pq->scan_us = h->pq->rescore_us = 0.0;
-    return LYNSE_OK;
+    return coded_stage_times(h->pq, out3, reset);
 }
 
 // ---- search --------------------------------------------------------------------------------------------------------------------
-// PQIndex::search_candidates + rescore_exact_candidates (pq_mmap.rs:176-240, vector_store.rs:611-638): k' = min(k, n_pq),
-// N = min(k' * oversample, n_pq) rows by the canonical (ADC score, row) key, rescored with compute_distance_f32 on the original rows,
-// the best k' by (exact distance, row).  Queries go in chunks whose score matrix stays under 512 MiB.
+// PQIndex::search_candidates + rescore_exact_candidates (pq_mmap.rs:176-240, vector_store.rs:611-638) through coded_search, by the ADC
+// score; the tables of a chunk are not capped.
 extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* queries, uint64_t nq, uint32_t k, int metric, uint32_t oversample,
                                             uint64_t* out_rows, float* out_dists, uint32_t* out_counts) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -326,44 +258,26 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
     if (!queries || !out_counts || (k && (!out_rows || !out_dists))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     LY_WRITER(h, lk);
     LY_TRY(use_device(h));
-    LY_TRY(pq_check_handle(h));
-    if (!h->pq || !h->pq->cb) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no PQ index on this handle: build or load one first");
-    PqState& p = *h->pq;
-    const uint64_t n = p.n;
-    const uint32_t D = h->dim;
-    if (k == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
-    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n);
-    const uint32_t N = (uint32_t)std::min<uint64_t>((uint64_t)kk * oversample, n);
-    if (N == 0) { memset(out_counts, 0, nq * 4); return LYNSE_OK; }
-    const bool asc = metric_ascending(metric);
-    const uint64_t qc = ScoreCut::chunk(nq, n, N);
-    PoolRerank::Search rr(p.rr);
-    LY_TRY(rr.begin(h->rows, n, h->ld, D, metric, N, kk, k, qc, false, h->profiling.load(), "PQ rescore"));
-    LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&p.d_lut, &p.lut_cap, (size_t)qc * p.M * p.K));
-    LY_TRY(p.cut.grow(qc, n));
-    hipStream_t st = cur(h).stream;
-    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
-        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        LY_TRY(rr.pool_start(st));
+    LY_TRY(coded_check_handle(h, "PQ", false));
+    if (!h->pq || !h->pq->ix.cb.p) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "no PQ index on this handle: build or load one first");
+    const PqIndex& p = h->pq->ix;
+    CodedScratch& s = h->pq->s;
+    const auto score = [&](hipStream_t st, uint32_t nqc, bool asc) -> int {
         const uint64_t lut_threads = (uint64_t)nqc * p.M * p.K;
-        hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, p.d_q, nqc, D, p.M, p.ss, p.K, p.cb,
-                           metric == M_IP ? 1 : 0, p.d_lut);
+        hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, s.d_q, nqc, h->dim, p.M, p.ss, p.K, p.cb.p,
+                           metric == M_IP ? 1 : 0, s.d_lut);
         LY_HIP(hipGetLastError());
         // the ADC scan: QB = 4 queries share a code load when the batch has them; tables in <= 64 KiB of LDS
         const int qb = nqc >= 4 ? 4 : 1;
         const uint32_t mc = std::max<uint32_t>(1, std::min<uint32_t>(p.M, 16384u / ((uint32_t)qb * p.K)));
-        PqAdcArgs aa{p.codes, n, p.M, p.K, mc, p.d_lut, nqc, asc ? 1 : 0, p.cut.d_S};
-        const dim3 agrid((uint32_t)((n + PQ_NT * PQ_R - 1) / (PQ_NT * PQ_R)), (nqc + qb - 1) / qb);
+        PqAdcArgs aa{p.codes.p, p.n, p.M, p.K, mc, s.d_lut, nqc, asc ? 1 : 0, s.cut.d_S};
+        const dim3 agrid((uint32_t)((p.n + PQ_NT * PQ_R - 1) / (PQ_NT * PQ_R)), (nqc + qb - 1) / qb);
         const size_t alds = (size_t)qb * mc * p.K * 4;
         if (qb == 4) hipLaunchKernelGGL(k_pq_adc<4>, agrid, dim3(PQ_NT), alds, st, aa);
         else hipLaunchKernelGGL(k_pq_adc<1>, agrid, dim3(PQ_NT), alds, st, aa);
         LY_HIP(hipGetLastError());
-        // the N best (score, row) keys -> pool rows
-        LY_TRY(p.cut.run(nqc, n, N, p.rr, h->num_cu, st));
-        LY_TRY(rr.run(p.d_q, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, nullptr, st));
-    }
-    if (rr.timed) { p.searches += 1; p.scan_us += rr.pool_us; p.rescore_us += rr.rerank_us; }
-    return LYNSE_OK;
+        return LYNSE_OK;
+    };
+    return coded_search(h, s, {"PQ", p.n, (size_t)p.M * p.K, false, false, false}, queries, nq, k, metric, oversample, out_rows, out_dists,
+                        out_counts, score);
 }

@@ -1,6 +1,7 @@
-// rerank_host.inc — the exact rerank stage shared by the quantised indexes (IVF-*-SQ8 in ivf_host.inc, FLAT-*-PQ in
-// pq_host.inc, FLAT-*-RABITQ in rabitq_host.inc) and, for the two FLAT ones, the cut of a score matrix into the pool (ScoreCut
-// below).  Included at the end of lynse_hip.hip, before them.  A cheap pool stage leaves a pool of candidate rows per query
+// rerank_host.inc — the exact rerank stage shared by the quantised indexes (IVF-*-SQ8 in ivf_host.inc; FLAT-*-PQ, FLAT-*-RABITQ and
+// FLAT-*-POLARVEC<b> through their one search driver, coded_search in coded_host.inc) and, for the FLAT ones and the range, additive
+// and approximate searches, the cut of a score matrix into the pool (ScoreCut below).  Included at the end of lynse_hip.hip, before
+// them.  A cheap pool stage leaves a pool of candidate rows per query
 // in d_prow / d_pcnt; k_pool_rerank (kernels.h) scores the pool exactly against the original rows and keeps the best k_sel by the
 // canonical (distance, row) key.  A pool of up to 16,384 keys whose keys and query fit the LDS is selected on the device, a larger
 // one is scored on the device and selected on the host.

@@ -268,6 +268,37 @@ def test_pool_beyond_the_device_selection_and_pool_of_all_rows(L, ref):
     check_search(got, ref_search(ref, data, enc, queries[:1], 30_000, L2))
 
 
+def test_query_chunks_of_256(L, ref):
+    """The search driver (coded_search, csrc/coded_host.inc) takes at most QCHUNK = 256 queries at a time: 257 run as 256 + 1, the last
+    chunk a single-query block.  k = 1, 10: N = 20, 200 < 300 rows, so both chunks go through the radix selection."""
+    rng = np.random.default_rng(257)
+    data = dataset(rng, 300, 20)
+    idx, enc = built(L, ref, data, 4, L2)
+    queries = rng.standard_normal((257, 20)).astype(f32)
+    queries[256] = data[11]
+    for metric in (L2, IP):
+        exp = ref_search_ks(ref, data, enc, queries, (1, 10), metric)
+        for k in (1, 10):
+            check_search(idx.search_polarvec_batch_arrays(queries, k, NAME[metric]), exp[k])
+
+
+def test_query_chunks_at_the_table_cap(L, ref):
+    """dim 1,100 -> padded 2,048 at bits 8: one query's table is 2,048 << 8 floats = 2 MiB, and a chunk's tables stay at or under
+    256 MiB, so a chunk is 128 queries, fewer than QCHUNK; 130 run as 128 + 2.  The smallest padded width at which the cap binds."""
+    rng = np.random.default_rng(1100)
+    dim, bits = 1100, 8
+    table_bytes = (pow2(dim) << bits) * 4
+    assert pow2(dim) == 2048 and (256 << 20) // table_bytes == 128 < 256
+    data = dataset(rng, 300, dim)
+    idx, enc = built(L, ref, data, bits, L2)
+    queries = rng.standard_normal((130, dim)).astype(f32)
+    queries[129] = data[11]
+    for metric in (L2, IP):
+        exp = ref_search_ks(ref, data, enc, queries, (1, 10), metric)
+        for k in (1, 10):
+            check_search(idx.search_polarvec_batch_arrays(queries, k, NAME[metric]), exp[k])
+
+
 def test_widest_padded_dim_and_the_lds_refusal(L, ref):
     """dim 20,000 -> padded 32,768: 128 KiB of LDS in the rotation kernels (the raised limit), 16,384 code bytes at bits 4.  dim 33,000
     -> padded 65,536 floats do not fit the 160 KiB: refused."""

@@ -236,6 +236,37 @@ def test_query_chunks_of_223_at_600k_rows(L, ref):
     check_search(idx.search_rabitq_batch_arrays(queries, 10, "ip"), exp)
 
 
+def test_query_chunks_of_256(L, ref):
+    """The search driver (coded_search, csrc/coded_host.inc) takes at most QCHUNK = 256 queries at a time: 257 run as 256 + 1, the last
+    chunk a single-query block.  k = 1: N = 200 < 300 rows, so both chunks go through the radix selection."""
+    rng = np.random.default_rng(257)
+    data = rng.standard_normal((300, 20)).astype(f32)
+    idx, enc = built(L, ref, data)
+    queries = rng.standard_normal((257, 20)).astype(f32)
+    queries[256] = data[11]
+    assert min(1 * OVERSAMPLE, 300) == 200
+    for metric in (IP, L2, COS):
+        exp = ref_search(ref, data, *enc, queries, 1, metric)
+        check_search(idx.search_rabitq_batch_arrays(queries, 1, NAME[metric]), exp)
+
+
+def test_query_chunks_at_the_table_cap(L, ref):
+    """dim 9,000 -> padded 16,384, 2,048 code bytes: one query's byte tables are 2,048 * 256 floats = 2 MiB, and a chunk's tables stay
+    at or under 256 MiB, so a chunk is 128 queries, fewer than QCHUNK; 130 run as 128 + 2.  The smallest padded width at which the cap
+    binds."""
+    rng = np.random.default_rng(9000)
+    dim = 9000
+    table_bytes = (pow2(dim) + 7) // 8 * 256 * 4
+    assert pow2(dim) == 16_384 and (256 << 20) // table_bytes == 128 < 256
+    data = rng.standard_normal((300, dim)).astype(f32)
+    idx, enc = built(L, ref, data)
+    queries = rng.standard_normal((130, dim)).astype(f32)
+    queries[129] = data[11]
+    for metric in (IP, L2):
+        exp = ref_search(ref, data, *enc, queries, 1, metric)
+        check_search(idx.search_rabitq_batch_arrays(queries, 1, NAME[metric]), exp)
+
+
 def test_widest_padded_dim_and_the_lds_refusal(L, ref):
     """dim 20,000 -> padded 32,768: 128 KiB of LDS in the rotation kernels (the raised limit), 4,096 code bytes in 256 chunks of 16
     (five queries: a group of four and a partial one) and in 64 chunks of 64 (one query).  dim 33,000 -> padded 65,536 floats do
