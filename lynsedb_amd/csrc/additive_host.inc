@@ -103,19 +103,19 @@ static int additive_search(lynse_hip_flat* h, const float* queries, uint64_t nq,
     }
     hipStream_t st = cur(h).stream;
     if (filtered) {
-        LY_TRY(ivf_grow(&p.d_mask, &p.mask_cap, (size_t)std::max<uint64_t>(1, mask_words)));
-        if (mask_words) LY_HIP(hipMemcpyAsync(p.d_mask, words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+        LY_TRY(p.mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+        if (mask_words) LY_HIP(hipMemcpyAsync(p.mask.p, words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
     }
-    LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&p.rr.d_keys, &p.rr.keys_cap, (size_t)qc * N));
-    LY_TRY(ivf_grow(&p.rr.d_pcnt, &p.rr.pcnt_cap, (size_t)qc));
-    if (sort_dev) LY_TRY(ivf_grow(&p.rr.d_out, &p.rr.out_cap, ((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
+    LY_TRY(p.q.reserve((size_t)qc * D));
+    LY_TRY(p.rr.keys.reserve((size_t)qc * N));
+    LY_TRY(p.rr.pcnt.reserve((size_t)qc));
+    if (sort_dev) LY_TRY(p.rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
     LY_TRY(p.cut.grow(qc, n));
     const bool select = live > N;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        AdditiveScanArgs a{h->rows, h->ld, D, n, p.d_q, nqc, filtered ? p.d_mask : nullptr, mask_words, R, TQ, p.cut.d_S};
+        LY_HIP(hipMemcpyAsync(p.q.p, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+        AdditiveScanArgs a{h->rows, h->ld, D, n, p.q.p, nqc, filtered ? p.mask.p : nullptr, mask_words, R, TQ, p.cut.S.p};
         const dim3 grid((uint32_t)std::min<uint64_t>((n + R - 1) / R, (uint64_t)h->num_cu * 4), (nqc + TQ - 1) / TQ);
         switch (metric) {
         case M_L1: LY_TRY(additive_launch<M_L1>(a, nqc == 1, grid, lds, st)); break;
@@ -125,28 +125,28 @@ static int additive_search(lynse_hip_flat* h, const float* queries, uint64_t nq,
         }
         // more live rows than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
         p.cut.sel0.assign(nqc, select ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
-        LY_TRY(p.cut.cut<true>(nqc, n, N, select, p.rr.d_keys, p.rr.d_pcnt, st));
+        LY_TRY(p.cut.cut<true>(nqc, n, N, select, p.rr.keys.p, p.rr.pcnt.p, st));
         if (sort_dev) {   // sorted in LDS (k_pool_select), rows | distances | counts of the chunk back in one copy
             uint32_t p2 = 2;
             while (p2 < N) p2 <<= 1;
             const size_t o_dist = (size_t)nqc * N * 8, o_cnt = (size_t)nqc * N * 12, o_all = o_cnt + (size_t)nqc * 4;
-            uint8_t* ob = reinterpret_cast<uint8_t*>(p.rr.d_out);
+            uint8_t* ob = reinterpret_cast<uint8_t*>(p.rr.out.p);
             PoolRerankArgs x{};
-            x.pool_cnt = p.rr.d_pcnt;
+            x.pool_cnt = p.rr.pcnt.p;
             x.pool_ld = N;
             x.p2 = p2;
             x.metric = metric;
             x.k = N;
             x.out_k = N;
-            x.out_rows = p.rr.d_out;
+            x.out_rows = p.rr.out.p;
             x.out_dists = reinterpret_cast<float*>(ob + o_dist);
             x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
-            x.keys_out = p.rr.d_keys;
+            x.keys_out = p.rr.keys.p;
             if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(nqc), dim3(1024), (size_t)p2 * 8, st, x);
             else hipLaunchKernelGGL(k_pool_select<256>, dim3(nqc), dim3(256), (size_t)p2 * 8, st, x);
             LY_HIP(hipGetLastError());
             p.h_out.resize((o_all + 7) / 8);
-            LY_HIP(hipMemcpyAsync(p.h_out.data(), p.rr.d_out, o_all, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(p.h_out.data(), p.rr.out.p, o_all, hipMemcpyDeviceToHost, st));
             LY_TRY(stream_wait(st));
             const uint8_t* hb = reinterpret_cast<const uint8_t*>(p.h_out.data());
             for (uint32_t i = 0; i < nqc; ++i) {
@@ -156,7 +156,7 @@ static int additive_search(lynse_hip_flat* h, const float* queries, uint64_t nq,
             }
         } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host
             p.keys.resize((size_t)nqc * N);
-            LY_HIP(hipMemcpyAsync(p.keys.data(), p.rr.d_keys, p.keys.size() * 8, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(p.keys.data(), p.rr.keys.p, p.keys.size() * 8, hipMemcpyDeviceToHost, st));
             LY_TRY(stream_wait(st));
             for (uint32_t i = 0; i < nqc; ++i)
                 out_counts[q0 + i] = select_pool_keys(p.keys.data() + (size_t)i * N, N, N, N, true, out_rows + (q0 + i) * k, out_dists + (q0 + i) * k);

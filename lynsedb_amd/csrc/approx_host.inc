@@ -85,16 +85,11 @@ extern "C" uint32_t lynse_hip_approx_sampled_dim_blocks(uint32_t dim, uint32_t s
 // an append moves h->n, and everything that rewrites rows goes through reset_derived_locked (mutate_host.inc) or empties the shard
 // (lynse_hip_top_k_search), which release the state — the keys the other derived copies (n_stats, n16, CodeSet::n) go by.
 struct ApproxState {
-    float *row_sum = nullptr, *norm2 = nullptr, *inv_norm = nullptr;
-    unsigned long long* d_fin = nullptr;
+    DevBuf<float> row_sum, norm2, inv_norm;
+    DevBuf<unsigned long long> fin;
     uint64_t n = 0, finite = 0;   // rows covered (0: nothing built) / rows with a finite sum
-    struct Order { uint64_t* rows = nullptr; uint32_t* d_cnt = nullptr; uint64_t n = 0; uint32_t pool = 0; } order[2];   // [0] sum desc, [1] sum asc
-    float* d_q = nullptr;
-    ~ApproxState() {
-        for (void* p : {(void*)row_sum, (void*)norm2, (void*)inv_norm, (void*)d_fin, (void*)order[0].rows, (void*)order[0].d_cnt,
-                        (void*)order[1].rows, (void*)order[1].d_cnt, (void*)d_q})
-            if (p) (void)hipFree(p);
-    }
+    struct Order { DevBuf<uint64_t> rows; DevBuf<uint32_t> cnt; uint64_t n = 0; uint32_t pool = 0; } order[2];   // [0] sum desc, [1] sum asc
+    DevBuf<float> q;
 };
 
 static void approx_release(lynse_hip_flat* h) {
@@ -108,17 +103,17 @@ static int approx_ensure_stats(lynse_hip_flat* h, hipStream_t st) {
     h->approx = new ApproxState();   // (n == 0 until the pass is done: a failure below leaves nothing that counts as built)
     ApproxState* s = h->approx;
     const uint64_t n = h->n;
-    LY_HIP(hipMalloc(&s->row_sum, (size_t)n * 4));
-    LY_HIP(hipMalloc(&s->norm2, (size_t)n * 4));
-    LY_HIP(hipMalloc(&s->inv_norm, (size_t)n * 4));
-    LY_HIP(hipMalloc(&s->d_fin, 8));
-    LY_HIP(hipMemsetAsync(s->d_fin, 0, 8, st));
-    ApproxStatsArgs a{h->rows, h->ld, h->dim, n, s->row_sum, s->norm2, s->inv_norm, s->d_fin};
+    LY_TRY(s->row_sum.alloc((size_t)n));
+    LY_TRY(s->norm2.alloc((size_t)n));
+    LY_TRY(s->inv_norm.alloc((size_t)n));
+    LY_TRY(s->fin.alloc(1));
+    LY_HIP(hipMemsetAsync(s->fin.p, 0, 8, st));
+    ApproxStatsArgs a{h->rows, h->ld, h->dim, n, s->row_sum.p, s->norm2.p, s->inv_norm.p, s->fin.p};
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 31) / 32, (uint64_t)h->num_cu * 16));
     hipLaunchKernelGGL(k_approx_rowstats, dim3(grid), dim3(APX_NT), 0, st, a);
     LY_HIP(hipGetLastError());
     unsigned long long fin = 0;
-    LY_HIP(hipMemcpyAsync(&fin, s->d_fin, 8, hipMemcpyDeviceToHost, st));
+    LY_HIP(hipMemcpyAsync(&fin, s->fin.p, 8, hipMemcpyDeviceToHost, st));
     LY_TRY(stream_wait(st));
     s->finite = fin;
     s->n = n;
@@ -153,7 +148,7 @@ static int approx_coarse_launch(const ApproxCoarseArgs& a, uint32_t q_floats, ui
     return LYNSE_OK;
 }
 
-// The keys in p.rr.d_keys (their number in p.rr.d_pcnt, at most `ld`) ordered by the canonical key: the best k_sel go out.  Sorted in LDS
+// The keys in p.rr.keys.p (their number in p.rr.pcnt.p, at most `ld`) ordered by the canonical key: the best k_sel go out.  Sorted in LDS
 // up to 16,384 keys (k_pool_select), on the host beyond.
 static int approx_order_keys(RangeState& p, uint32_t ld, uint32_t k_sel, int metric, hipStream_t st, uint64_t* out_rows, float* out_dists,
                              uint32_t* out_count) {
@@ -163,25 +158,25 @@ static int approx_order_keys(RangeState& p, uint32_t ld, uint32_t k_sel, int met
         while (p2 < ld) p2 <<= 1;
         LY_TRY(ensure_lds<k_pool_select<256>>(PoolRerank::LDS_MAX));
         LY_TRY(ensure_lds<k_pool_select<1024>>(PoolRerank::LDS_MAX));
-        LY_TRY(ivf_grow(&p.rr.d_out, &p.rr.out_cap, ((size_t)k_sel * 12 + 4 + 7) / 8));
+        LY_TRY(p.rr.out.reserve(((size_t)k_sel * 12 + 4 + 7) / 8));
         const size_t o_dist = (size_t)k_sel * 8, o_cnt = (size_t)k_sel * 12, o_all = o_cnt + 4;
-        uint8_t* ob = reinterpret_cast<uint8_t*>(p.rr.d_out);
+        uint8_t* ob = reinterpret_cast<uint8_t*>(p.rr.out.p);
         PoolRerankArgs x{};
-        x.pool_cnt = p.rr.d_pcnt;
+        x.pool_cnt = p.rr.pcnt.p;
         x.pool_ld = ld;
         x.p2 = p2;
         x.metric = metric;
         x.k = k_sel;
         x.out_k = k_sel;
-        x.out_rows = p.rr.d_out;
+        x.out_rows = p.rr.out.p;
         x.out_dists = reinterpret_cast<float*>(ob + o_dist);
         x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
-        x.keys_out = p.rr.d_keys;
+        x.keys_out = p.rr.keys.p;
         if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(1), dim3(1024), (size_t)p2 * 8, st, x);
         else hipLaunchKernelGGL(k_pool_select<256>, dim3(1), dim3(256), (size_t)p2 * 8, st, x);
         LY_HIP(hipGetLastError());
         p.h_out.resize((o_all + 7) / 8);
-        LY_HIP(hipMemcpyAsync(p.h_out.data(), p.rr.d_out, o_all, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(p.h_out.data(), p.rr.out.p, o_all, hipMemcpyDeviceToHost, st));
         LY_TRY(stream_wait(st));
         const uint8_t* hb = reinterpret_cast<const uint8_t*>(p.h_out.data());
         memcpy(out_count, hb + o_cnt, 4);
@@ -190,8 +185,8 @@ static int approx_order_keys(RangeState& p, uint32_t ld, uint32_t k_sel, int met
     } else {
         uint32_t cnt = 0;
         p.keys.resize(ld);
-        LY_HIP(hipMemcpyAsync(p.keys.data(), p.rr.d_keys, (size_t)ld * 8, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(&cnt, p.rr.d_pcnt, 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(p.keys.data(), p.rr.keys.p, (size_t)ld * 8, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(&cnt, p.rr.pcnt.p, 4, hipMemcpyDeviceToHost, st));
         LY_TRY(stream_wait(st));
         *out_count = select_pool_keys(p.keys.data(), std::min(cnt, ld), k_sel, k_sel, asc, out_rows, out_dists);
     }
@@ -279,16 +274,16 @@ static int approx_search_locked(lynse_hip_flat* h, const float* query, uint32_t 
     if (info->path == 1 || order >= 0) LY_TRY(approx_ensure_stats(h, st));
     if (!h->approx) h->approx = new ApproxState();
     ApproxState& s = *h->approx;
-    if (!s.d_q) LY_HIP(hipMalloc(&s.d_q, (size_t)D * 4));
-    LY_HIP(hipMemcpyAsync(s.d_q, query, (size_t)D * 4, hipMemcpyHostToDevice, st));
+    LY_TRY(s.q.reserve_exact((size_t)D));
+    LY_HIP(hipMemcpyAsync(s.q.p, query, (size_t)D * 4, hipMemcpyHostToDevice, st));
     LY_TRY(p.cut.grow(1, n));
-    LY_TRY(ivf_grow(&p.rr.d_pcnt, &p.rr.pcnt_cap, (size_t)1));
+    LY_TRY(p.rr.pcnt.reserve((size_t)1));
 
     if (form >= 0) {
         uint32_t q_floats = 0;
         for (uint32_t b = 0; b < blk.nb; ++b) q_floats += blk.len[b];
-        ApproxCoarseArgs a{h->rows, h->ld, D, n, s.d_q, blk, ip_form, (float)D / (float)std::max<uint32_t>(q_floats, 1), q_norm2, q_inv,
-                           s.norm2, s.inv_norm, p.cut.d_S};
+        ApproxCoarseArgs a{h->rows, h->ld, D, n, s.q.p, blk, ip_form, (float)D / (float)std::max<uint32_t>(q_floats, 1), q_norm2, q_inv,
+                           s.norm2.p, s.inv_norm.p, p.cut.S.p};
         switch (form) {
         case AF_IP: LY_TRY(approx_coarse_launch<AF_IP>(a, q_floats, h->num_cu, st)); break;
         case AF_L2EXP: LY_TRY(approx_coarse_launch<AF_L2EXP>(a, q_floats, h->num_cu, st)); break;
@@ -301,47 +296,45 @@ static int approx_search_locked(lynse_hip_flat* h, const float* query, uint32_t 
     }
 
     if (!pooled) {   // paths 1 and 2: the best k straight from the score vector
-        LY_TRY(ivf_grow(&p.rr.d_keys, &p.rr.keys_cap, (size_t)k));
+        LY_TRY(p.rr.keys.reserve((size_t)k));
         p.cut.sel0.assign(1, n > k ? PqSel{0ull, 64u, k, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
-        LY_TRY(p.cut.cut<true>(1, n, k, n > k, p.rr.d_keys, p.rr.d_pcnt, st));
+        LY_TRY(p.cut.cut<true>(1, n, k, n > k, p.rr.keys.p, p.rr.pcnt.p, st));
         return approx_order_keys(p, k, k, metric, st, out_rows, out_dists, out_count);
     }
 
     // paths 3 and 4: the pool — a cached sum order, or the cut of the coarse scores — rescored exactly
-    LY_TRY(ivf_grow(&p.rr.d_prow, &p.rr.prow_cap, (size_t)pool));
-    LY_TRY(ivf_grow(&p.rr.d_keys, &p.rr.keys_cap, (size_t)pool));
-    const uint64_t* pool_rows = p.rr.d_prow;
-    const uint32_t* pool_cnt = p.rr.d_pcnt;
+    LY_TRY(p.rr.prow.reserve((size_t)pool));
+    LY_TRY(p.rr.keys.reserve((size_t)pool));
+    const uint64_t* pool_rows = p.rr.prow.p;
+    const uint32_t* pool_cnt = p.rr.pcnt.p;
     if (order >= 0) {
         ApproxState::Order& o = s.order[order];
         if (o.n != n || o.pool != pool) {   // cut once per (n, pool)
-            if (o.rows) (void)hipFree(o.rows);
-            o.rows = nullptr;
             o.n = 0;
-            LY_HIP(hipMalloc(&o.rows, (size_t)pool * 8));
-            if (!o.d_cnt) LY_HIP(hipMalloc(&o.d_cnt, 4));
+            LY_TRY(o.rows.alloc((size_t)pool));
+            LY_TRY(o.cnt.reserve_exact(1));
             const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)h->num_cu * 32));
-            hipLaunchKernelGGL(k_approx_sum_keys, dim3(blocks), dim3(256), 0, st, s.row_sum, n, order == 0 ? 1 : 0, p.cut.d_S);
+            hipLaunchKernelGGL(k_approx_sum_keys, dim3(blocks), dim3(256), 0, st, s.row_sum.p, n, order == 0 ? 1 : 0, p.cut.S.p);
             LY_HIP(hipGetLastError());
             const bool select = s.finite > pool;
             p.cut.sel0.assign(1, select ? PqSel{0ull, 64u, pool, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
-            LY_TRY(p.cut.cut<false>(1, n, pool, select, o.rows, o.d_cnt, st));
+            LY_TRY(p.cut.cut<false>(1, n, pool, select, o.rows.p, o.cnt.p, st));
             LY_TRY(stream_wait(st));
             o.n = n;
             o.pool = pool;
         }
-        pool_rows = o.rows;
-        pool_cnt = o.d_cnt;
+        pool_rows = o.rows.p;
+        pool_cnt = o.cnt.p;
     } else {
         p.cut.sel0.assign(1, PqSel{0ull, 64u, pool, 0u, 0u});
-        LY_TRY(p.cut.cut<false>(1, n, pool, true, p.rr.d_prow, p.rr.d_pcnt, st));
+        LY_TRY(p.cut.cut<false>(1, n, pool, true, p.rr.prow.p, p.rr.pcnt.p, st));
     }
-    ApproxRescoreArgs ra{h->rows, h->ld, D, n, s.d_q, pool_rows, pool_cnt, pool, metric, p.rr.d_keys};
+    ApproxRescoreArgs ra{h->rows, h->ld, D, n, s.q.p, pool_rows, pool_cnt, pool, metric, p.rr.keys.p};
     LY_TRY(ensure_lds<k_approx_rescore>(PoolRerank::LDS_MAX));
     hipLaunchKernelGGL(k_approx_rescore, dim3(std::max<uint32_t>(1, std::min<uint32_t>((pool + 31) / 32, (uint32_t)h->num_cu * 8))), dim3(APX_NT),
                        (size_t)D * 4, st, ra);
     LY_HIP(hipGetLastError());
-    if (pool_cnt != p.rr.d_pcnt) LY_HIP(hipMemcpyAsync(p.rr.d_pcnt, pool_cnt, 4, hipMemcpyDeviceToDevice, st));
+    if (pool_cnt != p.rr.pcnt.p) LY_HIP(hipMemcpyAsync(p.rr.pcnt.p, pool_cnt, 4, hipMemcpyDeviceToDevice, st));
     return approx_order_keys(p, pool, k, metric, st, out_rows, out_dists, out_count);
 }
 

@@ -1,51 +1,17 @@
 // coded_host.inc — the host frame of the two-pass searches over auxiliary codes on a FLAT handle: FLAT-*-PQ (pq_host.inc),
 // FLAT-*-RABITQ (rabitq_host.inc) and FLAT-*-POLARVEC<b> (polarvec_host.inc).  Each scores its codes into a score matrix, ScoreCut cuts
 // the matrix to a pool and PoolRerank rescores the pool exactly (rerank_host.inc); what surrounds the codec's own kernels is here, once:
-// the owning device pointer, the per-handle search scratch, the search driver, the rotated-code container of RaBitQ and PolarVec, the
+// the per-handle search scratch, the search driver, the rotated-code container of RaBitQ and PolarVec, the
 // handle checks and the small per-index entry bodies.  Included at the end of lynse_hip.hip, before the three.  DESIGN.md §12, §15, §23.
-
-// An owning device pointer: freed on every exit path unless release() hands it over.
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (p) (void)hipFree(p);
-        p = o.release();
-        return *this;
-    }
-    int alloc(size_t count) {
-        LY_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-        return LYNSE_OK;
-    }
-    T* release() {
-        T* q = p;
-        p = nullptr;
-        return q;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 // The search scratch a handle keeps per coded index (its searches are serialised): it outlives the index it serves, so a rebuild or
 // a load keeps the buffers.
 struct CodedScratch {
-    float *d_q = nullptr, *d_lut = nullptr, *d_extra = nullptr;   // a chunk's queries, their tables, one more float per query (RaBitQ's total_q)
-    size_t q_cap = 0, lut_cap = 0, extra_cap = 0;
+    DevBuf<float> q, lut, extra;   // a chunk's queries, their tables, one more float per query (RaBitQ's total_q)
     ScoreCut cut;    // the [chunk][n] score matrix and its radix selection
     PoolRerank rr;   // the pool's rows and counts, the rescore's buffers and timing events
     double searches = 0.0, scan_us = 0.0, rescore_us = 0.0;
-    CodedScratch() = default;
-    CodedScratch(const CodedScratch&) = delete;
-    CodedScratch& operator=(const CodedScratch&) = delete;
-    ~CodedScratch() {
-        for (void* p : {(void*)d_q, (void*)d_lut, (void*)d_extra})
-            if (p) (void)hipFree(p);
-        cut.release();
-        rr.release();
-    }
+    ~CodedScratch() { rr.release(); }
     void stage_times(double* out3, int reset) {
         out3[0] = searches;
         out3[1] = scan_us;
@@ -138,7 +104,7 @@ struct RotCodes {
 // ---- the search ------------------------------------------------------------------------------------------------------------------
 // What a codec tells the driver about its index: the rows it covers, its name in messages, the floats of one query's table(s), whether
 // a chunk's tables are capped at 256 MiB, whether a small batch's pools are scored by several workgroups each (PoolRerank's
-// split_small), whether the kernels want CodedScratch::d_extra.
+// split_small), whether the kernels want CodedScratch::extra.
 struct CodedShape {
     const char* who;
     uint64_t n;
@@ -149,7 +115,7 @@ struct CodedShape {
 // search_candidates + rescore_exact of the three indexes: k' = min(k, n), N = min(k' * oversample, n) rows by the canonical (code
 // score, row) key, rescored with compute_distance_f32 on the original rows, the best k' by (exact distance, row).  Queries go in
 // chunks: score matrix <= 512 MiB, pool <= 256 MiB (ScoreCut::chunk) and, where capped, tables <= 256 MiB.  score(st, nqc, asc)
-// launches the codec's table and scan kernels for the nqc queries in s.d_q and leaves the score images in s.cut.d_S.  The caller
+// launches the codec's table and scan kernels for the nqc queries in s.q.p and leaves the score images in s.cut.S.p.  The caller
 // holds the writer lock and has checked its arguments, the handle and the index.
 template <typename Score>
 static int coded_search(lynse_hip_flat* h, CodedScratch& s, const CodedShape& c, const float* queries, uint64_t nq, uint32_t k, int metric,
@@ -165,18 +131,18 @@ static int coded_search(lynse_hip_flat* h, CodedScratch& s, const CodedShape& c,
     PoolRerank::Search rr(s.rr);
     rr.split_small = c.split_small;   // pools of thousands of rows: a single query's would be gathered by one CU
     LY_TRY(rr.begin(h->rows, n, h->ld, D, metric, N, kk, k, qc, false, h->profiling.load(), (std::string(c.who) + " rescore").c_str()));
-    LY_TRY(ivf_grow(&s.d_q, &s.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&s.d_lut, &s.lut_cap, (size_t)qc * c.lut_q));
-    if (c.extra) LY_TRY(ivf_grow(&s.d_extra, &s.extra_cap, (size_t)qc));
+    LY_TRY(s.q.reserve((size_t)qc * D));
+    LY_TRY(s.lut.reserve((size_t)qc * c.lut_q));
+    if (c.extra) LY_TRY(s.extra.reserve((size_t)qc));
     LY_TRY(s.cut.grow(qc, n));
     hipStream_t st = cur(h).stream;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(s.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(s.q.p, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
         LY_TRY(rr.pool_start(st));
         LY_TRY(score(st, nqc, asc));
         LY_TRY(s.cut.run(nqc, n, N, s.rr, h->num_cu, st));   // the N best (score, row) keys -> pool rows
-        LY_TRY(rr.run(s.d_q, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, nullptr, st));
+        LY_TRY(rr.run(s.q.p, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, nullptr, st));
     }
     if (rr.timed) { s.searches += 1; s.scan_us += rr.pool_us; s.rescore_us += rr.rerank_us; }
     return LYNSE_OK;

@@ -8,15 +8,14 @@ struct DiskannState {
     uint32_t r = 0, l = 0, entry = 0;
     float alpha = 0.0f;
     uint64_t n = 0;                       // the graph covers the first n rows of the handle
-    uint32_t* d_adj = nullptr;            // [n][r]
+    DevBuf<uint32_t> d_adj;               // [n][r]
     GraphSearchScratch search;            // with the searches timed with profiling on
     // the last build (microseconds of host time; the three stages only when it ran with profiling on, which synchronises them)
     double b_search_us = 0.0, b_prune_us = 0.0, b_commit_us = 0.0, b_draws_us = 0.0, b_total_us = 0.0;
 
-    bool built() const { return d_adj != nullptr; }
+    bool built() const { return d_adj.p != nullptr; }
     void free_index() {
-        if (d_adj) (void)hipFree(d_adj);
-        d_adj = nullptr;
+        d_adj.reset();
         metric = -1;
         r = l = entry = 0;
         alpha = 0.0f;
@@ -91,11 +90,11 @@ static int diskann_check_params(uint32_t r, uint32_t l) {
 }
 static size_t diskann_prune_lds(uint32_t cap, uint32_t D) { return (size_t)cap * 16 + (size_t)D * 8; }   // two key arrays, the rows of p and b
 
-static int diskann_install(lynse_hip_flat* h, uint32_t* d_adj, int metric, uint32_t r, uint32_t l, float alpha, uint64_t n, uint32_t entry) {
+static int diskann_install(lynse_hip_flat* h, DevBuf<uint32_t>&& d_adj, int metric, uint32_t r, uint32_t l, float alpha, uint64_t n, uint32_t entry) {
     if (!h->diskann) h->diskann = new DiskannState();
     DiskannState& s = *h->diskann;
     s.free_index();
-    s.d_adj = d_adj; s.metric = metric; s.r = r; s.l = l; s.alpha = alpha; s.n = n; s.entry = entry;
+    s.d_adj = std::move(d_adj); s.metric = metric; s.r = r; s.l = l; s.alpha = alpha; s.n = n; s.entry = entry;
     return LYNSE_OK;
 }
 
@@ -128,29 +127,26 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
     const uint32_t Bmax = (uint32_t)std::min<uint64_t>(VAMANA_BATCH, n);
     uint32_t P = 2;
     while (P < Bmax * r) P <<= 1;
-    uint32_t *d_adj = nullptr, *d_order = nullptr, *d_small = nullptr, *d_vis = nullptr, *d_beam_n = nullptr, *d_scored = nullptr, *d_status = nullptr;
-    uint64_t *d_beam = nullptr, *d_ckeys = nullptr;
-    float* d_pairs = nullptr;
-    GraphFree fr;
-    fr.ps = {(void**)&d_adj, (void**)&d_order, (void**)&d_small, (void**)&d_vis, (void**)&d_beam_n, (void**)&d_scored, (void**)&d_status,
-             (void**)&d_beam, (void**)&d_ckeys, (void**)&d_pairs};
-    LY_HIP(hipMalloc(&d_adj, std::max<size_t>((size_t)n * r, 1) * 4));
-    LY_TRY(h2d_done(d_adj, dr.adj0.data(), (size_t)n * r * 4));
-    LY_HIP(hipMalloc(&d_status, 4));
-    LY_TRY(memset_done(d_status, 0, 4));
+    DevBuf<uint32_t> d_adj, d_order, d_small, d_vis, d_beam_n, d_scored, d_status;
+    DevBuf<uint64_t> d_beam, d_ckeys;
+    DevBuf<float> d_pairs;
+    LY_TRY(d_adj.alloc((size_t)n * r));
+    LY_TRY(h2d_done(d_adj.p, dr.adj0.data(), (size_t)n * r * 4));
+    LY_TRY(d_status.alloc(1));
+    LY_TRY(memset_done(d_status.p, 0, 4));
     // rule 2: the entry point
     uint32_t entry = 0;
     if (n > 1) {
         const uint32_t nr = (uint32_t)dr.refs.size(), nc = (uint32_t)dr.cands.size();
-        LY_HIP(hipMalloc(&d_small, (size_t)(nr + nc) * 4));
-        LY_HIP(hipMalloc(&d_pairs, (size_t)nr * nc * 4));
-        LY_TRY(h2d_done(d_small, dr.refs.data(), (size_t)nr * 4));
-        LY_TRY(h2d_done(d_small + nr, dr.cands.data(), (size_t)nc * 4));
-        LY_TRY(launch_lds<k_vamana_pairs>(dim3(nc), dim3(64), (size_t)D * 4, st, (const float*)h->rows, h->ld, D, metric, (const uint32_t*)(d_small + nr),
-                                          (const uint32_t*)d_small, nr, d_pairs));
+        LY_TRY(d_small.alloc((size_t)(nr + nc)));
+        LY_TRY(d_pairs.alloc((size_t)nr * nc));
+        LY_TRY(h2d_done(d_small.p, dr.refs.data(), (size_t)nr * 4));
+        LY_TRY(h2d_done(d_small.p + nr, dr.cands.data(), (size_t)nc * 4));
+        LY_TRY(launch_lds<k_vamana_pairs>(dim3(nc), dim3(64), (size_t)D * 4, st, (const float*)h->rows, h->ld, D, metric, (const uint32_t*)(d_small.p + nr),
+                                          (const uint32_t*)d_small.p, nr, d_pairs.p));
         LY_HIP(hipStreamSynchronize(st));
         std::vector<float> pairs((size_t)nr * nc);
-        LY_HIP(hipMemcpy(pairs.data(), d_pairs, pairs.size() * 4, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(pairs.data(), d_pairs.p, pairs.size() * 4, hipMemcpyDeviceToHost));
         entry = dr.cands[0];
         float best_sum = LY_INF;
         for (uint32_t c = 0; c < nc; ++c) {
@@ -164,13 +160,13 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
         auto pos = std::find(dr.order.begin(), dr.order.end(), entry);
         if (pos != dr.order.end()) std::swap(dr.order[0], *pos);
     }
-    LY_HIP(hipMalloc(&d_order, (size_t)n * 4));
-    LY_TRY(h2d_done(d_order, dr.order.data(), (size_t)n * 4));
-    LY_HIP(hipMalloc(&d_vis, (size_t)Bmax * vis_words * 4));
-    LY_HIP(hipMalloc(&d_beam, (size_t)Bmax * ef_b * 8));
-    LY_HIP(hipMalloc(&d_beam_n, (size_t)Bmax * 4));
-    LY_HIP(hipMalloc(&d_scored, (size_t)Bmax * 4));
-    LY_HIP(hipMalloc(&d_ckeys, (size_t)P * 8));
+    LY_TRY(d_order.alloc((size_t)n));
+    LY_TRY(h2d_done(d_order.p, dr.order.data(), (size_t)n * 4));
+    LY_TRY(d_vis.alloc((size_t)Bmax * vis_words));
+    LY_TRY(d_beam.alloc((size_t)Bmax * ef_b));
+    LY_TRY(d_beam_n.alloc((size_t)Bmax));
+    LY_TRY(d_scored.alloc((size_t)Bmax));
+    LY_TRY(d_ckeys.alloc((size_t)P));
     // rule 5: a batch is four launches and a clear on one stream; the host waits once, at the end (per stage with profiling on)
     const bool timed = h->profiling.load();
     double st_us[3] = {0.0, 0.0, 0.0};
@@ -182,24 +178,24 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
         for (uint64_t b0 = 0; b0 < n && !stop; b0 += VAMANA_BATCH) {
             const uint32_t B = (uint32_t)std::min<uint64_t>(VAMANA_BATCH, n - b0);
             double t0 = timed ? graph_now_us() : 0.0;
-            LY_HIP(hipMemsetAsync(d_vis, 0, (size_t)B * vis_words * 4, st));
+            LY_HIP(hipMemsetAsync(d_vis.p, 0, (size_t)B * vis_words * 4, st));
             VamanaSearchArgs sa{};
-            sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = metric; sa.Q = nullptr; sa.qids = d_order + b0; sa.k = 0; sa.ef = ef_b; sa.r = r;
-            sa.anchors = DISKANN_BUILD_ANCHORS; sa.entry = entry; sa.n = n; sa.adj = d_adj; sa.vis = d_vis; sa.vis_words = vis_words;
-            sa.out_beam = d_beam; sa.out_beam_n = d_beam_n; sa.out_scored = d_scored; sa.status = d_status;
+            sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = metric; sa.Q = nullptr; sa.qids = d_order.p + b0; sa.k = 0; sa.ef = ef_b; sa.r = r;
+            sa.anchors = DISKANN_BUILD_ANCHORS; sa.entry = entry; sa.n = n; sa.adj = d_adj.p; sa.vis = d_vis.p; sa.vis_words = vis_words;
+            sa.out_beam = d_beam.p; sa.out_beam_n = d_beam_n.p; sa.out_scored = d_scored.p; sa.status = d_status.p;
             LY_TRY(launch_lds<k_vamana_search>(dim3(B), dim3(64), s_lds, st, sa));
             if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = graph_now_us(); st_us[0] += t1 - t0; t0 = t1; }
             VamanaPruneArgs pa{};
-            pa.V = h->rows; pa.ld = h->ld; pa.D = D; pa.metric = metric; pa.r = r; pa.cap = cap; pa.alpha = al; pa.adj = d_adj; pa.items = d_order + b0;
-            pa.beam = d_beam; pa.beam_n = d_beam_n; pa.beam_stride = ef_b;
+            pa.V = h->rows; pa.ld = h->ld; pa.D = D; pa.metric = metric; pa.r = r; pa.cap = cap; pa.alpha = al; pa.adj = d_adj.p; pa.items = d_order.p + b0;
+            pa.beam = d_beam.p; pa.beam_n = d_beam_n.p; pa.beam_stride = ef_b;
             LY_TRY(launch_lds<k_vamana_prune>(dim3(B), dim3(64), p_lds, st, pa));
             if (timed) { LY_HIP(hipStreamSynchronize(st)); const double t1 = graph_now_us(); st_us[1] += t1 - t0; t0 = t1; }
             uint32_t Pb = 2;
             while (Pb < B * r) Pb <<= 1;
             VamanaCommitArgs ca{};
-            ca.adj = d_adj; ca.r = r; ca.B = B; ca.P = Pb; ca.items = d_order + b0; ca.ckeys = d_ckeys;
+            ca.adj = d_adj.p; ca.r = r; ca.B = B; ca.P = Pb; ca.items = d_order.p + b0; ca.ckeys = d_ckeys.p;
             LY_TRY(launch_lds<k_vamana_commit>(dim3(1), dim3(1024), (size_t)Pb * 8, st, ca));
-            pa.ckeys = d_ckeys; pa.n_ckeys = Pb; pa.beam = nullptr; pa.beam_n = nullptr;
+            pa.ckeys = d_ckeys.p; pa.n_ckeys = Pb; pa.beam = nullptr; pa.beam_n = nullptr;
             LY_TRY(launch_lds<k_vamana_prune>(dim3(Pb), dim3(64), p_lds, st, pa));   // every slot: a wave that heads no over-long run exits at once
             if (timed) { LY_HIP(hipStreamSynchronize(st)); st_us[2] += graph_now_us() - t0; }
             stop = ++batches == max_batches;
@@ -207,10 +203,9 @@ extern "C" int lynse_hip_flat_build_diskann(lynse_hip_flat* h, int metric, uint3
     }
     LY_HIP(hipStreamSynchronize(st));
     uint32_t status = 0;
-    LY_HIP(hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(&status, d_status.p, 4, hipMemcpyDeviceToHost));
     if (status) return set_error(LYNSE_ERR_INTERNAL, "DiskANN: the candidate set outgrew its 2 ef + 41 slots");
-    LY_TRY(diskann_install(h, d_adj, metric, r, l, alpha, n, entry));
-    d_adj = nullptr;
+    LY_TRY(diskann_install(h, std::move(d_adj), metric, r, l, alpha, n, entry));
     DiskannState& s = *h->diskann;
     s.b_search_us = st_us[0]; s.b_prune_us = st_us[1]; s.b_commit_us = st_us[2]; s.b_draws_us = draws_us; s.b_total_us = graph_now_us() - t_begin;
     return LYNSE_OK;
@@ -237,11 +232,10 @@ extern "C" int lynse_hip_flat_load_diskann(lynse_hip_flat* h, int metric, uint32
     std::vector<uint32_t> lists((size_t)n * r, GRAPH_PAD);
     for (uint64_t i = 0; i < n; ++i)
         LY_TRY(graph_take_list(adj + (size_t)i * r, r, n, "DiskANN: a neighbour beyond the rows of the graph", &lists[(size_t)i * r]));
-    uint32_t* d_adj = nullptr;
-    LY_HIP(hipMalloc(&d_adj, lists.size() * 4));
-    const int rc = h2d_done(d_adj, lists.data(), lists.size() * 4);
-    if (rc != LYNSE_OK) { (void)hipFree(d_adj); return rc; }
-    return diskann_install(h, d_adj, metric, r, l, 0.0f, n, entry);   // (alpha belongs to a build: a loaded graph reports 0)
+    DevBuf<uint32_t> d_adj;
+    LY_TRY(d_adj.alloc(lists.size()));
+    LY_TRY(h2d_done(d_adj.p, lists.data(), lists.size() * 4));
+    return diskann_install(h, std::move(d_adj), metric, r, l, 0.0f, n, entry);   // (alpha belongs to a build: a loaded graph reports 0)
 }
 
 // info = {metric, r, l, entry}, all 0 (and alpha, n_diskann 0) without an index
@@ -259,7 +253,7 @@ extern "C" int lynse_hip_flat_diskann_params(lynse_hip_flat* h, uint32_t* info, 
     *alpha = s.alpha;
     *n_diskann = s.n;
     LY_TRY(use_device(h));
-    if (adj) LY_HIP(hipMemcpy(adj, s.d_adj, (size_t)s.n * s.r * 4, hipMemcpyDeviceToHost));
+    if (adj) LY_HIP(hipMemcpy(adj, s.d_adj.p, (size_t)s.n * s.r * 4, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
@@ -308,7 +302,7 @@ extern "C" int lynse_hip_flat_search_diskann_f32(lynse_hip_flat* h, const float*
                         [&](const GraphSearchChunk& c) {
         VamanaSearchArgs a{};
         a.V = h->rows; a.ld = h->ld; a.D = h->dim; a.metric = metric; a.Q = c.Q; a.k = k; a.ef = ef; a.r = s.r; a.anchors = DISKANN_QUERY_ANCHORS;
-        a.entry = s.entry; a.n = s.n; a.adj = s.d_adj; a.vis = c.vis; a.vis_words = c.vis_words; a.out_rows = c.out_rows; a.out_dists = c.out_dists;
+        a.entry = s.entry; a.n = s.n; a.adj = s.d_adj.p; a.vis = c.vis; a.vis_words = c.vis_words; a.out_rows = c.out_rows; a.out_dists = c.out_dists;
         a.out_counts = c.out_counts; a.out_scored = c.out_scored; a.status = c.status;
         return launch_lds<k_vamana_search>(dim3(c.nqc), dim3(64), c.lds, c.st, a);
     });

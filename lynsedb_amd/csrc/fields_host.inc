@@ -6,16 +6,11 @@ constexpr uint32_t FIELD_MAX_COLUMNS = 4096;
 
 struct FieldColumn {
     uint64_t n = 0, n_arrays = 0, n_elems = 0;
-    uint8_t* d_tags = nullptr;
-    uint64_t* d_payloads = nullptr;
-    uint64_t* d_arr_ptr = nullptr;
-    uint8_t* d_etags = nullptr;
-    uint64_t* d_epayloads = nullptr;
-    void release() {
-        for (void* p : {(void*)d_tags, (void*)d_payloads, (void*)d_arr_ptr, (void*)d_etags, (void*)d_epayloads})
-            if (p) (void)hipFree(p);
-        *this = FieldColumn{};
-    }
+    DevBuf<uint8_t> tags;
+    DevBuf<uint64_t> payloads;
+    DevBuf<uint64_t> arr_ptr;
+    DevBuf<uint8_t> etags;
+    DevBuf<uint64_t> epayloads;
     uint64_t bytes() const { return n * 9 + (n_arrays ? (n_arrays + 1) * 8 : 0) + n_elems * 9; }
 };
 
@@ -26,13 +21,11 @@ struct lynse_hip_fields {
     hipStream_t stream = nullptr;
     std::vector<FieldColumn> cols;
     // the result of the last filter and the scratch of a filter
-    uint64_t* d_words = nullptr;
-    size_t words_cap = 0;
+    DevBuf<uint64_t> words;
     uint64_t n_words = 0;
-    unsigned long long* d_count = nullptr;
-    FieldLeafDev* d_leaves = nullptr;
-    uint64_t* d_aux = nullptr;
-    size_t aux_cap = 0;
+    DevBuf<unsigned long long> count;
+    DevBuf<FieldLeafDev> leaves;
+    DevBuf<uint64_t> aux;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
@@ -48,12 +41,13 @@ extern "C" int lynse_hip_fields_create(int device, lynse_hip_fields** out) {
     h->device = device;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&h->d_count, 8);
-    if (e == hipSuccess) e = hipMalloc(&h->d_leaves, sizeof(FieldLeafDev) * FIELD_MAX_LEAVES);
-    if (e != hipSuccess) {
+    const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    int rc = e == hipSuccess ? LYNSE_OK : set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_fields_create: ") + hipGetErrorString(e));
+    if (rc == LYNSE_OK) rc = h->count.alloc(1);
+    if (rc == LYNSE_OK) rc = h->leaves.alloc(FIELD_MAX_LEAVES);
+    if (rc != LYNSE_OK) {
         lynse_hip_fields_destroy(h);
-        return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_fields_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = h;
     return LYNSE_OK;
@@ -63,9 +57,6 @@ extern "C" int lynse_hip_fields_destroy(lynse_hip_fields* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (FieldColumn& c : h->cols) c.release();
-    for (void* p : {(void*)h->d_words, (void*)h->d_count, (void*)h->d_leaves, (void*)h->d_aux})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -98,28 +89,23 @@ extern "C" int lynse_hip_fields_set_column(lynse_hip_fields* h, uint32_t column,
     }
     std::lock_guard<std::mutex> lk(h->mu);
     LY_HIP(hipSetDevice(h->device));
-    if (column < h->cols.size()) h->cols[column].release();
+    if (column < h->cols.size()) h->cols[column] = FieldColumn{};
     if (n == 0) return LYNSE_OK;
     if (column >= h->cols.size()) h->cols.resize((size_t)column + 1);
     FieldColumn c;
-    auto fail = [&](int rc) {
-        c.release();
-        return rc;
+    auto up = [&](auto& dst, const void* src, size_t count) -> int {
+        LY_TRY(dst.alloc(count));
+        return h2d_done(dst.p, src, count * sizeof(*dst.p));
     };
-    auto up = [&](auto** dst, const void* src, size_t bytes) -> int {
-        LY_HIP(hipMalloc(dst, bytes));
-        return h2d_done(*dst, src, bytes);
-    };
-    int rc = up(&c.d_tags, tags, (size_t)n);
-    if (rc == LYNSE_OK) rc = up(&c.d_payloads, payloads, (size_t)n * 8);
-    if (rc == LYNSE_OK && n_arrays) rc = up(&c.d_arr_ptr, arr_ptr, ((size_t)n_arrays + 1) * 8);
-    if (rc == LYNSE_OK && n_elems) rc = up(&c.d_etags, elem_tags, (size_t)n_elems);
-    if (rc == LYNSE_OK && n_elems) rc = up(&c.d_epayloads, elem_payloads, (size_t)n_elems * 8);
-    if (rc != LYNSE_OK) return fail(rc);
+    LY_TRY(up(c.tags, tags, (size_t)n));
+    LY_TRY(up(c.payloads, payloads, (size_t)n));
+    if (n_arrays) LY_TRY(up(c.arr_ptr, arr_ptr, (size_t)n_arrays + 1));
+    if (n_elems) LY_TRY(up(c.etags, elem_tags, (size_t)n_elems));
+    if (n_elems) LY_TRY(up(c.epayloads, elem_payloads, (size_t)n_elems));
     c.n = n;
     c.n_arrays = n_arrays;
     c.n_elems = n_elems;
-    h->cols[column] = c;
+    h->cols[column] = std::move(c);
     return LYNSE_OK;
 }
 
@@ -127,7 +113,7 @@ extern "C" int lynse_hip_fields_drop_column(lynse_hip_fields* h, uint32_t column
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
     std::lock_guard<std::mutex> lk(h->mu);
     LY_HIP(hipSetDevice(h->device));
-    if (column < h->cols.size()) h->cols[column].release();
+    if (column < h->cols.size()) h->cols[column] = FieldColumn{};
     return LYNSE_OK;
 }
 
@@ -141,7 +127,7 @@ extern "C" int lynse_hip_fields_column_rows(lynse_hip_fields* h, uint32_t column
 extern "C" uint64_t lynse_hip_fields_hbm_bytes(lynse_hip_fields* h) {
     if (!h) return 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    uint64_t b = (uint64_t)h->words_cap * 8 + (uint64_t)h->aux_cap * 8;
+    uint64_t b = (uint64_t)h->words.cap * 8 + (uint64_t)h->aux.cap * 8;
     for (const FieldColumn& c : h->cols) b += c.bytes();
     return b;
 }
@@ -187,21 +173,21 @@ extern "C" int lynse_hip_fields_filter(lynse_hip_fields* h, uint64_t n, int comb
         if (s.column == LYNSE_FIELD_NO_COLUMN || s.column >= h->cols.size() || h->cols[s.column].n == 0) continue;   // a field no row carries
         const FieldColumn& c = h->cols[s.column];
         if (c.n != n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "field filter: a column does not hold n rows");
-        d.tags = c.d_tags;
-        d.payloads = c.d_payloads;
-        d.arr_ptr = c.d_arr_ptr;
-        d.etags = c.d_etags;
-        d.epayloads = c.d_epayloads;
+        d.tags = c.tags.p;
+        d.payloads = c.payloads.p;
+        d.arr_ptr = c.arr_ptr.p;
+        d.etags = c.etags.p;
+        d.epayloads = c.epayloads.p;
         d.n_arrays = c.n_arrays;
     }
     const uint64_t nw = (n + 63) / 64;
     h->n_words = 0;
     if (n == 0) return LYNSE_OK;
-    LY_TRY(ivf_grow(&h->d_words, &h->words_cap, (size_t)nw));
-    LY_TRY(ivf_grow(&h->d_aux, &h->aux_cap, (size_t)std::max<uint64_t>(1, aux_words)));
+    LY_TRY(h->words.reserve((size_t)nw));
+    LY_TRY(h->aux.reserve((size_t)std::max<uint64_t>(1, aux_words)));
     for (uint32_t l = 0; l < n_leaves; ++l) {
         const bool has_aux = leaves[l].kind == FLEAF_KEYSET || leaves[l].kind == FLEAF_STRTABLE;
-        dev[l].aux = has_aux ? h->d_aux + leaves[l].aux_off : nullptr;
+        dev[l].aux = has_aux ? h->aux.p + leaves[l].aux_off : nullptr;
         dev[l].aux_len = has_aux ? leaves[l].aux_len : 0;
     }
     for (hipEvent_t& e : h->ev)
@@ -212,16 +198,16 @@ extern "C" int lynse_hip_fields_filter(lynse_hip_fields* h, uint64_t n, int comb
         (void)hipStreamSynchronize(st);
         return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_fields_filter: ") + hipGetErrorString(e));
     };
-    if (aux_words) LY_TRY(queued(hipMemcpyAsync(h->d_aux, aux, (size_t)aux_words * 8, hipMemcpyHostToDevice, st)));
-    LY_TRY(queued(hipMemcpyAsync(h->d_leaves, dev, sizeof(FieldLeafDev) * n_leaves, hipMemcpyHostToDevice, st)));
-    LY_TRY(queued(hipMemsetAsync(h->d_count, 0, 8, st)));
+    if (aux_words) LY_TRY(queued(hipMemcpyAsync(h->aux.p, aux, (size_t)aux_words * 8, hipMemcpyHostToDevice, st)));
+    LY_TRY(queued(hipMemcpyAsync(h->leaves.p, dev, sizeof(FieldLeafDev) * n_leaves, hipMemcpyHostToDevice, st)));
+    LY_TRY(queued(hipMemsetAsync(h->count.p, 0, 8, st)));
     FieldFilterArgs a{};
-    a.leaves = h->d_leaves;
+    a.leaves = h->leaves.p;
     a.n_leaves = n_leaves;
     a.any = combine == LYNSE_FIELD_ANY ? 1u : 0u;
     a.n = n;
-    a.words = h->d_words;
-    a.count = h->d_count;
+    a.words = h->words.p;
+    a.count = h->count.p;
     // (grid-stride: at most 4 workgroups per CU, 262,144 rows a pass on 256 CUs)
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FIELD_NT - 1) / FIELD_NT, (uint64_t)h->num_cu * 4);
     LY_TRY(queued(hipEventRecord(h->ev[0], st)));
@@ -229,7 +215,7 @@ extern "C" int lynse_hip_fields_filter(lynse_hip_fields* h, uint64_t n, int comb
     LY_TRY(queued(hipGetLastError()));
     LY_TRY(queued(hipEventRecord(h->ev[1], st)));
     unsigned long long count = 0;
-    LY_TRY(queued(hipMemcpyAsync(&count, h->d_count, 8, hipMemcpyDeviceToHost, st)));
+    LY_TRY(queued(hipMemcpyAsync(&count, h->count.p, 8, hipMemcpyDeviceToHost, st)));
     LY_HIP(hipStreamSynchronize(st));
     if (out_kernel_us) {
         float ms = 0.f;
@@ -248,14 +234,14 @@ extern "C" int lynse_hip_fields_words(lynse_hip_fields* h, uint64_t* out_words, 
     if (n_words == 0) return LYNSE_OK;
     if (!out_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     LY_HIP(hipSetDevice(h->device));
-    LY_HIP(hipMemcpy(out_words, h->d_words, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(out_words, h->words.p, (size_t)n_words * 8, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
 extern "C" int lynse_hip_fields_words_device(lynse_hip_fields* h, const uint64_t** out_d_words, uint64_t* out_n_words) {
     if (!h || !out_d_words || !out_n_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    *out_d_words = h->n_words ? h->d_words : nullptr;
+    *out_d_words = h->n_words ? h->words.p : nullptr;
     *out_n_words = h->n_words;
     return LYNSE_OK;
 }
@@ -286,20 +272,16 @@ struct lynse_hip_rowmap {
     int device = 0;
     uint32_t num_cu = 256;
     hipStream_t stream = nullptr;
-    uint32_t* d_row_of = nullptr;
-    size_t row_cap = 0;
+    DevBuf<uint32_t> row_of;
     uint64_t n_out = 0;
     uint64_t bound = 0;      // 1 + the largest row_of entry that is not ROWMAP_NONE, 0 without one: what n_src + n_tail must reach
     bool has_map = false;
-    uint64_t* d_src = nullptr;   // source words given from host memory
-    size_t src_cap = 0;
-    uint64_t* d_tail = nullptr;
-    size_t tail_cap = 0;
-    uint64_t* d_words = nullptr;
-    size_t words_cap = 0;
+    DevBuf<uint64_t> src;   // source words given from host memory
+    DevBuf<uint64_t> tail;
+    DevBuf<uint64_t> words;
     uint64_t n_words = 0;
     bool has_words = false;
-    unsigned long long* d_count = nullptr;
+    DevBuf<unsigned long long> count;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
@@ -315,11 +297,12 @@ extern "C" int lynse_hip_rowmap_create(int device, lynse_hip_rowmap** out) {
     h->device = device;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&h->d_count, 8);
-    if (e != hipSuccess) {
+    const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    int rc = e == hipSuccess ? LYNSE_OK : set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_rowmap_create: ") + hipGetErrorString(e));
+    if (rc == LYNSE_OK) rc = h->count.alloc(1);
+    if (rc != LYNSE_OK) {
         lynse_hip_rowmap_destroy(h);
-        return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_rowmap_create: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = h;
     return LYNSE_OK;
@@ -329,8 +312,6 @@ extern "C" int lynse_hip_rowmap_destroy(lynse_hip_rowmap* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_row_of, (void*)h->d_src, (void*)h->d_tail, (void*)h->d_words, (void*)h->d_count})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -351,8 +332,8 @@ extern "C" int lynse_hip_rowmap_set(lynse_hip_rowmap* h, const uint32_t* row_of,
     h->has_map = false;
     h->has_words = false;
     h->n_words = 0;
-    LY_TRY(ivf_grow(&h->d_row_of, &h->row_cap, (size_t)std::max<uint64_t>(1, n_out)));
-    if (n_out) LY_TRY(h2d_done(h->d_row_of, row_of, (size_t)n_out * 4));
+    LY_TRY(h->row_of.reserve((size_t)std::max<uint64_t>(1, n_out)));
+    if (n_out) LY_TRY(h2d_done(h->row_of.p, row_of, (size_t)n_out * 4));
     h->n_out = n_out;
     h->bound = bound;
     h->has_map = true;
@@ -370,7 +351,7 @@ extern "C" int lynse_hip_rowmap_len(lynse_hip_rowmap* h, uint64_t* out_rows, uin
 extern "C" uint64_t lynse_hip_rowmap_hbm_bytes(lynse_hip_rowmap* h) {
     if (!h) return 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    return (uint64_t)h->row_cap * 4 + ((uint64_t)h->src_cap + h->tail_cap + h->words_cap) * 8;
+    return (uint64_t)h->row_of.cap * 4 + ((uint64_t)h->src.cap + h->tail.cap + h->words.cap) * 8;
 }
 
 extern "C" int lynse_hip_rowmap_remap(lynse_hip_rowmap* h, const uint64_t* src_words, uint64_t n_src_words, uint64_t n_src, int src_on_device,
@@ -396,9 +377,9 @@ extern "C" int lynse_hip_rowmap_remap(lynse_hip_rowmap* h, const uint64_t* src_w
         h->has_words = true;
         return LYNSE_OK;
     }
-    LY_TRY(ivf_grow(&h->d_words, &h->words_cap, (size_t)nw));
-    if (n_tail_words) LY_TRY(ivf_grow(&h->d_tail, &h->tail_cap, (size_t)n_tail_words));
-    if (!src_on_device && n_src_words) LY_TRY(ivf_grow(&h->d_src, &h->src_cap, (size_t)n_src_words));
+    LY_TRY(h->words.reserve((size_t)nw));
+    if (n_tail_words) LY_TRY(h->tail.reserve((size_t)n_tail_words));
+    if (!src_on_device && n_src_words) LY_TRY(h->src.reserve((size_t)n_src_words));
     for (hipEvent_t& e : h->ev)
         if (!e) LY_HIP(hipEventCreate(&e));
     hipStream_t st = h->stream;
@@ -407,18 +388,18 @@ extern "C" int lynse_hip_rowmap_remap(lynse_hip_rowmap* h, const uint64_t* src_w
         (void)hipStreamSynchronize(st);
         return set_error(LYNSE_ERR_DEVICE, std::string("lynse_hip_rowmap_remap: ") + hipGetErrorString(e));
     };
-    if (!src_on_device && n_src_words) LY_TRY(queued(hipMemcpyAsync(h->d_src, src_words, (size_t)n_src_words * 8, hipMemcpyHostToDevice, st)));
-    if (n_tail_words) LY_TRY(queued(hipMemcpyAsync(h->d_tail, tail_words, (size_t)n_tail_words * 8, hipMemcpyHostToDevice, st)));
-    LY_TRY(queued(hipMemsetAsync(h->d_count, 0, 8, st)));
+    if (!src_on_device && n_src_words) LY_TRY(queued(hipMemcpyAsync(h->src.p, src_words, (size_t)n_src_words * 8, hipMemcpyHostToDevice, st)));
+    if (n_tail_words) LY_TRY(queued(hipMemcpyAsync(h->tail.p, tail_words, (size_t)n_tail_words * 8, hipMemcpyHostToDevice, st)));
+    LY_TRY(queued(hipMemsetAsync(h->count.p, 0, 8, st)));
     BitsetRemapArgs a{};
-    a.row_of = h->d_row_of;
+    a.row_of = h->row_of.p;
     a.n_out = n_out;
-    a.src = src_on_device ? src_words : h->d_src;
+    a.src = src_on_device ? src_words : h->src.p;
     a.n_src = n_src;
-    a.tail = n_tail_words ? h->d_tail : nullptr;
+    a.tail = n_tail_words ? h->tail.p : nullptr;
     a.n_tail = n_tail;
-    a.words = h->d_words;
-    a.count = h->d_count;
+    a.words = h->words.p;
+    a.count = h->count.p;
     // (grid-stride as k_field_filter: at most 4 workgroups per CU, 262,144 rows a pass on 256 CUs)
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_out + FIELD_NT - 1) / FIELD_NT, (uint64_t)h->num_cu * 4);
     LY_TRY(queued(hipEventRecord(h->ev[0], st)));
@@ -426,7 +407,7 @@ extern "C" int lynse_hip_rowmap_remap(lynse_hip_rowmap* h, const uint64_t* src_w
     LY_TRY(queued(hipGetLastError()));
     LY_TRY(queued(hipEventRecord(h->ev[1], st)));
     unsigned long long count = 0;
-    LY_TRY(queued(hipMemcpyAsync(&count, h->d_count, 8, hipMemcpyDeviceToHost, st)));
+    LY_TRY(queued(hipMemcpyAsync(&count, h->count.p, 8, hipMemcpyDeviceToHost, st)));
     LY_HIP(hipStreamSynchronize(st));
     if (out_kernel_us) {
         float ms = 0.f;
@@ -446,14 +427,14 @@ extern "C" int lynse_hip_rowmap_words(lynse_hip_rowmap* h, uint64_t* out_words, 
     if (n_words == 0) return LYNSE_OK;
     if (!out_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     LY_HIP(hipSetDevice(h->device));
-    LY_HIP(hipMemcpy(out_words, h->d_words, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(out_words, h->words.p, (size_t)n_words * 8, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
 extern "C" int lynse_hip_rowmap_words_device(lynse_hip_rowmap* h, const uint64_t** out_d_words, uint64_t* out_n_words) {
     if (!h || !out_d_words || !out_n_words) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    *out_d_words = h->n_words ? h->d_words : nullptr;
+    *out_d_words = h->n_words ? h->words.p : nullptr;
     *out_n_words = h->n_words;
     return LYNSE_OK;
 }

@@ -22,8 +22,6 @@ static inline double graph_now_us() {
     return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3;
 }
 
-// the device buffers of a build, freed on every way out
-struct GraphFree { std::vector<void**> ps; ~GraphFree() { for (void** p : ps) if (*p) (void)hipFree(*p); } };
 struct GraphEvFree { hipEvent_t &a, &b; ~GraphEvFree() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } };
 
 // One list of a loaded graph brought into the stored form: GRAPH_PAD entries dropped, a neighbour named twice kept once (its first
@@ -46,16 +44,10 @@ static int graph_take_list(const uint32_t* src, uint32_t cap, uint64_t n, const 
 
 // The scratch of an index's searches, and what they measured with profiling on
 struct GraphSearchScratch {
-    float *d_q = nullptr, *d_dists = nullptr;
-    uint64_t* d_rows = nullptr;
-    uint32_t *d_vis = nullptr, *d_counts = nullptr, *d_status = nullptr;
-    size_t q_cap = 0, dists_cap = 0, rows_cap = 0, vis_cap = 0, counts_cap = 0;
+    DevBuf<float> q, dists;
+    DevBuf<uint64_t> rows;
+    DevBuf<uint32_t> vis, counts, status;
     double searches = 0.0, search_us = 0.0, scored = 0.0;   // searches timed, their kernel microseconds (HIP events), distances scored
-
-    ~GraphSearchScratch() {
-        for (void* p : {(void*)d_q, (void*)d_dists, (void*)d_rows, (void*)d_vis, (void*)d_counts, (void*)d_status})
-            if (p) (void)hipFree(p);
-    }
 };
 
 // one chunk of queries as its kernel sees it: device pointers, the visited bitmaps zeroed
@@ -81,33 +73,33 @@ static int graph_search(lynse_hip_flat* h, GraphSearchScratch& s, uint64_t n, si
     const uint32_t D = h->dim;
     const uint32_t vis_words = (uint32_t)((n + 31) / 32);
     const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({nq, (256ull << 20) / ((uint64_t)vis_words * 4), (256ull << 20) / ((uint64_t)k * 12), 1ull << 20}));
-    LY_TRY(ivf_grow(&s.d_q, &s.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&s.d_vis, &s.vis_cap, (size_t)qc * vis_words));
-    LY_TRY(ivf_grow(&s.d_rows, &s.rows_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_dists, &s.dists_cap, (size_t)qc * k));
-    LY_TRY(ivf_grow(&s.d_counts, &s.counts_cap, (size_t)qc * 2));   // counts, then the distances scored
-    if (!s.d_status) LY_HIP(hipMalloc(&s.d_status, 4));
+    LY_TRY(s.q.reserve((size_t)qc * D));
+    LY_TRY(s.vis.reserve((size_t)qc * vis_words));
+    LY_TRY(s.rows.reserve((size_t)qc * k));
+    LY_TRY(s.dists.reserve((size_t)qc * k));
+    LY_TRY(s.counts.reserve((size_t)qc * 2));   // counts, then the distances scored
+    LY_TRY(s.status.reserve(1));
     hipStream_t st = cur(h).stream;
     const bool timed = h->profiling.load();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timed) { LY_HIP(hipEventCreate(&e0)); LY_HIP(hipEventCreate(&e1)); }
     GraphEvFree evfree{e0, e1};
     std::vector<uint32_t> scored;
-    LY_HIP(hipMemsetAsync(s.d_status, 0, 4, st));
+    LY_HIP(hipMemsetAsync(s.status.p, 0, 4, st));
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(s.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemsetAsync(s.d_vis, 0, (size_t)nqc * vis_words * 4, st));
-        const GraphSearchChunk c{nqc, s.d_q, s.d_vis, vis_words, s.d_rows, s.d_dists, s.d_counts, s.d_counts + qc, s.d_status, lds, st};
+        LY_HIP(hipMemcpyAsync(s.q.p, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(s.vis.p, 0, (size_t)nqc * vis_words * 4, st));
+        const GraphSearchChunk c{nqc, s.q.p, s.vis.p, vis_words, s.rows.p, s.dists.p, s.counts.p, s.counts.p + qc, s.status.p, lds, st};
         if (timed) LY_HIP(hipEventRecord(e0, st));
         LY_TRY(launch(c));
         if (timed) LY_HIP(hipEventRecord(e1, st));
-        LY_HIP(hipMemcpyAsync(out_rows + q0 * k, s.d_rows, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_dists + q0 * k, s.d_dists, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
-        LY_HIP(hipMemcpyAsync(out_counts + q0, s.d_counts, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(out_rows + q0 * k, s.rows.p, (size_t)nqc * k * 8, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(out_dists + q0 * k, s.dists.p, (size_t)nqc * k * 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(out_counts + q0, s.counts.p, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
         if (timed) {
             scored.resize(nqc);
-            LY_HIP(hipMemcpyAsync(scored.data(), s.d_counts + qc, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(scored.data(), s.counts.p + qc, (size_t)nqc * 4, hipMemcpyDeviceToHost, st));
         }
         LY_TRY(stream_wait(st));
         if (timed) {
@@ -118,7 +110,7 @@ static int graph_search(lynse_hip_flat* h, GraphSearchScratch& s, uint64_t n, si
         }
     }
     uint32_t status = 0;
-    LY_HIP(hipMemcpy(&status, s.d_status, 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(&status, s.status.p, 4, hipMemcpyDeviceToHost));
     if (status) return set_error(LYNSE_ERR_INTERNAL, outgrew);
     if (timed) s.searches += 1;
     return LYNSE_OK;

@@ -19,7 +19,7 @@ struct HnswState {
     uint64_t n = 0;                       // the graph covers the first n rows of the handle
     std::vector<uint32_t> levels;         // [n]
     std::vector<uint32_t> upper_node, upper_level;   // ascending (node, level), levels >= 1
-    uint32_t *d_adj0 = nullptr, *d_upper_off = nullptr, *d_upper_adj = nullptr;
+    DevBuf<uint32_t> d_adj0, d_upper_off, d_upper_adj;
     // a built graph (not a loaded one) can be extended: the parameters of rule 1-3 and the levels' forward lists
     bool extendable = false;
     uint32_t ef_construction = 0;
@@ -31,11 +31,11 @@ struct HnswState {
     // the last build, microseconds of host time around synchronised stages
     double cand_us = 0.0, select_us = 0.0, reverse_us = 0.0;
 
-    bool built() const { return d_adj0 != nullptr; }
+    bool built() const { return d_adj0.p != nullptr; }
     void free_device() {
-        for (void* p : {(void*)d_adj0, (void*)d_upper_off, (void*)d_upper_adj})
-            if (p) (void)hipFree(p);
-        d_adj0 = d_upper_off = d_upper_adj = nullptr;
+        d_adj0.reset();
+        d_upper_off.reset();
+        d_upper_adj.reset();
     }
     void drop_keep() {
         extendable = false;
@@ -121,26 +121,20 @@ struct HnswGraph {
 static int hnsw_install(lynse_hip_flat* h, HnswGraph& gph, int metric, uint32_t ef_search, bool keep_forward) {
     if (!h->hnsw) h->hnsw = new HnswState();
     HnswState& s = *h->hnsw;
-    uint32_t *d_adj0 = nullptr, *d_off = nullptr, *d_up = nullptr;
-    auto fail = [&](int rc) {
-        for (void* p : {(void*)d_adj0, (void*)d_off, (void*)d_up})
-            if (p) (void)hipFree(p);
-        return rc;
-    };
-    auto up = [&](uint32_t** d, const std::vector<uint32_t>& v) -> int {
-        LY_HIP(hipMalloc(d, std::max<size_t>(v.size(), 1) * 4));
-        if (!v.empty()) LY_TRY(h2d_done(*d, v.data(), v.size() * 4));
+    DevBuf<uint32_t> d_adj0, d_off, d_up;
+    auto up = [&](DevBuf<uint32_t>& d, const std::vector<uint32_t>& v) -> int {
+        LY_TRY(d.alloc(v.size()));
+        if (!v.empty()) LY_TRY(h2d_done(d.p, v.data(), v.size() * 4));
         return LYNSE_OK;
     };
-    int rc = up(&d_adj0, gph.adj0);
-    if (rc == LYNSE_OK) rc = up(&d_off, gph.upper_off);
-    if (rc == LYNSE_OK) rc = up(&d_up, gph.upper_adj);
-    if (rc != LYNSE_OK) return fail(rc);
+    LY_TRY(up(d_adj0, gph.adj0));
+    LY_TRY(up(d_off, gph.upper_off));
+    LY_TRY(up(d_up, gph.upper_adj));
     s.free_device();
     if (!keep_forward) s.drop_keep();
     s.metric = metric; s.m = gph.m; s.ef_search = ef_search; s.entry = gph.entry; s.top_level = gph.top_level; s.n = gph.n;
     s.levels.swap(gph.levels); s.upper_node.swap(gph.upper_node); s.upper_level.swap(gph.upper_level);
-    s.d_adj0 = d_adj0; s.d_upper_off = d_off; s.d_upper_adj = d_up;
+    s.d_adj0 = std::move(d_adj0); s.d_upper_off = std::move(d_off); s.d_upper_adj = std::move(d_up);
     return LYNSE_OK;
 }
 
@@ -177,33 +171,31 @@ static int hnsw_level_forward(const HnswLevelJob& jb, const uint32_t* q_nodes, u
     const uint32_t cap = jb.cap(), D = h->dim, ask = jb.ef_construction + 1, level = jb.level;
     if (nq == 0) return LYNSE_OK;
     hipStream_t st = cur(h).stream;
-    uint32_t* d_items = nullptr;
-    float *d_q = nullptr, *d_cd = nullptr, *d_fd = nullptr, *d_thr = nullptr;
-    uint64_t* d_cr = nullptr;
-    uint32_t *d_cc = nullptr, *d_fid = nullptr;
-    GraphFree fr;
-    fr.ps = {(void**)&d_items, (void**)&d_q, (void**)&d_cd, (void**)&d_fd, (void**)&d_thr, (void**)&d_cr, (void**)&d_cc, (void**)&d_fid};
-    LY_HIP(hipMalloc(&d_items, (size_t)nq * 4));
-    LY_TRY(h2d_done(d_items, q_nodes, (size_t)nq * 4));
+    DevBuf<uint32_t> d_items;
+    DevBuf<float> d_q, d_cd, d_fd, d_thr;
+    DevBuf<uint64_t> d_cr;
+    DevBuf<uint32_t> d_cc, d_fid;
+    LY_TRY(d_items.alloc((size_t)nq));
+    LY_TRY(h2d_done(d_items.p, q_nodes, (size_t)nq * 4));
     // queries per pass: the candidate lists of a pass stay under 256 MiB, its queries under 128 MiB
     const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)nq, (256ull << 20) / ((uint64_t)ask * 12), (128ull << 20) / ((uint64_t)D * 4)}));
-    LY_HIP(hipMalloc(&d_q, (size_t)qc * D * 4));
-    LY_HIP(hipMalloc(&d_cr, (size_t)qc * ask * 8));
-    LY_HIP(hipMalloc(&d_cd, (size_t)qc * ask * 4));
-    LY_HIP(hipMalloc(&d_cc, (size_t)qc * 4));
-    LY_HIP(hipMalloc(&d_fid, (size_t)nq * cap * 4));
-    LY_HIP(hipMalloc(&d_fd, (size_t)nq * cap * 4));
-    LY_HIP(hipMalloc(&d_thr, (size_t)nq * 4));
+    LY_TRY(d_q.alloc((size_t)qc * D));
+    LY_TRY(d_cr.alloc((size_t)qc * ask));
+    LY_TRY(d_cd.alloc((size_t)qc * ask));
+    LY_TRY(d_cc.alloc((size_t)qc));
+    LY_TRY(d_fid.alloc((size_t)nq * cap));
+    LY_TRY(d_fd.alloc((size_t)nq * cap));
+    LY_TRY(d_thr.alloc((size_t)nq));
     const size_t sel_lds = 512 + (size_t)D * 4;
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint64_t nqc = std::min<uint64_t>(qc, nq - q0);
         double t0 = graph_now_us();
         hipLaunchKernelGGL(k_hnsw_gather, dim3((uint32_t)std::min<uint64_t>((nqc * D + 255) / 256, (uint64_t)h->num_cu * 32)), dim3(256), 0, st,
-                           h->rows, h->ld, D, d_items + q0, 0u, nqc, d_q);
+                           h->rows, h->ld, D, d_items.p + q0, 0u, nqc, d_q.p);
         LY_HIP(hipGetLastError());
         LY_HIP(hipStreamSynchronize(st));
         // rule 2: the exact searches of the handle, single-row kernels (the caller pinned the SINGLE ip form), canonical (d, row) order
-        LY_TRY(search_impl(h, d_q, false, nqc, ask, jb.metric, d_cr, d_cd, d_cc, true, nullptr, nullptr, level > 0 ? (uint64_t)jb.ns : 0, level > 0,
+        LY_TRY(search_impl(h, d_q.p, false, nqc, ask, jb.metric, d_cr.p, d_cd.p, d_cc.p, true, nullptr, nullptr, level > 0 ? (uint64_t)jb.ns : 0, level > 0,
                            level > 0 ? jb.words.data() : nullptr, jb.words.size(), true));
         LY_HIP(hipStreamSynchronize(st));
         double t1 = graph_now_us();
@@ -211,16 +203,16 @@ static int hnsw_level_forward(const HnswLevelJob& jb, const uint32_t* q_nodes, u
         // rule 3: the forward lists
         HnswSelectArgs sa{};
         sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = jb.metric; sa.cap = cap;
-        sa.item_node = d_items + q0; sa.rows64 = d_cr; sa.d64 = d_cd; sa.cnt64 = d_cc; sa.stride = ask;
-        sa.out_ids = d_fid + q0 * cap; sa.out_d = d_fd + q0 * cap; sa.out_thr = d_thr + q0;
+        sa.item_node = d_items.p + q0; sa.rows64 = d_cr.p; sa.d64 = d_cd.p; sa.cnt64 = d_cc.p; sa.stride = ask;
+        sa.out_ids = d_fid.p + q0 * cap; sa.out_d = d_fd.p + q0 * cap; sa.out_thr = d_thr.p + q0;
         LY_TRY(launch_lds<k_hnsw_select>(dim3((uint32_t)nqc), dim3(64), sel_lds, st, sa));
         LY_HIP(hipStreamSynchronize(st));
         jb.times3[1] += graph_now_us() - t1;
     }
     double t2 = graph_now_us();
-    LY_HIP(hipMemcpy(fid, d_fid, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
-    LY_HIP(hipMemcpy(fd, d_fd, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
-    LY_HIP(hipMemcpy(thr, d_thr, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(fid, d_fid.p, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(fd, d_fd.p, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(thr, d_thr.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     jb.times3[2] += graph_now_us() - t2;
     return LYNSE_OK;
 }
@@ -232,9 +224,7 @@ static int hnsw_level_adjacency(const HnswLevelJob& jb, HnswGraph& gph, const ui
     lynse_hip_flat* h = jb.h;
     const uint32_t ns = jb.ns, cap = jb.cap(), D = h->dim, level = jb.level;
     hipStream_t st = cur(h).stream;
-    uint32_t *d_uid = nullptr, *d_oid = nullptr; float *d_ud = nullptr, *d_od = nullptr; uint64_t* d_uoff = nullptr;
-    GraphFree fr;
-    fr.ps = {(void**)&d_uid, (void**)&d_ud, (void**)&d_uoff, (void**)&d_oid, (void**)&d_od};
+    DevBuf<uint32_t> d_uid, d_oid; DevBuf<float> d_ud, d_od; DevBuf<uint64_t> d_uoff;
     double t2 = graph_now_us();
     auto want = [&](uint32_t t) { return !dirty || dirty[t]; };
     std::vector<uint64_t> off((size_t)ns + 1, 0);
@@ -276,21 +266,21 @@ static int hnsw_level_adjacency(const HnswLevelJob& jb, HnswGraph& gph, const ui
     if (!over.empty()) {
         double t3 = graph_now_us();
         const size_t no = over.size();
-        LY_HIP(hipMalloc(&d_uid, uid.size() * 4));
-        LY_HIP(hipMalloc(&d_ud, ud.size() * 4));
-        LY_HIP(hipMalloc(&d_uoff, uoff.size() * 8));
-        LY_HIP(hipMalloc(&d_oid, no * cap * 4));
-        LY_HIP(hipMalloc(&d_od, no * cap * 4));
-        LY_TRY(h2d_done(d_uid, uid.data(), uid.size() * 4));
-        LY_TRY(h2d_done(d_ud, ud.data(), ud.size() * 4));
-        LY_TRY(h2d_done(d_uoff, uoff.data(), uoff.size() * 8));
+        LY_TRY(d_uid.alloc(uid.size()));
+        LY_TRY(d_ud.alloc(ud.size()));
+        LY_TRY(d_uoff.alloc(uoff.size()));
+        LY_TRY(d_oid.alloc(no * cap));
+        LY_TRY(d_od.alloc(no * cap));
+        LY_TRY(h2d_done(d_uid.p, uid.data(), uid.size() * 4));
+        LY_TRY(h2d_done(d_ud.p, ud.data(), ud.size() * 4));
+        LY_TRY(h2d_done(d_uoff.p, uoff.data(), uoff.size() * 8));
         HnswSelectArgs sa{};
         sa.V = h->rows; sa.ld = h->ld; sa.D = D; sa.metric = jb.metric; sa.cap = cap;
-        sa.ids32 = d_uid; sa.d32 = d_ud; sa.offs = d_uoff; sa.out_ids = d_oid; sa.out_d = d_od;
+        sa.ids32 = d_uid.p; sa.d32 = d_ud.p; sa.offs = d_uoff.p; sa.out_ids = d_oid.p; sa.out_d = d_od.p;
         LY_TRY(launch_lds<k_hnsw_select>(dim3((uint32_t)no), dim3(64), 512 + (size_t)D * 4, st, sa));
         LY_HIP(hipStreamSynchronize(st));
         std::vector<uint32_t> oid(no * cap);
-        LY_HIP(hipMemcpy(oid.data(), d_oid, oid.size() * 4, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(oid.data(), d_oid.p, oid.size() * 4, hipMemcpyDeviceToHost));
         for (size_t o = 0; o < no; ++o) memcpy(gph.list(jb.node(over[o]), level), &oid[o * cap], (size_t)cap * 4);
         jb.times3[1] += graph_now_us() - t3;
         if (reselected) *reselected += no;
@@ -395,33 +385,31 @@ static int hnsw_reverse_scan(const HnswLevelJob& jb, uint32_t ns0, const float* 
     flags.assign(ns0, 0);
     if (ns0 == 0 || nn == 0) return LYNSE_OK;
     hipStream_t st = cur(h).stream;
-    uint32_t *d_old = nullptr, *d_new = nullptr; float* d_thr = nullptr; uint8_t* d_flags = nullptr;
-    GraphFree fr;
-    fr.ps = {(void**)&d_old, (void**)&d_new, (void**)&d_thr, (void**)&d_flags};
+    DevBuf<uint32_t> d_old, d_new; DevBuf<float> d_thr; DevBuf<uint8_t> d_flags;
     std::vector<uint32_t> new_ids(nn);
     for (uint32_t t = 0; t < nn; ++t) new_ids[t] = jb.node(ns0 + t);
     if (jb.items) {
-        LY_HIP(hipMalloc(&d_old, (size_t)ns0 * 4));
-        LY_TRY(h2d_done(d_old, jb.items, (size_t)ns0 * 4));
+        LY_TRY(d_old.alloc((size_t)ns0));
+        LY_TRY(h2d_done(d_old.p, jb.items, (size_t)ns0 * 4));
     }
-    LY_HIP(hipMalloc(&d_new, (size_t)nn * 4));
-    LY_TRY(h2d_done(d_new, new_ids.data(), (size_t)nn * 4));
-    LY_HIP(hipMalloc(&d_thr, (size_t)ns0 * 4));
-    LY_TRY(h2d_done(d_thr, thr, (size_t)ns0 * 4));
-    LY_HIP(hipMalloc(&d_flags, ns0));
-    LY_HIP(hipMemsetAsync(d_flags, 0, ns0, st));
+    LY_TRY(d_new.alloc((size_t)nn));
+    LY_TRY(h2d_done(d_new.p, new_ids.data(), (size_t)nn * 4));
+    LY_TRY(d_thr.alloc((size_t)ns0));
+    LY_TRY(h2d_done(d_thr.p, thr, (size_t)ns0 * 4));
+    LY_TRY(d_flags.alloc(ns0));
+    LY_HIP(hipMemsetAsync(d_flags.p, 0, ns0, st));
     // new rows per tile: what fits the 160 KiB of the graph kernels, never fewer than one (4 D + 512 fits: hnsw_check_rows)
     const uint32_t tile = (uint32_t)std::max<size_t>(1, std::min<size_t>(nn, PoolRerank::LDS_MAX / ((size_t)D * 4)));
     const uint32_t per_block = HNSW_REVERSE_THREADS / 64 * 8;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)ns0 + per_block - 1) / per_block, (uint64_t)h->num_cu * 4));
     for (uint32_t t0 = 0; t0 < nn; t0 += tile) {
         HnswReverseArgs a{};
-        a.V = h->rows; a.ld = h->ld; a.D = D; a.metric = jb.metric; a.old_ids = d_old; a.n_old = ns0; a.thr = d_thr;
-        a.new_ids = d_new; a.tile0 = t0; a.tn = std::min(tile, nn - t0); a.flags = d_flags;
+        a.V = h->rows; a.ld = h->ld; a.D = D; a.metric = jb.metric; a.old_ids = d_old.p; a.n_old = ns0; a.thr = d_thr.p;
+        a.new_ids = d_new.p; a.tile0 = t0; a.tn = std::min(tile, nn - t0); a.flags = d_flags.p;
         LY_TRY(launch_lds<k_hnsw_reverse_scan>(dim3(grid), dim3(HNSW_REVERSE_THREADS), (size_t)a.tn * D * 4, st, a));
     }
     LY_HIP(hipStreamSynchronize(st));
-    LY_HIP(hipMemcpy(flags.data(), d_flags, ns0, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(flags.data(), d_flags.p, ns0, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
@@ -461,8 +449,8 @@ extern "C" int lynse_hip_flat_hnsw_extend(lynse_hip_flat* h, int mode) {
     HnswGraph gph;
     gph.shape(m, lv.data(), n1);
     // the old lists are a prefix of the new arrays: new rows have the highest row numbers
-    LY_HIP(hipMemcpy(gph.adj0.data(), s.d_adj0, (size_t)n0 * 2 * m * 4, hipMemcpyDeviceToHost));
-    if (!s.upper_node.empty()) LY_HIP(hipMemcpy(gph.upper_adj.data(), s.d_upper_adj, s.upper_node.size() * (size_t)m * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(gph.adj0.data(), s.d_adj0.p, (size_t)n0 * 2 * m * 4, hipMemcpyDeviceToHost));
+    if (!s.upper_node.empty()) LY_HIP(hipMemcpy(gph.upper_adj.data(), s.d_upper_adj.p, s.upper_node.size() * (size_t)m * 4, hipMemcpyDeviceToHost));
     HnswFormGuard form_guard(h);
     HnswExtendUndo undo(s);
     double times3[3] = {0.0, 0.0, 0.0};
@@ -601,8 +589,8 @@ extern "C" int lynse_hip_flat_hnsw_params(lynse_hip_flat* h, uint32_t* info, uin
     if (levels) memcpy(levels, s.levels.data(), s.levels.size() * 4);
     if (upper_node && nu) memcpy(upper_node, s.upper_node.data(), nu * 4);
     if (upper_level && nu) memcpy(upper_level, s.upper_level.data(), nu * 4);
-    if (adj0) LY_HIP(hipMemcpy(adj0, s.d_adj0, (size_t)s.n * 2 * s.m * 4, hipMemcpyDeviceToHost));
-    if (upper_adj && nu) LY_HIP(hipMemcpy(upper_adj, s.d_upper_adj, nu * s.m * 4, hipMemcpyDeviceToHost));
+    if (adj0) LY_HIP(hipMemcpy(adj0, s.d_adj0.p, (size_t)s.n * 2 * s.m * 4, hipMemcpyDeviceToHost));
+    if (upper_adj && nu) LY_HIP(hipMemcpy(upper_adj, s.d_upper_adj.p, nu * s.m * 4, hipMemcpyDeviceToHost));
     return LYNSE_OK;
 }
 
@@ -650,7 +638,7 @@ extern "C" int lynse_hip_flat_search_hnsw_f32(lynse_hip_flat* h, const float* qu
                         [&](const GraphSearchChunk& c) {
         HnswSearchArgs a{};
         a.V = h->rows; a.ld = h->ld; a.D = h->dim; a.metric = metric; a.Q = c.Q; a.k = k; a.ef = ef; a.m = s.m;
-        a.entry = s.entry; a.top_level = s.top_level; a.adj0 = s.d_adj0; a.upper_off = s.d_upper_off; a.upper_adj = s.d_upper_adj;
+        a.entry = s.entry; a.top_level = s.top_level; a.adj0 = s.d_adj0.p; a.upper_off = s.d_upper_off.p; a.upper_adj = s.d_upper_adj.p;
         a.vis = c.vis; a.vis_words = c.vis_words; a.out_rows = c.out_rows; a.out_dists = c.out_dists; a.out_counts = c.out_counts;
         a.out_scored = c.out_scored; a.status = c.status;
         return launch_lds<k_hnsw_search>(dim3(c.nqc), dim3(64), c.lds, c.st, a);

@@ -11,23 +11,29 @@
 // positions to original rows and orders by (distance, original row).
 
 struct IvfScratch {
-    uint64_t* d_route_rows = nullptr; float* d_route_d = nullptr; uint32_t* d_route_c = nullptr; size_t route_cap = 0;   // centroid ranking
-    uint32_t* d_probes = nullptr; size_t probes_cap = 0;
-    uint32_t* d_pair_q = nullptr; size_t pairs_cap = 0;
-    GatherPair* d_pairs = nullptr; size_t gpairs_cap = 0;
-    IvfTile* d_tiles = nullptr; size_t tiles_cap = 0;
-    IvfGroup* d_groups = nullptr; size_t groups_cap = 0;   // device-side grouping (k_ivf_group)
-    uint32_t* d_tbase = nullptr; size_t tbase_cap = 0;      // first tile of every (window, group)
-    uint32_t* d_prank = nullptr; size_t prank_cap = 0;      // rank of every pair inside its list
-    uint32_t* d_ghdr = nullptr;                             // its header: groups, tiles per window, host-path flag, pairs
-    uint32_t* h_ghdr = nullptr;                             // pinned mirror
-    _Float16* d_gimg = nullptr; size_t gimg_cap = 0;  // halves
-    void release() {
-        for (void* p : {(void*)d_route_rows, (void*)d_route_d, (void*)d_route_c, (void*)d_probes, (void*)d_pair_q, (void*)d_pairs, (void*)d_tiles, (void*)d_groups,
-                        (void*)d_tbase, (void*)d_prank, (void*)d_ghdr, (void*)d_gimg})
-            if (p) (void)hipFree(p);
+    DevBuf<uint64_t> route_rows; DevBuf<float> route_d; DevBuf<uint32_t> route_c;   // centroid ranking
+    DevBuf<uint32_t> probes;
+    DevBuf<uint32_t> pair_q;
+    DevBuf<GatherPair> pairs;
+    DevBuf<IvfTile> tiles;
+    DevBuf<IvfGroup> groups;     // device-side grouping (k_ivf_group)
+    DevBuf<uint32_t> tbase;      // first tile of every (window, group)
+    DevBuf<uint32_t> prank;      // rank of every pair inside its list
+    DevBuf<uint32_t> ghdr;       // its header: groups, tiles per window, host-path flag, pairs
+    uint32_t* h_ghdr = nullptr;  // pinned mirror
+    DevBuf<_Float16> gimg;       // halves
+    void release() {   // (the pinned mirror: the device buffers free themselves)
         if (h_ghdr) (void)hipHostFree(h_ghdr);
-        *this = IvfScratch();
+        h_ghdr = nullptr;
+    }
+    // the centroid ranking of nq queries over np lists: rows and distances with a floor of one full chunk, the counts of one chunk
+    int reserve_route(size_t nq, size_t np) {
+        if (nq * np > std::min(route_rows.cap, route_d.cap)) {
+            const size_t cap = std::max<size_t>(nq * np, (size_t)QCHUNK * np);
+            LY_TRY(route_rows.reserve_exact(cap));
+            LY_TRY(route_d.reserve_exact(cap));
+        }
+        return route_c.reserve_exact(QCHUNK);
     }
 };
 
@@ -42,30 +48,29 @@ struct lynse_hip_ivf {
     std::vector<uint32_t> orig;       // slab position -> original row
     std::vector<uint32_t> assignments;
     std::vector<float> centroids;     // nlist x dim
-    uint32_t* d_orig = nullptr;
-    uint64_t* d_offsets = nullptr;    // nlist + 1 (the fused few-query search walks the probed lists on the device)
+    DevBuf<uint32_t> d_orig;
+    DevBuf<uint64_t> d_offsets;       // nlist + 1 (the fused few-query search walks the probed lists on the device)
     uint64_t max_list_len = 0;
     std::vector<uint64_t> worst_rows;  // worst_rows[p] = rows of the p LARGEST lists: what nprobe = p can touch at most
-    float* d_centroids = nullptr;
+    DevBuf<float> d_centroids;
     uint32_t ldc = 0;
     std::vector<uint32_t> rdims;
-    uint32_t* d_rdims = nullptr;
+    DevBuf<uint32_t> d_rdims;
     uint64_t row_stride = 1, row_offset = 0;
     // IVF-*-BINARY (ivf.rs:77-127): rows are BinaryQuantizer codes ({0,1} floats + packed u64 words), routing is L2 on
     // the codes, the list scan is packed popcount
     bool binary = false;
     int already_binary = 0;
     std::vector<float> bq_thr;        // dim per-dimension thresholds (0.5 everywhere for {0,1} corpora)
-    float* d_bq_thr = nullptr;
+    DevBuf<float> d_bq_thr;
     // IVF-{IP,L2,COS}-SQ8 (ivf.rs:132-337 with QuantizerType::Scalar): `store` holds the DECODED rows (the pool stage is the
     // ordinary IVF scan over them), d_raw the original f32 rows in ORIGINAL row order for the exact rerank
     bool sq8 = false;
     std::vector<float> sq_min, sq_scale;  // fitted ScalarQuantizer: min_val, scale = range / 255
-    float* d_sq = nullptr;            // [min | scale] on the device (2 x dim)
-    float* d_raw = nullptr;           // n x dim original rows
+    DevBuf<float> d_sq;               // [min | scale] on the device (2 x dim)
+    DevBuf<float> d_raw;              // n x dim original rows
     struct Sq8Scratch {               // per-search buffers of the SQ8 path (grown on demand; searches hold the guard)
-        float* d_q = nullptr; size_t q_cap = 0;
-        float* d_pdist = nullptr; size_t pdist_cap = 0;
+        DevBuf<float> q, pdist;
         PoolRerank rr;                // the pool's rows and counts, the rerank's buffers and timing events
     } sq;
     // profiling (lynse_hip_ivf_sq8_stage_times): searches timed, and the pool stage / the rerank in microseconds (HIP events on the
@@ -78,23 +83,17 @@ struct lynse_hip_ivf {
     uint32_t replicas = 0;
     uint64_t n_rows = 0;
     struct SpannScratch {             // per-search buffers of the SPANN path (grown on demand; searches hold the guard)
-        float* d_q = nullptr; size_t q_cap = 0;
-        uint64_t* d_rows = nullptr; size_t rows_cap = 0;   // the k' keys of the list scan ...
-        float* d_dists = nullptr; size_t dists_cap = 0;
-        uint32_t* d_cnt = nullptr; size_t cnt_cap = 0;
-        uint64_t* d_orow = nullptr; size_t orow_cap = 0;   // ... and the distinct rows (plain modes)
-        float* d_odist = nullptr; size_t odist_cap = 0;
-        uint32_t* d_ocnt = nullptr; size_t ocnt_cap = 0;
-        uint32_t* d_qmap = nullptr; size_t qmap_cap = 0;   // the queries of a fallback rerun
-        void release() {
-            for (void* p : {(void*)d_q, (void*)d_rows, (void*)d_dists, (void*)d_cnt, (void*)d_orow, (void*)d_odist, (void*)d_ocnt, (void*)d_qmap})
-                if (p) (void)hipFree(p);
-            *this = SpannScratch();
-        }
+        DevBuf<float> q;
+        DevBuf<uint64_t> rows;    // the k' keys of the list scan ...
+        DevBuf<float> dists;
+        DevBuf<uint32_t> cnt;
+        DevBuf<uint64_t> orow;    // ... and the distinct rows (plain modes)
+        DevBuf<float> odist;
+        DevBuf<uint32_t> ocnt;
+        DevBuf<uint32_t> qmap;    // the queries of a fallback rerun
     } sp;
     lynse_hip_flat* cstore = nullptr; // the centroid matrix as a FLAT shard: exact routing = its top-nprobe search
-    uint32_t* d_smask = nullptr;      // subset filter by slab position
-    uint64_t smask_words = 0;
+    DevBuf<uint32_t> smask;           // subset filter by slab position
     // per-search device scratch (grown on demand), ONE SET PER SEARCH CONTEXT of the slab store: the blocking searches run on context 0
     // under the store's exclusive lock, searches in flight (lynse_hip_ivf_search_submit_f32_device) on the contexts 1.. they lease
     IvfScratch scr[lynse_hip_flat::MAX_CTX];
@@ -122,11 +121,7 @@ static void ivf_free(lynse_hip_ivf* h) {
     if (!h) return;
     if (h->store) {
         (void)hipSetDevice(h->store->device);
-        for (void* p : {(void*)h->d_orig, (void*)h->d_offsets, (void*)h->d_centroids, (void*)h->d_rdims, (void*)h->d_bq_thr, (void*)h->d_smask,
-                        (void*)h->d_sq, (void*)h->d_raw, (void*)h->sq.d_q, (void*)h->sq.d_pdist})
-            if (p) (void)hipFree(p);
         h->sq.rr.release();
-        h->sp.release();
         for (auto& x : h->scr) x.release();
         if (h->cstore) lynse_hip_flat_destroy(h->cstore);
         lynse_hip_flat_destroy(h->store);
@@ -175,7 +170,7 @@ extern "C" int lynse_hip_ivf_set_routing(lynse_hip_ivf* h, int ivfflat_routing) 
     if (ivfflat_routing == 2) return LYNSE_OK;  // routing semantics unchanged, only the fallback is switched off
     h->ivfflat_routing = ivfflat_routing ? 1 : 0;
     h->rdims = ivfflat_routing ? ivf_routing_dims(h->centroids, h->dim, h->nlist) : std::vector<uint32_t>();
-    if (!h->rdims.empty()) LY_TRY(h2d_done(h->d_rdims, h->rdims.data(), h->rdims.size() * 4));
+    if (!h->rdims.empty()) LY_TRY(h2d_done(h->d_rdims.p, h->rdims.data(), h->rdims.size() * 4));
     return LYNSE_OK;
 }
 
@@ -286,10 +281,10 @@ static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float
         }
     }
     auto fail = [&](const char* what) { ivf_free(h); return set_error(LYNSE_ERR_OUT_OF_MEMORY, what); };
-    if (hipMalloc(&h->d_orig, std::max<size_t>((size_t)n * 4, 4)) != hipSuccess) return fail("hipMalloc(orig)");
-    if (n) (void)h2d_done(h->d_orig, h->orig.data(), (size_t)n * 4);
-    if (hipMalloc(&h->d_offsets, ((size_t)nlist + 1) * 8) != hipSuccess) return fail("hipMalloc(offsets)");
-    (void)h2d_done(h->d_offsets, h->offsets.data(), ((size_t)nlist + 1) * 8);
+    if (h->d_orig.alloc((size_t)n) != LYNSE_OK) return fail("hipMalloc(orig)");
+    if (n) (void)h2d_done(h->d_orig.p, h->orig.data(), (size_t)n * 4);
+    if (h->d_offsets.alloc((size_t)nlist + 1) != LYNSE_OK) return fail("hipMalloc(offsets)");
+    (void)h2d_done(h->d_offsets.p, h->offsets.data(), ((size_t)nlist + 1) * 8);
     for (uint32_t p = 0; p < nlist; ++p) h->max_list_len = std::max(h->max_list_len, h->offsets[p + 1] - h->offsets[p]);
     {
         std::vector<uint64_t> lens(nlist);
@@ -301,27 +296,26 @@ static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float
     rc = lynse_hip_flat_reserve(h->store, std::max<uint64_t>(n, 1));
     if (rs) {
         // re-assembly: the indexed rows are gathered from the OLD slab store inside HBM, only the new rows are uploaded
-        uint32_t *d_gid = nullptr, *d_spos = nullptr;
-        float* d_new = nullptr;
-        struct Free { uint32_t*& a; uint32_t*& b; float*& c; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } fr{d_gid, d_spos, d_new};
+        DevBuf<uint32_t> d_gid, d_spos;
+        DevBuf<float> d_new;
         std::vector<uint32_t> gid(n), spos(rs->n_new);
         for (uint64_t p = 0; p < n; ++p) {
             const uint32_t r = h->orig[p], op = rs->old_pos[r];
             gid[p] = op == 0xffffffffu ? 0u : op;
             if (op == 0xffffffffu) spos[r - rs->first_new] = (uint32_t)p;
         }
-        if (rc == LYNSE_OK && hipMalloc(&d_gid, std::max<size_t>((size_t)n * 4, 4)) != hipSuccess) rc = set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(gather ids)");
-        if (rc == LYNSE_OK && n) rc = h2d_done(d_gid, gid.data(), (size_t)n * 4);
+        if (rc == LYNSE_OK) rc = d_gid.alloc((size_t)n);
+        if (rc == LYNSE_OK && n) rc = h2d_done(d_gid.p, gid.data(), (size_t)n * 4);
         if (rc == LYNSE_OK && rs->n_new) {
-            if (hipMalloc(&d_spos, (size_t)rs->n_new * 4) != hipSuccess || hipMalloc(&d_new, (size_t)rs->n_new * dim * 4) != hipSuccess)
-                rc = set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(new rows)");
-            if (rc == LYNSE_OK) rc = h2d_done(d_spos, spos.data(), (size_t)rs->n_new * 4);
-            if (rc == LYNSE_OK) rc = h2d_done(d_new, rs->new_rows, (size_t)rs->n_new * dim * 4);
+            rc = d_spos.alloc((size_t)rs->n_new);
+            if (rc == LYNSE_OK) rc = d_new.alloc((size_t)rs->n_new * dim);
+            if (rc == LYNSE_OK) rc = h2d_done(d_spos.p, spos.data(), (size_t)rs->n_new * 4);
+            if (rc == LYNSE_OK) rc = h2d_done(d_new.p, rs->new_rows, (size_t)rs->n_new * dim * 4);
         }
-        if (rc == LYNSE_OK) rc = flat_append_gathered_device(h->store, rs->d_old_rows, d_gid, n, rs->old_ld, d_new, d_spos, rs->n_new);
+        if (rc == LYNSE_OK) rc = flat_append_gathered_device(h->store, rs->d_old_rows, d_gid.p, n, rs->old_ld, d_new.p, d_spos.p, rs->n_new);
     } else if (rows_on_device) {
         // rows already in HBM: the slab order is a gather by original row id inside HBM
-        if (rc == LYNSE_OK) rc = flat_append_gathered_device(h->store, rows, h->d_orig, n);
+        if (rc == LYNSE_OK) rc = flat_append_gathered_device(h->store, rows, h->d_orig.p, n);
     } else {
         // upload rows in slab order, chunked through a host staging buffer
         const uint64_t chunk = std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)dim * 4));
@@ -336,8 +330,8 @@ static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float
     if (rc != LYNSE_OK) { ivf_free(h); return rc; }
     h->centroids.assign(centroids, centroids + (size_t)nlist * dim);
     h->ldc = dim;
-    if (hipMalloc(&h->d_centroids, std::max<size_t>((size_t)nlist * dim * 4, 4)) != hipSuccess) return fail("hipMalloc(centroids)");
-    (void)h2d_done(h->d_centroids, centroids, (size_t)nlist * dim * 4);
+    if (h->d_centroids.alloc((size_t)nlist * dim) != LYNSE_OK) return fail("hipMalloc(centroids)");
+    (void)h2d_done(h->d_centroids.p, centroids, (size_t)nlist * dim * 4);
     // exact routing (mode 0) is a FLAT top-nprobe search over the centroids with the single-row kernels
     rc = lynse_hip_flat_create(dim, device, &h->cstore);
     if (rc == LYNSE_OK) rc = lynse_hip_flat_append_f32(h->cstore, centroids, nlist);
@@ -349,8 +343,8 @@ static int ivf_assemble(const float* rows, uint64_t n, uint32_t dim, const float
         h->binary = true;
         { const int prc = ensure_packed_locked(h->store); if (prc != LYNSE_OK) { ivf_free(h); return prc; } }
     }
-    if (hipMalloc(&h->d_rdims, 16 * 4) != hipSuccess) return fail("hipMalloc(rdims)");
-    if (!h->rdims.empty()) (void)h2d_done(h->d_rdims, h->rdims.data(), h->rdims.size() * 4);
+    if (h->d_rdims.alloc(16) != LYNSE_OK) return fail("hipMalloc(rdims)");
+    if (!h->rdims.empty()) (void)h2d_done(h->d_rdims.p, h->rdims.data(), h->rdims.size() * 4);
     *out = h;
     return LYNSE_OK;
 }
@@ -376,27 +370,26 @@ static int bq_fit_encode(const float* rows, uint64_t n, uint32_t dim, int device
     thr->assign(dim, 0.5f);
     *already_binary = 0;
     if (n == 0) return LYNSE_OK;
-    float *d_v = nullptr, *d_t = nullptr;
-    uint32_t* d_nb = nullptr;
-    struct G { std::vector<void*> b; ~G() { for (void* p : b) if (p) (void)hipFree(p); } } g;
-    LY_HIP(hipMalloc(&d_v, (size_t)n * dim * 4)); g.b.push_back(d_v);
-    LY_HIP(hipMalloc(&d_t, (size_t)dim * 4 * 3)); g.b.push_back(d_t);
-    LY_HIP(hipMalloc(&d_nb, 4)); g.b.push_back(d_nb);
-    LY_TRY(h2d_done(d_v, rows, (size_t)n * dim * 4));
+    DevBuf<float> d_v, d_t;
+    DevBuf<uint32_t> d_nb;
+    LY_TRY(d_v.alloc((size_t)n * dim));
+    LY_TRY(d_t.alloc((size_t)dim * 3));
+    LY_TRY(d_nb.alloc(1));
+    LY_TRY(h2d_done(d_v.p, rows, (size_t)n * dim * 4));
     if (thr_in) {
         thr->assign(thr_in, thr_in + dim);
     } else {
-        LY_TRY(memset_done(d_nb, 0, 4));
-        hipLaunchKernelGGL(k_bq_colstats, dim3(dim), dim3(256), 0, 0, d_v, dim, dim, n, d_t, d_t + dim, d_nb);
+        LY_TRY(memset_done(d_nb.p, 0, 4));
+        hipLaunchKernelGGL(k_bq_colstats, dim3(dim), dim3(256), 0, 0, d_v.p, dim, dim, n, d_t.p, d_t.p + dim, d_nb.p);
         LY_HIP(hipGetLastError());
         uint32_t nb = 0;
-        LY_HIP(hipMemcpy(&nb, d_nb, 4, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(&nb, d_nb.p, 4, hipMemcpyDeviceToHost));
         *already_binary = nb ? 0 : 1;
         if (nb) {
-            hipLaunchKernelGGL(k_bq_median, dim3(dim), dim3(256), 0, 0, d_v, dim, dim, n, d_t + 2 * (size_t)dim);
+            hipLaunchKernelGGL(k_bq_median, dim3(dim), dim3(256), 0, 0, d_v.p, dim, dim, n, d_t.p + 2 * (size_t)dim);
             LY_HIP(hipGetLastError());
             std::vector<float> st((size_t)dim * 3);
-            LY_HIP(hipMemcpy(st.data(), d_t, (size_t)dim * 12, hipMemcpyDeviceToHost));
+            LY_HIP(hipMemcpy(st.data(), d_t.p, (size_t)dim * 12, hipMemcpyDeviceToHost));
             for (uint32_t d = 0; d < dim; ++d) {
                 const float mn = st[d], mx = st[dim + d], med = st[2 * (size_t)dim + d];
                 const float mid = mn + mx;
@@ -405,11 +398,11 @@ static int bq_fit_encode(const float* rows, uint64_t n, uint32_t dim, int device
         }
     }
     if (enc) {
-        LY_TRY(h2d_done(d_t, thr->data(), (size_t)dim * 4));
-        hipLaunchKernelGGL(k_bq_binarize, dim3(1024), dim3(256), 0, 0, d_v, dim, dim, n, d_t, d_v, dim);
+        LY_TRY(h2d_done(d_t.p, thr->data(), (size_t)dim * 4));
+        hipLaunchKernelGGL(k_bq_binarize, dim3(1024), dim3(256), 0, 0, d_v.p, dim, dim, n, d_t.p, d_v.p, dim);
         LY_HIP(hipGetLastError());
         enc->resize((size_t)n * dim);
-        LY_HIP(hipMemcpy(enc->data(), d_v, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(enc->data(), d_v.p, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
     }
     return LYNSE_OK;
 }
@@ -417,8 +410,8 @@ static int bq_fit_encode(const float* rows, uint64_t n, uint32_t dim, int device
 static int ivf_set_thresholds(lynse_hip_ivf* h, const std::vector<float>& thr, int already_binary) {
     h->bq_thr = thr;
     h->already_binary = already_binary;
-    LY_HIP(hipMalloc(&h->d_bq_thr, std::max<size_t>(thr.size() * 4, 4)));
-    LY_TRY(h2d_done(h->d_bq_thr, thr.data(), thr.size() * 4));
+    LY_TRY(h->d_bq_thr.alloc(thr.size()));
+    LY_TRY(h2d_done(h->d_bq_thr.p, thr.data(), thr.size() * 4));
     return LYNSE_OK;
 }
 
@@ -496,8 +489,8 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
     // ---- the data as a FLAT store (queries for the assignment step come straight from it)
     lynse_hip_flat* data = nullptr;
     LY_TRY(lynse_hip_flat_create(dim, device, &data));
-    struct Guard { lynse_hip_flat*& d; std::vector<void*> bufs; lynse_hip_flat* cen = nullptr;
-                   ~Guard() { for (void* p : bufs) if (p) (void)hipFree(p); if (cen) lynse_hip_flat_destroy(cen); if (d) lynse_hip_flat_destroy(d); } } guard{data};
+    struct Guard { lynse_hip_flat*& d; lynse_hip_flat* cen = nullptr;   // (declared before the device buffers: they go first)
+                   ~Guard() { if (cen) lynse_hip_flat_destroy(cen); if (d) lynse_hip_flat_destroy(d); } } guard{data};
     LY_TRY(lynse_hip_flat_reserve(data, std::max<uint64_t>(n, 1)));
     if (n) {
         if (rows_on_device) LY_TRY(lynse_hip_flat_append_f32_device(data, rows, n));
@@ -530,14 +523,14 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
     if (rows_on_device && !own_row.empty()) {  // the init sample is gathered inside HBM and read back once
         const uint64_t m = own_row.size();
         std::vector<float> tmp((size_t)m * dim);
-        uint32_t* d_ids = nullptr; float* d_tmp = nullptr;
-        LY_HIP(hipMalloc(&d_ids, (size_t)m * 4)); guard.bufs.push_back(d_ids);
-        LY_HIP(hipMalloc(&d_tmp, (size_t)m * dim * 4)); guard.bufs.push_back(d_tmp);
-        LY_HIP(hipMemcpyAsync(d_ids, own_row.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+        DevBuf<uint32_t> d_ids; DevBuf<float> d_tmp;
+        LY_TRY(d_ids.alloc((size_t)m));
+        LY_TRY(d_tmp.alloc((size_t)m * dim));
+        LY_HIP(hipMemcpyAsync(d_ids.p, own_row.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((m * ((dim + 3) / 4) + 255) / 256, 4096)), dim3(256), 0, st,
-                           rows, dim, d_ids, m, d_tmp, dim, dim);
+                           rows, dim, d_ids.p, m, d_tmp.p, dim, dim);
         LY_HIP(hipGetLastError());
-        LY_HIP(hipMemcpyAsync(tmp.data(), d_tmp, (size_t)m * dim * 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(tmp.data(), d_tmp.p, (size_t)m * dim * 4, hipMemcpyDeviceToHost, st));
         LY_HIP(hipStreamSynchronize(st));
         for (uint64_t j = 0; j < m; ++j) memcpy(&sample[(size_t)own_pos[j] * dim], &tmp[(size_t)j * dim], (size_t)dim * 4);
     } else {
@@ -551,19 +544,19 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
     std::vector<float>& cen = *centroids_out;
     const uint64_t first = (uint64_t)(rng.next() * (double)sample_n) % sample_n;
     memcpy(&cen[0], &sample[(size_t)first * dim], (size_t)dim * 4);
-    float *d_sample = nullptr, *d_point = nullptr, *d_minrank = nullptr;
-    LY_HIP(hipMalloc(&d_sample, (size_t)sample_n * dim * 4)); guard.bufs.push_back(d_sample);
-    LY_HIP(hipMalloc(&d_point, (size_t)dim * 4)); guard.bufs.push_back(d_point);
-    LY_HIP(hipMalloc(&d_minrank, (size_t)sample_n * 4)); guard.bufs.push_back(d_minrank);
-    LY_HIP(hipMemcpyAsync(d_sample, sample.data(), (size_t)sample_n * dim * 4, hipMemcpyHostToDevice, st));
+    DevBuf<float> d_sample, d_point, d_minrank;
+    LY_TRY(d_sample.alloc((size_t)sample_n * dim));
+    LY_TRY(d_point.alloc((size_t)dim));
+    LY_TRY(d_minrank.alloc((size_t)sample_n));
+    LY_HIP(hipMemcpyAsync(d_sample.p, sample.data(), (size_t)sample_n * dim * 4, hipMemcpyHostToDevice, st));
     std::vector<float> minrank((size_t)sample_n, 3.402823466e+38f);
-    LY_HIP(hipMemcpyAsync(d_minrank, minrank.data(), (size_t)sample_n * 4, hipMemcpyHostToDevice, st));
+    LY_HIP(hipMemcpyAsync(d_minrank.p, minrank.data(), (size_t)sample_n * 4, hipMemcpyHostToDevice, st));
     for (uint32_t c = 1; c < k; ++c) {
-        LY_HIP(hipMemcpyAsync(d_point, &cen[(size_t)(c - 1) * dim], (size_t)dim * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_kmeans_minrank, dim3((uint32_t)((sample_n * 8 + 255) / 256)), dim3(256), 0, st, d_sample, dim, dim,
-                           (uint32_t)sample_n, d_point, metric, d_minrank);
+        LY_HIP(hipMemcpyAsync(d_point.p, &cen[(size_t)(c - 1) * dim], (size_t)dim * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kmeans_minrank, dim3((uint32_t)((sample_n * 8 + 255) / 256)), dim3(256), 0, st, d_sample.p, dim, dim,
+                           (uint32_t)sample_n, d_point.p, metric, d_minrank.p);
         LY_HIP(hipGetLastError());
-        LY_HIP(hipMemcpyAsync(minrank.data(), d_minrank, (size_t)sample_n * 4, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(minrank.data(), d_minrank.p, (size_t)sample_n * 4, hipMemcpyDeviceToHost, st));
         LY_HIP(hipStreamSynchronize(st));
         uint64_t best = 0;  // Iterator::max_by keeps the LAST maximal element (kmeans.rs:185-190)
         for (uint64_t i = 1; i < sample_n; ++i)
@@ -574,22 +567,22 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
     // ---- Lloyd (kmeans.rs:96-130)
     std::vector<uint32_t> cur(n, 0xffffffffu), nxt(n);
     std::vector<float> sums((size_t)k * dim);
-    float* d_sums = nullptr; uint32_t* d_members = nullptr; uint64_t* d_off = nullptr;
-    LY_HIP(hipMalloc(&d_sums, (size_t)k * dim * 4)); guard.bufs.push_back(d_sums);
-    LY_HIP(hipMalloc(&d_members, (size_t)n * 4)); guard.bufs.push_back(d_members);
-    LY_HIP(hipMalloc(&d_off, ((size_t)k + 1) * 8)); guard.bufs.push_back(d_off);
+    DevBuf<float> d_sums; DevBuf<uint32_t> d_members; DevBuf<uint64_t> d_off;
+    LY_TRY(d_sums.alloc((size_t)k * dim));
+    LY_TRY(d_members.alloc((size_t)n));
+    LY_TRY(d_off.alloc((size_t)k + 1));
     std::vector<uint64_t> rowsbuf(256);
     std::vector<float> dbuf(256);
     std::vector<uint32_t> cbuf(256);
-    float* d_q = nullptr; uint64_t* d_r = nullptr; float* d_d = nullptr; uint32_t* d_c = nullptr;
+    DevBuf<float> d_q; DevBuf<uint64_t> d_r; DevBuf<float> d_d; DevBuf<uint32_t> d_c;
     constexpr uint64_t AQ = 32768;  // rows assigned per search call (passes of ASSIGN_QCHUNK rows inside)
     constexpr uint32_t ASSIGN_QCHUNK = 8192;
-    LY_HIP(hipMalloc(&d_q, AQ * (size_t)dim * 4)); guard.bufs.push_back(d_q);
-    LY_HIP(hipMalloc(&d_r, AQ * 8)); guard.bufs.push_back(d_r);
-    LY_HIP(hipMalloc(&d_d, AQ * 4)); guard.bufs.push_back(d_d);
-    LY_HIP(hipMalloc(&d_c, AQ * 4)); guard.bufs.push_back(d_c);
+    LY_TRY(d_q.alloc(AQ * (size_t)dim));
+    LY_TRY(d_r.alloc(AQ));
+    LY_TRY(d_d.alloc(AQ));
+    LY_TRY(d_c.alloc(AQ));
     std::vector<uint64_t> hrows(AQ);
-    float* d_q2 = nullptr;          // the undecided rows of an assignment call, gathered (allocated on first use)
+    DevBuf<float> d_q2;             // the undecided rows of an assignment call, gathered (allocated on first use)
 
     auto assign = [&](std::vector<uint32_t>& out) -> int {  // assign_metric (kmeans.rs:237-264)
         if (guard.cen) { lynse_hip_flat_destroy(guard.cen); guard.cen = nullptr; }
@@ -612,36 +605,36 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
         // through the search (A/B; read per build)
         bool fast = k <= 16384 && env_on("LYNSE_HIP_ASSIGN_FAST", true);
         std::vector<uint32_t> hids(AQ), hredo(AQ);
-        uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_r);           // (AQ x 8 bytes: ids in the first half, the redo list in the second)
-        uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_r) + AQ;
+        uint32_t* d_ids = reinterpret_cast<uint32_t*>(d_r.p);           // (AQ x 8 bytes: ids in the first half, the redo list in the second)
+        uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_r.p) + AQ;
         for (uint64_t r0 = 0; r0 < n; r0 += AQ) {
             const uint64_t nr = std::min<uint64_t>(AQ, n - r0);
-            LY_TRY(lynse_hip_flat_copy_rows_device(data, r0, nr, d_q));
+            LY_TRY(lynse_hip_flat_copy_rows_device(data, r0, nr, d_q.p));
             if (fast) {
-                const int frc = flat_assign_top1_device(guard.cen, d_q, nr, metric, d_ids, d_redo, d_c);
+                const int frc = flat_assign_top1_device(guard.cen, d_q.p, nr, metric, d_ids, d_redo, d_c.p);
                 if (frc == LYNSE_ERR_UNSUPPORTED) fast = false;
                 else if (frc != LYNSE_OK) return frc;
             }
             if (fast) {
                 uint32_t nredo = 0;
-                LY_HIP(hipMemcpy(&nredo, d_c, 4, hipMemcpyDeviceToHost));
+                LY_HIP(hipMemcpy(&nredo, d_c.p, 4, hipMemcpyDeviceToHost));
                 LY_HIP(hipMemcpy(hids.data(), d_ids, nr * 4, hipMemcpyDeviceToHost));
                 if (nredo) {   // undecided rows: gathered into the front of a second buffer, answered exactly, scattered back
-                    if (!d_q2) { LY_HIP(hipMalloc(&d_q2, AQ * (size_t)dim * 4)); guard.bufs.push_back(d_q2); }
+                    LY_TRY(d_q2.reserve_exact(AQ * (size_t)dim));
                     LY_HIP(hipMemcpy(hredo.data(), d_redo, (size_t)nredo * 4, hipMemcpyDeviceToHost));
                     hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>(((uint64_t)nredo * ((dim + 3) / 4) + 255) / 256, 4096)), dim3(256), 0, st,
-                                       d_q, dim, d_redo, (uint64_t)nredo, d_q2, dim, dim);
+                                       d_q.p, dim, d_redo, (uint64_t)nredo, d_q2.p, dim, dim);
                     LY_HIP(hipGetLastError());
                     LY_HIP(hipStreamSynchronize(st));
-                    LY_TRY(lynse_hip_flat_search_f32_device(guard.cen, d_q2, nredo, 1, metric, d_r, d_d, d_c, nullptr));
-                    LY_HIP(hipMemcpy(hrows.data(), d_r, (size_t)nredo * 8, hipMemcpyDeviceToHost));
+                    LY_TRY(lynse_hip_flat_search_f32_device(guard.cen, d_q2.p, nredo, 1, metric, d_r.p, d_d.p, d_c.p, nullptr));
+                    LY_HIP(hipMemcpy(hrows.data(), d_r.p, (size_t)nredo * 8, hipMemcpyDeviceToHost));
                     for (uint32_t i = 0; i < nredo; ++i) hids[hredo[i]] = (uint32_t)hrows[i];
                 }
                 for (uint64_t i = 0; i < nr; ++i) out[r0 + i] = hids[i];
                 continue;
             }
-            LY_TRY(lynse_hip_flat_search_f32_device(guard.cen, d_q, nr, 1, metric, d_r, d_d, d_c, nullptr));
-            LY_HIP(hipMemcpy(hrows.data(), d_r, nr * 8, hipMemcpyDeviceToHost));
+            LY_TRY(lynse_hip_flat_search_f32_device(guard.cen, d_q.p, nr, 1, metric, d_r.p, d_d.p, d_c.p, nullptr));
+            LY_HIP(hipMemcpy(hrows.data(), d_r.p, nr * 8, hipMemcpyDeviceToHost));
             for (uint64_t i = 0; i < nr; ++i) out[r0 + i] = (uint32_t)hrows[i];
         }
         return LYNSE_OK;
@@ -661,16 +654,16 @@ static int ivf_kmeans(const float* rows, uint64_t n, uint32_t dim, uint32_t requ
             std::vector<uint64_t> wp(off.begin(), off.end() - 1);
             for (uint64_t i = 0; i < n; ++i) members[wp[cur[i]]++] = (uint32_t)i;
         }
-        LY_HIP(hipMemcpyAsync(d_members, members.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemcpyAsync(d_off, off.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_kmeans_sums, dim3(k), dim3(256), 0, st, data->rows, ld, dim, d_members, d_off, d_sums, dim);
+        LY_HIP(hipMemcpyAsync(d_members.p, members.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(d_off.p, off.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kmeans_sums, dim3(k), dim3(256), 0, st, data->rows, ld, dim, d_members.p, d_off.p, d_sums.p, dim);
         LY_HIP(hipGetLastError());
         // per-rank sums (sequential over the rank's members) added over the ranks IN RANK ORDER; counts + stop test of the whole collection
         int rr = 0;
         if (sh && sh->reduce_iter) {   // the communicator: all-gather + rank-ordered add + integer all-reduce on device buffers, one read-back
-            rr = sh->reduce_iter(d_sums, (uint64_t)k * dim, d_off, k, counts[k], st, sums.data(), counts.data());
+            rr = sh->reduce_iter(d_sums.p, (uint64_t)k * dim, d_off.p, k, counts[k], st, sums.data(), counts.data());
         } else {
-            LY_HIP(hipMemcpyAsync(sums.data(), d_sums, (size_t)k * dim * 4, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(sums.data(), d_sums.p, (size_t)k * dim * 4, hipMemcpyDeviceToHost, st));
             LY_HIP(hipStreamSynchronize(st));
             if (sh) {
                 rr = sh->reduce(sums.data(), (uint64_t)k * dim, 2);
@@ -760,12 +753,11 @@ extern "C" int lynse_hip_ivf_load_device(const float* d_rows, uint64_t n, uint32
 // ScalarQuantizer::fit over n rows in HBM (n > 0): mins, scales
 static int sq_fit_device(const float* d_v, uint64_t n, uint32_t dim, std::vector<float>* mins, std::vector<float>* scales) {
     const uint32_t strips = (uint32_t)std::min<uint64_t>(n, 1024);
-    float* d_p = nullptr;
-    struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_p};
-    LY_HIP(hipMalloc(&d_p, ((size_t)strips * 2 + 2) * dim * 4));
-    float* d_o = d_p + (size_t)strips * 2 * dim;
-    hipLaunchKernelGGL(k_ivfsq_minmax, dim3((dim + 255) / 256, strips), dim3(256), 0, 0, d_v, dim, n, d_p, d_p + (size_t)strips * dim);
-    hipLaunchKernelGGL(k_ivfsq_fit, dim3((dim + 255) / 256), dim3(256), 0, 0, d_p, d_p + (size_t)strips * dim, dim, strips, d_o, d_o + dim);
+    DevBuf<float> d_p;
+    LY_TRY(d_p.alloc(((size_t)strips * 2 + 2) * dim));
+    float* d_o = d_p.p + (size_t)strips * 2 * dim;
+    hipLaunchKernelGGL(k_ivfsq_minmax, dim3((dim + 255) / 256, strips), dim3(256), 0, 0, d_v, dim, n, d_p.p, d_p.p + (size_t)strips * dim);
+    hipLaunchKernelGGL(k_ivfsq_fit, dim3((dim + 255) / 256), dim3(256), 0, 0, d_p.p, d_p.p + (size_t)strips * dim, dim, strips, d_o, d_o + dim);
     LY_HIP(hipGetLastError());
     std::vector<float> o((size_t)dim * 2);
     LY_HIP(hipMemcpy(o.data(), d_o, (size_t)dim * 8, hipMemcpyDeviceToHost));
@@ -785,38 +777,37 @@ static int sq_codec_device(const float* d_in, uint64_t n, uint32_t dim, const fl
 }
 
 // decode(encode(rows)) of host rows for an SQ8 index (host copy unless dec is NULL): the routing space of insert / assign
-static int sq_decode_host(const lynse_hip_ivf* h, const float* rows, uint64_t n, std::vector<float>* dec, float** d_keep = nullptr) {
+static int sq_decode_host(const lynse_hip_ivf* h, const float* rows, uint64_t n, std::vector<float>* dec, DevBuf<float>* d_keep = nullptr) {
     if (dec) dec->resize((size_t)n * h->dim);
     if (n == 0) return LYNSE_OK;
     LY_HIP(hipSetDevice(h->store->device));   // (h->d_sq lives on the index's device, whatever the calling thread's current one is)
-    float* d_v = nullptr;
-    struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_v};
-    LY_HIP(hipMalloc(&d_v, (size_t)n * h->dim * 8));
-    LY_TRY(h2d_done(d_v, rows, (size_t)n * h->dim * 4));
-    LY_TRY(sq_codec_device(d_v, n, h->dim, h->d_sq, d_v + (size_t)n * h->dim, 0));
-    if (dec) LY_HIP(hipMemcpy(dec->data(), d_v + (size_t)n * h->dim, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost));
+    DevBuf<float> d_v;
+    LY_TRY(d_v.alloc((size_t)n * h->dim * 2));
+    LY_TRY(h2d_done(d_v.p, rows, (size_t)n * h->dim * 4));
+    LY_TRY(sq_codec_device(d_v.p, n, h->dim, h->d_sq.p, d_v.p + (size_t)n * h->dim, 0));
+    if (dec) LY_HIP(hipMemcpy(dec->data(), d_v.p + (size_t)n * h->dim, (size_t)n * h->dim * 4, hipMemcpyDeviceToHost));
     else LY_HIP(hipStreamSynchronize(nullptr));
-    if (d_keep) { *d_keep = d_v; d_v = nullptr; }   // (the caller takes the buffer: originals first, decoded rows behind them)
+    if (d_keep) *d_keep = std::move(d_v);   // (the caller takes the buffer: originals first, decoded rows behind them)
     return LYNSE_OK;
 }
 
 // the common part of build_sq8 / load_sq8: original rows uploaded, quantizer on the device, decoded rows beside them
 static int sq_prepare(const float* rows, uint64_t n, uint32_t dim, const float* mins_in, const float* scales_in, int device,
-                      float** d_raw, float** d_dec, float** d_sq, std::vector<float>* mins, std::vector<float>* scales) {
+                      DevBuf<float>& d_raw, DevBuf<float>& d_dec, DevBuf<float>& d_sq, std::vector<float>* mins, std::vector<float>* scales) {
     LY_HIP(hipSetDevice(device));
-    LY_HIP(hipMalloc(d_raw, std::max<size_t>((size_t)n * dim * 4, 4)));
-    LY_HIP(hipMalloc(d_dec, std::max<size_t>((size_t)n * dim * 4, 4)));
-    LY_HIP(hipMalloc(d_sq, (size_t)dim * 8));
-    if (n) LY_TRY(h2d_done(*d_raw, rows, (size_t)n * dim * 4));
+    LY_TRY(d_raw.alloc((size_t)n * dim));
+    LY_TRY(d_dec.alloc((size_t)n * dim));
+    LY_TRY(d_sq.alloc((size_t)dim * 2));
+    if (n) LY_TRY(h2d_done(d_raw.p, rows, (size_t)n * dim * 4));
     if (mins_in) {
         mins->assign(mins_in, mins_in + dim);
         scales->assign(scales_in, scales_in + dim);
     } else {
-        LY_TRY(sq_fit_device(*d_raw, n, dim, mins, scales));
+        LY_TRY(sq_fit_device(d_raw.p, n, dim, mins, scales));
     }
-    LY_TRY(h2d_done(*d_sq, mins->data(), (size_t)dim * 4));
-    LY_TRY(h2d_done(*d_sq + dim, scales->data(), (size_t)dim * 4));
-    LY_TRY(sq_codec_device(*d_raw, n, dim, *d_sq, *d_dec, 0));
+    LY_TRY(h2d_done(d_sq.p, mins->data(), (size_t)dim * 4));
+    LY_TRY(h2d_done(d_sq.p + dim, scales->data(), (size_t)dim * 4));
+    LY_TRY(sq_codec_device(d_raw.p, n, dim, d_sq.p, d_dec.p, 0));
     LY_HIP(hipStreamSynchronize(nullptr));
     return LYNSE_OK;
 }
@@ -826,26 +817,25 @@ static int ivf_sq8_common(const float* rows, uint64_t n, uint32_t dim, const flo
     if (metric != M_IP && metric != M_L2 && metric != M_COS)
         return set_error(LYNSE_ERR_INVALID_ARGUMENT, "IVF-*-SQ8 is defined for ip / l2 / cosine");
     if (n == 0) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "no vectors to index");   // ScalarQuantizer::fit: empty training data
-    float *d_raw = nullptr, *d_dec = nullptr, *d_sq = nullptr;
-    struct G { float*& a; float*& b; float*& c; ~G() { for (float* p : {a, b, c}) if (p) (void)hipFree(p); } } g{d_raw, d_dec, d_sq};
+    DevBuf<float> d_raw, d_dec, d_sq;
     std::vector<float> mins, scales, cen;
     std::vector<uint32_t> asg;
-    LY_TRY(sq_prepare(rows, n, dim, mins_in, scales_in, device, &d_raw, &d_dec, &d_sq, &mins, &scales));
+    LY_TRY(sq_prepare(rows, n, dim, mins_in, scales_in, device, d_raw, d_dec, d_sq, &mins, &scales));
     if (!centroids) {   // train_for_metric on the decoded rows (ivf.rs:163-170)
         uint32_t k = 0;
-        LY_TRY(ivf_kmeans(d_dec, n, dim, nlist, max_iter, metric, device, &cen, &asg, &k, true));
+        LY_TRY(ivf_kmeans(d_dec.p, n, dim, nlist, max_iter, metric, device, &cen, &asg, &k, true));
         if (k == 0) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "no vectors to index");
         nlist = k;
         centroids = cen.data();
         assignments = asg.data();
     }
-    LY_TRY(ivf_assemble(d_dec, n, dim, centroids, nlist, assignments, metric, 0, device, out, true));
+    LY_TRY(ivf_assemble(d_dec.p, n, dim, centroids, nlist, assignments, metric, 0, device, out, true));
     lynse_hip_ivf* h = *out;
     h->sq8 = true;
     h->sq_min = std::move(mins);
     h->sq_scale = std::move(scales);
-    std::swap(h->d_sq, d_sq);
-    std::swap(h->d_raw, d_raw);
+    h->d_sq = std::move(d_sq);
+    h->d_raw = std::move(d_raw);
     return LYNSE_OK;
 }
 
@@ -939,10 +929,10 @@ static int ivf_rows_in_original_order(lynse_hip_ivf* h, std::vector<float>* out)
 }
 
 // replace the device structures of `h` with a fresh assembly over (rows, assignments) under the SAME centroids / settings
-// (new_raw: an SQ8 index's original rows for the new assembly, n x dim in original row order; owned by the index on success)
+// (new_raw: an SQ8 index's original rows for the new assembly, n x dim in original row order; moved into the index on success)
 // hand the settings of `h` to a fresh assembly `fresh` under the same centroids, then swap them: `h` owns the new structures, the old
 // ones are freed (new_raw as in ivf_reassemble)
-static int ivf_adopt(lynse_hip_ivf* h, lynse_hip_ivf* fresh, float* new_raw) {
+static int ivf_adopt(lynse_hip_ivf* h, lynse_hip_ivf* fresh, DevBuf<float>* new_raw) {
     fresh->no_fallback = h->no_fallback;
     fresh->row_stride = h->row_stride; fresh->row_offset = h->row_offset;
     fresh->store->no_fused = h->store->no_fused;
@@ -954,7 +944,7 @@ static int ivf_adopt(lynse_hip_ivf* h, lynse_hip_ivf* fresh, float* new_raw) {
         fresh->sq8 = true;
         fresh->sq_min = h->sq_min; fresh->sq_scale = h->sq_scale;
         std::swap(fresh->d_sq, h->d_sq);
-        fresh->d_raw = new_raw;
+        if (new_raw) fresh->d_raw = std::move(*new_raw);
         fresh->sq_searches = h->sq_searches; fresh->sq_pool_us = h->sq_pool_us; fresh->sq_rerank_us = h->sq_rerank_us;
     }
     fresh->spann = h->spann;
@@ -976,7 +966,7 @@ static int ivf_adopt(lynse_hip_ivf* h, lynse_hip_ivf* fresh, float* new_raw) {
 }
 
 static int ivf_reassemble(lynse_hip_ivf* h, const std::vector<float>& rows, uint64_t n, const std::vector<uint32_t>& asg, const IvfRowSource* rs = nullptr,
-                          float* new_raw = nullptr) {
+                          DevBuf<float>* new_raw = nullptr) {
     lynse_hip_ivf* fresh = nullptr;
     const int device = h->store->device;
     LY_TRY(ivf_assemble(rs ? nullptr : rows.data(), n, h->dim, h->centroids.data(), h->nlist, asg.data(), h->metric, h->ivfflat_routing, device, &fresh, false, rs));
@@ -1003,17 +993,15 @@ extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uin
     std::vector<float> enc_new;
     const float* routed = rows;
     if (h->binary) { ivf_encode_rows(h, rows, n, &enc_new); routed = enc_new.data(); }
-    float* new_raw = nullptr;   // SQ8: the original rows of the grown index (old ones + the new ones, original row order)
-    struct FreeRaw { float*& p; ~FreeRaw() { if (p) (void)hipFree(p); } } fraw{new_raw};
+    DevBuf<float> new_raw;   // SQ8: the original rows of the grown index (old ones + the new ones, original row order)
     if (h->sq8) {   // encode with the FITTED quantizer (no refit: values outside its range clamp), route the decoded rows
-        float* d_new = nullptr;
-        struct G { float*& p; ~G() { if (p) (void)hipFree(p); } } g{d_new};
+        DevBuf<float> d_new;
         LY_HIP(hipSetDevice(h->store->device));
         LY_TRY(sq_decode_host(h, rows, n, &enc_new, &d_new));
         routed = enc_new.data();
-        LY_HIP(hipMalloc(&new_raw, (size_t)(old_n + n) * h->dim * 4));
-        if (old_n) LY_HIP(hipMemcpy(new_raw, h->d_raw, (size_t)old_n * h->dim * 4, hipMemcpyDeviceToDevice));
-        LY_HIP(hipMemcpy(new_raw + (size_t)old_n * h->dim, d_new, (size_t)n * h->dim * 4, hipMemcpyDeviceToDevice));
+        LY_TRY(new_raw.alloc((size_t)(old_n + n) * h->dim));
+        if (old_n) LY_HIP(hipMemcpy(new_raw.p, h->d_raw.p, (size_t)old_n * h->dim * 4, hipMemcpyDeviceToDevice));
+        LY_HIP(hipMemcpy(new_raw.p + (size_t)old_n * h->dim, d_new.p, (size_t)n * h->dim * 4, hipMemcpyDeviceToDevice));
     }
     std::vector<uint32_t> asg(h->assignments);
     asg.resize(old_n + n);
@@ -1024,9 +1012,7 @@ extern "C" int lynse_hip_ivf_insert_f32(lynse_hip_ivf* h, const float* rows, uin
     for (uint64_t p = 0; p < old_n; ++p) old_pos[h->orig[p]] = (uint32_t)p;
     IvfRowSource rs{h->store->rows, h->store->ld, old_pos.data(), routed, old_n, n};
     static const std::vector<float> none;
-    LY_TRY(ivf_reassemble(h, none, old_n + n, asg, &rs, new_raw));
-    new_raw = nullptr;   // (owned by the index now)
-    return LYNSE_OK;
+    return ivf_reassemble(h, none, old_n + n, asg, &rs, &new_raw);   // (on success the index owns new_raw)
 }
 
 extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_ids, uint64_t n_ids) {
@@ -1043,23 +1029,21 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
     std::vector<bool> gone(old_n, false);
     for (uint64_t i = 0; i < n_ids; ++i)
         if (row_ids[i] < old_n) gone[row_ids[i]] = true;   // unknown ids are ignored (a HashSet lookup that never matches)
-    float* new_raw = nullptr;   // SQ8: the original rows that are kept, in order (the decoded ones are reassigned below)
-    struct FreeRaw { float*& p; ~FreeRaw() { if (p) (void)hipFree(p); } } fraw{new_raw};
+    DevBuf<float> new_raw;   // SQ8: the original rows that are kept, in order (the decoded ones are reassigned below)
     if (h->sq8) {
         std::vector<uint32_t> keep;
         keep.reserve(old_n);
         for (uint64_t r = 0; r < old_n; ++r)
             if (!gone[r]) keep.push_back((uint32_t)r);
         LY_HIP(hipSetDevice(h->store->device));
-        uint32_t* d_keep = nullptr;
-        struct G { uint32_t*& p; ~G() { if (p) (void)hipFree(p); } } g{d_keep};
-        LY_HIP(hipMalloc(&new_raw, std::max<size_t>(keep.size() * h->dim * 4, 4)));
+        DevBuf<uint32_t> d_keep;
+        LY_TRY(new_raw.alloc(keep.size() * h->dim));
         if (!keep.empty()) {
-            LY_HIP(hipMalloc(&d_keep, keep.size() * 4));
-            LY_TRY(h2d_done(d_keep, keep.data(), keep.size() * 4));
+            LY_TRY(d_keep.alloc(keep.size()));
+            LY_TRY(h2d_done(d_keep.p, keep.data(), keep.size() * 4));
             const uint64_t pieces = (uint64_t)keep.size() * ((h->dim + 3) / 4);
             hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0,
-                               h->d_raw, h->dim, d_keep, (uint64_t)keep.size(), new_raw, h->dim, h->dim);
+                               h->d_raw.p, h->dim, d_keep.p, (uint64_t)keep.size(), new_raw.p, h->dim, h->dim);
             LY_HIP(hipGetLastError());
             LY_HIP(hipStreamSynchronize(nullptr));
         }
@@ -1069,17 +1053,16 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
         // centroid store with the slab rows themselves as device queries (every old slab position; the deleted ones are dropped
         // afterwards), then the re-assembled store gathers the kept rows from the old one.
         LY_HIP(hipSetDevice(h->store->device));
-        uint64_t* d_r = nullptr; float* d_d = nullptr; uint32_t* d_c = nullptr;
-        struct Free { uint64_t*& a; float*& b; uint32_t*& c; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } fr{d_r, d_d, d_c};
-        LY_HIP(hipMalloc(&d_r, (size_t)old_n * 8));
-        LY_HIP(hipMalloc(&d_d, (size_t)old_n * 4));
-        LY_HIP(hipMalloc(&d_c, (size_t)old_n * 4));
+        DevBuf<uint64_t> d_r; DevBuf<float> d_d; DevBuf<uint32_t> d_c;
+        LY_TRY(d_r.alloc((size_t)old_n));
+        LY_TRY(d_d.alloc((size_t)old_n));
+        LY_TRY(d_c.alloc((size_t)old_n));
         const int route_metric = h->binary ? M_L2 : h->metric;   // routing_metric (ivf.rs:77-87)
-        LY_TRY(lynse_hip_flat_search_f32_device(h->cstore, h->store->rows, old_n, 1, route_metric, d_r, d_d, d_c, nullptr));
+        LY_TRY(lynse_hip_flat_search_f32_device(h->cstore, h->store->rows, old_n, 1, route_metric, d_r.p, d_d.p, d_c.p, nullptr));
         std::vector<uint64_t> best(old_n);
         std::vector<uint32_t> cnt(old_n);
-        LY_HIP(hipMemcpy(best.data(), d_r, (size_t)old_n * 8, hipMemcpyDeviceToHost));
-        LY_HIP(hipMemcpy(cnt.data(), d_c, (size_t)old_n * 4, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(best.data(), d_r.p, (size_t)old_n * 8, hipMemcpyDeviceToHost));
+        LY_HIP(hipMemcpy(cnt.data(), d_c.p, (size_t)old_n * 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> pos_of_orig(old_n);
         for (uint64_t p = 0; p < old_n; ++p) pos_of_orig[h->orig[p]] = (uint32_t)p;
         std::vector<uint32_t> asg, old_pos;
@@ -1092,8 +1075,7 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
             }
         IvfRowSource rs{h->store->rows, h->store->ld, old_pos.data(), nullptr, (uint64_t)old_pos.size(), 0};
         static const std::vector<float> none;
-        LY_TRY(ivf_reassemble(h, none, old_pos.size(), asg, &rs, new_raw));
-        new_raw = nullptr;
+        return ivf_reassemble(h, none, old_pos.size(), asg, &rs, &new_raw);
         return LYNSE_OK;
     }
     std::vector<float> all;
@@ -1105,23 +1087,10 @@ extern "C" int lynse_hip_ivf_delete_rows(lynse_hip_ivf* h, const uint64_t* row_i
         if (!gone[r]) { kept.insert(kept.end(), all.begin() + (size_t)r * h->dim, all.begin() + (size_t)(r + 1) * h->dim); ++m; }
     std::vector<uint32_t> asg(m);
     LY_TRY(ivf_assign_rows(h, kept.data(), m, asg.data()));   // kmeans::assign_metric over everything that is left
-    LY_TRY(ivf_reassemble(h, kept, m, asg, nullptr, new_raw));
-    new_raw = nullptr;
-    return LYNSE_OK;
+    return ivf_reassemble(h, kept, m, asg, nullptr, &new_raw);
 }
 
 // ------------------------------------------------------------------------------------ search ----
-template <typename T>
-static int ivf_grow(T** p, size_t* cap, size_t need) {
-    if (need <= *cap) return LYNSE_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    size_t nc = std::max(need, *cap * 2);
-    LY_HIP(hipMalloc(p, nc * sizeof(T)));
-    *cap = nc;
-    return LYNSE_OK;
-}
-
 static int launch_scan_tiled(const ScanArgs& a, int metric, uint32_t grid, hipStream_t st) {
     return launch_scan_h16<with(F16_SMALL, &H16Cfg::tiled, true)>(a, metric, grid, st);
 }
@@ -1145,7 +1114,7 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
     Workspace& w = cur(s).ws;
     IvfScratch& scr = iscr(h);
     const uint32_t D = h->dim;
-    LY_TRY(ivf_grow(&scr.d_probes, &scr.probes_cap, (size_t)nq * np_eff));
+    LY_TRY(scr.probes.reserve((size_t)nq * np_eff));
     std::vector<uint32_t>& probes = *probes_out;
     probes.assign((size_t)nq * np_eff, 0u);
     const bool heuristic = h->ivfflat_routing && metric == M_IP && D >= 64 && h->nlist >= 64 && !h->rdims.empty() && np_eff < h->nlist;
@@ -1155,54 +1124,45 @@ static int ivf_route(lynse_hip_ivf* h, uint32_t nq, uint32_t np_eff, int metric,
     } else if (!heuristic) {
         // ---- exact ranking of all centroids (ivf.rs:227-249) = the (score, centroid id) top-nprobe of a FLAT search
         // over the centroid matrix: MFMA coarse pass + exact rescoring instead of nlist sequential scores per query
-        if ((size_t)nq * np_eff > scr.route_cap) {
-            for (void* p : {(void*)scr.d_route_rows, (void*)scr.d_route_d, (void*)scr.d_route_c})
-                if (p) (void)hipFree(p);
-            scr.d_route_rows = nullptr; scr.d_route_d = nullptr; scr.d_route_c = nullptr; scr.route_cap = 0;
-            const size_t cap = std::max<size_t>((size_t)nq * np_eff, (size_t)QCHUNK * np_eff);
-            LY_HIP(hipMalloc(&scr.d_route_rows, cap * 8));
-            LY_HIP(hipMalloc(&scr.d_route_d, cap * 4));
-            LY_HIP(hipMalloc(&scr.d_route_c, (size_t)QCHUNK * 4));
-            scr.route_cap = cap;
-        }
+        LY_TRY(scr.reserve_route(nq, np_eff));
         if (as) {
             // in flight: ONE plan level of the centroid store's own pipeline (or its fused few-query kernel) on the ticket's stream, with
             // the workspace of the centroid store's context of the same slot; an overflow of it is part of the ticket's status
             lynse_hip_flat* cs = h->cstore;
             Workspace& cw = cur(cs).ws;
             if (small_path_ok(cs, nq, np_eff, route_metric, false)) {
-                LY_TRY(run_small(cs, nq, np_eff, np_eff, route_metric, st, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, cw.h_hdr + cw.qcap, w.Qf));
+                LY_TRY(run_small(cs, nq, np_eff, np_eff, route_metric, st, nullptr, scr.route_rows.p, scr.route_d.p, scr.route_c.p, cw.h_hdr + cw.qcap, w.Qf));
                 as->routed_by_chunk = false;
             } else {
                 ScanProf sprof;
                 ChunkReq rq;
                 rq.nq = nq; rq.k = rq.out_k = np_eff; rq.metric = route_metric; rq.qsrc = w.Qf; rq.allow_sts = false;
-                rq.out.rows = scr.d_route_rows; rq.out.dists = scr.d_route_d; rq.out.counts2 = scr.d_route_c; rq.out.any_ovf = as->status; rq.out.hdr_direct = true;
+                rq.out.rows = scr.route_rows.p; rq.out.dists = scr.route_d.p; rq.out.counts2 = scr.route_c.p; rq.out.any_ovf = as->status; rq.out.hdr_direct = true;
                 LY_TRY(run_chunk(cs, rq, st, &sprof));
                 as->routed_by_chunk = true;
             }
-            *dev64 = scr.d_route_rows;
+            *dev64 = scr.route_rows.p;
             return LYNSE_OK;
         }
-        LY_TRY(search_impl(h->cstore, w.Qf, false, nq, np_eff, route_metric, scr.d_route_rows, scr.d_route_d, scr.d_route_c, true, st));
-        if (dev64) { *dev64 = scr.d_route_rows; return LYNSE_OK; }
+        LY_TRY(search_impl(h->cstore, w.Qf, false, nq, np_eff, route_metric, scr.route_rows.p, scr.route_d.p, scr.route_c.p, true, st));
+        if (dev64) { *dev64 = scr.route_rows.p; return LYNSE_OK; }
         std::vector<uint64_t> rr((size_t)nq * np_eff);
-        LY_HIP(hipMemcpyAsync(rr.data(), scr.d_route_rows, rr.size() * 8, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(rr.data(), scr.route_rows.p, rr.size() * 8, hipMemcpyDeviceToHost, st));
         LY_HIP(hipStreamSynchronize(st));
         for (size_t i = 0; i < rr.size(); ++i) probes[i] = (uint32_t)rr[i];
     } else {
         RouteArgs ra{};
-        ra.Qf = w.Qf; ra.D = D; ra.C = h->d_centroids; ra.ldc = h->ldc; ra.nlist = h->nlist; ra.metric = route_metric;
-        ra.nprobe = np_eff; ra.mode = heuristic ? 1 : 0; ra.rdims = h->d_rdims; ra.nrd = (uint32_t)h->rdims.size();
+        ra.Qf = w.Qf; ra.D = D; ra.C = h->d_centroids.p; ra.ldc = h->ldc; ra.nlist = h->nlist; ra.metric = route_metric;
+        ra.nprobe = np_eff; ra.mode = heuristic ? 1 : 0; ra.rdims = h->d_rdims.p; ra.nrd = (uint32_t)h->rdims.size();
         ra.shortlist = std::min<uint32_t>(std::max<uint32_t>(np_eff * 3, 24), 96);  // ivf_flat_mmap.rs:395
         LY_TRY(ensure_lds<k_ivf_route<256>>(16384 * 8));
         uint32_t np2 = 2;
         while (np2 < h->nlist) np2 <<= 1;
-        ra.probes = scr.d_probes;
+        ra.probes = scr.probes.p;
         hipLaunchKernelGGL(k_ivf_route<256>, dim3(nq), dim3(256), (size_t)np2 * 8, st, ra);
         LY_HIP(hipGetLastError());
-        if (dev32) { *dev32 = scr.d_probes; return LYNSE_OK; }
-        LY_HIP(hipMemcpyAsync(probes.data(), scr.d_probes, probes.size() * 4, hipMemcpyDeviceToHost, st));
+        if (dev32) { *dev32 = scr.probes.p; return LYNSE_OK; }
+        LY_HIP(hipMemcpyAsync(probes.data(), scr.probes.p, probes.size() * 4, hipMemcpyDeviceToHost, st));
         LY_HIP(hipStreamSynchronize(st));
     }
 
@@ -1256,16 +1216,7 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
             (size_t)((D + 3) / 4 * 4) * 4 + (size_t)128 * 1024 + 64 <= 150u * 1024u) {
             const float* d_q = on_device ? q_host : w.Qf;
             if (!on_device) LY_HIP(hipMemcpyAsync(w.Qf, q_host, (size_t)nq * D * 4, hipMemcpyHostToDevice, st));
-            if ((size_t)nq * np_f > scr.route_cap || !scr.d_route_rows) {
-                for (void* p : {(void*)scr.d_route_rows, (void*)scr.d_route_d, (void*)scr.d_route_c})
-                    if (p) (void)hipFree(p);
-                scr.d_route_rows = nullptr; scr.d_route_d = nullptr; scr.d_route_c = nullptr; scr.route_cap = 0;
-                const size_t cap = std::max<size_t>((size_t)nq * np_f, (size_t)QCHUNK * np_f);
-                LY_HIP(hipMalloc(&scr.d_route_rows, cap * 8));
-                LY_HIP(hipMalloc(&scr.d_route_d, cap * 4));
-                LY_HIP(hipMalloc(&scr.d_route_c, (size_t)QCHUNK * 4));
-                scr.route_cap = cap;
-            }
+            LY_TRY(scr.reserve_route(nq, np_f));
             // (1) centroid ranking: the top-nprobe (score, centroid id) of the centroid matrix, single-row kernels
             SmallRows cr{h->cstore->rows, h->cstore->ld, h->nlist, LYNSE_IPFORM_SINGLE, 1, 0};
             // (2) the probed lists
@@ -1274,7 +1225,7 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
             float* d_dst = on_device ? out_dists : reinterpret_cast<float*>(w.h_out + rows_b);
             uint32_t* c_dst = on_device ? out_counts : w.h_hdr;
             SmallRows sr{s->rows, s->ld, (uint64_t)std::min<uint64_t>(h->worst_rows[np_f], s->n), LYNSE_IPFORM_SINGLE, h->row_stride, h->row_offset};
-            SmallIvf si{scr.d_route_rows, np_f, h->nlist, h->d_offsets, h->d_orig, (!h->ivfflat_routing && !h->no_fallback) ? 1 : 0};
+            SmallIvf si{scr.route_rows.p, np_f, h->nlist, h->d_offsets.p, h->d_orig.p, (!h->ivfflat_routing && !h->no_fallback) ? 1 : 0};
             // lynse_hip_ivf_profile_get (round 6: the single-query shape reported no scan at all): HIP events around the list-scan launch, and the
             // rows it really scores — the lengths of the lists the ranking picked, read back behind the search.
             // (round 6, measured and removed: both launches as ONE kernel with a grid-wide hand-over of the probe list — 73.5 against 70.5 us;
@@ -1282,14 +1233,14 @@ static int ivf_search_chunk(lynse_hip_ivf* h, const float* q_host, uint32_t nq, 
             hipEvent_t pe0 = nullptr, pe1 = nullptr;
             const bool timed_small = s->profiling.load();
             if (timed_small) { LY_TRY(get_event(s, 0, &pe0)); LY_TRY(get_event(s, 1, &pe1)); }
-            LY_TRY(run_small(s, nq, np_f, np_f, route_metric, st, nullptr, scr.d_route_rows, scr.d_route_d, scr.d_route_c, w.overflow, d_q, &cr, nullptr));
+            LY_TRY(run_small(s, nq, np_f, np_f, route_metric, st, nullptr, scr.route_rows.p, scr.route_d.p, scr.route_c.p, w.overflow, d_q, &cr, nullptr));
             if (timed_small) LY_HIP(hipEventRecord(pe0, st));
             LY_TRY(run_small(s, nq, k, out_k, metric, st, nullptr, r_dst, d_dst, c_dst, w.h_hdr + QCHUNK, d_q, &sr, &si));
             if (timed_small) LY_HIP(hipEventRecord(pe1, st));
             LY_HIP(hipStreamSynchronize(st));
             if (timed_small) {
                 std::vector<uint64_t> probes((size_t)nq * np_f);
-                LY_HIP(hipMemcpy(probes.data(), scr.d_route_rows, probes.size() * 8, hipMemcpyDeviceToHost));
+                LY_HIP(hipMemcpy(probes.data(), scr.route_rows.p, probes.size() * 8, hipMemcpyDeviceToHost));
                 uint64_t rows_scored = 0;
                 for (uint64_t c : probes)
                     if (c < h->nlist) rows_scored += h->offsets[c + 1] - h->offsets[c];
@@ -1363,7 +1314,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     if (binary) {
         // ---- queries: quantizer encode->decode (ivf.rs:211-222) in place, pack, +inf thresholds
         hipLaunchKernelGGL(k_bq_binarize, dim3(std::min<uint32_t>((uint32_t)(((uint64_t)nq * D + 255) / 256), 1024)), dim3(256), 0, st,
-                           w.Qf, D, D, (uint64_t)nq, h->d_bq_thr, w.Qf, D);
+                           w.Qf, D, D, (uint64_t)nq, h->d_bq_thr.p, w.Qf, D);
         LY_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_pack_bits<float>, dim3((nq + 3) / 4), dim3(256), 0, st, w.Qf, D, D, nq, w.QW, s->words);
         LY_HIP(hipGetLastError());
@@ -1451,7 +1402,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     fa.ip_form = LYNSE_IPFORM_SINGLE;  // IVF scores with compute_distance_f32 (ivf.rs:294-298): single-row kernels
     fa.exact = binary ? 1 : 0; fa.Qf = w.Qf; fa.V = s->rows; fa.ld = s->ld; fa.D = D;
     fa.row_stride = h->row_stride; fa.row_offset = h->row_offset;
-    fa.orig_ids = binary ? nullptr : h->d_orig;  // the packed scan already emits original rows
+    fa.orig_ids = binary ? nullptr : h->d_orig.p;  // the packed scan already emits original rows
     fa.out_rows = w.out_rows; fa.out_dists = w.out_dists; fa.out_counts = w.out_counts; fa.pool_total = nullptr;
     LY_TRY(ensure_lds<k_select<SEL_NT>>(SEL_LDS_MAX));
     LY_TRY(ensure_lds<k_final<SEL_NT>>(SEL_LDS_MAX));
@@ -1473,7 +1424,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         if (binary) {
             BinTileArgs b{};
             b.P = s->packed; b.W = s->words; b.QW = w.QW; b.tiles = d_win_tiles; b.ntiles = ntiles_host;
-            b.pair_q = scr.d_pair_q; b.orig = h->d_orig; b.mask = smask; b.thr = w.thr; b.cand = w.cand; b.count = w.count; b.cap = w.cap;
+            b.pair_q = scr.pair_q.p; b.orig = h->d_orig.p; b.mask = smask; b.thr = w.thr; b.cand = w.cand; b.count = w.count; b.cap = w.cap;
             const uint32_t grid = std::min<uint32_t>(b.ntiles, (uint32_t)s->num_cu * 8);
             const size_t lds = (size_t)32 * s->words * 8 + 256;
             switch (metric) {
@@ -1484,10 +1435,10 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
             LY_HIP(hipGetLastError());
         } else {
         ScanArgs a{};
-        a.V = s->rows; a.ld = s->ld; a.V16 = s->rows16; a.ld16 = s->ld16; a.D = D; a.row0 = 0; a.row1 = (uint32_t)s->n; a.Q16 = scr.d_gimg; a.qpad = 32;
+        a.V = s->rows; a.ld = s->ld; a.V16 = s->rows16; a.ld16 = s->ld16; a.D = D; a.row0 = 0; a.row1 = (uint32_t)s->n; a.Q16 = scr.gimg.p; a.qpad = 32;
         a.nq = nq; a.nslab = nslab; a.ntiles = ntiles_host; a.qinv = w.qinv; a.qn2 = w.qn2; a.qrinv = w.qrinv;
         a.thr = w.thr; a.vn2 = s->vn2; a.vrinv = s->vrinv; a.sv = s->sv; a.vmax2 = s->vmax * s->vmax; a.cand = w.cand; a.count = w.count; a.cap = w.cap;
-        a.emit_all = 0; a.debug_flags = 0; a.tiles = d_win_tiles; a.ntiles_dev = ntiles_dev; a.pair_q = scr.d_pair_q; a.mask = smask;
+        a.emit_all = 0; a.debug_flags = 0; a.tiles = d_win_tiles; a.ntiles_dev = ntiles_dev; a.pair_q = scr.pair_q.p; a.mask = smask;
         const uint32_t grid = ntiles_dev ? (uint32_t)s->num_cu * 2 : std::min<uint32_t>(a.ntiles, (uint32_t)s->num_cu * 2);
         if (i8c) {
             a.V16 = reinterpret_cast<const _Float16*>(opd.codes); a.ld16 = opd.ld;
@@ -1518,33 +1469,33 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         const size_t P = (size_t)nq * np_eff;
         const size_t gmax = std::min<size_t>(P, (size_t)h->nlist + P / 32 + 1);
         if ((uint64_t)gmax * gimg_halves > 0xffffffffull) return set_error(LYNSE_ERR_UNSUPPORTED, "too many (list, query-group) pairs in one batch");
-        LY_TRY(ivf_grow(&scr.d_pair_q, &scr.pairs_cap, P));
-        LY_TRY(ivf_grow(&scr.d_groups, &scr.groups_cap, gmax));
-        LY_TRY(ivf_grow(&scr.d_tbase, &scr.tbase_cap, gmax * 3));
-        LY_TRY(ivf_grow(&scr.d_prank, &scr.prank_cap, P));
-        LY_TRY(ivf_grow(&scr.d_gimg, &scr.gimg_cap, gmax * (size_t)gimg_halves));
-        LY_TRY(ivf_grow(&scr.d_tiles, &scr.tiles_cap, (size_t)win_bound * 3));
-        if (!scr.d_ghdr) {
-            LY_HIP(hipMalloc(&scr.d_ghdr, 8 * 4));
+        LY_TRY(scr.pair_q.reserve(P));
+        LY_TRY(scr.groups.reserve(gmax));
+        LY_TRY(scr.tbase.reserve(gmax * 3));
+        LY_TRY(scr.prank.reserve(P));
+        LY_TRY(scr.gimg.reserve(gmax * (size_t)gimg_halves));
+        LY_TRY(scr.tiles.reserve((size_t)win_bound * 3));
+        if (!scr.h_ghdr) {
+            LY_TRY(scr.ghdr.reserve_exact(8));
             LY_HIP(hipHostMalloc(&scr.h_ghdr, 8 * 4, hipHostMallocDefault));
         }
         IvfGroupArgs ga{};
-        ga.probes64 = p64; ga.probes32 = p32; ga.nq = nq; ga.np = np_eff; ga.nlist = h->nlist; ga.offsets = h->d_offsets; ga.gimg_halves = gimg_halves;
+        ga.probes64 = p64; ga.probes32 = p32; ga.nq = nq; ga.np = np_eff; ga.nlist = h->nlist; ga.offsets = h->d_offsets.p; ga.gimg_halves = gimg_halves;
         ga.a0 = a0; ga.tile_rows = tile_rows; ga.win_cap = (uint32_t)win_bound; ga.flag_empty = (!h->ivfflat_routing && !h->no_fallback) ? 1u : 0u;
-        ga.pair_q = scr.d_pair_q; ga.groups = scr.d_groups; ga.tiles = scr.d_tiles; ga.hdr = scr.d_ghdr; ga.tbase = scr.d_tbase; ga.gmax = (uint32_t)gmax; ga.prank = scr.d_prank;
+        ga.pair_q = scr.pair_q.p; ga.groups = scr.groups.p; ga.tiles = scr.tiles.p; ga.hdr = scr.ghdr.p; ga.tbase = scr.tbase.p; ga.gmax = (uint32_t)gmax; ga.prank = scr.prank.p;
         const size_t glds = ((size_t)h->nlist * 2 + std::max<size_t>(h->nlist, P) + 16 + 256) * 4;
         LY_TRY(ensure_lds<k_ivf_group<1024>>(((size_t)IVF_GROUP_MAX_LISTS * 2 + IVF_GROUP_MAX_PAIRS + 16 + 256) * 4 + 64));
         hipLaunchKernelGGL(k_ivf_group<1024>, dim3(1), dim3(1024), glds, st, ga);
         hipLaunchKernelGGL(k_ivf_emit_tiles, dim3(64), dim3(256), 0, st, ga);
-        hipLaunchKernelGGL(k_ivf_gather_groups, dim3((uint32_t)s->num_cu * 8), dim3(256), 0, st, w.Q16, qpad, scr.d_gimg, scr.d_groups, scr.d_pair_q,
-                           scr.d_ghdr, nslab);
+        hipLaunchKernelGGL(k_ivf_gather_groups, dim3((uint32_t)s->num_cu * 8), dim3(256), 0, st, w.Q16, qpad, scr.gimg.p, scr.groups.p, scr.pair_q.p,
+                           scr.ghdr.p, nslab);
         LY_HIP(hipGetLastError());
-        LY_HIP(hipMemcpyAsync(scr.h_ghdr, scr.d_ghdr, 8 * 4, hipMemcpyDeviceToHost, st));   // (read behind the final synchronise)
+        LY_HIP(hipMemcpyAsync(scr.h_ghdr, scr.ghdr.p, 8 * 4, hipMemcpyDeviceToHost, st));   // (read behind the final synchronise)
         const uint64_t longest = h->worst_rows[1];   // the longest list of the index
         for (int wi = 0; wi < 3; ++wi) {
             if (wi == 1 && longest <= a0) break;
             if (wi == 2 && longest <= (uint64_t)a0 * 16) break;
-            LY_TRY(run_window(scr.d_tiles + (size_t)wi * win_bound, (uint32_t)win_bound, scr.d_ghdr + 1 + wi));
+            LY_TRY(run_window(scr.tiles.p + (size_t)wi * win_bound, (uint32_t)win_bound, scr.ghdr.p + 1 + wi));
         }
     }
     // (host path) the pair / tile lists are the SOURCE of asynchronous copies: they live until the final synchronise of the call
@@ -1590,17 +1541,17 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     if (!groups.empty()) {
         if ((uint64_t)groups.size() * gimg_halves > 0xffffffffull)
             return set_error(LYNSE_ERR_UNSUPPORTED, "too many (list, query-group) pairs in one batch");
-        LY_TRY(ivf_grow(&scr.d_pair_q, &scr.pairs_cap, pair_q.size()));
-        LY_HIP(hipMemcpyAsync(scr.d_pair_q, pair_q.data(), pair_q.size() * 4, hipMemcpyHostToDevice, st));
+        LY_TRY(scr.pair_q.reserve(pair_q.size()));
+        LY_HIP(hipMemcpyAsync(scr.pair_q.p, pair_q.data(), pair_q.size() * 4, hipMemcpyHostToDevice, st));
         if (!binary) {
-            LY_TRY(ivf_grow(&scr.d_pairs, &scr.gpairs_cap, gpairs.size()));
-            LY_TRY(ivf_grow(&scr.d_gimg, &scr.gimg_cap, groups.size() * (size_t)gimg_halves));
-            LY_HIP(hipMemcpyAsync(scr.d_pairs, gpairs.data(), gpairs.size() * sizeof(GatherPair), hipMemcpyHostToDevice, st));
-            LY_HIP(hipMemsetAsync(scr.d_gimg, 0, groups.size() * (size_t)gimg_halves * 2, st));
+            LY_TRY(scr.pairs.reserve(gpairs.size()));
+            LY_TRY(scr.gimg.reserve(groups.size() * (size_t)gimg_halves));
+            LY_HIP(hipMemcpyAsync(scr.pairs.p, gpairs.data(), gpairs.size() * sizeof(GatherPair), hipMemcpyHostToDevice, st));
+            LY_HIP(hipMemsetAsync(scr.gimg.p, 0, groups.size() * (size_t)gimg_halves * 2, st));
             const uint32_t slots = i8c ? 8u : SK / 8;   // 16-B slots per line
             const uint64_t gt = (uint64_t)gpairs.size() * nslab * slots;
             hipLaunchKernelGGL(k_ivf_gather_q, dim3((uint32_t)std::min<uint64_t>((gt + 255) / 256, 65535)), dim3(256), 0, st, w.Q16,
-                               qpad, scr.d_gimg, scr.d_pairs, (uint32_t)gpairs.size(), nslab, slots);
+                               qpad, scr.gimg.p, scr.pairs.p, (uint32_t)gpairs.size(), nslab, slots);
             LY_HIP(hipGetLastError());
         }
 
@@ -1627,12 +1578,12 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
         }
         if (timed) for (auto& tl : all_tiles) host_tile_rows += tl.nrows;
         if (!all_tiles.empty()) {
-            LY_TRY(ivf_grow(&scr.d_tiles, &scr.tiles_cap, all_tiles.size()));
-            LY_HIP(hipMemcpyAsync(scr.d_tiles, all_tiles.data(), all_tiles.size() * sizeof(IvfTile), hipMemcpyHostToDevice, st));
+            LY_TRY(scr.tiles.reserve(all_tiles.size()));
+            LY_HIP(hipMemcpyAsync(scr.tiles.p, all_tiles.data(), all_tiles.size() * sizeof(IvfTile), hipMemcpyHostToDevice, st));
         }
         for (auto& wr : win_range) {
             if (wr.second == 0) continue;
-            const IvfTile* d_win_tiles = scr.d_tiles + wr.first;
+            const IvfTile* d_win_tiles = scr.tiles.p + wr.first;
             struct { size_t n; size_t size() const { return n; } } tiles{wr.second};
             LY_TRY(run_window(d_win_tiles, (uint32_t)tiles.size(), nullptr));
         }
@@ -1662,7 +1613,7 @@ static int ivf_search_chunk_staged(lynse_hip_ivf* h, const float* q_host, uint32
     }
     if (as) {   // in flight: wait() reads the pinned headers (w.h_hdr, scr.h_ghdr, the centroid store's) behind the ticket's event
         if (as->status) {
-            hipLaunchKernelGGL(k_or_word, dim3(1), dim3(1), 0, st, as->status, (const uint32_t*)(scr.d_ghdr + 4));
+            hipLaunchKernelGGL(k_or_word, dim3(1), dim3(1), 0, st, as->status, (const uint32_t*)(scr.ghdr.p + 4));
             LY_HIP(hipGetLastError());
         }
         return LYNSE_OK;
@@ -1702,10 +1653,8 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
     const int metric = h->search_metric >= 0 ? h->search_metric : h->metric;
     const bool asc = metric_ascending(metric);
     const uint32_t D = h->dim, np_eff = std::min<uint32_t>(nprobe, h->nlist);
-    uint32_t* d_pos = nullptr;
-    uint64_t* d_keys = nullptr;
-    size_t cap_pos = 0;
-    struct G { uint32_t** a; uint64_t** b; ~G() { if (*a) (void)hipFree(*a); if (*b) (void)hipFree(*b); } } guard{&d_pos, &d_keys};
+    DevBuf<uint32_t> d_pos;
+    DevBuf<uint64_t> d_keys;
     std::vector<uint64_t> o_rows(on_device ? (size_t)nq * k : 0);
     std::vector<float> o_dists(on_device ? (size_t)nq * k : 0);
     std::vector<uint32_t> o_counts(on_device ? nq : 0);
@@ -1719,7 +1668,7 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
     for (uint64_t q = 0; q < nq; ++q) {
         LY_HIP(hipMemcpyAsync(w.Qf, queries + q * D, (size_t)D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         if (binary) {  // the query goes through the quantizer (ivf.rs:211-222), then routing is L2 on the codes
-            hipLaunchKernelGGL(k_bq_binarize, dim3(std::min<uint32_t>((D + 255) / 256, 1024u)), dim3(256), 0, st, w.Qf, D, D, (uint64_t)1, h->d_bq_thr, w.Qf, D);
+            hipLaunchKernelGGL(k_bq_binarize, dim3(std::min<uint32_t>((D + 255) / 256, 1024u)), dim3(256), 0, st, w.Qf, D, D, (uint64_t)1, h->d_bq_thr.p, w.Qf, D);
             hipLaunchKernelGGL(k_pack_bits<float>, dim3(1), dim3(256), 0, st, w.Qf, D, D, 1u, w.QW, s->words);
             LY_HIP(hipGetLastError());
         }
@@ -1737,25 +1686,19 @@ static int ivf_search_large_k(lynse_hip_ivf* h, const float* queries, uint64_t n
         }
         const uint32_t P = (uint32_t)pos.size();
         if (P) {
-            if (P > cap_pos) {
-                if (d_pos) (void)hipFree(d_pos);
-                if (d_keys) (void)hipFree(d_keys);
-                d_pos = nullptr; d_keys = nullptr;
-                cap_pos = std::max<size_t>(P, cap_pos * 2);
-                LY_HIP(hipMalloc(&d_pos, cap_pos * 4));
-                LY_HIP(hipMalloc(&d_keys, cap_pos * 8));
-            }
-            LY_HIP(hipMemcpyAsync(d_pos, pos.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+            LY_TRY(d_pos.reserve(P));
+            LY_TRY(d_keys.reserve(P));
+            LY_HIP(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
             if (binary) {
-                IvfScorePackedArgs a{s->packed, s->words, w.QW, d_pos, h->d_orig, P, metric == M_HAMMING ? 0 : (metric == M_DICE ? 2 : 1), d_keys};
+                IvfScorePackedArgs a{s->packed, s->words, w.QW, d_pos.p, h->d_orig.p, P, metric == M_HAMMING ? 0 : (metric == M_DICE ? 2 : 1), d_keys.p};
                 hipLaunchKernelGGL(k_ivf_score_positions_packed, dim3(std::min<uint32_t>((P + 31) / 32, (uint32_t)s->num_cu * 8)), dim3(256), 0, st, a);
             } else {
-                IvfScoreArgs a{s->rows, s->ld, D, w.Qf, d_pos, h->d_orig, P, metric, d_keys};
+                IvfScoreArgs a{s->rows, s->ld, D, w.Qf, d_pos.p, h->d_orig.p, P, metric, d_keys.p};
                 hipLaunchKernelGGL(k_ivf_score_positions, dim3(std::min<uint32_t>((P + 31) / 32, (uint32_t)s->num_cu * 8)), dim3(256), 0, st, a);
             }
             LY_HIP(hipGetLastError());
             keys.resize(P);
-            LY_HIP(hipMemcpyAsync(keys.data(), d_keys, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+            LY_HIP(hipMemcpyAsync(keys.data(), d_keys.p, (size_t)P * 8, hipMemcpyDeviceToHost, st));
             LY_HIP(hipStreamSynchronize(st));
         }
         res_counts[q] = select_pool_keys(keys.data(), P, kk, k, asc, res_rows + q * k, res_dists + q * k, h->row_stride, h->row_offset);
@@ -1852,35 +1795,20 @@ static int ivf_search_locked(lynse_hip_ivf* h, const float* queries, uint64_t nq
                 for (uint64_t p = h->offsets[c]; p < h->offsets[c + 1]; ++p) list_matches[c] += seen[h->orig[p]] ? 1 : 0;
         const uint64_t words = (s->n + 31) / 32 + 8;
         auto& fc = cur(s);   // (the slab store's context 0: IVF searches hold its exclusive lock)
-        if (words > fc.mask_words) {
-            if (fc.d_mask) (void)hipFree(fc.d_mask);
-            fc.d_mask = nullptr;
-            LY_HIP(hipMalloc(&fc.d_mask, words * 4));
-            fc.mask_words = words;
-        }
-        if (words > h->smask_words) {
-            if (h->d_smask) (void)hipFree(h->d_smask);
-            h->d_smask = nullptr;
-            LY_HIP(hipMalloc(&h->d_smask, words * 4));
-            h->smask_words = words;
-        }
-        if (n_subset > fc.subset_cap) {
-            if (fc.d_subset) (void)hipFree(fc.d_subset);
-            fc.d_subset = nullptr;
-            LY_HIP(hipMalloc(&fc.d_subset, n_subset * 8));
-            fc.subset_cap = n_subset;
-        }
+        LY_TRY(fc.mask.reserve_exact(words));
+        LY_TRY(h->smask.reserve_exact(words));
+        LY_TRY(fc.subset.reserve_exact(n_subset));
         hipStream_t st = cur(s).stream;
-        LY_HIP(hipMemsetAsync(fc.d_mask, 0, words * 4, st));
-        LY_HIP(hipMemsetAsync(h->d_smask, 0, words * 4, st));
-        LY_HIP(hipMemcpyAsync(fc.d_subset, subset, n_subset * 8, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(fc.mask.p, 0, words * 4, st));
+        LY_HIP(hipMemsetAsync(h->smask.p, 0, words * 4, st));
+        LY_HIP(hipMemcpyAsync(fc.subset.p, subset, n_subset * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_mask_build, dim3((uint32_t)std::min<uint64_t>((n_subset + 255) / 256, (uint64_t)s->num_cu * 8)), dim3(256), 0, st,
-                           fc.d_subset, n_subset, s->n, fc.d_mask);
+                           fc.subset.p, n_subset, s->n, fc.mask.p);
         hipLaunchKernelGGL(k_mask_permute, dim3((uint32_t)std::min<uint64_t>((s->n + 255) / 256, (uint64_t)s->num_cu * 8)), dim3(256), 0, st,
-                           fc.d_mask, h->d_orig, s->n, h->d_smask);
+                           fc.mask.p, h->d_orig.p, s->n, h->smask.p);
         LY_HIP(hipGetLastError());
         LY_HIP(hipStreamSynchronize(st));
-        smask = h->d_smask;
+        smask = h->smask.p;
     }
     for (uint64_t q0 = 0; q0 < nq; q0 += QCHUNK) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(QCHUNK, nq - q0);
@@ -1926,11 +1854,11 @@ static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, u
     auto& sc = h->sq;
     LY_HIP(hipSetDevice(s->device));
     PoolRerank::Search rr(sc.rr);
-    LY_TRY(rr.begin(h->d_raw, n, D, D, h->metric, pool, k, k, qc, on_device, s->profiling.load(), "IVF-*-SQ8 rerank"));
-    LY_TRY(ivf_grow(&sc.d_q, &sc.q_cap, (size_t)qc * D * 2));
-    LY_TRY(ivf_grow(&sc.d_pdist, &sc.pdist_cap, (size_t)qc * pool));
-    float* d_qo = sc.d_q;                       // original queries
-    float* d_qd = sc.d_q + (size_t)qc * D;      // decoded queries
+    LY_TRY(rr.begin(h->d_raw.p, n, D, D, h->metric, pool, k, k, qc, on_device, s->profiling.load(), "IVF-*-SQ8 rerank"));
+    LY_TRY(sc.q.reserve((size_t)qc * D * 2));
+    LY_TRY(sc.pdist.reserve((size_t)qc * pool));
+    float* d_qo = sc.q.p;                       // original queries
+    float* d_qd = sc.q.p + (size_t)qc * D;      // decoded queries
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
         {
@@ -1938,12 +1866,12 @@ static int ivf_search_sq8(lynse_hip_ivf* h, const float* queries, uint64_t nq, u
             LY_TRY(use_device(s));
             hipStream_t st = cur(s).stream;
             LY_HIP(hipMemcpyAsync(d_qo, queries + q0 * D, (size_t)nqc * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-            LY_TRY(sq_codec_device(d_qo, nqc, D, h->d_sq, d_qd, st));
+            LY_TRY(sq_codec_device(d_qo, nqc, D, h->d_sq.p, d_qd, st));
             LY_TRY(rr.pool_start(st));
             LY_HIP(hipStreamSynchronize(st));
         }
         // pool stage: the decoded queries over the decoded rows, k = pool, results left in device memory
-        LY_TRY(ivf_search_locked(h, d_qd, nqc, pool, nprobe, sc.rr.d_prow, sc.d_pdist, sc.rr.d_pcnt, filtered, subset, n_subset, -1, true));
+        LY_TRY(ivf_search_locked(h, d_qd, nqc, pool, nprobe, sc.rr.prow.p, sc.pdist.p, sc.rr.pcnt.p, filtered, subset, n_subset, -1, true));
         std::unique_lock<std::shared_mutex> lk(s->rw);
         LY_TRY(use_device(s));
         LY_TRY(rr.run(d_qo, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, s->profiling.load() ? cur(s).ws.pool_total : nullptr,

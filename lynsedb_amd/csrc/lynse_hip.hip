@@ -67,6 +67,58 @@ static int set_error(int code, const std::string& msg) {
         if (_rc != LYNSE_OK) return _rc; \
     } while (0)
 
+// The one owning device buffer of the host code: p and cap count elements of T.  Move-only; the destructor frees, so a struct of
+// these needs no release list and a local one is freed on every exit path; release() hands the block over.  Every grow-on-demand
+// scratch array, every function-local device temporary and the device arrays of the IVF, graph, sparse, text and field handles are
+// one.  Left as raw pointers: the flat handle's row data and derived
+// copies (rows, rows_h, rows16, packed, vn2, vrinv, bpm and the CodeSet members: the row-range views repoint them at offsets inside
+// the allocations, and rows16 can alias rows_h), Workspace (allocated in one place, ensure_workspace) and comm_host.inc.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    T* release() {
+        T* q = p;
+        p = nullptr;
+        cap = 0;
+        return q;
+    }
+    // a fresh block of max(count, 1) elements
+    int alloc(size_t count) { return fresh(std::max<size_t>(count, 1)); }
+    // Room for `need` elements; the contents are NOT preserved.  reserve() grows to max(need, 2 * cap), reserve_exact() to `need`.
+    // A failed allocation leaves (nullptr, 0): the next call allocates again instead of using a null pointer of the old capacity.
+    int reserve(size_t need) { return need <= cap ? LYNSE_OK : fresh(std::max(need, cap * 2)); }
+    int reserve_exact(size_t need) { return need <= cap ? LYNSE_OK : fresh(need); }
+
+private:
+    int fresh(size_t count) {
+        reset();
+        T* q = nullptr;
+        LY_HIP(hipMalloc(&q, count * sizeof(T)));
+        p = q;
+        cap = count;
+        return LYNSE_OK;
+    }
+};
+
 // hipMemset on device memory may return before the fill has run (it is ordered on the NULL stream), and the search contexts'
 // streams are created hipStreamNonBlocking: they do NOT wait for the null stream.  A kernel on a context stream could therefore
 // start before the one-time clears of a fresh workspace had landed — seen as a first search on a new index that came back with
@@ -313,10 +365,8 @@ struct lynse_hip_flat {
         std::vector<hipEvent_t> ev_pool;
         // filtered search: row bitmask of the subset + staging for the subset ids — per context, so that masked filtered
         // searches run under the shared lock like unfiltered ones (the gathered-rows strategy swaps handle fields: exclusive)
-        uint32_t* d_mask = nullptr;
-        uint64_t mask_words = 0;
-        uint64_t* d_subset = nullptr;
-        uint64_t subset_cap = 0;
+        DevBuf<uint32_t> mask;
+        DevBuf<uint64_t> subset;
     };
     static constexpr int MAX_CTX = 8;
     Ctx ctx[MAX_CTX];
@@ -388,10 +438,9 @@ struct lynse_hip_flat {
     uint64_t n_bpm = 0, bpm_cap = 0;
     bool bpm_failed = false;             // the copy did not fit: the popcount kernels answer
     // gathered ("few matches") filtered path: compact copy of the listed shadow rows, their norms and 32-bit ids
-    _Float16* g_rows16 = nullptr;
-    float *g_vn2 = nullptr, *g_vrinv = nullptr;
-    uint32_t* g_ids32 = nullptr;
-    uint64_t g_cap = 0;
+    DevBuf<_Float16> g_rows16;
+    DevBuf<float> g_vn2, g_vrinv;
+    DevBuf<uint32_t> g_ids32;
 
     PqState* pq = nullptr;                // FLAT-{IP,L2,COS}-PQ index over the first pq->n rows (pq_host.inc); NULL = none
     RbqState* rbq = nullptr;              // FLAT-{IP,L2,COS}-RABITQ index over the first rbq->n rows (rabitq_host.inc); NULL = none
@@ -555,13 +604,10 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
     for (auto& c : h->ctx) {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
         c.ws.release();
-        if (c.d_mask) (void)hipFree(c.d_mask);
-        if (c.d_subset) (void)hipFree(c.d_subset);
         for (auto e : c.ev_pool) (void)hipEventDestroy(e);
     }
     if (h->shadow_alias) h->rows16 = nullptr;
     for (void* p : {(void*)h->rows, (void*)h->rows_h, (void*)h->rows16, (void*)h->packed, (void*)h->vn2, (void*)h->vrinv, (void*)h->d_stats,
-                    (void*)h->g_rows16, (void*)h->g_vn2, (void*)h->g_vrinv, (void*)h->g_ids32,
                     (void*)h->bpm, (void*)h->sq8_mm_prev})
         if (p) (void)hipFree(p);
     for (CodeSet* s : {&h->sq8, &h->sq8a, &h->sq8c, &h->sq7}) s->release();
@@ -572,15 +618,27 @@ extern "C" int lynse_hip_flat_destroy(lynse_hip_flat* h) {
 }
 
 static int realloc_rows_h(lynse_hip_flat* h, uint64_t cap) {   // F16 shard: capacity of the f16 row matrix
-    _Float16* nr = nullptr;
-    LY_HIP(hipMalloc(&nr, (size_t)cap * h->ld16 * sizeof(_Float16) + 256));
+    DevBuf<_Float16> nr;   // (held until the copy has succeeded)
+    LY_TRY(nr.alloc((size_t)cap * h->ld16 + 128));
     if (h->rows_h && h->n)
-        LY_HIP(hipMemcpyAsync(nr, h->rows_h, (size_t)h->n * h->ld16 * sizeof(_Float16), hipMemcpyDeviceToDevice, cur(h).stream));
+        LY_HIP(hipMemcpyAsync(nr.p, h->rows_h, (size_t)h->n * h->ld16 * sizeof(_Float16), hipMemcpyDeviceToDevice, cur(h).stream));
     LY_HIP(hipStreamSynchronize(cur(h).stream));
     if (h->rows_h) (void)hipFree(h->rows_h);
-    h->rows_h = nr;
+    h->rows_h = nr.release();
     h->capacity = cap;
     if (h->shadow_alias) { h->rows16 = h->rows_h; h->cap16 = cap; }
+    return LYNSE_OK;
+}
+
+static int realloc_rows(lynse_hip_flat* h, uint64_t cap) {   // F32 shard: capacity of the f32 row matrix
+    DevBuf<float> nr;
+    LY_TRY(nr.alloc((size_t)cap * h->ld));
+    if (h->rows && h->n)
+        LY_HIP(hipMemcpyAsync(nr.p, h->rows, (size_t)h->n * h->ld * sizeof(float), hipMemcpyDeviceToDevice, cur(h).stream));
+    LY_HIP(hipStreamSynchronize(cur(h).stream));
+    if (h->rows) (void)hipFree(h->rows);
+    h->rows = nr.release();
+    h->capacity = cap;
     return LYNSE_OK;
 }
 
@@ -589,28 +647,20 @@ static int grow_rows(lynse_hip_flat* h, uint64_t need) {
     uint64_t cap = std::max<uint64_t>(need, h->capacity + h->capacity / 2);
     cap = std::max<uint64_t>(cap, 1024);
     if (is_f16(h)) return realloc_rows_h(h, cap);
-    float* nr = nullptr;
-    LY_HIP(hipMalloc(&nr, (size_t)cap * h->ld * sizeof(float)));
-    if (h->rows && h->n)
-        LY_HIP(hipMemcpyAsync(nr, h->rows, (size_t)h->n * h->ld * sizeof(float), hipMemcpyDeviceToDevice, cur(h).stream));
-    LY_HIP(hipStreamSynchronize(cur(h).stream));
-    if (h->rows) (void)hipFree(h->rows);
-    h->rows = nr;
-    h->capacity = cap;
-    return LYNSE_OK;
+    return realloc_rows(h, cap);
 }
 
 static int grow_packed(lynse_hip_flat* h, uint64_t need) {
     if (need <= h->packed_capacity) return LYNSE_OK;
     uint64_t cap = std::max<uint64_t>(need, h->packed_capacity + h->packed_capacity / 2);
     cap = std::max<uint64_t>(cap, 1024);
-    uint64_t* np = nullptr;
-    LY_HIP(hipMalloc(&np, (size_t)cap * h->words * sizeof(uint64_t)));
+    DevBuf<uint64_t> np;
+    LY_TRY(np.alloc((size_t)cap * h->words));
     if (h->packed && h->n_packed)
-        LY_HIP(hipMemcpyAsync(np, h->packed, (size_t)h->n_packed * h->words * 8, hipMemcpyDeviceToDevice, cur(h).stream));
+        LY_HIP(hipMemcpyAsync(np.p, h->packed, (size_t)h->n_packed * h->words * 8, hipMemcpyDeviceToDevice, cur(h).stream));
     LY_HIP(hipStreamSynchronize(cur(h).stream));
     if (h->packed) (void)hipFree(h->packed);
-    h->packed = np;
+    h->packed = np.release();
     h->packed_capacity = cap;
     return LYNSE_OK;
 }
@@ -622,17 +672,7 @@ extern "C" int lynse_hip_flat_reserve(lynse_hip_flat* h, uint64_t rows) {
     if (rows > 0xfffffff0ull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row count exceeds the u32 id capacity of one shard");
     if (h->packed_only) return grow_packed(h, rows);
     if (rows > h->capacity && is_f16(h)) return realloc_rows_h(h, rows);
-    if (rows > h->capacity) {
-        // exact reservation (no 1.5x slack): callers reserve to size a shard to its HBM budget
-        float* nr = nullptr;
-        LY_HIP(hipMalloc(&nr, (size_t)rows * h->ld * sizeof(float)));
-        if (h->rows && h->n)
-            LY_HIP(hipMemcpyAsync(nr, h->rows, (size_t)h->n * h->ld * sizeof(float), hipMemcpyDeviceToDevice, cur(h).stream));
-        LY_HIP(hipStreamSynchronize(cur(h).stream));
-        if (h->rows) (void)hipFree(h->rows);
-        h->rows = nr;
-        h->capacity = rows;
-    }
+    if (rows > h->capacity) return realloc_rows(h, rows);   // exact reservation (no 1.5x slack): callers reserve to size a shard to its HBM budget
     return LYNSE_OK;
 }
 
@@ -679,16 +719,15 @@ static int append_f32_impl(lynse_hip_flat* h, const float* src, uint64_t n, hipM
             LY_TRY(convert(src, n, 0));
         } else {
             const uint64_t chunk = std::max<uint64_t>(1, STAGE_BYTES / ((uint64_t)h->dim * 4));
-            float* stage = nullptr;
-            LY_HIP(hipMalloc(&stage, (size_t)std::min<uint64_t>(chunk, n) * h->dim * 4));
+            DevBuf<float> stage;
+            LY_TRY(stage.alloc((size_t)std::min<uint64_t>(chunk, n) * h->dim));
             for (uint64_t r = 0; r < n; r += chunk) {
                 const uint64_t nr = std::min<uint64_t>(chunk, n - r);
-                int rc = hipMemcpyAsync(stage, src + r * h->dim, (size_t)nr * h->dim * 4, kind, cur(h).stream) == hipSuccess ? convert(stage, nr, r)
+                int rc = hipMemcpyAsync(stage.p, src + r * h->dim, (size_t)nr * h->dim * 4, kind, cur(h).stream) == hipSuccess ? convert(stage.p, nr, r)
                                                                                                                        : set_error(LYNSE_ERR_DEVICE, "host-to-device copy failed");
                 if (rc == LYNSE_OK && hipStreamSynchronize(cur(h).stream) != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "stream sync failed");
-                if (rc != LYNSE_OK) { (void)hipFree(stage); return rc; }
+                if (rc != LYNSE_OK) return rc;
             }
-            (void)hipFree(stage);
         }
         LY_HIP(hipStreamSynchronize(cur(h).stream));
         h->n += n;
@@ -701,17 +740,16 @@ static int append_f32_impl(lynse_hip_flat* h, const float* src, uint64_t n, hipM
         LY_TRY(copy_rows_kernel(h, dst, h->ld, src, h->dim, h->dim, n, 1));
     } else {
         const uint64_t chunk = std::max<uint64_t>(1, STAGE_BYTES / ((uint64_t)h->dim * 4));
-        float* stage = nullptr;
-        LY_HIP(hipMalloc(&stage, (size_t)std::min<uint64_t>(chunk, n) * h->dim * 4));
+        DevBuf<float> stage;
+        LY_TRY(stage.alloc((size_t)std::min<uint64_t>(chunk, n) * h->dim));
         for (uint64_t r = 0; r < n; r += chunk) {
             const uint64_t nr = std::min<uint64_t>(chunk, n - r);
-            hipError_t e = hipMemcpyAsync(stage, src + r * h->dim, (size_t)nr * h->dim * 4, kind, cur(h).stream);
-            int rc = e == hipSuccess ? copy_rows_kernel(h, dst + r * h->ld, h->ld, stage, h->dim, h->dim, nr, 1)
+            hipError_t e = hipMemcpyAsync(stage.p, src + r * h->dim, (size_t)nr * h->dim * 4, kind, cur(h).stream);
+            int rc = e == hipSuccess ? copy_rows_kernel(h, dst + r * h->ld, h->ld, stage.p, h->dim, h->dim, nr, 1)
                                      : set_error(LYNSE_ERR_DEVICE, hipGetErrorString(e));
             if (rc == LYNSE_OK && hipStreamSynchronize(cur(h).stream) != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "stream sync failed");
-            if (rc != LYNSE_OK) { (void)hipFree(stage); return rc; }
+            if (rc != LYNSE_OK) return rc;
         }
-        (void)hipFree(stage);
     }
     LY_HIP(hipStreamSynchronize(cur(h).stream));   // (F16 shards returned above: they keep their rows as f16 bits only)
     h->n += n;
@@ -949,18 +987,17 @@ extern "C" int lynse_hip_flat_read_rows(const lynse_hip_flat* hc, uint64_t first
         return LYNSE_OK;
     }
     const uint64_t chunk = std::max<uint64_t>(1, STAGE_BYTES / ((uint64_t)h->dim * 4));
-    float* stage = nullptr;
-    LY_HIP(hipMalloc(&stage, (size_t)std::min<uint64_t>(chunk, n) * h->dim * 4));
+    DevBuf<float> stage;
+    LY_TRY(stage.alloc((size_t)std::min<uint64_t>(chunk, n) * h->dim));
     for (uint64_t r = 0; r < n; r += chunk) {
         const uint64_t nr = std::min<uint64_t>(chunk, n - r);
-        int rc = is_f16(h) ? decode_rows_kernel(h, stage, h->dim, first + r, nr)
-                           : copy_rows_kernel(h, stage, h->dim, h->rows + (size_t)(first + r) * h->ld, h->ld, h->dim, nr, 0);
-        if (rc == LYNSE_OK && hipMemcpyAsync(out + r * h->dim, stage, (size_t)nr * h->dim * 4, hipMemcpyDeviceToHost, cur(h).stream) != hipSuccess)
+        int rc = is_f16(h) ? decode_rows_kernel(h, stage.p, h->dim, first + r, nr)
+                           : copy_rows_kernel(h, stage.p, h->dim, h->rows + (size_t)(first + r) * h->ld, h->ld, h->dim, nr, 0);
+        if (rc == LYNSE_OK && hipMemcpyAsync(out + r * h->dim, stage.p, (size_t)nr * h->dim * 4, hipMemcpyDeviceToHost, cur(h).stream) != hipSuccess)
             rc = set_error(LYNSE_ERR_DEVICE, "device-to-host copy failed");
         if (rc == LYNSE_OK && hipStreamSynchronize(cur(h).stream) != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "stream sync failed");
-        if (rc != LYNSE_OK) { (void)hipFree(stage); return rc; }
+        if (rc != LYNSE_OK) return rc;
     }
-    (void)hipFree(stage);
     return LYNSE_OK;
 }
 
@@ -2899,35 +2936,19 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
     if (filtered) {
         direct = strategy_known ? strategy_direct : choose_direct();   // (caller_holds_exclusive: evaluated here, under that lock)
         if (direct && !xlk.owns_lock() && !caller_holds_exclusive) return set_error(LYNSE_ERR_INTERNAL, "gathered-rows filter strategy without the exclusive lock");
-        if (n_subset > fc.subset_cap && (direct || !bitset_words)) {
-            if (fc.d_subset) (void)hipFree(fc.d_subset);
-            fc.d_subset = nullptr;
-            LY_HIP(hipMalloc(&fc.d_subset, n_subset * 8));
-            fc.subset_cap = n_subset;
-        }
+        if (direct || !bitset_words) LY_TRY(fc.subset.reserve_exact(n_subset));
         bool ids_on_device = false;
         if (bitset_words && direct) {  // BitSet::to_vec on the device: upload the words (they double as scratch in d_mask), expand
             const uint64_t nw = std::min<uint64_t>(n_words, (h->n + 63) / 64);
             const uint64_t words32 = (std::max<uint64_t>(h->n, h->capacity) + 511) / 32 + 8;
             const uint32_t nblocks = (uint32_t)((nw + 255) / 256);
-            if (words32 + nblocks + 16 > fc.mask_words) {
-                if (fc.d_mask) (void)hipFree(fc.d_mask);
-                fc.d_mask = nullptr;
-                LY_HIP(hipMalloc(&fc.d_mask, (words32 + nblocks + 16) * 4));
-                fc.mask_words = words32 + nblocks + 16;
-            }
-            if (n_subset > fc.subset_cap) {
-                if (fc.d_subset) (void)hipFree(fc.d_subset);
-                fc.d_subset = nullptr;
-                LY_HIP(hipMalloc(&fc.d_subset, n_subset * 8));
-                fc.subset_cap = n_subset;
-            }
-            uint32_t* d_counts = fc.d_mask + words32;
-            LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, nw * 8, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
-            const uint64_t* d_words = reinterpret_cast<const uint64_t*>(fc.d_mask);
+            LY_TRY(fc.mask.reserve_exact(words32 + nblocks + 16));
+            uint32_t* d_counts = fc.mask.p + words32;
+            LY_HIP(hipMemcpyAsync(fc.mask.p, bitset_words, nw * 8, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
+            const uint64_t* d_words = reinterpret_cast<const uint64_t*>(fc.mask.p);
             hipLaunchKernelGGL(k_bits_count, dim3(nblocks), dim3(256), 0, st0, d_words, nw, h->n, d_counts);
             hipLaunchKernelGGL(k_bits_offsets, dim3(1), dim3(1024), 0, st0, d_counts, nblocks);
-            hipLaunchKernelGGL(k_bits_expand, dim3(nblocks), dim3(256), 0, st0, d_words, nw, h->n, d_counts, fc.d_subset);
+            hipLaunchKernelGGL(k_bits_expand, dim3(nblocks), dim3(256), 0, st0, d_words, nw, h->n, d_counts, fc.subset.p);
             LY_HIP(hipGetLastError());
             ids_on_device = true;
         }
@@ -2944,45 +2965,36 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
                 n_subset = sorted_subset.size();
             }
         }
-        if (src && n_subset && !ids_on_device) LY_HIP(hipMemcpyAsync(fc.d_subset, src, n_subset * 8, hipMemcpyHostToDevice, st0));
+        if (src && n_subset && !ids_on_device) LY_HIP(hipMemcpyAsync(fc.subset.p, src, n_subset * 8, hipMemcpyHostToDevice, st0));
         if (!direct) {  // subset ids -> row bitmask on the device (the reference's bitset, flat_mmap.rs:672-679)
             const uint64_t words = (std::max<uint64_t>(h->n, h->capacity) + 511) / 32 + 8;
-            if (words > fc.mask_words) {
-                if (fc.d_mask) (void)hipFree(fc.d_mask);
-                fc.d_mask = nullptr;
-                LY_HIP(hipMalloc(&fc.d_mask, words * 4));
-                fc.mask_words = words;
-            }
-            LY_HIP(hipMemsetAsync(fc.d_mask, 0, fc.mask_words * 4, st0));
+            LY_TRY(fc.mask.reserve_exact(words));
+            LY_HIP(hipMemsetAsync(fc.mask.p, 0, fc.mask.cap * 4, st0));
             if (bitset_words) {  // the caller's BitSet words ARE the mask (u64 LE = two u32 words); bits >= len never match a row
                 const uint64_t bytes = std::min<uint64_t>(n_words * 8, (h->n + 63) / 64 * 8);
-                LY_HIP(hipMemcpyAsync(fc.d_mask, bitset_words, bytes, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
+                LY_HIP(hipMemcpyAsync(fc.mask.p, bitset_words, bytes, words_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st0));
             } else {
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_subset + 255) / 256, (uint64_t)h->num_cu * 8);
-                hipLaunchKernelGGL(k_mask_build, dim3(std::max<uint32_t>(blocks, 1)), dim3(256), 0, st0, fc.d_subset, n_subset, h->n, fc.d_mask);
+                hipLaunchKernelGGL(k_mask_build, dim3(std::max<uint32_t>(blocks, 1)), dim3(256), 0, st0, fc.subset.p, n_subset, h->n, fc.mask.p);
                 LY_HIP(hipGetLastError());
             }
         }
         if (direct && n_subset) {  // compact copy of the listed shadow rows + norms + 32-bit ids
-            if (n_subset > h->g_cap) {
-                for (void* p : {(void*)h->g_rows16, (void*)h->g_vn2, (void*)h->g_vrinv, (void*)h->g_ids32})
-                    if (p) (void)hipFree(p);
-                h->g_rows16 = nullptr; h->g_vn2 = h->g_vrinv = nullptr; h->g_ids32 = nullptr; h->g_cap = 0;
-                LY_HIP(hipMalloc(&h->g_rows16, (size_t)n_subset * h->ld16 * 2 + 256));
-                LY_HIP(hipMalloc(&h->g_vn2, ((size_t)n_subset + 256) * 4));
-                LY_HIP(hipMalloc(&h->g_vrinv, ((size_t)n_subset + 256) * 4));
-                LY_HIP(hipMalloc(&h->g_ids32, ((size_t)n_subset + 256) * 4));
-                LY_HIP(hipMemsetAsync(h->g_vn2, 0, ((size_t)n_subset + 256) * 4, st0));
-                LY_HIP(hipMemsetAsync(h->g_vrinv, 0, ((size_t)n_subset + 256) * 4, st0));
-                h->g_cap = n_subset;
-            }
+            const size_t padded = (size_t)n_subset + 256;
+            LY_TRY(h->g_rows16.reserve_exact((size_t)n_subset * h->ld16 + 128));
+            for (DevBuf<float>* g : {&h->g_vn2, &h->g_vrinv})
+                if (padded > g->cap) {
+                    LY_TRY(g->reserve_exact(padded));
+                    LY_HIP(hipMemsetAsync(g->p, 0, padded * 4, st0));
+                }
+            LY_TRY(h->g_ids32.reserve_exact(padded));
             const uint64_t pieces = n_subset * (h->ld16 / 8);
             LY_TRY(need_shadow());   // (the gathered-rows strategy runs under the writer lock)
             hipLaunchKernelGGL(k_gather_rows16, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, (uint64_t)h->num_cu * 32)), dim3(256), 0,
-                               st0, h->rows16, h->ld16, fc.d_subset, n_subset, h->g_rows16);
+                               st0, h->rows16, h->ld16, fc.subset.p, n_subset, h->g_rows16.p);
             LY_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_gather_norms, dim3((uint32_t)std::min<uint64_t>((n_subset + 255) / 256, (uint64_t)h->num_cu * 8)), dim3(256), 0,
-                               st0, h->vn2, h->vrinv, fc.d_subset, n_subset, h->g_vn2, h->g_vrinv, h->g_ids32);
+                               st0, h->vn2, h->vrinv, fc.subset.p, n_subset, h->g_vn2.p, h->g_vrinv.p, h->g_ids32.p);
             LY_HIP(hipGetLastError());
         }
         LY_HIP(hipStreamSynchronize(st0));  // `subset` / sorted_subset are caller / stack memory
@@ -2993,14 +3005,14 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             return LYNSE_OK;
         }
     }
-    const uint32_t* mask = (filtered && !direct) ? fc.d_mask : nullptr;
+    const uint32_t* mask = (filtered && !direct) ? fc.mask.p : nullptr;
     // the gathered path scans the compact store through the ordinary pipeline: point the scan-side fields of the handle
     // at it for the duration of this call (the mutex is held); rescoring keeps using the f32 source rows by original id
     struct ViewGuard {
         lynse_hip_flat* h; bool on; _Float16* r16; uint64_t n; float *vn2, *vrinv;
         ~ViewGuard() { if (on) { h->rows16 = r16; h->n = n; h->vn2 = vn2; h->vrinv = vrinv; } }
     } view{h, direct, h->rows16, h->n, h->vn2, h->vrinv};
-    if (direct) { h->rows16 = h->g_rows16; h->n = n_subset; h->vn2 = h->g_vn2; h->vrinv = h->g_vrinv; }
+    if (direct) { h->rows16 = h->g_rows16.p; h->n = n_subset; h->vn2 = h->g_vn2.p; h->vrinv = h->g_vrinv.p; }
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     ScanProf sprof;
@@ -3075,7 +3087,7 @@ static int search_impl_once(lynse_hip_flat* h, const void* q_src, bool packed_qu
             const bool staged = !on_device && rows_b + dists_b <= H_OUT_BYTES;
             ChunkReq rq;
             rq.nq = nqc; rq.k = kk; rq.out_k = k; rq.metric = metric; rq.level = level;
-            rq.mask = mask; rq.row_ids = direct ? h->g_ids32 : nullptr; rq.qsrc = qsrc;
+            rq.mask = mask; rq.row_ids = direct ? h->g_ids32.p : nullptr; rq.qsrc = qsrc;
             rq.i8c = i8c; rq.allow_sts = allow_sts; rq.allow_sq7 = allow_sq7; rq.allow_predict = allow_predict;
             rq.out.rows = on_device ? out_rows + q0 * k : (staged ? reinterpret_cast<uint64_t*>(w.h_out) : nullptr);
             rq.out.dists = on_device ? out_dists + q0 * k : (staged ? reinterpret_cast<float*>(w.h_out + rows_b) : nullptr);

@@ -112,37 +112,35 @@ static int compact_rows_locked(lynse_hip_flat* h, const CompactPlan& p) {
     if (rb / 4 > 0xffffffffull) return set_error(LYNSE_ERR_UNSUPPORTED, "row too wide to compact");
     char* rows = is_f16(h) ? reinterpret_cast<char*>(h->rows_h) : reinterpret_cast<char*>(h->rows);
     const bool wide = rb % 16 == 0;   // (every pitch this library produces: round_up(dim, 4) floats, round_up(dim, 8) halves)
-    uint64_t* d_keep = nullptr;
-    uint32_t* d_base = nullptr;
-    char* scratch = nullptr;
+    DevBuf<uint64_t> d_keep;   // (freed on return, behind the synchronise below)
+    DevBuf<uint32_t> d_base;
+    DevBuf<char> scratch;
     auto run = [&]() -> int {
         uint64_t staged_rows = 0;
         for (const CompactWindow& w : p.windows)
             if (w.path == COMPACT_STAGED) staged_rows = std::max(staged_rows, w.live);
-        LY_HIP(hipMalloc(&d_keep, p.keep.size() * 8));
-        LY_HIP(hipMalloc(&d_base, p.word_base.size() * 4));
-        if (staged_rows) LY_HIP(hipMalloc(&scratch, (size_t)(staged_rows * rb)));
-        LY_HIP(hipMemcpyAsync(d_keep, p.keep.data(), p.keep.size() * 8, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemcpyAsync(d_base, p.word_base.data(), p.word_base.size() * 4, hipMemcpyHostToDevice, st));
+        LY_TRY(d_keep.alloc(p.keep.size()));
+        LY_TRY(d_base.alloc(p.word_base.size()));
+        if (staged_rows) LY_TRY(scratch.alloc((size_t)(staged_rows * rb)));
+        LY_HIP(hipMemcpyAsync(d_keep.p, p.keep.data(), p.keep.size() * 8, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(d_base.p, p.word_base.data(), p.word_base.size() * 4, hipMemcpyHostToDevice, st));
         for (const CompactWindow& w : p.windows) {
             if (w.path == COMPACT_UNTOUCHED || w.live == 0) continue;
             const uint64_t nrows = std::min<uint64_t>(p.window_rows, h->n - w.src);
             const bool staged = w.path == COMPACT_STAGED;
-            char* dst = staged ? scratch : rows + (size_t)(w.dst * rb);
+            char* dst = staged ? scratch.p : rows + (size_t)(w.dst * rb);
             const char* src = rows + (size_t)(w.src * rb);
-            if (wide) LY_TRY(launch_compact_window<uint4>(h, dst, src, rb, d_keep + w.src / 64, d_base + w.src / 64, (uint32_t)w.dst, nrows));
-            else LY_TRY(launch_compact_window<uint32_t>(h, dst, src, rb, d_keep + w.src / 64, d_base + w.src / 64, (uint32_t)w.dst, nrows));
+            if (wide) LY_TRY(launch_compact_window<uint4>(h, dst, src, rb, d_keep.p + w.src / 64, d_base.p + w.src / 64, (uint32_t)w.dst, nrows));
+            else LY_TRY(launch_compact_window<uint32_t>(h, dst, src, rb, d_keep.p + w.src / 64, d_base.p + w.src / 64, (uint32_t)w.dst, nrows));
             // staged: the copy writes rows [dst, dst + live), all below the window's end — every one of them has been read by this
             // launch or an earlier one, and the stream keeps the order
-            if (staged) LY_HIP(hipMemcpyAsync(rows + (size_t)(w.dst * rb), scratch, (size_t)(w.live * rb), hipMemcpyDeviceToDevice, st));
+            if (staged) LY_HIP(hipMemcpyAsync(rows + (size_t)(w.dst * rb), scratch.p, (size_t)(w.live * rb), hipMemcpyDeviceToDevice, st));
         }
         LY_HIP(hipStreamSynchronize(st));
         return LYNSE_OK;
     };
     const int rc = run();
     if (rc != LYNSE_OK) (void)hipStreamSynchronize(st);
-    for (void* q : {(void*)d_keep, (void*)d_base, (void*)scratch})
-        if (q) (void)hipFree(q);
     return rc;
 }
 
@@ -167,7 +165,7 @@ extern "C" int lynse_hip_flat_compact_rows(lynse_hip_flat* h, const uint64_t* ke
 
 // ------------------------------------------------------------------------------------------------------------------ update ----
 // the row list on the device, after the host has checked every row against `len` (and, for an update, against the others)
-static int upload_row_list(lynse_hip_flat* h, const uint64_t* rows, uint64_t n, bool distinct, uint64_t** d_rows) {
+static int upload_row_list(lynse_hip_flat* h, const uint64_t* rows, uint64_t n, bool distinct, DevBuf<uint64_t>& d_rows) {
     for (uint64_t i = 0; i < n; ++i)
         if (rows[i] >= h->n) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row " + std::to_string(rows[i]) + " is out of bounds (len " + std::to_string(h->n) + ")");
     if (distinct) {
@@ -177,13 +175,10 @@ static int upload_row_list(lynse_hip_flat* h, const uint64_t* rows, uint64_t n, 
         if (dup != s.end()) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "row " + std::to_string(*dup) + " is named twice in one update");
     }
     LY_TRY(use_device(h));
-    LY_HIP(hipMalloc(d_rows, (size_t)n * 8));
-    if (hipMemcpyAsync(*d_rows, rows, (size_t)n * 8, hipMemcpyHostToDevice, cur(h).stream) != hipSuccess ||
-        hipStreamSynchronize(cur(h).stream) != hipSuccess) {
-        (void)hipFree(*d_rows);
-        *d_rows = nullptr;
+    LY_TRY(d_rows.alloc((size_t)n));
+    if (hipMemcpyAsync(d_rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, cur(h).stream) != hipSuccess ||
+        hipStreamSynchronize(cur(h).stream) != hipSuccess)
         return set_error(LYNSE_ERR_DEVICE, "host-to-device copy of the row list failed");
-    }
     return LYNSE_OK;
 }
 
@@ -193,27 +188,25 @@ extern "C" int lynse_hip_flat_update_rows_f32(lynse_hip_flat* h, const uint64_t*
     LY_WRITER(h, lk);
     if (h->packed_only) return set_error(LYNSE_ERR_UNSUPPORTED, "store holds packed rows only: no f32 rows to update");
     if (n == 0) return LYNSE_OK;
-    uint64_t* d_rows = nullptr;
-    LY_TRY(upload_row_list(h, rows, n, true, &d_rows));   // (nothing has been written when it refuses)
+    DevBuf<uint64_t> d_rows;
+    LY_TRY(upload_row_list(h, rows, n, true, d_rows));   // (nothing has been written when it refuses)
     hipStream_t st = cur(h).stream;
     const uint64_t chunk = std::max<uint64_t>(1, STAGE_BYTES / ((uint64_t)h->dim * 4));
-    float* stage = nullptr;
-    int rc = hipMalloc(&stage, (size_t)std::min<uint64_t>(chunk, n) * h->dim * 4) == hipSuccess ? LYNSE_OK : set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(stage)");
+    DevBuf<float> stage;
+    int rc = stage.alloc((size_t)std::min<uint64_t>(chunk, n) * h->dim);
     for (uint64_t r = 0; rc == LYNSE_OK && r < n; r += chunk) {
         const uint64_t nr = std::min<uint64_t>(chunk, n - r);
-        if (hipMemcpyAsync(stage, data + r * h->dim, (size_t)nr * h->dim * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
+        if (hipMemcpyAsync(stage.p, data + r * h->dim, (size_t)nr * h->dim * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
             rc = set_error(LYNSE_ERR_DEVICE, "host-to-device copy failed");
             break;
         }
         const uint32_t pitch = is_f16(h) ? h->ld16 : h->ld;
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nr * pitch + 255) / 256, (uint64_t)h->num_cu * 32));
-        if (is_f16(h)) hipLaunchKernelGGL(k_scatter_rows<_Float16>, dim3(grid), dim3(256), 0, st, h->rows_h, pitch, d_rows + r, stage, h->dim, nr);
-        else hipLaunchKernelGGL(k_scatter_rows<float>, dim3(grid), dim3(256), 0, st, h->rows, pitch, d_rows + r, stage, h->dim, nr);
+        if (is_f16(h)) hipLaunchKernelGGL(k_scatter_rows<_Float16>, dim3(grid), dim3(256), 0, st, h->rows_h, pitch, d_rows.p + r, stage.p, h->dim, nr);
+        else hipLaunchKernelGGL(k_scatter_rows<float>, dim3(grid), dim3(256), 0, st, h->rows, pitch, d_rows.p + r, stage.p, h->dim, nr);
         if (hipGetLastError() != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "k_scatter_rows launch failed");
         else if (hipStreamSynchronize(st) != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "stream sync failed");   // (the stage is reused)
     }
-    if (stage) (void)hipFree(stage);
-    (void)hipFree(d_rows);
     const int rc2 = reset_derived_locked(h);   // (after a failure too: some rows may have been written)
     return rc != LYNSE_OK ? rc : rc2;
 }
@@ -225,23 +218,21 @@ extern "C" int lynse_hip_flat_gather_rows(const lynse_hip_flat* hc, const uint64
     std::unique_lock<std::shared_mutex> lk(h->rw);   // (the discipline of lynse_hip_flat_read_rows)
     if (h->packed_only) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "store holds packed rows only");
     if (n == 0) return LYNSE_OK;
-    uint64_t* d_rows = nullptr;
-    LY_TRY(upload_row_list(h, rows, n, false, &d_rows));
+    DevBuf<uint64_t> d_rows;
+    LY_TRY(upload_row_list(h, rows, n, false, d_rows));
     hipStream_t st = cur(h).stream;
     const uint64_t chunk = std::max<uint64_t>(1, STAGE_BYTES / ((uint64_t)h->dim * 4));
-    float* stage = nullptr;
-    int rc = hipMalloc(&stage, (size_t)std::min<uint64_t>(chunk, n) * h->dim * 4) == hipSuccess ? LYNSE_OK : set_error(LYNSE_ERR_OUT_OF_MEMORY, "hipMalloc(stage)");
+    DevBuf<float> stage;
+    int rc = stage.alloc((size_t)std::min<uint64_t>(chunk, n) * h->dim);
     for (uint64_t r = 0; rc == LYNSE_OK && r < n; r += chunk) {
         const uint64_t nr = std::min<uint64_t>(chunk, n - r);
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nr * h->dim + 255) / 256, (uint64_t)h->num_cu * 32));
-        if (is_f16(h)) hipLaunchKernelGGL(k_gather_rows<_Float16>, dim3(grid), dim3(256), 0, st, stage, h->rows_h, h->ld16, d_rows + r, h->dim, nr);
-        else hipLaunchKernelGGL(k_gather_rows<float>, dim3(grid), dim3(256), 0, st, stage, h->rows, h->ld, d_rows + r, h->dim, nr);
+        if (is_f16(h)) hipLaunchKernelGGL(k_gather_rows<_Float16>, dim3(grid), dim3(256), 0, st, stage.p, h->rows_h, h->ld16, d_rows.p + r, h->dim, nr);
+        else hipLaunchKernelGGL(k_gather_rows<float>, dim3(grid), dim3(256), 0, st, stage.p, h->rows, h->ld, d_rows.p + r, h->dim, nr);
         if (hipGetLastError() != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "k_gather_rows launch failed");
-        else if (hipMemcpyAsync(out + r * h->dim, stage, (size_t)nr * h->dim * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        else if (hipMemcpyAsync(out + r * h->dim, stage.p, (size_t)nr * h->dim * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
             rc = set_error(LYNSE_ERR_DEVICE, "device-to-host copy failed");
         else if (hipStreamSynchronize(st) != hipSuccess) rc = set_error(LYNSE_ERR_DEVICE, "stream sync failed");
     }
-    if (stage) (void)hipFree(stage);
-    (void)hipFree(d_rows);
     return rc;
 }

@@ -169,14 +169,14 @@ extern "C" int lynse_hip_flat_search_polarvec_f32(lynse_hip_flat* h, const float
     const auto score = [&](hipStream_t st, uint32_t nqc, bool asc) -> int {
         // a small batch spreads each query's table over up to 16 workgroups
         const uint32_t parts = nqc >= 32 ? 1u : (uint32_t)std::max<size_t>(1, std::min<size_t>(16, lut_q / 4096));
-        hipLaunchKernelGGL(k_plv_query, dim3(nqc, parts), dim3(RBQ_Q_NT), (size_t)p.P * 4, st, s.d_q, h->dim, p.P, p.bits, metric, p.d_sign.p,
-                           p.dim_mins.p, p.dim_scales.p, s.d_lut);
+        hipLaunchKernelGGL(k_plv_query, dim3(nqc, parts), dim3(RBQ_Q_NT), (size_t)p.P * 4, st, s.q.p, h->dim, p.P, p.bits, metric, p.d_sign.p,
+                           p.dim_mins.p, p.dim_scales.p, s.lut.p);
         LY_HIP(hipGetLastError());
         // the scan: QB = 4 queries share a code load when the batch has them and four unit tables fit 64 KiB of LDS
         const int qb = nqc >= 4 && (size_t)ue * 16 <= 64u * 1024u ? 4 : 1;
         const uint32_t cu = std::max<uint32_t>(1, std::min<uint32_t>(units, (64u * 1024u) / (ue * 4u * (uint32_t)qb)));
-        PlvScanArgs sa{reinterpret_cast<const uint4*>(p.codes.p), p.n, p.P, p.bits, p.cb, p.ng, cu, ub, ue, s.d_lut, nqc, asc ? 1 : 0,
-                       metric == M_L2 ? p.residual_sq.p : nullptr, metric == M_COS ? p.inv_norms.p : nullptr, s.cut.d_S};
+        PlvScanArgs sa{reinterpret_cast<const uint4*>(p.codes.p), p.n, p.P, p.bits, p.cb, p.ng, cu, ub, ue, s.lut.p, nqc, asc ? 1 : 0,
+                       metric == M_L2 ? p.residual_sq.p : nullptr, metric == M_COS ? p.inv_norms.p : nullptr, s.cut.S.p};
         const dim3 sgrid((uint32_t)((p.n + PLV_NT * PLV_R - 1) / (PLV_NT * PLV_R)), (nqc + qb - 1) / qb);
         const size_t slds = (size_t)qb * cu * ue * 4;
         switch (cls) {

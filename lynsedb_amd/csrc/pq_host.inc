@@ -264,13 +264,13 @@ extern "C" int lynse_hip_flat_search_pq_f32(lynse_hip_flat* h, const float* quer
     CodedScratch& s = h->pq->s;
     const auto score = [&](hipStream_t st, uint32_t nqc, bool asc) -> int {
         const uint64_t lut_threads = (uint64_t)nqc * p.M * p.K;
-        hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, s.d_q, nqc, h->dim, p.M, p.ss, p.K, p.cb.p,
-                           metric == M_IP ? 1 : 0, s.d_lut);
+        hipLaunchKernelGGL(k_pq_lut, dim3((uint32_t)((lut_threads + 255) / 256)), dim3(256), 0, st, s.q.p, nqc, h->dim, p.M, p.ss, p.K, p.cb.p,
+                           metric == M_IP ? 1 : 0, s.lut.p);
         LY_HIP(hipGetLastError());
         // the ADC scan: QB = 4 queries share a code load when the batch has them; tables in <= 64 KiB of LDS
         const int qb = nqc >= 4 ? 4 : 1;
         const uint32_t mc = std::max<uint32_t>(1, std::min<uint32_t>(p.M, 16384u / ((uint32_t)qb * p.K)));
-        PqAdcArgs aa{p.codes.p, p.n, p.M, p.K, mc, s.d_lut, nqc, asc ? 1 : 0, s.cut.d_S};
+        PqAdcArgs aa{p.codes.p, p.n, p.M, p.K, mc, s.lut.p, nqc, asc ? 1 : 0, s.cut.S.p};
         const dim3 agrid((uint32_t)((p.n + PQ_NT * PQ_R - 1) / (PQ_NT * PQ_R)), (nqc + qb - 1) / qb);
         const size_t alds = (size_t)qb * mc * p.K * 4;
         if (qb == 4) hipLaunchKernelGGL(k_pq_adc<4>, agrid, dim3(PQ_NT), alds, st, aa);

@@ -10,7 +10,7 @@ struct RbqIndex : RotCodes {
 };
 struct RbqState {
     RbqIndex ix;
-    CodedScratch s;   // (coded_host.inc; d_extra is total_q)
+    CodedScratch s;   // (coded_host.inc; extra is total_q)
 };
 
 // generate_sign_words (rabitq_mmap.rs:337-340): word w = the w-th next_u64() of SmallRng::seed_from_u64(seed)
@@ -125,14 +125,14 @@ extern "C" int lynse_hip_flat_search_rabitq_f32(lynse_hip_flat* h, const float* 
     const auto score = [&](hipStream_t st, uint32_t nqc, bool asc) -> int {
         // a small batch spreads each query's tables over up to 8 workgroups; one more per query sums total_q
         const uint32_t parts = nqc >= 32 ? 1u : std::max<uint32_t>(1, std::min<uint32_t>(8, p.cb / 16));
-        hipLaunchKernelGGL(k_rbq_query, dim3(nqc, parts + 1), dim3(RBQ_Q_NT), (size_t)p.P * 4, st, s.d_q, h->dim, p.P, p.cb, p.d_sign.p, s.d_lut,
-                           s.d_extra);
+        hipLaunchKernelGGL(k_rbq_query, dim3(nqc, parts + 1), dim3(RBQ_Q_NT), (size_t)p.P * 4, st, s.q.p, h->dim, p.P, p.cb, p.d_sign.p, s.lut.p,
+                           s.extra.p);
         LY_HIP(hipGetLastError());
         // the scan: QB = 4 queries share a code load when the batch has them; tables in <= 64 KiB of LDS, whole column groups
         const int qb = nqc >= 4 ? 4 : 1;
         const uint32_t mc = p.cb < 16 ? p.cb : std::min<uint32_t>(p.cb, 64u / (uint32_t)qb);
-        RbqScanArgs sa{reinterpret_cast<const uint4*>(p.codes.p), p.norms.p, p.n, p.cb, p.ng, mc, (float)p.P, s.d_lut, s.d_extra, nqc,
-                       asc ? 1 : 0, s.cut.d_S};
+        RbqScanArgs sa{reinterpret_cast<const uint4*>(p.codes.p), p.norms.p, p.n, p.cb, p.ng, mc, (float)p.P, s.lut.p, s.extra.p, nqc,
+                       asc ? 1 : 0, s.cut.S.p};
         const dim3 sgrid((uint32_t)((p.n + RBQ_NT * RBQ_R - 1) / (RBQ_NT * RBQ_R)), (nqc + qb - 1) / qb);
         const size_t slds = (size_t)qb * mc * 256 * 4;
         if (qb == 4) hipLaunchKernelGGL(k_rbq_scan<4>, sgrid, dim3(RBQ_NT), slds, st, sa);

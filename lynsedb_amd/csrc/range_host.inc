@@ -2,23 +2,17 @@
 // lynse_hip.hip after rabitq_host.inc; kernels in range.h, the cut at max_results is ScoreCut::cut and the order k_pool_select or
 // select_pool_keys (rerank_host.inc).  DESIGN.md §16.
 
-// The per-handle scratch of the search (it runs under the exclusive lock).  rr lends its buffers: d_keys takes the emitted keys,
-// d_pcnt their number, d_out the sorted rows | distances | counts of a chunk.
+// The per-handle scratch of the search (it runs under the exclusive lock).  rr lends its buffers: keys takes the emitted keys,
+// pcnt their number, out the sorted rows | distances | counts of a chunk.
 struct RangeState {
-    float *d_q = nullptr, *d_thr = nullptr;
-    uint64_t *d_qw = nullptr, *d_mask = nullptr;
-    uint32_t* d_cnt = nullptr;
-    size_t q_cap = 0, thr_cap = 0, qw_cap = 0, mask_cap = 0, cnt_cap = 0;
+    DevBuf<float> q, thr;
+    DevBuf<uint64_t> d_qw, mask;   // (qw and cnt are the host images below)
+    DevBuf<uint32_t> d_cnt;
     ScoreCut cut;
     PoolRerank rr;
     std::vector<uint32_t> cnt;
     std::vector<uint64_t> qw, keys, h_out;
-    ~RangeState() {
-        for (void* p : {(void*)d_q, (void*)d_thr, (void*)d_qw, (void*)d_mask, (void*)d_cnt})
-            if (p) (void)hipFree(p);
-        cut.release();
-        rr.release();
-    }
+    ~RangeState() { rr.release(); }
 };
 
 static void range_release(lynse_hip_flat* h) {
@@ -26,7 +20,7 @@ static void range_release(lynse_hip_flat* h) {
     h->range = nullptr;
 }
 
-// What follows a scan that left the score images in cut.d_S and the passer counts in d_cnt (the range search here, the sparse search
+// What follows a scan that left the score images in cut.S and the passer counts in d_cnt (the range search here, the sparse search
 // in sparse_host.inc): the counts read back into out_passed / out_counts, the best min(passed, N) keys of each of the nqc queries by the
 // canonical (score, row) key written best first at stride out_k and padded with rows ~0 and the worst score.  A query with more
 // passers than N goes through the radix selection of its N best keys; any other takes every key below RANGE_FAIL (a state that starts
@@ -63,30 +57,30 @@ static int range_cut_and_order(ScoreCut& cut, PoolRerank& rr, const uint32_t* d_
         for (uint32_t i = 0; i < nqc; ++i) pad(i, 0);
         return launched();
     }
-    LY_TRY(cut.cut<true>(nqc, n, N, select, rr.d_keys, rr.d_pcnt, st));
+    LY_TRY(cut.cut<true>(nqc, n, N, select, rr.keys.p, rr.pcnt.p, st));
     if (sort_dev) {   // sorted in LDS (k_pool_select), rows | distances | counts of the chunk back in one copy
         uint32_t p2 = 2;
         while (p2 < most) p2 <<= 1;
         const uint32_t ok = most;   // output stride of the chunk on the device: no query emitted more
         const size_t o_dist = (size_t)nqc * ok * 8, o_cnt = (size_t)nqc * ok * 12, o_all = o_cnt + (size_t)nqc * 4;
-        uint8_t* ob = reinterpret_cast<uint8_t*>(rr.d_out);
+        uint8_t* ob = reinterpret_cast<uint8_t*>(rr.out.p);
         PoolRerankArgs x{};
-        x.pool_cnt = rr.d_pcnt;
+        x.pool_cnt = rr.pcnt.p;
         x.pool_ld = N;
         x.p2 = p2;
         x.metric = metric;
         x.k = ok;
         x.out_k = ok;
-        x.out_rows = rr.d_out;
+        x.out_rows = rr.out.p;
         x.out_dists = reinterpret_cast<float*>(ob + o_dist);
         x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
-        x.keys_out = rr.d_keys;
+        x.keys_out = rr.keys.p;
         if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(nqc), dim3(1024), (size_t)p2 * 8, st, x);
         else hipLaunchKernelGGL(k_pool_select<256>, dim3(nqc), dim3(256), (size_t)p2 * 8, st, x);
         LY_HIP(hipGetLastError());
         LY_TRY(launched());
         h_out.resize((o_all + 7) / 8);
-        LY_HIP(hipMemcpyAsync(h_out.data(), rr.d_out, o_all, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(h_out.data(), rr.out.p, o_all, hipMemcpyDeviceToHost, st));
         LY_TRY(stream_wait(st));
         const uint8_t* hb = reinterpret_cast<const uint8_t*>(h_out.data());
         for (uint32_t i = 0; i < nqc; ++i) {   // (k_pool_select padded a shorter result up to `ok`)
@@ -97,7 +91,7 @@ static int range_cut_and_order(ScoreCut& cut, PoolRerank& rr, const uint32_t* d_
     } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host, as select_pool_keys does for large pools
         LY_TRY(launched());
         keys.resize((size_t)nqc * N);
-        LY_HIP(hipMemcpyAsync(keys.data(), rr.d_keys, keys.size() * 8, hipMemcpyDeviceToHost, st));
+        LY_HIP(hipMemcpyAsync(keys.data(), rr.keys.p, keys.size() * 8, hipMemcpyDeviceToHost, st));
         LY_TRY(stream_wait(st));
         for (uint32_t i = 0; i < nqc; ++i)
             select_pool_keys(keys.data() + (size_t)i * N, out_counts[i], N, out_k, asc, out_rows + (size_t)i * out_k, out_dists + (size_t)i * out_k);
@@ -192,26 +186,26 @@ extern "C" int lynse_hip_flat_search_range_f32(lynse_hip_flat* h, const float* q
     hipStream_t st = cur(h).stream;
     const uint64_t mask_words = bitset_words ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
     if (bitset_words) {
-        LY_TRY(ivf_grow(&p.d_mask, &p.mask_cap, (size_t)std::max<uint64_t>(1, mask_words)));
-        if (mask_words) LY_HIP(hipMemcpyAsync(p.d_mask, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+        LY_TRY(p.mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+        if (mask_words) LY_HIP(hipMemcpyAsync(p.mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
     }
-    if (binary) LY_TRY(ivf_grow(&p.d_qw, &p.qw_cap, (size_t)qc * W));
-    else LY_TRY(ivf_grow(&p.d_q, &p.q_cap, (size_t)qc * D));
-    LY_TRY(ivf_grow(&p.d_thr, &p.thr_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&p.d_cnt, &p.cnt_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&p.rr.d_keys, &p.rr.keys_cap, (size_t)qc * N));
-    LY_TRY(ivf_grow(&p.rr.d_pcnt, &p.rr.pcnt_cap, (size_t)qc));
-    if (sort_dev) LY_TRY(ivf_grow(&p.rr.d_out, &p.rr.out_cap, ((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
+    if (binary) LY_TRY(p.d_qw.reserve((size_t)qc * W));
+    else LY_TRY(p.q.reserve((size_t)qc * D));
+    LY_TRY(p.thr.reserve((size_t)qc));
+    LY_TRY(p.d_cnt.reserve((size_t)qc));
+    LY_TRY(p.rr.keys.reserve((size_t)qc * N));
+    LY_TRY(p.rr.pcnt.reserve((size_t)qc));
+    if (sort_dev) LY_TRY(p.rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
     LY_TRY(p.cut.grow(qc, n));
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-        LY_HIP(hipMemcpyAsync(p.d_thr, thresholds + q0, (size_t)nqc * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemsetAsync(p.d_cnt, 0, (size_t)nqc * 4, st));
+        LY_HIP(hipMemcpyAsync(p.thr.p, thresholds + q0, (size_t)nqc * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(p.d_cnt.p, 0, (size_t)nqc * 4, st));
         if (binary) {
             p.qw.resize((size_t)nqc * W);
             range_pack_queries(queries + q0 * D, nqc, D, W, p.qw.data());
-            LY_HIP(hipMemcpyAsync(p.d_qw, p.qw.data(), p.qw.size() * 8, hipMemcpyHostToDevice, st));
-            RangeBinArgs a{h->packed, W, n, p.d_qw, p.d_thr, nqc, bitset_words ? p.d_mask : nullptr, mask_words, p.cut.d_S, p.d_cnt};
+            LY_HIP(hipMemcpyAsync(p.d_qw.p, p.qw.data(), p.qw.size() * 8, hipMemcpyHostToDevice, st));
+            RangeBinArgs a{h->packed, W, n, p.d_qw.p, p.thr.p, nqc, bitset_words ? p.mask.p : nullptr, mask_words, p.cut.S.p, p.d_cnt.p};
             const dim3 grid((uint32_t)std::min<uint64_t>((n + 31) / 32, (uint64_t)h->num_cu * 8), (nqc + RANGE_MAX_Q - 1) / RANGE_MAX_Q);
             switch (metric) {
             case M_HAMMING: hipLaunchKernelGGL(k_range_scan_bin<0>, grid, dim3(RANGE_NT), 0, st, a); break;
@@ -219,15 +213,15 @@ extern "C" int lynse_hip_flat_search_range_f32(lynse_hip_flat* h, const float* q
             default: hipLaunchKernelGGL(k_range_scan_bin<1>, grid, dim3(RANGE_NT), 0, st, a); break;
             }
         } else {
-            LY_HIP(hipMemcpyAsync(p.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+            LY_HIP(hipMemcpyAsync(p.q.p, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
             const bool f16 = is_f16(h);
-            RangeScanArgs a{f16 ? (const void*)h->rows_h : (const void*)h->rows, f16 ? h->ld16 : h->ld, D, f16 ? 1 : 0, n, p.d_q, p.d_thr, nqc,
-                            metric, bitset_words ? p.d_mask : nullptr, mask_words, R, TQ, stride, p.cut.d_S, p.d_cnt};
+            RangeScanArgs a{f16 ? (const void*)h->rows_h : (const void*)h->rows, f16 ? h->ld16 : h->ld, D, f16 ? 1 : 0, n, p.q.p, p.thr.p, nqc,
+                            metric, bitset_words ? p.mask.p : nullptr, mask_words, R, TQ, stride, p.cut.S.p, p.d_cnt.p};
             const dim3 grid((uint32_t)std::min<uint64_t>((n + R - 1) / R, (uint64_t)h->num_cu * 4), (nqc + TQ - 1) / TQ);
             hipLaunchKernelGGL(k_range_scan, grid, dim3(RANGE_NT), lds, st, a);
         }
         LY_HIP(hipGetLastError());
-        LY_TRY(range_cut_and_order(p.cut, p.rr, p.d_cnt, p.cnt, p.keys, p.h_out, nqc, n, N, max_results, metric, st, out_rows + q0 * max_results,
+        LY_TRY(range_cut_and_order(p.cut, p.rr, p.d_cnt.p, p.cnt, p.keys, p.h_out, nqc, n, N, max_results, metric, st, out_rows + q0 * max_results,
                                    out_dists + q0 * max_results, out_counts + q0, out_passed ? out_passed + q0 : nullptr, []() { return (int)LYNSE_OK; }));
     }
     return LYNSE_OK;

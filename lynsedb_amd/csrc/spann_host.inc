@@ -23,51 +23,45 @@ static int spann_postings(lynse_hip_flat* cs, const float* d_rows, uint64_t n, u
     }
     constexpr uint64_t B = 65536;   // rows per FLAT search of the top-keep
     const uint64_t nb = std::min<uint64_t>(B, n);
-    uint8_t* d_flag = nullptr;
-    uint32_t *d_lists = nullptr, *d_cnt = nullptr, *d_slow = nullptr, *d_nslow = nullptr, *d_tc = nullptr;
-    uint64_t* d_tr = nullptr;
-    float* d_td = nullptr;
-    struct G { std::vector<void*> b; ~G() { for (void* p : b) if (p) (void)hipFree(p); } } g;
-    auto alloc = [&](auto** p, size_t bytes) -> int {
-        LY_HIP(hipMalloc(p, std::max<size_t>(bytes, 4)));
-        g.b.push_back((void*)*p);
-        return LYNSE_OK;
-    };
-    LY_TRY(alloc(&d_flag, n));
-    LY_TRY(alloc(&d_lists, (size_t)n * keep * 4));
-    LY_TRY(alloc(&d_cnt, (size_t)n * 4));
-    LY_TRY(alloc(&d_slow, (size_t)n * 4));
-    LY_TRY(alloc(&d_nslow, 4));
-    LY_TRY(alloc(&d_tr, (size_t)nb * keep * 8));
-    LY_TRY(alloc(&d_td, (size_t)nb * keep * 4));
-    LY_TRY(alloc(&d_tc, (size_t)nb * 4));
-    LY_TRY(memset_done(d_nslow, 0, 4));
+    DevBuf<uint8_t> d_flag;
+    DevBuf<uint32_t> d_lists, d_cnt, d_slow, d_nslow, d_tc;
+    DevBuf<uint64_t> d_tr;
+    DevBuf<float> d_td;
+    LY_TRY(d_flag.alloc(n));
+    LY_TRY(d_lists.alloc((size_t)n * keep));
+    LY_TRY(d_cnt.alloc((size_t)n));
+    LY_TRY(d_slow.alloc((size_t)n));
+    LY_TRY(d_nslow.alloc(1));
+    LY_TRY(d_tr.alloc((size_t)nb * keep));
+    LY_TRY(d_td.alloc((size_t)nb * keep));
+    LY_TRY(d_tc.alloc((size_t)nb));
+    LY_TRY(memset_done(d_nslow.p, 0, 4));
     hipLaunchKernelGGL(k_spann_flag, dim3((uint32_t)std::min<uint64_t>((n + 3) / 4, 8192)), dim3(256), 0, 0, d_rows, dim, dim, n, cmax, metric,
-                       cbad, d_flag);
+                       cbad, d_flag.p);
     LY_HIP(hipGetLastError());
     LY_HIP(hipStreamSynchronize(nullptr));
     for (uint64_t r0 = 0; r0 < n; r0 += B) {
         const uint64_t nr = std::min<uint64_t>(B, n - r0);
         // the canonical (rank, centroid) top-keep: the exact FLAT search of the rows against the centroid store
-        LY_TRY(lynse_hip_flat_search_f32_device(cs, d_rows + (size_t)r0 * dim, nr, keep, metric, d_tr, d_td, d_tc, nullptr));
-        SpannPostArgs a{d_tr, d_td, d_tc, d_flag, nr, r0, keep, R, metric, d_lists, d_cnt, d_slow, d_nslow};
+        LY_TRY(lynse_hip_flat_search_f32_device(cs, d_rows + (size_t)r0 * dim, nr, keep, metric, d_tr.p, d_td.p, d_tc.p, nullptr));
+        SpannPostArgs a{d_tr.p, d_td.p, d_tc.p, d_flag.p, nr, r0, keep, R, metric, d_lists.p, d_cnt.p, d_slow.p, d_nslow.p};
         hipLaunchKernelGGL(k_spann_postings, dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, 0, a);
         LY_HIP(hipGetLastError());
         LY_HIP(hipStreamSynchronize(nullptr));
     }
     uint32_t n_slow = 0;
-    LY_HIP(hipMemcpy(&n_slow, d_nslow, 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(&n_slow, d_nslow.p, 4, hipMemcpyDeviceToHost));
     if (n_slow) {   // rows that can meet a NaN / infinite rank: the sequential rule over every centroid
         const size_t lds = (size_t)nlist * 4 + (size_t)keep * 8;
         LY_TRY(ensure_lds<k_spann_slow>(16384 * 4 + SPANN_MAX_KEEP * 8));
-        hipLaunchKernelGGL(k_spann_slow, dim3(n_slow), dim3(256), lds, 0, d_rows, dim, cs->rows, cs->ld, dim, nlist, keep, R, metric, d_slow,
-                           d_lists, d_cnt);
+        hipLaunchKernelGGL(k_spann_slow, dim3(n_slow), dim3(256), lds, 0, d_rows, dim, cs->rows, cs->ld, dim, nlist, keep, R, metric, d_slow.p,
+                           d_lists.p, d_cnt.p);
         LY_HIP(hipGetLastError());
         LY_HIP(hipStreamSynchronize(nullptr));
     }
     std::vector<uint32_t> cnt(n), all((size_t)n * keep);
-    LY_HIP(hipMemcpy(cnt.data(), d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost));
-    LY_HIP(hipMemcpy(all.data(), d_lists, (size_t)n * keep * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(cnt.data(), d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    LY_HIP(hipMemcpy(all.data(), d_lists.p, (size_t)n * keep * 4, hipMemcpyDeviceToHost));
     for (uint64_t r = 0; r < n; ++r) {
         if (cnt[r] == 0 || cnt[r] > keep) return set_error(LYNSE_ERR_INTERNAL, "SPANN posting count out of range");
         (*row_off)[r + 1] = (*row_off)[r] + cnt[r];
@@ -107,22 +101,21 @@ static int spann_common(const float* rows, uint64_t n, uint32_t dim, uint32_t nl
                         int sq8, const float* mins_in, const float* scales_in, const float* centroids, const uint64_t* list_off,
                         const uint32_t* list_rows, int device, lynse_hip_ivf** out) {
     LY_TRY(spann_check(n, dim, metric, R));
-    float *d_raw = nullptr, *d_dec = nullptr, *d_sq = nullptr;
-    struct G { float*& a; float*& b; float*& c; ~G() { for (float* p : {a, b, c}) if (p) (void)hipFree(p); } } g{d_raw, d_dec, d_sq};
+    DevBuf<float> d_raw, d_dec, d_sq;
     std::vector<float> mins, scales, cen;
     std::vector<uint32_t> asg;
     if (sq8) {
-        LY_TRY(sq_prepare(rows, n, dim, mins_in, scales_in, device, &d_raw, &d_dec, &d_sq, &mins, &scales));
+        LY_TRY(sq_prepare(rows, n, dim, mins_in, scales_in, device, d_raw, d_dec, d_sq, &mins, &scales));
     } else {
         LY_HIP(hipSetDevice(device));
-        LY_HIP(hipMalloc(&d_dec, (size_t)n * dim * 4));
-        LY_TRY(h2d_done(d_dec, rows, (size_t)n * dim * 4));
+        LY_TRY(d_dec.alloc((size_t)n * dim));
+        LY_TRY(h2d_done(d_dec.p, rows, (size_t)n * dim * 4));
     }
     std::vector<uint64_t> row_off;
     std::vector<uint32_t> lists;
     if (!centroids) {   // train_for_metric(decoded, n, dim, n_clusters, 20, metric) (spann.rs:291-298)
         uint32_t k = 0;
-        LY_TRY(ivf_kmeans(d_dec, n, dim, nlist, max_iter, metric, device, &cen, &asg, &k, true));
+        LY_TRY(ivf_kmeans(d_dec.p, n, dim, nlist, max_iter, metric, device, &cen, &asg, &k, true));
         if (k == 0) return set_error(LYNSE_ERR_INDEX_NOT_BUILT, "no vectors to index");
         nlist = k;
         centroids = cen.data();
@@ -160,11 +153,11 @@ static int spann_common(const float* rows, uint64_t n, uint32_t dim, uint32_t nl
     } else {   // the posting rule against the final centroids (spann.rs:304-306)
         lynse_hip_flat* cs = nullptr;
         LY_TRY(spann_centroid_store(centroids, nlist, dim, device, &cs));
-        const int rc = spann_postings(cs, d_dec, n, dim, centroids, nlist, metric, R, &row_off, &lists);
+        const int rc = spann_postings(cs, d_dec.p, n, dim, centroids, nlist, metric, R, &row_off, &lists);
         lynse_hip_flat_destroy(cs);
         LY_TRY(rc);
     }
-    LY_TRY(ivf_assemble(d_dec, n, dim, centroids, nlist, lists.data(), metric, 0, device, out, true, nullptr, row_off.data()));
+    LY_TRY(ivf_assemble(d_dec.p, n, dim, centroids, nlist, lists.data(), metric, 0, device, out, true, nullptr, row_off.data()));
     lynse_hip_ivf* h = *out;
     h->spann = true;
     h->replicas = R;
@@ -176,8 +169,8 @@ static int spann_common(const float* rows, uint64_t n, uint32_t dim, uint32_t nl
         h->sq8 = true;
         h->sq_min = std::move(mins);
         h->sq_scale = std::move(scales);
-        std::swap(h->d_sq, d_sq);
-        std::swap(h->d_raw, d_raw);
+        h->d_sq = std::move(d_sq);
+        h->d_raw = std::move(d_raw);
     }
     return LYNSE_OK;
 }
@@ -226,13 +219,12 @@ static int spann_rows_in_order(lynse_hip_ivf* h, const std::vector<uint32_t>& ro
         pos[i] = first[rows[i]];
         if (pos[i] == 0xffffffffu) return set_error(LYNSE_ERR_INTERNAL, "a SPANN row sits in no list");
     }
-    uint32_t* d_pos = nullptr;
-    struct G { uint32_t*& p; ~G() { if (p) (void)hipFree(p); } } g{d_pos};
-    LY_HIP(hipMalloc(&d_pos, pos.size() * 4));
-    LY_TRY(h2d_done(d_pos, pos.data(), pos.size() * 4));
+    DevBuf<uint32_t> d_pos;
+    LY_TRY(d_pos.alloc(pos.size()));
+    LY_TRY(h2d_done(d_pos.p, pos.data(), pos.size() * 4));
     const uint64_t pieces = (uint64_t)pos.size() * ((h->dim + 3) / 4);
     hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0,
-                       h->store->rows, h->store->ld, d_pos, (uint64_t)pos.size(), d_out, h->dim, h->dim);
+                       h->store->rows, h->store->ld, d_pos.p, (uint64_t)pos.size(), d_out, h->dim, h->dim);
     LY_HIP(hipGetLastError());
     LY_HIP(hipStreamSynchronize(nullptr));
     return LYNSE_OK;
@@ -240,7 +232,7 @@ static int spann_rows_in_order(lynse_hip_ivf* h, const std::vector<uint32_t>& ro
 
 // re-assemble over n rows in HBM (original row order) with their lists, and hand the index over (new_raw: ivf_adopt)
 static int spann_reassemble(lynse_hip_ivf* h, const float* d_rows, uint64_t n, const std::vector<uint64_t>& row_off,
-                            const std::vector<uint32_t>& lists, float* new_raw) {
+                            const std::vector<uint32_t>& lists, DevBuf<float>* new_raw) {
     lynse_hip_ivf* fresh = nullptr;
     LY_TRY(ivf_assemble(d_rows, n, h->dim, h->centroids.data(), h->nlist, lists.data(), h->metric, 0, h->store->device, &fresh, true, nullptr,
                         row_off.data()));
@@ -255,20 +247,19 @@ static int spann_insert(lynse_hip_ivf* h, const float* rows, uint64_t n) {
     const uint32_t D = h->dim;
     if (total * (h->replicas + 1) > 0xfffffff0ull) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "SPANN posting count exceeds the u32 position capacity");
     LY_HIP(hipSetDevice(h->store->device));
-    float *d_all = nullptr, *d_new = nullptr, *new_raw = nullptr;
-    struct G { float*& a; float*& b; float*& c; ~G() { for (float* p : {a, b, c}) if (p) (void)hipFree(p); } } g{d_all, d_new, new_raw};
-    LY_HIP(hipMalloc(&d_all, (size_t)total * D * 4));
+    DevBuf<float> d_all, d_new, new_raw;
+    LY_TRY(d_all.alloc((size_t)total * D));
     const float* d_routed = nullptr;   // the new rows as the index sees them (decoded under SQ8)
     if (h->sq8) {
         LY_TRY(sq_decode_host(h, rows, n, nullptr, &d_new));   // (d_new: originals, then the decoded rows; no host copy)
-        d_routed = d_new + (size_t)n * D;
-        LY_HIP(hipMalloc(&new_raw, (size_t)total * D * 4));
-        if (old_n) LY_HIP(hipMemcpy(new_raw, h->d_raw, (size_t)old_n * D * 4, hipMemcpyDeviceToDevice));
-        LY_HIP(hipMemcpy(new_raw + (size_t)old_n * D, d_new, (size_t)n * D * 4, hipMemcpyDeviceToDevice));
+        d_routed = d_new.p + (size_t)n * D;
+        LY_TRY(new_raw.alloc((size_t)total * D));
+        if (old_n) LY_HIP(hipMemcpy(new_raw.p, h->d_raw.p, (size_t)old_n * D * 4, hipMemcpyDeviceToDevice));
+        LY_HIP(hipMemcpy(new_raw.p + (size_t)old_n * D, d_new.p, (size_t)n * D * 4, hipMemcpyDeviceToDevice));
     } else {
-        LY_HIP(hipMalloc(&d_new, (size_t)n * D * 4));
-        LY_TRY(h2d_done(d_new, rows, (size_t)n * D * 4));
-        d_routed = d_new;
+        LY_TRY(d_new.alloc((size_t)n * D));
+        LY_TRY(h2d_done(d_new.p, rows, (size_t)n * D * 4));
+        d_routed = d_new.p;
     }
     std::vector<uint64_t> new_off;
     std::vector<uint32_t> new_lists;
@@ -287,11 +278,9 @@ static int spann_insert(lynse_hip_ivf* h, const float* rows, uint64_t n) {
     std::copy(new_lists.begin(), new_lists.end(), lists.begin() + row_off[old_n]);
     std::vector<uint32_t> old_rows(old_n);
     for (uint64_t r = 0; r < old_n; ++r) old_rows[r] = (uint32_t)r;
-    LY_TRY(spann_rows_in_order(h, old_rows, d_all));
-    LY_HIP(hipMemcpy(d_all + (size_t)old_n * D, d_routed, (size_t)n * D * 4, hipMemcpyDeviceToDevice));
-    LY_TRY(spann_reassemble(h, d_all, total, row_off, lists, new_raw));
-    new_raw = nullptr;   // (owned by the index now)
-    return LYNSE_OK;
+    LY_TRY(spann_rows_in_order(h, old_rows, d_all.p));
+    LY_HIP(hipMemcpy(d_all.p + (size_t)old_n * D, d_routed, (size_t)n * D * 4, hipMemcpyDeviceToDevice));
+    return spann_reassemble(h, d_all.p, total, row_off, lists, &new_raw);   // (on success the index owns new_raw)
 }
 
 // SPANNIndex::delete (spann.rs:435-457): the rows go, the rest keep their order under consecutive row ids, and ALL lists are
@@ -308,33 +297,30 @@ static int spann_delete(lynse_hip_ivf* h, const uint64_t* row_ids, uint64_t n_id
         if (!gone[r]) keep.push_back((uint32_t)r);
     const uint64_t m = keep.size();
     LY_HIP(hipSetDevice(h->store->device));
-    float *d_all = nullptr, *new_raw = nullptr;
-    uint32_t* d_keep = nullptr;
-    struct G { float*& a; float*& b; uint32_t*& c; ~G() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } g{d_all, new_raw, d_keep};
-    LY_HIP(hipMalloc(&d_all, std::max<size_t>((size_t)m * D * 4, 4)));
-    LY_TRY(spann_rows_in_order(h, keep, d_all));
+    DevBuf<float> d_all, new_raw;
+    DevBuf<uint32_t> d_keep;
+    LY_TRY(d_all.alloc((size_t)m * D));
+    LY_TRY(spann_rows_in_order(h, keep, d_all.p));
     if (h->sq8) {   // the original rows that are kept, in order
-        LY_HIP(hipMalloc(&new_raw, std::max<size_t>((size_t)m * D * 4, 4)));
+        LY_TRY(new_raw.alloc((size_t)m * D));
         if (m) {
-            LY_HIP(hipMalloc(&d_keep, (size_t)m * 4));
-            LY_TRY(h2d_done(d_keep, keep.data(), (size_t)m * 4));
+            LY_TRY(d_keep.alloc((size_t)m));
+            LY_TRY(h2d_done(d_keep.p, keep.data(), (size_t)m * 4));
             const uint64_t pieces = m * ((D + 3) / 4);
             hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0,
-                               h->d_raw, D, d_keep, m, new_raw, D, D);
+                               h->d_raw.p, D, d_keep.p, m, new_raw.p, D, D);
             LY_HIP(hipGetLastError());
             LY_HIP(hipStreamSynchronize(nullptr));
         }
     }
     std::vector<uint64_t> row_off;
     std::vector<uint32_t> lists;
-    LY_TRY(spann_postings(h->cstore, d_all, m, D, h->centroids.data(), h->nlist, h->metric, h->replicas, &row_off, &lists));
-    LY_TRY(spann_reassemble(h, d_all, m, row_off, lists, new_raw));
-    new_raw = nullptr;
-    return LYNSE_OK;
+    LY_TRY(spann_postings(h->cstore, d_all.p, m, D, h->centroids.data(), h->nlist, h->metric, h->replicas, &row_off, &lists));
+    return spann_reassemble(h, d_all.p, m, row_off, lists, &new_raw);
 }
 
 // ------------------------------------------------------------------------------------------ search ----
-// The k_spann_unique launch on the slab store's stream, the store lock held: `nq` queries of `in_k` keys in sp.d_rows / d_dists / d_cnt
+// The k_spann_unique launch on the slab store's stream, the store lock held: `nq` queries of `in_k` keys in sp.rows.p / d_dists / d_cnt
 // -> the first k_sel distinct rows of output query qmap[q] at stride out_k.
 static int spann_unique(lynse_hip_ivf* h, uint32_t nq, uint32_t in_k, uint32_t k_sel, const uint32_t* d_qmap, uint64_t* d_orow, float* d_odist,
                         uint32_t* d_ocnt, uint32_t out_k) {
@@ -342,7 +328,7 @@ static int spann_unique(lynse_hip_ivf* h, uint32_t nq, uint32_t in_k, uint32_t k
     std::unique_lock<std::shared_mutex> lk(s->rw);
     LY_TRY(use_device(s));
     hipStream_t st = cur(s).stream;
-    hipLaunchKernelGGL(k_spann_unique, dim3(nq), dim3(64), 0, st, h->sp.d_rows, d_odist ? h->sp.d_dists : nullptr, h->sp.d_cnt, in_k, nq, k_sel,
+    hipLaunchKernelGGL(k_spann_unique, dim3(nq), dim3(64), 0, st, h->sp.rows.p, d_odist ? h->sp.dists.p : nullptr, h->sp.cnt.p, in_k, nq, k_sel,
                        d_qmap, d_orow, d_odist, d_ocnt, out_k, metric_ascending(h->metric) ? 1 : 0);
     LY_HIP(hipGetLastError());
     LY_HIP(hipStreamSynchronize(st));
@@ -356,7 +342,7 @@ static int spann_chunk(lynse_hip_ivf* h, const float* d_q, uint32_t nqc, uint32_
     auto& sp = h->sp;
     const uint64_t kp = (uint64_t)k_sel * (h->replicas + 1);
     const uint32_t D = h->dim;
-    LY_TRY(ivf_search_locked(h, d_q, nqc, (uint32_t)kp, nprobe, sp.d_rows, sp.d_dists, sp.d_cnt, filtered, subset, n_subset, -1, true));
+    LY_TRY(ivf_search_locked(h, d_q, nqc, (uint32_t)kp, nprobe, sp.rows.p, sp.dists.p, sp.cnt.p, filtered, subset, n_subset, -1, true));
     LY_TRY(spann_unique(h, nqc, (uint32_t)kp, k_sel, nullptr, d_orow, d_odist, d_ocnt, out_k));
     const uint32_t np_eff = std::min<uint32_t>(std::max<uint32_t>(nprobe, 1), h->nlist);
     if (np_eff >= h->nlist) return LYNSE_OK;   // (every list probed already: nothing more to find)
@@ -366,15 +352,15 @@ static int spann_chunk(lynse_hip_ivf* h, const float* d_q, uint32_t nqc, uint32_
         if (cnt[i] < k_min) redo.push_back(i);
     if (redo.empty()) return LYNSE_OK;
     // fewer than k distinct candidates (spann.rs:376-379): the candidates become all (subset) rows = every list probed
-    float* d_rq = sp.d_q + (size_t)nqc * D;   // (the second half of the query buffer)
-    LY_HIP(hipMemcpy(sp.d_qmap, redo.data(), redo.size() * 4, hipMemcpyHostToDevice));
+    float* d_rq = sp.q.p + (size_t)nqc * D;   // (the second half of the query buffer)
+    LY_HIP(hipMemcpy(sp.qmap.p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice));
     const uint64_t pieces = (uint64_t)redo.size() * ((D + 3) / 4);
-    hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0, d_q, D, sp.d_qmap,
+    hipLaunchKernelGGL(k_gather_rows_f32, dim3((uint32_t)std::min<uint64_t>((pieces + 255) / 256, 8192)), dim3(256), 0, 0, d_q, D, sp.qmap.p,
                        (uint64_t)redo.size(), d_rq, D, D);
     LY_HIP(hipGetLastError());
     LY_HIP(hipStreamSynchronize(nullptr));
-    LY_TRY(ivf_search_locked(h, d_rq, (uint32_t)redo.size(), (uint32_t)kp, h->nlist, sp.d_rows, sp.d_dists, sp.d_cnt, filtered, subset, n_subset, -1, true));
-    return spann_unique(h, (uint32_t)redo.size(), (uint32_t)kp, k_sel, sp.d_qmap, d_orow, d_odist, d_ocnt, out_k);
+    LY_TRY(ivf_search_locked(h, d_rq, (uint32_t)redo.size(), (uint32_t)kp, h->nlist, sp.rows.p, sp.dists.p, sp.cnt.p, filtered, subset, n_subset, -1, true));
+    return spann_unique(h, (uint32_t)redo.size(), (uint32_t)kp, k_sel, sp.qmap.p, d_orow, d_odist, d_ocnt, out_k);
 }
 
 // SPANNIndex::search (spann.rs:326-433), the index guard held.  Plain modes: the top k distinct rows by (distance, row).  SQ8: the
@@ -403,30 +389,30 @@ static int spann_search(lynse_hip_ivf* h, const float* queries, uint64_t nq, uin
     const uint64_t qc = std::max<uint64_t>(1, std::min<uint64_t>(QCHUNK, (256ull << 20) / (kp * 16)));
     auto& sp = h->sp;
     LY_HIP(hipSetDevice(s->device));
-    LY_TRY(ivf_grow(&sp.d_q, &sp.q_cap, (size_t)qc * D * 2));
-    LY_TRY(ivf_grow(&sp.d_rows, &sp.rows_cap, (size_t)qc * kp));
-    LY_TRY(ivf_grow(&sp.d_dists, &sp.dists_cap, (size_t)qc * kp));
-    LY_TRY(ivf_grow(&sp.d_cnt, &sp.cnt_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&sp.d_qmap, &sp.qmap_cap, (size_t)qc));
+    LY_TRY(sp.q.reserve((size_t)qc * D * 2));
+    LY_TRY(sp.rows.reserve((size_t)qc * kp));
+    LY_TRY(sp.dists.reserve((size_t)qc * kp));
+    LY_TRY(sp.cnt.reserve((size_t)qc));
+    LY_TRY(sp.qmap.reserve((size_t)qc));
     if (!h->sq8) {
-        LY_TRY(ivf_grow(&sp.d_orow, &sp.orow_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&sp.d_odist, &sp.odist_cap, (size_t)qc * k));
-        LY_TRY(ivf_grow(&sp.d_ocnt, &sp.ocnt_cap, (size_t)qc));
+        LY_TRY(sp.orow.reserve((size_t)qc * k));
+        LY_TRY(sp.odist.reserve((size_t)qc * k));
+        LY_TRY(sp.ocnt.reserve((size_t)qc));
         for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
             const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
-            LY_TRY(h2d_done(sp.d_q, queries + q0 * D, (size_t)nqc * D * 4));
-            LY_TRY(spann_chunk(h, sp.d_q, nqc, k_sel, k_sel, nprobe, filtered, subset, n_subset, sp.d_orow, sp.d_odist, sp.d_ocnt, k));
-            LY_HIP(hipMemcpy(out_rows + q0 * k, sp.d_orow, (size_t)nqc * k * 8, hipMemcpyDeviceToHost));
-            LY_HIP(hipMemcpy(out_dists + q0 * k, sp.d_odist, (size_t)nqc * k * 4, hipMemcpyDeviceToHost));
-            LY_HIP(hipMemcpy(out_counts + q0, sp.d_ocnt, (size_t)nqc * 4, hipMemcpyDeviceToHost));
+            LY_TRY(h2d_done(sp.q.p, queries + q0 * D, (size_t)nqc * D * 4));
+            LY_TRY(spann_chunk(h, sp.q.p, nqc, k_sel, k_sel, nprobe, filtered, subset, n_subset, sp.orow.p, sp.odist.p, sp.ocnt.p, k));
+            LY_HIP(hipMemcpy(out_rows + q0 * k, sp.orow.p, (size_t)nqc * k * 8, hipMemcpyDeviceToHost));
+            LY_HIP(hipMemcpy(out_dists + q0 * k, sp.odist.p, (size_t)nqc * k * 4, hipMemcpyDeviceToHost));
+            LY_HIP(hipMemcpy(out_counts + q0, sp.ocnt.p, (size_t)nqc * 4, hipMemcpyDeviceToHost));
         }
         return LYNSE_OK;
     }
-    // SQ8: the pool stage leaves the distinct pool rows in PoolRerank's d_prow / d_pcnt
+    // SQ8: the pool stage leaves the distinct pool rows in PoolRerank's prow / pcnt
     auto& sc = h->sq;
     PoolRerank::Search rr(sc.rr);
-    LY_TRY(rr.begin(h->d_raw, n, D, D, h->metric, k_sel, k, k, qc, false, s->profiling.load(), "SPANN-*-SQ8 rerank"));
-    LY_TRY(ivf_grow(&sc.d_q, &sc.q_cap, (size_t)qc * D));
+    LY_TRY(rr.begin(h->d_raw.p, n, D, D, h->metric, k_sel, k, k, qc, false, s->profiling.load(), "SPANN-*-SQ8 rerank"));
+    LY_TRY(sc.q.reserve((size_t)qc * D));
     const uint32_t k_min = (uint32_t)std::min<uint64_t>(k, n);
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
         const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
@@ -434,16 +420,16 @@ static int spann_search(lynse_hip_ivf* h, const float* queries, uint64_t nq, uin
             std::unique_lock<std::shared_mutex> lk(s->rw);
             LY_TRY(use_device(s));
             hipStream_t st = cur(s).stream;
-            LY_HIP(hipMemcpyAsync(sc.d_q, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
-            LY_TRY(sq_codec_device(sc.d_q, nqc, D, h->d_sq, sp.d_q, st));
+            LY_HIP(hipMemcpyAsync(sc.q.p, queries + q0 * D, (size_t)nqc * D * 4, hipMemcpyHostToDevice, st));
+            LY_TRY(sq_codec_device(sc.q.p, nqc, D, h->d_sq.p, sp.q.p, st));
             LY_TRY(rr.pool_start(st));
             LY_HIP(hipStreamSynchronize(st));
         }
         // (the pool keeps no distances: k_spann_unique writes rows and counts only)
-        LY_TRY(spann_chunk(h, sp.d_q, nqc, k_sel, k_min, nprobe, filtered, subset, n_subset, sc.rr.d_prow, nullptr, sc.rr.d_pcnt, k_sel));
+        LY_TRY(spann_chunk(h, sp.q.p, nqc, k_sel, k_min, nprobe, filtered, subset, n_subset, sc.rr.prow.p, nullptr, sc.rr.pcnt.p, k_sel));
         std::unique_lock<std::shared_mutex> lk(s->rw);
         LY_TRY(use_device(s));
-        LY_TRY(rr.run(sc.d_q, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, s->profiling.load() ? cur(s).ws.pool_total : nullptr,
+        LY_TRY(rr.run(sc.q.p, nqc, out_rows + q0 * k, out_dists + q0 * k, out_counts + q0, s->profiling.load() ? cur(s).ws.pool_total : nullptr,
                       cur(s).stream));
     }
     if (rr.timed) { h->sq_searches += 1; h->sq_pool_us += rr.pool_us; h->sq_rerank_us += rr.rerank_us; }

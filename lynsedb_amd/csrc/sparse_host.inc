@@ -9,14 +9,12 @@ struct lynse_hip_sparse {
     uint32_t num_cu = 256;
     hipStream_t stream = nullptr;
     uint64_t n = 0, nnz = 0;
-    uint64_t* d_indptr = nullptr;   // structure of arrays: the index stream is read without the values
-    uint32_t* d_indices = nullptr;
-    float* d_values = nullptr;
-    size_t indptr_cap = 0, indices_cap = 0, values_cap = 0;
+    DevBuf<uint64_t> indptr;   // structure of arrays: the index stream is read without the values
+    DevBuf<uint32_t> indices;
+    DevBuf<float> values;
     // the scratch of a search (it runs under the exclusive lock)
-    uint32_t *d_tab = nullptr, *d_cnt = nullptr;
-    uint64_t* d_mask = nullptr;
-    size_t tab_cap = 0, cnt_cap = 0, mask_cap = 0;
+    DevBuf<uint32_t> d_tab, d_cnt;   // (tab and cnt are their host images below)
+    DevBuf<uint64_t> mask;
     ScoreCut cut;
     PoolRerank rr;
     std::vector<uint32_t> cnt, tab, uni;
@@ -103,9 +101,6 @@ extern "C" int lynse_hip_sparse_destroy(lynse_hip_sparse* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_indptr, (void*)h->d_indices, (void*)h->d_values, (void*)h->d_tab, (void*)h->d_cnt, (void*)h->d_mask})
-        if (p) (void)hipFree(p);
-    h->cut.release();
     h->rr.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -127,13 +122,13 @@ extern "C" int lynse_hip_sparse_set_rows(lynse_hip_sparse* h, const uint64_t* in
     }
     const uint64_t nnz = indptr[n];
     h->n = h->nnz = 0;   // (a failed upload leaves an empty store, not a torn one)
-    LY_TRY(ivf_grow(&h->d_indptr, &h->indptr_cap, (size_t)n + 1));
-    LY_TRY(ivf_grow(&h->d_indices, &h->indices_cap, (size_t)std::max<uint64_t>(1, nnz)));
-    LY_TRY(ivf_grow(&h->d_values, &h->values_cap, (size_t)std::max<uint64_t>(1, nnz)));
-    LY_TRY(h2d_done(h->d_indptr, indptr, ((size_t)n + 1) * 8));
+    LY_TRY(h->indptr.reserve((size_t)n + 1));
+    LY_TRY(h->indices.reserve((size_t)std::max<uint64_t>(1, nnz)));
+    LY_TRY(h->values.reserve((size_t)std::max<uint64_t>(1, nnz)));
+    LY_TRY(h2d_done(h->indptr.p, indptr, ((size_t)n + 1) * 8));
     if (nnz) {
-        LY_TRY(h2d_done(h->d_indices, indices, (size_t)nnz * 4));
-        LY_TRY(h2d_done(h->d_values, values, (size_t)nnz * 4));
+        LY_TRY(h2d_done(h->indices.p, indices, (size_t)nnz * 4));
+        LY_TRY(h2d_done(h->values.p, values, (size_t)nnz * 4));
     }
     h->n = n;
     h->nnz = nnz;
@@ -151,7 +146,7 @@ extern "C" int lynse_hip_sparse_len(lynse_hip_sparse* h, uint64_t* out_rows, uin
 extern "C" uint64_t lynse_hip_sparse_hbm_bytes(lynse_hip_sparse* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> lk(h->rw);
-    return (uint64_t)h->indptr_cap * 8 + (uint64_t)h->indices_cap * 4 + (uint64_t)h->values_cap * 4;
+    return (uint64_t)h->indptr.cap * 8 + (uint64_t)h->indices.cap * 4 + (uint64_t)h->values.cap * 4;
 }
 
 extern "C" int lynse_hip_sparse_profile_enable(lynse_hip_sparse* h, int on) {
@@ -269,14 +264,14 @@ extern "C" int lynse_hip_sparse_search(lynse_hip_sparse* h, const uint64_t* q_in
     }
     hipStream_t st = h->stream;
     const uint64_t mask_words = bitset_words ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
-    if (bitset_words) LY_TRY(ivf_grow(&h->d_mask, &h->mask_cap, (size_t)std::max<uint64_t>(1, mask_words)));
-    LY_TRY(ivf_grow(&h->d_cnt, &h->cnt_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&h->rr.d_keys, &h->rr.keys_cap, (size_t)qc * N));
-    LY_TRY(ivf_grow(&h->rr.d_pcnt, &h->rr.pcnt_cap, (size_t)qc));
-    if (sort_dev) LY_TRY(ivf_grow(&h->rr.d_out, &h->rr.out_cap, ((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
+    if (bitset_words) LY_TRY(h->mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+    LY_TRY(h->d_cnt.reserve((size_t)qc));
+    LY_TRY(h->rr.keys.reserve((size_t)qc * N));
+    LY_TRY(h->rr.pcnt.reserve((size_t)qc));
+    if (sort_dev) LY_TRY(h->rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
     LY_TRY(h->cut.grow(qc, n));
     // (the caller's words are queued only once nothing before the first launch can fail and return with the copy still pending)
-    if (mask_words) LY_HIP(hipMemcpyAsync(h->d_mask, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+    if (mask_words) LY_HIP(hipMemcpyAsync(h->mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
     const bool timed = h->profiling;
     if (timed) {
         for (hipEvent_t& e : h->ev)
@@ -303,23 +298,23 @@ extern "C" int lynse_hip_sparse_search(lynse_hip_sparse* h, const uint64_t* q_in
         h->keys.resize((size_t)nqc + 1);
         for (uint32_t i = 0; i <= nqc; ++i) h->keys[i] = q_indptr[q0 + i] - e0;
         int rc = sparse_plan(h, h->keys.data(), q_indices + e0, q_values + e0, nqc, &a, &lds);
-        if (rc == LYNSE_OK) rc = ivf_grow(&h->d_tab, &h->tab_cap, h->tab.size());
+        if (rc == LYNSE_OK) rc = h->d_tab.reserve(h->tab.size());
         if (rc != LYNSE_OK) {   // (the copy of the caller's mask words may still be queued: it must not outlive the call)
             (void)hipStreamSynchronize(st);
             return rc;
         }
-        LY_HIP(hipMemcpyAsync(h->d_tab, h->tab.data(), h->tab.size() * 4, hipMemcpyHostToDevice, st));
-        LY_HIP(hipMemsetAsync(h->d_cnt, 0, (size_t)nqc * 4, st));
-        a.indptr = h->d_indptr;
-        a.indices = h->d_indices;
-        a.values = h->d_values;
+        LY_HIP(hipMemcpyAsync(h->d_tab.p, h->tab.data(), h->tab.size() * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemsetAsync(h->d_cnt.p, 0, (size_t)nqc * 4, st));
+        a.indptr = h->indptr.p;
+        a.indices = h->indices.p;
+        a.values = h->values.p;
         a.n = n;
-        a.tables = h->d_tab;
+        a.tables = h->d_tab.p;
         a.nq = nqc;
-        a.mask = bitset_words ? h->d_mask : nullptr;
+        a.mask = bitset_words ? h->mask.p : nullptr;
         a.mask_words = mask_words;
-        a.S = h->cut.d_S;
-        a.count = h->d_cnt;
+        a.S = h->cut.S.p;
+        a.count = h->d_cnt.p;
         const uint32_t qtiles = (nqc + a.TQ - 1) / a.TQ;
         const dim3 grid((uint32_t)std::min<uint64_t>((n + SPARSE_ROWS - 1) / SPARSE_ROWS, (uint64_t)h->num_cu * 4), qtiles);
         if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
@@ -331,7 +326,7 @@ extern "C" int lynse_hip_sparse_search(lynse_hip_sparse* h, const uint64_t* q_in
             h->prof.scan_rows += n * qtiles;
             h->prof.scan_bytes += (h->nnz * 8 + (n + 1) * 8) * qtiles;
         }
-        LY_TRY(range_cut_and_order(h->cut, h->rr, h->d_cnt, h->cnt, h->keys, h->h_out, nqc, n, N, k, M_IP, st, out_rows + q0 * k, out_scores + q0 * k,
+        LY_TRY(range_cut_and_order(h->cut, h->rr, h->d_cnt.p, h->cnt, h->keys, h->h_out, nqc, n, N, k, M_IP, st, out_rows + q0 * k, out_scores + q0 * k,
                                    out_counts + q0, out_passed ? out_passed + q0 : nullptr, chunk_done));
     }
     return LYNSE_OK;

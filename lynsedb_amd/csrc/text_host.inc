@@ -8,14 +8,12 @@ struct lynse_hip_text {
     hipStream_t stream = nullptr;
     uint64_t n = 0, V = 0, nnz = 0, total_len = 0;
     std::vector<uint64_t> term_ptr;   // V + 1, host only: a query's slot table carries the posting ranges to the device
-    uint32_t *d_post_row = nullptr, *d_post_tf = nullptr, *d_doc_len = nullptr;
-    size_t post_row_cap = 0, post_tf_cap = 0, doc_len_cap = 0;
-    // the scratch of a search (it runs under the exclusive lock)
-    TextSlot* d_slots = nullptr;
-    uint64_t *d_slot_ptr = nullptr, *d_mask = nullptr, *d_stats = nullptr;   // d_stats: live rows | their length sum | df of every slot
-    float* d_avg = nullptr;
-    uint32_t* d_cnt = nullptr;
-    size_t slots_cap = 0, slot_ptr_cap = 0, mask_cap = 0, stats_cap = 0, avg_cap = 0, cnt_cap = 0;
+    DevBuf<uint32_t> post_row, post_tf, doc_len;
+    // the scratch of a search (it runs under the exclusive lock); the d_ ones have a host image of the same name below
+    DevBuf<TextSlot> d_slots;
+    DevBuf<uint64_t> d_slot_ptr, mask, d_stats;   // d_stats: live rows | their length sum | df of every slot
+    DevBuf<float> d_avg;
+    DevBuf<uint32_t> d_cnt;
     ScoreCut cut;
     PoolRerank rr;
     std::vector<TextSlot> slots;
@@ -83,10 +81,6 @@ extern "C" int lynse_hip_text_destroy(lynse_hip_text* h) {
     if (!h) return LYNSE_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_post_row, (void*)h->d_post_tf, (void*)h->d_doc_len, (void*)h->d_slots, (void*)h->d_slot_ptr, (void*)h->d_mask,
-                    (void*)h->d_stats, (void*)h->d_avg, (void*)h->d_cnt})
-        if (p) (void)hipFree(p);
-    h->cut.release();
     h->rr.release();
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -132,13 +126,13 @@ extern "C" int lynse_hip_text_set(lynse_hip_text* h, const uint32_t* doc_len, ui
     h->n = h->V = h->nnz = h->total_len = 0;   // (a failed upload leaves an empty store, not a torn one)
     h->term_ptr.clear();
     if (n == 0) return LYNSE_OK;
-    LY_TRY(ivf_grow(&h->d_doc_len, &h->doc_len_cap, (size_t)n));
-    LY_TRY(ivf_grow(&h->d_post_row, &h->post_row_cap, (size_t)std::max<uint64_t>(1, nnz)));
-    LY_TRY(ivf_grow(&h->d_post_tf, &h->post_tf_cap, (size_t)std::max<uint64_t>(1, nnz)));
-    LY_TRY(h2d_done(h->d_doc_len, doc_len, (size_t)n * 4));
+    LY_TRY(h->doc_len.reserve((size_t)n));
+    LY_TRY(h->post_row.reserve((size_t)std::max<uint64_t>(1, nnz)));
+    LY_TRY(h->post_tf.reserve((size_t)std::max<uint64_t>(1, nnz)));
+    LY_TRY(h2d_done(h->doc_len.p, doc_len, (size_t)n * 4));
     if (nnz) {
-        LY_TRY(h2d_done(h->d_post_row, post_row, (size_t)nnz * 4));
-        LY_TRY(h2d_done(h->d_post_tf, post_tf, (size_t)nnz * 4));
+        LY_TRY(h2d_done(h->post_row.p, post_row, (size_t)nnz * 4));
+        LY_TRY(h2d_done(h->post_tf.p, post_tf, (size_t)nnz * 4));
     }
     h->term_ptr.assign(term_ptr, term_ptr + V + 1);
     h->n = n;
@@ -160,7 +154,7 @@ extern "C" int lynse_hip_text_len(lynse_hip_text* h, uint64_t* out_rows, uint64_
 extern "C" uint64_t lynse_hip_text_hbm_bytes(lynse_hip_text* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> lk(h->rw);
-    return ((uint64_t)h->doc_len_cap + h->post_row_cap + h->post_tf_cap) * 4;
+    return ((uint64_t)h->doc_len.cap + h->post_row.cap + h->post_tf.cap) * 4;
 }
 
 extern "C" int lynse_hip_text_profile_enable(lynse_hip_text* h, int on) {
@@ -231,15 +225,15 @@ extern "C" int lynse_hip_text_search(lynse_hip_text* h, const uint64_t* q_ptr, c
     const uint64_t mask_words = masked ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
     uint64_t most_slots = 0;   // of a chunk
     for (uint64_t q0 = 0; q0 < nq; q0 += qc) most_slots = std::max(most_slots, q_ptr[std::min(nq, q0 + qc)] - q_ptr[q0]);
-    if (masked) LY_TRY(ivf_grow(&h->d_mask, &h->mask_cap, (size_t)std::max<uint64_t>(1, mask_words)));
-    if (masked) LY_TRY(ivf_grow(&h->d_stats, &h->stats_cap, (size_t)most_slots + 2));
-    LY_TRY(ivf_grow(&h->d_slots, &h->slots_cap, (size_t)std::max<uint64_t>(1, most_slots)));
-    LY_TRY(ivf_grow(&h->d_slot_ptr, &h->slot_ptr_cap, (size_t)qc + 1));
-    LY_TRY(ivf_grow(&h->d_avg, &h->avg_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&h->d_cnt, &h->cnt_cap, (size_t)qc));
-    LY_TRY(ivf_grow(&h->rr.d_keys, &h->rr.keys_cap, (size_t)qc * N));
-    LY_TRY(ivf_grow(&h->rr.d_pcnt, &h->rr.pcnt_cap, (size_t)qc));
-    if (sort_dev) LY_TRY(ivf_grow(&h->rr.d_out, &h->rr.out_cap, ((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
+    if (masked) LY_TRY(h->mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+    if (masked) LY_TRY(h->d_stats.reserve((size_t)most_slots + 2));
+    LY_TRY(h->d_slots.reserve((size_t)std::max<uint64_t>(1, most_slots)));
+    LY_TRY(h->d_slot_ptr.reserve((size_t)qc + 1));
+    LY_TRY(h->d_avg.reserve((size_t)qc));
+    LY_TRY(h->d_cnt.reserve((size_t)qc));
+    LY_TRY(h->rr.keys.reserve((size_t)qc * N));
+    LY_TRY(h->rr.pcnt.reserve((size_t)qc));
+    if (sort_dev) LY_TRY(h->rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
     LY_TRY(h->cut.grow(qc, n));
     const bool timed = h->profiling;
     if (timed) {
@@ -262,7 +256,7 @@ extern "C" int lynse_hip_text_search(lynse_hip_text* h, const uint64_t* q_ptr, c
     // of the caller's words or of the handle's tables must not outlive the call.
     auto run = [&]() -> int {
         // (the caller's words are queued only once nothing before the first launch can fail without being drained)
-        if (mask_words) LY_HIP(hipMemcpyAsync(h->d_mask, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+        if (mask_words) LY_HIP(hipMemcpyAsync(h->mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
         uint64_t docs = n, total = h->total_len;   // rule a without a mask: the totals kept from set
         bool have_corpus = !masked;                // under a mask: counted by the first chunk that reaches the device
         for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
@@ -283,23 +277,23 @@ extern "C" int lynse_hip_text_search(lynse_hip_text* h, const uint64_t* q_ptr, c
             }
             if (masked) {   // rules a and c under the mask: exact integer counts from the device
                 const uint32_t row_blocks = have_corpus ? 0u : (uint32_t)std::min<uint64_t>((n + TEXT_NT - 1) / TEXT_NT, 1024);
-                LY_HIP(hipMemcpyAsync(h->d_slots, h->slots.data(), (size_t)ns * sizeof(TextSlot), hipMemcpyHostToDevice, st));
-                LY_HIP(hipMemsetAsync(h->d_stats, 0, ((size_t)ns + 2) * 8, st));
+                LY_HIP(hipMemcpyAsync(h->d_slots.p, h->slots.data(), (size_t)ns * sizeof(TextSlot), hipMemcpyHostToDevice, st));
+                LY_HIP(hipMemsetAsync(h->d_stats.p, 0, ((size_t)ns + 2) * 8, st));
                 TextStatsArgs sa{};
-                sa.post_row = h->d_post_row;
-                sa.doc_len = h->d_doc_len;
+                sa.post_row = h->post_row.p;
+                sa.doc_len = h->doc_len.p;
                 sa.n = n;
-                sa.slots = h->d_slots;
+                sa.slots = h->d_slots.p;
                 sa.n_slots = ns;
                 sa.row_blocks = row_blocks;
-                sa.mask = h->d_mask;
+                sa.mask = h->mask.p;
                 sa.mask_words = mask_words;
-                sa.corpus = reinterpret_cast<unsigned long long*>(h->d_stats);
-                sa.df = reinterpret_cast<unsigned long long*>(h->d_stats) + 2;
+                sa.corpus = reinterpret_cast<unsigned long long*>(h->d_stats.p);
+                sa.df = reinterpret_cast<unsigned long long*>(h->d_stats.p) + 2;
                 hipLaunchKernelGGL(k_text_stats, dim3((uint32_t)(row_blocks + ns * TEXT_STATS_PARTS)), dim3(TEXT_NT), 0, st, sa);
                 if (hipGetLastError() != hipSuccess) return set_error(LYNSE_ERR_DEVICE, "k_text_stats launch failed");
                 h->stats.resize((size_t)ns + 2);
-                LY_HIP(hipMemcpyAsync(h->stats.data(), h->d_stats, ((size_t)ns + 2) * 8, hipMemcpyDeviceToHost, st));
+                LY_HIP(hipMemcpyAsync(h->stats.data(), h->d_stats.p, ((size_t)ns + 2) * 8, hipMemcpyDeviceToHost, st));
                 LY_TRY(stream_wait(st));
                 if (!have_corpus) {
                     docs = h->stats[0];
@@ -325,23 +319,23 @@ extern "C" int lynse_hip_text_search(lynse_hip_text* h, const uint64_t* q_ptr, c
                     scan_bytes += (s.p1 - s.p0) * 12;
                 }
             }
-            LY_HIP(hipMemcpyAsync(h->d_slots, h->slots.data(), (size_t)ns * sizeof(TextSlot), hipMemcpyHostToDevice, st));
-            LY_HIP(hipMemcpyAsync(h->d_slot_ptr, h->slot_ptr.data(), ((size_t)nqc + 1) * 8, hipMemcpyHostToDevice, st));
-            LY_HIP(hipMemcpyAsync(h->d_avg, h->avg.data(), (size_t)nqc * 4, hipMemcpyHostToDevice, st));
-            LY_HIP(hipMemsetAsync(h->d_cnt, 0, (size_t)nqc * 4, st));
+            LY_HIP(hipMemcpyAsync(h->d_slots.p, h->slots.data(), (size_t)ns * sizeof(TextSlot), hipMemcpyHostToDevice, st));
+            LY_HIP(hipMemcpyAsync(h->d_slot_ptr.p, h->slot_ptr.data(), ((size_t)nqc + 1) * 8, hipMemcpyHostToDevice, st));
+            LY_HIP(hipMemcpyAsync(h->d_avg.p, h->avg.data(), (size_t)nqc * 4, hipMemcpyHostToDevice, st));
+            LY_HIP(hipMemsetAsync(h->d_cnt.p, 0, (size_t)nqc * 4, st));
             TextScanArgs a{};
-            a.post_row = h->d_post_row;
-            a.post_tf = h->d_post_tf;
-            a.doc_len = h->d_doc_len;
+            a.post_row = h->post_row.p;
+            a.post_tf = h->post_tf.p;
+            a.doc_len = h->doc_len.p;
             a.n = n;
-            a.slots = h->d_slots;
-            a.slot_ptr = h->d_slot_ptr;
-            a.avg = h->d_avg;
+            a.slots = h->d_slots.p;
+            a.slot_ptr = h->d_slot_ptr.p;
+            a.avg = h->d_avg.p;
             a.nq = nqc;
-            a.mask = masked ? h->d_mask : nullptr;
+            a.mask = masked ? h->mask.p : nullptr;
             a.mask_words = mask_words;
-            a.S = h->cut.d_S;
-            a.count = h->d_cnt;
+            a.S = h->cut.S.p;
+            a.count = h->d_cnt.p;
             const dim3 grid((uint32_t)((n + TEXT_ROWS - 1) / TEXT_ROWS), nqc);
             if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
             hipLaunchKernelGGL(k_text_scan, grid, dim3(TEXT_NT), 0, st, a);
@@ -352,7 +346,7 @@ extern "C" int lynse_hip_text_search(lynse_hip_text* h, const uint64_t* q_ptr, c
                 h->prof.scan_rows += n * nqc;
                 h->prof.scan_bytes += scan_bytes;
             }
-            LY_TRY(range_cut_and_order(h->cut, h->rr, h->d_cnt, h->cnt, h->keys, h->h_out, nqc, n, N, k, M_IP, st, out_rows + q0 * k, out_scores + q0 * k,
+            LY_TRY(range_cut_and_order(h->cut, h->rr, h->d_cnt.p, h->cnt, h->keys, h->h_out, nqc, n, N, k, M_IP, st, out_rows + q0 * k, out_scores + q0 * k,
                                        out_counts + q0, out_passed ? out_passed + q0 : nullptr, chunk_done));
         }
         return LYNSE_OK;

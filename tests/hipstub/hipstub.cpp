@@ -35,6 +35,15 @@ extern "C" {
 // (called by the stub RCCL in hang mode, and by tests)
 void hipstub_make_stream_stuck(hipStream_t s) { S(s)->stuck.store(1, std::memory_order_relaxed); }
 
+// ---- allocation accounting and failure injection for the `buffers` scenario of the driver
+static std::atomic<int64_t> g_live_allocs{0};     // hipMalloc blocks not yet freed
+static std::atomic<int64_t> g_malloc_calls{0};    // every hipMalloc, failed ones included
+static std::atomic<int64_t> g_fail_at{-1};        // the g_malloc_calls value whose call fails; negative: none
+int64_t hipstub_live_device_allocs(void) { return g_live_allocs.load(std::memory_order_relaxed); }
+int64_t hipstub_malloc_calls(void) { return g_malloc_calls.load(std::memory_order_relaxed); }
+// the nth hipMalloc from now (0 = the next one) returns hipErrorOutOfMemory; a negative nth disarms
+void hipstub_fail_malloc_at(int64_t nth) { g_fail_at.store(nth < 0 ? -1 : g_malloc_calls.load(std::memory_order_relaxed) + nth, std::memory_order_relaxed); }
+
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t* p, int) {
@@ -44,12 +53,22 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t* p, int) {
     p->totalGlobalMem = (size_t)8 << 30;
     return hipSuccess;
 }
-const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : (e == hipErrorNotReady ? "not ready" : "hipstub error"); }
+const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : (e == hipErrorNotReady ? "not ready" : (e == hipErrorOutOfMemory ? "out of memory" : "hipstub error")); }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
 
-hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) {
+    if (g_malloc_calls.fetch_add(1, std::memory_order_relaxed) == g_fail_at.load(std::memory_order_relaxed)) return hipErrorOutOfMemory;   // (*p untouched, as HIP leaves it)
+    *p = calloc(n ? n : 1, 1);
+    if (!*p) return hipErrorOutOfMemory;
+    g_live_allocs.fetch_add(1, std::memory_order_relaxed);
+    return hipSuccess;
+}
+hipError_t hipFree(void* p) {
+    if (p) g_live_allocs.fetch_sub(1, std::memory_order_relaxed);
+    free(p);
+    return hipSuccess;
+}
 hipError_t hipHostMalloc(void** p, size_t n, unsigned int) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 

@@ -8,11 +8,19 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/lynse_hip.h"
+
+// the stub's allocation accounting and failure injection (hipstub.cpp)
+extern "C" {
+int64_t hipstub_live_device_allocs(void);
+int64_t hipstub_malloc_calls(void);
+void hipstub_fail_malloc_at(int64_t nth);
+}
 
 static int g_fail = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s -- ", __FILE__, __LINE__, #cond); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
@@ -348,6 +356,143 @@ static void scenario_dead_peer() {
     lynse_hip_set_wait_timeout_ms(0);
 }
 
+// ---- 5. the grow-on-demand device scratch: nothing leaks over a small / large / small sequence of calls, and a call whose n-th
+// allocation fails returns LYNSE_ERR_OUT_OF_MEMORY and leaves a handle that the next calls can use (single-threaded; the stub counts
+// the live blocks and fails the allocation it is told to)
+struct BufKind {
+    const char* name;
+    std::function<void*()> create;
+    std::function<int(void*, bool)> call;   // (handle, large): the small or the larger call
+    std::function<void(void*)> destroy;
+};
+
+static void buffers_leak_check(const BufKind& kd) {
+    const int64_t base = hipstub_live_device_allocs();
+    void* h = kd.create();
+    if (!h) return;
+    for (const bool large : {false, true, false}) CHECK(kd.call(h, large) == LYNSE_OK, "%s (%s call): %s", kd.name, large ? "large" : "small", last_error().c_str());
+    kd.destroy(h);
+    CHECK(hipstub_live_device_allocs() == base, "%s: %lld device blocks live after destroy, %lld before create", kd.name,
+          (long long)hipstub_live_device_allocs(), (long long)base);
+}
+
+static void buffers_failure_sweep(const BufKind& kd) {
+    const int64_t base = hipstub_live_device_allocs();
+    int64_t M = 0;
+    {
+        void* h = kd.create();
+        if (!h) return;
+        CHECK(kd.call(h, false) == LYNSE_OK, "%s: %s", kd.name, last_error().c_str());
+        const int64_t c0 = hipstub_malloc_calls();
+        CHECK(kd.call(h, true) == LYNSE_OK, "%s: %s", kd.name, last_error().c_str());
+        M = hipstub_malloc_calls() - c0;
+        kd.destroy(h);
+    }
+    CHECK(M > 0 && M <= 200, "%s: the larger call made %lld allocations", kd.name, (long long)M);
+    for (int64_t i = 0; i < M && i < 200; ++i) {
+        void* h = kd.create();
+        if (!h) return;
+        CHECK(kd.call(h, false) == LYNSE_OK, "%s: %s", kd.name, last_error().c_str());
+        hipstub_fail_malloc_at(i);
+        const int rc = kd.call(h, true);
+        hipstub_fail_malloc_at(-1);
+        CHECK(rc == LYNSE_ERR_OUT_OF_MEMORY, "%s: allocation %lld of %lld failed, the call returned %d (%s)", kd.name, (long long)i, (long long)M, rc, last_error().c_str());
+        CHECK(kd.call(h, false) == LYNSE_OK, "%s: the small call after failure %lld: %s", kd.name, (long long)i, last_error().c_str());
+        CHECK(kd.call(h, true) == LYNSE_OK, "%s: the larger call after failure %lld: %s", kd.name, (long long)i, last_error().c_str());
+        kd.destroy(h);
+        CHECK(hipstub_live_device_allocs() == base, "%s: %lld device blocks live after failure %lld, %lld before", kd.name,
+              (long long)hipstub_live_device_allocs(), (long long)i, (long long)base);
+    }
+    fprintf(stderr, "[tsan_driver] buffers: %s: the larger call allocates %lld times, each failed in turn\n", kd.name, (long long)M);
+}
+
+static void scenario_buffers() {
+    const uint32_t dim = 32, k = 10, nlist = 16; const uint64_t n = 2048;
+    const uint64_t nq_of[2] = {4, 300}, ns_of[2] = {64, 1500};
+    const auto q = rows_of(300, dim, 31);
+    std::vector<uint64_t> subset;   // descending: the gathered-rows strategy sorts it
+    for (uint64_t i = 0; i < 1500; ++i) subset.push_back(n - 1 - i);
+    std::vector<uint64_t> words[2];   // the same subsets as BitSet words
+    for (int l = 0; l < 2; ++l) {
+        words[l].assign(n / 64, 0ull);
+        for (uint64_t i = 0; i < ns_of[l]; ++i) words[l][subset[i] / 64] |= 1ull << (subset[i] % 64);
+    }
+    const std::vector<float> thr(300, 0.5f);
+    Out o(300, k);
+
+    auto flat_create = [&]() -> void* {
+        lynse_hip_flat* h = nullptr;
+        CHECK(lynse_hip_flat_create(dim, 0, &h) == LYNSE_OK, "%s", last_error().c_str());
+        const auto data = rows_of(n, dim, 30);
+        CHECK(lynse_hip_flat_append_f32(h, data.data(), n) == LYNSE_OK, "%s", last_error().c_str());
+        CHECK(lynse_hip_flat_finalize(h) == LYNSE_OK, "%s", last_error().c_str());
+        return h;
+    };
+    auto flat_destroy = [](void* h) { lynse_hip_flat_destroy((lynse_hip_flat*)h); };
+    auto flat_list = [&](void* h, bool l) {
+        return lynse_hip_flat_search_filtered_f32((lynse_hip_flat*)h, q.data(), nq_of[l], k, 0, subset.data(), ns_of[l], o.rows.data(), o.dists.data(), o.counts.data());
+    };
+    auto flat_bits = [&](void* h, bool l) {
+        return lynse_hip_flat_search_filtered_bitset_f32((lynse_hip_flat*)h, q.data(), nq_of[l], k, 1, words[l].data(), words[l].size(), o.rows.data(), o.dists.data(), o.counts.data());
+    };
+    Out ro(300, 64);   // (a range search writes max_results per query)
+    auto flat_range = [&](void* h, bool l) {
+        return lynse_hip_flat_search_range_f32((lynse_hip_flat*)h, q.data(), nq_of[l], thr.data(), l ? 64 : 8, 0, nullptr, 0, ro.rows.data(), ro.dists.data(), ro.counts.data(), nullptr);
+    };
+    auto ivf_create = [&](bool sq8) -> void* {
+        const auto data = rows_of(n, dim, 32);
+        const auto cen = rows_of(nlist, dim, 33);
+        std::vector<uint32_t> asg(n);
+        for (uint64_t i = 0; i < n; ++i) asg[i] = (uint32_t)(i % nlist);
+        const std::vector<float> mins(dim, 0.0f), scales(dim, 1.0f / 255.0f);
+        lynse_hip_ivf* h = nullptr;
+        const int rc = sq8 ? lynse_hip_ivf_load_sq8(data.data(), n, dim, cen.data(), nlist, asg.data(), mins.data(), scales.data(), 1, 0, &h)
+                           : lynse_hip_ivf_load(data.data(), n, dim, cen.data(), nlist, asg.data(), 0, 0, &h);
+        CHECK(rc == LYNSE_OK, "%s", last_error().c_str());
+        return h;
+    };
+    auto ivf_destroy = [](void* h) { lynse_hip_ivf_destroy((lynse_hip_ivf*)h); };
+    auto ivf_filtered = [&](void* h, bool l) {
+        return lynse_hip_ivf_search_filtered_f32((lynse_hip_ivf*)h, q.data(), nq_of[l], k, 4, subset.data(), ns_of[l], o.rows.data(), o.dists.data(), o.counts.data());
+    };
+    auto ivf_plain = [&](void* h, bool l) {
+        return lynse_hip_ivf_search_f32((lynse_hip_ivf*)h, q.data(), nq_of[l], k, 4, o.rows.data(), o.dists.data(), o.counts.data());
+    };
+    // sparse rows and queries: four ascending column ids each
+    std::vector<uint64_t> indptr(n + 1);
+    std::vector<uint32_t> indices(n * 4);
+    const std::vector<float> values(n * 4, 1.0f);
+    for (uint64_t r = 0; r <= n; ++r) indptr[r] = r * 4;
+    for (uint64_t r = 0; r < n; ++r)
+        for (uint32_t j = 0; j < 4; ++j) indices[r * 4 + j] = j * 8 + (uint32_t)(r % 8);
+    auto sparse_create = [&]() -> void* {
+        lynse_hip_sparse* h = nullptr;
+        CHECK(lynse_hip_sparse_create(0, &h) == LYNSE_OK, "%s", last_error().c_str());
+        CHECK(lynse_hip_sparse_set_rows(h, indptr.data(), indices.data(), values.data(), n) == LYNSE_OK, "%s", last_error().c_str());
+        return h;
+    };
+    auto sparse_destroy = [](void* h) { lynse_hip_sparse_destroy((lynse_hip_sparse*)h); };
+    auto sparse_call = [&](void* h, bool l) {
+        return lynse_hip_sparse_search((lynse_hip_sparse*)h, indptr.data(), indices.data(), values.data(), nq_of[l], k, words[l].data(), words[l].size(),
+                                       o.rows.data(), o.dists.data(), o.counts.data(), nullptr);
+    };
+
+    const BufKind flat_list_kind{"FLAT list subset", flat_create, flat_list, flat_destroy};
+    const BufKind ivf_filtered_kind{"IVF filtered", [&]() { return ivf_create(false); }, ivf_filtered, ivf_destroy};
+    for (const char* strategy : {"1", "2"}) {   // the gathered rows, the masked scan
+        setenv("LYNSE_HIP_FILTER_STRATEGY", strategy, 1);
+        buffers_leak_check(flat_list_kind);
+        buffers_failure_sweep(flat_list_kind);
+    }
+    unsetenv("LYNSE_HIP_FILTER_STRATEGY");
+    buffers_leak_check({"FLAT bitset", flat_create, flat_bits, flat_destroy});
+    buffers_leak_check({"FLAT range", flat_create, flat_range, flat_destroy});
+    buffers_leak_check(ivf_filtered_kind);
+    buffers_leak_check({"IVF-SQ8", [&]() { return ivf_create(true); }, ivf_plain, ivf_destroy});
+    buffers_leak_check({"sparse", sparse_create, sparse_call, sparse_destroy});
+    buffers_failure_sweep(ivf_filtered_kind);
+}
+
 int main(int argc, char** argv) {
     const std::string which = argc > 1 ? argv[1] : "all";
     if (which == "all" || which == "readers") scenario_readers();
@@ -355,6 +500,7 @@ int main(int argc, char** argv) {
     if (which == "all" || which == "ivf") scenario_ivf();
     if (which == "all" || which == "comm1") scenario_comm1();
     if (which == "all" || which == "dead_peer") scenario_dead_peer();
+    if (which == "all" || which == "buffers") scenario_buffers();
     fprintf(stderr, "[tsan_driver] %s: %d failed checks\n", which.c_str(), g_fail);
     return g_fail ? 1 : 0;
 }

@@ -49,7 +49,7 @@ def _without_aslr(cmd):
     return cmd
 
 
-@pytest.mark.parametrize("scenario", ["readers", "tickets", "ivf", "comm1", "dead_peer"])
+@pytest.mark.parametrize("scenario", ["readers", "tickets", "ivf", "comm1", "dead_peer", "buffers"])
 def test_host_state_machine_under_threadsanitizer(driver, scenario):
     env = dict(os.environ)
     env["LYNSE_HIP_RCCL_PATH"] = str(OUT / "librcclstub.so")
