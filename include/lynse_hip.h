@@ -1063,6 +1063,52 @@ int lynse_hip_sparse_search(lynse_hip_sparse *h, const uint64_t *q_indptr /* nq+
 int lynse_hip_sparse_profile_enable(lynse_hip_sparse *h, int on);
 int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, int reset);
 
+/* ---- multi-vector records: late interaction (MaxSim), index mode MULTIVEC-MAXSIM-IP ---- */
+
+/* MULTI-VECTOR SEARCH (this build's addition; the reference has no counterpart).  A record is a SET of token vectors of one
+ * dimension dim_mv, a query is a set of token vectors too, and score(Q, P) = sum_i max_j <q_i, p_j>.  The store is append-only; record
+ * rows are 0 .. n - 1 in the order appended.  The rules:
+ *  1. Layout.  Token rows are one contiguous f32 array [total_tokens][ld] in HBM (ld = dim_mv rounded up to a multiple of 32, the
+ *     columns past dim_mv zero); a u64 rec_ptr[n_records + 1] gives the offsets, a record's tokens are consecutive, in the order given.
+ *     (The device copy of rec_ptr lists the records that have tokens, with their record rows next to it: the others never score.)
+ *  2. Score.  s_ij is the f32 inner product of query token i and record token j, accumulated by v_mfma_f32_32x32x2_f32; the order of
+ *     that accumulation is the hardware's and NOT part of the contract.
+ *  3. Max.  m_i = max_j s_ij over the record's tokens: exact and order-free.  A NaN s_ij is skipped, as fmaxf does; all NaN: m_i = -inf.
+ *  4. Sum.  score = ((m_0 + m_1) + m_2) + ... in f32, in query-token order, separate adds, nothing fused.
+ *  5. A record with no tokens, or one the mask leaves out, is never returned.  bitset_words are BitSet words over record rows, treated
+ *     as lynse_hip_sparse_search treats its words (NULL = every record, records the words do not cover are out).
+ *  6. Order: score descending, then record row ascending.  NON-FINITE VALUES as for the ip searches: a NaN score is reported as -inf
+ *     and ranks with -inf, -0 is reported as +0, +-inf are ordinary values.  k above the number of live records returns them all:
+ *     layout as lynse_hip_flat_search_f32, stride k, out_counts[q] = min(k, live) entries valid.
+ *  7. Limits: 1 <= tokens of a query <= 256 and 1 <= dim_mv <= 1024, LYNSE_ERR_UNSUPPORTED beyond (a query without tokens:
+ *     LYNSE_ERR_INVALID_ARGUMENT); no limit on the tokens of a record.  The query's tiles of 32 tokens (1, 2, 4 or 8 of them) stay in
+ *     LDS next to two blocks of 32 token rows per wave; where one wave's share does not fit the 160 KiB — more than 128 query tokens
+ *     at dim_mv > 96, more than 64 above 192, more than 32 above 288, any query above 416 — the answer is LYNSE_ERR_UNSUPPORTED
+ *     ("... do not fit in LDS").  So the EFFECTIVE limit on dim_mv is 416: lynse_hip_multivec_create refuses a wider store with that
+ *     message, since no query could be answered from it; 417 .. 1024 are inside the contract and wait for a column-chunked block.
+ *  8. A search holds the handle's lock EXCLUSIVELY (the scratch is per handle; the handle has no submit / wait form, so no tickets)
+ *     and goes in query chunks that keep the score matrix at or under 512 MiB.  Queries of one call may differ in their token count.
+ *  9. Profile: scan_launches, scan_us, scan_rows = token rows streamed (all of them, once per query), scan_bytes likewise,
+ *     total_us = first launch to last launch of a chunk.
+ * Without a usable HIP device lynse_hip_multivec_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+typedef struct lynse_hip_multivec lynse_hip_multivec;
+/* Rule 7 for a query of tq tokens at dim_mv, host only (no handle, no device): the query tiles held in LDS, the waves of a workgroup
+ * and the LDS bytes; LYNSE_ERR_UNSUPPORTED with the message of rule 7 where the answer is a refusal.  Each output may be NULL. */
+int lynse_hip_multivec_plan(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
+int lynse_hip_multivec_create(int device, uint32_t dim_mv, lynse_hip_multivec **out);
+int lynse_hip_multivec_destroy(lynse_hip_multivec *h);
+/* n_records records more: record i has counts[i] >= 0 rows of dim_mv floats, consecutive in `tokens`.  A failed call changes nothing. */
+int lynse_hip_multivec_append(lynse_hip_multivec *h, const float *tokens, const uint64_t *counts /* n_records */, uint64_t n_records);
+/* records (those without tokens included), token rows, wave ranges of the scan; each pointer may be NULL */
+int lynse_hip_multivec_counts(lynse_hip_multivec *h, uint64_t *out_records, uint64_t *out_tokens, uint64_t *out_ranges);
+int lynse_hip_multivec_search_f32(lynse_hip_multivec *h, const float *q_tokens /* q_ptr[nq] x dim_mv */, const uint64_t *q_ptr /* nq+1 */,
+                                  uint64_t nq, uint32_t k, uint64_t *out_rows /* nq*k */, float *out_scores, uint32_t *out_counts /* nq */);
+int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec *h, const float *q_tokens, const uint64_t *q_ptr /* nq+1 */, uint64_t nq,
+                                         uint32_t k, const uint64_t *bitset_words /* NULL = every record */, uint64_t n_words,
+                                         uint64_t *out_rows /* nq*k */, float *out_scores, uint32_t *out_counts /* nq */);
+int lynse_hip_multivec_profile_enable(lynse_hip_multivec *h, int on);
+int lynse_hip_multivec_profile_get(lynse_hip_multivec *h, lynse_hip_profile *out, int reset);
+
 /* ---- text search: InvertedTextIndex (src/engine.rs:720-1118), index mode BM25-INVERTED ---- */
 
 /* TEXT SEARCH (Collection::text_search, src/engine.rs:5056-5076, over InvertedTextIndex::search, :927-1054).  The caller tokenises

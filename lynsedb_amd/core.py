@@ -1624,6 +1624,94 @@ class SparseIndex:
 
 
 # ---------------------------------------------------------------------------------------------
+# Multi-vector records: late interaction, score(Q, P) = sum_i max_j <q_i, p_j> (include/lynse_hip.h, MULTI-VECTOR SEARCH)
+# ---------------------------------------------------------------------------------------------
+MULTIVEC_INDEX_MODE = "MULTIVEC-MAXSIM-IP"
+MULTIVEC_MAX_QUERY_TOKENS = 256   # include/lynse_hip.h, MULTI-VECTOR SEARCH rule 7
+MULTIVEC_MAX_DIM = 1024
+
+
+def _multivec_queries(queries, dim: Optional[int]) -> list:
+    """the query token arrays as (Tq, dim) f32, checked against rule 7 before any device is touched"""
+    out = []
+    for q in queries:
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("query tokens must be a 2-D array (tokens, dim)")
+        if q.shape[0] < 1:
+            raise ValueError("a multi-vector query needs at least one token")
+        if q.shape[0] > MULTIVEC_MAX_QUERY_TOKENS:
+            raise NotImplementedError(f"multi-vector search: a query of more than {MULTIVEC_MAX_QUERY_TOKENS} tokens is not supported")
+        if q.shape[1] < 1 or q.shape[1] > MULTIVEC_MAX_DIM:
+            raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
+        if dim is not None and q.shape[1] != dim:
+            raise RuntimeError(f"Dimension mismatch: expected {dim}, got {q.shape[1]}")
+        check(lib.lynse_hip_multivec_plan(q.shape[1], q.shape[0], None, None, None))   # the LDS half of rule 7 (host only)
+        out.append(q)
+    return out
+
+
+class MultiVectorIndex:
+    """The token rows of multi-vector records in HBM, append-only, and their exact MaxSim scan (k_maxsim_scan)."""
+
+    def __init__(self, dim: int, device: Optional[int] = None):
+        self._h, self._dim = C.c_void_p(), int(dim)
+        dev = default_device() if device is None else int(device)
+        check(lib.lynse_hip_multivec_create(dev, self._dim, C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.lynse_hip_multivec_destroy(h)
+
+    def append(self, token_sets) -> None:
+        """records more, one (T_r, dim) f32 array each, T_r >= 0"""
+        counts = np.array([t.shape[0] for t in token_sets], dtype=np.uint64)
+        full = [t for t in token_sets if t.shape[0]]
+        tokens = np.ascontiguousarray(np.concatenate(full)) if full else np.zeros((0, self._dim), np.float32)
+        check(lib.lynse_hip_multivec_append(self._h, _ptr(tokens) if tokens.size else None, _ptr(counts), counts.size))
+
+    def counts(self) -> dict:
+        r, t, g = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib.lynse_hip_multivec_counts(self._h, C.byref(r), C.byref(t), C.byref(g)))
+        return {"records": int(r.value), "tokens": int(t.value), "ranges": int(g.value)}
+
+    def search_batch_arrays(self, queries, k: int, words=None):
+        """-> (rows u64[nq, k], scores f32[nq, k], counts u32[nq]) by (score descending, record row ascending); `words` are BitSet
+        words over record rows (None = every record)."""
+        queries = _multivec_queries(queries, self._dim)
+        nq, k = len(queries), int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        rows = np.full((nq, k), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        scores = np.full((nq, k), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        if nq == 0:
+            return rows, scores, counts
+        q_ptr = np.zeros(nq + 1, np.uint64)
+        np.cumsum([q.shape[0] for q in queries], out=q_ptr[1:])
+        tokens = np.ascontiguousarray(np.concatenate(queries))
+        if words is None:
+            check(lib.lynse_hip_multivec_search_f32(self._h, _ptr(tokens), _ptr(q_ptr), nq, k, _ptr(rows), _ptr(scores), _ptr(counts)))
+        else:
+            words = np.ascontiguousarray(np.asarray(words).reshape(-1), dtype=np.uint64)
+            n_words = int(words.size)
+            if n_words == 0:   # an empty mask is still a mask (NULL would mean every record)
+                words = np.zeros(1, np.uint64)
+            check(lib.lynse_hip_multivec_search_bitset_f32(self._h, _ptr(tokens), _ptr(q_ptr), nq, k, _ptr(words), n_words,
+                                                           _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def profile_enable(self, on=True) -> None:
+        check(lib.lynse_hip_multivec_profile_enable(self._h, int(bool(on))))
+
+    def profile_get(self, reset: bool = True) -> dict:
+        p = _lib.Profile()
+        check(lib.lynse_hip_multivec_profile_get(self._h, C.byref(p), 1 if reset else 0))
+        return {f: getattr(p, f) for f, _ in _lib.Profile._fields_}
+
+
+# ---------------------------------------------------------------------------------------------
 # Text search (InvertedTextIndex, src/engine.rs:720-1118; index modes BM25-INVERTED, HYBRID-RRF, HYBRID-WEIGHTED)
 # ---------------------------------------------------------------------------------------------
 TEXT_INDEX_MODE = "BM25-INVERTED"
@@ -1977,6 +2065,7 @@ class Collection:
         self._sparse_ids = np.zeros(0, np.int64)   # the ids of the uploaded sparse rows, ascending: sparse row -> user id
         self._sparse_index = None       # SparseIndex, created by the first sparse search
         self._sparse_dirty = False      # the store changed since the last upload
+        self._mv_reset()                # the multi-vector records (add_multi_vectors / search_multi_vector)
         self._docs: dict = {}           # user id -> {field: {term: tf}} (InvertedTextIndex.postings / doc_lengths), flushed or pending rows alike
         self._text_index = None         # TextIndex, created by the first text search
         self._text_key = None           # the field selection the device store holds: () = all fields, else the sorted names
@@ -2183,6 +2272,7 @@ class Collection:
             save_sparse_vectors(self._path / SPARSE_VECTORS_FILE, self._sparse)
         if self._vfields:
             self._compact_vector_fields(dead_ids)
+        self._mv_dead |= self._tombstone & self._mv_seen   # (the token store is append-only: the records stay, masked out for good)
         self._row_stamp += 1
         self._tombstone.clear()
         self._rebuild_index()
@@ -2568,7 +2658,7 @@ class Collection:
         return normalize_eps(eps)
 
     def search_profile(self, vector, k: Optional[int] = None, where_expr: Optional[str] = None, nprobe: Optional[int] = None,
-                       approx: Optional[bool] = None, eps: Optional[float] = None, subset=None, where=None) -> dict:
+                       approx: Optional[bool] = None, eps: Optional[float] = None, subset=None, where=None, query_tokens=None) -> dict:
         """`Collection.search_profile` (src/python/mod.rs:1240-1271 over Collection::search_with_profile, src/engine.rs:5005-5054): the
         search + a `QueryProfile` (engine.rs:6906-6919) with the reference's field names — query_kind, vector_field, index_path
         ("ann_index" / "flat_mmap_filtered" / "flat_mmap", engine.rs:5163-5177), total_vectors, filter_expression, filter_matches,
@@ -2577,9 +2667,12 @@ class Collection:
         search with HIP events on the search stream (pipeline_us, scan_us, scan_launches, rows and bytes the scan launches streamed,
         rescored_candidates, fallback_queries).  The precomputed filter is `subset=`; with `where=` filter_expression is the string,
         filter_matches the rows it selects (flushed and pending), filter_us the time of the filter (column upload, kernel, count read-back
-        and the host pass over the pending rows), and index_path "flat_mmap_filtered" unless an IVF index answers."""
+        and the host pass over the pending rows), and index_path "flat_mmap_filtered" unless an IVF index answers.  `query_tokens=` (a
+        (Tq, dim_mv) array) profiles `search_multi_vector` instead: `vector` is not read and the device entry is `device.multivec`."""
         import time
 
+        if query_tokens is not None:   # a multi-vector query: `vector` is not read; the profile's device entry is `multivec`
+            return self.search_multi_vector_profile(query_tokens, k, where=where, subset=subset)
         started = time.perf_counter()
         filter_us, filter_matches = 0, None
         if where_expr:
@@ -3060,6 +3153,129 @@ class Collection:
         if where_expr:
             raise NotImplementedError("`where_expr` needs the field store (out of scope, SURVEY.md §2); pass the resolved row filter as subset=")
         return self.batch_search_sparse([vector], k, subset=subset, where=where)[0]
+
+    # -- multi-vector records (include/lynse_hip.h, MULTI-VECTOR SEARCH) ------------
+    def _mv_reset(self) -> None:
+        self._mv_dim = None             # dim_mv, fixed by the first add_multi_vectors
+        self._mv_ids: list = []         # record row -> user id, in the order added (the store is append-only)
+        self._mv_seen: set = set()
+        self._mv_dead: set = set()      # ids that `compact` removed from the collection: their records are never returned again
+        self._mv_pending: list = []     # token sets not yet on the device: uploaded by the next search
+        self._mv_index = None           # MultiVectorIndex, created by the first search
+
+    def add_multi_vectors(self, ids: Sequence[int], token_sets) -> None:
+        """Attaches a set of token vectors to each id (ids that exist, flushed or pending, as for add_sparse_vectors): token_sets[r] is
+        a (T_r, dim_mv) f32 array, T_r >= 0 — a record without tokens is never returned.  dim_mv is fixed by the first call and is
+        independent of the collection's own dimension; the contract allows up to 1024, this build answers up to 416 (beyond, a
+        block of token rows does not fit the LDS next to one query tile) and refuses a wider first call with NotImplementedError.
+        The store is append-only: an id added twice is refused, a refused call changes nothing, and an id that `compact` removed
+        from the collection stays masked out for good.  The device copy follows at the next multi-vector search."""
+        ids = [int(i) for i in ids]
+        sets = [np.asarray(t, dtype=np.float32) for t in token_sets]
+        if len(ids) != len(sets):
+            raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match token set count ({len(sets)})")
+        dim = self._mv_dim
+        for t in sets:
+            if t.ndim != 2 and t.size:
+                raise ValueError("a token set must be a 2-D array (tokens, dim_mv)")
+            if t.ndim == 2 and dim is None:
+                dim = int(t.shape[1])
+        if dim is None:
+            raise ValueError("the first add_multi_vectors call must give a 2-D token set: it fixes dim_mv")
+        if dim < 1 or dim > MULTIVEC_MAX_DIM:
+            raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
+        check(lib.lynse_hip_multivec_plan(dim, 1, None, None, None))   # above 416 not even one query tile fits the LDS: refused here
+        sets = [np.ascontiguousarray(t.reshape(-1, dim) if t.size == 0 else t) for t in sets]
+        for t in sets:
+            if t.shape[1] != dim:
+                raise RuntimeError(f"Dimension mismatch: expected {dim}, got {t.shape[1]}")
+        seen, known = set(), self._ids_known(np.asarray(ids, dtype=np.int64))
+        for i, ok in zip(ids, known):
+            if i in seen or i in self._mv_seen:
+                raise RuntimeError(f"Invalid argument: multi-vector id {i} was already added")
+            seen.add(i)
+            if not ok:
+                raise RuntimeError(f"Invalid argument: cannot add multi-vector for unknown id {i}")
+        self._mv_dim = dim
+        self._mv_ids.extend(ids)
+        self._mv_seen |= seen
+        self._mv_pending.extend(sets)
+
+    def multi_vector_len(self) -> int:
+        return len(self._mv_ids)
+
+    def _mv_upload(self) -> None:
+        if self._mv_index is None:
+            self._mv_index = MultiVectorIndex(self._mv_dim, self._device)
+        if self._mv_pending:
+            self._mv_index.append(self._mv_pending)
+            self._mv_pending = []
+
+    def _mv_words(self, subset) -> Optional[np.ndarray]:
+        """the BitSet words over record rows of a dense-row subset minus the tombstoned and the compacted-away ids; None = every record"""
+        n, mv_ids = len(self._mv_ids), np.asarray(self._mv_ids, dtype=np.int64)
+        words = None
+        if subset is not None:
+            rows = self._subset_rows(subset).astype(np.int64)
+            rows = rows[rows < len(self._flat) + self._pending_rows]
+            words = BitSet.from_rows(np.nonzero(np.isin(mv_ids, self._user_ids(rows)))[0], n).words
+        gone = self._tombstone | self._mv_dead
+        if gone:
+            dead = np.nonzero(np.isin(mv_ids, np.fromiter(gone, dtype=np.int64, count=len(gone))))[0]
+            if dead.size:
+                if words is None:
+                    words = BitSet.from_rows(np.arange(n, dtype=np.uint64), n).words
+                words = words & ~BitSet.from_rows(dead, n).words
+        return words
+
+    def batch_search_multi_vector(self, queries, k: Optional[int] = None, where=None, subset=None) -> list:
+        """`search_multi_vector` for a list of query token arrays (their token counts may differ) sharing one filter, in ONE device
+        call."""
+        k = 10 if k is None else int(k)
+        if k < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        queries = _multivec_queries(queries, self._mv_dim)
+        subset = self._where_subset(where, subset)
+        empty = lambda: SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), MULTIVEC_INDEX_MODE, self._mv_dim or 0, k)   # noqa: E731
+        if k == 0 or not self._mv_ids or not queries:   # the device is not touched
+            return [empty() for _ in queries]
+        self._mv_upload()
+        rows, scores, counts = self._mv_index.search_batch_arrays(queries, k, self._mv_words(subset))
+        mv_ids = np.asarray(self._mv_ids, dtype=np.int64)
+        return [SearchResult(mv_ids[rows[i, :int(c)].astype(np.int64)], scores[i, :int(c)].copy(), MULTIVEC_INDEX_MODE, self._mv_dim, k)
+                for i, c in enumerate(counts)]
+
+    def search_multi_vector(self, query_tokens, k: Optional[int] = None, where=None, subset=None) -> SearchResult:
+        """Late interaction (MaxSim): the ids whose token set scores best against the (Tq, dim_mv) query tokens, score = sum over the
+        query tokens of the best inner product among the record's tokens, by (score descending, record row ascending), at most k
+        (default 10); the scores are in `distances()`, the mode is MULTIVEC-MAXSIM-IP.  `where=`, `subset=` and tombstones mean what
+        they mean in `search_sparse`.  1 <= Tq <= 256, NotImplementedError beyond — and for a query whose tiles of 32 tokens do not
+        fit the LDS next to the token blocks: more than 128 tokens above dim_mv 96, more than 64 above 192, more than 32 above 288."""
+        return self.batch_search_multi_vector([query_tokens], k, where=where, subset=subset)[0]
+
+    def search_multi_vector_profile(self, query_tokens, k: Optional[int] = None, where=None, subset=None) -> dict:
+        """`search_multi_vector` + what the handle measured with HIP events on its stream: the `device.multivec` entry of `search_profile`."""
+        import time
+
+        t0 = time.perf_counter()
+        dev, counts = None, {"records": 0, "tokens": 0, "ranges": 0}
+        if self._mv_ids:
+            self._mv_upload()
+            self._mv_index.profile_enable(True)
+            self._mv_index.profile_get(reset=True)
+        try:
+            res = self.search_multi_vector(query_tokens, k, where=where, subset=subset)
+        finally:
+            if self._mv_ids:
+                dev = self._mv_index.profile_get(reset=True)
+                self._mv_index.profile_enable(False)
+                counts = self._mv_index.counts()
+        multivec = dict(counts, scan_us=float(dev["scan_us"]) if dev else 0.0, pipeline_us=float(dev["total_us"]) if dev else 0.0,
+                        scan_launches=int(dev["scan_launches"]) if dev else 0, scan_rows=int(dev["scan_rows"]) if dev else 0,
+                        scan_bytes=int(dev["scan_bytes"]) if dev else 0)
+        return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
+                "profile": {"query_kind": "multi_vector", "index_path": "multivec_scan", "total_vectors": len(self._mv_ids), "result_count": len(res),
+                            "total_us": int((time.perf_counter() - t0) * 1e6), "device": {"multivec": multivec}}}
 
     # -- text search (engine.rs:5056-5161, :927-1054) -------------------------------------------
     def text_len(self) -> int:

@@ -41,6 +41,7 @@
 #include "spann.h"
 #include "mutate.h"
 #include "predict.h"
+#include "maxsim.h"
 
 using namespace lynse;
 
@@ -3828,3 +3829,4 @@ static inline bool status_failed(uint32_t st) { return (st & 0xffffff00u) != 0u;
 #include "text_host.inc"
 #include "fields_host.inc"
 #include "mutate_host.inc"
+#include "maxsim_host.inc"

@@ -1,0 +1,355 @@
+// maxsim_host.inc — multi-vector search (MaxSim: score(Q, P) = sum_i max_j <q_i, p_j>): a handle of its own that holds the token rows
+// of the records in HBM, append-only.  Included at the end of lynse_hip.hip after mutate_host.inc; the kernel is in maxsim.h.  The
+// search is the additive search's shape: one exact scan into S[q][record], then the shared cut (ScoreCut::cut<true>) and order
+// (k_pool_select, or select_pool_keys beyond 16,384 keys), descending as for ip.  include/lynse_hip.h, MULTI-VECTOR SEARCH; DESIGN.md §28.
+
+struct lynse_hip_multivec {
+    std::shared_mutex rw;
+    int device = 0;
+    uint32_t num_cu = 256;
+    hipStream_t stream = nullptr;
+    uint32_t dim = 0, ld = 0;
+    uint64_t n = 0, total = 0;              // records (those without tokens included), token rows
+    // the records that have tokens, which are all the kernel sees: their token offsets, their record rows, and the wave ranges
+    std::vector<uint64_t> cptr{0};
+    std::vector<uint32_t> crec, ranges{0};
+    DevBuf<float> tokens;
+    DevBuf<uint64_t> d_cptr;
+    DevBuf<uint32_t> d_crec, d_ranges;
+    // the scratch of a search (it runs under the exclusive lock)
+    DevBuf<float> q;
+    DevBuf<uint64_t> qdesc, mask;
+    ScoreCut cut;
+    PoolRerank rr;
+    std::vector<float> hq, stage;
+    std::vector<uint64_t> hdesc, keys, h_out;
+    bool profiling = false;
+    lynse_hip_profile prof{};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // the scan begins / the scan ends / the last launch of the chunk
+};
+
+// Rule 7 for a query of tq tokens against token rows of `dim` floats, host only: the query tiles the LDS holds (a power of two of
+// them: one kernel each), the waves of a workgroup that fit next to them (4, 2 or 1) and the bytes.  Each output may be NULL.
+extern "C" int lynse_hip_multivec_plan(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
+    if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
+    if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
+    if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
+    const uint32_t ld = maxsim_ld(dim);
+    uint32_t tiles = 1, waves = MAXSIM_MAX_WAVES;
+    while (tiles * 32u < tq) tiles *= 2;
+    while (waves > 1 && maxsim_lds_bytes(ld, tiles, waves) > PoolRerank::LDS_MAX) waves /= 2;
+    const size_t lds = maxsim_lds_bytes(ld, tiles, waves);
+    if (lds > PoolRerank::LDS_MAX)
+        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) and two token blocks of dimension " +
+                                                    std::to_string(dim) + " do not fit in LDS");
+    if (out_tiles) *out_tiles = tiles;
+    if (out_waves) *out_waves = waves;
+    if (out_lds_bytes) *out_lds_bytes = lds;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_multivec** out) {
+    if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    LY_TRY(lynse_hip_multivec_plan(dim, 1, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
+    int ndev = 0;
+    LY_TRY(lynse_hip_device_count(&ndev));
+    if (ndev <= 0) return set_error(LYNSE_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    LY_HIP(hipSetDevice(device));
+    auto* h = new lynse_hip_multivec();
+    h->device = device;
+    h->dim = dim;
+    h->ld = maxsim_ld(dim);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount;
+    const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete h;
+        return set_error(LYNSE_ERR_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_destroy(lynse_hip_multivec* h) {
+    if (!h) return LYNSE_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->rr.release();
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return LYNSE_OK;
+}
+
+// The wave ranges over the records that have tokens: whole records, closed once they hold MAXSIM_RANGE tokens or the next record
+// would take them past it — so a record of MAXSIM_RANGE tokens or more stands alone.
+static void maxsim_ranges(const std::vector<uint64_t>& cptr, std::vector<uint32_t>& ranges) {
+    const uint32_t m = (uint32_t)(cptr.size() - 1);
+    ranges.assign(1, 0u);
+    uint64_t held = 0;
+    for (uint32_t c = 0; c < m; ++c) {
+        const uint64_t t = cptr[c + 1] - cptr[c];
+        if (held && held + t > MAXSIM_RANGE) {
+            ranges.push_back(c);
+            held = 0;
+        }
+        held += t;
+        if (held >= MAXSIM_RANGE) {
+            ranges.push_back(c + 1);
+            held = 0;
+        }
+    }
+    if (ranges.back() != m) ranges.push_back(m);
+}
+
+// n_records records more: record i has counts[i] >= 0 token rows of `dim` floats, all of them consecutive in `tokens`.  The token
+// array grows by doubling (its rows are copied on the device); a failed call leaves the store as it was.
+extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tokens, const uint64_t* counts, uint64_t n_records) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (n_records == 0) return LYNSE_OK;
+    if (!counts) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t add = 0;
+    for (uint64_t i = 0; i < n_records; ++i) add += counts[i];
+    if (add && !tokens) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    if (h->n + n_records >= (1ull << 32)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector records: a selection key carries a 32-bit row, n must be below 2^32");
+    LY_HIP(hipSetDevice(h->device));
+    const uint32_t D = h->dim, ld = h->ld;
+    const uint64_t total = h->total + add;
+    std::vector<uint64_t> cptr = h->cptr;
+    std::vector<uint32_t> crec = h->crec, ranges;
+    for (uint64_t i = 0; i < n_records; ++i)
+        if (counts[i]) {
+            cptr.push_back(cptr.back() + counts[i]);
+            crec.push_back((uint32_t)(h->n + i));
+        }
+    maxsim_ranges(cptr, ranges);
+    // A call that fails below leaves the handle answering as before: a grown token block holds the old rows and the new ones land
+    // past them; the device tables go up into fresh buffers; everything is swapped in only once nothing can fail any more.
+    DevBuf<uint64_t> n_cptr;
+    DevBuf<uint32_t> n_crec, n_ranges;
+    if (add) {
+        if (total > h->tokens.cap / ld) {   // grow: the rows held move to the new block
+            DevBuf<float> grown;
+            LY_TRY(grown.alloc((size_t)std::max<uint64_t>(total, 2 * h->total) * ld));
+            if (h->total) LY_HIP(hipMemcpy(grown.p, h->tokens.p, (size_t)h->total * ld * 4, hipMemcpyDeviceToDevice));
+            LY_HIP(hipStreamSynchronize(nullptr));   // (the copy is ordered on the NULL stream: h2d_done)
+            h->tokens = std::move(grown);
+        }
+        h->stage.assign((size_t)add * ld, 0.0f);   // the rows at the device pitch, zero columns past the dimension
+        for (uint64_t t = 0; t < add; ++t) memcpy(h->stage.data() + (size_t)t * ld, tokens + (size_t)t * D, (size_t)D * 4);
+        LY_TRY(h2d_done(h->tokens.p + (size_t)h->total * ld, h->stage.data(), h->stage.size() * 4));
+        LY_TRY(n_cptr.alloc(cptr.size()));
+        LY_TRY(n_crec.alloc(crec.size()));
+        LY_TRY(n_ranges.alloc(ranges.size()));
+        LY_TRY(h2d_done(n_cptr.p, cptr.data(), cptr.size() * 8));
+        LY_TRY(h2d_done(n_crec.p, crec.data(), crec.size() * 4));
+        LY_TRY(h2d_done(n_ranges.p, ranges.data(), ranges.size() * 4));
+        h->d_cptr = std::move(n_cptr);
+        h->d_crec = std::move(n_crec);
+        h->d_ranges = std::move(n_ranges);
+    }
+    h->cptr.swap(cptr);
+    h->crec.swap(crec);
+    h->ranges.swap(ranges);
+    h->total = total;
+    h->n += n_records;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_counts(lynse_hip_multivec* h, uint64_t* out_records, uint64_t* out_tokens, uint64_t* out_ranges) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    if (out_records) *out_records = h->n;
+    if (out_tokens) *out_tokens = h->total;
+    if (out_ranges) *out_ranges = h->ranges.size() - 1;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_profile_enable(lynse_hip_multivec* h, int on) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    h->profiling = on != 0;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_profile_get(lynse_hip_multivec* h, lynse_hip_profile* out, int reset) {
+    if (!h || !out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    *out = h->prof;
+    if (reset) h->prof = lynse_hip_profile{};
+    return LYNSE_OK;
+}
+
+template <int NT>
+static int maxsim_launch(const MaxSimArgs& a, dim3 grid, uint32_t waves, size_t lds, hipStream_t st) {
+    LY_TRY(ensure_lds<k_maxsim_scan<NT>>(PoolRerank::LDS_MAX));
+    hipLaunchKernelGGL(k_maxsim_scan<NT>, grid, dim3(waves * 64u), lds, st, a);
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
+
+// nq queries, query i with q_ptr[i + 1] - q_ptr[i] token rows of `dim` floats in q_tokens: the best min(k, live) records of each
+// by (score descending, record row ascending) at stride k, out_counts[q] entries valid.  Live = has tokens and is in the mask.
+extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
+                                                    const uint64_t* bitset_words, uint64_t n_words, uint64_t* out_rows, float* out_scores,
+                                                    uint32_t* out_counts) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (nq == 0) return LYNSE_OK;
+    if (!q_tokens || !q_ptr || !out_counts || (k && (!out_rows || !out_scores))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (nq >= (1ull << 32)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "too many queries");
+    if (q_ptr[0] != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: q_ptr must start at 0");
+    uint32_t tq_max = 0;
+    for (uint64_t i = 0; i < nq; ++i) {
+        if (q_ptr[i + 1] <= q_ptr[i]) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
+        if (q_ptr[i + 1] - q_ptr[i] > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
+        tq_max = std::max(tq_max, (uint32_t)(q_ptr[i + 1] - q_ptr[i]));
+    }
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    LY_HIP(hipSetDevice(h->device));
+    const uint64_t m = h->crec.size(), n = h->n;
+    const uint32_t D = h->dim, ld = h->ld;
+    const uint64_t mask_words = bitset_words ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
+    uint64_t live = m;
+    if (bitset_words) {
+        live = 0;
+        for (uint64_t c = 0; c < m; ++c) {
+            const uint64_t r = h->crec[c];
+            live += (r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull);
+        }
+    }
+    if (m == 0 || k == 0 || live == 0) {
+        memset(out_counts, 0, nq * 4);
+        return LYNSE_OK;
+    }
+    uint32_t tiles = 0, waves = 0;
+    uint64_t lds = 0;
+    LY_TRY(lynse_hip_multivec_plan(D, tq_max, &tiles, &waves, &lds));
+    // workgroups a CU can hold by their LDS (the registers allow one wave per SIMD at 8 tiles, two or three below): the grid's width
+    const uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
+    const uint32_t N = (uint32_t)std::min<uint64_t>(k, live);
+    const uint64_t qc = ScoreCut::chunk(nq, m, N);
+    const bool sort_dev = N <= 16384;
+    if (sort_dev) {
+        LY_TRY(ensure_lds<k_pool_select<256>>(PoolRerank::LDS_MAX));
+        LY_TRY(ensure_lds<k_pool_select<1024>>(PoolRerank::LDS_MAX));
+    }
+    hipStream_t st = h->stream;
+    if (bitset_words) LY_TRY(h->mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+    LY_TRY(h->q.reserve((size_t)qc * tiles * 32u * ld));
+    LY_TRY(h->qdesc.reserve((size_t)qc * 2));
+    LY_TRY(h->rr.keys.reserve((size_t)qc * N));
+    LY_TRY(h->rr.pcnt.reserve((size_t)qc));
+    if (sort_dev) LY_TRY(h->rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
+    LY_TRY(h->cut.grow(qc, m));
+    // (the caller's words are queued only once nothing before the first launch can fail and return with the copy still pending)
+    if (mask_words) LY_HIP(hipMemcpyAsync(h->mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+    const bool timed = h->profiling, select = live > N;
+    if (timed) {
+        for (hipEvent_t& e : h->ev)
+            if (!e) LY_HIP(hipEventCreate(&e));
+        h->prof.searches += 1;
+    }
+    const uint32_t n_ranges = (uint32_t)(h->ranges.size() - 1);
+    auto chunks = [&]() -> int {
+    for (uint64_t q0 = 0; q0 < nq; q0 += qc) {
+        const uint32_t nqc = (uint32_t)std::min<uint64_t>(qc, nq - q0);
+        // the chunk's queries at the device pitch: zero columns past the dimension, zero rows up to whole tiles of 32
+        h->hdesc.resize((size_t)nqc * 2);
+        size_t floats = 0;
+        for (uint32_t i = 0; i < nqc; ++i) {
+            const uint32_t tq = (uint32_t)(q_ptr[q0 + i + 1] - q_ptr[q0 + i]);
+            h->hdesc[2 * i] = floats;
+            h->hdesc[2 * i + 1] = tq;
+            floats += (size_t)((tq + 31u) / 32u * 32u) * ld;
+        }
+        h->hq.assign(floats, 0.0f);
+        for (uint32_t i = 0; i < nqc; ++i)
+            for (uint64_t t = q_ptr[q0 + i]; t < q_ptr[q0 + i + 1]; ++t)
+                memcpy(h->hq.data() + h->hdesc[2 * i] + (size_t)(t - q_ptr[q0 + i]) * ld, q_tokens + (size_t)t * D, (size_t)D * 4);
+        LY_HIP(hipMemcpyAsync(h->q.p, h->hq.data(), floats * 4, hipMemcpyHostToDevice, st));
+        LY_HIP(hipMemcpyAsync(h->qdesc.p, h->hdesc.data(), h->hdesc.size() * 8, hipMemcpyHostToDevice, st));
+        const MaxSimArgs a{h->tokens.p, ld, h->d_cptr.p, h->d_crec.p, m, h->d_ranges.p, n_ranges, h->q.p, h->qdesc.p,
+                           bitset_words ? h->mask.p : nullptr, mask_words, h->cut.S.p};
+        const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
+        if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
+        switch (tiles) {
+        case 1: LY_TRY(maxsim_launch<1>(a, grid, waves, lds, st)); break;
+        case 2: LY_TRY(maxsim_launch<2>(a, grid, waves, lds, st)); break;
+        case 4: LY_TRY(maxsim_launch<4>(a, grid, waves, lds, st)); break;
+        default: LY_TRY(maxsim_launch<8>(a, grid, waves, lds, st)); break;
+        }
+        if (timed) {
+            LY_HIP(hipEventRecord(h->ev[1], st));
+            h->prof.scan_launches += 1;
+            h->prof.scan_rows += h->total * nqc;
+            h->prof.scan_bytes += (h->total * ld * 4 + (m + 1) * 8) * nqc;
+        }
+        // more live records than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
+        h->cut.sel0.assign(nqc, select ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
+        LY_TRY(h->cut.cut<true>(nqc, m, N, select, h->rr.keys.p, h->rr.pcnt.p, st));
+        const size_t o_dist = (size_t)nqc * N * 8, o_cnt = (size_t)nqc * N * 12, o_all = o_cnt + (size_t)nqc * 4;
+        if (sort_dev) {   // sorted in LDS (k_pool_select), rows | scores | counts of the chunk back in one copy
+            uint32_t p2 = 2;
+            while (p2 < N) p2 <<= 1;
+            uint8_t* ob = reinterpret_cast<uint8_t*>(h->rr.out.p);
+            PoolRerankArgs x{};
+            x.pool_cnt = h->rr.pcnt.p;
+            x.pool_ld = N;
+            x.p2 = p2;
+            x.metric = M_IP;
+            x.k = N;
+            x.out_k = N;
+            x.out_rows = h->rr.out.p;
+            x.out_dists = reinterpret_cast<float*>(ob + o_dist);
+            x.out_counts = reinterpret_cast<uint32_t*>(ob + o_cnt);
+            x.keys_out = h->rr.keys.p;
+            if (p2 >= 2048) hipLaunchKernelGGL(k_pool_select<1024>, dim3(nqc), dim3(1024), (size_t)p2 * 8, st, x);
+            else hipLaunchKernelGGL(k_pool_select<256>, dim3(nqc), dim3(256), (size_t)p2 * 8, st, x);
+            LY_HIP(hipGetLastError());
+        }
+        if (timed) {
+            LY_HIP(hipEventRecord(h->ev[2], st));
+            LY_HIP(hipEventSynchronize(h->ev[2]));
+            float scan_ms = 0.f, all_ms = 0.f;
+            LY_HIP(hipEventElapsedTime(&scan_ms, h->ev[0], h->ev[1]));
+            LY_HIP(hipEventElapsedTime(&all_ms, h->ev[0], h->ev[2]));
+            h->prof.scan_us += (double)scan_ms * 1000.0;
+            h->prof.total_us += (double)all_ms * 1000.0;
+        }
+        if (sort_dev) {
+            h->h_out.resize((o_all + 7) / 8);
+            LY_HIP(hipMemcpyAsync(h->h_out.data(), h->rr.out.p, o_all, hipMemcpyDeviceToHost, st));
+            LY_TRY(stream_wait(st));
+            const uint8_t* hb = reinterpret_cast<const uint8_t*>(h->h_out.data());
+            for (uint32_t i = 0; i < nqc; ++i) {
+                memcpy(out_rows + (q0 + i) * k, hb + (size_t)i * N * 8, (size_t)N * 8);
+                memcpy(out_scores + (q0 + i) * k, hb + o_dist + (size_t)i * N * 4, (size_t)N * 4);
+                out_counts[q0 + i] = N;
+            }
+        } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host
+            h->keys.resize((size_t)nqc * N);
+            LY_HIP(hipMemcpyAsync(h->keys.data(), h->rr.keys.p, h->keys.size() * 8, hipMemcpyDeviceToHost, st));
+            LY_TRY(stream_wait(st));
+            for (uint32_t i = 0; i < nqc; ++i)
+                out_counts[q0 + i] = select_pool_keys(h->keys.data() + (size_t)i * N, N, N, N, false, out_rows + (q0 + i) * k, out_scores + (q0 + i) * k);
+        }
+        // the kernel numbers the records that have tokens: back to record rows (ascending with them, so the order of ties holds)
+        for (uint32_t i = 0; i < nqc; ++i)
+            for (uint32_t j = 0; j < N; ++j) out_rows[(q0 + i) * k + j] = h->crec[(size_t)out_rows[(q0 + i) * k + j]];
+    }
+    return LYNSE_OK;
+    };
+    const int rc = chunks();
+    if (rc != LYNSE_OK && mask_words) (void)hipStreamSynchronize(st);   // (the copy of the caller's words must not outlive the call)
+    return rc;
+}
+
+extern "C" int lynse_hip_multivec_search_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
+                                             uint64_t* out_rows, float* out_scores, uint32_t* out_counts) {
+    return lynse_hip_multivec_search_bitset_f32(h, q_tokens, q_ptr, nq, k, nullptr, 0, out_rows, out_scores, out_counts);
+}
