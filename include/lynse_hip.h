@@ -1090,8 +1090,28 @@ int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, in
  *     and goes in query chunks that keep the score matrix at or under 512 MiB.  Queries of one call may differ in their token count.
  *  9. Profile: scan_launches, scan_us, scan_rows = token rows streamed (all of them, once per query), scan_bytes likewise,
  *     total_us = first launch to last launch of a chunk.
- * Without a usable HIP device lynse_hip_multivec_create returns LYNSE_ERR_DEVICE: there is no CPU fallback. */
+ * Without a usable HIP device lynse_hip_multivec_create returns LYNSE_ERR_DEVICE: there is no CPU fallback.
+ *
+ * F16 TOKEN STORAGE (lynse_hip_multivec_create_dtype with dtype 1; index mode MULTIVEC-MAXSIM-IP-F16).  Token rows are halves,
+ * [total_tokens][ld] with the same ld, half the bytes; the scan is k_maxsim_h16 on v_mfma_f32_32x32x16_f16.  Rules 1, 2 and the LDS
+ * half of 7 read as follows for such a handle, rules 3 - 6, 8, 9 and 1 <= tokens of a query <= 256 stand as they are:
+ *  1'. Stored value.  p^ = the f32 value rounded to nearest even to IEEE binary16, overflow to +-inf as the conversion gives it; then
+ *      every |p^| < 2^-14 (an f16 subnormal) is stored as a zero of the same sign.  lynse_hip_multivec_append converts on the device;
+ *      lynse_hip_multivec_append_f16 takes raw halves as they are and applies the same flush.  The query gets the same treatment,
+ *      q^ = flush(f16(q)), on the device as its tiles are staged: ROUNDING THE QUERY TO F16 IS PART OF THIS CONTRACT (a hi/lo split
+ *      that keeps its f32 precision is out of scope).  No subnormal half ever reaches the matrix instruction.
+ *  2'. Score block.  s_ij = sum_k f32(q^_ik) * f32(p^_jk) accumulated in f32; every product is exact in f32 (11 + 11 significant
+ *      bits), the order of the sum is the hardware's and not part of the contract.
+ *  7'. The LDS holds the query's tiles only, as halves at a row pitch of 2 ld + 16 bytes, plus 512 B of flags: tiles * 32 * (2 ld + 16)
+ *      + 512 <= 160 KiB or LYNSE_ERR_UNSUPPORTED ("... do not fit in LDS").  That serves 256 query tokens up to dim_mv 288, 128 up to
+ *      512 and 64 up to 1024: every dim_mv in 1 .. 1024 can be created. */
 typedef struct lynse_hip_multivec lynse_hip_multivec;
+/* dtype: 0 = f32 (lynse_hip_multivec_create), 1 = f16; anything else LYNSE_ERR_INVALID_ARGUMENT */
+int lynse_hip_multivec_create_dtype(int device, uint32_t dim_mv, int dtype, lynse_hip_multivec **out);
+/* the plan of lynse_hip_multivec_plan by dtype, host only: dtype 0 is that rule, dtype 1 is rule 7' (waves: always 4) */
+int lynse_hip_multivec_plan_dtype(uint32_t dim_mv, uint32_t tq, int dtype, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
+/* lynse_hip_multivec_append for raw IEEE binary16 rows; valid on an f16 handle only (LYNSE_ERR_INVALID_ARGUMENT otherwise) */
+int lynse_hip_multivec_append_f16(lynse_hip_multivec *h, const uint16_t *tokens, const uint64_t *counts /* n_records */, uint64_t n_records);
 /* Rule 7 for a query of tq tokens at dim_mv, host only (no handle, no device): the query tiles held in LDS, the waves of a workgroup
  * and the LDS bytes; LYNSE_ERR_UNSUPPORTED with the message of rule 7 where the answer is a refusal.  Each output may be NULL. */
 int lynse_hip_multivec_plan(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);

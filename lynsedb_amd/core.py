@@ -1627,12 +1627,22 @@ class SparseIndex:
 # Multi-vector records: late interaction, score(Q, P) = sum_i max_j <q_i, p_j> (include/lynse_hip.h, MULTI-VECTOR SEARCH)
 # ---------------------------------------------------------------------------------------------
 MULTIVEC_INDEX_MODE = "MULTIVEC-MAXSIM-IP"
+MULTIVEC_INDEX_MODE_F16 = "MULTIVEC-MAXSIM-IP-F16"   # f16 token storage (include/lynse_hip.h, F16 TOKEN STORAGE)
 MULTIVEC_MAX_QUERY_TOKENS = 256   # include/lynse_hip.h, MULTI-VECTOR SEARCH rule 7
 MULTIVEC_MAX_DIM = 1024
 
 
-def _multivec_queries(queries, dim: Optional[int]) -> list:
-    """the query token arrays as (Tq, dim) f32, checked against rule 7 before any device is touched"""
+def _multivec_dtype(dtype) -> Optional[str]:
+    """None, or "f32" / "f16" for the spellings of `vector_dtype_name`"""
+    return None if dtype is None else {"float32": "f32", "float16": "f16"}[vector_dtype_name(dtype)]
+
+
+def _multivec_mode(dtype: Optional[str]) -> str:
+    return MULTIVEC_INDEX_MODE_F16 if dtype == "f16" else MULTIVEC_INDEX_MODE
+
+
+def _multivec_queries(queries, dim: Optional[int], dtype: Optional[str] = None) -> list:
+    """the query token arrays as (Tq, dim) f32, checked against rule 7 (7' for an f16 store) before any device is touched"""
     out = []
     for q in queries:
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -1646,18 +1656,19 @@ def _multivec_queries(queries, dim: Optional[int]) -> list:
             raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
         if dim is not None and q.shape[1] != dim:
             raise RuntimeError(f"Dimension mismatch: expected {dim}, got {q.shape[1]}")
-        check(lib.lynse_hip_multivec_plan(q.shape[1], q.shape[0], None, None, None))   # the LDS half of rule 7 (host only)
+        check(lib.lynse_hip_multivec_plan_dtype(q.shape[1], q.shape[0], int(dtype == "f16"), None, None, None))   # the LDS half of rule 7 (host only)
         out.append(q)
     return out
 
 
 class MultiVectorIndex:
-    """The token rows of multi-vector records in HBM, append-only, and their exact MaxSim scan (k_maxsim_scan)."""
+    """The token rows of multi-vector records in HBM, append-only, and their exact MaxSim scan: f32 rows (k_maxsim_scan) or, with
+    dtype="f16", half the bytes (k_maxsim_h16; tokens and queries rounded to f16, subnormals flushed)."""
 
-    def __init__(self, dim: int, device: Optional[int] = None):
-        self._h, self._dim = C.c_void_p(), int(dim)
+    def __init__(self, dim: int, device: Optional[int] = None, dtype: str = "f32"):
+        self._h, self._dim, self.dtype = C.c_void_p(), int(dim), _multivec_dtype(dtype)
         dev = default_device() if device is None else int(device)
-        check(lib.lynse_hip_multivec_create(dev, self._dim, C.byref(self._h)))
+        check(lib.lynse_hip_multivec_create_dtype(dev, self._dim, int(self.dtype == "f16"), C.byref(self._h)))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -1665,11 +1676,15 @@ class MultiVectorIndex:
             lib.lynse_hip_multivec_destroy(h)
 
     def append(self, token_sets) -> None:
-        """records more, one (T_r, dim) f32 array each, T_r >= 0"""
+        """records more, one (T_r, dim) f32 array each, T_r >= 0; an f16 store also takes np.float16 arrays, stored as they are"""
         counts = np.array([t.shape[0] for t in token_sets], dtype=np.uint64)
         full = [t for t in token_sets if t.shape[0]]
+        raw = self.dtype == "f16" and bool(full) and all(t.dtype == np.float16 for t in full)
+        if not raw:   # (f16 -> f32 is exact, and back: mixed input stores the same halves)
+            full = [np.asarray(t, dtype=np.float32) for t in full]
         tokens = np.ascontiguousarray(np.concatenate(full)) if full else np.zeros((0, self._dim), np.float32)
-        check(lib.lynse_hip_multivec_append(self._h, _ptr(tokens) if tokens.size else None, _ptr(counts), counts.size))
+        append = lib.lynse_hip_multivec_append_f16 if raw else lib.lynse_hip_multivec_append
+        check(append(self._h, _ptr(tokens) if tokens.size else None, _ptr(counts), counts.size))
 
     def counts(self) -> dict:
         r, t, g = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -1679,7 +1694,7 @@ class MultiVectorIndex:
     def search_batch_arrays(self, queries, k: int, words=None):
         """-> (rows u64[nq, k], scores f32[nq, k], counts u32[nq]) by (score descending, record row ascending); `words` are BitSet
         words over record rows (None = every record)."""
-        queries = _multivec_queries(queries, self._dim)
+        queries = _multivec_queries(queries, self._dim, self.dtype)
         nq, k = len(queries), int(k)
         if k < 0:
             raise ValueError("k must not be negative")
@@ -3157,21 +3172,29 @@ class Collection:
     # -- multi-vector records (include/lynse_hip.h, MULTI-VECTOR SEARCH) ------------
     def _mv_reset(self) -> None:
         self._mv_dim = None             # dim_mv, fixed by the first add_multi_vectors
+        self._mv_dtype = None           # "f32" | "f16", fixed by it too
         self._mv_ids: list = []         # record row -> user id, in the order added (the store is append-only)
         self._mv_seen: set = set()
         self._mv_dead: set = set()      # ids that `compact` removed from the collection: their records are never returned again
         self._mv_pending: list = []     # token sets not yet on the device: uploaded by the next search
         self._mv_index = None           # MultiVectorIndex, created by the first search
 
-    def add_multi_vectors(self, ids: Sequence[int], token_sets) -> None:
+    def add_multi_vectors(self, ids: Sequence[int], token_sets, dtype: Optional[str] = None) -> None:
         """Attaches a set of token vectors to each id (ids that exist, flushed or pending, as for add_sparse_vectors): token_sets[r] is
         a (T_r, dim_mv) f32 array, T_r >= 0 — a record without tokens is never returned.  dim_mv is fixed by the first call and is
         independent of the collection's own dimension; the contract allows up to 1024, this build answers up to 416 (beyond, a
         block of token rows does not fit the LDS next to one query tile) and refuses a wider first call with NotImplementedError.
         The store is append-only: an id added twice is refused, a refused call changes nothing, and an id that `compact` removed
-        from the collection stays masked out for good.  The device copy follows at the next multi-vector search."""
+        from the collection stays masked out for good.  The device copy follows at the next multi-vector search.
+        `dtype` ("f32"/"float32" or "f16"/"float16") is fixed by the first call like dim_mv: None means f32 then and the store's own
+        afterwards, the other one is refused.  An f16 store holds half the bytes: f32 token arrays are rounded to f16 (nearest even,
+        subnormals to zero), np.float16 arrays are taken as they are, queries are rounded the same way, every dim_mv up to 1024 is
+        accepted, and the mode reported is MULTIVEC-MAXSIM-IP-F16."""
         ids = [int(i) for i in ids]
-        sets = [np.asarray(t, dtype=np.float32) for t in token_sets]
+        want = _multivec_dtype(dtype) or self._mv_dtype or "f32"
+        if self._mv_dtype is not None and want != self._mv_dtype:
+            raise RuntimeError(f"Invalid argument: the multi-vector store holds {self._mv_dtype} tokens, dtype {want} was asked for")
+        sets = [t if want == "f16" and isinstance(t, np.ndarray) and t.dtype == np.float16 else np.asarray(t, dtype=np.float32) for t in token_sets]
         if len(ids) != len(sets):
             raise RuntimeError(f"Invalid argument: ids length ({len(ids)}) must match token set count ({len(sets)})")
         dim = self._mv_dim
@@ -3184,7 +3207,7 @@ class Collection:
             raise ValueError("the first add_multi_vectors call must give a 2-D token set: it fixes dim_mv")
         if dim < 1 or dim > MULTIVEC_MAX_DIM:
             raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
-        check(lib.lynse_hip_multivec_plan(dim, 1, None, None, None))   # above 416 not even one query tile fits the LDS: refused here
+        check(lib.lynse_hip_multivec_plan_dtype(dim, 1, int(want == "f16"), None, None, None))   # f32 above 416: not even one query tile fits the LDS, refused here
         sets = [np.ascontiguousarray(t.reshape(-1, dim) if t.size == 0 else t) for t in sets]
         for t in sets:
             if t.shape[1] != dim:
@@ -3196,7 +3219,7 @@ class Collection:
             seen.add(i)
             if not ok:
                 raise RuntimeError(f"Invalid argument: cannot add multi-vector for unknown id {i}")
-        self._mv_dim = dim
+        self._mv_dim, self._mv_dtype = dim, want
         self._mv_ids.extend(ids)
         self._mv_seen |= seen
         self._mv_pending.extend(sets)
@@ -3204,9 +3227,13 @@ class Collection:
     def multi_vector_len(self) -> int:
         return len(self._mv_ids)
 
+    def multi_vector_dtype(self) -> Optional[str]:
+        """"f32" or "f16" once the first add_multi_vectors has fixed it, None before"""
+        return self._mv_dtype
+
     def _mv_upload(self) -> None:
         if self._mv_index is None:
-            self._mv_index = MultiVectorIndex(self._mv_dim, self._device)
+            self._mv_index = MultiVectorIndex(self._mv_dim, self._device, self._mv_dtype)
         if self._mv_pending:
             self._mv_index.append(self._mv_pending)
             self._mv_pending = []
@@ -3234,15 +3261,16 @@ class Collection:
         k = 10 if k is None else int(k)
         if k < 0:
             raise OverflowError("can't convert negative int to unsigned")
-        queries = _multivec_queries(queries, self._mv_dim)
+        queries = _multivec_queries(queries, self._mv_dim, self._mv_dtype)
         subset = self._where_subset(where, subset)
-        empty = lambda: SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), MULTIVEC_INDEX_MODE, self._mv_dim or 0, k)   # noqa: E731
+        mode = _multivec_mode(self._mv_dtype)
+        empty = lambda: SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), mode, self._mv_dim or 0, k)   # noqa: E731
         if k == 0 or not self._mv_ids or not queries:   # the device is not touched
             return [empty() for _ in queries]
         self._mv_upload()
         rows, scores, counts = self._mv_index.search_batch_arrays(queries, k, self._mv_words(subset))
         mv_ids = np.asarray(self._mv_ids, dtype=np.int64)
-        return [SearchResult(mv_ids[rows[i, :int(c)].astype(np.int64)], scores[i, :int(c)].copy(), MULTIVEC_INDEX_MODE, self._mv_dim, k)
+        return [SearchResult(mv_ids[rows[i, :int(c)].astype(np.int64)], scores[i, :int(c)].copy(), mode, self._mv_dim, k)
                 for i, c in enumerate(counts)]
 
     def search_multi_vector(self, query_tokens, k: Optional[int] = None, where=None, subset=None) -> SearchResult:

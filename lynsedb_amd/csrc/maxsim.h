@@ -36,8 +36,9 @@ __host__ __device__ inline size_t maxsim_lds_bytes(uint32_t ld, uint32_t tiles, 
     return ((size_t)tiles * blk + (size_t)waves * (2u * blk + MAXSIM_BLOCK)) * 4u;
 }
 
-struct MaxSimArgs {
-    const float* tokens;      // [total tokens][ld], columns dim .. ld - 1 are zero
+template <typename T>
+struct MaxSimArgsT {
+    const T* tokens;          // [total tokens][ld], columns dim .. ld - 1 are zero
     uint32_t ld;
     const uint64_t* cptr;     // m + 1 token offsets of the records that have tokens
     const uint32_t* crec;     // m: their record rows (the mask is over record rows)
@@ -50,6 +51,8 @@ struct MaxSimArgs {
     uint64_t mask_words;
     uint32_t* S;              // [nq][m]
 };
+using MaxSimArgs = MaxSimArgsT<float>;          // k_maxsim_scan
+using MaxSimH16Args = MaxSimArgsT<_Float16>;    // k_maxsim_h16: the token rows are halves, the queries still f32 (converted as they are staged)
 
 // no packed f32 arithmetic in the scan: rule 4 adds one row maximum at a time (the host pass does not know the feature)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -226,6 +229,259 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_s
             }
             rc0 += n_adv;
             maxsim_wave_sync();   // the next block is stored; this one may be overwritten by the block after it
+        }
+    }
+}
+
+// ---- f16 token storage (include/lynse_hip.h, MULTI-VECTOR SEARCH, f16 addendum) ------------------------------------
+//   k_maxsim_h16    the same split (one wave, one range of whole records, blocks of 32 token rows) and the same epilogue on
+//                   v_mfma_f32_32x32x16_f16.  The 16 bytes a lane gives that instruction for B are 8 consecutive halves of ONE token
+//                   row, so lane (j = lane % 32, h = lane / 32) loads its fragments of row j from HBM straight into the operand
+//                   registers: the token stream never sees the LDS, which holds the query tiles (halves, converted as they are
+//                   staged) and 32 boundary flags per wave.  Of each 32 columns of a row half h owns the 16 at 16 h: k-steps 2 p and
+//                   2 p + 1 take its halves 0..7 and 8..15, so a lane reads 32 contiguous bytes and a row 64 per pair of steps; the
+//                   query fragments follow the same assignment (the order of a sum is not part of the contract).  A chunk of 128
+//                   columns (64 at 8 query tiles) is 8 fragments = 32 VGPRs; the chunks of the stream (block after block) go through a ring of RING such
+//                   buffers, loaded RING - 1 chunks ahead of the MFMAs that read them.
+
+// LDS row pitch of a query tile in BYTES: 2 ld + 16 = 16 s with s = ld / 8 + 1 odd (ld / 8 is a multiple of 4), so by the argument at
+// maxsim_pitch the ds_read_b128 fragment reads (16 lanes: one 16-B piece of 16 consecutive rows) are conflict-free.
+__host__ __device__ inline uint32_t maxsim_h16_pitch(uint32_t ld) { return 2u * ld + 16u; }
+// LDS bytes: the query tiles | the 32 boundary flags of each of the (always 4) waves
+__host__ __device__ inline size_t maxsim_h16_lds_bytes(uint32_t ld, uint32_t tiles) {
+    return (size_t)tiles * MAXSIM_BLOCK * maxsim_h16_pitch(ld) + (size_t)MAXSIM_MAX_WAVES * MAXSIM_BLOCK * 4u;
+}
+
+// Rule 1 of the addendum: round to nearest even to binary16, then a subnormal result becomes a zero of its sign.
+__host__ __device__ inline uint16_t maxsim_h16_flush(uint16_t b) { return (b & 0x7c00u) ? b : (uint16_t)(b & 0x8000u); }
+__device__ __forceinline__ uint32_t maxsim_h16_of(float x) { return maxsim_h16_flush(__builtin_bit_cast(uint16_t, (_Float16)x)); }
+
+// The store's rows at the device pitch from what `append` was given: SRC = float (converted) or uint16_t (raw halves), [rows][dim]
+// -> [rows][ld] with rule 1 applied and zero columns past the dimension.  One thread per stored half.
+template <typename SRC>
+__global__ void __launch_bounds__(256) k_maxsim_store_h16(const SRC* __restrict__ src, uint16_t* __restrict__ dst, uint64_t rows, uint32_t dim, uint32_t ld) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= rows * ld) return;
+    const uint64_t r = i / ld;
+    const uint32_t c = (uint32_t)(i - r * ld);
+    uint16_t v = 0;
+    if (c < dim) {
+        if constexpr (sizeof(SRC) == 4) v = (uint16_t)maxsim_h16_of(src[r * dim + c]);
+        else v = maxsim_h16_flush(src[r * dim + c]);
+    }
+    dst[i] = v;
+}
+
+// One chunk of a block into a ring buffer: lane (col, half) takes, of each of the chunk's NP column groups of 32 that exist, the 32
+// bytes at halves 16 half .. 16 half + 15 of token row t_first + col.  Rows at or past `t_end` (the end of the wave's range, or a
+// block past its last) are zero, as are the groups past the row pitch: nothing outside the range is read.
+template <int NP>
+__device__ __forceinline__ void maxsim_h16_load(const MaxSimH16Args& a, uint64_t t_first, uint64_t t_end, uint32_t kc, uint32_t col, uint32_t half, half8 (&f)[2 * NP]) {
+    const bool in = t_first + col < t_end;
+    const _Float16* src = a.tokens + (size_t)(t_first + col) * a.ld + kc + half * 16u;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        f[2 * p] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        f[2 * p + 1] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (in && kc + (uint32_t)p * 32u < a.ld) {
+            f[2 * p] = *reinterpret_cast<const half8*>(src + p * 32);
+            f[2 * p + 1] = *reinterpret_cast<const half8*>(src + p * 32 + 8);
+        }
+    }
+}
+
+// the record boundaries of a block, wave-uniform
+struct MaxSimBounds {
+    uint32_t starts;     // bit j = a record begins at column j (1 <= j <= 31)
+    uint32_t endmask;    // bit j = a record ends at column j
+    uint32_t n_adv;      // records that end in the block
+    bool open_next;      // the last record runs on into the next block
+};
+// rec_end: lane l < 32 holds the end of record rc0 + l (~0 past the range); at most 32 of them fall into (tb, tb + 32]
+__device__ __forceinline__ MaxSimBounds maxsim_h16_bounds(uint64_t rec_end, uint64_t tb, bool more, uint32_t lane, uint32_t col, uint32_t* flag_l) {
+    const uint64_t rel64 = rec_end - tb;   // >= 1; ~0 - tb stays huge
+    const uint32_t rel = rel64 > 64u ? 64u : (uint32_t)rel64;
+    if (lane < 32u) flag_l[lane] = 0u;
+    maxsim_wave_sync();
+    if (lane < 32u && rel < 32u) flag_l[rel] = 1u;   // (the ends ascend strictly: one lane per flag)
+    maxsim_wave_sync();
+    MaxSimBounds bd;
+    bd.starts = (uint32_t)__ballot(flag_l[col] != 0u);
+    const bool end32 = __ballot(lane < 32u && rel == 32u) != 0ull;   // a record ends with the block's last column
+    bd.n_adv = (uint32_t)__popcll(__ballot(lane < 32u && rel <= 32u));
+    bd.endmask = (bd.starts >> 1) | (end32 ? 0x80000000u : 0u);
+    bd.open_next = more && !end32;
+    maxsim_wave_sync();   // (the flags are read: the next block may clear them)
+    return bd;
+}
+
+// Rules 3 and 4 for one query tile of a block, as in k_maxsim_scan (the 32 x 32 accumulator of v_mfma_f32_32x32x16_f16 has the lane
+// and register layout of v_mfma_f32_32x32x2_f32): columns past the range score -inf, the running record's maxima join at column 0,
+// a segmented inclusive max over the 32 column lanes of each half, the carry out of column 31, and in the lanes of half 0 the sum of
+// the row maxima in query-token order, `s` running on from tile to tile.
+__device__ __forceinline__ LY_MAXSIM_FN void maxsim_h16_fold(const f32x16& acc, float (&carry)[16], const MaxSimBounds& bd, uint32_t ok_d, bool col_in,
+                                                             uint32_t lane, uint32_t col, uint32_t half, uint32_t t, uint32_t tq, float& s) {
+    const float NINF = -__builtin_huge_valf();
+    float x[16], o[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        x[v] = col_in ? acc[v] : NINF;
+        if (col == 0u) x[v] = fmaxf(x[v], carry[v]);
+    }
+    // fmaxf skips a NaN (rule 3), so only a record whose every s_ij is NaN still holds one at its last column: the fold makes it -inf
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const bool ok = (ok_d >> i) & 1u;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const float y = maxsim_from_lane(x[v], lane - (1u << i));
+            x[v] = ok ? fmaxf(x[v], y) : x[v];
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        x[v] = x[v] != x[v] ? NINF : x[v];
+        const float c = maxsim_from_lane(x[v], half * 32u + 31u);
+        carry[v] = bd.open_next ? c : NINF;
+        o[v] = maxsim_from_lane(x[v], lane ^ 32u);
+    }
+    // accumulator register v of half h is row 8 (v / 4) + 4 h + v % 4 of the tile
+#pragma unroll
+    for (int g = 0; g < 8; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t row = t * 32u + 4u * g + e;
+            const int v = (g >> 1) * 4 + e;
+            const float mv = (g & 1) ? o[v] : x[v];
+            if (row == 0u) s = mv;
+            else if (row < tq) s = s + mv;
+        }
+}
+
+// NT = query tiles of 32 rows the LDS holds (1, 2, 4 or 8); a query of fewer tiles skips the rest.  grid.x strides over the ranges,
+// grid.y is the query; blockDim.x / 64 waves.  RING - 1 = the chunks a load runs ahead: two while the accumulators and carried maxima
+// of the tiles leave the registers for a third buffer, one from 4 tiles on.
+template <int NT>
+__global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_h16(MaxSimH16Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm_maxsim_h16[];
+    constexpr int RING = NT <= 2 ? 3 : 2;
+    constexpr int NP = NT == 8 ? 2 : 4;   // column groups of 32 in a chunk: 128 columns, 64 where 8 tiles' accumulators and maxima fill the registers
+    constexpr uint32_t KC = 32u * NP;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = lane & 31u, half = lane >> 5;
+    const uint32_t wave = maxsim_uniform(tid >> 6), waves = blockDim.x >> 6;
+    const uint32_t K = a.ld, PB = maxsim_h16_pitch(K), nch = (K + KC - 1u) / KC;
+    const uint32_t q = blockIdx.y;
+    const uint64_t q_off = a.qdesc[2u * q];
+    const uint32_t tq = (uint32_t)a.qdesc[2u * q + 1u], tq_rows = (tq + 31u) / 32u * 32u;
+    unsigned char* q_l = sm_maxsim_h16;
+    uint32_t* flag_l = reinterpret_cast<uint32_t*>(q_l + (size_t)NT * MAXSIM_BLOCK * PB) + wave * MAXSIM_BLOCK;
+    // the query tiles as halves (rule 1 on the way), zero rows past the query's own: 16-B pieces of 8 columns
+    const uint32_t c8n = K / 8u;
+    for (uint32_t p = tid; p < (uint32_t)NT * 32u * c8n; p += blockDim.x) {
+        const uint32_t r = p / c8n, c = p - r * c8n;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (r < tq_rows) {
+            const float* src = a.Q + q_off + (size_t)r * K + c * 8u;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+            v = u32x4{maxsim_h16_of(lo[0]) | (maxsim_h16_of(lo[1]) << 16), maxsim_h16_of(lo[2]) | (maxsim_h16_of(lo[3]) << 16),
+                      maxsim_h16_of(hi[0]) | (maxsim_h16_of(hi[1]) << 16), maxsim_h16_of(hi[2]) | (maxsim_h16_of(hi[3]) << 16)};
+        }
+        *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = v;
+    }
+    __syncthreads();   // the only workgroup barrier: from here on the waves run their own ranges
+    // this lane's query fragments: row `col` of a tile, the bytes of its halves 16 half .. of each column group
+    const unsigned char* qa = q_l + (size_t)col * PB + half * 32u;
+    // one tile: the fragments of the first chunk stay in registers for the whole kernel — up to 128 columns the loop reads no LDS
+    half8 qreg[8];
+    if constexpr (NT == 1) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            qreg[2 * p] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+            qreg[2 * p + 1] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+            if ((uint32_t)p * 32u < K) {
+                qreg[2 * p] = *reinterpret_cast<const half8*>(qa + p * 64);
+                qreg[2 * p + 1] = *reinterpret_cast<const half8*>(qa + p * 64 + 16);
+            }
+        }
+    }
+    const float NINF = -__builtin_huge_valf();
+    for (uint32_t r = blockIdx.x * waves + wave; r < a.n_ranges; r += gridDim.x * waves) {
+        const uint32_t ca = maxsim_uniform(a.ranges[r]), cb = maxsim_uniform(a.ranges[r + 1u]);
+        const uint64_t t0 = maxsim_uniform(a.cptr[ca]), t1 = maxsim_uniform(a.cptr[cb]);
+        const uint32_t nb = (uint32_t)((t1 - t0 + MAXSIM_BLOCK - 1u) / MAXSIM_BLOCK);
+        half8 buf[RING][2 * NP];
+        uint32_t lb = 0, lc = 0;   // the load cursor: block and chunk, RING - 1 chunks ahead of (b, c)
+#pragma unroll
+        for (int i = 0; i < RING - 1; ++i) {
+            maxsim_h16_load<NP>(a, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc * KC, col, half, buf[i]);
+            if (++lc == nch) lc = 0, ++lb;
+        }
+        uint32_t rc0 = ca;       // the record of the block's first token
+        float carry[NT][16];     // the row maxima of the record that runs on from the previous block (read at column 0 only)
+        f32x16 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) carry[t][v] = NINF;
+        uint64_t rec_end = ~0ull;
+        uint32_t b = 0, c = 0;
+        while (b < nb) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {
+                if (b < nb) {
+                    const uint64_t tb = t0 + (uint64_t)b * MAXSIM_BLOCK;
+                    if (c == 0u) {
+                        // the ends of the records from rc0 on, asked for BEFORE the chunk ahead: the epilogue's wait then leaves that one in flight
+                        rec_end = ~0ull;
+                        if (lane < 32u && (uint64_t)rc0 + 1u + lane <= cb) rec_end = a.cptr[rc0 + 1u + lane];
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) acc[t] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    }
+                    maxsim_h16_load<NP>(a, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc * KC, col, half, buf[(i + RING - 1) % RING]);
+                    if (++lc == nch) lc = 0, ++lb;
+                    const uint32_t kc = c * KC;
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        if (kc + (uint32_t)p * 32u >= K) continue;
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+#pragma unroll
+                            for (int t = 0; t < NT; ++t) {
+                                if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                                half8 av;
+                                if (NT == 1 && c == 0u) av = qreg[2 * p + e];
+                                else av = *reinterpret_cast<const half8*>(qa + (size_t)t * 32u * PB + (kc + (uint32_t)p * 32u) * 2u + e * 16);
+                                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, buf[i][2 * p + e], acc[t], 0, 0, 0);
+                            }
+                        }
+                    }
+                    if (c + 1u == nch) {   // the block's last chunk: rules 3 and 4, the scores of the records that end in it
+                        const MaxSimBounds bd = maxsim_h16_bounds(rec_end, tb, b + 1u < nb, lane, col, flag_l);
+                        uint32_t ok_d = 0u;   // bit i: the lane 2^i columns down is in the same record
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) {
+                            const uint32_t d = 1u << j;
+                            if (col >= d && ((bd.starts >> (col - d + 1u)) & ((1u << d) - 1u)) == 0u) ok_d |= 1u << j;
+                        }
+                        float s = 0.0f;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                            maxsim_h16_fold(acc[t], carry[t], bd, ok_d, tb + col < t1, lane, col, half, (uint32_t)t, tq, s);
+                        }
+                        if (half == 0u && ((bd.endmask >> col) & 1u)) {
+                            const uint32_t cr = rc0 + (uint32_t)__popc(bd.starts & ((2u << col) - 1u));
+                            const bool live = !a.mask || range_live(a.mask, a.mask_words, a.crec[cr]);
+                            a.S[(size_t)q * a.m + cr] = live ? score_ord(s, false) : RANGE_FAIL;
+                        }
+                        rc0 += bd.n_adv;
+                        c = 0u;
+                        ++b;
+                    } else {
+                        ++c;
+                    }
+                }
+            }
         }
     }
 }

@@ -9,6 +9,8 @@ struct lynse_hip_multivec {
     uint32_t num_cu = 256;
     hipStream_t stream = nullptr;
     uint32_t dim = 0, ld = 0;
+    int dtype = 0;                          // 0: f32 rows in `tokens`, k_maxsim_scan; 1: f16 rows in `tokens_h`, k_maxsim_h16 (same pitch in elements)
+    DevBuf<uint16_t> tokens_h;
     uint64_t n = 0, total = 0;              // records (those without tokens included), token rows
     // the records that have tokens, which are all the kernel sees: their token offsets, their record rows, and the wave ranges
     std::vector<uint64_t> cptr{0};
@@ -49,10 +51,33 @@ extern "C" int lynse_hip_multivec_plan(uint32_t dim, uint32_t tq, uint32_t* out_
     return LYNSE_OK;
 }
 
-extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_multivec** out) {
+// The plan by token dtype (0 = f32: the rule above).  f16 (the addendum): the LDS holds the query tiles as halves and 32 flags per
+// wave, no token block, so the waves are always 4 and every dimension up to 1024 serves a query of up to 64 tokens.
+extern "C" int lynse_hip_multivec_plan_dtype(uint32_t dim, uint32_t tq, int dtype, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    if (dtype == 0) return lynse_hip_multivec_plan(dim, tq, out_tiles, out_waves, out_lds_bytes);
+    if (dtype != 1) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dtype must be 0 (f32) or 1 (f16)");
+    if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
+    if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
+    if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
+    if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
+    uint32_t tiles = 1;
+    while (tiles * 32u < tq) tiles *= 2;
+    const size_t lds = maxsim_h16_lds_bytes(maxsim_ld(dim), tiles);
+    if (lds > PoolRerank::LDS_MAX)
+        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) of f16 tokens of dimension " +
+                                                    std::to_string(dim) + " do not fit in LDS");
+    if (out_tiles) *out_tiles = tiles;
+    if (out_waves) *out_waves = MAXSIM_MAX_WAVES;
+    if (out_lds_bytes) *out_lds_bytes = lds;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_multivec** out) { return lynse_hip_multivec_create_dtype(device, dim, 0, out); }
+
+extern "C" int lynse_hip_multivec_create_dtype(int device, uint32_t dim, int dtype, lynse_hip_multivec** out) {
     if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    LY_TRY(lynse_hip_multivec_plan(dim, 1, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
+    LY_TRY(lynse_hip_multivec_plan_dtype(dim, 1, dtype, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
     int ndev = 0;
     LY_TRY(lynse_hip_device_count(&ndev));
     if (ndev <= 0) return set_error(LYNSE_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
@@ -61,6 +86,7 @@ extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_mul
     auto* h = new lynse_hip_multivec();
     h->device = device;
     h->dim = dim;
+    h->dtype = dtype;
     h->ld = maxsim_ld(dim);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount;
@@ -108,8 +134,10 @@ static void maxsim_ranges(const std::vector<uint64_t>& cptr, std::vector<uint32_
 
 // n_records records more: record i has counts[i] >= 0 token rows of `dim` floats, all of them consecutive in `tokens`.  The token
 // array grows by doubling (its rows are copied on the device); a failed call leaves the store as it was.
-extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tokens, const uint64_t* counts, uint64_t n_records) {
+// `tokens` are f32, or raw halves for an f16 handle (raw_h16): an f16 handle takes either and stores rule 1's image of them.
+static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16, const uint64_t* counts, uint64_t n_records) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (raw_h16 && h->dtype != 1) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector append_f16 is valid on an f16 handle only");
     if (n_records == 0) return LYNSE_OK;
     if (!counts) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     uint64_t add = 0;
@@ -132,7 +160,31 @@ extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tok
     // past them; the device tables go up into fresh buffers; everything is swapped in only once nothing can fail any more.
     DevBuf<uint64_t> n_cptr;
     DevBuf<uint32_t> n_crec, n_ranges;
-    if (add) {
+    if (add && h->dtype == 1) {
+        if (total > h->tokens_h.cap / ld) {   // grow: the rows held move to the new block
+            DevBuf<uint16_t> grown;
+            LY_TRY(grown.alloc((size_t)std::max<uint64_t>(total, 2 * h->total) * ld));
+            if (h->total) LY_HIP(hipMemcpy(grown.p, h->tokens_h.p, (size_t)h->total * ld * 2, hipMemcpyDeviceToDevice));
+            LY_HIP(hipStreamSynchronize(nullptr));
+            h->tokens_h = std::move(grown);
+        }
+        // the rows as given go up once; the device writes them at the store's pitch (k_maxsim_store_h16: conversion, flush, zero columns)
+        const size_t esz = raw_h16 ? 2 : 4;
+        DevBuf<uint8_t> raw;
+        LY_TRY(raw.alloc((size_t)add * D * esz));
+        LY_TRY(h2d_done(raw.p, tokens, (size_t)add * D * esz));
+        uint16_t* dst = h->tokens_h.p + (size_t)h->total * ld;
+        const uint64_t step = (1ull << 30) / ld;   // rows of a launch: its grid stays below 2^22 workgroups
+        for (uint64_t r0 = 0; r0 < add; r0 += step) {
+            const uint64_t rows = std::min<uint64_t>(step, add - r0);
+            const dim3 grid((uint32_t)((rows * ld + 255) / 256));
+            if (raw_h16) hipLaunchKernelGGL(k_maxsim_store_h16<uint16_t>, grid, dim3(256), 0, nullptr, reinterpret_cast<const uint16_t*>(raw.p) + (size_t)r0 * D, dst + (size_t)r0 * ld, rows, D, ld);
+            else hipLaunchKernelGGL(k_maxsim_store_h16<float>, grid, dim3(256), 0, nullptr, reinterpret_cast<const float*>(raw.p) + (size_t)r0 * D, dst + (size_t)r0 * ld, rows, D, ld);
+            LY_HIP(hipGetLastError());
+        }
+        LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
+    }
+    if (add && h->dtype == 0) {
         if (total > h->tokens.cap / ld) {   // grow: the rows held move to the new block
             DevBuf<float> grown;
             LY_TRY(grown.alloc((size_t)std::max<uint64_t>(total, 2 * h->total) * ld));
@@ -141,8 +193,10 @@ extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tok
             h->tokens = std::move(grown);
         }
         h->stage.assign((size_t)add * ld, 0.0f);   // the rows at the device pitch, zero columns past the dimension
-        for (uint64_t t = 0; t < add; ++t) memcpy(h->stage.data() + (size_t)t * ld, tokens + (size_t)t * D, (size_t)D * 4);
+        for (uint64_t t = 0; t < add; ++t) memcpy(h->stage.data() + (size_t)t * ld, static_cast<const float*>(tokens) + (size_t)t * D, (size_t)D * 4);
         LY_TRY(h2d_done(h->tokens.p + (size_t)h->total * ld, h->stage.data(), h->stage.size() * 4));
+    }
+    if (add) {
         LY_TRY(n_cptr.alloc(cptr.size()));
         LY_TRY(n_crec.alloc(crec.size()));
         LY_TRY(n_ranges.alloc(ranges.size()));
@@ -159,6 +213,14 @@ extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tok
     h->total = total;
     h->n += n_records;
     return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_append(lynse_hip_multivec* h, const float* tokens, const uint64_t* counts, uint64_t n_records) {
+    return maxsim_append(h, tokens, false, counts, n_records);
+}
+
+extern "C" int lynse_hip_multivec_append_f16(lynse_hip_multivec* h, const uint16_t* tokens, const uint64_t* counts, uint64_t n_records) {
+    return maxsim_append(h, tokens, true, counts, n_records);
 }
 
 extern "C" int lynse_hip_multivec_counts(lynse_hip_multivec* h, uint64_t* out_records, uint64_t* out_tokens, uint64_t* out_ranges) {
@@ -193,6 +255,13 @@ static int maxsim_launch(const MaxSimArgs& a, dim3 grid, uint32_t waves, size_t 
     return LYNSE_OK;
 }
 
+template <int NT>
+static int maxsim_h16_launch(const MaxSimH16Args& a, dim3 grid, size_t lds, hipStream_t st) {
+    LY_TRY(ensure_lds<k_maxsim_h16<NT>>(PoolRerank::LDS_MAX));
+    hipLaunchKernelGGL(k_maxsim_h16<NT>, grid, dim3(MAXSIM_MAX_WAVES * 64u), lds, st, a);
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
 // nq queries, query i with q_ptr[i + 1] - q_ptr[i] token rows of `dim` floats in q_tokens: the best min(k, live) records of each
 // by (score descending, record row ascending) at stride k, out_counts[q] entries valid.  Live = has tokens and is in the mask.
 extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
@@ -228,9 +297,12 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
     }
     uint32_t tiles = 0, waves = 0;
     uint64_t lds = 0;
-    LY_TRY(lynse_hip_multivec_plan(D, tq_max, &tiles, &waves, &lds));
+    const bool h16 = h->dtype == 1;
+    LY_TRY(lynse_hip_multivec_plan_dtype(D, tq_max, h->dtype, &tiles, &waves, &lds));
     // workgroups a CU can hold by their LDS (the registers allow one wave per SIMD at 8 tiles, two or three below): the grid's width
-    const uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
+    uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
+    // (k_maxsim_h16, a workgroup = one wave per SIMD: by registers two waves per SIMD at 1 and 2 tiles, one above — resource_usage.txt)
+    if (h16) wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles <= 2 ? 2u : 1u);
     const uint32_t N = (uint32_t)std::min<uint64_t>(k, live);
     const uint64_t qc = ScoreCut::chunk(nq, m, N);
     const bool sort_dev = N <= 16384;
@@ -277,17 +349,27 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
                            bitset_words ? h->mask.p : nullptr, mask_words, h->cut.S.p};
         const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
         if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
-        switch (tiles) {
-        case 1: LY_TRY(maxsim_launch<1>(a, grid, waves, lds, st)); break;
-        case 2: LY_TRY(maxsim_launch<2>(a, grid, waves, lds, st)); break;
-        case 4: LY_TRY(maxsim_launch<4>(a, grid, waves, lds, st)); break;
-        default: LY_TRY(maxsim_launch<8>(a, grid, waves, lds, st)); break;
+        if (h16) {   // the same tables and queries, the token rows as halves
+            const MaxSimH16Args ah{reinterpret_cast<const _Float16*>(h->tokens_h.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S};
+            switch (tiles) {
+            case 1: LY_TRY(maxsim_h16_launch<1>(ah, grid, lds, st)); break;
+            case 2: LY_TRY(maxsim_h16_launch<2>(ah, grid, lds, st)); break;
+            case 4: LY_TRY(maxsim_h16_launch<4>(ah, grid, lds, st)); break;
+            default: LY_TRY(maxsim_h16_launch<8>(ah, grid, lds, st)); break;
+            }
+        } else {
+            switch (tiles) {
+            case 1: LY_TRY(maxsim_launch<1>(a, grid, waves, lds, st)); break;
+            case 2: LY_TRY(maxsim_launch<2>(a, grid, waves, lds, st)); break;
+            case 4: LY_TRY(maxsim_launch<4>(a, grid, waves, lds, st)); break;
+            default: LY_TRY(maxsim_launch<8>(a, grid, waves, lds, st)); break;
+            }
         }
         if (timed) {
             LY_HIP(hipEventRecord(h->ev[1], st));
             h->prof.scan_launches += 1;
             h->prof.scan_rows += h->total * nqc;
-            h->prof.scan_bytes += (h->total * ld * 4 + (m + 1) * 8) * nqc;
+            h->prof.scan_bytes += (h->total * ld * (h16 ? 2 : 4) + (m + 1) * 8) * nqc;
         }
         // more live records than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
         h->cut.sel0.assign(nqc, select ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
