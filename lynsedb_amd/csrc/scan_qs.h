@@ -19,7 +19,9 @@
 //     v_max chain against ONE register-resident integer threshold (the integer image of the certified threshold, DESIGN.md
 //     §3b), one ballot, and a rare grouped path that appends (score, row) keys to the lane's private segment;
 //   * XPF: the first fragments of step g + 1 are read before barrier g + 1 (the wait in front of barrier g covers the data of
-//     step g + 1 too), so no wave opens a step waiting for its first LDS round trip.
+//     step g + 1 too), so no wave opens a step waiting for its first LDS round trip;
+//   * CARRY (the 16x16x64 form under the ping-pong order, where a fourth ring stage for XPF does not fit): the other direction — a wave holds the
+//     last NBUF - 1 fragments of step g in registers across barrier g + 1 and runs their MFMAs behind it, in the shadow of step g + 1's opening reads.
 // Keys, segments and counts are the ones k_select gathers (ScanArgs::candB / segcnt; two segments per workgroup and query: the
 // two wave halves of the owning wave).
 //
@@ -85,6 +87,7 @@ constexpr size_t qs_lds_bytes(QsCfg c) {
 // integer threshold and constants — and the four lanes that share a query have a private segment each (candB / segcnt index
 // blockIdx.x * 4 + lane / 16: the host sizes the segments with four per workgroup and query).  Keys are formed exactly as in the 32x32x32
 // form, so a stage emits the identical key set.  Why: the power-capped chip holds a higher clock on the smaller shape.
+// M16 = 2: the same form on the plain ping-pong order, without the carried step tail (CARRY below) — the A/B of scripts/qs_microbench.hip only.
 template <int NSLAB, int RB, int SL, int NS, bool XPF, int NBUF, int DBG = 0, int PING = 0, int STS = 0, int MET = 0, int SMP = 0, int MSK = 0, int F4 = 0, int M16 = 0>
 __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     static_assert(NSLAB % SL == 0, "a tile is a whole number of steps");
@@ -115,6 +118,17 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     constexpr int KX = M16 != 0 ? 64 : 32;  // byte distance of two of them inside a 128-B row (an XOR: it commutes with the slot swizzle)
     constexpr int WAITN = (XPF ? NS - 3 : NS - 2) * PPW;   // DMA instructions that may still be in flight at the barrier
     static_assert(WAITN <= 63, "vmcnt");
+    // CARRY (M16 = 1 under PING = 1): a step's last NH fragments are HELD in registers across the barrier and their MFMAs run behind it, in the
+    // shadow of the next step's opening reads.  NMA fragments stay in the step's own loop.  The held reads are issued HE iterations before
+    // their natural place (iteration H0 on), so that the lgkmcnt(0) in front of the barrier finds them returned.
+    constexpr bool CARRY = M16 == 1 && PING == 1;
+    constexpr int NH = NBUF - 1, NMA = NM - NH;
+    constexpr int HE = NMA - NH < NH ? NMA - NH : NH, H0 = NMA - NH - HE;
+    static_assert(!CARRY || (!XPF && NMA >= NH && NMA >= R16), "carry: the ring refills from the step's own stage, and the C = 0 MFMAs of a tile stay in its own loop");
+    // (the carried loop has no self-tightening pickup, no norm ring, no sample keys, no phase stamps and always emits; every tile is ONE step)
+    static_assert(!CARRY || (STS == 0 && MET == 0 && SMP == 0 && F4 == 0 && TS == 1 && (DBG & 32) == 0), "carry: plain threshold stages of the IP / cosine form, whole-K stages");
+    // M16 = 2 (the plain order of the 16x16x64 form) is built by scripts/qs_microbench.hip alone: launch_scan_qs must never name it
+    static_assert(M16 >= 0 && M16 <= 2, "M16: 0 = 32x32x32, 1 = 16x16x64 (carried tail under PING = 1), 2 = 16x16x64 on the plain order (microbenchmark only)");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -416,6 +430,84 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
     [[maybe_unused]] auto stamp = [&](unsigned long long& bucket) {
         if constexpr (TIMING) { const unsigned long long t = __builtin_amdgcn_s_memtime(); bucket += t - tp; tp = t; }
     };
+    // M16: the fragment idx = (sl, k64, rb16) of step s of a tile against the two 16-query blocks: two v_mfma_i32_16x16x64_i8 into whole
+    // 4-register accumulators
+    [[maybe_unused]] auto mfma16_pair = [&](const qs_i32x4& fr, auto sc, auto idxc) {
+        constexpr int s = decltype(sc)::value, idx = decltype(idxc)::value;
+        constexpr int k64 = (idx / R16) % 2, rb16 = idx % R16;
+        constexpr int kb = (s * SL + idx / (2 * R16)) * 4 + k64 * 2;
+        ly_static_for<2>([&](auto qbc) {
+            constexpr int qb = decltype(qbc)::value;
+            if constexpr (kb == 0) {   // first k-step of a tile: C = 0
+                const qs_i32x4 z = {0, 0, 0, 0};
+                acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fr, bq[kb + qb], z, 0, 0, 0);
+            } else {
+                acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fr, bq[kb + qb], acc16[rb16][qb], 0, 0, 0);
+            }
+        });
+    };
+    // ---- CARRY: the three pieces of a step.  Reads in issue order: the NH opening reads (behind the barrier; drained behind the held MFMAs
+    // of the step before, so the counts below start at zero), then per iteration it of the step's own loop the ring read of fragment
+    // it + NH (while that is < NMA) and, from iteration H0 on, one held read (fragment NMA + it - H0).  LDS reads return in order: MFMA it
+    // may run once at most the reads issued BEHIND fragment it's are outstanding.
+    [[maybe_unused]] qs_i32x4 hf[NH];   // the held fragments NMA .. NM - 1 of the step computed last
+    if constexpr (CARRY) {
+#pragma unroll
+        for (int i = 0; i < NH; ++i) {
+            if constexpr ((DBG & 2) != 0) asm volatile("" : "=v"(hf[i]) : "0"(bq[NBUF + i]));
+            else hf[i] = qs_i32x4{0, 0, 0, 0};
+        }
+    }
+    [[maybe_unused]] auto carry_open = [&]() {   // the opening reads of the step whose stage wait_and_barrier() just made current
+        if constexpr (CARRY && !(DBG & 2)) ly_static_for<NH>([&](auto ic) { read_frag(af[decltype(ic)::value], ad_cur, ic); });
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto carry_tail = [&]() {   // the MFMAs of the held fragments (never a tile's C = 0 ones: NMA >= R16)
+        if constexpr (CARRY) ly_static_for<NH>([&](auto hc) {
+            constexpr int h = decltype(hc)::value;
+            if constexpr ((DBG & 1) != 0) asm volatile("" ::"v"(hf[h]), "v"(bq[((NMA + h) / (2 * R16)) * 4]));
+            else mfma16_pair(hf[h], std::integral_constant<int, 0>{}, std::integral_constant<int, NMA + h>{});
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto carry_opened = [&]() {   // the opening reads have returned (they had the held MFMAs' time to do so)
+        if constexpr (CARRY && !(DBG & 2)) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            // (each register is defined HERE, behind the wait; a plain unrolled loop: an asm operand cannot name a variable captured by a nested lambda)
+#pragma unroll
+            for (int i = 0; i < NH; ++i) asm volatile("" : "+v"(af[i]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    [[maybe_unused]] auto carry_head = [&]() {   // fragments 0 .. NMA - 1 of the current step; leaves NMA .. NM - 1 in hf, returned
+        if constexpr (CARRY) ly_static_for<NMA>([&](auto ic) {
+            constexpr int it = decltype(ic)::value;
+            constexpr int hd = it - H0;
+            if (!(DBG & 2)) {
+                if constexpr (it + NH < NMA) read_frag(af[(it + NH) % NBUF], ad_cur, std::integral_constant<int, it + NH>{});
+                if constexpr (hd >= 0 && hd < NH) read_frag(hf[hd], ad_cur, std::integral_constant<int, NMA + hd>{});
+                if constexpr (it >= NH) {
+                    // reads issued so far in this loop, less those up to and including fragment it's (iteration j = it - NH, first of it)
+                    constexpr int j = it - NH;
+                    constexpr auto clampNH = [](int x) { return x < 0 ? 0 : (x > NH ? NH : x); };
+                    constexpr int issued = (it + 1 < NMA - NH ? it + 1 : NMA - NH) + clampNH(it - H0 + 1);
+                    constexpr int behind = issued - (j + clampNH(j - H0)) - 1;
+                    static_assert(behind >= 0 && behind <= 15, "lgkmcnt");
+                    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(af[it % NBUF]) : "n"(behind));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr ((DBG & 1) != 0) asm volatile("" ::"v"(af[it % NBUF]), "v"(bq[(it / (2 * R16)) * 4]));
+            else mfma16_pair(af[it % NBUF], std::integral_constant<int, 0>{}, ic);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        if constexpr (CARRY && !(DBG & 2)) {   // every read of the stage has returned before the barrier that lets it be refilled
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < NH; ++i) asm volatile("" : "+v"(hf[i]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
     // the MFMAs of one step (s = the step's position in its tile); DMA_IN: the refill pieces are issued between them
     auto mfma_step = [&](auto sc, auto dma_in) {
         constexpr int s = decltype(sc)::value;
@@ -444,18 +536,7 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
             if constexpr ((DBG & 1) != 0) {
                 asm volatile("" ::"v"(af[idx % NBUF]), "v"(bq[ks]));
             } else if constexpr (M16 != 0) {
-                // the fragment (sl, k64, rb16) against the two 16-query blocks: two v_mfma_i32_16x16x64_i8 into whole 4-register accumulators
-                constexpr int k64 = (idx / R16) % 2, rb16 = idx % R16;
-                constexpr int kb = (s * SL + idx / (2 * R16)) * 4 + k64 * 2;
-                ly_static_for<2>([&](auto qbc) {
-                    constexpr int qb = decltype(qbc)::value;
-                    if constexpr (kb == 0) {   // first k-step of a tile: C = 0
-                        const qs_i32x4 z = {0, 0, 0, 0};
-                        acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[kb + qb], z, 0, 0, 0);
-                    } else {
-                        acc16[rb16][qb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[idx % NBUF], bq[kb + qb], acc16[rb16][qb], 0, 0, 0);
-                    }
-                });
+                mfma16_pair(af[idx % NBUF], sc, ic);
             } else if constexpr (F4 != 0) {
                 if constexpr (ks == 0) {
                     const f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -583,12 +664,16 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
                 if constexpr (MSK != 0) {   // (uniform) a tile of the emit-all sample stage: its rows are candidates already
                     if (a.skip_stride && rbase % a.skip_stride < 256u && rbase / a.skip_stride < a.skip_tiles) return;
                 }
+                // (the query numbers are opaque from here on: the segment, count and candidate addresses of the two queries are formed on
+                // this rare path — hoisted out of the tile loop they are 16 registers the loop does not have)
+                uint32_t qn_e[2] = {qn16[0], qn16[1]};
+                asm volatile("" : "+v"(qn_e[0]), "+v"(qn_e[1]));
 #pragma unroll
                 for (int i = 0; i < R16; ++i) {
 #pragma unroll
                     for (int qb = 0; qb < 2; ++qb) {
                         if (__builtin_expect(__ballot(gm[i][qb] >= T16[qb]) == 0ull, 1)) continue;
-                        uint64_t* segdst = a.candB + ((size_t)qn16[qb] * a.nseg + (blockIdx.x * 4 + g4)) * a.seg;
+                        uint64_t* segdst = a.candB + ((size_t)qn_e[qb] * a.nseg + (blockIdx.x * 4 + g4)) * a.seg;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int v = acc16[i][qb][e];
@@ -600,8 +685,8 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
                                         segdst[cnt16[qb]] = key;
                                         ++cnt16[qb];
                                     } else {
-                                        const uint32_t slot = atomicAdd(&a.count[qn16[qb]], 1u);
-                                        if (slot < a.cap) a.cand[(size_t)qn16[qb] * a.cap + slot] = key;
+                                        const uint32_t slot = atomicAdd(&a.count[qn_e[qb]], 1u);
+                                        if (slot < a.cap) a.cand[(size_t)qn_e[qb] * a.cap + slot] = key;
                                     }
                                 }
                             }
@@ -778,6 +863,40 @@ __global__ void __launch_bounds__(512, 2) k_scan_qs(ScanArgs a) {
             });
             if constexpr (STS != 0) sts_pickup();
             if (wave_live) epilogue(tile_of(c_ord), c_ord >= warm, c_ord);
+        }
+    } else if constexpr (CARRY) {
+        // The ping-pong roles below with a step's tail CARRIED across the barrier.  Behind barrier g no wave of the plain order holds a
+        // fragment: the early waves wait out an LDS round trip and the fill of the fragment ring, the late waves run an epilogue, and the
+        // matrix pipe of every SIMD stands still.  Here a wave passes barrier g with the last NH fragments of step g - 1 in registers (read
+        // and returned before the barrier, so the stage is free for its refill as ever), issues the opening reads of step g and runs the
+        // held MFMAs in their shadow; only then the epilogue of tile g - 1 and the step's own MFMAs.  EARLY: barrier -> open -> held MFMAs
+        // -> epilogue(g - 1) -> MFMAs(g) -> DMA issue;  LATE: barrier -> open -> held MFMAs -> epilogue(g - 1) -> DMA issue -> MFMAs(g).
+        // The epilogue reads the accumulators before the C = 0 MFMAs of the step write them, and its key stores stay older than the
+        // step's pieces in both roles (the counted vmcnt at the barrier, see below).  Integer sums: the keys are the plain order's.
+        const bool late = wave >= 4;
+        for (uint32_t g = 0; g < n_ord; ++g) {
+            wait_and_barrier();
+            if (wave_live) {
+                carry_open();
+                if (g) carry_tail();
+                carry_opened();
+                if (g) epilogue(tile_of(g - 1), true, g - 1);
+            }
+            if (late) {
+#pragma unroll
+                for (int j = 0; j < PPW; ++j) issue_piece(j);
+                advance();
+            }
+            if (wave_live) carry_head();
+            if (!late) {
+#pragma unroll
+                for (int j = 0; j < PPW; ++j) issue_piece(j);
+                advance();
+            }
+        }
+        if (wave_live) {   // the last tile: no further barrier
+            carry_tail();
+            epilogue(tile_of(n_ord - 1), true, n_ord - 1);
         }
     } else {
         // PING-PONG (PING): the two waves of a SIMD share one matrix pipe, and with equal priority the older wave wins every slot — waves

@@ -9,6 +9,9 @@
 // 1b. `qs_microbench qs16 [rows rounds sigma]`: the MFMA-shape axis: the default instantiation against its 16x16x64 form (scan_qs.h, M16) — the check
 //    passes of both, then everything / MFMA only / MFMA + LDS reads / DMA + MFMA of both in interleaved rounds, on SQ7-like and centred operands, with
 //    the s_memtime clock, the socket power and the cycles per MFMA (profiles/qs16_microbench.txt).
+// 1c. `qs_microbench carry [rows rounds sigma]`: the same protocol on the ORDER axis of the 16x16x64 form: the plain ping-pong order (every step
+//    opens behind its barrier with no fragment held; M16 = 2, built here only) against the carried step tail (scan_qs.h, CARRY: M16 = 1, what the
+//    library launches) — everything / MFMA only / MFMA + LDS reads / DMA + MFMA of both in interleaved rounds of one process.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -pragma-unroll-threshold=262144 \
 //        [-DLYNSE_EXPERIMENTS] -o qs_microbench scripts/qs_microbench.hip
 #include <algorithm>
@@ -307,6 +310,9 @@ int main(int argc, char** argv) {
     // form only, then both forms and their decompositions timed in interleaved rounds on SQ7-like and on centred operands
     const bool qs16_axis = !operand_axis && argc > 1 && strcmp(argv[1], "qs16") == 0;
     if (qs16_axis) { --argc; ++argv; }
+    // "carry": section 1b's protocol on the order axis of the 16x16x64 form (1c above)
+    const bool carry_axis = !operand_axis && !qs16_axis && argc > 1 && strcmp(argv[1], "carry") == 0;
+    if (carry_axis) { --argc; ++argv; }
     const uint64_t n_big = argc > 1 ? strtoull(argv[1], nullptr, 10) : 10000000ull;
     const int rounds = argc > 2 ? atoi(argv[2]) : 5;
     const double sigma_tight = argc > 3 ? atof(argv[3]) : 4.3;   // thresholds in units of the dot product's standard deviation
@@ -380,6 +386,8 @@ int main(int argc, char** argv) {
     // the 16x16x64 form at the same wave tile (scan_qs.h, M16): four private segments per workgroup and query
     vars.push_back({"qs16 RB2 SL6 NS3 noXPF NBUF8 PP1", 4, launch_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 1>, true});
     vars.push_back({"qs16 RB2 SL6 NS3 noXPF NBUF8", 4, launch_qs<6, 2, 6, 3, false, 8, 0, 0, 0, 0, 1>, true});
+    // the plain ping-pong order of the 16x16x64 form (M16 = 2: no fragment carried across the barrier; the library launches M16 = 1)
+    vars.push_back({"qs16 plain order RB2 SL6 NS3 PP1", 4, launch_qs<6, 2, 6, 3, false, 8, 0, 1, 0, 0, 2>, true});
     vars.push_back({"qs2 4w x 64q RB2 NS3 NBUF8", 2, launch_qs2<6, 2, 3, 8, 0>, true});
     vars.push_back({"qs2 4w x 64q RB2 NS3 NBUF12", 2, launch_qs2<6, 2, 3, 12, 0>, true});
     vars.push_back({"qs2 4w x 64q RB1 NS6 NBUF8", 2, launch_qs2<6, 1, 6, 8, 0>, true});
@@ -412,6 +420,9 @@ int main(int argc, char** argv) {
     vars.push_back({"qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8 + 2, 1, 0, 0, 1>, true});
     vars.push_back({"qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8, 1, 0, 0, 1>, true});
     vars.push_back({"qs16 RB2 SL6 NS3 PP1 | DMA + MFMA", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 2, 1, 0, 0, 1>, true});
+    vars.push_back({"qs16 plain order RB2 SL6 NS3 PP1 | MFMA only", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8 + 2, 1, 0, 0, 2>, true});
+    vars.push_back({"qs16 plain order RB2 SL6 NS3 PP1 | MFMA + LDS reads", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 8, 1, 0, 0, 2>, true});
+    vars.push_back({"qs16 plain order RB2 SL6 NS3 PP1 | DMA + MFMA", 4, launch_qs<6, 2, 6, 3, false, 8, 16 + 2, 1, 0, 0, 2>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | MFMA + LDS reads", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 8, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | DMA + MFMA", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 2, 1>, true});
     vars.push_back({"qs RB2 SL6 NS3 PP1 | DMA only", 2, launch_qs<6, 2, 6, 3, false, 8, 16 + 2 + 1, 1>, true});
@@ -597,7 +608,7 @@ int main(int argc, char** argv) {
         for (size_t vi = 0; vi < vars.size(); ++vi) {
             const Variant& v = vars[vi];
             if (v.name.find('|') != std::string::npos) continue;
-            if (qs16_axis && v.name.rfind("qs16", 0) != 0 && v.name != "qs RB2 SL6 NS3 noXPF NBUF8 PP1") continue;
+            if ((qs16_axis || carry_axis) && v.name.rfind("qs16", 0) != 0 && v.name != "qs RB2 SL6 NS3 noXPF NBUF8 PP1") continue;
             const bool l2v = v.name.rfind("L2", 0) == 0;
             if (l2v) set_thr_l2(sig, nq);
             struct Restore { std::function<void()> f; ~Restore() { f(); } } restore{[&]() { if (l2v) set_thr(sig, nq); }};
@@ -667,7 +678,7 @@ int main(int argc, char** argv) {
                 std::vector<uint64_t> got = collect(b, nq, a.nseg, a.seg);
                 const std::vector<uint64_t>& ref = ref_use;
                 const bool ok = got == ref;
-                if (ok && qs16_axis) printf("ok       pass %d %-34s starve %d: %zu keys, identical to the brute-force set\n", pass, v.name.c_str(), starve, got.size());
+                if (ok && (qs16_axis || carry_axis)) printf("ok       pass %d %-34s starve %d: %zu keys, identical to the brute-force set\n", pass, v.name.c_str(), starve, got.size());
                 if (!ok) {
                     ++bad;
                     printf("MISMATCH pass %d %-34s starve %d: ref %zu keys, got %zu\n", pass, v.name.c_str(), starve, ref.size(), got.size());
@@ -684,7 +695,7 @@ int main(int argc, char** argv) {
 
     // ---- 1b. MFMA shape (first argument "qs16"): v_mfma_i32_32x32x32_i8 against v_mfma_i32_16x16x64_i8 at the same wave tile, everything and
     // the decompositions, on (b) SQ7-like operands (rows and query image in [0,127]) and (a) centred ones.  Protocol of section 0.
-    if (qs16_axis) {
+    if (qs16_axis || carry_axis) {
 #ifndef LYNSE_EXPERIMENTS
         fprintf(stderr, "the qs16 axis needs -DLYNSE_EXPERIMENTS (the decomposition rows)\n");
         return 2;
@@ -692,10 +703,17 @@ int main(int argc, char** argv) {
         struct Op { const char* name; uint32_t and_mask; bool nonneg; double mean, var; };
         const Op ops[2] = {{"(b) rows [0,127], queries [0,127]", 0x7f7f7f7fu, true, 63.5, (16384.0 - 1.0) / 12.0},
                            {"(a) rows [-128,127], queries [-127,127]", 0xffffffffu, false, -0.5, (65536.0 - 1.0) / 12.0}};
-        const char* names[8] = {"qs RB2 SL6 NS3 noXPF NBUF8 PP1", "qs16 RB2 SL6 NS3 noXPF NBUF8 PP1",
-                                "qs RB2 SL6 NS3 PP1 | MFMA only 32x32x32", "qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64",
-                                "qs RB2 SL6 NS3 PP1 | MFMA + LDS reads", "qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads",
-                                "qs RB2 SL6 NS3 PP1 | DMA + MFMA", "qs16 RB2 SL6 NS3 PP1 | DMA + MFMA"};
+        const char* names_shape[8] = {"qs RB2 SL6 NS3 noXPF NBUF8 PP1", "qs16 RB2 SL6 NS3 noXPF NBUF8 PP1",
+                                      "qs RB2 SL6 NS3 PP1 | MFMA only 32x32x32", "qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64",
+                                      "qs RB2 SL6 NS3 PP1 | MFMA + LDS reads", "qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads",
+                                      "qs RB2 SL6 NS3 PP1 | DMA + MFMA", "qs16 RB2 SL6 NS3 PP1 | DMA + MFMA"};
+        // the order axis: even = the plain order, odd = the carried tail; both 96 MFMAs per wave and step
+        const char* names_order[8] = {"qs16 plain order RB2 SL6 NS3 PP1", "qs16 RB2 SL6 NS3 noXPF NBUF8 PP1",
+                                      "qs16 plain order RB2 SL6 NS3 PP1 | MFMA only", "qs16 RB2 SL6 NS3 PP1 | MFMA only 16x16x64",
+                                      "qs16 plain order RB2 SL6 NS3 PP1 | MFMA + LDS reads", "qs16 RB2 SL6 NS3 PP1 | MFMA + LDS reads",
+                                      "qs16 plain order RB2 SL6 NS3 PP1 | DMA + MFMA", "qs16 RB2 SL6 NS3 PP1 | DMA + MFMA"};
+        const char* const* names = carry_axis ? names_order : names_shape;
+        const char* even_name = carry_axis ? "plain order" : "32x32x32", *odd_name = carry_axis ? "carried tail" : "16x16x64";
         const Variant* vs[8] = {};
         for (int i = 0; i < 8; ++i) {
             for (const Variant& v : vars) if (v.name == names[i]) vs[i] = &v;
@@ -794,11 +812,11 @@ int main(int argc, char** argv) {
                 const double med = c.ms[c.ms.size() / 2] * 1e3, mn = c.ms.front() * 1e3, sp = (c.ms.back() - c.ms.front()) * 1e3;
                 med_of[vi] = med; sp_of[vi] = sp;
                 printf("%-46s %8.1f %8.1f %7.1f   %6.0f MHz   hwmon %6.0f W %6.0f MHz   %6.1f cyc/MFMA\n", names[vi], med, mn, sp, c.clk, c.watts, c.smhz,
-                       c.ticks / (tiles0 * ((vi & 1) ? 96.0 : 48.0) * 2.0));
+                       c.ticks / (tiles0 * ((vi & 1) || carry_axis ? 96.0 : 48.0) * 2.0));
             }
             const double gain = med_of[0] - med_of[1], need = 3.0 * std::max(sp_of[0], sp_of[1]);
-            printf("GATE %s: 32x32x32 %.1f us - 16x16x64 %.1f us = %.1f us; three times the larger spread = %.1f us -> %s\n", ops[oi].name, med_of[0], med_of[1], gain, need,
-                   gain > need ? "16x16x64 WINS" : "no gain");
+            printf("GATE %s: %s %.1f us - %s %.1f us = %.1f us; three times the larger spread = %.1f us -> %s %s\n", ops[oi].name, even_name, med_of[0], odd_name, med_of[1], gain,
+                   need, gain > need ? odd_name : "no gain", gain > need ? "WINS" : "");
         }
         sampler.finish();
         printf("mismatches: %d\n", bad);
