@@ -1104,7 +1104,27 @@ int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, in
  *      bits), the order of the sum is the hardware's and not part of the contract.
  *  7'. The LDS holds the query's tiles only, as halves at a row pitch of 2 ld + 16 bytes, plus 512 B of flags: tiles * 32 * (2 ld + 16)
  *      + 512 <= 160 KiB or LYNSE_ERR_UNSUPPORTED ("... do not fit in LDS").  That serves 256 query tokens up to dim_mv 288, 128 up to
- *      512 and 64 up to 1024: every dim_mv in 1 .. 1024 can be created. */
+ *      512 and 64 up to 1024: every dim_mv in 1 .. 1024 can be created.
+ *
+ * INT8 TOKEN STORAGE (lynse_hip_multivec_create_i8; index mode MULTIVEC-MAXSIM-IP-I8).  Token rows are int8 codes with one f32 scale
+ * per token; the scan is k_maxsim_i8 on v_mfma_i32_32x32x32_i8.  lynse_hip_multivec_append takes f32 rows and quantises them on the
+ * device; lynse_hip_multivec_append_f16 on such a handle is LYNSE_ERR_INVALID_ARGUMENT.  Every step is either exact or ONE f32
+ * rounding, so the scores are reproducible bit for bit from the rules.  Rules 5, 6, 8 and 9 stand; the others read:
+ *  1". Stored value, per token row p (its first dim_mv columns).  amax = max_k |p_k| taken with fmaxf (a NaN element is skipped).
+ *      amax 0 or +inf, or every element NaN: the scale s = 0 and every code 0.  Otherwise inv = 127.0f / amax and s = amax / 127.0f
+ *      (IEEE f32 divisions) and c_k = clamp(rintf(p_k * inv), -127, 127), ties to even, a NaN element codes as 0.  The codes are int8
+ *      rows at pitch ld = dim_mv rounded up to a multiple of 32 BYTES, zero past dim_mv; the scales an f32 array, one per token.
+ *      Each query token gets the same treatment on the device as its tiles are staged: codes cq_i and scale sq_i.
+ *  2". Score block.  d_ij = sum_k cq_ik * c_jk in int32: exact, its order free.  |d_ij| <= 127^2 * 1024 < 2^24, so f32(d_ij) is
+ *      exact; v_ij = f32(d_ij) * s_j, one f32 multiply.
+ *  3". m_i = sq_i * max_j v_ij over the record's tokens, one f32 multiply (sq_i >= 0 and a rounded multiply is monotone, so scaling
+ *      before or after the max gives the same bits).  No NaN and no -inf arises.
+ *  4". Sum.  Within a tile of 32 query tokens the m_i are added as a balanced pairwise tree in f32: level 0 adds slots (2i, 2i + 1),
+ *      level 1 pairs of those sums, 5 levels; slots at or past the query's tokens count as +0.0f.  The sums of the query's tiles are
+ *      then added in tile order, ((T_0 + T_1) + T_2) + ..., separate adds.  (This order is this store's own, not rule 4.)
+ *  7". 1 <= dim_mv <= 1024 and 1 <= tokens of a query <= 256.  The LDS holds the query's tiles as codes at a row pitch of ld + 16
+ *      bytes, their scales and 512 B of flags: tiles * 32 * (ld + 20) + 512 <= 160 KiB or LYNSE_ERR_UNSUPPORTED ("... do not fit in
+ *      LDS").  That serves 256 query tokens up to dim_mv 608 and 128 up to 1024: every dim_mv in 1 .. 1024 can be created. */
 typedef struct lynse_hip_multivec lynse_hip_multivec;
 /* dtype: 0 = f32 (lynse_hip_multivec_create), 1 = f16; anything else LYNSE_ERR_INVALID_ARGUMENT */
 int lynse_hip_multivec_create_dtype(int device, uint32_t dim_mv, int dtype, lynse_hip_multivec **out);
@@ -1112,6 +1132,10 @@ int lynse_hip_multivec_create_dtype(int device, uint32_t dim_mv, int dtype, lyns
 int lynse_hip_multivec_plan_dtype(uint32_t dim_mv, uint32_t tq, int dtype, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
 /* lynse_hip_multivec_append for raw IEEE binary16 rows; valid on an f16 handle only (LYNSE_ERR_INVALID_ARGUMENT otherwise) */
 int lynse_hip_multivec_append_f16(lynse_hip_multivec *h, const uint16_t *tokens, const uint64_t *counts /* n_records */, uint64_t n_records);
+/* an int8 store (INT8 TOKEN STORAGE); the append, search, counts, profile and destroy calls below serve it too */
+int lynse_hip_multivec_create_i8(int device, uint32_t dim_mv, lynse_hip_multivec **out);
+/* rule 7" for a query of tq tokens at dim_mv, host only (waves: always 4) */
+int lynse_hip_multivec_plan_i8(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
 /* Rule 7 for a query of tq tokens at dim_mv, host only (no handle, no device): the query tiles held in LDS, the waves of a workgroup
  * and the LDS bytes; LYNSE_ERR_UNSUPPORTED with the message of rule 7 where the answer is a refusal.  Each output may be NULL. */
 int lynse_hip_multivec_plan(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);

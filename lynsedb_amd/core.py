@@ -1628,17 +1628,30 @@ class SparseIndex:
 # ---------------------------------------------------------------------------------------------
 MULTIVEC_INDEX_MODE = "MULTIVEC-MAXSIM-IP"
 MULTIVEC_INDEX_MODE_F16 = "MULTIVEC-MAXSIM-IP-F16"   # f16 token storage (include/lynse_hip.h, F16 TOKEN STORAGE)
+MULTIVEC_INDEX_MODE_I8 = "MULTIVEC-MAXSIM-IP-I8"     # int8 token storage (include/lynse_hip.h, INT8 TOKEN STORAGE)
 MULTIVEC_MAX_QUERY_TOKENS = 256   # include/lynse_hip.h, MULTI-VECTOR SEARCH rule 7
 MULTIVEC_MAX_DIM = 1024
 
 
 def _multivec_dtype(dtype) -> Optional[str]:
-    """None, or "f32" / "f16" for the spellings of `vector_dtype_name`"""
-    return None if dtype is None else {"float32": "f32", "float16": "f16"}[vector_dtype_name(dtype)]
+    """None, "i8" for "i8" / "int8", or "f32" / "f16" for the spellings of `vector_dtype_name`"""
+    if dtype is None:
+        return None
+    if str(dtype).strip().lower() in ("i8", "int8"):
+        return "i8"
+    return {"float32": "f32", "float16": "f16"}[vector_dtype_name(dtype)]
 
 
 def _multivec_mode(dtype: Optional[str]) -> str:
-    return MULTIVEC_INDEX_MODE_F16 if dtype == "f16" else MULTIVEC_INDEX_MODE
+    return {"f16": MULTIVEC_INDEX_MODE_F16, "i8": MULTIVEC_INDEX_MODE_I8}.get(dtype, MULTIVEC_INDEX_MODE)
+
+
+def _multivec_plan(dim: int, tq: int, dtype: Optional[str]) -> None:
+    """the LDS half of rule 7 (7' for an f16 store, 7" for an int8 one), host only: raises where the answer is a refusal"""
+    if dtype == "i8":
+        check(lib.lynse_hip_multivec_plan_i8(dim, tq, None, None, None))
+    else:
+        check(lib.lynse_hip_multivec_plan_dtype(dim, tq, int(dtype == "f16"), None, None, None))
 
 
 def _multivec_queries(queries, dim: Optional[int], dtype: Optional[str] = None) -> list:
@@ -1656,19 +1669,23 @@ def _multivec_queries(queries, dim: Optional[int], dtype: Optional[str] = None) 
             raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
         if dim is not None and q.shape[1] != dim:
             raise RuntimeError(f"Dimension mismatch: expected {dim}, got {q.shape[1]}")
-        check(lib.lynse_hip_multivec_plan_dtype(q.shape[1], q.shape[0], int(dtype == "f16"), None, None, None))   # the LDS half of rule 7 (host only)
+        _multivec_plan(q.shape[1], q.shape[0], dtype)
         out.append(q)
     return out
 
 
 class MultiVectorIndex:
     """The token rows of multi-vector records in HBM, append-only, and their exact MaxSim scan: f32 rows (k_maxsim_scan) or, with
-    dtype="f16", half the bytes (k_maxsim_h16; tokens and queries rounded to f16, subnormals flushed)."""
+    dtype="f16", half the bytes (k_maxsim_h16; tokens and queries rounded to f16, subnormals flushed), or, with dtype="i8", int8 codes
+    and one f32 scale a token (k_maxsim_i8; tokens and queries quantised on the device, scores reproducible bit for bit)."""
 
     def __init__(self, dim: int, device: Optional[int] = None, dtype: str = "f32"):
         self._h, self._dim, self.dtype = C.c_void_p(), int(dim), _multivec_dtype(dtype)
         dev = default_device() if device is None else int(device)
-        check(lib.lynse_hip_multivec_create_dtype(dev, self._dim, int(self.dtype == "f16"), C.byref(self._h)))
+        if self.dtype == "i8":
+            check(lib.lynse_hip_multivec_create_i8(dev, self._dim, C.byref(self._h)))
+        else:
+            check(lib.lynse_hip_multivec_create_dtype(dev, self._dim, int(self.dtype == "f16"), C.byref(self._h)))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -3189,7 +3206,9 @@ class Collection:
         `dtype` ("f32"/"float32" or "f16"/"float16") is fixed by the first call like dim_mv: None means f32 then and the store's own
         afterwards, the other one is refused.  An f16 store holds half the bytes: f32 token arrays are rounded to f16 (nearest even,
         subnormals to zero), np.float16 arrays are taken as they are, queries are rounded the same way, every dim_mv up to 1024 is
-        accepted, and the mode reported is MULTIVEC-MAXSIM-IP-F16."""
+        accepted, and the mode reported is MULTIVEC-MAXSIM-IP-F16.  An "i8"/"int8" store holds a quarter of the bytes plus one f32 scale
+        a token: the f32 token arrays (np.float16 ones are widened) wait on the host and are quantised on the device at upload, as is
+        each query; every dim_mv up to 1024 is accepted and the mode is MULTIVEC-MAXSIM-IP-I8."""
         ids = [int(i) for i in ids]
         want = _multivec_dtype(dtype) or self._mv_dtype or "f32"
         if self._mv_dtype is not None and want != self._mv_dtype:
@@ -3207,7 +3226,7 @@ class Collection:
             raise ValueError("the first add_multi_vectors call must give a 2-D token set: it fixes dim_mv")
         if dim < 1 or dim > MULTIVEC_MAX_DIM:
             raise NotImplementedError(f"multi-vector search: a token dimension outside 1..{MULTIVEC_MAX_DIM} is not supported")
-        check(lib.lynse_hip_multivec_plan_dtype(dim, 1, int(want == "f16"), None, None, None))   # f32 above 416: not even one query tile fits the LDS, refused here
+        _multivec_plan(dim, 1, want)   # f32 above 416: not even one query tile fits the LDS, refused here
         sets = [np.ascontiguousarray(t.reshape(-1, dim) if t.size == 0 else t) for t in sets]
         for t in sets:
             if t.shape[1] != dim:
@@ -3228,7 +3247,7 @@ class Collection:
         return len(self._mv_ids)
 
     def multi_vector_dtype(self) -> Optional[str]:
-        """"f32" or "f16" once the first add_multi_vectors has fixed it, None before"""
+        """"f32", "f16" or "i8" once the first add_multi_vectors has fixed it, None before"""
         return self._mv_dtype
 
     def _mv_upload(self) -> None:

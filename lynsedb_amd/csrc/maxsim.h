@@ -486,4 +486,309 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_h
     }
 }
 
+// ---- int8 token storage (include/lynse_hip.h, MULTI-VECTOR SEARCH, INT8 TOKEN STORAGE) ---------------------------
+//   k_maxsim_i8     the same split (one wave, one range of whole records, blocks of 32 token rows) with the operand roles SWAPPED:
+//                   the block's tokens are the A operand of v_mfma_i32_32x32x32_i8 and the query tile the B operand, so in the
+//                   32 x 32 accumulator a lane holds ONE query column and 16 of the 32 token rows.  The max over a record's tokens
+//                   then walks down the lane's own registers (v_max_f32, no cross-lane traffic inside 4 rows) and crosses to the
+//                   other half of the wave once per 4 rows (v_permlane32_swap); only where a record ENDS do the 32 column lanes
+//                   meet, in the 5-step pairwise tree of rule 4".  The 16 bytes a lane gives the instruction for A are 16 codes of
+//                   ONE token row: lane (j = lane % 32, h = lane / 32) loads them from HBM straight into the operand registers.
+//                   Of each 64 columns of a row half h owns the 32 at 32 h: k-steps 2 p and 2 p + 1 take its bytes 0..15 and
+//                   16..31, so a lane reads 32 contiguous bytes per pair of steps; the query fragments follow the same assignment
+//                   (the integer sum is exact, its order free).  A chunk of 128 columns is 4 fragments = 16 VGPRs; the chunks of
+//                   the stream go through a ring of RING such buffers, loaded RING - 1 chunks ahead of the MFMAs that read them.
+//   k_maxsim_store_i8  rule 1": f32 rows [rows][dim] -> codes [rows][ld] and scales[rows], 16 lanes a row.
+typedef int maxsim_i32x4 __attribute__((ext_vector_type(4)));
+typedef int maxsim_i32x16 __attribute__((ext_vector_type(16)));
+typedef float maxsim_f32x4_u __attribute__((ext_vector_type(4), aligned(4)));   // the scales of 4 rows: a token offset is any multiple of 4 B
+
+constexpr uint32_t MAXSIM_I8_KC = 128;   // columns of a chunk: 2 pairs of k-steps
+
+// LDS row pitch of a query tile in BYTES: ld + 16 = 16 s with s = ld / 16 + 1 odd (ld / 16 is even), so by the argument at
+// maxsim_pitch the ds_read_b128 fragment reads (16 lanes: one 16-B piece of 16 consecutive rows) are conflict-free.
+__host__ __device__ inline uint32_t maxsim_i8_pitch(uint32_t ld) { return ld + 16u; }
+// LDS bytes: the query tiles as codes | their scales | the 32 boundary flags of each of the (always 4) waves
+__host__ __device__ inline size_t maxsim_i8_lds_bytes(uint32_t ld, uint32_t tiles) {
+    return (size_t)tiles * MAXSIM_BLOCK * (maxsim_i8_pitch(ld) + 4u) + (size_t)MAXSIM_MAX_WAVES * MAXSIM_BLOCK * 4u;
+}
+
+struct MaxSimI8Args {
+    MaxSimArgsT<int8_t> a;    // the token rows are codes, ld BYTES a row; the queries still f32 (quantised as they are staged)
+    const float* scales;      // [total tokens]
+};
+
+// Rule 1": the scale pair of a row from its amax (fmaxf over |p_k|: a NaN element is skipped), and the code of an element
+__device__ __forceinline__ void maxsim_i8_scale(float amax, float& inv, float& s) {
+    const bool none = amax == 0.0f || amax == __builtin_huge_valf();
+    inv = none ? 0.0f : 127.0f / amax;
+    s = none ? 0.0f : amax / 127.0f;
+}
+__device__ __forceinline__ uint32_t maxsim_i8_code(float p, float inv) {
+    float r = rintf(p * inv);
+    r = r != r ? 0.0f : fminf(fmaxf(r, -127.0f), 127.0f);   // (inv = 0 where the row has no scale: 0, or NaN from an inf element)
+    return (uint32_t)(int)r & 0xffu;
+}
+__device__ __forceinline__ uint32_t maxsim_i8_pack(f32x4 v, float inv) {
+    return maxsim_i8_code(v[0], inv) | (maxsim_i8_code(v[1], inv) << 8) | (maxsim_i8_code(v[2], inv) << 16) | (maxsim_i8_code(v[3], inv) << 24);
+}
+
+// 16 lanes a row: the amax over the lanes' columns (order-free), then 4 codes a lane and trip as one 32-bit store.
+__global__ void __launch_bounds__(256) k_maxsim_store_i8(const float* __restrict__ src, uint32_t* __restrict__ codes, float* __restrict__ scales,
+                                                         uint64_t rows, uint32_t dim, uint32_t ld) {
+    const uint32_t lane = threadIdx.x & 63u, l = threadIdx.x & 15u;
+    const uint64_t r = (uint64_t)blockIdx.x * 16u + (threadIdx.x >> 4);
+    const bool in = r < rows;   // (no early return: the lanes of a wave exchange below)
+    const float* p = src + (in ? r : 0) * dim;
+    float amax = 0.0f;
+    if (in)
+        for (uint32_t c = l; c < dim; c += 16u) amax = fmaxf(amax, fabsf(p[c]));
+#pragma unroll
+    for (uint32_t d = 1; d < 16u; d <<= 1) amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ d));
+    if (!in) return;
+    float inv, s;
+    maxsim_i8_scale(amax, inv, s);
+    if (l == 0u) scales[r] = s;
+    for (uint32_t c4 = l; c4 < ld / 4u; c4 += 16u) {
+        f32x4 v;
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; ++e) v[e] = c4 * 4u + e < dim ? p[c4 * 4u + e] : 0.0f;
+        codes[r * (ld / 4u) + c4] = maxsim_i8_pack(v, inv);
+    }
+}
+
+// One chunk of a block into a ring buffer: lane (col, half) takes, of each of the chunk's 2 column groups of 64, the 32 bytes at
+// 32 half of token row t_first + col.  Rows at or past `t_end` (the end of the wave's range, or a block past its last) are zero,
+// as are the bytes past the row pitch (ld may end in the middle of a group): nothing outside the range is read.
+__device__ __forceinline__ void maxsim_i8_load(const MaxSimI8Args& x, uint64_t t_first, uint64_t t_end, uint32_t kc, uint32_t col, uint32_t half, maxsim_i32x4 (&f)[4]) {
+    const bool in = t_first + col < t_end;
+    const int8_t* src = x.a.tokens + (size_t)(t_first + col) * x.a.ld + kc + half * 32u;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        f[2 * p] = maxsim_i32x4{0, 0, 0, 0};
+        f[2 * p + 1] = maxsim_i32x4{0, 0, 0, 0};
+        if (in && kc + (uint32_t)p * 64u + half * 32u < x.a.ld) {
+            f[2 * p] = *reinterpret_cast<const maxsim_i32x4*>(src + p * 64);
+            f[2 * p + 1] = *reinterpret_cast<const maxsim_i32x4*>(src + p * 64 + 16);
+        }
+    }
+}
+// the matching query fragment: 16 codes of the lane's query row at byte `off` of it, zero past the pitch
+__device__ __forceinline__ maxsim_i32x4 maxsim_i8_qfrag(const unsigned char* qrow, uint32_t off, uint32_t K) {
+    maxsim_i32x4 v = {0, 0, 0, 0};
+    if (off < K) v = *reinterpret_cast<const maxsim_i32x4*>(qrow + off);
+    return v;
+}
+
+// v of this lane and of the lane 32 away: v_permlane32_swap of a register with itself leaves (own | lower half's) and (upper half's | own)
+__device__ __forceinline__ void maxsim_i8_halves(float v, float& from_lo, float& from_hi) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    from_lo = __uint_as_float(r[0]);   // lanes 32..63: the value of lane - 32; lanes 0..31: their own
+    from_hi = __uint_as_float(r[1]);   // lanes 0..31: the value of lane + 32; lanes 32..63: their own
+}
+// Rule 4" within a tile: the balanced pairwise tree over the 32 column lanes of a half, as a butterfly — an f32 add commutes, so
+// every lane ends with the bits of the tree's root.  Lanes 1, 2 apart by quad_perm, 4 and 8 apart by the mirrors (the lanes of a
+// finished level agree, so the mirror's partner holds the partner group's sum), 16 apart by ds_swizzle.
+__device__ __forceinline__ LY_MAXSIM_FN float maxsim_i8_tree(float m) {
+    m = m + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
+    m = m + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
+    m = m + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x141, 0xf, 0xf, false));   // row_half_mirror
+    m = m + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), 0x140, 0xf, 0xf, false));   // row_mirror
+    return m + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(m), 0x401F));                    // lane ^ 16
+}
+
+// NT = query tiles of 32 rows the LDS holds (1, 2, 4 or 8); a query of fewer tiles skips the rest.  grid.x strides over the ranges,
+// grid.y is the query; 4 waves.  RING - 1 = the chunks a load runs ahead (DESIGN.md §30 has the register report behind the choice).
+template <int NT>
+__global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_i8(MaxSimI8Args x) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm_maxsim_i8[];
+    constexpr int RING = NT <= 2 ? 4 : 3;
+    constexpr uint32_t KC = MAXSIM_I8_KC;
+    const MaxSimArgsT<int8_t>& a = x.a;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = lane & 31u, half = lane >> 5;
+    const uint32_t wave = maxsim_uniform(tid >> 6), waves = blockDim.x >> 6;
+    const uint32_t K = a.ld, PB = maxsim_i8_pitch(K), nch = (K + KC - 1u) / KC;
+    const uint32_t q = blockIdx.y;
+    const uint64_t q_off = a.qdesc[2u * q];
+    const uint32_t tq = (uint32_t)a.qdesc[2u * q + 1u], tq_rows = (tq + 31u) / 32u * 32u;
+    unsigned char* q_l = sm_maxsim_i8;
+    float* sq_l = reinterpret_cast<float*>(q_l + (size_t)NT * MAXSIM_BLOCK * PB);
+    uint32_t* flag_l = reinterpret_cast<uint32_t*>(sq_l + NT * MAXSIM_BLOCK) + wave * MAXSIM_BLOCK;
+    // the query tiles by rule 1", 8 lanes a row and 32 rows of the workgroup a trip: the row's amax over its 16-B pieces, then the
+    // codes of those pieces (the row comes from the cache the second time); rows past the query's own tiles are never read
+    {
+        const uint32_t g = tid & 7u, c16n = K / 16u;
+        for (uint32_t r = tid >> 3; r < tq_rows; r += blockDim.x >> 3) {   // (uniform over a wave's groups of 8: tq_rows is a multiple of 32)
+            const float* src = a.Q + q_off + (size_t)r * K;
+            float amax = 0.0f;
+            for (uint32_t c = g; c < c16n; c += 8u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(src + c * 16u + e * 4);
+                    amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                }
+#pragma unroll
+            for (uint32_t d = 1; d < 8u; d <<= 1) amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ d));
+            float inv, s;
+            maxsim_i8_scale(amax, inv, s);
+            if (g == 0u) sq_l[r] = s;
+            for (uint32_t c = g; c < c16n; c += 8u) {
+                u32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = maxsim_i8_pack(*reinterpret_cast<const f32x4*>(src + c * 16u + e * 4), inv);
+                *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = o;
+            }
+        }
+    }
+    __syncthreads();   // the only workgroup barrier: from here on the waves run their own ranges
+    // this lane's query column: row `col` of each tile, its scale (+0 and never used past the query's tokens) and its fragment bytes
+    const unsigned char* qa = q_l + (size_t)col * PB;
+    float sq[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sq[t] = (uint32_t)t * 32u + col < tq ? sq_l[(uint32_t)t * 32u + col] : 0.0f;
+    // one tile: the fragments of the first chunk stay in registers for the whole kernel — up to 128 columns the loop reads no LDS
+    maxsim_i32x4 qreg[4];
+    if constexpr (NT == 1) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) qreg[f] = maxsim_i8_qfrag(qa, (uint32_t)(f >> 1) * 64u + half * 32u + (uint32_t)(f & 1) * 16u, K);
+    }
+    const float NINF = -__builtin_huge_valf();
+    for (uint32_t r = blockIdx.x * waves + wave; r < a.n_ranges; r += gridDim.x * waves) {
+        const uint32_t ca = maxsim_uniform(a.ranges[r]), cb = maxsim_uniform(a.ranges[r + 1u]);
+        const uint64_t t0 = maxsim_uniform(a.cptr[ca]), t1 = maxsim_uniform(a.cptr[cb]);
+        const uint32_t nb = (uint32_t)((t1 - t0 + MAXSIM_BLOCK - 1u) / MAXSIM_BLOCK);
+        maxsim_i32x4 buf[RING][4];
+        uint32_t lb = 0, lc = 0;   // the load cursor: block and chunk, RING - 1 chunks ahead of (b, c)
+#pragma unroll
+        for (int i = 0; i < RING - 1; ++i) {
+            maxsim_i8_load(x, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc * KC, col, half, buf[i]);
+            if (++lc == nch) lc = 0, ++lb;
+        }
+        uint32_t rc0 = ca;   // the record of the block's first token
+        float run[NT];       // the maximum so far of the record that is open, ONE register a tile: it runs on from block to block
+        maxsim_i32x16 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) run[t] = NINF;
+        uint64_t rec_end = ~0ull;
+        uint32_t b = 0, c = 0;
+        while (b < nb) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {
+                if (b < nb) {
+                    const uint64_t tb = t0 + (uint64_t)b * MAXSIM_BLOCK;
+                    const uint32_t nrows = t1 - tb < MAXSIM_BLOCK ? (uint32_t)(t1 - tb) : MAXSIM_BLOCK;   // rows of the block inside the range
+                    const bool last = c + 1u == nch;
+                    if (c == 0u) {
+                        // the ends of the records from rc0 on, asked for BEFORE the chunk ahead: the epilogue's wait then leaves that one in flight
+                        rec_end = ~0ull;
+                        if (lane < 32u && (uint64_t)rc0 + 1u + lane <= cb) rec_end = a.cptr[rc0 + 1u + lane];
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) acc[t] = maxsim_i32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    }
+                    // the scales of this half's 16 rows (register v is row 8 (v / 4) + 4 half + v % 4), ahead of the block's last MFMAs;
+                    // rows past the range are not read
+                    f32x4 sc[4];
+                    if (last) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const uint32_t r0 = 8u * g + 4u * half;
+                            if (r0 + 4u <= nrows) {
+                                sc[g] = *reinterpret_cast<const maxsim_f32x4_u*>(x.scales + tb + r0);
+                            } else {
+#pragma unroll
+                                for (uint32_t e = 0; e < 4u; ++e) sc[g][e] = r0 + e < nrows ? x.scales[tb + r0 + e] : 0.0f;
+                            }
+                        }
+                    }
+                    maxsim_i8_load(x, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc * KC, col, half, buf[(i + RING - 1) % RING]);
+                    if (++lc == nch) lc = 0, ++lb;
+                    const uint32_t kc = c * KC;
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) {
+                        const uint32_t off = kc + (uint32_t)(f >> 1) * 64u;   // the column group of 64; half h of it, bytes 16 (f & 1) ..
+                        if (off >= K) continue;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                            maxsim_i32x4 bv;
+                            if (NT == 1 && c == 0u) bv = qreg[f];
+                            else bv = maxsim_i8_qfrag(qa + (size_t)t * 32u * PB, off + half * 32u + (uint32_t)(f & 1) * 16u, K);
+                            acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(buf[i][f], bv, acc[t], 0, 0, 0);
+                        }
+                    }
+                    if (last) {   // the block's last chunk: rules 2" - 4", the scores of the records that end in it
+                        const MaxSimBounds bd = maxsim_h16_bounds(rec_end, tb, b + 1u < nb, lane, col, flag_l);
+                        // v_ij = f32(d_ij) * s_j in place of the sums
+                        float v[NT][16];
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+#pragma unroll
+                            for (int k = 0; k < 16; ++k) v[t][k] = (float)acc[t][k] * sc[k >> 2][k & 3];
+                        }
+                        // down the 32 rows in groups of 8: rows 8 g .. 8 g + 3 are registers 4 g .. of half 0, the next four of half 1
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            if (8u * g >= nrows) continue;
+                            if (8u * g + 8u <= nrows && ((bd.endmask >> (8 * g)) & 0xffu) == 0u) {
+                                // no record ends in these 8 rows: each half folds its own four, one exchange joins them in both halves
+#pragma unroll
+                                for (int t = 0; t < NT; ++t) {
+                                    if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                                    const float m4 = fmaxf(fmaxf(v[t][4 * g], v[t][4 * g + 1]), fmaxf(v[t][4 * g + 2], v[t][4 * g + 3]));
+                                    float lo, hi;
+                                    maxsim_i8_halves(m4, lo, hi);
+                                    run[t] = fmaxf(run[t], fmaxf(lo, hi));
+                                }
+                                continue;
+                            }
+#pragma unroll
+                            for (int o = 0; o < 2; ++o) {   // the owning half of rows 8 g + 4 o ..: its lanes hold the record's maximum so far
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const uint32_t row = 8u * g + 4u * o + e;
+                                    if (row >= nrows) continue;
+#pragma unroll
+                                    for (int t = 0; t < NT; ++t) {
+                                        if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                                        run[t] = fmaxf(run[t], v[t][4 * g + e]);
+                                    }
+                                    if ((bd.endmask >> row) & 1u) {   // a record ends here: rules 3" and 4" in the owning half
+                                        float s = 0.0f;
+#pragma unroll
+                                        for (int t = 0; t < NT; ++t) {
+                                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                                            const float tile = maxsim_i8_tree((uint32_t)t * 32u + col < tq ? sq[t] * run[t] : 0.0f);
+                                            s = t == 0 ? tile : s + tile;
+                                            run[t] = NINF;
+                                        }
+                                        if (lane == 32u * o) {
+                                            const uint32_t cr = rc0 + (uint32_t)__popc(bd.endmask & ((1u << row) - 1u));
+                                            const bool live = !a.mask || range_live(a.mask, a.mask_words, a.crec[cr]);
+                                            a.S[(size_t)q * a.m + cr] = live ? score_ord(s, false) : RANGE_FAIL;
+                                        }
+                                    }
+                                }
+                                // hand the maximum so far to the other half, which owns the next four rows (both halves agree after it)
+#pragma unroll
+                                for (int t = 0; t < NT; ++t) {
+                                    if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                                    float lo, hi;
+                                    maxsim_i8_halves(run[t], lo, hi);
+                                    run[t] = o == 0 ? lo : hi;
+                                }
+                            }
+                        }
+                        rc0 += bd.n_adv;
+                        c = 0u;
+                        ++b;
+                    } else {
+                        ++c;
+                    }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace lynse

@@ -10,7 +10,10 @@ struct lynse_hip_multivec {
     hipStream_t stream = nullptr;
     uint32_t dim = 0, ld = 0;
     int dtype = 0;                          // 0: f32 rows in `tokens`, k_maxsim_scan; 1: f16 rows in `tokens_h`, k_maxsim_h16 (same pitch in elements)
+                                            // 2 (internal, lynse_hip_multivec_create_i8): codes in `tokens_i8` + `scales`, k_maxsim_i8
     DevBuf<uint16_t> tokens_h;
+    DevBuf<uint8_t> tokens_i8;
+    DevBuf<float> scales;
     uint64_t n = 0, total = 0;              // records (those without tokens included), token rows
     // the records that have tokens, which are all the kernel sees: their token offsets, their record rows, and the wave ranges
     std::vector<uint64_t> cptr{0};
@@ -72,12 +75,47 @@ extern "C" int lynse_hip_multivec_plan_dtype(uint32_t dim, uint32_t tq, int dtyp
     return LYNSE_OK;
 }
 
+// Rule 7" of the int8 store, host only: the LDS holds the query tiles as codes at a row pitch of ld + 16 bytes, their scales and 32
+// flags per wave; the waves are always 4 and every dimension up to 1024 serves a query of up to 128 tokens.
+extern "C" int lynse_hip_multivec_plan_i8(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
+    if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
+    if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
+    if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
+    uint32_t tiles = 1;
+    while (tiles * 32u < tq) tiles *= 2;
+    const size_t lds = maxsim_i8_lds_bytes(maxsim_ld(dim), tiles);
+    if (lds > PoolRerank::LDS_MAX)
+        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) of int8 tokens of dimension " +
+                                                    std::to_string(dim) + " do not fit in LDS");
+    if (out_tiles) *out_tiles = tiles;
+    if (out_waves) *out_waves = MAXSIM_MAX_WAVES;
+    if (out_lds_bytes) *out_lds_bytes = lds;
+    return LYNSE_OK;
+}
+
+// the plan by the handle's tag: 0 and 1 are the public dtype ids, 2 is the int8 store
+static int maxsim_plan(uint32_t dim, uint32_t tq, int tag, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    if (tag == 2) return lynse_hip_multivec_plan_i8(dim, tq, out_tiles, out_waves, out_lds_bytes);
+    return lynse_hip_multivec_plan_dtype(dim, tq, tag, out_tiles, out_waves, out_lds_bytes);
+}
+
+static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out);
+
 extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_multivec** out) { return lynse_hip_multivec_create_dtype(device, dim, 0, out); }
 
 extern "C" int lynse_hip_multivec_create_dtype(int device, uint32_t dim, int dtype, lynse_hip_multivec** out) {
+    if (out) *out = nullptr;
+    if (out && dtype != 0 && dtype != 1) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dtype must be 0 (f32) or 1 (f16)");
+    return maxsim_create(device, dim, dtype, out);
+}
+
+extern "C" int lynse_hip_multivec_create_i8(int device, uint32_t dim, lynse_hip_multivec** out) { return maxsim_create(device, dim, 2, out); }
+
+static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out) {
     if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    LY_TRY(lynse_hip_multivec_plan_dtype(dim, 1, dtype, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
+    LY_TRY(maxsim_plan(dim, 1, dtype, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
     int ndev = 0;
     LY_TRY(lynse_hip_device_count(&ndev));
     if (ndev <= 0) return set_error(LYNSE_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
@@ -184,6 +222,35 @@ static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16
         }
         LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
     }
+    if (add && h->dtype == 2) {
+        // both arrays grow together; a fresh pair replaces the held one only once both exist
+        if (total > h->tokens_i8.cap / ld || total > h->scales.cap) {
+            const uint64_t cap = std::max<uint64_t>(total, 2 * h->total);
+            DevBuf<uint8_t> grown;
+            DevBuf<float> grown_s;
+            LY_TRY(grown.alloc((size_t)cap * ld));
+            LY_TRY(grown_s.alloc((size_t)cap));
+            if (h->total) {
+                LY_HIP(hipMemcpy(grown.p, h->tokens_i8.p, (size_t)h->total * ld, hipMemcpyDeviceToDevice));
+                LY_HIP(hipMemcpy(grown_s.p, h->scales.p, (size_t)h->total * 4, hipMemcpyDeviceToDevice));
+            }
+            LY_HIP(hipStreamSynchronize(nullptr));
+            h->tokens_i8 = std::move(grown);
+            h->scales = std::move(grown_s);
+        }
+        // the f32 rows as given go up once; the device quantises them at the store's pitch (k_maxsim_store_i8: rule 1", zero columns)
+        DevBuf<float> raw;
+        LY_TRY(raw.alloc((size_t)add * D));
+        LY_TRY(h2d_done(raw.p, tokens, (size_t)add * D * 4));
+        const uint64_t step = (1ull << 30) / ld;   // rows of a launch: its grid stays below 2^26 workgroups
+        for (uint64_t r0 = 0; r0 < add; r0 += step) {
+            const uint64_t rows = std::min<uint64_t>(step, add - r0);
+            hipLaunchKernelGGL(k_maxsim_store_i8, dim3((uint32_t)((rows + 15) / 16)), dim3(256), 0, nullptr, raw.p + (size_t)r0 * D,
+                               reinterpret_cast<uint32_t*>(h->tokens_i8.p + (size_t)(h->total + r0) * ld), h->scales.p + h->total + r0, rows, D, ld);
+            LY_HIP(hipGetLastError());
+        }
+        LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
+    }
     if (add && h->dtype == 0) {
         if (total > h->tokens.cap / ld) {   // grow: the rows held move to the new block
             DevBuf<float> grown;
@@ -256,6 +323,14 @@ static int maxsim_launch(const MaxSimArgs& a, dim3 grid, uint32_t waves, size_t 
 }
 
 template <int NT>
+static int maxsim_i8_launch(const MaxSimI8Args& a, dim3 grid, size_t lds, hipStream_t st) {
+    LY_TRY(ensure_lds<k_maxsim_i8<NT>>(PoolRerank::LDS_MAX));
+    hipLaunchKernelGGL(k_maxsim_i8<NT>, grid, dim3(MAXSIM_MAX_WAVES * 64u), lds, st, a);
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
+
+template <int NT>
 static int maxsim_h16_launch(const MaxSimH16Args& a, dim3 grid, size_t lds, hipStream_t st) {
     LY_TRY(ensure_lds<k_maxsim_h16<NT>>(PoolRerank::LDS_MAX));
     hipLaunchKernelGGL(k_maxsim_h16<NT>, grid, dim3(MAXSIM_MAX_WAVES * 64u), lds, st, a);
@@ -297,12 +372,13 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
     }
     uint32_t tiles = 0, waves = 0;
     uint64_t lds = 0;
-    const bool h16 = h->dtype == 1;
-    LY_TRY(lynse_hip_multivec_plan_dtype(D, tq_max, h->dtype, &tiles, &waves, &lds));
+    const bool h16 = h->dtype == 1, i8 = h->dtype == 2;
+    LY_TRY(maxsim_plan(D, tq_max, h->dtype, &tiles, &waves, &lds));
     // workgroups a CU can hold by their LDS (the registers allow one wave per SIMD at 8 tiles, two or three below): the grid's width
     uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
     // (k_maxsim_h16, a workgroup = one wave per SIMD: by registers two waves per SIMD at 1 and 2 tiles, one above — resource_usage.txt)
-    if (h16) wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles <= 2 ? 2u : 1u);
+    // (k_maxsim_i8 likewise: 166 + 16 and 196 + 32 registers at 1 and 2 tiles are two waves per SIMD, 236 + 64 and 256 + 245 above are one)
+    if (h16 || i8) wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles <= 2 ? 2u : 1u);
     const uint32_t N = (uint32_t)std::min<uint64_t>(k, live);
     const uint64_t qc = ScoreCut::chunk(nq, m, N);
     const bool sort_dev = N <= 16384;
@@ -349,7 +425,15 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
                            bitset_words ? h->mask.p : nullptr, mask_words, h->cut.S.p};
         const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
         if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
-        if (h16) {   // the same tables and queries, the token rows as halves
+        if (i8) {   // the same tables and queries, the token rows as codes with a scale each
+            const MaxSimI8Args ai{{reinterpret_cast<const int8_t*>(h->tokens_i8.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S}, h->scales.p};
+            switch (tiles) {
+            case 1: LY_TRY(maxsim_i8_launch<1>(ai, grid, lds, st)); break;
+            case 2: LY_TRY(maxsim_i8_launch<2>(ai, grid, lds, st)); break;
+            case 4: LY_TRY(maxsim_i8_launch<4>(ai, grid, lds, st)); break;
+            default: LY_TRY(maxsim_i8_launch<8>(ai, grid, lds, st)); break;
+            }
+        } else if (h16) {   // the same tables and queries, the token rows as halves
             const MaxSimH16Args ah{reinterpret_cast<const _Float16*>(h->tokens_h.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S};
             switch (tiles) {
             case 1: LY_TRY(maxsim_h16_launch<1>(ah, grid, lds, st)); break;
@@ -369,7 +453,7 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
             LY_HIP(hipEventRecord(h->ev[1], st));
             h->prof.scan_launches += 1;
             h->prof.scan_rows += h->total * nqc;
-            h->prof.scan_bytes += (h->total * ld * (h16 ? 2 : 4) + (m + 1) * 8) * nqc;
+            h->prof.scan_bytes += (h->total * (i8 ? ld + 4 : ld * (h16 ? 2 : 4)) + (m + 1) * 8) * nqc;
         }
         // more live records than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
         h->cut.sel0.assign(nqc, select ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
