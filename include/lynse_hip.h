@@ -1153,6 +1153,34 @@ int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec *h, const float *q_t
 int lynse_hip_multivec_profile_enable(lynse_hip_multivec *h, int on);
 int lynse_hip_multivec_profile_get(lynse_hip_multivec *h, lynse_hip_profile *out, int reset);
 
+/* MULTI-VECTOR RERANK (this build's addition).  MaxSim over PER-QUERY candidate lists: query i is scored against the records
+ * cand_rows[cand_ptr[i] .. cand_ptr[i + 1]) and nothing else of the store is read.  On an f16 or int8 store the scores come from
+ * k_maxsim_cand_h16 / k_maxsim_cand_i8: one wave per (query, candidate record), the record's token rows fetched straight into the
+ * MFMA operand registers.  The rules of the store's dtype (1 - 4, 1' - 2', 1" - 4") define the score; what is added:
+ *  1. cand_rows are record rows, STRICTLY ASCENDING inside each query's list; cand_ptr[0] = 0 and cand_ptr does not descend.  A
+ *     descending or repeated row, or a row >= n, is LYNSE_ERR_INVALID_ARGUMENT before any device work.
+ *  2. Order of the checks: the pointers and the queries (as lynse_hip_multivec_search_f32: q_ptr, 1 <= tokens of a query <= 256),
+ *     cand_ptr, the order of each list — none of which needs a store — then the handle, the rows against n, the plan's refusal of
+ *     the store's dtype (rule 7 / 7' / 7").
+ *  3. A listed record without tokens is dropped (rule 5); an empty list gives out_counts[q] = 0.
+ *  4. Result: the best min(k, scored candidates of the query) by rule 6 — score descending, record row ascending, NaN as -inf, -0 as
+ *     +0 — at stride k, out_counts[q] entries valid.
+ *  5. int8 store: the score bits of a record equal those of lynse_hip_multivec_search_f32 (every step of rules 1" - 4" is exact or
+ *     one f32 rounding).  f16 store: rules 3 and 4 are followed to the letter; the order inside rule 2' is the hardware's for either
+ *     kernel, and the token rows are the A operand here, the B operand in the scan.
+ *  6. f32 store: NO candidate kernel exists for it in this build.  The entry answers by running the scan once per query with that
+ *     query's candidates as the BitSet: the same results, at the cost of one full scan a query.
+ *  7. The lock, the stream and the scratch are the handle's (rule 8 of the search).  Profile: scan_launches counts the candidate
+ *     launches, scan_rows / scan_bytes the token rows and bytes they actually read (the listed records' rows, their list entries and
+ *     extents), last_plan = 1 when the last profiled chunk ran a candidate kernel, 0 for the scan.
+ *  8. Routing of lynse_hip_multivec_search_bitset_f32: on an int8 or f16 store, a mask whose live records hold at most 1/4 of the
+ *     store's token rows is answered by the candidate kernel (the live records are one list shared by the call's queries).  int8:
+ *     bit-identical by rule 5.  f16: the two kernels' score bits were compared on Gaussian data on the MI355X and agreed on every
+ *     record, which is why such stores are routed; the contract for f16 remains rule 2'. */
+int lynse_hip_multivec_rerank_f32(lynse_hip_multivec *h, const float *q_tokens, const uint64_t *q_ptr /* nq+1 */, uint64_t nq, uint32_t k,
+                                  const uint64_t *cand_rows /* cand_ptr[nq] */, const uint64_t *cand_ptr /* nq+1 */,
+                                  uint64_t *out_rows /* nq*k */, float *out_scores, uint32_t *out_counts /* nq */);
+
 /* ---- text search: InvertedTextIndex (src/engine.rs:720-1118), index mode BM25-INVERTED ---- */
 
 /* TEXT SEARCH (Collection::text_search, src/engine.rs:5056-5076, over InvertedTextIndex::search, :927-1054).  The caller tokenises

@@ -263,6 +263,7 @@ SIGNATURES = {
     "lynse_hip_multivec_counts": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "lynse_hip_multivec_search_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "lynse_hip_multivec_search_bitset_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "lynse_hip_multivec_rerank_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "lynse_hip_multivec_profile_enable": (C.c_int, [_vp, C.c_int]),
     "lynse_hip_multivec_profile_get": (C.c_int, [_vp, C.POINTER(Profile), C.c_int]),
 }

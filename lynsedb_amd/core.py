@@ -1734,6 +1734,32 @@ class MultiVectorIndex:
                                                            _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
+    def rerank_batch_arrays(self, queries, cand_rows_list, k: int):
+        """MaxSim over per-query candidate lists (include/lynse_hip.h, MULTI-VECTOR RERANK): query i against the record rows
+        cand_rows_list[i], strictly ascending, and nothing else of the store -> (rows u64[nq, k], scores f32[nq, k], counts u32[nq])
+        by (score descending, record row ascending).  f16 / i8 stores run k_maxsim_cand_h16 / k_maxsim_cand_i8; an f32 store runs the
+        scan once per query with the list as its mask."""
+        queries = _multivec_queries(queries, self._dim, self.dtype)
+        nq, k = len(queries), int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        if len(cand_rows_list) != nq:
+            raise ValueError(f"candidate lists ({len(cand_rows_list)}) must match the queries ({nq})")
+        lists = [np.ascontiguousarray(np.asarray(c).reshape(-1), dtype=np.uint64) for c in cand_rows_list]
+        rows = np.full((nq, k), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+        scores = np.full((nq, k), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        if nq == 0:
+            return rows, scores, counts
+        q_ptr, c_ptr = np.zeros(nq + 1, np.uint64), np.zeros(nq + 1, np.uint64)
+        np.cumsum([q.shape[0] for q in queries], out=q_ptr[1:])
+        np.cumsum([c.size for c in lists], out=c_ptr[1:])
+        tokens = np.ascontiguousarray(np.concatenate(queries))
+        cand = np.ascontiguousarray(np.concatenate(lists))
+        check(lib.lynse_hip_multivec_rerank_f32(self._h, _ptr(tokens), _ptr(q_ptr), nq, k, _ptr(cand) if cand.size else None, _ptr(c_ptr),
+                                                _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
     def profile_enable(self, on=True) -> None:
         check(lib.lynse_hip_multivec_profile_enable(self._h, int(bool(on))))
 
@@ -3300,6 +3326,37 @@ class Collection:
         fit the LDS next to the token blocks: more than 128 tokens above dim_mv 96, more than 64 above 192, more than 32 above 288."""
         return self.batch_search_multi_vector([query_tokens], k, where=where, subset=subset)[0]
 
+    def batch_rerank_multi_vector(self, queries, id_lists, k: Optional[int] = None) -> list:
+        """`rerank_multi_vector` for a list of query token arrays, each with a candidate id list of its own, in ONE device call."""
+        if k is not None and int(k) < 0:
+            raise OverflowError("can't convert negative int to unsigned")
+        queries = _multivec_queries(queries, self._mv_dim, self._mv_dtype)
+        if len(id_lists) != len(queries):
+            raise RuntimeError(f"Invalid argument: id lists ({len(id_lists)}) must match the queries ({len(queries)})")
+        mv_ids = np.asarray(self._mv_ids, dtype=np.int64)
+        gone = self._tombstone | self._mv_dead
+        gone = np.fromiter(gone, dtype=np.int64, count=len(gone))
+        lists = []
+        for ids in id_lists:   # user ids in any order -> ascending record rows: duplicates collapse, unknown / deleted / compacted ids drop out
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            lists.append(np.nonzero(np.isin(mv_ids, ids[~np.isin(ids, gone)]))[0].astype(np.uint64))
+        longest = max((c.size for c in lists), default=0)
+        k = longest if k is None else int(k)
+        mode = _multivec_mode(self._mv_dtype)
+        if k == 0 or longest == 0:   # the device is not touched
+            return [SearchResult(np.zeros(0, np.int64), np.zeros(0, np.float32), mode, self._mv_dim or 0, k) for _ in queries]
+        self._mv_upload()
+        rows, scores, counts = self._mv_index.rerank_batch_arrays(queries, lists, k)
+        return [SearchResult(mv_ids[rows[i, :int(c)].astype(np.int64)], scores[i, :int(c)].copy(), mode, self._mv_dim, k)
+                for i, c in enumerate(counts)]
+
+    def rerank_multi_vector(self, query_tokens, ids, k: Optional[int] = None) -> SearchResult:
+        """MaxSim over a candidate list: the second stage behind `search`, `text_search`, `hybrid_search` or a filter.  `ids` are user
+        ids in any order (duplicates collapse; ids that are unknown, deleted, compacted away or without a token set are left out); only
+        their token sets are read.  The best k (None: every scored candidate) by (score descending, record row ascending), as a
+        `search_multi_vector` result with the store's mode.  An f32 store is answered by one masked scan per query."""
+        return self.batch_rerank_multi_vector([query_tokens], [ids], k)[0]
+
     def search_multi_vector_profile(self, query_tokens, k: Optional[int] = None, where=None, subset=None) -> dict:
         """`search_multi_vector` + what the handle measured with HIP events on its stream: the `device.multivec` entry of `search_profile`."""
         import time
@@ -3321,7 +3378,7 @@ class Collection:
                         scan_launches=int(dev["scan_launches"]) if dev else 0, scan_rows=int(dev["scan_rows"]) if dev else 0,
                         scan_bytes=int(dev["scan_bytes"]) if dev else 0)
         return {"items": {"k": res._k, "ids": [int(x) for x in res.ids()], "scores": [float(x) for x in res.distances()], "index": res.index_mode()},
-                "profile": {"query_kind": "multi_vector", "index_path": "multivec_scan", "total_vectors": len(self._mv_ids), "result_count": len(res),
+                "profile": {"query_kind": "multi_vector", "index_path": "multivec_candidates" if dev and dev["last_plan"] == 1 else "multivec_scan", "total_vectors": len(self._mv_ids), "result_count": len(res),
                             "total_us": int((time.perf_counter() - t0) * 1e6), "device": {"multivec": multivec}}}
 
     # -- text search (engine.rs:5056-5161, :927-1054) -------------------------------------------

@@ -358,6 +358,23 @@ __device__ __forceinline__ LY_MAXSIM_FN void maxsim_h16_fold(const f32x16& acc, 
         }
 }
 
+// The query tiles of a workgroup into LDS as halves (rule 1 on the way), `rows` rows at pitch PB, zero rows past the query's own:
+// 16-B pieces of 8 columns.  Shared by k_maxsim_h16 and k_maxsim_cand_h16.
+__device__ __forceinline__ void maxsim_h16_stage(const float* Q, uint32_t tq_rows, uint32_t rows, uint32_t K, uint32_t PB, unsigned char* q_l, uint32_t tid) {
+    const uint32_t c8n = K / 8u;
+    for (uint32_t p = tid; p < rows * c8n; p += blockDim.x) {
+        const uint32_t r = p / c8n, c = p - r * c8n;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (r < tq_rows) {
+            const float* src = Q + (size_t)r * K + c * 8u;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+            v = u32x4{maxsim_h16_of(lo[0]) | (maxsim_h16_of(lo[1]) << 16), maxsim_h16_of(lo[2]) | (maxsim_h16_of(lo[3]) << 16),
+                      maxsim_h16_of(hi[0]) | (maxsim_h16_of(hi[1]) << 16), maxsim_h16_of(hi[2]) | (maxsim_h16_of(hi[3]) << 16)};
+        }
+        *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = v;
+    }
+}
+
 // NT = query tiles of 32 rows the LDS holds (1, 2, 4 or 8); a query of fewer tiles skips the rest.  grid.x strides over the ranges,
 // grid.y is the query; blockDim.x / 64 waves.  RING - 1 = the chunks a load runs ahead: two while the accumulators and carried maxima
 // of the tiles leave the registers for a third buffer, one from 4 tiles on.
@@ -375,19 +392,7 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_h
     const uint32_t tq = (uint32_t)a.qdesc[2u * q + 1u], tq_rows = (tq + 31u) / 32u * 32u;
     unsigned char* q_l = sm_maxsim_h16;
     uint32_t* flag_l = reinterpret_cast<uint32_t*>(q_l + (size_t)NT * MAXSIM_BLOCK * PB) + wave * MAXSIM_BLOCK;
-    // the query tiles as halves (rule 1 on the way), zero rows past the query's own: 16-B pieces of 8 columns
-    const uint32_t c8n = K / 8u;
-    for (uint32_t p = tid; p < (uint32_t)NT * 32u * c8n; p += blockDim.x) {
-        const uint32_t r = p / c8n, c = p - r * c8n;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (r < tq_rows) {
-            const float* src = a.Q + q_off + (size_t)r * K + c * 8u;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            v = u32x4{maxsim_h16_of(lo[0]) | (maxsim_h16_of(lo[1]) << 16), maxsim_h16_of(lo[2]) | (maxsim_h16_of(lo[3]) << 16),
-                      maxsim_h16_of(hi[0]) | (maxsim_h16_of(hi[1]) << 16), maxsim_h16_of(hi[2]) | (maxsim_h16_of(hi[3]) << 16)};
-        }
-        *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = v;
-    }
+    maxsim_h16_stage(a.Q + q_off, tq_rows, (uint32_t)NT * 32u, K, PB, q_l, tid);
     __syncthreads();   // the only workgroup barrier: from here on the waves run their own ranges
     // this lane's query fragments: row `col` of a tile, the bytes of its halves 16 half .. of each column group
     const unsigned char* qa = q_l + (size_t)col * PB + half * 32u;
@@ -597,6 +602,34 @@ __device__ __forceinline__ LY_MAXSIM_FN float maxsim_i8_tree(float m) {
     return m + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(m), 0x401F));                    // lane ^ 16
 }
 
+// The query tiles of a workgroup into LDS by rule 1", 8 lanes a row and 32 rows of the workgroup a trip: the row's amax over its 16-B
+// pieces, then the codes of those pieces (the row comes from the cache the second time) and the scale; rows past the query's own
+// tiles are never read.  Shared by k_maxsim_i8 and k_maxsim_cand_i8.
+__device__ __forceinline__ void maxsim_i8_stage(const float* Q, uint32_t tq_rows, uint32_t K, uint32_t PB, unsigned char* q_l, float* sq_l, uint32_t tid, uint32_t lane) {
+    const uint32_t g = tid & 7u, c16n = K / 16u;
+    for (uint32_t r = tid >> 3; r < tq_rows; r += blockDim.x >> 3) {   // (uniform over a wave's groups of 8: tq_rows is a multiple of 32)
+        const float* src = Q + (size_t)r * K;
+        float amax = 0.0f;
+        for (uint32_t c = g; c < c16n; c += 8u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(src + c * 16u + e * 4);
+                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            }
+#pragma unroll
+        for (uint32_t d = 1; d < 8u; d <<= 1) amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ d));
+        float inv, s;
+        maxsim_i8_scale(amax, inv, s);
+        if (g == 0u) sq_l[r] = s;
+        for (uint32_t c = g; c < c16n; c += 8u) {
+            u32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = maxsim_i8_pack(*reinterpret_cast<const f32x4*>(src + c * 16u + e * 4), inv);
+            *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = o;
+        }
+    }
+}
+
 // NT = query tiles of 32 rows the LDS holds (1, 2, 4 or 8); a query of fewer tiles skips the rest.  grid.x strides over the ranges,
 // grid.y is the query; 4 waves.  RING - 1 = the chunks a load runs ahead (DESIGN.md §30 has the register report behind the choice).
 template <int NT>
@@ -614,32 +647,7 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_i
     unsigned char* q_l = sm_maxsim_i8;
     float* sq_l = reinterpret_cast<float*>(q_l + (size_t)NT * MAXSIM_BLOCK * PB);
     uint32_t* flag_l = reinterpret_cast<uint32_t*>(sq_l + NT * MAXSIM_BLOCK) + wave * MAXSIM_BLOCK;
-    // the query tiles by rule 1", 8 lanes a row and 32 rows of the workgroup a trip: the row's amax over its 16-B pieces, then the
-    // codes of those pieces (the row comes from the cache the second time); rows past the query's own tiles are never read
-    {
-        const uint32_t g = tid & 7u, c16n = K / 16u;
-        for (uint32_t r = tid >> 3; r < tq_rows; r += blockDim.x >> 3) {   // (uniform over a wave's groups of 8: tq_rows is a multiple of 32)
-            const float* src = a.Q + q_off + (size_t)r * K;
-            float amax = 0.0f;
-            for (uint32_t c = g; c < c16n; c += 8u)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(src + c * 16u + e * 4);
-                    amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-                }
-#pragma unroll
-            for (uint32_t d = 1; d < 8u; d <<= 1) amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ d));
-            float inv, s;
-            maxsim_i8_scale(amax, inv, s);
-            if (g == 0u) sq_l[r] = s;
-            for (uint32_t c = g; c < c16n; c += 8u) {
-                u32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = maxsim_i8_pack(*reinterpret_cast<const f32x4*>(src + c * 16u + e * 4), inv);
-                *reinterpret_cast<u32x4*>(q_l + (size_t)r * PB + c * 16u) = o;
-            }
-        }
-    }
+    maxsim_i8_stage(a.Q + q_off, tq_rows, K, PB, q_l, sq_l, tid, lane);
     __syncthreads();   // the only workgroup barrier: from here on the waves run their own ranges
     // this lane's query column: row `col` of each tile, its scale (+0 and never used past the query's tokens) and its fragment bytes
     const unsigned char* qa = q_l + (size_t)col * PB;
@@ -789,6 +797,242 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_i
             }
         }
     }
+}
+
+// ---- candidate lists (include/lynse_hip.h, MULTI-VECTOR RERANK) ----------------------------------------------------
+//   k_maxsim_cand_h16 / k_maxsim_cand_i8   MaxSim over per-query candidate lists: a gather, not the scan with an indirection.  A
+//                   work item is one (query, candidate record) pair and ONE WAVE owns it; the workgroups of a query (grid.y) take
+//                   its candidates grid-stride over grid.x.  A wave walks its record's token rows in blocks of 32; every block
+//                   belongs to one record, so nothing of the scans' boundary machinery exists here: rows past the record's end are
+//                   not read and are masked by the wave-uniform row count.  Operand roles for BOTH dtypes are §30's — the token rows
+//                   are A, the query tile B, a lane holds one query column and 16 token rows — so the max over a record's tokens is
+//                   v_max_f32 down the lane's own registers into one running register a tile, block after block, and ONE
+//                   v_permlane32_swap a tile and record joins the halves.  In bytes the two stores look alike: of each 64 bytes of a
+//                   row half h owns the 32 at 32 h, two 16-B fragments — so one body serves both, fragment f of a chunk in the
+//                   scan's k-step order.  The chunks of the wave's whole item stream go through one statically indexed ring, loaded
+//                   RING - 1 chunks ahead: the first loads of the next candidate are in flight before this record's epilogue.  The
+//                   extents of up to 64 items sit one per lane (loaded together), read by v_readlane as the two cursors cross records.
+//   S[q][slot] = the score_ord image of the slot-th candidate of query q, RANGE_FAIL in the slots past the query's list.
+struct MaxSimCandArgs {
+    const unsigned char* tokens;   // [total tokens][row bytes]: halves (2 ld) or codes (ld)
+    const float* scales;           // i8: [total tokens]
+    uint32_t ld;
+    const uint64_t* cptr;          // m + 1 token offsets of the records that have tokens
+    const uint32_t* cand;          // compact record numbers (indices into cptr), strictly ascending within a query's list
+    const uint64_t* cand_ptr;      // nq + 1 offsets into cand; NULL: cand[0 .. n_shared) is every query's list
+    uint32_t n_shared;
+    uint32_t pitch;                // slots of a query in S: the longest list
+    const float* Q;                // as for the scans
+    const uint64_t* qdesc;
+    uint32_t* S;                   // [nq][pitch]
+};
+
+template <bool I8> struct MaxSimCandAcc { using T = f32x16; };
+template <> struct MaxSimCandAcc<true> { using T = maxsim_i32x16; };
+
+__device__ __forceinline__ uint64_t maxsim_lane64(uint64_t v, uint32_t l) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+}
+
+// A position in the wave's item stream, wave-uniform: item j of the batch, the first token row of its current block, the record's
+// end, the chunk of the block.  step() moves on one chunk; true when that left the record (and entered the next, if there is one).
+struct MaxSimCursor {
+    uint32_t j, c;
+    uint64_t t, t_end;
+    __device__ __forceinline__ void enter(uint64_t e0, uint64_t e1) { t = maxsim_lane64(e0, j), t_end = maxsim_lane64(e1, j), c = 0u; }
+    __device__ __forceinline__ bool step(uint32_t nch, uint32_t nit, uint64_t e0, uint64_t e1) {
+        if (++c < nch) return false;
+        c = 0u, t += MAXSIM_BLOCK;
+        if (t < t_end) return false;
+        if (++j < nit) enter(e0, e1);
+        return true;
+    }
+};
+
+// One chunk of the cursor's block into a ring buffer: lane (col, half) takes, of each of the chunk's F / 2 groups of 64 row bytes,
+// the 32 at 32 half of token row cu.t + col.  Rows at or past the record's end and bytes past the row are zero and NOT read.
+template <int F>
+__device__ __forceinline__ void maxsim_cand_load(const unsigned char* tokens, uint32_t RB, const MaxSimCursor& cu, uint32_t col, uint32_t half, maxsim_i32x4 (&f)[F]) {
+    const bool in = cu.t + col < cu.t_end;
+    const uint32_t kcb = cu.c * (uint32_t)F * 32u + half * 32u;
+    const unsigned char* src = tokens + (size_t)(cu.t + col) * RB + kcb;
+#pragma unroll
+    for (int p = 0; p < F / 2; ++p) {
+        f[2 * p] = maxsim_i32x4{0, 0, 0, 0};
+        f[2 * p + 1] = maxsim_i32x4{0, 0, 0, 0};
+        if (in && kcb + (uint32_t)p * 64u < RB) {
+            f[2 * p] = *reinterpret_cast<const maxsim_i32x4*>(src + p * 64);
+            f[2 * p + 1] = *reinterpret_cast<const maxsim_i32x4*>(src + p * 64 + 16);
+        }
+    }
+}
+
+// NT = query tiles of 32 rows the LDS holds; I8: codes + scales and rules 2" - 4", else halves and rules 3, 4.  RING and the chunk
+// (F fragments of 16 B a lane) are those of the scan of the dtype.
+template <int NT, bool I8>
+__device__ __forceinline__ LY_MAXSIM_FN void maxsim_cand(const MaxSimCandArgs& a, unsigned char* q_l) {
+    constexpr int RING = I8 ? (NT <= 2 ? 4 : 3) : (NT <= 2 ? 3 : 2);
+    constexpr int F = I8 ? 4 : (NT == 8 ? 4 : 8);
+    constexpr uint32_t KCB = (uint32_t)F * 32u;   // row bytes of a chunk
+    using Acc = typename MaxSimCandAcc<I8>::T;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = lane & 31u, half = lane >> 5;
+    const uint32_t wave = maxsim_uniform(tid >> 6), waves = blockDim.x >> 6;
+    const uint32_t K = a.ld, RB = I8 ? K : 2u * K, PB = RB + 16u, nch = (RB + KCB - 1u) / KCB;   // (PB: maxsim_i8_pitch / maxsim_h16_pitch)
+    const uint32_t q = blockIdx.y;
+    const uint64_t q_off = a.qdesc[2u * q];
+    const uint32_t tq = (uint32_t)a.qdesc[2u * q + 1u], tq_rows = (tq + 31u) / 32u * 32u;
+    float* sq_l = reinterpret_cast<float*>(q_l + (size_t)NT * MAXSIM_BLOCK * PB);
+    if constexpr (I8) maxsim_i8_stage(a.Q + q_off, tq_rows, K, PB, q_l, sq_l, tid, lane);
+    else maxsim_h16_stage(a.Q + q_off, tq_rows, (uint32_t)NT * 32u, K, PB, q_l, tid);
+    __syncthreads();   // the only barrier
+    // this lane's query column: row `col` of each tile, its bytes at 32 half of each group of 64; i8: its scale
+    const unsigned char* qa = q_l + (size_t)col * PB + half * 32u;
+    float sq[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sq[t] = I8 && (uint32_t)t * 32u + col < tq ? sq_l[(uint32_t)t * 32u + col] : 0.0f;
+    maxsim_i32x4 qreg[F];   // one tile: the fragments of the first chunk stay in registers
+    if constexpr (NT == 1) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            qreg[f] = maxsim_i32x4{0, 0, 0, 0};
+            if ((uint32_t)(f >> 1) * 64u + half * 32u < RB) qreg[f] = *reinterpret_cast<const maxsim_i32x4*>(qa + (f >> 1) * 64 + (f & 1) * 16);
+        }
+    }
+    uint64_t c0 = 0;
+    uint32_t len = a.n_shared;
+    if (a.cand_ptr) {
+        c0 = a.cand_ptr[q];
+        len = (uint32_t)(a.cand_ptr[q + 1u] - c0);
+    }
+    uint32_t* Sq = a.S + (size_t)q * a.pitch;
+    for (uint32_t s = len + blockIdx.x * blockDim.x + tid; s < a.pitch; s += gridDim.x * blockDim.x) Sq[s] = RANGE_FAIL;
+    const uint32_t w = blockIdx.x * waves + wave, W = gridDim.x * waves;
+    if (w >= len) return;
+    const uint32_t mine = (len - w + W - 1u) / W;   // the wave's items: slots w, w + W, ...
+    const float NINF = -__builtin_huge_valf();
+    for (uint32_t jb = 0; jb < mine; jb += 64u) {
+        const uint32_t nit = mine - jb < 64u ? mine - jb : 64u;
+        uint64_t e0 = 0, e1 = 0;   // lane l: the token rows [e0, e1) of item jb + l
+        if (lane < nit) {
+            const uint32_t rec = a.cand[c0 + w + (uint64_t)(jb + lane) * W];
+            e0 = a.cptr[rec], e1 = a.cptr[rec + 1u];
+        }
+        MaxSimCursor lc, cc;   // the load cursor runs RING - 1 chunks ahead of the compute cursor, across records
+        lc.j = 0u, lc.enter(e0, e1);
+        cc = lc;
+        maxsim_i32x4 buf[RING][F];
+#pragma unroll
+        for (int i = 0; i < RING - 1; ++i)
+            if (lc.j < nit) {
+                maxsim_cand_load<F>(a.tokens, RB, lc, col, half, buf[i]);
+                lc.step(nch, nit, e0, e1);
+            }
+        float run[NT];   // the maximum so far of the record, one register a tile
+        Acc acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) run[t] = NINF;
+        while (cc.j < nit) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {
+                if (cc.j < nit) {
+                    const bool last = cc.c + 1u == nch;
+                    const uint32_t nrows = cc.t_end - cc.t < MAXSIM_BLOCK ? (uint32_t)(cc.t_end - cc.t) : MAXSIM_BLOCK;
+                    if (cc.c == 0u) {
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) acc[t] = Acc{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    }
+                    // i8: the scales of this half's 16 rows (register v is row 8 (v / 4) + 4 half + v % 4), ahead of the block's last
+                    // MFMAs; rows past the record are not read
+                    f32x4 sc[4];
+                    if (I8 && last) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const uint32_t r0 = 8u * g + 4u * half;
+                            if (r0 + 4u <= nrows) {
+                                sc[g] = *reinterpret_cast<const maxsim_f32x4_u*>(a.scales + cc.t + r0);
+                            } else {
+#pragma unroll
+                                for (uint32_t e = 0; e < 4u; ++e) sc[g][e] = r0 + e < nrows ? a.scales[cc.t + r0 + e] : 0.0f;
+                            }
+                        }
+                    }
+                    if (lc.j < nit) {
+                        maxsim_cand_load<F>(a.tokens, RB, lc, col, half, buf[(i + RING - 1) % RING]);
+                        lc.step(nch, nit, e0, e1);
+                    }
+                    const uint32_t kcb = cc.c * KCB;
+#pragma unroll
+                    for (int f = 0; f < F; ++f) {
+                        const uint32_t off = kcb + (uint32_t)(f >> 1) * 64u;   // the group of 64 row bytes; half h of it, bytes 16 (f & 1) ..
+                        if (off >= RB) continue;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                            maxsim_i32x4 bv = {0, 0, 0, 0};
+                            if (NT == 1 && cc.c == 0u) bv = qreg[f];
+                            else if (!I8 || off + half * 32u < RB) bv = *reinterpret_cast<const maxsim_i32x4*>(qa + (size_t)t * 32u * PB + off + (uint32_t)(f & 1) * 16u);
+                            if constexpr (I8) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(buf[i][f], bv, acc[t], 0, 0, 0);
+                            else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, buf[i][f]), __builtin_bit_cast(half8, bv), acc[t], 0, 0, 0);
+                        }
+                    }
+                    if (!last) {
+                        ++cc.c;
+                        continue;
+                    }
+                    // the block is complete: down the lane's 16 rows into the running maximum (fmaxf skips a NaN: rule 3)
+                    const int lim = (int)nrows - 4 * (int)half;   // register v holds a row of the record iff 8 (v / 4) + v % 4 < lim
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                        float v[16];
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) v[k] = I8 ? (float)acc[t][k] * sc[k >> 2][k & 3] : (float)acc[t][k];
+                        if (nrows < MAXSIM_BLOCK) {
+#pragma unroll
+                            for (int k = 0; k < 16; ++k) v[k] = 8 * (k >> 2) + (k & 3) < lim ? v[k] : NINF;
+                        }
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) run[t] = fmaxf(run[t], v[k]);
+                    }
+                    const uint32_t slot = w + (jb + cc.j) * W;
+                    if (!cc.step(nch, nit, e0, e1)) continue;
+                    // the record is complete: one exchange a tile joins the halves, then the sum over the query's tokens
+                    float s = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                        float lo, hi;
+                        maxsim_i8_halves(run[t], lo, hi);
+                        const float m = fmaxf(lo, hi);
+                        run[t] = NINF;
+                        if constexpr (I8) {   // rules 3" and 4": the scaled maxima through the pairwise tree, the tiles in order
+                            const float tile = maxsim_i8_tree((uint32_t)t * 32u + col < tq ? sq[t] * m : 0.0f);
+                            s = t == 0 ? tile : s + tile;
+                        } else {   // rule 4: m_i sits in lane i; ((m_0 + m_1) + m_2) + ... one v_readlane and one add a query token
+                            const uint32_t nv = tq - (uint32_t)t * 32u < 32u ? tq - (uint32_t)t * 32u : 32u;
+                            for (uint32_t i2 = 0; i2 < nv; ++i2) {
+                                const float mi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), (int)i2));
+                                s = t == 0 && i2 == 0u ? mi : s + mi;
+                            }
+                        }
+                    }
+                    if (lane == 0u) Sq[slot] = score_ord(s, false);
+                }
+            }
+        }
+    }
+}
+
+// grid.x strides over a query's candidates, grid.y is the query; blockDim.x / 64 waves (up to 4).  The LDS is the scan's plan.
+template <int NT>
+__global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_cand_h16(MaxSimCandArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm_maxsim_cand_h16[];
+    maxsim_cand<NT, false>(a, sm_maxsim_cand_h16);
+}
+template <int NT>
+__global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_cand_i8(MaxSimCandArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm_maxsim_cand_i8[];
+    maxsim_cand<NT, true>(a, sm_maxsim_cand_i8);
 }
 
 }  // namespace lynse

@@ -2,6 +2,7 @@
 // of the records in HBM, append-only.  Included at the end of lynse_hip.hip after mutate_host.inc; the kernel is in maxsim.h.  The
 // search is the additive search's shape: one exact scan into S[q][record], then the shared cut (ScoreCut::cut<true>) and order
 // (k_pool_select, or select_pool_keys beyond 16,384 keys), descending as for ip.  include/lynse_hip.h, MULTI-VECTOR SEARCH; DESIGN.md §28.
+// The rerank entry and a filtered search that leaves few tokens run the candidate kernels instead of the scan (MULTI-VECTOR RERANK; §31).
 
 struct lynse_hip_multivec {
     std::shared_mutex rw;
@@ -23,7 +24,9 @@ struct lynse_hip_multivec {
     DevBuf<uint32_t> d_crec, d_ranges;
     // the scratch of a search (it runs under the exclusive lock)
     DevBuf<float> q;
-    DevBuf<uint64_t> qdesc, mask;
+    DevBuf<uint64_t> qdesc, mask, cand_ptr;
+    DevBuf<uint32_t> cand;                  // the candidate lists of a rerank, or the live records of a routed filtered search
+    std::vector<uint32_t> h_cand;
     ScoreCut cut;
     PoolRerank rr;
     std::vector<float> hq, stage;
@@ -337,42 +340,94 @@ static int maxsim_h16_launch(const MaxSimH16Args& a, dim3 grid, size_t lds, hipS
     LY_HIP(hipGetLastError());
     return LYNSE_OK;
 }
-// nq queries, query i with q_ptr[i + 1] - q_ptr[i] token rows of `dim` floats in q_tokens: the best min(k, live) records of each
-// by (score descending, record row ascending) at stride k, out_counts[q] entries valid.  Live = has tokens and is in the mask.
-extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
-                                                    const uint64_t* bitset_words, uint64_t n_words, uint64_t* out_rows, float* out_scores,
-                                                    uint32_t* out_counts) {
-    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
-    if (nq == 0) return LYNSE_OK;
+
+// The candidate kernels (k_maxsim_cand_h16 / k_maxsim_cand_i8): `waves` waves a workgroup, the LDS of the scan's plan.
+template <int NT>
+static int maxsim_cand_launch(const MaxSimCandArgs& a, bool i8, dim3 grid, uint32_t waves, size_t lds, hipStream_t st) {
+    if (i8) {
+        LY_TRY(ensure_lds<k_maxsim_cand_i8<NT>>(PoolRerank::LDS_MAX));
+        hipLaunchKernelGGL(k_maxsim_cand_i8<NT>, grid, dim3(waves * 64u), lds, st, a);
+    } else {
+        LY_TRY(ensure_lds<k_maxsim_cand_h16<NT>>(PoolRerank::LDS_MAX));
+        hipLaunchKernelGGL(k_maxsim_cand_h16<NT>, grid, dim3(waves * 64u), lds, st, a);
+    }
+    LY_HIP(hipGetLastError());
+    return LYNSE_OK;
+}
+
+// The candidate lists of a call that the candidate kernels serve: compact record numbers (indices into cptr / crec), strictly
+// ascending within a list — so a slot order is a record-row order and the tie rule of the shared order holds.
+struct MaxSimCand {
+    const uint32_t* list;
+    const uint64_t* ptr;      // nq + 1 offsets into list; NULL: list[0 .. n_shared) is every query's list (a routed filtered search)
+    uint64_t n_shared;
+    uint64_t len(uint64_t q) const { return ptr ? ptr[q + 1] - ptr[q] : n_shared; }
+};
+
+// Routing of the filtered search (RERANK rule 8): the live records' tokens as a share of the store at or below which the candidate
+// kernel answers a filtered search: the largest share measured at which it was at least 1.25x faster than the scan (it was 4.7x on
+// int8 and 5.4x on f16 there; larger shares were not measured).  DESIGN.md §31 has the table.  f16 stores are routed too: the two
+// kernels accumulate a score block with the operand roles swapped and the order inside an MFMA is the hardware's, but their score
+// bits were compared on Gaussian data on the MI355X and agree (same section).
+constexpr uint64_t MAXSIM_CAND_SHARE_DEN = 4;
+
+// the checks of a call's queries (rule 7 and the pointers), before the lock and any device work
+static int maxsim_check_queries(const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k, const uint64_t* out_rows, const float* out_scores,
+                                const uint32_t* out_counts, uint32_t* tq_max) {
     if (!q_tokens || !q_ptr || !out_counts || (k && (!out_rows || !out_scores))) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
     if (nq >= (1ull << 32)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "too many queries");
     if (q_ptr[0] != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: q_ptr must start at 0");
-    uint32_t tq_max = 0;
+    *tq_max = 0;
     for (uint64_t i = 0; i < nq; ++i) {
         if (q_ptr[i + 1] <= q_ptr[i]) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
         if (q_ptr[i + 1] - q_ptr[i] > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
-        tq_max = std::max(tq_max, (uint32_t)(q_ptr[i + 1] - q_ptr[i]));
+        *tq_max = std::max(*tq_max, (uint32_t)(q_ptr[i + 1] - q_ptr[i]));
     }
-    std::unique_lock<std::shared_mutex> lk(h->rw);
+    return LYNSE_OK;
+}
+
+// The search under the handle's exclusive lock, the queries checked.  cand == NULL: the scan over every record, S[q][record], the
+// mask applied where a record ends — unless the mask leaves few enough tokens (rule 8), then its live records become one shared
+// candidate list.  With candidate lists: the candidate kernel, S[q][slot] at the pitch of the longest list.  The tail is one:
+// the cut (ScoreCut::cut<true>), the order (k_pool_select, or select_pool_keys beyond 16,384 keys), compact numbers back to rows.
+static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t tq_max, uint32_t k,
+                         const uint64_t* bitset_words, uint64_t n_words, const MaxSimCand* cand, uint64_t* out_rows, float* out_scores,
+                         uint32_t* out_counts) {
     LY_HIP(hipSetDevice(h->device));
     const uint64_t m = h->crec.size(), n = h->n;
     const uint32_t D = h->dim, ld = h->ld;
-    const uint64_t mask_words = bitset_words ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
-    uint64_t live = m;
-    if (bitset_words) {
+    const bool h16 = h->dtype == 1, i8 = h->dtype == 2;
+    const uint64_t mask_words = bitset_words && !cand ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
+    uint64_t live = m;   // the most records any query of the call can return
+    MaxSimCand routed{nullptr, nullptr, 0};
+    if (cand) {
         live = 0;
+        for (uint64_t i = 0; i < nq; ++i) live = std::max(live, cand->len(i));
+    } else if (bitset_words) {
+        live = 0;
+        uint64_t live_tokens = 0;
         for (uint64_t c = 0; c < m; ++c) {
             const uint64_t r = h->crec[c];
-            live += (r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull);
+            if ((r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull)) live += 1, live_tokens += h->cptr[c + 1] - h->cptr[c];
+        }
+        if (live && (i8 || h16) && live_tokens * MAXSIM_CAND_SHARE_DEN <= h->total) {
+            h->h_cand.clear();
+            for (uint64_t c = 0; c < m; ++c) {
+                const uint64_t r = h->crec[c];
+                if ((r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull)) h->h_cand.push_back((uint32_t)c);
+            }
+            routed = MaxSimCand{h->h_cand.data(), nullptr, live};
+            cand = &routed;
         }
     }
     if (m == 0 || k == 0 || live == 0) {
         memset(out_counts, 0, nq * 4);
         return LYNSE_OK;
     }
+    const bool masked = mask_words && !cand;
+    const uint64_t pitch = cand ? live : m;   // slots of a query in S
     uint32_t tiles = 0, waves = 0;
     uint64_t lds = 0;
-    const bool h16 = h->dtype == 1, i8 = h->dtype == 2;
     LY_TRY(maxsim_plan(D, tq_max, h->dtype, &tiles, &waves, &lds));
     // workgroups a CU can hold by their LDS (the registers allow one wave per SIMD at 8 tiles, two or three below): the grid's width
     uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
@@ -380,23 +435,32 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
     // (k_maxsim_i8 likewise: 166 + 16 and 196 + 32 registers at 1 and 2 tiles are two waves per SIMD, 236 + 64 and 256 + 245 above are one)
     if (h16 || i8) wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles <= 2 ? 2u : 1u);
     const uint32_t N = (uint32_t)std::min<uint64_t>(k, live);
-    const uint64_t qc = ScoreCut::chunk(nq, m, N);
+    const uint64_t qc = ScoreCut::chunk(nq, pitch, N);
     const bool sort_dev = N <= 16384;
     if (sort_dev) {
         LY_TRY(ensure_lds<k_pool_select<256>>(PoolRerank::LDS_MAX));
         LY_TRY(ensure_lds<k_pool_select<1024>>(PoolRerank::LDS_MAX));
     }
     hipStream_t st = h->stream;
-    if (bitset_words) LY_TRY(h->mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+    if (masked) LY_TRY(h->mask.reserve((size_t)std::max<uint64_t>(1, mask_words)));
+    const uint64_t cand_total = cand ? (cand->ptr ? cand->ptr[nq] : cand->n_shared) : 0;
+    if (cand) {
+        LY_TRY(h->cand.reserve((size_t)cand_total));
+        if (cand->ptr) LY_TRY(h->cand_ptr.reserve((size_t)nq + 1));
+    }
     LY_TRY(h->q.reserve((size_t)qc * tiles * 32u * ld));
     LY_TRY(h->qdesc.reserve((size_t)qc * 2));
     LY_TRY(h->rr.keys.reserve((size_t)qc * N));
     LY_TRY(h->rr.pcnt.reserve((size_t)qc));
     if (sort_dev) LY_TRY(h->rr.out.reserve(((size_t)qc * N * 12 + (size_t)qc * 4 + 7) / 8));
-    LY_TRY(h->cut.grow(qc, m));
-    // (the caller's words are queued only once nothing before the first launch can fail and return with the copy still pending)
-    if (mask_words) LY_HIP(hipMemcpyAsync(h->mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
-    const bool timed = h->profiling, select = live > N;
+    LY_TRY(h->cut.grow(qc, pitch));
+    // (the caller's words and lists are queued only once nothing before the first launch can fail and return with a copy pending)
+    if (masked) LY_HIP(hipMemcpyAsync(h->mask.p, bitset_words, (size_t)mask_words * 8, hipMemcpyHostToDevice, st));
+    if (cand) {
+        LY_HIP(hipMemcpyAsync(h->cand.p, cand->list, (size_t)cand_total * 4, hipMemcpyHostToDevice, st));
+        if (cand->ptr) LY_HIP(hipMemcpyAsync(h->cand_ptr.p, cand->ptr, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    const bool timed = h->profiling;
     if (timed) {
         for (hipEvent_t& e : h->ev)
             if (!e) LY_HIP(hipEventCreate(&e));
@@ -421,10 +485,24 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
                 memcpy(h->hq.data() + h->hdesc[2 * i] + (size_t)(t - q_ptr[q0 + i]) * ld, q_tokens + (size_t)t * D, (size_t)D * 4);
         LY_HIP(hipMemcpyAsync(h->q.p, h->hq.data(), floats * 4, hipMemcpyHostToDevice, st));
         LY_HIP(hipMemcpyAsync(h->qdesc.p, h->hdesc.data(), h->hdesc.size() * 8, hipMemcpyHostToDevice, st));
-        const MaxSimArgs a{h->tokens.p, ld, h->d_cptr.p, h->d_crec.p, m, h->d_ranges.p, n_ranges, h->q.p, h->qdesc.p,
-                           bitset_words ? h->mask.p : nullptr, mask_words, h->cut.S.p};
-        const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
         if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
+        if (cand) {
+            // a wave per (query, candidate): workgroups of up to 4 waves, as many of them a query as fill the part once over the chunk
+            const uint32_t cw = (uint32_t)std::min<uint64_t>(MAXSIM_MAX_WAVES, live);
+            const uint32_t per_q = std::max<uint32_t>(1u, h->num_cu * wg_per_cu / nqc);
+            const dim3 grid((uint32_t)std::min<uint64_t>((live + cw - 1) / cw, per_q), nqc);
+            const MaxSimCandArgs ac{i8 ? h->tokens_i8.p : reinterpret_cast<const unsigned char*>(h->tokens_h.p), h->scales.p, ld, h->d_cptr.p, h->cand.p,
+                                    cand->ptr ? h->cand_ptr.p + q0 : nullptr, (uint32_t)cand->n_shared, (uint32_t)pitch, h->q.p, h->qdesc.p, h->cut.S.p};
+            switch (tiles) {
+            case 1: LY_TRY(maxsim_cand_launch<1>(ac, i8, grid, cw, lds, st)); break;
+            case 2: LY_TRY(maxsim_cand_launch<2>(ac, i8, grid, cw, lds, st)); break;
+            case 4: LY_TRY(maxsim_cand_launch<4>(ac, i8, grid, cw, lds, st)); break;
+            default: LY_TRY(maxsim_cand_launch<8>(ac, i8, grid, cw, lds, st)); break;
+            }
+        } else {
+        const MaxSimArgs a{h->tokens.p, ld, h->d_cptr.p, h->d_crec.p, m, h->d_ranges.p, n_ranges, h->q.p, h->qdesc.p,
+                           masked ? h->mask.p : nullptr, mask_words, h->cut.S.p};
+        const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
         if (i8) {   // the same tables and queries, the token rows as codes with a scale each
             const MaxSimI8Args ai{{reinterpret_cast<const int8_t*>(h->tokens_i8.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S}, h->scales.p};
             switch (tiles) {
@@ -449,15 +527,35 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
             default: LY_TRY(maxsim_launch<8>(a, grid, waves, lds, st)); break;
             }
         }
+        }
         if (timed) {
             LY_HIP(hipEventRecord(h->ev[1], st));
+            const uint64_t row_bytes = i8 ? ld + 4 : ld * (h16 ? 2 : 4);
             h->prof.scan_launches += 1;
-            h->prof.scan_rows += h->total * nqc;
-            h->prof.scan_bytes += (h->total * (i8 ? ld + 4 : ld * (h16 ? 2 : 4)) + (m + 1) * 8) * nqc;
+            h->prof.last_plan = cand ? 1 : 0;
+            if (cand) {   // the rows and bytes the candidate kernel read: the listed records' tokens, their list entries and extents
+                for (uint32_t i = 0; i < nqc; ++i) {
+                    const uint32_t* l = cand->list + (cand->ptr ? cand->ptr[q0 + i] : 0);
+                    uint64_t rows = 0;
+                    for (uint64_t j = 0; j < cand->len(q0 + i); ++j) rows += h->cptr[l[j] + 1] - h->cptr[l[j]];
+                    h->prof.scan_rows += rows;
+                    h->prof.scan_bytes += rows * row_bytes + cand->len(q0 + i) * 20;
+                }
+            } else {
+                h->prof.scan_rows += h->total * nqc;
+                h->prof.scan_bytes += (h->total * row_bytes + (m + 1) * 8) * nqc;
+            }
         }
-        // more live records than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
-        h->cut.sel0.assign(nqc, select ? PqSel{0ull, 64u, N, 0u, 0u} : PqSel{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u});
-        LY_TRY(h->cut.cut<true>(nqc, m, N, select, h->rr.keys.p, h->rr.pcnt.p, st));
+        // more candidates than N: the radix selection of the N best keys; else every key below RANGE_FAIL (a state that starts done)
+        const PqSel sel_n{0ull, 64u, N, 0u, 0u}, sel_all{(uint64_t)(RANGE_FAIL - 1u), 32u, 0u, 1u, 0u};
+        bool select = false;
+        h->cut.sel0.resize(nqc);
+        for (uint32_t i = 0; i < nqc; ++i) {
+            const bool sel = (cand ? cand->len(q0 + i) : live) > N;
+            h->cut.sel0[i] = sel ? sel_n : sel_all;
+            select |= sel;
+        }
+        LY_TRY(h->cut.cut<true>(nqc, pitch, N, select, h->rr.keys.p, h->rr.pcnt.p, st));
         const size_t o_dist = (size_t)nqc * N * 8, o_cnt = (size_t)nqc * N * 12, o_all = o_cnt + (size_t)nqc * 4;
         if (sort_dev) {   // sorted in LDS (k_pool_select), rows | scores | counts of the chunk back in one copy
             uint32_t p2 = 2;
@@ -487,35 +585,108 @@ extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const
             h->prof.scan_us += (double)scan_ms * 1000.0;
             h->prof.total_us += (double)all_ms * 1000.0;
         }
+        // what a query returns: the N best of its own candidates (every query of a scan has `live` of them)
+        auto count_of = [&](uint32_t i) { return (uint32_t)std::min<uint64_t>(N, cand ? cand->len(q0 + i) : live); };
         if (sort_dev) {
             h->h_out.resize((o_all + 7) / 8);
             LY_HIP(hipMemcpyAsync(h->h_out.data(), h->rr.out.p, o_all, hipMemcpyDeviceToHost, st));
             LY_TRY(stream_wait(st));
             const uint8_t* hb = reinterpret_cast<const uint8_t*>(h->h_out.data());
-            for (uint32_t i = 0; i < nqc; ++i) {
+            for (uint32_t i = 0; i < nqc; ++i) {   // (k_pool_select padded a shorter result up to N)
                 memcpy(out_rows + (q0 + i) * k, hb + (size_t)i * N * 8, (size_t)N * 8);
                 memcpy(out_scores + (q0 + i) * k, hb + o_dist + (size_t)i * N * 4, (size_t)N * 4);
-                out_counts[q0 + i] = N;
+                out_counts[q0 + i] = count_of(i);
             }
         } else {   // beyond the 16,384 keys of the LDS sort: sorted on the host
             h->keys.resize((size_t)nqc * N);
             LY_HIP(hipMemcpyAsync(h->keys.data(), h->rr.keys.p, h->keys.size() * 8, hipMemcpyDeviceToHost, st));
             LY_TRY(stream_wait(st));
             for (uint32_t i = 0; i < nqc; ++i)
-                out_counts[q0 + i] = select_pool_keys(h->keys.data() + (size_t)i * N, N, N, N, false, out_rows + (q0 + i) * k, out_scores + (q0 + i) * k);
+                out_counts[q0 + i] = select_pool_keys(h->keys.data() + (size_t)i * N, count_of(i), N, N, false, out_rows + (q0 + i) * k, out_scores + (q0 + i) * k);
         }
-        // the kernel numbers the records that have tokens: back to record rows (ascending with them, so the order of ties holds)
-        for (uint32_t i = 0; i < nqc; ++i)
-            for (uint32_t j = 0; j < N; ++j) out_rows[(q0 + i) * k + j] = h->crec[(size_t)out_rows[(q0 + i) * k + j]];
+        // the kernels number the records that have tokens, the candidate kernel the slots of a list of those numbers: back to record
+        // rows (ascending with either, so the order of ties holds)
+        for (uint32_t i = 0; i < nqc; ++i) {
+            const uint32_t* l = cand ? cand->list + (cand->ptr ? cand->ptr[q0 + i] : 0) : nullptr;
+            for (uint32_t j = 0; j < out_counts[q0 + i]; ++j) {
+                const uint64_t c = out_rows[(q0 + i) * k + j];
+                out_rows[(q0 + i) * k + j] = h->crec[(size_t)(l ? l[c] : c)];
+            }
+        }
     }
     return LYNSE_OK;
     };
     const int rc = chunks();
-    if (rc != LYNSE_OK && mask_words) (void)hipStreamSynchronize(st);   // (the copy of the caller's words must not outlive the call)
+    if (rc != LYNSE_OK && (masked || cand)) (void)hipStreamSynchronize(st);   // (the copies of the caller's words and lists must not outlive the call)
     return rc;
+}
+
+// nq queries, query i with q_ptr[i + 1] - q_ptr[i] token rows of `dim` floats in q_tokens: the best min(k, live) records of each
+// by (score descending, record row ascending) at stride k, out_counts[q] entries valid.  Live = has tokens and is in the mask.
+extern "C" int lynse_hip_multivec_search_bitset_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
+                                                    const uint64_t* bitset_words, uint64_t n_words, uint64_t* out_rows, float* out_scores,
+                                                    uint32_t* out_counts) {
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    if (nq == 0) return LYNSE_OK;
+    uint32_t tq_max = 0;
+    LY_TRY(maxsim_check_queries(q_tokens, q_ptr, nq, k, out_rows, out_scores, out_counts, &tq_max));
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    return maxsim_search(h, q_tokens, q_ptr, nq, tq_max, k, bitset_words, n_words, nullptr, out_rows, out_scores, out_counts);
 }
 
 extern "C" int lynse_hip_multivec_search_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
                                              uint64_t* out_rows, float* out_scores, uint32_t* out_counts) {
     return lynse_hip_multivec_search_bitset_f32(h, q_tokens, q_ptr, nq, k, nullptr, 0, out_rows, out_scores, out_counts);
+}
+
+// MULTI-VECTOR RERANK: query i scored against the records cand_rows[cand_ptr[i] .. cand_ptr[i + 1]) only.  The checks that need no
+// store come first (rule 2), then the handle, then the rows against n — all before any device work.
+extern "C" int lynse_hip_multivec_rerank_f32(lynse_hip_multivec* h, const float* q_tokens, const uint64_t* q_ptr, uint64_t nq, uint32_t k,
+                                             const uint64_t* cand_rows, const uint64_t* cand_ptr, uint64_t* out_rows, float* out_scores,
+                                             uint32_t* out_counts) {
+    if (nq == 0) return h ? LYNSE_OK : set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    uint32_t tq_max = 0;
+    LY_TRY(maxsim_check_queries(q_tokens, q_ptr, nq, k, out_rows, out_scores, out_counts, &tq_max));
+    if (!cand_ptr) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (cand_ptr[0] != 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector rerank: cand_ptr must start at 0");
+    for (uint64_t i = 0; i < nq; ++i)
+        if (cand_ptr[i + 1] < cand_ptr[i]) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector rerank: cand_ptr must not descend");
+    if (cand_ptr[nq] && !cand_rows) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint64_t i = 0; i < nq; ++i)
+        for (uint64_t j = cand_ptr[i] + 1; j < cand_ptr[i + 1]; ++j)
+            if (cand_rows[j] <= cand_rows[j - 1])
+                return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector rerank: the candidate rows of a query must be strictly ascending");
+    if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    for (uint64_t i = 0; i < nq; ++i)
+        if (cand_ptr[i + 1] > cand_ptr[i] && cand_rows[cand_ptr[i + 1] - 1] >= h->n)
+            return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector rerank: candidate row " + std::to_string(cand_rows[cand_ptr[i + 1] - 1]) + " is not a record (n = " +
+                                                             std::to_string(h->n) + ")");
+    LY_TRY(maxsim_plan(h->dim, tq_max, h->dtype, nullptr, nullptr, nullptr));
+    if (h->dtype == 0) {
+        // an f32 store has no candidate kernel: the scan once per query with the query's candidates as its BitSet — the same
+        // results at the scan's cost
+        std::vector<uint64_t> words((h->n + 63) / 64 + 1);
+        for (uint64_t i = 0; i < nq; ++i) {
+            std::fill(words.begin(), words.end(), 0ull);
+            for (uint64_t j = cand_ptr[i]; j < cand_ptr[i + 1]; ++j) words[cand_rows[j] >> 6] |= 1ull << (cand_rows[j] & 63u);
+            const uint64_t qp[2] = {0, q_ptr[i + 1] - q_ptr[i]};
+            LY_TRY(maxsim_search(h, q_tokens + (size_t)q_ptr[i] * h->dim, qp, 1, (uint32_t)qp[1], k, words.data(), words.size(), nullptr,
+                                 out_rows + i * k, out_scores + i * k, out_counts + i));
+        }
+        return LYNSE_OK;
+    }
+    // records without tokens drop out here: the lists as compact record numbers (a binary search in crec), still ascending
+    std::vector<uint32_t> list;
+    std::vector<uint64_t> ptr(nq + 1, 0);
+    list.reserve((size_t)cand_ptr[nq]);
+    for (uint64_t i = 0; i < nq; ++i) {
+        for (uint64_t j = cand_ptr[i]; j < cand_ptr[i + 1]; ++j) {
+            const auto it = std::lower_bound(h->crec.begin(), h->crec.end(), (uint32_t)cand_rows[j]);
+            if (it != h->crec.end() && *it == cand_rows[j]) list.push_back((uint32_t)(it - h->crec.begin()));
+        }
+        ptr[i + 1] = list.size();
+    }
+    const MaxSimCand cand{list.data(), ptr.data(), 0};
+    return maxsim_search(h, q_tokens, q_ptr, nq, tq_max, k, nullptr, 0, &cand, out_rows, out_scores, out_counts);
 }
