@@ -10,16 +10,14 @@ struct lynse_hip_multivec {
     uint32_t num_cu = 256;
     hipStream_t stream = nullptr;
     uint32_t dim = 0, ld = 0;
-    int dtype = 0;                          // 0: f32 rows in `tokens`, k_maxsim_scan; 1: f16 rows in `tokens_h`, k_maxsim_h16 (same pitch in elements)
-                                            // 2 (internal, lynse_hip_multivec_create_i8): codes in `tokens_i8` + `scales`, k_maxsim_i8
-    DevBuf<uint16_t> tokens_h;
-    DevBuf<uint8_t> tokens_i8;
-    DevBuf<float> scales;
+    int dtype = 0;                          // the tag of MAXSIM_DTYPES: 0 f32 (k_maxsim_scan), 1 f16 (k_maxsim_h16), 2 int8 codes (internal,
+                                            // lynse_hip_multivec_create_i8: k_maxsim_i8)
+    DevBuf<uint8_t> tokens;                 // the token rows, ld elements of the dtype each (cap counts bytes)
+    DevBuf<float> scales;                   // int8: one a token row
     uint64_t n = 0, total = 0;              // records (those without tokens included), token rows
     // the records that have tokens, which are all the kernel sees: their token offsets, their record rows, and the wave ranges
     std::vector<uint64_t> cptr{0};
     std::vector<uint32_t> crec, ranges{0};
-    DevBuf<float> tokens;
     DevBuf<uint64_t> d_cptr;
     DevBuf<uint32_t> d_crec, d_ranges;
     // the scratch of a search (it runs under the exclusive lock)
@@ -36,71 +34,75 @@ struct lynse_hip_multivec {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // the scan begins / the scan ends / the last launch of the chunk
 };
 
-// Rule 7 for a query of tq tokens against token rows of `dim` floats, host only: the query tiles the LDS holds (a power of two of
-// them: one kernel each), the waves of a workgroup that fit next to them (4, 2 or 1) and the bytes.  Each output may be NULL.
-extern "C" int lynse_hip_multivec_plan(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+// What the host code knows of a token dtype, by the handle's tag: 0 and 1 are the public dtype ids, 2 is the int8 store.
+struct MaxSimDtype {
+    uint32_t esz;        // bytes of a stored element
+    bool scaled;         // a token row has an f32 scale next to it (`scales`)
+    bool shrink;         // the waves of a workgroup go 4, 2, 1 until the LDS fits: only the f32 kernel keeps token blocks there
+    bool cand;           // the dtype has candidate kernels (k_maxsim_cand_*)
+    const char* what;    // what does not fit, in the refusal of a plan
+    size_t (*lds)(uint32_t ld, uint32_t tiles, uint32_t waves);
+    // Workgroups a CU holds by the kernels' registers (resource_usage.txt).  k_maxsim_scan: one wave per SIMD at 8 tiles, two or
+    // three below.  k_maxsim_h16, k_maxsim_i8 (a workgroup = one wave per SIMD): two waves per SIMD at 1 and 2 tiles, one above.
+    uint32_t wg_cap(uint32_t tiles, uint32_t waves) const { return shrink ? (tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves)) : (tiles <= 2 ? 2u : 1u); }
+};
+constexpr MaxSimDtype MAXSIM_DTYPES[3] = {
+    {4, false, true, false, "and two token blocks", [](uint32_t ld, uint32_t tiles, uint32_t waves) { return maxsim_lds_bytes(ld, tiles, waves); }},
+    {2, false, false, true, "of f16 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_h16_lds_bytes(ld, tiles); }},
+    {1, true, false, true, "of int8 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_i8_lds_bytes(ld, tiles); }},
+};
+
+struct MaxSimPlan {
+    uint32_t tiles, waves;
+    uint64_t lds;
+    uint32_t wg_per_cu;   // workgroups a CU can hold, by their LDS and by their registers: the grid's width
+};
+
+// The plan of a query of tq tokens against token rows of `dim` elements, host only: the query tiles the LDS holds (a power of two of
+// them: one kernel each), the waves of a workgroup and the LDS bytes.  f32 (rule 7): the LDS holds the query tiles and two token
+// blocks a wave, so the waves are those that fit next to the tiles (4, 2 or 1).  f16 (the addendum): the query tiles as halves and
+// 32 flags per wave, no token block, so the waves are always 4 and every dimension up to 1024 serves a query of up to 64 tokens.
+// int8 (rule 7"): the query tiles as codes at a row pitch of ld + 16 bytes, their scales and the flags; 4 waves, and every
+// dimension up to 1024 serves a query of up to 128 tokens.  `out` may be NULL.
+static int maxsim_plan(uint32_t dim, uint32_t tq, int tag, MaxSimPlan* out) {
     if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
     if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
     if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
     if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
+    const MaxSimDtype& dt = MAXSIM_DTYPES[tag];
     const uint32_t ld = maxsim_ld(dim);
     uint32_t tiles = 1, waves = MAXSIM_MAX_WAVES;
     while (tiles * 32u < tq) tiles *= 2;
-    while (waves > 1 && maxsim_lds_bytes(ld, tiles, waves) > PoolRerank::LDS_MAX) waves /= 2;
-    const size_t lds = maxsim_lds_bytes(ld, tiles, waves);
+    while (dt.shrink && waves > 1 && dt.lds(ld, tiles, waves) > PoolRerank::LDS_MAX) waves /= 2;
+    const size_t lds = dt.lds(ld, tiles, waves);
     if (lds > PoolRerank::LDS_MAX)
-        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) and two token blocks of dimension " +
+        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) " + dt.what + " of dimension " +
                                                     std::to_string(dim) + " do not fit in LDS");
-    if (out_tiles) *out_tiles = tiles;
-    if (out_waves) *out_waves = waves;
-    if (out_lds_bytes) *out_lds_bytes = lds;
+    if (out) *out = MaxSimPlan{tiles, waves, lds, (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, dt.wg_cap(tiles, waves))};
     return LYNSE_OK;
 }
 
-// The plan by token dtype (0 = f32: the rule above).  f16 (the addendum): the LDS holds the query tiles as halves and 32 flags per
-// wave, no token block, so the waves are always 4 and every dimension up to 1024 serves a query of up to 64 tokens.
+// the C face of the plan: each output may be NULL
+static int maxsim_plan_out(uint32_t dim, uint32_t tq, int tag, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    MaxSimPlan p;
+    LY_TRY(maxsim_plan(dim, tq, tag, &p));
+    if (out_tiles) *out_tiles = p.tiles;
+    if (out_waves) *out_waves = p.waves;
+    if (out_lds_bytes) *out_lds_bytes = p.lds;
+    return LYNSE_OK;
+}
+
+extern "C" int lynse_hip_multivec_plan(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    return maxsim_plan_out(dim, tq, 0, out_tiles, out_waves, out_lds_bytes);
+}
+
 extern "C" int lynse_hip_multivec_plan_dtype(uint32_t dim, uint32_t tq, int dtype, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
-    if (dtype == 0) return lynse_hip_multivec_plan(dim, tq, out_tiles, out_waves, out_lds_bytes);
-    if (dtype != 1) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dtype must be 0 (f32) or 1 (f16)");
-    if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
-    if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
-    if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
-    if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
-    uint32_t tiles = 1;
-    while (tiles * 32u < tq) tiles *= 2;
-    const size_t lds = maxsim_h16_lds_bytes(maxsim_ld(dim), tiles);
-    if (lds > PoolRerank::LDS_MAX)
-        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) of f16 tokens of dimension " +
-                                                    std::to_string(dim) + " do not fit in LDS");
-    if (out_tiles) *out_tiles = tiles;
-    if (out_waves) *out_waves = MAXSIM_MAX_WAVES;
-    if (out_lds_bytes) *out_lds_bytes = lds;
-    return LYNSE_OK;
+    if (dtype != 0 && dtype != 1) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dtype must be 0 (f32) or 1 (f16)");
+    return maxsim_plan_out(dim, tq, dtype, out_tiles, out_waves, out_lds_bytes);
 }
 
-// Rule 7" of the int8 store, host only: the LDS holds the query tiles as codes at a row pitch of ld + 16 bytes, their scales and 32
-// flags per wave; the waves are always 4 and every dimension up to 1024 serves a query of up to 128 tokens.
 extern "C" int lynse_hip_multivec_plan_i8(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
-    if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
-    if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
-    if (dim > MAXSIM_MAX_DIM) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a token dimension above 1024 is not supported");
-    if (tq > MAXSIM_MAX_TQ) return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: a query of more than 256 tokens is not supported");
-    uint32_t tiles = 1;
-    while (tiles * 32u < tq) tiles *= 2;
-    const size_t lds = maxsim_i8_lds_bytes(maxsim_ld(dim), tiles);
-    if (lds > PoolRerank::LDS_MAX)
-        return set_error(LYNSE_ERR_UNSUPPORTED, "multi-vector search: " + std::to_string(tiles) + " query tile(s) of int8 tokens of dimension " +
-                                                    std::to_string(dim) + " do not fit in LDS");
-    if (out_tiles) *out_tiles = tiles;
-    if (out_waves) *out_waves = MAXSIM_MAX_WAVES;
-    if (out_lds_bytes) *out_lds_bytes = lds;
-    return LYNSE_OK;
-}
-
-// the plan by the handle's tag: 0 and 1 are the public dtype ids, 2 is the int8 store
-static int maxsim_plan(uint32_t dim, uint32_t tq, int tag, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
-    if (tag == 2) return lynse_hip_multivec_plan_i8(dim, tq, out_tiles, out_waves, out_lds_bytes);
-    return lynse_hip_multivec_plan_dtype(dim, tq, tag, out_tiles, out_waves, out_lds_bytes);
+    return maxsim_plan_out(dim, tq, 2, out_tiles, out_waves, out_lds_bytes);
 }
 
 static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out);
@@ -118,7 +120,7 @@ extern "C" int lynse_hip_multivec_create_i8(int device, uint32_t dim, lynse_hip_
 static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out) {
     if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    LY_TRY(maxsim_plan(dim, 1, dtype, nullptr, nullptr, nullptr));   // a store no query could ever be answered from is refused here
+    LY_TRY(maxsim_plan(dim, 1, dtype, nullptr));   // a store no query could ever be answered from is refused here
     int ndev = 0;
     LY_TRY(lynse_hip_device_count(&ndev));
     if (ndev <= 0) return set_error(LYNSE_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
@@ -173,8 +175,30 @@ static void maxsim_ranges(const std::vector<uint64_t>& cptr, std::vector<uint32_
     if (ranges.back() != m) ranges.push_back(m);
 }
 
+// Room for `total` token rows: where the block (or, for a dtype that has them, the scales) is too small, a new one of max(total,
+// twice the rows held) rows, the rows held copied on the device.  The new arrays replace the held ones only once every allocation
+// exists and the copies are done, so a failed call leaves the store answering as before.
+static int maxsim_grow(lynse_hip_multivec* h, uint64_t total) {
+    const MaxSimDtype& dt = MAXSIM_DTYPES[h->dtype];
+    const size_t rb = (size_t)h->ld * dt.esz;
+    if (total <= h->tokens.cap / rb && (!dt.scaled || total <= h->scales.cap)) return LYNSE_OK;
+    const uint64_t cap = std::max<uint64_t>(total, 2 * h->total);
+    DevBuf<uint8_t> grown;
+    DevBuf<float> grown_s;
+    LY_TRY(grown.alloc((size_t)cap * rb));
+    if (dt.scaled) LY_TRY(grown_s.alloc((size_t)cap));
+    if (h->total) {
+        LY_HIP(hipMemcpy(grown.p, h->tokens.p, (size_t)h->total * rb, hipMemcpyDeviceToDevice));
+        if (dt.scaled) LY_HIP(hipMemcpy(grown_s.p, h->scales.p, (size_t)h->total * 4, hipMemcpyDeviceToDevice));
+    }
+    LY_HIP(hipStreamSynchronize(nullptr));   // (the copies are ordered on the NULL stream: h2d_done)
+    h->tokens = std::move(grown);
+    if (dt.scaled) h->scales = std::move(grown_s);
+    return LYNSE_OK;
+}
+
 // n_records records more: record i has counts[i] >= 0 token rows of `dim` floats, all of them consecutive in `tokens`.  The token
-// array grows by doubling (its rows are copied on the device); a failed call leaves the store as it was.
+// array grows by doubling (maxsim_grow); a failed call leaves the store as it was.
 // `tokens` are f32, or raw halves for an f16 handle (raw_h16): an f16 handle takes either and stores rule 1's image of them.
 static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16, const uint64_t* counts, uint64_t n_records) {
     if (!h) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "handle is NULL");
@@ -187,7 +211,9 @@ static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16
     std::unique_lock<std::shared_mutex> lk(h->rw);
     if (h->n + n_records >= (1ull << 32)) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector records: a selection key carries a 32-bit row, n must be below 2^32");
     LY_HIP(hipSetDevice(h->device));
+    const MaxSimDtype& dt = MAXSIM_DTYPES[h->dtype];
     const uint32_t D = h->dim, ld = h->ld;
+    const size_t rb = (size_t)ld * dt.esz;
     const uint64_t total = h->total + add;
     std::vector<uint64_t> cptr = h->cptr;
     std::vector<uint32_t> crec = h->crec, ranges;
@@ -201,72 +227,39 @@ static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16
     // past them; the device tables go up into fresh buffers; everything is swapped in only once nothing can fail any more.
     DevBuf<uint64_t> n_cptr;
     DevBuf<uint32_t> n_crec, n_ranges;
-    if (add && h->dtype == 1) {
-        if (total > h->tokens_h.cap / ld) {   // grow: the rows held move to the new block
-            DevBuf<uint16_t> grown;
-            LY_TRY(grown.alloc((size_t)std::max<uint64_t>(total, 2 * h->total) * ld));
-            if (h->total) LY_HIP(hipMemcpy(grown.p, h->tokens_h.p, (size_t)h->total * ld * 2, hipMemcpyDeviceToDevice));
-            LY_HIP(hipStreamSynchronize(nullptr));
-            h->tokens_h = std::move(grown);
-        }
-        // the rows as given go up once; the device writes them at the store's pitch (k_maxsim_store_h16: conversion, flush, zero columns)
-        const size_t esz = raw_h16 ? 2 : 4;
-        DevBuf<uint8_t> raw;
-        LY_TRY(raw.alloc((size_t)add * D * esz));
-        LY_TRY(h2d_done(raw.p, tokens, (size_t)add * D * esz));
-        uint16_t* dst = h->tokens_h.p + (size_t)h->total * ld;
-        const uint64_t step = (1ull << 30) / ld;   // rows of a launch: its grid stays below 2^22 workgroups
-        for (uint64_t r0 = 0; r0 < add; r0 += step) {
-            const uint64_t rows = std::min<uint64_t>(step, add - r0);
-            const dim3 grid((uint32_t)((rows * ld + 255) / 256));
-            if (raw_h16) hipLaunchKernelGGL(k_maxsim_store_h16<uint16_t>, grid, dim3(256), 0, nullptr, reinterpret_cast<const uint16_t*>(raw.p) + (size_t)r0 * D, dst + (size_t)r0 * ld, rows, D, ld);
-            else hipLaunchKernelGGL(k_maxsim_store_h16<float>, grid, dim3(256), 0, nullptr, reinterpret_cast<const float*>(raw.p) + (size_t)r0 * D, dst + (size_t)r0 * ld, rows, D, ld);
-            LY_HIP(hipGetLastError());
-        }
-        LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
-    }
-    if (add && h->dtype == 2) {
-        // both arrays grow together; a fresh pair replaces the held one only once both exist
-        if (total > h->tokens_i8.cap / ld || total > h->scales.cap) {
-            const uint64_t cap = std::max<uint64_t>(total, 2 * h->total);
-            DevBuf<uint8_t> grown;
-            DevBuf<float> grown_s;
-            LY_TRY(grown.alloc((size_t)cap * ld));
-            LY_TRY(grown_s.alloc((size_t)cap));
-            if (h->total) {
-                LY_HIP(hipMemcpy(grown.p, h->tokens_i8.p, (size_t)h->total * ld, hipMemcpyDeviceToDevice));
-                LY_HIP(hipMemcpy(grown_s.p, h->scales.p, (size_t)h->total * 4, hipMemcpyDeviceToDevice));
-            }
-            LY_HIP(hipStreamSynchronize(nullptr));
-            h->tokens_i8 = std::move(grown);
-            h->scales = std::move(grown_s);
-        }
-        // the f32 rows as given go up once; the device quantises them at the store's pitch (k_maxsim_store_i8: rule 1", zero columns)
-        DevBuf<float> raw;
-        LY_TRY(raw.alloc((size_t)add * D));
-        LY_TRY(h2d_done(raw.p, tokens, (size_t)add * D * 4));
-        const uint64_t step = (1ull << 30) / ld;   // rows of a launch: its grid stays below 2^26 workgroups
-        for (uint64_t r0 = 0; r0 < add; r0 += step) {
-            const uint64_t rows = std::min<uint64_t>(step, add - r0);
-            hipLaunchKernelGGL(k_maxsim_store_i8, dim3((uint32_t)((rows + 15) / 16)), dim3(256), 0, nullptr, raw.p + (size_t)r0 * D,
-                               reinterpret_cast<uint32_t*>(h->tokens_i8.p + (size_t)(h->total + r0) * ld), h->scales.p + h->total + r0, rows, D, ld);
-            LY_HIP(hipGetLastError());
-        }
-        LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
-    }
-    if (add && h->dtype == 0) {
-        if (total > h->tokens.cap / ld) {   // grow: the rows held move to the new block
-            DevBuf<float> grown;
-            LY_TRY(grown.alloc((size_t)std::max<uint64_t>(total, 2 * h->total) * ld));
-            if (h->total) LY_HIP(hipMemcpy(grown.p, h->tokens.p, (size_t)h->total * ld * 4, hipMemcpyDeviceToDevice));
-            LY_HIP(hipStreamSynchronize(nullptr));   // (the copy is ordered on the NULL stream: h2d_done)
-            h->tokens = std::move(grown);
-        }
-        h->stage.assign((size_t)add * ld, 0.0f);   // the rows at the device pitch, zero columns past the dimension
-        for (uint64_t t = 0; t < add; ++t) memcpy(h->stage.data() + (size_t)t * ld, static_cast<const float*>(tokens) + (size_t)t * D, (size_t)D * 4);
-        LY_TRY(h2d_done(h->tokens.p + (size_t)h->total * ld, h->stage.data(), h->stage.size() * 4));
-    }
     if (add) {
+        LY_TRY(maxsim_grow(h, total));
+        uint8_t* dst = h->tokens.p + (size_t)h->total * rb;
+        if (h->dtype == 0) {   // f32 rows are laid out on the host and go up in one copy
+            h->stage.assign((size_t)add * ld, 0.0f);   // the rows at the device pitch, zero columns past the dimension
+            for (uint64_t t = 0; t < add; ++t) memcpy(h->stage.data() + (size_t)t * ld, static_cast<const float*>(tokens) + (size_t)t * D, (size_t)D * 4);
+            LY_TRY(h2d_done(dst, h->stage.data(), h->stage.size() * 4));
+        } else {
+            // the rows as given go up once; the device writes them at the store's pitch (k_maxsim_store_h16: conversion, flush, zero
+            // columns; k_maxsim_store_i8: rule 1", zero columns)
+            const size_t src_rb = (size_t)D * (raw_h16 ? 2 : 4);
+            DevBuf<uint8_t> raw;
+            LY_TRY(raw.alloc((size_t)add * src_rb));
+            LY_TRY(h2d_done(raw.p, tokens, (size_t)add * src_rb));
+            // rows of a launch: rows * ld <= 2^30, so k_maxsim_store_h16 (a thread a stored half) has at most 2^22 workgroups and
+            // k_maxsim_store_i8 (16 rows a workgroup, ld >= 32) at most 2^21
+            const uint64_t step = (1ull << 30) / ld;
+            for (uint64_t r0 = 0; r0 < add; r0 += step) {
+                const uint64_t rows = std::min<uint64_t>(step, add - r0);
+                const uint8_t* src = raw.p + (size_t)r0 * src_rb;
+                uint8_t* out = dst + (size_t)r0 * rb;
+                const dim3 grid_h((uint32_t)((rows * ld + 255) / 256));
+                if (dt.scaled)
+                    hipLaunchKernelGGL(k_maxsim_store_i8, dim3((uint32_t)((rows + 15) / 16)), dim3(256), 0, nullptr, reinterpret_cast<const float*>(src),
+                                       reinterpret_cast<uint32_t*>(out), h->scales.p + h->total + r0, rows, D, ld);
+                else if (raw_h16)
+                    hipLaunchKernelGGL(k_maxsim_store_h16<uint16_t>, grid_h, dim3(256), 0, nullptr, reinterpret_cast<const uint16_t*>(src), reinterpret_cast<uint16_t*>(out), rows, D, ld);
+                else
+                    hipLaunchKernelGGL(k_maxsim_store_h16<float>, grid_h, dim3(256), 0, nullptr, reinterpret_cast<const float*>(src), reinterpret_cast<uint16_t*>(out), rows, D, ld);
+                LY_HIP(hipGetLastError());
+            }
+            LY_HIP(hipStreamSynchronize(nullptr));   // (`raw` is freed on return)
+        }
         LY_TRY(n_cptr.alloc(cptr.size()));
         LY_TRY(n_crec.alloc(crec.size()));
         LY_TRY(n_ranges.alloc(ranges.size()));
@@ -317,42 +310,15 @@ extern "C" int lynse_hip_multivec_profile_get(lynse_hip_multivec* h, lynse_hip_p
     return LYNSE_OK;
 }
 
-template <int NT>
-static int maxsim_launch(const MaxSimArgs& a, dim3 grid, uint32_t waves, size_t lds, hipStream_t st) {
-    LY_TRY(ensure_lds<k_maxsim_scan<NT>>(PoolRerank::LDS_MAX));
-    hipLaunchKernelGGL(k_maxsim_scan<NT>, grid, dim3(waves * 64u), lds, st, a);
-    LY_HIP(hipGetLastError());
-    return LYNSE_OK;
-}
-
-template <int NT>
-static int maxsim_i8_launch(const MaxSimI8Args& a, dim3 grid, size_t lds, hipStream_t st) {
-    LY_TRY(ensure_lds<k_maxsim_i8<NT>>(PoolRerank::LDS_MAX));
-    hipLaunchKernelGGL(k_maxsim_i8<NT>, grid, dim3(MAXSIM_MAX_WAVES * 64u), lds, st, a);
-    LY_HIP(hipGetLastError());
-    return LYNSE_OK;
-}
-
-template <int NT>
-static int maxsim_h16_launch(const MaxSimH16Args& a, dim3 grid, size_t lds, hipStream_t st) {
-    LY_TRY(ensure_lds<k_maxsim_h16<NT>>(PoolRerank::LDS_MAX));
-    hipLaunchKernelGGL(k_maxsim_h16<NT>, grid, dim3(MAXSIM_MAX_WAVES * 64u), lds, st, a);
-    LY_HIP(hipGetLastError());
-    return LYNSE_OK;
-}
-
-// The candidate kernels (k_maxsim_cand_h16 / k_maxsim_cand_i8): `waves` waves a workgroup, the LDS of the scan's plan.
-template <int NT>
-static int maxsim_cand_launch(const MaxSimCandArgs& a, bool i8, dim3 grid, uint32_t waves, size_t lds, hipStream_t st) {
-    if (i8) {
-        LY_TRY(ensure_lds<k_maxsim_cand_i8<NT>>(PoolRerank::LDS_MAX));
-        hipLaunchKernelGGL(k_maxsim_cand_i8<NT>, grid, dim3(waves * 64u), lds, st, a);
-    } else {
-        LY_TRY(ensure_lds<k_maxsim_cand_h16<NT>>(PoolRerank::LDS_MAX));
-        hipLaunchKernelGGL(k_maxsim_cand_h16<NT>, grid, dim3(waves * 64u), lds, st, a);
+// f(std::integral_constant<int, NT>) for the plan's tiles (1, 2, 4 or 8): a kernel instantiation each
+template <typename F>
+static int maxsim_by_tiles(uint32_t tiles, F&& f) {
+    switch (tiles) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
     }
-    LY_HIP(hipGetLastError());
-    return LYNSE_OK;
 }
 
 // The candidate lists of a call that the candidate kernels serve: compact record numbers (indices into cptr / crec), strictly
@@ -396,7 +362,7 @@ static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uin
     LY_HIP(hipSetDevice(h->device));
     const uint64_t m = h->crec.size(), n = h->n;
     const uint32_t D = h->dim, ld = h->ld;
-    const bool h16 = h->dtype == 1, i8 = h->dtype == 2;
+    const MaxSimDtype& dt = MAXSIM_DTYPES[h->dtype];
     const uint64_t mask_words = bitset_words && !cand ? std::min<uint64_t>(n_words, (n + 63) / 64) : 0;
     uint64_t live = m;   // the most records any query of the call can return
     MaxSimCand routed{nullptr, nullptr, 0};
@@ -404,18 +370,15 @@ static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uin
         live = 0;
         for (uint64_t i = 0; i < nq; ++i) live = std::max(live, cand->len(i));
     } else if (bitset_words) {
-        live = 0;
+        // the live records as compact numbers and their tokens, then the routing
         uint64_t live_tokens = 0;
+        h->h_cand.clear();
         for (uint64_t c = 0; c < m; ++c) {
             const uint64_t r = h->crec[c];
-            if ((r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull)) live += 1, live_tokens += h->cptr[c + 1] - h->cptr[c];
+            if ((r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull)) h->h_cand.push_back((uint32_t)c), live_tokens += h->cptr[c + 1] - h->cptr[c];
         }
-        if (live && (i8 || h16) && live_tokens * MAXSIM_CAND_SHARE_DEN <= h->total) {
-            h->h_cand.clear();
-            for (uint64_t c = 0; c < m; ++c) {
-                const uint64_t r = h->crec[c];
-                if ((r >> 6) < mask_words && ((bitset_words[r >> 6] >> (r & 63u)) & 1ull)) h->h_cand.push_back((uint32_t)c);
-            }
+        live = h->h_cand.size();
+        if (live && dt.cand && live_tokens * MAXSIM_CAND_SHARE_DEN <= h->total) {
             routed = MaxSimCand{h->h_cand.data(), nullptr, live};
             cand = &routed;
         }
@@ -426,14 +389,10 @@ static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uin
     }
     const bool masked = mask_words && !cand;
     const uint64_t pitch = cand ? live : m;   // slots of a query in S
-    uint32_t tiles = 0, waves = 0;
-    uint64_t lds = 0;
-    LY_TRY(maxsim_plan(D, tq_max, h->dtype, &tiles, &waves, &lds));
-    // workgroups a CU can hold by their LDS (the registers allow one wave per SIMD at 8 tiles, two or three below): the grid's width
-    uint32_t wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves));
-    // (k_maxsim_h16, a workgroup = one wave per SIMD: by registers two waves per SIMD at 1 and 2 tiles, one above — resource_usage.txt)
-    // (k_maxsim_i8 likewise: 166 + 16 and 196 + 32 registers at 1 and 2 tiles are two waves per SIMD, 236 + 64 and 256 + 245 above are one)
-    if (h16 || i8) wg_per_cu = (uint32_t)std::min<uint64_t>(PoolRerank::LDS_MAX / lds, tiles <= 2 ? 2u : 1u);
+    MaxSimPlan plan;
+    LY_TRY(maxsim_plan(D, tq_max, h->dtype, &plan));
+    const uint32_t tiles = plan.tiles, waves = plan.waves, wg_per_cu = plan.wg_per_cu;
+    const size_t lds = plan.lds;
     const uint32_t N = (uint32_t)std::min<uint64_t>(k, live);
     const uint64_t qc = ScoreCut::chunk(nq, pitch, N);
     const bool sort_dev = N <= 16384;
@@ -486,51 +445,32 @@ static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uin
         LY_HIP(hipMemcpyAsync(h->q.p, h->hq.data(), floats * 4, hipMemcpyHostToDevice, st));
         LY_HIP(hipMemcpyAsync(h->qdesc.p, h->hdesc.data(), h->hdesc.size() * 8, hipMemcpyHostToDevice, st));
         if (timed) LY_HIP(hipEventRecord(h->ev[0], st));
-        if (cand) {
-            // a wave per (query, candidate): workgroups of up to 4 waves, as many of them a query as fill the part once over the chunk
-            const uint32_t cw = (uint32_t)std::min<uint64_t>(MAXSIM_MAX_WAVES, live);
-            const uint32_t per_q = std::max<uint32_t>(1u, h->num_cu * wg_per_cu / nqc);
-            const dim3 grid((uint32_t)std::min<uint64_t>((live + cw - 1) / cw, per_q), nqc);
-            const MaxSimCandArgs ac{i8 ? h->tokens_i8.p : reinterpret_cast<const unsigned char*>(h->tokens_h.p), h->scales.p, ld, h->d_cptr.p, h->cand.p,
-                                    cand->ptr ? h->cand_ptr.p + q0 : nullptr, (uint32_t)cand->n_shared, (uint32_t)pitch, h->q.p, h->qdesc.p, h->cut.S.p};
-            switch (tiles) {
-            case 1: LY_TRY(maxsim_cand_launch<1>(ac, i8, grid, cw, lds, st)); break;
-            case 2: LY_TRY(maxsim_cand_launch<2>(ac, i8, grid, cw, lds, st)); break;
-            case 4: LY_TRY(maxsim_cand_launch<4>(ac, i8, grid, cw, lds, st)); break;
-            default: LY_TRY(maxsim_cand_launch<8>(ac, i8, grid, cw, lds, st)); break;
+        // The scan: a wave per range, `waves` of them a workgroup.  The candidate kernels: a wave per (query, candidate), workgroups of
+        // up to 4 waves, as many of them a query as fill the part once over the chunk.  The LDS is the plan's for both.
+        const uint32_t cw = (uint32_t)std::min<uint64_t>(MAXSIM_MAX_WAVES, live);
+        const uint32_t per_q = std::max<uint32_t>(1u, h->num_cu * wg_per_cu / nqc);
+        const dim3 grid(cand ? (uint32_t)std::min<uint64_t>((live + cw - 1) / cw, per_q) : std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
+        const dim3 block((cand ? cw : waves) * 64u);
+        // the scans' arguments are the same tables and queries for every dtype: only the type of a token row differs
+        auto scan_args = [&]<typename T>(const T* rows) {
+            return MaxSimArgsT<T>{rows, ld, h->d_cptr.p, h->d_crec.p, m, h->d_ranges.p, n_ranges, h->q.p, h->qdesc.p, masked ? h->mask.p : nullptr, mask_words, h->cut.S.p};
+        };
+        LY_TRY(maxsim_by_tiles(tiles, [&](auto nt) -> int {
+            constexpr int NT = decltype(nt)::value;
+            if (cand) {
+                const MaxSimCandArgs ac{h->tokens.p, h->scales.p, ld, h->d_cptr.p, h->cand.p, cand->ptr ? h->cand_ptr.p + q0 : nullptr, (uint32_t)cand->n_shared,
+                                        (uint32_t)pitch, h->q.p, h->qdesc.p, h->cut.S.p};
+                return dt.scaled ? launch_lds<k_maxsim_cand_i8<NT>>(grid, block, lds, st, ac) : launch_lds<k_maxsim_cand_h16<NT>>(grid, block, lds, st, ac);
             }
-        } else {
-        const MaxSimArgs a{h->tokens.p, ld, h->d_cptr.p, h->d_crec.p, m, h->d_ranges.p, n_ranges, h->q.p, h->qdesc.p,
-                           masked ? h->mask.p : nullptr, mask_words, h->cut.S.p};
-        const dim3 grid(std::min<uint32_t>((n_ranges + waves - 1) / waves, h->num_cu * wg_per_cu), nqc);
-        if (i8) {   // the same tables and queries, the token rows as codes with a scale each
-            const MaxSimI8Args ai{{reinterpret_cast<const int8_t*>(h->tokens_i8.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S}, h->scales.p};
-            switch (tiles) {
-            case 1: LY_TRY(maxsim_i8_launch<1>(ai, grid, lds, st)); break;
-            case 2: LY_TRY(maxsim_i8_launch<2>(ai, grid, lds, st)); break;
-            case 4: LY_TRY(maxsim_i8_launch<4>(ai, grid, lds, st)); break;
-            default: LY_TRY(maxsim_i8_launch<8>(ai, grid, lds, st)); break;
+            switch (h->dtype) {
+            case 0: return launch_lds<k_maxsim_scan<NT>>(grid, block, lds, st, scan_args(reinterpret_cast<const float*>(h->tokens.p)));
+            case 1: return launch_lds<k_maxsim_h16<NT>>(grid, block, lds, st, scan_args(reinterpret_cast<const _Float16*>(h->tokens.p)));
+            default: return launch_lds<k_maxsim_i8<NT>>(grid, block, lds, st, MaxSimI8Args{scan_args(reinterpret_cast<const int8_t*>(h->tokens.p)), h->scales.p});
             }
-        } else if (h16) {   // the same tables and queries, the token rows as halves
-            const MaxSimH16Args ah{reinterpret_cast<const _Float16*>(h->tokens_h.p), ld, a.cptr, a.crec, m, a.ranges, n_ranges, a.Q, a.qdesc, a.mask, mask_words, a.S};
-            switch (tiles) {
-            case 1: LY_TRY(maxsim_h16_launch<1>(ah, grid, lds, st)); break;
-            case 2: LY_TRY(maxsim_h16_launch<2>(ah, grid, lds, st)); break;
-            case 4: LY_TRY(maxsim_h16_launch<4>(ah, grid, lds, st)); break;
-            default: LY_TRY(maxsim_h16_launch<8>(ah, grid, lds, st)); break;
-            }
-        } else {
-            switch (tiles) {
-            case 1: LY_TRY(maxsim_launch<1>(a, grid, waves, lds, st)); break;
-            case 2: LY_TRY(maxsim_launch<2>(a, grid, waves, lds, st)); break;
-            case 4: LY_TRY(maxsim_launch<4>(a, grid, waves, lds, st)); break;
-            default: LY_TRY(maxsim_launch<8>(a, grid, waves, lds, st)); break;
-            }
-        }
-        }
+        }));
         if (timed) {
             LY_HIP(hipEventRecord(h->ev[1], st));
-            const uint64_t row_bytes = i8 ? ld + 4 : ld * (h16 ? 2 : 4);
+            const uint64_t row_bytes = (uint64_t)ld * dt.esz + (dt.scaled ? 4u : 0u);
             h->prof.scan_launches += 1;
             h->prof.last_plan = cand ? 1 : 0;
             if (cand) {   // the rows and bytes the candidate kernel read: the listed records' tokens, their list entries and extents
@@ -662,8 +602,8 @@ extern "C" int lynse_hip_multivec_rerank_f32(lynse_hip_multivec* h, const float*
         if (cand_ptr[i + 1] > cand_ptr[i] && cand_rows[cand_ptr[i + 1] - 1] >= h->n)
             return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector rerank: candidate row " + std::to_string(cand_rows[cand_ptr[i + 1] - 1]) + " is not a record (n = " +
                                                              std::to_string(h->n) + ")");
-    LY_TRY(maxsim_plan(h->dim, tq_max, h->dtype, nullptr, nullptr, nullptr));
-    if (h->dtype == 0) {
+    LY_TRY(maxsim_plan(h->dim, tq_max, h->dtype, nullptr));
+    if (!MAXSIM_DTYPES[h->dtype].cand) {
         // an f32 store has no candidate kernel: the scan once per query with the query's candidates as its BitSet — the same
         // results at the scan's cost
         std::vector<uint64_t> words((h->n + 63) / 64 + 1);
