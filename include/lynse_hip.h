@@ -1124,7 +1124,33 @@ int lynse_hip_sparse_profile_get(lynse_hip_sparse *h, lynse_hip_profile *out, in
  *      then added in tile order, ((T_0 + T_1) + T_2) + ..., separate adds.  (This order is this store's own, not rule 4.)
  *  7". 1 <= dim_mv <= 1024 and 1 <= tokens of a query <= 256.  The LDS holds the query's tiles as codes at a row pitch of ld + 16
  *      bytes, their scales and 512 B of flags: tiles * 32 * (ld + 20) + 512 <= 160 KiB or LYNSE_ERR_UNSUPPORTED ("... do not fit in
- *      LDS").  That serves 256 query tokens up to dim_mv 608 and 128 up to 1024: every dim_mv in 1 .. 1024 can be created. */
+ *      LDS").  That serves 256 query tokens up to dim_mv 608 and 128 up to 1024: every dim_mv in 1 .. 1024 can be created.
+ *
+ * MXFP4 TOKEN STORAGE (lynse_hip_multivec_create_mxfp4; index mode MULTIVEC-MAXSIM-IP-MXFP4).  Token rows are OCP MX blocks: 32 E2M1
+ * (4-bit) codes under one E8M0 scale byte; the query is kept at higher precision, MXFP8 (E4M3 codes, the same blocks); the scan is
+ * k_maxsim_mx4 on v_mfma_scale_f32_32x32x64_f8f6f4, which takes both formats and applies both scales.  lynse_hip_multivec_append takes
+ * f32 rows and quantises them on the device; lynse_hip_multivec_append_f16 on such a handle is LYNSE_ERR_INVALID_ARGUMENT.  Every step
+ * below is exact or a stated rounding.  Rules 5, 6, 8 and 9 stand; the others read:
+ *  1'''. Token row.  ld = dim_mv rounded up to a multiple of 32 elements, zero past dim_mv, in blocks of 32 consecutive elements.  Per
+ *      block: amax = max_k |p_k| (a NaN element is skipped).  amax 0 or +inf, or every element NaN: every code 0 and the scale byte
+ *      127.  Otherwise E = clamp(floor(log2 amax) - 2, -127, 127) from the f32 exponent of amax (a subnormal amax gives -127), the
+ *      scale byte is E + 127, v_k = p_k * 2^-E, and the code is the E2M1 value nearest v_k out of +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}; a
+ *      tie goes to the code whose low bit is 0 (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), |v_k| > 6
+ *      saturates to +-6, NaN codes as 0.  Two codes a byte, the low nibble the even element: ld / 2 bytes a row.  The scale bytes
+ *      are an array of their own, ld / 32 a row padded with 127 to a multiple of 4 bytes.
+ *  1''''. Query token.  The same blocks with E = clamp(floor(log2 amax) - 8, -127, 127) and the code v_k rounded to nearest even to
+ *      E4M3 (e4m3fn: 3 mantissa bits, subnormals at 2^-9), saturated at +-448, NaN as 0; the degenerate block as for tokens.  Done on
+ *      the device as the tiles are staged.
+ *  2'''. Score block.  s_ij = sum over the blocks of 2^(Eq + Ep) * sum_k cq_ik * cp_jk, accumulated in f32 by the instruction; every
+ *      product is exact (4 x 2 significant bits), the order and internal rounding of the sum are the hardware's and not part of the
+ *      contract.
+ *  3'''. m_i = max_j s_ij over the record's tokens; a NaN s_ij is skipped, all NaN: -inf.
+ *  4'''. Sum: rule 4" (the pairwise tree inside a tile of 32 query tokens, slots past the query +0.0f, then the tiles in order).
+ *  7'''. 1 <= dim_mv <= 1024 and 1 <= tokens of a query <= 256.  The LDS holds the query's tiles as E4M3 bytes at a row pitch of
+ *      ld + 16 bytes, ld / 32 scale bytes a query row and 512 B of flags: tiles * 32 * (ld + 16 + ld / 32) + 512 <= 160 KiB or
+ *      LYNSE_ERR_UNSUPPORTED ("... do not fit in LDS").  That serves 256 query tokens up to dim_mv 576 and 128 up to 1024: every
+ *      dim_mv in 1 .. 1024 can be created.  Always 4 waves.
+ *  No candidate kernel exists for this store: the rerank entry and a sparse filter take the masked scan, as for an f32 store. */
 typedef struct lynse_hip_multivec lynse_hip_multivec;
 /* dtype: 0 = f32 (lynse_hip_multivec_create), 1 = f16; anything else LYNSE_ERR_INVALID_ARGUMENT */
 int lynse_hip_multivec_create_dtype(int device, uint32_t dim_mv, int dtype, lynse_hip_multivec **out);
@@ -1136,6 +1162,10 @@ int lynse_hip_multivec_append_f16(lynse_hip_multivec *h, const uint16_t *tokens,
 int lynse_hip_multivec_create_i8(int device, uint32_t dim_mv, lynse_hip_multivec **out);
 /* rule 7" for a query of tq tokens at dim_mv, host only (waves: always 4) */
 int lynse_hip_multivec_plan_i8(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
+/* an MXFP4 store (MXFP4 TOKEN STORAGE); the append, search, rerank, counts, profile and destroy calls serve it too */
+int lynse_hip_multivec_create_mxfp4(int device, uint32_t dim_mv, lynse_hip_multivec **out);
+/* rule 7''' for a query of tq tokens at dim_mv, host only (waves: always 4) */
+int lynse_hip_multivec_plan_mxfp4(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
 /* Rule 7 for a query of tq tokens at dim_mv, host only (no handle, no device): the query tiles held in LDS, the waves of a workgroup
  * and the LDS bytes; LYNSE_ERR_UNSUPPORTED with the message of rule 7 where the answer is a refusal.  Each output may be NULL. */
 int lynse_hip_multivec_plan(uint32_t dim_mv, uint32_t tq, uint32_t *out_tiles, uint32_t *out_waves, uint64_t *out_lds_bytes);
@@ -1168,7 +1198,7 @@ int lynse_hip_multivec_profile_get(lynse_hip_multivec *h, lynse_hip_profile *out
  *  5. int8 store: the score bits of a record equal those of lynse_hip_multivec_search_f32 (every step of rules 1" - 4" is exact or
  *     one f32 rounding).  f16 store: rules 3 and 4 are followed to the letter; the order inside rule 2' is the hardware's for either
  *     kernel, and the token rows are the A operand here, the B operand in the scan.
- *  6. f32 store: NO candidate kernel exists for it in this build.  The entry answers by running the scan once per query with that
+ *  6. f32 or MXFP4 store: NO candidate kernel exists for it in this build.  The entry answers by running the scan once per query with that
  *     query's candidates as the BitSet: the same results, at the cost of one full scan a query.
  *  7. The lock, the stream and the scratch are the handle's (rule 8 of the search).  Profile: scan_launches counts the candidate
  *     launches, scan_rows / scan_bytes the token rows and bytes they actually read (the listed records' rows, their list entries and

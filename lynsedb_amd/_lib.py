@@ -258,6 +258,8 @@ SIGNATURES = {
     "lynse_hip_multivec_append_f16": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "lynse_hip_multivec_create_i8": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(_vp)]),
     "lynse_hip_multivec_plan_i8": (C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, _u64p]),
+    "lynse_hip_multivec_create_mxfp4": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(_vp)]),
+    "lynse_hip_multivec_plan_mxfp4": (C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, _u64p]),
     "lynse_hip_multivec_destroy": (C.c_int, [_vp]),
     "lynse_hip_multivec_append": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "lynse_hip_multivec_counts": (C.c_int, [_vp, _u64p, _u64p, _u64p]),

@@ -1629,27 +1629,32 @@ class SparseIndex:
 MULTIVEC_INDEX_MODE = "MULTIVEC-MAXSIM-IP"
 MULTIVEC_INDEX_MODE_F16 = "MULTIVEC-MAXSIM-IP-F16"   # f16 token storage (include/lynse_hip.h, F16 TOKEN STORAGE)
 MULTIVEC_INDEX_MODE_I8 = "MULTIVEC-MAXSIM-IP-I8"     # int8 token storage (include/lynse_hip.h, INT8 TOKEN STORAGE)
+MULTIVEC_INDEX_MODE_MXFP4 = "MULTIVEC-MAXSIM-IP-MXFP4"   # MXFP4 token storage (include/lynse_hip.h, MXFP4 TOKEN STORAGE)
 MULTIVEC_MAX_QUERY_TOKENS = 256   # include/lynse_hip.h, MULTI-VECTOR SEARCH rule 7
 MULTIVEC_MAX_DIM = 1024
 
 
 def _multivec_dtype(dtype) -> Optional[str]:
-    """None, "i8" for "i8" / "int8", or "f32" / "f16" for the spellings of `vector_dtype_name`"""
+    """None, "i8" for "i8" / "int8", "mxfp4" for "mxfp4" / "fp4", or "f32" / "f16" for the spellings of `vector_dtype_name`"""
     if dtype is None:
         return None
     if str(dtype).strip().lower() in ("i8", "int8"):
         return "i8"
+    if str(dtype).strip().lower() in ("mxfp4", "fp4"):
+        return "mxfp4"
     return {"float32": "f32", "float16": "f16"}[vector_dtype_name(dtype)]
 
 
 def _multivec_mode(dtype: Optional[str]) -> str:
-    return {"f16": MULTIVEC_INDEX_MODE_F16, "i8": MULTIVEC_INDEX_MODE_I8}.get(dtype, MULTIVEC_INDEX_MODE)
+    return {"f16": MULTIVEC_INDEX_MODE_F16, "i8": MULTIVEC_INDEX_MODE_I8, "mxfp4": MULTIVEC_INDEX_MODE_MXFP4}.get(dtype, MULTIVEC_INDEX_MODE)
 
 
 def _multivec_plan(dim: int, tq: int, dtype: Optional[str]) -> None:
-    """the LDS half of rule 7 (7' for an f16 store, 7" for an int8 one), host only: raises where the answer is a refusal"""
+    """the LDS half of rule 7 (7' for an f16 store, 7" for an int8 one, 7''' for an MXFP4 one), host only: raises where the answer is a refusal"""
     if dtype == "i8":
         check(lib.lynse_hip_multivec_plan_i8(dim, tq, None, None, None))
+    elif dtype == "mxfp4":
+        check(lib.lynse_hip_multivec_plan_mxfp4(dim, tq, None, None, None))
     else:
         check(lib.lynse_hip_multivec_plan_dtype(dim, tq, int(dtype == "f16"), None, None, None))
 
@@ -1677,13 +1682,16 @@ def _multivec_queries(queries, dim: Optional[int], dtype: Optional[str] = None) 
 class MultiVectorIndex:
     """The token rows of multi-vector records in HBM, append-only, and their exact MaxSim scan: f32 rows (k_maxsim_scan) or, with
     dtype="f16", half the bytes (k_maxsim_h16; tokens and queries rounded to f16, subnormals flushed), or, with dtype="i8", int8 codes
-    and one f32 scale a token (k_maxsim_i8; tokens and queries quantised on the device, scores reproducible bit for bit)."""
+    and one f32 scale a token (k_maxsim_i8; tokens and queries quantised on the device, scores reproducible bit for bit), or, with
+    dtype="mxfp4", OCP MX blocks of 32 E2M1 nibbles under one E8M0 scale byte (k_maxsim_mx4; the query as MXFP8 E4M3 blocks)."""
 
     def __init__(self, dim: int, device: Optional[int] = None, dtype: str = "f32"):
         self._h, self._dim, self.dtype = C.c_void_p(), int(dim), _multivec_dtype(dtype)
         dev = default_device() if device is None else int(device)
         if self.dtype == "i8":
             check(lib.lynse_hip_multivec_create_i8(dev, self._dim, C.byref(self._h)))
+        elif self.dtype == "mxfp4":
+            check(lib.lynse_hip_multivec_create_mxfp4(dev, self._dim, C.byref(self._h)))
         else:
             check(lib.lynse_hip_multivec_create_dtype(dev, self._dim, int(self.dtype == "f16"), C.byref(self._h)))
 
@@ -1737,8 +1745,8 @@ class MultiVectorIndex:
     def rerank_batch_arrays(self, queries, cand_rows_list, k: int):
         """MaxSim over per-query candidate lists (include/lynse_hip.h, MULTI-VECTOR RERANK): query i against the record rows
         cand_rows_list[i], strictly ascending, and nothing else of the store -> (rows u64[nq, k], scores f32[nq, k], counts u32[nq])
-        by (score descending, record row ascending).  f16 / i8 stores run k_maxsim_cand_h16 / k_maxsim_cand_i8; an f32 store runs the
-        scan once per query with the list as its mask."""
+        by (score descending, record row ascending).  f16 / i8 stores run k_maxsim_cand_h16 / k_maxsim_cand_i8; an f32 or MXFP4 store
+        runs the scan once per query with the list as its mask."""
         queries = _multivec_queries(queries, self._dim, self.dtype)
         nq, k = len(queries), int(k)
         if k < 0:
@@ -3215,7 +3223,7 @@ class Collection:
     # -- multi-vector records (include/lynse_hip.h, MULTI-VECTOR SEARCH) ------------
     def _mv_reset(self) -> None:
         self._mv_dim = None             # dim_mv, fixed by the first add_multi_vectors
-        self._mv_dtype = None           # "f32" | "f16", fixed by it too
+        self._mv_dtype = None           # "f32" | "f16" | "i8" | "mxfp4", fixed by it too
         self._mv_ids: list = []         # record row -> user id, in the order added (the store is append-only)
         self._mv_seen: set = set()
         self._mv_dead: set = set()      # ids that `compact` removed from the collection: their records are never returned again
@@ -3234,7 +3242,9 @@ class Collection:
         subnormals to zero), np.float16 arrays are taken as they are, queries are rounded the same way, every dim_mv up to 1024 is
         accepted, and the mode reported is MULTIVEC-MAXSIM-IP-F16.  An "i8"/"int8" store holds a quarter of the bytes plus one f32 scale
         a token: the f32 token arrays (np.float16 ones are widened) wait on the host and are quantised on the device at upload, as is
-        each query; every dim_mv up to 1024 is accepted and the mode is MULTIVEC-MAXSIM-IP-I8."""
+        each query; every dim_mv up to 1024 is accepted and the mode is MULTIVEC-MAXSIM-IP-I8.  An "mxfp4"/"fp4" store holds half a byte
+        an element plus one scale byte per 32 (OCP MX blocks), quantised on the device at upload the same way; each query becomes
+        MXFP8 (E4M3) blocks; every dim_mv up to 1024 is accepted and the mode is MULTIVEC-MAXSIM-IP-MXFP4."""
         ids = [int(i) for i in ids]
         want = _multivec_dtype(dtype) or self._mv_dtype or "f32"
         if self._mv_dtype is not None and want != self._mv_dtype:
@@ -3273,7 +3283,7 @@ class Collection:
         return len(self._mv_ids)
 
     def multi_vector_dtype(self) -> Optional[str]:
-        """"f32", "f16" or "i8" once the first add_multi_vectors has fixed it, None before"""
+        """"f32", "f16", "i8" or "mxfp4" once the first add_multi_vectors has fixed it, None before"""
         return self._mv_dtype
 
     def _mv_upload(self) -> None:

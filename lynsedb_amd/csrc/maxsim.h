@@ -799,6 +799,327 @@ __global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_i
     }
 }
 
+// ---- MXFP4 token storage (include/lynse_hip.h, MULTI-VECTOR SEARCH, MXFP4 TOKEN STORAGE) -------------------------
+//   k_maxsim_mx4    k_maxsim_i8's split and swapped roles on v_mfma_scale_f32_32x32x64_f8f6f4: the block's token rows are the A
+//                   operand as E2M1 nibbles, the query tile the B operand as E4M3 bytes, and the E8M0 block scales of both go into
+//                   the instruction, so the accumulator IS s_ij.  A k-step is 64 columns; lane (j = lane % 32, h = lane / 32) gives it
+//                   the 32 columns at 32 h of token row j — exactly MX block 2 s + h of that row: 16 bytes (one global_load_dwordx4
+//                   into four of the operand's eight registers, the others zero) — and ONE scale byte, that block's.  The query
+//                   operand is 32 bytes a lane (two ds_read_b128) in the 8-bit layout, 16 columns of each of the step's two blocks
+//                   (maxsim_mx4_qfrag), with the scale byte of block 2 s + h.  A chunk of 128 columns is 2 k-steps = 4 MX blocks: 8 VGPRs of codes and
+//                   one dword of scale bytes a lane (shifted by 8 h as it arrives, so step p reads byte 2 p by the instruction's
+//                   byte select).  The chunks of the stream go through a ring of RING such buffers, loaded RING - 1 chunks ahead.
+//   k_maxsim_store_mx4  rule 1''': f32 rows [rows][dim] -> codes [rows][ld / 2] and scale bytes [rows][scale pitch], 4 lanes a block.
+typedef int maxsim_i32x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t maxsim_u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr uint32_t MAXSIM_MX_KC = 128;             // columns of a chunk: 2 k-steps of 64
+constexpr uint32_t MAXSIM_MX_UNIT = 0x7f7f7f7fu;   // four E8M0 bytes 127 = 2^0: the scale next to an operand that is zero
+
+// LDS row pitch of a query tile in BYTES (one E4M3 byte an element): ld + 16 = 16 s with s odd, as maxsim_i8_pitch.
+__host__ __device__ inline uint32_t maxsim_mx4_pitch(uint32_t ld) { return ld + 16u; }
+// HBM: the scale bytes of a token row, ld / 32 of them padded with 127 to whole dwords — a lane's load of a chunk's four is aligned
+__host__ __device__ inline uint32_t maxsim_mx4_scale_pitch(uint32_t ld) { return (ld / 32u + 3u) / 4u * 4u; }
+// LDS bytes: the query tiles as E4M3 bytes | their ld / 32 scale bytes a row | the 32 boundary flags of each of the (always 4) waves
+__host__ __device__ inline size_t maxsim_mx4_lds_bytes(uint32_t ld, uint32_t tiles) {
+    return (size_t)tiles * MAXSIM_BLOCK * (maxsim_mx4_pitch(ld) + ld / 32u) + (size_t)MAXSIM_MAX_WAVES * MAXSIM_BLOCK * 4u;
+}
+
+struct MaxSimMx4Args {
+    MaxSimArgsT<uint8_t> a;   // the token rows are E2M1 codes, two a byte (low nibble the even element): ld / 2 BYTES a row
+    const uint8_t* scales;    // [total tokens][maxsim_mx4_scale_pitch(ld)]
+};
+
+// Rules 1''' (SHIFT 2: amax lands in [4, 8), E2M1 tops at 6) and 1'''' (SHIFT 8: [256, 512), E4M3 tops at 448): the scale byte
+// E + 127 = max(biased exponent of amax - SHIFT, 0) — a subnormal amax clamps to E = -127 whatever its log2 — and inv = 2^-E.
+// amax 0 (every element 0 or NaN: fmaxf skipped them) or +inf: byte 127 and inv 0, which codes every element as 0.
+template <int SHIFT>
+__device__ __forceinline__ void maxsim_mx_scale(float amax, uint32_t& byte, float& inv) {
+    const bool none = amax == 0.0f || amax == __builtin_huge_valf();
+    const int e = (int)(__float_as_uint(amax) >> 23) - SHIFT;
+    byte = none ? 127u : (uint32_t)(e < 0 ? 0 : e);
+    inv = none ? 0.0f : __uint_as_float((254u - byte) << 23);
+}
+// the E2M1 code nearest v, ties to the code whose low bit is 0, saturating at 6; NaN -> 0
+__device__ __forceinline__ uint32_t maxsim_e2m1(float v) {
+    const float m = fabsf(v);
+    const uint32_t c = (uint32_t)(m > 0.25f) + (uint32_t)(m >= 0.75f) + (uint32_t)(m > 1.25f) + (uint32_t)(m >= 1.75f) + (uint32_t)(m > 2.5f) +
+                       (uint32_t)(m >= 3.5f) + (uint32_t)(m > 5.0f);
+    return c ? c | ((__float_as_uint(v) >> 28) & 8u) : 0u;
+}
+// the E4M3 (e4m3fn) code nearest v, ties to even, subnormals at 2^-9, saturating at 448 = 0x7e; NaN -> 0
+__device__ __forceinline__ uint32_t maxsim_e4m3(float v) {
+    const float m = fabsf(v);
+    uint32_t b = __float_as_uint(m);
+    b += 0x7ffffu + ((b >> 20) & 1u);   // nearest even at 3 mantissa bits
+    uint32_t c = (b >> 20) - 960u;      // (exponent, mantissa) at e4m3's bias: 2^-6 = 121 << 3 -> 8
+    c = c > 0x7eu ? 0x7eu : c;
+    if (m < 0.015625f) c = (uint32_t)rintf(m * 512.0f);   // below the least normal: whole steps of 2^-9 (8 of them are that normal)
+    c = m == m ? c : 0u;
+    return c ? c | ((__float_as_uint(v) >> 24) & 0x80u) : 0u;
+}
+
+// 4 lanes a block of 32 elements: its amax over them (order-free), then 8 codes a lane as one 32-bit store and the block's scale byte.
+__global__ void __launch_bounds__(256) k_maxsim_store_mx4(const float* __restrict__ src, uint32_t* __restrict__ codes, uint8_t* __restrict__ scales,
+                                                          uint64_t rows, uint32_t dim, uint32_t ld) {
+    const uint32_t lane = threadIdx.x & 63u, sub = threadIdx.x & 3u, nsb = ld / 32u, sp = maxsim_mx4_scale_pitch(ld);
+    const uint64_t blk = (uint64_t)blockIdx.x * 64u + (threadIdx.x >> 2);
+    const bool in = blk < rows * nsb;   // (no early return: the lanes of a wave exchange below)
+    const uint64_t r = in ? blk / nsb : 0;
+    const uint32_t bk = in ? (uint32_t)(blk - r * nsb) : 0u, c0 = bk * 32u + sub * 8u;
+    float v[8], amax = 0.0f;
+#pragma unroll
+    for (uint32_t e = 0; e < 8u; ++e) {
+        v[e] = in && c0 + e < dim ? src[r * dim + c0 + e] : 0.0f;
+        amax = fmaxf(amax, fabsf(v[e]));
+    }
+    amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ 1u));
+    amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ 2u));
+    if (!in) return;
+    uint32_t byte, w = 0u;
+    float inv;
+    maxsim_mx_scale<2>(amax, byte, inv);
+#pragma unroll
+    for (uint32_t e = 0; e < 8u; ++e) w |= maxsim_e2m1(v[e] * inv) << (4u * e);
+    codes[blk * 4u + sub] = w;   // (a row is ld / 8 = 4 nsb dwords)
+    if (sub == 0u) {
+        scales[r * sp + bk] = (uint8_t)byte;
+        if (bk + 1u == nsb)
+            for (uint32_t b = nsb; b < sp; ++b) scales[r * sp + b] = 127u;
+    }
+}
+
+// The query tiles of a workgroup into LDS by rule 1'''', 4 lanes a block of 32 columns: the block's amax, then 8 E4M3 bytes a lane and
+// the block's scale byte; rows past the query's own tiles are never read (nor written: the scan skips those tiles).
+__device__ __forceinline__ void maxsim_mx4_stage(const float* Q, uint32_t tq_rows, uint32_t K, uint32_t PB, unsigned char* q_l, unsigned char* sq_l,
+                                                 uint32_t tid, uint32_t lane) {
+    const uint32_t sub = tid & 3u, nsb = K / 32u;
+    for (uint32_t p = tid >> 2; p < tq_rows * nsb; p += blockDim.x >> 2) {   // (uniform over a group of 4 lanes)
+        const uint32_t r = p / nsb, bk = p - r * nsb;
+        const float* src = Q + (size_t)r * K + bk * 32u + sub * 8u;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+        float amax = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) amax = fmaxf(fmaxf(amax, fabsf(lo[e])), fabsf(hi[e]));
+        amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ 1u));
+        amax = fmaxf(amax, maxsim_from_lane(amax, lane ^ 2u));
+        uint32_t byte;
+        float inv;
+        maxsim_mx_scale<8>(amax, byte, inv);
+        maxsim_u32x2 o = {0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o[0] |= maxsim_e4m3(lo[e] * inv) << (8 * e);
+            o[1] |= maxsim_e4m3(hi[e] * inv) << (8 * e);
+        }
+        *reinterpret_cast<maxsim_u32x2*>(q_l + (size_t)r * PB + bk * 32u + sub * 8u) = o;
+        if (sub == 0u) sq_l[r * nsb + bk] = (unsigned char)byte;
+    }
+}
+
+// One chunk of a block in the ring: the two 16-B code fragments of lane (col, half) and the chunk's four scale bytes of its row,
+// shifted so that byte 2 p is the block of k-step p and this half.
+struct MaxSimMx4Chunk {
+    maxsim_i32x4 f[2];
+    uint32_t sc;
+};
+// Lane (col, half) takes, of each of chunk c's 2 column groups of 64, the 16 bytes (32 codes) at 32 half of token row t_first + col,
+// and the dword of the row's scale bytes 4 c ...  Rows at or past `t_end` (the end of the wave's range, or a block past its last) and
+// the half-step past the row pitch are zero codes under a unit scale: nothing outside the range is read.
+__device__ __forceinline__ void maxsim_mx4_load(const MaxSimMx4Args& x, uint64_t t_first, uint64_t t_end, uint32_t c, uint32_t col, uint32_t half, MaxSimMx4Chunk& o) {
+    const bool in = t_first + col < t_end;
+    const uint32_t K = x.a.ld;
+    const uint64_t row = t_first + col;
+    o.sc = MAXSIM_MX_UNIT;
+    if (in) o.sc = *reinterpret_cast<const uint32_t*>(x.scales + (size_t)row * maxsim_mx4_scale_pitch(K) + c * 4u) >> (8u * half);
+#pragma unroll
+    for (uint32_t p = 0; p < 2u; ++p) {
+        o.f[p] = maxsim_i32x4{0, 0, 0, 0};
+        if (in && c * MAXSIM_MX_KC + p * 64u + half * 32u < K)
+            o.f[p] = *reinterpret_cast<const maxsim_i32x4*>(x.a.tokens + (size_t)row * (K / 2u) + c * (MAXSIM_MX_KC / 2u) + p * 32u + half * 16u);
+    }
+}
+// The matching query operand of one tile for the k-step at column k0 = 64 s.  An 8-bit operand is laid out differently from a 4-bit
+// one: registers 0 .. 3 of lane half h are columns k0 + 16 h .. + 15 (the step's first MX block), registers 4 .. 7 columns k0 + 32 +
+// 16 h .. (its second block) — while the SCALE of block h is still the one lanes of half h supply.  So the lane reads two 16-B pieces
+// 32 bytes apart and the scale byte of block 2 s + h.  Past the row pitch: zero under a unit scale (the pad of a row is never
+// written: an E4M3 NaN there would poison the sum).
+struct MaxSimMx4Q {
+    maxsim_i32x8 v;
+    uint32_t sc;
+};
+__device__ __forceinline__ MaxSimMx4Q maxsim_mx4_qfrag(const unsigned char* qrow, const unsigned char* srow, uint32_t k0, uint32_t half, uint32_t K) {
+    const maxsim_i32x4 lo = *reinterpret_cast<const maxsim_i32x4*>(qrow + k0 + half * 16u);   // (k0 < K, a multiple of 32: the first block exists)
+    maxsim_i32x4 hi = {0, 0, 0, 0};
+    if (k0 + 32u < K) hi = *reinterpret_cast<const maxsim_i32x4*>(qrow + k0 + 32u + half * 16u);
+    return MaxSimMx4Q{maxsim_i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}, k0 + half * 32u < K ? (uint32_t)srow[k0 / 32u + half] : 127u};
+}
+// k-step P of a chunk: A = 32 E2M1 codes (cbsz 4; four of the eight registers: the lane's own MX block, columns in order), its scale
+// byte 2 P of the shifted dword; B = 32 E4M3 bytes (blgp 0) in the 8-bit layout above, its scale in byte 0.
+template <int P>
+__device__ __forceinline__ f32x16 maxsim_mx4_mfma(const MaxSimMx4Chunk& ch, const MaxSimMx4Q& qf, f32x16 acc) {
+    const maxsim_i32x8 av = {ch.f[P][0], ch.f[P][1], ch.f[P][2], ch.f[P][3], 0, 0, 0, 0};
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, qf.v, acc, 4, 0, 2 * P, (int)ch.sc, 0, (int)qf.sc);
+#else
+    (void)av;
+    return acc;
+#endif
+}
+
+// Rules 3''' and 4''' for the finished block, k_maxsim_i8's walk with the accumulator already s_ij: down the 32 token rows in groups
+// of 8 (rows 8 g .. 8 g + 3 are registers 4 g .. of half 0, the next four of half 1), run[t] the maximum so far of the open record.
+template <int NT>
+__device__ __forceinline__ LY_MAXSIM_FN void maxsim_mx4_fold(const MaxSimArgsT<uint8_t>& a, const f32x16 (&acc)[NT], float (&run)[NT], const MaxSimBounds& bd,
+                                                             uint32_t nrows, uint32_t tq, uint32_t q, uint32_t rc0, uint32_t lane, uint32_t col) {
+    const float NINF = -__builtin_huge_valf();
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (8u * g >= nrows) continue;
+        if (8u * g + 8u <= nrows && ((bd.endmask >> (8 * g)) & 0xffu) == 0u) {
+            // no record ends in these 8 rows: each half folds its own four, one exchange joins them in both halves
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                const float m4 = fmaxf(fmaxf(acc[t][4 * g], acc[t][4 * g + 1]), fmaxf(acc[t][4 * g + 2], acc[t][4 * g + 3]));
+                float lo, hi;
+                maxsim_i8_halves(m4, lo, hi);
+                run[t] = fmaxf(run[t], fmaxf(lo, hi));
+            }
+            continue;
+        }
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {   // the owning half of rows 8 g + 4 o ..: its lanes hold the record's maximum so far
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t row = 8u * g + 4u * o + e;
+                if (row >= nrows) continue;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                    run[t] = fmaxf(run[t], acc[t][4 * g + e]);   // (fmaxf skips a NaN s_ij: all NaN leaves -inf)
+                }
+                if ((bd.endmask >> row) & 1u) {   // a record ends here: rule 4''' in the owning half
+                    float s = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                        const float tile = maxsim_i8_tree((uint32_t)t * 32u + col < tq ? run[t] : 0.0f);
+                        s = t == 0 ? tile : s + tile;
+                        run[t] = NINF;
+                    }
+                    if (lane == 32u * o) {
+                        const uint32_t cr = rc0 + (uint32_t)__popc(bd.endmask & ((1u << row) - 1u));
+                        const bool live = !a.mask || range_live(a.mask, a.mask_words, a.crec[cr]);
+                        a.S[(size_t)q * a.m + cr] = live ? score_ord(s, false) : RANGE_FAIL;
+                    }
+                }
+            }
+            // hand the maximum so far to the other half, which owns the next four rows (both halves agree after it)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                float lo, hi;
+                maxsim_i8_halves(run[t], lo, hi);
+                run[t] = o == 0 ? lo : hi;
+            }
+        }
+    }
+}
+
+// NT = query tiles of 32 rows the LDS holds (1, 2, 4 or 8); a query of fewer tiles skips the rest.  grid.x strides over the ranges,
+// grid.y is the query; 4 waves.  RING - 1 = the chunks a load runs ahead: a chunk is 9 registers, about half of k_maxsim_i8's 16, and
+// the difference goes into depth (DESIGN.md §33 has the register report behind the choice).
+template <int NT>
+__global__ void LY_MAXSIM_FN __launch_bounds__(MAXSIM_MAX_WAVES * 64) k_maxsim_mx4(MaxSimMx4Args x) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm_maxsim_mx4[];
+    constexpr int RING = NT <= 2 ? 6 : 4;
+    const MaxSimArgsT<uint8_t>& a = x.a;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = lane & 31u, half = lane >> 5;
+    const uint32_t wave = maxsim_uniform(tid >> 6), waves = blockDim.x >> 6;
+    const uint32_t K = a.ld, NSB = K / 32u, PB = maxsim_mx4_pitch(K), nch = (K + MAXSIM_MX_KC - 1u) / MAXSIM_MX_KC;
+    const uint32_t q = blockIdx.y;
+    const uint64_t q_off = a.qdesc[2u * q];
+    const uint32_t tq = (uint32_t)a.qdesc[2u * q + 1u], tq_rows = (tq + 31u) / 32u * 32u;
+    unsigned char* q_l = sm_maxsim_mx4;
+    unsigned char* sq_l = q_l + (size_t)NT * MAXSIM_BLOCK * PB;
+    uint32_t* flag_l = reinterpret_cast<uint32_t*>(sq_l + (size_t)NT * MAXSIM_BLOCK * NSB) + wave * MAXSIM_BLOCK;
+    maxsim_mx4_stage(a.Q + q_off, tq_rows, K, PB, q_l, sq_l, tid, lane);
+    __syncthreads();   // the only workgroup barrier: from here on the waves run their own ranges
+    // this lane's query column: row `col` of each tile, its E4M3 bytes and its scale bytes
+    const unsigned char* qa = q_l + (size_t)col * PB;
+    const unsigned char* qs = sq_l + (size_t)col * NSB;
+    // one tile: the operands of the first chunk stay in registers for the whole kernel — up to 128 columns the loop reads no LDS
+    MaxSimMx4Q qreg[2];
+    if constexpr (NT == 1) {
+        qreg[0] = maxsim_mx4_qfrag(qa, qs, 0u, half, K);
+        if (64u < K) qreg[1] = maxsim_mx4_qfrag(qa, qs, 64u, half, K);
+    }
+    const float NINF = -__builtin_huge_valf();
+    for (uint32_t r = blockIdx.x * waves + wave; r < a.n_ranges; r += gridDim.x * waves) {
+        const uint32_t ca = maxsim_uniform(a.ranges[r]), cb = maxsim_uniform(a.ranges[r + 1u]);
+        const uint64_t t0 = maxsim_uniform(a.cptr[ca]), t1 = maxsim_uniform(a.cptr[cb]);
+        const uint32_t nb = (uint32_t)((t1 - t0 + MAXSIM_BLOCK - 1u) / MAXSIM_BLOCK);
+        MaxSimMx4Chunk buf[RING];
+        uint32_t lb = 0, lc = 0;   // the load cursor: block and chunk, RING - 1 chunks ahead of (b, c)
+#pragma unroll
+        for (int i = 0; i < RING - 1; ++i) {
+            maxsim_mx4_load(x, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc, col, half, buf[i]);
+            if (++lc == nch) lc = 0, ++lb;
+        }
+        uint32_t rc0 = ca;   // the record of the block's first token
+        float run[NT];       // the maximum so far of the record that is open, ONE register a tile: it runs on from block to block
+        f32x16 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) run[t] = NINF;
+        uint64_t rec_end = ~0ull;
+        uint32_t b = 0, c = 0;
+        while (b < nb) {
+#pragma unroll
+            for (int i = 0; i < RING; ++i) {
+                if (b < nb) {
+                    const uint64_t tb = t0 + (uint64_t)b * MAXSIM_BLOCK;
+                    if (c == 0u) {
+                        // the ends of the records from rc0 on, asked for BEFORE the chunk ahead: the epilogue's wait then leaves that one in flight
+                        rec_end = ~0ull;
+                        if (lane < 32u && (uint64_t)rc0 + 1u + lane <= cb) rec_end = a.cptr[rc0 + 1u + lane];
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) acc[t] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                    }
+                    maxsim_mx4_load(x, t0 + (uint64_t)lb * MAXSIM_BLOCK, lb < nb ? t1 : 0ull, lc, col, half, buf[(i + RING - 1) % RING]);
+                    if (++lc == nch) lc = 0, ++lb;
+                    const uint32_t kc = c * MAXSIM_MX_KC;
+                    // a token fragment meets every tile before the next one: consecutive MFMAs write different accumulators
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                        const MaxSimMx4Q qf = NT == 1 && c == 0u ? qreg[0] : maxsim_mx4_qfrag(qa + (size_t)t * 32u * PB, qs + (size_t)t * 32u * NSB, kc, half, K);
+                        acc[t] = maxsim_mx4_mfma<0>(buf[i], qf, acc[t]);
+                    }
+                    if (kc + 64u < K) {
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if (t != 0 && (uint32_t)t * 32u >= tq) continue;
+                            const MaxSimMx4Q qf = NT == 1 && c == 0u ? qreg[1] : maxsim_mx4_qfrag(qa + (size_t)t * 32u * PB, qs + (size_t)t * 32u * NSB, kc + 64u, half, K);
+                            acc[t] = maxsim_mx4_mfma<1>(buf[i], qf, acc[t]);
+                        }
+                    }
+                    if (c + 1u == nch) {   // the block's last chunk: rules 3''' and 4''', the scores of the records that end in it
+                        const uint32_t nrows = t1 - tb < MAXSIM_BLOCK ? (uint32_t)(t1 - tb) : MAXSIM_BLOCK;   // rows of the block inside the range
+                        const MaxSimBounds bd = maxsim_h16_bounds(rec_end, tb, b + 1u < nb, lane, col, flag_l);
+                        maxsim_mx4_fold<NT>(a, acc, run, bd, nrows, tq, q, rc0, lane, col);
+                        rc0 += bd.n_adv;
+                        c = 0u;
+                        ++b;
+                    } else {
+                        ++c;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- candidate lists (include/lynse_hip.h, MULTI-VECTOR RERANK) ----------------------------------------------------
 //   k_maxsim_cand_h16 / k_maxsim_cand_i8   MaxSim over per-query candidate lists: a gather, not the scan with an indirection.  A
 //                   work item is one (query, candidate record) pair and ONE WAVE owns it; the workgroups of a query (grid.y) take

@@ -11,9 +11,9 @@ struct lynse_hip_multivec {
     hipStream_t stream = nullptr;
     uint32_t dim = 0, ld = 0;
     int dtype = 0;                          // the tag of MAXSIM_DTYPES: 0 f32 (k_maxsim_scan), 1 f16 (k_maxsim_h16), 2 int8 codes (internal,
-                                            // lynse_hip_multivec_create_i8: k_maxsim_i8)
+                                            // lynse_hip_multivec_create_i8: k_maxsim_i8), 3 MXFP4 codes (lynse_hip_multivec_create_mxfp4: k_maxsim_mx4)
     DevBuf<uint8_t> tokens;                 // the token rows, ld elements of the dtype each (cap counts bytes)
-    DevBuf<float> scales;                   // int8: one a token row
+    DevBuf<uint8_t> scales;                 // int8: one f32 a token row; MXFP4: the E8M0 bytes of its blocks (cap counts bytes)
     uint64_t n = 0, total = 0;              // records (those without tokens included), token rows
     // the records that have tokens, which are all the kernel sees: their token offsets, their record rows, and the wave ranges
     std::vector<uint64_t> cptr{0};
@@ -34,22 +34,28 @@ struct lynse_hip_multivec {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // the scan begins / the scan ends / the last launch of the chunk
 };
 
-// What the host code knows of a token dtype, by the handle's tag: 0 and 1 are the public dtype ids, 2 is the int8 store.
+// What the host code knows of a token dtype, by the handle's tag: 0 and 1 are the public dtype ids, 2 is the int8 store, 3 the MXFP4 one.
 struct MaxSimDtype {
-    uint32_t esz;        // bytes of a stored element
-    bool scaled;         // a token row has an f32 scale next to it (`scales`)
+    uint32_t hb;         // half-bytes of a stored element
+    uint32_t (*scale_bytes)(uint32_t ld);   // the bytes a token row has in `scales`; NULL: the dtype has no scales
     bool shrink;         // the waves of a workgroup go 4, 2, 1 until the LDS fits: only the f32 kernel keeps token blocks there
     bool cand;           // the dtype has candidate kernels (k_maxsim_cand_*)
+    uint32_t two_tiles;  // the most query tiles at which the kernel's registers still let two of its waves share a SIMD
     const char* what;    // what does not fit, in the refusal of a plan
     size_t (*lds)(uint32_t ld, uint32_t tiles, uint32_t waves);
     // Workgroups a CU holds by the kernels' registers (resource_usage.txt).  k_maxsim_scan: one wave per SIMD at 8 tiles, two or
-    // three below.  k_maxsim_h16, k_maxsim_i8 (a workgroup = one wave per SIMD): two waves per SIMD at 1 and 2 tiles, one above.
-    uint32_t wg_cap(uint32_t tiles, uint32_t waves) const { return shrink ? (tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves)) : (tiles <= 2 ? 2u : 1u); }
+    // three below.  k_maxsim_h16, k_maxsim_i8 (a workgroup = one wave per SIMD): two waves per SIMD at 1 and 2 tiles, one above;
+    // k_maxsim_mx4 (232 registers at 4 tiles, its ring being half the size): two up to 4 tiles.
+    size_t row_bytes(uint32_t ld) const { return (size_t)ld * hb / 2; }
+    size_t srow_bytes(uint32_t ld) const { return scale_bytes ? scale_bytes(ld) : 0; }
+    uint32_t wg_cap(uint32_t tiles, uint32_t waves) const { return shrink ? (tiles == 8 ? 1u : 2u * (MAXSIM_MAX_WAVES / waves)) : (tiles <= two_tiles ? 2u : 1u); }
 };
-constexpr MaxSimDtype MAXSIM_DTYPES[3] = {
-    {4, false, true, false, "and two token blocks", [](uint32_t ld, uint32_t tiles, uint32_t waves) { return maxsim_lds_bytes(ld, tiles, waves); }},
-    {2, false, false, true, "of f16 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_h16_lds_bytes(ld, tiles); }},
-    {1, true, false, true, "of int8 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_i8_lds_bytes(ld, tiles); }},
+constexpr MaxSimDtype MAXSIM_DTYPES[4] = {
+    {8, nullptr, true, false, 0, "and two token blocks", [](uint32_t ld, uint32_t tiles, uint32_t waves) { return maxsim_lds_bytes(ld, tiles, waves); }},
+    {4, nullptr, false, true, 2, "of f16 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_h16_lds_bytes(ld, tiles); }},
+    {2, [](uint32_t) { return 4u; }, false, true, 2, "of int8 tokens", [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_i8_lds_bytes(ld, tiles); }},
+    {1, [](uint32_t ld) { return maxsim_mx4_scale_pitch(ld); }, false, false, 4, "of MXFP4 tokens",
+     [](uint32_t ld, uint32_t tiles, uint32_t) { return maxsim_mx4_lds_bytes(ld, tiles); }},
 };
 
 struct MaxSimPlan {
@@ -63,7 +69,8 @@ struct MaxSimPlan {
 // blocks a wave, so the waves are those that fit next to the tiles (4, 2 or 1).  f16 (the addendum): the query tiles as halves and
 // 32 flags per wave, no token block, so the waves are always 4 and every dimension up to 1024 serves a query of up to 64 tokens.
 // int8 (rule 7"): the query tiles as codes at a row pitch of ld + 16 bytes, their scales and the flags; 4 waves, and every
-// dimension up to 1024 serves a query of up to 128 tokens.  `out` may be NULL.
+// dimension up to 1024 serves a query of up to 128 tokens.  MXFP4 (rule 7'''): the query tiles as E4M3 bytes at the same pitch, ld / 32
+// scale bytes a query row and the flags; 4 waves, and again every dimension serves 128 query tokens.  `out` may be NULL.
 static int maxsim_plan(uint32_t dim, uint32_t tq, int tag, MaxSimPlan* out) {
     if (dim == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector dimension must be positive");
     if (tq == 0) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "multi-vector queries: a query needs at least one token");
@@ -105,6 +112,10 @@ extern "C" int lynse_hip_multivec_plan_i8(uint32_t dim, uint32_t tq, uint32_t* o
     return maxsim_plan_out(dim, tq, 2, out_tiles, out_waves, out_lds_bytes);
 }
 
+extern "C" int lynse_hip_multivec_plan_mxfp4(uint32_t dim, uint32_t tq, uint32_t* out_tiles, uint32_t* out_waves, uint64_t* out_lds_bytes) {
+    return maxsim_plan_out(dim, tq, 3, out_tiles, out_waves, out_lds_bytes);
+}
+
 static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out);
 
 extern "C" int lynse_hip_multivec_create(int device, uint32_t dim, lynse_hip_multivec** out) { return lynse_hip_multivec_create_dtype(device, dim, 0, out); }
@@ -116,6 +127,8 @@ extern "C" int lynse_hip_multivec_create_dtype(int device, uint32_t dim, int dty
 }
 
 extern "C" int lynse_hip_multivec_create_i8(int device, uint32_t dim, lynse_hip_multivec** out) { return maxsim_create(device, dim, 2, out); }
+
+extern "C" int lynse_hip_multivec_create_mxfp4(int device, uint32_t dim, lynse_hip_multivec** out) { return maxsim_create(device, dim, 3, out); }
 
 static int maxsim_create(int device, uint32_t dim, int dtype, lynse_hip_multivec** out) {
     if (!out) return set_error(LYNSE_ERR_INVALID_ARGUMENT, "out is NULL");
@@ -180,20 +193,19 @@ static void maxsim_ranges(const std::vector<uint64_t>& cptr, std::vector<uint32_
 // exists and the copies are done, so a failed call leaves the store answering as before.
 static int maxsim_grow(lynse_hip_multivec* h, uint64_t total) {
     const MaxSimDtype& dt = MAXSIM_DTYPES[h->dtype];
-    const size_t rb = (size_t)h->ld * dt.esz;
-    if (total <= h->tokens.cap / rb && (!dt.scaled || total <= h->scales.cap)) return LYNSE_OK;
+    const size_t rb = dt.row_bytes(h->ld), sb = dt.srow_bytes(h->ld);
+    if (total <= h->tokens.cap / rb && (!sb || total <= h->scales.cap / sb)) return LYNSE_OK;
     const uint64_t cap = std::max<uint64_t>(total, 2 * h->total);
-    DevBuf<uint8_t> grown;
-    DevBuf<float> grown_s;
+    DevBuf<uint8_t> grown, grown_s;
     LY_TRY(grown.alloc((size_t)cap * rb));
-    if (dt.scaled) LY_TRY(grown_s.alloc((size_t)cap));
+    if (sb) LY_TRY(grown_s.alloc((size_t)cap * sb));
     if (h->total) {
         LY_HIP(hipMemcpy(grown.p, h->tokens.p, (size_t)h->total * rb, hipMemcpyDeviceToDevice));
-        if (dt.scaled) LY_HIP(hipMemcpy(grown_s.p, h->scales.p, (size_t)h->total * 4, hipMemcpyDeviceToDevice));
+        if (sb) LY_HIP(hipMemcpy(grown_s.p, h->scales.p, (size_t)h->total * sb, hipMemcpyDeviceToDevice));
     }
     LY_HIP(hipStreamSynchronize(nullptr));   // (the copies are ordered on the NULL stream: h2d_done)
     h->tokens = std::move(grown);
-    if (dt.scaled) h->scales = std::move(grown_s);
+    if (sb) h->scales = std::move(grown_s);
     return LYNSE_OK;
 }
 
@@ -213,7 +225,7 @@ static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16
     LY_HIP(hipSetDevice(h->device));
     const MaxSimDtype& dt = MAXSIM_DTYPES[h->dtype];
     const uint32_t D = h->dim, ld = h->ld;
-    const size_t rb = (size_t)ld * dt.esz;
+    const size_t rb = dt.row_bytes(ld), sb = dt.srow_bytes(ld);
     const uint64_t total = h->total + add;
     std::vector<uint64_t> cptr = h->cptr;
     std::vector<uint32_t> crec = h->crec, ranges;
@@ -236,22 +248,26 @@ static int maxsim_append(lynse_hip_multivec* h, const void* tokens, bool raw_h16
             LY_TRY(h2d_done(dst, h->stage.data(), h->stage.size() * 4));
         } else {
             // the rows as given go up once; the device writes them at the store's pitch (k_maxsim_store_h16: conversion, flush, zero
-            // columns; k_maxsim_store_i8: rule 1", zero columns)
+            // columns; k_maxsim_store_i8: rule 1", zero columns; k_maxsim_store_mx4: rule 1''', zero columns)
             const size_t src_rb = (size_t)D * (raw_h16 ? 2 : 4);
             DevBuf<uint8_t> raw;
             LY_TRY(raw.alloc((size_t)add * src_rb));
             LY_TRY(h2d_done(raw.p, tokens, (size_t)add * src_rb));
             // rows of a launch: rows * ld <= 2^30, so k_maxsim_store_h16 (a thread a stored half) has at most 2^22 workgroups and
-            // k_maxsim_store_i8 (16 rows a workgroup, ld >= 32) at most 2^21
+            // k_maxsim_store_i8 (16 rows a workgroup, ld >= 32) at most 2^21, k_maxsim_store_mx4 (64 blocks of 32 elements) 2^19
             const uint64_t step = (1ull << 30) / ld;
             for (uint64_t r0 = 0; r0 < add; r0 += step) {
                 const uint64_t rows = std::min<uint64_t>(step, add - r0);
                 const uint8_t* src = raw.p + (size_t)r0 * src_rb;
                 uint8_t* out = dst + (size_t)r0 * rb;
                 const dim3 grid_h((uint32_t)((rows * ld + 255) / 256));
-                if (dt.scaled)
+                uint8_t* out_s = sb ? h->scales.p + (size_t)(h->total + r0) * sb : nullptr;
+                if (h->dtype == 3)
+                    hipLaunchKernelGGL(k_maxsim_store_mx4, dim3((uint32_t)((rows * (ld / 32u) + 63) / 64)), dim3(256), 0, nullptr, reinterpret_cast<const float*>(src),
+                                       reinterpret_cast<uint32_t*>(out), out_s, rows, D, ld);
+                else if (h->dtype == 2)
                     hipLaunchKernelGGL(k_maxsim_store_i8, dim3((uint32_t)((rows + 15) / 16)), dim3(256), 0, nullptr, reinterpret_cast<const float*>(src),
-                                       reinterpret_cast<uint32_t*>(out), h->scales.p + h->total + r0, rows, D, ld);
+                                       reinterpret_cast<uint32_t*>(out), reinterpret_cast<float*>(out_s), rows, D, ld);
                 else if (raw_h16)
                     hipLaunchKernelGGL(k_maxsim_store_h16<uint16_t>, grid_h, dim3(256), 0, nullptr, reinterpret_cast<const uint16_t*>(src), reinterpret_cast<uint16_t*>(out), rows, D, ld);
                 else
@@ -458,19 +474,20 @@ static int maxsim_search(lynse_hip_multivec* h, const float* q_tokens, const uin
         LY_TRY(maxsim_by_tiles(tiles, [&](auto nt) -> int {
             constexpr int NT = decltype(nt)::value;
             if (cand) {
-                const MaxSimCandArgs ac{h->tokens.p, h->scales.p, ld, h->d_cptr.p, h->cand.p, cand->ptr ? h->cand_ptr.p + q0 : nullptr, (uint32_t)cand->n_shared,
+                const MaxSimCandArgs ac{h->tokens.p, reinterpret_cast<const float*>(h->scales.p), ld, h->d_cptr.p, h->cand.p, cand->ptr ? h->cand_ptr.p + q0 : nullptr, (uint32_t)cand->n_shared,
                                         (uint32_t)pitch, h->q.p, h->qdesc.p, h->cut.S.p};
-                return dt.scaled ? launch_lds<k_maxsim_cand_i8<NT>>(grid, block, lds, st, ac) : launch_lds<k_maxsim_cand_h16<NT>>(grid, block, lds, st, ac);
+                return h->dtype == 2 ? launch_lds<k_maxsim_cand_i8<NT>>(grid, block, lds, st, ac) : launch_lds<k_maxsim_cand_h16<NT>>(grid, block, lds, st, ac);
             }
             switch (h->dtype) {
             case 0: return launch_lds<k_maxsim_scan<NT>>(grid, block, lds, st, scan_args(reinterpret_cast<const float*>(h->tokens.p)));
             case 1: return launch_lds<k_maxsim_h16<NT>>(grid, block, lds, st, scan_args(reinterpret_cast<const _Float16*>(h->tokens.p)));
-            default: return launch_lds<k_maxsim_i8<NT>>(grid, block, lds, st, MaxSimI8Args{scan_args(reinterpret_cast<const int8_t*>(h->tokens.p)), h->scales.p});
+            case 2: return launch_lds<k_maxsim_i8<NT>>(grid, block, lds, st, MaxSimI8Args{scan_args(reinterpret_cast<const int8_t*>(h->tokens.p)), reinterpret_cast<const float*>(h->scales.p)});
+            default: return launch_lds<k_maxsim_mx4<NT>>(grid, block, lds, st, MaxSimMx4Args{scan_args(h->tokens.p), h->scales.p});
             }
         }));
         if (timed) {
             LY_HIP(hipEventRecord(h->ev[1], st));
-            const uint64_t row_bytes = (uint64_t)ld * dt.esz + (dt.scaled ? 4u : 0u);
+            const uint64_t row_bytes = dt.row_bytes(ld) + dt.srow_bytes(ld);
             h->prof.scan_launches += 1;
             h->prof.last_plan = cand ? 1 : 0;
             if (cand) {   // the rows and bytes the candidate kernel read: the listed records' tokens, their list entries and extents
@@ -604,7 +621,7 @@ extern "C" int lynse_hip_multivec_rerank_f32(lynse_hip_multivec* h, const float*
                                                              std::to_string(h->n) + ")");
     LY_TRY(maxsim_plan(h->dim, tq_max, h->dtype, nullptr));
     if (!MAXSIM_DTYPES[h->dtype].cand) {
-        // an f32 store has no candidate kernel: the scan once per query with the query's candidates as its BitSet — the same
+        // an f32 or MXFP4 store has no candidate kernel: the scan once per query with the query's candidates as its BitSet — the same
         // results at the scan's cost
         std::vector<uint64_t> words((h->n + 63) / 64 + 1);
         for (uint64_t i = 0; i < nq; ++i) {
